@@ -31,6 +31,12 @@ dominant kernel is bracketed by events (-> `roofline`), and the stage events are
 region (untimed) a sample of the traced rays is compared with the oracle's brute force, the bitmask with the oracle's and the
 AABB list in the consumer's buffer with the oracle's list -> `verified`.
 
+`--dump-outputs DIR` (rank 0): what the LAST timed step handed its caller, taken right after the timed region, as DIR/<name>.npy --
+t.npy (float32; -1 = miss) and prim.npy (float64; 0xFFFFFFFF = miss) per ray, aabbs.npy (float32, min xyz and max xyz per
+record of the getAabbs list) and aabbs_count.npy (float64, the count getAabbs returned).  An output of more than DUMP_ROWS
+rows keeps a fixed seeded sample of its rows, ascending, and their indices beside it (rays_index.npy / aabbs_index.npy,
+float64): at most 52 MiB in all.  The inputs are seeded, so two builds run with the same arguments can be compared file for file.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -54,6 +60,7 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 VALU_ISSUE_PEAK = 1.2288e12  # wave64 VALU instructions/s: 256 CUs x 4 SIMD-32 x 2.4 GHz / 2 cycles per wave64 instruction
 PROFILE_TAGS = ("r3", "r2", "r1")  # profiles/<tag>_traffic.json / _issue.json, newest first
+DUMP_ROWS = 1 << 20  # --dump-outputs: rows kept per output (t + prim + aabbs + both indices <= 52 MiB)
 
 
 def parse():
@@ -84,7 +91,12 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal with one rank: initialise the process group and run the sharded build + exchange path at world size 1 "
                          "(the only way to execute the RCCL calls on a one-GPU box)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (first-hit t and primitive per ray, the getAabbs list and its count) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    return a
 
 
 def spawn_ranks(a):
@@ -136,6 +148,32 @@ def reference_sat_calls(verts, tris, vs, org, dim):
     s = np.maximum(((tmn - org) / np.float32(vs)).astype(np.int64), 0)
     e = np.minimum(((tmx - org) / np.float32(vs)).astype(np.int64) + 2, np.array(dim, np.int64))
     return int(np.prod(np.maximum(e - s, 0), axis=1).sum())
+
+
+def dump_outputs(out_dir, t, prim, aabbs, count):
+    """--dump-outputs: t (float32), prim (uint32), aabbs (float32, 6 per record) as one step's caller received them -> out_dir/*.npy in
+    float32 / float64.  Outputs longer than DUMP_ROWS keep a fixed seeded sample of their rows (the same one on every run of the same
+    arguments) and write its indices as rays_index.npy (t and prim) / aabbs_index.npy.  Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name in ("rays_index", "aabbs_index"):   # an index left by an earlier run into the same directory would describe other rows
+        if os.path.exists(os.path.join(out_dir, name + ".npy")):
+            os.remove(os.path.join(out_dir, name + ".npy"))
+    aabbs = aabbs.reshape(-1, 6)
+
+    def rows(n, seed):
+        return None if n <= DUMP_ROWS else np.sort(np.random.default_rng(seed).choice(n, DUMP_ROWS, replace=False))
+
+    ri, ai = rows(len(t), 11), rows(len(aabbs), 12)
+    out = {"t": t if ri is None else t[ri], "prim": (prim if ri is None else prim[ri]).astype(np.float64),
+           "aabbs": aabbs if ai is None else aabbs[ai], "aabbs_count": np.array([count], dtype=np.float64)}
+    if ri is not None:
+        out["rays_index"] = ri.astype(np.float64)
+    if ai is not None:
+        out["aabbs_index"] = ai.astype(np.float64)
+    for name, arr in out.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
+    return sorted(out)
 
 
 def load_profile_json(suffix):
@@ -384,6 +422,9 @@ def main():
     voxhip.profile_enable(False)
     kern = voxhip.profile_read()   # the dominant kernel only, measured inside the timed region
     voxhip.profile_select(None)
+    if a.dump_outputs and rank == 0:
+        # untimed, before the stage pass below runs the step again: the barrier above waited for every stream, the list's side stream too
+        dump_outputs(a.dump_outputs, d_t.cpu().numpy(), d_prim.cpu().numpy().view(np.uint32), d_aabbs[: int(nocc) * 6].cpu().numpy(), int(nocc))
     # stage breakdown: a pass of its own after the timed region, five events per step
     for k in range(stage_steps):
         step(True, k)

@@ -53,6 +53,32 @@ def test_bench_line_contract(gpu):
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["sample"]
 
 
+def test_bench_dump_outputs(gpu, tmp_path):
+    """--dump-outputs: the last timed step's rays and getAabbs list as float32 / float64 .npy files within 64 MB, the same on a second run
+    of the same arguments, and consistent with the JSON line of their run."""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--big-rays", "0", "--no-cpu-baseline", "--no-context", "--pipelined-steps", "0", "--rays", "300000"]
+    d = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    assert d["steps"] == 3 and d["verified"] is True and d["ms_per_step"] > 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    # 300 000 rays are all kept; the ~4M-record list of the 512^3 VoxelGridVec build is sampled
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["aabbs.npy", "aabbs_count.npy", "aabbs_index.npy", "prim.npy", "t.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64_000_000
+    out = {}
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.dtype == y.dtype and x.shape == y.shape, n
+        assert x.tobytes() == y.tobytes(), n
+        out[n[:-4]] = x
+    assert out["t"].shape == (300000,) and out["t"].dtype == np.float32 and int((out["t"] > 0).sum()) == d["ray_hits_rank0"]
+    assert np.array_equal(out["prim"] != 0xFFFFFFFF, out["t"] > 0)
+    assert out["aabbs_count"][0] == d["aabbs_returned"] and out["aabbs"].shape == (len(out["aabbs_index"]), 6)
+    idx = out["aabbs_index"]
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < d["aabbs_returned"]
+    assert np.all(out["aabbs"][:, :3] < out["aabbs"][:, 3:])
+
+
 def test_bench_rccl_path_world1(gpu):
     d = run_bench("--force-dist", "--dist-backend", "nccl", "--steps", "3", "--warmup", "1", "--big-rays", "0", "--no-cpu-baseline", "--c4-grid", "0",
                   "--rays", "200000")
