@@ -288,6 +288,22 @@ typedef struct vx_trace_args {
 vx_status vx_trace_ex_device(const vx_grid* g, const vx_trace_args* args);
 vx_status vx_trace_ex(const vx_grid* g, const vx_trace_args* args);
 
+/* ---- rays on the octree: the reference's second BLAS input (Octree{path, vs} -> getAabbs, hello_vulkan.cpp:690-697) under the
+ * same raytrace.rint.  The contract of the grid trace above, applied to the list vx_octree_aabbs() returns (ascending Morton code,
+ * duplicates included, octTree.hpp:502-510):
+ *   t       the minimum of hitAabb over all list boxes, accepted iff t > 0 and tmin <= t <= tmax (or tmax_per_ray[r]); miss: -1;
+ *   prim    the smallest list index among the boxes reaching that minimum (duplicate items have identical boxes, so prim is always the
+ *           first index of its run of equal codes); miss: 0xFFFFFFFF;
+ *   normal, shadowed (any_hit), camera rays and the compacted hit list exactly as vx_trace_ex / vx_trace_ex_device give them.
+ * An octree without items (empty mesh) gives all misses.  Grids with an axis above 65535 cells: the traced boxes are the ones
+ * vx_octree_aabbs emits, which carry the reference's low-16-bit Morton interleave (octTree.hpp:211-218): cell coordinates alias
+ * modulo 65536 along such an axis.  Work runs on the octree's stream.  Argument rules as for vx_trace_ex*: any_hit together with
+ * prim, normal or hits is VX_ERR_INVALID_ARG, hits on the host variant VX_ERR_UNSUPPORTED. */
+vx_status vx_octree_trace_ex_device(const vx_octree* o, const vx_trace_args* args);  /* device pointers, incl. compacted hits */
+vx_status vx_octree_trace_ex(const vx_octree* o, const vx_trace_args* args);         /* host pointers (staged), no `hits` */
+vx_status vx_octree_trace(const vx_octree* o, const float* host_rays, uint64_t num_rays, float tmin, float tmax,
+                          float* host_t /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
+
 /* ---- test aid: the device radix sort the Octree uses for its Morton items (octTree.hpp:363 -> vx_sort.hip), applied to a host array.
  * Keys must have no bit set at or above `bits` (1..64); sorted in place. */
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits);

@@ -16,6 +16,8 @@
 //                                       matrices used (column-major float32), for comparisons.
 //   --gpus N [--logical]                spread the build over N GPUs of this node (word shards + peer copies, vx_voxelize_multi);
 //                                       --logical maps all N ranks onto device 0 (rehearsal on a box with fewer GPUs)
+//   --grid octree --render FILE.ppm     the same picture from the octree's list (hello_vulkan.cpp:690-697), traced on the tree itself
+//                                       (vx_octree_trace_ex) with the default material; --materials is refused there
 //   --materials                         switch on the reference's commented-out material plumbing (usemtl / mtllib -> per-voxel
 //                                       material ids; VoxelBuilder.hpp:375-395): --render shades with them, --dump-materials FILE writes
 //                                       getMatIdx() as int16
@@ -64,7 +66,9 @@ void camera(float vi[16], float pi[16], float aspect)
 
 struct RenderOpts { std::vector<MaterialObj> materials; std::vector<int16_t> matIdx; std::string cameraDump; };
 
-int render(vx_grid* grid, const std::string& file, uint32_t W, uint32_t H, const RenderOpts& ro)
+// trace(const vx_trace_args*) -> vx_status runs one ray batch on whatever holds the boxes: vx_trace_ex on a grid, vx_octree_trace_ex on an octree
+template <class Trace>
+int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const RenderOpts& ro)
 {
     float vi[16], pi[16];
     camera(vi, pi, (float)W / (float)H);
@@ -80,7 +84,7 @@ int render(vx_grid* grid, const std::string& file, uint32_t W, uint32_t H, const
     vx_trace_args a{};
     a.view_inverse = vi; a.proj_inverse = pi; a.width = W; a.height = H; a.tmin = 0.001f; a.tmax = 10000.0f;  // rgen:50-51
     a.t = t.data(); a.prim = prim.data(); a.normal = nrm.data();
-    vxdetail::check(vx_trace_ex(grid, &a));
+    vxdetail::check(trace(&a));
     // shadow rays from the hit points toward the point light (rchit:76-122)
     const V3 light{10.f, 55.f, 8.f};  // hello_vulkan.h:86
     const float intensity = 1000.f;   // :88
@@ -102,7 +106,7 @@ int render(vx_grid* grid, const std::string& file, uint32_t W, uint32_t H, const
     vx_trace_args sa{};
     sa.rays = rays.data(); sa.num_rays = n; sa.tmin = 0.001f; sa.tmax = 10000.0f; sa.tmax_per_ray = tmaxs.data(); sa.any_hit = 1;
     sa.shadowed = shadowed.data();
-    vxdetail::check(vx_trace_ex(grid, &sa));
+    vxdetail::check(trace(&sa));
     const MaterialObj defmat{};  // the single default material createAABB uploads (hello_vulkan.cpp:701-702)
     std::vector<unsigned char> img(3 * n);
     size_t hits = 0;
@@ -180,7 +184,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
             f.write(reinterpret_cast<const char*>(ro.matIdx.data()), (std::streamsize)(ro.matIdx.size() * sizeof(int16_t)));
         }
     }
-    if (!renderFile.empty()) return render(vox.handle(), renderFile, rw, rh, ro);
+    if (!renderFile.empty()) return render([g = vox.handle()](const vx_trace_args* a) { return vx_trace_ex(g, a); }, renderFile, rw, rh, ro);
     return 0;
 }
 }  // namespace
@@ -188,7 +192,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE]] [--materials [--dump-materials FILE]] [--gpus N [--logical]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
                      argv[0]);
         return 2;
     }
@@ -229,6 +233,7 @@ int main(int argc, char** argv)
             return 0;
         }
         if (grid == "octree") {
+            if (materials) { std::fprintf(stderr, "--materials is not available with --grid octree: the octree has no material ids\n"); return 2; }
             // the commented-out alternative in createAABB (hello_vulkan.cpp:690-697)
             const auto t0 = Clock::now();
             Octree tree{std::filesystem::path(path), vs};
@@ -238,6 +243,11 @@ int main(int argc, char** argv)
             const std::vector<Aabb> aabbs = tree.getAabbs();
             std::printf("[voxhip] octree: %zu AABBs\n", aabbs.size());
             dump(dumpFile, aabbs);
+            if (!renderFile.empty()) {  // the same picture of the octree's list, traced on the tree itself
+                RenderOpts ro;
+                ro.cameraDump = cameraDump;
+                return render([o = tree.handle()](const vx_trace_args* a) { return vx_octree_trace_ex(o, a); }, renderFile, rw, rh, ro);
+            }
             return 0;
         }
         if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices)

@@ -458,6 +458,7 @@ struct vx_octree {
     vx_octree_node* dnodes = nullptr;  // pre-order node array (device): in `nodebuf` (pooled) or hipMalloc'ed (level-by-level build)
     DevBuf nodebuf;
     uint64_t nnodes = 0;
+    DevBuf camera;  // vx_octree_trace*: the camera block of primary-ray batches
     void free_nodes(bool in_flight)
     {
         if (nodebuf.p) nodebuf.release(in_flight);
@@ -1856,47 +1857,56 @@ vx_status vx_trace_ex_device(const vx_grid* gc, const vx_trace_args* args)
     return trace_common(g, io);
 }
 
-// host-buffer variant: stages every non-null array through pooled device memory
-vx_status vx_trace_ex(const vx_grid* gc, const vx_trace_args* args)
+// host-buffer variant: stages every non-null array through pooled device memory on (device, stream), then runs `run(io)` on the staged io
+extern "C++" {
+template <class Run>
+static vx_status trace_ex_staged(int device, hipStream_t stream, const vx_trace_args* args, Run run)
 {
-    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
     vx::Camera cam{};
     vx::TraceIO io;
     VX_TRY(args_to_io(args, &cam, &io));
-    if (args->hits) return fail(VX_ERR_UNSUPPORTED, "the compacted hit list is a device-side output: use vx_trace_ex_device");
+    if (args->hits) return fail(VX_ERR_UNSUPPORTED, "the compacted hit list is a device-side output: use the _device variant");
     const uint64_t n = io.nrays;
     if (!n) return VX_OK;
     DevBuf dr, dtm, dt, dp, dn, ds;
-    for (DevBuf* b : {&dr, &dtm, &dt, &dp, &dn, &ds}) { b->dev = g->device; b->stream = g->stream; }
+    for (DevBuf* b : {&dr, &dtm, &dt, &dp, &dn, &ds}) { b->dev = device; b->stream = stream; }
     auto rel = [&]() { for (DevBuf* b : {&dr, &dtm, &dt, &dp, &dn, &ds}) b->release(); };
     hipError_t e = hipSuccess;
     vx_status st = VX_OK;
-    if (io.rays) { e = dr.ensure((size_t)n * 24); if (e == hipSuccess) e = hipMemcpyAsync(dr.p, args->rays, (size_t)n * 24, hipMemcpyHostToDevice, g->stream); io.rays = dr.as<float>(); }
-    if (e == hipSuccess && io.tmax_per_ray) { e = dtm.ensure((size_t)n * 4); if (e == hipSuccess) e = hipMemcpyAsync(dtm.p, args->tmax_per_ray, (size_t)n * 4, hipMemcpyHostToDevice, g->stream); io.tmax_per_ray = dtm.as<float>(); }
+    if (io.rays) { e = dr.ensure((size_t)n * 24); if (e == hipSuccess) e = hipMemcpyAsync(dr.p, args->rays, (size_t)n * 24, hipMemcpyHostToDevice, stream); io.rays = dr.as<float>(); }
+    if (e == hipSuccess && io.tmax_per_ray) { e = dtm.ensure((size_t)n * 4); if (e == hipSuccess) e = hipMemcpyAsync(dtm.p, args->tmax_per_ray, (size_t)n * 4, hipMemcpyHostToDevice, stream); io.tmax_per_ray = dtm.as<float>(); }
     if (e == hipSuccess && args->t) { e = dt.ensure((size_t)n * 4); io.t_out = dt.as<float>(); }
     if (e == hipSuccess && args->prim) { e = dp.ensure((size_t)n * 4); io.prim_out = dp.as<uint32_t>(); }
     if (e == hipSuccess && args->normal) { e = dn.ensure((size_t)n * 12); io.normal_out = dn.as<float>(); }
     if (e == hipSuccess && args->shadowed) { e = ds.ensure((size_t)n); io.shadowed_out = ds.as<uint8_t>(); }
-    if (e == hipSuccess) st = trace_common(g, io);
+    if (e == hipSuccess) st = run(io);
     if (e == hipSuccess && st == VX_OK) {
-        if (args->t) e = hipMemcpyAsync(args->t, dt.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess && args->prim) e = hipMemcpyAsync(args->prim, dp.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess && args->normal) e = hipMemcpyAsync(args->normal, dn.p, (size_t)n * 12, hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess && args->shadowed) e = hipMemcpyAsync(args->shadowed, ds.p, (size_t)n, hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+        if (args->t) e = hipMemcpyAsync(args->t, dt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && args->prim) e = hipMemcpyAsync(args->prim, dp.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && args->normal) e = hipMemcpyAsync(args->normal, dn.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && args->shadowed) e = hipMemcpyAsync(args->shadowed, ds.p, (size_t)n, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
     }
     rel();
     if (st != VX_OK) return st;
     VX_HIP(e);
     return VX_OK;
 }
+}  // extern "C++"
 
-vx_status vx_trace(const vx_grid* gc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim,
-                   uint64_t* num_hits)
+vx_status vx_trace_ex(const vx_grid* gc, const vx_trace_args* args)
 {
-    if (!gc || (nrays && !host_rays)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return trace_ex_staged(g->device, g->stream, args, [&](const vx::TraceIO& io) { return trace_common(g, io); });
+}
+
+// vx_trace / vx_octree_trace: t and prim of a host ray buffer through the handle's host-buffer extended query, hits counted on the host
+extern "C++" {
+template <class Ex>
+static vx_status trace_simple(const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim, uint64_t* num_hits, Ex ex)
+{
     if (num_hits) *num_hits = 0;
     if (!nrays) return VX_OK;
     std::vector<float> tbuf;
@@ -1904,13 +1914,21 @@ vx_status vx_trace(const vx_grid* gc, const float* host_rays, uint64_t nrays, fl
     if (!tdst) { tbuf.resize(nrays); tdst = tbuf.data(); }
     vx_trace_args a{};
     a.rays = host_rays; a.num_rays = nrays; a.tmin = tmin; a.tmax = tmax; a.t = tdst; a.prim = host_prim;
-    VX_TRY(vx_trace_ex(gc, &a));
+    VX_TRY(ex(&a));
     if (num_hits) {
         uint64_t n = 0;
         for (uint64_t i = 0; i < nrays; ++i) n += tdst[i] > 0.0f;
         *num_hits = n;
     }
     return VX_OK;
+}
+}  // extern "C++"
+
+vx_status vx_trace(const vx_grid* gc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim,
+                   uint64_t* num_hits)
+{
+    if (!gc || (nrays && !host_rays)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return trace_simple(host_rays, nrays, tmin, tmax, host_t, host_prim, num_hits, [&](const vx_trace_args* a) { return vx_trace_ex(gc, a); });
 }
 
 // ---- octree ---------------------------------------------------------------------------------------------------
@@ -1928,8 +1946,8 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
     o->stream = s;
     o->vs = vs;
     o->max_items = max_items;
-    o->items.dev = o->nodebuf.dev = o->device;
-    o->items.stream = o->nodebuf.stream = s;
+    o->items.dev = o->nodebuf.dev = o->camera.dev = o->device;
+    o->items.stream = o->nodebuf.stream = o->camera.stream = s;
     DevBuf small, recs, ext, units, ubase, btri, scantmp, umask, bhits, hbase, unsorted, sorttmp, ncount, nbase;
     for (DevBuf* b : {&small, &recs, &ext, &units, &ubase, &btri, &scantmp, &umask, &bhits, &hbase, &unsorted, &sorttmp, &ncount, &nbase}) { b->dev = o->device; b->stream = s; }
     Mail* mail = nullptr;
@@ -2084,6 +2102,48 @@ vx_status vx_octree_aabbs(const vx_octree* o, vx_aabb* host_out, uint64_t cap, u
     return VX_OK;
 }
 
+// ---- rays on the octree: the grid trace's contract over the vx_octree_aabbs list (vx_octrace.hip) ----------------------------------
+static vx_status octree_trace_common(vx_octree* o, vx::TraceIO io)
+{
+    if (!io.nrays) return VX_OK;
+    if (io.cam) {
+        VX_HIP(o->camera.ensure(sizeof(vx::Camera)));
+        VX_HIP(hipMemcpyAsync(o->camera.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, o->stream));
+        VX_HIP(hipStreamSynchronize(o->stream));  // the host copy lives on the caller's stack
+        io.cam_dev = o->camera.as<vx::Camera>();
+    }
+    const uint64_t nitems = o->nnodes == 0 ? 0 : o->nitems;  // the list vx_octree_aabbs returns
+    vx::launch_octree_trace(o->dnodes, o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, o->stream);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+vx_status vx_octree_trace_ex_device(const vx_octree* oc, const vx_trace_args* args)
+{
+    if (!oc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    vx_octree* o = const_cast<vx_octree*>(oc);
+    DeviceGuard dg(o->device);
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(args_to_io(args, &cam, &io));
+    return octree_trace_common(o, io);
+}
+
+vx_status vx_octree_trace_ex(const vx_octree* oc, const vx_trace_args* args)
+{
+    if (!oc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    vx_octree* o = const_cast<vx_octree*>(oc);
+    DeviceGuard dg(o->device);
+    return trace_ex_staged(o->device, o->stream, args, [&](const vx::TraceIO& io) { return octree_trace_common(o, io); });
+}
+
+vx_status vx_octree_trace(const vx_octree* oc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim,
+                          uint64_t* num_hits)
+{
+    if (!oc || (nrays && !host_rays)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return trace_simple(host_rays, nrays, tmin, tmax, host_t, host_prim, num_hits, [&](const vx_trace_args* a) { return vx_octree_trace_ex(oc, a); });
+}
+
 void vx_octree_free(vx_octree* o)
 {
     if (!o) return;
@@ -2092,6 +2152,7 @@ void vx_octree_free(vx_octree* o)
         (void)hipStreamSynchronize(o->stream);
         o->items.release(/*in_flight=*/false);
         o->free_nodes(/*in_flight=*/false);
+        o->camera.release(/*in_flight=*/false);
     }
     delete o;
 }

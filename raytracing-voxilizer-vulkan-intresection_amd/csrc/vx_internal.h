@@ -166,6 +166,11 @@ void launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* wo
                   void* idx_tmp /*trace_idx_bytes when ranks / normals / the hit list are wanted*/, hipStream_t s,
                   const uint32_t* prefix16 = nullptr /*optional: launch_scan_u32's group16 of word_prefix*/, WalkQueue* queue = nullptr);
 
+// First hit per ray against the octree's AABB list by descending its node array (vx_octrace.hip).  io as for launch_trace (cam_dev, not cam;
+// prim = index in vx_octree_aabbs order); nodes may be null / nitems 0: every ray misses.
+void launch_octree_trace(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,
+                         hipStream_t s);
+
 // single-voxel helpers
 void launch_set_bit(uint32_t* words, uint64_t idx, hipStream_t s);
 

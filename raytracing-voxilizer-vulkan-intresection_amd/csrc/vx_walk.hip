@@ -41,6 +41,7 @@
 //
 // No MFMA: this is traversal, not a contraction.  Algorithmic HBM traffic is the ray stream (24 B in, 4-8 B out per ray).
 #include "vx_internal.h"
+#include "vx_ray.h"
 
 #include <cstddef>
 #include <cstdlib>
@@ -304,33 +305,6 @@ __device__ __forceinline__ void unperm(int p, int cu, int cv, int cw, int& x, in
     x = sel3i(p, cw, cv, cu);
     y = sel3i(p, cu, cw, cv);
     z = sel3i(p, cv, cu, cw);
-}
-
-// Ray r of the batch: from the ray buffer, or generated from the reference camera model (raytrace.rgen:41-47; mat*vec in glm's
-// association (m0*v0 + m1*v1) + (m2*v2 + m3*v3)).
-__device__ __forceinline__ void load_ray_w(bool primary, uint64_t r, const float* __restrict__ rays, const Camera* __restrict__ camp, float& ox, float& oy,
-                                           float& oz, float& dx, float& dy, float& dz)
-{
-    if (primary) {
-        const Camera& cam = *camp;
-        const uint32_t px = (uint32_t)(r % cam.width), py = (uint32_t)(r / cam.width);
-        const float u = ((float)px + 0.5f) / (float)cam.width, v = ((float)py + 0.5f) / (float)cam.height;
-        const float ndx = u * 2.0f - 1.0f, ndy = v * 2.0f - 1.0f;
-        float tg[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            tg[k] = (cam.projInv[0 + k] * ndx + cam.projInv[4 + k] * ndy) + (cam.projInv[8 + k] * 1.0f + cam.projInv[12 + k] * 1.0f);
-        const float il = 1.0f / sqrtf((tg[0] * tg[0] + tg[1] * tg[1]) + tg[2] * tg[2]);
-        const float n0 = tg[0] * il, n1 = tg[1] * il, n2 = tg[2] * il;
-        ox = cam.viewInv[12]; oy = cam.viewInv[13]; oz = cam.viewInv[14];
-        dx = (cam.viewInv[0] * n0 + cam.viewInv[4] * n1) + cam.viewInv[8] * n2;
-        dy = (cam.viewInv[1] * n0 + cam.viewInv[5] * n1) + cam.viewInv[9] * n2;
-        dz = (cam.viewInv[2] * n0 + cam.viewInv[6] * n1) + cam.viewInv[10] * n2;
-    } else {
-        const float2* rp = reinterpret_cast<const float2*>(rays + 6 * r);
-        const float2 a = rp[0], b = rp[1], c = rp[2];
-        ox = a.x; oy = a.y; oz = b.x; dx = b.y; dy = c.x; dz = c.y;
-    }
 }
 
 // Ray set-up: major axis, tolerance, grid clip, first slab.  Returns false when the ray cannot touch the grid.
@@ -904,7 +878,7 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
                     const uint64_t ro = C->ray_base + r;
                     const float* rays = C->rays;
                     float ox, oy, oz, dx, dy, dz;
-                    load_ray_w(rays == nullptr, ro, rays, C->cam, ox, oy, oz, dx, dy, dz);
+                    load_ray(rays == nullptr, ro, rays, C->cam, ox, oy, oz, dx, dy, dz);
                     const float* tpr = C->tmax_per_ray;
                     const float tmax_r = tpr ? tpr[ro] : C->tmax;
                     busy = walk_setup(R, g, P.inv_vs, tmax_r, ox, oy, oz, dx, dy, dz);

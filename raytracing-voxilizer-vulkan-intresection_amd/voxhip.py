@@ -26,6 +26,38 @@ MATERIAL = np.dtype([("ambient", np.float32, 3), ("diffuse", np.float32, 3), ("s
                      ("illum", np.int32), ("texture_id", np.int32)])
 
 
+def _trace_ex(fn, h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want):
+    """vx_trace_ex / vx_octree_trace_ex on host arrays -> dict of the requested outputs (t, prim, normal, shadowed)."""
+    a = TraceArgs()
+    keep = []
+    if rays is not None:
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        keep.append(r)
+        a.rays, a.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
+    else:
+        vi, pi, w, h_ = camera
+        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
+        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
+        keep += [cvi, cpi]
+        a.view_inverse, a.proj_inverse, a.width, a.height, n = cvi, cpi, w, h_, w * h_
+    a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
+    if tmax_per_ray is not None:
+        tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
+        keep.append(tm)
+        a.tmax_per_ray = tm.ctypes.data
+    out = {}
+    if "t" in want:
+        out["t"] = np.zeros(n, np.float32); a.t = out["t"].ctypes.data
+    if "prim" in want:
+        out["prim"] = np.zeros(n, np.uint32); a.prim = out["prim"].ctypes.data
+    if "normal" in want:
+        out["normal"] = np.zeros((n, 3), np.float32); a.normal = out["normal"].ctypes.data
+    if "shadowed" in want:
+        out["shadowed"] = np.zeros(n, np.uint8); a.shadowed = out["shadowed"].ctypes.data
+    _check(fn(h, C.byref(a)))
+    return out
+
+
 class GridDesc(C.Structure):
     _fields_ = [("dim", C.c_uint64 * 3), ("voxel_size", C.c_float), ("origin", C.c_float * 3), ("bbox_min", C.c_float * 3),
                 ("bbox_max", C.c_float * 3), ("bbox_center", C.c_float * 3), ("num_words", C.c_uint64), ("set_calls", C.c_uint64),
@@ -65,6 +97,7 @@ SYMBOLS = [
     "vx_octree_build", "vx_octree_num_items", "vx_octree_num_nodes", "vx_octree_bytes", "vx_octree_items", "vx_octree_nodes",
     "vx_octree_root_bounds", "vx_octree_aabbs", "vx_octree_aabbs_device", "vx_octree_free",
     "vx_trace", "vx_trace_device", "vx_trace_primary_device", "vx_trace_ex", "vx_trace_ex_device",
+    "vx_octree_trace", "vx_octree_trace_ex", "vx_octree_trace_ex_device",
     "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read",
     "vx_shard_words", "vx_shard_range",
 ]
@@ -187,6 +220,9 @@ def lib():
     L.vx_profile_read.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), u64p]
     L.vx_trace_ex.argtypes = [vp, C.POINTER(TraceArgs)]
     L.vx_trace_ex_device.argtypes = [vp, C.POINTER(TraceArgs)]
+    L.vx_octree_trace.argtypes = [vp, vp, C.c_uint64, C.c_float, C.c_float, vp, vp, u64p]
+    L.vx_octree_trace_ex.argtypes = [vp, C.POINTER(TraceArgs)]
+    L.vx_octree_trace_ex_device.argtypes = [vp, C.POINTER(TraceArgs)]
     L.vx_shard_words.argtypes = [C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p]
     L.vx_shard_words.restype = None
     L.vx_shard_range.argtypes = [C.c_uint64, C.c_int, C.c_int, u64p, u64p]
@@ -471,34 +507,7 @@ class Grid:
 
     def trace_ex(self, rays=None, camera=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, any_hit=False, want=("t", "prim")):
         """Host-buffer extended query -> dict of the requested outputs (t, prim, normal, shadowed)."""
-        a = TraceArgs()
-        keep = []
-        if rays is not None:
-            r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
-            keep.append(r)
-            a.rays, a.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
-        else:
-            vi, pi, w, h = camera
-            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-            keep += [cvi, cpi]
-            a.view_inverse, a.proj_inverse, a.width, a.height, n = cvi, cpi, w, h, w * h
-        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
-        if tmax_per_ray is not None:
-            tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
-            keep.append(tm)
-            a.tmax_per_ray = tm.ctypes.data
-        out = {}
-        if "t" in want:
-            out["t"] = np.zeros(n, np.float32); a.t = out["t"].ctypes.data
-        if "prim" in want:
-            out["prim"] = np.zeros(n, np.uint32); a.prim = out["prim"].ctypes.data
-        if "normal" in want:
-            out["normal"] = np.zeros((n, 3), np.float32); a.normal = out["normal"].ctypes.data
-        if "shadowed" in want:
-            out["shadowed"] = np.zeros(n, np.uint8); a.shadowed = out["shadowed"].ctypes.data
-        _check(lib().vx_trace_ex(self.h, C.byref(a)))
-        return out
+        return _trace_ex(lib().vx_trace_ex, self.h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want)
 
     def trace_device(self, rays_ptr, nrays, t_ptr, prim_ptr=None, hits_ptr=None, nhits_ptr=None, tmin=0.001, tmax=10000.0):
         _check(lib().vx_trace_device(self.h, rays_ptr, nrays, np.float32(tmin), np.float32(tmax), t_ptr, prim_ptr, hits_ptr, nhits_ptr))
@@ -605,6 +614,38 @@ class Octree:
         if n.value:
             _check(lib().vx_octree_aabbs(self.h, out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    def trace(self, rays, tmin=0.001, tmax=10000.0, want_prim=True):
+        """vx_octree_trace: first hit per ray over the aabbs() list -> (t, prim, num_hits), or (t, num_hits) without prim."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        t = np.zeros(r.shape[0], dtype=np.float32)
+        p = np.zeros(r.shape[0], dtype=np.uint32) if want_prim else None
+        nh = C.c_uint64()
+        _check(lib().vx_octree_trace(self.h, r.ctypes.data, r.shape[0], np.float32(tmin), np.float32(tmax), t.ctypes.data,
+                                     p.ctypes.data if want_prim else None, C.byref(nh)))
+        return (t, p, nh.value) if want_prim else (t, nh.value)
+
+    def trace_ex(self, rays=None, camera=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, any_hit=False, want=("t", "prim")):
+        """vx_octree_trace_ex: host-buffer extended query -> dict of the requested outputs (t, prim, normal, shadowed)."""
+        return _trace_ex(lib().vx_octree_trace_ex, self.h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want)
+
+    def trace_device(self, rays_ptr, nrays, t_ptr=None, prim_ptr=None, hits_ptr=None, nhits_ptr=None, tmin=0.001, tmax=10000.0,
+                     normal_ptr=None, shadowed_ptr=None, tmax_per_ray_ptr=None, any_hit=False, camera=None):
+        """vx_octree_trace_ex_device on device pointers (e.g. torch tensors' data_ptr()); camera = (view_inv, proj_inv, W, H) instead of rays."""
+        a = TraceArgs()
+        keep = []
+        if camera is not None:
+            vi, pi, w, h = camera
+            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
+            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
+            keep += [cvi, cpi]
+            a.view_inverse, a.proj_inverse, a.width, a.height = cvi, cpi, w, h
+        else:
+            a.rays, a.num_rays = rays_ptr, nrays
+        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
+        a.tmax_per_ray, a.t, a.prim, a.normal, a.shadowed = tmax_per_ray_ptr, t_ptr, prim_ptr, normal_ptr, shadowed_ptr
+        a.hits, a.num_hits = hits_ptr, nhits_ptr
+        _check(lib().vx_octree_trace_ex_device(self.h, C.byref(a)))
 
     def free(self):
         if self.h:
