@@ -304,6 +304,57 @@ vx_status vx_octree_trace_ex(const vx_octree* o, const vx_trace_args* args);    
 vx_status vx_octree_trace(const vx_octree* o, const float* host_rays, uint64_t num_rays, float tmin, float tmax,
                           float* host_t /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
 
+/* ---- rays on the triangle mesh: the reference's triangle BLAS (hello_vulkan.cpp:596-635, objectToVkGeometryKHR over the model loadModel
+ * reads at :197) under raytrace.rchit, as a BVH built on the device.  Rays, ray interval, camera rays and the compacted hit list are those
+ * of vx_trace_ex.  Triangle k is the k-th index triple of the mesh (its gl_PrimitiveID in a single-geometry BLAS), vertices v0 v1 v2 as
+ * stored.  Per (ray, triangle) Moeller-Trumbore in float32, exactly in this order, no contraction:
+ *     e1 = v1 - v0;  e2 = v2 - v0;  cross(a,b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x);  dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *     p = cross(d, e2);  det = dot(e1, p);  inv = 1.0f / det;  s = o - v0;  u = dot(s, p) * inv;  q = cross(s, e1);  v = dot(d, q) * inv;
+ *     t = dot(e2, q) * inv;   accepted iff u >= 0 && u <= 1 && v >= 0 && u + v <= 1 && t > 0 && t >= tmin && t <= tmax
+ * (a comparison with NaN fails; det == 0 needs no special case; edges and vertices are closed; triangles are two-sided, as the reference's
+ * TRIANGLE_FACING_CULL_DISABLE makes them).
+ *   t        the minimum accepted t over all triangles, -1 on a miss;
+ *   prim     the smallest triangle index among those reaching it (a ray through a shared edge reports the lower index), 0xFFFFFFFF on a miss;
+ *   bary     (u, v) of prim: raytrace.rchit's hitAttributeEXT vec2 attribs (:31,66); (0, 0) on a miss;
+ *   normal   the unit geometric normal cross(e1, e2) / sqrt(dot(., .)) of prim, not flipped (rounding not pinned); zeros on a miss;
+ *   shadowed (any_hit) 1 iff some triangle is accepted, t then some accepted t; tmax_per_ray honoured.
+ * t, prim and bary are bit-equal to the brute force over all triangles: the BVH only accelerates.
+ * The BVH is a binary LBVH: vx_bvh_nodes returns its node array, vx_bvh_node records with the root at index 0:
+ *   interior  a, b = the indices of its two children;
+ *   leaf      b = 0x80000000 | count, a = the position of its first triangle in LEAF ORDER (the leaves' triangles, leaf after leaf);
+ *   min, max  the exact float min / max of the vertices below the node.
+ * vx_bvh_leaf_triangles returns the triangle index of every leaf-order position.  Once built the BVH holds its own copy of the vertices
+ * (freeing the mesh is legal).  Work runs on the BVH's stream.  Argument rules as for vx_trace_ex*: any_hit together with prim, normal,
+ * hits or bary is VX_ERR_INVALID_ARG, hits on the host variant VX_ERR_UNSUPPORTED.  A mesh without triangles gives all misses. */
+typedef struct vx_bvh vx_bvh;
+typedef struct vx_bvh_node { float min[3]; uint32_t a; float max[3]; uint32_t b; } vx_bvh_node;
+#define VX_BVH_LEAF 0x80000000u
+#define VX_BVH_DEFAULT_LEAF 4u
+/* max_leaf_triangles: 0 = VX_BVH_DEFAULT_LEAF.  A borrowed device mesh whose indices leave [0, num_vertices) fails with VX_ERR_INVALID_ARG. */
+vx_status vx_bvh_build(const vx_mesh* mesh, uint32_t max_leaf_triangles, void* stream, vx_bvh** out);
+/* steady state: rebuild from the (refreshed) mesh into the same handle -- no allocation when the triangle count repeats */
+vx_status vx_bvh_build_into(const vx_mesh* mesh, vx_bvh* bvh);
+uint64_t vx_bvh_num_triangles(const vx_bvh* b);
+uint64_t vx_bvh_num_nodes(const vx_bvh* b);
+uint64_t vx_bvh_bytes(const vx_bvh* b);     /* device bytes of the node array + the triangle copies (32 B per node, 48 B per triangle) */
+uint32_t vx_bvh_height(const vx_bvh* b);    /* an upper bound of the tree's height (<= 62 by construction) */
+/* triangles whose angle at v0 has a sine below 2^-10 (slivers, collinear): their Moeller-Trumbore t is rounding noise that no box can
+ * bound, so every ray tests them one by one before the descent -- a mesh made mostly of them traces at brute-force speed */
+uint64_t vx_bvh_num_ill_conditioned(const vx_bvh* b);
+vx_status vx_bvh_root_bounds(const vx_bvh* b, float mn[3], float mx[3]);
+vx_status vx_bvh_nodes(const vx_bvh* b, void* host_out, uint64_t capacity_bytes, uint64_t* bytes);  /* vx_bvh_node array; capacity 0 = size query */
+vx_status vx_bvh_leaf_triangles(const vx_bvh* b, uint32_t* host_out, uint64_t capacity);            /* num_triangles entries */
+const void* vx_bvh_nodes_device(const vx_bvh* b);  /* the node array in device memory (stable across vx_bvh_build_into of the same size) */
+typedef struct vx_bvh_trace_args {
+    vx_trace_args base;  /* normal = the geometric normal above */
+    float* bary;         /* 2 f32 per ray (u, v), optional */
+} vx_bvh_trace_args;
+vx_status vx_bvh_trace_ex_device(const vx_bvh* b, const vx_bvh_trace_args* args);  /* device pointers, incl. compacted hits */
+vx_status vx_bvh_trace_ex(const vx_bvh* b, const vx_bvh_trace_args* args);         /* host pointers (staged), no `hits` */
+vx_status vx_bvh_trace(const vx_bvh* b, const float* host_rays, uint64_t num_rays, float tmin, float tmax,
+                       float* host_t /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
+void vx_bvh_free(vx_bvh* b);
+
 /* ---- test aid: the device radix sort the Octree uses for its Morton items (octTree.hpp:363 -> vx_sort.hip), applied to a host array.
  * Keys must have no bit set at or above `bits` (1..64); sorted in place. */
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits);
@@ -316,6 +367,9 @@ vx_status vx_profile_enable(int on);
 vx_status vx_profile_select(const char* kernel_name);
 vx_status vx_profile_reset(void);
 vx_status vx_profile_read(int slot, char* name, size_t name_capacity, double* total_ms, uint64_t* launches);
+/* the number of device blocks the library's handles have requested from its memory pool since the library was loaded (pool hits
+ * included): a steady-state call that allocates nothing leaves it unchanged */
+uint64_t vx_device_allocations(void);
 
 /* ---- multi-GPU helpers (host arithmetic only) ----------------------------------------------------------------
  * Word-aligned shard of the bitmask for rank r of n: contributions of different ranks are word-disjoint, so an

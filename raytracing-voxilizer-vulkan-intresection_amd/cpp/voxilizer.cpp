@@ -18,6 +18,14 @@
 //                                       --logical maps all N ranks onto device 0 (rehearsal on a box with fewer GPUs)
 //   --grid octree --render FILE.ppm     the same picture from the octree's list (hello_vulkan.cpp:690-697), traced on the tree itself
 //                                       (vx_octree_trace_ex) with the default material; --materials is refused there
+//   --render FILE.ppm --mesh FILE.obj   the reference's full frame: the triangle model beside the voxels in one scene (hello_vulkan.cpp:596-635
+//                                       triangle BLAS + the voxel AABB BLAS under one TLAS).  The model is read as loadModel does
+//                                       (hello_vulkan.cpp:197) and traced on its BVH (vx_bvh_trace_ex).  A primary ray takes the closer of the
+//                                       voxel hit and the triangle hit; on EQUAL t the voxel wins.  A voxel hit is shaded as without --mesh; a
+//                                       triangle hit as raytrace.rchit:49-143 with the geometric normal turned toward the ray (the library has
+//                                       no vertex normals), the triangle's OBJ material (MaterialObj{} without one), no textures.  Shadow rays
+//                                       from both kinds of hit are any-hit queries against the voxels AND the mesh.  --grid bool or octree
+//                                       (the grids that render); refused with --bench.
 //   --materials                         switch on the reference's commented-out material plumbing (usemtl / mtllib -> per-voxel
 //                                       material ids; VoxelBuilder.hpp:375-395): --render shades with them, --dump-materials FILE writes
 //                                       getMatIdx() as int16
@@ -64,7 +72,28 @@ void camera(float vi[16], float pi[16], float aspect)
     pi[0] = 1.0f / a; pi[5] = 1.0f / b; pi[11] = 1.0f / d; pi[14] = -1.0f; pi[15] = c / d;  // column-major inverse of the projection
 }
 
-struct RenderOpts { std::vector<MaterialObj> materials; std::vector<int16_t> matIdx; std::string cameraDump; };
+// the triangle model of --mesh: its BVH and what raytrace.rchit reads besides the hit (vertices, per-triangle material)
+struct MeshScene {
+    vx_bvh* bvh = nullptr;
+    const float* verts = nullptr;
+    const int32_t* idx = nullptr;
+    std::vector<MaterialObj> materials;  // the OBJ's records
+    const int32_t* matIds = nullptr;     // per triangle, -1 = none (null: the file has no materials)
+};
+
+struct RenderOpts { std::vector<MaterialObj> materials; std::vector<int16_t> matIdx; std::string cameraDump; const MeshScene* mesh = nullptr; };
+
+// computeSpecular, wavefront.glsl:32-48
+void specular(const MaterialObj& mat, V3 dir, V3 N, V3 L, float spec[3])
+{
+    const float kPi = 3.14159265f, kSh = std::fmax(mat.shininess, 4.0f);
+    const float kE = (2.0f + kSh) / (2.0f * kPi);
+    const V3 V = norm(dir * -1.0f);
+    const V3 I = L * -1.0f;                                     // reflect(-L, N) = I - 2 dot(N, I) N
+    const V3 Rr = I - N * (2.0f * dot(N, I));
+    const float sp = kE * std::pow(std::fmax(dot(V, Rr), 0.0f), kSh);
+    spec[0] = mat.specular.x * sp; spec[1] = mat.specular.y * sp; spec[2] = mat.specular.z * sp;
+}
 
 // trace(const vx_trace_args*) -> vx_status runs one ray batch on whatever holds the boxes: vx_trace_ex on a grid, vx_octree_trace_ex on an octree
 template <class Trace>
@@ -85,6 +114,19 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
     a.view_inverse = vi; a.proj_inverse = pi; a.width = W; a.height = H; a.tmin = 0.001f; a.tmax = 10000.0f;  // rgen:50-51
     a.t = t.data(); a.prim = prim.data(); a.normal = nrm.data();
     vxdetail::check(trace(&a));
+    // --mesh: the same primary rays against the triangles; the closer hit wins, the voxel on equal t
+    const MeshScene* ms = ro.mesh;
+    std::vector<float> mt, mnrm, mbary;
+    std::vector<uint32_t> mprim;
+    std::vector<uint8_t> tri(n, 0);
+    if (ms) {
+        mt.resize(n); mnrm.resize(3 * n); mbary.resize(2 * n); mprim.resize(n);
+        vx_bvh_trace_args ma{};
+        ma.base = a;
+        ma.base.t = mt.data(); ma.base.prim = mprim.data(); ma.base.normal = mnrm.data(); ma.bary = mbary.data();
+        vxdetail::check(vx_bvh_trace_ex(ms->bvh, &ma));
+        for (size_t i = 0; i < n; ++i) tri[i] = mt[i] > 0 && !(t[i] > 0 && t[i] <= mt[i]);
+    }
     // shadow rays from the hit points toward the point light (rchit:76-122)
     const V3 light{10.f, 55.f, 8.f};  // hello_vulkan.h:86
     const float intensity = 1000.f;   // :88
@@ -95,8 +137,17 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
         const float u = ((float)px + 0.5f) / (float)W, v = ((float)py + 0.5f) / (float)H, dx = u * 2.f - 1.f, dy = v * 2.f - 1.f;
         const V3 tg = norm(V3{pi[0] * dx + pi[4] * dy + pi[8] + pi[12], pi[1] * dx + pi[5] * dy + pi[9] + pi[13], pi[2] * dx + pi[6] * dy + pi[10] + pi[14]});
         dirs[i] = V3{vi[0] * tg.x + vi[4] * tg.y + vi[8] * tg.z, vi[1] * tg.x + vi[5] * tg.y + vi[9] * tg.z, vi[2] * tg.x + vi[6] * tg.y + vi[10] * tg.z};
-        const V3 wp = org + dirs[i] * (t[i] > 0 ? t[i] : 0.f);
-        const V3 l = light - wp;
+        const V3 wp = org + dirs[i] * (tri[i] ? mt[i] : (t[i] > 0 ? t[i] : 0.f));
+        V3 l = light - wp;
+        if (tri[i]) {  // rchit:67-68,78-83: the light vector from the hit position interpolated with the barycentrics
+            const int32_t* ti = ms->idx + 3 * (size_t)mprim[i];
+            const float b1 = mbary[2 * i], b2 = mbary[2 * i + 1], b0 = 1.0f - b1 - b2;
+            const float* p0 = ms->verts + 3 * (size_t)ti[0];
+            const float* p1 = ms->verts + 3 * (size_t)ti[1];
+            const float* p2 = ms->verts + 3 * (size_t)ti[2];
+            const V3 pos{p0[0] * b0 + p1[0] * b1 + p2[0] * b2, p0[1] * b0 + p1[1] * b1 + p2[1] * b2, p0[2] * b0 + p1[2] * b1 + p2[2] * b2};
+            l = light - pos;
+        }
         const float dist = std::sqrt(dot(l, l));
         const V3 L = l * (1.0f / dist);
         rays[6 * i + 0] = wp.x; rays[6 * i + 1] = wp.y; rays[6 * i + 2] = wp.z;
@@ -107,12 +158,37 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
     sa.rays = rays.data(); sa.num_rays = n; sa.tmin = 0.001f; sa.tmax = 10000.0f; sa.tmax_per_ray = tmaxs.data(); sa.any_hit = 1;
     sa.shadowed = shadowed.data();
     vxdetail::check(trace(&sa));
+    if (ms) {  // the TLAS holds both BLAS kinds: a shadow ray is blocked by a voxel or a triangle
+        std::vector<uint8_t> ms_shadowed(n);
+        vx_bvh_trace_args mb{};
+        mb.base = sa;
+        mb.base.shadowed = ms_shadowed.data();
+        vxdetail::check(vx_bvh_trace_ex(ms->bvh, &mb));
+        for (size_t i = 0; i < n; ++i) shadowed[i] |= ms_shadowed[i];
+    }
     const MaterialObj defmat{};  // the single default material createAABB uploads (hello_vulkan.cpp:701-702)
     std::vector<unsigned char> img(3 * n);
-    size_t hits = 0;
+    size_t hits = 0, thits = 0;
     for (size_t i = 0; i < n; ++i) {
         float c[3] = {0.8f, 0.8f, 0.8f};  // rmiss:37 with the white clear colour of main.cpp:184
-        if (t[i] > 0) {
+        if (tri[i]) {  // raytrace.rchit:49-143
+            ++thits;
+            V3 N{mnrm[3 * i], mnrm[3 * i + 1], mnrm[3 * i + 2]};
+            if (dot(N, dirs[i]) > 0.0f) N = N * -1.0f;                          // the geometric normal, toward the ray
+            const V3 L{rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]};
+            const int32_t mi = ms->matIds ? ms->matIds[mprim[i]] : -1;           // rchit:92-93
+            const MaterialObj& mat = (mi >= 0 && (size_t)mi < ms->materials.size()) ? ms->materials[(size_t)mi] : defmat;
+            const float li = intensity / (tmaxs[i] * tmaxs[i]);                 // rchit:83
+            const float dnl = std::fmax(dot(N, L), 0.0f);                       // computeDiffuse, wavefront.glsl:25
+            float diff[3] = {mat.diffuse.x * dnl, mat.diffuse.y * dnl, mat.diffuse.z * dnl};
+            if (mat.illum >= 1) { diff[0] += mat.ambient.x; diff[1] += mat.ambient.y; diff[2] += mat.ambient.z; }
+            float att = 1.0f, spec[3] = {0.f, 0.f, 0.f};                        // rchit:106-140
+            if (dot(N, L) > 0) {
+                if (shadowed[i]) att = 0.3f;
+                else if (mat.illum >= 2) specular(mat, dirs[i], N, L, spec);
+            }
+            for (int k = 0; k < 3; ++k) c[k] = li * att * (diff[k] + spec[k]);
+        } else if (t[i] > 0) {
             ++hits;
             const V3 N{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]}, L{rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]};
             // matIndices.i[gl_PrimitiveID] -> materials.m[matIdx] (rchit:92-94); without --materials: index 0 of the one default material
@@ -125,15 +201,7 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
             float att = 0.3f, spec[3] = {0.f, 0.f, 0.f};                        // rchit:99-133
             if (dot(N, L) > 0 && !shadowed[i]) {
                 att = 1.0f;
-                if (mat.illum >= 2) {                                           // computeSpecular, wavefront.glsl:32-48
-                    const float kPi = 3.14159265f, kSh = std::fmax(mat.shininess, 4.0f);
-                    const float kE = (2.0f + kSh) / (2.0f * kPi);
-                    const V3 V = norm(dirs[i] * -1.0f);
-                    const V3 I = L * -1.0f;                                     // reflect(-L, N) = I - 2 dot(N, I) N
-                    const V3 Rr = I - N * (2.0f * dot(N, I));
-                    const float sp = kE * std::pow(std::fmax(dot(V, Rr), 0.0f), kSh);
-                    spec[0] = mat.specular.x * sp; spec[1] = mat.specular.y * sp; spec[2] = mat.specular.z * sp;
-                }
+                if (mat.illum >= 2) specular(mat, dirs[i], N, L, spec);
             }
             for (int k = 0; k < 3; ++k) c[k] = li * att * (diff[k] + spec[k]);
         }
@@ -145,14 +213,15 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
     std::ofstream f(file, std::ios::binary);
     f << "P6\n" << W << " " << H << "\n255\n";
     f.write(reinterpret_cast<const char*>(img.data()), (std::streamsize)img.size());
-    std::printf("[voxhip] rendered %ux%u to %s: %zu of %zu primary rays hit a voxel\n", W, H, file.c_str(), hits, n);
+    if (ms) std::printf("[voxhip] rendered %ux%u to %s: %zu of %zu primary rays hit a voxel, %zu hit a triangle\n", W, H, file.c_str(), hits, n, thits);
+    else std::printf("[voxhip] rendered %ux%u to %s: %zu of %zu primary rays hit a voxel\n", W, H, file.c_str(), hits, n);
     return 0;
 }
 
 template <class T, bool P>
 int run_grid(const std::string& path, float vs, const std::string& dumpFile, const char* label, const std::string& renderFile = "",
              uint32_t rw = 1280, uint32_t rh = 720, bool materials = false, const std::string& matDump = "", const std::string& cameraDump = "",
-             const std::vector<int>& devices = {})
+             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr)
 {
     VoxelBuilder<T, P> voxelBuilder{std::filesystem::path(path)};
     voxelBuilder.withMaterials(materials);
@@ -175,6 +244,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
     dump(dumpFile, aabbs);
     RenderOpts ro;
     ro.cameraDump = cameraDump;
+    ro.mesh = mesh;
     if (materials) {
         ro.materials = vox.getMatrials();
         ro.matIdx = vox.getMatIdx();
@@ -192,14 +262,14 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
                      argv[0]);
         return 2;
     }
     const std::string path = argv[1];
     float vs = 0.f;
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
-    std::string grid = "bool", dumpFile, renderFile, matDump, cameraDump;
+    std::string grid = "bool", dumpFile, renderFile, matDump, cameraDump, meshFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false;
     int gpus = 1;
@@ -215,8 +285,14 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--logical")) logical = true;
         else if (!std::strcmp(argv[i], "--dump-materials") && i + 1 < argc) matDump = argv[++i];
         else if (!std::strcmp(argv[i], "--camera-dump") && i + 1 < argc) cameraDump = argv[++i];
+        else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) meshFile = argv[++i];
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+    }
+    if (!meshFile.empty() && renderFile.empty()) { std::fprintf(stderr, "--mesh needs --render: the triangle model only takes part in the picture\n"); return 2; }
+    if (!meshFile.empty() && (benchRuns > 0 || (grid != "bool" && grid != "octree"))) {
+        std::fprintf(stderr, "--mesh renders with --grid bool or octree only, and not with --bench\n");
+        return 2;
     }
     std::vector<int> devices;
     if (gpus > 1) {
@@ -224,7 +300,36 @@ int main(int argc, char** argv)
         if (!logical && gpus > have) { std::fprintf(stderr, "--gpus %d but %d device(s) visible (add --logical to rehearse on one)\n", gpus, have); return 2; }
         for (int k = 0; k < gpus; ++k) devices.push_back(logical ? 0 : k);
     }
+    // --mesh: the triangle model (loadModel, hello_vulkan.cpp:197) and its BVH, freed when main returns
+    MeshScene meshScene;
+    std::unique_ptr<vx_mesh, vxdetail::MeshDeleter> meshModel;
+    std::unique_ptr<vx_bvh, void (*)(vx_bvh*)> meshBvh(nullptr, vx_bvh_free);
     try {
+        if (!meshFile.empty()) {
+            vx_mesh* m = nullptr;
+            vxdetail::check(vx_mesh_load_obj(meshFile.c_str(), &m));
+            meshModel.reset(m);
+            vx_bvh* b = nullptr;
+            vxdetail::check(vx_bvh_build(m, 0, nullptr, &b));
+            meshBvh.reset(b);
+            meshScene.bvh = b;
+            meshScene.verts = vx_mesh_host_vertices(m);
+            meshScene.idx = vx_mesh_host_indices(m);
+            std::vector<vx_material> recs(vx_mesh_num_materials(m));
+            if (!recs.empty()) vxdetail::check(vx_mesh_materials(m, recs.data(), recs.size()));
+            for (const vx_material& r : recs) {
+                MaterialObj o;
+                o.ambient = vec3(r.ambient[0], r.ambient[1], r.ambient[2]);
+                o.diffuse = vec3(r.diffuse[0], r.diffuse[1], r.diffuse[2]);
+                o.specular = vec3(r.specular[0], r.specular[1], r.specular[2]);
+                o.shininess = r.shininess;
+                o.illum = r.illum;
+                meshScene.materials.push_back(o);
+            }
+            meshScene.matIds = vx_mesh_host_material_ids(m);
+            std::printf("[voxhip] mesh %s: %zu triangles in the BVH\n", meshFile.c_str(), (size_t)vx_bvh_num_triangles(b));
+        }
+        const MeshScene* msp = meshFile.empty() ? nullptr : &meshScene;
         if (benchRuns > 0) {
             if (grid == "octree") Benchmaker<VoxelGridBool, true>{std::filesystem::path(path), vs, (size_t)benchRuns};
             else if (grid == "vec") Benchmaker<VoxelGridVec>{std::filesystem::path(path), vs, (size_t)benchRuns};
@@ -246,12 +351,13 @@ int main(int argc, char** argv)
             if (!renderFile.empty()) {  // the same picture of the octree's list, traced on the tree itself
                 RenderOpts ro;
                 ro.cameraDump = cameraDump;
+                ro.mesh = msp;
                 return render([o = tree.handle()](const vx_trace_args* a) { return vx_octree_trace_ex(o, a); }, renderFile, rw, rh, ro);
             }
             return 0;
         }
-        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices)
-                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices);
+        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp)
+                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp);
         if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct") : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct");
         if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec") : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec");
         std::fprintf(stderr, "unknown grid flavour %s\n", grid.c_str());

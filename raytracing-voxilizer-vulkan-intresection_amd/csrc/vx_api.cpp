@@ -4,6 +4,7 @@
 
 #include <cmath>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -72,8 +73,11 @@ size_t round_size(size_t b)
     return p;
 }
 
+std::atomic<uint64_t> g_pool_requests{0};  // vx_device_allocations
+
 hipError_t pool_alloc(int dev, size_t bytes, void** out, hipStream_t stream)
 {
+    g_pool_requests.fetch_add(1, std::memory_order_relaxed);
     const size_t sz = round_size(bytes);
     Pool& P = g_pool[dev];
     {
@@ -2157,6 +2161,245 @@ void vx_octree_free(vx_octree* o)
     delete o;
 }
 
+// ---- triangle BVH: the reference's triangle BLAS (hello_vulkan.cpp:596-635) under raytrace.rchit (vx_bvh.hip) -------------------------
+struct vx_bvh {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint32_t max_leaf = VX_BVH_DEFAULT_LEAF;
+    uint64_t ntri = 0, nnodes = 0;
+    uint32_t height = 0;
+    float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0};
+    float coord_max = 0.f;  // the largest |coordinate| below the root and ...
+    float extent = 0.f;     // ... the root box's largest side: the traversal's box widening is relative to these
+    uint32_t nill = 0;      // ill-conditioned triangles (vx_bvh.hip): tested by every ray
+    DevBuf nodes, tris, ill;  // the BVH itself
+    DevBuf keys_a, keys_b, sorttmp, child, parent, range, arrived, kbox, alive, newidx, scantmp, small, camera;  // build scratch, kept for rebuilds
+    DevBuf* all[16] = {&nodes, &tris, &ill, &keys_a, &keys_b, &sorttmp, &child, &parent, &range, &arrived, &kbox, &alive, &newidx, &scantmp, &small, &camera};
+};
+
+namespace {
+struct BvhSmall {
+    uint32_t box6[6];
+    uint32_t err;
+    uint32_t nill;
+    unsigned long long total;
+};
+
+vx_status bvh_build_impl(vx_mesh* mesh, vx_bvh* b)
+{
+    VX_TRY(need_device(mesh->device));
+    if (mesh->device != b->device) return fail(VX_ERR_INVALID_ARG, "mesh and BVH live on different devices");
+    DeviceGuard dg(b->device);
+    VX_TRY(mesh_to_device(mesh));
+    hipStream_t s = b->stream;
+    const uint64_t n = mesh->nt;
+    if (n >= 0x7FFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^31 triangles");
+    b->ntri = 0; b->nnodes = 0; b->height = 0; b->coord_max = 0.f; b->extent = 0.f; b->nill = 0;
+    for (int a = 0; a < 3; ++a) b->root_min[a] = b->root_max[a] = 0.f;
+    if (n == 0) return VX_OK;
+    const uint32_t nt = (uint32_t)n, nall = 2 * nt - 1;
+    VX_HIP(b->small.ensure(sizeof(BvhSmall)));
+    VX_HIP(b->keys_a.ensure(n * 8));
+    VX_HIP(b->keys_b.ensure(n * 8));
+    const size_t tb = vx::sort_tmp_bytes(n);
+    VX_HIP(b->sorttmp.ensure(tb));
+    VX_HIP(b->child.ensure((size_t)n * 8));
+    VX_HIP(b->range.ensure((size_t)n * 8));
+    VX_HIP(b->parent.ensure((size_t)nall * 4));
+    VX_HIP(b->arrived.ensure((size_t)n * 4));
+    VX_HIP(b->kbox.ensure((size_t)nall * 32));
+    VX_HIP(b->alive.ensure(((size_t)nall + 16) * 4));
+    VX_HIP(b->newidx.ensure(((size_t)nall + 16) * 4));
+    VX_HIP(b->scantmp.ensure(vx::scan_tmp_bytes(nall)));
+    VX_HIP(b->nodes.ensure((size_t)nall * 32));
+    VX_HIP(b->tris.ensure((size_t)n * 48));
+    VX_HIP(b->ill.ensure((size_t)n * 4));
+    BvhSmall* ds = b->small.as<BvhSmall>();
+    VX_HIP(hipMemsetAsync(ds->box6, 0xFF, 12, s));  // min: the largest ordered value
+    VX_HIP(hipMemsetAsync(ds->box6 + 3, 0, 20, s)); // max: the smallest; err = nill = 0
+    vx::launch_bvh_prep(mesh->dv, mesh->di, mesh->nv, nt, ds->box6, &ds->err, b->keys_a.as<uint64_t>(), s);
+    const uint64_t* keys =
+        vx::launch_sort_u64(b->keys_a.as<uint64_t>(), b->keys_b.as<uint64_t>(), n, 62, b->sorttmp.p, tb, s) == 0 ? b->keys_a.as<uint64_t>() : b->keys_b.as<uint64_t>();
+    vx::launch_bvh_tree(mesh->dv, mesh->di, mesh->nv, nt, keys, b->max_leaf, b->child.as<uint32_t>(), b->parent.as<uint32_t>(), b->range.as<uint32_t>(),
+                        b->arrived.as<uint32_t>(), b->kbox.as<float>(), b->tris.as<float>(), b->alive.as<uint32_t>(), b->ill.as<uint32_t>(), &ds->nill, s);
+    vx::launch_scan_u32(b->alive.as<uint32_t>(), b->newidx.as<uint32_t>(), nall, false, b->scantmp.p, &ds->total, s);
+    vx::launch_bvh_emit(nt, b->alive.as<uint32_t>(), b->newidx.as<uint32_t>(), b->child.as<uint32_t>(), b->range.as<uint32_t>(), b->max_leaf,
+                        b->kbox.as<float>(), b->nodes.as<float>(), s);
+    VX_HIP(hipGetLastError());
+    float root[8];
+    uint32_t nn = 0, err = 0, nill = 0;
+    VX_HIP(hipMemcpyAsync(root, b->kbox.p, 32, hipMemcpyDeviceToHost, s));  // the radix tree's root (unified index 0) and its height
+    VX_HIP(hipMemcpyAsync(&nn, b->newidx.as<uint32_t>() + nall, 4, hipMemcpyDeviceToHost, s));
+    VX_HIP(hipMemcpyAsync(&err, &ds->err, 4, hipMemcpyDeviceToHost, s));
+    VX_HIP(hipMemcpyAsync(&nill, &ds->nill, 4, hipMemcpyDeviceToHost, s));
+    VX_HIP(hipStreamSynchronize(s));
+    if (err) return fail(VX_ERR_INVALID_ARG, "triangle index out of range");
+    std::memcpy(&b->height, &root[3], 4);
+    for (int a = 0; a < 3; ++a) {
+        b->root_min[a] = root[a];
+        b->root_max[a] = root[4 + a];
+        b->coord_max = std::max(b->coord_max, std::max(std::fabs(root[a]), std::fabs(root[4 + a])));
+        b->extent = std::max(b->extent, root[4 + a] - root[a]);
+    }
+    if (!std::isfinite(b->coord_max)) b->coord_max = 0.f;
+    if (!std::isfinite(b->extent)) b->extent = 0.f;
+    b->ntri = n;
+    b->nnodes = nn;
+    b->nill = nill;
+    return VX_OK;
+}
+}  // namespace
+
+vx_status vx_bvh_build(const vx_mesh* mesh_c, uint32_t max_leaf, void* stream, vx_bvh** out)
+{
+    if (!mesh_c || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (max_leaf >= 0x80000000u) return fail(VX_ERR_INVALID_ARG, "max_leaf_triangles must be below 2^31");
+    vx_mesh* mesh = const_cast<vx_mesh*>(mesh_c);
+    VX_TRY(need_device(mesh->device));
+    vx_bvh* b = new vx_bvh();
+    b->device = mesh->device;
+    b->stream = (hipStream_t)stream;
+    b->max_leaf = max_leaf ? max_leaf : VX_BVH_DEFAULT_LEAF;
+    for (DevBuf* x : b->all) { x->dev = b->device; x->stream = b->stream; }
+    const vx_status st = bvh_build_impl(mesh, b);
+    if (st != VX_OK) {
+        const std::string e = g_err;
+        vx_bvh_free(b);
+        return fail(st, e);
+    }
+    *out = b;
+    return VX_OK;
+}
+
+vx_status vx_bvh_build_into(const vx_mesh* mesh_c, vx_bvh* b)
+{
+    if (!mesh_c || !b) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return bvh_build_impl(const_cast<vx_mesh*>(mesh_c), b);
+}
+
+uint64_t vx_bvh_num_triangles(const vx_bvh* b) { return b ? b->ntri : 0; }
+uint64_t vx_bvh_num_nodes(const vx_bvh* b) { return b ? b->nnodes : 0; }
+uint64_t vx_bvh_bytes(const vx_bvh* b) { return b ? b->nnodes * 32 + b->ntri * 48 : 0; }
+uint32_t vx_bvh_height(const vx_bvh* b) { return b ? b->height : 0; }
+uint64_t vx_bvh_num_ill_conditioned(const vx_bvh* b) { return b ? b->nill : 0; }
+const void* vx_bvh_nodes_device(const vx_bvh* b) { return b ? b->nodes.p : nullptr; }
+
+vx_status vx_bvh_root_bounds(const vx_bvh* b, float mn[3], float mx[3])
+{
+    if (!b || !mn || !mx) return fail(VX_ERR_INVALID_ARG, "null argument");
+    std::memcpy(mn, b->root_min, 12);
+    std::memcpy(mx, b->root_max, 12);
+    return VX_OK;
+}
+
+vx_status vx_bvh_nodes(const vx_bvh* b, void* host, uint64_t cap, uint64_t* bytes)
+{
+    if (!b || (!host && cap)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    const uint64_t nb = b->nnodes * sizeof(vx_bvh_node);
+    if (bytes) *bytes = nb;
+    if (!cap || !nb) return VX_OK;
+    if (cap < nb) return fail(VX_ERR_CAPACITY, "node buffer too small");
+    DeviceGuard dg(b->device);
+    VX_HIP(hipMemcpyAsync(host, b->nodes.p, (size_t)nb, hipMemcpyDeviceToHost, b->stream));
+    VX_HIP(hipStreamSynchronize(b->stream));
+    return VX_OK;
+}
+
+vx_status vx_bvh_leaf_triangles(const vx_bvh* b, uint32_t* host, uint64_t cap)
+{
+    if (!b || (!host && cap)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (cap < b->ntri) return fail(VX_ERR_CAPACITY, "triangle buffer too small");
+    if (!b->ntri) return VX_OK;
+    DeviceGuard dg(b->device);
+    std::vector<float> t((size_t)b->ntri * 12);  // the triangle copies: the index rides in the w of the first vertex
+    VX_HIP(hipMemcpyAsync(t.data(), b->tris.p, t.size() * 4, hipMemcpyDeviceToHost, b->stream));
+    VX_HIP(hipStreamSynchronize(b->stream));
+    for (uint64_t i = 0; i < b->ntri; ++i) std::memcpy(&host[i], &t[(size_t)i * 12 + 3], 4);
+    return VX_OK;
+}
+
+static vx_status bvh_trace_common(vx_bvh* b, vx::TraceIO io, float* bary)
+{
+    if (!io.nrays) return VX_OK;
+    if (io.cam) {
+        VX_HIP(b->camera.ensure(sizeof(vx::Camera)));
+        VX_HIP(hipMemcpyAsync(b->camera.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, b->stream));
+        VX_HIP(hipStreamSynchronize(b->stream));  // the host copy lives on the caller's stack
+        io.cam_dev = b->camera.as<vx::Camera>();
+    }
+    vx::launch_bvh_trace(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height, b->extent, b->coord_max, io, bary,
+                         b->stream);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+static vx_status bvh_args_to_io(const vx_bvh_trace_args* a, vx::Camera* cam, vx::TraceIO* io)
+{
+    if (!a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    VX_TRY(args_to_io(&a->base, cam, io));
+    if (io->any_hit && a->bary) return fail(VX_ERR_INVALID_ARG, "any_hit reports only `shadowed` (and an arbitrary accepted t)");
+    return VX_OK;
+}
+
+vx_status vx_bvh_trace_ex_device(const vx_bvh* bc, const vx_bvh_trace_args* args)
+{
+    if (!bc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    vx_bvh* b = const_cast<vx_bvh*>(bc);
+    DeviceGuard dg(b->device);
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(bvh_args_to_io(args, &cam, &io));
+    return bvh_trace_common(b, io, args->bary);
+}
+
+vx_status vx_bvh_trace_ex(const vx_bvh* bc, const vx_bvh_trace_args* args)
+{
+    if (!bc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    vx_bvh* b = const_cast<vx_bvh*>(bc);
+    DeviceGuard dg(b->device);
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(bvh_args_to_io(args, &cam, &io));
+    if (!args->bary) return trace_ex_staged(b->device, b->stream, &args->base, [&](const vx::TraceIO& sio) { return bvh_trace_common(b, sio, nullptr); });
+    // bary: staged here, the rest by the shared staging
+    DevBuf db;
+    db.dev = b->device;
+    db.stream = b->stream;
+    VX_HIP(db.ensure((size_t)io.nrays * 8 + 16));
+    vx_status st = trace_ex_staged(b->device, b->stream, &args->base, [&](const vx::TraceIO& sio) { return bvh_trace_common(b, sio, db.as<float>()); });
+    hipError_t e = hipSuccess;
+    if (st == VX_OK && io.nrays) {
+        e = hipMemcpyAsync(args->bary, db.p, (size_t)io.nrays * 8, hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    }
+    db.release();
+    if (st != VX_OK) return st;
+    VX_HIP(e);
+    return VX_OK;
+}
+
+vx_status vx_bvh_trace(const vx_bvh* bc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim,
+                       uint64_t* num_hits)
+{
+    if (!bc || (nrays && !host_rays)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return trace_simple(host_rays, nrays, tmin, tmax, host_t, host_prim, num_hits, [&](const vx_trace_args* a) {
+        vx_bvh_trace_args ba{};
+        ba.base = *a;
+        return vx_bvh_trace_ex(bc, &ba);
+    });
+}
+
+void vx_bvh_free(vx_bvh* b)
+{
+    if (!b) return;
+    {
+        DeviceGuard dg(b->device);
+        (void)hipStreamSynchronize(b->stream);
+        for (DevBuf* x : b->all) x->release(/*in_flight=*/false);
+    }
+    delete b;
+}
+
 // ---- test aid: the octree's item sort on a host array ----------------------------------------------------------
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits)
 {
@@ -2183,6 +2426,8 @@ vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits)
     VX_HIP(e);
     return VX_OK;
 }
+
+uint64_t vx_device_allocations(void) { return g_pool_requests.load(std::memory_order_relaxed); }
 
 // ---- per-kernel timing (bench / profiling aid) ----------------------------------------------------------------
 vx_status vx_profile_enable(int on)

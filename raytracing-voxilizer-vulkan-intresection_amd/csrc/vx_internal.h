@@ -171,6 +171,22 @@ void launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* wo
 void launch_octree_trace(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,
                          hipStream_t s);
 
+// Triangle BVH (vx_bvh.hip).  Build, all on `s`: launch_bvh_prep (box6 = ordered-uint bounds of all triangles, initialised to ~0 x3 / 0 x3;
+// *err |= 1 when an index leaves [0, nv); keys = Morton code << 32 | triangle), launch_sort_u64 over 62 bits, launch_bvh_tree (radix tree,
+// bottom-up bounds + heights into kbox (2n-1 records of 32 B), the de-indexed triangles in leaf order into tris (48 B each), the survivors of
+// the collapse into alive[2n-1]), an exclusive scan of alive into newidx, launch_bvh_emit (the node array, 32 B per node, root at 0).
+void launch_bvh_prep(const float* v, const int32_t* idx, uint64_t nv, uint32_t ntri, uint32_t* box6, uint32_t* err, uint64_t* keys, hipStream_t s);
+void launch_bvh_tree(const float* v, const int32_t* idx, uint64_t nv, uint32_t n, const uint64_t* keys, uint32_t max_leaf, uint32_t* child,
+                     uint32_t* parent, uint32_t* range, uint32_t* arrived, float* kbox, float* tris, uint32_t* alive,
+                     uint32_t* ill /*n entries: the ill-conditioned triangles' leaf-order positions*/, uint32_t* nill /*zeroed by the caller*/, hipStream_t s);
+void launch_bvh_emit(uint32_t n, const uint32_t* alive, const uint32_t* newidx, const uint32_t* child, const uint32_t* range, uint32_t max_leaf,
+                     const float* kbox, float* nodes, hipStream_t s);
+// First hit per ray on the BVH: io as for launch_octree_trace (cam_dev, not cam; prim = triangle index); bary_out optional (2 f32 per ray).
+// height: the tree's height (LDS stack entries); extent (the largest side of the root box) and coord_max (the largest |coordinate| of the
+// mesh) size the traversal's box widening.
+void launch_bvh_trace(const float* nodes, const float* tris, const uint32_t* ill, uint32_t nill, uint32_t ntri, uint32_t height, float extent,
+                      float coord_max, const TraceIO& io, float* bary_out, hipStream_t s);
+
 // single-voxel helpers
 void launch_set_bit(uint32_t* words, uint64_t idx, hipStream_t s);
 

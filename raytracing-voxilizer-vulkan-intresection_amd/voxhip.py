@@ -21,14 +21,18 @@ STATUS_NAMES = {0: "VX_OK", 1: "VX_ERR_INVALID_ARG", 2: "VX_ERR_PATH", 3: "VX_ER
 AABB = np.dtype([("mn", np.float32, 3), ("mx", np.float32, 3)])
 NODE = np.dtype([("children", np.uint32, 8), ("start", np.uint32), ("count", np.uint32)])
 HIT = np.dtype([("ray", np.uint32), ("prim", np.uint32), ("t", np.float32)])
+BVH_NODE = np.dtype([("mn", np.float32, 3), ("a", np.uint32), ("mx", np.float32, 3), ("b", np.uint32)])   # vx_bvh_node
+BVH_LEAF = 0x80000000
 MATERIAL = np.dtype([("ambient", np.float32, 3), ("diffuse", np.float32, 3), ("specular", np.float32, 3), ("transmittance", np.float32, 3),
                      ("emission", np.float32, 3), ("shininess", np.float32), ("ior", np.float32), ("dissolve", np.float32),
                      ("illum", np.int32), ("texture_id", np.int32)])
 
 
-def _trace_ex(fn, h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want):
-    """vx_trace_ex / vx_octree_trace_ex on host arrays -> dict of the requested outputs (t, prim, normal, shadowed)."""
-    a = TraceArgs()
+def _trace_ex(fn, h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want, bvh=False):
+    """vx_trace_ex / vx_octree_trace_ex / vx_bvh_trace_ex (bvh=True: fn takes vx_bvh_trace_args) on host arrays -> dict of the requested
+    outputs (t, prim, normal, shadowed; bary for the BVH)."""
+    ba = BvhTraceArgs() if bvh else None
+    a = ba.base if bvh else TraceArgs()
     keep = []
     if rays is not None:
         r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
@@ -54,7 +58,11 @@ def _trace_ex(fn, h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want):
         out["normal"] = np.zeros((n, 3), np.float32); a.normal = out["normal"].ctypes.data
     if "shadowed" in want:
         out["shadowed"] = np.zeros(n, np.uint8); a.shadowed = out["shadowed"].ctypes.data
-    _check(fn(h, C.byref(a)))
+    if "bary" in want:
+        if not bvh:
+            raise ValueError("bary is an output of the triangle BVH only")
+        out["bary"] = np.zeros((n, 2), np.float32); ba.bary = out["bary"].ctypes.data
+    _check(fn(h, C.byref(ba if bvh else a)))
     return out
 
 
@@ -74,6 +82,10 @@ class TraceArgs(C.Structure):
                 ("height", C.c_uint32), ("num_rays", C.c_uint64), ("tmin", C.c_float), ("tmax", C.c_float), ("tmax_per_ray", C.c_void_p),
                 ("any_hit", C.c_int32), ("reserved", C.c_int32), ("t", C.c_void_p), ("prim", C.c_void_p), ("normal", C.c_void_p),
                 ("shadowed", C.c_void_p), ("hits", C.c_void_p), ("num_hits", C.c_void_p)]
+
+
+class BvhTraceArgs(C.Structure):
+    _fields_ = [("base", TraceArgs), ("bary", C.c_void_p)]
 
 
 class VxError(RuntimeError):
@@ -98,7 +110,9 @@ SYMBOLS = [
     "vx_octree_root_bounds", "vx_octree_aabbs", "vx_octree_aabbs_device", "vx_octree_free",
     "vx_trace", "vx_trace_device", "vx_trace_primary_device", "vx_trace_ex", "vx_trace_ex_device",
     "vx_octree_trace", "vx_octree_trace_ex", "vx_octree_trace_ex_device",
-    "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read",
+    "vx_bvh_build", "vx_bvh_build_into", "vx_bvh_num_triangles", "vx_bvh_num_nodes", "vx_bvh_bytes", "vx_bvh_height", "vx_bvh_num_ill_conditioned", "vx_bvh_root_bounds",
+    "vx_bvh_nodes", "vx_bvh_leaf_triangles", "vx_bvh_nodes_device", "vx_bvh_trace_ex_device", "vx_bvh_trace_ex", "vx_bvh_trace", "vx_bvh_free",
+    "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read", "vx_device_allocations",
     "vx_shard_words", "vx_shard_range",
 ]
 
@@ -223,6 +237,27 @@ def lib():
     L.vx_octree_trace.argtypes = [vp, vp, C.c_uint64, C.c_float, C.c_float, vp, vp, u64p]
     L.vx_octree_trace_ex.argtypes = [vp, C.POINTER(TraceArgs)]
     L.vx_octree_trace_ex_device.argtypes = [vp, C.POINTER(TraceArgs)]
+    L.vx_bvh_build.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
+    L.vx_bvh_build_into.argtypes = [vp, vp]
+    for n in ("vx_bvh_num_triangles", "vx_bvh_num_nodes", "vx_bvh_bytes"):
+        getattr(L, n).argtypes = [vp]
+        getattr(L, n).restype = C.c_uint64
+    L.vx_bvh_height.argtypes = [vp]
+    L.vx_bvh_height.restype = C.c_uint32
+    L.vx_bvh_num_ill_conditioned.argtypes = [vp]
+    L.vx_bvh_num_ill_conditioned.restype = C.c_uint64
+    L.vx_device_allocations.argtypes = []
+    L.vx_device_allocations.restype = C.c_uint64
+    L.vx_bvh_root_bounds.argtypes = [vp, fp, fp]
+    L.vx_bvh_nodes.argtypes = [vp, vp, C.c_uint64, u64p]
+    L.vx_bvh_leaf_triangles.argtypes = [vp, vp, C.c_uint64]
+    L.vx_bvh_nodes_device.argtypes = [vp]
+    L.vx_bvh_nodes_device.restype = vp
+    L.vx_bvh_trace_ex.argtypes = [vp, C.POINTER(BvhTraceArgs)]
+    L.vx_bvh_trace_ex_device.argtypes = [vp, C.POINTER(BvhTraceArgs)]
+    L.vx_bvh_trace.argtypes = [vp, vp, C.c_uint64, C.c_float, C.c_float, vp, vp, u64p]
+    L.vx_bvh_free.argtypes = [vp]
+    L.vx_bvh_free.restype = None
     L.vx_shard_words.argtypes = [C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p]
     L.vx_shard_words.restype = None
     L.vx_shard_range.argtypes = [C.c_uint64, C.c_int, C.c_int, u64p, u64p]
@@ -271,6 +306,11 @@ def profile_read():
         out[key] = (a + ms.value, b + n.value)
         slot += 1
     return out
+
+
+def device_allocations():
+    """vx_device_allocations: device blocks requested from the library's pool so far (unchanged by a call that allocates nothing)."""
+    return int(lib().vx_device_allocations())
 
 
 def shard_words(num_words, rank, world):
@@ -337,6 +377,10 @@ class Mesh:
         nt = self.num_triangles
         ids = np.ctypeslib.as_array(C.cast(ip_, C.POINTER(C.c_int32)), shape=(nt,)).copy() if (ip_ and nt) else None
         return recs, ids
+
+    def bvh(self, max_leaf=0, stream=None):
+        """vx_bvh_build: the triangle BVH of this mesh (max_leaf 0 = the library default)."""
+        return Bvh(self, max_leaf, stream)
 
     def set_materials(self, records, tri_ids):
         r = np.ascontiguousarray(records, dtype=MATERIAL)
@@ -650,6 +694,108 @@ class Octree:
     def free(self):
         if self.h:
             lib().vx_octree_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Bvh:
+    """vx_bvh handle: the mesh's triangle BVH (the reference's triangle BLAS)."""
+
+    def __init__(self, mesh, max_leaf=0, stream=None):
+        h = C.c_void_p()
+        _check(lib().vx_bvh_build(mesh.h, max_leaf, stream, C.byref(h)))
+        self.h = h
+
+    def build_into(self, mesh):
+        """vx_bvh_build_into: rebuild from the (refreshed) mesh in this handle's memory."""
+        _check(lib().vx_bvh_build_into(mesh.h, self.h))
+
+    @property
+    def num_triangles(self):
+        return int(lib().vx_bvh_num_triangles(self.h))
+
+    @property
+    def num_nodes(self):
+        return int(lib().vx_bvh_num_nodes(self.h))
+
+    @property
+    def height(self):
+        return int(lib().vx_bvh_height(self.h))
+
+    @property
+    def num_ill_conditioned(self):
+        """triangles on the side list every ray tests (slivers, collinear)"""
+        return int(lib().vx_bvh_num_ill_conditioned(self.h))
+
+    def memory_bytes(self):
+        return int(lib().vx_bvh_bytes(self.h))
+
+    def nodes_device_ptr(self):
+        return lib().vx_bvh_nodes_device(self.h)
+
+    def nodes(self):
+        """The node array decoded as BVH_NODE records (root at 0; leaf iff b & BVH_LEAF)."""
+        nb = C.c_uint64()
+        _check(lib().vx_bvh_nodes(self.h, None, 0, C.byref(nb)))
+        out = np.zeros(max(nb.value // BVH_NODE.itemsize, 1), dtype=BVH_NODE)
+        if nb.value:
+            _check(lib().vx_bvh_nodes(self.h, out.ctypes.data, nb.value, C.byref(nb)))
+        return out[:nb.value // BVH_NODE.itemsize]
+
+    def leaf_triangles(self):
+        """Triangle index of every leaf-order position."""
+        n = self.num_triangles
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        _check(lib().vx_bvh_leaf_triangles(self.h, out.ctypes.data, n))
+        return out[:n]
+
+    def root_bounds(self):
+        mn, mx = (C.c_float * 3)(), (C.c_float * 3)()
+        _check(lib().vx_bvh_root_bounds(self.h, mn, mx))
+        return np.array(mn, np.float32), np.array(mx, np.float32)
+
+    def trace(self, rays, tmin=0.001, tmax=10000.0, want_prim=True):
+        """vx_bvh_trace: first hit per ray -> (t, prim, num_hits), or (t, num_hits) without prim."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        t = np.zeros(r.shape[0], dtype=np.float32)
+        p = np.zeros(r.shape[0], dtype=np.uint32) if want_prim else None
+        nh = C.c_uint64()
+        _check(lib().vx_bvh_trace(self.h, r.ctypes.data, r.shape[0], np.float32(tmin), np.float32(tmax), t.ctypes.data,
+                                  p.ctypes.data if want_prim else None, C.byref(nh)))
+        return (t, p, nh.value) if want_prim else (t, nh.value)
+
+    def trace_ex(self, rays=None, camera=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, any_hit=False, want=("t", "prim")):
+        """vx_bvh_trace_ex: host-buffer extended query -> dict of the requested outputs (t, prim, normal, shadowed, bary)."""
+        return _trace_ex(lib().vx_bvh_trace_ex, self.h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want, bvh=True)
+
+    def trace_device(self, rays_ptr, nrays, t_ptr=None, prim_ptr=None, hits_ptr=None, nhits_ptr=None, tmin=0.001, tmax=10000.0,
+                     normal_ptr=None, shadowed_ptr=None, tmax_per_ray_ptr=None, any_hit=False, camera=None, bary_ptr=None):
+        """vx_bvh_trace_ex_device on device pointers; camera = (view_inv, proj_inv, W, H) instead of rays."""
+        ba = BvhTraceArgs()
+        a = ba.base
+        keep = []
+        if camera is not None:
+            vi, pi, w, h = camera
+            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
+            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
+            keep += [cvi, cpi]
+            a.view_inverse, a.proj_inverse, a.width, a.height = cvi, cpi, w, h
+        else:
+            a.rays, a.num_rays = rays_ptr, nrays
+        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
+        a.tmax_per_ray, a.t, a.prim, a.normal, a.shadowed = tmax_per_ray_ptr, t_ptr, prim_ptr, normal_ptr, shadowed_ptr
+        a.hits, a.num_hits = hits_ptr, nhits_ptr
+        ba.bary = bary_ptr
+        _check(lib().vx_bvh_trace_ex_device(self.h, C.byref(ba)))
+
+    def free(self):
+        if self.h:
+            lib().vx_bvh_free(self.h)
             self.h = None
 
     def __del__(self):
