@@ -355,6 +355,62 @@ vx_status vx_bvh_trace(const vx_bvh* b, const float* host_rays, uint64_t num_ray
                        float* host_t /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
 void vx_bvh_free(vx_bvh* b);
 
+/* ---- frames: the reference's per-frame dispatch (raytrace.rgen -> raytrace.rint / raytrace2.rchit on the voxels, raytrace.rchit on the
+ * triangles, a shadow ray into the TLAS, raytrace.rmiss, post.frag) as one asynchronous sequence of kernels that leaves a shaded RGBA8
+ * image in device memory.  Per pixel r = py*width + px:
+ *   primary ray   the camera ray of vx_trace_args (rgen:41-51, tmin 0.001, tmax 10000) against the voxels and, with a mesh, its BVH; the
+ *                 closer hit wins, the voxel on equal t (kind 1 voxel, 2 triangle, 0 miss);
+ *   shadow ray    from org + dir*t toward the light (a triangle hit: the light vector from the position its barycentrics interpolate),
+ *                 tMax = the light distance, any-hit against the voxels and the mesh; dir is computed as voxilizer --render computes it
+ *                 on the host, and origin, direction and tMax are bit-equal to that function's;
+ *   shading       raytrace2.rchit:53-137 (voxels: cube normal, the grid's per-voxel material or MaterialObj{}) / raytrace.rchit:49-143
+ *                 (triangles: the geometric normal turned toward the ray, the OBJ material of the triangle or MaterialObj{}, no textures):
+ *                 diffuse + ambient (illum >= 1), specular (illum >= 2, lit and not shadowed), attenuation 0.3 when shadowed -- and for
+ *                 a voxel facing away from the light, 1 for such a triangle; miss colour 0.8 (rmiss:37); gamma pow(clamp(c, 0, 1), 1/2.2)
+ *                 rounded to nearest (post.frag:36); alpha 255.
+ * The image equals voxilizer --render's within 1 LSB per channel (device powf against host powf); kind and shadowed are exact.
+ * Light: position / intensity / type as the reference's push constants (hello_vulkan.h:84-90); NULL = its default, a point light at
+ * {10, 55, 8} of intensity 1000.  Type 1 (directional, rchit:86-91): L = position * (1 / |position|), light distance 100000 (the shadow
+ * ray's tMax), intensity not divided by the squared distance.
+ * Streams: a frame runs on the scene's stream.  It first makes that stream wait for the work queued so far on the voxel source's and the
+ * BVH's streams, and at its end makes those streams wait for the frame -- a later vx_voxelize_into / vx_bvh_build_into on them cannot
+ * overwrite what the frame still reads.  The grid's traversal structure is built lazily on the grid's own stream, as for vx_trace_ex.
+ * The scene owns all its scratch (pooled): a frame of a size already rendered allocates nothing, and vx_render_frame_device neither
+ * synchronises nor copies to the host -- it returns once the frame is enqueued.
+ * The scene BORROWS its handles: grid or octree, BVH and mesh must outlive it.  Unlike vx_bvh alone, the mesh must stay alive too (the
+ * frame reads its vertices, index triples and per-triangle materials).  A grid or BVH rebuilt in place is picked up by the next frame;
+ * material tables (the grid's, the mesh's) are read at creation and by vx_render_refresh only.
+ * Errors, checked before anything is enqueued: VX_ERR_INVALID_ARG for a null scene / args / camera / rgba, zero width or height, both or
+ * neither voxel source, a grid other than VX_GRID_BOOL, bvh without mesh or the reverse, a mesh whose triangle count differs from the
+ * BVH's, a light type other than 0 or 1; VX_ERR_CAPACITY above 2^32 pixels; VX_ERR_NO_DEVICE without a device (there is no CPU path). */
+typedef struct vx_render_scene vx_render_scene;
+typedef struct vx_render_light {
+    float position[3];
+    float intensity;
+    int32_t type;           /* 0 point, 1 directional */
+} vx_render_light;
+typedef struct vx_render_desc {
+    const vx_grid* grid;     /* exactly one of grid (VX_GRID_BOOL) and octree */
+    const vx_octree* octree;
+    const vx_bvh* bvh;       /* optional triangle model ... */
+    const vx_mesh* mesh;     /* ... and the mesh it was built from (vertices, indices, per-triangle materials): both or neither */
+    void* stream;            /* hipStream_t of the frames; NULL = the default stream */
+} vx_render_desc;
+typedef struct vx_render_args {
+    const float* view_inverse;       /* host, column-major, as vx_trace_args */
+    const float* proj_inverse;
+    uint32_t width, height;
+    const vx_render_light* light;    /* NULL = the reference's default */
+    uint32_t* rgba;                  /* width*height RGBA8, R in the low byte (device pointer in _device, host pointer in vx_render_frame) */
+    uint8_t* kind;                   /* optional: 0 miss, 1 voxel, 2 triangle */
+    uint8_t* shadowed;               /* optional: the OR of both shadow queries where the shading reads it (a hit with dot(N, L) > 0), 0 elsewhere */
+} vx_render_args;
+vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out);
+vx_status vx_render_refresh(vx_render_scene* s);                               /* re-read the material tables after a source was rebuilt */
+vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a);  /* asynchronous on the scene's stream */
+vx_status vx_render_frame(vx_render_scene* s, const vx_render_args* a);         /* host buffers: returns when they are written */
+void vx_render_free(vx_render_scene* s);                                        /* waits for the scene's stream */
+
 /* ---- test aid: the device radix sort the Octree uses for its Morton items (octTree.hpp:363 -> vx_sort.hip), applied to a host array.
  * Keys must have no bit set at or above `bits` (1..64); sorted in place. */
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits);

@@ -14,6 +14,7 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libvoxhip.so")
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+ROCM = os.environ.get("ROCM_PATH", os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))))
 ARCH = "gfx950"
 EXTRA = os.environ.get("VOXHIP_EXTRA_FLAGS", "").split()
 # -fno-slp-vectorize: the SLP vectorizer packs the SAT / plane arithmetic into v_pk_*_f32 pairs and then spends as many v_mov
@@ -25,7 +26,7 @@ FLAGS = EXTRA + ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-m
 # k_walk at 1M and at 8M rays, any value from 8 to 48; no effect on the other kernels (measured on vx_kernels.hip)
 SOURCE_FLAGS = {"vx_walk.hip": ["-mllvm", "-two-entry-phi-node-folding-threshold=16"]}
 
-SOURCES = ["vx_kernels.hip", "vx_trace.hip", "vx_walk.hip", "vx_octrace.hip", "vx_bvh.hip", "vx_octree.hip", "vx_sort.hip", "vx_api.cpp", "vx_obj.cpp", "vx_prof.cpp"]
+SOURCES = ["vx_kernels.hip", "vx_trace.hip", "vx_walk.hip", "vx_octrace.hip", "vx_bvh.hip", "vx_octree.hip", "vx_sort.hip", "vx_render.hip", "vx_api.cpp", "vx_obj.cpp", "vx_prof.cpp"]
 HEADERS = ["vx_math.h", "vx_internal.h", "vx_ray.h", os.path.join(ROOT, "include", "voxhip.h")]
 
 
@@ -72,7 +73,8 @@ def build_lib(force=False, verbose=False):
 
 
 def build_cpp(force=False):
-    """C++ facade: the `voxilizer <obj> <voxelsize>` CLI and the facade self-test, plain g++ against libvoxhip.so."""
+    """C++ facade: the `voxilizer <obj> <voxelsize>` CLI and the facade self-test, plain g++ against libvoxhip.so (and the HIP runtime's
+    host API, which the CLI's --frames uses for its device image buffers)."""
     outs = []
     for name in ("voxilizer", "facade_selftest"):
         src = os.path.join(CPP, name + ".cpp")
@@ -81,8 +83,9 @@ def build_cpp(force=False):
         out = os.path.join(HERE, name)
         deps = [src, LIB] + [os.path.join(CPP, f) for f in os.listdir(CPP) if f.endswith((".hpp", ".h"))]
         if force or _newer(out, deps):
-            _run(["g++", "-O2", "-std=c++20", "-ffp-contract=off", "-I", CPP, "-I", os.path.join(ROOT, "include"), src, "-o", out,
-                  "-L", HERE, "-lvoxhip", "-Wl,-rpath,$ORIGIN", "-lpthread"])
+            _run(["g++", "-O2", "-std=c++20", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I", CPP, "-I", os.path.join(ROOT, "include"),
+                  "-isystem", os.path.join(ROCM, "include"), src, "-o", out, "-L", HERE, "-lvoxhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64",
+                  "-Wl,-rpath,$ORIGIN", "-lpthread"])
         outs.append(out)
     return outs
 

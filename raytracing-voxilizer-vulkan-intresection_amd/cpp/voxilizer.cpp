@@ -26,6 +26,10 @@
 //                                       no vertex normals), the triangle's OBJ material (MaterialObj{} without one), no textures.  Shadow rays
 //                                       from both kinds of hit are any-hit queries against the voxels AND the mesh.  --grid bool or octree
 //                                       (the grids that render); refused with --bench.
+//   --render FILE.ppm --frames N        the same scene as a whole frame on the device (vx_render_frame_device: shading, shadow rays and the
+//                                       merge of voxel and triangle hits in kernels, one asynchronous sequence per frame), N frames from the
+//                                       reference camera; writes the last one and prints its hit counts and the device frame time (host wall
+//                                       between device-synchronised points, first frame excluded).  Refused with --bench.
 //   --materials                         switch on the reference's commented-out material plumbing (usemtl / mtllib -> per-voxel
 //                                       material ids; VoxelBuilder.hpp:375-395): --render shades with them, --dump-materials FILE writes
 //                                       getMatIdx() as int16
@@ -35,6 +39,8 @@
 #include <cstring>
 #include <fstream>
 #include <string>
+
+#include <hip/hip_runtime_api.h>
 
 #include "Benchmaker.hpp"
 #include "VoxelBuilder.hpp"
@@ -75,13 +81,75 @@ void camera(float vi[16], float pi[16], float aspect)
 // the triangle model of --mesh: its BVH and what raytrace.rchit reads besides the hit (vertices, per-triangle material)
 struct MeshScene {
     vx_bvh* bvh = nullptr;
+    const vx_mesh* model = nullptr;
     const float* verts = nullptr;
     const int32_t* idx = nullptr;
     std::vector<MaterialObj> materials;  // the OBJ's records
     const int32_t* matIds = nullptr;     // per triangle, -1 = none (null: the file has no materials)
 };
 
-struct RenderOpts { std::vector<MaterialObj> materials; std::vector<int16_t> matIdx; std::string cameraDump; const MeshScene* mesh = nullptr; };
+struct RenderOpts { std::vector<MaterialObj> materials; std::vector<int16_t> matIdx; std::string cameraDump; const MeshScene* mesh = nullptr; long frames = 0; };
+
+void hip_check(hipError_t e)
+{
+    if (e != hipSuccess) throw std::runtime_error(std::string("HIP: ") + hipGetErrorString(e));
+}
+
+// --frames N: the picture of render() as device frames (vx_render_frame_device) on the default stream; the last one is written to `file`
+int render_frames(const vx_grid* grid, const vx_octree* octree, const std::string& file, uint32_t W, uint32_t H, const RenderOpts& ro)
+{
+    float vi[16], pi[16];
+    camera(vi, pi, (float)W / (float)H);
+    if (!ro.cameraDump.empty()) {
+        std::ofstream cf(ro.cameraDump, std::ios::binary);
+        cf.write(reinterpret_cast<const char*>(vi), 64);
+        cf.write(reinterpret_cast<const char*>(pi), 64);
+    }
+    vx_render_desc d{};
+    d.grid = grid;
+    d.octree = octree;
+    if (ro.mesh) { d.bvh = ro.mesh->bvh; d.mesh = ro.mesh->model; }
+    vx_render_scene* scene = nullptr;
+    vxdetail::check(vx_render_create(&d, &scene));
+    std::unique_ptr<vx_render_scene, void (*)(vx_render_scene*)> keep(scene, vx_render_free);
+    const size_t n = (size_t)W * H;
+    void *drgba = nullptr, *dkind = nullptr;
+    hip_check(hipMalloc(&drgba, n * 4));
+    hip_check(hipMalloc(&dkind, n));
+    vx_render_args a{};
+    a.view_inverse = vi; a.proj_inverse = pi; a.width = W; a.height = H;
+    a.rgba = static_cast<uint32_t*>(drgba);
+    a.kind = static_cast<uint8_t*>(dkind);
+    // frame 1 builds the traversal structure and sizes the scene's buffers; frames 2..N are timed as a block between two synchronisations
+    vxdetail::check(vx_render_frame_device(scene, &a));
+    hip_check(hipStreamSynchronize(nullptr));
+    const auto t0 = Clock::now();
+    for (long f = 1; f < ro.frames; ++f) vxdetail::check(vx_render_frame_device(scene, &a));
+    hip_check(hipStreamSynchronize(nullptr));
+    const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+    std::vector<uint32_t> rgba(n);
+    std::vector<uint8_t> kind(n);
+    hip_check(hipMemcpy(rgba.data(), drgba, n * 4, hipMemcpyDeviceToHost));
+    hip_check(hipMemcpy(kind.data(), dkind, n, hipMemcpyDeviceToHost));
+    hip_check(hipFree(drgba));
+    hip_check(hipFree(dkind));
+    std::vector<unsigned char> img(3 * n);
+    size_t hits = 0, thits = 0;
+    for (size_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) img[3 * i + k] = (unsigned char)(rgba[i] >> (8 * k));
+        hits += kind[i] == 1;
+        thits += kind[i] == 2;
+    }
+    std::ofstream f(file, std::ios::binary);
+    f << "P6\n" << W << " " << H << "\n255\n";
+    f.write(reinterpret_cast<const char*>(img.data()), (std::streamsize)img.size());
+    if (ro.mesh) std::printf("[voxhip] rendered %ux%u to %s: %zu of %zu primary rays hit a voxel, %zu hit a triangle\n", W, H, file.c_str(), hits, n, thits);
+    else std::printf("[voxhip] rendered %ux%u to %s: %zu of %zu primary rays hit a voxel\n", W, H, file.c_str(), hits, n);
+    const long timed = ro.frames - 1;
+    if (timed > 0) std::printf("[voxhip] device frame %ux%u: %.3f ms/frame (%.1f FPS) over %ld frames\n", W, H, ms / (double)timed, 1000.0 * (double)timed / ms, timed);
+    else std::printf("[voxhip] device frame %ux%u: no timed frame (--frames 1)\n", W, H);
+    return 0;
+}
 
 // computeSpecular, wavefront.glsl:32-48
 void specular(const MaterialObj& mat, V3 dir, V3 N, V3 L, float spec[3])
@@ -221,7 +289,7 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
 template <class T, bool P>
 int run_grid(const std::string& path, float vs, const std::string& dumpFile, const char* label, const std::string& renderFile = "",
              uint32_t rw = 1280, uint32_t rh = 720, bool materials = false, const std::string& matDump = "", const std::string& cameraDump = "",
-             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr)
+             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0)
 {
     VoxelBuilder<T, P> voxelBuilder{std::filesystem::path(path)};
     voxelBuilder.withMaterials(materials);
@@ -254,6 +322,8 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
             f.write(reinterpret_cast<const char*>(ro.matIdx.data()), (std::streamsize)(ro.matIdx.size() * sizeof(int16_t)));
         }
     }
+    ro.frames = frames;
+    if (!renderFile.empty() && frames > 0) return render_frames(vox.handle(), nullptr, renderFile, rw, rh, ro);
     if (!renderFile.empty()) return render([g = vox.handle()](const vx_trace_args* a) { return vx_trace_ex(g, a); }, renderFile, rw, rh, ro);
     return 0;
 }
@@ -262,7 +332,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj] [--frames N]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
                      argv[0]);
         return 2;
     }
@@ -273,7 +343,7 @@ int main(int argc, char** argv)
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false;
     int gpus = 1;
-    long benchRuns = 0;
+    long benchRuns = 0, frames = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--grid") && i + 1 < argc) grid = argv[++i];
         else if (!std::strcmp(argv[i], "--parallel")) parallel = true;
@@ -286,12 +356,17 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--dump-materials") && i + 1 < argc) matDump = argv[++i];
         else if (!std::strcmp(argv[i], "--camera-dump") && i + 1 < argc) cameraDump = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) meshFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (!meshFile.empty() && renderFile.empty()) { std::fprintf(stderr, "--mesh needs --render: the triangle model only takes part in the picture\n"); return 2; }
     if (!meshFile.empty() && (benchRuns > 0 || (grid != "bool" && grid != "octree"))) {
         std::fprintf(stderr, "--mesh renders with --grid bool or octree only, and not with --bench\n");
+        return 2;
+    }
+    if (frames > 0 && (renderFile.empty() || benchRuns > 0 || (grid != "bool" && grid != "octree"))) {
+        std::fprintf(stderr, "--frames renders with --render and --grid bool or octree only, and not with --bench\n");
         return 2;
     }
     std::vector<int> devices;
@@ -313,6 +388,7 @@ int main(int argc, char** argv)
             vxdetail::check(vx_bvh_build(m, 0, nullptr, &b));
             meshBvh.reset(b);
             meshScene.bvh = b;
+            meshScene.model = m;
             meshScene.verts = vx_mesh_host_vertices(m);
             meshScene.idx = vx_mesh_host_indices(m);
             std::vector<vx_material> recs(vx_mesh_num_materials(m));
@@ -352,12 +428,13 @@ int main(int argc, char** argv)
                 RenderOpts ro;
                 ro.cameraDump = cameraDump;
                 ro.mesh = msp;
+                if (frames > 0) { ro.frames = frames; return render_frames(nullptr, tree.handle(), renderFile, rw, rh, ro); }
                 return render([o = tree.handle()](const vx_trace_args* a) { return vx_octree_trace_ex(o, a); }, renderFile, rw, rh, ro);
             }
             return 0;
         }
-        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp)
-                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp);
+        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames)
+                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames);
         if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct") : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct");
         if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec") : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec");
         std::fprintf(stderr, "unknown grid flavour %s\n", grid.c_str());

@@ -2400,6 +2400,345 @@ void vx_bvh_free(vx_bvh* b)
     delete b;
 }
 
+// ---- frames: the reference's per-frame raytrace dispatch as one asynchronous sequence on the scene's stream (vx_render.hip) ------------
+// camera block -> primary traversals (voxels, mesh) -> k_render_shadow_rays -> shadow traversals (voxels, mesh) -> k_render_shade.  The
+// scene owns every buffer the sequence touches, the walk's work counters included, so a frame never shares scratch with a trace the user
+// runs on a source's own stream.
+struct vx_render_scene {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    vx_grid* grid = nullptr;
+    vx_octree* octree = nullptr;
+    vx_bvh* bvh = nullptr;
+    vx_mesh* mesh = nullptr;
+    DevBuf camera, counters, idxtmp, vt, vprim, vnrm, mt, mprim, mnrm, mbary, srays, sdist, stmax, sv, sm, vmat, mmat, mids, rgba, kind, shad;
+    DevBuf* all[21] = {&camera, &counters, &idxtmp, &vt, &vprim, &vnrm, &mt, &mprim, &mnrm, &mbary, &srays, &sdist, &stmax, &sv, &sm, &vmat, &mmat, &mids, &rgba, &kind, &shad};
+    int phase = 0;              // which of the two walk counters the next k_walk launch draws from (launch_trace)
+    uint64_t nvmat = 0, nmmat = 0;
+    bool has_mids = false;
+    hipEvent_t ev_src[2] = {nullptr, nullptr};  // recorded on the voxel source's and the BVH's stream at the start of a frame
+    hipEvent_t ev_end = nullptr;                          // recorded on the scene's stream at its end
+};
+
+namespace {
+// Shadow rays of pixels whose shading cannot read the flag (misses, hits facing away from the light) get the empty interval tmax 0 < tmin:
+// the traversals leave them at once (5-12 % of the frame).  VOXHIP_RENDER_CULL=0 traces every pixel's ray as render() does.
+bool render_cull()
+{
+    static const bool on = !(getenv("VOXHIP_RENDER_CULL") && atoi(getenv("VOXHIP_RENDER_CULL")) == 0);
+    return on;
+}
+
+vx_status render_desc_check(const vx_render_desc* d)
+{
+    if (!d) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (!d->grid == !d->octree) return fail(VX_ERR_INVALID_ARG, "exactly one voxel source: grid or octree");
+    if (!d->bvh != !d->mesh) return fail(VX_ERR_INVALID_ARG, "bvh and mesh go together: both or neither");
+    return VX_OK;
+}
+
+vx_status render_light(const vx_render_light* l, vx_render_light* out)
+{
+    if (!l) {  // hello_vulkan.h:84-90: point light at {10, 55, 8}, intensity 1000
+        out->position[0] = 10.f; out->position[1] = 55.f; out->position[2] = 8.f;
+        out->intensity = 1000.f;
+        out->type = 0;
+        return VX_OK;
+    }
+    if (l->type != 0 && l->type != 1) return fail(VX_ERR_INVALID_ARG, "light type must be 0 (point) or 1 (directional)");
+    *out = *l;
+    return VX_OK;
+}
+
+vx_status render_args_check(const vx_render_args* a, vx_render_light* light)
+{
+    if (!a || !a->view_inverse || !a->proj_inverse || !a->rgba) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (!a->width || !a->height) return fail(VX_ERR_INVALID_ARG, "zero width or height");
+    if ((uint64_t)a->width * a->height >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 pixels");
+    return render_light(a->light, light);
+}
+
+// the handles' state that a frame reads (checked at creation and before every frame: sources may be rebuilt in between)
+vx_status render_sources_check(const vx_render_scene* s)
+{
+    if (s->grid && s->grid->kind != VX_GRID_BOOL) return fail(VX_ERR_INVALID_ARG, "the grid must be a VX_GRID_BOOL grid");
+    if (s->bvh && s->bvh->ntri != s->mesh->nt) return fail(VX_ERR_INVALID_ARG, "the mesh's triangle count differs from the BVH's");
+    const int dev = s->grid ? s->grid->device : s->octree->device;
+    if ((s->bvh && s->bvh->device != dev) || (s->mesh && s->mesh->device != dev)) return fail(VX_ERR_INVALID_ARG, "the scene's handles live on different devices");
+    return VX_OK;
+}
+
+hipStream_t source_stream(const vx_render_scene* s, int k)
+{
+    if (k == 0) return s->grid ? s->grid->stream : s->octree->stream;
+    return k == 1 ? s->bvh->stream : nullptr;
+}
+
+vx_status render_upload_materials(vx_render_scene* s)
+{
+    // the grid's material table (getMatrials) and the mesh's OBJ records with its per-triangle ids; staged once, not per frame
+    s->nvmat = s->nmmat = 0;
+    s->has_mids = false;
+    std::vector<vx_material> vm = (s->grid && s->grid->has_materials) ? s->grid->materials : std::vector<vx_material>();
+    if (!vm.empty()) {
+        VX_HIP(s->vmat.ensure(vm.size() * sizeof(vx_material)));
+        VX_HIP(hipMemcpyAsync(s->vmat.p, vm.data(), vm.size() * sizeof(vx_material), hipMemcpyHostToDevice, s->stream));
+        s->nvmat = vm.size();
+    }
+    if (s->mesh && !s->mesh->materials.empty()) {
+        VX_HIP(s->mmat.ensure(s->mesh->materials.size() * sizeof(vx_material)));
+        VX_HIP(hipMemcpyAsync(s->mmat.p, s->mesh->materials.data(), s->mesh->materials.size() * sizeof(vx_material), hipMemcpyHostToDevice, s->stream));
+        s->nmmat = s->mesh->materials.size();
+    }
+    if (s->mesh && !s->mesh->tri_mat.empty() && s->mesh->tri_mat.size() == s->mesh->nt) {
+        VX_HIP(s->mids.ensure(s->mesh->nt * 4));
+        VX_HIP(hipMemcpyAsync(s->mids.p, s->mesh->tri_mat.data(), s->mesh->nt * 4, hipMemcpyHostToDevice, s->stream));
+        s->has_mids = true;
+    }
+    VX_HIP(hipStreamSynchronize(s->stream));  // the host vectors may change after this call
+    return VX_OK;
+}
+
+// size the per-pixel buffers (pooled: a size already rendered requests nothing)
+vx_status render_buffers(vx_render_scene* s, uint64_t n, bool cull)
+{
+    VX_HIP(s->vt.ensure(n * 4 + 8));
+    VX_HIP(s->vprim.ensure(n * 4 + 8));
+    VX_HIP(s->vnrm.ensure(n * 12 + 8));
+    if (s->grid) VX_HIP(s->idxtmp.ensure(vx::trace_idx_bytes(s->grid->g, n)));
+    if (s->bvh) {
+        VX_HIP(s->mt.ensure(n * 4 + 8));
+        VX_HIP(s->mprim.ensure(n * 4 + 8));
+        VX_HIP(s->mnrm.ensure(n * 12 + 8));
+        VX_HIP(s->mbary.ensure(n * 8 + 8));
+        VX_HIP(s->sm.ensure(n + 8));
+    }
+    VX_HIP(s->srays.ensure(n * 24 + 8));
+    VX_HIP(s->sdist.ensure(n * 4 + 8));
+    if (cull) VX_HIP(s->stmax.ensure(n * 4 + 8));
+    VX_HIP(s->sv.ensure(n + 8));
+    return VX_OK;
+}
+
+// one frame, enqueued on s->stream; rgba / kind / shadowed are device pointers
+vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_render_light& light, uint32_t* rgba, uint8_t* kind, uint8_t* shadowed)
+{
+    const uint64_t n = (uint64_t)a->width * a->height;
+    const bool cull = render_cull();
+    hipStream_t st = s->stream;
+    vx_grid* g = s->grid;
+    if (g) {  // the traversal structure and the word prefix, built once per grid build on the grid's own stream (no-ops when current)
+        VX_TRY(ensure_coarse(g));
+        bool pending = false;
+        VX_TRY(prefix_launch(g, &pending));
+    }
+    VX_TRY(render_buffers(s, n, cull));
+    // start: the frame's stream waits for everything queued so far on the sources' streams
+    for (int k = 0; k < 2; ++k) {
+        if (k == 1 && !s->bvh) continue;
+        const hipStream_t ss = source_stream(s, k);
+        if (ss == st) continue;
+        VX_HIP(hipEventRecord(s->ev_src[k], ss));
+        VX_HIP(hipStreamWaitEvent(st, s->ev_src[k], 0));
+    }
+    vx::Camera cam;
+    std::memcpy(cam.viewInv, a->view_inverse, 64);
+    std::memcpy(cam.projInv, a->proj_inverse, 64);
+    cam.width = a->width;
+    cam.height = a->height;
+    vx::launch_render_camera(cam, s->camera.as<vx::Camera>(), st);
+    // primary rays, rgen:50-51
+    vx::TraceIO io;
+    io.cam_dev = s->camera.as<vx::Camera>();
+    io.nrays = n;
+    io.tmin = 0.001f;
+    io.tmax = 10000.0f;
+    io.t_out = s->vt.as<float>();
+    io.prim_out = s->vprim.as<uint32_t>();
+    io.normal_out = s->vnrm.as<float>();
+    vx::TraceMips mips{};
+    const uint32_t* p16 = nullptr;
+    if (g) {
+        mips.bricks3 = g->bricks.as<unsigned long long>();
+        mips.w0 = g->words.as<uint32_t>();
+        mips.w1 = g->cwords.as<uint32_t>();
+        mips.w2 = g->c2words.as<uint32_t>();
+        for (int k = 0; k < 3; ++k) { mips.d1[k] = g->cdim[k]; mips.d2[k] = g->c2dim[k]; }
+        static const bool rank16 = !(getenv("VOXHIP_RANK16") && atoi(getenv("VOXHIP_RANK16")) == 0);
+        p16 = (g->sel_valid && rank16 && (g->g.nwords % 16) == 0) ? g->wp16.as<uint32_t>() : nullptr;  // as trace_common
+    }
+    vx_octree* o = s->octree;
+    auto voxels = [&](const vx::TraceIO& q) {
+        if (g) vx::launch_trace(g->g, mips, g->wprefix.as<uint32_t>(), q, s->counters.as<unsigned long long>(), &s->phase, s->idxtmp.p, st, p16, nullptr);
+        else vx::launch_octree_trace(o->dnodes, o->items.as<uint64_t>(), o->nnodes == 0 ? 0 : o->nitems, o->bits, o->root_min, o->vs, q, st);
+    };
+    vx_bvh* b = s->bvh;
+    auto triangles = [&](const vx::TraceIO& q, float* bary) {
+        vx::launch_bvh_trace(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height, b->extent,
+                             b->coord_max, q, bary, st);
+    };
+    voxels(io);
+    if (b) {
+        vx::TraceIO mio = io;
+        mio.t_out = s->mt.as<float>();
+        mio.prim_out = s->mprim.as<uint32_t>();
+        mio.normal_out = s->mnrm.as<float>();
+        triangles(mio, s->mbary.as<float>());
+    }
+    vx::RenderParams P;
+    P.n = n;
+    P.cam = s->camera.as<vx::Camera>();
+    P.vt = s->vt.as<float>();
+    P.vprim = s->vprim.as<uint32_t>();
+    P.vnrm = s->vnrm.as<float>();
+    if (b) {
+        P.mt = s->mt.as<float>();
+        P.mprim = s->mprim.as<uint32_t>();
+        P.mnrm = s->mnrm.as<float>();
+        P.mbary = s->mbary.as<float>();
+        P.verts = s->mesh->dv;
+        P.idx = s->mesh->di;
+        P.sm = s->sm.as<uint8_t>();
+        if (s->has_mids) P.mids = s->mids.as<int32_t>();
+        P.mmat = s->mmat.as<vx_material>();
+        P.nmmat = s->nmmat;
+    }
+    for (int k = 0; k < 3; ++k) P.light[k] = light.position[k];
+    P.intensity = light.intensity;
+    P.light_type = light.type;
+    P.srays = s->srays.as<float>();
+    P.sdist = s->sdist.as<float>();
+    P.stmax = cull ? s->stmax.as<float>() : nullptr;
+    P.sv = s->sv.as<uint8_t>();
+    const int16_t* vids = g ? vx_grid_material_ids_device(g) : nullptr;
+    if (vids && s->nvmat) {
+        P.vids = vids;
+        P.nvids = g->mat_gathered ? g->mat_gather_count : g->mat_count;
+        P.vmat = s->vmat.as<vx_material>();
+        P.nvmat = s->nvmat;
+    }
+    P.rgba = rgba;
+    P.kind_out = kind;
+    P.shadowed_out = shadowed;
+    vx::launch_render_shadow_rays(P, st);
+    // shadow rays: any-hit against the voxels and the mesh (rchit:108-122), tMax = the light distance
+    vx::TraceIO sio;
+    sio.rays = s->srays.as<float>();
+    sio.nrays = n;
+    sio.tmin = 0.001f;
+    sio.tmax = 10000.0f;
+    sio.tmax_per_ray = cull ? s->stmax.as<float>() : s->sdist.as<float>();
+    sio.any_hit = true;
+    sio.shadowed_out = s->sv.as<uint8_t>();
+    voxels(sio);
+    if (b) {
+        sio.shadowed_out = s->sm.as<uint8_t>();
+        triangles(sio, nullptr);
+    }
+    vx::launch_render_shade(P, st);
+    VX_HIP(hipGetLastError());
+    // end: later work on the sources' streams (a rebuild) waits for the frame's reads
+    VX_HIP(hipEventRecord(s->ev_end, st));
+    for (int k = 0; k < 2; ++k) {
+        if (k == 1 && !s->bvh) continue;
+        const hipStream_t ss = source_stream(s, k);
+        if (ss != st) VX_HIP(hipStreamWaitEvent(ss, s->ev_end, 0));
+    }
+    return VX_OK;
+}
+}  // namespace
+
+vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out)
+{
+    if (!out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    VX_TRY(render_desc_check(desc));
+    VX_TRY(need_device(g_device));
+    vx_render_scene* s = new vx_render_scene();
+    s->grid = const_cast<vx_grid*>(desc->grid);
+    s->octree = const_cast<vx_octree*>(desc->octree);
+    s->bvh = const_cast<vx_bvh*>(desc->bvh);
+    s->mesh = const_cast<vx_mesh*>(desc->mesh);
+    s->stream = (hipStream_t)desc->stream;
+    const vx_status cs = render_sources_check(s);
+    if (cs != VX_OK) { delete s; return cs; }
+    s->device = s->grid ? s->grid->device : s->octree->device;
+    for (DevBuf* x : s->all) { x->dev = s->device; x->stream = s->stream; }
+    auto bail = [&](vx_status st) {
+        const std::string e = g_err;
+        vx_render_free(s);
+        return fail(st, e);
+    };
+    DeviceGuard dg(s->device);
+    if (s->mesh) { const vx_status ms = mesh_to_device(s->mesh); if (ms != VX_OK) return bail(ms); }
+    hipError_t e = s->camera.ensure(sizeof(vx::Camera));
+    if (e == hipSuccess) e = s->counters.ensure(4 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(s->counters.p, 0, 4 * sizeof(unsigned long long), s->stream);  // the walk's counters start at zero
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&s->ev_src[k], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_end, hipEventDisableTiming);
+    if (e != hipSuccess) return bail(fail(VX_ERR_HIP, std::string("vx_render_create: ") + hipGetErrorString(e)));
+    const vx_status ms = render_upload_materials(s);
+    if (ms != VX_OK) return bail(ms);
+    *out = s;
+    return VX_OK;
+}
+
+vx_status vx_render_refresh(vx_render_scene* s)
+{
+    if (!s) return fail(VX_ERR_INVALID_ARG, "null argument");
+    VX_TRY(render_sources_check(s));
+    DeviceGuard dg(s->device);
+    // the old tables may still be read by a frame in flight: queue the refresh behind it on the scene's stream (upload is stream-ordered)
+    return render_upload_materials(s);
+}
+
+vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a)
+{
+    vx_render_light light;
+    VX_TRY(render_args_check(a, &light));
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return fail(VX_ERR_NO_DEVICE, "no HIP device available: libvoxhip has no CPU path");
+    if (!s) return fail(VX_ERR_INVALID_ARG, "null argument");
+    VX_TRY(render_sources_check(s));
+    DeviceGuard dg(s->device);
+    return render_enqueue(s, a, light, a->rgba, a->kind, a->shadowed);
+}
+
+vx_status vx_render_frame(vx_render_scene* s, const vx_render_args* a)
+{
+    vx_render_light light;
+    VX_TRY(render_args_check(a, &light));
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return fail(VX_ERR_NO_DEVICE, "no HIP device available: libvoxhip has no CPU path");
+    if (!s) return fail(VX_ERR_INVALID_ARG, "null argument");
+    VX_TRY(render_sources_check(s));
+    DeviceGuard dg(s->device);
+    const uint64_t n = (uint64_t)a->width * a->height;
+    VX_HIP(s->rgba.ensure(n * 4));
+    if (a->kind) VX_HIP(s->kind.ensure(n));
+    if (a->shadowed) VX_HIP(s->shad.ensure(n));
+    VX_TRY(render_enqueue(s, a, light, s->rgba.as<uint32_t>(), a->kind ? s->kind.as<uint8_t>() : nullptr, a->shadowed ? s->shad.as<uint8_t>() : nullptr));
+    VX_HIP(hipMemcpyAsync(a->rgba, s->rgba.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+    if (a->kind) VX_HIP(hipMemcpyAsync(a->kind, s->kind.p, n, hipMemcpyDeviceToHost, s->stream));
+    if (a->shadowed) VX_HIP(hipMemcpyAsync(a->shadowed, s->shad.p, n, hipMemcpyDeviceToHost, s->stream));
+    VX_HIP(hipStreamSynchronize(s->stream));
+    return VX_OK;
+}
+
+void vx_render_free(vx_render_scene* s)
+{
+    if (!s) return;
+    {
+        DeviceGuard dg(s->device);
+        (void)hipStreamSynchronize(s->stream);
+        for (DevBuf* x : s->all) x->release(/*in_flight=*/false);
+        for (hipEvent_t& ev : s->ev_src)
+            if (ev) (void)hipEventDestroy(ev);
+        if (s->ev_end) (void)hipEventDestroy(s->ev_end);
+    }
+    delete s;
+}
+
 // ---- test aid: the octree's item sort on a host array ----------------------------------------------------------
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits)
 {

@@ -187,6 +187,45 @@ void launch_bvh_emit(uint32_t n, const uint32_t* alive, const uint32_t* newidx, 
 void launch_bvh_trace(const float* nodes, const float* tris, const uint32_t* ill, uint32_t nill, uint32_t ntri, uint32_t height, float extent,
                       float coord_max, const TraceIO& io, float* bary_out, hipStream_t s);
 
+// Frames (vx_render.hip): the per-pixel stages of vx_render_frame_device around the traversals.  n = width * height pixels, pixel
+// r = py * width + px.  Hit arrays as the traversals write them (mt / mprim / mnrm / mbary null without a mesh); srays (6 f32 per pixel),
+// sdist (the light distance: the shadow ray's tMax and the shading's 1/d^2) and, optional, stmax (sdist with 0 where no shading reads
+// the shadow flag) are written by the shadow-ray stage and read by the shading stage; sv / sm (optional) are the two shadow queries.
+struct RenderParams {
+    uint64_t n = 0;
+    const Camera* cam = nullptr;
+    const float* vt = nullptr;
+    const uint32_t* vprim = nullptr;
+    const float* vnrm = nullptr;
+    const float* mt = nullptr;
+    const uint32_t* mprim = nullptr;
+    const float* mnrm = nullptr;
+    const float* mbary = nullptr;
+    const float* verts = nullptr;   // the mesh (device): vertices and index triples
+    const int32_t* idx = nullptr;
+    float light[3] = {0, 0, 0};
+    float intensity = 0.f;
+    int light_type = 0;             // 0 point, 1 directional
+    float* srays = nullptr;
+    float* sdist = nullptr;
+    float* stmax = nullptr;
+    const uint8_t* sv = nullptr;
+    const uint8_t* sm = nullptr;
+    const int16_t* vids = nullptr;  // per-voxel material ids (vx_grid_material_ids_device), nvids of them; null: MaterialObj{}
+    uint64_t nvids = 0;
+    const vx_material* vmat = nullptr;
+    uint64_t nvmat = 0;
+    const int32_t* mids = nullptr;  // per-triangle material ids (-1 none); null: MaterialObj{}
+    const vx_material* mmat = nullptr;
+    uint64_t nmmat = 0;
+    uint32_t* rgba = nullptr;
+    uint8_t* kind_out = nullptr;
+    uint8_t* shadowed_out = nullptr;
+};
+void launch_render_camera(const Camera& cam, Camera* dev, hipStream_t s);  // one thread: the camera block, from a kernel argument
+void launch_render_shadow_rays(const RenderParams& P, hipStream_t s);
+void launch_render_shade(const RenderParams& P, hipStream_t s);
+
 // single-voxel helpers
 void launch_set_bit(uint32_t* words, uint64_t idx, hipStream_t s);
 

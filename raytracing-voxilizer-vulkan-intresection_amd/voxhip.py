@@ -88,6 +88,19 @@ class BvhTraceArgs(C.Structure):
     _fields_ = [("base", TraceArgs), ("bary", C.c_void_p)]
 
 
+class RenderLight(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("intensity", C.c_float), ("type", C.c_int32)]
+
+
+class RenderDesc(C.Structure):
+    _fields_ = [("grid", C.c_void_p), ("octree", C.c_void_p), ("bvh", C.c_void_p), ("mesh", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class RenderArgs(C.Structure):
+    _fields_ = [("view_inverse", C.POINTER(C.c_float)), ("proj_inverse", C.POINTER(C.c_float)), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("light", C.POINTER(RenderLight)), ("rgba", C.c_void_p), ("kind", C.c_void_p), ("shadowed", C.c_void_p)]
+
+
 class VxError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__("%s: %s" % (STATUS_NAMES.get(status, status), msg))
@@ -112,6 +125,7 @@ SYMBOLS = [
     "vx_octree_trace", "vx_octree_trace_ex", "vx_octree_trace_ex_device",
     "vx_bvh_build", "vx_bvh_build_into", "vx_bvh_num_triangles", "vx_bvh_num_nodes", "vx_bvh_bytes", "vx_bvh_height", "vx_bvh_num_ill_conditioned", "vx_bvh_root_bounds",
     "vx_bvh_nodes", "vx_bvh_leaf_triangles", "vx_bvh_nodes_device", "vx_bvh_trace_ex_device", "vx_bvh_trace_ex", "vx_bvh_trace", "vx_bvh_free",
+    "vx_render_create", "vx_render_refresh", "vx_render_frame_device", "vx_render_frame", "vx_render_free",
     "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read", "vx_device_allocations",
     "vx_shard_words", "vx_shard_range",
 ]
@@ -258,6 +272,12 @@ def lib():
     L.vx_bvh_trace.argtypes = [vp, vp, C.c_uint64, C.c_float, C.c_float, vp, vp, u64p]
     L.vx_bvh_free.argtypes = [vp]
     L.vx_bvh_free.restype = None
+    L.vx_render_create.argtypes = [C.POINTER(RenderDesc), C.POINTER(vp)]
+    L.vx_render_refresh.argtypes = [vp]
+    L.vx_render_frame_device.argtypes = [vp, C.POINTER(RenderArgs)]
+    L.vx_render_frame.argtypes = [vp, C.POINTER(RenderArgs)]
+    L.vx_render_free.argtypes = [vp]
+    L.vx_render_free.restype = None
     L.vx_shard_words.argtypes = [C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p]
     L.vx_shard_words.restype = None
     L.vx_shard_range.argtypes = [C.c_uint64, C.c_int, C.c_int, u64p, u64p]
@@ -797,6 +817,104 @@ class Bvh:
         if self.h:
             lib().vx_bvh_free(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _stream_handle(stream):
+    """a torch.cuda.Stream, a raw hipStream_t (int) or None (the default stream) -> the pointer the C ABI takes"""
+    if stream is None:
+        return None
+    return getattr(stream, "cuda_stream", stream)
+
+
+class Renderer:
+    """vx_render_scene: whole frames on the device -- primary rays on the voxels (a Grid of kind GRID_BOOL, or an Octree) and the optional
+    triangle model (bvh + the mesh it was built from), shadow rays, shading, gamma.  The scene borrows voxels, bvh and mesh: keep them
+    alive while it is in use (this object holds references to them)."""
+
+    def __init__(self, voxels, bvh=None, mesh=None, stream=None):
+        d = RenderDesc()
+        if isinstance(voxels, Octree):
+            d.octree = voxels.h
+        else:
+            d.grid = voxels.h
+        d.bvh = bvh.h if bvh is not None else None
+        d.mesh = mesh.h if mesh is not None else None
+        d.stream = _stream_handle(stream)
+        self._torch_stream = stream if hasattr(stream, "cuda_stream") else None
+        self._keep = (voxels, bvh, mesh)
+        h = C.c_void_p()
+        _check(lib().vx_render_create(C.byref(d), C.byref(h)))
+        self.h = h
+
+    @staticmethod
+    def _args(camera, light):
+        vi, pi, w, h = camera
+        a = RenderArgs()
+        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi, np.float32).reshape(16)])
+        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi, np.float32).reshape(16)])
+        a.view_inverse, a.proj_inverse, a.width, a.height = cvi, cpi, int(w), int(h)
+        keep = [cvi, cpi]
+        if light is not None:
+            pos, intensity, kind = light
+            lt = RenderLight()
+            lt.position = (C.c_float * 3)(*[float(x) for x in np.asarray(pos, np.float32).reshape(3)])
+            lt.intensity, lt.type = float(np.float32(intensity)), int(kind)
+            a.light = C.pointer(lt)
+            keep.append(lt)
+        return a, keep
+
+    def render(self, camera, light=None, out=None, kind=None, shadowed=None):
+        """vx_render_frame_device, asynchronous on the scene's stream -> `out`, a device torch.uint8 tensor [H, W, 4] (RGBA8).
+        camera = (view_inv, proj_inv, W, H) as for trace_ex; light = (position[3], intensity, type 0 point / 1 directional), None = the
+        reference's default point light; kind / shadowed: optional device uint8 tensors of H*W elements."""
+        import torch
+        w, h = int(camera[2]), int(camera[3])
+        if out is None:
+            out = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
+        if out.dtype != torch.uint8 or out.numel() != 4 * w * h or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous device uint8 tensor of H*W*4 elements")
+        for x in (kind, shadowed):
+            if x is not None and (x.dtype != torch.uint8 or x.numel() != w * h or not x.is_contiguous() or not x.is_cuda):
+                raise ValueError("kind / shadowed must be contiguous device uint8 tensors of H*W elements")
+        a, keep = self._args(camera, light)
+        a.rgba = out.data_ptr()
+        a.kind = kind.data_ptr() if kind is not None else None
+        a.shadowed = shadowed.data_ptr() if shadowed is not None else None
+        _check(lib().vx_render_frame_device(self.h, C.byref(a)))
+        if self._torch_stream is not None:  # the caching allocator must not hand these out again before the frame has written them
+            for x in (out, kind, shadowed):
+                if x is not None:
+                    x.record_stream(self._torch_stream)
+        return out
+
+    def render_host(self, camera, light=None, want=("rgba",)):
+        """vx_render_frame on host buffers -> dict: rgba uint8[H, W, 4], and on request kind / shadowed uint8[H, W]."""
+        w, h = int(camera[2]), int(camera[3])
+        a, keep = self._args(camera, light)
+        out = {"rgba": np.zeros((h, w, 4), np.uint8)}
+        a.rgba = out["rgba"].ctypes.data
+        for k in ("kind", "shadowed"):
+            if k in want:
+                out[k] = np.zeros((h, w), np.uint8)
+                setattr(a, k, out[k].ctypes.data)
+        _check(lib().vx_render_frame(self.h, C.byref(a)))
+        return out
+
+    def refresh(self):
+        """vx_render_refresh: re-read the material tables after a source was rebuilt."""
+        _check(lib().vx_render_refresh(self.h))
+
+    def free(self):
+        if self.h:
+            lib().vx_render_free(self.h)
+            self.h = None
+        self._keep = None
 
     def __del__(self):
         try:
