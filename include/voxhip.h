@@ -355,6 +355,73 @@ vx_status vx_bvh_trace(const vx_bvh* b, const float* host_rays, uint64_t num_ray
                        float* host_t /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
 void vx_bvh_free(vx_bvh* b);
 
+/* ---- instanced triangle scenes: the reference's top-level acceleration structure (createTopLevelAS, hello_vulkan.cpp:760-790) over the
+ * models loadModel(filename, transform) appends (:197-240), as a TLAS built on the device over transformed instances of vx_bvh BLAS.
+ * Instance i: object-to-world M = transform (row-major 3x4 as VkTransformMatrixKHR, hello_vulkan.cpp:771: rows (m0 m1 m2 | m3),
+ * (m4 m5 m6 | m7), (m8 m9 m10 | m11)), blas = the index into the BLAS list given at build (gl_InstanceCustomIndexEXT -> objDesc),
+ * mask 0 = never hit (the instance mask against the reference's cullMask 0xFF).
+ * World-to-object W, computed on the device by the build and by every update, in float64 exactly in this order, then rounded to float32:
+ *     C = cofactors of the 3x3 A = (m0 m1 m2; m4 m5 m6; m8 m9 m10):
+ *         c00 = m5*m10 - m6*m9   c01 = m6*m8 - m4*m10   c02 = m4*m9 - m5*m8
+ *         c10 = m2*m9 - m1*m10   c11 = m0*m10 - m2*m8   c12 = m1*m8 - m0*m9
+ *         c20 = m1*m6 - m2*m5    c21 = m2*m4 - m0*m6    c22 = m0*m5 - m1*m4
+ *     det = (m0*c00 + m1*c01) + m2*c02;   inv[r][c] = c{c}{r} / det;   w3(row r) = -((inv[r][0]*m3 + inv[r][1]*m7) + inv[r][2]*m11)
+ *     W row r = (float)inv[r][0], (float)inv[r][1], (float)inv[r][2], (float)w3(row r)   (the inv used for w3 is the float64 one)
+ * An instance is INACTIVE (never hit) when mask == 0, blas >= num_blas, its BLAS has no triangles, det is 0 or not finite, or an entry of
+ * W is not finite.  vx_tlas_build / vx_tlas_update reject a blas index out of range and a non-finite transform with VX_ERR_INVALID_ARG;
+ * vx_tlas_update_device cannot report them and marks such instances inactive.  vx_tlas_world_to_object returns the W actually used.
+ * Per ray, for each active instance i and each triangle k of its BLAS, in float32, no contraction:
+ *     o' = ((w0*ox + w1*oy) + w2*oz) + w3,  d' = (w0*dx + w1*dy) + w2*dz   per row of W;
+ *     k tested on (o', d') with vx_bvh's pinned Moeller-Trumbore and the SAME tmin / tmax (t is parametric: the interval carries over).
+ *   t         the minimum accepted t over all active (instance, triangle) pairs, -1 on a miss;
+ *   instance  and prim: the lexicographically smallest (instance, triangle) pair reaching it; 0xFFFFFFFF / 0xFFFFFFFF on a miss;
+ *   bary      (u, v) of that pair; (0, 0) on a miss;
+ *   normal    the unit geometric normal of the WORLD-space triangle, vertices M*v = ((m0*x + m1*y) + m2*z) + m3 per row, then
+ *             cross(e1, e2) / sqrt(dot(., .)) as vx_bvh computes it, not flipped (rounding not pinned); zeros on a miss;
+ *   shadowed  (any_hit) and tmax_per_ray as for vx_bvh;
+ *   hits      the compacted list as for vx_bvh: vx_hit carries the ray, prim and t but NOT the instance -- request `instance` as well to
+ *             attribute a listed hit to its object.
+ * t, instance, prim and bary are bit-equal to the brute force over every pair: the TLAS only accelerates.  One exception is not covered
+ * by that argument: a BLAS's side list of ill-conditioned triangles (vx_bvh_num_ill_conditioned) is tested only when the ray
+ * reaches the instance's TLAS leaf, so a rounding-noise hit on such a sliver far outside the instance's widened world box may be pruned.
+ * vx_tlas_nodes returns the node array (vx_bvh_node records, root at 0, 2n-1 of them for n >= 1 instances): interior a, b = the children;
+ * leaf b = VX_BVH_LEAF | 1, a = the instance; min / max the widened world boxes (empty boxes, min > max, for inactive instances).
+ * Ownership: the TLAS BORROWS its BLAS handles; they must outlive it.  After a BLAS is rebuilt (vx_bvh_build_into) the caller calls
+ * vx_tlas_update* (as in Vulkan): an update re-reads every BLAS's root box, node and triangle arrays, height and side list, and rebuilds the
+ * TLAS over the given instances.  vx_tlas_update has copied the host array when it returns (the caller may reuse it at once) and does not
+ * wait for the rebuild; it stages through two pinned buffers in turn and waits on the host only for the copy of the update before the
+ * previous one; vx_tlas_update_device reads a DEVICE array of vx_instance on the TLAS's stream and neither synchronises nor copies
+ * to or from the host.  An update with the same instance count requests no device memory (vx_device_allocations unchanged).
+ * Streams: work runs on the TLAS's stream; build, update and trace make it wait for the work queued so far on the BLAS streams, and a
+ * trace makes those streams wait for it (a later vx_bvh_build_into cannot overwrite what it reads).  Argument rules of the trace functions
+ * as for vx_bvh_trace_ex*; any_hit together with instance is VX_ERR_INVALID_ARG too.  Zero instances give all misses. */
+typedef struct vx_tlas vx_tlas;
+typedef struct vx_instance {
+    float transform[12];  /* object-to-world, row-major 3x4 */
+    uint32_t blas;        /* index into the BLAS list given at build */
+    uint32_t mask;        /* 0 = never hit */
+} vx_instance;
+vx_status vx_tlas_build(const vx_bvh* const* blas, uint32_t num_blas, const vx_instance* host_instances, uint64_t num_instances, void* stream,
+                        vx_tlas** out);
+vx_status vx_tlas_update(vx_tlas* t, const vx_instance* host_instances, uint64_t num_instances);
+vx_status vx_tlas_update_device(vx_tlas* t, const vx_instance* dev_instances, uint64_t num_instances);  /* asynchronous, no host sync */
+uint64_t vx_tlas_num_instances(const vx_tlas* t);
+uint64_t vx_tlas_num_nodes(const vx_tlas* t);
+uint32_t vx_tlas_height(const vx_tlas* t);   /* the built tree's height (reads it back: synchronises the TLAS's stream) */
+uint64_t vx_tlas_bytes(const vx_tlas* t);    /* device bytes of the node array (32 B per node) and the per-instance records (100 B) */
+vx_status vx_tlas_world_to_object(const vx_tlas* t, float* host_out /* 12 per instance */, uint64_t capacity /* floats */);
+vx_status vx_tlas_nodes(const vx_tlas* t, void* host_out, uint64_t capacity_bytes, uint64_t* bytes);  /* capacity 0 = size query */
+typedef struct vx_tlas_trace_args {
+    vx_trace_args base;   /* normal = the world geometric normal above */
+    float* bary;          /* 2 f32 per ray (u, v), optional */
+    uint32_t* instance;   /* instance index, 0xFFFFFFFF on a miss, optional */
+} vx_tlas_trace_args;
+vx_status vx_tlas_trace_ex_device(const vx_tlas* t, const vx_tlas_trace_args* args);  /* device pointers, incl. compacted hits */
+vx_status vx_tlas_trace_ex(const vx_tlas* t, const vx_tlas_trace_args* args);         /* host pointers (staged), no `hits` */
+vx_status vx_tlas_trace(const vx_tlas* t, const float* host_rays, uint64_t num_rays, float tmin, float tmax, float* host_t /*NULL ok*/,
+                        uint32_t* host_instance /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
+void vx_tlas_free(vx_tlas* t);   /* waits for the TLAS's stream */
+
 /* ---- frames: the reference's per-frame dispatch (raytrace.rgen -> raytrace.rint / raytrace2.rchit on the voxels, raytrace.rchit on the
  * triangles, a shadow ray into the TLAS, raytrace.rmiss, post.frag) as one asynchronous sequence of kernels that leaves a shaded RGBA8
  * image in device memory.  Per pixel r = py*width + px:
@@ -406,6 +473,25 @@ typedef struct vx_render_args {
     uint8_t* shadowed;               /* optional: the OR of both shadow queries where the shading reads it (a hit with dot(N, L) > 0), 0 elsewhere */
 } vx_render_args;
 vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out);
+/* Instanced scenes: the triangles come from a vx_tlas (its BLAS list gives one mesh each, in the same order: vertices, index triples,
+ * per-triangle materials, objDesc[gl_InstanceCustomIndexEXT] of raytrace.rchit:52).  The frame is the sequence above with k_tlas_trace
+ * in place of the BVH's traversal for the primary and the shadow rays; the primary merge is unchanged; the triangle hit point is
+ * M * ((p0*b0 + p1*b1) + p2*b2) with M the instance's object-to-world rows in the pinned association ((m0*x + m1*y) + m2*z) + m3 (with M
+ * the identity, the BVH scene's expression bit for bit); the shading normal is vx_tlas's world geometric normal turned toward the ray;
+ * the material is the instance's mesh's.  At most one voxel source: a triangle-only scene (grid = octree = NULL) is allowed.  Streams:
+ * a frame waits for the work queued so far on the voxel source's and the TLAS's streams, and at its end makes those streams and every
+ * BLAS's stream wait for it -- an update enqueued after the frame cannot change what the frame reads, and a TLAS updated on its stream is
+ * picked up by the next frame.  A frame of a size already rendered allocates nothing and never synchronises, with or without TLAS updates
+ * of the same instance count between frames.  Errors: VX_ERR_INVALID_ARG for a null tlas or meshes, both voxel sources, a grid other than
+ * VX_GRID_BOOL, a null mesh, a mesh whose triangle count differs from its BLAS's, or handles on different devices. */
+typedef struct vx_render_tlas_desc {
+    const vx_grid* grid;            /* at most one of grid (VX_GRID_BOOL) and octree; neither = triangles only */
+    const vx_octree* octree;
+    const vx_tlas* tlas;
+    const vx_mesh* const* meshes;   /* one per BLAS of the TLAS, in its BLAS order */
+    void* stream;
+} vx_render_tlas_desc;
+vx_status vx_render_create_tlas(const vx_render_tlas_desc* desc, vx_render_scene** out);
 vx_status vx_render_refresh(vx_render_scene* s);                               /* re-read the material tables after a source was rebuilt */
 vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a);  /* asynchronous on the scene's stream */
 vx_status vx_render_frame(vx_render_scene* s, const vx_render_args* a);         /* host buffers: returns when they are written */

@@ -38,6 +38,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <sstream>
 #include <string>
 
 #include <hip/hip_runtime_api.h>
@@ -86,6 +87,7 @@ struct MeshScene {
     const int32_t* idx = nullptr;
     std::vector<MaterialObj> materials;  // the OBJ's records
     const int32_t* matIds = nullptr;     // per triangle, -1 = none (null: the file has no materials)
+    std::vector<vx_instance> instances;  // --instances: placements of the model (object-to-world, row-major 3x4); empty = the model once, as is
 };
 
 struct RenderOpts { std::vector<MaterialObj> materials; std::vector<int16_t> matIdx; std::string cameraDump; const MeshScene* mesh = nullptr; long frames = 0; };
@@ -105,12 +107,28 @@ int render_frames(const vx_grid* grid, const vx_octree* octree, const std::strin
         cf.write(reinterpret_cast<const char*>(vi), 64);
         cf.write(reinterpret_cast<const char*>(pi), 64);
     }
-    vx_render_desc d{};
-    d.grid = grid;
-    d.octree = octree;
-    if (ro.mesh) { d.bvh = ro.mesh->bvh; d.mesh = ro.mesh->model; }
     vx_render_scene* scene = nullptr;
-    vxdetail::check(vx_render_create(&d, &scene));
+    std::unique_ptr<vx_tlas, void (*)(vx_tlas*)> tlas(nullptr, vx_tlas_free);
+    if (ro.mesh && !ro.mesh->instances.empty()) {  // the model at every placement: a TLAS over its BVH (createTopLevelAS)
+        const vx_bvh* bl[1] = {ro.mesh->bvh};
+        vx_tlas* t = nullptr;
+        vxdetail::check(vx_tlas_build(bl, 1, ro.mesh->instances.data(), ro.mesh->instances.size(), nullptr, &t));
+        tlas.reset(t);
+        const vx_mesh* ms[1] = {ro.mesh->model};
+        vx_render_tlas_desc d{};
+        d.grid = grid;
+        d.octree = octree;
+        d.tlas = t;
+        d.meshes = ms;
+        vxdetail::check(vx_render_create_tlas(&d, &scene));
+        std::printf("[voxhip] %zu instances of the mesh, TLAS height %u\n", ro.mesh->instances.size(), vx_tlas_height(t));
+    } else {
+        vx_render_desc d{};
+        d.grid = grid;
+        d.octree = octree;
+        if (ro.mesh) { d.bvh = ro.mesh->bvh; d.mesh = ro.mesh->model; }
+        vxdetail::check(vx_render_create(&d, &scene));
+    }
     std::unique_ptr<vx_render_scene, void (*)(vx_render_scene*)> keep(scene, vx_render_free);
     const size_t n = (size_t)W * H;
     void *drgba = nullptr, *dkind = nullptr;
@@ -332,14 +350,14 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj] [--frames N]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
                      argv[0]);
         return 2;
     }
     const std::string path = argv[1];
     float vs = 0.f;
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
-    std::string grid = "bool", dumpFile, renderFile, matDump, cameraDump, meshFile;
+    std::string grid = "bool", dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false;
     int gpus = 1;
@@ -356,6 +374,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--dump-materials") && i + 1 < argc) matDump = argv[++i];
         else if (!std::strcmp(argv[i], "--camera-dump") && i + 1 < argc) cameraDump = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) meshFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--instances") && i + 1 < argc) instFile = argv[++i];
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
@@ -363,6 +382,10 @@ int main(int argc, char** argv)
     if (!meshFile.empty() && renderFile.empty()) { std::fprintf(stderr, "--mesh needs --render: the triangle model only takes part in the picture\n"); return 2; }
     if (!meshFile.empty() && (benchRuns > 0 || (grid != "bool" && grid != "octree"))) {
         std::fprintf(stderr, "--mesh renders with --grid bool or octree only, and not with --bench\n");
+        return 2;
+    }
+    if (!instFile.empty() && (renderFile.empty() || meshFile.empty() || frames < 1)) {
+        std::fprintf(stderr, "--instances places the --mesh model: it needs --render, --mesh and --frames\n");
         return 2;
     }
     if (frames > 0 && (renderFile.empty() || benchRuns > 0 || (grid != "bool" && grid != "octree"))) {
@@ -403,6 +426,23 @@ int main(int argc, char** argv)
                 meshScene.materials.push_back(o);
             }
             meshScene.matIds = vx_mesh_host_material_ids(m);
+            if (!instFile.empty()) {  // one instance per line: 12 floats, the row-major 3x4 object-to-world transform
+                std::ifstream in(instFile);
+                if (!in) { std::fprintf(stderr, "cannot read %s\n", instFile.c_str()); return 2; }
+                std::string line;
+                while (std::getline(in, line)) {
+                    if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+                    std::istringstream ls(line);
+                    vx_instance ins{};
+                    int k = 0;
+                    while (k < 12 && ls >> ins.transform[k]) ++k;
+                    if (k != 12) { std::fprintf(stderr, "%s: a line needs 12 floats (row-major 3x4)\n", instFile.c_str()); return 2; }
+                    ins.blas = 0;
+                    ins.mask = 0xFF;
+                    meshScene.instances.push_back(ins);
+                }
+                if (meshScene.instances.empty()) { std::fprintf(stderr, "%s: no instances\n", instFile.c_str()); return 2; }
+            }
             std::printf("[voxhip] mesh %s: %zu triangles in the BVH\n", meshFile.c_str(), (size_t)vx_bvh_num_triangles(b));
         }
         const MeshScene* msp = meshFile.empty() ? nullptr : &meshScene;

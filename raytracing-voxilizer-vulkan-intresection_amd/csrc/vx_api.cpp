@@ -2400,6 +2400,333 @@ void vx_bvh_free(vx_bvh* b)
     delete b;
 }
 
+// ---- instanced scenes: the reference's TLAS (createTopLevelAS, hello_vulkan.cpp:760-790) over vx_bvh BLAS (vx_tlas.hip) --------------
+struct vx_tlas {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<vx_bvh*> blas;            // borrowed
+    std::vector<vx::TlasBlas> tab;        // the table as last written to the device
+    uint64_t n = 0;
+    uint32_t levels = 1;                  // LDS stack entries of k_tlas_trace
+    DevBuf dinst, xf, w2o, iblas, ibox, keys_a, keys_b, sorttmp, child, parent, range, arrived, nodes, hgt, small, dtab, camera;
+    DevBuf* all[17] = {&dinst, &xf, &w2o, &iblas, &ibox, &keys_a, &keys_b, &sorttmp, &child, &parent, &range, &arrived, &nodes, &hgt, &small, &dtab, &camera};
+    // host staging of vx_tlas_update: two pinned buffers used in turn, so that an update waits (on the host) only for the copy out of
+    // the buffer it reuses, the one of the update before the previous one
+    vx_instance* pinned[2] = {nullptr, nullptr};
+    uint64_t pinned_cap[2] = {0, 0};
+    bool staged[2] = {false, false};      // ev_staged[k] marks the end of the last copy out of pinned[k]
+    int stage = 0;                        // the buffer the next host update fills
+    hipEvent_t ev_src = nullptr, ev_end = nullptr, ev_staged[2] = {nullptr, nullptr};
+};
+
+namespace {
+vx::TlasDev tlas_dev(const vx_tlas* t)
+{
+    vx::TlasDev d;
+    d.nodes = t->nodes.as<float>();
+    d.w2o = t->w2o.as<float>();
+    d.xf = t->xf.as<float>();
+    d.iblas = t->iblas.as<uint32_t>();
+    d.tab = t->dtab.as<vx::TlasBlas>();
+    d.small = t->small.as<uint32_t>();
+    d.ninst = (uint32_t)t->n;
+    d.levels = t->levels;
+    return d;
+}
+
+// the BLAS streams wait for / are waited on by the TLAS's stream
+vx_status tlas_wait_blas(vx_tlas* t)
+{
+    for (vx_bvh* b : t->blas) {
+        if (b->stream == t->stream) continue;
+        VX_HIP(hipEventRecord(t->ev_src, b->stream));
+        VX_HIP(hipStreamWaitEvent(t->stream, t->ev_src, 0));
+    }
+    return VX_OK;
+}
+vx_status tlas_fence_blas(vx_tlas* t)
+{
+    VX_HIP(hipEventRecord(t->ev_end, t->stream));
+    for (vx_bvh* b : t->blas)
+        if (b->stream != t->stream) VX_HIP(hipStreamWaitEvent(b->stream, t->ev_end, 0));
+    return VX_OK;
+}
+
+vx_status tlas_check_host(const vx_instance* in, uint64_t n, uint32_t nb)
+{
+    if (n && !in) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (n >= 0x7FFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^31 instances");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (in[i].blas >= nb) return fail(VX_ERR_INVALID_ARG, "instance " + std::to_string(i) + ": blas index out of range");
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(in[i].transform[k])) return fail(VX_ERR_INVALID_ARG, "instance " + std::to_string(i) + ": non-finite transform");
+    }
+    return VX_OK;
+}
+
+// rebuild from `in` (device pointer, n instances) on t->stream: no host synchronisation, no copy
+vx_status tlas_build_impl(vx_tlas* t, const vx_instance* in, uint64_t n)
+{
+    DeviceGuard dg(t->device);
+    hipStream_t s = t->stream;
+    VX_TRY(tlas_wait_blas(t));
+    // the BLAS table, re-read from the handles; written to the device (from kernel arguments) only when it changed
+    std::vector<vx::TlasBlas> tab(t->blas.size());
+    uint32_t hmax = 0;
+    for (size_t k = 0; k < t->blas.size(); ++k) {
+        const vx_bvh* b = t->blas[k];
+        vx::TlasBlas& e = tab[k];
+        std::memset(&e, 0, sizeof(e));
+        e.nodes = b->ntri ? b->nodes.as<float>() : nullptr;
+        e.tris = b->tris.as<float>();
+        e.ill = b->ill.as<uint32_t>();
+        e.nill = b->ntri ? b->nill : 0;
+        e.ntri = (uint32_t)b->ntri;
+        e.pad = vx::bvh_pad(b->extent, b->coord_max);
+        for (int a = 0; a < 3; ++a) { e.rmin[a] = b->root_min[a]; e.rmax[a] = b->root_max[a]; }
+        e.height = b->height;
+        hmax = std::max(hmax, b->ntri ? b->height : 0u);
+    }
+    if (!tab.empty()) {
+        VX_HIP(t->dtab.ensure(tab.size() * sizeof(vx::TlasBlas)));
+        if (t->dtab.fresh || tab.size() != t->tab.size() || std::memcmp(tab.data(), t->tab.data(), tab.size() * sizeof(vx::TlasBlas)) != 0) {
+            vx::launch_tlas_table(tab.data(), (uint32_t)tab.size(), t->dtab.as<vx::TlasBlas>(), s);
+            t->dtab.fresh = false;
+            t->tab = tab;
+        }
+    }
+    t->n = n;
+    t->levels = std::max(1u, vx::tlas_height_bound(n) + hmax);
+    if (n == 0) return VX_OK;
+    const uint32_t nn = (uint32_t)n, nall = 2 * nn - 1;
+    VX_HIP(t->xf.ensure((size_t)n * 48));
+    VX_HIP(t->w2o.ensure((size_t)n * 48));
+    VX_HIP(t->iblas.ensure((size_t)n * 4));
+    VX_HIP(t->ibox.ensure((size_t)n * 32));
+    VX_HIP(t->keys_a.ensure((size_t)n * 8));
+    VX_HIP(t->keys_b.ensure((size_t)n * 8));
+    const size_t tb = vx::sort_tmp_bytes(n);
+    VX_HIP(t->sorttmp.ensure(tb));
+    VX_HIP(t->child.ensure((size_t)n * 8));
+    VX_HIP(t->range.ensure((size_t)n * 8));
+    VX_HIP(t->parent.ensure((size_t)nall * 4));
+    VX_HIP(t->arrived.ensure((size_t)n * 4));
+    VX_HIP(t->nodes.ensure((size_t)nall * 32));
+    VX_HIP(t->hgt.ensure((size_t)nall * 4));
+    VX_HIP(t->small.ensure(8 * 4));
+    uint32_t* sm = t->small.as<uint32_t>();
+    VX_HIP(hipMemsetAsync(sm, 0xFF, 12, s));     // box min: the largest ordered value
+    VX_HIP(hipMemsetAsync(sm + 3, 0, 20, s));    // box max, the condition number, the height
+    vx::launch_tlas_prep(in, nn, t->dtab.as<vx::TlasBlas>(), (uint32_t)t->blas.size(), t->xf.as<float>(), t->w2o.as<float>(), t->iblas.as<uint32_t>(),
+                         t->ibox.as<float>(), sm, t->keys_a.as<uint64_t>(), s);
+    const uint64_t* keys =
+        vx::launch_sort_u64(t->keys_a.as<uint64_t>(), t->keys_b.as<uint64_t>(), n, 62, t->sorttmp.p, tb, s) == 0 ? t->keys_a.as<uint64_t>() : t->keys_b.as<uint64_t>();
+    vx::launch_tlas_tree(nn, keys, t->ibox.as<float>(), t->child.as<uint32_t>(), t->parent.as<uint32_t>(), t->range.as<uint32_t>(), t->arrived.as<uint32_t>(),
+                         t->nodes.as<float>(), t->hgt.as<uint32_t>(), sm, s);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+// host instances: staged through the TLAS's pinned buffer (free for the caller on return), then the device build
+vx_status tlas_update_host(vx_tlas* t, const vx_instance* in, uint64_t n)
+{
+    VX_TRY(tlas_check_host(in, n, (uint32_t)t->blas.size()));
+    DeviceGuard dg(t->device);
+    if (n) {
+        const int k = t->stage;
+        if (t->staged[k]) { VX_HIP(hipEventSynchronize(t->ev_staged[k])); t->staged[k] = false; }  // the copy out of this buffer is done
+        if (n > t->pinned_cap[k]) {
+            if (t->pinned[k]) VX_HIP(hipHostFree(t->pinned[k]));
+            t->pinned[k] = nullptr;
+            t->pinned_cap[k] = 0;
+            VX_HIP(hipHostMalloc((void**)&t->pinned[k], (size_t)n * sizeof(vx_instance), hipHostMallocDefault));
+            t->pinned_cap[k] = n;
+        }
+        std::memcpy(t->pinned[k], in, (size_t)n * sizeof(vx_instance));
+        VX_HIP(t->dinst.ensure((size_t)n * sizeof(vx_instance)));
+        VX_HIP(hipMemcpyAsync(t->dinst.p, t->pinned[k], (size_t)n * sizeof(vx_instance), hipMemcpyHostToDevice, t->stream));
+        VX_HIP(hipEventRecord(t->ev_staged[k], t->stream));
+        t->staged[k] = true;
+        t->stage = 1 - k;
+    }
+    return tlas_build_impl(t, t->dinst.as<vx_instance>(), n);
+}
+
+vx_status tlas_trace_common(vx_tlas* t, vx::TraceIO io, float* bary, uint32_t* inst)
+{
+    if (!io.nrays) return VX_OK;
+    if (io.cam) {
+        VX_HIP(t->camera.ensure(sizeof(vx::Camera)));
+        VX_HIP(hipMemcpyAsync(t->camera.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, t->stream));
+        VX_HIP(hipStreamSynchronize(t->stream));  // the host copy lives on the caller's stack
+        io.cam_dev = t->camera.as<vx::Camera>();
+    }
+    VX_TRY(tlas_wait_blas(t));
+    vx::launch_tlas_trace(tlas_dev(t), io, bary, inst, t->stream);
+    VX_HIP(hipGetLastError());
+    return tlas_fence_blas(t);
+}
+
+vx_status tlas_args_to_io(const vx_tlas_trace_args* a, vx::Camera* cam, vx::TraceIO* io)
+{
+    if (!a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    VX_TRY(args_to_io(&a->base, cam, io));
+    if (io->any_hit && (a->bary || a->instance)) return fail(VX_ERR_INVALID_ARG, "any_hit reports only `shadowed` (and an arbitrary accepted t)");
+    return VX_OK;
+}
+}  // namespace
+
+vx_status vx_tlas_build(const vx_bvh* const* blas, uint32_t num_blas, const vx_instance* host_instances, uint64_t num_instances, void* stream,
+                        vx_tlas** out)
+{
+    if (!out || (num_blas && !blas)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    for (uint32_t k = 0; k < num_blas; ++k)
+        if (!blas[k]) return fail(VX_ERR_INVALID_ARG, "null BLAS handle");
+    if (num_instances && !num_blas) return fail(VX_ERR_INVALID_ARG, "instances need at least one BLAS");
+    VX_TRY(tlas_check_host(host_instances, num_instances, num_blas));
+    const int dev = num_blas ? blas[0]->device : g_device;
+    VX_TRY(need_device(dev));
+    for (uint32_t k = 0; k < num_blas; ++k)
+        if (blas[k]->device != dev) return fail(VX_ERR_INVALID_ARG, "the BLAS handles live on different devices");
+    vx_tlas* t = new vx_tlas();
+    t->device = dev;
+    t->stream = (hipStream_t)stream;
+    for (uint32_t k = 0; k < num_blas; ++k) t->blas.push_back(const_cast<vx_bvh*>(blas[k]));
+    for (DevBuf* x : t->all) { x->dev = t->device; x->stream = t->stream; }
+    DeviceGuard dg(t->device);
+    hipError_t e = hipEventCreateWithFlags(&t->ev_src, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev_end, hipEventDisableTiming);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&t->ev_staged[k], hipEventDisableTiming);
+    vx_status st = e == hipSuccess ? tlas_update_host(t, host_instances, num_instances) : fail(VX_ERR_HIP, std::string("vx_tlas_build: ") + hipGetErrorString(e));
+    if (st == VX_OK) { const hipError_t se = hipStreamSynchronize(t->stream); if (se != hipSuccess) st = fail(VX_ERR_HIP, hipGetErrorString(se)); }
+    if (st != VX_OK) {
+        const std::string err = g_err;
+        vx_tlas_free(t);
+        return fail(st, err);
+    }
+    *out = t;
+    return VX_OK;
+}
+
+vx_status vx_tlas_update(vx_tlas* t, const vx_instance* host_instances, uint64_t num_instances)
+{
+    if (!t) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return tlas_update_host(t, host_instances, num_instances);
+}
+
+vx_status vx_tlas_update_device(vx_tlas* t, const vx_instance* dev_instances, uint64_t num_instances)
+{
+    if (!t || (num_instances && !dev_instances)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (num_instances >= 0x7FFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^31 instances");
+    return tlas_build_impl(t, dev_instances, num_instances);
+}
+
+uint64_t vx_tlas_num_instances(const vx_tlas* t) { return t ? t->n : 0; }
+uint64_t vx_tlas_num_nodes(const vx_tlas* t) { return t && t->n ? 2 * t->n - 1 : 0; }
+uint64_t vx_tlas_bytes(const vx_tlas* t) { return t ? vx_tlas_num_nodes(t) * 32 + t->n * 100 : 0; }
+
+uint32_t vx_tlas_height(const vx_tlas* t)
+{
+    if (!t || !t->n) return 0;
+    DeviceGuard dg(t->device);
+    uint32_t h = 0;
+    if (hipMemcpyAsync(&h, t->small.as<uint32_t>() + 7, 4, hipMemcpyDeviceToHost, t->stream) != hipSuccess) return 0;
+    if (hipStreamSynchronize(t->stream) != hipSuccess) return 0;
+    return h;
+}
+
+vx_status vx_tlas_world_to_object(const vx_tlas* t, float* host, uint64_t cap)
+{
+    if (!t || (!host && cap)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (cap < t->n * 12) return fail(VX_ERR_CAPACITY, "matrix buffer too small (12 floats per instance)");
+    if (!t->n) return VX_OK;
+    DeviceGuard dg(t->device);
+    VX_HIP(hipMemcpyAsync(host, t->w2o.p, (size_t)t->n * 48, hipMemcpyDeviceToHost, t->stream));
+    VX_HIP(hipStreamSynchronize(t->stream));
+    return VX_OK;
+}
+
+vx_status vx_tlas_nodes(const vx_tlas* t, void* host, uint64_t cap, uint64_t* bytes)
+{
+    if (!t || (!host && cap)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    const uint64_t nb = vx_tlas_num_nodes(t) * sizeof(vx_bvh_node);
+    if (bytes) *bytes = nb;
+    if (!cap || !nb) return VX_OK;
+    if (cap < nb) return fail(VX_ERR_CAPACITY, "node buffer too small");
+    DeviceGuard dg(t->device);
+    VX_HIP(hipMemcpyAsync(host, t->nodes.p, (size_t)nb, hipMemcpyDeviceToHost, t->stream));
+    VX_HIP(hipStreamSynchronize(t->stream));
+    return VX_OK;
+}
+
+vx_status vx_tlas_trace_ex_device(const vx_tlas* tc, const vx_tlas_trace_args* args)
+{
+    if (!tc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    vx_tlas* t = const_cast<vx_tlas*>(tc);
+    DeviceGuard dg(t->device);
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(tlas_args_to_io(args, &cam, &io));
+    return tlas_trace_common(t, io, args->bary, args->instance);
+}
+
+vx_status vx_tlas_trace_ex(const vx_tlas* tc, const vx_tlas_trace_args* args)
+{
+    if (!tc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    vx_tlas* t = const_cast<vx_tlas*>(tc);
+    DeviceGuard dg(t->device);
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(tlas_args_to_io(args, &cam, &io));
+    // bary / instance: staged here, the rest by the shared staging
+    DevBuf db, di;
+    for (DevBuf* x : {&db, &di}) { x->dev = t->device; x->stream = t->stream; }
+    hipError_t e = hipSuccess;
+    if (args->bary && io.nrays) e = db.ensure((size_t)io.nrays * 8 + 16);
+    if (e == hipSuccess && args->instance && io.nrays) e = di.ensure((size_t)io.nrays * 4 + 16);
+    vx_status st = e == hipSuccess ? trace_ex_staged(t->device, t->stream, &args->base, [&](const vx::TraceIO& sio) {
+        return tlas_trace_common(t, sio, args->bary ? db.as<float>() : nullptr, args->instance ? di.as<uint32_t>() : nullptr);
+    }) : VX_OK;
+    if (e == hipSuccess && st == VX_OK && io.nrays) {
+        if (args->bary) e = hipMemcpyAsync(args->bary, db.p, (size_t)io.nrays * 8, hipMemcpyDeviceToHost, t->stream);
+        if (e == hipSuccess && args->instance) e = hipMemcpyAsync(args->instance, di.p, (size_t)io.nrays * 4, hipMemcpyDeviceToHost, t->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+    }
+    db.release();
+    di.release();
+    if (st != VX_OK) return st;
+    VX_HIP(e);
+    return VX_OK;
+}
+
+vx_status vx_tlas_trace(const vx_tlas* tc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_instance,
+                        uint32_t* host_prim, uint64_t* num_hits)
+{
+    if (!tc || (nrays && !host_rays)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return trace_simple(host_rays, nrays, tmin, tmax, host_t, host_prim, num_hits, [&](const vx_trace_args* a) {
+        vx_tlas_trace_args ta{};
+        ta.base = *a;
+        ta.instance = host_instance;
+        return vx_tlas_trace_ex(tc, &ta);
+    });
+}
+
+void vx_tlas_free(vx_tlas* t)
+{
+    if (!t) return;
+    {
+        DeviceGuard dg(t->device);
+        (void)hipStreamSynchronize(t->stream);
+        for (DevBuf* x : t->all) x->release(/*in_flight=*/false);
+        for (vx_instance* p : t->pinned)
+            if (p) (void)hipHostFree(p);
+        for (hipEvent_t ev : {t->ev_src, t->ev_end, t->ev_staged[0], t->ev_staged[1]})
+            if (ev) (void)hipEventDestroy(ev);
+    }
+    delete t;
+}
+
 // ---- frames: the reference's per-frame raytrace dispatch as one asynchronous sequence on the scene's stream (vx_render.hip) ------------
 // camera block -> primary traversals (voxels, mesh) -> k_render_shadow_rays -> shadow traversals (voxels, mesh) -> k_render_shade.  The
 // scene owns every buffer the sequence touches, the walk's work counters included, so a frame never shares scratch with a trace the user
@@ -2411,8 +2738,10 @@ struct vx_render_scene {
     vx_octree* octree = nullptr;
     vx_bvh* bvh = nullptr;
     vx_mesh* mesh = nullptr;
-    DevBuf camera, counters, idxtmp, vt, vprim, vnrm, mt, mprim, mnrm, mbary, srays, sdist, stmax, sv, sm, vmat, mmat, mids, rgba, kind, shad;
-    DevBuf* all[21] = {&camera, &counters, &idxtmp, &vt, &vprim, &vnrm, &mt, &mprim, &mnrm, &mbary, &srays, &sdist, &stmax, &sv, &sm, &vmat, &mmat, &mids, &rgba, &kind, &shad};
+    vx_tlas* tlas = nullptr;              // instanced scenes (vx_render_create_tlas): the TLAS and one mesh per BLAS
+    std::vector<vx_mesh*> meshes;
+    DevBuf camera, counters, idxtmp, vt, vprim, vnrm, mt, mprim, mnrm, mbary, srays, sdist, stmax, sv, sm, vmat, mmat, mids, rgba, kind, shad, minst, imesh;
+    DevBuf* all[23] = {&camera, &counters, &idxtmp, &vt, &vprim, &vnrm, &mt, &mprim, &mnrm, &mbary, &srays, &sdist, &stmax, &sv, &sm, &vmat, &mmat, &mids, &rgba, &kind, &shad, &minst, &imesh};
     int phase = 0;              // which of the two walk counters the next k_walk launch draws from (launch_trace)
     uint64_t nvmat = 0, nmmat = 0;
     bool has_mids = false;
@@ -2463,15 +2792,26 @@ vx_status render_sources_check(const vx_render_scene* s)
 {
     if (s->grid && s->grid->kind != VX_GRID_BOOL) return fail(VX_ERR_INVALID_ARG, "the grid must be a VX_GRID_BOOL grid");
     if (s->bvh && s->bvh->ntri != s->mesh->nt) return fail(VX_ERR_INVALID_ARG, "the mesh's triangle count differs from the BVH's");
-    const int dev = s->grid ? s->grid->device : s->octree->device;
+    const int dev = s->grid ? s->grid->device : (s->octree ? s->octree->device : s->tlas->device);
     if ((s->bvh && s->bvh->device != dev) || (s->mesh && s->mesh->device != dev)) return fail(VX_ERR_INVALID_ARG, "the scene's handles live on different devices");
+    if (s->tlas) {
+        if (s->tlas->device != dev) return fail(VX_ERR_INVALID_ARG, "the scene's handles live on different devices");
+        if (s->meshes.size() != s->tlas->blas.size()) return fail(VX_ERR_INVALID_ARG, "one mesh per BLAS of the TLAS");
+        for (size_t k = 0; k < s->meshes.size(); ++k) {
+            if (!s->meshes[k]) return fail(VX_ERR_INVALID_ARG, "null mesh");
+            if (s->meshes[k]->nt != s->tlas->blas[k]->ntri) return fail(VX_ERR_INVALID_ARG, "mesh " + std::to_string(k) + ": its triangle count differs from its BLAS's");
+            if (s->meshes[k]->device != dev) return fail(VX_ERR_INVALID_ARG, "the scene's handles live on different devices");
+        }
+    }
     return VX_OK;
 }
 
+// the voxel source's stream (k = 0) and the triangles' (k = 1: the BVH's or the TLAS's); null when the scene has no such source
+bool has_source(const vx_render_scene* s, int k) { return k == 0 ? (s->grid || s->octree) : (s->bvh || s->tlas); }
 hipStream_t source_stream(const vx_render_scene* s, int k)
 {
     if (k == 0) return s->grid ? s->grid->stream : s->octree->stream;
-    return k == 1 ? s->bvh->stream : nullptr;
+    return s->bvh ? s->bvh->stream : s->tlas->stream;
 }
 
 vx_status render_upload_materials(vx_render_scene* s)
@@ -2495,6 +2835,39 @@ vx_status render_upload_materials(vx_render_scene* s)
         VX_HIP(hipMemcpyAsync(s->mids.p, s->mesh->tri_mat.data(), s->mesh->nt * 4, hipMemcpyHostToDevice, s->stream));
         s->has_mids = true;
     }
+    std::vector<vx_material> tm;  // instanced scenes: every mesh's materials and material ids, concatenated, and a table of the meshes
+    std::vector<int32_t> ti;
+    std::vector<vx::InstMesh> im(s->meshes.size());
+    std::vector<std::pair<int64_t, int64_t>> off(s->meshes.size(), {-1, 0});
+    for (size_t k = 0; k < s->meshes.size(); ++k) {
+        const vx_mesh* m = s->meshes[k];
+        off[k].second = (int64_t)tm.size();
+        tm.insert(tm.end(), m->materials.begin(), m->materials.end());
+        if (!m->tri_mat.empty() && m->tri_mat.size() == m->nt) {
+            off[k].first = (int64_t)ti.size();
+            ti.insert(ti.end(), m->tri_mat.begin(), m->tri_mat.end());
+        }
+    }
+    if (!tm.empty()) {
+        VX_HIP(s->mmat.ensure(tm.size() * sizeof(vx_material)));
+        VX_HIP(hipMemcpyAsync(s->mmat.p, tm.data(), tm.size() * sizeof(vx_material), hipMemcpyHostToDevice, s->stream));
+    }
+    if (!ti.empty()) {
+        VX_HIP(s->mids.ensure(ti.size() * 4));
+        VX_HIP(hipMemcpyAsync(s->mids.p, ti.data(), ti.size() * 4, hipMemcpyHostToDevice, s->stream));
+    }
+    for (size_t k = 0; k < s->meshes.size(); ++k) {
+        const vx_mesh* m = s->meshes[k];
+        im[k].verts = m->dv;
+        im[k].idx = m->di;
+        im[k].mids = off[k].first >= 0 ? s->mids.as<int32_t>() + off[k].first : nullptr;
+        im[k].mat = m->materials.empty() ? nullptr : s->mmat.as<vx_material>() + off[k].second;
+        im[k].nmat = m->materials.size();
+    }
+    if (!im.empty()) {
+        VX_HIP(s->imesh.ensure(im.size() * sizeof(vx::InstMesh)));
+        VX_HIP(hipMemcpyAsync(s->imesh.p, im.data(), im.size() * sizeof(vx::InstMesh), hipMemcpyHostToDevice, s->stream));
+    }
     VX_HIP(hipStreamSynchronize(s->stream));  // the host vectors may change after this call
     return VX_OK;
 }
@@ -2502,11 +2875,15 @@ vx_status render_upload_materials(vx_render_scene* s)
 // size the per-pixel buffers (pooled: a size already rendered requests nothing)
 vx_status render_buffers(vx_render_scene* s, uint64_t n, bool cull)
 {
-    VX_HIP(s->vt.ensure(n * 4 + 8));
-    VX_HIP(s->vprim.ensure(n * 4 + 8));
-    VX_HIP(s->vnrm.ensure(n * 12 + 8));
+    if (has_source(s, 0)) {
+        VX_HIP(s->vt.ensure(n * 4 + 8));
+        VX_HIP(s->vprim.ensure(n * 4 + 8));
+        VX_HIP(s->vnrm.ensure(n * 12 + 8));
+        VX_HIP(s->sv.ensure(n + 8));
+    }
     if (s->grid) VX_HIP(s->idxtmp.ensure(vx::trace_idx_bytes(s->grid->g, n)));
-    if (s->bvh) {
+    if (s->tlas) VX_HIP(s->minst.ensure(n * 4 + 8));
+    if (has_source(s, 1)) {
         VX_HIP(s->mt.ensure(n * 4 + 8));
         VX_HIP(s->mprim.ensure(n * 4 + 8));
         VX_HIP(s->mnrm.ensure(n * 12 + 8));
@@ -2516,7 +2893,6 @@ vx_status render_buffers(vx_render_scene* s, uint64_t n, bool cull)
     VX_HIP(s->srays.ensure(n * 24 + 8));
     VX_HIP(s->sdist.ensure(n * 4 + 8));
     if (cull) VX_HIP(s->stmax.ensure(n * 4 + 8));
-    VX_HIP(s->sv.ensure(n + 8));
     return VX_OK;
 }
 
@@ -2535,7 +2911,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     VX_TRY(render_buffers(s, n, cull));
     // start: the frame's stream waits for everything queued so far on the sources' streams
     for (int k = 0; k < 2; ++k) {
-        if (k == 1 && !s->bvh) continue;
+        if (!has_source(s, k)) continue;
         const hipStream_t ss = source_stream(s, k);
         if (ss == st) continue;
         VX_HIP(hipEventRecord(s->ev_src[k], ss));
@@ -2573,24 +2949,38 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
         else vx::launch_octree_trace(o->dnodes, o->items.as<uint64_t>(), o->nnodes == 0 ? 0 : o->nitems, o->bits, o->root_min, o->vs, q, st);
     };
     vx_bvh* b = s->bvh;
-    auto triangles = [&](const vx::TraceIO& q, float* bary) {
-        vx::launch_bvh_trace(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height, b->extent,
-                             b->coord_max, q, bary, st);
+    vx_tlas* tl = s->tlas;
+    auto triangles = [&](const vx::TraceIO& q, float* bary, uint32_t* inst) {
+        if (tl) vx::launch_tlas_trace(tlas_dev(tl), q, bary, inst, st);
+        else vx::launch_bvh_trace(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height,
+                                  b->extent, b->coord_max, q, bary, st);
     };
-    voxels(io);
-    if (b) {
+    const bool vox = has_source(s, 0);
+    if (vox) voxels(io);
+    if (b || tl) {
         vx::TraceIO mio = io;
         mio.t_out = s->mt.as<float>();
         mio.prim_out = s->mprim.as<uint32_t>();
         mio.normal_out = s->mnrm.as<float>();
-        triangles(mio, s->mbary.as<float>());
+        triangles(mio, s->mbary.as<float>(), tl ? s->minst.as<uint32_t>() : nullptr);
     }
     vx::RenderParams P;
     P.n = n;
     P.cam = s->camera.as<vx::Camera>();
-    P.vt = s->vt.as<float>();
-    P.vprim = s->vprim.as<uint32_t>();
-    P.vnrm = s->vnrm.as<float>();
+    P.vt = vox ? s->vt.as<float>() : nullptr;
+    P.vprim = vox ? s->vprim.as<uint32_t>() : nullptr;
+    P.vnrm = vox ? s->vnrm.as<float>() : nullptr;
+    if (tl) {
+        P.mt = s->mt.as<float>();
+        P.mprim = s->mprim.as<uint32_t>();
+        P.mnrm = s->mnrm.as<float>();
+        P.mbary = s->mbary.as<float>();
+        P.sm = s->sm.as<uint8_t>();
+        P.minst = s->minst.as<uint32_t>();
+        P.ixf = tl->xf.as<float>();
+        P.iblas = tl->iblas.as<uint32_t>();
+        P.imesh = s->imesh.as<vx::InstMesh>();
+    }
     if (b) {
         P.mt = s->mt.as<float>();
         P.mprim = s->mprim.as<uint32_t>();
@@ -2609,7 +2999,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     P.srays = s->srays.as<float>();
     P.sdist = s->sdist.as<float>();
     P.stmax = cull ? s->stmax.as<float>() : nullptr;
-    P.sv = s->sv.as<uint8_t>();
+    P.sv = vox ? s->sv.as<uint8_t>() : nullptr;
     const int16_t* vids = g ? vx_grid_material_ids_device(g) : nullptr;
     if (vids && s->nvmat) {
         P.vids = vids;
@@ -2620,7 +3010,8 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     P.rgba = rgba;
     P.kind_out = kind;
     P.shadowed_out = shadowed;
-    vx::launch_render_shadow_rays(P, st);
+    if (tl) vx::launch_render_shadow_rays_tlas(P, st);
+    else vx::launch_render_shadow_rays(P, st);
     // shadow rays: any-hit against the voxels and the mesh (rchit:108-122), tMax = the light distance
     vx::TraceIO sio;
     sio.rays = s->srays.as<float>();
@@ -2630,23 +3021,31 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     sio.tmax_per_ray = cull ? s->stmax.as<float>() : s->sdist.as<float>();
     sio.any_hit = true;
     sio.shadowed_out = s->sv.as<uint8_t>();
-    voxels(sio);
-    if (b) {
+    if (vox) voxels(sio);
+    if (b || tl) {
         sio.shadowed_out = s->sm.as<uint8_t>();
-        triangles(sio, nullptr);
+        triangles(sio, nullptr, nullptr);
     }
-    vx::launch_render_shade(P, st);
+    if (tl) vx::launch_render_shade_tlas(P, st);
+    else vx::launch_render_shade(P, st);
     VX_HIP(hipGetLastError());
     // end: later work on the sources' streams (a rebuild) waits for the frame's reads
     VX_HIP(hipEventRecord(s->ev_end, st));
     for (int k = 0; k < 2; ++k) {
-        if (k == 1 && !s->bvh) continue;
+        if (!has_source(s, k)) continue;
         const hipStream_t ss = source_stream(s, k);
         if (ss != st) VX_HIP(hipStreamWaitEvent(ss, s->ev_end, 0));
     }
+    if (tl)  // the BLAS a frame reads: a later vx_bvh_build_into waits for it too
+        for (vx_bvh* bb : tl->blas)
+            if (bb->stream != st && bb->stream != tl->stream) VX_HIP(hipStreamWaitEvent(bb->stream, s->ev_end, 0));
     return VX_OK;
 }
 }  // namespace
+
+namespace {
+vx_status render_create_common(vx_render_scene* s, vx_render_scene** out);
+}
 
 vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out)
 {
@@ -2660,9 +3059,31 @@ vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out)
     s->bvh = const_cast<vx_bvh*>(desc->bvh);
     s->mesh = const_cast<vx_mesh*>(desc->mesh);
     s->stream = (hipStream_t)desc->stream;
+    return render_create_common(s, out);
+}
+
+vx_status vx_render_create_tlas(const vx_render_tlas_desc* desc, vx_render_scene** out)
+{
+    if (!out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!desc || !desc->tlas || (!desc->meshes && desc->tlas->blas.size())) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (desc->grid && desc->octree) return fail(VX_ERR_INVALID_ARG, "at most one voxel source: grid or octree");
+    VX_TRY(need_device(desc->tlas->device));
+    vx_render_scene* s = new vx_render_scene();
+    s->grid = const_cast<vx_grid*>(desc->grid);
+    s->octree = const_cast<vx_octree*>(desc->octree);
+    s->tlas = const_cast<vx_tlas*>(desc->tlas);
+    for (size_t k = 0; k < s->tlas->blas.size(); ++k) s->meshes.push_back(const_cast<vx_mesh*>(desc->meshes[k]));
+    s->stream = (hipStream_t)desc->stream;
+    return render_create_common(s, out);
+}
+
+namespace {
+vx_status render_create_common(vx_render_scene* s, vx_render_scene** out)
+{
     const vx_status cs = render_sources_check(s);
     if (cs != VX_OK) { delete s; return cs; }
-    s->device = s->grid ? s->grid->device : s->octree->device;
+    s->device = s->grid ? s->grid->device : (s->octree ? s->octree->device : s->tlas->device);
     for (DevBuf* x : s->all) { x->dev = s->device; x->stream = s->stream; }
     auto bail = [&](vx_status st) {
         const std::string e = g_err;
@@ -2671,6 +3092,7 @@ vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out)
     };
     DeviceGuard dg(s->device);
     if (s->mesh) { const vx_status ms = mesh_to_device(s->mesh); if (ms != VX_OK) return bail(ms); }
+    for (vx_mesh* m : s->meshes) { const vx_status ms = mesh_to_device(m); if (ms != VX_OK) return bail(ms); }
     hipError_t e = s->camera.ensure(sizeof(vx::Camera));
     if (e == hipSuccess) e = s->counters.ensure(4 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemsetAsync(s->counters.p, 0, 4 * sizeof(unsigned long long), s->stream);  // the walk's counters start at zero
@@ -2682,6 +3104,7 @@ vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out)
     *out = s;
     return VX_OK;
 }
+}  // namespace
 
 vx_status vx_render_refresh(vx_render_scene* s)
 {

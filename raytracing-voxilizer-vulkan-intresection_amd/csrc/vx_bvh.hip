@@ -261,6 +261,15 @@ void launch_bvh_tree(const float* v, const int32_t* idx, uint64_t nv, uint32_t n
     VX_KL(k_bvh_alive, dim3((2 * n - 1 + kBuildBlock - 1) / kBuildBlock), dim3(kBuildBlock), 0, s, n, parent, range, max_leaf, alive);
 }
 
+// the traversal's absolute box widening of a BVH (launch_bvh_trace's), for the TLAS's per-BLAS table
+float bvh_pad(float extent, float coord_max) { return kBoxExt * extent + kBoxPos * coord_max + 1e-30f; }
+
+// the radix tree alone (the TLAS's build sorts its own keys; vx_tlas.hip): child / parent / range as in launch_bvh_tree, parent pre-filled
+void launch_bvh_karras(const uint64_t* keys, uint32_t n, uint32_t* child, uint32_t* parent, uint32_t* range, hipStream_t s)
+{
+    if (n > 1) VX_KL(k_bvh_karras, dim3((n - 1 + kBuildBlock - 1) / kBuildBlock), dim3(kBuildBlock), 0, s, keys, n, child, parent, range);
+}
+
 void launch_bvh_emit(uint32_t n, const uint32_t* alive, const uint32_t* newidx, const uint32_t* child, const uint32_t* range, uint32_t max_leaf,
                      const float* kbox, float* nodes, hipStream_t s)
 {
@@ -319,6 +328,9 @@ __device__ __forceinline__ bool box_enter(const float4& m0, const float4& m1, co
 
 }  // namespace
 
+// vx_blas.h restates this descent for k_tlas_trace (box_enter, Moeller-Trumbore, the stack walk, the normal): the two copies must change
+// together (tests/test_gpu_instances.py::test_tlas_identity_matches_bvh checks them against each other bit for bit).  This kernel keeps
+// its own copy because moving it onto the template changed its code generation.
 __global__ __launch_bounds__(kBvhBlock) void k_bvh_trace(BvhParams P)
 {
     extern __shared__ uint32_t bvh_lds[];  // [level][lane]: consecutive lanes on consecutive banks

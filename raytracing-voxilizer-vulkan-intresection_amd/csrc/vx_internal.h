@@ -187,10 +187,81 @@ void launch_bvh_emit(uint32_t n, const uint32_t* alive, const uint32_t* newidx, 
 void launch_bvh_trace(const float* nodes, const float* tris, const uint32_t* ill, uint32_t nill, uint32_t ntri, uint32_t height, float extent,
                       float coord_max, const TraceIO& io, float* bary_out, hipStream_t s);
 
+// Instanced scenes (vx_tlas.hip).  One record per BLAS of a TLAS, re-read from its vx_bvh at every build / update: node and triangle arrays,
+// side list, triangle count (0: instances of it are inactive), the box widening of its traversal and its root box.
+struct TlasBlas {
+    const float* nodes;
+    const float* tris;
+    const uint32_t* ill;
+    uint32_t nill;
+    uint32_t ntri;
+    float pad;
+    float rmin[3], rmax[3];
+    uint32_t height;
+};
+// Build / update, all on `s`: launch_tlas_prep (xf / w2o: 12 f32 per instance, iblas, ibox: 2 float4 per instance, small[0..6] initialised
+// to ~0 x3 / 0 x4, keys), launch_sort_u64 over 62 bits, launch_tlas_tree (nodes: 2n-1 vx_bvh_node records, hgt: 2n-1 heights, small[7] =
+// the root's height).  n >= 1.
+void launch_tlas_prep(const vx_instance* in, uint32_t n, const TlasBlas* tab, uint32_t nb, float* xf, float* w2o, uint32_t* iblas, float* ibox,
+                      uint32_t* small, uint64_t* keys, hipStream_t s);
+void launch_tlas_tree(uint32_t n, const uint64_t* keys, const float* ibox, uint32_t* child, uint32_t* parent, uint32_t* range, uint32_t* arrived,
+                      float* nodes, uint32_t* hgt, uint32_t* small, hipStream_t s);
+void launch_bvh_karras(const uint64_t* keys, uint32_t n, uint32_t* child, uint32_t* parent, uint32_t* range, hipStream_t s);  // vx_bvh.hip
+// the upper bound of a TLAS's height over n instances that the trace's stack is sized to: min(n - 1, 30 + ceil(log2 n))
+uint32_t tlas_height_bound(uint64_t n);
+float bvh_pad(float extent, float coord_max);  // vx_bvh.hip: the box widening launch_bvh_trace applies
+// the BLAS table (nb records) written on `s` from kernel arguments
+void launch_tlas_table(const TlasBlas* host, uint32_t nb, TlasBlas* dev, hipStream_t s);
+struct TlasDev {
+    const float* nodes = nullptr;
+    const float* w2o = nullptr;
+    const float* xf = nullptr;
+    const uint32_t* iblas = nullptr;
+    const TlasBlas* tab = nullptr;
+    const uint32_t* small = nullptr;
+    uint32_t ninst = 0;
+    uint32_t levels = 1;
+};
+// First hit per ray on the instances: io as for launch_bvh_trace (prim = triangle index in its mesh, normal = the world geometric normal);
+// bary_out (2 f32 per ray) and inst_out (instance, kNone on a miss) optional.
+void launch_tlas_trace(const TlasDev& T, const TraceIO& io, float* bary_out, uint32_t* inst_out, hipStream_t s);
+
+#if defined(__HIPCC__)
+// The unit geometric normal of triangle k (leaf-order position in its BLAS) of instance inst in WORLD space: vertices M*v in the pinned
+// association ((m0*x + m1*y) + m2*z) + m3 per row, then e1, e2, cross(e1, e2) / sqrt(dot) as vx_bvh computes it.
+__device__ __forceinline__ void tlas_world_normal(const TlasBlas* tab, const uint32_t* iblas, const float* xf, uint32_t inst, uint32_t k, float& n0,
+                                                  float& n1, float& n2)
+{
+    const float4* t = reinterpret_cast<const float4*>(tab[iblas[inst]].tris) + 3ull * k;
+    const float* m = xf + 12ull * inst;
+    float p[9];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const float4 q = t[v];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) p[3 * v + r] = ((m[4 * r] * q.x + m[4 * r + 1] * q.y) + m[4 * r + 2] * q.z) + m[4 * r + 3];
+    }
+    const float e1x = p[3] - p[0], e1y = p[4] - p[1], e1z = p[5] - p[2];
+    const float e2x = p[6] - p[0], e2y = p[7] - p[1], e2z = p[8] - p[2];
+    const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+    const float il = 1.0f / sqrtf((cx * cx + cy * cy) + cz * cz);
+    n0 = cx * il; n1 = cy * il; n2 = cz * il;
+}
+#endif
+
 // Frames (vx_render.hip): the per-pixel stages of vx_render_frame_device around the traversals.  n = width * height pixels, pixel
 // r = py * width + px.  Hit arrays as the traversals write them (mt / mprim / mnrm / mbary null without a mesh); srays (6 f32 per pixel),
 // sdist (the light distance: the shadow ray's tMax and the shading's 1/d^2) and, optional, stmax (sdist with 0 where no shading reads
 // the shadow flag) are written by the shadow-ray stage and read by the shading stage; sv / sm (optional) are the two shadow queries.
+// the mesh of each BLAS of an instanced scene (vx_render_create_tlas): vertices, index triples, per-triangle material ids (null: none)
+// and its material table
+struct InstMesh {
+    const float* verts;
+    const int32_t* idx;
+    const int32_t* mids;
+    const vx_material* mat;
+    uint64_t nmat;
+};
 struct RenderParams {
     uint64_t n = 0;
     const Camera* cam = nullptr;
@@ -218,6 +289,12 @@ struct RenderParams {
     const int32_t* mids = nullptr;  // per-triangle material ids (-1 none); null: MaterialObj{}
     const vx_material* mmat = nullptr;
     uint64_t nmmat = 0;
+    // instanced scenes (the _tlas launches): the hit's instance per pixel, the instances' object-to-world rows (12 f32 each), their BLAS,
+    // and the mesh of each BLAS; vt may be null (no voxel source: every voxel query misses)
+    const uint32_t* minst = nullptr;
+    const float* ixf = nullptr;
+    const uint32_t* iblas = nullptr;
+    const InstMesh* imesh = nullptr;
     uint32_t* rgba = nullptr;
     uint8_t* kind_out = nullptr;
     uint8_t* shadowed_out = nullptr;
@@ -225,6 +302,10 @@ struct RenderParams {
 void launch_render_camera(const Camera& cam, Camera* dev, hipStream_t s);  // one thread: the camera block, from a kernel argument
 void launch_render_shadow_rays(const RenderParams& P, hipStream_t s);
 void launch_render_shade(const RenderParams& P, hipStream_t s);
+// the same stages for an instanced scene (P.minst / ixf / iblas / imesh set): the triangle hit point M * ((p0*b0 + p1*b1) + p2*b2) and the
+// instance's mesh materials
+void launch_render_shadow_rays_tlas(const RenderParams& P, hipStream_t s);
+void launch_render_shade_tlas(const RenderParams& P, hipStream_t s);
 
 // single-voxel helpers
 void launch_set_bit(uint32_t* words, uint64_t idx, hipStream_t s);

@@ -64,12 +64,13 @@ __device__ __forceinline__ void shade_normal(bool tri, const RenderParams& P, ui
     if (tri && dot3(n0, n1, n2, d0, d1, d2) > 0.0f) { n0 = n0 * -1.0f; n1 = n1 * -1.0f; n2 = n2 * -1.0f; }
 }
 
-__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays(RenderParams P)
+template <bool kInst>
+__device__ __forceinline__ void render_shadow_rays(const RenderParams& P)
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= P.n) return;
     const Camera& cam = *P.cam;
-    const float vt = P.vt[r];
+    const float vt = (!kInst || P.vt) ? P.vt[r] : -1.0f;
     const bool tri = is_tri(vt, P.mt, r);
     float d0, d1, d2;
     host_dir(cam, r, d0, d1, d2);
@@ -80,14 +81,33 @@ __global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays(RenderParam
         l0 = P.light[0]; l1 = P.light[1]; l2 = P.light[2];
     } else if (tri) {          // rchit:67-68,78-83: from the position the barycentrics interpolate
         const uint32_t k = P.mprim[r];
-        const int32_t* ti = P.idx + 3 * (uint64_t)k;
+        const float* verts = P.verts;
+        const int32_t* idx = P.idx;
+        const float* m = nullptr;
+        if (kInst) {                // the instance's mesh, and its object-to-world rows (rchit:70, gl_ObjectToWorldEXT)
+            const uint32_t inst = P.minst[r];
+            const InstMesh& im = P.imesh[P.iblas[inst]];
+            verts = im.verts;
+            idx = im.idx;
+            m = P.ixf + 12ull * inst;
+        }
+        const int32_t* ti = idx + 3 * (uint64_t)k;
         const float b1 = P.mbary[2 * r], b2 = P.mbary[2 * r + 1], b0 = 1.0f - b1 - b2;
-        const float* p0 = P.verts + 3 * (uint64_t)ti[0];
-        const float* p1 = P.verts + 3 * (uint64_t)ti[1];
-        const float* p2 = P.verts + 3 * (uint64_t)ti[2];
-        l0 = P.light[0] - (p0[0] * b0 + p1[0] * b1 + p2[0] * b2);
-        l1 = P.light[1] - (p0[1] * b0 + p1[1] * b1 + p2[1] * b2);
-        l2 = P.light[2] - (p0[2] * b0 + p1[2] * b1 + p2[2] * b2);
+        const float* p0 = verts + 3 * (uint64_t)ti[0];
+        const float* p1 = verts + 3 * (uint64_t)ti[1];
+        const float* p2 = verts + 3 * (uint64_t)ti[2];
+        float h0 = p0[0] * b0 + p1[0] * b1 + p2[0] * b2;
+        float h1 = p0[1] * b0 + p1[1] * b1 + p2[1] * b2;
+        float h2 = p0[2] * b0 + p1[2] * b1 + p2[2] * b2;
+        if (kInst) {  // M * p in the pinned association ((m0*x + m1*y) + m2*z) + m3
+            const float x = h0, y = h1, z = h2;
+            h0 = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+            h1 = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+            h2 = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+        }
+        l0 = P.light[0] - h0;
+        l1 = P.light[1] - h1;
+        l2 = P.light[2] - h2;
     } else {
         l0 = P.light[0] - w0; l1 = P.light[1] - w1; l2 = P.light[2] - w2;
     }
@@ -110,6 +130,9 @@ __global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays(RenderParam
         P.stmax[r] = active ? dist : 0.0f;  // tmax 0 < tmin 0.001: no hit can be accepted
     }
 }
+
+__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays(RenderParams P) { render_shadow_rays<false>(P); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays_tlas(RenderParams P) { render_shadow_rays<true>(P); }
 
 // MaterialObj{} (obj_loader.h:32-43): the fields the shading reads
 __device__ __forceinline__ void load_material(const vx_material* tab, int64_t i, uint64_t n, float amb[3], float dif[3], float spc[3], float& shin, int& illum)
@@ -134,11 +157,12 @@ __device__ __forceinline__ uint32_t gamma8(float c)
     return (uint32_t)lroundf(g * 255.0f);
 }
 
-__global__ __launch_bounds__(kRenderBlock) void k_render_shade(RenderParams P)
+template <bool kInst>
+__device__ __forceinline__ void render_shade(const RenderParams& P)
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= P.n) return;
-    const float vt = P.vt[r];
+    const float vt = (!kInst || P.vt) ? P.vt[r] : -1.0f;
     const bool tri = is_tri(vt, P.mt, r);
     const bool hit = tri || vt > 0.f;
     float c[3] = {0.8f, 0.8f, 0.8f};  // rmiss:37 with the white clear colour of main.cpp:184
@@ -153,7 +177,11 @@ __global__ __launch_bounds__(kRenderBlock) void k_render_shade(RenderParams P)
         int64_t mi = -1;
         uint64_t nmat = 0;
         const vx_material* tab = nullptr;
-        if (tri) {  // rchit:92-93: the triangle's OBJ material
+        if (tri && kInst) {  // rchit:52,92-93: objDesc[gl_InstanceCustomIndexEXT] -> the instance's mesh's material of the triangle
+            const InstMesh& im = P.imesh[P.iblas[P.minst[r]]];
+            if (im.mids) mi = im.mids[P.mprim[r]];
+            tab = im.mat; nmat = im.nmat;
+        } else if (tri) {  // rchit:92-93: the triangle's OBJ material
             if (P.mids) mi = P.mids[P.mprim[r]];
             tab = P.mmat; nmat = P.nmmat;
         } else if (P.vids) {  // matIndices.i[gl_PrimitiveID] -> materials.m[matIdx]
@@ -196,6 +224,9 @@ __global__ __launch_bounds__(kRenderBlock) void k_render_shade(RenderParams P)
     if (P.kind_out) P.kind_out[r] = tri ? 2 : (hit ? 1 : 0);
 }
 
+__global__ __launch_bounds__(kRenderBlock) void k_render_shade(RenderParams P) { render_shade<false>(P); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shade_tlas(RenderParams P) { render_shade<true>(P); }
+
 }  // namespace
 
 void launch_render_camera(const Camera& cam, Camera* dev, hipStream_t s)
@@ -213,6 +244,18 @@ void launch_render_shade(const RenderParams& P, hipStream_t s)
 {
     if (!P.n) return;
     VX_KL(k_render_shade, dim3((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, P);
+}
+
+void launch_render_shadow_rays_tlas(const RenderParams& P, hipStream_t s)
+{
+    if (!P.n) return;
+    VX_KL(k_render_shadow_rays_tlas, dim3((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, P);
+}
+
+void launch_render_shade_tlas(const RenderParams& P, hipStream_t s)
+{
+    if (!P.n) return;
+    VX_KL(k_render_shade_tlas, dim3((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, P);
 }
 
 }  // namespace vx

@@ -88,12 +88,24 @@ class BvhTraceArgs(C.Structure):
     _fields_ = [("base", TraceArgs), ("bary", C.c_void_p)]
 
 
+class TlasTraceArgs(C.Structure):
+    _fields_ = [("base", TraceArgs), ("bary", C.c_void_p), ("instance", C.c_void_p)]
+
+
+# vx_instance: object-to-world (row-major 3x4), BLAS index, mask (0 = never hit)
+INSTANCE = np.dtype([("transform", np.float32, (12,)), ("blas", np.uint32), ("mask", np.uint32)])
+
+
 class RenderLight(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("intensity", C.c_float), ("type", C.c_int32)]
 
 
 class RenderDesc(C.Structure):
     _fields_ = [("grid", C.c_void_p), ("octree", C.c_void_p), ("bvh", C.c_void_p), ("mesh", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class RenderTlasDesc(C.Structure):
+    _fields_ = [("grid", C.c_void_p), ("octree", C.c_void_p), ("tlas", C.c_void_p), ("meshes", C.c_void_p), ("stream", C.c_void_p)]
 
 
 class RenderArgs(C.Structure):
@@ -125,7 +137,9 @@ SYMBOLS = [
     "vx_octree_trace", "vx_octree_trace_ex", "vx_octree_trace_ex_device",
     "vx_bvh_build", "vx_bvh_build_into", "vx_bvh_num_triangles", "vx_bvh_num_nodes", "vx_bvh_bytes", "vx_bvh_height", "vx_bvh_num_ill_conditioned", "vx_bvh_root_bounds",
     "vx_bvh_nodes", "vx_bvh_leaf_triangles", "vx_bvh_nodes_device", "vx_bvh_trace_ex_device", "vx_bvh_trace_ex", "vx_bvh_trace", "vx_bvh_free",
-    "vx_render_create", "vx_render_refresh", "vx_render_frame_device", "vx_render_frame", "vx_render_free",
+    "vx_tlas_build", "vx_tlas_update", "vx_tlas_update_device", "vx_tlas_num_instances", "vx_tlas_num_nodes", "vx_tlas_height", "vx_tlas_bytes",
+    "vx_tlas_world_to_object", "vx_tlas_nodes", "vx_tlas_trace_ex_device", "vx_tlas_trace_ex", "vx_tlas_trace", "vx_tlas_free",
+    "vx_render_create", "vx_render_create_tlas", "vx_render_refresh", "vx_render_frame_device", "vx_render_frame", "vx_render_free",
     "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read", "vx_device_allocations",
     "vx_shard_words", "vx_shard_range",
 ]
@@ -272,6 +286,22 @@ def lib():
     L.vx_bvh_trace.argtypes = [vp, vp, C.c_uint64, C.c_float, C.c_float, vp, vp, u64p]
     L.vx_bvh_free.argtypes = [vp]
     L.vx_bvh_free.restype = None
+    L.vx_tlas_build.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, C.POINTER(vp)]
+    L.vx_tlas_update.argtypes = [vp, vp, C.c_uint64]
+    L.vx_tlas_update_device.argtypes = [vp, vp, C.c_uint64]
+    for _f in ("vx_tlas_num_instances", "vx_tlas_num_nodes", "vx_tlas_bytes"):
+        getattr(L, _f).argtypes = [vp]
+        getattr(L, _f).restype = C.c_uint64
+    L.vx_tlas_height.argtypes = [vp]
+    L.vx_tlas_height.restype = C.c_uint32
+    L.vx_tlas_world_to_object.argtypes = [vp, vp, C.c_uint64]
+    L.vx_tlas_nodes.argtypes = [vp, vp, C.c_uint64, u64p]
+    L.vx_tlas_trace_ex.argtypes = [vp, C.POINTER(TlasTraceArgs)]
+    L.vx_tlas_trace_ex_device.argtypes = [vp, C.POINTER(TlasTraceArgs)]
+    L.vx_tlas_trace.argtypes = [vp, vp, C.c_uint64, C.c_float, C.c_float, vp, vp, vp, u64p]
+    L.vx_tlas_free.argtypes = [vp]
+    L.vx_tlas_free.restype = None
+    L.vx_render_create_tlas.argtypes = [C.POINTER(RenderTlasDesc), C.POINTER(vp)]
     L.vx_render_create.argtypes = [C.POINTER(RenderDesc), C.POINTER(vp)]
     L.vx_render_refresh.argtypes = [vp]
     L.vx_render_frame_device.argtypes = [vp, C.POINTER(RenderArgs)]
@@ -825,6 +855,148 @@ class Bvh:
             pass
 
 
+def instances(transforms, blas=None, mask=None):
+    """(transforms[n, 12], blas[n], mask[n]) -> an INSTANCE array (blas defaults to 0, mask to 0xFF)."""
+    tr = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 12)
+    out = np.zeros(tr.shape[0], dtype=INSTANCE)
+    out["transform"] = tr
+    out["blas"] = 0 if blas is None else np.asarray(blas, dtype=np.uint32)
+    out["mask"] = 0xFF if mask is None else np.asarray(mask, dtype=np.uint32)
+    return out
+
+
+def _as_instances(inst):
+    if isinstance(inst, np.ndarray) and inst.dtype == INSTANCE:
+        return np.ascontiguousarray(inst)
+    if isinstance(inst, tuple):
+        return instances(*inst)
+    return np.ascontiguousarray(np.asarray(inst), dtype=INSTANCE)
+
+
+class Tlas:
+    """vx_tlas handle: a top-level structure over transformed instances of Bvh handles (borrowed: keep them alive)."""
+
+    def __init__(self, blas_list, instances, stream=None):
+        self.blas = list(blas_list)
+        inst = _as_instances(instances)
+        arr = (C.c_void_p * max(len(self.blas), 1))(*[b.h for b in self.blas])
+        h = C.c_void_p()
+        _check(lib().vx_tlas_build(arr if self.blas else None, len(self.blas), inst.ctypes.data if len(inst) else None, len(inst),
+                                   _stream_handle(stream), C.byref(h)))
+        self.h = h
+
+    def update(self, instances=None, device_ptr=None, count=None):
+        """vx_tlas_update from host instances, or vx_tlas_update_device from a device array (a torch tensor of INSTANCE.itemsize-byte
+        records, or a raw pointer with `count`)."""
+        if device_ptr is not None:
+            if hasattr(device_ptr, "data_ptr"):
+                n = device_ptr.numel() * device_ptr.element_size() // INSTANCE.itemsize if count is None else count
+                _check(lib().vx_tlas_update_device(self.h, device_ptr.data_ptr(), n))
+            else:
+                _check(lib().vx_tlas_update_device(self.h, device_ptr, count))
+            return
+        inst = _as_instances(instances)
+        _check(lib().vx_tlas_update(self.h, inst.ctypes.data if len(inst) else None, len(inst)))
+
+    def num_instances(self):
+        return int(lib().vx_tlas_num_instances(self.h))
+
+    def num_nodes(self):
+        return int(lib().vx_tlas_num_nodes(self.h))
+
+    def height(self):
+        return int(lib().vx_tlas_height(self.h))
+
+    def memory_bytes(self):
+        return int(lib().vx_tlas_bytes(self.h))
+
+    def world_to_object(self):
+        n = self.num_instances()
+        out = np.zeros((max(n, 1), 12), dtype=np.float32)
+        _check(lib().vx_tlas_world_to_object(self.h, out.ctypes.data, n * 12))
+        return out[:n]
+
+    def nodes(self):
+        nb = C.c_uint64()
+        _check(lib().vx_tlas_nodes(self.h, None, 0, C.byref(nb)))
+        out = np.zeros(max(nb.value // BVH_NODE.itemsize, 1), dtype=BVH_NODE)
+        if nb.value:
+            _check(lib().vx_tlas_nodes(self.h, out.ctypes.data, nb.value, C.byref(nb)))
+        return out[:nb.value // BVH_NODE.itemsize]
+
+    def trace(self, rays, tmin=0.001, tmax=10000.0):
+        """vx_tlas_trace: first hit per ray -> (t, instance, prim, num_hits)."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        t = np.zeros(n, dtype=np.float32)
+        ins = np.zeros(n, dtype=np.uint32)
+        p = np.zeros(n, dtype=np.uint32)
+        nh = C.c_uint64()
+        _check(lib().vx_tlas_trace(self.h, r.ctypes.data, n, np.float32(tmin), np.float32(tmax), t.ctypes.data, ins.ctypes.data, p.ctypes.data,
+                                   C.byref(nh)))
+        return t, ins, p, nh.value
+
+    def trace_ex(self, rays=None, camera=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, any_hit=False,
+                 want=("t", "instance", "prim", "bary", "normal")):
+        """vx_tlas_trace_ex: host-buffer query -> dict of the requested outputs (t, instance, prim, bary, normal, shadowed)."""
+        ta = TlasTraceArgs()
+        a = ta.base
+        keep = []
+        if camera is not None:
+            vi, pi, w, h = camera
+            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
+            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
+            keep += [cvi, cpi]
+            a.view_inverse, a.proj_inverse, a.width, a.height = cvi, cpi, w, h
+            n = w * h
+        else:
+            r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+            keep.append(r)
+            a.rays, a.num_rays = r.ctypes.data, r.shape[0]
+            n = r.shape[0]
+        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
+        if tmax_per_ray is not None:
+            tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
+            keep.append(tm)
+            a.tmax_per_ray = tm.ctypes.data
+        out = {}
+        shapes = {"t": ((n,), np.float32), "instance": ((n,), np.uint32), "prim": ((n,), np.uint32), "bary": ((n, 2), np.float32),
+                  "normal": ((n, 3), np.float32), "shadowed": ((n,), np.uint8)}
+        for k in want:
+            out[k] = np.zeros(*shapes[k])
+        if "t" in out: a.t = out["t"].ctypes.data
+        if "prim" in out: a.prim = out["prim"].ctypes.data
+        if "normal" in out: a.normal = out["normal"].ctypes.data
+        if "shadowed" in out: a.shadowed = out["shadowed"].ctypes.data
+        if "bary" in out: ta.bary = out["bary"].ctypes.data
+        if "instance" in out: ta.instance = out["instance"].ctypes.data
+        _check(lib().vx_tlas_trace_ex(self.h, C.byref(ta)))
+        return out
+
+    def trace_device(self, rays_ptr, nrays, t_ptr=None, prim_ptr=None, instance_ptr=None, bary_ptr=None, normal_ptr=None, shadowed_ptr=None,
+                     hits_ptr=None, nhits_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None, any_hit=False):
+        """vx_tlas_trace_ex_device on device pointers."""
+        ta = TlasTraceArgs()
+        a = ta.base
+        a.rays, a.num_rays = rays_ptr, nrays
+        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
+        a.tmax_per_ray, a.t, a.prim, a.normal, a.shadowed = tmax_per_ray_ptr, t_ptr, prim_ptr, normal_ptr, shadowed_ptr
+        a.hits, a.num_hits = hits_ptr, nhits_ptr
+        ta.bary, ta.instance = bary_ptr, instance_ptr
+        _check(lib().vx_tlas_trace_ex_device(self.h, C.byref(ta)))
+
+    def free(self):
+        if self.h:
+            lib().vx_tlas_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def _stream_handle(stream):
     """a torch.cuda.Stream, a raw hipStream_t (int) or None (the default stream) -> the pointer the C ABI takes"""
     if stream is None:
@@ -851,6 +1023,29 @@ class Renderer:
         h = C.c_void_p()
         _check(lib().vx_render_create(C.byref(d), C.byref(h)))
         self.h = h
+
+    @classmethod
+    def from_tlas(cls, voxels=None, tlas=None, meshes=(), stream=None):
+        """vx_render_create_tlas: an instanced scene -- at most one voxel source (Grid of kind GRID_BOOL, Octree or None), a Tlas and one
+        Mesh per BLAS of it (vertices, indices, materials), in the Tlas's BLAS order."""
+        self = cls.__new__(cls)
+        d = RenderTlasDesc()
+        if isinstance(voxels, Octree):
+            d.octree = voxels.h
+        elif voxels is not None:
+            d.grid = voxels.h
+        d.tlas = tlas.h if tlas is not None else None
+        meshes = list(meshes)
+        arr = (C.c_void_p * max(len(meshes), 1))(*[m.h if m is not None else None for m in meshes])
+        d.meshes = C.cast(arr, C.c_void_p) if meshes else None
+        d.stream = _stream_handle(stream)
+        self._torch_stream = stream if hasattr(stream, "cuda_stream") else None
+        self._keep = (voxels, tlas, meshes)
+        self.h = None
+        h = C.c_void_p()
+        _check(lib().vx_render_create_tlas(C.byref(d), C.byref(h)))
+        self.h = h
+        return self
 
     @staticmethod
     def _args(camera, light):
