@@ -139,14 +139,25 @@ vx_status vx_mesh_set_materials(vx_mesh* m, const vx_material* materials, size_t
 void vx_mesh_free(vx_mesh* m);
 
 /* ---- voxelize: replaces VoxelBuilder<T,inParaell>::buildVoxelGrid (VoxelBuilder.hpp:338-542) ---------------
- * Limits (the reference has none besides memory): at most 2^21 cells per axis -- the bound the reference's own Octree has
- * (octTree.hpp:583-585); the per-triangle candidate ranges are 16 + 16 bits in the triangle record plus 5 + 5 high bits in an
- * extension word read only by grids with an axis above 65535 cells -- and 2^37 cells in total.  Beyond either vx_voxelize fails with
- * VX_ERR_CAPACITY, vx_octree_build with VX_ERR_MORTON_BITS and the reference's message.  Rays (vx_trace*) work on every grid the
+ * Limits (the reference has none besides memory): at most 2^21 cells per axis, 2^21 itself included -- the bound the reference's
+ * own Octree has (octTree.hpp:583-585); the per-triangle candidate ranges are 16 + 16 bits in the triangle record plus 5 + 6 high
+ * bits (start, count) in an extension word read only by grids with an axis above 65535 cells, so a triangle may span a whole
+ * 2^21-cell axis -- and 2^37 cells in total.  Beyond either vx_voxelize fails with VX_ERR_CAPACITY, vx_octree_build with
+ * VX_ERR_MORTON_BITS and the reference's message.  Rays (vx_trace*) work on every grid the
  * builds accept (grids with an axis above 65535 cells are walked by variants of the ray kernel that keep 32-bit cell coordinates). */
 vx_status vx_voxelize(const vx_mesh* mesh, float voxel_size, vx_grid_kind kind, const vx_voxelize_opts* opts /*NULL ok*/,
                       vx_grid** out);
-/* same, re-using an existing grid handle's device buffers (steady-state loops; no allocation when sizes repeat) */
+/* same, re-using an existing grid handle's device buffers (steady-state loops; no allocation when sizes repeat).
+ * A failed vx_voxelize_into leaves the grid in one of two defined states:
+ *  - errors found from the arguments alone (a NULL mesh or grid, a voxel size that is not finite and positive, a mesh on another
+ *    device, sat_variant, shard_rank / shard_world, a triangle range past the mesh, word_begin > word_end) or in the mesh itself
+ *    (with VX_VOXELIZE_MATERIALS, more than 32767 distinct materials; a failed upload of the mesh): nothing has been queued on the
+ *    grid and it still holds its previous build, unchanged through every reader;
+ *  - every other error (an axis above 2^21 cells, more than 2^37 cells, word_end past the new grid's word count, a counter
+ *    overflow, a HIP error during the build): the grid is EMPTY -- 0 x 0 x 0 cells, no words, 0 occupied voxels and setVoxel calls, an empty list
+ *    (a VX_VOXELIZE_LIST_ASYNC list of the previous build that was never written is dropped; a bound buffer holds 0 records), no
+ *    materials, and every ray misses.
+ * In both cases the next successful build on the handle gives what a build on a fresh handle gives. */
 vx_status vx_voxelize_into(const vx_mesh* mesh, float voxel_size, const vx_voxelize_opts* opts, vx_grid* grid);
 
 /* ---- the same build spread over several GPUs of one process (the call site on a multi-GPU node: hello_vulkan.cpp:677-683).

@@ -898,6 +898,28 @@ void vx_mesh_free(vx_mesh* m)
 }
 
 // ---- voxelize -------------------------------------------------------------------------------------------------
+// What a build that failed after it queued work leaves (voxhip.h, vx_voxelize_into): a grid of 0 x 0 x 0 cells -- no words, no
+// voxels, no setVoxel calls, an empty list and no materials; every ray misses.  Host state only: the error may be the device's.
+static void grid_set_empty(vx_grid* g, float vs)
+{
+    const float zero3[3] = {0.f, 0.f, 0.f};
+    const uint64_t zdim[3] = {0, 0, 0};
+    fill_params(g->g, zero3, vs, zdim);
+    for (int a = 0; a < 3; ++a) g->bbmin[a] = g->bbmax[a] = g->bbc[a] = 0.f;
+    g->triangles = 0;
+    g->coarse_valid = g->prefix_valid = false;
+    g->occupied_known = g->counts_valid = true;
+    g->occupied = g->set_calls = g->host_set_calls = 0;
+    g->vec_count = 0;
+    g->vec_in_bound = false;
+    g->list_deferred = false;  // (a list of the previous build that was never emitted: its records are gone with it)
+    g->has_materials = g->mat_pending = g->mat_gathered = false;
+    g->materials.clear();
+    g->mat_count = 0;
+}
+
+static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g);
+
 vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_opts* opts, vx_grid* g)
 {
     if (!mesh_c || !g) return fail(VX_ERR_INVALID_ARG, "null argument");
@@ -905,25 +927,37 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
     vx_mesh* mesh = const_cast<vx_mesh*>(mesh_c);
     VX_TRY(need_device(g->device));
     if (mesh->device != g->device) return fail(VX_ERR_INVALID_ARG, "mesh and grid live on different devices");
-    DeviceGuard dg(g->device);
-    VX_TRY(mesh_to_device(mesh));
     vx_voxelize_opts o{};
     if (opts) o = *opts;
+    // Errors the arguments alone tell (and the mesh's own: its upload, its material table): found before anything touches the
+    // handle, which keeps its previous build (voxhip.h)
+    if (o.sat_variant != 0 && o.sat_variant != 1) return fail(VX_ERR_INVALID_ARG, "sat_variant must be 0 or 1");
+    if (o.shard_world < 0 || (o.shard_world > 0 && (o.shard_rank < 0 || o.shard_rank >= o.shard_world))) return fail(VX_ERR_INVALID_ARG, "shard_rank / shard_world out of range");
+    if ((o.tri_begin || o.tri_end) && (o.tri_begin > o.tri_end || o.tri_end > mesh->nt)) return fail(VX_ERR_INVALID_ARG, "triangle shard out of range");
+    if (o.word_begin > o.word_end) return fail(VX_ERR_INVALID_ARG, "word shard out of range");
+    DeviceGuard dg(g->device);
+    VX_TRY(mesh_to_device(mesh));
+    if (o.flags & VX_VOXELIZE_MATERIALS) VX_TRY(mesh_material_values(mesh));
+    // ... every later error: the handle is left empty, whatever the build had queued or changed by then
+    const vx_status st = voxelize_build(mesh, vs, o, g);
+    if (st != VX_OK) grid_set_empty(g, vs);
+    return st;
+}
+
+static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g)
+{
     g->set_stream((hipStream_t)o.stream);
     hipStream_t s = g->stream;
     // a list emission of the previous build that is still to come reads the unit masks, hit bases and records this build overwrites (one
     // that was never queued is dropped: its list is about to be replaced)
     VX_HIP(g->list_resolve(/*drop_unqueued=*/true));
-    if (o.sat_variant != 0 && o.sat_variant != 1) return fail(VX_ERR_INVALID_ARG, "sat_variant must be 0 or 1");
     const bool want_mat = (o.flags & VX_VOXELIZE_MATERIALS) != 0;
     const bool list_async = (o.flags & VX_VOXELIZE_LIST_ASYNC) != 0 && g->kind == VX_GRID_VEC && !want_mat;  // (the material ids need the hit bases on the main stream)
-    if (want_mat) VX_TRY(mesh_material_values(mesh));
     g->has_materials = false;
     g->mat_pending = false;
     g->mat_gathered = false;
     g->materials.clear();
     g->mat_count = 0;
-    if (o.shard_world < 0 || (o.shard_world > 0 && (o.shard_rank < 0 || o.shard_rank >= o.shard_world))) return fail(VX_ERR_INVALID_ARG, "shard_rank / shard_world out of range");
     const bool by_rank = o.shard_world > 1 && !(o.word_begin || o.word_end);
 
     VX_HIP(ensure_small(g->small));
@@ -931,7 +965,6 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
     Small* ds = g->small.as<Small>();
     uint64_t tb = 0, te = mesh->nt;
     if (o.tri_begin || o.tri_end) {
-        if (o.tri_begin > o.tri_end || o.tri_end > mesh->nt) return fail(VX_ERR_INVALID_ARG, "triangle shard out of range");
         tb = o.tri_begin;
         te = o.tri_end;
     }
@@ -992,7 +1025,6 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
     for (int a = 0; a < 3; ++a) { g->bbmin[a] = ex.mn[a]; g->bbmax[a] = ex.mx[a]; g->bbc[a] = ex.ctr[a]; }
     VX_TRY(init_grid_storage(g, /*clear=*/false));
     const size_t mask_bytes = (size_t)(g->g.nwords + 2) * 4;
-    const bool words_fresh = g->words.fresh;
     if (g->words.fresh) { if (!cleared_tiled) cleared = 0; g->words.fresh = false; }  // a new block: the early clear hit the old one
     bool mask_is_clear = !cleared_tiled && cleared >= mask_bytes;
 
@@ -1000,7 +1032,7 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
     if (by_rank) {
         vx_shard_words(g->g.nwords, o.shard_rank, o.shard_world, &wb, &we, nullptr);
     } else if (sharded_words) {
-        if (o.word_begin > o.word_end || o.word_end > g->g.nwords) return fail(VX_ERR_INVALID_ARG, "word shard out of range");
+        if (o.word_end > g->g.nwords) return fail(VX_ERR_INVALID_ARG, "word shard out of range");
         wb = o.word_begin;
         we = o.word_end;
     }
@@ -1040,8 +1072,8 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
         const bool tw_clear = cleared_tiled && cleared >= tbytes && !g->twords.fresh;
         g->twords.fresh = false;
         if (!tw_clear) VX_HIP(hipMemsetAsync(g->twords.p, 0, tbytes, s));
-        if (words_fresh) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));  // (the two words behind the mask)
-        mask_is_clear = true;  // every word of the mask is written by launch_untile
+        mask_is_clear = true;  // every word of the mask and the two spare words behind it are written by launch_untile (or the brick kernel) --
+                               // or, when there is no unit to run, by the memset below
     }
     uint64_t U = 0;
     if (setup_queued) {
@@ -1059,7 +1091,10 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
         VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
         VX_TRY(setup_finish(ntri, g->ubase, g->btri, g->mail, s, &U));
     }
-    if (U == 0) return no_calls_materials();
+    if (U == 0) {  // (e.g. a word shard whose z slab holds no triangle): nothing will write the mask
+        if (tiled) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
+        return no_calls_materials();
+    }
     uint32_t* umask = nullptr;
     if (g->kind == VX_GRID_VEC || want_mat) {
         VX_HIP(g->umask.ensure((size_t)(U + 1) * 4));

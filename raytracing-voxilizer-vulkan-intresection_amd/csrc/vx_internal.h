@@ -18,7 +18,8 @@ struct __attribute__((aligned(16))) TriRec {
 static_assert(sizeof(TriRec) == 48, "TriRec must be 48 bytes");
 
 // Cells per axis: the reference's grids are bounded by memory only, its Octree by 21 Morton bits per axis (octTree.hpp:583-585);
-// candidate ranges are kept as 16 + 16 bits per axis in TriRec plus 5 + 5 high bits in a per-triangle extension word.
+// candidate ranges are kept as 16 + 16 bits per axis in TriRec plus 5 + 6 high bits in a per-triangle extension word (vx_math.h,
+// range_ext).  The limit is inclusive: a triangle may span all 2^21 cells of an axis.
 constexpr uint32_t kMaxDim = 1u << 21;
 constexpr uint32_t kCoarse = 8;        // cells per brick edge, bricks per block edge (ray traversal structure)
 constexpr uint32_t kCoarseShift = 3;

@@ -587,13 +587,13 @@ __global__ __launch_bounds__(256) void k_tri_setup(const float* __restrict__ ver
         const uint64_t uu = (uint64_t)nseg * ny * nz;
         u = uu > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)uu;
     }
-    // start | count << 16 per axis, low 16 bits each; bits 16..20 (cells 65536 .. 2^21 - 1) go to the extension word, which the unit
-    // kernels only read for grids that have such an axis
+    // start | count << 16 per axis, low 16 bits each; the high bits go to the extension word (range_ext), which the unit kernels
+    // only read for grids that have an axis above 65535 cells
     const uint32_t xs_ = nx ? (uint32_t)xs : 0u, ys_ = ny ? (uint32_t)ys : 0u, zs_ = nz ? (uint32_t)zs : 0u;
-    r.xr = (xs_ & 0xFFFFu) | (nx << 16);
-    r.yr = (ys_ & 0xFFFFu) | (ny << 16);
-    r.zr = (zs_ & 0xFFFFu) | (nz << 16);
-    if (ext) ext[t] = (xs_ >> 16) | ((nx >> 16) << 5) | ((ys_ >> 16) << 10) | ((ny >> 16) << 15) | ((zs_ >> 16) << 20) | ((nz >> 16) << 25);
+    r.xr = range_word(xs_, nx);
+    r.yr = range_word(ys_, ny);
+    r.zr = range_word(zs_, nz);
+    if (ext) ext[t] = range_ext(xs_, nx, ys_, ny, zs_);
     recs[t] = r;
     units[t] = u;
 }
@@ -647,9 +647,8 @@ __device__ __forceinline__ Unit decode_unit(const TriRec& r, uint32_t tri, uint3
 {
     Unit w;
     w.tri = tri;
-    const uint32_t xs = (r.xr & 0xFFFFu) | ((e & 31u) << 16), nx = (r.xr >> 16) | (((e >> 5) & 31u) << 16);
-    const uint32_t ys = (r.yr & 0xFFFFu) | (((e >> 10) & 31u) << 16), ny = (r.yr >> 16) | (((e >> 15) & 31u) << 16);
-    const uint32_t zs = (r.zr & 0xFFFFu) | (((e >> 20) & 31u) << 16);
+    uint32_t xs, nx, ys, ny, zs;
+    range_unpack(r.xr, r.yr, r.zr, e, xs, nx, ys, ny, zs);
     const uint32_t seg0 = xs >> 5;
     const uint32_t nseg = ((xs + nx - 1u) >> 5) - seg0 + 1u;
     uint32_t row, sx, zz, yy;
@@ -1071,7 +1070,7 @@ uint64_t tiled_mask_words(const uint32_t dim[3]) { return (uint64_t)((dim[2] + 3
 // One workgroup = four tile rows (ty, tz) x sixteen tiles along x = 4 KiB: one 16-byte load per thread (the four y words of one z of a
 // tile), sixteen-by-sixteen transposes in LDS, one 16-byte store per thread (four consecutive words of a row of the reference's mask).
 // [wb, we): the words this build owns (a word shard; the whole mask otherwise) -- every OTHER word of the mask is written as zero, as a
-// sharded build leaves it (the exchange fills those in).
+// sharded build leaves it (the exchange fills those in), and so are the two spare words behind it.
 __global__ __launch_bounds__(256) void k_untile(const uint32_t* __restrict__ tiled, uint32_t* __restrict__ words, uint32_t xw, uint32_t Y, uint32_t Z, uint32_t tiles_y,
                                                 uint32_t ntile_rows /*tiles_y * ceil(Z / 4)*/, uint32_t xchunks /*ceil(xw / 16)*/, uint64_t wb, uint64_t we)
 {
@@ -1079,6 +1078,7 @@ __global__ __launch_bounds__(256) void k_untile(const uint32_t* __restrict__ til
     const uint32_t q = threadIdx.x >> 6, l = threadIdx.x & 63u;
     const uint32_t grp = blockIdx.x / xchunks, x0 = (blockIdx.x - grp * xchunks) * 16u;
     const uint32_t tr = grp * 4u + q;
+    if (blockIdx.x == 0u && threadIdx.x < 2u) words[(uint64_t)xw * Y * Z + threadIdx.x] = 0u;  // the two spare words behind the mask (init_grid_storage)
     {
         const uint32_t xt = l >> 2, zz = l & 3u;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);

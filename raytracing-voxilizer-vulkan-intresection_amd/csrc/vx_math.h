@@ -212,4 +212,23 @@ VX_HD uint32_t compact_bits(uint64_t v)
     return (uint32_t)v;
 }
 
+// Candidate ranges of a triangle record (k_tri_setup writes them, decode_unit reads them).  TriRec's xr / yr / zr keep the low 16
+// bits of start and count per axis (range_word); the extension word keeps the high bits for grids with an axis above 65535 cells.
+// A start is below 2^21 (5 high bits), a count at most 2^21 (6 high bits: a triangle over a whole 2^21-cell axis).  nz is never
+// decoded (the unit count carries it), so it has no field.
+//   bits 0..4 xs | 5..10 nx | 11..15 ys | 16..21 ny | 22..26 zs
+VX_HD uint32_t range_word(uint32_t start, uint32_t count) { return (start & 0xFFFFu) | (count << 16); }
+VX_HD uint32_t range_ext(uint32_t xs, uint32_t nx, uint32_t ys, uint32_t ny, uint32_t zs)
+{
+    return (xs >> 16) | ((nx >> 16) << 5) | ((ys >> 16) << 11) | ((ny >> 16) << 16) | ((zs >> 16) << 22);
+}
+VX_HD void range_unpack(uint32_t xr, uint32_t yr, uint32_t zr, uint32_t e, uint32_t& xs, uint32_t& nx, uint32_t& ys, uint32_t& ny, uint32_t& zs)
+{
+    xs = (xr & 0xFFFFu) | ((e & 31u) << 16);
+    nx = (xr >> 16) | (((e >> 5) & 63u) << 16);
+    ys = (yr & 0xFFFFu) | (((e >> 11) & 31u) << 16);
+    ny = (yr >> 16) | (((e >> 16) & 63u) << 16);
+    zs = (zr & 0xFFFFu) | (((e >> 22) & 31u) << 16);
+}
+
 }  // namespace vx

@@ -84,6 +84,7 @@ __global__ __launch_bounds__(256) void k_build_bricks3(uint32_t* __restrict__ wo
     __shared__ uint32_t rows[64][17];              // [z*8 + y][32-voxel chunk of the 512]; padded against bank conflicts of the column reads
     __shared__ unsigned long long sz[64][9];       // [brick][z slab]: bit y*8 + x (padded)
     const uint64_t ngroups = (uint64_t)chunks_x * BY * BZ;
+    if (tiled && blockIdx.x == 0u && threadIdx.x < 2u) words[nwords + threadIdx.x] = 0u;  // the two spare words behind the mask (init_grid_storage)
     for (uint64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const uint32_t cx = (uint32_t)(grp % chunks_x);
         const uint64_t q = grp / chunks_x;
