@@ -136,6 +136,32 @@ size_t vx_mesh_num_materials(const vx_mesh* m);
 vx_status vx_mesh_materials(const vx_mesh* m, vx_material* out, size_t capacity);
 const int32_t* vx_mesh_host_material_ids(const vx_mesh* m); /* num_triangles entries; NULL when the mesh has no materials */
 vx_status vx_mesh_set_materials(vx_mesh* m, const vx_material* materials, size_t num_materials, const int32_t* tri_material_ids);
+/* Corner attributes and textures: what attribute shading of frames reads (vx_render_set_shading; common/obj_loader.cpp:49-121).  Positions,
+ * the BVH and the voxelizer never read them.
+ *   Corner k of triangle t sits at 3t + k in the mesh's index order (OBJ polygons fan as (0, k-1, k)): 3 f32 normal, 2 f32 uv.
+ *   vx_mesh_load_obj reads `vt u v` and `vn x y z` and the v/vt, v//vn, v/vt/vn corners (negative = relative): uv = (u, 1 - v); a corner
+ *   without vt gets (0, 0), without vn (0, 0, 0); a vt / vn index that is 0 or out of range leaves that attribute absent (never an error:
+ *   positions, triangles, materials and errors are those of the same file without attributes).  The mesh has corner normals when the file
+ *   has at least one vn line, corner uvs when it has at least one vt line.
+ *   Textures: one slot per material with a map_Kd, in material order (the file is its last token, options skipped, relative to the MTL's
+ *   directory).  vx_material.texture_id stays -1; the slot of each material is a separate array.  vx_mesh_load_obj reads no image:
+ *   vx_mesh_load_textures decodes every slot's file -- binary PPM (P6, maxval 255) and TGA (types 2 and 10, 24 or 32 bpp, origin bits
+ *   honoured) -> RGBA8, top row first -- and gives a missing, unreadable, truncated or unsupported file the reference's 1x1 (255, 0, 255, 255)
+ *   (hello_vulkan.cpp:318-327).  A slot without an image is shaded as that 1x1 magenta. */
+const float* vx_mesh_host_corner_normals(const vx_mesh* m);  /* 9 f32 per triangle; NULL when the mesh has none */
+const float* vx_mesh_host_corner_uvs(const vx_mesh* m);      /* 6 f32 per triangle; NULL when the mesh has none */
+/* copies num_triangles*9 normals / *6 uvs from host arrays (any kind of mesh); NULL removes that attribute */
+vx_status vx_mesh_set_attributes(vx_mesh* m, const float* corner_normals, const float* corner_uvs);
+size_t vx_mesh_num_textures(const vx_mesh* m);                          /* texture slots */
+const char* vx_mesh_texture_name(const vx_mesh* m, size_t slot);        /* the slot's file ("" when set by vx_mesh_set_texture); NULL out of range */
+/* the slot's RGBA8 image (width*height*4 bytes, top row first) and its size; NULL (size 0) when the slot has no image */
+const uint8_t* vx_mesh_host_texture(const vx_mesh* m, size_t slot, uint32_t* width, uint32_t* height);
+const int32_t* vx_mesh_host_material_textures(const vx_mesh* m);       /* num_materials slots (-1 none); NULL without materials */
+vx_status vx_mesh_set_material_textures(vx_mesh* m, const int32_t* slots, size_t num_materials); /* num_materials must match; any int32 */
+/* sets slot `slot` (0..65535; the slot list grows to it) to a width x height RGBA8 image (copied); width and height 1..16384, else
+ * VX_ERR_INVALID_ARG */
+vx_status vx_mesh_set_texture(vx_mesh* m, int32_t slot, uint32_t width, uint32_t height, const uint8_t* rgba8);
+vx_status vx_mesh_load_textures(vx_mesh* m);
 void vx_mesh_free(vx_mesh* m);
 
 /* ---- voxelize: replaces VoxelBuilder<T,inParaell>::buildVoxelGrid (VoxelBuilder.hpp:338-542) ---------------
@@ -442,7 +468,8 @@ void vx_tlas_free(vx_tlas* t);   /* waits for the TLAS's stream */
  *                 tMax = the light distance, any-hit against the voxels and the mesh; dir is computed as voxilizer --render computes it
  *                 on the host, and origin, direction and tMax are bit-equal to that function's;
  *   shading       raytrace2.rchit:53-137 (voxels: cube normal, the grid's per-voxel material or MaterialObj{}) / raytrace.rchit:49-143
- *                 (triangles: the geometric normal turned toward the ray, the OBJ material of the triangle or MaterialObj{}, no textures):
+ *                 (triangles: the geometric normal turned toward the ray, the OBJ material of the triangle or MaterialObj{}, no textures -- see
+ *                 vx_render_set_shading for vertex normals and textures):
  *                 diffuse + ambient (illum >= 1), specular (illum >= 2, lit and not shadowed), attenuation 0.3 when shadowed -- and for
  *                 a voxel facing away from the light, 1 for such a triangle; miss colour 0.8 (rmiss:37); gamma pow(clamp(c, 0, 1), 1/2.2)
  *                 rounded to nearest (post.frag:36); alpha 255.
@@ -503,7 +530,28 @@ typedef struct vx_render_tlas_desc {
     void* stream;
 } vx_render_tlas_desc;
 vx_status vx_render_create_tlas(const vx_render_tlas_desc* desc, vx_render_scene** out);
-vx_status vx_render_refresh(vx_render_scene* s);                               /* re-read the material tables after a source was rebuilt */
+vx_status vx_render_refresh(vx_render_scene* s);                               /* re-read the material and attribute tables of the sources */
+/* Attribute shading (flags = VX_RENDER_ATTRIBUTES; 0 = the shading above; other bits VX_ERR_INVALID_ARG), from the next frame, in BVH and
+ * TLAS scenes.  Voxel hits are shaded as above.  A triangle hit, in float32 with every association pinned (b0 = (1 - b1) - b2):
+ *   n   object space: the corner normals (n0*b0 + n1*b1) + n2*b2 when the mesh has them, else the face normal cross(p1 - p0, p2 - p0) =
+ *       (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x), e1 = p1 - p0, e2 = p2 - p0;
+ *   N   world space: W^T n for an instance, W its world-to-object 3x3 (vx_tlas_world_to_object), component j = (w0j*n0 + w1j*n1) + w2j*n2;
+ *       n itself in a BVH scene; then N = n / sqrtf((n0*n0 + n1*n1) + n2*n2), NOT turned toward the ray (raytrace.rchit:73-74: a back face is
+ *       lit as the reference lights it).  N zero or not finite: the default normal (the geometric normal turned toward the ray).  N is the
+ *       normal of the light test dot(N, L) > 0, of the shadow-ray compaction, of the diffuse and of the specular term.
+ *   tex when the triangle's material (none: MaterialObj{}, no texture) has a slot with 0 <= slot < vx_mesh_num_textures: uv = (uv0*b0 +
+ *       uv1*b1) + uv2*b2; per axis, w the width or height: x = u*w - 0.5, f = x - floorf(x), i0 = floorf(x) mod w (non-negative, repeat
+ *       addressing), i1 = (i0 + 1) mod w, and for a non-finite x or |x| >= 2^62 i0 = i1 = 0, f = 0; texels decoded by a 256-entry table of
+ *       the sRGB EOTF (c/12.92 for c <= 0.04045, else ((c + 0.055)/1.055)^2.4, computed in float64 and rounded to float32; R8G8B8A8_SRGB of
+ *       hello_vulkan.cpp:286-350); tex = (t00*(1-fx) + t10*fx)*(1-fy) + (t01*(1-fx) + t11*fx)*fy per rgb channel (t10: texel (i1x, i0y)),
+ *       1-f in float32, alpha ignored; the base level only, no mipmaps; float weights where a hardware sampler quantises them.  The diffuse
+ *       term, ambient already added, is multiplied by tex (rchit:99-104); the specular term is not.
+ * kind and shadowed are exact and rgba is within 1 LSB of a float32 restatement (powf of the specular term and of the gamma being the only
+ * difference); with one identity instance a TLAS scene's frame equals the BVH scene's bit for bit.  Corner attributes, textures, material
+ * slots and the table are uploaded at creation and by vx_render_refresh, never per frame; a frame in this mode allocates nothing at a size
+ * already rendered and neither synchronises nor copies to the host. */
+#define VX_RENDER_ATTRIBUTES 1u
+vx_status vx_render_set_shading(vx_render_scene* s, uint32_t flags);
 vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a);  /* asynchronous on the scene's stream */
 vx_status vx_render_frame(vx_render_scene* s, const vx_render_args* a);         /* host buffers: returns when they are written */
 void vx_render_free(vx_render_scene* s);                                        /* waits for the scene's stream */

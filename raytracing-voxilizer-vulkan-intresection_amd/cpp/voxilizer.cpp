@@ -30,6 +30,10 @@
 //                                       merge of voxel and triangle hits in kernels, one asynchronous sequence per frame), N frames from the
 //                                       reference camera; writes the last one and prints its hit counts and the device frame time (host wall
 //                                       between device-synchronised points, first frame excluded).  Refused with --bench.
+//   --render F.ppm --mesh M.obj --frames N --attributes
+//                                       the frames shade the mesh's triangles in attribute mode (vx_render_set_shading): interpolated vertex
+//                                       normals and the map_Kd textures of its materials (PPM / TGA, loaded by vx_mesh_load_textures), as
+//                                       raytrace.rchit:73-74,99-104; with or without --instances.  Refused without --frames or --mesh.
 //   --materials                         switch on the reference's commented-out material plumbing (usemtl / mtllib -> per-voxel
 //                                       material ids; VoxelBuilder.hpp:375-395): --render shades with them, --dump-materials FILE writes
 //                                       getMatIdx() as int16
@@ -88,6 +92,7 @@ struct MeshScene {
     std::vector<MaterialObj> materials;  // the OBJ's records
     const int32_t* matIds = nullptr;     // per triangle, -1 = none (null: the file has no materials)
     std::vector<vx_instance> instances;  // --instances: placements of the model (object-to-world, row-major 3x4); empty = the model once, as is
+    bool attributes = false;             // --attributes: the frames shade its triangles with vertex normals and diffuse textures
 };
 
 struct RenderOpts { std::vector<MaterialObj> materials; std::vector<int16_t> matIdx; std::string cameraDump; const MeshScene* mesh = nullptr; long frames = 0; };
@@ -130,6 +135,7 @@ int render_frames(const vx_grid* grid, const vx_octree* octree, const std::strin
         vxdetail::check(vx_render_create(&d, &scene));
     }
     std::unique_ptr<vx_render_scene, void (*)(vx_render_scene*)> keep(scene, vx_render_free);
+    if (ro.mesh && ro.mesh->attributes) vxdetail::check(vx_render_set_shading(scene, VX_RENDER_ATTRIBUTES));  // --attributes: vertex normals and textures
     const size_t n = (size_t)W * H;
     void *drgba = nullptr, *dkind = nullptr;
     hip_check(hipMalloc(&drgba, n * 4));
@@ -350,7 +356,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
                      argv[0]);
         return 2;
     }
@@ -359,7 +365,7 @@ int main(int argc, char** argv)
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
     std::string grid = "bool", dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
-    bool parallel = false, materials = false, logical = false;
+    bool parallel = false, materials = false, logical = false, attributes = false;
     int gpus = 1;
     long benchRuns = 0, frames = 0;
     for (int i = 3; i < argc; ++i) {
@@ -375,6 +381,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--camera-dump") && i + 1 < argc) cameraDump = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) meshFile = argv[++i];
         else if (!std::strcmp(argv[i], "--instances") && i + 1 < argc) instFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--attributes")) attributes = true;
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
@@ -382,6 +389,10 @@ int main(int argc, char** argv)
     if (!meshFile.empty() && renderFile.empty()) { std::fprintf(stderr, "--mesh needs --render: the triangle model only takes part in the picture\n"); return 2; }
     if (!meshFile.empty() && (benchRuns > 0 || (grid != "bool" && grid != "octree"))) {
         std::fprintf(stderr, "--mesh renders with --grid bool or octree only, and not with --bench\n");
+        return 2;
+    }
+    if (attributes && (renderFile.empty() || meshFile.empty() || frames < 1)) {
+        std::fprintf(stderr, "--attributes shades the --mesh model in device frames: it needs --render, --mesh and --frames\n");
         return 2;
     }
     if (!instFile.empty() && (renderFile.empty() || meshFile.empty() || frames < 1)) {
@@ -407,11 +418,13 @@ int main(int argc, char** argv)
             vx_mesh* m = nullptr;
             vxdetail::check(vx_mesh_load_obj(meshFile.c_str(), &m));
             meshModel.reset(m);
+            if (attributes) vxdetail::check(vx_mesh_load_textures(m));  // the map_Kd images (PPM / TGA; 1x1 magenta where that fails)
             vx_bvh* b = nullptr;
             vxdetail::check(vx_bvh_build(m, 0, nullptr, &b));
             meshBvh.reset(b);
             meshScene.bvh = b;
             meshScene.model = m;
+            meshScene.attributes = attributes;
             meshScene.verts = vx_mesh_host_vertices(m);
             meshScene.idx = vx_mesh_host_indices(m);
             std::vector<vx_material> recs(vx_mesh_num_materials(m));

@@ -2,7 +2,9 @@
 // All compute happens in the kernels of vx_kernels.hip; there is no CPU compute path in this library.
 #include "vx_internal.h"
 
+#include <cctype>
 #include <cmath>
+#include <cstdio>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -17,10 +19,7 @@
 
 #pragma clang fp contract(off)
 
-namespace vx {
-int load_obj(const char* path, std::vector<float>& verts, std::vector<int32_t>& tris, std::vector<int32_t>& tri_mat, std::vector<vx_material>& mats,
-             std::string& msg);
-}
+#include "vx_obj.h"
 
 namespace {
 
@@ -271,9 +270,110 @@ struct vx_mesh {
     DevBuf bv, bi;
     bool borrowed = false;
     bool uploaded = false;
+    // attribute shading (vx_render_set_shading): corner normals / uvs (9 / 6 f32 per triangle, empty: none), texture slots (file name, RGBA8
+    // image top row first; w = 0: no image yet) and the slot of every material (-1 none).  Host only; scenes upload them.
+    std::vector<float> cnrm, cuv;
+    struct Texture { std::string name; uint32_t w = 0, h = 0; std::vector<uint8_t> rgba; };
+    std::vector<Texture> tex;
+    std::vector<int32_t> mat_slot;
 };
 
 namespace {
+constexpr int32_t kMaxTextureSlots = 1 << 16;
+constexpr uint32_t kMaxTextureSide = 16384;
+
+// Texture files of vx_mesh_load_textures: binary PPM (P6, maxval 255) and TGA (types 2 and 10: uncompressed / RLE true colour, 24 or 32 bpp,
+// the origin bits honoured) -> RGBA8, top row first, as stbi_load returns an image.  false: missing, unreadable, truncated or unsupported.
+bool decode_ppm(const std::string& d, uint32_t& w, uint32_t& h, std::vector<uint8_t>& out)
+{
+    size_t i = 2;
+    uint64_t v[3];
+    for (int k = 0; k < 3; ++k) {
+        for (;;) {  // whitespace and comments between the header fields
+            while (i < d.size() && std::isspace((unsigned char)d[i])) ++i;
+            if (i < d.size() && d[i] == '#') { while (i < d.size() && d[i] != '\n') ++i; continue; }
+            break;
+        }
+        if (i >= d.size() || !std::isdigit((unsigned char)d[i])) return false;
+        v[k] = 0;
+        while (i < d.size() && std::isdigit((unsigned char)d[i]) && v[k] < 1000000) v[k] = v[k] * 10 + (uint64_t)(d[i++] - '0');
+    }
+    if (i >= d.size() || !std::isspace((unsigned char)d[i])) return false;
+    ++i;  // the single whitespace before the raster
+    if (v[2] != 255 || v[0] < 1 || v[0] > kMaxTextureSide || v[1] < 1 || v[1] > kMaxTextureSide) return false;
+    const size_t n = (size_t)v[0] * v[1];
+    if (d.size() - i < n * 3) return false;
+    w = (uint32_t)v[0];
+    h = (uint32_t)v[1];
+    out.resize(n * 4);
+    for (size_t p = 0; p < n; ++p) {
+        for (int c = 0; c < 3; ++c) out[4 * p + c] = (uint8_t)d[i + 3 * p + c];
+        out[4 * p + 3] = 255;
+    }
+    return true;
+}
+
+bool decode_tga(const std::string& d, uint32_t& w, uint32_t& h, std::vector<uint8_t>& out)
+{
+    if (d.size() < 18) return false;
+    const uint8_t* b = reinterpret_cast<const uint8_t*>(d.data());
+    const uint32_t idlen = b[0], cmap = b[1], type = b[2], bpp = b[16], desc = b[17];
+    const uint32_t tw = b[12] | (b[13] << 8), th = b[14] | (b[15] << 8);
+    if (cmap != 0 || (type != 2 && type != 10) || (bpp != 24 && bpp != 32)) return false;
+    if (tw < 1 || th < 1 || tw > kMaxTextureSide || th > kMaxTextureSide) return false;
+    const size_t bytes = bpp / 8, n = (size_t)tw * th;
+    size_t i = 18 + idlen;
+    std::vector<uint8_t> px(n * 4);  // file order
+    auto put = [&](size_t p, const uint8_t* src) {
+        px[4 * p] = src[2]; px[4 * p + 1] = src[1]; px[4 * p + 2] = src[0];  // BGR(A)
+        px[4 * p + 3] = bytes == 4 ? src[3] : 255;
+    };
+    if (type == 2) {
+        if (i > d.size() || d.size() - i < n * bytes) return false;
+        for (size_t p = 0; p < n; ++p) put(p, b + i + p * bytes);
+    } else {
+        size_t p = 0;
+        while (p < n) {
+            if (i >= d.size()) return false;
+            const uint32_t hdr = b[i++], cnt = (hdr & 0x7F) + 1;
+            if (p + cnt > n) return false;
+            if (hdr & 0x80) {
+                if (d.size() - i < bytes) return false;
+                for (uint32_t k = 0; k < cnt; ++k) put(p++, b + i);
+                i += bytes;
+            } else {
+                if (d.size() - i < cnt * bytes) return false;
+                for (uint32_t k = 0; k < cnt; ++k) put(p++, b + i + k * bytes);
+                i += cnt * bytes;
+            }
+        }
+    }
+    const bool top = (desc & 0x20) != 0, right = (desc & 0x10) != 0;  // origin: bottom-left unless bit 5 (top) / bit 4 (right) is set
+    w = tw;
+    h = th;
+    out.resize(n * 4);
+    for (uint32_t y = 0; y < th; ++y)
+        for (uint32_t x = 0; x < tw; ++x) {
+            const size_t sy = top ? y : th - 1 - y, sx = right ? tw - 1 - x : x;
+            std::memcpy(&out[4 * ((size_t)y * tw + x)], &px[4 * (sy * tw + sx)], 4);
+        }
+    return true;
+}
+
+bool decode_image(const std::string& path, uint32_t& w, uint32_t& h, std::vector<uint8_t>& out)
+{
+    if (path.empty()) return false;
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return false;
+    std::string d;
+    char buf[1 << 16];
+    size_t k;
+    while ((k = std::fread(buf, 1, sizeof(buf), f)) > 0) d.append(buf, k);
+    std::fclose(f);
+    if (d.size() >= 2 && d[0] == 'P' && d[1] == '6') return decode_ppm(d, w, h, out);
+    return decode_tga(d, w, h, out);
+}
+
 vx_material default_material()  // MaterialObj{} (common/obj_loader.h:32-43)
 {
     vx_material m;
@@ -814,12 +914,17 @@ vx_status vx_mesh_load_obj(const char* path, vx_mesh** out)
     if (!path || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
     vx_mesh* m = new vx_mesh();
     std::string msg;
-    const int rc = vx::load_obj(path, m->hv, m->hi, m->tri_mat, m->materials, msg);
+    vx::ObjAttributes attr;
+    const int rc = vx::load_obj(path, m->hv, m->hi, m->tri_mat, m->materials, msg, &attr);
     if (rc == 1) { delete m; return fail(VX_ERR_PATH, "Path does not exist!"); }                                    // VoxelBuilder.hpp:54-56
     if (rc == 2) { delete m; return fail(VX_ERR_PARSE, "Colud not get valid reader! Error message " + msg); }        // :63-65
     m->nv = m->hv.size() / 3;
     m->nt = m->hi.size() / 3;
     if (m->materials.empty()) m->tri_mat.clear();  // no mtllib: every id is -1
+    m->cnrm = std::move(attr.nrm);
+    m->cuv = std::move(attr.uv);
+    for (std::string& n : attr.tex_names) { m->tex.emplace_back(); m->tex.back().name = std::move(n); }
+    m->mat_slot = std::move(attr.mat_slot);
     m->device = g_device;
     *out = m;
     return VX_OK;
@@ -879,7 +984,59 @@ vx_status vx_mesh_set_materials(vx_mesh* m, const vx_material* mats, size_t n, c
             if (ids[t] < -1 || (ids[t] >= 0 && (size_t)ids[t] >= n)) return fail(VX_ERR_INVALID_ARG, "material id out of range");
     m->materials.assign(mats, mats + n);
     if (ids && n) m->tri_mat.assign(ids, ids + m->nt); else m->tri_mat.clear();
+    m->mat_slot.assign(n, -1);
     m->values_ready = false;
+    return VX_OK;
+}
+
+// ---- corner attributes and textures (attribute shading of frames) ----------------------------------------------
+const float* vx_mesh_host_corner_normals(const vx_mesh* m) { return (m && !m->cnrm.empty()) ? m->cnrm.data() : nullptr; }
+const float* vx_mesh_host_corner_uvs(const vx_mesh* m) { return (m && !m->cuv.empty()) ? m->cuv.data() : nullptr; }
+vx_status vx_mesh_set_attributes(vx_mesh* m, const float* corner_normals, const float* corner_uvs)
+{
+    if (!m) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (corner_normals) m->cnrm.assign(corner_normals, corner_normals + m->nt * 9); else m->cnrm.clear();
+    if (corner_uvs) m->cuv.assign(corner_uvs, corner_uvs + m->nt * 6); else m->cuv.clear();
+    return VX_OK;
+}
+size_t vx_mesh_num_textures(const vx_mesh* m) { return m ? m->tex.size() : 0; }
+const char* vx_mesh_texture_name(const vx_mesh* m, size_t slot) { return (m && slot < m->tex.size()) ? m->tex[slot].name.c_str() : nullptr; }
+const uint8_t* vx_mesh_host_texture(const vx_mesh* m, size_t slot, uint32_t* width, uint32_t* height)
+{
+    const bool ok = m && slot < m->tex.size() && m->tex[slot].w;
+    if (width) *width = ok ? m->tex[slot].w : 0;
+    if (height) *height = ok ? m->tex[slot].h : 0;
+    return ok ? m->tex[slot].rgba.data() : nullptr;
+}
+const int32_t* vx_mesh_host_material_textures(const vx_mesh* m) { return (m && !m->mat_slot.empty()) ? m->mat_slot.data() : nullptr; }
+vx_status vx_mesh_set_material_textures(vx_mesh* m, const int32_t* slots, size_t n)
+{
+    if (!m || (n && !slots)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (n != m->materials.size()) return fail(VX_ERR_INVALID_ARG, "one texture slot per material");
+    m->mat_slot.assign(slots, slots + n);
+    return VX_OK;
+}
+vx_status vx_mesh_set_texture(vx_mesh* m, int32_t slot, uint32_t width, uint32_t height, const uint8_t* rgba8)
+{
+    if (!m || !rgba8) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (slot < 0 || slot >= kMaxTextureSlots) return fail(VX_ERR_INVALID_ARG, "texture slot out of range");
+    if (width < 1 || width > kMaxTextureSide || height < 1 || height > kMaxTextureSide) return fail(VX_ERR_INVALID_ARG, "texture width and height must be 1..16384");
+    if ((size_t)slot >= m->tex.size()) m->tex.resize((size_t)slot + 1);
+    vx_mesh::Texture& t = m->tex[(size_t)slot];
+    t.w = width;
+    t.h = height;
+    t.rgba.assign(rgba8, rgba8 + (size_t)width * height * 4);
+    return VX_OK;
+}
+vx_status vx_mesh_load_textures(vx_mesh* m)
+{
+    if (!m) return fail(VX_ERR_INVALID_ARG, "null argument");
+    for (vx_mesh::Texture& t : m->tex) {
+        if (!decode_image(t.name, t.w, t.h, t.rgba)) {  // hello_vulkan.cpp:318-327: a 1x1 magenta image stands in
+            t.w = t.h = 1;
+            t.rgba = {255, 0, 255, 255};
+        }
+    }
     return VX_OK;
 }
 
@@ -2776,7 +2933,12 @@ struct vx_render_scene {
     vx_tlas* tlas = nullptr;              // instanced scenes (vx_render_create_tlas): the TLAS and one mesh per BLAS
     std::vector<vx_mesh*> meshes;
     DevBuf camera, counters, idxtmp, vt, vprim, vnrm, mt, mprim, mnrm, mbary, srays, sdist, stmax, sv, sm, vmat, mmat, mids, rgba, kind, shad, minst, imesh;
-    DevBuf* all[23] = {&camera, &counters, &idxtmp, &vt, &vprim, &vnrm, &mt, &mprim, &mnrm, &mbary, &srays, &sdist, &stmax, &sv, &sm, &vmat, &mmat, &mids, &rgba, &kind, &shad, &minst, &imesh};
+    // attribute shading: per-mesh records, corner normals / uvs, material slots, texture records and texels of every mesh (concatenated), the
+    // sRGB table, and the per-pixel normal scratch
+    DevBuf amesh, anrm, auv, aslot, atex, texels, srgb, nbuf;
+    DevBuf* all[31] = {&camera, &counters, &idxtmp, &vt, &vprim, &vnrm, &mt, &mprim, &mnrm, &mbary, &srays, &sdist, &stmax, &sv, &sm, &vmat, &mmat, &mids, &rgba, &kind, &shad, &minst, &imesh,
+                       &amesh, &anrm, &auv, &aslot, &atex, &texels, &srgb, &nbuf};
+    uint32_t shading = 0;       // vx_render_set_shading flags
     int phase = 0;              // which of the two walk counters the next k_walk launch draws from (launch_trace)
     uint64_t nvmat = 0, nmmat = 0;
     bool has_mids = false;
@@ -2907,6 +3069,84 @@ vx_status render_upload_materials(vx_render_scene* s)
     return VX_OK;
 }
 
+// the sRGB EOTF of c / 255 for every byte c, in float64, rounded to float32 (include/voxhip.h)
+void srgb_table(float out[256])
+{
+    for (int c = 0; c < 256; ++c) {
+        const double x = c / 255.0;
+        out[c] = (float)(x <= 0.04045 ? x / 12.92 : std::pow((x + 0.055) / 1.055, 2.4));
+    }
+}
+
+// attribute shading's tables: every mesh's corner attributes, material slots and textures (the texel pool with an {offset, w, h} record per
+// slot; a slot without an image gets the 1x1 magenta of a file that failed to load), one AttrMesh per mesh, and the sRGB table.  Staged once
+// at creation and by vx_render_refresh, never per frame.
+vx_status render_upload_attributes(vx_render_scene* s)
+{
+    std::vector<const vx_mesh*> ms;
+    if (s->mesh) ms.push_back(s->mesh);
+    for (const vx_mesh* m : s->meshes) ms.push_back(m);
+    std::vector<float> nrm, uv;
+    std::vector<int32_t> slot;
+    std::vector<vx::TexRec> tex;
+    std::vector<uint32_t> texels;
+    struct Off { int64_t nrm, uv; size_t slot, tex; };
+    std::vector<Off> off(ms.size());
+    for (size_t k = 0; k < ms.size(); ++k) {
+        const vx_mesh* m = ms[k];
+        off[k].nrm = m->cnrm.size() == m->nt * 9 && m->nt ? (int64_t)nrm.size() : -1;
+        if (off[k].nrm >= 0) nrm.insert(nrm.end(), m->cnrm.begin(), m->cnrm.end());
+        off[k].uv = m->cuv.size() == m->nt * 6 && m->nt ? (int64_t)uv.size() : -1;
+        if (off[k].uv >= 0) uv.insert(uv.end(), m->cuv.begin(), m->cuv.end());
+        off[k].slot = slot.size();
+        for (size_t i = 0; i < m->materials.size(); ++i) slot.push_back(i < m->mat_slot.size() ? m->mat_slot[i] : -1);
+        off[k].tex = tex.size();
+        for (const vx_mesh::Texture& t : m->tex) {
+            vx::TexRec r;
+            r.offset = texels.size();
+            if (t.w) {
+                r.w = t.w;
+                r.h = t.h;
+                const size_t cnt = (size_t)t.w * t.h;
+                texels.resize(texels.size() + cnt);
+                std::memcpy(texels.data() + r.offset, t.rgba.data(), cnt * 4);
+            } else {
+                r.w = r.h = 1;
+                texels.push_back(0xFFFF00FFu);  // (255, 0, 255, 255), R in the low byte
+            }
+            tex.push_back(r);
+        }
+    }
+    auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
+        if (!bytes) return hipSuccess;
+        hipError_t e = b.ensure(bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s->stream);
+        return e;
+    };
+    float lut[256];
+    srgb_table(lut);
+    VX_HIP(up(s->srgb, lut, sizeof(lut)));
+    VX_HIP(up(s->anrm, nrm.data(), nrm.size() * 4));
+    VX_HIP(up(s->auv, uv.data(), uv.size() * 4));
+    VX_HIP(up(s->aslot, slot.data(), slot.size() * 4));
+    VX_HIP(up(s->atex, tex.data(), tex.size() * sizeof(vx::TexRec)));
+    VX_HIP(up(s->texels, texels.data(), texels.size() * 4));
+    std::vector<vx::AttrMesh> am(ms.size());
+    for (size_t k = 0; k < ms.size(); ++k) {
+        const vx_mesh* m = ms[k];
+        am[k].nrm = off[k].nrm >= 0 ? s->anrm.as<float>() + off[k].nrm : nullptr;
+        am[k].uv = off[k].uv >= 0 ? s->auv.as<float>() + off[k].uv : nullptr;
+        am[k].nslot = m->materials.size();
+        am[k].slot = am[k].nslot ? s->aslot.as<int32_t>() + off[k].slot : nullptr;
+        am[k].ntex = (uint32_t)m->tex.size();
+        am[k].tex = am[k].ntex ? s->atex.as<vx::TexRec>() + off[k].tex : nullptr;
+        am[k].pad = 0;
+    }
+    VX_HIP(up(s->amesh, am.data(), am.size() * sizeof(vx::AttrMesh)));
+    VX_HIP(hipStreamSynchronize(s->stream));  // the host vectors go out of scope
+    return VX_OK;
+}
+
 // size the per-pixel buffers (pooled: a size already rendered requests nothing)
 vx_status render_buffers(vx_render_scene* s, uint64_t n, bool cull)
 {
@@ -2928,6 +3168,7 @@ vx_status render_buffers(vx_render_scene* s, uint64_t n, bool cull)
     VX_HIP(s->srays.ensure(n * 24 + 8));
     VX_HIP(s->sdist.ensure(n * 4 + 8));
     if (cull) VX_HIP(s->stmax.ensure(n * 4 + 8));
+    if ((s->shading & VX_RENDER_ATTRIBUTES) && has_source(s, 1)) VX_HIP(s->nbuf.ensure(n * 12 + 8));
     return VX_OK;
 }
 
@@ -3045,7 +3286,17 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     P.rgba = rgba;
     P.kind_out = kind;
     P.shadowed_out = shadowed;
-    if (tl) vx::launch_render_shadow_rays_tlas(P, st);
+    const bool attr = (s->shading & VX_RENDER_ATTRIBUTES) && (b || tl);  // voxel hits are shaded as by default: only triangles change
+    vx::AttrParams A;
+    if (attr) {
+        A.mesh = s->amesh.as<vx::AttrMesh>();
+        A.texels = s->texels.as<uint32_t>();
+        A.srgb = s->srgb.as<float>();
+        A.w2o = tl ? tl->w2o.as<float>() : nullptr;
+        A.nbuf = s->nbuf.as<float>();
+    }
+    if (attr) vx::launch_render_shadow_rays_attr(P, A, tl != nullptr, st);
+    else if (tl) vx::launch_render_shadow_rays_tlas(P, st);
     else vx::launch_render_shadow_rays(P, st);
     // shadow rays: any-hit against the voxels and the mesh (rchit:108-122), tMax = the light distance
     vx::TraceIO sio;
@@ -3061,7 +3312,8 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
         sio.shadowed_out = s->sm.as<uint8_t>();
         triangles(sio, nullptr, nullptr);
     }
-    if (tl) vx::launch_render_shade_tlas(P, st);
+    if (attr) vx::launch_render_shade_attr(P, A, tl != nullptr, st);
+    else if (tl) vx::launch_render_shade_tlas(P, st);
     else vx::launch_render_shade(P, st);
     VX_HIP(hipGetLastError());
     // end: later work on the sources' streams (a rebuild) waits for the frame's reads
@@ -3134,7 +3386,8 @@ vx_status render_create_common(vx_render_scene* s, vx_render_scene** out)
     for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&s->ev_src[k], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_end, hipEventDisableTiming);
     if (e != hipSuccess) return bail(fail(VX_ERR_HIP, std::string("vx_render_create: ") + hipGetErrorString(e)));
-    const vx_status ms = render_upload_materials(s);
+    vx_status ms = render_upload_materials(s);
+    if (ms == VX_OK) ms = render_upload_attributes(s);
     if (ms != VX_OK) return bail(ms);
     *out = s;
     return VX_OK;
@@ -3147,7 +3400,16 @@ vx_status vx_render_refresh(vx_render_scene* s)
     VX_TRY(render_sources_check(s));
     DeviceGuard dg(s->device);
     // the old tables may still be read by a frame in flight: queue the refresh behind it on the scene's stream (upload is stream-ordered)
-    return render_upload_materials(s);
+    VX_TRY(render_upload_materials(s));
+    return render_upload_attributes(s);
+}
+
+vx_status vx_render_set_shading(vx_render_scene* s, uint32_t flags)
+{
+    if (!s) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (flags & ~(uint32_t)VX_RENDER_ATTRIBUTES) return fail(VX_ERR_INVALID_ARG, "unknown shading flag");
+    s->shading = flags;
+    return VX_OK;
 }
 
 vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a)

@@ -307,6 +307,32 @@ void launch_render_shade(const RenderParams& P, hipStream_t s);
 // instance's mesh materials
 void launch_render_shadow_rays_tlas(const RenderParams& P, hipStream_t s);
 void launch_render_shade_tlas(const RenderParams& P, hipStream_t s);
+// Attribute shading (vx_render_set_shading(VX_RENDER_ATTRIBUTES)): what a triangle hit reads besides RenderParams, per mesh (one record for a
+// BVH scene, one per BLAS of an instanced scene): corner normals (9 f32 per triangle, null: the face normal), corner uvs (6 f32 per triangle,
+// null: (0, 0)), the texture slot of every material (nslot of them) and the mesh's textures (ntex records into the scene's texel pool).
+struct TexRec {
+    uint64_t offset;  // first texel (RGBA8 as uint32, R in the low byte) in the pool, rows top first
+    uint32_t w, h;
+};
+struct AttrMesh {
+    const float* nrm;
+    const float* uv;
+    const int32_t* slot;
+    uint64_t nslot;
+    const TexRec* tex;
+    uint32_t ntex;
+    uint32_t pad;
+};
+struct AttrParams {
+    const AttrMesh* mesh = nullptr;  // [0] in a BVH scene, [iblas[inst]] in an instanced one
+    const uint32_t* texels = nullptr;
+    const float* srgb = nullptr;     // 256 f32: the sRGB EOTF of c / 255, computed in float64 and rounded
+    const float* w2o = nullptr;      // instanced scenes: the TLAS's world-to-object rows (12 f32 per instance)
+    float* nbuf = nullptr;           // 3 f32 per pixel: the normal of a triangle hit, written by the shadow-ray stage, read by the shading
+};
+// the same stages with attribute shading; the default launches above keep their kernels (and ISA) unchanged
+void launch_render_shadow_rays_attr(const RenderParams& P, const AttrParams& A, bool inst, hipStream_t s);
+void launch_render_shade_attr(const RenderParams& P, const AttrParams& A, bool inst, hipStream_t s);
 
 // single-voxel helpers
 void launch_set_bit(uint32_t* words, uint64_t idx, hipStream_t s);

@@ -64,8 +64,62 @@ __device__ __forceinline__ void shade_normal(bool tri, const RenderParams& P, ui
     if (tri && dot3(n0, n1, n2, d0, d1, d2) > 0.0f) { n0 = n0 * -1.0f; n1 = n1 * -1.0f; n2 = n2 * -1.0f; }
 }
 
+// Attribute shading (include/voxhip.h): the unit normal N of a triangle hit -- the corner normals interpolated ((n0*b0 + n1*b1) +
+// n2*b2, or the face normal cross(p1 - p0, p2 - p0) without them), moved to world space by W^T n for an instance ((w0j*n0 + w1j*n1) + w2j*n2),
+// then n / sqrtf(dot(n, n)), NOT turned toward the ray (raytrace.rchit:73-74).  A zero-length or non-finite N: the default normal.
 template <bool kInst>
-__device__ __forceinline__ void render_shadow_rays(const RenderParams& P)
+__device__ __forceinline__ void attr_normal(const RenderParams& P, const AttrParams& A, uint64_t r, float d0, float d1, float d2, float& n0, float& n1,
+                                            float& n2)
+{
+    const uint32_t k = P.mprim[r];
+    const float* verts = P.verts;
+    const int32_t* idx = P.idx;
+    const AttrMesh* am = A.mesh;
+    uint32_t inst = 0;
+    if (kInst) {
+        inst = P.minst[r];
+        const uint32_t b = P.iblas[inst];
+        const InstMesh& im = P.imesh[b];
+        verts = im.verts;
+        idx = im.idx;
+        am = A.mesh + b;
+    }
+    const float b1 = P.mbary[2 * r], b2 = P.mbary[2 * r + 1], b0 = 1.0f - b1 - b2;
+    float x, y, z;
+    if (am->nrm) {
+        const float* c = am->nrm + 9ull * k;
+        x = (c[0] * b0 + c[3] * b1) + c[6] * b2;
+        y = (c[1] * b0 + c[4] * b1) + c[7] * b2;
+        z = (c[2] * b0 + c[5] * b1) + c[8] * b2;
+    } else {
+        const int32_t* ti = idx + 3 * (uint64_t)k;
+        const float* p0 = verts + 3 * (uint64_t)ti[0];
+        const float* p1 = verts + 3 * (uint64_t)ti[1];
+        const float* p2 = verts + 3 * (uint64_t)ti[2];
+        const float e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e1z = p1[2] - p0[2];
+        const float e2x = p2[0] - p0[0], e2y = p2[1] - p0[1], e2z = p2[2] - p0[2];
+        x = e1y * e2z - e1z * e2y;
+        y = e1z * e2x - e1x * e2z;
+        z = e1x * e2y - e1y * e2x;
+    }
+    if (kInst) {
+        const float* w = A.w2o + 12ull * inst;
+        const float ox = x, oy = y, oz = z;
+        x = (w[0] * ox + w[4] * oy) + w[8] * oz;
+        y = (w[1] * ox + w[5] * oy) + w[9] * oz;
+        z = (w[2] * ox + w[6] * oy) + w[10] * oz;
+    }
+    const float len = sqrtf((x * x + y * y) + z * z);
+    const float N0 = x / len, N1 = y / len, N2 = z / len;
+    if (isfinite(N0) && isfinite(N1) && isfinite(N2) && !(N0 == 0.0f && N1 == 0.0f && N2 == 0.0f)) {
+        n0 = N0; n1 = N1; n2 = N2;
+    } else {
+        shade_normal(true, P, r, d0, d1, d2, n0, n1, n2);
+    }
+}
+
+template <bool kInst, bool kAttr>
+__device__ __forceinline__ void render_shadow_rays(const RenderParams& P, const AttrParams& A)
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= P.n) return;
@@ -120,19 +174,27 @@ __device__ __forceinline__ void render_shadow_rays(const RenderParams& P)
     rp[1] = make_float2(w2, L0);
     rp[2] = make_float2(L1, L2);
     P.sdist[r] = dist;
+    float an0 = 0.f, an1 = 0.f, an2 = 0.f;
+    if (kAttr && tri) {  // computed once per pixel: the compaction below and the shading read the same N
+        attr_normal<kInst>(P, A, r, d0, d1, d2, an0, an1, an2);
+        A.nbuf[3 * r] = an0; A.nbuf[3 * r + 1] = an1; A.nbuf[3 * r + 2] = an2;
+    }
     if (P.stmax) {  // compaction by empty intervals: only a hit facing the light can read its shadow flag
         bool active = tri || vt > 0.f;
         if (active) {
             float n0, n1, n2;
-            shade_normal(tri, P, r, d0, d1, d2, n0, n1, n2);
+            if (kAttr && tri) { n0 = an0; n1 = an1; n2 = an2; }
+            else shade_normal(tri, P, r, d0, d1, d2, n0, n1, n2);
             active = dot3(n0, n1, n2, L0, L1, L2) > 0.0f;
         }
         P.stmax[r] = active ? dist : 0.0f;  // tmax 0 < tmin 0.001: no hit can be accepted
     }
 }
 
-__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays(RenderParams P) { render_shadow_rays<false>(P); }
-__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays_tlas(RenderParams P) { render_shadow_rays<true>(P); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays(RenderParams P) { render_shadow_rays<false, false>(P, AttrParams{}); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays_tlas(RenderParams P) { render_shadow_rays<true, false>(P, AttrParams{}); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays_attr(RenderParams P, AttrParams A) { render_shadow_rays<false, true>(P, A); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays_attr_tlas(RenderParams P, AttrParams A) { render_shadow_rays<true, true>(P, A); }
 
 // MaterialObj{} (obj_loader.h:32-43): the fields the shading reads
 __device__ __forceinline__ void load_material(const vx_material* tab, int64_t i, uint64_t n, float amb[3], float dif[3], float spc[3], float& shin, int& illum)
@@ -157,8 +219,62 @@ __device__ __forceinline__ uint32_t gamma8(float c)
     return (uint32_t)lroundf(g * 255.0f);
 }
 
+// one axis of the bilinear lookup with repeat addressing: x = u*w - 0.5, the two texels floor(x) mod w and the next, the weight f = x - floor(x);
+// x non-finite or |x| >= 2^62: texel 0 with weight 0
+__device__ __forceinline__ void tex_axis(float u, uint32_t w, uint32_t& i0, uint32_t& i1, float& f)
+{
+    const float x = u * (float)w - 0.5f;
+    if (!(fabsf(x) < 0x1p62f)) { i0 = i1 = 0; f = 0.0f; return; }
+    const float fl = floorf(x);
+    f = x - fl;
+    int64_t m;
+    if (fabsf(fl) < 0x1p31f) m = (int64_t)((int32_t)fl % (int32_t)w);  // the common case in 32-bit arithmetic: the same residue
+    else m = (int64_t)fl % (int64_t)w;
+    if (m < 0) m += w;
+    i0 = (uint32_t)m;
+    i1 = i0 + 1 == w ? 0u : i0 + 1;
+}
+
+// the texture of the triangle hit's material multiplies the diffuse term (raytrace.rchit:99-104): bilinear at the base level from RGBA8
+// texels decoded through the sRGB table (lut, in LDS), float weights, alpha ignored
 template <bool kInst>
-__device__ __forceinline__ void render_shade(const RenderParams& P)
+__device__ __forceinline__ void attr_texture(const RenderParams& P, const AttrParams& A, const float* lut, uint64_t r, int64_t mi, float diff[3])
+{
+    const AttrMesh* am = kInst ? A.mesh + P.iblas[P.minst[r]] : A.mesh;
+    if (mi < 0 || (uint64_t)mi >= am->nslot) return;
+    const int32_t slot = am->slot[mi];
+    if (slot < 0 || (uint32_t)slot >= am->ntex) return;
+    const uint32_t k = P.mprim[r];
+    const float b1 = P.mbary[2 * r], b2 = P.mbary[2 * r + 1], b0 = 1.0f - b1 - b2;
+    float u = 0.0f, v = 0.0f;
+    if (am->uv) {
+        const float* c = am->uv + 6ull * k;
+        u = (c[0] * b0 + c[2] * b1) + c[4] * b2;
+        v = (c[1] * b0 + c[3] * b1) + c[5] * b2;
+    } else {
+        u = (0.0f * b0 + 0.0f * b1) + 0.0f * b2;
+        v = u;
+    }
+    const TexRec t = am->tex[slot];
+    uint32_t x0, x1, y0, y1;
+    float fx, fy;
+    tex_axis(u, t.w, x0, x1, fx);
+    tex_axis(v, t.h, y0, y1, fy);
+    const uint32_t* base = A.texels + t.offset;
+    const uint32_t t00 = base[(uint64_t)y0 * t.w + x0], t10 = base[(uint64_t)y0 * t.w + x1];
+    const uint32_t t01 = base[(uint64_t)y1 * t.w + x0], t11 = base[(uint64_t)y1 * t.w + x1];
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t sh = 8 * c;
+        const float a = lut[(t00 >> sh) & 255u] * gx + lut[(t10 >> sh) & 255u] * fx;
+        const float b = lut[(t01 >> sh) & 255u] * gx + lut[(t11 >> sh) & 255u] * fx;
+        diff[c] = diff[c] * (a * gy + b * fy);
+    }
+}
+
+template <bool kInst, bool kAttr>
+__device__ __forceinline__ void render_shade(const RenderParams& P, const AttrParams& A, const float* lut)
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= P.n) return;
@@ -169,7 +285,8 @@ __device__ __forceinline__ void render_shade(const RenderParams& P)
     if (hit) {
         float d0, d1, d2, n0, n1, n2;
         host_dir(*P.cam, r, d0, d1, d2);
-        shade_normal(tri, P, r, d0, d1, d2, n0, n1, n2);
+        if (kAttr && tri) { n0 = A.nbuf[3 * r]; n1 = A.nbuf[3 * r + 1]; n2 = A.nbuf[3 * r + 2]; }
+        else shade_normal(tri, P, r, d0, d1, d2, n0, n1, n2);
         const float2* rp = reinterpret_cast<const float2*>(P.srays + 6 * r);
         const float2 a = rp[1], b = rp[2];
         const float L0 = a.y, L1 = b.x, L2 = b.y;
@@ -197,6 +314,7 @@ __device__ __forceinline__ void render_shade(const RenderParams& P)
         const float dnl = fmaxf(dnl0, 0.0f);                                            // computeDiffuse, wavefront.glsl:25
         float diff[3] = {dif[0] * dnl, dif[1] * dnl, dif[2] * dnl};
         if (illum >= 1) { diff[0] += amb[0]; diff[1] += amb[1]; diff[2] += amb[2]; }
+        if (kAttr && tri) attr_texture<kInst>(P, A, lut, r, mi, diff);  // after the ambient term, as rchit:99-104
         const bool lit = dnl0 > 0.0f;
         const bool shadowed = lit && ((P.sv && P.sv[r]) || (P.sm && P.sm[r]));
         float att = tri ? 1.0f : 0.3f;  // unlit: 1 for a triangle (rchit:106-140), 0.3 for a voxel (raytrace2.rchit:99-133)
@@ -224,8 +342,21 @@ __device__ __forceinline__ void render_shade(const RenderParams& P)
     if (P.kind_out) P.kind_out[r] = tri ? 2 : (hit ? 1 : 0);
 }
 
-__global__ __launch_bounds__(kRenderBlock) void k_render_shade(RenderParams P) { render_shade<false>(P); }
-__global__ __launch_bounds__(kRenderBlock) void k_render_shade_tlas(RenderParams P) { render_shade<true>(P); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shade(RenderParams P) { render_shade<false, false>(P, AttrParams{}, nullptr); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shade_tlas(RenderParams P) { render_shade<true, false>(P, AttrParams{}, nullptr); }
+
+// the sRGB table goes to LDS first: one entry per thread of the 256-thread block, before any thread of the block leaves
+static_assert(kRenderBlock == 256, "one sRGB table entry per thread");
+template <bool kInst>
+__device__ __forceinline__ void render_shade_attr(const RenderParams& P, const AttrParams& A)
+{
+    __shared__ float lut[256];
+    lut[threadIdx.x] = A.srgb[threadIdx.x];
+    __syncthreads();
+    render_shade<kInst, true>(P, A, lut);
+}
+__global__ __launch_bounds__(kRenderBlock) void k_render_shade_attr(RenderParams P, AttrParams A) { render_shade_attr<false>(P, A); }
+__global__ __launch_bounds__(kRenderBlock) void k_render_shade_attr_tlas(RenderParams P, AttrParams A) { render_shade_attr<true>(P, A); }
 
 }  // namespace
 
@@ -256,6 +387,22 @@ void launch_render_shade_tlas(const RenderParams& P, hipStream_t s)
 {
     if (!P.n) return;
     VX_KL(k_render_shade_tlas, dim3((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, P);
+}
+
+void launch_render_shadow_rays_attr(const RenderParams& P, const AttrParams& A, bool inst, hipStream_t s)
+{
+    if (!P.n) return;
+    const dim3 g((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock));
+    if (inst) VX_KL(k_render_shadow_rays_attr_tlas, g, dim3(kRenderBlock), 0, s, P, A);
+    else VX_KL(k_render_shadow_rays_attr, g, dim3(kRenderBlock), 0, s, P, A);
+}
+
+void launch_render_shade_attr(const RenderParams& P, const AttrParams& A, bool inst, hipStream_t s)
+{
+    if (!P.n) return;
+    const dim3 g((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock));
+    if (inst) VX_KL(k_render_shade_attr_tlas, g, dim3(kRenderBlock), 0, s, P, A);
+    else VX_KL(k_render_shade_attr, g, dim3(kRenderBlock), 0, s, P, A);
 }
 
 }  // namespace vx

@@ -96,6 +96,9 @@ class TlasTraceArgs(C.Structure):
 INSTANCE = np.dtype([("transform", np.float32, (12,)), ("blas", np.uint32), ("mask", np.uint32)])
 
 
+RENDER_ATTRIBUTES = 1   # VX_RENDER_ATTRIBUTES
+
+
 class RenderLight(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("intensity", C.c_float), ("type", C.c_int32)]
 
@@ -126,6 +129,8 @@ SYMBOLS = [
     "vx_mesh_load_obj", "vx_mesh_from_arrays", "vx_mesh_from_device", "vx_mesh_num_vertices", "vx_mesh_num_triangles",
     "vx_mesh_host_vertices", "vx_mesh_host_indices", "vx_mesh_num_materials", "vx_mesh_materials", "vx_mesh_host_material_ids",
     "vx_mesh_set_materials", "vx_mesh_free",
+    "vx_mesh_host_corner_normals", "vx_mesh_host_corner_uvs", "vx_mesh_set_attributes", "vx_mesh_num_textures", "vx_mesh_texture_name",
+    "vx_mesh_host_texture", "vx_mesh_host_material_textures", "vx_mesh_set_material_textures", "vx_mesh_set_texture", "vx_mesh_load_textures",
     "vx_voxelize", "vx_voxelize_into", "vx_voxelize_multi",
     "vx_grid_create", "vx_grid_describe", "vx_grid_set_voxel", "vx_grid_test_voxel", "vx_grid_coords", "vx_grid_bytes",
     "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_aabbs",
@@ -139,7 +144,7 @@ SYMBOLS = [
     "vx_bvh_nodes", "vx_bvh_leaf_triangles", "vx_bvh_nodes_device", "vx_bvh_trace_ex_device", "vx_bvh_trace_ex", "vx_bvh_trace", "vx_bvh_free",
     "vx_tlas_build", "vx_tlas_update", "vx_tlas_update_device", "vx_tlas_num_instances", "vx_tlas_num_nodes", "vx_tlas_height", "vx_tlas_bytes",
     "vx_tlas_world_to_object", "vx_tlas_nodes", "vx_tlas_trace_ex_device", "vx_tlas_trace_ex", "vx_tlas_trace", "vx_tlas_free",
-    "vx_render_create", "vx_render_create_tlas", "vx_render_refresh", "vx_render_frame_device", "vx_render_frame", "vx_render_free",
+    "vx_render_create", "vx_render_create_tlas", "vx_render_refresh", "vx_render_set_shading", "vx_render_frame_device", "vx_render_frame", "vx_render_free",
     "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read", "vx_device_allocations",
     "vx_shard_words", "vx_shard_range",
 ]
@@ -205,6 +210,19 @@ def lib():
     L.vx_mesh_set_materials.argtypes = [vp, vp, C.c_size_t, vp]
     L.vx_mesh_free.argtypes = [vp]
     L.vx_mesh_free.restype = None
+    for _f in ("vx_mesh_host_corner_normals", "vx_mesh_host_corner_uvs", "vx_mesh_host_material_textures"):
+        getattr(L, _f).argtypes = [vp]
+        getattr(L, _f).restype = vp
+    L.vx_mesh_set_attributes.argtypes = [vp, vp, vp]
+    L.vx_mesh_num_textures.argtypes = [vp]
+    L.vx_mesh_num_textures.restype = C.c_size_t
+    L.vx_mesh_texture_name.argtypes = [vp, C.c_size_t]
+    L.vx_mesh_texture_name.restype = C.c_char_p
+    L.vx_mesh_host_texture.argtypes = [vp, C.c_size_t, u32p, u32p]
+    L.vx_mesh_host_texture.restype = vp
+    L.vx_mesh_set_material_textures.argtypes = [vp, vp, C.c_size_t]
+    L.vx_mesh_set_texture.argtypes = [vp, C.c_int32, C.c_uint32, C.c_uint32, vp]
+    L.vx_mesh_load_textures.argtypes = [vp]
     L.vx_voxelize.argtypes = [vp, C.c_float, C.c_int, C.POINTER(VoxelizeOpts), C.POINTER(vp)]
     L.vx_voxelize_into.argtypes = [vp, C.c_float, C.POINTER(VoxelizeOpts), vp]
     L.vx_voxelize_multi.argtypes = [vp, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(vp)]
@@ -304,6 +322,7 @@ def lib():
     L.vx_render_create_tlas.argtypes = [C.POINTER(RenderTlasDesc), C.POINTER(vp)]
     L.vx_render_create.argtypes = [C.POINTER(RenderDesc), C.POINTER(vp)]
     L.vx_render_refresh.argtypes = [vp]
+    L.vx_render_set_shading.argtypes = [vp, C.c_uint32]
     L.vx_render_frame_device.argtypes = [vp, C.POINTER(RenderArgs)]
     L.vx_render_frame.argtypes = [vp, C.POINTER(RenderArgs)]
     L.vx_render_free.argtypes = [vp]
@@ -436,6 +455,63 @@ class Mesh:
         r = np.ascontiguousarray(records, dtype=MATERIAL)
         ids = None if tri_ids is None else np.ascontiguousarray(tri_ids, dtype=np.int32)
         _check(lib().vx_mesh_set_materials(self.h, r.ctypes.data if r.size else None, r.size, ids.ctypes.data if ids is not None else None))
+
+    def _host_f32(self, ptr, per_tri):
+        nt = self.num_triangles
+        if not ptr or not nt:
+            return None
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(nt * per_tri,)).reshape(nt, 3, per_tri // 3).copy()
+
+    def corner_normals(self):
+        """float32[T, 3, 3] (corner k of triangle t: [t, k]) or None when the mesh has no corner normals"""
+        return self._host_f32(lib().vx_mesh_host_corner_normals(self.h), 9)
+
+    def corner_uvs(self):
+        """float32[T, 3, 2] (uv = (u, 1 - v) of the OBJ) or None when the mesh has no corner uvs"""
+        return self._host_f32(lib().vx_mesh_host_corner_uvs(self.h), 6)
+
+    def set_attributes(self, normals=None, uvs=None):
+        """vx_mesh_set_attributes: corner normals [T, 3, 3] and / or uvs [T, 3, 2]; None removes that attribute"""
+        nt = self.num_triangles
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(nt * 9)
+        u = None if uvs is None else np.ascontiguousarray(uvs, dtype=np.float32).reshape(nt * 6)
+        _check(lib().vx_mesh_set_attributes(self.h, n.ctypes.data if n is not None else None, u.ctypes.data if u is not None else None))
+
+    def texture_names(self):
+        """the file of every texture slot (map_Kd, relative to the MTL's directory); "" for a slot set by set_texture"""
+        return [lib().vx_mesh_texture_name(self.h, k).decode("utf-8", "replace") for k in range(lib().vx_mesh_num_textures(self.h))]
+
+    def material_textures(self):
+        """int32[num_materials]: the texture slot of every material (-1 none), or None without materials"""
+        n = lib().vx_mesh_num_materials(self.h)
+        p = lib().vx_mesh_host_material_textures(self.h)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), shape=(n,)).copy() if (p and n) else None
+
+    def set_material_textures(self, slots):
+        a = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        _check(lib().vx_mesh_set_material_textures(self.h, a.ctypes.data if a.size else None, a.size))
+
+    def texture(self, slot):
+        """uint8[H, W, 4] (RGBA8, top row first) of a slot, or None when the slot has no image"""
+        w, h = C.c_uint32(), C.c_uint32()
+        p = lib().vx_mesh_host_texture(self.h, slot, C.byref(w), C.byref(h))
+        if not p:
+            return None
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(h.value * w.value * 4,)).reshape(h.value, w.value, 4).copy()
+
+    def set_texture(self, slot, rgba):
+        """vx_mesh_set_texture: rgba uint8[H, W, 4] (or [H, W, 3]: alpha 255), top row first"""
+        a = np.asarray(rgba, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] not in (3, 4):
+            raise ValueError("rgba must be [H, W, 4] or [H, W, 3]")
+        if a.shape[2] == 3:
+            a = np.concatenate([a, np.full(a.shape[:2] + (1,), 255, np.uint8)], 2)
+        a = np.ascontiguousarray(a)
+        _check(lib().vx_mesh_set_texture(self.h, int(slot), a.shape[1], a.shape[0], a.ctypes.data))
+
+    def load_textures(self):
+        """vx_mesh_load_textures: decode every slot's file (PPM P6 / TGA; 1x1 magenta where that fails)"""
+        _check(lib().vx_mesh_load_textures(self.h))
 
     def free(self):
         if self.h:
@@ -1009,7 +1085,7 @@ class Renderer:
     triangle model (bvh + the mesh it was built from), shadow rays, shading, gamma.  The scene borrows voxels, bvh and mesh: keep them
     alive while it is in use (this object holds references to them)."""
 
-    def __init__(self, voxels, bvh=None, mesh=None, stream=None):
+    def __init__(self, voxels, bvh=None, mesh=None, stream=None, attributes=False):
         d = RenderDesc()
         if isinstance(voxels, Octree):
             d.octree = voxels.h
@@ -1023,9 +1099,11 @@ class Renderer:
         h = C.c_void_p()
         _check(lib().vx_render_create(C.byref(d), C.byref(h)))
         self.h = h
+        if attributes:
+            self.set_shading(RENDER_ATTRIBUTES)
 
     @classmethod
-    def from_tlas(cls, voxels=None, tlas=None, meshes=(), stream=None):
+    def from_tlas(cls, voxels=None, tlas=None, meshes=(), stream=None, attributes=False):
         """vx_render_create_tlas: an instanced scene -- at most one voxel source (Grid of kind GRID_BOOL, Octree or None), a Tlas and one
         Mesh per BLAS of it (vertices, indices, materials), in the Tlas's BLAS order."""
         self = cls.__new__(cls)
@@ -1045,7 +1123,13 @@ class Renderer:
         h = C.c_void_p()
         _check(lib().vx_render_create_tlas(C.byref(d), C.byref(h)))
         self.h = h
+        if attributes:
+            self.set_shading(RENDER_ATTRIBUTES)
         return self
+
+    def set_shading(self, flags):
+        """vx_render_set_shading: RENDER_ATTRIBUTES (corner normals and diffuse textures of triangle hits) or 0, from the next frame"""
+        _check(lib().vx_render_set_shading(self.h, int(flags)))
 
     @staticmethod
     def _args(camera, light):
@@ -1102,7 +1186,7 @@ class Renderer:
         return out
 
     def refresh(self):
-        """vx_render_refresh: re-read the material tables after a source was rebuilt."""
+        """vx_render_refresh: re-read the material and attribute tables (corner attributes, textures) of the sources."""
         _check(lib().vx_render_refresh(self.h))
 
     def free(self):

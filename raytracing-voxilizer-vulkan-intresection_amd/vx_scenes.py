@@ -65,6 +65,49 @@ def blob(nlon=190, nlat=185, seed=1):
     return _f32(v), np.concatenate(tris).astype(np.int32)
 
 
+def smooth_attributes(v, t):
+    """corner attributes of a closed blob-like mesh: smooth normals (the area-weighted vertex normals, float64, unit) and spherical uvs
+    (u = 0.5 + atan2(z, x) / 2pi, v = acos(y) / pi of the direction from the centre) -> (normals [T, 3, 3], uvs [T, 3, 2]) float32"""
+    v64 = np.asarray(v, np.float64)
+    t = np.asarray(t, np.int64)
+    p = v64[t]
+    fn = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    vn = np.zeros_like(v64)
+    for k in range(3):
+        np.add.at(vn, t[:, k], fn)
+    vn /= np.maximum(np.linalg.norm(vn, axis=1, keepdims=True), 1e-30)
+    c = v64 - 0.5 * (v64.min(0) + v64.max(0))
+    d = c / np.maximum(np.linalg.norm(c, axis=1, keepdims=True), 1e-30)
+    uv = np.stack([0.5 + np.arctan2(d[:, 2], d[:, 0]) / (2 * np.pi), np.arccos(np.clip(d[:, 1], -1.0, 1.0)) / np.pi], 1)
+    return _f32(vn[t]), _f32(uv[t])
+
+
+def checker_texture(w, h, cells=8, seed=0):
+    """an RGBA8 checker of w x h texels (top row first), cells x cells squares of two random colours with a gradient over them"""
+    rng = np.random.default_rng(seed)
+    a, b = rng.integers(0, 256, 3), rng.integers(0, 256, 3)
+    y, x = np.mgrid[0:h, 0:w]
+    on = ((x * cells // w) + (y * cells // h)) % 2 == 1
+    rgb = np.where(on[..., None], a, b).astype(np.int64)
+    rgb = (rgb * (128 + (x * 127 // max(w - 1, 1)))[..., None]) // 255
+    return np.concatenate([rgb.astype(np.uint8), np.full((h, w, 1), 255, np.uint8)], 2)
+
+
+def attr_blob_field(n=32, tex=1024):
+    """the blob-instance field of attribute shading's timings: a 5.9k-triangle blob with smooth corner normals and spherical uvs into a
+    tex x tex checker, placed n x n times at scale 0.3 on a 0.75 pitch (x, z from -12, y = 1) -> dict(verts, tris, normals, uvs, texture,
+    transforms [n*n, 12] row-major object-to-world)"""
+    v, t = blob(nlon=60, nlat=50)
+    nrm, uv = smooth_attributes(v, t)
+    g = np.stack(np.meshgrid(np.arange(n), np.arange(n), indexing="ij"), -1).reshape(-1, 2).astype(np.float32)
+    tr = np.zeros((n * n, 12), np.float32)
+    tr[:, 0] = tr[:, 5] = tr[:, 10] = 0.3
+    tr[:, 3] = -12 + g[:, 0] * 0.75
+    tr[:, 7] = 1.0
+    tr[:, 11] = -12 + g[:, 1] * 0.75
+    return dict(verts=v, tris=t, normals=nrm, uvs=uv, texture=checker_texture(tex, tex, cells=16, seed=5), transforms=tr)
+
+
 def _grid_sheet(p00, du, dv, nu, nv, disp=None):
     u = np.linspace(0, 1, nu + 1)
     w = np.linspace(0, 1, nv + 1)
