@@ -3,8 +3,11 @@
 #pragma once
 #include <voxhip.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <filesystem>
+#include <limits>
 #include <memory>
 #include <vector>
 
@@ -76,11 +79,29 @@ private:
         vxdetail::check(vx_octree_build(mesh, voxSize, maxItems, nullptr, &o));  // VX_ERR_MORTON_BITS -> runtime_error, octTree.hpp:583-585
         m_o.reset(o);
         if (!vxdetail::quiet()) {
-            // octTree.hpp:568-569, :798-808
+            // octTree.hpp:562-575 (grid dimensions from the vertex bbox, as computeBboxFromAttrib :531-557), :697-700, :798-808
+            const float* v = vx_mesh_host_vertices(mesh);   // both constructors make meshes with host copies
+            const size_t nv = v ? vx_mesh_num_vertices(mesh) : 0;
+            size_t dim[3] = {0, 0, 0};
+            for (int a = 0; a < 3 && nv; ++a) {
+                float mn = std::numeric_limits<float>::infinity(), mx = -std::numeric_limits<float>::infinity();
+                for (size_t i = 0; i < nv; ++i) {
+                    mn = std::min(mn, v[3 * i + a]);
+                    mx = std::max(mx, v[3 * i + a]);
+                }
+                dim[a] = static_cast<size_t>(std::ceil((mx - mn) / voxSize));
+            }
+            std::printf("Grid dimensions: %zux%zux%zu\n", dim[0], dim[1], dim[2]);
             std::printf("Voxel size: %s\n", vxdetail::fmt(voxSize).c_str());
-            std::printf("Total triangles processed: %zu\n", vx_mesh_num_triangles(mesh));
-            std::printf("Total voxels inserted (before tree build): %zu\n", (size_t)vx_octree_num_items(o));
-            std::printf("Total octree nodes: %zu\n", (size_t)vx_octree_num_nodes(o));
+            if (std::max(dim[0], std::max(dim[1], dim[2])) == 0) {
+                std::printf("Empty voxel grid (zero extent).\n");
+            } else if (vx_mesh_num_triangles(mesh) == 0) {
+                std::printf("No triangles in OBJ, nothing to voxelize.\n");
+            } else {
+                std::printf("Total triangles processed: %zu\n", vx_mesh_num_triangles(mesh));
+                std::printf("Total voxels inserted (before tree build): %zu\n", (size_t)vx_octree_num_items(o));
+                std::printf("Total octree nodes: %zu\n", (size_t)vx_octree_num_nodes(o));
+            }
         }
     }
 };

@@ -1,8 +1,11 @@
 """CPU tests of the oracle (oracle/vx_oracle.c): the survey-recorded reference outputs, the invariants SURVEY.md
 Appendix A verified on the unmodified reference, and the committed self-generated regression vectors.
 
-Formal status: PARITY UNPINNED beyond the survey anchors -- the reference ships no fixtures and cannot be compiled in
-this image without stand-in headers (glm, tinyobjloader, <print>)."""
+Rows a2-a19 of SURVEY.md 8(a) (bbox, grid, SAT both variants, the three grids, Morton and octree) are pinned to the
+reference built from its sources by tests/test_reference_cpu.py (live, oracle/_ref/vxref) and
+tests/golden/reference_outputs.json; the remaining assumption is the three stand-in headers in oracle/ref/shim (glm,
+tinyobjloader, <print>).  Still unpinned: the ray stage (GLSL), tinyobj's number parser and n-gon triangulation, the
+material plumbing (commented out upstream) and the glm version -- see DESIGN.md section 2."""
 import hashlib
 import json
 import os

@@ -1,8 +1,9 @@
 """the oracle's results must not depend on the compiler or its optimisation level as long as
 floating-point contraction is off -- and must change when it is on (which is why every build of this repo passes
--ffp-contract=off).  This does not pin the oracle to the reference (nothing here can); it removes
-compiler luck from the checker: gcc -O0, gcc -O2, gcc -O3 and AMD clang -O2 must produce the committed regression hashes
-bit for bit, a -ffp-contract=fast -mfma build must not."""
+-ffp-contract=off).  Pinning the oracle to the reference is tests/test_reference_cpu.py's job (rows a2-a19 against the
+reference built from its sources, the three stand-in headers in oracle/ref/shim being the remaining assumption; DESIGN.md
+section 2); this test removes compiler luck from the checker: gcc -O0, gcc -O2, gcc -O3 and AMD clang -O2 must produce
+the committed regression hashes bit for bit, a -ffp-contract=fast -mfma build must not."""
 import json
 import os
 import shutil
