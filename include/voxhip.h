@@ -109,6 +109,22 @@ typedef struct vx_voxelize_opts {
                                    queued on the grid's stream after vx_grid_list_wait(g).  Every other reader of the list in this API
                                    (host copies, copies into another buffer, re-binding, setVoxel, the next build, free) waits by
                                    itself; without a ray batch in between the emission runs on the grid's stream when first asked for. */
+#define VX_VOXELIZE_SOLID 4     /* solid voxelization: the inside of closed surfaces is filled.  S = the surface bitmask the build gives without the
+                                   flag (bit for bit); an empty cell is EXTERIOR when a path of empty, 6-connected (face-neighbour) cells joins it to an
+                                   empty cell of the grid's boundary (x in {0, X-1}, y in {0, Y-1} or z in {0, Z-1}); H = the empty cells that are not
+                                   exterior (= binary_fill_holes(S) minus S).  The build then behaves as if, after the triangle loop, setVoxel(x, y, z,
+                                   MaterialObj{}) ran once per cell of H in ascending voxel index:
+                                     dim, origin, bbox, triangles   unchanged;  bitmask S | H, occupied its popcount;  set_calls + |H|
+                                     Bool / AABBstruct list         ascending voxel index over S | H
+                                     Vec list                       the triangles' records (duplicates included), then one cell_aabb record per cell
+                                                                    of H in ascending index; vx_grid_bytes 24 x that length; a bound buffer receives
+                                                                    the whole list when it fits
+                                     materials                      surface voxels / calls keep their ids; interior ones get MaterialObj{}'s, appended
+                                                                    to the table when no triangle used it and H is not empty
+                                   An open mesh (or a hole wider than the conservative surface closes) gives H = {}, a grid with an axis of 1 or 2
+                                   cells too.  Integer bit operations only: bit-exact.  VX_VOXELIZE_LIST_ASYNC is ignored together with this flag.
+                                   With a word shard (word_begin / word_end, shard_world > 1), a triangle range or in vx_multi_voxelize:
+                                   VX_ERR_INVALID_ARG before anything is queued (the fill is global).  More than 2^32 interior cells: VX_ERR_CAPACITY. */
 
 /* ---- library ------------------------------------------------------------------------------------------- */
 const char* vx_last_error(void);
@@ -239,6 +255,14 @@ vx_status vx_grid_bitmask(const vx_grid* g, uint32_t* host_words, uint64_t capac
 const uint32_t* vx_grid_bitmask_device(const vx_grid* g);
 uint32_t* vx_grid_bitmask_device_mut(vx_grid* g); /* for the multi-GPU exchange; call vx_grid_refresh afterwards */
 vx_status vx_grid_refresh(vx_grid* g);            /* recount + rebuild derived data after the bitmask was written externally */
+/* The fill of VX_VOXELIZE_SOLID on any grid (vx_grid_create + setVoxel, a mask written through vx_grid_bitmask_device_mut): exactly
+ * vx_grid_set_voxel on every cell of the grid's interior H in ascending voxel index -- set_calls + |H|, a Vec list gets the records
+ * appended (in the grid's own storage), materials are dropped when H is not empty -- then the derived data is refreshed. */
+vx_status vx_grid_fill_interior(vx_grid* g);
+/* |H| of the last VX_VOXELIZE_SOLID build or vx_grid_fill_interior on the handle; 0 after any other build and for a new grid */
+vx_status vx_grid_interior(const vx_grid* g, uint64_t* count);
+/* diagnostics: the flood-fill rounds that fill took, the final quiet round included (0: no fill, or a grid with an axis below 3 cells) */
+uint32_t vx_grid_fill_rounds(const vx_grid* g);
 /* getAabbs (voxelgridBool.cpp:18-52, voxelgridAABBstruct.cpp:10-22, voxelgridVecEncoding.cpp:15-18).
  * *count receives the list length; at most `capacity` entries are written (capacity 0 = size query). */
 vx_status vx_grid_aabbs(const vx_grid* g, vx_aabb* host_out, uint64_t capacity, uint64_t* count);

@@ -70,6 +70,11 @@ public:
     // the reference today (every voxel MaterialObj{}, nothing recorded).
     VoxelBuilder& withMaterials(bool on = true) { m_materials = on; return *this; }
 
+    // Solid voxelization (VX_VOXELIZE_SOLID): after the triangle loop every enclosed empty cell -- one that no path of 6-connected empty
+    // cells joins to the grid's boundary -- is set as well (setVoxel with MaterialObj{}, ascending).  Off by default: the reference marks
+    // the surface only.  A single-device build; with withDevices of more than one device buildVoxelGrid throws std::invalid_argument.
+    VoxelBuilder& withSolid(bool on = true) { m_solid = on; return *this; }
+
     // Spreads buildVoxelGrid over several GPUs of this process (vx_voxelize_multi: word shards of the one grid, peer copies over
     // xGMI; the grid returned lives on the first device).  Empty = the current device only.  VoxelGridBool / VoxelGridAABBstruct.
     VoxelBuilder& withDevices(std::vector<int> devices) { m_devices = std::move(devices); return *this; }
@@ -77,6 +82,7 @@ public:
 private:
     std::shared_ptr<vx_mesh> m_mesh;
     bool m_materials = false;
+    bool m_solid = false;
     std::vector<int> m_devices;
 
     void readObjFile(const std::filesystem::path& path)
@@ -95,7 +101,7 @@ public:
         }
         vx_voxelize_opts opts{};
         opts.sat_variant = inParaell ? 1 : 0;
-        opts.flags = m_materials ? VX_VOXELIZE_MATERIALS : 0;
+        opts.flags = (m_materials ? VX_VOXELIZE_MATERIALS : 0) | (m_solid ? VX_VOXELIZE_SOLID : 0);
         vx_grid* g = nullptr;
         if (m_devices.size() > 1) {
             // word shards on the listed devices, peer copies to the first; with materials the shards' first uses are combined and

@@ -34,6 +34,9 @@
 //                                       the frames shade the mesh's triangles in attribute mode (vx_render_set_shading): interpolated vertex
 //                                       normals and the map_Kd textures of its materials (PPM / TGA, loaded by vx_mesh_load_textures), as
 //                                       raytrace.rchit:73-74,99-104; with or without --instances.  Refused without --frames or --mesh.
+//   --solid                             solid voxelization (VX_VOXELIZE_SOLID): the enclosed empty cells are filled after the triangle loop;
+//                                       one more line gives their count.  bool / aabbstruct / vec with their options; not with --grid octree,
+//                                       --gpus N > 1 or --bench
 //   --materials                         switch on the reference's commented-out material plumbing (usemtl / mtllib -> per-voxel
 //                                       material ids; VoxelBuilder.hpp:375-395): --render shades with them, --dump-materials FILE writes
 //                                       getMatIdx() as int16
@@ -313,15 +316,21 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
 template <class T, bool P>
 int run_grid(const std::string& path, float vs, const std::string& dumpFile, const char* label, const std::string& renderFile = "",
              uint32_t rw = 1280, uint32_t rh = 720, bool materials = false, const std::string& matDump = "", const std::string& cameraDump = "",
-             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0)
+             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0, bool solid = false)
 {
     VoxelBuilder<T, P> voxelBuilder{std::filesystem::path(path)};
     voxelBuilder.withMaterials(materials);
+    voxelBuilder.withSolid(solid);
     voxelBuilder.withDevices(devices);
     if (devices.size() > 1) std::printf("[voxhip] build sharded over %zu ranks (first device %d)\n", devices.size(), devices[0]);
     const auto t0 = Clock::now();
     T vox = voxelBuilder.buildVoxelGrid(vs);
     const auto t1 = Clock::now();
+    if (solid) {
+        uint64_t interior = 0;
+        vxdetail::check(vx_grid_interior(vox.handle(), &interior));
+        std::printf("[voxhip] solid: %llu interior voxels filled\n", (unsigned long long)interior);
+    }
     const std::vector<Aabb> aabbs = vox.getAabbs();
     const auto t2 = Clock::now();
     const auto msBuild = std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();
@@ -356,7 +365,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid]\n",
                      argv[0]);
         return 2;
     }
@@ -365,7 +374,7 @@ int main(int argc, char** argv)
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
     std::string grid = "bool", dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
-    bool parallel = false, materials = false, logical = false, attributes = false;
+    bool parallel = false, materials = false, logical = false, attributes = false, solid = false;
     int gpus = 1;
     long benchRuns = 0, frames = 0;
     for (int i = 3; i < argc; ++i) {
@@ -382,6 +391,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) meshFile = argv[++i];
         else if (!std::strcmp(argv[i], "--instances") && i + 1 < argc) instFile = argv[++i];
         else if (!std::strcmp(argv[i], "--attributes")) attributes = true;
+        else if (!std::strcmp(argv[i], "--solid")) solid = true;
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
@@ -401,6 +411,10 @@ int main(int argc, char** argv)
     }
     if (frames > 0 && (renderFile.empty() || benchRuns > 0 || (grid != "bool" && grid != "octree"))) {
         std::fprintf(stderr, "--frames renders with --render and --grid bool or octree only, and not with --bench\n");
+        return 2;
+    }
+    if (solid && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
+        std::fprintf(stderr, "--solid fills the interior of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
         return 2;
     }
     std::vector<int> devices;
@@ -486,10 +500,12 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames)
-                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames);
-        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct") : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct");
-        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec") : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec");
+        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid)
+                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid);
+        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, false, "", "", {}, nullptr, 0, solid)
+                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, false, "", "", {}, nullptr, 0, solid);
+        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid)
+                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid);
         std::fprintf(stderr, "unknown grid flavour %s\n", grid.c_str());
         return 2;
     } catch (const std::exception& e) {

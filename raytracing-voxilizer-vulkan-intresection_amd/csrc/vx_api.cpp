@@ -181,6 +181,7 @@ struct Small {
     unsigned long long set_calls[vx::kCallCounters * 8];  // 64 counters on lines of their own (k_voxelize), summed by sync_counts
     unsigned long long nhits;
     unsigned long long trace_counters[4];
+    uint32_t solid_flags[2 * 32];      // one word per round of a solid fill: two halves, batches alternate between them
 };
 
 // The few values the HOST waits for (bbox -> grid dims, unit / hit / occupied counts -> buffer sizes).  Kernels write them
@@ -189,6 +190,7 @@ struct Small {
 struct Mail {
     float bbox[8];
     unsigned long long units, hits, occupied, pad;
+    unsigned long long solid_rounds, interior;  // solid fill: changed rounds of the last batch, |H|
 };
 
 // Totals may arrive tagged with the build's sequence number in bits 48..63 (see launch_scan_u32): the host then polls the word
@@ -408,6 +410,12 @@ struct vx_grid {
     uint64_t triangles = 0;
     uint32_t cdim[3] = {0, 0, 0}, c2dim[3] = {0, 0, 0};
     DevBuf words, twords /*tiled build mask (launch_voxelize)*/, cwords, c2words, bricks, idxtmp, ttmp, camera, wprefix, wsel /*word of every 1024th occupied voxel (prefix scan)*/, wp16 /*every 16th entry of wprefix, dense (prefix scan)*/, recs, ext /*high bits of the candidate ranges*/, units, ubase, btri, umask, bhits /*hits per block of 64 units*/, hbase /*their exclusive scan*/, scantmp, small, vec, matids, mattmp;
+    // solid voxelization (vx_solid.hip): padded mask, exterior, H in the reference's layout (padded rows only) and the word prefix over H
+    DevBuf solid_m, solid_e, solid_h, solid_pre, solid_agg /*the column scans' per-chunk words*/;
+    uint64_t interior = 0;        // |H| of the last build or fill on the handle (vx_grid_interior)
+    uint32_t solid_rounds = 0;    // rounds of that fill, the quiet one included (vx_grid_fill_rounds)
+    uint64_t mat_interior = 0;    // a solid VX_VOXELIZE_MATERIALS build: ids of interior voxels / calls still to be given MaterialObj{}'s index
+    uint64_t mat_surface = 0;     // ... Vec: they follow the triangles' mat_surface calls
     std::vector<vx_material> materials;  // m_materials: distinct values in first-use order (VX_VOXELIZE_MATERIALS builds only)
     uint64_t mat_count = 0;              // entries of matids
     bool has_materials = false;
@@ -529,7 +537,7 @@ struct vx_grid {
     void set_dev(int d)
     {
         device = d;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp}) b->dev = d;
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg}) b->dev = d;
     }
     // the stream this handle queues work on; the pool orders the reuse of released blocks by it
     void set_stream(hipStream_t st)
@@ -539,11 +547,11 @@ struct vx_grid {
             (void)hipStreamSynchronize(stream);
         }
         stream = st;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp}) b->stream = st;
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg}) b->stream = st;
     }
     void release_all()
     {
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp}) b->release();
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg}) b->release();
         if (mail) (void)hipHostFree(mail);
         mail = nullptr;
     }
@@ -842,10 +850,71 @@ vx_status finish_materials(vx_grid* g, const long long* first_use, size_t nvalue
         else
             vx::launch_mat_ids(last_tri, g->mat_nids, g->mat_dtv, value_index, g->matids.as<int16_t>(), s);
     }
+    if (g->mat_interior && g->mat_first_use.size() && vindex[0] >= 0)  // solid build: the second loop's setVoxel calls carry MaterialObj{} (value 0)
+        vx::launch_solid_ids(g->matids.as<int16_t>() + (vec ? g->mat_surface : 0), vec ? g->mat_interior : g->mat_nids, vindex[0], /*only_unset=*/!vec, s);
     VX_HIP(hipStreamSynchronize(s));  // vindex lives on this stack frame
     g->mat_count = g->mat_nids;
     g->has_materials = true;
     g->mat_pending = false;
+    return VX_OK;
+}
+
+// Solid voxelization (vx_solid.hip): the interior H of the grid's complete bitmask is OR-ed into it; H in the reference's layout stays in
+// *h_words with its word prefix in g->solid_pre (nwords + 1 entries) for the Vec list.  The host reads one mailbox word per batch of rounds
+// and queues batches until a round is quiet: no cap on the rounds.  Grids with an axis of 1 or 2 cells have no interior (nothing queued).
+vx_status solid_fill(vx_grid* g, uint64_t* n_interior, const uint32_t** h_words)
+{
+    *n_interior = 0;
+    *h_words = nullptr;
+    g->solid_rounds = 0;
+    const uint32_t* dim = g->g.dim;
+    if (dim[0] < 3 || dim[1] < 3 || dim[2] < 3) return VX_OK;
+    hipStream_t s = g->stream;
+    const vx::SolidPlan plan = vx::solid_plan(dim);
+    VX_HIP(g->solid_e.ensure((size_t)plan.pwords * 4 + 16));
+    if (plan.padded) {
+        VX_HIP(g->solid_m.ensure((size_t)plan.pwords * 4 + 16));
+        VX_HIP(g->solid_h.ensure((size_t)g->g.nwords * 4 + 16));
+    }
+    VX_HIP(g->solid_pre.ensure((size_t)(g->g.nwords + 2) * 4));
+    VX_HIP(g->solid_agg.ensure((size_t)vx::solid_agg_words(dim) * 4 + 16));
+    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(g->g.nwords), s));
+    uint32_t* flags = g->small.as<Small>()->solid_flags;
+    uint32_t* words = g->words.as<uint32_t>();
+    const uint32_t* m = plan.padded ? g->solid_m.as<uint32_t>() : words;
+    uint32_t* ext = g->solid_e.as<uint32_t>();
+    uint32_t prev = 2 * 32 - 1;  // the flag the first round reads: set by the seed (the other half of what batch 0 clears)
+    vx::launch_solid_seed(words, g->solid_m.as<uint32_t>(), ext, dim, flags + prev, s);
+    static const bool poll = !(getenv("VOXHIP_POLL_MAIL") && atoi(getenv("VOXHIP_POLL_MAIL")) == 0);
+    uint32_t batch = 4, rounds = 0;
+    for (uint32_t k = 0;; ++k) {
+        const uint32_t first = (k & 1u) * 32u;
+        VX_HIP(hipMemsetAsync(flags + first, 0, batch * 4, s));
+        for (uint32_t r = 0; r < batch; ++r) {
+            vx::launch_solid_round(m, ext, g->solid_agg.as<uint32_t>(), dim, flags + prev, flags + first + r, s);
+            prev = first + r;
+        }
+        g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
+        const unsigned long long tag = (unsigned long long)g->mail_seq << 48;
+        vx::launch_solid_report(flags + first, batch, &g->mail->solid_rounds, tag, s);
+        if (!(poll && mail_wait(&g->mail->solid_rounds, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+        const uint32_t changed = (uint32_t)(g->mail->solid_rounds & kMailValue);
+        rounds += changed;
+        if (changed < batch) break;  // a quiet round: every round after it exited at once
+        if (batch < 32) batch *= 2;
+    }
+    g->solid_rounds = rounds + 1;
+    uint32_t* h = plan.padded ? g->solid_h.as<uint32_t>() : ext;
+    vx::launch_solid_finish(words, g->solid_m.as<uint32_t>(), ext, h, dim, g->g.nwords, s);
+    g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
+    const unsigned long long tag = (unsigned long long)g->mail_seq << 48;
+    const bool tagged = vx::launch_scan_u32(h, g->solid_pre.as<uint32_t>(), g->g.nwords, true, g->scantmp.p, &g->mail->interior, s, true, tag, nullptr,
+                                            next_scan_gen(g->scantmp, s));
+    if (!(poll && tagged && mail_wait(&g->mail->interior, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+    const unsigned long long n = g->mail->interior & kMailValue;
+    if (n >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 interior voxels");
+    *n_interior = n;
+    *h_words = h;
     return VX_OK;
 }
 
@@ -1073,6 +1142,9 @@ static void grid_set_empty(vx_grid* g, float vs)
     g->has_materials = g->mat_pending = g->mat_gathered = false;
     g->materials.clear();
     g->mat_count = 0;
+    g->interior = 0;
+    g->solid_rounds = 0;
+    g->mat_interior = 0;
 }
 
 static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g);
@@ -1092,6 +1164,8 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
     if (o.shard_world < 0 || (o.shard_world > 0 && (o.shard_rank < 0 || o.shard_rank >= o.shard_world))) return fail(VX_ERR_INVALID_ARG, "shard_rank / shard_world out of range");
     if ((o.tri_begin || o.tri_end) && (o.tri_begin > o.tri_end || o.tri_end > mesh->nt)) return fail(VX_ERR_INVALID_ARG, "triangle shard out of range");
     if (o.word_begin > o.word_end) return fail(VX_ERR_INVALID_ARG, "word shard out of range");
+    if ((o.flags & VX_VOXELIZE_SOLID) && (o.word_begin || o.word_end || o.shard_world > 1 || o.tri_begin || o.tri_end))
+        return fail(VX_ERR_INVALID_ARG, "VX_VOXELIZE_SOLID needs the whole grid: no word shard, no triangle range");
     DeviceGuard dg(g->device);
     VX_TRY(mesh_to_device(mesh));
     if (o.flags & VX_VOXELIZE_MATERIALS) VX_TRY(mesh_material_values(mesh));
@@ -1109,7 +1183,12 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     // that was never queued is dropped: its list is about to be replaced)
     VX_HIP(g->list_resolve(/*drop_unqueued=*/true));
     const bool want_mat = (o.flags & VX_VOXELIZE_MATERIALS) != 0;
-    const bool list_async = (o.flags & VX_VOXELIZE_LIST_ASYNC) != 0 && g->kind == VX_GRID_VEC && !want_mat;  // (the material ids need the hit bases on the main stream)
+    const bool solid = (o.flags & VX_VOXELIZE_SOLID) != 0;
+    // (the material ids need the hit bases on the main stream; a solid build appends the interior's records behind the triangles')
+    const bool list_async = (o.flags & VX_VOXELIZE_LIST_ASYNC) != 0 && g->kind == VX_GRID_VEC && !want_mat && !solid;
+    g->interior = 0;
+    g->solid_rounds = 0;
+    g->mat_interior = g->mat_surface = 0;
     g->has_materials = false;
     g->mat_pending = false;
     g->mat_gathered = false;
@@ -1273,13 +1352,22 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     // (the tiled mask -> the reference's bitmask: by the brick kernel on its way when the traversal structure is built right away, below)
     static const bool eager = !(getenv("VOXHIP_EAGER") && atoi(getenv("VOXHIP_EAGER")) == 0);
     static const bool fuse_untile = !(getenv("VOXHIP_FUSE_UNTILE") && atoi(getenv("VOXHIP_FUSE_UNTILE")) == 0);
-    const bool untile_in_bricks = tiled && eager && fuse_untile && whole_words;
+    // (VX_VOXELIZE_SOLID: the fill reads and extends the reference's bitmask, the traversal structure is built from the final one)
+    const bool untile_in_bricks = tiled && eager && fuse_untile && whole_words && !solid;
     if (tiled && !untile_in_bricks) vx::launch_untile(g->twords.as<uint32_t>(), g->words.as<uint32_t>(), g->g.dim, s, wb, we);
     g->counts_valid = false;
     bool hits_tagged = false, occ_tagged = false, occ_queued = false;
     if (g->kind == VX_GRID_VEC) {
         VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nUB), s));
         hits_tagged = vx::launch_scan_u32(bhits, g->hbase.as<uint32_t>(), nUB, false, g->scantmp.p, &g->mail->hits, s, true, mtag, nullptr, next_scan_gen(g->scantmp, s));
+    }
+    // VX_VOXELIZE_SOLID: the second loop -- setVoxel on every interior cell in ascending order -- once the surface mask is complete
+    uint64_t n_interior = 0;
+    const uint32_t* h_words = nullptr;
+    if (solid) {
+        VX_TRY(solid_fill(g, &n_interior, &h_words));
+        g->interior = n_interior;
+        g->host_set_calls += n_interior;
     }
     // A complete (unsharded) bitmask: queue what every consumer of the grid needs next -- the traversal structure (bricks,
     // bounds, mips = the reference's acceleration-structure build, hello_vulkan.cpp:700-703) and the word prefix (getAabbs /
@@ -1321,8 +1409,10 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
             g->occupied = g->mail->occupied & kMailValue;
             g->occupied_known = true;
         }
-        if (hits + 1 <= cap_rec) g->vec_in_bound = to_bound;
-        if (hits + 1 > cap_rec) VX_HIP(g->vec.ensure((size_t)(hits + 1) * sizeof(vx_aabb)));
+        const uint64_t total = hits + n_interior;  // (a solid build: the interior's records follow the triangles')
+        if (total >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 voxel records");
+        if (total + 1 <= cap_rec) g->vec_in_bound = to_bound;
+        if (total + 1 > cap_rec) VX_HIP(g->vec.ensure((size_t)(total + 1) * sizeof(vx_aabb)));
         if (list_async) {
             // VX_VOXELIZE_LIST_ASYNC: the count is known, the records are written later -- beside the next ray batch (trace_common), or
             // on this stream by whatever asks for them first (list_resolve)
@@ -1332,11 +1422,14 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
             g->ld.tgt = g->vec_ptr();
             g->ld.cap = g->vec_in_bound ? g->bound_cap : ~0ull;
             g->list_deferred = hits != 0;
-        } else if (hits + 1 > cap_rec) {
+        } else if (total + 1 > cap_rec) {
             vx::launch_emit_units(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, umask,
                                   g->hbase.as<uint32_t>(), g->vec.as<vx_aabb>(), nullptr, s, ~0ull, xw);
         }
-        g->vec_count = hits;
+        if (n_interior)  // cell_aabb of every interior cell in ascending order, at offset `hits`
+            vx::launch_emit_bool_aabbs(h_words, g->solid_pre.as<uint32_t>(), g->g, g->vec_ptr() + hits, n_interior, s);
+        g->vec_count = total;
+        g->mat_surface = hits;
     }
     if (want_mat) {
         // ---- per-voxel material ids (see k_mat_last): needs the word prefix (queued above for an unsharded build) and, for the Vec
@@ -1363,6 +1456,9 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         const int32_t* tv = mesh->tri_value.data() + tb;
         for (uint32_t t = 0; t < ntri; ++t)
             if (hit[t] && g->mat_first_use[(size_t)tv[t]] < 0) g->mat_first_use[(size_t)tv[t]] = (long long)(tb + t);
+        // the interior's calls come after every triangle's and carry MaterialObj{} (value 0): addMatrialIfNeeded appends it if no triangle used it
+        g->mat_interior = n_interior;
+        if (n_interior && g->mat_first_use[0] < 0) g->mat_first_use[0] = (long long)(tb + ntri);
         g->mat_dtv = mesh->btv.as<int32_t>() + tb;
         g->mat_ntri = ntri;
         g->mat_nids = nids;
@@ -1490,6 +1586,7 @@ vx_status vx_multi_voxelize(vx_multi* m, float vs, const vx_voxelize_opts* opts,
     vx_voxelize_opts o{};
     if (opts) o = *opts;
     if (o.word_begin || o.word_end || o.tri_begin || o.tri_end || o.shard_world) return fail(VX_ERR_INVALID_ARG, "vx_multi_voxelize shards the build itself");
+    if (o.flags & VX_VOXELIZE_SOLID) return fail(VX_ERR_INVALID_ARG, "VX_VOXELIZE_SOLID needs the whole grid on one device: vx_multi_voxelize shards it");
     const bool want_mat = (o.flags & VX_VOXELIZE_MATERIALS) != 0;
     const int nd = m->nd;
     for (int k = 0; k < nd; ++k)
@@ -1781,6 +1878,53 @@ vx_status vx_grid_refresh(vx_grid* g)
     VX_TRY(ensure_prefix(g));
     return ensure_coarse(g);
 }
+
+vx_status vx_grid_fill_interior(vx_grid* g)
+{
+    if (!g) return fail(VX_ERR_INVALID_ARG, "null argument");
+    DeviceGuard dg(g->device);
+    VX_HIP(g->list_resolve());  // (an emission still to come reads the mask / writes the list this call extends)
+    if (!g->mail) VX_HIP(mail_alloc(&g->mail));
+    VX_HIP(ensure_small(g->small));
+    uint64_t n = 0;
+    const uint32_t* h = nullptr;
+    const vx_status st = solid_fill(g, &n, &h);
+    g->coarse_valid = g->prefix_valid = g->occupied_known = false;  // (the mask may have changed even when the fill failed)
+    VX_TRY(st);
+    if (g->kind == VX_GRID_VEC && n) {
+        // setVoxel appends one record per call: the list continues in the grid's own storage, as after vx_grid_set_voxel
+        const size_t need = (size_t)(g->vec_count + n + 1) * sizeof(vx_aabb);
+        if (g->vec_in_bound || need > g->vec.cap) {
+            DevBuf nb;
+            nb.dev = g->device;
+            nb.stream = g->stream;
+            VX_HIP(nb.ensure(need));
+            if (g->vec_count) VX_HIP(hipMemcpyAsync(nb.p, g->vec_ptr(), (size_t)g->vec_count * sizeof(vx_aabb), hipMemcpyDeviceToDevice, g->stream));
+            g->vec.release();
+            g->vec = nb;
+            g->vec_in_bound = false;
+        }
+        vx::launch_emit_bool_aabbs(h, g->solid_pre.as<uint32_t>(), g->g, g->vec.as<vx_aabb>() + g->vec_count, n, g->stream);
+        g->vec_count += n;
+    }
+    g->host_set_calls += n;
+    g->set_calls += n;
+    g->interior = n;
+    if (n) g->has_materials = false;  // (setVoxel from the host drops the per-voxel ids)
+    VX_TRY(ensure_prefix(g));
+    VX_TRY(ensure_coarse(g));
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+vx_status vx_grid_interior(const vx_grid* g, uint64_t* count)
+{
+    if (!g || !count) return fail(VX_ERR_INVALID_ARG, "null argument");
+    *count = g->interior;
+    return VX_OK;
+}
+
+uint32_t vx_grid_fill_rounds(const vx_grid* g) { return g ? g->solid_rounds : 0; }
 
 vx_status vx_grid_aabbs_device(const vx_grid* gc, vx_aabb* dev_out, uint64_t cap, uint64_t* count)
 {

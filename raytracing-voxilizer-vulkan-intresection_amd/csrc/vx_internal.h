@@ -337,6 +337,27 @@ void launch_render_shade_attr(const RenderParams& P, const AttrParams& A, bool i
 // single-voxel helpers
 void launch_set_bit(uint32_t* words, uint64_t idx, hipStream_t s);
 
+// Solid voxelization (vx_solid.hip): the exterior of the mask grown from the boundary's empty cells in rounds, then H = empty & ~exterior.
+// Padded layout: W words per (y, z) row, pwords in all; `padded` is false when X % 32 == 0 (the reference's bitmask is that layout).
+struct SolidPlan {
+    uint32_t W = 0;
+    bool padded = false;
+    uint64_t pwords = 0;
+};
+SolidPlan solid_plan(const uint32_t dim[3]);
+// mp (padded only, pwords): the padded mask; ext (pwords): the exterior's seed; *flag = 1 (the flag the first round reads)
+void launch_solid_seed(const uint32_t* words, uint32_t* mp, uint32_t* ext, const uint32_t dim[3], uint32_t* flag, hipStream_t s);
+// one round (x, y, z sweeps) over the padded mask m (mp, or the bitmask when not padded); every kernel exits at once when *prev_flag == 0 and
+// sets *flag = 1 when it grows the exterior; agg: solid_agg_words(dim) words of scratch (the column scans' per-chunk words)
+uint64_t solid_agg_words(const uint32_t dim[3]);
+void launch_solid_round(const uint32_t* m, uint32_t* ext, uint32_t* agg, const uint32_t dim[3], const uint32_t* prev_flag, uint32_t* flag, hipStream_t s);
+// *out = tag | (number of the nrounds flags that are set)
+void launch_solid_report(const uint32_t* flags, uint32_t nrounds, unsigned long long* out, unsigned long long tag, hipStream_t s);
+// words |= H; H in the reference's layout into h (padded) or over ext (not padded: h unused)
+void launch_solid_finish(uint32_t* words, const uint32_t* mp, uint32_t* ext, uint32_t* h, const uint32_t dim[3], uint64_t nwords, hipStream_t s);
+// ids[i] = v for i < n (only_unset: only where ids[i] < 0)
+void launch_solid_ids(int16_t* ids, uint64_t n, int16_t v, bool only_unset, hipStream_t s);
+
 // device radix sort of uint64 keys (octree items; vx_sort.hip); tmp sized by sort_tmp_bytes.  The two key buffers ping-pong:
 // returns 0 when the sorted keys end up in keys_a, 1 for keys_b (the other buffer is scratch afterwards).
 size_t sort_tmp_bytes(uint64_t n);

@@ -15,6 +15,7 @@ VX_OK = 0
 GRID_BOOL, GRID_AABBSTRUCT, GRID_VEC = 0, 1, 2
 VOXELIZE_MATERIALS = 1
 VOXELIZE_LIST_ASYNC = 2
+VOXELIZE_SOLID = 4
 STATUS_NAMES = {0: "VX_OK", 1: "VX_ERR_INVALID_ARG", 2: "VX_ERR_PATH", 3: "VX_ERR_PARSE", 4: "VX_ERR_OUT_OF_BOUNDS",
                 5: "VX_ERR_MORTON_BITS", 6: "VX_ERR_NO_DEVICE", 7: "VX_ERR_HIP", 8: "VX_ERR_CAPACITY", 9: "VX_ERR_UNSUPPORTED"}
 
@@ -133,7 +134,7 @@ SYMBOLS = [
     "vx_mesh_host_texture", "vx_mesh_host_material_textures", "vx_mesh_set_material_textures", "vx_mesh_set_texture", "vx_mesh_load_textures",
     "vx_voxelize", "vx_voxelize_into", "vx_voxelize_multi",
     "vx_grid_create", "vx_grid_describe", "vx_grid_set_voxel", "vx_grid_test_voxel", "vx_grid_coords", "vx_grid_bytes",
-    "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_aabbs",
+    "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_fill_interior", "vx_grid_interior", "vx_grid_fill_rounds", "vx_grid_aabbs",
     "vx_grid_aabbs_device", "vx_grid_bind_aabbs_device", "vx_grid_list_wait", "vx_grid_aabbs_device_async", "vx_grid_materials", "vx_grid_material_ids", "vx_grid_material_ids_device", "vx_grid_material_first_use",
     "vx_grid_finish_materials", "vx_multi_create", "vx_multi_voxelize", "vx_multi_grid", "vx_multi_release_grid", "vx_multi_free", "vx_sort_u64", "vx_grid_free",
     "vx_octree_build", "vx_octree_num_items", "vx_octree_num_nodes", "vx_octree_bytes", "vx_octree_items", "vx_octree_nodes",
@@ -250,6 +251,10 @@ def lib():
     L.vx_grid_bitmask_device_mut.argtypes = [vp]
     L.vx_grid_bitmask_device_mut.restype = vp
     L.vx_grid_refresh.argtypes = [vp]
+    L.vx_grid_fill_interior.argtypes = [vp]
+    L.vx_grid_interior.argtypes = [vp, u64p]
+    L.vx_grid_fill_rounds.argtypes = [vp]
+    L.vx_grid_fill_rounds.restype = C.c_uint32
     L.vx_grid_aabbs.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_grid_aabbs_device.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_grid_bind_aabbs_device.argtypes = [vp, vp, C.c_uint64]
@@ -534,10 +539,10 @@ class Grid:
         self.h = handle
 
     @classmethod
-    def voxelize(cls, mesh, voxel_size, kind=GRID_BOOL, sat_variant=0, words=None, tris=None, stream=None, materials=False, shard=None):
+    def voxelize(cls, mesh, voxel_size, kind=GRID_BOOL, sat_variant=0, words=None, tris=None, stream=None, materials=False, shard=None, solid=False):
         o = VoxelizeOpts()
         o.sat_variant = sat_variant
-        o.flags = VOXELIZE_MATERIALS if materials else 0
+        o.flags = (VOXELIZE_MATERIALS if materials else 0) | (VOXELIZE_SOLID if solid else 0)
         if shard is not None:
             o.shard_rank, o.shard_world = shard
         if words is not None:
@@ -558,10 +563,11 @@ class Grid:
         _check(lib().vx_voxelize_multi(mesh.h, np.float32(voxel_size), kind, sat_variant, dv, len(devices), 1 if all_gather else 0, hs))
         return [cls(C.c_void_p(hs[i])) for i in range(n)]
 
-    def revoxelize(self, mesh, voxel_size, sat_variant=0, words=None, tris=None, stream=None, materials=False, shard=None, list_async=False):
+    def revoxelize(self, mesh, voxel_size, sat_variant=0, words=None, tris=None, stream=None, materials=False, shard=None, list_async=False,
+                   solid=False):
         o = VoxelizeOpts()
         o.sat_variant = sat_variant
-        o.flags = (VOXELIZE_MATERIALS if materials else 0) | (VOXELIZE_LIST_ASYNC if list_async else 0)
+        o.flags = (VOXELIZE_MATERIALS if materials else 0) | (VOXELIZE_LIST_ASYNC if list_async else 0) | (VOXELIZE_SOLID if solid else 0)
         if shard is not None:
             o.shard_rank, o.shard_world = shard
         if words is not None:
@@ -613,6 +619,21 @@ class Grid:
 
     def refresh(self):
         _check(lib().vx_grid_refresh(self.h))
+
+    def fill_interior(self):
+        """vx_grid_fill_interior: setVoxel on every enclosed empty cell (6-connected exterior), ascending; returns the count."""
+        _check(lib().vx_grid_fill_interior(self.h))
+        return self.interior()
+
+    def interior(self):
+        """|H| of the last solid build or fill_interior on this handle (0 otherwise)."""
+        n = C.c_uint64()
+        _check(lib().vx_grid_interior(self.h, C.byref(n)))
+        return int(n.value)
+
+    def fill_rounds(self):
+        """Flood-fill rounds of the last solid build or fill_interior, the final quiet round included."""
+        return int(lib().vx_grid_fill_rounds(self.h))
 
     def aabbs(self):
         n = C.c_uint64()

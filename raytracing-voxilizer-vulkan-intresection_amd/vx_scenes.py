@@ -287,6 +287,84 @@ def camera_matrices(eye=(6.16636, 2.42256, -3.15471), ctr=(0.0, 1.0, 0.0), up=(0
 INTERIOR_CAMERAS = (dict(eye=(0.0, 6.0, 14.0), ctr=(-2.0, 10.0, -16.0)), dict(eye=(-10.0, 12.0, 10.0), ctr=(8.0, 8.0, -12.0)))
 
 
+# ---- closed meshes for solid voxelization (VX_VOXELIZE_SOLID) ----
+def _rotate(v, angles=(0.37, 0.61, 0.23), offset=(0.113, -0.071, 0.057)):
+    ax, ay, az = angles
+    rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+    ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+    rz = np.array([[np.cos(az), -np.sin(az), 0], [np.sin(az), np.cos(az), 0], [0, 0, 1]])
+    return np.asarray(v, dtype=np.float64) @ (rz @ ry @ rx).T + np.array(offset)
+
+
+def torus(major=1.0, minor=0.38, nu=96, nv=48):
+    """Closed torus around the y axis: its tube is filled by a solid build, the hole through the middle stays empty."""
+    u = np.linspace(0, 2 * np.pi, nu, endpoint=False)
+    w = np.linspace(0, 2 * np.pi, nv, endpoint=False)
+    U, W = np.meshgrid(u, w, indexing="ij")
+    r = major + minor * np.cos(W)
+    v = np.stack([r * np.cos(U), minor * np.sin(W), r * np.sin(U)], -1).reshape(-1, 3)
+    i = np.arange(nu)[:, None]
+    j = np.arange(nv)[None, :]
+    a = i * nv + j
+    b = ((i + 1) % nu) * nv + j
+    c = ((i + 1) % nu) * nv + (j + 1) % nv
+    d = i * nv + (j + 1) % nv
+    t = np.concatenate([np.stack([a, b, c], -1).reshape(-1, 3), np.stack([a, c, d], -1).reshape(-1, 3)])
+    return _f32(_rotate(v, (0.21, 0.13, 0.05), (0.0, 0.0, 0.0))), t.astype(np.int32)
+
+
+def nested_shells(outer=1.0, inner=0.45):
+    """Two closed shells, one inside the other (a rotated cube around a smaller one): a solid build fills both and the gap between them."""
+    v0, t0 = cube(outer)
+    v1, t1 = cube(inner, center=(0.05, -0.03, 0.02))
+    v = np.concatenate([v0, v1]).astype(np.float64)
+    return _f32(_rotate(v)), np.concatenate([t0, t1 + v0.shape[0]]).astype(np.int32)
+
+
+def holed_box(hole, half=1.0):
+    """A closed box whose +z face has a square hole of side `hole` at its centre (the face is the four rectangles around it), rotated so that
+    no face lies in a voxel plane.  A hole several voxels wide lets the exterior in (no interior); one narrower than a voxel is closed by the
+    conservative surface (the box is filled)."""
+    h, k = half, hole / 2.0
+    corners = np.array([[x, y, z] for z in (-1, 1) for y in (-1, 1) for x in (-1, 1)], dtype=np.float64) * h
+    tris = []
+    verts = [c for c in corners]
+    q = [(0, 2, 3, 1), (0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5)]  # every face of cube() but +z
+    for a, b, c, d in q:
+        tris += [(a, b, c), (a, c, d)]
+
+    def quad(p0, p1, p2, p3):
+        n = len(verts)
+        verts.extend([np.array(p, dtype=np.float64) for p in (p0, p1, p2, p3)])
+        tris.extend([(n, n + 1, n + 2), (n, n + 2, n + 3)])
+    z = h
+    quad((-h, -h, z), (h, -h, z), (h, -k, z), (-h, -k, z))   # below the hole
+    quad((-h, k, z), (h, k, z), (h, h, z), (-h, h, z))       # above it
+    quad((-h, -k, z), (-k, -k, z), (-k, k, z), (-h, k, z))   # left of it
+    quad((k, -k, z), (h, -k, z), (h, k, z), (k, k, z))       # right of it
+    return _f32(_rotate(np.array(verts))), np.array(tris, dtype=np.int32)
+
+
+def spiral_maze(n=96, closed_core=True):
+    """A bitmask (bool[Z, Y, X], n^3) of nested cubic shells one cell thick with a one-cell gap between them.  Shell k has a single opening at the
+    centre of its +x face (k even) or -x face (k odd), so the way in from the boundary winds half around every shell: at least three turns per
+    shell.  With closed_core the innermost shell has no opening and its inside is the interior."""
+    m = np.zeros((n, n, n), dtype=bool)
+    c = n // 2
+    shells = []
+    lo = 1
+    while n - 1 - lo - lo >= 4:
+        shells.append(lo)
+        lo += 2
+    for k, lo in enumerate(shells):
+        hi = n - 1 - lo
+        m[lo:hi + 1, lo:hi + 1, lo] = m[lo:hi + 1, lo:hi + 1, hi] = True
+        m[lo:hi + 1, lo, lo:hi + 1] = m[lo:hi + 1, hi, lo:hi + 1] = True
+        m[lo, lo:hi + 1, lo:hi + 1] = m[hi, lo:hi + 1, lo:hi + 1] = True
+        if not (closed_core and k == len(shells) - 1):
+            m[c, c, hi if k % 2 == 0 else lo] = False
+    return m
+
 def write_obj(path, verts, tris, header="synthetic scene"):
     v = np.asarray(verts, dtype=np.float32)
     t = np.asarray(tris, dtype=np.int64) + 1
