@@ -263,6 +263,28 @@ vx_status vx_grid_fill_interior(vx_grid* g);
 vx_status vx_grid_interior(const vx_grid* g, uint64_t* count);
 /* diagnostics: the flood-fill rounds that fill took, the final quiet round included (0: no fill, or a grid with an axis below 3 cells) */
 uint32_t vx_grid_fill_rounds(const vx_grid* g);
+/* Exact Euclidean distance fields of the bitmask.  A cell is c = (x, y, z); outputs hold one value per cell at x + X*(y + Y*z).  M = the
+ * occupied cells of the bitmask as it stands when the call is queued (after the last build, setVoxel, fill_interior, or an external write
+ * followed by vx_grid_refresh).  Only cells of the grid count: nothing outside it is empty or occupied.
+ *   flags 0                D_out(c) = min over o in M of (cx-ox)^2 + (cy-oy)^2 + (cz-oz)^2, in cell units, exact: 0 on M;
+ *                          0xFFFFFFFF everywhere when M is empty
+ *   VX_DISTANCE_INSIDE     D_in(c) = the same minimum over the empty cells of the grid: 0 off M; 0xFFFFFFFF everywhere when every cell is
+ *                          occupied
+ *   vx_grid_sdf*           s(c) = vs * sqrtf((float)D_out(c)) off M, -(vs * sqrtf((float)D_in(c))) on M (vs = the voxel size; (float) rounds
+ *                          to nearest even, sqrtf and * are correctly rounded f32); the sentinel gives +inf / -inf; no cell is 0.  Bit for
+ *                          bit the float32 evaluation of that formula.
+ * A grid with (X-1)^2 + (Y-1)^2 + (Z-1)^2 > 0xFFFFFFFE fails with VX_ERR_CAPACITY before anything is queued (65536 x 2 x 2 is accepted,
+ * 65537 x 1 x 1 is not).  A NULL grid or buffer or unknown flag bits: VX_ERR_INVALID_ARG; capacity (in values) < X*Y*Z: VX_ERR_CAPACITY;
+ * every failure writes nothing.  A grid of 0 cells (e.g. after a failed build): VX_OK, nothing written.
+ * The _device variants queue on the grid's stream (the one its builds and ray batches use) and return without a host wait; the host variants
+ * return once host_out is written.  Nothing a reader of the grid can see changes (bitmask, counts, lists, materials; a pending
+ * VX_VOXELIZE_LIST_ASYNC emission is neither forced nor dropped; a bound list buffer is untouched).  Scratch comes from the library's pool:
+ * a repeated call at the same dimensions allocates nothing. */
+#define VX_DISTANCE_INSIDE 1
+vx_status vx_grid_distance_sq_device(const vx_grid* g, uint32_t flags, uint32_t* dev_out, uint64_t capacity);
+vx_status vx_grid_distance_sq(const vx_grid* g, uint32_t flags, uint32_t* host_out, uint64_t capacity);
+vx_status vx_grid_sdf_device(const vx_grid* g, float* dev_out, uint64_t capacity);
+vx_status vx_grid_sdf(const vx_grid* g, float* host_out, uint64_t capacity);
 /* getAabbs (voxelgridBool.cpp:18-52, voxelgridAABBstruct.cpp:10-22, voxelgridVecEncoding.cpp:15-18).
  * *count receives the list length; at most `capacity` entries are written (capacity 0 = size query). */
 vx_status vx_grid_aabbs(const vx_grid* g, vx_aabb* host_out, uint64_t capacity, uint64_t* count);

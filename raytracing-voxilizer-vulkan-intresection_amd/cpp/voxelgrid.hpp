@@ -180,6 +180,22 @@ public:
     float voxelSize() const noexcept { return m_voxelSize; }
     vec3 origin() const noexcept { return m_org; }
 
+    // Exact distance fields of the occupancy (vx_grid_distance_sq / vx_grid_sdf), one value per cell at x + X*(y + Y*z).
+    // squaredDistances: squared distance in cells to the nearest occupied cell (inside: to the nearest empty one), 0xFFFFFFFF when there is none.
+    // signedDistances: voxelSize() * sqrt of the outside distance off the occupied cells, minus that of the inside distance on them.
+    std::vector<uint32_t> squaredDistances(bool inside = false) const
+    {
+        std::vector<uint32_t> ret(m_x * m_y * m_z);
+        vxdetail::check(vx_grid_distance_sq(m_grid.get(), inside ? VX_DISTANCE_INSIDE : 0u, ret.data(), ret.size()));
+        return ret;
+    }
+    std::vector<float> signedDistances() const
+    {
+        std::vector<float> ret(m_x * m_y * m_z);
+        vxdetail::check(vx_grid_sdf(m_grid.get(), ret.data(), ret.size()));
+        return ret;
+    }
+
     // Abstract methods (voxelgrid.hpp:124-127)
     virtual std::vector<Aabb> getAabbs() const noexcept = 0;
     virtual void setVoxel(size_t x, size_t y, size_t z, const MaterialObj& material = MaterialObj{}) = 0;

@@ -37,6 +37,10 @@
 //   --solid                             solid voxelization (VX_VOXELIZE_SOLID): the enclosed empty cells are filled after the triangle loop;
 //                                       one more line gives their count.  bool / aabbstruct / vec with their options; not with --grid octree,
 //                                       --gpus N > 1 or --bench
+//   --sdf FILE                          the grid's signed distance field (vx_grid_sdf: voxel size x Euclidean distance to the nearest occupied
+//                                       cell, negative inside by the distance to the nearest empty one) as raw little-endian f32, x fastest,
+//                                       X*Y*Z values; one line gives the dims and the finite min / max.  bool / aabbstruct / vec, with or
+//                                       without --solid; not with --grid octree, --gpus N > 1 or --bench
 //   --materials                         switch on the reference's commented-out material plumbing (usemtl / mtllib -> per-voxel
 //                                       material ids; VoxelBuilder.hpp:375-395): --render shades with them, --dump-materials FILE writes
 //                                       getMatIdx() as int16
@@ -44,7 +48,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <algorithm>
 #include <fstream>
+#include <limits>
 #include <sstream>
 #include <string>
 
@@ -316,7 +322,7 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
 template <class T, bool P>
 int run_grid(const std::string& path, float vs, const std::string& dumpFile, const char* label, const std::string& renderFile = "",
              uint32_t rw = 1280, uint32_t rh = 720, bool materials = false, const std::string& matDump = "", const std::string& cameraDump = "",
-             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0, bool solid = false)
+             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0, bool solid = false, const std::string& sdfFile = "")
 {
     VoxelBuilder<T, P> voxelBuilder{std::filesystem::path(path)};
     voxelBuilder.withMaterials(materials);
@@ -343,6 +349,16 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
     std::printf("[voxhip] %s: %zu AABBs, %.1f Mvoxels/s build (host wall, incl. launch+sync), %.1f M AABBs/s getAabbs (incl. D2H copy)\n", label,
                 aabbs.size(), cells / sb / 1e6, aabbs.size() / (sa > 0 ? sa : 1e-9) / 1e6);
     dump(dumpFile, aabbs);
+    if (!sdfFile.empty()) {
+        const std::vector<float> sdf = vox.signedDistances();
+        float lo = std::numeric_limits<float>::infinity(), hi = -lo;
+        for (const float v : sdf)
+            if (std::isfinite(v)) { lo = std::min(lo, v); hi = std::max(hi, v); }
+        std::ofstream f(sdfFile, std::ios::binary);
+        f.write(reinterpret_cast<const char*>(sdf.data()), (std::streamsize)(sdf.size() * sizeof(float)));
+        if (!f) throw std::runtime_error("cannot write " + sdfFile);
+        std::printf("[voxhip] sdf: %zu x %zu x %zu cells, min %g max %g\n", vox.dimX(), vox.dimY(), vox.dimZ(), (double)lo, (double)hi);
+    }
     RenderOpts ro;
     ro.cameraDump = cameraDump;
     ro.mesh = mesh;
@@ -365,14 +381,14 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE]\n",
                      argv[0]);
         return 2;
     }
     const std::string path = argv[1];
     float vs = 0.f;
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
-    std::string grid = "bool", dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
+    std::string grid = "bool", sdfFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false, attributes = false, solid = false;
     int gpus = 1;
@@ -392,6 +408,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--instances") && i + 1 < argc) instFile = argv[++i];
         else if (!std::strcmp(argv[i], "--attributes")) attributes = true;
         else if (!std::strcmp(argv[i], "--solid")) solid = true;
+        else if (!std::strcmp(argv[i], "--sdf") && i + 1 < argc) sdfFile = argv[++i];
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
@@ -415,6 +432,10 @@ int main(int argc, char** argv)
     }
     if (solid && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
         std::fprintf(stderr, "--solid fills the interior of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (!sdfFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
+        std::fprintf(stderr, "--sdf writes the distance field of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
         return 2;
     }
     std::vector<int> devices;
@@ -500,12 +521,12 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid)
-                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid);
-        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, false, "", "", {}, nullptr, 0, solid)
-                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, false, "", "", {}, nullptr, 0, solid);
-        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid)
-                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid);
+        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile)
+                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile);
+        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile)
+                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile);
+        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile)
+                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile);
         std::fprintf(stderr, "unknown grid flavour %s\n", grid.c_str());
         return 2;
     } catch (const std::exception& e) {

@@ -412,6 +412,8 @@ struct vx_grid {
     DevBuf words, twords /*tiled build mask (launch_voxelize)*/, cwords, c2words, bricks, idxtmp, ttmp, camera, wprefix, wsel /*word of every 1024th occupied voxel (prefix scan)*/, wp16 /*every 16th entry of wprefix, dense (prefix scan)*/, recs, ext /*high bits of the candidate ranges*/, units, ubase, btri, umask, bhits /*hits per block of 64 units*/, hbase /*their exclusive scan*/, scantmp, small, vec, matids, mattmp;
     // solid voxelization (vx_solid.hip): padded mask, exterior, H in the reference's layout (padded rows only) and the word prefix over H
     DevBuf solid_m, solid_e, solid_h, solid_pre, solid_agg /*the column scans' per-chunk words*/;
+    // distance fields (vx_distance.hip): the envelopes' stacks, and the field itself for the host variants
+    DevBuf dist_stk, dist_out;
     uint64_t interior = 0;        // |H| of the last build or fill on the handle (vx_grid_interior)
     uint32_t solid_rounds = 0;    // rounds of that fill, the quiet one included (vx_grid_fill_rounds)
     uint64_t mat_interior = 0;    // a solid VX_VOXELIZE_MATERIALS build: ids of interior voxels / calls still to be given MaterialObj{}'s index
@@ -537,7 +539,7 @@ struct vx_grid {
     void set_dev(int d)
     {
         device = d;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg}) b->dev = d;
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out}) b->dev = d;
     }
     // the stream this handle queues work on; the pool orders the reuse of released blocks by it
     void set_stream(hipStream_t st)
@@ -547,11 +549,11 @@ struct vx_grid {
             (void)hipStreamSynchronize(stream);
         }
         stream = st;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg}) b->stream = st;
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out}) b->stream = st;
     }
     void release_all()
     {
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg}) b->release();
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out}) b->release();
         if (mail) (void)hipHostFree(mail);
         mail = nullptr;
     }
@@ -1925,6 +1927,82 @@ vx_status vx_grid_interior(const vx_grid* g, uint64_t* count)
 }
 
 uint32_t vx_grid_fill_rounds(const vx_grid* g) { return g ? g->solid_rounds : 0; }
+
+// Distance fields: the argument checks in the order the header lists them, then the three passes on the grid's stream (vx_distance.hip).
+// Nothing the grid's readers see is touched: the passes only read the bitmask, and a pending list emission (which reads it too) stays pending.
+static vx_status distance_check(const vx_grid* g, uint64_t cap, uint64_t* n)
+{
+    *n = 0;
+    if (!g->g.nvox) return VX_OK;  // (a grid of 0 cells: nothing to write)
+    const uint64_t d0 = g->g.dim[0] - 1ull, d1 = g->g.dim[1] - 1ull, d2 = g->g.dim[2] - 1ull;
+    if (d0 * d0 + d1 * d1 + d2 * d2 > 0xFFFFFFFEull) return fail(VX_ERR_CAPACITY, "distance fields need (X-1)^2 + (Y-1)^2 + (Z-1)^2 <= 0xFFFFFFFE");
+    if (cap < g->g.nvox) return fail(VX_ERR_CAPACITY, "distance field buffer too small");
+    *n = g->g.nvox;
+    return VX_OK;
+}
+
+static vx_status distance_queue(vx_grid* g, int mode, void* dev_out)
+{
+    VX_HIP(g->dist_stk.ensure((size_t)vx::distance_stack_entries(g->g.dim, mode == 2) * 8));
+    vx::launch_distance(g->words.as<uint32_t>(), g->g.dim, mode, g->g.vs, static_cast<uint32_t*>(dev_out), g->dist_stk.as<uint2>(), g->stream);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+static vx_status distance_host(vx_grid* g, int mode, void* host_out, uint64_t n)
+{
+    VX_HIP(g->dist_out.ensure((size_t)n * 4));
+    VX_TRY(distance_queue(g, mode, g->dist_out.p));
+    VX_HIP(hipMemcpyAsync(host_out, g->dist_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream));
+    VX_HIP(hipStreamSynchronize(g->stream));
+    return VX_OK;
+}
+
+vx_status vx_grid_distance_sq_device(const vx_grid* gc, uint32_t flags, uint32_t* dev_out, uint64_t capacity)
+{
+    if (!gc || !dev_out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (flags & ~(uint32_t)VX_DISTANCE_INSIDE) return fail(VX_ERR_INVALID_ARG, "unknown distance flags");
+    uint64_t n = 0;
+    VX_TRY(distance_check(gc, capacity, &n));
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return distance_queue(g, (flags & VX_DISTANCE_INSIDE) ? 1 : 0, dev_out);
+}
+
+vx_status vx_grid_distance_sq(const vx_grid* gc, uint32_t flags, uint32_t* host_out, uint64_t capacity)
+{
+    if (!gc || !host_out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (flags & ~(uint32_t)VX_DISTANCE_INSIDE) return fail(VX_ERR_INVALID_ARG, "unknown distance flags");
+    uint64_t n = 0;
+    VX_TRY(distance_check(gc, capacity, &n));
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return distance_host(g, (flags & VX_DISTANCE_INSIDE) ? 1 : 0, host_out, n);
+}
+
+vx_status vx_grid_sdf_device(const vx_grid* gc, float* dev_out, uint64_t capacity)
+{
+    if (!gc || !dev_out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    uint64_t n = 0;
+    VX_TRY(distance_check(gc, capacity, &n));
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return distance_queue(g, 2, dev_out);
+}
+
+vx_status vx_grid_sdf(const vx_grid* gc, float* host_out, uint64_t capacity)
+{
+    if (!gc || !host_out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    uint64_t n = 0;
+    VX_TRY(distance_check(gc, capacity, &n));
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return distance_host(g, 2, host_out, n);
+}
 
 vx_status vx_grid_aabbs_device(const vx_grid* gc, vx_aabb* dev_out, uint64_t cap, uint64_t* count)
 {

@@ -358,6 +358,12 @@ void launch_solid_finish(uint32_t* words, const uint32_t* mp, uint32_t* ext, uin
 // ids[i] = v for i < n (only_unset: only where ids[i] < 0)
 void launch_solid_ids(int16_t* ids, uint64_t n, int16_t v, bool only_unset, hipStream_t s);
 
+// Distance fields (vx_distance.hip): x pass from the bitmask, then an exact lower envelope per y and per z column, in place in buf (N = X*Y*Z
+// values).  mode 0: D_out, 1: D_in, 2: the signed field (buf ends as f32, vs the voxel size).  stk: distance_stack_entries(dim, mode == 2)
+// entries of scratch (the envelopes' stacks, [k][column]).
+uint64_t distance_stack_entries(const uint32_t dim[3], bool is_signed);
+void launch_distance(const uint32_t* words, const uint32_t dim[3], int mode, float vs, uint32_t* buf, uint2* stk, hipStream_t s);
+
 // device radix sort of uint64 keys (octree items; vx_sort.hip); tmp sized by sort_tmp_bytes.  The two key buffers ping-pong:
 // returns 0 when the sorted keys end up in keys_a, 1 for keys_b (the other buffer is scratch afterwards).
 size_t sort_tmp_bytes(uint64_t n);

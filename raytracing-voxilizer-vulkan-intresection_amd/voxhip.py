@@ -16,6 +16,7 @@ GRID_BOOL, GRID_AABBSTRUCT, GRID_VEC = 0, 1, 2
 VOXELIZE_MATERIALS = 1
 VOXELIZE_LIST_ASYNC = 2
 VOXELIZE_SOLID = 4
+DISTANCE_INSIDE = 1
 STATUS_NAMES = {0: "VX_OK", 1: "VX_ERR_INVALID_ARG", 2: "VX_ERR_PATH", 3: "VX_ERR_PARSE", 4: "VX_ERR_OUT_OF_BOUNDS",
                 5: "VX_ERR_MORTON_BITS", 6: "VX_ERR_NO_DEVICE", 7: "VX_ERR_HIP", 8: "VX_ERR_CAPACITY", 9: "VX_ERR_UNSUPPORTED"}
 
@@ -134,7 +135,8 @@ SYMBOLS = [
     "vx_mesh_host_texture", "vx_mesh_host_material_textures", "vx_mesh_set_material_textures", "vx_mesh_set_texture", "vx_mesh_load_textures",
     "vx_voxelize", "vx_voxelize_into", "vx_voxelize_multi",
     "vx_grid_create", "vx_grid_describe", "vx_grid_set_voxel", "vx_grid_test_voxel", "vx_grid_coords", "vx_grid_bytes",
-    "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_fill_interior", "vx_grid_interior", "vx_grid_fill_rounds", "vx_grid_aabbs",
+    "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_fill_interior", "vx_grid_interior", "vx_grid_fill_rounds",
+    "vx_grid_distance_sq_device", "vx_grid_distance_sq", "vx_grid_sdf_device", "vx_grid_sdf", "vx_grid_aabbs",
     "vx_grid_aabbs_device", "vx_grid_bind_aabbs_device", "vx_grid_list_wait", "vx_grid_aabbs_device_async", "vx_grid_materials", "vx_grid_material_ids", "vx_grid_material_ids_device", "vx_grid_material_first_use",
     "vx_grid_finish_materials", "vx_multi_create", "vx_multi_voxelize", "vx_multi_grid", "vx_multi_release_grid", "vx_multi_free", "vx_sort_u64", "vx_grid_free",
     "vx_octree_build", "vx_octree_num_items", "vx_octree_num_nodes", "vx_octree_bytes", "vx_octree_items", "vx_octree_nodes",
@@ -255,6 +257,10 @@ def lib():
     L.vx_grid_interior.argtypes = [vp, u64p]
     L.vx_grid_fill_rounds.argtypes = [vp]
     L.vx_grid_fill_rounds.restype = C.c_uint32
+    L.vx_grid_distance_sq_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
+    L.vx_grid_distance_sq.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
+    L.vx_grid_sdf_device.argtypes = [vp, vp, C.c_uint64]
+    L.vx_grid_sdf.argtypes = [vp, vp, C.c_uint64]
     L.vx_grid_aabbs.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_grid_aabbs_device.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_grid_bind_aabbs_device.argtypes = [vp, vp, C.c_uint64]
@@ -552,7 +558,9 @@ class Grid:
         o.stream = stream
         h = C.c_void_p()
         _check(lib().vx_voxelize(mesh.h, np.float32(voxel_size), kind, C.byref(o), C.byref(h)))
-        return cls(h)
+        g = cls(h)
+        g._stream = stream
+        return g
 
     @classmethod
     def voxelize_multi(cls, mesh, voxel_size, devices, kind=GRID_BOOL, sat_variant=0, all_gather=False):
@@ -575,6 +583,7 @@ class Grid:
         if tris is not None:
             o.tri_begin, o.tri_end = tris
         o.stream = stream
+        self._stream = stream
         _check(lib().vx_voxelize_into(mesh.h, np.float32(voxel_size), C.byref(o), self.h))
 
     @classmethod
@@ -582,7 +591,9 @@ class Grid:
         org = (C.c_float * 3)(*origin)
         h = C.c_void_p()
         _check(lib().vx_grid_create(kind, x, y, z, np.float32(voxel_size), org, stream, C.byref(h)))
-        return cls(h)
+        g = cls(h)
+        g._stream = stream
+        return g
 
     def describe(self):
         d = GridDesc()
@@ -634,6 +645,62 @@ class Grid:
     def fill_rounds(self):
         """Flood-fill rounds of the last solid build or fill_interior, the final quiet round included."""
         return int(lib().vx_grid_fill_rounds(self.h))
+
+    def _cells(self):
+        x, y, z = self.describe()["dim"]
+        return (z, y, x), x * y * z
+
+    def distance_sq(self, inside=False):
+        """vx_grid_distance_sq: the exact squared distance (cell units) of every cell to the nearest occupied cell (inside=True: to the
+        nearest empty cell) -> numpy uint32 [Z, Y, X]; 0xFFFFFFFF where no such cell exists."""
+        shape, n = self._cells()
+        out = np.zeros(shape, dtype=np.uint32)
+        _check(lib().vx_grid_distance_sq(self.h, DISTANCE_INSIDE if inside else 0, out.ctypes.data, n))
+        return out
+
+    def sdf(self):
+        """vx_grid_sdf: the signed distance field -> numpy float32 [Z, Y, X]; vs * sqrt(D_out) off the mask, -vs * sqrt(D_in) on it."""
+        shape, n = self._cells()
+        out = np.zeros(shape, dtype=np.float32)
+        _check(lib().vx_grid_sdf(self.h, out.ctypes.data, n))
+        return out
+
+    def _device_out(self, out, dtypes, name):
+        import torch
+        shape, n = self._cells()
+        if out is None:
+            out = torch.empty(shape, dtype=dtypes[0], device="cuda")
+        if out.dtype not in dtypes or out.numel() != n or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous device %s tensor of X*Y*Z elements" % name)
+        return out, n
+
+    def _record(self, out):
+        """the caching allocator must not hand `out` out again before the grid's stream has written it"""
+        import torch
+        st = getattr(self, "_stream", None)
+        if hasattr(st, "cuda_stream"):
+            out.record_stream(st)
+        elif st:
+            out.record_stream(torch.cuda.ExternalStream(st))
+        else:
+            out.record_stream(torch.cuda.default_stream(out.device))
+
+    def distance_sq_device(self, out=None, inside=False):
+        """vx_grid_distance_sq_device, asynchronous on the grid's stream -> `out`, a device torch.uint32 tensor [Z, Y, X] (an int32
+        tensor receives the same bits)."""
+        import torch
+        out, n = self._device_out(out, (torch.uint32, torch.int32), "uint32 / int32")
+        _check(lib().vx_grid_distance_sq_device(self.h, DISTANCE_INSIDE if inside else 0, out.data_ptr(), n))
+        self._record(out)
+        return out
+
+    def sdf_device(self, out=None):
+        """vx_grid_sdf_device, asynchronous on the grid's stream -> `out`, a device torch.float32 tensor [Z, Y, X]."""
+        import torch
+        out, n = self._device_out(out, (torch.float32,), "float32")
+        _check(lib().vx_grid_sdf_device(self.h, out.data_ptr(), n))
+        self._record(out)
+        return out
 
     def aabbs(self):
         n = C.c_uint64()
