@@ -285,6 +285,27 @@ vx_status vx_grid_distance_sq_device(const vx_grid* g, uint32_t flags, uint32_t*
 vx_status vx_grid_distance_sq(const vx_grid* g, uint32_t flags, uint32_t* host_out, uint64_t capacity);
 vx_status vx_grid_sdf_device(const vx_grid* g, float* dev_out, uint64_t capacity);
 vx_status vx_grid_sdf(const vx_grid* g, float* host_out, uint64_t capacity);
+/* The boundary mesh of the bitmask M (as it stands when the call is queued, as for the distance fields).  Cell c = (x, y, z) in M has a face
+ * in direction d = 0..5 (-X, +X, -Y, +Y, -Z, +Z) when c + e_d is outside the grid or not in M.  Lattice points (i, j, k), 0 <= i <= X,
+ * 0 <= j <= Y, 0 <= k <= Z, index i + (X+1)*(j + (Y+1)*k), lie per axis at org + ((float)i + 0.5f)*vs - half (f32, no contraction: the minimum
+ * corner of cell i's AABB, continued to i = X).  Vertices: the lattice points some face touches (equivalently: the 2x2x2 cells around them
+ * are mixed), in ascending lattice index.  Triangles: faces in ascending cell index, then ascending d; each gives (c0, c1, c2), (c0, c2, c3)
+ * with c0..c3 the points (x+dx, y+dy, z+dz), dx dy dz =
+ *   -X 000 001 011 010   +X 100 110 111 101   -Y 000 100 101 001   +Y 010 011 111 110   -Z 000 010 110 100   +Z 001 101 111 011
+ * (counter-clockwise seen from the empty side).  mat (optional): per triangle the cell's entry of vx_grid_material_ids, a VX_GRID_BOOL /
+ * VX_GRID_AABBSTRUCT grid built with VX_VOXELIZE_MATERIALS only (VX_GRID_VEC: VX_ERR_UNSUPPORTED; any other grid: VX_ERR_INVALID_ARG).
+ * Capacities in vertices (3 f32 each) and triangles (3 int32 each; mat: 1 int32 each).  Both capacities 0 = size query (buffers may be
+ * NULL).  Either capacity short: VX_ERR_CAPACITY, counts reported, nothing written.  V or T above 2^31 - 1: VX_ERR_CAPACITY, counts
+ * reported, nothing written.  A NULL grid or buffer: VX_ERR_INVALID_ARG.  A grid of 0 cells: VX_OK, V = T = 0.
+ * The _device variant waits on the host for the two counts only and queues the emission on the grid's stream; the host variant returns once
+ * the buffers are written.  No side effects, as for the distance fields; scratch stays on the handle. */
+vx_status vx_grid_surface_device(const vx_grid* g, float* dev_xyz, uint64_t vertex_capacity, int32_t* dev_tri, uint64_t triangle_capacity,
+                                 int32_t* dev_mat, uint64_t* num_vertices, uint64_t* num_triangles);
+vx_status vx_grid_surface(const vx_grid* g, float* host_xyz, uint64_t vertex_capacity, int32_t* host_tri, uint64_t triangle_capacity,
+                          int32_t* host_mat, uint64_t* num_vertices, uint64_t* num_triangles);
+/* a mesh that owns its arrays, equal in everything observable to vx_mesh_from_arrays(the vx_grid_surface arrays) followed, with
+ * with_materials, by vx_mesh_set_materials(vx_grid_materials records, the triangle ids); usable by vx_bvh_*, vx_render_*, vx_voxelize */
+vx_status vx_grid_surface_mesh(const vx_grid* g, int with_materials, vx_mesh** out);
 /* getAabbs (voxelgridBool.cpp:18-52, voxelgridAABBstruct.cpp:10-22, voxelgridVecEncoding.cpp:15-18).
  * *count receives the list length; at most `capacity` entries are written (capacity 0 = size query). */
 vx_status vx_grid_aabbs(const vx_grid* g, vx_aabb* host_out, uint64_t capacity, uint64_t* count);

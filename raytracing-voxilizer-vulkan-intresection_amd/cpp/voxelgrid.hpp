@@ -196,6 +196,20 @@ public:
         return ret;
     }
 
+    // The boundary mesh of the occupancy (vx_grid_surface): one quad (two triangles) per exposed cell face over de-duplicated lattice
+    // points.  xyz: 3 floats per vertex; tris: 3 vertex indices per triangle; mats (optional; a grid built with materials, not VoxelGridVec):
+    // one index into getMatrials() per triangle.
+    void surface(std::vector<float>& xyz, std::vector<int32_t>& tris, std::vector<int32_t>* mats = nullptr) const
+    {
+        uint64_t nv = 0, nt = 0;
+        int32_t probe = 0;
+        vxdetail::check(vx_grid_surface(m_grid.get(), nullptr, 0, nullptr, 0, mats ? &probe : nullptr, &nv, &nt));
+        xyz.assign(nv * 3, 0.0f);
+        tris.assign(nt * 3, 0);
+        if (mats) mats->assign(nt, 0);
+        if (nv || nt) vxdetail::check(vx_grid_surface(m_grid.get(), xyz.data(), nv, tris.data(), nt, mats ? mats->data() : nullptr, &nv, &nt));
+    }
+
     // Abstract methods (voxelgrid.hpp:124-127)
     virtual std::vector<Aabb> getAabbs() const noexcept = 0;
     virtual void setVoxel(size_t x, size_t y, size_t z, const MaterialObj& material = MaterialObj{}) = 0;

@@ -41,6 +41,11 @@
 //                                       cell, negative inside by the distance to the nearest empty one) as raw little-endian f32, x fastest,
 //                                       X*Y*Z values; one line gives the dims and the finite min / max.  bool / aabbstruct / vec, with or
 //                                       without --solid; not with --grid octree, --gpus N > 1 or --bench
+//   --surface FILE.obj                  the boundary mesh of the grid (vx_grid_surface: two triangles per exposed cell face over shared lattice
+//                                       points) as an OBJ: `v` lines in vertex order, then `f` lines (1-based) in triangle order.  With
+//                                       --materials also FILE.mtl (one `newmtl m<id>` per grid material) and a `usemtl m<id>` before each run
+//                                       of equal ids.  bool / aabbstruct / vec, with or without --solid; not with --grid octree, --gpus N > 1,
+//                                       --bench, or --materials with --grid vec
 //   --materials                         switch on the reference's commented-out material plumbing (usemtl / mtllib -> per-voxel
 //                                       material ids; VoxelBuilder.hpp:375-395): --render shades with them, --dump-materials FILE writes
 //                                       getMatIdx() as int16
@@ -319,10 +324,54 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
     return 0;
 }
 
+// --surface: the grid's boundary mesh as an OBJ (and, with materials, its MTL beside it)
+template <class T>
+void write_surface(const T& vox, const std::string& file, bool materials)
+{
+    std::vector<float> xyz;
+    std::vector<int32_t> tris, mats;
+    vox.surface(xyz, tris, materials ? &mats : nullptr);
+    std::FILE* f = std::fopen(file.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + file);
+    if (materials) {
+        std::string mtl = file;
+        const size_t dot = mtl.find_last_of('.'), slash = mtl.find_last_of("/\\");
+        if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) mtl.resize(dot);
+        mtl += ".mtl";
+        std::vector<vx_material> recs;
+        uint64_t n = 0;
+        vxdetail::check(vx_grid_materials(vox.handle(), nullptr, 0, &n));
+        recs.resize(n);
+        if (n) vxdetail::check(vx_grid_materials(vox.handle(), recs.data(), n, &n));
+        std::FILE* m = std::fopen(mtl.c_str(), "w");
+        if (!m) { std::fclose(f); throw std::runtime_error("cannot write " + mtl); }
+        for (size_t i = 0; i < recs.size(); ++i) {
+            const vx_material& r = recs[i];
+            std::fprintf(m, "newmtl m%zu\n", i);
+            const float* v3[5] = {r.ambient, r.diffuse, r.specular, r.transmittance, r.emission};
+            const char* k3[5] = {"Ka", "Kd", "Ks", "Tf", "Ke"};
+            for (int k = 0; k < 5; ++k) std::fprintf(m, "%s %.9g %.9g %.9g\n", k3[k], (double)v3[k][0], (double)v3[k][1], (double)v3[k][2]);
+            std::fprintf(m, "Ns %.9g\nNi %.9g\nd %.9g\nillum %d\n", (double)r.shininess, (double)r.ior, (double)r.dissolve, (int)r.illum);
+        }
+        std::fclose(m);
+        const size_t s2 = mtl.find_last_of("/\\");
+        std::fprintf(f, "mtllib %s\n", s2 == std::string::npos ? mtl.c_str() : mtl.c_str() + s2 + 1);
+    }
+    for (size_t i = 0; i < xyz.size(); i += 3) std::fprintf(f, "v %.9g %.9g %.9g\n", (double)xyz[i], (double)xyz[i + 1], (double)xyz[i + 2]);
+    for (size_t t = 0; t < tris.size() / 3; ++t) {
+        if (materials && (t == 0 || mats[t] != mats[t - 1])) std::fprintf(f, "usemtl m%d\n", (int)mats[t]);
+        std::fprintf(f, "f %d %d %d\n", tris[3 * t] + 1, tris[3 * t + 1] + 1, tris[3 * t + 2] + 1);
+    }
+    const bool ok = std::ferror(f) == 0;
+    if (std::fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + file);
+    std::printf("[voxhip] surface: %zu vertices, %zu triangles\n", xyz.size() / 3, tris.size() / 3);
+}
+
 template <class T, bool P>
 int run_grid(const std::string& path, float vs, const std::string& dumpFile, const char* label, const std::string& renderFile = "",
              uint32_t rw = 1280, uint32_t rh = 720, bool materials = false, const std::string& matDump = "", const std::string& cameraDump = "",
-             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0, bool solid = false, const std::string& sdfFile = "")
+             const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0, bool solid = false, const std::string& sdfFile = "",
+             const std::string& surfaceFile = "")
 {
     VoxelBuilder<T, P> voxelBuilder{std::filesystem::path(path)};
     voxelBuilder.withMaterials(materials);
@@ -359,6 +408,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
         if (!f) throw std::runtime_error("cannot write " + sdfFile);
         std::printf("[voxhip] sdf: %zu x %zu x %zu cells, min %g max %g\n", vox.dimX(), vox.dimY(), vox.dimZ(), (double)lo, (double)hi);
     }
+    if (!surfaceFile.empty()) write_surface(vox, surfaceFile, materials);
     RenderOpts ro;
     ro.cameraDump = cameraDump;
     ro.mesh = mesh;
@@ -381,14 +431,14 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj]\n",
                      argv[0]);
         return 2;
     }
     const std::string path = argv[1];
     float vs = 0.f;
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
-    std::string grid = "bool", sdfFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
+    std::string grid = "bool", sdfFile, surfaceFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false, attributes = false, solid = false;
     int gpus = 1;
@@ -409,6 +459,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--attributes")) attributes = true;
         else if (!std::strcmp(argv[i], "--solid")) solid = true;
         else if (!std::strcmp(argv[i], "--sdf") && i + 1 < argc) sdfFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
@@ -436,6 +487,10 @@ int main(int argc, char** argv)
     }
     if (!sdfFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
         std::fprintf(stderr, "--sdf writes the distance field of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (!surfaceFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0 || (materials && grid == "vec"))) {
+        std::fprintf(stderr, "--surface writes the boundary mesh of one grid on one device: not with --grid octree, --gpus N > 1, --bench, or --materials with --grid vec\n");
         return 2;
     }
     std::vector<int> devices;
@@ -521,12 +576,13 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile)
-                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile);
-        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile)
-                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile);
-        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile)
-                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile);
+        const bool surfMat = materials && !surfaceFile.empty();  // (--materials reaches an aabbstruct grid only for its surface's ids)
+        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile)
+                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile);
+        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, surfMat, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile)
+                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, surfMat, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile);
+        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile)
+                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile);
         std::fprintf(stderr, "unknown grid flavour %s\n", grid.c_str());
         return 2;
     } catch (const std::exception& e) {

@@ -191,6 +191,7 @@ struct Mail {
     float bbox[8];
     unsigned long long units, hits, occupied, pad;
     unsigned long long solid_rounds, interior;  // solid fill: changed rounds of the last batch, |H|
+    unsigned long long surf_tris, surf_verts;   // surface mesh: T and V
 };
 
 // Totals may arrive tagged with the build's sequence number in bits 48..63 (see launch_scan_u32): the host then polls the word
@@ -414,6 +415,8 @@ struct vx_grid {
     DevBuf solid_m, solid_e, solid_h, solid_pre, solid_agg /*the column scans' per-chunk words*/;
     // distance fields (vx_distance.hip): the envelopes' stacks, and the field itself for the host variants
     DevBuf dist_stk, dist_out;
+    // surface mesh (vx_surface.hip): triangles per mask word and their scan, the used lattice points and their scan, the host variant's arrays
+    DevBuf surf_cnt, surf_tpre, surf_cm, surf_vpre, surf_out;
     uint64_t interior = 0;        // |H| of the last build or fill on the handle (vx_grid_interior)
     uint32_t solid_rounds = 0;    // rounds of that fill, the quiet one included (vx_grid_fill_rounds)
     uint64_t mat_interior = 0;    // a solid VX_VOXELIZE_MATERIALS build: ids of interior voxels / calls still to be given MaterialObj{}'s index
@@ -539,7 +542,7 @@ struct vx_grid {
     void set_dev(int d)
     {
         device = d;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out}) b->dev = d;
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out}) b->dev = d;
     }
     // the stream this handle queues work on; the pool orders the reuse of released blocks by it
     void set_stream(hipStream_t st)
@@ -549,11 +552,11 @@ struct vx_grid {
             (void)hipStreamSynchronize(stream);
         }
         stream = st;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out}) b->stream = st;
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out}) b->stream = st;
     }
     void release_all()
     {
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out}) b->release();
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out}) b->release();
         if (mail) (void)hipHostFree(mail);
         mail = nullptr;
     }
@@ -2002,6 +2005,127 @@ vx_status vx_grid_sdf(const vx_grid* gc, float* host_out, uint64_t capacity)
     vx_grid* g = const_cast<vx_grid*>(gc);
     DeviceGuard dg(g->device);
     return distance_host(g, 2, host_out, n);
+}
+
+// Surface mesh: the argument checks in the header's order, the counting pass and both scans on the grid's stream, one host wait for the
+// totals, then the emission (vx_surface.hip).  The passes only read the bitmask (and, with materials, the word prefix and the ids); a
+// pending list emission stays pending.
+static vx_status surface_materials(const vx_grid* g, const int16_t** ids)
+{
+    if (g->kind == VX_GRID_VEC) return fail(VX_ERR_UNSUPPORTED, "surface materials: a Vec grid's cell may carry several records");
+    if (!g->has_materials) return fail(VX_ERR_INVALID_ARG, "surface materials: the grid was not built with VX_VOXELIZE_MATERIALS");
+    *ids = vx_grid_material_ids_device(g);
+    return VX_OK;
+}
+
+// counts -> *nv / *nt; the emission's inputs stay in the handle's scratch.  *mat_ids: the per-cell ids when want_mat (word prefix queued).
+static vx_status surface_count(vx_grid* g, bool want_mat, uint64_t* nv, uint64_t* nt, const int16_t** mat_ids)
+{
+    *nv = *nt = 0;
+    const int16_t* ids = nullptr;
+    if (want_mat) VX_TRY(surface_materials(g, &ids));
+    *mat_ids = ids;
+    if (!g->g.nvox) return VX_OK;
+    const vx::SurfacePlan p = vx::surface_plan(g->g);
+    const uint64_t nmax = g->g.nwords > p.nlw ? g->g.nwords : p.nlw;
+    VX_HIP(g->surf_cnt.ensure((size_t)(g->g.nwords + 4) * 4));
+    VX_HIP(g->surf_tpre.ensure((size_t)(g->g.nwords + 4) * 4));
+    VX_HIP(g->surf_cm.ensure((size_t)(p.nlw + 4) * 4));
+    VX_HIP(g->surf_vpre.ensure((size_t)(p.nlw + 4) * 4));
+    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nmax), g->stream));
+    bool pending = false;
+    if (want_mat) VX_TRY(prefix_launch(g, &pending));
+    vx::launch_surface_count(g->words.as<uint32_t>(), g->g, p, g->surf_cnt.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->stream);
+    vx::launch_scan_u32(g->surf_cnt.as<uint32_t>(), g->surf_tpre.as<uint32_t>(), g->g.nwords, false, g->scantmp.p, &g->mail->surf_tris, g->stream, true, 0,
+                        nullptr, next_scan_gen(g->scantmp, g->stream));
+    vx::launch_scan_u32(g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(), p.nlw, true, g->scantmp.p, &g->mail->surf_verts, g->stream, true, 0,
+                        nullptr, next_scan_gen(g->scantmp, g->stream));
+    VX_HIP(hipGetLastError());
+    VX_HIP(hipStreamSynchronize(g->stream));
+    VX_TRY(prefix_finish(g, pending));
+    if (want_mat && g->occupied > (g->mat_gathered ? g->mat_gather_count : g->mat_count))
+        return fail(VX_ERR_INVALID_ARG, "surface materials: the grid's material ids do not cover its occupied cells");
+    *nt = g->mail->surf_tris & kMailValue;
+    *nv = g->mail->surf_verts & kMailValue;
+    return VX_OK;
+}
+
+static vx_status surface_check(uint64_t nv, uint64_t nt, uint64_t vcap, uint64_t tcap)
+{
+    if (nv > 0x7FFFFFFFull || nt > 0x7FFFFFFFull) return fail(VX_ERR_CAPACITY, "surface mesh above 2^31 - 1 vertices or triangles (int32 indices)");
+    if (!vcap && !tcap) return VX_OK;  // (size query)
+    if (vcap < nv || tcap < nt) return fail(VX_ERR_CAPACITY, "surface mesh buffer too small");
+    return VX_OK;
+}
+
+static vx_status surface_run(vx_grid* g, bool host, float* xyz, uint64_t vcap, int32_t* tri, uint64_t tcap, int32_t* mat, uint64_t* num_vertices,
+                             uint64_t* num_triangles)
+{
+    if ((vcap || tcap) && (!xyz || !tri)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    DeviceGuard dg(g->device);
+    uint64_t nv = 0, nt = 0;
+    const int16_t* ids = nullptr;
+    VX_TRY(surface_count(g, mat != nullptr, &nv, &nt, &ids));
+    if (num_vertices) *num_vertices = nv;
+    if (num_triangles) *num_triangles = nt;
+    VX_TRY(surface_check(nv, nt, vcap, tcap));
+    if ((!vcap && !tcap) || (!nv && !nt)) return VX_OK;
+    const vx::SurfacePlan p = vx::surface_plan(g->g);
+    float* dx = xyz;
+    int32_t* dt = tri;
+    int32_t* dm = mat;
+    if (host) {  // one staging block: positions, triangles, ids
+        VX_HIP(g->surf_out.ensure((size_t)nv * 12 + (size_t)nt * 12 + (mat ? (size_t)nt * 4 : 0) + 16));
+        dx = g->surf_out.as<float>();
+        dt = reinterpret_cast<int32_t*>(dx + 3 * nv);
+        dm = mat ? dt + 3 * nt : nullptr;
+    }
+    vx::launch_surface_emit(g->words.as<uint32_t>(), g->g, p, g->surf_tpre.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(),
+                            mat ? g->wprefix.as<uint32_t>() : nullptr, ids, dx, dt, dm, g->stream);
+    VX_HIP(hipGetLastError());
+    if (host) {
+        VX_HIP(hipMemcpyAsync(xyz, dx, (size_t)nv * 12, hipMemcpyDeviceToHost, g->stream));
+        VX_HIP(hipMemcpyAsync(tri, dt, (size_t)nt * 12, hipMemcpyDeviceToHost, g->stream));
+        if (mat) VX_HIP(hipMemcpyAsync(mat, dm, (size_t)nt * 4, hipMemcpyDeviceToHost, g->stream));
+        VX_HIP(hipStreamSynchronize(g->stream));
+    }
+    return VX_OK;
+}
+
+vx_status vx_grid_surface_device(const vx_grid* gc, float* dev_xyz, uint64_t vertex_capacity, int32_t* dev_tri, uint64_t triangle_capacity,
+                                 int32_t* dev_mat, uint64_t* num_vertices, uint64_t* num_triangles)
+{
+    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return surface_run(const_cast<vx_grid*>(gc), false, dev_xyz, vertex_capacity, dev_tri, triangle_capacity, dev_mat, num_vertices, num_triangles);
+}
+
+vx_status vx_grid_surface(const vx_grid* gc, float* host_xyz, uint64_t vertex_capacity, int32_t* host_tri, uint64_t triangle_capacity,
+                          int32_t* host_mat, uint64_t* num_vertices, uint64_t* num_triangles)
+{
+    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return surface_run(const_cast<vx_grid*>(gc), true, host_xyz, vertex_capacity, host_tri, triangle_capacity, host_mat, num_vertices, num_triangles);
+}
+
+vx_status vx_grid_surface_mesh(const vx_grid* gc, int with_materials, vx_mesh** out)
+{
+    if (!gc || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (with_materials) {
+        const int16_t* ids = nullptr;
+        VX_TRY(surface_materials(gc, &ids));
+    }
+    uint64_t nv = 0, nt = 0;
+    VX_TRY(vx_grid_surface(gc, nullptr, 0, nullptr, 0, nullptr, &nv, &nt));
+    std::vector<float> xyz((size_t)nv * 3 + 1);
+    std::vector<int32_t> tri((size_t)nt * 3 + 1), mat(with_materials ? (size_t)nt + 1 : 0);
+    if (nv || nt) VX_TRY(vx_grid_surface(gc, xyz.data(), nv, tri.data(), nt, with_materials ? mat.data() : nullptr, &nv, &nt));
+    vx_mesh* m = nullptr;
+    VX_TRY(vx_mesh_from_arrays(xyz.data(), (size_t)nv, tri.data(), (size_t)nt, &m));
+    if (with_materials) {
+        const vx_status st = vx_mesh_set_materials(m, gc->materials.data(), gc->materials.size(), mat.data());
+        if (st != VX_OK) { vx_mesh_free(m); return st; }
+    }
+    *out = m;
+    return VX_OK;
 }
 
 vx_status vx_grid_aabbs_device(const vx_grid* gc, vx_aabb* dev_out, uint64_t cap, uint64_t* count)

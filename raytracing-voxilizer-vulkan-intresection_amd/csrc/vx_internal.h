@@ -364,6 +364,19 @@ void launch_solid_ids(int16_t* ids, uint64_t n, int16_t v, bool only_unset, hipS
 uint64_t distance_stack_entries(const uint32_t dim[3], bool is_signed);
 void launch_distance(const uint32_t* words, const uint32_t dim[3], int mode, float vs, uint32_t* buf, uint2* stk, hipStream_t s);
 
+// Surface mesh (vx_surface.hip): npts = (X+1)(Y+1)(Z+1) lattice points, nlw = ceil(npts / 32) corner words.
+struct SurfacePlan {
+    uint64_t npts = 0, nlw = 0;
+};
+SurfacePlan surface_plan(const GridParams& g);
+// tcount (nwords): triangles of every mask word; cmask (nlw): the used lattice points, one bit each
+void launch_surface_count(const uint32_t* words, const GridParams& g, const SurfacePlan& p, uint32_t* tcount, uint32_t* cmask, hipStream_t s);
+// tpre / vpre: exclusive scans of tcount / of cmask's popcounts.  Positions (3 f32 per vertex), triangles (3 int32) and, with cell_mat
+// (the per-occupied-cell ids, indexed through wprefix = the word prefix of the mask) and mat non-null, one id per triangle.
+void launch_surface_emit(const uint32_t* words, const GridParams& g, const SurfacePlan& p, const uint32_t* tpre, const uint32_t* cmask,
+                         const uint32_t* vpre, const uint32_t* wprefix, const int16_t* cell_mat, float* xyz, int32_t* tri, int32_t* mat,
+                         hipStream_t s);
+
 // device radix sort of uint64 keys (octree items; vx_sort.hip); tmp sized by sort_tmp_bytes.  The two key buffers ping-pong:
 // returns 0 when the sorted keys end up in keys_a, 1 for keys_b (the other buffer is scratch afterwards).
 size_t sort_tmp_bytes(uint64_t n);

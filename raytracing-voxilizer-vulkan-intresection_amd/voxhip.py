@@ -136,7 +136,8 @@ SYMBOLS = [
     "vx_voxelize", "vx_voxelize_into", "vx_voxelize_multi",
     "vx_grid_create", "vx_grid_describe", "vx_grid_set_voxel", "vx_grid_test_voxel", "vx_grid_coords", "vx_grid_bytes",
     "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_fill_interior", "vx_grid_interior", "vx_grid_fill_rounds",
-    "vx_grid_distance_sq_device", "vx_grid_distance_sq", "vx_grid_sdf_device", "vx_grid_sdf", "vx_grid_aabbs",
+    "vx_grid_distance_sq_device", "vx_grid_distance_sq", "vx_grid_sdf_device", "vx_grid_sdf",
+    "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh", "vx_grid_aabbs",
     "vx_grid_aabbs_device", "vx_grid_bind_aabbs_device", "vx_grid_list_wait", "vx_grid_aabbs_device_async", "vx_grid_materials", "vx_grid_material_ids", "vx_grid_material_ids_device", "vx_grid_material_first_use",
     "vx_grid_finish_materials", "vx_multi_create", "vx_multi_voxelize", "vx_multi_grid", "vx_multi_release_grid", "vx_multi_free", "vx_sort_u64", "vx_grid_free",
     "vx_octree_build", "vx_octree_num_items", "vx_octree_num_nodes", "vx_octree_bytes", "vx_octree_items", "vx_octree_nodes",
@@ -261,6 +262,9 @@ def lib():
     L.vx_grid_distance_sq.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_sdf_device.argtypes = [vp, vp, C.c_uint64]
     L.vx_grid_sdf.argtypes = [vp, vp, C.c_uint64]
+    L.vx_grid_surface_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, u64p, u64p]
+    L.vx_grid_surface.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, u64p, u64p]
+    L.vx_grid_surface_mesh.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.vx_grid_aabbs.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_grid_aabbs_device.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_grid_bind_aabbs_device.argtypes = [vp, vp, C.c_uint64]
@@ -701,6 +705,46 @@ class Grid:
         _check(lib().vx_grid_sdf_device(self.h, out.data_ptr(), n))
         self._record(out)
         return out
+
+    def surface_counts(self, materials=False):
+        """(V, T) of the boundary mesh (vx_grid_surface size query; materials=True also checks that the grid has per-cell ids)."""
+        nv, nt = C.c_uint64(), C.c_uint64()
+        probe = np.zeros(1, np.int32)
+        _check(lib().vx_grid_surface(self.h, None, 0, None, 0, probe.ctypes.data if materials else None, C.byref(nv), C.byref(nt)))
+        return nv.value, nt.value
+
+    def surface(self, materials=False):
+        """vx_grid_surface: the boundary mesh of the occupancy -> (verts (V, 3) float32, tris (T, 3) int32[, mats (T,) int32])."""
+        nv, nt = self.surface_counts(materials)
+        v = np.zeros((nv, 3), np.float32)
+        t = np.zeros((nt, 3), np.int32)
+        m = np.zeros(nt, np.int32) if materials else None
+        if nv or nt:
+            a, b = C.c_uint64(), C.c_uint64()
+            _check(lib().vx_grid_surface(self.h, v.ctypes.data, nv, t.ctypes.data, nt, m.ctypes.data if materials else None, C.byref(a), C.byref(b)))
+        return (v, t, m) if materials else (v, t)
+
+    def surface_device(self, materials=False):
+        """vx_grid_surface_device: the same arrays as device torch tensors, written asynchronously on the grid's stream (the host waits
+        for the two counts only)."""
+        import torch
+        nv, nt = self.surface_counts(materials)
+        v = torch.empty((nv, 3), dtype=torch.float32, device="cuda")
+        t = torch.empty((nt, 3), dtype=torch.int32, device="cuda")
+        m = torch.empty(nt, dtype=torch.int32, device="cuda") if materials else None
+        if nv or nt:
+            a, b = C.c_uint64(), C.c_uint64()
+            _check(lib().vx_grid_surface_device(self.h, v.data_ptr(), nv, t.data_ptr(), nt, m.data_ptr() if materials else None, C.byref(a),
+                                                C.byref(b)))
+            for x in (v, t) + ((m,) if materials else ()):
+                self._record(x)
+        return (v, t, m) if materials else (v, t)
+
+    def surface_mesh(self, materials=False):
+        """vx_grid_surface_mesh: the boundary mesh as a Mesh (with materials: the grid's records and one id per triangle)."""
+        h = C.c_void_p()
+        _check(lib().vx_grid_surface_mesh(self.h, 1 if materials else 0, C.byref(h)))
+        return Mesh(h)
 
     def aabbs(self):
         n = C.c_uint64()
