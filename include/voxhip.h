@@ -306,6 +306,30 @@ vx_status vx_grid_surface(const vx_grid* g, float* host_xyz, uint64_t vertex_cap
 /* a mesh that owns its arrays, equal in everything observable to vx_mesh_from_arrays(the vx_grid_surface arrays) followed, with
  * with_materials, by vx_mesh_set_materials(vx_grid_materials records, the triangle ids); usable by vx_bvh_*, vx_render_*, vx_voxelize */
 vx_status vx_grid_surface_mesh(const vx_grid* g, int with_materials, vx_mesh** out);
+/* Connected components of the bitmask M (as it stands when the call is queued, as for the distance fields).  Two cells of M are adjacent
+ * under VX_CONNECT_6 when they share a face, under VX_CONNECT_26 when they share a face, an edge or a corner; only cells of the grid count
+ * (nothing wraps, no padding).  A component is a maximal set of cells of M that adjacency joins.  Labels: one uint32 per cell at
+ * x + X*(y + Y*z); 0 for empty cells, 1..K for cells of M, the components numbered in ascending order of their smallest cell index (exactly
+ * scipy.ndimage.label(cells[Z, Y, X], generate_binary_structure(3, 1 or 3))).  vx_component record k - 1 describes label k: its cell
+ * count and its inclusive cell-coordinate bounds, x, y, z.
+ * Checks, in this order; every failure writes nothing: a NULL grid or buffer, or a connectivity other than 6 or 26: VX_ERR_INVALID_ARG; a
+ * grid of 0 cells: VX_OK, K = 0; X*Y*Z > 2^32 - 1: VX_ERR_CAPACITY before anything is queued (32-bit labels and union-find indices: 1024^3
+ * is accepted, 2048 x 2048 x 1024 is not); label capacity < X*Y*Z or stats capacity < K: VX_ERR_CAPACITY, the count still reported where
+ * the signature has one.  vx_grid_components: host_labels NULL with capacity 0 = K only.  vx_grid_component_stats: capacity 0 = size
+ * query.  The _device variant queues on the grid's stream and returns without a host wait (dev_count: NULL, or K as one uint32 on the
+ * device); the host variants return once their outputs are written.  No side effects, as for the distance fields; scratch stays on the
+ * handle (the parent array of the union-find is the label buffer itself). */
+#define VX_CONNECT_6 6u
+#define VX_CONNECT_26 26u
+typedef struct vx_component { uint64_t cells; uint32_t min[3]; uint32_t max[3]; } vx_component;
+#ifdef __cplusplus
+static_assert(sizeof(vx_component) == 32, "vx_component is 32 bytes");
+#else
+_Static_assert(sizeof(vx_component) == 32, "vx_component is 32 bytes");
+#endif
+vx_status vx_grid_components_device(const vx_grid* g, uint32_t connectivity, uint32_t* dev_labels, uint64_t capacity, uint32_t* dev_count);
+vx_status vx_grid_components(const vx_grid* g, uint32_t connectivity, uint32_t* host_labels, uint64_t capacity, uint64_t* count);
+vx_status vx_grid_component_stats(const vx_grid* g, uint32_t connectivity, vx_component* host_out, uint64_t capacity, uint64_t* count);
 /* getAabbs (voxelgridBool.cpp:18-52, voxelgridAABBstruct.cpp:10-22, voxelgridVecEncoding.cpp:15-18).
  * *count receives the list length; at most `capacity` entries are written (capacity 0 = size query). */
 vx_status vx_grid_aabbs(const vx_grid* g, vx_aabb* host_out, uint64_t capacity, uint64_t* count);

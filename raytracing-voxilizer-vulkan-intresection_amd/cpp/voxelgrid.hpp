@@ -210,6 +210,25 @@ public:
         if (nv || nt) vxdetail::check(vx_grid_surface(m_grid.get(), xyz.data(), nv, tris.data(), nt, mats ? mats->data() : nullptr, &nv, &nt));
     }
 
+    // Connected components of the occupancy (vx_grid_components): connectivity 6 (shared faces) or 26 (faces, edges, corners).  labels
+    // gets one value per cell at x + X*(y + Y*z): 0 for empty cells, 1..K in ascending order of each component's smallest cell.  Returns K.
+    uint32_t components(int connectivity, std::vector<uint32_t>& labels) const
+    {
+        labels.assign(m_x * m_y * m_z, 0u);
+        uint64_t k = 0;
+        vxdetail::check(vx_grid_components(m_grid.get(), (uint32_t)connectivity, labels.empty() ? nullptr : labels.data(), labels.size(), &k));
+        return (uint32_t)k;
+    }
+    // componentStats: record k - 1 describes label k (cell count, inclusive cell bounds in x, y, z)
+    std::vector<vx_component> componentStats(int connectivity) const
+    {
+        uint64_t k = 0;
+        vxdetail::check(vx_grid_component_stats(m_grid.get(), (uint32_t)connectivity, nullptr, 0, &k));
+        std::vector<vx_component> ret(k);
+        if (k) vxdetail::check(vx_grid_component_stats(m_grid.get(), (uint32_t)connectivity, ret.data(), ret.size(), &k));
+        return ret;
+    }
+
     // Abstract methods (voxelgrid.hpp:124-127)
     virtual std::vector<Aabb> getAabbs() const noexcept = 0;
     virtual void setVoxel(size_t x, size_t y, size_t z, const MaterialObj& material = MaterialObj{}) = 0;

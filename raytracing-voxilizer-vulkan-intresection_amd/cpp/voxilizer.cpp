@@ -46,6 +46,11 @@
 //                                       --materials also FILE.mtl (one `newmtl m<id>` per grid material) and a `usemtl m<id>` before each run
 //                                       of equal ids.  bool / aabbstruct / vec, with or without --solid; not with --grid octree, --gpus N > 1,
 //                                       --bench, or --materials with --grid vec
+//   --components FILE.csv [--connectivity 6|26]
+//                                       the connected components of the grid's occupied cells (vx_grid_component_stats; 6: shared faces, the
+//                                       default; 26: faces, edges and corners) as CSV: a header line, then label,cells,minx,miny,minz,maxx,
+//                                       maxy,maxz per component in label order (bounds in cells, inclusive); one line gives K.  bool /
+//                                       aabbstruct / vec, with or without --solid; not with --grid octree, --gpus N > 1 or --bench
 //   --materials                         switch on the reference's commented-out material plumbing (usemtl / mtllib -> per-voxel
 //                                       material ids; VoxelBuilder.hpp:375-395): --render shades with them, --dump-materials FILE writes
 //                                       getMatIdx() as int16
@@ -371,7 +376,7 @@ template <class T, bool P>
 int run_grid(const std::string& path, float vs, const std::string& dumpFile, const char* label, const std::string& renderFile = "",
              uint32_t rw = 1280, uint32_t rh = 720, bool materials = false, const std::string& matDump = "", const std::string& cameraDump = "",
              const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0, bool solid = false, const std::string& sdfFile = "",
-             const std::string& surfaceFile = "")
+             const std::string& surfaceFile = "", const std::string& componentsFile = "", int connectivity = 6)
 {
     VoxelBuilder<T, P> voxelBuilder{std::filesystem::path(path)};
     voxelBuilder.withMaterials(materials);
@@ -409,6 +414,16 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
         std::printf("[voxhip] sdf: %zu x %zu x %zu cells, min %g max %g\n", vox.dimX(), vox.dimY(), vox.dimZ(), (double)lo, (double)hi);
     }
     if (!surfaceFile.empty()) write_surface(vox, surfaceFile, materials);
+    if (!componentsFile.empty()) {
+        const std::vector<vx_component> cs = vox.componentStats(connectivity);
+        std::ofstream f(componentsFile);
+        f << "label,cells,minx,miny,minz,maxx,maxy,maxz\n";
+        for (size_t k = 0; k < cs.size(); ++k)
+            f << k + 1 << ',' << cs[k].cells << ',' << cs[k].min[0] << ',' << cs[k].min[1] << ',' << cs[k].min[2] << ',' << cs[k].max[0] << ','
+              << cs[k].max[1] << ',' << cs[k].max[2] << '\n';
+        if (!f) throw std::runtime_error("cannot write " + componentsFile);
+        std::printf("[voxhip] components: %zu\n", cs.size());
+    }
     RenderOpts ro;
     ro.cameraDump = cameraDump;
     ro.mesh = mesh;
@@ -431,17 +446,17 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]]\n",
                      argv[0]);
         return 2;
     }
     const std::string path = argv[1];
     float vs = 0.f;
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
-    std::string grid = "bool", sdfFile, surfaceFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
+    std::string grid = "bool", sdfFile, surfaceFile, componentsFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false, attributes = false, solid = false;
-    int gpus = 1;
+    int gpus = 1, connectivity = 6;
     long benchRuns = 0, frames = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--grid") && i + 1 < argc) grid = argv[++i];
@@ -460,6 +475,8 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--solid")) solid = true;
         else if (!std::strcmp(argv[i], "--sdf") && i + 1 < argc) sdfFile = argv[++i];
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--components") && i + 1 < argc) componentsFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--connectivity") && i + 1 < argc) connectivity = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
@@ -493,6 +510,11 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--surface writes the boundary mesh of one grid on one device: not with --grid octree, --gpus N > 1, --bench, or --materials with --grid vec\n");
         return 2;
     }
+    if (!componentsFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
+        std::fprintf(stderr, "--components labels the occupied cells of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (connectivity != 6 && connectivity != 26) { std::fprintf(stderr, "--connectivity must be 6 or 26\n"); return 2; }
     std::vector<int> devices;
     if (gpus > 1) {
         const int have = vx_device_count();
@@ -577,12 +599,12 @@ int main(int argc, char** argv)
             return 0;
         }
         const bool surfMat = materials && !surfaceFile.empty();  // (--materials reaches an aabbstruct grid only for its surface's ids)
-        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile)
-                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile);
-        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, surfMat, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile)
-                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, surfMat, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile);
-        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile)
-                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile);
+        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile, componentsFile, connectivity)
+                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile, componentsFile, connectivity);
+        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, surfMat, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity)
+                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, surfMat, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity);
+        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity)
+                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity);
         std::fprintf(stderr, "unknown grid flavour %s\n", grid.c_str());
         return 2;
     } catch (const std::exception& e) {

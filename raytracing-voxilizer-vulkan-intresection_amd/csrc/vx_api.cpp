@@ -192,6 +192,7 @@ struct Mail {
     unsigned long long units, hits, occupied, pad;
     unsigned long long solid_rounds, interior;  // solid fill: changed rounds of the last batch, |H|
     unsigned long long surf_tris, surf_verts;   // surface mesh: T and V
+    unsigned long long cc_count;                // connected components: K
 };
 
 // Totals may arrive tagged with the build's sequence number in bits 48..63 (see launch_scan_u32): the host then polls the word
@@ -417,6 +418,8 @@ struct vx_grid {
     DevBuf dist_stk, dist_out;
     // surface mesh (vx_surface.hip): triangles per mask word and their scan, the used lattice points and their scan, the host variant's arrays
     DevBuf surf_cnt, surf_tpre, surf_cm, surf_vpre, surf_out;
+    // connected components (vx_components.hip): the root bitmask and its scan, the host variants' labels, the statistics
+    DevBuf cc_roots, cc_rpre, cc_lab, cc_stat;
     uint64_t interior = 0;        // |H| of the last build or fill on the handle (vx_grid_interior)
     uint32_t solid_rounds = 0;    // rounds of that fill, the quiet one included (vx_grid_fill_rounds)
     uint64_t mat_interior = 0;    // a solid VX_VOXELIZE_MATERIALS build: ids of interior voxels / calls still to be given MaterialObj{}'s index
@@ -542,7 +545,7 @@ struct vx_grid {
     void set_dev(int d)
     {
         device = d;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out}) b->dev = d;
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out, &cc_roots, &cc_rpre, &cc_lab, &cc_stat}) b->dev = d;
     }
     // the stream this handle queues work on; the pool orders the reuse of released blocks by it
     void set_stream(hipStream_t st)
@@ -552,11 +555,11 @@ struct vx_grid {
             (void)hipStreamSynchronize(stream);
         }
         stream = st;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out}) b->stream = st;
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out, &cc_roots, &cc_rpre, &cc_lab, &cc_stat}) b->stream = st;
     }
     void release_all()
     {
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out}) b->release();
+        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out, &cc_roots, &cc_rpre, &cc_lab, &cc_stat}) b->release();
         if (mail) (void)hipHostFree(mail);
         mail = nullptr;
     }
@@ -2125,6 +2128,95 @@ vx_status vx_grid_surface_mesh(const vx_grid* gc, int with_materials, vx_mesh** 
         if (st != VX_OK) { vx_mesh_free(m); return st; }
     }
     *out = m;
+    return VX_OK;
+}
+
+// Connected components: the argument checks in the header's order, then the labelling passes and one scan on the grid's stream
+// (vx_components.hip).  The passes only read the bitmask; the union-find's parent array is the label buffer itself.  *empty: a grid of
+// 0 cells (VX_OK, nothing to write).
+static vx_status components_check(const vx_grid* g, uint32_t connectivity, bool* empty)
+{
+    if (connectivity != VX_CONNECT_6 && connectivity != VX_CONNECT_26) return fail(VX_ERR_INVALID_ARG, "connectivity must be VX_CONNECT_6 or VX_CONNECT_26");
+    *empty = !g->g.nvox;
+    if (*empty) return VX_OK;
+    if (g->g.nvox > 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "components need X*Y*Z <= 2^32 - 1 (32-bit labels and union-find indices)");
+    return VX_OK;
+}
+
+// labels (X*Y*Z, device) <- the labels; K lands in the mailbox and, when dev_count is non-null, in *dev_count on the device
+static vx_status components_queue(vx_grid* g, uint32_t connectivity, uint32_t* labels, uint32_t* dev_count)
+{
+    VX_HIP(g->cc_roots.ensure((size_t)(g->g.nwords + 4) * 4));
+    VX_HIP(g->cc_rpre.ensure((size_t)(g->g.nwords + 4) * 4));
+    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(g->g.nwords), g->stream));
+    vx::launch_components(g->words.as<uint32_t>(), g->g, connectivity == VX_CONNECT_26, labels, g->cc_roots.as<uint32_t>(), g->stream);
+    vx::launch_scan_u32(g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), g->g.nwords, true, g->scantmp.p, &g->mail->cc_count, g->stream, true, 0,
+                        nullptr, next_scan_gen(g->scantmp, g->stream));
+    vx::launch_components_label(g->words.as<uint32_t>(), g->g, labels, g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), dev_count, g->stream);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+// the labels into the handle's staging buffer (and on to host_labels, when non-null), one host wait, K
+static vx_status components_host(vx_grid* g, uint32_t connectivity, uint32_t* host_labels, uint64_t* k)
+{
+    VX_HIP(g->cc_lab.ensure((size_t)g->g.nvox * 4));
+    VX_TRY(components_queue(g, connectivity, g->cc_lab.as<uint32_t>(), nullptr));
+    if (host_labels) VX_HIP(hipMemcpyAsync(host_labels, g->cc_lab.p, (size_t)g->g.nvox * 4, hipMemcpyDeviceToHost, g->stream));
+    VX_HIP(hipStreamSynchronize(g->stream));
+    *k = g->mail->cc_count & kMailValue;
+    return VX_OK;
+}
+
+vx_status vx_grid_components_device(const vx_grid* gc, uint32_t connectivity, uint32_t* dev_labels, uint64_t capacity, uint32_t* dev_count)
+{
+    if (!gc || !dev_labels) return fail(VX_ERR_INVALID_ARG, "null argument");
+    bool empty = false;
+    VX_TRY(components_check(gc, connectivity, &empty));
+    if (empty) return VX_OK;
+    if (capacity < gc->g.nvox) return fail(VX_ERR_CAPACITY, "component label buffer too small");
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return components_queue(g, connectivity, dev_labels, dev_count);
+}
+
+vx_status vx_grid_components(const vx_grid* gc, uint32_t connectivity, uint32_t* host_labels, uint64_t capacity, uint64_t* count)
+{
+    if (!gc || (capacity && !host_labels)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    bool empty = false;
+    VX_TRY(components_check(gc, connectivity, &empty));
+    if (count) *count = 0;
+    if (empty) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    const bool write = host_labels && capacity >= g->g.nvox;
+    uint64_t k = 0;
+    VX_TRY(components_host(g, connectivity, write ? host_labels : nullptr, &k));
+    if (count) *count = k;
+    if (host_labels && !write) return fail(VX_ERR_CAPACITY, "component label buffer too small");
+    return VX_OK;
+}
+
+vx_status vx_grid_component_stats(const vx_grid* gc, uint32_t connectivity, vx_component* host_out, uint64_t capacity, uint64_t* count)
+{
+    if (!gc || (capacity && !host_out)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    bool empty = false;
+    VX_TRY(components_check(gc, connectivity, &empty));
+    if (count) *count = 0;
+    if (empty) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    uint64_t k = 0;
+    VX_TRY(components_host(g, connectivity, nullptr, &k));
+    if (count) *count = k;
+    if (!capacity) return VX_OK;  // (size query)
+    if (capacity < k) return fail(VX_ERR_CAPACITY, "component statistics buffer too small");
+    if (!k) return VX_OK;
+    VX_HIP(g->cc_stat.ensure((size_t)k * sizeof(vx_component)));
+    vx::launch_component_stats(g->cc_lab.as<uint32_t>(), g->g, k, g->cc_stat.as<uint32_t>(), g->stream);
+    VX_HIP(hipGetLastError());
+    VX_HIP(hipMemcpyAsync(host_out, g->cc_stat.p, (size_t)k * sizeof(vx_component), hipMemcpyDeviceToHost, g->stream));
+    VX_HIP(hipStreamSynchronize(g->stream));
     return VX_OK;
 }
 

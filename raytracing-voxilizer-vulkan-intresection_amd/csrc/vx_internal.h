@@ -377,6 +377,15 @@ void launch_surface_emit(const uint32_t* words, const GridParams& g, const Surfa
                          const uint32_t* vpre, const uint32_t* wprefix, const int16_t* cell_mat, float* xyz, int32_t* tri, int32_t* mat,
                          hipStream_t s);
 
+// Connected components (vx_components.hip), X*Y*Z <= 2^32 - 1.  launch_components: labels (X*Y*Z) receives parent = the smallest cell of
+// the component for the occupied cells (empty slots untouched), roots (nwords) the root bitmask.  launch_components_label: rpre = the
+// exclusive scan of the roots' popcounts; labels in place (0 for empty cells), and K into dev_count when non-null.
+void launch_components(const uint32_t* words, const GridParams& g, bool conn26, uint32_t* labels, uint32_t* roots, hipStream_t s);
+void launch_components_label(const uint32_t* words, const GridParams& g, uint32_t* labels, const uint32_t* roots, const uint32_t* rpre,
+                             uint32_t* dev_count, hipStream_t s);
+// rec: k records of vx_component (8 words each) from the labels
+void launch_component_stats(const uint32_t* labels, const GridParams& g, uint64_t k, uint32_t* rec, hipStream_t s);
+
 // device radix sort of uint64 keys (octree items; vx_sort.hip); tmp sized by sort_tmp_bytes.  The two key buffers ping-pong:
 // returns 0 when the sorted keys end up in keys_a, 1 for keys_b (the other buffer is scratch afterwards).
 size_t sort_tmp_bytes(uint64_t n);

@@ -17,12 +17,14 @@ VOXELIZE_MATERIALS = 1
 VOXELIZE_LIST_ASYNC = 2
 VOXELIZE_SOLID = 4
 DISTANCE_INSIDE = 1
+CONNECT_6, CONNECT_26 = 6, 26
 STATUS_NAMES = {0: "VX_OK", 1: "VX_ERR_INVALID_ARG", 2: "VX_ERR_PATH", 3: "VX_ERR_PARSE", 4: "VX_ERR_OUT_OF_BOUNDS",
                 5: "VX_ERR_MORTON_BITS", 6: "VX_ERR_NO_DEVICE", 7: "VX_ERR_HIP", 8: "VX_ERR_CAPACITY", 9: "VX_ERR_UNSUPPORTED"}
 
 AABB = np.dtype([("mn", np.float32, 3), ("mx", np.float32, 3)])
 NODE = np.dtype([("children", np.uint32, 8), ("start", np.uint32), ("count", np.uint32)])
 HIT = np.dtype([("ray", np.uint32), ("prim", np.uint32), ("t", np.float32)])
+COMPONENT = np.dtype([("cells", np.uint64), ("min", np.uint32, 3), ("max", np.uint32, 3)])  # vx_component, 32 B
 BVH_NODE = np.dtype([("mn", np.float32, 3), ("a", np.uint32), ("mx", np.float32, 3), ("b", np.uint32)])   # vx_bvh_node
 BVH_LEAF = 0x80000000
 MATERIAL = np.dtype([("ambient", np.float32, 3), ("diffuse", np.float32, 3), ("specular", np.float32, 3), ("transmittance", np.float32, 3),
@@ -137,7 +139,8 @@ SYMBOLS = [
     "vx_grid_create", "vx_grid_describe", "vx_grid_set_voxel", "vx_grid_test_voxel", "vx_grid_coords", "vx_grid_bytes",
     "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_fill_interior", "vx_grid_interior", "vx_grid_fill_rounds",
     "vx_grid_distance_sq_device", "vx_grid_distance_sq", "vx_grid_sdf_device", "vx_grid_sdf",
-    "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh", "vx_grid_aabbs",
+    "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh",
+    "vx_grid_components_device", "vx_grid_components", "vx_grid_component_stats", "vx_grid_aabbs",
     "vx_grid_aabbs_device", "vx_grid_bind_aabbs_device", "vx_grid_list_wait", "vx_grid_aabbs_device_async", "vx_grid_materials", "vx_grid_material_ids", "vx_grid_material_ids_device", "vx_grid_material_first_use",
     "vx_grid_finish_materials", "vx_multi_create", "vx_multi_voxelize", "vx_multi_grid", "vx_multi_release_grid", "vx_multi_free", "vx_sort_u64", "vx_grid_free",
     "vx_octree_build", "vx_octree_num_items", "vx_octree_num_nodes", "vx_octree_bytes", "vx_octree_items", "vx_octree_nodes",
@@ -265,6 +268,9 @@ def lib():
     L.vx_grid_surface_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, u64p, u64p]
     L.vx_grid_surface.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, u64p, u64p]
     L.vx_grid_surface_mesh.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.vx_grid_components_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp]
+    L.vx_grid_components.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
+    L.vx_grid_component_stats.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.vx_grid_aabbs.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_grid_aabbs_device.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_grid_bind_aabbs_device.argtypes = [vp, vp, C.c_uint64]
@@ -745,6 +751,37 @@ class Grid:
         h = C.c_void_p()
         _check(lib().vx_grid_surface_mesh(self.h, 1 if materials else 0, C.byref(h)))
         return Mesh(h)
+
+    def components(self, connectivity=CONNECT_6):
+        """vx_grid_components: connected-component labels of the occupied cells (connectivity 6 or 26) -> (numpy uint32 [Z, Y, X], K);
+        0 for empty cells, 1..K in ascending order of each component's smallest cell index."""
+        shape, n = self._cells()
+        out = np.zeros(shape, dtype=np.uint32)
+        k = C.c_uint64()
+        _check(lib().vx_grid_components(self.h, connectivity, out.ctypes.data if n else None, n, C.byref(k)))
+        return out, k.value
+
+    def components_device(self, out=None, connectivity=CONNECT_6):
+        """vx_grid_components_device, asynchronous on the grid's stream -> (`out`, a device torch.uint32 tensor [Z, Y, X] of labels (an int32
+        tensor receives the same bits), K as a one-element device int32 tensor)."""
+        import torch
+        out, n = self._device_out(out, (torch.uint32, torch.int32), "uint32 / int32")
+        if not n:
+            return out, torch.zeros(1, dtype=torch.int32, device=out.device)
+        k = torch.empty(1, dtype=torch.int32, device=out.device)
+        _check(lib().vx_grid_components_device(self.h, connectivity, out.data_ptr(), n, k.data_ptr()))
+        self._record(out)
+        self._record(k)
+        return out, k
+
+    def component_stats(self, connectivity=CONNECT_6):
+        """vx_grid_component_stats -> numpy COMPONENT[K]: record k - 1 describes label k (cells, inclusive min / max cell in x, y, z)."""
+        k = C.c_uint64()
+        _check(lib().vx_grid_component_stats(self.h, connectivity, None, 0, C.byref(k)))
+        out = np.zeros(k.value, dtype=COMPONENT)
+        if k.value:
+            _check(lib().vx_grid_component_stats(self.h, connectivity, out.ctypes.data, k.value, C.byref(k)))
+        return out
 
     def aabbs(self):
         n = C.c_uint64()
