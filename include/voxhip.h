@@ -253,7 +253,10 @@ uint64_t vx_grid_bytes(const vx_grid* g);
 /* bitmask access */
 vx_status vx_grid_bitmask(const vx_grid* g, uint32_t* host_words, uint64_t capacity_words);
 const uint32_t* vx_grid_bitmask_device(const vx_grid* g);
-uint32_t* vx_grid_bitmask_device_mut(vx_grid* g); /* for the multi-GPU exchange; call vx_grid_refresh afterwards */
+/* for the multi-GPU exchange; call vx_grid_refresh afterwards.  Bits past X*Y*Z in the last word are not cells: a writer may set them
+ * (a fill of the whole word array, for example), and vx_grid_refresh clears them, so that occupied, the AABB lists and the rays see
+ * exactly the X*Y*Z cells. */
+uint32_t* vx_grid_bitmask_device_mut(vx_grid* g);
 vx_status vx_grid_refresh(vx_grid* g);            /* recount + rebuild derived data after the bitmask was written externally */
 /* The fill of VX_VOXELIZE_SOLID on any grid (vx_grid_create + setVoxel, a mask written through vx_grid_bitmask_device_mut): exactly
  * vx_grid_set_voxel on every cell of the grid's interior H in ascending voxel index -- set_calls + |H|, a Vec list gets the records
@@ -650,6 +653,54 @@ void vx_render_free(vx_render_scene* s);                                        
 /* ---- test aid: the device radix sort the Octree uses for its Morton items (octTree.hpp:363 -> vx_sort.hip), applied to a host array.
  * Keys must have no bit set at or above `bits` (1..64); sorted in place. */
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits);
+
+/* ---- test aid: the device-wide exclusive prefix scan every feature runs on (vx_kernels.hip, launch_scan_u32 / launch_scan_u8), applied
+ * to host arrays, scan after scan on ONE scratch block that keeps its generation counter between scans.
+ * mode: VX_SCAN_VALUES (uint32 elements), VX_SCAN_POPCOUNT (the popcounts of uint32 words), VX_SCAN_BYTES (uint8 elements).
+ * Scan k reads sizes[k] elements from `in` (the inputs one after another) and writes out[0..n] = the exclusive prefix mod 2^32
+ * (n + 1 entries) followed by VX_SCAN_CANARY words that must still read VX_SCAN_CANARY_VALUE; `out` holds the scans one after
+ * another, sizes[k] + 1 + VX_SCAN_CANARY words each.  totals[k] is the 64-bit total as the scan wrote it: the true total T while
+ * T < 2^40 - 1, else at least 2^40 - 1 and below 2^48 (values, and the three-pass path: exactly 2^40 - 1), OR-ed with total_tag
+ * (bits 48..63) by the single-pass paths.  out[i] is exact for every 16384-element tile whose exclusive prefix is below 2^40 - 1.
+ * paths[k]: VX_SCAN_PATH_GEN (single pass, the block's next generation number; ticket mode past 512 tiles of 16384, as for the
+ * library's callers), VX_SCAN_PATH_TICKET (single pass without a generation number), VX_SCAN_PATH_THREE (three passes),
+ * VX_SCAN_PATH_AUTO (what the library does, VOXHIP_SCAN_3PASS / VOXHIP_SCAN_GEN switches included).  in_offset / out_offset
+ * (elements) move the device arrays off their 16-byte alignment: a uint32 scan then takes the three-pass path whatever paths[k]
+ * asks.  taken[k] (optional) is the path the scan took.  sel / group16 (optional; VX_SCAN_POPCOUNT / VX_SCAN_VALUES): sel_cap /
+ * group16_cap words per scan (at least ceil(32 n / 1024) / n / 16 + 1; sel in popcount mode only), filled with VX_SCAN_CANARY_VALUE before the scan; the single-pass paths write sel[c] = the element
+ * whose range [pre, pre + v) holds c * 1024 (values of at most 1024) and group16[i] = out[16 i]; the three-pass path writes neither.
+ * gen_start: the block's generation counter before the first scan (< 2^22; the counter wraps to 1 at 2^22 and clears the block).
+ * clean[k] (optional): 1 when, after scan k, the block is in the state the next scan relies on -- all zero after a scan without a
+ * generation number; after one with a generation number, the ticket words zero and every state word of that or an older
+ * generation. */
+#define VX_SCAN_VALUES 0u
+#define VX_SCAN_POPCOUNT 1u
+#define VX_SCAN_BYTES 2u
+#define VX_SCAN_PATH_GEN 0u
+#define VX_SCAN_PATH_TICKET 1u
+#define VX_SCAN_PATH_THREE 2u
+#define VX_SCAN_PATH_AUTO 3u
+#define VX_SCAN_CANARY 16u
+#define VX_SCAN_CANARY_VALUE 0xA5A5A5A5u
+typedef struct vx_scan_args {
+    uint32_t mode;
+    uint32_t nscans;
+    const uint64_t* sizes;   /* nscans */
+    const uint32_t* paths;   /* nscans */
+    const void* in;
+    uint32_t* out;
+    uint64_t* totals;        /* nscans */
+    uint32_t* taken;         /* nscans, optional */
+    uint32_t* clean;         /* nscans, optional */
+    uint32_t* sel;           /* nscans * sel_cap, optional */
+    uint32_t* group16;       /* nscans * group16_cap, optional */
+    uint64_t sel_cap, group16_cap;
+    uint64_t in_offset, out_offset;
+    uint64_t total_tag;
+    uint32_t gen_start;
+    uint32_t pad;
+} vx_scan_args;
+vx_status vx_scan_u32(const vx_scan_args* a);
 
 /* ---- measurement aid: per-kernel durations from HIP events recorded on the launch stream (off by default).
  * slot = 0,1,... until VX_ERR_INVALID_ARG; name is the kernel symbol as launched. */

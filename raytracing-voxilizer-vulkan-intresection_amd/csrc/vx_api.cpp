@@ -242,15 +242,20 @@ hipError_t ensure_scan_tmp(DevBuf& tmp, size_t bytes, hipStream_t s)
 }
 
 // the number of the next scan on this scratch block (generation mode: state words of older scans read as "not there yet")
-uint32_t next_scan_gen(DevBuf& tmp, hipStream_t s)
+uint32_t advance_scan_gen(DevBuf& tmp, hipStream_t s)
 {
-    static const bool off = getenv("VOXHIP_SCAN_GEN") && atoi(getenv("VOXHIP_SCAN_GEN")) == 0;  // 0: tickets + self-cleaning state (A/B, tests)
-    if (off) return 0u;
     if (++tmp.scan_gen >= (1u << 22)) {
         (void)hipMemsetAsync(tmp.p, 0, tmp.cap, s);
         tmp.scan_gen = 1u;
     }
     return tmp.scan_gen;
+}
+
+uint32_t next_scan_gen(DevBuf& tmp, hipStream_t s)
+{
+    static const bool off = getenv("VOXHIP_SCAN_GEN") && atoi(getenv("VOXHIP_SCAN_GEN")) == 0;  // 0: tickets + self-cleaning state (A/B, tests)
+    if (off) return 0u;
+    return advance_scan_gen(tmp, s);
 }
 
 }  // namespace
@@ -1881,7 +1886,11 @@ uint32_t* vx_grid_bitmask_device_mut(vx_grid* g)
 vx_status vx_grid_refresh(vx_grid* g)
 {
     if (!g) return fail(VX_ERR_INVALID_ARG, "null argument");
-    { DeviceGuard dg(g->device); VX_HIP(g->list_resolve()); }
+    {
+        DeviceGuard dg(g->device);
+        VX_HIP(g->list_resolve());
+        if (g->g.nwords) vx::launch_mask_tail(g->words.as<uint32_t>(), g->g.nvox, g->stream);  // (padding bits are not cells)
+    }
     g->coarse_valid = g->prefix_valid = g->occupied_known = false;
     VX_TRY(ensure_prefix(g));
     return ensure_coarse(g);
@@ -3918,6 +3927,108 @@ vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits)
         const int where = vx::launch_sort_u64(a.as<uint64_t>(), b.as<uint64_t>(), n, bits, tmp.p, tb, nullptr);
         e = hipStreamSynchronize(nullptr);
         if (e == hipSuccess) e = hipMemcpy(host_keys, where == 0 ? a.p : b.p, (size_t)n * 8, hipMemcpyDeviceToHost);
+    }
+    rel();
+    VX_HIP(e);
+    return VX_OK;
+}
+
+// ---- test aid: the device prefix scan on host arrays, scan after scan on one scratch block --------------------------
+vx_status vx_scan_u32(const vx_scan_args* a)
+{
+    if (!a || (a->nscans && (!a->sizes || !a->paths || !a->totals))) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (a->mode > VX_SCAN_BYTES) return fail(VX_ERR_INVALID_ARG, "mode must be VX_SCAN_VALUES, VX_SCAN_POPCOUNT or VX_SCAN_BYTES");
+    if (a->total_tag & kMailValue) return fail(VX_ERR_INVALID_ARG, "total_tag must only have bits 48..63");
+    if (a->gen_start >= (1u << 22)) return fail(VX_ERR_INVALID_ARG, "gen_start must be below 2^22");
+    if (a->mode == VX_SCAN_BYTES && ((a->sel && a->sel_cap) || (a->group16 && a->group16_cap)))
+        return fail(VX_ERR_INVALID_ARG, "the byte scan has no sel / group16 outputs");
+    if (a->mode != VX_SCAN_POPCOUNT && a->sel && a->sel_cap) return fail(VX_ERR_INVALID_ARG, "sel needs values of at most 1024: popcount mode only");
+    const size_t esz = a->mode == VX_SCAN_BYTES ? 1 : 4;
+    uint64_t nmax = 0, nin = 0, nout = 0;
+    for (uint32_t k = 0; k < a->nscans; ++k) {
+        if (a->paths[k] > VX_SCAN_PATH_AUTO) return fail(VX_ERR_INVALID_ARG, "unknown scan path");
+        if (a->sizes[k] >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 elements");
+        nmax = std::max(nmax, a->sizes[k]);
+        nin += a->sizes[k];
+        nout += a->sizes[k] + 1 + VX_SCAN_CANARY;
+    }
+    if ((nin && !a->in) || (nout && !a->out)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    // what the kernel writes: sel[c] for c * 1024 below the total (at most 32 per word), group16[0..n / 16]
+    if (a->sel && a->sel_cap && a->sel_cap < (32 * nmax + 1023) / 1024) return fail(VX_ERR_INVALID_ARG, "sel_cap below ceil(32 n / 1024)");
+    if (a->group16 && a->group16_cap && a->group16_cap < nmax / 16 + 1) return fail(VX_ERR_INVALID_ARG, "group16_cap below n / 16 + 1");
+    if (!a->nscans) return VX_OK;
+    VX_TRY(need_device(g_device));
+    DeviceGuard dg(g_device);
+    hipStream_t s = nullptr;
+    DevBuf din, dout, dsel, dg16, tmp, dtot;
+    for (DevBuf* x : {&din, &dout, &dsel, &dg16, &tmp, &dtot}) x->dev = g_device;
+    auto rel = [&]() { for (DevBuf* x : {&din, &dout, &dsel, &dg16, &tmp, &dtot}) x->release(false); };
+    const uint64_t out_words = a->out_offset + nmax + 1 + VX_SCAN_CANARY;
+    const uint64_t sel_cap = a->sel ? a->sel_cap : 0, g16_cap = a->group16 ? a->group16_cap : 0;
+    std::vector<uint32_t> canary(std::max<uint64_t>(std::max(out_words, sel_cap), g16_cap), VX_SCAN_CANARY_VALUE);
+    std::vector<unsigned long long> state;
+    hipError_t e = din.ensure((size_t)(a->in_offset + nmax) * esz + 16);
+    if (e == hipSuccess) e = dout.ensure((size_t)out_words * 4);
+    if (e == hipSuccess) e = dsel.ensure((size_t)sel_cap * 4 + 4);
+    if (e == hipSuccess) e = dg16.ensure((size_t)g16_cap * 4 + 4);
+    if (e == hipSuccess) e = dtot.ensure(8);
+    if (e == hipSuccess) e = ensure_scan_tmp(tmp, vx::scan_tmp_bytes(nmax), s);
+    if (e == hipSuccess) state.resize(tmp.cap / sizeof(unsigned long long));
+    tmp.scan_gen = a->gen_start;
+    bool zero = true;  // the scratch block is known to be all zero (what ticket-mode and three-pass scans require and leave behind)
+    uint64_t ioff = 0, ooff = 0;
+    for (uint32_t k = 0; k < a->nscans && e == hipSuccess; ++k) {
+        const uint64_t n = a->sizes[k];
+        uint32_t* out = dout.as<uint32_t>() + a->out_offset;
+        uint32_t* sel = sel_cap ? dsel.as<uint32_t>() : nullptr;
+        uint32_t* g16 = g16_cap ? dg16.as<uint32_t>() : nullptr;
+        e = hipMemcpy(dout.p, canary.data(), (size_t)out_words * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && sel) e = hipMemcpy(sel, canary.data(), (size_t)sel_cap * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && g16) e = hipMemcpy(g16, canary.data(), (size_t)g16_cap * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && n) e = hipMemcpy((char*)din.p + a->in_offset * esz, (const char*)a->in + ioff * esz, (size_t)n * esz, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(dtot.p, 0, 8);
+        if (e != hipSuccess) break;
+        // the path: GEN = the next generation of the block (ticket mode above kScanGenTiles tiles, as for every library caller);
+        // TICKET / THREE = no generation, on a block that is all zero (cleared first when an older generation-mode scan left words);
+        // AUTO = what the library's own callers do (the VOXHIP_SCAN_3PASS / VOXHIP_SCAN_GEN switches)
+        const uint32_t p = a->paths[k];
+        const uint32_t gen = p == VX_SCAN_PATH_GEN ? advance_scan_gen(tmp, s) : p == VX_SCAN_PATH_AUTO ? next_scan_gen(tmp, s) : 0u;
+        const int lp = p == VX_SCAN_PATH_THREE ? vx::kScanPathThree : p == VX_SCAN_PATH_AUTO ? vx::kScanPathAuto : vx::kScanPathOne;
+        if (!gen && !zero) (void)hipMemsetAsync(tmp.p, 0, tmp.cap, s);
+        const bool tz = true;
+        bool one;
+        if (a->mode == VX_SCAN_BYTES) {
+            vx::launch_scan_u8((const uint8_t*)din.p + a->in_offset, out, n, tmp.p, dtot.as<unsigned long long>(), s, a->total_tag, gen);
+            one = true;
+        } else {
+            one = vx::launch_scan_u32(din.as<uint32_t>() + a->in_offset, out, n, a->mode == VX_SCAN_POPCOUNT, tmp.p, dtot.as<unsigned long long>(), s, tz,
+                                      a->total_tag, sel, gen, g16, lp);
+        }
+        const bool gen_mode = one && gen && (n + 1 + 16383) / 16384 <= 512;  // (kScanGenTiles tiles of 16384)
+        e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = hipMemcpy(a->out + ooff, out, (size_t)(n + 1 + VX_SCAN_CANARY) * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&a->totals[k], dtot.p, 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && sel) e = hipMemcpy(a->sel + (size_t)k * sel_cap, sel, (size_t)sel_cap * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && g16) e = hipMemcpy(a->group16 + (size_t)k * g16_cap, g16, (size_t)g16_cap * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(state.data(), tmp.p, state.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) break;
+        // clean: a scan without a generation number leaves the block all zero; one with a generation number leaves the ticket and the
+        // finished-tiles words zero and state words of its own or an older generation only, never of a later one (which a later scan
+        // would take for its own)
+        bool all_zero = true, ok = true;
+        for (size_t i = 0; i < state.size(); ++i) {
+            const unsigned long long w = state[i];
+            if (!w) continue;
+            all_zero = false;
+            const unsigned long long wg = (w >> 40) & ((1ull << 22) - 1ull);
+            if (i < 2 || (w >> 62) == 0 || wg == 0 || wg > tmp.scan_gen) ok = false;
+        }
+        if (!gen && !all_zero) ok = false;
+        if (a->clean) a->clean[k] = ok ? 1u : 0u;
+        if (a->taken) a->taken[k] = !one ? VX_SCAN_PATH_THREE : gen_mode ? VX_SCAN_PATH_GEN : VX_SCAN_PATH_TICKET;
+        zero = all_zero;
+        ioff += n;
+        ooff += n + 1 + VX_SCAN_CANARY;
     }
     rel();
     VX_HIP(e);

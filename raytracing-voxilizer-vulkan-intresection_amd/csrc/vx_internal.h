@@ -67,8 +67,12 @@ void launch_tri_setup(const float* verts, const int32_t* idx, uint64_t tri_begin
                       uint32_t* ext = nullptr /*optional, ntri words: bits 16..20 of the range values, for grids with an axis above 65535 cells*/,
                       uint32_t shard_rank = 0, uint32_t shard_world = 0 /*with dgrid and world > 1: the word shard vx_shard_words gives that rank*/);
 
-// exclusive scan of n uint32 (or of their popcounts) into out[0..n] (out[n] = total, saturating check via *total64)
+// exclusive scan of n uint32 (or of their popcounts) into out[0..n] (out[n] = total mod 2^32, saturating check via *total64)
+// *total64: exact below 2^40 - 1, then at least 2^40 - 1 and below 2^48 (vx_kernels.hip, THE TOTAL): a caller refuses a total >= 0xFFFFFFFF.
 size_t scan_tmp_bytes(uint64_t n);
+// path: kScanPathAuto = single-pass unless VOXHIP_SCAN_3PASS=1 (read once per process); the other two choose in the call (test aid).
+// Unaligned in / out take the three-pass path whatever `path` says.
+constexpr int kScanPathAuto = 0, kScanPathOne = 1, kScanPathThree = 2;
 // tmp_is_zero: the caller guarantees tmp (scan_tmp_bytes(n)) is all zero; the scan leaves it all zero again.
 // total_tag (bits 48..63 only): OR-ed into *total64 by the single-pass kernel, so that a host polling a pinned mailbox word can tell
 // this scan's total from an older one; returns whether the tag was applied (false: the three-pass path, *total64 is the bare total).
@@ -77,7 +81,11 @@ bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcoun
                      uint32_t* sel1024 = nullptr /*optional (single-pass kernel only, values <= 1024): sel1024[c] = the element whose range holds c * 1024*/,
                      uint32_t gen = 0 /*generation mode (vx_kernels.hip): the number of this scan on `tmp`, 1, 2, 3 ... < 2^22; 0 = tickets + self-cleaning state*/,
                      uint32_t* group16 = nullptr /*optional (single-pass kernel only): group16[i] = out[16 i], n / 16 + 1 entries -- a dense array small
-                                                   enough to stay in L2 for readers that gather (k_rank)*/);
+                                                   enough to stay in L2 for readers that gather (k_rank)*/,
+                     int path = kScanPathAuto);
+
+// clears the bits past nvox in the last word of a bitmask of nvox cells (nothing to do when nvox is a multiple of 32)
+void launch_mask_tail(uint32_t* words, uint64_t nvox, hipStream_t s);
 
 void launch_scan_u8(const uint8_t* in, uint32_t* out, uint64_t n, void* tmp /*scan_tmp_bytes(n), all zero*/, unsigned long long* total64, hipStream_t s,
                     unsigned long long total_tag = 0, uint32_t gen = 0);

@@ -14,6 +14,7 @@
 #include "vx_internal.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -179,7 +180,14 @@ void launch_bbox(const float* verts, uint64_t nverts, unsigned long long* state7
 // Device-wide exclusive scan of uint32 (optionally of their popcounts): out[i] = sum_{j<i} f(in[j]) for i in [0,n].
 // Three passes: tile sums -> spine (one block) -> apply.  Sums are carried in 64 bits so the caller can detect a
 // total that does not fit the 32-bit outputs.
+//
+// THE TOTAL (*total64, every path and mode): the true total T exactly while T < 2^40 - 1; from there on at least 2^40 - 1 and
+// below 2^48 (uint32 values and the three-pass path: exactly 2^40 - 1).  So a caller's `total >= 0xFFFFFFFF` refusal fires
+// exactly when T reaches 2^32 - 1, and the value never reaches bits 48..63, where the single-pass kernel ORs total_tag in.
+// The per-element outputs out[i] are the exclusive prefix mod 2^32 for every tile whose own exclusive prefix is below
+// 2^40 - 1 (a scan whose total saturates is refused by every caller; past that point only the total is specified).
 // ------------------------------------------------------------------------------------------------------------
+constexpr unsigned long long kScanTotalSat = (1ull << 40) - 1ull;
 template <bool POPC>
 __device__ __forceinline__ unsigned scan_ld(const uint32_t* __restrict__ in, uint64_t i, uint64_t n)
 {
@@ -256,7 +264,7 @@ __global__ __launch_bounds__(1024) void k_scan_spine(unsigned long long* sums, u
         if (threadIdx.x == 0) carry_s = carry + tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0 && total) *total = carry_s;
+    if (threadIdx.x == 0 && total) *total = carry_s < kScanTotalSat ? carry_s : kScanTotalSat;
 }
 
 template <bool POPC>
@@ -317,7 +325,12 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
                                                            uint32_t gen /*0: tickets + self-cleaning state; else generation mode*/,
                                                            uint32_t* __restrict__ group16 /*optional: group16[i] = out[16 i], a dense copy of every 16th output*/)
 {
-    __shared__ unsigned wsum[kOneBlock / 64];
+    // MODE 0: 16384 uint32 sum to up to 2^46, so the tile total (what the look-back publishes) is carried in 64 bits; the
+    // per-element prefixes only need it mod 2^32 and stay 32-bit.  MODE 1 / 2: at most 32 / 255 per element, i.e. below 2^19 /
+    // 2^22 per tile, which 32 bits hold.
+    typedef typename std::conditional<MODE == 0, unsigned long long, unsigned>::type tsum_t;
+    static_assert(MODE == 0 || (unsigned long long)kOneTile * 255ull < (1ull << 32), "32-bit tile sums of popcounts / bytes");
+    __shared__ tsum_t wsum[kOneBlock / 64];
     __shared__ unsigned tile_s;
     __shared__ unsigned long long prefix_s;
     unsigned tile = blockIdx.x;
@@ -327,12 +340,14 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
         tile = tile_s;
     }
     const unsigned long long gtag = (unsigned long long)gen << 40;                       // this scan's words: flag | gtag | value
-    const unsigned long long vmask = gen ? kScanGenValMask : kScanValMask;
+    // (MODE 0 saturates every published value at kScanTotalSat, in both modes: no sum reaches the generation or tag bits)
+    const unsigned long long vmask = MODE == 0 ? kScanTotalSat : gen ? kScanGenValMask : kScanValMask;
     const unsigned long long fmask = gen ? (3ull << 62) | (((1ull << 22) - 1ull) << 40) : (3ull << 62);  // what must match for a word to count
     unsigned long long* st = status + 2;
     const uint64_t base = (uint64_t)tile * kOneTile + (uint64_t)threadIdx.x * kOneItems;
     unsigned v[kOneItems];
-    const bool full = base + kOneItems <= n;
+    // (MODE 0 / 1: the launcher takes the three-pass path for unaligned pointers; bytes have no such path and go element-wise)
+    const bool full = base + kOneItems <= n && (MODE != 2 || ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0);
     constexpr bool POPC = MODE == 1;
     if (MODE == 2) {
         static_assert(kOneItems == 16, "one 16-byte load per thread");
@@ -363,30 +378,42 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
     unsigned tsum = 0;
 #pragma unroll
     for (int j = 0; j < kOneItems; ++j) tsum += v[j];
-    // exclusive scan of the thread sums over the block
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    tsum_t wtot = 0;  // MODE 0: the wave's exact total
+    if constexpr (MODE == 0) {
+        unsigned long long t64 = 0;
+#pragma unroll
+        for (int j = 0; j < kOneItems; ++j) t64 += v[j];
+        wtot = wave_sum_u64(t64);
+    }
+    // exclusive scan of the thread sums over the block
     unsigned inc = tsum;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const unsigned o = __shfl_up(inc, d, 64);
         if (lane >= d) inc += o;
     }
-    if (lane == 63) wsum[wv] = inc;
+    if (lane == 63) wsum[wv] = MODE == 0 ? wtot : (tsum_t)inc;
     __syncthreads();
-    unsigned wbase = 0, btot = 0;
+    unsigned wbase = 0;
+    tsum_t btot = 0;
 #pragma unroll
     for (int w = 0; w < kOneBlock / 64; ++w) {
-        const unsigned x = wsum[w];
-        if (w < wv) wbase += x;
+        const tsum_t x = wsum[w];
+        if (w < wv) wbase += (unsigned)x;
         btot += x;
     }
     unsigned pre = wbase + inc - tsum;
+    // what the tile publishes as its own sum and, behind its predecessors, as its inclusive prefix (MODE 0: saturated at vmask --
+    // 2^46 would run into the generation bits; MODE 1 / 2: exact, btot < 2^22 <= vmask)
+    const unsigned long long bpub = MODE == 0 ? ((unsigned long long)btot < vmask ? (unsigned long long)btot : vmask) : (unsigned long long)btot;
+    auto incl_of = [&](unsigned long long ex) { return MODE == 0 ? (ex + bpub < vmask ? ex + bpub : vmask) : ex + (unsigned long long)btot; };
     if (threadIdx.x < 64) {
         unsigned long long excl = 0;
         if (tile == 0) {
-            if (lane == 0) __hip_atomic_store(&st[0], kScanFlagP | gtag | (unsigned long long)btot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) __hip_atomic_store(&st[0], kScanFlagP | gtag | bpub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-            if (lane == 0) __hip_atomic_store(&st[tile], kScanFlagA | gtag | (unsigned long long)btot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) __hip_atomic_store(&st[tile], kScanFlagA | gtag | bpub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             long long look = (long long)tile - 1;
             for (;;) {
                 const long long idx = look - lane;
@@ -400,17 +427,18 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
                 const unsigned long long pm = __ballot((w >> 62) == 2ull);
                 const int first_p = pm ? __ffsll((long long)pm) - 1 : 64;
                 excl += wave_sum_u64(lane <= first_p ? (w & vmask) : 0ull);
+                if (MODE == 0 && excl > vmask) excl = vmask;  // (at most 65 saturated values in one window: no wrap)
                 if (pm) break;
                 look -= 64;
             }
             // (generation mode keeps 40 value bits: sums saturate there instead of running into the generation number -- a total that
             // large is far beyond what the 32-bit outputs can address and is reported as a capacity error by every caller)
-            if (excl + (unsigned long long)btot > vmask) excl = vmask - (unsigned long long)btot;
-            if (lane == 0) __hip_atomic_store(&st[tile], kScanFlagP | gtag | (excl + (unsigned long long)btot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (MODE != 0 && excl + (unsigned long long)btot > vmask) excl = vmask - (unsigned long long)btot;
+            if (lane == 0) __hip_atomic_store(&st[tile], kScanFlagP | gtag | incl_of(excl), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (lane == 0) {
             prefix_s = excl;
-            if (tile == ntiles - 1 && total) *total = total_tag | (excl + (unsigned long long)btot);
+            if (tile == ntiles - 1 && total) *total = total_tag | incl_of(excl);
         }
     }
     __syncthreads();
@@ -458,12 +486,14 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
 
 size_t scan_tmp_bytes(uint64_t n) { return (size_t)(((n + 1) + kScanTile - 1) / kScanTile + 4) * sizeof(unsigned long long); }
 
+// *total64: see THE TOTAL above (the exact range, the saturation at 2^40 - 1 and the tag bits).
 bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp, unsigned long long* total64,
-                     hipStream_t s, bool tmp_is_zero, unsigned long long total_tag, uint32_t* sel1024, uint32_t gen, uint32_t* group16)
+                     hipStream_t s, bool tmp_is_zero, unsigned long long total_tag, uint32_t* sel1024, uint32_t gen, uint32_t* group16, int path)
 {
     const uint32_t nblocks = (uint32_t)(((n + 1) + kScanTile - 1) / kScanTile);
     unsigned long long* status = (unsigned long long*)tmp;
-    static const bool three_pass = getenv("VOXHIP_SCAN_3PASS") && atoi(getenv("VOXHIP_SCAN_3PASS"));
+    static const bool env_three_pass = getenv("VOXHIP_SCAN_3PASS") && atoi(getenv("VOXHIP_SCAN_3PASS"));
+    const bool three_pass = path == kScanPathAuto ? env_three_pass : path == kScanPathThree;
     const bool aligned = ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;  // the single-pass kernel moves 16-byte vectors
     if (!three_pass && aligned) {
         const uint32_t ntiles = (uint32_t)(((n + 1) + kOneTile - 1) / kOneTile);
@@ -487,6 +517,20 @@ bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcoun
     }
     if (tmp_is_zero || gen) (void)hipMemsetAsync(status, 0, scan_tmp_bytes(n), s);  // keep the caller's "zero between scans" contract (no stale words either)
     return false;  // (*total64 carries no tag)
+}
+
+// the bits past the grid's nvox cells in the last bitmask word (an externally written mask may set them): cleared, so that nothing
+// downstream counts them
+__global__ void k_mask_tail(uint32_t* __restrict__ words, uint64_t nwords, uint32_t keep)
+{
+    if (threadIdx.x == 0) words[nwords - 1] &= keep;
+}
+
+void launch_mask_tail(uint32_t* words, uint64_t nvox, hipStream_t s)
+{
+    const uint32_t used = (uint32_t)(nvox & 31u);
+    if (!used) return;
+    VX_KL(k_mask_tail, dim3(1), dim3(64), 0, s, words, (nvox + 31u) / 32u, (1u << used) - 1u);
 }
 
 // exclusive scan of n BYTES into out[0..n] (uint32); single-pass kernel only (in and out 16-byte aligned, tmp all zero before and after)

@@ -81,6 +81,13 @@ class VoxelizeOpts(C.Structure):
                 ("tri_begin", C.c_uint64), ("tri_end", C.c_uint64), ("stream", C.c_void_p), ("shard_rank", C.c_int32), ("shard_world", C.c_int32)]
 
 
+class ScanArgs(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("nscans", C.c_uint32), ("sizes", C.c_void_p), ("paths", C.c_void_p), ("inp", C.c_void_p), ("out", C.c_void_p),
+                ("totals", C.c_void_p), ("taken", C.c_void_p), ("clean", C.c_void_p), ("sel", C.c_void_p), ("group16", C.c_void_p),
+                ("sel_cap", C.c_uint64), ("group16_cap", C.c_uint64), ("in_offset", C.c_uint64), ("out_offset", C.c_uint64),
+                ("total_tag", C.c_uint64), ("gen_start", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class TraceArgs(C.Structure):
     _fields_ = [("rays", C.c_void_p), ("view_inverse", C.POINTER(C.c_float)), ("proj_inverse", C.POINTER(C.c_float)), ("width", C.c_uint32),
                 ("height", C.c_uint32), ("num_rays", C.c_uint64), ("tmin", C.c_float), ("tmax", C.c_float), ("tmax_per_ray", C.c_void_p),
@@ -142,7 +149,7 @@ SYMBOLS = [
     "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh",
     "vx_grid_components_device", "vx_grid_components", "vx_grid_component_stats", "vx_grid_aabbs",
     "vx_grid_aabbs_device", "vx_grid_bind_aabbs_device", "vx_grid_list_wait", "vx_grid_aabbs_device_async", "vx_grid_materials", "vx_grid_material_ids", "vx_grid_material_ids_device", "vx_grid_material_first_use",
-    "vx_grid_finish_materials", "vx_multi_create", "vx_multi_voxelize", "vx_multi_grid", "vx_multi_release_grid", "vx_multi_free", "vx_sort_u64", "vx_grid_free",
+    "vx_grid_finish_materials", "vx_multi_create", "vx_multi_voxelize", "vx_multi_grid", "vx_multi_release_grid", "vx_multi_free", "vx_sort_u64", "vx_scan_u32", "vx_grid_free",
     "vx_octree_build", "vx_octree_num_items", "vx_octree_num_nodes", "vx_octree_bytes", "vx_octree_items", "vx_octree_nodes",
     "vx_octree_root_bounds", "vx_octree_aabbs", "vx_octree_aabbs_device", "vx_octree_free",
     "vx_trace", "vx_trace_device", "vx_trace_primary_device", "vx_trace_ex", "vx_trace_ex_device",
@@ -234,6 +241,7 @@ def lib():
     L.vx_voxelize_into.argtypes = [vp, C.c_float, C.POINTER(VoxelizeOpts), vp]
     L.vx_voxelize_multi.argtypes = [vp, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(vp)]
     L.vx_sort_u64.argtypes = [vp, C.c_uint64, C.c_int]
+    L.vx_scan_u32.argtypes = [C.POINTER(ScanArgs)]
     L.vx_multi_create.argtypes = [vp, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(vp)]
     L.vx_multi_voxelize.argtypes = [vp, C.c_float, vp, C.c_int]
     L.vx_multi_grid.argtypes = [vp, C.c_int]
@@ -873,6 +881,51 @@ def sort_u64(keys, bits):
     k = np.ascontiguousarray(keys, dtype=np.uint64).copy()
     _check(lib().vx_sort_u64(k.ctypes.data, k.size, int(bits)))
     return k
+
+
+SCAN_MODES = {"values": 0, "popcount": 1, "bytes": 2}
+SCAN_PATHS = {"gen": 0, "ticket": 1, "three": 2, "auto": 3}
+SCAN_CANARY, SCAN_CANARY_VALUE = 16, 0xA5A5A5A5
+
+
+def scan_u32(inputs, mode="values", paths="gen", in_offset=0, out_offset=0, sel_cap=0, group16_cap=0, total_tag=0, gen_start=0):
+    """vx_scan_u32: the device prefix scan on host arrays, one scan per entry of `inputs`, all on one scratch block (voxhip.h).
+    paths: one name of SCAN_PATHS or one per scan.  Returns one dict per scan: out (n + 1 uint32), canary (the SCAN_CANARY words
+    behind out[n]), total (the 64-bit word as written), taken (the path's name), clean, and sel / group16 (sel_cap / group16_cap words
+    each, when asked for)."""
+    dt = np.uint8 if mode == "bytes" else np.uint32
+    arrs = [np.ascontiguousarray(x, dtype=dt) for x in inputs]
+    k = len(arrs)
+    paths = [paths] * k if isinstance(paths, str) else list(paths)
+    sizes = np.array([a.size for a in arrs], dtype=np.uint64)
+    pth = np.array([SCAN_PATHS[p] for p in paths], dtype=np.uint32)
+    inp = np.concatenate(arrs) if k else np.zeros(0, dt)
+    if inp.size == 0:
+        inp = np.zeros(1, dt)
+    out = np.zeros(int(sizes.sum()) + k * (1 + SCAN_CANARY), dtype=np.uint32)
+    totals = np.zeros(k, np.uint64)
+    taken = np.zeros(k, np.uint32)
+    clean = np.zeros(k, np.uint32)
+    sel = np.zeros(max(k * sel_cap, 1), np.uint32)
+    g16 = np.zeros(max(k * group16_cap, 1), np.uint32)
+    a = ScanArgs(mode=SCAN_MODES[mode], nscans=k, sizes=sizes.ctypes.data, paths=pth.ctypes.data, inp=inp.ctypes.data, out=out.ctypes.data,
+                 totals=totals.ctypes.data, taken=taken.ctypes.data, clean=clean.ctypes.data, sel=sel.ctypes.data if sel_cap else None,
+                 group16=g16.ctypes.data if group16_cap else None, sel_cap=sel_cap, group16_cap=group16_cap, in_offset=in_offset,
+                 out_offset=out_offset, total_tag=total_tag, gen_start=gen_start)
+    _check(lib().vx_scan_u32(C.byref(a)))
+    names = {v: n for n, v in SCAN_PATHS.items()}
+    res, o = [], 0
+    for i, x in enumerate(arrs):
+        n = x.size
+        r = dict(out=out[o:o + n + 1], canary=out[o + n + 1:o + n + 1 + SCAN_CANARY], total=int(totals[i]), taken=names[int(taken[i])],
+                 clean=bool(clean[i]))
+        if sel_cap:
+            r["sel"] = sel[i * sel_cap:(i + 1) * sel_cap]
+        if group16_cap:
+            r["group16"] = g16[i * group16_cap:(i + 1) * group16_cap]
+        res.append(r)
+        o += n + 1 + SCAN_CANARY
+    return res
 
 
 class BorrowedGrid(Grid):

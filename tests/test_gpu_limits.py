@@ -6,6 +6,8 @@
 - vx_voxelize_into's failure contract (voxhip.h): an error the arguments alone show leaves the previous build untouched, every other
   error leaves an empty grid, and the next build on the handle equals a fresh handle's.
 - The two spare words behind the bitmask stay zero when a handle is rebuilt at a smaller grid, tiled or direct.
+- The 2^32 edges: a unit total past 2^32, occupied counts and primitive ids next to 2^32, frames of 2^32 pixels, and the bits past
+  the last cell of an externally written mask.
 """
 import numpy as np
 import pytest
@@ -438,3 +440,252 @@ def test_word_shard_without_triangles(gpu, x_cells):
         full.free()
         empty_ranks += check(gpu.Grid.voxelize(mesh, vs, shard=(rank, world)), rank)
     assert empty_ranks == 4   # ranks 1 and 2, on both kinds of handle
+
+
+# ---------------------------------------------------------------------------------------------- 2^32 edges
+# Every total of a count at or above 2^32 - 1 is refused (VX_ERR_CAPACITY): the prefix scans that produce them carry 64-bit totals
+# (tests/test_gpu_scan.py); here the guards behind them through the public API.
+UNITS_MSG = "more than 2^32 candidate row segments: shard the mesh or the grid"
+OCC_MSG = "more than 2^32 occupied voxels"
+F = np.float32
+
+
+def _cand_axis(a, b, c, gmin, vsize, dim):
+    """cand_axis (vx_math.h; VoxelBuilder.hpp:175-184) in float32"""
+    tmn, tmx = min(a, b, c), max(a, b, c)
+    s0 = int(F(F(tmn - gmin) / vsize))
+    e0 = int(F(F(tmx - gmin) / vsize)) + 2
+    return max(s0, 0), min(e0, int(dim))
+
+
+def _trim_axis(a0, a1, a2, org, vs, half, s, e):
+    """trim_axis (vx_kernels.hip): drop end slabs that the box-axis test separates"""
+    def sep(i):
+        c = F(org + F(F(F(i) + F(0.5)) * vs))
+        p = (F(a0 - c), F(a1 - c), F(a2 - c))
+        return min(p) > half or max(p) < -half
+    while e > s and sep(e - 1):
+        e -= 1
+    while e > s and sep(s):
+        s += 1
+    return s, e
+
+
+def units_per_triangle(tri, gi, vs, sat=0):
+    """k_tri_setup's unit count of one triangle (float32 vertices [3, 3]): rows of the trimmed candidate box cut at multiples of 32 in x"""
+    vs = F(vs)
+    half = F(vs * F(0.5))
+    vsize = F(half * F(2.0)) if sat == 0 else vs
+    org = [F(x) for x in gi["bmin"]]
+    rng = []
+    for a in range(3):
+        v = [F(tri[k][a]) for k in range(3)]
+        s, e = _cand_axis(*v, org[a], vsize, gi["dim"][a])
+        rng.append(_trim_axis(*v, org[a], vs, half, s, e))
+    (xs, xe), (ys, ye), (zs, ze) = rng
+    nx, ny, nz = max(xe - xs, 0), max(ye - ys, 0), max(ze - zs, 0)
+    if not (nx and ny and nz):
+        return 0
+    nseg = ((xs + nx - 1) >> 5) - (xs >> 5) + 1
+    return min(nseg * ny * nz, 0xFFFFFFFF)
+
+
+def _units_mesh():
+    """4096 copies of a triangle of 2^20 units over a 4096 x 4096 x 2 grid (2^32 units, all in one 16384-triangle scan tile), then one
+    small triangle: the true total is 2^32 + a few units, and a 32-bit tile sum reads it as those few"""
+    big = np.array([[0.0, 0.0, 0.0], [4096.0, 0.0, 1.0], [0.0, 4096.0, 2.0]], np.float32)
+    small = np.array([[100.25, 200.25, 0.25], [101.75, 200.5, 0.5], [100.5, 201.75, 0.75]], np.float32)
+    tri = np.concatenate([np.repeat(big[None], 4096, 0), small[None]])
+    v = np.ascontiguousarray(tri.reshape(-1, 3))
+    return v, np.arange(len(v), dtype=np.int32).reshape(-1, 3), np.float32(1.0), big, small
+
+
+def test_units_total_past_2_32(gpu):
+    """a unit total just past 2^32 in one scan tile: VX_ERR_CAPACITY from the grid build, a triangle shard and the Octree (a wrapped total
+    used to return VX_OK with the mask of a few units)"""
+    v, t, vs, big, small = _units_mesh()
+    gi = oracle.grid_info(v, vs)
+    assert gi["dim"] == (4096, 4096, 2)
+    ub, us = units_per_triangle(big, gi, vs), units_per_triangle(small, gi, vs)
+    assert ub == 1 << 20 and 0 < us < 64
+    assert 4096 * ub + us == (1 << 32) + us
+    mesh = gpu.Mesh.from_arrays(v, t)
+    for what, build in (("grid", lambda: gpu.Grid.voxelize(mesh, vs)), ("vec", lambda: gpu.Grid.voxelize(mesh, vs, gpu.GRID_VEC)),
+                        ("triangle shard", lambda: gpu.Grid.voxelize(mesh, vs, tris=(0, len(t)))),
+                        ("octree", lambda: gpu.Octree(mesh, vs))):
+        with pytest.raises(gpu.VxError) as ei:
+            build()
+        assert ei.value.status == ERR_CAPACITY and ei.value.message == UNITS_MSG, what
+
+
+@pytest.mark.parametrize("flavour", sorted(FLAVOURS))
+def test_units_total_past_2_32_rebuild(gpu, flavour):
+    """revoxelize into a live handle of every flavour with the unit total past 2^32: VX_ERR_CAPACITY, the empty grid of the failure
+    contract, and the next build equals a fresh handle's"""
+    import torch
+    kind_name, flags, bound = FLAVOURS[flavour]
+    kind = getattr(gpu, kind_name)
+    v, t, vs = _scene_a()
+    mesh = gpu.Mesh.from_arrays(v, t)
+    cv, ct, cvs, _, _ = _units_mesh()
+    cmesh = gpu.Mesh.from_arrays(cv, ct)
+    if flags.get("materials"):
+        mesh.set_materials(*_materials(len(t))[:2])
+        cmesh.set_materials(*_materials(len(ct))[:2])
+    gi = oracle.grid_info(v, vs)
+    rays = vx_scenes.random_rays(3000, gi["bmin"], gi["bmin"] + np.array(gi["dim"], np.float32) * vs, seed=31)
+    probes = [tuple(int(x) for x in np.random.default_rng(k).integers(0, gi["dim"])) for k in range(12)]
+    ref = gpu.Grid.voxelize(mesh, vs, kind, materials=flags.get("materials", False))
+    cap = ref.describe()["set_calls"] + 64
+    exp = _read(gpu, ref, rays, probes, cap)
+    ref.free()
+    g = gpu.Grid.voxelize(mesh, vs, kind, materials=flags.get("materials", False))
+    bbuf = None
+    if bound:
+        bbuf = torch.zeros(cap * 6, dtype=torch.float32, device="cuda")
+        g.bind_aabbs_device(bbuf.data_ptr(), cap)
+    g.revoxelize(mesh, vs, **flags)
+    with pytest.raises(gpu.VxError) as ei:
+        g.revoxelize(cmesh, cvs, **flags)
+    assert ei.value.status == ERR_CAPACITY and ei.value.message == UNITS_MSG
+    _assert_empty(gpu, _read(gpu, g, rays, probes, cap), len(rays), len(probes))
+    with pytest.raises(gpu.VxError) as ei:
+        g.revoxelize(cmesh, cvs, tris=(0, len(ct)), **flags)
+    assert ei.value.status == ERR_CAPACITY
+    g.revoxelize(mesh, vs, **flags)
+    _assert_same(exp, _read(gpu, g, rays, probes, cap), "%s rebuilt after the unit total" % flavour)
+    g.free()
+
+
+def _down_rays(cells, X, Y):
+    """rays from above (z = 3) down through the centres of cells (x, y, 0), slightly oblique"""
+    i = np.asarray(cells, np.uint64)
+    x = (i % np.uint64(X)).astype(np.float32) + np.float32(0.5)
+    y = (i // np.uint64(X) % np.uint64(Y)).astype(np.float32) + np.float32(0.5)
+    n = len(i)
+    return np.ascontiguousarray(np.stack([x, y, np.full(n, 3.0, np.float32), np.full(n, 1e-6, np.float32), np.full(n, -1e-6, np.float32),
+                                          np.full(n, -1.0, np.float32)], 1))
+
+
+def _cell_aabbs(cells, X, Y):
+    i = np.asarray(cells, np.uint64)
+    mn = np.stack([(i % np.uint64(X)), (i // np.uint64(X) % np.uint64(Y)), np.zeros_like(i)], 1).astype(np.float32)
+    a = np.zeros(len(i), dtype=oracle.AABB)
+    a["mn"], a["mx"] = mn, mn + np.float32(1.0)
+    return a
+
+
+def _full_grid_less(gpu, X, Y, cleared):
+    """a Bool grid X x Y x 1 (vs 1, origin 0) with every cell set but `cleared`, written through the mutable device pointer after a fill
+    of the whole word array (padding bits included) and refreshed"""
+    import torch
+    g = gpu.Grid.create(gpu.GRID_BOOL, X, Y, 1, 1.0)
+    nw = g.describe()["num_words"]
+    m = _mask_words(g, nw, mutable=True)
+    m.fill_(-1)
+    for c in cleared:
+        w = int(m[c // 32].item()) & 0xFFFFFFFF
+        m[c // 32] = int(np.uint32(w & ~(1 << (c % 32))).view(np.int32))
+    torch.cuda.synchronize()
+    del m
+    return g, nw
+
+
+@pytest.mark.parametrize("X,Y", [(65535, 65537), (65535, 65535)], ids=["wp16", "word_prefix"])
+def test_occupied_and_rays_near_2_32(gpu, X, Y):
+    """2^32 - 1 cells (64-bit ray indices; a word count divisible by 16: k_rank's wp16 path) and 65535^2 cells (the plain word_prefix
+    path): every cell set but one gives occupied = N - 1, exact; rays at cells near the end and around rank 2^31 return primitive ids
+    bit-equal to oracle.voxel_rank, t bit-equal to the slab formula of the hit cell, the cube normal and the shadow flag; the cleared cell
+    is a miss."""
+    N = X * Y
+    c0 = N - 5
+    g, nw = _full_grid_less(gpu, X, Y, [c0])
+    assert (nw % 16 == 0) == (X * Y == (1 << 32) - 1)
+    g.refresh()
+    assert g.describe()["occupied"] == N - 1
+    if N == (1 << 32) - 1:
+        assert N - 1 == 0xFFFFFFFE
+    cells = [N - 1, N - 2, N - 3, N - 4, c0, c0 - 1, c0 - 17, N - 32 * 16 - 1, 1 << 31, (1 << 31) + 1, (1 << 31) - 1, (1 << 31) + 12345, 3 << 30, 0, 31, 32]
+    rays = _down_rays(cells, X, Y)
+    ex = g.trace_ex(rays, want=("t", "prim", "normal"))
+    words = g.bitmask()
+    last = (0xFFFFFFFF if N % 32 == 0 else (1 << (N % 32)) - 1) & ~((1 << (c0 % 32)) if c0 // 32 == nw - 1 else 0)
+    assert int(words[-1]) == last   # the padding bits were cleared by refresh
+    want_prim = oracle.voxel_rank(words, np.array([c if c != c0 else 0xFFFFFFFFFFFFFFFF for c in cells], np.uint64))
+    del words
+    hit = np.array([c != c0 for c in cells])
+    assert np.array_equal(ex["prim"][hit], want_prim[hit])
+    assert (ex["t"][~hit] <= 0).all()
+    assert want_prim[hit].max() == N - 2 and (want_prim[hit] >= (1 << 31)).sum() >= 8
+    aabbs = _cell_aabbs(cells, X, Y)
+    for k in np.flatnonzero(hit):    # t and normal of the one cell the ray enters
+        bt, bp = oracle.trace_brute(aabbs[k:k + 1], rays[k:k + 1])
+        assert ex["t"][k].tobytes() == bt.tobytes() and bp[0] == 0, k
+        assert np.array_equal(ex["normal"][k:k + 1], oracle.cube_normals(aabbs[k:k + 1], bp, rays[k:k + 1], bt)), k
+    t2, p2, _ = g.trace(rays)
+    assert np.array_equal(t2, ex["t"]) and np.array_equal(p2[hit], ex["prim"][hit])
+    sh = g.trace_ex(rays, any_hit=True, want=("shadowed",))["shadowed"]
+    assert np.array_equal(sh.astype(bool), hit)
+    g.free()
+
+
+def test_occupied_at_2_32(gpu):
+    """2^32 - 1 cells all set: VX_ERR_CAPACITY "more than 2^32 occupied voxels"; 65535 x 65536 cells (4294901760) all set: accepted and
+    exact"""
+    g, _ = _full_grid_less(gpu, 65535, 65537, [])
+    with pytest.raises(gpu.VxError) as ei:
+        g.refresh()
+    assert ei.value.status == ERR_CAPACITY and ei.value.message == OCC_MSG
+    g.free()
+    g, nw = _full_grid_less(gpu, 65535, 65536, [])
+    g.refresh()
+    assert g.describe()["occupied"] == 65535 * 65536 == 4294901760
+    g.free()
+
+
+def test_render_pixels_at_2_32(gpu):
+    """vx_render_frame* with width * height >= 2^32 - 1: VX_ERR_CAPACITY before anything is allocated or queued"""
+    import ctypes as C
+    v, t = vx_scenes.rotated_cube()
+    grid = gpu.Grid.voxelize(gpu.Mesh.from_arrays(v, t), np.float32(0.09))
+    r = gpu.Renderer(grid)
+    eye = np.eye(4, dtype=np.float32)
+    dummy = np.zeros(16, np.uint32)
+    for w, h in ((65536, 65536), (65535, 65537), (0xFFFFFFFF, 1), (0xFFFFFFFF, 0xFFFFFFFF)):
+        a, keep = r._args((eye, eye, w, h), None)
+        a.rgba = dummy.ctypes.data
+        for fn in (gpu.lib().vx_render_frame, gpu.lib().vx_render_frame_device):
+            before = gpu.device_allocations()
+            st = fn(r.h, C.byref(a))
+            assert st == ERR_CAPACITY and gpu.lib().vx_last_error().decode() == "more than 2^32 pixels", (w, h)
+            assert gpu.device_allocations() == before
+    assert not dummy.any()
+    r.free()
+
+
+@pytest.mark.parametrize("X", [33, 63, 64, 1])
+def test_mask_padding_bits(gpu, X):
+    """bits past X*Y*Z in the last word of an externally written mask are not cells: refresh clears them (voxhip.h,
+    vx_grid_bitmask_device_mut), so occupied, the AABB list and the rays see exactly the grid's cells"""
+    import torch
+    g = gpu.Grid.create(gpu.GRID_BOOL, X, 1, 1, 1.0)
+    nw = g.describe()["num_words"]
+    assert nw == (X + 31) // 32
+    m = _mask_words(g, nw, mutable=True)
+    m.fill_(-1)
+    torch.cuda.synchronize()
+    del m
+    g.refresh()
+    d = g.describe()
+    assert d["occupied"] == X
+    w = g.bitmask()
+    want = np.full(nw, 0xFFFFFFFF, np.uint32)
+    if X % 32:
+        want[-1] = (1 << (X % 32)) - 1
+    assert np.array_equal(w, want)
+    a = g.aabbs()
+    assert len(a) == X and a["mx"][:, 0].max() == np.float32(X)
+    rays = np.array([[X + 40.0, 0.5, 0.5, -1.0, 1e-7, -1e-7]], np.float32)   # along -x from beyond the grid: the first hit is cell X - 1
+    tt, pp, _ = g.trace(rays)
+    assert pp[0] == X - 1 and tt[0] > 0
+    g.free()
