@@ -664,7 +664,7 @@ vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits);
  * (bits 48..63) by the single-pass paths.  out[i] is exact for every 16384-element tile whose exclusive prefix is below 2^40 - 1.
  * paths[k]: VX_SCAN_PATH_GEN (single pass, the block's next generation number; ticket mode past 512 tiles of 16384, as for the
  * library's callers), VX_SCAN_PATH_TICKET (single pass without a generation number), VX_SCAN_PATH_THREE (three passes),
- * VX_SCAN_PATH_AUTO (what the library does, VOXHIP_SCAN_3PASS / VOXHIP_SCAN_GEN switches included).  in_offset / out_offset
+ * VX_SCAN_PATH_AUTO (what the library's own callers do: the block's next generation number).  in_offset / out_offset
  * (elements) move the device arrays off their 16-byte alignment: a uint32 scan then takes the three-pass path whatever paths[k]
  * asks.  taken[k] (optional) is the path the scan took.  sel / group16 (optional; VX_SCAN_POPCOUNT / VX_SCAN_VALUES): sel_cap /
  * group16_cap words per scan (at least ceil(32 n / 1024) / n / 16 + 1; sel in popcount mode only), filled with VX_SCAN_CANARY_VALUE before the scan; the single-pass paths write sel[c] = the element

@@ -251,13 +251,6 @@ uint32_t advance_scan_gen(DevBuf& tmp, hipStream_t s)
     return tmp.scan_gen;
 }
 
-uint32_t next_scan_gen(DevBuf& tmp, hipStream_t s)
-{
-    static const bool off = getenv("VOXHIP_SCAN_GEN") && atoi(getenv("VOXHIP_SCAN_GEN")) == 0;  // 0: tickets + self-cleaning state (A/B, tests)
-    if (off) return 0u;
-    return advance_scan_gen(tmp, s);
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------
@@ -471,11 +464,9 @@ struct vx_grid {
         if (side) return hipSuccess;
         int lo = 0, hi = 0;
         hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);  // (lo: numerically greatest = lowest priority)
-        static const bool low_prio = !(getenv("VOXHIP_LIST_SIDE_PRIO") && atoi(getenv("VOXHIP_LIST_SIDE_PRIO")) == 0);
-        static const bool light_ev = !(getenv("VOXHIP_LIST_LIGHT_EVENTS") && atoi(getenv("VOXHIP_LIST_LIGHT_EVENTS")) == 0);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, low_prio ? lo : hi);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, lo);
         // (both events order streams of ONE device: no system-scope fence -- its cache write-back would stand in front of the ray kernel)
-        const unsigned evf = hipEventDisableTiming | (light_ev ? hipEventDisableSystemFence : 0u);
+        const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_ready, evf);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_list, evf);
         return e;
@@ -497,22 +488,21 @@ struct vx_grid {
         return e;
     }
     // `counter`, `dry_at`: the ray kernel's work queue (vx::WalkQueue), for the gate in front of the emission.  Holding the emission until the
-    // queue is DRY (VOXHIP_LIST_WAIT=2) was measured and is not the default: the drain frees registers wave by wave but LDS only workgroup
-    // by workgroup, the emission then needs the whole drain (155 us) and ends about when the ray kernel does -- 0.504-0.510 ms per step.
+    // queue is DRY was measured and dropped: the drain frees registers wave by wave but LDS only workgroup by workgroup, the emission then
+    // needs the whole drain (155 us) and ends about when the ray kernel does -- 0.504-0.510 ms per step.
     hipError_t list_side_launch(unsigned long long* counter, unsigned long long dry_at)
     {
         hipError_t e = hipStreamWaitEvent(side, ev_ready, 0);
         if (e != hipSuccess) return e;
-        // VOXHIP_LIST_WAIT: 0 no hold; 1 (default) until the first wave of the ray kernel has come back to the queue for more rays -- the
-        // kernel's persistent workgroups are all placed by then, the emission cannot take their slots first (without the hold the step
-        // varies 0.497-0.535 ms from run to run, with it 0.489-0.494); 2 until the queue is dry (measured: slower).  The hold is a
-        // one-wave gate kernel with a time bound (vx_trace.hip: a stream-level wait on the counter hangs under serialising profilers).
-        static const int wait_mode = getenv("VOXHIP_LIST_WAIT") ? atoi(getenv("VOXHIP_LIST_WAIT")) : 1;
-        if (wait_mode && counter && dry_at) {  // (dry_at == 0: the static first chunks cover the batch, the counter never moves)
+        // The emission is held until the first wave of the ray kernel has come back to the queue for more rays -- the kernel's persistent
+        // workgroups are all placed by then, the emission cannot take their slots first (without the hold the step varies 0.497-0.535 ms
+        // from run to run, with it 0.489-0.494).  The hold is a one-wave gate kernel with a time bound (vx_trace.hip: a stream-level wait
+        // on the counter hangs under serialising profilers).
+        if (counter && dry_at) {  // (dry_at == 0: the static first chunks cover the batch, the counter never moves)
             vx::WalkQueue q;
             q.counter = counter;
             q.dry_at = dry_at;
-            vx::launch_queue_gate(q, wait_mode == 2 ? dry_at : 1ull, /*timeout_us=*/wait_mode == 2 ? 2000u : 300u, side);
+            vx::launch_queue_gate(q, side);
         }
         list_emit(side);
         e = hipEventRecord(ev_list, side);
@@ -709,7 +699,7 @@ vx_status setup_launch(const vx_mesh* m, const vx::GridParams& g, int sat, uint6
     vx::launch_tri_setup(m->dv, m->di, tb, ntri, g, sat, zlo, zhi, recs.as<vx::TriRec>(), units.as<uint32_t>(), s, dgrid, clear, clear_bytes, shard_wb, shard_we,
                          ext.as<uint32_t>(), shard_rank, shard_world);
     const bool tg = vx::launch_scan_u32(units.as<uint32_t>(), ubase.as<uint32_t>(), ntri, false, scantmp.p, &mail->units, s, true, mail_tag, nullptr,
-                                        next_scan_gen(scantmp, s));
+                                        advance_scan_gen(scantmp, s));
     if (tagged) *tagged = tg && mail_tag != 0;
     return VX_OK;
 }
@@ -745,7 +735,7 @@ vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0, b
     VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(g->g.nwords), g->stream));
     VX_HIP(g->wp16.ensure((size_t)(g->g.nwords / 16 + 4) * 4));
     const bool tg = vx::launch_scan_u32(g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), g->g.nwords, true, g->scantmp.p, &g->mail->occupied, g->stream, true, tag,
-                                        g->wsel.as<uint32_t>(), next_scan_gen(g->scantmp, g->stream), g->wp16.as<uint32_t>());
+                                        g->wsel.as<uint32_t>(), advance_scan_gen(g->scantmp, g->stream), g->wp16.as<uint32_t>());
     g->sel_valid = tg;  // (the three-pass scan writes neither wsel nor wp16)
     if (tagged) *tagged = tg;
     g->occ_tag = tg ? tag : 0;  // what the host may poll the mailbox for instead of draining the stream (prefix_finish)
@@ -758,8 +748,7 @@ vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0, b
 vx_status prefix_finish(vx_grid* g, bool pending)
 {
     if (!pending || g->occupied_known) return VX_OK;
-    static const bool poll = !(getenv("VOXHIP_POLL_MAIL") && atoi(getenv("VOXHIP_POLL_MAIL")) == 0);
-    if (!(poll && g->occ_tag && mail_wait(&g->mail->occupied, nullptr, g->occ_tag, 5.0))) VX_HIP(hipStreamSynchronize(g->stream));
+    if (!(g->occ_tag && mail_wait(&g->mail->occupied, nullptr, g->occ_tag, 5.0))) VX_HIP(hipStreamSynchronize(g->stream));
     const unsigned long long tot = g->mail->occupied & kMailValue;
     if (tot >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 occupied voxels");
     g->occupied = tot;
@@ -898,7 +887,6 @@ vx_status solid_fill(vx_grid* g, uint64_t* n_interior, const uint32_t** h_words)
     uint32_t* ext = g->solid_e.as<uint32_t>();
     uint32_t prev = 2 * 32 - 1;  // the flag the first round reads: set by the seed (the other half of what batch 0 clears)
     vx::launch_solid_seed(words, g->solid_m.as<uint32_t>(), ext, dim, flags + prev, s);
-    static const bool poll = !(getenv("VOXHIP_POLL_MAIL") && atoi(getenv("VOXHIP_POLL_MAIL")) == 0);
     uint32_t batch = 4, rounds = 0;
     for (uint32_t k = 0;; ++k) {
         const uint32_t first = (k & 1u) * 32u;
@@ -910,7 +898,7 @@ vx_status solid_fill(vx_grid* g, uint64_t* n_interior, const uint32_t** h_words)
         g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
         const unsigned long long tag = (unsigned long long)g->mail_seq << 48;
         vx::launch_solid_report(flags + first, batch, &g->mail->solid_rounds, tag, s);
-        if (!(poll && mail_wait(&g->mail->solid_rounds, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+        if (!mail_wait(&g->mail->solid_rounds, nullptr, tag, 5.0)) VX_HIP(hipStreamSynchronize(s));
         const uint32_t changed = (uint32_t)(g->mail->solid_rounds & kMailValue);
         rounds += changed;
         if (changed < batch) break;  // a quiet round: every round after it exited at once
@@ -922,8 +910,8 @@ vx_status solid_fill(vx_grid* g, uint64_t* n_interior, const uint32_t** h_words)
     g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
     const unsigned long long tag = (unsigned long long)g->mail_seq << 48;
     const bool tagged = vx::launch_scan_u32(h, g->solid_pre.as<uint32_t>(), g->g.nwords, true, g->scantmp.p, &g->mail->interior, s, true, tag, nullptr,
-                                            next_scan_gen(g->scantmp, s));
-    if (!(poll && tagged && mail_wait(&g->mail->interior, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+                                            advance_scan_gen(g->scantmp, s));
+    if (!(tagged && mail_wait(&g->mail->interior, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
     const unsigned long long n = g->mail->interior & kMailValue;
     if (n >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 interior voxels");
     *n_interior = n;
@@ -1223,11 +1211,9 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     // Unsharded build: K1 leaves origin + dims in device memory, so the triangle records and the unit scan are queued right
     // behind it and the host waits ONCE for the bbox and the unit count (every host round trip costs ~20 us of idle GPU: the
     // wake-up plus the launch latency of an empty queue).  The bitmask of the previous build is cleared in the same window.
-    // sequence tag of this build's totals in the mailbox (never 0: an untagged word never matches); VOXHIP_POLL_MAIL=0: the host
-    // drains the stream instead of polling the mailbox
+    // sequence tag of this build's totals in the mailbox (never 0: an untagged word never matches)
     g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
     const unsigned long long mtag = (unsigned long long)g->mail_seq << 48;
-    static const bool poll_mail = !(getenv("VOXHIP_POLL_MAIL") && atoi(getenv("VOXHIP_POLL_MAIL")) == 0);
     Extent ex;
     uint64_t btri_entries = 0;  // entries of the block table filled by the launch queued ahead of the unit total
     bool setup_queued = false;
@@ -1262,7 +1248,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
             cleared = cb.cap;
         }
         // the bbox (written by k_bbox, two kernels earlier) and the unit total: polled from the mailbox, see the hit count below
-        if (!(poll_mail && units_tagged && mail_wait(&g->mail->units, nullptr, mtag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+        if (!(units_tagged && mail_wait(&g->mail->units, nullptr, mtag, 5.0))) VX_HIP(hipStreamSynchronize(s));
         VX_TRY(extent_from_bbox(g->mail->bbox, mesh->nv, vs, &ex));
         setup_queued = true;
     } else {
@@ -1303,9 +1289,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     }
 
     // Unsharded words, rows of whole words: the voxelizer ORs into the tiled build mask (one atomic request per 4 x 4 rows instead of one per
-    // row, launch_voxelize) and launch_untile writes every word of the reference's bitmask from it.  VOXHIP_VOX_TILED=0: always the direct form.
-    static const bool tiled_ok = !(getenv("VOXHIP_VOX_TILED") && atoi(getenv("VOXHIP_VOX_TILED")) == 0);
-    static const bool tiled_shards = !(getenv("VOXHIP_VOX_TILED_SHARDS") && atoi(getenv("VOXHIP_VOX_TILED_SHARDS")) == 0);
+    // row, launch_voxelize) and launch_untile writes every word of the reference's bitmask from it.  Ragged rows take the direct form.
     const bool whole_words = wb == 0 && we == g->g.nwords;
     // (a word shard goes the same way: the voxelizer keeps to the rows whose words it owns, launch_untile writes those and zeroes the rest --
     // a second pass over the WHOLE mask per rank, so only where the mask is small against the mesh: the size rule of the clear that rides in
@@ -1313,7 +1297,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     // ... and only for shards of a fifth of the mask or more: shard 0 of 2 / 4 / 8 at 512^3 (tools/shard_time.py, kernels of a rebuild)
     // 119.7 -> 97.9 / 90.6 -> 73.3 / 55.1 -> 64.0 us -- at an eighth the un-tiling pass costs what the voxelizer no longer has to gain
     const bool shard_small = (size_t)vx::tiled_mask_words(g->g.dim) * 4 / 256 <= (size_t)ntri && (we - wb) * 5 >= g->g.nwords;
-    const bool tiled = tiled_ok && (whole_words || (tiled_shards && shard_small)) && (ex.dim[0] % 32) == 0;
+    const bool tiled = (whole_words || shard_small) && (ex.dim[0] % 32) == 0;
     g->last_tiled = tiled;
     if (tiled) {
         const size_t tbytes = (size_t)vx::tiled_mask_words(g->g.dim) * 4;
@@ -1363,16 +1347,14 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     vx::launch_voxelize(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, o.sat_variant,
                         tiled ? g->twords.as<uint32_t>() : g->words.as<uint32_t>(), wb, we, umask, ds->set_calls, s, xw, bhits, tiled);
     // (the tiled mask -> the reference's bitmask: by the brick kernel on its way when the traversal structure is built right away, below)
-    static const bool eager = !(getenv("VOXHIP_EAGER") && atoi(getenv("VOXHIP_EAGER")) == 0);
-    static const bool fuse_untile = !(getenv("VOXHIP_FUSE_UNTILE") && atoi(getenv("VOXHIP_FUSE_UNTILE")) == 0);
     // (VX_VOXELIZE_SOLID: the fill reads and extends the reference's bitmask, the traversal structure is built from the final one)
-    const bool untile_in_bricks = tiled && eager && fuse_untile && whole_words && !solid;
+    const bool untile_in_bricks = tiled && whole_words && !solid;
     if (tiled && !untile_in_bricks) vx::launch_untile(g->twords.as<uint32_t>(), g->words.as<uint32_t>(), g->g.dim, s, wb, we);
     g->counts_valid = false;
     bool hits_tagged = false, occ_tagged = false, occ_queued = false;
     if (g->kind == VX_GRID_VEC) {
         VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nUB), s));
-        hits_tagged = vx::launch_scan_u32(bhits, g->hbase.as<uint32_t>(), nUB, false, g->scantmp.p, &g->mail->hits, s, true, mtag, nullptr, next_scan_gen(g->scantmp, s));
+        hits_tagged = vx::launch_scan_u32(bhits, g->hbase.as<uint32_t>(), nUB, false, g->scantmp.p, &g->mail->hits, s, true, mtag, nullptr, advance_scan_gen(g->scantmp, s));
     }
     // VX_VOXELIZE_SOLID: the second loop -- setVoxel on every interior cell in ascending order -- once the surface mask is complete
     uint64_t n_interior = 0;
@@ -1385,8 +1367,8 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     // A complete (unsharded) bitmask: queue what every consumer of the grid needs next -- the traversal structure (bricks,
     // bounds, mips = the reference's acceleration-structure build, hello_vulkan.cpp:700-703) and the word prefix (getAabbs /
     // primitive ids) -- behind the voxelizer instead of lazily in front of the first query.  For the Vec flavour this work
-    // runs while the host waits for the hit count.  VOXHIP_EAGER=0 keeps it lazy.
-    if (eager && wb == 0 && we == g->g.nwords) {
+    // runs while the host waits for the hit count.  A word shard's stay lazy (ensure_coarse / ensure_prefix in the query paths).
+    if (whole_words) {
         VX_TRY(ensure_coarse(g, untile_in_bricks));
         bool pending = false;
         occ_queued = !g->prefix_valid;
@@ -1404,15 +1386,15 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
                                   g->hbase.as<uint32_t>(), tgt, nullptr, s, to_bound ? g->bound_cap : cap_rec, xw);
         // The host needs the hit count (and takes the occupied count along).  Both are written by scans that run BEFORE the
         // emission: the host polls the tagged mailbox words and goes on queueing work (the caller's next call: a trace) while
-        // the emission still runs; a stream synchronize would wake it ~15 us after the last kernel.  VOXHIP_POLL_MAIL=0, an
-        // untagged total (three-pass scan) or 5 ms without an answer: the synchronize.
+        // the emission still runs; a stream synchronize would wake it ~15 us after the last kernel.  An untagged total
+        // (three-pass scan) or 5 ms without an answer: the synchronize.
         // VX_VOXELIZE_LIST_ASYNC: only the hit count -- its scan runs in front of the traversal structure and the word prefix, so the host
         // is back in the caller ~40 us of GPU work before the build ends and the caller's ray batch is queued in time; the occupied count
         // (the LAST kernel's total) is fetched when somebody asks for it (prefix_finish).
         const bool occ_in_flight = g->prefix_valid && !g->occupied_known;
         const bool occ_along = occ_in_flight && !(list_async && occ_queued && occ_tagged);
         bool got = false;
-        if (poll_mail && hits_tagged && (!occ_along || (occ_queued && occ_tagged)))
+        if (hits_tagged && (!occ_along || (occ_queued && occ_tagged)))
             got = mail_wait(&g->mail->hits, occ_along ? &g->mail->occupied : nullptr, mtag, 5.0);
         if (!got) VX_HIP(hipStreamSynchronize(s));
         const unsigned long long hits = g->mail->hits & kMailValue;
@@ -2049,9 +2031,9 @@ static vx_status surface_count(vx_grid* g, bool want_mat, uint64_t* nv, uint64_t
     if (want_mat) VX_TRY(prefix_launch(g, &pending));
     vx::launch_surface_count(g->words.as<uint32_t>(), g->g, p, g->surf_cnt.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->stream);
     vx::launch_scan_u32(g->surf_cnt.as<uint32_t>(), g->surf_tpre.as<uint32_t>(), g->g.nwords, false, g->scantmp.p, &g->mail->surf_tris, g->stream, true, 0,
-                        nullptr, next_scan_gen(g->scantmp, g->stream));
+                        nullptr, advance_scan_gen(g->scantmp, g->stream));
     vx::launch_scan_u32(g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(), p.nlw, true, g->scantmp.p, &g->mail->surf_verts, g->stream, true, 0,
-                        nullptr, next_scan_gen(g->scantmp, g->stream));
+                        nullptr, advance_scan_gen(g->scantmp, g->stream));
     VX_HIP(hipGetLastError());
     VX_HIP(hipStreamSynchronize(g->stream));
     VX_TRY(prefix_finish(g, pending));
@@ -2160,7 +2142,7 @@ static vx_status components_queue(vx_grid* g, uint32_t connectivity, uint32_t* l
     VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(g->g.nwords), g->stream));
     vx::launch_components(g->words.as<uint32_t>(), g->g, connectivity == VX_CONNECT_26, labels, g->cc_roots.as<uint32_t>(), g->stream);
     vx::launch_scan_u32(g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), g->g.nwords, true, g->scantmp.p, &g->mail->cc_count, g->stream, true, 0,
-                        nullptr, next_scan_gen(g->scantmp, g->stream));
+                        nullptr, advance_scan_gen(g->scantmp, g->stream));
     vx::launch_components_label(g->words.as<uint32_t>(), g->g, labels, g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), dev_count, g->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
@@ -2250,10 +2232,7 @@ vx_status vx_grid_aabbs_device(const vx_grid* gc, vx_aabb* dev_out, uint64_t cap
     VX_TRY(prefix_launch(g, &pending));
     if (cap && dev_out && (pending || g->occupied))
         vx::launch_emit_bool_aabbs(g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), g->g, dev_out, cap, g->stream, g->sel_valid ? g->wsel.as<uint32_t>() : nullptr);
-    {   // (as in vx_grid_aabbs_device_async: the traversal structure of an externally written mask, built while the host waits)
-        static const bool eager = !(getenv("VOXHIP_EAGER") && atoi(getenv("VOXHIP_EAGER")) == 0);
-        if (eager && pending) VX_TRY(ensure_coarse(g));
-    }
+    if (pending) VX_TRY(ensure_coarse(g));  // (as in vx_grid_aabbs_device_async: the traversal structure of an externally written mask, built while the host waits)
     VX_TRY(prefix_finish(g, pending));
     if (count) *count = g->occupied;
     VX_HIP(hipGetLastError());
@@ -2272,9 +2251,8 @@ vx_status vx_grid_aabbs_device_async(const vx_grid* gc, vx_aabb* dev_out, uint64
     bool pending = false;
     VX_TRY(prefix_launch(g, &pending));
     // a mask written from outside (the multi-rank exchange) has no traversal structure yet: queued here, it is built while the host waits
-    // for the count instead of after it, in front of the caller's ray batch (VOXHIP_EAGER=0: left to the ray batch)
-    static const bool eager = !(getenv("VOXHIP_EAGER") && atoi(getenv("VOXHIP_EAGER")) == 0);
-    if (eager && pending) VX_TRY(ensure_coarse(g));
+    // for the count instead of after it, in front of the caller's ray batch
+    if (pending) VX_TRY(ensure_coarse(g));
     VX_TRY(prefix_finish(g, pending));
     if (count) *count = g->occupied;
     if (cap && dev_out && g->occupied) {
@@ -2398,6 +2376,21 @@ void vx_grid_free(vx_grid* g)
 }
 
 // ---- rays -----------------------------------------------------------------------------------------------------
+// the grid's traversal structure as launch_trace takes it; *p16: the 16th-prefix table of the word prefix for the rank pass, null where it
+// cannot be used (a three-pass scan wrote none; the mask is allocated with two spare words, so a rank may read its voxel's whole
+// 16-word group only when that lies inside: nwords % 16 == 0)
+static vx::TraceMips grid_mips(const vx_grid* g, const uint32_t** p16)
+{
+    vx::TraceMips mips;
+    mips.bricks3 = g->bricks.as<unsigned long long>();
+    mips.w0 = g->words.as<uint32_t>();
+    mips.w1 = g->cwords.as<uint32_t>();
+    mips.w2 = g->c2words.as<uint32_t>();
+    for (int a = 0; a < 3; ++a) { mips.d1[a] = g->cdim[a]; mips.d2[a] = g->c2dim[a]; }
+    *p16 = (g->sel_valid && (g->g.nwords % 16) == 0) ? g->wp16.as<uint32_t>() : nullptr;
+    return mips;
+}
+
 static vx_status trace_common(vx_grid* g, vx::TraceIO io)
 {
     VX_TRY(ensure_coarse(g));
@@ -2414,12 +2407,8 @@ static vx_status trace_common(vx_grid* g, vx::TraceIO io)
             io.t_out = g->ttmp.as<float>();
         }
     }
-    vx::TraceMips mips;
-    mips.bricks3 = g->bricks.as<unsigned long long>();
-    mips.w0 = g->words.as<uint32_t>();
-    mips.w1 = g->cwords.as<uint32_t>();
-    mips.w2 = g->c2words.as<uint32_t>();
-    for (int a = 0; a < 3; ++a) { mips.d1[a] = g->cdim[a]; mips.d2[a] = g->c2dim[a]; }
+    const uint32_t* p16 = nullptr;  // (read by the rank pass only, which runs with `prefix`)
+    const vx::TraceMips mips = grid_mips(g, &p16);
     if (io.cam) {
         VX_HIP(g->camera.ensure(sizeof(vx::Camera)));
         VX_HIP(hipMemcpyAsync(g->camera.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, g->stream));
@@ -2428,9 +2417,6 @@ static vx_status trace_common(vx_grid* g, vx::TraceIO io)
     }
     const bool list_beside = g->list_deferred;  // VX_VOXELIZE_LIST_ASYNC: the list's emission goes beside this ray batch
     if (list_beside) VX_HIP(g->list_side_begin());
-    static const bool rank16 = !(getenv("VOXHIP_RANK16") && atoi(getenv("VOXHIP_RANK16")) == 0);
-    // (the mask is allocated with two spare words, so a rank may read its voxel's whole 16-word group only when that lies inside: nwords % 16 == 0)
-    const uint32_t* p16 = (prefix && g->sel_valid && rank16 && (g->g.nwords % 16) == 0) ? g->wp16.as<uint32_t>() : nullptr;
     vx::WalkQueue wq;
     vx::launch_trace(g->g, mips, prefix, io, g->small.as<Small>()->trace_counters, &g->trace_phase, idx_tmp, g->stream, p16, list_beside ? &wq : nullptr);
     if (list_beside) VX_HIP(g->list_side_launch(wq.counter, wq.dry_at));
@@ -2632,7 +2618,7 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
         OCT_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(nUB), s));
         vx::launch_voxelize(recs.as<vx::TriRec>(), ubase.as<uint32_t>(), btri.as<uint32_t>(), ntri, g, 0, nullptr, 0, 0, umask.as<uint32_t>(), ds->set_calls, s, xw,
                             bhits.as<uint32_t>());
-        vx::launch_scan_u32(bhits.as<uint32_t>(), hbase.as<uint32_t>(), nUB, false, scantmp.p, &mail->hits, s, true, 0, nullptr, next_scan_gen(scantmp, s));
+        vx::launch_scan_u32(bhits.as<uint32_t>(), hbase.as<uint32_t>(), nUB, false, scantmp.p, &mail->hits, s, true, 0, nullptr, advance_scan_gen(scantmp, s));
         OCT_HIP(hipStreamSynchronize(s));
         hits = mail->hits & kMailValue;
         if (hits >= 0xFFFFFFFFull) return bail(fail(VX_ERR_CAPACITY, "more than 2^32 octree items"));
@@ -2657,7 +2643,7 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
         OCT_HIP(nbase.ensure(((size_t)ni + 2) * 4));
         OCT_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(ni), s));
         vx::launch_oct_depths(o->items.as<uint64_t>(), ni, o->bits, (uint32_t)max_items, ncount.as<uint8_t>(), s);
-        vx::launch_scan_u8(ncount.as<uint8_t>(), nbase.as<uint32_t>(), ni, scantmp.p, &mail->occupied, s, 0, next_scan_gen(scantmp, s));
+        vx::launch_scan_u8(ncount.as<uint8_t>(), nbase.as<uint32_t>(), ni, scantmp.p, &mail->occupied, s, 0, advance_scan_gen(scantmp, s));
         OCT_HIP(hipStreamSynchronize(s));
         const unsigned long long nn = mail->occupied & kMailValue;
         if (nn == 0 || nn >= 0xFFFFFFFFull) return bail(fail(VX_ERR_CAPACITY, "more than 2^32 octree nodes"));
@@ -3394,14 +3380,6 @@ struct vx_render_scene {
 };
 
 namespace {
-// Shadow rays of pixels whose shading cannot read the flag (misses, hits facing away from the light) get the empty interval tmax 0 < tmin:
-// the traversals leave them at once (5-12 % of the frame).  VOXHIP_RENDER_CULL=0 traces every pixel's ray as render() does.
-bool render_cull()
-{
-    static const bool on = !(getenv("VOXHIP_RENDER_CULL") && atoi(getenv("VOXHIP_RENDER_CULL")) == 0);
-    return on;
-}
-
 vx_status render_desc_check(const vx_render_desc* d)
 {
     if (!d) return fail(VX_ERR_INVALID_ARG, "null argument");
@@ -3595,7 +3573,7 @@ vx_status render_upload_attributes(vx_render_scene* s)
 }
 
 // size the per-pixel buffers (pooled: a size already rendered requests nothing)
-vx_status render_buffers(vx_render_scene* s, uint64_t n, bool cull)
+vx_status render_buffers(vx_render_scene* s, uint64_t n)
 {
     if (has_source(s, 0)) {
         VX_HIP(s->vt.ensure(n * 4 + 8));
@@ -3614,7 +3592,7 @@ vx_status render_buffers(vx_render_scene* s, uint64_t n, bool cull)
     }
     VX_HIP(s->srays.ensure(n * 24 + 8));
     VX_HIP(s->sdist.ensure(n * 4 + 8));
-    if (cull) VX_HIP(s->stmax.ensure(n * 4 + 8));
+    VX_HIP(s->stmax.ensure(n * 4 + 8));
     if ((s->shading & VX_RENDER_ATTRIBUTES) && has_source(s, 1)) VX_HIP(s->nbuf.ensure(n * 12 + 8));
     return VX_OK;
 }
@@ -3623,7 +3601,6 @@ vx_status render_buffers(vx_render_scene* s, uint64_t n, bool cull)
 vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_render_light& light, uint32_t* rgba, uint8_t* kind, uint8_t* shadowed)
 {
     const uint64_t n = (uint64_t)a->width * a->height;
-    const bool cull = render_cull();
     hipStream_t st = s->stream;
     vx_grid* g = s->grid;
     if (g) {  // the traversal structure and the word prefix, built once per grid build on the grid's own stream (no-ops when current)
@@ -3631,7 +3608,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
         bool pending = false;
         VX_TRY(prefix_launch(g, &pending));
     }
-    VX_TRY(render_buffers(s, n, cull));
+    VX_TRY(render_buffers(s, n));
     // start: the frame's stream waits for everything queued so far on the sources' streams
     for (int k = 0; k < 2; ++k) {
         if (!has_source(s, k)) continue;
@@ -3657,15 +3634,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     io.normal_out = s->vnrm.as<float>();
     vx::TraceMips mips{};
     const uint32_t* p16 = nullptr;
-    if (g) {
-        mips.bricks3 = g->bricks.as<unsigned long long>();
-        mips.w0 = g->words.as<uint32_t>();
-        mips.w1 = g->cwords.as<uint32_t>();
-        mips.w2 = g->c2words.as<uint32_t>();
-        for (int k = 0; k < 3; ++k) { mips.d1[k] = g->cdim[k]; mips.d2[k] = g->c2dim[k]; }
-        static const bool rank16 = !(getenv("VOXHIP_RANK16") && atoi(getenv("VOXHIP_RANK16")) == 0);
-        p16 = (g->sel_valid && rank16 && (g->g.nwords % 16) == 0) ? g->wp16.as<uint32_t>() : nullptr;  // as trace_common
-    }
+    if (g) mips = grid_mips(g, &p16);
     vx_octree* o = s->octree;
     auto voxels = [&](const vx::TraceIO& q) {
         if (g) vx::launch_trace(g->g, mips, g->wprefix.as<uint32_t>(), q, s->counters.as<unsigned long long>(), &s->phase, s->idxtmp.p, st, p16, nullptr);
@@ -3721,7 +3690,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     P.light_type = light.type;
     P.srays = s->srays.as<float>();
     P.sdist = s->sdist.as<float>();
-    P.stmax = cull ? s->stmax.as<float>() : nullptr;
+    P.stmax = s->stmax.as<float>();
     P.sv = vox ? s->sv.as<uint8_t>() : nullptr;
     const int16_t* vids = g ? vx_grid_material_ids_device(g) : nullptr;
     if (vids && s->nvmat) {
@@ -3745,13 +3714,15 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     if (attr) vx::launch_render_shadow_rays_attr(P, A, tl != nullptr, st);
     else if (tl) vx::launch_render_shadow_rays_tlas(P, st);
     else vx::launch_render_shadow_rays(P, st);
-    // shadow rays: any-hit against the voxels and the mesh (rchit:108-122), tMax = the light distance
+    // shadow rays: any-hit against the voxels and the mesh (rchit:108-122), tMax = the light distance -- or 0, the empty interval
+    // (0 < tmin) that the traversals leave at once, for pixels whose shading cannot read the flag: misses, hits facing away from the
+    // light (5-12 % of the frame)
     vx::TraceIO sio;
     sio.rays = s->srays.as<float>();
     sio.nrays = n;
     sio.tmin = 0.001f;
     sio.tmax = 10000.0f;
-    sio.tmax_per_ray = cull ? s->stmax.as<float>() : s->sdist.as<float>();
+    sio.tmax_per_ray = s->stmax.as<float>();
     sio.any_hit = true;
     sio.shadowed_out = s->sv.as<uint8_t>();
     if (vox) voxels(sio);
@@ -3990,9 +3961,9 @@ vx_status vx_scan_u32(const vx_scan_args* a)
         if (e != hipSuccess) break;
         // the path: GEN = the next generation of the block (ticket mode above kScanGenTiles tiles, as for every library caller);
         // TICKET / THREE = no generation, on a block that is all zero (cleared first when an older generation-mode scan left words);
-        // AUTO = what the library's own callers do (the VOXHIP_SCAN_3PASS / VOXHIP_SCAN_GEN switches)
+        // AUTO = what the library's own callers do (the next generation, kScanPathAuto)
         const uint32_t p = a->paths[k];
-        const uint32_t gen = p == VX_SCAN_PATH_GEN ? advance_scan_gen(tmp, s) : p == VX_SCAN_PATH_AUTO ? next_scan_gen(tmp, s) : 0u;
+        const uint32_t gen = (p == VX_SCAN_PATH_GEN || p == VX_SCAN_PATH_AUTO) ? advance_scan_gen(tmp, s) : 0u;
         const int lp = p == VX_SCAN_PATH_THREE ? vx::kScanPathThree : p == VX_SCAN_PATH_AUTO ? vx::kScanPathAuto : vx::kScanPathOne;
         if (!gen && !zero) (void)hipMemsetAsync(tmp.p, 0, tmp.cap, s);
         const bool tz = true;

@@ -70,7 +70,7 @@ void launch_tri_setup(const float* verts, const int32_t* idx, uint64_t tri_begin
 // exclusive scan of n uint32 (or of their popcounts) into out[0..n] (out[n] = total mod 2^32, saturating check via *total64)
 // *total64: exact below 2^40 - 1, then at least 2^40 - 1 and below 2^48 (vx_kernels.hip, THE TOTAL): a caller refuses a total >= 0xFFFFFFFF.
 size_t scan_tmp_bytes(uint64_t n);
-// path: kScanPathAuto = single-pass unless VOXHIP_SCAN_3PASS=1 (read once per process); the other two choose in the call (test aid).
+// path: kScanPathAuto = single-pass; the other two choose in the call (test aid).
 // Unaligned in / out take the three-pass path whatever `path` says.
 constexpr int kScanPathAuto = 0, kScanPathOne = 1, kScanPathThree = 2;
 // tmp_is_zero: the caller guarantees tmp (scan_tmp_bytes(n)) is all zero; the scan leaves it all zero again.
@@ -170,7 +170,7 @@ struct WalkQueue {
     unsigned long long* counter = nullptr;
     unsigned long long dry_at = 0;
 };
-void launch_queue_gate(const WalkQueue& q, unsigned long long at_least, unsigned timeout_us, hipStream_t s);  // vx_trace.hip
+void launch_queue_gate(const WalkQueue& q, hipStream_t s);  // vx_trace.hip: holds `s` until the kernel's first wave has drawn from q (300 us bound)
 void launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, unsigned long long* counters /*2 device words, zero before the first trace; they alternate*/, int* phase /*host*/,
                   void* idx_tmp /*trace_idx_bytes when ranks / normals / the hit list are wanted*/, hipStream_t s,
                   const uint32_t* prefix16 = nullptr /*optional: launch_scan_u32's group16 of word_prefix*/, WalkQueue* queue = nullptr);
@@ -260,8 +260,8 @@ __device__ __forceinline__ void tlas_world_normal(const TlasBlas* tab, const uin
 
 // Frames (vx_render.hip): the per-pixel stages of vx_render_frame_device around the traversals.  n = width * height pixels, pixel
 // r = py * width + px.  Hit arrays as the traversals write them (mt / mprim / mnrm / mbary null without a mesh); srays (6 f32 per pixel),
-// sdist (the light distance: the shadow ray's tMax and the shading's 1/d^2) and, optional, stmax (sdist with 0 where no shading reads
-// the shadow flag) are written by the shadow-ray stage and read by the shading stage; sv / sm (optional) are the two shadow queries.
+// sdist (the light distance, for the shading's 1/d^2) and stmax (the shadow ray's tMax: sdist, with 0 where no shading reads the shadow
+// flag) are written by the shadow-ray stage; sv / sm (optional) are the two shadow queries.
 // the mesh of each BLAS of an instanced scene (vx_render_create_tlas): vertices, index triples, per-triangle material ids (null: none)
 // and its material table
 struct InstMesh {

@@ -492,8 +492,7 @@ bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcoun
 {
     const uint32_t nblocks = (uint32_t)(((n + 1) + kScanTile - 1) / kScanTile);
     unsigned long long* status = (unsigned long long*)tmp;
-    static const bool env_three_pass = getenv("VOXHIP_SCAN_3PASS") && atoi(getenv("VOXHIP_SCAN_3PASS"));
-    const bool three_pass = path == kScanPathAuto ? env_three_pass : path == kScanPathThree;
+    const bool three_pass = path == kScanPathThree;
     const bool aligned = ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;  // the single-pass kernel moves 16-byte vectors
     if (!three_pass && aligned) {
         const uint32_t ntiles = (uint32_t)(((n + 1) + kOneTile - 1) / kOneTile);

@@ -179,16 +179,15 @@ __device__ __forceinline__ void render_shadow_rays(const RenderParams& P, const 
         attr_normal<kInst>(P, A, r, d0, d1, d2, an0, an1, an2);
         A.nbuf[3 * r] = an0; A.nbuf[3 * r + 1] = an1; A.nbuf[3 * r + 2] = an2;
     }
-    if (P.stmax) {  // compaction by empty intervals: only a hit facing the light can read its shadow flag
-        bool active = tri || vt > 0.f;
-        if (active) {
-            float n0, n1, n2;
-            if (kAttr && tri) { n0 = an0; n1 = an1; n2 = an2; }
-            else shade_normal(tri, P, r, d0, d1, d2, n0, n1, n2);
-            active = dot3(n0, n1, n2, L0, L1, L2) > 0.0f;
-        }
-        P.stmax[r] = active ? dist : 0.0f;  // tmax 0 < tmin 0.001: no hit can be accepted
+    // compaction by empty intervals: only a hit facing the light can read its shadow flag
+    bool active = tri || vt > 0.f;
+    if (active) {
+        float n0, n1, n2;
+        if (kAttr && tri) { n0 = an0; n1 = an1; n2 = an2; }
+        else shade_normal(tri, P, r, d0, d1, d2, n0, n1, n2);
+        active = dot3(n0, n1, n2, L0, L1, L2) > 0.0f;
     }
+    P.stmax[r] = active ? dist : 0.0f;  // tmax 0 < tmin 0.001: no hit can be accepted
 }
 
 __global__ __launch_bounds__(kRenderBlock) void k_render_shadow_rays(RenderParams P) { render_shadow_rays<false, false>(P, AttrParams{}); }

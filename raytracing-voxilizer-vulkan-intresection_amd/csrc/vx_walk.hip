@@ -1082,7 +1082,6 @@ void launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, 
     const char* env_lds = getenv("VOXHIP_TRACE_LDS");
     const bool wide = g.dim[0] > 65535u || g.dim[1] > 65535u || g.dim[2] > 65535u;  // cell coordinates beyond 16 bits: the WIDE variants (global-memory mips only)
     const bool lds = !wide && (size_t)(m1_words + m2_words) * 4 <= 32768 + 1024 && !(env_lds && atoi(env_lds) == 0);
-    const int env_blocks = getenv("VOXHIP_TRACE_BLOCKS") ? atoi(getenv("VOXHIP_TRACE_BLOCKS")) : 0;
     WalkParams P;
     std::memset(&P, 0, sizeof(P));
     P.hot.g = g;
@@ -1120,7 +1119,6 @@ void launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, 
         // rays in flight (measured on the bench scene, 0.5M / 0.75M / 1M rays: -3 / -8 / -8 %; below ~0.4M rays, where a lane has at
         // most one or two rays anyway, the full width is faster, and from ~1.1M rays on the rule gives the full width).
         if (n >= 400000ull && n / 1040ull < max_blocks) max_blocks = n / 1040ull;
-        if (env_blocks > 0) max_blocks = (uint64_t)env_blocks;
         uint64_t nblk = (n + VX_W_BLOCK - 1) / VX_W_BLOCK;
         if (nblk > max_blocks) nblk = max_blocks;
         const dim3 grid((unsigned)nblk), block(VX_W_BLOCK);

@@ -7,7 +7,6 @@ vx_scenes.INTERIOR_CAMERAS[0] at 1280x720 and 3840x2160, and the reference camer
   cli_host_ms   the CLI's host path (voxilizer --render --mesh, host staging + host shading) on the same scene and size: the host wall of
                 that command minus the wall of the same command without --render / --mesh, median of --cli-reps runs (the difference also
                 holds the mesh's OBJ read and BVH build, a few ms).
-VOXHIP_RENDER_CULL=0 in the environment switches the shadow-ray compaction off; the line reports which was measured.
    usage: render_time.py [--frames 50] [--cli-reps 3] [--no-cli]"""
 import argparse
 import json
@@ -84,7 +83,7 @@ def main():
     grid = voxhip.Grid.voxelize(mesh, np.float32(VS))
     bvh = mesh.bvh()
     r = voxhip.Renderer(grid, bvh, mesh)
-    res = {"scene": "atrium262k@512^3 + atrium mesh", "cull": os.environ.get("VOXHIP_RENDER_CULL", "1") != "0", "frames": a.frames}
+    res = {"scene": "atrium262k@512^3 + atrium mesh", "frames": a.frames}
     tmp = tempfile.mkdtemp()
     obj = os.path.join(tmp, "atrium.obj")
     if not a.no_cli:

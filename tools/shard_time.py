@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel times of a steady-state SHARDED rebuild of the bench scene (word shard 0 of N by rank), HIP events on the launch stream.
-   usage: shard_time.py [N=2] [grid=512]      (VOXHIP_VOX_TILED_SHARDS=0 for the direct form)"""
+   usage: shard_time.py [N=2] [grid=512]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "raytracing-voxilizer-vulkan-intresection_amd")]
