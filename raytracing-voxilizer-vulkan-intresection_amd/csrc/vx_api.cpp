@@ -10,6 +10,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -2391,6 +2392,17 @@ static vx::TraceMips grid_mips(const vx_grid* g, const uint32_t** p16)
     return mips;
 }
 
+// primary rays: the batch's camera (io.cam, on the caller's stack) into the handle's device copy, for the kernels to read as io.cam_dev
+static vx_status upload_camera(DevBuf& buf, hipStream_t stream, vx::TraceIO& io)
+{
+    if (!io.cam) return VX_OK;
+    VX_HIP(buf.ensure(sizeof(vx::Camera)));
+    VX_HIP(hipMemcpyAsync(buf.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, stream));
+    VX_HIP(hipStreamSynchronize(stream));  // the host copy lives on the caller's stack
+    io.cam_dev = buf.as<vx::Camera>();
+    return VX_OK;
+}
+
 static vx_status trace_common(vx_grid* g, vx::TraceIO io)
 {
     VX_TRY(ensure_coarse(g));
@@ -2409,12 +2421,7 @@ static vx_status trace_common(vx_grid* g, vx::TraceIO io)
     }
     const uint32_t* p16 = nullptr;  // (read by the rank pass only, which runs with `prefix`)
     const vx::TraceMips mips = grid_mips(g, &p16);
-    if (io.cam) {
-        VX_HIP(g->camera.ensure(sizeof(vx::Camera)));
-        VX_HIP(hipMemcpyAsync(g->camera.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, g->stream));
-        VX_HIP(hipStreamSynchronize(g->stream));  // the host copy lives on the caller's stack
-        io.cam_dev = g->camera.as<vx::Camera>();
-    }
+    VX_TRY(upload_camera(g->camera, g->stream, io));
     const bool list_beside = g->list_deferred;  // VX_VOXELIZE_LIST_ASYNC: the list's emission goes beside this ray batch
     if (list_beside) VX_HIP(g->list_side_begin());
     vx::WalkQueue wq;
@@ -2486,10 +2493,19 @@ vx_status vx_trace_ex_device(const vx_grid* gc, const vx_trace_args* args)
     return trace_common(g, io);
 }
 
-// host-buffer variant: stages every non-null array through pooled device memory on (device, stream), then runs `run(io)` on the staged io
+// an output of one handle type beside vx_trace_args' (bary, instance): the host array (null: not wanted), its bytes per ray, and where
+// `run` finds the staged device array
+struct StagedOut {
+    void* host;
+    size_t stride;
+    void** dev;
+};
+
+// host-buffer variant: stages every non-null array (and at most two `extra` outputs) through pooled device memory on (device, stream),
+// then runs `run(io)` on the staged io
 extern "C++" {
 template <class Run>
-static vx_status trace_ex_staged(int device, hipStream_t stream, const vx_trace_args* args, Run run)
+static vx_status trace_ex_staged(int device, hipStream_t stream, const vx_trace_args* args, Run run, std::initializer_list<StagedOut> extra = {})
 {
     vx::Camera cam{};
     vx::TraceIO io;
@@ -2497,9 +2513,10 @@ static vx_status trace_ex_staged(int device, hipStream_t stream, const vx_trace_
     if (args->hits) return fail(VX_ERR_UNSUPPORTED, "the compacted hit list is a device-side output: use the _device variant");
     const uint64_t n = io.nrays;
     if (!n) return VX_OK;
-    DevBuf dr, dtm, dt, dp, dn, ds;
-    for (DevBuf* b : {&dr, &dtm, &dt, &dp, &dn, &ds}) { b->dev = device; b->stream = stream; }
-    auto rel = [&]() { for (DevBuf* b : {&dr, &dtm, &dt, &dp, &dn, &ds}) b->release(); };
+    if (extra.size() > 2) return fail(VX_ERR_INVALID_ARG, "trace_ex_staged: more than two extra outputs");
+    DevBuf dr, dtm, dt, dp, dn, ds, dx[2];
+    DevBuf* const all[] = {&dr, &dtm, &dt, &dp, &dn, &ds, &dx[0], &dx[1]};
+    for (DevBuf* b : all) { b->dev = device; b->stream = stream; }
     hipError_t e = hipSuccess;
     vx_status st = VX_OK;
     if (io.rays) { e = dr.ensure((size_t)n * 24); if (e == hipSuccess) e = hipMemcpyAsync(dr.p, args->rays, (size_t)n * 24, hipMemcpyHostToDevice, stream); io.rays = dr.as<float>(); }
@@ -2508,15 +2525,25 @@ static vx_status trace_ex_staged(int device, hipStream_t stream, const vx_trace_
     if (e == hipSuccess && args->prim) { e = dp.ensure((size_t)n * 4); io.prim_out = dp.as<uint32_t>(); }
     if (e == hipSuccess && args->normal) { e = dn.ensure((size_t)n * 12); io.normal_out = dn.as<float>(); }
     if (e == hipSuccess && args->shadowed) { e = ds.ensure((size_t)n); io.shadowed_out = ds.as<uint8_t>(); }
+    DevBuf* xb = dx;
+    for (const StagedOut& x : extra) {
+        if (e == hipSuccess && x.host) { e = xb->ensure((size_t)n * x.stride + 16); *x.dev = xb->p; }
+        ++xb;
+    }
     if (e == hipSuccess) st = run(io);
     if (e == hipSuccess && st == VX_OK) {
         if (args->t) e = hipMemcpyAsync(args->t, dt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess && args->prim) e = hipMemcpyAsync(args->prim, dp.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess && args->normal) e = hipMemcpyAsync(args->normal, dn.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess && args->shadowed) e = hipMemcpyAsync(args->shadowed, ds.p, (size_t)n, hipMemcpyDeviceToHost, stream);
+        xb = dx;
+        for (const StagedOut& x : extra) {
+            if (e == hipSuccess && x.host) e = hipMemcpyAsync(x.host, xb->p, (size_t)n * x.stride, hipMemcpyDeviceToHost, stream);
+            ++xb;
+        }
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
     }
-    rel();
+    for (DevBuf* b : all) b->release();
     if (st != VX_OK) return st;
     VX_HIP(e);
     return VX_OK;
@@ -2735,12 +2762,7 @@ vx_status vx_octree_aabbs(const vx_octree* o, vx_aabb* host_out, uint64_t cap, u
 static vx_status octree_trace_common(vx_octree* o, vx::TraceIO io)
 {
     if (!io.nrays) return VX_OK;
-    if (io.cam) {
-        VX_HIP(o->camera.ensure(sizeof(vx::Camera)));
-        VX_HIP(hipMemcpyAsync(o->camera.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, o->stream));
-        VX_HIP(hipStreamSynchronize(o->stream));  // the host copy lives on the caller's stack
-        io.cam_dev = o->camera.as<vx::Camera>();
-    }
+    VX_TRY(upload_camera(o->camera, o->stream, io));
     const uint64_t nitems = o->nnodes == 0 ? 0 : o->nitems;  // the list vx_octree_aabbs returns
     vx::launch_octree_trace(o->dnodes, o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, o->stream);
     VX_HIP(hipGetLastError());
@@ -2946,12 +2968,7 @@ vx_status vx_bvh_leaf_triangles(const vx_bvh* b, uint32_t* host, uint64_t cap)
 static vx_status bvh_trace_common(vx_bvh* b, vx::TraceIO io, float* bary)
 {
     if (!io.nrays) return VX_OK;
-    if (io.cam) {
-        VX_HIP(b->camera.ensure(sizeof(vx::Camera)));
-        VX_HIP(hipMemcpyAsync(b->camera.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, b->stream));
-        VX_HIP(hipStreamSynchronize(b->stream));  // the host copy lives on the caller's stack
-        io.cam_dev = b->camera.as<vx::Camera>();
-    }
+    VX_TRY(upload_camera(b->camera, b->stream, io));
     vx::launch_bvh_trace(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height, b->extent, b->coord_max, io, bary,
                          b->stream);
     VX_HIP(hipGetLastError());
@@ -2985,22 +3002,9 @@ vx_status vx_bvh_trace_ex(const vx_bvh* bc, const vx_bvh_trace_args* args)
     vx::Camera cam{};
     vx::TraceIO io;
     VX_TRY(bvh_args_to_io(args, &cam, &io));
-    if (!args->bary) return trace_ex_staged(b->device, b->stream, &args->base, [&](const vx::TraceIO& sio) { return bvh_trace_common(b, sio, nullptr); });
-    // bary: staged here, the rest by the shared staging
-    DevBuf db;
-    db.dev = b->device;
-    db.stream = b->stream;
-    VX_HIP(db.ensure((size_t)io.nrays * 8 + 16));
-    vx_status st = trace_ex_staged(b->device, b->stream, &args->base, [&](const vx::TraceIO& sio) { return bvh_trace_common(b, sio, db.as<float>()); });
-    hipError_t e = hipSuccess;
-    if (st == VX_OK && io.nrays) {
-        e = hipMemcpyAsync(args->bary, db.p, (size_t)io.nrays * 8, hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-    }
-    db.release();
-    if (st != VX_OK) return st;
-    VX_HIP(e);
-    return VX_OK;
+    void* bary = nullptr;  // the staged array (null when args->bary is)
+    return trace_ex_staged(b->device, b->stream, &args->base, [&](const vx::TraceIO& sio) { return bvh_trace_common(b, sio, (float*)bary); },
+                           {{args->bary, 8, &bary}});
 }
 
 vx_status vx_bvh_trace(const vx_bvh* bc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim,
@@ -3180,12 +3184,7 @@ vx_status tlas_update_host(vx_tlas* t, const vx_instance* in, uint64_t n)
 vx_status tlas_trace_common(vx_tlas* t, vx::TraceIO io, float* bary, uint32_t* inst)
 {
     if (!io.nrays) return VX_OK;
-    if (io.cam) {
-        VX_HIP(t->camera.ensure(sizeof(vx::Camera)));
-        VX_HIP(hipMemcpyAsync(t->camera.p, io.cam, sizeof(vx::Camera), hipMemcpyHostToDevice, t->stream));
-        VX_HIP(hipStreamSynchronize(t->stream));  // the host copy lives on the caller's stack
-        io.cam_dev = t->camera.as<vx::Camera>();
-    }
+    VX_TRY(upload_camera(t->camera, t->stream, io));
     VX_TRY(tlas_wait_blas(t));
     vx::launch_tlas_trace(tlas_dev(t), io, bary, inst, t->stream);
     VX_HIP(hipGetLastError());
@@ -3304,25 +3303,9 @@ vx_status vx_tlas_trace_ex(const vx_tlas* tc, const vx_tlas_trace_args* args)
     vx::Camera cam{};
     vx::TraceIO io;
     VX_TRY(tlas_args_to_io(args, &cam, &io));
-    // bary / instance: staged here, the rest by the shared staging
-    DevBuf db, di;
-    for (DevBuf* x : {&db, &di}) { x->dev = t->device; x->stream = t->stream; }
-    hipError_t e = hipSuccess;
-    if (args->bary && io.nrays) e = db.ensure((size_t)io.nrays * 8 + 16);
-    if (e == hipSuccess && args->instance && io.nrays) e = di.ensure((size_t)io.nrays * 4 + 16);
-    vx_status st = e == hipSuccess ? trace_ex_staged(t->device, t->stream, &args->base, [&](const vx::TraceIO& sio) {
-        return tlas_trace_common(t, sio, args->bary ? db.as<float>() : nullptr, args->instance ? di.as<uint32_t>() : nullptr);
-    }) : VX_OK;
-    if (e == hipSuccess && st == VX_OK && io.nrays) {
-        if (args->bary) e = hipMemcpyAsync(args->bary, db.p, (size_t)io.nrays * 8, hipMemcpyDeviceToHost, t->stream);
-        if (e == hipSuccess && args->instance) e = hipMemcpyAsync(args->instance, di.p, (size_t)io.nrays * 4, hipMemcpyDeviceToHost, t->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    }
-    db.release();
-    di.release();
-    if (st != VX_OK) return st;
-    VX_HIP(e);
-    return VX_OK;
+    void *bary = nullptr, *inst = nullptr;  // the staged arrays (null when the argument is)
+    return trace_ex_staged(t->device, t->stream, &args->base, [&](const vx::TraceIO& sio) { return tlas_trace_common(t, sio, (float*)bary, (uint32_t*)inst); },
+                           {{args->bary, 8, &bary}, {args->instance, 4, &inst}});
 }
 
 vx_status vx_tlas_trace(const vx_tlas* tc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_instance,

@@ -1,10 +1,11 @@
 // vx_blas.h -- the descent of one triangle BVH (a BLAS) inside k_tlas_trace (vx_tlas.hip), restating k_bvh_trace's (vx_bvh.hip): the widened
 // box test, Moeller-Trumbore in the order include/voxhip.h pins, and the front-to-back descent with its LDS stack.  The closest-hit tie
 // rule is a template parameter: the triangle index alone for one BVH, (instance, triangle) lexicographically for a TLAS.  The reasoning
-// behind the widening (kTRel, the per-BVH pad) is at the head of vx_bvh.hip.  k_bvh_trace keeps its own copy of this code (its ISA is pinned):
-// a change here must be made there too.
+// behind the widening (kTRel, the per-BVH pad) is at the head of vx_bvh.hip.  k_bvh_trace keeps its own copy of this code (on this header it
+// was measured slower): a change here must be made there too.  The constants below are the only copy.
 #pragma once
 #include "vx_internal.h"
+#include "vx_ray.h"
 
 #pragma clang fp contract(off)
 
@@ -15,21 +16,8 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr float kTRel = 1.0f / 1024.0f;   // slab interval widening, relative to |t|
 
-struct BRay {
-    float o[3], inv[3];
-    bool deg[3];
-};
-
-__device__ __forceinline__ void make_bray(float ox, float oy, float oz, float dx, float dy, float dz, BRay& R)
-{
-    R.o[0] = ox; R.o[1] = oy; R.o[2] = oz;
-    R.inv[0] = 1.0f / dx; R.inv[1] = 1.0f / dy; R.inv[2] = 1.0f / dz;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) R.deg[a] = isinf(R.inv[a]);
-}
-
 // entry t of the widened box, or false when the ray cannot have an accepted hit in it at t in [tlow, best]
-__device__ __forceinline__ bool box_enter(const float4& m0, const float4& m1, const BRay& R, float pad, float tlow, float best, float& t0)
+__device__ __forceinline__ bool box_enter(const float4& m0, const float4& m1, const SlabRay& R, float pad, float tlow, float best, float& t0)
 {
     const float lo[3] = {m0.x - pad, m0.y - pad, m0.z - pad}, hi[3] = {m1.x + pad, m1.y + pad, m1.z + pad};
     float a0 = -INFINITY, a1 = INFINITY;
@@ -48,9 +36,9 @@ __device__ __forceinline__ bool box_enter(const float4& m0, const float4& m1, co
 
 // the running closest hit of one ray: t, (u, v), triangle index, leaf-order position, instance (TLAS only)
 struct Hit {
-    float best, bu, bv;
-    uint32_t bp, bk, bi;
-    bool found;
+    float best = -1.0f, bu = 0.0f, bv = 0.0f;
+    uint32_t bp = kNone, bk = 0, bi = kNone;
+    bool found = false;
 };
 
 // tie rules on an equal t: a lower triangle index (one BVH) ...
@@ -67,7 +55,7 @@ struct TieInst {
 // the ray of one BLAS: origin, direction, its slab form, the interval
 struct Ray {
     float ox, oy, oz, dx, dy, dz;
-    BRay R;
+    SlabRay R;
     float tmin, tlow;
 };
 

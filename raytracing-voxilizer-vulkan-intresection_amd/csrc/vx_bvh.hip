@@ -32,6 +32,7 @@
 // every ray tests that list before the descent, whatever the boxes say: the brute force's answer cannot be pruned away there either.
 #include "vx_internal.h"
 #include "vx_ray.h"
+#include "vx_blas.h"
 
 #include <cstring>
 
@@ -49,29 +50,9 @@ namespace {
 
 constexpr uint32_t kBuildBlock = 256;
 constexpr uint32_t kBvhBlock = 128;       // lanes per trace workgroup; the stack is [level][lane] in LDS
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr uint32_t kLeafBit = 0x80000000u;
-constexpr float kTRel = 1.0f / 1024.0f;   // slab interval widening, relative to |t|
 constexpr double kIllSin = 1.0 / 1024.0;  // triangles thinner than this go on the side list every ray tests (see the head of the file)
 constexpr float kBoxExt = 1.0f / 1024.0f; // box widening: relative to the mesh's extent (the size of its triangles' rounding terms)...
 constexpr float kBoxPos = 1.0f / 262144.0f; // ... plus 2^-18 (~32 ulps) of its largest |coordinate| (the rounding of positions themselves)
-
-__device__ __forceinline__ uint32_t f2ord(float f)
-{
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
-
-__device__ __forceinline__ uint32_t spread10(uint32_t x)
-{
-    x &= 0x3FFu;
-    x = (x | (x << 16)) & 0x030000FFu;
-    x = (x | (x << 8)) & 0x0300F00Fu;
-    x = (x | (x << 4)) & 0x030C30C3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
-}
 
 // the triangle's three vertices; false (and zeros) when an index leaves [0, nv)
 __device__ __forceinline__ bool load_tri(const float* __restrict__ v, const int32_t* __restrict__ idx, uint64_t nv, uint32_t t, float p[9])
@@ -198,7 +179,7 @@ __global__ __launch_bounds__(kBuildBlock) void k_bvh_bounds(const float* __restr
     kbox[2ull * leaf] = make_float4(fminf(fminf(p[0], p[3]), p[6]), fminf(fminf(p[1], p[4]), p[7]), fminf(fminf(p[2], p[5]), p[8]), __uint_as_float(0u));
     kbox[2ull * leaf + 1] = make_float4(fmaxf(fmaxf(p[0], p[3]), p[6]), fmaxf(fmaxf(p[1], p[4]), p[7]), fmaxf(fmaxf(p[2], p[5]), p[8]), 0.0f);
     uint32_t node = parent[leaf];
-    while (node != kNone) {
+    while (node != blas::kNone) {
         __threadfence();                                   // release this lane's box
         if (atomicAdd(&arrived[node], 1u) == 0u) return;   // the sibling's box is not there yet: its lane carries on
         __threadfence();                                   // acquire the sibling's
@@ -219,7 +200,7 @@ __global__ __launch_bounds__(kBuildBlock) void k_bvh_alive(uint32_t n, const uin
     const uint32_t u = blockIdx.x * kBuildBlock + threadIdx.x;
     if (u >= 2 * n - 1) return;
     const uint32_t p = parent[u];
-    alive[u] = (p == kNone || range[2 * p + 1] - range[2 * p] + 1u > max_leaf) ? 1u : 0u;
+    alive[u] = (p == blas::kNone || range[2 * p + 1] - range[2 * p] + 1u > max_leaf) ? 1u : 0u;
 }
 
 // the collapsed node array: {min xyz, a, max xyz, b}; interior: a, b = the children's new indices; leaf: a = first triangle (leaf order),
@@ -234,7 +215,7 @@ __global__ __launch_bounds__(kBuildBlock) void k_bvh_emit(uint32_t n, const uint
     const uint32_t first = is_leaf ? u - (n - 1) : range[2 * u];
     const uint32_t cnt = is_leaf ? 1u : range[2 * u + 1] - range[2 * u] + 1u;
     uint32_t a, b;
-    if (is_leaf || cnt <= max_leaf) { a = first; b = kLeafBit | cnt; }
+    if (is_leaf || cnt <= max_leaf) { a = first; b = blas::kLeafBit | cnt; }
     else { a = newidx[child[2 * u]]; b = newidx[child[2 * u + 1]]; }
     const float4 m0 = kbox[2ull * u], m1 = kbox[2ull * u + 1];
     const uint32_t o = newidx[u];
@@ -288,28 +269,13 @@ struct BvhParams {
     uint32_t ntri;    // 0: every ray misses
     uint32_t levels;  // LDS stack entries per lane (>= the tree's height, >= 1)
     float pad;        // box widening (absolute)
-    const float* rays;
-    const Camera* cam;
-    uint64_t nrays;
-    float tmin, tmax;
-    const float* tmax_per_ray;
-    int any_hit;
-    float* t_out;
-    uint32_t* prim_out;
-    float* normal_out;
+    RayArgs io;
     float* bary_out;
-    uint8_t* shadowed_out;
-    vx_hit* hits;
-    unsigned long long* nhits;
 };
 
-struct BRay {
-    float o[3], inv[3];
-    bool deg[3];
-};
-
-// entry t of the widened box, or false when the ray cannot have an accepted hit in it at t in [tlow, best]
-__device__ __forceinline__ bool box_enter(const float4& m0, const float4& m1, const BRay& R, float pad, float tlow, float best, float& t0)
+// entry t of the widened box, or false when the ray cannot have an accepted hit in it at t in [tlow, best].  k_bvh_trace calls THIS one
+// (unqualified); blas::box_enter in vx_blas.h is k_tlas_trace's copy of the same text.
+__device__ __forceinline__ bool box_enter(const float4& m0, const float4& m1, const SlabRay& R, float pad, float tlow, float best, float& t0)
 {
     const float lo[3] = {m0.x - pad, m0.y - pad, m0.z - pad}, hi[3] = {m1.x + pad, m1.y + pad, m1.z + pad};
     float a0 = -INFINITY, a1 = INFINITY;
@@ -321,8 +287,8 @@ __device__ __forceinline__ bool box_enter(const float4& m0, const float4& m1, co
         a1 = R.deg[a] ? a1 : fminf(a1, fmaxf(p, q));
         inside &= !R.deg[a] || (lo[a] <= R.o[a] && R.o[a] <= hi[a]);
     }
-    t0 = a0 - kTRel * fabsf(a0);
-    const float t1 = a1 + kTRel * fabsf(a1);
+    t0 = a0 - blas::kTRel * fabsf(a0);
+    const float t1 = a1 + blas::kTRel * fabsf(a1);
     return inside && t0 <= t1 && t1 >= tlow && t0 <= best;
 }
 
@@ -330,27 +296,26 @@ __device__ __forceinline__ bool box_enter(const float4& m0, const float4& m1, co
 
 // vx_blas.h restates this descent for k_tlas_trace (box_enter, Moeller-Trumbore, the stack walk, the normal): the two copies must change
 // together (tests/test_gpu_instances.py::test_tlas_identity_matches_bvh checks them against each other bit for bit).  This kernel keeps
-// its own copy because moving it onto the template changed its code generation.
+// its own copy because on the template it was measured 1.5 to 3 % slower on every workload.  After a side-list hit with
+// any_hit this kernel still descends (`alive` stays true: root to the first leaf, no box test), while k_tlas_trace does not enter the BLAS
+// at all; the contract allows either (any_hit reports `shadowed` and an arbitrary accepted t).
 __global__ __launch_bounds__(kBvhBlock) void k_bvh_trace(BvhParams P)
 {
     extern __shared__ uint32_t bvh_lds[];  // [level][lane]: consecutive lanes on consecutive banks
     const uint32_t tid = threadIdx.x;
     const uint64_t r = (uint64_t)blockIdx.x * kBvhBlock + tid;
-    const bool active = r < P.nrays;
+    const bool active = r < P.io.nrays;
 
     float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
     float best = -1.0f, bu = 0.0f, bv = 0.0f;
-    uint32_t bp = kNone, bk = 0;
+    uint32_t bp = blas::kNone, bk = 0;
     bool found = false;
     if (active) {
-        load_ray(P.rays == nullptr, r, P.rays, P.cam, ox, oy, oz, dx, dy, dz);
-        BRay R;
-        R.o[0] = ox; R.o[1] = oy; R.o[2] = oz;
-        R.inv[0] = 1.0f / dx; R.inv[1] = 1.0f / dy; R.inv[2] = 1.0f / dz;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) R.deg[a] = isinf(R.inv[a]);
-        const float tmin = P.tmin, tlow = fmaxf(tmin, 0.0f);
-        best = P.tmax_per_ray ? P.tmax_per_ray[r] : P.tmax;  // acceptance bound until the first hit
+        load_ray(P.io.rays == nullptr, r, P.io.rays, P.io.cam, ox, oy, oz, dx, dy, dz);
+        SlabRay R;
+        make_slab_ray(ox, oy, oz, dx, dy, dz, R);
+        const float tmin = P.io.tmin, tlow = fmaxf(tmin, 0.0f);
+        best = P.io.tmax_per_ray ? P.io.tmax_per_ray[r] : P.io.tmax;  // acceptance bound until the first hit
         const float pad = P.pad;
 
         // Moeller-Trumbore exactly as include/voxhip.h pins it, and the closest-hit / tie rule
@@ -375,7 +340,7 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_trace(BvhParams P)
         };
         bool alive = P.ntri != 0;
         for (uint32_t i = 0; i < P.nill && alive; ++i) test_tri(P.ill[i]);
-        if (alive && !(found && P.any_hit)) {
+        if (alive && !(found && P.io.any_hit)) {
             float t0;
             alive = box_enter(P.nodes[0], P.nodes[1], R, pad, tlow, best, t0);
         }
@@ -383,10 +348,10 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_trace(BvhParams P)
         while (alive) {
             const float4 n0 = P.nodes[2ull * cur], n1 = P.nodes[2ull * cur + 1];
             const uint32_t na = __float_as_uint(n0.w), nb = __float_as_uint(n1.w);
-            if (nb & kLeafBit) {
-                const uint32_t end = na + (nb & ~kLeafBit);
+            if (nb & blas::kLeafBit) {
+                const uint32_t end = na + (nb & ~blas::kLeafBit);
                 for (uint32_t k = na; k < end; ++k) test_tri(k);
-                if (found && P.any_hit) break;  // gl_RayFlagsTerminateOnFirstHitEXT (raytrace.rchit:113)
+                if (found && P.io.any_hit) break;  // gl_RayFlagsTerminateOnFirstHitEXT (raytrace.rchit:113)
             } else {
                 const float4 l0 = P.nodes[2ull * na], l1 = P.nodes[2ull * na + 1];
                 const float4 r0 = P.nodes[2ull * nb], r1 = P.nodes[2ull * nb + 1];
@@ -419,13 +384,13 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_trace(BvhParams P)
         }
     }
     const float tt = found ? best : -1.0f;
-    const uint32_t prim = found ? bp : kNone;
+    const uint32_t prim = found ? bp : blas::kNone;
     if (active) {
-        if (P.t_out) P.t_out[r] = tt;
-        if (P.prim_out) P.prim_out[r] = prim;
-        if (P.shadowed_out) P.shadowed_out[r] = found ? 1 : 0;
+        if (P.io.t_out) P.io.t_out[r] = tt;
+        if (P.io.prim_out) P.io.prim_out[r] = prim;
+        if (P.io.shadowed_out) P.io.shadowed_out[r] = found ? 1 : 0;
         if (P.bary_out) { P.bary_out[2 * r] = found ? bu : 0.0f; P.bary_out[2 * r + 1] = found ? bv : 0.0f; }
-        if (P.normal_out) {
+        if (P.io.normal_out) {
             float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
             if (found) {  // the geometric normal cross(e1, e2) / |.| of prim, not flipped
                 const float4 A = P.tris[3ull * bk], B = P.tris[3ull * bk + 1], Cc = P.tris[3ull * bk + 2];
@@ -435,10 +400,10 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_trace(BvhParams P)
                 const float il = 1.0f / sqrtf((cx * cx + cy * cy) + cz * cz);
                 n0 = cx * il; n1 = cy * il; n2 = cz * il;
             }
-            P.normal_out[3 * r] = n0; P.normal_out[3 * r + 1] = n1; P.normal_out[3 * r + 2] = n2;
+            P.io.normal_out[3 * r] = n0; P.io.normal_out[3 * r + 1] = n1; P.io.normal_out[3 * r + 2] = n2;
         }
     }
-    if (P.hits) compact_hit(found, r, prim, tt, P.hits, P.nhits);  // every lane of the workgroup gets here
+    if (P.io.hits) compact_hit(found, r, prim, tt, P.io.hits, P.io.nhits);  // every lane of the workgroup gets here
 }
 
 void launch_bvh_trace(const float* nodes, const float* tris, const uint32_t* ill, uint32_t nill, uint32_t ntri, uint32_t height, float extent,
@@ -453,22 +418,9 @@ void launch_bvh_trace(const float* nodes, const float* tris, const uint32_t* ill
     P.ill = ill;
     P.nill = nodes ? nill : 0;
     P.levels = height ? height : 1u;
-    P.pad = kBoxExt * extent + kBoxPos * coord_max + 1e-30f;
-    P.rays = io.rays;
-    P.cam = io.cam_dev;
-    P.nrays = io.nrays;
-    P.tmin = io.tmin;
-    P.tmax = io.tmax;
-    P.tmax_per_ray = io.tmax_per_ray;
-    P.any_hit = io.any_hit ? 1 : 0;
-    P.t_out = io.t_out;
-    P.prim_out = io.prim_out;
-    P.normal_out = io.normal_out;
+    P.pad = bvh_pad(extent, coord_max);
+    set_ray_args(P.io, io, s);
     P.bary_out = bary_out;
-    P.shadowed_out = io.shadowed_out;
-    P.hits = io.hits;
-    P.nhits = io.nhits;
-    if (io.hits && io.nhits) (void)hipMemsetAsync(io.nhits, 0, sizeof(unsigned long long), s);
     const size_t shmem = (size_t)P.levels * kBvhBlock * 4u;
     const uint64_t nblk = (io.nrays + kBvhBlock - 1) / kBvhBlock;
     VX_KL(k_bvh_trace, dim3((unsigned)nblk), dim3(kBvhBlock), shmem, s, P);

@@ -231,4 +231,25 @@ VX_HD void range_unpack(uint32_t xr, uint32_t yr, uint32_t zr, uint32_t e, uint3
     zs = (zr & 0xFFFFu) | (((e >> 22) & 31u) << 16);
 }
 
+#if defined(__HIPCC__)
+// float <-> uint32 whose unsigned order is the float order: what the BVH / TLAS builders' atomicMin / atomicMax bounds run on
+__device__ __forceinline__ uint32_t f2ord(float f)
+{
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
+
+// the low 10 bits of x on every third bit: one axis of the builders' 30-bit Morton codes
+__device__ __forceinline__ uint32_t spread10(uint32_t x)
+{
+    x &= 0x3FFu;
+    x = (x | (x << 16)) & 0x030000FFu;
+    x = (x | (x << 8)) & 0x0300F00Fu;
+    x = (x | (x << 4)) & 0x030C30C3u;
+    x = (x | (x << 2)) & 0x09249249u;
+    return x;
+}
+#endif
+
 }  // namespace vx

@@ -47,11 +47,6 @@ namespace {
 
 constexpr uint32_t kOctBlock = 256;  // lanes per workgroup (4 waves); the stack is [level][lane] in LDS
 
-struct OctRay {
-    float o[3], inv[3];
-    bool deg[3];  // 1/d is infinite on this axis
-};
-
 // corner cell of the node whose Morton prefix is `path` at depth `depth`
 __device__ __forceinline__ void node_corner(uint64_t path, uint32_t depth, uint32_t bits, uint32_t c[3])
 {
@@ -62,7 +57,7 @@ __device__ __forceinline__ void node_corner(uint64_t path, uint32_t depth, uint3
 }
 
 // Entry / exit of the box of `n` cells per axis from corner c (see the head of the file): false when the ray misses it
-__device__ __forceinline__ bool node_enter(const GridParams& g, const OctRay& R, const uint32_t c[3], uint32_t n, float& t0, float& t1)
+__device__ __forceinline__ bool node_enter(const GridParams& g, const SlabRay& R, const uint32_t c[3], uint32_t n, float& t0, float& t1)
 {
     float mn[3], mx[3];
     bool inside = true;
@@ -90,18 +85,7 @@ struct OctParams {
     GridParams g;     // org = root_min, vs, half (dims unused)
     uint32_t bits;
     uint32_t levels;  // LDS stack entries per lane (>= bits, >= 1)
-    const float* rays;
-    const Camera* cam;
-    uint64_t nrays;
-    float tmin, tmax;
-    const float* tmax_per_ray;
-    int any_hit;
-    float* t_out;
-    uint32_t* prim_out;
-    float* normal_out;
-    uint8_t* shadowed_out;
-    vx_hit* hits;
-    unsigned long long* nhits;
+    RayArgs io;
 };
 
 }  // namespace
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(kOctBlock) void k_octree_trace(OctParams P)
     uint32_t* stk_mask = oct_lds + P.levels * kOctBlock;
     const uint32_t tid = threadIdx.x;
     const uint64_t r = (uint64_t)blockIdx.x * kOctBlock + tid;
-    const bool active = r < P.nrays;
+    const bool active = r < P.io.nrays;
     const GridParams g = P.g;
     const uint32_t bits = P.bits;
 
@@ -122,15 +106,12 @@ __global__ __launch_bounds__(kOctBlock) void k_octree_trace(OctParams P)
     uint32_t bp = 0xFFFFFFFFu;
     bool found = false;
     if (active) {
-        load_ray(P.rays == nullptr, r, P.rays, P.cam, ox, oy, oz, dx, dy, dz);
-        OctRay R;
-        R.o[0] = ox; R.o[1] = oy; R.o[2] = oz;
-        R.inv[0] = 1.0f / dx; R.inv[1] = 1.0f / dy; R.inv[2] = 1.0f / dz;  // rint:48
-#pragma unroll
-        for (int a = 0; a < 3; ++a) R.deg[a] = isinf(R.inv[a]);
+        load_ray(P.io.rays == nullptr, r, P.io.rays, P.io.cam, ox, oy, oz, dx, dy, dz);
+        SlabRay R;
+        make_slab_ray(ox, oy, oz, dx, dy, dz, R);
         const uint32_t dirmask = (signbit(dx) ? 1u : 0u) | (signbit(dy) ? 2u : 0u) | (signbit(dz) ? 4u : 0u);
-        const float tmin = P.tmin;
-        best = P.tmax_per_ray ? P.tmax_per_ray[r] : P.tmax;  // acceptance bound until the first hit (rint:69 + rgen:50-51)
+        const float tmin = P.io.tmin;
+        best = P.io.tmax_per_ray ? P.io.tmax_per_ray[r] : P.io.tmax;  // acceptance bound until the first hit (rint:69 + rgen:50-51)
 
         bool alive = P.nitems != 0;
         if (alive) {
@@ -158,7 +139,7 @@ __global__ __launch_bounds__(kOctBlock) void k_octree_trace(OctParams P)
                     const float t = hit_aabb(bb, R.o, R.inv);
                     if (t > 0.0f && t >= tmin && (found ? (t < best || (t == best && j < bp)) : t <= best)) { best = t; bp = j; found = true; }  // rint:69
                 }
-                if (found && P.any_hit) break;  // gl_RayFlagsTerminateOnFirstHitEXT (raytrace2.rchit:108)
+                if (found && P.io.any_hit) break;  // gl_RayFlagsTerminateOnFirstHitEXT (raytrace2.rchit:108)
             } else {
                 // interior: the children the ray enters, front to back, as bits of the level's mask.  Per axis the children's bounds are four
                 // planes -- the node's own min and max and the two middle ones, cell_aabb of the last lower and the first upper cell -- the
@@ -226,20 +207,20 @@ __global__ __launch_bounds__(kOctBlock) void k_octree_trace(OctParams P)
     const float tt = found ? best : -1.0f;
     const uint32_t prim = found ? bp : 0xFFFFFFFFu;
     if (active) {
-        if (P.t_out) P.t_out[r] = tt;
-        if (P.prim_out) P.prim_out[r] = prim;
-        if (P.shadowed_out) P.shadowed_out[r] = found ? 1 : 0;
-        if (P.normal_out) {
+        if (P.io.t_out) P.io.t_out[r] = tt;
+        if (P.io.prim_out) P.io.prim_out[r] = prim;
+        if (P.io.shadowed_out) P.io.shadowed_out[r] = found ? 1 : 0;
+        if (P.io.normal_out) {
             float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
             if (found) {
                 float bb[6];
                 item_aabb(g, P.items[bp], bb);
                 cube_normal(bb, ox, oy, oz, dx, dy, dz, tt, n0, n1, n2);
             }
-            P.normal_out[3 * r] = n0; P.normal_out[3 * r + 1] = n1; P.normal_out[3 * r + 2] = n2;
+            P.io.normal_out[3 * r] = n0; P.io.normal_out[3 * r + 1] = n1; P.io.normal_out[3 * r + 2] = n2;
         }
     }
-    if (P.hits) compact_hit(found, r, prim, tt, P.hits, P.nhits);  // every lane of the workgroup gets here
+    if (P.io.hits) compact_hit(found, r, prim, tt, P.io.hits, P.io.nhits);  // every lane of the workgroup gets here
 }
 
 void launch_octree_trace(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,
@@ -256,20 +237,7 @@ void launch_octree_trace(const vx_octree_node* nodes, const uint64_t* items, uin
     P.g.half = vs * 0.5f;  // == k_emit_morton_aabbs
     P.bits = bits;
     P.levels = bits ? bits : 1u;
-    P.rays = io.rays;
-    P.cam = io.cam_dev;
-    P.nrays = io.nrays;
-    P.tmin = io.tmin;
-    P.tmax = io.tmax;
-    P.tmax_per_ray = io.tmax_per_ray;
-    P.any_hit = io.any_hit ? 1 : 0;
-    P.t_out = io.t_out;
-    P.prim_out = io.prim_out;
-    P.normal_out = io.normal_out;
-    P.shadowed_out = io.shadowed_out;
-    P.hits = io.hits;
-    P.nhits = io.nhits;
-    if (io.hits && io.nhits) (void)hipMemsetAsync(io.nhits, 0, sizeof(unsigned long long), s);
+    set_ray_args(P.io, io, s);
     const size_t shmem = (size_t)P.levels * kOctBlock * 8u;
     const uint64_t nblk = (io.nrays + kOctBlock - 1) / kOctBlock;
     VX_KL(k_octree_trace, dim3((unsigned)nblk), dim3(kOctBlock), shmem, s, P);

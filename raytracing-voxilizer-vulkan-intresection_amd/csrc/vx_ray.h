@@ -1,11 +1,63 @@
-// vx_ray.h -- device pieces every ray kernel shares: the ray of a batch (buffer or camera model), the closest-hit stage's cube-face
-// normal, and the wavefront compaction of the hit list.  Used by k_walk / k_rank (Bool grid) and k_octree_trace (octree).
+// vx_ray.h -- pieces every ray kernel shares: the ray of a batch (buffer or camera model), the closest-hit stage's cube-face normal and
+// the wavefront compaction of the hit list (k_walk / k_rank, k_octree_trace, k_bvh_trace, k_tlas_trace); and, for the last three, the
+// ray-batch block of their kernel arguments and the slab form of a ray.  Their epilogues (t / prim / shadowed / own outputs / hit list)
+// stay in the kernels: a shared one changed the order of k_tlas_trace's stores and with it its register allocation.
 #pragma once
 #include "vx_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace vx {
+
+// The ray batch of k_octree_trace / k_bvh_trace / k_tlas_trace as a block of their kernel arguments: TraceIO's fields, the camera in
+// device memory.
+struct RayArgs {
+    const float* rays;
+    const Camera* cam;
+    uint64_t nrays;
+    float tmin, tmax;
+    const float* tmax_per_ray;
+    int any_hit;
+    float* t_out;
+    uint32_t* prim_out;
+    float* normal_out;
+    uint8_t* shadowed_out;
+    vx_hit* hits;
+    unsigned long long* nhits;
+};
+
+// fills the block from io and queues the clear of the hit counter on `s`
+inline void set_ray_args(RayArgs& a, const TraceIO& io, hipStream_t s)
+{
+    a.rays = io.rays;
+    a.cam = io.cam_dev;
+    a.nrays = io.nrays;
+    a.tmin = io.tmin;
+    a.tmax = io.tmax;
+    a.tmax_per_ray = io.tmax_per_ray;
+    a.any_hit = io.any_hit ? 1 : 0;
+    a.t_out = io.t_out;
+    a.prim_out = io.prim_out;
+    a.normal_out = io.normal_out;
+    a.shadowed_out = io.shadowed_out;
+    a.hits = io.hits;
+    a.nhits = io.nhits;
+    if (io.hits && io.nhits) (void)hipMemsetAsync(io.nhits, 0, sizeof(unsigned long long), s);
+}
+
+// A ray as the slab tests read it: origin, 1/d (raytrace.rint:48), and the axes on which 1/d is infinite (d = +-0 or denormal)
+struct SlabRay {
+    float o[3], inv[3];
+    bool deg[3];
+};
+
+__device__ __forceinline__ void make_slab_ray(float ox, float oy, float oz, float dx, float dy, float dz, SlabRay& R)
+{
+    R.o[0] = ox; R.o[1] = oy; R.o[2] = oz;
+    R.inv[0] = 1.0f / dx; R.inv[1] = 1.0f / dy; R.inv[2] = 1.0f / dz;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) R.deg[a] = isinf(R.inv[a]);
+}
 
 // Ray r of the batch: from the ray buffer, or generated from the reference camera model (raytrace.rgen:41-47; mat*vec in glm's
 // association (m0*v0 + m1*v1) + (m2*v2 + m3*v3)).

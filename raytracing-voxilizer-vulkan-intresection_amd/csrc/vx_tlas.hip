@@ -51,23 +51,6 @@ constexpr float kCorner = 1.0f / 262144.0f;  // the rounding of the transformed 
 constexpr float kExt = 1.0f / 1024.0f;       // relative to the instance's world extent
 constexpr float kRayPad = 1.0f / 32768.0f;   // per ray: cond_max |o|
 
-__device__ __forceinline__ uint32_t f2ord(float f)
-{
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
-
-__device__ __forceinline__ uint32_t spread10(uint32_t x)
-{
-    x &= 0x3FFu;
-    x = (x | (x << 16)) & 0x030000FFu;
-    x = (x | (x << 8)) & 0x0300F00Fu;
-    x = (x | (x << 4)) & 0x030C30C3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
-}
-
 __device__ __forceinline__ float fabs_max3(float a, float b, float c) { return fmaxf(fmaxf(fabsf(a), fabsf(b)), fabsf(c)); }
 
 // row r of a 3x4 matrix applied to a point, in the pinned association ((m0*x + m1*y) + m2*z) + m3
@@ -235,24 +218,13 @@ struct TlasParams {
     const uint32_t* small;   // [6] = the largest condition number (ordered uint)
     uint32_t ninst;          // 0: every ray misses
     uint32_t levels;         // LDS stack entries per lane (>= TLAS height bound + the largest BLAS height, >= 1)
-    const float* rays;
-    const Camera* cam;
-    uint64_t nrays;
-    float tmin, tmax;
-    const float* tmax_per_ray;
-    int any_hit;
-    float* t_out;
-    uint32_t* prim_out;
-    float* normal_out;
+    RayArgs io;
     float* bary_out;
     uint32_t* inst_out;
-    uint8_t* shadowed_out;
-    vx_hit* hits;
-    unsigned long long* nhits;
 };
 
 // a TLAS box: empty boxes (inactive instances, subtrees of them) are never entered
-__device__ __forceinline__ bool tlas_enter(const float4& m0, const float4& m1, const blas::BRay& R, float pad, float tlow, float best, float& t0)
+__device__ __forceinline__ bool tlas_enter(const float4& m0, const float4& m1, const SlabRay& R, float pad, float tlow, float best, float& t0)
 {
     return m0.x <= m1.x && m0.y <= m1.y && m0.z <= m1.z && blas::box_enter(m0, m1, R, pad, tlow, best, t0);
 }
@@ -264,19 +236,16 @@ __global__ __launch_bounds__(kTlasBlock) void k_tlas_trace(TlasParams P)
     extern __shared__ uint32_t tlas_lds[];  // [level][lane]: the TLAS's entries below, the current BLAS's above them
     const uint32_t tid = threadIdx.x;
     const uint64_t r = (uint64_t)blockIdx.x * kTlasBlock + tid;
-    const bool active = r < P.nrays;
+    const bool active = r < P.io.nrays;
 
     blas::Hit h;
-    h.best = -1.0f; h.bu = 0.0f; h.bv = 0.0f;
-    h.bp = blas::kNone; h.bk = 0; h.bi = blas::kNone;
-    h.found = false;
     if (active) {
         float ox, oy, oz, dx, dy, dz;
-        load_ray(P.rays == nullptr, r, P.rays, P.cam, ox, oy, oz, dx, dy, dz);
-        blas::BRay Rw;
-        blas::make_bray(ox, oy, oz, dx, dy, dz, Rw);
-        const float tmin = P.tmin, tlow = fmaxf(tmin, 0.0f);
-        h.best = P.tmax_per_ray ? P.tmax_per_ray[r] : P.tmax;  // acceptance bound until the first hit
+        load_ray(P.io.rays == nullptr, r, P.io.rays, P.io.cam, ox, oy, oz, dx, dy, dz);
+        SlabRay Rw;
+        make_slab_ray(ox, oy, oz, dx, dy, dz, Rw);
+        const float tmin = P.io.tmin, tlow = fmaxf(tmin, 0.0f);
+        h.best = P.io.tmax_per_ray ? P.io.tmax_per_ray[r] : P.io.tmax;  // acceptance bound until the first hit
         const float rpad = kRayPad * ord2f(P.small[6]) * fabs_max3(ox, oy, oz);
         bool alive = P.ninst != 0;
         if (alive) {
@@ -299,21 +268,23 @@ __global__ __launch_bounds__(kTlasBlock) void k_tlas_trace(TlasParams P)
                     y.dx = (W0.x * dx + W0.y * dy) + W0.z * dz;
                     y.dy = (W1.x * dx + W1.y * dy) + W1.z * dz;
                     y.dz = (W2.x * dx + W2.y * dy) + W2.z * dz;
-                    blas::make_bray(y.ox, y.oy, y.oz, y.dx, y.dy, y.dz, y.R);
+                    make_slab_ray(y.ox, y.oy, y.oz, y.dx, y.dy, y.dz, y.R);
                     y.tmin = tmin;
                     y.tlow = tlow;
                     const TlasBlas& D = P.tab[b];
                     const float4* bn = reinterpret_cast<const float4*>(D.nodes);
                     const float4* bt = reinterpret_cast<const float4*>(D.tris);
                     for (uint32_t k = 0; k < D.nill; ++k) blas::test_tri<blas::TieInst>(bt, D.ill[k], y, na, h);
-                    bool enter = !(h.found && P.any_hit);
+                    // After a side-list hit with any_hit the BLAS is not entered, while k_bvh_trace still walks from its root to the first
+                    // leaf.  The contract allows either (any_hit reports `shadowed` and an arbitrary accepted t).
+                    bool enter = !(h.found && P.io.any_hit);
                     if (enter) {
                         float t0;
                         enter = blas::box_enter(bn[0], bn[1], y.R, D.pad, tlow, h.best, t0);
                     }
-                    blas::descend<blas::TieInst, kTlasBlock>(bn, bt, y, D.pad, P.any_hit, tlas_lds, tid, sp, na, h, enter);
+                    blas::descend<blas::TieInst, kTlasBlock>(bn, bt, y, D.pad, P.io.any_hit, tlas_lds, tid, sp, na, h, enter);
                 }
-                if (h.found && P.any_hit) break;
+                if (h.found && P.io.any_hit) break;
             } else {
                 const float4 l0 = P.nodes[2ull * na], l1 = P.nodes[2ull * na + 1];
                 const float4 r0 = P.nodes[2ull * nb], r1 = P.nodes[2ull * nb + 1];
@@ -348,18 +319,18 @@ __global__ __launch_bounds__(kTlasBlock) void k_tlas_trace(TlasParams P)
     const float tt = found ? h.best : -1.0f;
     const uint32_t prim = found ? h.bp : blas::kNone;
     if (active) {
-        if (P.t_out) P.t_out[r] = tt;
-        if (P.prim_out) P.prim_out[r] = prim;
+        if (P.io.t_out) P.io.t_out[r] = tt;
+        if (P.io.prim_out) P.io.prim_out[r] = prim;
         if (P.inst_out) P.inst_out[r] = found ? h.bi : blas::kNone;
-        if (P.shadowed_out) P.shadowed_out[r] = found ? 1 : 0;
+        if (P.io.shadowed_out) P.io.shadowed_out[r] = found ? 1 : 0;
         if (P.bary_out) { P.bary_out[2 * r] = found ? h.bu : 0.0f; P.bary_out[2 * r + 1] = found ? h.bv : 0.0f; }
-        if (P.normal_out) {
+        if (P.io.normal_out) {
             float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
             if (found) tlas_world_normal(P.tab, P.iblas, reinterpret_cast<const float*>(P.xf), h.bi, h.bk, n0, n1, n2);
-            P.normal_out[3 * r] = n0; P.normal_out[3 * r + 1] = n1; P.normal_out[3 * r + 2] = n2;
+            P.io.normal_out[3 * r] = n0; P.io.normal_out[3 * r + 1] = n1; P.io.normal_out[3 * r + 2] = n2;
         }
     }
-    if (P.hits) compact_hit(found, r, prim, tt, P.hits, P.nhits);  // every lane of the workgroup gets here
+    if (P.io.hits) compact_hit(found, r, prim, tt, P.io.hits, P.io.nhits);  // every lane of the workgroup gets here
 }
 
 uint32_t tlas_height_bound(uint64_t n)
@@ -384,22 +355,9 @@ void launch_tlas_trace(const TlasDev& T, const TraceIO& io, float* bary_out, uin
     P.small = T.small;
     P.ninst = T.ninst;
     P.levels = T.levels ? T.levels : 1u;
-    P.rays = io.rays;
-    P.cam = io.cam_dev;
-    P.nrays = io.nrays;
-    P.tmin = io.tmin;
-    P.tmax = io.tmax;
-    P.tmax_per_ray = io.tmax_per_ray;
-    P.any_hit = io.any_hit ? 1 : 0;
-    P.t_out = io.t_out;
-    P.prim_out = io.prim_out;
-    P.normal_out = io.normal_out;
+    set_ray_args(P.io, io, s);
     P.bary_out = bary_out;
     P.inst_out = inst_out;
-    P.shadowed_out = io.shadowed_out;
-    P.hits = io.hits;
-    P.nhits = io.nhits;
-    if (io.hits && io.nhits) (void)hipMemsetAsync(io.nhits, 0, sizeof(unsigned long long), s);
     const size_t shmem = (size_t)P.levels * kTlasBlock * 4u;
     const uint64_t nblk = (io.nrays + kTlasBlock - 1) / kTlasBlock;
     VX_KL(k_tlas_trace, dim3((unsigned)nblk), dim3(kTlasBlock), shmem, s, P);
