@@ -419,6 +419,34 @@ typedef struct vx_trace_args {
 vx_status vx_trace_ex_device(const vx_grid* g, const vx_trace_args* args);
 vx_status vx_trace_ex(const vx_grid* g, const vx_trace_args* args);
 
+/* Multi-hit query: ALL the voxels a ray meets, in order -- X-ray and thickness images, depth peeling, counting wall crossings.
+ * For ray r let A(r) be the set of occupied cells c whose t_c = hitAabb(box_c) is accepted by the rule above (t_c > 0 and
+ * tmin <= t_c <= tmax, or tmax_per_ray[r] in place of tmax); box_c is the box vx_grid_aabbs emits for the cell and prim_c its index in
+ * the Bool grid's list order.  A(r) is ordered by (t, prim) ascending: t compared as float, ties broken by the smaller prim.  With the
+ * optional per-ray cursor (after_t[r], after_prim[r]) only the hits STRICTLY after the cursor in that order belong to A(r), for the
+ * counts and the lists alike; a cursor of (-1, anything) is the same as no cursor.  Outputs per ray, K = max_hits:
+ *   t[r*K + j], prim[r*K + j]   the j-th element of A(r) for j < min(K, |A(r)|); the remaining slots are -1.0f and 0xFFFFFFFF;
+ *   count[r]                    |A(r)|, the full count even when it exceeds K.
+ * Every output is bit-equal to the brute force over all occupied boxes; without a cursor slot 0 is what vx_trace_ex returns for t and
+ * prim.  Lists longer than K are paged: call again with the cursor at the last hit of the previous page.
+ * Checks, in this order, each writing nothing: NULL grid or args, K outside 1..VX_MULTIHIT_MAX, exactly one of the two cursor arrays,
+ * any forbidden field of `base` set: VX_ERR_INVALID_ARG.  Zero rays: VX_OK.  A grid without occupied cells: every count 0, every slot
+ * padded.  The traversal structure is built on demand as for vx_trace_ex; a list emission left pending by VX_VOXELIZE_LIST_ASYNC stays
+ * pending; a repeated device call at the same ray count requests no device memory (vx_device_allocations unchanged). */
+#define VX_MULTIHIT_MAX 32
+typedef struct vx_multihit_args {
+    vx_trace_args base;        /* rays / camera / num_rays / tmin / tmax / tmax_per_ray as for vx_trace_ex;
+                                  base.t and base.prim hold max_hits entries PER RAY (ray-major), both optional;
+                                  any_hit, normal, shadowed, hits, num_hits must be 0 / NULL -> else VX_ERR_INVALID_ARG */
+    uint32_t max_hits;         /* K, 1..VX_MULTIHIT_MAX (32) */
+    uint32_t reserved;
+    uint32_t* count;           /* |A(r)|, the full count even when it exceeds K; optional */
+    const float* after_t;      /* cursor, optional; both or neither */
+    const uint32_t* after_prim;
+} vx_multihit_args;
+vx_status vx_trace_multi_device(const vx_grid* g, const vx_multihit_args* a);  /* device pointers, asynchronous on the grid's stream */
+vx_status vx_trace_multi(const vx_grid* g, const vx_multihit_args* a);         /* host pointers, staged like vx_trace_ex */
+
 /* ---- rays on the octree: the reference's second BLAS input (Octree{path, vs} -> getAabbs, hello_vulkan.cpp:690-697) under the
  * same raytrace.rint.  The contract of the grid trace above, applied to the list vx_octree_aabbs() returns (ascending Morton code,
  * duplicates included, octTree.hpp:502-510):

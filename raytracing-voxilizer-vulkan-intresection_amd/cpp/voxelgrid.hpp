@@ -229,6 +229,22 @@ public:
         return ret;
     }
 
+    // Multi-hit ray query (vx_trace_multi): for each ray (6 floats: origin, direction) the first maxHits (1..32) voxels it meets, ordered by
+    // (t, index in getAabbs() order of the Bool grid), into t / prim (maxHits entries per ray, padded with -1 / 0xFFFFFFFF), and the number of
+    // all voxels it meets within [tmin, tmax] into count.
+    void traceMulti(const std::vector<float>& rays, uint32_t maxHits, float tmin, float tmax, std::vector<float>& t, std::vector<uint32_t>& prim,
+                    std::vector<uint32_t>& count) const
+    {
+        const size_t n = rays.size() / 6;
+        t.assign(n * maxHits, -1.0f);
+        prim.assign(n * maxHits, 0xFFFFFFFFu);
+        count.assign(n, 0u);
+        vx_multihit_args a{};
+        a.base.rays = rays.data(); a.base.num_rays = n; a.base.tmin = tmin; a.base.tmax = tmax;
+        a.base.t = t.data(); a.base.prim = prim.data(); a.max_hits = maxHits; a.count = count.data();
+        vxdetail::check(vx_trace_multi(m_grid.get(), &a));
+    }
+
     // Abstract methods (voxelgrid.hpp:124-127)
     virtual std::vector<Aabb> getAabbs() const noexcept = 0;
     virtual void setVoxel(size_t x, size_t y, size_t z, const MaterialObj& material = MaterialObj{}) = 0;

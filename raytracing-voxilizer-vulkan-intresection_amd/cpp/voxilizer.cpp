@@ -46,6 +46,8 @@
 //                                       --materials also FILE.mtl (one `newmtl m<id>` per grid material) and a `usemtl m<id>` before each run
 //                                       of equal ids.  bool / aabbstruct / vec, with or without --solid; not with --grid octree, --gpus N > 1,
 //                                       --bench, or --materials with --grid vec
+//   --xray FILE.pgm [--size WxH]        how many voxels each camera ray of --render meets (vx_trace_multi's count), as a binary 16-bit PGM
+//                                       (big-endian, min(count, 65535) per pixel); --camera-dump FILE as for --render
 //   --components FILE.csv [--connectivity 6|26]
 //                                       the connected components of the grid's occupied cells (vx_grid_component_stats; 6: shared faces, the
 //                                       default; 26: faces, edges and corners) as CSV: a header line, then label,cells,minx,miny,minz,maxx,
@@ -372,11 +374,45 @@ void write_surface(const T& vox, const std::string& file, bool materials)
     std::printf("[voxhip] surface: %zu vertices, %zu triangles\n", xyz.size() / 3, tris.size() / 3);
 }
 
+// --xray: the hit count of every primary ray of the reference camera as a 16-bit PGM
+void write_xray(const vx_grid* grid, const std::string& file, uint32_t W, uint32_t H, const std::string& cameraDump)
+{
+    float vi[16], pi[16];
+    camera(vi, pi, (float)W / (float)H);
+    if (!cameraDump.empty()) {
+        std::ofstream cf(cameraDump, std::ios::binary);
+        cf.write(reinterpret_cast<const char*>(vi), 64);
+        cf.write(reinterpret_cast<const char*>(pi), 64);
+    }
+    const size_t n = (size_t)W * H;
+    std::vector<uint32_t> count(n);
+    vx_multihit_args a{};
+    a.base.view_inverse = vi; a.base.proj_inverse = pi; a.base.width = W; a.base.height = H; a.base.tmin = 0.001f; a.base.tmax = 10000.0f;  // rgen:50-51
+    a.max_hits = 1;
+    a.count = count.data();
+    vxdetail::check(vx_trace_multi(grid, &a));
+    std::vector<unsigned char> px(2 * n);
+    uint32_t most = 0;
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t c = count[i] < 65535u ? count[i] : 65535u;
+        px[2 * i] = (unsigned char)(c >> 8);  // PGM samples above 255 are two bytes, most significant first
+        px[2 * i + 1] = (unsigned char)(c & 255u);
+        most = std::max(most, count[i]);
+        sum += count[i];
+    }
+    std::ofstream f(file, std::ios::binary);
+    f << "P5\n" << W << ' ' << H << "\n65535\n";
+    f.write(reinterpret_cast<const char*>(px.data()), (std::streamsize)px.size());
+    if (!f) throw std::runtime_error("cannot write " + file);
+    std::printf("[voxhip] xray %ux%u: %llu voxel crossings, at most %u on a ray\n", W, H, (unsigned long long)sum, most);
+}
+
 template <class T, bool P>
 int run_grid(const std::string& path, float vs, const std::string& dumpFile, const char* label, const std::string& renderFile = "",
              uint32_t rw = 1280, uint32_t rh = 720, bool materials = false, const std::string& matDump = "", const std::string& cameraDump = "",
              const std::vector<int>& devices = {}, const MeshScene* mesh = nullptr, long frames = 0, bool solid = false, const std::string& sdfFile = "",
-             const std::string& surfaceFile = "", const std::string& componentsFile = "", int connectivity = 6)
+             const std::string& surfaceFile = "", const std::string& componentsFile = "", int connectivity = 6, const std::string& xrayFile = "")
 {
     VoxelBuilder<T, P> voxelBuilder{std::filesystem::path(path)};
     voxelBuilder.withMaterials(materials);
@@ -424,6 +460,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
         if (!f) throw std::runtime_error("cannot write " + componentsFile);
         std::printf("[voxhip] components: %zu\n", cs.size());
     }
+    if (!xrayFile.empty()) write_xray(vox.handle(), xrayFile, rw, rh, cameraDump);
     RenderOpts ro;
     ro.cameraDump = cameraDump;
     ro.mesh = mesh;
@@ -446,14 +483,14 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]]\n",
                      argv[0]);
         return 2;
     }
     const std::string path = argv[1];
     float vs = 0.f;
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
-    std::string grid = "bool", sdfFile, surfaceFile, componentsFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
+    std::string grid = "bool", sdfFile, surfaceFile, componentsFile, xrayFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false, attributes = false, solid = false;
     int gpus = 1, connectivity = 6;
@@ -476,6 +513,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--sdf") && i + 1 < argc) sdfFile = argv[++i];
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
         else if (!std::strcmp(argv[i], "--components") && i + 1 < argc) componentsFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--xray") && i + 1 < argc) xrayFile = argv[++i];
         else if (!std::strcmp(argv[i], "--connectivity") && i + 1 < argc) connectivity = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
@@ -512,6 +550,10 @@ int main(int argc, char** argv)
     }
     if (!componentsFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
         std::fprintf(stderr, "--components labels the occupied cells of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (!xrayFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
+        std::fprintf(stderr, "--xray counts the voxels of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
         return 2;
     }
     if (connectivity != 6 && connectivity != 26) { std::fprintf(stderr, "--connectivity must be 6 or 26\n"); return 2; }
@@ -599,12 +641,12 @@ int main(int argc, char** argv)
             return 0;
         }
         const bool surfMat = materials && !surfaceFile.empty();  // (--materials reaches an aabbstruct grid only for its surface's ids)
-        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile, componentsFile, connectivity)
-                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile, componentsFile, connectivity);
-        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, surfMat, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity)
-                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", 1280, 720, surfMat, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity);
-        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity)
-                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", 1280, 720, false, "", "", {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity);
+        if (grid == "bool") return parallel ? run_grid<VoxelGridBool, true>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile, componentsFile, connectivity, xrayFile)
+                                               : run_grid<VoxelGridBool, false>(path, vs, dumpFile, "VoxelGridBool", renderFile, rw, rh, materials, matDump, cameraDump, devices, msp, frames, solid, sdfFile, surfaceFile, componentsFile, connectivity, xrayFile);
+        if (grid == "aabbstruct") return parallel ? run_grid<VoxelGridAABBstruct, true>(path, vs, dumpFile, "VoxelGridAABBstruct", "", rw, rh, surfMat, "", cameraDump, {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity, xrayFile)
+                                                  : run_grid<VoxelGridAABBstruct, false>(path, vs, dumpFile, "VoxelGridAABBstruct", "", rw, rh, surfMat, "", cameraDump, {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity, xrayFile);
+        if (grid == "vec") return parallel ? run_grid<VoxelGridVec, true>(path, vs, dumpFile, "VoxelGridVec", "", rw, rh, false, "", cameraDump, {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity, xrayFile)
+                                           : run_grid<VoxelGridVec, false>(path, vs, dumpFile, "VoxelGridVec", "", rw, rh, false, "", cameraDump, {}, nullptr, 0, solid, sdfFile, surfaceFile, componentsFile, connectivity, xrayFile);
         std::fprintf(stderr, "unknown grid flavour %s\n", grid.c_str());
         return 2;
     } catch (const std::exception& e) {

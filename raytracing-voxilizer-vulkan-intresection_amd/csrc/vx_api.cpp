@@ -2558,6 +2558,99 @@ vx_status vx_trace_ex(const vx_grid* gc, const vx_trace_args* args)
     return trace_ex_staged(g->device, g->stream, args, [&](const vx::TraceIO& io) { return trace_common(g, io); });
 }
 
+// ---- multi-hit query (vx_multihit.hip) -----------------------------------------------------------------------------
+// the argument checks of vx_trace_multi*, in the header's order; *io receives the ray batch (nrays == 0: nothing to do)
+static vx_status multihit_args_to_io(const vx_grid* g, const vx_multihit_args* a, vx::Camera* cam, vx::TraceIO* io)
+{
+    if (!g || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (a->max_hits < 1 || a->max_hits > VX_MULTIHIT_MAX) return fail(VX_ERR_INVALID_ARG, "max_hits must be 1..VX_MULTIHIT_MAX");
+    if ((a->after_t != nullptr) != (a->after_prim != nullptr)) return fail(VX_ERR_INVALID_ARG, "the cursor needs both after_t and after_prim");
+    const vx_trace_args& b = a->base;
+    if (b.any_hit || b.normal || b.shadowed || b.hits || b.num_hits)
+        return fail(VX_ERR_INVALID_ARG, "any_hit, normal, shadowed, hits and num_hits are not part of the multi-hit query");
+    const bool camera = b.view_inverse && b.proj_inverse && b.width && b.height;
+    if (!b.rays && !camera && !b.num_rays) { io->nrays = 0; return VX_OK; }  // zero rays
+    return args_to_io(&b, cam, io);
+}
+
+// the query on device arrays: io's pointers, count and the cursor are device memory
+static vx_status multihit_common(vx_grid* g, vx::TraceIO io, const vx_multihit_args* a, uint32_t* count, const float* after_t, const uint32_t* after_prim)
+{
+    vx::TraceMips mips{};
+    const uint32_t* prefix = nullptr;
+    if (g->g.nvox) {  // (a grid of 0 cells has nothing to build or to walk: every slot is padded)
+        VX_TRY(ensure_coarse(g));
+        bool pending = false;
+        VX_TRY(prefix_launch(g, &pending));  // prim needs the prefix array on the stream, not the count on the host
+        prefix = g->wprefix.as<uint32_t>();
+        const uint32_t* p16 = nullptr;
+        mips = grid_mips(g, &p16);
+    }
+    VX_TRY(upload_camera(g->camera, g->stream, io));
+    // (read-only: a deferred list emission is neither queued nor waited for here)
+    vx::launch_multihit(g->g, mips, prefix, io, a->max_hits, count, after_t, after_prim, g->stream);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+vx_status vx_trace_multi_device(const vx_grid* gc, const vx_multihit_args* a)
+{
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(multihit_args_to_io(gc, a, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return multihit_common(g, io, a, a->count, a->after_t, a->after_prim);
+}
+
+vx_status vx_trace_multi(const vx_grid* gc, const vx_multihit_args* a)
+{
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(multihit_args_to_io(gc, a, &cam, &io));
+    const uint64_t n = io.nrays;
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    const size_t K = a->max_hits;
+    // every non-null array through pooled device memory on the grid's stream, as trace_ex_staged does for one entry per ray
+    DevBuf dr, dtm, dt, dp, dc, dat, dap;
+    DevBuf* const all[] = {&dr, &dtm, &dt, &dp, &dc, &dat, &dap};
+    for (DevBuf* b : all) { b->dev = g->device; b->stream = g->stream; }
+    hipError_t e = hipSuccess;
+    vx_status st = VX_OK;
+    auto upload = [&](DevBuf& b, const void* host, size_t bytes) {
+        if (e == hipSuccess && host) { e = b.ensure(bytes); if (e == hipSuccess) e = hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, g->stream); }
+    };
+    upload(dr, a->base.rays, (size_t)n * 24);
+    upload(dtm, a->base.tmax_per_ray, (size_t)n * 4);
+    upload(dat, a->after_t, (size_t)n * 4);
+    upload(dap, a->after_prim, (size_t)n * 4);
+    if (e == hipSuccess && a->base.t) e = dt.ensure((size_t)n * K * 4);
+    if (e == hipSuccess && a->base.prim) e = dp.ensure((size_t)n * K * 4);
+    if (e == hipSuccess && a->count) e = dc.ensure((size_t)n * 4);
+    if (e == hipSuccess) {
+        if (io.rays) io.rays = dr.as<float>();
+        if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
+        io.t_out = dt.as<float>();
+        io.prim_out = dp.as<uint32_t>();
+        st = multihit_common(g, io, a, dc.as<uint32_t>(), dat.as<float>(), dap.as<uint32_t>());
+    }
+    if (e == hipSuccess && st == VX_OK) {
+        if (a->base.t) e = hipMemcpyAsync(a->base.t, dt.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, g->stream);
+        if (e == hipSuccess && a->base.prim) e = hipMemcpyAsync(a->base.prim, dp.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, g->stream);
+        if (e == hipSuccess && a->count) e = hipMemcpyAsync(a->count, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    } else if (e == hipSuccess) {
+        e = hipStreamSynchronize(g->stream);  // the uploads read the caller's arrays
+    }
+    for (DevBuf* b : all) b->release();
+    if (st != VX_OK) return st;
+    VX_HIP(e);
+    return VX_OK;
+}
+
 // vx_trace / vx_octree_trace: t and prim of a host ray buffer through the handle's host-buffer extended query, hits counted on the host
 extern "C++" {
 template <class Ex>

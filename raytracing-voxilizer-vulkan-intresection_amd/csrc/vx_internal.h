@@ -175,6 +175,13 @@ void launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* wo
                   void* idx_tmp /*trace_idx_bytes when ranks / normals / the hit list are wanted*/, hipStream_t s,
                   const uint32_t* prefix16 = nullptr /*optional: launch_scan_u32's group16 of word_prefix*/, WalkQueue* queue = nullptr);
 
+// Multi-hit query on the grid (vx_multihit.hip): per ray the first K (1..32) accepted hits in (t, prim) order into io.t_out / io.prim_out (K
+// entries per ray, ray-major, padded with -1 / all ones; both optional) and the number of all accepted hits into count (optional); after_t /
+// after_prim: the optional per-ray cursor.  io as for launch_octree_trace (cam_dev, not cam); the other outputs of io are not written.
+// mips.bricks3 or word_prefix null: every ray misses.
+void launch_multihit(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, uint32_t K, uint32_t* count,
+                     const float* after_t, const uint32_t* after_prim, hipStream_t s);
+
 // First hit per ray against the octree's AABB list by descending its node array (vx_octrace.hip).  io as for launch_trace (cam_dev, not cam;
 // prim = index in vx_octree_aabbs order); nodes may be null / nitems 0: every ray misses.
 void launch_octree_trace(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,

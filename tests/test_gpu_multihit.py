@@ -1,0 +1,482 @@
+"""GPU tests of the multi-hit ray query (vx_trace_multi*, Grid.trace_multi): ordered hit lists and hit counts are compared whole, bit for
+bit (t through its uint32 view), with the numpy restatement of hitAabb (tests/multihit_ref.py) over the grid's own AABB list."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import multihit_ref as mr
+import vx_scenes
+from test_gpu_solid import write_mask
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+INVALID_ARG = 1
+KS = (1, 3, 32)
+ORG = (0.25, -1.0, 3.0)   # with vs = 0.5 every lattice plane and box corner is an exact float: rays can lie exactly on them
+VS = F(0.5)
+# the full brick's lattice is NOT exact: boxes of neighbouring cells overlap by a few float32 ulps at some planes, and a ray inside such an
+# overlap enters both cells of every slab at the same t (family_rays' last family) -- the ties that only prim can order
+LATTICE = {"full_8": ((0.3, -1.1, 3.7), F(0.3))}
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "raytracing-voxilizer-vulkan-intresection_amd")
+
+
+# ---- grids ----------------------------------------------------------------------------------------------------------------------------
+def cells_of(name):
+    """bool [Z, Y, X] of the named case"""
+    def rnd(x, y, z, p, seed):
+        return np.random.default_rng(seed).random((z, y, x)) < p
+    if name == "one_1":
+        return np.ones((1, 1, 1), bool)
+    if name == "one_27":
+        c = np.zeros((3, 3, 3), bool)
+        c[1, 1, 1] = True
+        return c
+    if name == "full_8":
+        return np.ones((8, 8, 8), bool)
+    if name == "ragged":
+        return rnd(9, 7, 5, 0.3, 1)
+    if name == "blocks_70":
+        return rnd(70, 70, 70, 0.05, 2)
+    if name == "long_130":
+        return rnd(130, 8, 8, 0.5, 3)
+    raise KeyError(name)
+
+
+CASES = ("one_1", "one_27", "full_8", "ragged", "blocks_70", "long_130", "mesh_40")
+
+
+def family_rays(dim, org, vs, occupied, seed):
+    """A few hundred rays of every family the query has to get right -> float32 [n, 6].  occupied: (x, y, z) of some occupied cells."""
+    rng = np.random.default_rng(seed)
+    dim = np.asarray(dim, np.float64)
+    org = np.asarray(org, np.float64)
+    vs = float(vs)
+    lo, hi = org, org + dim * vs
+    ctr, diag = (lo + hi) / 2, float(np.linalg.norm(hi - lo))
+    rays = []
+
+    def add(o, d):
+        rays.append(np.concatenate([np.asarray(o, np.float64), np.asarray(d, np.float64)]))
+
+    # from outside the hull at random interior points, and the same lines walked the other way
+    for _ in range(64):
+        u = rng.normal(size=3)
+        o = ctr + 2.0 * diag * u / np.linalg.norm(u)
+        tgt = rng.uniform(lo, hi)
+        d = (tgt - o) / np.linalg.norm(tgt - o)
+        add(o, d)
+        add(2.0 * tgt - o, -d)
+    # axis-parallel (two zero components), both ways: through cell centres and lying exactly on lattice planes
+    for a in range(3):
+        u, v = (a + 1) % 3, (a + 2) % 3
+        for sgn in (1.0, -1.0):
+            for k in range(8):
+                o = np.zeros(3)
+                iu, iv = rng.integers(0, int(dim[u]) + 1), rng.integers(0, int(dim[v]) + 1)
+                if k < 3:      # cell centres
+                    o[u], o[v] = org[u] + (min(iu, dim[u] - 1) + 0.5) * vs, org[v] + (min(iv, dim[v] - 1) + 0.5) * vs
+                elif k < 6:    # one lattice plane
+                    o[u], o[v] = org[u] + iu * vs, org[v] + (min(iv, dim[v] - 1) + 0.5) * vs
+                else:          # a lattice line: two planes at once
+                    o[u], o[v] = org[u] + iu * vs, org[v] + iv * vs
+                o[a] = lo[a] - 1.75 * vs if sgn > 0 else hi[a] + 1.75 * vs
+                d = np.zeros(3)
+                d[a] = sgn
+                add(o, d)
+    # one zero component, some of them inside a lattice plane
+    for k in range(36):
+        a = k % 3
+        tgt = rng.uniform(lo, hi)
+        if k % 2:
+            tgt[a] = org[a] + rng.integers(0, int(dim[a]) + 1) * vs
+        d = rng.normal(size=3)
+        d[a] = 0.0
+        d /= np.linalg.norm(d)
+        add(tgt - 1.5 * diag * d, d)
+    # the main diagonals through cell corners
+    for sx in (1.0, -1.0):
+        for sy in (1.0, -1.0):
+            for sz in (1.0, -1.0):
+                for _ in range(2):
+                    c = org + np.array([rng.integers(0, int(dim[i]) + 1) for i in range(3)]) * vs
+                    d = np.array([sx, sy, sz])
+                    add(c - d * (float(dim.max()) + 2.0) * vs, d)
+    # from inside occupied cells
+    for k in range(24):
+        x, y, z = occupied[rng.integers(0, len(occupied))]
+        o = org + (np.array([x, y, z]) + (0.5 if k % 3 == 0 else rng.uniform(0.1, 0.9, size=3))) * vs
+        d = rng.normal(size=3)
+        if k % 4 == 1:
+            d[k % 3] = 0.0
+        add(o, d / np.linalg.norm(d))
+    # misses: beside the grid and pointing away from it
+    for k in range(12):
+        a = k % 3
+        o = ctr.copy()
+        o[a] = hi[a] + (0.5 + k) * vs
+        d = rng.normal(size=3)
+        d[a] = abs(d[a]) + 0.1 if k % 2 else 0.0
+        if not d.any():
+            d[(a + 1) % 3] = 1.0
+        add(o, d / np.linalg.norm(d))
+    # inside the overlap of two neighbouring cells' float boxes (cell_aabb's own arithmetic), where there is one: both cells are hit at one t
+    o32, v32 = np.asarray(org, F), F(vs)
+    for u in range(3):
+        c = o32[u] + (np.arange(int(dim[u]), dtype=F) + F(0.5)) * v32
+        amax, bmin = c[:-1] + v32 * F(0.5), c[1:] - v32 * F(0.5)
+        for j in np.flatnonzero(amax > bmin)[:4]:
+            for a in ((u + 1) % 3, (u + 2) % 3):
+                v = 3 - u - a
+                for sgn in (1.0, -1.0):
+                    for exact in (False, True):
+                        o, d = np.zeros(3), np.zeros(3)
+                        if exact:   # strictly inside both boxes, a zero component (needs two ulps of overlap)
+                            o[u] = np.nextafter(bmin[j], F(np.inf))
+                            if not o[u] < amax[j]:
+                                continue
+                        else:       # on the upper cell's own min plane, moving into it by nothing that a float can see
+                            o[u], d[u] = bmin[j], 1e-30
+                        o[v] = org[v] + (rng.integers(0, int(dim[v])) + 0.5) * vs
+                        o[a] = lo[a] - 1.75 * vs if sgn > 0 else hi[a] + 1.75 * vs
+                        d[a] = sgn
+                        add(o, d)
+    return np.ascontiguousarray(np.array(rays), F)
+
+
+class Case:
+    pass
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """grid, its AABB list, the rays and the matrix of reference hit times -- built once per case and left unchanged"""
+    import voxhip as gpu
+    c = Case()
+    if name == "mesh_40":
+        v, t = vx_scenes.blob()
+        c.g = gpu.Grid.voxelize(gpu.Mesh.from_arrays(v, t), F(2.0 / 40))
+        d = c.g.describe()
+        c.dim, c.org, c.vs = d["dim"], tuple(float(x) for x in d["origin"]), F(d["voxel_size"])
+        bits = np.unpackbits(c.g.bitmask().view(np.uint8), bitorder="little")[: c.dim[0] * c.dim[1] * c.dim[2]]
+        cells = bits.reshape(c.dim[2], c.dim[1], c.dim[0]).astype(bool)
+    else:
+        cells = cells_of(name)
+        Z, Y, X = cells.shape
+        c.org, c.vs = LATTICE.get(name, (ORG, VS))
+        c.dim = (X, Y, Z)
+        c.g = gpu.Grid.create(gpu.GRID_BOOL, X, Y, Z, c.vs, c.org)
+        if name.startswith("one"):   # through setVoxel
+            z, y, x = np.argwhere(cells)[0]
+            c.g.set_voxel(int(x), int(y), int(z))
+        else:                        # through the bitmask and refresh
+            write_mask(c.g, mr.pack(cells))
+            c.g.refresh()
+    c.aabbs = c.g.aabbs()
+    assert len(c.aabbs) == int(cells.sum()) > 0
+    occ = np.argwhere(cells)[:, ::-1]
+    c.rays = family_rays(c.dim, c.org, c.vs, occ, seed=len(name))
+    c.times = mr.hit_times(c.aabbs, c.rays)
+    return c
+
+
+@pytest.fixture(params=CASES)
+def case(gpu, request):
+    return _case(request.param)
+
+
+def same(got, ref, what=""):
+    """whole arrays, t through its bits"""
+    t, p, c = ref
+    if "t" in got:
+        assert got["t"].dtype == F and got["t"].shape == t.shape
+        bad = np.flatnonzero((got["t"].view(np.uint32) != t.view(np.uint32)).any(axis=1))
+        assert not len(bad), "%s t: %d rays differ, first %d: %r want %r" % (what, len(bad), bad[0], got["t"][bad[0]], t[bad[0]])
+    if "prim" in got:
+        bad = np.flatnonzero((got["prim"] != p).any(axis=1))
+        assert not len(bad), "%s prim: %d rays differ, first %d: %r want %r" % (what, len(bad), bad[0], got["prim"][bad[0]], p[bad[0]])
+    if "count" in got:
+        bad = np.flatnonzero(got["count"] != c)
+        assert not len(bad), "%s count: %d rays differ, first %d: %d want %d" % (what, len(bad), bad[0], got["count"][bad[0]], c[bad[0]])
+
+
+# ---- the lists and the counts -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", KS)
+def test_lists_and_counts(case, k):
+    ref = mr.select(case.times, k)
+    got = case.g.trace_multi(case.rays, max_hits=k)
+    same(got, ref, "K=%d" % k)
+    # the padding is exact (the reference pads; say so on the GPU's own arrays)
+    pad = np.arange(k)[None, :] >= np.minimum(ref[2], k)[:, None]
+    assert (got["t"][pad] == F(-1)).all() and (got["prim"][pad] == 0xFFFFFFFF).all()
+    assert (got["t"][~pad] > 0).all()
+    # slot 0 is the first-hit query's answer
+    one = case.g.trace_ex(case.rays, want=("t", "prim"))
+    assert np.array_equal(got["t"][:, 0].view(np.uint32), one["t"].view(np.uint32)) and np.array_equal(got["prim"][:, 0], one["prim"])
+    # without the count the ray may stop early: the same lists
+    same(case.g.trace_multi(case.rays, max_hits=k, want=("t", "prim")), ref, "K=%d, no count" % k)
+    same(case.g.trace_multi(case.rays, max_hits=k, want=("count",)), ref, "K=%d, count only" % k)
+
+
+def test_inputs_cover_ties_and_overflow(gpu):
+    """The full brick must tie (several cells at bit-equal t on one ray) and overflow K = 1 and 3; the long grid must overflow K = 32."""
+    full = _case("full_8")
+    t, p, c = mr.select(full.times, 32)
+    ties = ((t[:, 1:] == t[:, :-1]) & (t[:, 1:] > 0)).sum(axis=1)     # pairs of neighbouring list entries with bit-equal t
+    assert (ties >= 4).sum() >= 8, ties[ties > 0]
+    assert (p[:, 1:] > p[:, :-1])[(t[:, 1:] == t[:, :-1]) & (t[:, 1:] > 0)].all()
+    assert (c > 3).sum() >= 50
+    assert (mr.select(_case("long_130").times, 32)[2] > 32).sum() >= 5
+    assert (mr.select(_case("blocks_70").times, 1)[2] == 0).any() and (mr.select(_case("blocks_70").times, 1)[2] > 3).any()
+
+
+@pytest.mark.parametrize("name", ["full_8", "blocks_70", "mesh_40"])
+def test_windows(gpu, name):
+    """tmin / tmax that cut the lists in the middle, bounds that ARE hit times (inclusive), and a tmax per ray"""
+    c = _case(name)
+    pos = np.sort(c.times[c.times > 0])
+    a, b = float(pos[int(0.35 * len(pos))]), float(pos[int(0.65 * len(pos))])
+    for k in (3, 32):
+        same(c.g.trace_multi(c.rays, max_hits=k, tmin=a, tmax=b), mr.select(c.times, k, tmin=a, tmax=b), "window K=%d" % k)
+    full_t = mr.select(c.times, 4)[0]
+    tpr = np.where(full_t[:, 2] > 0, full_t[:, 2], F(10000.0)).astype(F)     # the third hit's own t: the list ends with it and its ties
+    ref = mr.select(c.times, 8, tmax_per_ray=tpr)
+    assert (ref[2] >= 3).any()
+    same(c.g.trace_multi(c.rays, max_hits=8, tmax_per_ray=tpr), ref, "tmax_per_ray")
+    same(c.g.trace_multi(c.rays, max_hits=8, tmax_per_ray=tpr, want=("t", "prim")), ref, "tmax_per_ray, no count")
+
+
+@pytest.mark.parametrize("name", ["full_8", "long_130", "ragged"])
+def test_paging_with_the_cursor(gpu, name):
+    """K = 2 pages chained through `after` reassemble the K = 32 list and count down the total"""
+    c = _case(name)
+    t32, p32, cnt = mr.select(c.times, 32)
+    n = len(c.rays)
+    at, ap = np.full(n, F(-1), F), np.full(n, 12345, np.uint32)   # (-1, anything) = no cursor
+    pages_t, pages_p = [], []
+    for page in range(16):
+        got = c.g.trace_multi(c.rays, max_hits=2, after=(at, ap))
+        same(got, mr.select(c.times, 2, after=(at, ap)), "page %d" % page)
+        assert np.array_equal(got["count"], np.maximum(cnt.astype(np.int64) - 2 * page, 0))
+        pages_t.append(got["t"])
+        pages_p.append(got["prim"])
+        last = np.where(got["t"][:, 1] > 0, 1, 0)
+        have = got["t"][:, 0] > 0
+        at = np.where(have, got["t"][np.arange(n), last], at).astype(F)
+        ap = np.where(have, got["prim"][np.arange(n), last], ap).astype(np.uint32)
+    assert np.array_equal(np.concatenate(pages_t, axis=1).view(np.uint32), t32.view(np.uint32))
+    assert np.array_equal(np.concatenate(pages_p, axis=1), p32)
+    # the early-out path under a cursor
+    same(c.g.trace_multi(c.rays, max_hits=2, after=(at, ap), want=("t", "prim")), mr.select(c.times, 2, after=(at, ap)), "last page, no count")
+
+
+def test_camera_rays(gpu):
+    """Rays generated in the kernel against the same rays from the host: the rule test_gpu_parity.py applies to generated rays (the same
+    hit pattern, t within 1e-5)."""
+    import oracle
+    v, t = vx_scenes.rotated_cube(half=1.0, offset=(0.0, 1.0, 0.0))
+    g = gpu.Grid.voxelize(gpu.Mesh.from_arrays(v, t), F(0.05))
+    vi, pi = vx_scenes.camera_matrices(aspect=160.0 / 90.0)
+    W, H = 160, 90
+    cam = g.trace_multi(camera=(vi, pi, W, H), max_hits=8)
+    exp = g.trace_multi(oracle.primary_rays(vi, pi, W, H), max_hits=8)
+    assert (exp["count"] > 1).mean() > 0.01
+    assert np.array_equal(cam["t"] > 0, exp["t"] > 0)
+    assert np.allclose(cam["t"], exp["t"], rtol=0, atol=1e-5)
+
+
+# ---- the device variant, side effects, errors -----------------------------------------------------------------------------------------
+def test_device_variant_allocates_once(gpu):
+    import torch
+    c = _case("blocks_70")
+    n, k = len(c.rays), 8
+    d_rays = torch.from_numpy(c.rays).cuda()
+    d_t = torch.zeros((n, k), dtype=torch.float32, device="cuda")
+    d_p = torch.zeros((n, k), dtype=torch.int32, device="cuda")
+    d_c = torch.zeros(n, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+
+    def run():
+        c.g.trace_multi_device(d_rays.data_ptr(), n, k, d_t.data_ptr(), d_p.data_ptr(), d_c.data_ptr())
+    run()
+    before = gpu.device_allocations()
+    run()
+    run()
+    assert gpu.device_allocations() == before
+    torch.cuda.synchronize()
+    ref = mr.select(c.times, k)
+    same({"t": d_t.cpu().numpy(), "prim": d_p.cpu().numpy().view(np.uint32), "count": d_c.cpu().numpy().view(np.uint32)}, ref, "device")
+    # camera rays on the device variant: what the host variant gives
+    vi, pi = vx_scenes.camera_matrices(eye=(40.0, 30.0, -20.0), ctr=(17.0, 16.0, 20.0), aspect=1.0)
+    W = H = 24
+    d_t2 = torch.zeros((W * H, k), dtype=torch.float32, device="cuda")
+    d_c2 = torch.zeros(W * H, dtype=torch.int32, device="cuda")
+    c.g.trace_multi_device(None, 0, k, d_t2.data_ptr(), None, d_c2.data_ptr(), camera=(vi, pi, W, H))
+    torch.cuda.synchronize()
+    host = c.g.trace_multi(camera=(vi, pi, W, H), max_hits=k)
+    assert (host["count"] > 0).any()
+    assert np.array_equal(d_t2.cpu().numpy().view(np.uint32), host["t"].view(np.uint32))
+    assert np.array_equal(d_c2.cpu().numpy().view(np.uint32), host["count"])
+
+
+def test_pending_list_stays_pending(gpu):
+    """A VX_VOXELIZE_LIST_ASYNC emission is queued by the next FIRST-HIT batch or by whoever reads the list -- not by this query."""
+    import torch
+    v, t = vx_scenes.blob()
+    vs = F(2.0 / 48)
+    mesh = gpu.Mesh.from_arrays(v, t)
+    g = gpu.Grid.voxelize(mesh, vs, gpu.GRID_VEC)
+    want = g.aabbs()
+    cap = len(want) + 8
+    buf = torch.zeros(cap * 6, dtype=torch.float32, device="cuda")
+    g.bind_aabbs_device(buf.data_ptr(), cap)
+    d = g.describe()
+    rays = vx_scenes.random_rays(500, d["bbox_min"], d["bbox_max"], seed=3)
+    g.revoxelize(mesh, vs, list_async=True)
+    got = g.trace_multi(rays, max_hits=4)
+    torch.cuda.synchronize()
+    assert not buf.cpu().numpy().any(), "the multi-hit query queued the list emission"
+    g.list_wait()
+    torch.cuda.synchronize()
+    assert buf.cpu().numpy()[: len(want) * 6].tobytes() == want.tobytes()
+    b = gpu.Grid.voxelize(mesh, vs, gpu.GRID_BOOL)
+    same(got, mr.multi(b.aabbs(), rays, 4), "vec grid")
+    assert (got["count"] > 4).any()
+
+
+def test_empty_grids_and_zero_rays(gpu):
+    rays = family_rays((4, 5, 6), ORG, VS, [(1, 1, 1)], seed=9)
+    for dims in ((4, 5, 6), (0, 0, 0)):
+        g = gpu.Grid.create(gpu.GRID_BOOL, dims[0], dims[1], dims[2], VS, ORG)
+        got = g.trace_multi(rays, max_hits=3)
+        assert (got["t"] == F(-1)).all() and (got["prim"] == 0xFFFFFFFF).all() and not got["count"].any()
+    g = _case("ragged").g
+    L = gpu.lib()
+    a = gpu.MultiHitArgs()
+    a.max_hits = 4
+    assert L.vx_trace_multi(g.h, C.byref(a)) == 0 and L.vx_trace_multi_device(g.h, C.byref(a)) == 0
+    one = np.zeros((1, 6), F)
+    a.base.rays = one.ctypes.data
+    assert L.vx_trace_multi(g.h, C.byref(a)) == 0
+
+
+def test_argument_errors_write_nothing(gpu):
+    c = _case("ragged")
+    L = gpu.lib()
+    n = len(c.rays)
+    t = np.full((n, 4), F(7), F)
+    p = np.full((n, 4), 7, np.uint32)
+    cnt = np.full(n, 7, np.uint32)
+    junk = np.zeros(max(n, 16) * 3, F)
+
+    def args():
+        a = gpu.MultiHitArgs()
+        a.base.rays, a.base.num_rays, a.base.tmin, a.base.tmax = c.rays.ctypes.data, n, 0.001, 10000.0
+        a.base.t, a.base.prim, a.count, a.max_hits = t.ctypes.data, p.ctypes.data, cnt.ctypes.data, 4
+        return a
+
+    for fn in (L.vx_trace_multi, L.vx_trace_multi_device):
+        assert fn(None, C.byref(args())) == INVALID_ARG
+        assert fn(c.g.h, None) == INVALID_ARG
+        for k in (0, 33, 0xFFFFFFFF):
+            a = args()
+            a.max_hits = k
+            assert fn(c.g.h, C.byref(a)) == INVALID_ARG, k
+        a = args()
+        a.after_t = junk.ctypes.data
+        assert fn(c.g.h, C.byref(a)) == INVALID_ARG
+        a = args()
+        a.after_prim = junk.ctypes.data
+        assert fn(c.g.h, C.byref(a)) == INVALID_ARG
+        for field in ("normal", "shadowed", "hits", "num_hits"):
+            a = args()
+            setattr(a.base, field, junk.ctypes.data)
+            assert fn(c.g.h, C.byref(a)) == INVALID_ARG, field
+        a = args()
+        a.base.any_hit = 1
+        assert fn(c.g.h, C.byref(a)) == INVALID_ARG
+        a = args()
+        a.base.rays = None     # rays announced, but neither a buffer nor a camera
+        assert fn(c.g.h, C.byref(a)) == INVALID_ARG
+    assert (t == F(7)).all() and (p == 7).all() and (cnt == 7).all()
+
+
+def test_default_paths_queue_no_multihit_kernel(gpu):
+    v, t = vx_scenes.blob()
+    mesh = gpu.Mesh.from_arrays(v, t)
+    gpu.profile_enable(True)
+    gpu.profile_reset()
+    g = gpu.Grid.voxelize(mesh, F(2.0 / 64))
+    d = g.describe()
+    rays = vx_scenes.random_rays(1000, d["bbox_min"], d["bbox_max"], seed=1)
+    g.trace(rays)
+    names = list(gpu.profile_read())
+    assert "k_walk" in names and not any(n.startswith("k_multihit") for n in names), names
+    gpu.profile_reset()
+    g.trace_multi(rays, max_hits=8)
+    g.trace_multi(rays, max_hits=32)
+    prof = gpu.profile_read()   # (kernel names come without their template arguments)
+    gpu.profile_enable(False)
+    assert prof["k_multihit"][1] == 2 and "k_walk" not in prof and "k_rank" not in prof, prof
+
+
+# ---- C++ facade and CLI -----------------------------------------------------------------------------------------------------------------
+def run(cmd):
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = PKG + ":" + env.get("LD_LIBRARY_PATH", "")
+    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=300)
+
+
+def test_facade_trace_multi(gpu, tmp_path):
+    import build as vxbuild
+    exe = str(tmp_path / "multihit_facade")
+    subprocess.check_call(["g++", "-O2", "-std=c++20", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I", vxbuild.CPP,
+                           "-I", os.path.join(vxbuild.ROOT, "include"), "-isystem", os.path.join(vxbuild.ROCM, "include"),
+                           os.path.join(ROOT, "tests", "multihit_facade.cpp"), "-o", exe, "-L", vxbuild.HERE, "-lvoxhip",
+                           "-L", os.path.join(vxbuild.ROCM, "lib"), "-lamdhip64", "-Wl,-rpath," + vxbuild.HERE, "-lpthread"])
+    v, t = vx_scenes.rotated_cube()
+    obj = tmp_path / "c.obj"
+    vx_scenes.write_obj(str(obj), v, t)
+    vs = F(0.09)
+    g = gpu.Grid.voxelize(gpu.Mesh.from_arrays(v, t), vs)
+    d = g.describe()
+    rays = vx_scenes.random_rays(200, d["bbox_min"], d["bbox_max"], seed=8)
+    rays.tofile(str(tmp_path / "rays.bin"))
+    k, tmin, tmax = 5, 0.001, 10000.0
+    r = run([exe, str(obj), repr(float(vs)), str(tmp_path / "rays.bin"), str(tmp_path / "out.bin"), str(k), repr(tmin), repr(tmax)])
+    assert r.returncode == 0, r.stdout
+    ref = mr.multi(g.aabbs(), rays, k, tmin=tmin, tmax=tmax)
+    assert (ref[2] > k).any() and (ref[2] == 0).any()
+    raw = np.fromfile(str(tmp_path / "out.bin"), np.uint32)
+    n = len(rays)
+    assert len(raw) == 3 * (2 * n * k + n)
+    for flavour, blk in enumerate(raw.reshape(3, -1)):
+        got = {"t": blk[: n * k].view(F).reshape(n, k), "prim": blk[n * k: 2 * n * k].reshape(n, k), "count": blk[2 * n * k:]}
+        same(got, ref, "flavour %d" % flavour)
+
+
+def test_cli_xray(gpu, tmp_path):
+    """--xray: a 16-bit PGM of min(count, 65535) per camera ray, against Grid.trace_multi with the camera the CLI used"""
+    v, t = vx_scenes.cube()
+    obj = tmp_path / "cube.obj"
+    vx_scenes.write_obj(str(obj), v, t)
+    pgm, cam = tmp_path / "x.pgm", tmp_path / "cam.bin"
+    W, H = 96, 54
+    r = run([os.path.join(PKG, "voxilizer"), str(obj), "0.0625", "--xray", str(pgm), "--size", "%dx%d" % (W, H), "--camera-dump", str(cam)])
+    assert r.returncode == 0 and "xray %dx%d" % (W, H) in r.stdout, r.stdout
+    raw = open(pgm, "rb").read()
+    hdr = b"P5\n%d %d\n65535\n" % (W, H)
+    assert raw.startswith(hdr) and len(raw) == len(hdr) + 2 * W * H
+    img = np.frombuffer(raw[len(hdr):], ">u2").reshape(H, W)
+    cm = np.fromfile(cam, F)
+    g = gpu.Grid.voxelize(gpu.Mesh.from_arrays(v, t), F(0.0625))
+    cnt = g.trace_multi(camera=(cm[:16], cm[16:], W, H), max_hits=1, want=("count",))["count"].reshape(H, W)
+    assert np.array_equal(img, np.minimum(cnt, 65535))
+    assert cnt.max() >= 4 and (cnt == 0).any()
+    r = run([os.path.join(PKG, "voxilizer"), str(obj), "0.0625", "--xray", str(pgm), "--grid", "octree"])
+    assert r.returncode == 2 and "--xray" in r.stdout
