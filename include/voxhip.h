@@ -741,6 +741,9 @@ vx_status vx_profile_read(int slot, char* name, size_t name_capacity, double* to
 /* the number of device blocks the library's handles have requested from its memory pool since the library was loaded (pool hits
  * included): a steady-state call that allocates nothing leaves it unchanged */
 uint64_t vx_device_allocations(void);
+/* the number of pool blocks the library's handles and calls in progress hold right now, summed over the devices: back to its earlier
+ * value once everything created in between is freed */
+uint64_t vx_device_live_blocks(void);
 
 /* ---- multi-GPU helpers (host arithmetic only) ----------------------------------------------------------------
  * Word-aligned shard of the bitmask for rank r of n: contributions of different ranks are word-disjoint, so an

@@ -12,9 +12,11 @@
 #include <cstring>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -132,29 +134,58 @@ void pool_free(int dev, void* p, hipStream_t stream, bool in_flight)
     P.live.erase(it);
 }
 
+// Where a buffer lives: the device of its blocks and the stream its owner queues their work on (the pool orders reuse by it).  Every handle
+// IS a Home (g->device, g->stream), a function's temporaries share a local one.  `drained`: the owner has synchronised the stream and queues
+// nothing more -- its blocks go back without an event each (the free functions).  Not copyable: buffers point at it.
+struct Home {
+    int device;
+    hipStream_t stream;
+    bool drained;
+    explicit Home(int d = 0, hipStream_t s = nullptr, bool is_drained = false) : device(d), stream(s), drained(is_drained) {}
+    Home(const Home&) = delete;
+    Home& operator=(const Home&) = delete;
+};
+
+// One pool block and its owner: a buffer is named once, where it is declared -- bound there to its Home, released by its destructor.  A
+// move hands the block over and leaves the source empty; the target keeps its own Home.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
-    int dev = 0;
-    hipStream_t stream = nullptr;  // the stream the owner queues this buffer's work on (set by the owning handle)
+    const Home* const home;
     bool fresh = false;  // set when ensure() handed out a new block (contents undefined); the owner clears it
     uint32_t scan_gen = 0;  // scan scratch only: the number of the last scan that used this block (generation mode of the single-pass scan)
+    explicit DevBuf(const Home* h) : home(h) {}
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), home(o.home), fresh(o.fresh), scan_gen(o.scan_gen) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p; cap = o.cap; fresh = o.fresh; scan_gen = o.scan_gen;
+            o.p = nullptr; o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t bytes)
     {
         if (bytes <= cap && p) return hipSuccess;
         release();
-        hipError_t e = pool_alloc(dev, bytes, &p, stream);
+        hipError_t e = pool_alloc(home->device, bytes, &p, home->stream);
         if (e == hipSuccess) { cap = round_size(bytes); fresh = true; }
         return e;
     }
+    // `in_flight`: see pool_free; a drained Home's blocks never are
     void release(bool in_flight = true)
     {
-        if (p) pool_free(dev, p, stream, in_flight);
+        if (p) pool_free(home->device, p, home->stream, in_flight && !home->drained);
         p = nullptr;
         cap = 0;
     }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "a block has one owner");
 
 struct DeviceGuard {
     int prev = -1;
@@ -209,13 +240,18 @@ inline bool mail_wait(const volatile unsigned long long* a, const volatile unsig
     }
 }
 
-hipError_t mail_alloc(Mail** out)
+struct MailFree {
+    void operator()(Mail* m) const { (void)hipHostFree(m); }
+};
+using MailPtr = std::unique_ptr<Mail, MailFree>;
+
+hipError_t mail_alloc(MailPtr& out)
 {
     void* p = nullptr;
     const hipError_t e = hipHostMalloc(&p, sizeof(Mail), hipHostMallocCoherent);
     if (e != hipSuccess) return e;
     std::memset(p, 0, sizeof(Mail));
-    *out = reinterpret_cast<Mail*>(p);
+    out.reset(reinterpret_cast<Mail*>(p));
     return hipSuccess;
 }
 
@@ -255,8 +291,7 @@ uint32_t advance_scan_gen(DevBuf& tmp, hipStream_t s)
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------
-struct vx_mesh {
-    int device = 0;
+struct vx_mesh : Home {  // (no stream of its own: uploads are synchronous)
     std::vector<float> hv;
     std::vector<int32_t> hi;
     std::vector<int32_t> tri_mat;        // material id per triangle (-1 = none); empty: the mesh has no materials
@@ -266,11 +301,11 @@ struct vx_mesh {
     std::vector<vx_material> values;
     std::vector<int32_t> tri_value;
     bool values_ready = false;
-    DevBuf btv;  // tri_value on the device
+    DevBuf btv{this};  // tri_value on the device
     size_t nv = 0, nt = 0;
     const float* dv = nullptr;
     const int32_t* di = nullptr;
-    DevBuf bv, bi;
+    DevBuf bv{this}, bi{this};
     bool borrowed = false;
     bool uploaded = false;
     // attribute shading (vx_render_set_shading): corner normals / uvs (9 / 6 f32 per triangle, empty: none), texture slots (file name, RGBA8
@@ -402,23 +437,25 @@ bool same_material(const vx_material& a, const vx_material& b)  // MaterialObj::
 }
 }  // namespace
 
-struct vx_grid {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vx_grid : Home {
     int kind = VX_GRID_BOOL;
     vx::GridParams g{};
     float bbmin[3] = {0, 0, 0}, bbmax[3] = {0, 0, 0}, bbc[3] = {0, 0, 0};
     uint64_t triangles = 0;
     uint32_t cdim[3] = {0, 0, 0}, c2dim[3] = {0, 0, 0};
-    DevBuf words, twords /*tiled build mask (launch_voxelize)*/, cwords, c2words, bricks, idxtmp, ttmp, camera, wprefix, wsel /*word of every 1024th occupied voxel (prefix scan)*/, wp16 /*every 16th entry of wprefix, dense (prefix scan)*/, recs, ext /*high bits of the candidate ranges*/, units, ubase, btri, umask, bhits /*hits per block of 64 units*/, hbase /*their exclusive scan*/, scantmp, small, vec, matids, mattmp;
+    MailPtr mail;  // (ahead of the buffers: freed after them)
+    DevBuf words{this}, twords{this} /*tiled build mask (launch_voxelize)*/, cwords{this}, c2words{this}, bricks{this}, idxtmp{this}, ttmp{this}, camera{this}, wprefix{this};
+    DevBuf wsel{this} /*word of every 1024th occupied voxel (prefix scan)*/, wp16{this} /*every 16th entry of wprefix, dense (prefix scan)*/, recs{this};
+    DevBuf ext{this} /*high bits of the candidate ranges*/, units{this}, ubase{this}, btri{this}, umask{this}, bhits{this} /*hits per block of 64 units*/;
+    DevBuf hbase{this} /*their exclusive scan*/, scantmp{this}, small{this}, vec{this}, matids{this}, mattmp{this};
     // solid voxelization (vx_solid.hip): padded mask, exterior, H in the reference's layout (padded rows only) and the word prefix over H
-    DevBuf solid_m, solid_e, solid_h, solid_pre, solid_agg /*the column scans' per-chunk words*/;
+    DevBuf solid_m{this}, solid_e{this}, solid_h{this}, solid_pre{this}, solid_agg{this} /*the column scans' per-chunk words*/;
     // distance fields (vx_distance.hip): the envelopes' stacks, and the field itself for the host variants
-    DevBuf dist_stk, dist_out;
+    DevBuf dist_stk{this}, dist_out{this};
     // surface mesh (vx_surface.hip): triangles per mask word and their scan, the used lattice points and their scan, the host variant's arrays
-    DevBuf surf_cnt, surf_tpre, surf_cm, surf_vpre, surf_out;
+    DevBuf surf_cnt{this}, surf_tpre{this}, surf_cm{this}, surf_vpre{this}, surf_out{this};
     // connected components (vx_components.hip): the root bitmask and its scan, the host variants' labels, the statistics
-    DevBuf cc_roots, cc_rpre, cc_lab, cc_stat;
+    DevBuf cc_roots{this}, cc_rpre{this}, cc_lab{this}, cc_stat{this};
     uint64_t interior = 0;        // |H| of the last build or fill on the handle (vx_grid_interior)
     uint32_t solid_rounds = 0;    // rounds of that fill, the quiet one included (vx_grid_fill_rounds)
     uint64_t mat_interior = 0;    // a solid VX_VOXELIZE_MATERIALS build: ids of interior voxels / calls still to be given MaterialObj{}'s index
@@ -537,12 +574,6 @@ struct vx_grid {
         ev_ready = ev_list = nullptr;
         list_deferred = list_pending = false;
     }
-    Mail* mail = nullptr;
-    void set_dev(int d)
-    {
-        device = d;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out, &cc_roots, &cc_rpre, &cc_lab, &cc_stat}) b->dev = d;
-    }
     // the stream this handle queues work on; the pool orders the reuse of released blocks by it
     void set_stream(hipStream_t st)
     {
@@ -551,35 +582,24 @@ struct vx_grid {
             (void)hipStreamSynchronize(stream);
         }
         stream = st;
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out, &cc_roots, &cc_rpre, &cc_lab, &cc_stat}) b->stream = st;
-    }
-    void release_all()
-    {
-        for (DevBuf* b : {&words, &twords, &cwords, &c2words, &bricks, &idxtmp, &ttmp, &camera, &wprefix, &wsel, &wp16, &recs, &ext, &units, &ubase, &btri, &umask, &bhits, &hbase, &scantmp, &small, &vec, &matids, &mattmp, &solid_m, &solid_e, &solid_h, &solid_pre, &solid_agg, &dist_stk, &dist_out, &surf_cnt, &surf_tpre, &surf_cm, &surf_vpre, &surf_out, &cc_roots, &cc_rpre, &cc_lab, &cc_stat}) b->release();
-        if (mail) (void)hipHostFree(mail);
-        mail = nullptr;
     }
 };
 
-struct vx_octree {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vx_octree : Home {
     float vs = 0.f;
     float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0};
     uint64_t dim[3] = {0, 0, 0};
     uint32_t bits = 0;
     uint64_t max_items = 16;
     uint64_t nitems = 0;
-    DevBuf items;  // sorted Morton codes
+    DevBuf items{this};  // sorted Morton codes
     vx_octree_node* dnodes = nullptr;  // pre-order node array (device): in `nodebuf` (pooled) or hipMalloc'ed (level-by-level build)
-    DevBuf nodebuf;
+    DevBuf nodebuf{this};
     uint64_t nnodes = 0;
-    DevBuf camera;  // vx_octree_trace*: the camera block of primary-ray batches
-    void free_nodes(bool in_flight)
+    DevBuf camera{this};  // vx_octree_trace*: the camera block of primary-ray batches
+    ~vx_octree()  // (destroyed with its device current: vx_octree_build, vx_octree_free)
     {
-        if (nodebuf.p) nodebuf.release(in_flight);
-        else if (dnodes) (void)hipFree(dnodes);
-        dnodes = nullptr;
+        if (!nodebuf.p && dnodes) (void)hipFree(dnodes);
     }
 };
 
@@ -589,7 +609,6 @@ vx_status mesh_to_device(vx_mesh* m)
 {
     if (m->uploaded || m->borrowed) return VX_OK;
     VX_TRY(need_device(m->device));
-    m->bv.dev = m->bi.dev = m->device;
     VX_HIP(m->bv.ensure(m->nv * 12 + 16));
     VX_HIP(m->bi.ensure(m->nt * 12 + 16));
     if (m->nv) VX_HIP(hipMemcpy(m->bv.p, m->hv.data(), m->nv * 12, hipMemcpyHostToDevice));
@@ -629,7 +648,6 @@ vx_status mesh_material_values(vx_mesh* m)
         m->btv.release();
     }
     if (!m->btv.p && m->nt) {
-        m->btv.dev = m->device;
         VX_HIP(m->btv.ensure(m->nt * 4 + 16));
         VX_HIP(hipMemcpy(m->btv.p, m->tri_value.data(), m->nt * 4, hipMemcpyHostToDevice));
     }
@@ -807,7 +825,7 @@ vx_status sync_counts(vx_grid* g)
 vx_status init_grid_storage(vx_grid* g, bool clear = true)
 {
     VX_HIP(ensure_small(g->small));
-    if (!g->mail) VX_HIP(mail_alloc(&g->mail));
+    if (!g->mail) VX_HIP(mail_alloc(g->mail));
     VX_HIP(g->words.ensure((size_t)(g->g.nwords + 2) * 4));
     if (clear) {
         VX_HIP(hipMemsetAsync(g->words.p, 0, (size_t)(g->g.nwords + 2) * 4, g->stream));
@@ -1119,9 +1137,7 @@ void vx_mesh_free(vx_mesh* m)
         DeviceGuard dg(m->device);
         (void)hipDeviceSynchronize();
     }
-    m->bv.release(/*in_flight=*/false);
-    m->bi.release(/*in_flight=*/false);
-    m->btv.release(/*in_flight=*/false);
+    m->drained = true;  // (or nothing was ever queued on its blocks)
     delete m;
 }
 
@@ -1199,7 +1215,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     const bool by_rank = o.shard_world > 1 && !(o.word_begin || o.word_end);
 
     VX_HIP(ensure_small(g->small));
-    if (!g->mail) VX_HIP(mail_alloc(&g->mail));
+    if (!g->mail) VX_HIP(mail_alloc(g->mail));
     Small* ds = g->small.as<Small>();
     uint64_t tb = 0, te = mesh->nt;
     if (o.tri_begin || o.tri_end) {
@@ -1233,7 +1249,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         DevBuf& cb = (g->last_tiled && g->twords.p) ? g->twords : g->words;
         cleared_tiled = &cb == &g->twords;
         const bool clear_in_setup = cb.p && (cb.cap % 16) == 0 && cb.cap / 256 <= (size_t)ntri;
-        VX_TRY(setup_launch(mesh, gp, o.sat_variant, tb, ntri, 0, 0, g->recs, g->units, g->ubase, g->scantmp, g->mail, s, g->ext, &ds->dgrid, mtag, &units_tagged,
+        VX_TRY(setup_launch(mesh, gp, o.sat_variant, tb, ntri, 0, 0, g->recs, g->units, g->ubase, g->scantmp, g->mail.get(), s, g->ext, &ds->dgrid, mtag, &units_tagged,
                             clear_in_setup ? cb.p : nullptr, clear_in_setup ? cb.cap : 0, sharded_words ? o.word_begin : 0,
                             sharded_words ? o.word_end : 0, by_rank ? (uint32_t)o.shard_rank : 0u, by_rank ? (uint32_t)o.shard_world : 0u));
         if (clear_in_setup) cleared = cb.cap;
@@ -1253,7 +1269,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         VX_TRY(extent_from_bbox(g->mail->bbox, mesh->nv, vs, &ex));
         setup_queued = true;
     } else {
-        VX_TRY(compute_extent(mesh, vs, ds, g->mail, s, &ex));  // also clears the per-build call counter
+        VX_TRY(compute_extent(mesh, vs, ds, g->mail.get(), s, &ex));  // also clears the per-build call counter
     }
     const uint64_t nvox = ex.dim[0] * ex.dim[1] * ex.dim[2];
     if (nvox > kMaxVoxels) return fail(VX_ERR_CAPACITY, "grid exceeds 2^37 voxels");
@@ -1312,7 +1328,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     uint64_t U = 0;
     if (setup_queued) {
         if (!mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
-        VX_TRY(setup_finish(ntri, g->ubase, g->btri, g->mail, s, &U, /*stream_is_drained=*/true, btri_entries));
+        VX_TRY(setup_finish(ntri, g->ubase, g->btri, g->mail.get(), s, &U, /*stream_is_drained=*/true, btri_entries));
     } else {
         // z slab that contains the voxels of words [wb, we)
         const uint64_t XY = ex.dim[0] * ex.dim[1];
@@ -1321,9 +1337,9 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         if (zh > ex.dim[2]) zh = ex.dim[2];
         const uint32_t zhi = (uint32_t)zh;
         // records + unit scan are queued, THEN the bitmask is cleared (it does not depend on the unit count), then the host waits
-        VX_TRY(setup_launch(mesh, g->g, o.sat_variant, tb, ntri, zlo, zhi, g->recs, g->units, g->ubase, g->scantmp, g->mail, s, g->ext));
+        VX_TRY(setup_launch(mesh, g->g, o.sat_variant, tb, ntri, zlo, zhi, g->recs, g->units, g->ubase, g->scantmp, g->mail.get(), s, g->ext));
         VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
-        VX_TRY(setup_finish(ntri, g->ubase, g->btri, g->mail, s, &U));
+        VX_TRY(setup_finish(ntri, g->ubase, g->btri, g->mail.get(), s, &U));
     }
     if (U == 0) {  // (e.g. a word shard whose z slab holds no triangle): nothing will write the mask
         if (tiled) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
@@ -1471,10 +1487,9 @@ vx_status vx_voxelize(const vx_mesh* mesh, float vs, vx_grid_kind kind, const vx
     if (kind != VX_GRID_BOOL && kind != VX_GRID_AABBSTRUCT && kind != VX_GRID_VEC) return fail(VX_ERR_INVALID_ARG, "unknown grid kind");
     vx_grid* g = new vx_grid();
     g->kind = kind;
-    g->set_dev(mesh->device);
+    g->device = mesh->device;
     const vx_status s = vx_voxelize_into(mesh, vs, opts, g);
     if (s != VX_OK) {
-        g->release_all();
         delete g;
         return s;
     }
@@ -1564,7 +1579,7 @@ vx_status vx_multi_create(const vx_mesh* mesh, const int* devices, int nd, vx_gr
         if (s == VX_OK) {
             vx_grid* g = new vx_grid();
             g->kind = kind;
-            g->set_dev(devices[k]);
+            g->device = devices[k];
             m->grids[(size_t)k] = g;
         }
     }
@@ -1658,9 +1673,7 @@ vx_status vx_multi_voxelize(vx_multi* m, float vs, const vx_voxelize_opts* opts,
         DeviceGuard dg(gd->device);
         if (want_mat && nd > 1) {
             // gather the shards' ids in shard order (a destination's own ids move to their place first: a copy within the device)
-            DevBuf all;
-            all.dev = gd->device;
-            all.stream = gd->stream;
+            DevBuf all{gd};
             VX_HIP(all.ensure((size_t)total_ids * 2 + 16));
             uint64_t off = 0;
             for (int k = 0; k < nd; ++k) {
@@ -1673,7 +1686,7 @@ vx_status vx_multi_voxelize(vx_multi* m, float vs, const vx_voxelize_opts* opts,
             }
             VX_HIP(hipStreamSynchronize(gd->stream));
             gd->mattmp.release();   // (its first-half scratch is spent; every rank's own ids stay in its matids for the other destinations)
-            gd->mattmp = all;       // (kept so that the next build finds a block of this size)
+            gd->mattmp = std::move(all);  // (kept so that the next build finds a block of this size)
             gd->mat_gathered = true;
             gd->mat_gather_count = total_ids;
         }
@@ -1738,14 +1751,14 @@ vx_status vx_grid_create(vx_grid_kind kind, uint64_t x, uint64_t y, uint64_t z, 
     VX_TRY(need_device(g_device));
     vx_grid* g = new vx_grid();
     g->kind = kind;
-    g->set_dev(g_device);
+    g->device = g_device;
     g->set_stream((hipStream_t)stream);
     const float zero[3] = {0.f, 0.f, 0.f};
     const uint64_t dim[3] = {x, y, z};
     fill_params(g->g, origin ? origin : zero, vs, dim);
     DeviceGuard dg(g->device);
     const vx_status s = init_grid_storage(g);
-    if (s != VX_OK) { g->release_all(); delete g; return s; }
+    if (s != VX_OK) { delete g; return s; }
     *out = g;
     return VX_OK;
 }
@@ -1793,14 +1806,12 @@ vx_status vx_grid_set_voxel(vx_grid* g, uint64_t x, uint64_t y, uint64_t z)
             g->vec_in_bound = false;
         }
         if (need > g->vec.cap) {
-            DevBuf nb;
-            nb.dev = g->device;
-            nb.stream = g->stream;
+            DevBuf nb{g};
             VX_HIP(nb.ensure(need * 2));
             if (g->vec_count) VX_HIP(hipMemcpyAsync(nb.p, g->vec.p, (size_t)g->vec_count * sizeof(vx_aabb), hipMemcpyDeviceToDevice, g->stream));
             VX_HIP(hipStreamSynchronize(g->stream));
             g->vec.release();
-            g->vec = nb;
+            g->vec = std::move(nb);
         }
         VX_HIP(hipMemcpyAsync(g->vec.as<vx_aabb>() + g->vec_count, &b, sizeof(b), hipMemcpyHostToDevice, g->stream));
         VX_HIP(hipStreamSynchronize(g->stream));
@@ -1884,7 +1895,7 @@ vx_status vx_grid_fill_interior(vx_grid* g)
     if (!g) return fail(VX_ERR_INVALID_ARG, "null argument");
     DeviceGuard dg(g->device);
     VX_HIP(g->list_resolve());  // (an emission still to come reads the mask / writes the list this call extends)
-    if (!g->mail) VX_HIP(mail_alloc(&g->mail));
+    if (!g->mail) VX_HIP(mail_alloc(g->mail));
     VX_HIP(ensure_small(g->small));
     uint64_t n = 0;
     const uint32_t* h = nullptr;
@@ -1895,13 +1906,11 @@ vx_status vx_grid_fill_interior(vx_grid* g)
         // setVoxel appends one record per call: the list continues in the grid's own storage, as after vx_grid_set_voxel
         const size_t need = (size_t)(g->vec_count + n + 1) * sizeof(vx_aabb);
         if (g->vec_in_bound || need > g->vec.cap) {
-            DevBuf nb;
-            nb.dev = g->device;
-            nb.stream = g->stream;
+            DevBuf nb{g};
             VX_HIP(nb.ensure(need));
             if (g->vec_count) VX_HIP(hipMemcpyAsync(nb.p, g->vec_ptr(), (size_t)g->vec_count * sizeof(vx_aabb), hipMemcpyDeviceToDevice, g->stream));
             g->vec.release();
-            g->vec = nb;
+            g->vec = std::move(nb);
             g->vec_in_bound = false;
         }
         vx::launch_emit_bool_aabbs(h, g->solid_pre.as<uint32_t>(), g->g, g->vec.as<vx_aabb>() + g->vec_count, n, g->stream);
@@ -2283,15 +2292,11 @@ vx_status vx_grid_aabbs(const vx_grid* gc, vx_aabb* host_out, uint64_t cap, uint
         VX_HIP(hipStreamSynchronize(g->stream));
         return VX_OK;
     }
-    DevBuf tmp;
-    tmp.dev = g->device;
-    tmp.stream = g->stream;
+    DevBuf tmp{g};
     VX_HIP(tmp.ensure((size_t)m * sizeof(vx_aabb)));
     vx::launch_emit_bool_aabbs(g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), g->g, tmp.as<vx_aabb>(), m, g->stream, g->sel_valid ? g->wsel.as<uint32_t>() : nullptr);
-    hipError_t e = hipMemcpyAsync(host_out, tmp.p, (size_t)m * sizeof(vx_aabb), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    tmp.release();
-    VX_HIP(e);
+    VX_HIP(hipMemcpyAsync(host_out, tmp.p, (size_t)m * sizeof(vx_aabb), hipMemcpyDeviceToHost, g->stream));
+    VX_HIP(hipStreamSynchronize(g->stream));
     return VX_OK;
 }
 
@@ -2372,7 +2377,6 @@ void vx_grid_free(vx_grid* g)
 {
     if (!g) return;
     { DeviceGuard dg(g->device); (void)g->list_resolve(/*drop_unqueued=*/true); g->side_release(); (void)hipStreamSynchronize(g->stream); }
-    g->release_all();
     delete g;
 }
 
@@ -2501,11 +2505,11 @@ struct StagedOut {
     void** dev;
 };
 
-// host-buffer variant: stages every non-null array (and at most two `extra` outputs) through pooled device memory on (device, stream),
-// then runs `run(io)` on the staged io
+// host-buffer variant: stages every non-null array (and at most two `extra` outputs) through pooled device memory of `home` (the handle:
+// its device and stream), then runs `run(io)` on the staged io
 extern "C++" {
 template <class Run>
-static vx_status trace_ex_staged(int device, hipStream_t stream, const vx_trace_args* args, Run run, std::initializer_list<StagedOut> extra = {})
+static vx_status trace_ex_staged(const Home& home, const vx_trace_args* args, Run run, std::initializer_list<StagedOut> extra = {})
 {
     vx::Camera cam{};
     vx::TraceIO io;
@@ -2514,38 +2518,38 @@ static vx_status trace_ex_staged(int device, hipStream_t stream, const vx_trace_
     const uint64_t n = io.nrays;
     if (!n) return VX_OK;
     if (extra.size() > 2) return fail(VX_ERR_INVALID_ARG, "trace_ex_staged: more than two extra outputs");
-    DevBuf dr, dtm, dt, dp, dn, ds, dx[2];
-    DevBuf* const all[] = {&dr, &dtm, &dt, &dp, &dn, &ds, &dx[0], &dx[1]};
-    for (DevBuf* b : all) { b->dev = device; b->stream = stream; }
-    hipError_t e = hipSuccess;
-    vx_status st = VX_OK;
-    if (io.rays) { e = dr.ensure((size_t)n * 24); if (e == hipSuccess) e = hipMemcpyAsync(dr.p, args->rays, (size_t)n * 24, hipMemcpyHostToDevice, stream); io.rays = dr.as<float>(); }
-    if (e == hipSuccess && io.tmax_per_ray) { e = dtm.ensure((size_t)n * 4); if (e == hipSuccess) e = hipMemcpyAsync(dtm.p, args->tmax_per_ray, (size_t)n * 4, hipMemcpyHostToDevice, stream); io.tmax_per_ray = dtm.as<float>(); }
-    if (e == hipSuccess && args->t) { e = dt.ensure((size_t)n * 4); io.t_out = dt.as<float>(); }
-    if (e == hipSuccess && args->prim) { e = dp.ensure((size_t)n * 4); io.prim_out = dp.as<uint32_t>(); }
-    if (e == hipSuccess && args->normal) { e = dn.ensure((size_t)n * 12); io.normal_out = dn.as<float>(); }
-    if (e == hipSuccess && args->shadowed) { e = ds.ensure((size_t)n); io.shadowed_out = ds.as<uint8_t>(); }
+    hipStream_t stream = home.stream;
+    DevBuf dr{&home}, dtm{&home}, dt{&home}, dp{&home}, dn{&home}, ds{&home}, dx[2] = {DevBuf{&home}, DevBuf{&home}};
+    if (io.rays) {
+        VX_HIP(dr.ensure((size_t)n * 24));
+        VX_HIP(hipMemcpyAsync(dr.p, args->rays, (size_t)n * 24, hipMemcpyHostToDevice, stream));
+        io.rays = dr.as<float>();
+    }
+    if (io.tmax_per_ray) {
+        VX_HIP(dtm.ensure((size_t)n * 4));
+        VX_HIP(hipMemcpyAsync(dtm.p, args->tmax_per_ray, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+        io.tmax_per_ray = dtm.as<float>();
+    }
+    if (args->t) { VX_HIP(dt.ensure((size_t)n * 4)); io.t_out = dt.as<float>(); }
+    if (args->prim) { VX_HIP(dp.ensure((size_t)n * 4)); io.prim_out = dp.as<uint32_t>(); }
+    if (args->normal) { VX_HIP(dn.ensure((size_t)n * 12)); io.normal_out = dn.as<float>(); }
+    if (args->shadowed) { VX_HIP(ds.ensure((size_t)n)); io.shadowed_out = ds.as<uint8_t>(); }
     DevBuf* xb = dx;
     for (const StagedOut& x : extra) {
-        if (e == hipSuccess && x.host) { e = xb->ensure((size_t)n * x.stride + 16); *x.dev = xb->p; }
+        if (x.host) { VX_HIP(xb->ensure((size_t)n * x.stride + 16)); *x.dev = xb->p; }
         ++xb;
     }
-    if (e == hipSuccess) st = run(io);
-    if (e == hipSuccess && st == VX_OK) {
-        if (args->t) e = hipMemcpyAsync(args->t, dt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess && args->prim) e = hipMemcpyAsync(args->prim, dp.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess && args->normal) e = hipMemcpyAsync(args->normal, dn.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess && args->shadowed) e = hipMemcpyAsync(args->shadowed, ds.p, (size_t)n, hipMemcpyDeviceToHost, stream);
-        xb = dx;
-        for (const StagedOut& x : extra) {
-            if (e == hipSuccess && x.host) e = hipMemcpyAsync(x.host, xb->p, (size_t)n * x.stride, hipMemcpyDeviceToHost, stream);
-            ++xb;
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    VX_TRY(run(io));
+    if (args->t) VX_HIP(hipMemcpyAsync(args->t, dt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    if (args->prim) VX_HIP(hipMemcpyAsync(args->prim, dp.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    if (args->normal) VX_HIP(hipMemcpyAsync(args->normal, dn.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
+    if (args->shadowed) VX_HIP(hipMemcpyAsync(args->shadowed, ds.p, (size_t)n, hipMemcpyDeviceToHost, stream));
+    xb = dx;
+    for (const StagedOut& x : extra) {
+        if (x.host) VX_HIP(hipMemcpyAsync(x.host, xb->p, (size_t)n * x.stride, hipMemcpyDeviceToHost, stream));
+        ++xb;
     }
-    for (DevBuf* b : all) b->release();
-    if (st != VX_OK) return st;
-    VX_HIP(e);
+    VX_HIP(hipStreamSynchronize(stream));
     return VX_OK;
 }
 }  // extern "C++"
@@ -2555,7 +2559,7 @@ vx_status vx_trace_ex(const vx_grid* gc, const vx_trace_args* args)
     if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
     vx_grid* g = const_cast<vx_grid*>(gc);
     DeviceGuard dg(g->device);
-    return trace_ex_staged(g->device, g->stream, args, [&](const vx::TraceIO& io) { return trace_common(g, io); });
+    return trace_ex_staged(*g, args, [&](const vx::TraceIO& io) { return trace_common(g, io); });
 }
 
 // ---- multi-hit query (vx_multihit.hip) -----------------------------------------------------------------------------
@@ -2615,39 +2619,32 @@ vx_status vx_trace_multi(const vx_grid* gc, const vx_multihit_args* a)
     DeviceGuard dg(g->device);
     const size_t K = a->max_hits;
     // every non-null array through pooled device memory on the grid's stream, as trace_ex_staged does for one entry per ray
-    DevBuf dr, dtm, dt, dp, dc, dat, dap;
-    DevBuf* const all[] = {&dr, &dtm, &dt, &dp, &dc, &dat, &dap};
-    for (DevBuf* b : all) { b->dev = g->device; b->stream = g->stream; }
-    hipError_t e = hipSuccess;
-    vx_status st = VX_OK;
-    auto upload = [&](DevBuf& b, const void* host, size_t bytes) {
-        if (e == hipSuccess && host) { e = b.ensure(bytes); if (e == hipSuccess) e = hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, g->stream); }
+    DevBuf dr{g}, dtm{g}, dt{g}, dp{g}, dc{g}, dat{g}, dap{g};
+    auto upload = [&](DevBuf& b, const void* host, size_t bytes) -> hipError_t {
+        if (!host) return hipSuccess;
+        const hipError_t e = b.ensure(bytes);
+        return e == hipSuccess ? hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, g->stream) : e;
     };
-    upload(dr, a->base.rays, (size_t)n * 24);
-    upload(dtm, a->base.tmax_per_ray, (size_t)n * 4);
-    upload(dat, a->after_t, (size_t)n * 4);
-    upload(dap, a->after_prim, (size_t)n * 4);
-    if (e == hipSuccess && a->base.t) e = dt.ensure((size_t)n * K * 4);
-    if (e == hipSuccess && a->base.prim) e = dp.ensure((size_t)n * K * 4);
-    if (e == hipSuccess && a->count) e = dc.ensure((size_t)n * 4);
-    if (e == hipSuccess) {
-        if (io.rays) io.rays = dr.as<float>();
-        if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
-        io.t_out = dt.as<float>();
-        io.prim_out = dp.as<uint32_t>();
-        st = multihit_common(g, io, a, dc.as<uint32_t>(), dat.as<float>(), dap.as<uint32_t>());
+    VX_HIP(upload(dr, a->base.rays, (size_t)n * 24));
+    VX_HIP(upload(dtm, a->base.tmax_per_ray, (size_t)n * 4));
+    VX_HIP(upload(dat, a->after_t, (size_t)n * 4));
+    VX_HIP(upload(dap, a->after_prim, (size_t)n * 4));
+    if (a->base.t) VX_HIP(dt.ensure((size_t)n * K * 4));
+    if (a->base.prim) VX_HIP(dp.ensure((size_t)n * K * 4));
+    if (a->count) VX_HIP(dc.ensure((size_t)n * 4));
+    if (io.rays) io.rays = dr.as<float>();
+    if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
+    io.t_out = dt.as<float>();
+    io.prim_out = dp.as<uint32_t>();
+    const vx_status st = multihit_common(g, io, a, dc.as<uint32_t>(), dat.as<float>(), dap.as<uint32_t>());
+    if (st != VX_OK) {
+        (void)hipStreamSynchronize(g->stream);  // the uploads read the caller's arrays
+        return st;
     }
-    if (e == hipSuccess && st == VX_OK) {
-        if (a->base.t) e = hipMemcpyAsync(a->base.t, dt.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess && a->base.prim) e = hipMemcpyAsync(a->base.prim, dp.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess && a->count) e = hipMemcpyAsync(a->count, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    } else if (e == hipSuccess) {
-        e = hipStreamSynchronize(g->stream);  // the uploads read the caller's arrays
-    }
-    for (DevBuf* b : all) b->release();
-    if (st != VX_OK) return st;
-    VX_HIP(e);
+    if (a->base.t) VX_HIP(hipMemcpyAsync(a->base.t, dt.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, g->stream));
+    if (a->base.prim) VX_HIP(hipMemcpyAsync(a->base.prim, dp.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, g->stream));
+    if (a->count) VX_HIP(hipMemcpyAsync(a->count, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream));
+    VX_HIP(hipStreamSynchronize(g->stream));
     return VX_OK;
 }
 
@@ -2690,67 +2687,58 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
     DeviceGuard dg(mesh->device);
     VX_TRY(mesh_to_device(mesh));
     hipStream_t s = (hipStream_t)stream;
-    vx_octree* o = new vx_octree();
+    const Home here(mesh->device, s);  // of the build's scratch: it outlives the octree, which a failed build deletes on its way out
+    std::unique_ptr<vx_octree> o(new vx_octree());
     o->device = mesh->device;
     o->stream = s;
     o->vs = vs;
     o->max_items = max_items;
-    o->items.dev = o->nodebuf.dev = o->camera.dev = o->device;
-    o->items.stream = o->nodebuf.stream = o->camera.stream = s;
-    DevBuf small, recs, ext, units, ubase, btri, scantmp, umask, bhits, hbase, unsorted, sorttmp, ncount, nbase;
-    for (DevBuf* b : {&small, &recs, &ext, &units, &ubase, &btri, &scantmp, &umask, &bhits, &hbase, &unsorted, &sorttmp, &ncount, &nbase}) { b->dev = o->device; b->stream = s; }
-    Mail* mail = nullptr;
-    auto cleanup = [&]() {
-        for (DevBuf* b : {&small, &recs, &ext, &units, &ubase, &btri, &scantmp, &umask, &bhits, &hbase, &unsorted, &sorttmp, &ncount, &nbase}) b->release();
-        if (mail) (void)hipHostFree(mail);
-        mail = nullptr;
-    };
-    auto bail = [&](vx_status st) { cleanup(); o->items.release(); o->free_nodes(true); delete o; return st; };
-#define OCT_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return bail(fail(VX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__))); } while (0)
-#define OCT_TRY(expr) do { vx_status s__ = (expr); if (s__ != VX_OK) return bail(s__); } while (0)
-    OCT_HIP(ensure_small(small));
+    MailPtr mail;
+    DevBuf small{&here}, recs{&here}, ext{&here}, units{&here}, ubase{&here}, btri{&here}, scantmp{&here}, umask{&here}, bhits{&here}, hbase{&here}, unsorted{&here},
+        sorttmp{&here}, ncount{&here}, nbase{&here};
+    VX_HIP(ensure_small(small));
     Small* ds = small.as<Small>();
-    OCT_HIP(mail_alloc(&mail));
+    VX_HIP(mail_alloc(mail));
     Extent ex;
-    OCT_TRY(compute_extent(mesh, vs, ds, mail, s, &ex, /*morton_error=*/true));
+    VX_TRY(compute_extent(mesh, vs, ds, mail.get(), s, &ex, /*morton_error=*/true));
     for (int a = 0; a < 3; ++a) { o->root_min[a] = ex.mn[a]; o->root_max[a] = ex.mx[a]; o->dim[a] = ex.dim[a]; }
     uint64_t maxDim = ex.dim[0] > ex.dim[1] ? ex.dim[0] : ex.dim[1];
     if (ex.dim[2] > maxDim) maxDim = ex.dim[2];
-    if (maxDim == 0) { cleanup(); *out = o; return VX_OK; }  // octTree.hpp:571-574
+    if (maxDim == 0) { *out = o.release(); return VX_OK; }  // octTree.hpp:571-574
     o->bits = (uint32_t)std::ceil(std::log2((double)maxDim));  // :577-578
-    if (o->bits > 21) return bail(fail(VX_ERR_MORTON_BITS, "We support up to 21 bits per axis (max 2^21 voxels per dimension)!"));
+    if (o->bits > 21) return fail(VX_ERR_MORTON_BITS, "We support up to 21 bits per axis (max 2^21 voxels per dimension)!");
     const float root_ext = vs * (float)(1u << o->bits);  // :592
     for (int a = 0; a < 3; ++a) o->root_max[a] = ex.mn[a] + root_ext;
     const uint32_t ntri = (uint32_t)mesh->nt;
-    if (ntri == 0) { cleanup(); *out = o; return VX_OK; }  // :696-699 (returns before buildTree)
+    if (ntri == 0) { *out = o.release(); return VX_OK; }  // :696-699 (returns before buildTree)
     vx::GridParams g;
     fill_params(g, ex.mn, vs, ex.dim);
     uint64_t U = 0;
-    OCT_TRY(setup_launch(mesh, g, /*sat a7: octTree.hpp:762*/ 0, 0, ntri, 0, (uint32_t)ex.dim[2], recs, units, ubase, scantmp, mail, s, ext));
+    VX_TRY(setup_launch(mesh, g, /*sat a7: octTree.hpp:762*/ 0, 0, ntri, 0, (uint32_t)ex.dim[2], recs, units, ubase, scantmp, mail.get(), s, ext));
     const uint32_t* xw = (ex.dim[0] > 65535 || ex.dim[1] > 65535 || ex.dim[2] > 65535) ? ext.as<uint32_t>() : nullptr;
-    OCT_TRY(setup_finish(ntri, ubase, btri, mail, s, &U));
+    VX_TRY(setup_finish(ntri, ubase, btri, mail.get(), s, &U));
     unsigned long long hits = 0;
     if (U) {
-        OCT_HIP(umask.ensure((size_t)(U + 1) * 4));
+        VX_HIP(umask.ensure((size_t)(U + 1) * 4));
         const uint64_t nUB = (U + 63) / 64;  // hits per block of 64 units from the voxelizer, scanned: the items' positions (as for the Vec grid)
-        OCT_HIP(bhits.ensure((size_t)(nUB + 4) * 4));
-        OCT_HIP(hbase.ensure((size_t)(nUB + 4) * 4));
-        OCT_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(nUB), s));
+        VX_HIP(bhits.ensure((size_t)(nUB + 4) * 4));
+        VX_HIP(hbase.ensure((size_t)(nUB + 4) * 4));
+        VX_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(nUB), s));
         vx::launch_voxelize(recs.as<vx::TriRec>(), ubase.as<uint32_t>(), btri.as<uint32_t>(), ntri, g, 0, nullptr, 0, 0, umask.as<uint32_t>(), ds->set_calls, s, xw,
                             bhits.as<uint32_t>());
         vx::launch_scan_u32(bhits.as<uint32_t>(), hbase.as<uint32_t>(), nUB, false, scantmp.p, &mail->hits, s, true, 0, nullptr, advance_scan_gen(scantmp, s));
-        OCT_HIP(hipStreamSynchronize(s));
+        VX_HIP(hipStreamSynchronize(s));
         hits = mail->hits & kMailValue;
-        if (hits >= 0xFFFFFFFFull) return bail(fail(VX_ERR_CAPACITY, "more than 2^32 octree items"));
+        if (hits >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 octree items");
     }
     o->nitems = hits;
     if (hits) {
-        OCT_HIP(unsorted.ensure((size_t)hits * 8));
-        OCT_HIP(o->items.ensure((size_t)hits * 8));
+        VX_HIP(unsorted.ensure((size_t)hits * 8));
+        VX_HIP(o->items.ensure((size_t)hits * 8));
         vx::launch_emit_units(recs.as<vx::TriRec>(), ubase.as<uint32_t>(), btri.as<uint32_t>(), ntri, g, umask.as<uint32_t>(), hbase.as<uint32_t>(),
                               nullptr, unsorted.as<uint64_t>(), s, ~0ull, xw);
         const size_t tb = vx::sort_tmp_bytes(hits);
-        OCT_HIP(sorttmp.ensure(tb));
+        VX_HIP(sorttmp.ensure(tb));
         // octTree.hpp:363; the sort ping-pongs between the two buffers: whichever holds the result becomes the octree's item list
         if (vx::launch_sort_u64(unsorted.as<uint64_t>(), o->items.as<uint64_t>(), hits, o->bits ? (int)(3 * o->bits) : 1, sorttmp.p, tb, s) == 0)
             std::swap(unsorted, o->items);
@@ -2759,28 +2747,25 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
     if (hits && max_items <= vx::kOctDirectMaxItems) {
         // direct form (vx_octree.hip): nodes starting at every item position -> scan -> start / count / links; one wait for the node count
         const uint32_t ni = (uint32_t)hits;
-        OCT_HIP(ncount.ensure((size_t)ni + 16));
-        OCT_HIP(nbase.ensure(((size_t)ni + 2) * 4));
-        OCT_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(ni), s));
+        VX_HIP(ncount.ensure((size_t)ni + 16));
+        VX_HIP(nbase.ensure(((size_t)ni + 2) * 4));
+        VX_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(ni), s));
         vx::launch_oct_depths(o->items.as<uint64_t>(), ni, o->bits, (uint32_t)max_items, ncount.as<uint8_t>(), s);
         vx::launch_scan_u8(ncount.as<uint8_t>(), nbase.as<uint32_t>(), ni, scantmp.p, &mail->occupied, s, 0, advance_scan_gen(scantmp, s));
-        OCT_HIP(hipStreamSynchronize(s));
+        VX_HIP(hipStreamSynchronize(s));
         const unsigned long long nn = mail->occupied & kMailValue;
-        if (nn == 0 || nn >= 0xFFFFFFFFull) return bail(fail(VX_ERR_CAPACITY, "more than 2^32 octree nodes"));
-        OCT_HIP(o->nodebuf.ensure((size_t)nn * sizeof(vx_octree_node)));
+        if (nn == 0 || nn >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 octree nodes");
+        VX_HIP(o->nodebuf.ensure((size_t)nn * sizeof(vx_octree_node)));
         o->dnodes = o->nodebuf.as<vx_octree_node>();
-        OCT_HIP(hipMemsetAsync(o->dnodes, 0xFF, (size_t)nn * sizeof(vx_octree_node), s));  // children = 0xFFFFFFFF (none)
+        VX_HIP(hipMemsetAsync(o->dnodes, 0xFF, (size_t)nn * sizeof(vx_octree_node), s));  // children = 0xFFFFFFFF (none)
         vx::launch_oct_nodes(o->items.as<uint64_t>(), ni, o->bits, nbase.as<uint32_t>(), o->dnodes, s);
-        OCT_HIP(hipStreamSynchronize(s));
+        VX_HIP(hipStreamSynchronize(s));
         o->nnodes = nn;
     } else {
         // level by level: breadth-first expansion + pre-order renumbering (any max_items; also the empty item list's lone root)
-        OCT_HIP(vx::build_octree_nodes(o->items.as<uint64_t>(), (uint32_t)hits, o->bits, max_items, &o->dnodes, &o->nnodes, s));
+        VX_HIP(vx::build_octree_nodes(o->items.as<uint64_t>(), (uint32_t)hits, o->bits, max_items, &o->dnodes, &o->nnodes, s));
     }
-    cleanup();
-#undef OCT_HIP
-#undef OCT_TRY
-    *out = o;
+    *out = o.release();
     return VX_OK;
 }
 
@@ -2839,15 +2824,11 @@ vx_status vx_octree_aabbs(const vx_octree* o, vx_aabb* host_out, uint64_t cap, u
     const uint64_t m = cap < n ? cap : n;
     if (!m || !host_out) return VX_OK;
     DeviceGuard dg(o->device);
-    DevBuf tmp;
-    tmp.dev = o->device;
-    tmp.stream = o->stream;
+    DevBuf tmp{o};
     VX_HIP(tmp.ensure((size_t)m * sizeof(vx_aabb)));
     vx::launch_emit_morton_aabbs(o->items.as<uint64_t>(), m, o->root_min, o->vs, tmp.as<vx_aabb>(), o->stream);
-    hipError_t e = hipMemcpyAsync(host_out, tmp.p, (size_t)m * sizeof(vx_aabb), hipMemcpyDeviceToHost, o->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(o->stream);
-    tmp.release();
-    VX_HIP(e);
+    VX_HIP(hipMemcpyAsync(host_out, tmp.p, (size_t)m * sizeof(vx_aabb), hipMemcpyDeviceToHost, o->stream));
+    VX_HIP(hipStreamSynchronize(o->stream));
     return VX_OK;
 }
 
@@ -2878,7 +2859,7 @@ vx_status vx_octree_trace_ex(const vx_octree* oc, const vx_trace_args* args)
     if (!oc) return fail(VX_ERR_INVALID_ARG, "null argument");
     vx_octree* o = const_cast<vx_octree*>(oc);
     DeviceGuard dg(o->device);
-    return trace_ex_staged(o->device, o->stream, args, [&](const vx::TraceIO& io) { return octree_trace_common(o, io); });
+    return trace_ex_staged(*o, args, [&](const vx::TraceIO& io) { return octree_trace_common(o, io); });
 }
 
 vx_status vx_octree_trace(const vx_octree* oc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim,
@@ -2894,17 +2875,13 @@ void vx_octree_free(vx_octree* o)
     {   // vx_octree_aabbs_device is asynchronous: nothing of this octree may still be in flight when its memory goes back
         DeviceGuard dg(o->device);
         (void)hipStreamSynchronize(o->stream);
-        o->items.release(/*in_flight=*/false);
-        o->free_nodes(/*in_flight=*/false);
-        o->camera.release(/*in_flight=*/false);
+        o->drained = true;
+        delete o;
     }
-    delete o;
 }
 
 // ---- triangle BVH: the reference's triangle BLAS (hello_vulkan.cpp:596-635) under raytrace.rchit (vx_bvh.hip) -------------------------
-struct vx_bvh {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vx_bvh : Home {
     uint32_t max_leaf = VX_BVH_DEFAULT_LEAF;
     uint64_t ntri = 0, nnodes = 0;
     uint32_t height = 0;
@@ -2912,9 +2889,10 @@ struct vx_bvh {
     float coord_max = 0.f;  // the largest |coordinate| below the root and ...
     float extent = 0.f;     // ... the root box's largest side: the traversal's box widening is relative to these
     uint32_t nill = 0;      // ill-conditioned triangles (vx_bvh.hip): tested by every ray
-    DevBuf nodes, tris, ill;  // the BVH itself
-    DevBuf keys_a, keys_b, sorttmp, child, parent, range, arrived, kbox, alive, newidx, scantmp, small, camera;  // build scratch, kept for rebuilds
-    DevBuf* all[16] = {&nodes, &tris, &ill, &keys_a, &keys_b, &sorttmp, &child, &parent, &range, &arrived, &kbox, &alive, &newidx, &scantmp, &small, &camera};
+    DevBuf nodes{this}, tris{this}, ill{this};  // the BVH itself
+    // build scratch, kept for rebuilds
+    DevBuf keys_a{this}, keys_b{this}, sorttmp{this}, child{this}, parent{this}, range{this}, arrived{this}, kbox{this}, alive{this}, newidx{this}, scantmp{this}, small{this},
+        camera{this};
 };
 
 namespace {
@@ -3000,7 +2978,6 @@ vx_status vx_bvh_build(const vx_mesh* mesh_c, uint32_t max_leaf, void* stream, v
     b->device = mesh->device;
     b->stream = (hipStream_t)stream;
     b->max_leaf = max_leaf ? max_leaf : VX_BVH_DEFAULT_LEAF;
-    for (DevBuf* x : b->all) { x->dev = b->device; x->stream = b->stream; }
     const vx_status st = bvh_build_impl(mesh, b);
     if (st != VX_OK) {
         const std::string e = g_err;
@@ -3096,7 +3073,7 @@ vx_status vx_bvh_trace_ex(const vx_bvh* bc, const vx_bvh_trace_args* args)
     vx::TraceIO io;
     VX_TRY(bvh_args_to_io(args, &cam, &io));
     void* bary = nullptr;  // the staged array (null when args->bary is)
-    return trace_ex_staged(b->device, b->stream, &args->base, [&](const vx::TraceIO& sio) { return bvh_trace_common(b, sio, (float*)bary); },
+    return trace_ex_staged(*b, &args->base, [&](const vx::TraceIO& sio) { return bvh_trace_common(b, sio, (float*)bary); },
                            {{args->bary, 8, &bary}});
 }
 
@@ -3117,21 +3094,19 @@ void vx_bvh_free(vx_bvh* b)
     {
         DeviceGuard dg(b->device);
         (void)hipStreamSynchronize(b->stream);
-        for (DevBuf* x : b->all) x->release(/*in_flight=*/false);
+        b->drained = true;
+        delete b;
     }
-    delete b;
 }
 
 // ---- instanced scenes: the reference's TLAS (createTopLevelAS, hello_vulkan.cpp:760-790) over vx_bvh BLAS (vx_tlas.hip) --------------
-struct vx_tlas {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vx_tlas : Home {
     std::vector<vx_bvh*> blas;            // borrowed
     std::vector<vx::TlasBlas> tab;        // the table as last written to the device
     uint64_t n = 0;
     uint32_t levels = 1;                  // LDS stack entries of k_tlas_trace
-    DevBuf dinst, xf, w2o, iblas, ibox, keys_a, keys_b, sorttmp, child, parent, range, arrived, nodes, hgt, small, dtab, camera;
-    DevBuf* all[17] = {&dinst, &xf, &w2o, &iblas, &ibox, &keys_a, &keys_b, &sorttmp, &child, &parent, &range, &arrived, &nodes, &hgt, &small, &dtab, &camera};
+    DevBuf dinst{this}, xf{this}, w2o{this}, iblas{this}, ibox{this}, keys_a{this}, keys_b{this}, sorttmp{this}, child{this}, parent{this}, range{this}, arrived{this},
+        nodes{this}, hgt{this}, small{this}, dtab{this}, camera{this};
     // host staging of vx_tlas_update: two pinned buffers used in turn, so that an update waits (on the host) only for the copy out of
     // the buffer it reuses, the one of the update before the previous one
     vx_instance* pinned[2] = {nullptr, nullptr};
@@ -3310,7 +3285,6 @@ vx_status vx_tlas_build(const vx_bvh* const* blas, uint32_t num_blas, const vx_i
     t->device = dev;
     t->stream = (hipStream_t)stream;
     for (uint32_t k = 0; k < num_blas; ++k) t->blas.push_back(const_cast<vx_bvh*>(blas[k]));
-    for (DevBuf* x : t->all) { x->dev = t->device; x->stream = t->stream; }
     DeviceGuard dg(t->device);
     hipError_t e = hipEventCreateWithFlags(&t->ev_src, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev_end, hipEventDisableTiming);
@@ -3397,7 +3371,7 @@ vx_status vx_tlas_trace_ex(const vx_tlas* tc, const vx_tlas_trace_args* args)
     vx::TraceIO io;
     VX_TRY(tlas_args_to_io(args, &cam, &io));
     void *bary = nullptr, *inst = nullptr;  // the staged arrays (null when the argument is)
-    return trace_ex_staged(t->device, t->stream, &args->base, [&](const vx::TraceIO& sio) { return tlas_trace_common(t, sio, (float*)bary, (uint32_t*)inst); },
+    return trace_ex_staged(*t, &args->base, [&](const vx::TraceIO& sio) { return tlas_trace_common(t, sio, (float*)bary, (uint32_t*)inst); },
                            {{args->bary, 8, &bary}, {args->instance, 4, &inst}});
 }
 
@@ -3419,34 +3393,31 @@ void vx_tlas_free(vx_tlas* t)
     {
         DeviceGuard dg(t->device);
         (void)hipStreamSynchronize(t->stream);
-        for (DevBuf* x : t->all) x->release(/*in_flight=*/false);
+        t->drained = true;
         for (vx_instance* p : t->pinned)
             if (p) (void)hipHostFree(p);
         for (hipEvent_t ev : {t->ev_src, t->ev_end, t->ev_staged[0], t->ev_staged[1]})
             if (ev) (void)hipEventDestroy(ev);
+        delete t;
     }
-    delete t;
 }
 
 // ---- frames: the reference's per-frame raytrace dispatch as one asynchronous sequence on the scene's stream (vx_render.hip) ------------
 // camera block -> primary traversals (voxels, mesh) -> k_render_shadow_rays -> shadow traversals (voxels, mesh) -> k_render_shade.  The
 // scene owns every buffer the sequence touches, the walk's work counters included, so a frame never shares scratch with a trace the user
 // runs on a source's own stream.
-struct vx_render_scene {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vx_render_scene : Home {
     vx_grid* grid = nullptr;
     vx_octree* octree = nullptr;
     vx_bvh* bvh = nullptr;
     vx_mesh* mesh = nullptr;
     vx_tlas* tlas = nullptr;              // instanced scenes (vx_render_create_tlas): the TLAS and one mesh per BLAS
     std::vector<vx_mesh*> meshes;
-    DevBuf camera, counters, idxtmp, vt, vprim, vnrm, mt, mprim, mnrm, mbary, srays, sdist, stmax, sv, sm, vmat, mmat, mids, rgba, kind, shad, minst, imesh;
+    DevBuf camera{this}, counters{this}, idxtmp{this}, vt{this}, vprim{this}, vnrm{this}, mt{this}, mprim{this}, mnrm{this}, mbary{this}, srays{this}, sdist{this},
+        stmax{this}, sv{this}, sm{this}, vmat{this}, mmat{this}, mids{this}, rgba{this}, kind{this}, shad{this}, minst{this}, imesh{this};
     // attribute shading: per-mesh records, corner normals / uvs, material slots, texture records and texels of every mesh (concatenated), the
     // sRGB table, and the per-pixel normal scratch
-    DevBuf amesh, anrm, auv, aslot, atex, texels, srgb, nbuf;
-    DevBuf* all[31] = {&camera, &counters, &idxtmp, &vt, &vprim, &vnrm, &mt, &mprim, &mnrm, &mbary, &srays, &sdist, &stmax, &sv, &sm, &vmat, &mmat, &mids, &rgba, &kind, &shad, &minst, &imesh,
-                       &amesh, &anrm, &auv, &aslot, &atex, &texels, &srgb, &nbuf};
+    DevBuf amesh{this}, anrm{this}, auv{this}, aslot{this}, atex{this}, texels{this}, srgb{this}, nbuf{this};
     uint32_t shading = 0;       // vx_render_set_shading flags
     int phase = 0;              // which of the two walk counters the next k_walk launch draws from (launch_trace)
     uint64_t nvmat = 0, nmmat = 0;
@@ -3860,30 +3831,27 @@ vx_status vx_render_create_tlas(const vx_render_tlas_desc* desc, vx_render_scene
 }
 
 namespace {
-vx_status render_create_common(vx_render_scene* s, vx_render_scene** out)
+struct RenderFree {
+    void operator()(vx_render_scene* s) const { vx_render_free(s); }
+};
+
+vx_status render_create_common(vx_render_scene* fresh, vx_render_scene** out)
 {
-    const vx_status cs = render_sources_check(s);
-    if (cs != VX_OK) { delete s; return cs; }
-    s->device = s->grid ? s->grid->device : (s->octree ? s->octree->device : s->tlas->device);
-    for (DevBuf* x : s->all) { x->dev = s->device; x->stream = s->stream; }
-    auto bail = [&](vx_status st) {
-        const std::string e = g_err;
-        vx_render_free(s);
-        return fail(st, e);
-    };
+    const vx_status cs = render_sources_check(fresh);
+    if (cs != VX_OK) { delete fresh; return cs; }
+    fresh->device = fresh->grid ? fresh->grid->device : (fresh->octree ? fresh->octree->device : fresh->tlas->device);
+    std::unique_ptr<vx_render_scene, RenderFree> s(fresh);  // a failure below frees what the scene holds by then
     DeviceGuard dg(s->device);
-    if (s->mesh) { const vx_status ms = mesh_to_device(s->mesh); if (ms != VX_OK) return bail(ms); }
-    for (vx_mesh* m : s->meshes) { const vx_status ms = mesh_to_device(m); if (ms != VX_OK) return bail(ms); }
-    hipError_t e = s->camera.ensure(sizeof(vx::Camera));
-    if (e == hipSuccess) e = s->counters.ensure(4 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(s->counters.p, 0, 4 * sizeof(unsigned long long), s->stream);  // the walk's counters start at zero
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&s->ev_src[k], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_end, hipEventDisableTiming);
-    if (e != hipSuccess) return bail(fail(VX_ERR_HIP, std::string("vx_render_create: ") + hipGetErrorString(e)));
-    vx_status ms = render_upload_materials(s);
-    if (ms == VX_OK) ms = render_upload_attributes(s);
-    if (ms != VX_OK) return bail(ms);
-    *out = s;
+    if (s->mesh) VX_TRY(mesh_to_device(s->mesh));
+    for (vx_mesh* m : s->meshes) VX_TRY(mesh_to_device(m));
+    VX_HIP(s->camera.ensure(sizeof(vx::Camera)));
+    VX_HIP(s->counters.ensure(4 * sizeof(unsigned long long)));
+    VX_HIP(hipMemsetAsync(s->counters.p, 0, 4 * sizeof(unsigned long long), s->stream));  // the walk's counters start at zero
+    for (int k = 0; k < 2; ++k) VX_HIP(hipEventCreateWithFlags(&s->ev_src[k], hipEventDisableTiming));
+    VX_HIP(hipEventCreateWithFlags(&s->ev_end, hipEventDisableTiming));
+    VX_TRY(render_upload_materials(s.get()));
+    VX_TRY(render_upload_attributes(s.get()));
+    *out = s.release();
     return VX_OK;
 }
 }  // namespace
@@ -3945,12 +3913,12 @@ void vx_render_free(vx_render_scene* s)
     {
         DeviceGuard dg(s->device);
         (void)hipStreamSynchronize(s->stream);
-        for (DevBuf* x : s->all) x->release(/*in_flight=*/false);
+        s->drained = true;
         for (hipEvent_t& ev : s->ev_src)
             if (ev) (void)hipEventDestroy(ev);
         if (s->ev_end) (void)hipEventDestroy(s->ev_end);
+        delete s;
     }
-    delete s;
 }
 
 // ---- test aid: the octree's item sort on a host array ----------------------------------------------------------
@@ -3962,21 +3930,16 @@ vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits)
     if (!n) return VX_OK;
     VX_TRY(need_device(g_device));
     DeviceGuard dg(g_device);
-    DevBuf a, b, tmp;
-    for (DevBuf* x : {&a, &b, &tmp}) x->dev = g_device;
-    auto rel = [&]() { for (DevBuf* x : {&a, &b, &tmp}) x->release(false); };
-    hipError_t e = a.ensure((size_t)n * 8);
-    if (e == hipSuccess) e = b.ensure((size_t)n * 8);
+    const Home here(g_device, nullptr, /*drained=*/true);  // (every step below waits for the device)
+    DevBuf a{&here}, b{&here}, tmp{&here};
+    VX_HIP(a.ensure((size_t)n * 8));
+    VX_HIP(b.ensure((size_t)n * 8));
     const size_t tb = vx::sort_tmp_bytes(n);
-    if (e == hipSuccess) e = tmp.ensure(tb);
-    if (e == hipSuccess) e = hipMemcpy(a.p, host_keys, (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const int where = vx::launch_sort_u64(a.as<uint64_t>(), b.as<uint64_t>(), n, bits, tmp.p, tb, nullptr);
-        e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess) e = hipMemcpy(host_keys, where == 0 ? a.p : b.p, (size_t)n * 8, hipMemcpyDeviceToHost);
-    }
-    rel();
-    VX_HIP(e);
+    VX_HIP(tmp.ensure(tb));
+    VX_HIP(hipMemcpy(a.p, host_keys, (size_t)n * 8, hipMemcpyHostToDevice));
+    const int where = vx::launch_sort_u64(a.as<uint64_t>(), b.as<uint64_t>(), n, bits, tmp.p, tb, nullptr);
+    VX_HIP(hipStreamSynchronize(nullptr));
+    VX_HIP(hipMemcpy(host_keys, where == 0 ? a.p : b.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return VX_OK;
 }
 
@@ -4007,34 +3970,31 @@ vx_status vx_scan_u32(const vx_scan_args* a)
     VX_TRY(need_device(g_device));
     DeviceGuard dg(g_device);
     hipStream_t s = nullptr;
-    DevBuf din, dout, dsel, dg16, tmp, dtot;
-    for (DevBuf* x : {&din, &dout, &dsel, &dg16, &tmp, &dtot}) x->dev = g_device;
-    auto rel = [&]() { for (DevBuf* x : {&din, &dout, &dsel, &dg16, &tmp, &dtot}) x->release(false); };
+    const Home here(g_device, s, /*drained=*/true);  // (every scan below is waited for before the next step)
+    DevBuf din{&here}, dout{&here}, dsel{&here}, dg16{&here}, tmp{&here}, dtot{&here};
     const uint64_t out_words = a->out_offset + nmax + 1 + VX_SCAN_CANARY;
     const uint64_t sel_cap = a->sel ? a->sel_cap : 0, g16_cap = a->group16 ? a->group16_cap : 0;
     std::vector<uint32_t> canary(std::max<uint64_t>(std::max(out_words, sel_cap), g16_cap), VX_SCAN_CANARY_VALUE);
-    std::vector<unsigned long long> state;
-    hipError_t e = din.ensure((size_t)(a->in_offset + nmax) * esz + 16);
-    if (e == hipSuccess) e = dout.ensure((size_t)out_words * 4);
-    if (e == hipSuccess) e = dsel.ensure((size_t)sel_cap * 4 + 4);
-    if (e == hipSuccess) e = dg16.ensure((size_t)g16_cap * 4 + 4);
-    if (e == hipSuccess) e = dtot.ensure(8);
-    if (e == hipSuccess) e = ensure_scan_tmp(tmp, vx::scan_tmp_bytes(nmax), s);
-    if (e == hipSuccess) state.resize(tmp.cap / sizeof(unsigned long long));
+    VX_HIP(din.ensure((size_t)(a->in_offset + nmax) * esz + 16));
+    VX_HIP(dout.ensure((size_t)out_words * 4));
+    VX_HIP(dsel.ensure((size_t)sel_cap * 4 + 4));
+    VX_HIP(dg16.ensure((size_t)g16_cap * 4 + 4));
+    VX_HIP(dtot.ensure(8));
+    VX_HIP(ensure_scan_tmp(tmp, vx::scan_tmp_bytes(nmax), s));
+    std::vector<unsigned long long> state(tmp.cap / sizeof(unsigned long long));
     tmp.scan_gen = a->gen_start;
     bool zero = true;  // the scratch block is known to be all zero (what ticket-mode and three-pass scans require and leave behind)
     uint64_t ioff = 0, ooff = 0;
-    for (uint32_t k = 0; k < a->nscans && e == hipSuccess; ++k) {
+    for (uint32_t k = 0; k < a->nscans; ++k) {
         const uint64_t n = a->sizes[k];
         uint32_t* out = dout.as<uint32_t>() + a->out_offset;
         uint32_t* sel = sel_cap ? dsel.as<uint32_t>() : nullptr;
         uint32_t* g16 = g16_cap ? dg16.as<uint32_t>() : nullptr;
-        e = hipMemcpy(dout.p, canary.data(), (size_t)out_words * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && sel) e = hipMemcpy(sel, canary.data(), (size_t)sel_cap * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && g16) e = hipMemcpy(g16, canary.data(), (size_t)g16_cap * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && n) e = hipMemcpy((char*)din.p + a->in_offset * esz, (const char*)a->in + ioff * esz, (size_t)n * esz, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(dtot.p, 0, 8);
-        if (e != hipSuccess) break;
+        VX_HIP(hipMemcpy(dout.p, canary.data(), (size_t)out_words * 4, hipMemcpyHostToDevice));
+        if (sel) VX_HIP(hipMemcpy(sel, canary.data(), (size_t)sel_cap * 4, hipMemcpyHostToDevice));
+        if (g16) VX_HIP(hipMemcpy(g16, canary.data(), (size_t)g16_cap * 4, hipMemcpyHostToDevice));
+        if (n) VX_HIP(hipMemcpy((char*)din.p + a->in_offset * esz, (const char*)a->in + ioff * esz, (size_t)n * esz, hipMemcpyHostToDevice));
+        VX_HIP(hipMemset(dtot.p, 0, 8));
         // the path: GEN = the next generation of the block (ticket mode above kScanGenTiles tiles, as for every library caller);
         // TICKET / THREE = no generation, on a block that is all zero (cleared first when an older generation-mode scan left words);
         // AUTO = what the library's own callers do (the next generation, kScanPathAuto)
@@ -4052,13 +4012,12 @@ vx_status vx_scan_u32(const vx_scan_args* a)
                                       a->total_tag, sel, gen, g16, lp);
         }
         const bool gen_mode = one && gen && (n + 1 + 16383) / 16384 <= 512;  // (kScanGenTiles tiles of 16384)
-        e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipMemcpy(a->out + ooff, out, (size_t)(n + 1 + VX_SCAN_CANARY) * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&a->totals[k], dtot.p, 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && sel) e = hipMemcpy(a->sel + (size_t)k * sel_cap, sel, (size_t)sel_cap * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && g16) e = hipMemcpy(a->group16 + (size_t)k * g16_cap, g16, (size_t)g16_cap * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(state.data(), tmp.p, state.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) break;
+        VX_HIP(hipStreamSynchronize(s));
+        VX_HIP(hipMemcpy(a->out + ooff, out, (size_t)(n + 1 + VX_SCAN_CANARY) * 4, hipMemcpyDeviceToHost));
+        VX_HIP(hipMemcpy(&a->totals[k], dtot.p, 8, hipMemcpyDeviceToHost));
+        if (sel) VX_HIP(hipMemcpy(a->sel + (size_t)k * sel_cap, sel, (size_t)sel_cap * 4, hipMemcpyDeviceToHost));
+        if (g16) VX_HIP(hipMemcpy(a->group16 + (size_t)k * g16_cap, g16, (size_t)g16_cap * 4, hipMemcpyDeviceToHost));
+        VX_HIP(hipMemcpy(state.data(), tmp.p, state.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         // clean: a scan without a generation number leaves the block all zero; one with a generation number leaves the ticket and the
         // finished-tiles words zero and state words of its own or an older generation only, never of a later one (which a later scan
         // would take for its own)
@@ -4077,12 +4036,20 @@ vx_status vx_scan_u32(const vx_scan_args* a)
         ioff += n;
         ooff += n + 1 + VX_SCAN_CANARY;
     }
-    rel();
-    VX_HIP(e);
     return VX_OK;
 }
 
 uint64_t vx_device_allocations(void) { return g_pool_requests.load(std::memory_order_relaxed); }
+
+uint64_t vx_device_live_blocks(void)
+{
+    uint64_t n = 0;
+    for (Pool& P : g_pool) {
+        std::lock_guard<std::mutex> lk(P.mu);
+        n += P.live.size();
+    }
+    return n;
+}
 
 // ---- per-kernel timing (bench / profiling aid) ----------------------------------------------------------------
 vx_status vx_profile_enable(int on)

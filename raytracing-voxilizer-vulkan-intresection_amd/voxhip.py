@@ -168,7 +168,7 @@ SYMBOLS = [
     "vx_tlas_build", "vx_tlas_update", "vx_tlas_update_device", "vx_tlas_num_instances", "vx_tlas_num_nodes", "vx_tlas_height", "vx_tlas_bytes",
     "vx_tlas_world_to_object", "vx_tlas_nodes", "vx_tlas_trace_ex_device", "vx_tlas_trace_ex", "vx_tlas_trace", "vx_tlas_free",
     "vx_render_create", "vx_render_create_tlas", "vx_render_refresh", "vx_render_set_shading", "vx_render_frame_device", "vx_render_frame", "vx_render_free",
-    "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read", "vx_device_allocations",
+    "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read", "vx_device_allocations", "vx_device_live_blocks",
     "vx_shard_words", "vx_shard_range",
 ]
 
@@ -334,6 +334,8 @@ def lib():
     L.vx_bvh_num_ill_conditioned.restype = C.c_uint64
     L.vx_device_allocations.argtypes = []
     L.vx_device_allocations.restype = C.c_uint64
+    L.vx_device_live_blocks.argtypes = []
+    L.vx_device_live_blocks.restype = C.c_uint64
     L.vx_bvh_root_bounds.argtypes = [vp, fp, fp]
     L.vx_bvh_nodes.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_bvh_leaf_triangles.argtypes = [vp, vp, C.c_uint64]
@@ -420,6 +422,11 @@ def profile_read():
 def device_allocations():
     """vx_device_allocations: device blocks requested from the library's pool so far (unchanged by a call that allocates nothing)."""
     return int(lib().vx_device_allocations())
+
+
+def device_live_blocks():
+    """vx_device_live_blocks: pool blocks held right now by handles and calls in progress, over all devices."""
+    return int(lib().vx_device_live_blocks())
 
 
 def shard_words(num_words, rank, world):
