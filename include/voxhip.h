@@ -512,6 +512,28 @@ vx_status vx_bvh_trace_ex_device(const vx_bvh* b, const vx_bvh_trace_args* args)
 vx_status vx_bvh_trace_ex(const vx_bvh* b, const vx_bvh_trace_args* args);         /* host pointers (staged), no `hits` */
 vx_status vx_bvh_trace(const vx_bvh* b, const float* host_rays, uint64_t num_rays, float tmin, float tmax,
                        float* host_t /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
+/* Multi-hit query on the mesh: ALL the triangles a ray crosses, in order -- X-ray and thickness images of the mesh itself, depth peeling,
+ * counting wall crossings, the layers behind a transparent surface.  For ray r let A(r) be the set of triangles k that the pinned
+ * Moeller-Trumbore above accepts (u >= 0 && u <= 1 && v >= 0 && u + v <= 1 && t > 0 && t >= tmin && t <= tmax, tmax_per_ray[r] in place of
+ * tmax when given).  A(r) is ordered by (t, prim) ascending: t compared as float, prim the triangle's index in the mesh -- on a closed mesh
+ * a ray through a shared edge meets two triangles at one t, so the prim part decides often.  With the optional per-ray cursor
+ * (after_t[r], after_prim[r]) only the hits STRICTLY after the cursor in that order belong to A(r), for the counts and the lists alike; a
+ * cursor of (-1, anything) is the same as no cursor.  Outputs per ray, K = m.max_hits in 1..VX_MULTIHIT_MAX:
+ *   m.base.t[r*K + j], m.base.prim[r*K + j], bary[(r*K + j)*2 ..]   the j-th element of A(r) and its (u, v) for j < min(K, |A(r)|); the
+ *                                remaining slots are -1.0f, 0xFFFFFFFF and (0, 0);
+ *   m.count[r]                   |A(r)|, the full count even when it exceeds K.
+ * Every output is bit-equal to the brute force over all triangles; without a cursor slot 0 is what vx_bvh_trace_ex returns for t, prim and
+ * bary.  Lists longer than K are paged: call again with the cursor at the last hit of the previous page.
+ * Checks, in this order, each writing nothing: NULL handle or args, K outside 1..VX_MULTIHIT_MAX, exactly one of the two cursor arrays, any
+ * forbidden field of m.base set (any_hit, normal, shadowed, hits, num_hits): VX_ERR_INVALID_ARG.  Zero rays: VX_OK.  A mesh without
+ * triangles: every count 0, every slot padded.  Camera rays (m.base.rays == NULL) as for vx_bvh_trace_ex.  Work runs on the BVH's stream;
+ * a repeated device call requests no device memory (vx_device_allocations unchanged). */
+typedef struct vx_bvh_multihit_args {
+    vx_multihit_args m;  /* as for vx_trace_multi; m.base.t and m.base.prim hold max_hits entries PER RAY (ray-major) */
+    float* bary;         /* 2 f32 per slot (u, v), optional */
+} vx_bvh_multihit_args;
+vx_status vx_bvh_trace_multi_device(const vx_bvh* b, const vx_bvh_multihit_args* a);  /* device pointers, asynchronous on the BVH's stream */
+vx_status vx_bvh_trace_multi(const vx_bvh* b, const vx_bvh_multihit_args* a);         /* host pointers, staged like vx_bvh_trace_ex */
 void vx_bvh_free(vx_bvh* b);
 
 /* ---- instanced triangle scenes: the reference's top-level acceleration structure (createTopLevelAS, hello_vulkan.cpp:760-790) over the
@@ -579,6 +601,23 @@ vx_status vx_tlas_trace_ex_device(const vx_tlas* t, const vx_tlas_trace_args* ar
 vx_status vx_tlas_trace_ex(const vx_tlas* t, const vx_tlas_trace_args* args);         /* host pointers (staged), no `hits` */
 vx_status vx_tlas_trace(const vx_tlas* t, const float* host_rays, uint64_t num_rays, float tmin, float tmax, float* host_t /*NULL ok*/,
                         uint32_t* host_instance /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
+/* Multi-hit query on the instances: the contract of vx_bvh_trace_multi over all active (instance, triangle) pairs.  Each pair is tested on
+ * the instance's object-space ray above (o' = ((w0*ox + w1*oy) + w2*oz) + w3, d' = (w0*dx + w1*dy) + w2*dz per row of W) with the SAME
+ * tmin / tmax.  A(r) is ordered by (t, instance, prim) ascending -- two instances of one BLAS under the same transform tie at every hit, and
+ * the lower instance comes first.  `instance[r*K + j]` is one more output, padded with 0xFFFFFFFF.  The cursor is (after_t[r],
+ * after_instance[r], after_prim[r]): all three arrays or none, else VX_ERR_INVALID_ARG (the third check).  Without a cursor slot 0 is what
+ * vx_tlas_trace_ex returns for t, instance, prim and bary.  Every output is bit-equal to the brute force over every pair, with the one
+ * exception of vx_tlas_trace_ex, verbatim: a BLAS's side list of ill-conditioned triangles is tested only when the ray reaches the
+ * instance's TLAS leaf.  Zero instances, or none active: every count 0, every slot padded.  Streams as for vx_tlas_trace_ex: the call
+ * waits for the work queued on the BLAS streams and makes them wait for it. */
+typedef struct vx_tlas_multihit_args {
+    vx_multihit_args m;
+    float* bary;                     /* 2 f32 per slot (u, v), optional */
+    uint32_t* instance;              /* max_hits entries per ray, optional */
+    const uint32_t* after_instance;  /* the cursor's instance part: with m.after_t and m.after_prim, or none of the three */
+} vx_tlas_multihit_args;
+vx_status vx_tlas_trace_multi_device(const vx_tlas* t, const vx_tlas_multihit_args* a);  /* device pointers, asynchronous on the TLAS's stream */
+vx_status vx_tlas_trace_multi(const vx_tlas* t, const vx_tlas_multihit_args* a);         /* host pointers, staged like vx_tlas_trace_ex */
 void vx_tlas_free(vx_tlas* t);   /* waits for the TLAS's stream */
 
 /* ---- frames: the reference's per-frame dispatch (raytrace.rgen -> raytrace.rint / raytrace2.rchit on the voxels, raytrace.rchit on the

@@ -48,6 +48,9 @@
 //                                       --bench, or --materials with --grid vec
 //   --xray FILE.pgm [--size WxH]        how many voxels each camera ray of --render meets (vx_trace_multi's count), as a binary 16-bit PGM
 //                                       (big-endian, min(count, 65535) per pixel); --camera-dump FILE as for --render
+//   --mesh M.obj --mesh-xray FILE.pgm [--size WxH]
+//                                       the same picture of the triangle model itself: how many triangles of M.obj each camera ray crosses
+//                                       (vx_bvh_trace_multi's count), same file format; --mesh then needs no --render
 //   --components FILE.csv [--connectivity 6|26]
 //                                       the connected components of the grid's occupied cells (vx_grid_component_stats; 6: shared faces, the
 //                                       default; 26: faces, edges and corners) as CSV: a header line, then label,cells,minx,miny,minz,maxx,
@@ -374,23 +377,21 @@ void write_surface(const T& vox, const std::string& file, bool materials)
     std::printf("[voxhip] surface: %zu vertices, %zu triangles\n", xyz.size() / 3, tris.size() / 3);
 }
 
-// --xray: the hit count of every primary ray of the reference camera as a 16-bit PGM
-void write_xray(const vx_grid* grid, const std::string& file, uint32_t W, uint32_t H, const std::string& cameraDump)
+// the reference camera of a WxH picture, written to `cameraDump` when that is given
+void xray_camera(float vi[16], float pi[16], uint32_t W, uint32_t H, const std::string& cameraDump)
 {
-    float vi[16], pi[16];
     camera(vi, pi, (float)W / (float)H);
     if (!cameraDump.empty()) {
         std::ofstream cf(cameraDump, std::ios::binary);
         cf.write(reinterpret_cast<const char*>(vi), 64);
         cf.write(reinterpret_cast<const char*>(pi), 64);
     }
+}
+
+// per-pixel hit counts as a binary 16-bit PGM (min(count, 65535), most significant byte first) and the summary line; `what` names the hits
+void write_counts_pgm(const std::vector<uint32_t>& count, const std::string& file, uint32_t W, uint32_t H, const char* what)
+{
     const size_t n = (size_t)W * H;
-    std::vector<uint32_t> count(n);
-    vx_multihit_args a{};
-    a.base.view_inverse = vi; a.base.proj_inverse = pi; a.base.width = W; a.base.height = H; a.base.tmin = 0.001f; a.base.tmax = 10000.0f;  // rgen:50-51
-    a.max_hits = 1;
-    a.count = count.data();
-    vxdetail::check(vx_trace_multi(grid, &a));
     std::vector<unsigned char> px(2 * n);
     uint32_t most = 0;
     uint64_t sum = 0;
@@ -405,7 +406,35 @@ void write_xray(const vx_grid* grid, const std::string& file, uint32_t W, uint32
     f << "P5\n" << W << ' ' << H << "\n65535\n";
     f.write(reinterpret_cast<const char*>(px.data()), (std::streamsize)px.size());
     if (!f) throw std::runtime_error("cannot write " + file);
-    std::printf("[voxhip] xray %ux%u: %llu voxel crossings, at most %u on a ray\n", W, H, (unsigned long long)sum, most);
+    std::printf("[voxhip] xray %ux%u: %llu %s crossings, at most %u on a ray\n", W, H, (unsigned long long)sum, what, most);
+}
+
+// --xray: the hit count of every primary ray of the reference camera as a 16-bit PGM
+void write_xray(const vx_grid* grid, const std::string& file, uint32_t W, uint32_t H, const std::string& cameraDump)
+{
+    float vi[16], pi[16];
+    xray_camera(vi, pi, W, H, cameraDump);
+    std::vector<uint32_t> count((size_t)W * H);
+    vx_multihit_args a{};
+    a.base.view_inverse = vi; a.base.proj_inverse = pi; a.base.width = W; a.base.height = H; a.base.tmin = 0.001f; a.base.tmax = 10000.0f;  // rgen:50-51
+    a.max_hits = 1;
+    a.count = count.data();
+    vxdetail::check(vx_trace_multi(grid, &a));
+    write_counts_pgm(count, file, W, H, "voxel");
+}
+
+// --mesh-xray: the same picture of the --mesh model itself, the triangles every primary ray crosses (vx_bvh_trace_multi's count)
+void write_mesh_xray(const vx_bvh* bvh, const std::string& file, uint32_t W, uint32_t H, const std::string& cameraDump)
+{
+    float vi[16], pi[16];
+    xray_camera(vi, pi, W, H, cameraDump);
+    std::vector<uint32_t> count((size_t)W * H);
+    vx_bvh_multihit_args a{};
+    a.m.base.view_inverse = vi; a.m.base.proj_inverse = pi; a.m.base.width = W; a.m.base.height = H; a.m.base.tmin = 0.001f; a.m.base.tmax = 10000.0f;  // rgen:50-51
+    a.m.max_hits = 1;
+    a.m.count = count.data();
+    vxdetail::check(vx_bvh_trace_multi(bvh, &a));
+    write_counts_pgm(count, file, W, H, "triangle");
 }
 
 template <class T, bool P>
@@ -483,14 +512,14 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
                      argv[0]);
         return 2;
     }
     const std::string path = argv[1];
     float vs = 0.f;
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
-    std::string grid = "bool", sdfFile, surfaceFile, componentsFile, xrayFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
+    std::string grid = "bool", sdfFile, surfaceFile, componentsFile, xrayFile, meshXrayFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false, attributes = false, solid = false;
     int gpus = 1, connectivity = 6;
@@ -514,12 +543,14 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
         else if (!std::strcmp(argv[i], "--components") && i + 1 < argc) componentsFile = argv[++i];
         else if (!std::strcmp(argv[i], "--xray") && i + 1 < argc) xrayFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--mesh-xray") && i + 1 < argc) meshXrayFile = argv[++i];
         else if (!std::strcmp(argv[i], "--connectivity") && i + 1 < argc) connectivity = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--size") && i + 1 < argc) { if (std::sscanf(argv[++i], "%ux%u", &rw, &rh) != 2) { std::fprintf(stderr, "bad --size\n"); return 2; } }
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
-    if (!meshFile.empty() && renderFile.empty()) { std::fprintf(stderr, "--mesh needs --render: the triangle model only takes part in the picture\n"); return 2; }
+    if (!meshXrayFile.empty() && meshFile.empty()) { std::fprintf(stderr, "--mesh-xray counts the triangles of the --mesh model: it needs --mesh\n"); return 2; }
+    if (!meshFile.empty() && renderFile.empty() && meshXrayFile.empty()) { std::fprintf(stderr, "--mesh needs --render: the triangle model only takes part in the picture\n"); return 2; }
     if (!meshFile.empty() && (benchRuns > 0 || (grid != "bool" && grid != "octree"))) {
         std::fprintf(stderr, "--mesh renders with --grid bool or octree only, and not with --bench\n");
         return 2;
@@ -611,6 +642,7 @@ int main(int argc, char** argv)
                 if (meshScene.instances.empty()) { std::fprintf(stderr, "%s: no instances\n", instFile.c_str()); return 2; }
             }
             std::printf("[voxhip] mesh %s: %zu triangles in the BVH\n", meshFile.c_str(), (size_t)vx_bvh_num_triangles(b));
+            if (!meshXrayFile.empty()) write_mesh_xray(b, meshXrayFile, rw, rh, cameraDump);
         }
         const MeshScene* msp = meshFile.empty() ? nullptr : &meshScene;
         if (benchRuns > 0) {

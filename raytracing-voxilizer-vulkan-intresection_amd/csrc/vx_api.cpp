@@ -3088,6 +3088,129 @@ vx_status vx_bvh_trace(const vx_bvh* bc, const float* host_rays, uint64_t nrays,
     });
 }
 
+// ---- multi-hit queries on the mesh (vx_meshmulti.hip) -------------------------------------------------------------------------------
+// Both structures share one argument form inside the library: vx_tlas_multihit_args, of which vx_bvh_multihit_args is the leading part.
+// The checks of vx_bvh_trace_multi* / vx_tlas_trace_multi*, in the header's order; *io receives the ray batch (nrays == 0: nothing to do)
+static vx_status mesh_multihit_args_to_io(const void* handle, const vx_tlas_multihit_args* a, bool tlas, vx::Camera* cam, vx::TraceIO* io)
+{
+    if (!handle || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    const vx_multihit_args& m = a->m;
+    if (m.max_hits < 1 || m.max_hits > VX_MULTIHIT_MAX) return fail(VX_ERR_INVALID_ARG, "max_hits must be 1..VX_MULTIHIT_MAX");
+    const bool cursor = m.after_t != nullptr;
+    if (cursor != (m.after_prim != nullptr) || (tlas && cursor != (a->after_instance != nullptr)))
+        return fail(VX_ERR_INVALID_ARG, tlas ? "the cursor needs after_t, after_instance and after_prim" : "the cursor needs both after_t and after_prim");
+    const vx_trace_args& b = m.base;
+    if (b.any_hit || b.normal || b.shadowed || b.hits || b.num_hits)
+        return fail(VX_ERR_INVALID_ARG, "any_hit, normal, shadowed, hits and num_hits are not part of the multi-hit query");
+    const bool camera = b.view_inverse && b.proj_inverse && b.width && b.height;
+    if (!b.rays && !camera && !b.num_rays) { io->nrays = 0; return VX_OK; }  // zero rays
+    return args_to_io(&b, cam, io);
+}
+
+static vx::MeshMultiIO mesh_multi_io(const vx_tlas_multihit_args& a)
+{
+    vx::MeshMultiIO m;
+    m.K = a.m.max_hits;
+    m.count = a.m.count;
+    m.bary = a.bary;
+    m.instance = a.instance;
+    m.after_t = a.m.after_t;
+    m.after_instance = a.after_instance;
+    m.after_prim = a.m.after_prim;
+    return m;
+}
+
+// the host variants: every non-null array of `a` through pooled device memory of `home` (the handle: its device and stream), then
+// `run(io, d)` on the staged batch io and the staged copy d of the arguments
+extern "C++" {
+template <class Run>
+static vx_status mesh_multihit_staged(const Home& home, const vx_tlas_multihit_args& a, vx::TraceIO io, Run run)
+{
+    const size_t n = (size_t)io.nrays, K = a.m.max_hits;
+    hipStream_t stream = home.stream;
+    DevBuf dr{&home}, dtm{&home}, dat{&home}, dai{&home}, dap{&home}, dt{&home}, dp{&home}, db{&home}, di{&home}, dc{&home};
+    auto upload = [&](DevBuf& b, const void* host, size_t bytes) -> hipError_t {
+        if (!host) return hipSuccess;
+        const hipError_t e = b.ensure(bytes);
+        return e == hipSuccess ? hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, stream) : e;
+    };
+    VX_HIP(upload(dr, a.m.base.rays, n * 24));
+    VX_HIP(upload(dtm, a.m.base.tmax_per_ray, n * 4));
+    VX_HIP(upload(dat, a.m.after_t, n * 4));
+    VX_HIP(upload(dai, a.after_instance, n * 4));
+    VX_HIP(upload(dap, a.m.after_prim, n * 4));
+    if (a.m.base.t) VX_HIP(dt.ensure(n * K * 4));
+    if (a.m.base.prim) VX_HIP(dp.ensure(n * K * 4));
+    if (a.bary) VX_HIP(db.ensure(n * K * 8));
+    if (a.instance) VX_HIP(di.ensure(n * K * 4));
+    if (a.m.count) VX_HIP(dc.ensure(n * 4));
+    if (io.rays) io.rays = dr.as<float>();
+    if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
+    io.t_out = dt.as<float>();
+    io.prim_out = dp.as<uint32_t>();
+    vx_tlas_multihit_args d = a;
+    d.m.count = dc.as<uint32_t>();
+    d.m.after_t = dat.as<float>();
+    d.after_instance = dai.as<uint32_t>();
+    d.m.after_prim = dap.as<uint32_t>();
+    d.bary = db.as<float>();
+    d.instance = di.as<uint32_t>();
+    const vx_status st = run(io, d);
+    if (st != VX_OK) {
+        (void)hipStreamSynchronize(stream);  // the uploads read the caller's arrays
+        return st;
+    }
+    if (a.m.base.t) VX_HIP(hipMemcpyAsync(a.m.base.t, dt.p, n * K * 4, hipMemcpyDeviceToHost, stream));
+    if (a.m.base.prim) VX_HIP(hipMemcpyAsync(a.m.base.prim, dp.p, n * K * 4, hipMemcpyDeviceToHost, stream));
+    if (a.bary) VX_HIP(hipMemcpyAsync(a.bary, db.p, n * K * 8, hipMemcpyDeviceToHost, stream));
+    if (a.instance) VX_HIP(hipMemcpyAsync(a.instance, di.p, n * K * 4, hipMemcpyDeviceToHost, stream));
+    if (a.m.count) VX_HIP(hipMemcpyAsync(a.m.count, dc.p, n * 4, hipMemcpyDeviceToHost, stream));
+    VX_HIP(hipStreamSynchronize(stream));
+    return VX_OK;
+}
+}  // extern "C++"
+
+// the query on device arrays: io's pointers and those of `a` are device memory
+static vx_status bvh_multihit_common(vx_bvh* b, vx::TraceIO io, const vx_tlas_multihit_args& a)
+{
+    VX_TRY(upload_camera(b->camera, b->stream, io));
+    vx::launch_bvh_multihit(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height,
+                            b->extent, b->coord_max, io, mesh_multi_io(a), b->stream);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+static vx_tlas_multihit_args from_bvh_args(const vx_bvh_multihit_args* a)
+{
+    vx_tlas_multihit_args x{};
+    if (a) { x.m = a->m; x.bary = a->bary; }
+    return x;
+}
+
+vx_status vx_bvh_trace_multi_device(const vx_bvh* bc, const vx_bvh_multihit_args* args)
+{
+    const vx_tlas_multihit_args a = from_bvh_args(args);
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(mesh_multihit_args_to_io(bc, args ? &a : nullptr, false, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    vx_bvh* b = const_cast<vx_bvh*>(bc);
+    DeviceGuard dg(b->device);
+    return bvh_multihit_common(b, io, a);
+}
+
+vx_status vx_bvh_trace_multi(const vx_bvh* bc, const vx_bvh_multihit_args* args)
+{
+    const vx_tlas_multihit_args a = from_bvh_args(args);
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(mesh_multihit_args_to_io(bc, args ? &a : nullptr, false, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    vx_bvh* b = const_cast<vx_bvh*>(bc);
+    DeviceGuard dg(b->device);
+    return mesh_multihit_staged(*b, a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return bvh_multihit_common(b, sio, d); });
+}
+
 void vx_bvh_free(vx_bvh* b)
 {
     if (!b) return;
@@ -3385,6 +3508,38 @@ vx_status vx_tlas_trace(const vx_tlas* tc, const float* host_rays, uint64_t nray
         ta.instance = host_instance;
         return vx_tlas_trace_ex(tc, &ta);
     });
+}
+
+// the multi-hit query on device arrays, under the stream rules of tlas_trace_common
+static vx_status tlas_multihit_common(vx_tlas* t, vx::TraceIO io, const vx_tlas_multihit_args& a)
+{
+    VX_TRY(upload_camera(t->camera, t->stream, io));
+    VX_TRY(tlas_wait_blas(t));
+    vx::launch_tlas_multihit(tlas_dev(t), io, mesh_multi_io(a), t->stream);
+    VX_HIP(hipGetLastError());
+    return tlas_fence_blas(t);
+}
+
+vx_status vx_tlas_trace_multi_device(const vx_tlas* tc, const vx_tlas_multihit_args* a)
+{
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(mesh_multihit_args_to_io(tc, a, true, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    vx_tlas* t = const_cast<vx_tlas*>(tc);
+    DeviceGuard dg(t->device);
+    return tlas_multihit_common(t, io, *a);
+}
+
+vx_status vx_tlas_trace_multi(const vx_tlas* tc, const vx_tlas_multihit_args* a)
+{
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(mesh_multihit_args_to_io(tc, a, true, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    vx_tlas* t = const_cast<vx_tlas*>(tc);
+    DeviceGuard dg(t->device);
+    return mesh_multihit_staged(*t, *a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return tlas_multihit_common(t, sio, d); });
 }
 
 void vx_tlas_free(vx_tlas* t)

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kBuildBlock) void k_bvh_karras(const uint64_t* __re
 }
 
 // kbox: per unified node {min xyz, height, max xyz, pad} (32 B).  tris: the de-indexed triangles in sorted (= leaf) order, 3 float4 each:
-// (v0, triangle index), (v1, 0), (v2, 0).
+// (v0, triangle index), (v1, 1 when the triangle is on the side list, else 0), (v2, 0).
 __global__ __launch_bounds__(kBuildBlock) void k_bvh_bounds(const float* __restrict__ v, const int32_t* __restrict__ idx, uint64_t nv, uint32_t n,
                                                             const uint64_t* __restrict__ keys, const uint32_t* __restrict__ child,
                                                             const uint32_t* __restrict__ parent, uint32_t* __restrict__ arrived, float4* kbox,
@@ -165,16 +165,20 @@ __global__ __launch_bounds__(kBuildBlock) void k_bvh_bounds(const float* __restr
     const uint32_t tri = (uint32_t)(keys[j] & 0xFFFFFFFFull);
     float p[9];
     (void)load_tri(v, idx, nv, tri, p);
-    tris[3ull * j] = make_float4(p[0], p[1], p[2], __uint_as_float(tri));
-    tris[3ull * j + 1] = make_float4(p[3], p[4], p[5], 0.0f);
-    tris[3ull * j + 2] = make_float4(p[6], p[7], p[8], 0.0f);
+    bool on_side_list = false;
     {   // ill-conditioned (sin of the angle at v0 below kIllSin, collinear included): its MT t is rounding noise -> the side list
         const double e1[3] = {(double)p[3] - p[0], (double)p[4] - p[1], (double)p[5] - p[2]};
         const double e2[3] = {(double)p[6] - p[0], (double)p[7] - p[1], (double)p[8] - p[2]};
         const double c0 = e1[1] * e2[2] - e1[2] * e2[1], c1 = e1[2] * e2[0] - e1[0] * e2[2], c2 = e1[0] * e2[1] - e1[1] * e2[0];
         const double l1 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], l2 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
-        if (l1 > 0.0 && l2 > 0.0 && c0 * c0 + c1 * c1 + c2 * c2 <= kIllSin * kIllSin * l1 * l2) ill[atomicAdd(nill, 1u)] = j;
+        on_side_list = l1 > 0.0 && l2 > 0.0 && c0 * c0 + c1 * c1 + c2 * c2 <= kIllSin * kIllSin * l1 * l2;
+        if (on_side_list) ill[atomicAdd(nill, 1u)] = j;
     }
+    // the w of v1 marks a side-listed triangle for the multi-hit kernels (vx_meshmulti.hip), which must count it once; the first-hit
+    // kernels do not read it
+    tris[3ull * j] = make_float4(p[0], p[1], p[2], __uint_as_float(tri));
+    tris[3ull * j + 1] = make_float4(p[3], p[4], p[5], __uint_as_float(on_side_list ? 1u : 0u));
+    tris[3ull * j + 2] = make_float4(p[6], p[7], p[8], 0.0f);
     const uint32_t leaf = n - 1 + j;
     kbox[2ull * leaf] = make_float4(fminf(fminf(p[0], p[3]), p[6]), fminf(fminf(p[1], p[4]), p[7]), fminf(fminf(p[2], p[5]), p[8]), __uint_as_float(0u));
     kbox[2ull * leaf + 1] = make_float4(fmaxf(fmaxf(p[0], p[3]), p[6]), fmaxf(fmaxf(p[1], p[4]), p[7]), fmaxf(fmaxf(p[2], p[5]), p[8]), 0.0f);

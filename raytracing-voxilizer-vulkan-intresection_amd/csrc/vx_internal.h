@@ -189,7 +189,8 @@ void launch_octree_trace(const vx_octree_node* nodes, const uint64_t* items, uin
 
 // Triangle BVH (vx_bvh.hip).  Build, all on `s`: launch_bvh_prep (box6 = ordered-uint bounds of all triangles, initialised to ~0 x3 / 0 x3;
 // *err |= 1 when an index leaves [0, nv); keys = Morton code << 32 | triangle), launch_sort_u64 over 62 bits, launch_bvh_tree (radix tree,
-// bottom-up bounds + heights into kbox (2n-1 records of 32 B), the de-indexed triangles in leaf order into tris (48 B each), the survivors of
+// bottom-up bounds + heights into kbox (2n-1 records of 32 B), the de-indexed triangles in leaf order into tris (48 B each: (v0, triangle
+// index), (v1, 1 when the triangle is on the side list `ill`, else 0), (v2, 0)), the survivors of
 // the collapse into alive[2n-1]), an exclusive scan of alive into newidx, launch_bvh_emit (the node array, 32 B per node, root at 0).
 void launch_bvh_prep(const float* v, const int32_t* idx, uint64_t nv, uint32_t ntri, uint32_t* box6, uint32_t* err, uint64_t* keys, hipStream_t s);
 void launch_bvh_tree(const float* v, const int32_t* idx, uint64_t nv, uint32_t n, const uint64_t* keys, uint32_t max_leaf, uint32_t* child,
@@ -241,6 +242,24 @@ struct TlasDev {
 // First hit per ray on the instances: io as for launch_bvh_trace (prim = triangle index in its mesh, normal = the world geometric normal);
 // bary_out (2 f32 per ray) and inst_out (instance, kNone on a miss) optional.
 void launch_tlas_trace(const TlasDev& T, const TraceIO& io, float* bary_out, uint32_t* inst_out, hipStream_t s);
+float tlas_ray_pad();  // vx_tlas.hip: the per-ray widening of every TLAS box test, per unit of cond_max |o|
+
+// Multi-hit queries on the mesh (vx_meshmulti.hip): per ray the first K (1..32) accepted triangles in (t, prim) order -- (t, instance, prim) on
+// a TLAS -- into io.t_out / io.prim_out / bary / instance (K entries per ray, ray-major, padded with -1 / all ones / (0, 0); all optional)
+// and the number of all accepted triangles into count (optional); after_*: the optional per-ray cursor (after_instance: TLAS only).  io as
+// for launch_bvh_trace; its other outputs are not written.  The remaining arguments are launch_bvh_trace's / launch_tlas_trace's.
+struct MeshMultiIO {
+    uint32_t K = 0;
+    uint32_t* count = nullptr;
+    float* bary = nullptr;
+    uint32_t* instance = nullptr;
+    const float* after_t = nullptr;
+    const uint32_t* after_instance = nullptr;
+    const uint32_t* after_prim = nullptr;
+};
+void launch_bvh_multihit(const float* nodes, const float* tris, const uint32_t* ill, uint32_t nill, uint32_t ntri, uint32_t height, float extent,
+                         float coord_max, const TraceIO& io, const MeshMultiIO& m, hipStream_t s);
+void launch_tlas_multihit(const TlasDev& T, const TraceIO& io, const MeshMultiIO& m, hipStream_t s);
 
 #if defined(__HIPCC__)
 // The unit geometric normal of triangle k (leaf-order position in its BLAS) of instance inst in WORLD space: vertices M*v in the pinned

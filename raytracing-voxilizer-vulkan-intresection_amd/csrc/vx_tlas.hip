@@ -333,6 +333,8 @@ __global__ __launch_bounds__(kTlasBlock) void k_tlas_trace(TlasParams P)
     if (P.io.hits) compact_hit(found, r, prim, tt, P.io.hits, P.io.nhits);  // every lane of the workgroup gets here
 }
 
+float tlas_ray_pad() { return kRayPad; }
+
 uint32_t tlas_height_bound(uint64_t n)
 {
     if (n <= 1) return 0;

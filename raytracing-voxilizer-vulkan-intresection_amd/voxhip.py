@@ -111,6 +111,14 @@ class TlasTraceArgs(C.Structure):
     _fields_ = [("base", TraceArgs), ("bary", C.c_void_p), ("instance", C.c_void_p)]
 
 
+class BvhMultiHitArgs(C.Structure):
+    _fields_ = [("m", MultiHitArgs), ("bary", C.c_void_p)]
+
+
+class TlasMultiHitArgs(C.Structure):
+    _fields_ = [("m", MultiHitArgs), ("bary", C.c_void_p), ("instance", C.c_void_p), ("after_instance", C.c_void_p)]
+
+
 # vx_instance: object-to-world (row-major 3x4), BLAS index, mask (0 = never hit)
 INSTANCE = np.dtype([("transform", np.float32, (12,)), ("blas", np.uint32), ("mask", np.uint32)])
 
@@ -164,9 +172,11 @@ SYMBOLS = [
     "vx_trace_multi", "vx_trace_multi_device",
     "vx_octree_trace", "vx_octree_trace_ex", "vx_octree_trace_ex_device",
     "vx_bvh_build", "vx_bvh_build_into", "vx_bvh_num_triangles", "vx_bvh_num_nodes", "vx_bvh_bytes", "vx_bvh_height", "vx_bvh_num_ill_conditioned", "vx_bvh_root_bounds",
-    "vx_bvh_nodes", "vx_bvh_leaf_triangles", "vx_bvh_nodes_device", "vx_bvh_trace_ex_device", "vx_bvh_trace_ex", "vx_bvh_trace", "vx_bvh_free",
+    "vx_bvh_nodes", "vx_bvh_leaf_triangles", "vx_bvh_nodes_device", "vx_bvh_trace_ex_device", "vx_bvh_trace_ex", "vx_bvh_trace",
+    "vx_bvh_trace_multi", "vx_bvh_trace_multi_device", "vx_bvh_free",
     "vx_tlas_build", "vx_tlas_update", "vx_tlas_update_device", "vx_tlas_num_instances", "vx_tlas_num_nodes", "vx_tlas_height", "vx_tlas_bytes",
-    "vx_tlas_world_to_object", "vx_tlas_nodes", "vx_tlas_trace_ex_device", "vx_tlas_trace_ex", "vx_tlas_trace", "vx_tlas_free",
+    "vx_tlas_world_to_object", "vx_tlas_nodes", "vx_tlas_trace_ex_device", "vx_tlas_trace_ex", "vx_tlas_trace",
+    "vx_tlas_trace_multi", "vx_tlas_trace_multi_device", "vx_tlas_free",
     "vx_render_create", "vx_render_create_tlas", "vx_render_refresh", "vx_render_set_shading", "vx_render_frame_device", "vx_render_frame", "vx_render_free",
     "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read", "vx_device_allocations", "vx_device_live_blocks",
     "vx_shard_words", "vx_shard_range",
@@ -344,6 +354,10 @@ def lib():
     L.vx_bvh_trace_ex.argtypes = [vp, C.POINTER(BvhTraceArgs)]
     L.vx_bvh_trace_ex_device.argtypes = [vp, C.POINTER(BvhTraceArgs)]
     L.vx_bvh_trace.argtypes = [vp, vp, C.c_uint64, C.c_float, C.c_float, vp, vp, u64p]
+    L.vx_bvh_trace_multi.argtypes = [vp, C.POINTER(BvhMultiHitArgs)]
+    L.vx_bvh_trace_multi_device.argtypes = [vp, C.POINTER(BvhMultiHitArgs)]
+    L.vx_tlas_trace_multi.argtypes = [vp, C.POINTER(TlasMultiHitArgs)]
+    L.vx_tlas_trace_multi_device.argtypes = [vp, C.POINTER(TlasMultiHitArgs)]
     L.vx_bvh_free.argtypes = [vp]
     L.vx_bvh_free.restype = None
     L.vx_tlas_build.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, C.POINTER(vp)]
@@ -1124,6 +1138,70 @@ class Octree:
             pass
 
 
+def _mesh_trace_multi(fn, h, a, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want, tlas):
+    """vx_bvh_trace_multi / vx_tlas_trace_multi (a = the matching args structure) on host arrays -> dict of the requested outputs: t (n, K)
+    float32, prim and instance (n, K) uint32, bary (n, K, 2) float32, padded with -1 / 0xFFFFFFFF / (0, 0); count (n,) uint32."""
+    m = a.m
+    keep = []
+    if rays is not None:
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        keep.append(r)
+        m.base.rays, m.base.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
+    else:
+        vi, pi, w, h_ = camera
+        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
+        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
+        keep += [cvi, cpi]
+        m.base.view_inverse, m.base.proj_inverse, m.base.width, m.base.height, n = cvi, cpi, w, h_, w * h_
+    m.base.tmin, m.base.tmax, m.max_hits = np.float32(tmin), np.float32(tmax), int(max_hits)
+    if tmax_per_ray is not None:
+        tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
+        keep.append(tm)
+        m.base.tmax_per_ray = tm.ctypes.data
+    if after is not None:
+        if len(after) != (3 if tlas else 2):
+            raise ValueError("after = (after_t, after_instance, after_prim)" if tlas else "after = (after_t, after_prim)")
+        cur = [np.ascontiguousarray(after[0], dtype=np.float32)] + [np.ascontiguousarray(x, dtype=np.uint32) for x in after[1:]]
+        if any(c.shape != (n,) for c in cur):
+            raise ValueError("the cursor has one entry per ray in each of its arrays")
+        keep += cur
+        m.after_t, m.after_prim = cur[0].ctypes.data, cur[-1].ctypes.data
+        if tlas:
+            a.after_instance = cur[1].ctypes.data
+    k = max(int(max_hits), 0)
+    out = {}
+    if "t" in want:
+        out["t"] = np.zeros((n, k), np.float32); m.base.t = out["t"].ctypes.data
+    if "prim" in want:
+        out["prim"] = np.zeros((n, k), np.uint32); m.base.prim = out["prim"].ctypes.data
+    if "bary" in want:
+        out["bary"] = np.zeros((n, k, 2), np.float32); a.bary = out["bary"].ctypes.data
+    if "instance" in want:
+        if not tlas:
+            raise ValueError("instance is an output of the TLAS only")
+        out["instance"] = np.zeros((n, k), np.uint32); a.instance = out["instance"].ctypes.data
+    if "count" in want:
+        out["count"] = np.zeros(n, np.uint32); m.count = out["count"].ctypes.data
+    _check(fn(h, C.byref(a)))
+    return out
+
+
+def _mesh_trace_multi_device(fn, h, a, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax, tmax_per_ray_ptr, after_t_ptr,
+                             after_prim_ptr, camera):
+    """the device variants: raw device pointers (the caller has set a's own fields), asynchronous on the handle's stream"""
+    m = a.m
+    if camera is not None:
+        vi, pi, w, h_ = camera
+        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
+        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
+        m.base.view_inverse, m.base.proj_inverse, m.base.width, m.base.height = cvi, cpi, w, h_
+    else:
+        m.base.rays, m.base.num_rays = rays_ptr, nrays
+    m.base.tmin, m.base.tmax, m.base.tmax_per_ray, m.max_hits = np.float32(tmin), np.float32(tmax), tmax_per_ray_ptr, int(max_hits)
+    m.base.t, m.base.prim, m.count, m.after_t, m.after_prim = t_ptr, prim_ptr, count_ptr, after_t_ptr, after_prim_ptr
+    _check(fn(h, C.byref(a)))
+
+
 class Bvh:
     """vx_bvh handle: the mesh's triangle BVH (the reference's triangle BLAS)."""
 
@@ -1213,6 +1291,21 @@ class Bvh:
         a.hits, a.num_hits = hits_ptr, nhits_ptr
         ba.bary = bary_ptr
         _check(lib().vx_bvh_trace_ex_device(self.h, C.byref(ba)))
+
+    def trace_multi(self, rays=None, camera=None, max_hits=8, tmin=0.001, tmax=10000.0, tmax_per_ray=None, after=None, want=("t", "prim", "count")):
+        """vx_bvh_trace_multi on host arrays: per ray the first max_hits accepted triangles in (t, prim) order and the number of all of them
+        -> dict of the requested outputs (t, prim, bary, count).  after = (after_t, after_prim): per-ray cursor, only hits strictly behind it
+        are listed and counted."""
+        return _mesh_trace_multi(lib().vx_bvh_trace_multi, self.h, BvhMultiHitArgs(), rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want, False)
+
+    def trace_multi_device(self, rays_ptr, nrays, max_hits, t_ptr=None, prim_ptr=None, count_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None,
+                           after_t_ptr=None, after_prim_ptr=None, camera=None, bary_ptr=None):
+        """vx_bvh_trace_multi_device on raw device pointers, asynchronous on the BVH's stream; t / prim / bary hold max_hits entries per ray.
+        camera = (view_inv, proj_inv, width, height) in place of rays_ptr / nrays."""
+        a = BvhMultiHitArgs()
+        a.bary = bary_ptr
+        _mesh_trace_multi_device(lib().vx_bvh_trace_multi_device, self.h, a, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax,
+                                 tmax_per_ray_ptr, after_t_ptr, after_prim_ptr, camera)
 
     def free(self):
         if self.h:
@@ -1355,6 +1448,20 @@ class Tlas:
         a.hits, a.num_hits = hits_ptr, nhits_ptr
         ta.bary, ta.instance = bary_ptr, instance_ptr
         _check(lib().vx_tlas_trace_ex_device(self.h, C.byref(ta)))
+
+    def trace_multi(self, rays=None, camera=None, max_hits=8, tmin=0.001, tmax=10000.0, tmax_per_ray=None, after=None, want=("t", "instance", "prim", "count")):
+        """vx_tlas_trace_multi on host arrays: per ray the first max_hits accepted (instance, triangle) pairs in (t, instance, prim) order and
+        the number of all of them -> dict of the requested outputs (t, instance, prim, bary, count).  after = (after_t, after_instance,
+        after_prim): per-ray cursor."""
+        return _mesh_trace_multi(lib().vx_tlas_trace_multi, self.h, TlasMultiHitArgs(), rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want, True)
+
+    def trace_multi_device(self, rays_ptr, nrays, max_hits, t_ptr=None, prim_ptr=None, count_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None,
+                           after_t_ptr=None, after_prim_ptr=None, camera=None, bary_ptr=None, instance_ptr=None, after_instance_ptr=None):
+        """vx_tlas_trace_multi_device on raw device pointers, asynchronous on the TLAS's stream."""
+        a = TlasMultiHitArgs()
+        a.bary, a.instance, a.after_instance = bary_ptr, instance_ptr, after_instance_ptr
+        _mesh_trace_multi_device(lib().vx_tlas_trace_multi_device, self.h, a, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax,
+                                 tmax_per_ray_ptr, after_t_ptr, after_prim_ptr, camera)
 
     def free(self):
         if self.h:
