@@ -914,14 +914,22 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
                 ip = ip > R.dimw ? R.dimw : ip;
                 const float t_cur = fmaxf(R.iw * (((R.orgw + (float)ip * g.vs) + (pos ? -R.tol : R.tol)) - R.ow), R.tn);  // the current slab's ta
                 const float t_end = fminf(R.tf, R.best);
-                const bool can = busy && R.lvl != 0 && (t_end - t_cur > kDonateBricks * 8.0f * g.vs * fabsf(R.iw));
+                // A piece walks every slab within `tol` of its interval and every cell within 2 tol of the ray there, so it costs its
+                // own length PLUS about 4 tol |iw| whatever its length: a cut pays only while the interval is longer than that, and the
+                // 4 tol term is what bounds the number of pieces of a ray.  It also keeps the cut representable: |t| <= 4 Mx |iw| (origin
+                // and grid both within Mx of zero, the clip's slack on top), so ulp(t) <= 2^-21 Mx |iw| = tol |iw| / 2, the interval spans at least eight
+                // ulps and t_mid lies strictly inside (t_cur, t_end).  Without the term an interval of ONE ulp at |t| > 6 * 8 * vs * 2^23 |iw| -- origins some
+                // 4 * 10^8 voxel sizes away -- still passed the length test, t_mid rounded onto one of its ends, the receiver got the
+                // whole interval back and donated it again at lvl 2 of the same slab: pieces without end, the ray never retired.  The
+                // strict comparisons state the invariant itself: both halves are shorter than what was cut.
+                const float t_mid = 0.5f * (t_cur + t_end);
+                const bool can = busy && R.lvl != 0 && (t_end - t_cur > (kDonateBricks * 8.0f * g.vs + 4.0f * R.tol) * fabsf(R.iw)) && t_cur < t_mid && t_mid < t_end;
                 const unsigned long long dm = __ballot(can);
                 const unsigned long long im = ~bm;
                 const int ndon = min(__popcll(dm), 64 - nb);
                 if (ndon > 0) {
                     const unsigned long long lt = (1ull << lane) - 1ull;
                     const bool donor = can && __popcll(dm & lt) < ndon;
-                    const float t_mid = 0.5f * (t_cur + t_end);
                     if (donor) {
                         if (slot < 0) {  // first split of this ray: open its merge slot (this piece counts as one)
                             slot = (int)threadIdx.x;
