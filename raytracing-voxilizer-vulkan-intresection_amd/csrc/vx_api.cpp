@@ -211,6 +211,7 @@ struct Small {
     unsigned long long bbox_state[8];  // K1's self-cleaning reduction state (initialised once, see ensure_small)
     vx::DevGrid dgrid;                 // origin + dims as K1 derives them, for kernels queued before the host has seen the bbox
     unsigned long long set_calls[vx::kCallCounters * 8];  // 64 counters on lines of their own (k_voxelize), summed by sync_counts
+    unsigned long long units64;        // the unit scan's tagged total where the voxelizer is queued before the host has seen it (voxelize_build)
     unsigned long long nhits;
     unsigned long long trace_counters[4];
     uint32_t solid_flags[2 * 32];      // one word per round of a solid fill: two halves, batches alternate between them
@@ -225,6 +226,7 @@ struct Mail {
     unsigned long long solid_rounds, interior;  // solid fill: changed rounds of the last batch, |H|
     unsigned long long surf_tris, surf_verts;   // surface mesh: T and V
     unsigned long long cc_count;                // connected components: K
+    unsigned long long bbox_tag;                // the build's tag once bbox is complete (k_bbox), for a host that polls for the bbox alone
 };
 
 // Totals may arrive tagged with the build's sequence number in bits 48..63 (see launch_scan_u32): the host then polls the word
@@ -446,6 +448,7 @@ struct vx_grid : Home {
     MailPtr mail;  // (ahead of the buffers: freed after them)
     DevBuf words{this}, twords{this} /*tiled build mask (launch_voxelize)*/, cwords{this}, c2words{this}, bricks{this}, idxtmp{this}, ttmp{this}, camera{this}, wprefix{this};
     DevBuf wsel{this} /*word of every 1024th occupied voxel (prefix scan)*/, wp16{this} /*every 16th entry of wprefix, dense (prefix scan)*/, recs{this};
+    DevBuf lcnt{this} /*set bits per 16-word line of the bitmask (the brick kernel of a whole Vec build): wp16 is their scan*/;
     DevBuf ext{this} /*high bits of the candidate ranges*/, units{this}, ubase{this}, btri{this}, umask{this}, bhits{this} /*hits per block of 64 units*/;
     DevBuf hbase{this} /*their exclusive scan*/, scantmp{this}, small{this}, vec{this}, matids{this}, mattmp{this};
     // solid voxelization (vx_solid.hip): padded mask, exterior, H in the reference's layout (padded rows only) and the word prefix over H
@@ -474,6 +477,9 @@ struct vx_grid : Home {
     bool mat_gathered = false;             // multi-GPU build: the ids of ALL shards, gathered in shard order, live in mattmp
     uint64_t mat_gather_count = 0;
     bool coarse_valid = false, prefix_valid = false /*word_prefix queued or done*/, occupied_known = false, counts_valid = true;
+    // wp16 and the occupied count queued or done WITHOUT the word prefix: scanned from the brick kernel's line counts (p16_launch).  All a ray
+    // batch's rank pass reads; whoever indexes wprefix itself builds it on demand (prefix_launch / ensure_prefix)
+    bool p16_valid = false;
     bool last_tiled = false;  // the previous build on this handle went through the tiled build mask (twords)
     uint64_t occupied = 0, set_calls = 0, host_set_calls = 0;
     uint64_t vec_count = 0;
@@ -708,7 +714,8 @@ constexpr uint64_t kMaxVoxels = 1ull << 37;  // 16 GiB of bitmask
 vx_status setup_launch(const vx_mesh* m, const vx::GridParams& g, int sat, uint64_t tb, uint32_t ntri, uint32_t zlo, uint32_t zhi, DevBuf& recs,
                        DevBuf& units, DevBuf& ubase, DevBuf& scantmp, Mail* mail, hipStream_t s, DevBuf& ext, const vx::DevGrid* dgrid = nullptr,
                        unsigned long long mail_tag = 0, bool* tagged = nullptr, void* clear = nullptr, uint64_t clear_bytes = 0,
-                       uint64_t shard_wb = 0, uint64_t shard_we = 0, uint32_t shard_rank = 0, uint32_t shard_world = 0)
+                       uint64_t shard_wb = 0, uint64_t shard_we = 0, uint32_t shard_rank = 0, uint32_t shard_world = 0,
+                       unsigned long long* units_total = nullptr /*where the unit total goes instead of the mailbox (device memory)*/)
 {
     VX_HIP(recs.ensure((size_t)ntri * sizeof(vx::TriRec) + 64));
     VX_HIP(ext.ensure(((size_t)ntri + 1) * 4));  // high bits of the candidate ranges (read only when an axis has more than 65535 cells)
@@ -717,8 +724,8 @@ vx_status setup_launch(const vx_mesh* m, const vx::GridParams& g, int sat, uint6
     VX_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(ntri), s));
     vx::launch_tri_setup(m->dv, m->di, tb, ntri, g, sat, zlo, zhi, recs.as<vx::TriRec>(), units.as<uint32_t>(), s, dgrid, clear, clear_bytes, shard_wb, shard_we,
                          ext.as<uint32_t>(), shard_rank, shard_world);
-    const bool tg = vx::launch_scan_u32(units.as<uint32_t>(), ubase.as<uint32_t>(), ntri, false, scantmp.p, &mail->units, s, true, mail_tag, nullptr,
-                                        advance_scan_gen(scantmp, s));
+    const bool tg = vx::launch_scan_u32(units.as<uint32_t>(), ubase.as<uint32_t>(), ntri, false, scantmp.p, units_total ? units_total : &mail->units, s, true, mail_tag,
+                                        nullptr, advance_scan_gen(scantmp, s));
     if (tagged) *tagged = tg && mail_tag != 0;
     return VX_OK;
 }
@@ -745,6 +752,7 @@ vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0, b
     *pending = !g->occupied_known;
     if (tagged) *tagged = false;
     if (g->prefix_valid) return VX_OK;
+    const bool count_known = g->p16_valid && g->occupied_known;  // (the line counts' scan gave the count already: nobody has to wait for this one's)
     if (!tag) {  // a scan outside a build: its own sequence tag
         g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
         tag = (unsigned long long)g->mail_seq << 48;
@@ -757,11 +765,38 @@ vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0, b
                                         g->wsel.as<uint32_t>(), advance_scan_gen(g->scantmp, g->stream), g->wp16.as<uint32_t>());
     g->sel_valid = tg;  // (the three-pass scan writes neither wsel nor wp16)
     if (tagged) *tagged = tg;
-    g->occ_tag = tg ? tag : 0;  // what the host may poll the mailbox for instead of draining the stream (prefix_finish)
     g->prefix_valid = true;
+    if (count_known) return VX_OK;
+    g->occ_tag = tg ? tag : 0;  // what the host may poll the mailbox for instead of draining the stream (prefix_finish)
     g->occupied_known = false;
     *pending = true;
     return VX_OK;
+}
+
+// A whole Vec build on the tiled build mask whose rows are multiples of 512 voxels: the brick kernel, which has every word of the bitmask
+// in its hands, also left the set bits of every 16-word line (g->lcnt).  Their exclusive scan IS word_prefix[16 i] -- the table the rank pass
+// of a ray batch reads beside the voxel's own line of the mask -- and its total the occupied count, posted to the same mailbox word: a scan
+// over nwords / 16 values instead of a pass that reads the mask again and writes nwords prefixes nobody on this path reads.
+vx_status p16_launch(vx_grid* g, unsigned long long tag, bool* tagged)
+{
+    const uint64_t nl = g->g.nwords / 16;
+    VX_HIP(g->wp16.ensure((size_t)(nl + 4) * 4));
+    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nl), g->stream));
+    const bool tg = vx::launch_scan_u32(g->lcnt.as<uint32_t>(), g->wp16.as<uint32_t>(), nl, false, g->scantmp.p, &g->mail->occupied, g->stream, true, tag, nullptr,
+                                        advance_scan_gen(g->scantmp, g->stream));
+    *tagged = tg;
+    g->p16_valid = true;
+    g->prefix_valid = g->sel_valid = false;  // (wprefix and wsel still describe an older mask)
+    g->occ_tag = tg ? tag : 0;
+    g->occupied_known = false;
+    return VX_OK;
+}
+
+// what the rank pass of a ray batch needs on the stream: wp16 where the build left it, the word prefix (which brings wp16 along) otherwise
+vx_status rank_launch(vx_grid* g, bool* pending)
+{
+    if (g->p16_valid) { *pending = !g->occupied_known; return VX_OK; }
+    return prefix_launch(g, pending);
 }
 
 vx_status prefix_finish(vx_grid* g, bool pending)
@@ -783,8 +818,17 @@ vx_status ensure_prefix(vx_grid* g)
     return prefix_finish(g, pending);
 }
 
+// the occupied count on the host (no word prefix is built for it where the line counts' scan delivers it)
+vx_status ensure_occupied(vx_grid* g)
+{
+    if (!g->p16_valid) return ensure_prefix(g);
+    DeviceGuard dg(g->device);
+    return prefix_finish(g, !g->occupied_known);
+}
+
 // from_tiled: the reference's bitmask has not been written yet -- the brick kernel reads the tiled build mask (g->twords) and writes it on the way
-vx_status ensure_coarse(vx_grid* g, bool from_tiled = false)
+// line_counts (with from_tiled): it also leaves the set bits per 16-word line in g->lcnt (p16_launch)
+vx_status ensure_coarse(vx_grid* g, bool from_tiled = false, bool line_counts = false)
 {
     if (g->coarse_valid && !from_tiled) return VX_OK;
     DeviceGuard dg(g->device);
@@ -800,7 +844,8 @@ vx_status ensure_coarse(vx_grid* g, bool from_tiled = false)
     // bitmask -> brick-major slabs in three orientations -> level-1 mip (from the z orientation) -> level-2 mip
     const bool fuse_mip1 = !(getenv("VOXHIP_FUSE_MIP1") && atoi(getenv("VOXHIP_FUSE_MIP1")) == 0);  // 0: the separate kernel, every brick stored (tests)
     const bool fused = vx::launch_build_bricks3(g->words.as<uint32_t>(), g->g.dim, g->cdim, g->bricks.as<unsigned long long>(),
-                                                fuse_mip1 ? g->cwords.as<uint32_t>() : nullptr, g->stream, from_tiled ? g->twords.as<uint32_t>() : nullptr);
+                                                fuse_mip1 ? g->cwords.as<uint32_t>() : nullptr, g->stream, from_tiled ? g->twords.as<uint32_t>() : nullptr,
+                                                from_tiled && line_counts ? g->lcnt.as<uint32_t>() : nullptr);
     if (!fused) vx::launch_brick_mip1(g->bricks.as<unsigned long long>() + 2ull * nc * 8ull, nc, g->cwords.as<uint32_t>(), g->stream);
     vx::launch_build_mip2(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->stream);
     g->coarse_valid = true;
@@ -831,7 +876,7 @@ vx_status init_grid_storage(vx_grid* g, bool clear = true)
         VX_HIP(hipMemsetAsync(g->words.p, 0, (size_t)(g->g.nwords + 2) * 4, g->stream));
         VX_HIP(hipMemsetAsync(g->small.as<Small>()->set_calls, 0, sizeof(Small::set_calls), g->stream));
     }
-    g->coarse_valid = g->prefix_valid = g->occupied_known = false;
+    g->coarse_valid = g->prefix_valid = g->p16_valid = g->occupied_known = false;
     g->counts_valid = true;
     g->occupied = g->set_calls = g->host_set_calls = g->vec_count = 0;
     return VX_OK;
@@ -1151,7 +1196,7 @@ static void grid_set_empty(vx_grid* g, float vs)
     fill_params(g->g, zero3, vs, zdim);
     for (int a = 0; a < 3; ++a) g->bbmin[a] = g->bbmax[a] = g->bbc[a] = 0.f;
     g->triangles = 0;
-    g->coarse_valid = g->prefix_valid = false;
+    g->coarse_valid = g->prefix_valid = g->p16_valid = false;
     g->occupied_known = g->counts_valid = true;
     g->occupied = g->set_calls = g->host_set_calls = 0;
     g->vec_count = 0;
@@ -1165,7 +1210,7 @@ static void grid_set_empty(vx_grid* g, float vs)
     g->mat_interior = 0;
 }
 
-static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g);
+static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g, bool allow_early = true);
 
 vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_opts* opts, vx_grid* g)
 {
@@ -1193,7 +1238,7 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
     return st;
 }
 
-static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g)
+static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g, bool allow_early)
 {
     g->set_stream((hipStream_t)o.stream);
     hipStream_t s = g->stream;
@@ -1231,6 +1276,14 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     // sequence tag of this build's totals in the mailbox (never 0: an untagged word never matches)
     g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
     const unsigned long long mtag = (unsigned long long)g->mail_seq << 48;
+    // A VX_VOXELIZE_LIST_ASYNC rebuild (nothing queued inside the build but the voxelizer reads a buffer sized by the unit total U): the host
+    // waits for the BBOX only -- k_bbox posts a tag of its own -- and queues the voxelizer and everything behind it while the record kernel
+    // and the unit scan still run, instead of leaving the GPU idle for a mailbox round trip plus a launch (8-12 us) behind the scan.  The
+    // voxelizer finds U in device memory (the scan's total goes there, and on to the mailbox with k_unit_blocks) and does nothing when U
+    // exceeds what the handle's buffers from the previous build hold; the host reads U in the wait for the hit count and only then, or with
+    // 2^32 units or more, goes the way of a first build: U first, buffers, the same kernels again.
+    bool early = allow_early && ntri > 0 && !sharded_words && list_async && g->umask.cap >= 64 && g->bhits.cap >= 64 && g->hbase.cap >= 64 && g->btri.cap >= 64;
+    uint64_t unit_cap = 0;
     Extent ex;
     uint64_t btri_entries = 0;  // entries of the block table filled by the launch queued ahead of the unit total
     bool setup_queued = false;
@@ -1241,7 +1294,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         const float zero3[3] = {0.f, 0.f, 0.f};
         const uint64_t zdim[3] = {0, 0, 0};
         fill_params(gp, zero3, vs, zdim);
-        vx::launch_bbox(mesh->dv, mesh->nv, ds->bbox_state, g->mail->bbox, ds->set_calls, s, vs, &ds->dgrid);
+        vx::launch_bbox(mesh->dv, mesh->nv, ds->bbox_state, g->mail->bbox, ds->set_calls, s, vs, &ds->dgrid, early ? &g->mail->bbox_tag : nullptr, mtag);
         bool units_tagged = false;
         // the previous build's bitmask is cleared in the same window -- by the record kernel's own threads when there are enough of
         // them (at most 256 bytes each), by a memset behind the block table otherwise
@@ -1251,24 +1304,41 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         const bool clear_in_setup = cb.p && (cb.cap % 16) == 0 && cb.cap / 256 <= (size_t)ntri;
         VX_TRY(setup_launch(mesh, gp, o.sat_variant, tb, ntri, 0, 0, g->recs, g->units, g->ubase, g->scantmp, g->mail.get(), s, g->ext, &ds->dgrid, mtag, &units_tagged,
                             clear_in_setup ? cb.p : nullptr, clear_in_setup ? cb.cap : 0, sharded_words ? o.word_begin : 0,
-                            sharded_words ? o.word_end : 0, by_rank ? (uint32_t)o.shard_rank : 0u, by_rank ? (uint32_t)o.shard_world : 0u));
+                            sharded_words ? o.word_end : 0, by_rank ? (uint32_t)o.shard_rank : 0u, by_rank ? (uint32_t)o.shard_world : 0u,
+                            early ? &ds->units64 : nullptr));
         if (clear_in_setup) cleared = cb.cap;
         // the block table of the units: queued now, for as many blocks as the handle's table from the previous build holds, so that
         // it runs while the host waits for the unit total (redone by setup_finish should the table turn out too small)
         if (g->btri.p && g->btri.cap >= 64) {
             btri_entries = g->btri.cap / 4;
             if (btri_entries > 0x3FFFFFFull) btri_entries = 0x3FFFFFFull;
-            vx::launch_unit_blocks(g->ubase.as<uint32_t>(), ntri, (uint32_t)((btri_entries - 2) * 64), g->btri.as<uint32_t>(), s, (uint32_t)btri_entries);
+            if (early) {
+                // the units the buffers of the previous build hold; the hit scan runs over the blocks of that many units, so the entries
+                // behind this build's last block are zeroed on the way
+                unit_cap = std::min(std::min((uint64_t)g->umask.cap / 4 - 1, ((uint64_t)g->bhits.cap / 4 - 4) * 64),
+                                    std::min(((uint64_t)g->hbase.cap / 4 - 4) * 64, (btri_entries - 2) * 64));
+            }
+            vx::launch_unit_blocks(g->ubase.as<uint32_t>(), ntri, (uint32_t)((btri_entries - 2) * 64), g->btri.as<uint32_t>(), s, (uint32_t)btri_entries,
+                                   early ? &ds->units64 : nullptr, early ? &g->mail->units : nullptr, early ? g->bhits.as<uint32_t>() : nullptr,
+                                   (uint32_t)((unit_cap + 63) / 64));
         }
         if (cb.p && !clear_in_setup) {
             VX_HIP(hipMemsetAsync(cb.p, 0, cb.cap, s));
             cleared = cb.cap;
         }
-        // the bbox (written by k_bbox, two kernels earlier) and the unit total: polled from the mailbox, see the hit count below
-        if (!(units_tagged && mail_wait(&g->mail->units, nullptr, mtag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+        if (early && units_tagged) {
+            if (!mail_wait(&g->mail->bbox_tag, nullptr, mtag, 5.0)) VX_HIP(hipStreamSynchronize(s));
+            std::atomic_thread_fence(std::memory_order_acquire);
+        } else {
+            // the bbox (written by k_bbox, two kernels earlier) and the unit total: polled from the mailbox, see the hit count below
+            // (an untagged total on its way through device memory: the drained stream has forwarded it)
+            if (!(units_tagged && !early && mail_wait(&g->mail->units, nullptr, mtag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+            early = false;
+        }
         VX_TRY(extent_from_bbox(g->mail->bbox, mesh->nv, vs, &ex));
         setup_queued = true;
     } else {
+        early = false;
         VX_TRY(compute_extent(mesh, vs, ds, g->mail.get(), s, &ex));  // also clears the per-build call counter
     }
     const uint64_t nvox = ex.dim[0] * ex.dim[1] * ex.dim[2];
@@ -1326,7 +1396,10 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
                                // or, when there is no unit to run, by the memset below
     }
     uint64_t U = 0;
-    if (setup_queued) {
+    if (early) {
+        if (!mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
+        U = unit_cap;  // (what the buffers below are sized for: they are the previous build's)
+    } else if (setup_queued) {
         if (!mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
         VX_TRY(setup_finish(ntri, g->ubase, g->btri, g->mail.get(), s, &U, /*stream_is_drained=*/true, btri_entries));
     } else {
@@ -1362,7 +1435,8 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         bhits = g->bhits.as<uint32_t>();
     }
     vx::launch_voxelize(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, o.sat_variant,
-                        tiled ? g->twords.as<uint32_t>() : g->words.as<uint32_t>(), wb, we, umask, ds->set_calls, s, xw, bhits, tiled);
+                        tiled ? g->twords.as<uint32_t>() : g->words.as<uint32_t>(), wb, we, umask, ds->set_calls, s, xw, bhits, tiled,
+                        early ? &ds->units64 : nullptr, (uint32_t)unit_cap);
     // (the tiled mask -> the reference's bitmask: by the brick kernel on its way when the traversal structure is built right away, below)
     // (VX_VOXELIZE_SOLID: the fill reads and extends the reference's bitmask, the traversal structure is built from the final one)
     const bool untile_in_bricks = tiled && whole_words && !solid;
@@ -1386,10 +1460,20 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     // primitive ids) -- behind the voxelizer instead of lazily in front of the first query.  For the Vec flavour this work
     // runs while the host waits for the hit count.  A word shard's stay lazy (ensure_coarse / ensure_prefix in the query paths).
     if (whole_words) {
-        VX_TRY(ensure_coarse(g, untile_in_bricks));
-        bool pending = false;
-        occ_queued = !g->prefix_valid;
-        VX_TRY(prefix_launch(g, &pending, mtag, &occ_tagged));
+        // (a Vec build's consumers -- the ray batch's rank pass -- read wp16 only: from the brick kernel's line counts where a line lies in
+        // one row, i.e. X % 512 == 0, which makes nwords a multiple of 16 as the rank pass's 16-word path needs it.  The Bool flavours emit
+        // their list from the word prefix right away, materials index it: today's scan)
+        const bool lines = untile_in_bricks && g->kind == VX_GRID_VEC && !want_mat && (ex.dim[0] % 512) == 0;
+        if (lines) VX_HIP(g->lcnt.ensure((size_t)(g->g.nwords / 16 + 4) * 4));
+        VX_TRY(ensure_coarse(g, untile_in_bricks, lines));
+        if (lines) {
+            occ_queued = true;
+            VX_TRY(p16_launch(g, mtag, &occ_tagged));
+        } else {
+            bool pending = false;
+            occ_queued = !g->prefix_valid;
+            VX_TRY(prefix_launch(g, &pending, mtag, &occ_tagged));
+        }
     }
     if (g->kind == VX_GRID_VEC) {
         // The list is emitted into the handle's existing buffer before the host knows the hit count (writes beyond the
@@ -1408,15 +1492,30 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         // VX_VOXELIZE_LIST_ASYNC: only the hit count -- its scan runs in front of the traversal structure and the word prefix, so the host
         // is back in the caller ~40 us of GPU work before the build ends and the caller's ray batch is queued in time; the occupied count
         // (the LAST kernel's total) is fetched when somebody asks for it (prefix_finish).
-        const bool occ_in_flight = g->prefix_valid && !g->occupied_known;
+        const bool occ_in_flight = (g->prefix_valid || g->p16_valid) && !g->occupied_known;
         const bool occ_along = occ_in_flight && !(list_async && occ_queued && occ_tagged);
         bool got = false;
         if (hits_tagged && (!occ_along || (occ_queued && occ_tagged)))
             got = mail_wait(&g->mail->hits, occ_along ? &g->mail->occupied : nullptr, mtag, 5.0);
         if (!got) VX_HIP(hipStreamSynchronize(s));
+        if (early) {
+            // the unit total, in the mailbox since k_unit_blocks: checked as setup_finish checks it.  More units than the early launch's
+            // buffers hold: the voxelizer did nothing -- the buffers grow and the build runs again the way of a first build
+            if ((g->mail->units & ~kMailValue) != mtag) VX_HIP(hipStreamSynchronize(s));
+            const unsigned long long tot = g->mail->units & kMailValue;
+            if (tot >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 candidate row segments: shard the mesh or the grid");
+            if (tot > unit_cap) {
+                VX_HIP(hipStreamSynchronize(s));  // (the kernels of this pass read the blocks that are about to be replaced)
+                VX_HIP(g->umask.ensure((size_t)(tot + 1) * 4));
+                VX_HIP(g->bhits.ensure((size_t)(tot / 64 + 5) * 4));
+                VX_HIP(g->hbase.ensure((size_t)(tot / 64 + 5) * 4));
+                VX_HIP(g->btri.ensure((size_t)(tot / 64 + 2) * 4));
+                return voxelize_build(mesh, vs, o, g, /*allow_early=*/false);
+            }
+        }
         const unsigned long long hits = g->mail->hits & kMailValue;
         if (hits >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 voxel hits");
-        if (g->prefix_valid && (occ_along || !got)) {  // the same wait covered the occupied count
+        if ((g->prefix_valid || g->p16_valid) && (occ_along || !got)) {  // the same wait covered the occupied count
             if ((g->mail->occupied & kMailValue) >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 occupied voxels");
             g->occupied = g->mail->occupied & kMailValue;
             g->occupied_known = true;
@@ -1768,7 +1867,7 @@ vx_status vx_grid_describe(const vx_grid* gc, vx_grid_desc* d)
     if (!gc || !d) return fail(VX_ERR_INVALID_ARG, "null argument");
     vx_grid* g = const_cast<vx_grid*>(gc);
     VX_TRY(sync_counts(g));
-    VX_TRY(ensure_prefix(g));
+    VX_TRY(ensure_occupied(g));
     std::memset(d, 0, sizeof(*d));
     for (int a = 0; a < 3; ++a) {
         d->dim[a] = g->g.dim[a];
@@ -1819,7 +1918,7 @@ vx_status vx_grid_set_voxel(vx_grid* g, uint64_t x, uint64_t y, uint64_t z)
     }
     g->host_set_calls++;
     g->set_calls++;
-    g->coarse_valid = g->prefix_valid = g->occupied_known = false;
+    g->coarse_valid = g->prefix_valid = g->p16_valid = g->occupied_known = false;
     g->has_materials = false;  // ids are per box of the list: a host-side setVoxel (default material, not recorded) invalidates them
     return VX_OK;
 }
@@ -1874,7 +1973,7 @@ uint32_t* vx_grid_bitmask_device_mut(vx_grid* g)
 {
     if (!g) return nullptr;
     { DeviceGuard dg(g->device); (void)g->list_resolve(); }  // (an emission still to come reads the mask the caller is about to write)
-    g->coarse_valid = g->prefix_valid = g->occupied_known = false;
+    g->coarse_valid = g->prefix_valid = g->p16_valid = g->occupied_known = false;
     return g->words.as<uint32_t>();
 }
 vx_status vx_grid_refresh(vx_grid* g)
@@ -1885,7 +1984,7 @@ vx_status vx_grid_refresh(vx_grid* g)
         VX_HIP(g->list_resolve());
         if (g->g.nwords) vx::launch_mask_tail(g->words.as<uint32_t>(), g->g.nvox, g->stream);  // (padding bits are not cells)
     }
-    g->coarse_valid = g->prefix_valid = g->occupied_known = false;
+    g->coarse_valid = g->prefix_valid = g->p16_valid = g->occupied_known = false;
     VX_TRY(ensure_prefix(g));
     return ensure_coarse(g);
 }
@@ -1900,7 +1999,7 @@ vx_status vx_grid_fill_interior(vx_grid* g)
     uint64_t n = 0;
     const uint32_t* h = nullptr;
     const vx_status st = solid_fill(g, &n, &h);
-    g->coarse_valid = g->prefix_valid = g->occupied_known = false;  // (the mask may have changed even when the fill failed)
+    g->coarse_valid = g->prefix_valid = g->p16_valid = g->occupied_known = false;  // (the mask may have changed even when the fill failed)
     VX_TRY(st);
     if (g->kind == VX_GRID_VEC && n) {
         // setVoxel appends one record per call: the list continues in the grid's own storage, as after vx_grid_set_voxel
@@ -2392,7 +2491,7 @@ static vx::TraceMips grid_mips(const vx_grid* g, const uint32_t** p16)
     mips.w1 = g->cwords.as<uint32_t>();
     mips.w2 = g->c2words.as<uint32_t>();
     for (int a = 0; a < 3; ++a) { mips.d1[a] = g->cdim[a]; mips.d2[a] = g->c2dim[a]; }
-    *p16 = (g->sel_valid && (g->g.nwords % 16) == 0) ? g->wp16.as<uint32_t>() : nullptr;
+    *p16 = ((g->sel_valid || g->p16_valid) && (g->g.nwords % 16) == 0) ? g->wp16.as<uint32_t>() : nullptr;
     return mips;
 }
 
@@ -2414,8 +2513,8 @@ static vx_status trace_common(vx_grid* g, vx::TraceIO io)
     void* idx_tmp = nullptr;
     if (io.prim_out || io.hits || io.normal_out) {
         bool pending = false;
-        VX_TRY(prefix_launch(g, &pending));  // the ranks need the prefix array on the stream, not the count on the host
-        prefix = g->wprefix.as<uint32_t>();
+        VX_TRY(rank_launch(g, &pending));  // the ranks need wp16 or the prefix array on the stream, not the count on the host
+        prefix = g->prefix_valid ? g->wprefix.as<uint32_t>() : nullptr;
         VX_HIP(g->idxtmp.ensure(vx::trace_idx_bytes(g->g, io.nrays)));
         idx_tmp = g->idxtmp.p;
         if (!io.t_out) {  // the rank / normal / compaction pass reads t

@@ -57,7 +57,9 @@ struct DevGrid {
 };
 void bbox_state_init(unsigned long long state7[7]);
 void launch_bbox(const float* verts, uint64_t nverts, unsigned long long* state7, float* out6, unsigned long long* zero64, hipStream_t s,
-                 float vs = 1.0f, DevGrid* dgrid = nullptr);
+                 float vs = 1.0f, DevGrid* dgrid = nullptr,
+                 unsigned long long* tag_out = nullptr /*optional, host mailbox word: receives `tag` once out6 is complete, for a host that polls*/,
+                 unsigned long long tag = 0);
 
 // K2a: per-triangle record + number of row-segment work units; zlo/zhi clamp the candidate box to a z slab.
 void launch_tri_setup(const float* verts, const int32_t* idx, uint64_t tri_begin, uint32_t ntri, const GridParams& g,
@@ -93,14 +95,21 @@ void launch_scan_u8(const uint8_t* in, uint32_t* out, uint64_t n, void* tmp /*sc
 // K2: triangle/voxel overlap over all work units; ORs hits into `words` (only words in [wb,we)), optionally
 // stores each unit's 32-bit hit mask (unit_mask) for the ordered emitters; adds the hit count to *set_calls.
 // block_tri (optional): per 256-unit block the triangle of its first unit (launch_unit_blocks), enables LDS staging.
-void launch_unit_blocks(const uint32_t* unit_base, uint32_t ntri, uint32_t total_units, uint32_t* block_tri, hipStream_t s, uint32_t cap_blocks = 0xFFFFFFFFu);
+void launch_unit_blocks(const uint32_t* unit_base, uint32_t ntri, uint32_t total_units, uint32_t* block_tri, hipStream_t s, uint32_t cap_blocks = 0xFFFFFFFFu,
+                        const unsigned long long* fwd_src = nullptr, unsigned long long* fwd_dst = nullptr /*optional: *fwd_dst = *fwd_src, the unit
+                        scan's total on its way from device memory to the host's mailbox*/,
+                        uint32_t* zero_hits = nullptr, uint32_t zero_n = 0 /*optional: entries [nUB, zero_n) of the voxelizer's block_hits are zeroed (zero_n
+                        at most the blocks this launch covers)*/);
 void launch_voxelize(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const GridParams& g,
                      int sat_variant, uint32_t* words, uint64_t wb, uint64_t we, uint32_t* unit_mask, unsigned long long* set_calls,
                      hipStream_t s, const uint32_t* ext = nullptr /*k_tri_setup's extension words; null unless an axis has more than 65535 cells*/,
                      uint32_t* block_hits = nullptr /*with unit_mask: hits per block of 64 units, (U + 63) / 64 entries -- what launch_emit_units'
                                                       block_base is the exclusive scan of*/,
                      bool tiled = false /*`words` is the tiled build mask (tiled_mask_words(dim) words, dim[0] % 32 == 0, whole grid): launch_untile
-                                          then writes the reference's bitmask*/);
+                                          then writes the reference's bitmask*/,
+                     const unsigned long long* units_total = nullptr /*a launch queued before the host knows the unit total: the scan's 64-bit total in
+                                          device memory; the kernel does nothing when it exceeds unit_cap*/,
+                     uint32_t unit_cap = 0 /*the units unit_mask / block_hits / block_tri were sized for*/);
 uint64_t tiled_mask_words(const uint32_t dim[3]);
 void launch_untile(const uint32_t* tiled, uint32_t* words, const uint32_t dim[3], hipStream_t s, uint64_t wb = 0, uint64_t we = ~0ull /*the words the build owns: the others are written as zero*/);
 
@@ -134,7 +143,9 @@ void launch_emit_morton_aabbs(const uint64_t* items, uint64_t n, const float roo
 // (m1 given and bdim[0] % 64 == 0: the brick kernel writes the level-1 mip itself, leaves empty bricks unwritten and returns true)
 bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const uint32_t bdim[3], unsigned long long* bricks3, uint32_t* m1, hipStream_t s,
                           const uint32_t* tiled = nullptr /*the voxelizer's tiled build mask (dim[0] % 32 == 0): the source instead of `words`, and `words`
-                                                            is WRITTEN from it -- launch_untile's job done on the way*/);
+                                                            is WRITTEN from it -- launch_untile's job done on the way*/,
+                          uint32_t* line_cnt = nullptr /*with `tiled`, dim[0] % 512 == 0 (so every 16-word line of the bitmask lies in one row): the set
+                                                         bits per line, nwords / 16 counts; their exclusive scan is word_prefix[16 i]*/);
 void launch_brick_mip1(const unsigned long long* bricks_z /*orientation 2*/, uint64_t nbricks, uint32_t* m1, hipStream_t s);
 void launch_build_mip2(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, hipStream_t s);
 struct TraceMips {

@@ -81,7 +81,8 @@ __device__ __forceinline__ unsigned ord_bits(float f)
 // host-to-device initialisation nor a second kernel.  `zero64` (optional) is cleared by the same workgroup: the per-build
 // setVoxel call counter.
 __global__ __launch_bounds__(256) void k_bbox(const float* __restrict__ verts, uint64_t nverts, unsigned long long* state, float* out6,
-                                              unsigned long long* zero64, float vs, DevGrid* dgrid)
+                                              unsigned long long* zero64, float vs, DevGrid* dgrid,
+                                              unsigned long long* tag_out /*optional, host mailbox: receives `tag` once out6 is complete*/, unsigned long long tag)
 {
     unsigned long long mn[3] = {~0ull, ~0ull, ~0ull}, mx[3] = {0ull, 0ull, 0ull};
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nverts; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -159,6 +160,12 @@ __global__ __launch_bounds__(256) void k_bbox(const float* __restrict__ verts, u
             dgrid->dim[threadIdx.x] = d;
         }
     }
+    // the host may poll for the bbox instead of for a later kernel's total: the tag leaves behind the six floats (the same wave stored
+    // them; a system-scope fence between the two)
+    if (tag_out && threadIdx.x < 64) {
+        __threadfence_system();
+        if (threadIdx.x == 0) __hip_atomic_store(tag_out, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 #ifndef VX_BBOX_PER_THREAD
@@ -171,9 +178,9 @@ void bbox_state_init(unsigned long long state7[7])
 }
 
 void launch_bbox(const float* verts, uint64_t nverts, unsigned long long* state7, float* out6, unsigned long long* zero64, hipStream_t s, float vs,
-                 DevGrid* dgrid)
+                 DevGrid* dgrid, unsigned long long* tag_out, unsigned long long tag)
 {
-    VX_KL(k_bbox, dim3(nverts ? grid_for(nverts, 256 * VX_BBOX_PER_THREAD, 512) : 1u), dim3(256), 0, s, verts, nverts, state7, out6, zero64, vs, dgrid);
+    VX_KL(k_bbox, dim3(nverts ? grid_for(nverts, 256 * VX_BBOX_PER_THREAD, 512) : 1u), dim3(256), 0, s, verts, nverts, state7, out6, zero64, vs, dgrid, tag_out, tag);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -743,11 +750,17 @@ constexpr uint32_t kUnitBlockLog2 = 6;
 // the LAST such t).  The previous form -- one thread per triangle writing the blocks it spans -- serialised on the few
 // triangles that span hundreds of blocks.
 __global__ __launch_bounds__(256) void k_unit_blocks(const uint32_t* __restrict__ unit_base, uint32_t ntri, uint32_t* __restrict__ block_tri,
-                                                     uint32_t cap_blocks /*entries block_tri can hold*/)
+                                                     uint32_t cap_blocks /*entries block_tri can hold*/,
+                                                     const unsigned long long* fwd_src, unsigned long long* fwd_dst /*optional: the unit scan's total, left in
+                                                     device memory for the voxelizer, goes on to the host's mailbox from here*/,
+                                                     uint32_t* __restrict__ zero_hits, uint32_t zero_n /*optional: block_hits entries [nUB, zero_n) are zeroed --
+                                                     the hit scan of a voxelizer queued ahead of the unit total runs over zero_n entries*/)
 {
+    if (fwd_dst && blockIdx.x == 0u && threadIdx.x == 0u) *fwd_dst = *fwd_src;
     const uint32_t U = unit_base[ntri];
     const uint32_t nUB = (U + 63u) >> kUnitBlockLog2;
     const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (zero_hits && b >= nUB && b < zero_n) zero_hits[b] = 0u;
     if (b >= nUB || b >= cap_blocks) return;
     const uint32_t u = b << kUnitBlockLog2;
     uint32_t lo = 0, hi = ntri;  // unit_base[lo] <= u < unit_base[hi]
@@ -760,11 +773,12 @@ __global__ __launch_bounds__(256) void k_unit_blocks(const uint32_t* __restrict_
 
 // total_units: the host's figure -- or, for a launch queued before the host knows it, the most the table can describe (the kernel
 // reads the real total from unit_base[ntri] and never writes at or beyond cap_blocks)
-void launch_unit_blocks(const uint32_t* unit_base, uint32_t ntri, uint32_t total_units, uint32_t* block_tri, hipStream_t s, uint32_t cap_blocks)
+void launch_unit_blocks(const uint32_t* unit_base, uint32_t ntri, uint32_t total_units, uint32_t* block_tri, hipStream_t s, uint32_t cap_blocks,
+                        const unsigned long long* fwd_src, unsigned long long* fwd_dst, uint32_t* zero_hits, uint32_t zero_n)
 {
     const uint32_t nUB = (uint32_t)(((uint64_t)total_units + 63u) >> kUnitBlockLog2);
     if (!ntri || !nUB) return;
-    VX_KL(k_unit_blocks, dim3((nUB + 255) / 256), dim3(256), 0, s, unit_base, ntri, block_tri, cap_blocks);
+    VX_KL(k_unit_blocks, dim3((nUB + 255) / 256), dim3(256), 0, s, unit_base, ntri, block_tri, cap_blocks, fwd_src, fwd_dst, zero_hits, zero_n);
 }
 
 #ifdef VX_VOX_DEBUG
@@ -934,8 +948,13 @@ __global__ __launch_bounds__(256, VX_VOX_MINWG) void k_voxelize(const TriRec* __
                                                   uint64_t wb, uint64_t we, uint32_t* __restrict__ unit_mask, unsigned long long* set_calls,
                                                   const uint32_t* __restrict__ ext /*null unless the grid has an axis above 65535 cells*/,
                                                   uint32_t* __restrict__ block_hits /*optional, with unit_mask: hits per block of 64 units*/,
-                                                  uint32_t tiles_y /*0: `words` is the reference's bitmask; else: the tiled build mask, see k_untile*/, uint32_t xw)
+                                                  uint32_t tiles_y /*0: `words` is the reference's bitmask; else: the tiled build mask, see k_untile*/, uint32_t xw,
+                                                  const unsigned long long* __restrict__ units_total /*optional: a launch queued before the host knew the unit
+                                                  total -- the scan's 64-bit total (tag in bits 48..63), in device memory*/,
+                                                  uint32_t unit_cap /*... and the units the launch's buffers (unit_mask, block_hits, block_tri) were sized for*/)
 {
+    // more units than the buffers hold (or than 32 bits count): nothing is read or written, the host sees the total and queues the build again
+    if (units_total && (*units_total & ((1ull << 48) - 1ull)) > (unsigned long long)unit_cap) return;
     __shared__ UnitStage stage[VX_VOX_NBUF * 4];
     unsigned hits = 0;
 #ifdef VX_VOX_DEBUG
@@ -1085,17 +1104,17 @@ namespace vx {
 
 void launch_voxelize(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const GridParams& g, int sat_variant,
                      uint32_t* words, uint64_t wb, uint64_t we, uint32_t* unit_mask, unsigned long long* set_calls, hipStream_t s, const uint32_t* ext,
-                     uint32_t* block_hits, bool tiled)
+                     uint32_t* block_hits, bool tiled, const unsigned long long* units_total, uint32_t unit_cap)
 {
     if (!ntri) return;
     const dim3 grid(kUnitBlocks), block(256);
     const uint32_t ty = tiled ? (g.dim[1] + 3u) / 4u : 0u, xw = g.dim[0] / 32u;
     if (sat_variant == 0) {
-        if (unit_mask) VX_KL((k_voxelize<true, true>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, block_hits, ty, xw);
-        else VX_KL((k_voxelize<true, false>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, (uint32_t*)nullptr, ty, xw);
+        if (unit_mask) VX_KL((k_voxelize<true, true>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, block_hits, ty, xw, units_total, unit_cap);
+        else VX_KL((k_voxelize<true, false>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, (uint32_t*)nullptr, ty, xw, units_total, unit_cap);
     } else {
-        if (unit_mask) VX_KL((k_voxelize<false, true>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, block_hits, ty, xw);
-        else VX_KL((k_voxelize<false, false>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, (uint32_t*)nullptr, ty, xw);
+        if (unit_mask) VX_KL((k_voxelize<false, true>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, block_hits, ty, xw, units_total, unit_cap);
+        else VX_KL((k_voxelize<false, false>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, (uint32_t*)nullptr, ty, xw, units_total, unit_cap);
     }
 }
 

@@ -173,7 +173,8 @@ void launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* wo
 {
     const uint64_t nrays = io.nrays;
     if (!nrays) return;
-    const bool want_rank = (io.prim_out || io.hits || io.normal_out) && word_prefix && idx_tmp && io.t_out;
+    // (the rank pass reads prefix16 where it is given and word_prefix otherwise: a build that left only prefix16 passes no word_prefix)
+    const bool want_rank = (io.prim_out || io.hits || io.normal_out) && (word_prefix || prefix16) && idx_tmp && io.t_out;
     const bool idx32 = trace_idx32(g);
     launch_walk(g, mips, io, counters, phase, want_rank ? idx_tmp : nullptr, idx32, s, queue);
     if (want_rank) {

@@ -79,7 +79,9 @@ __global__ __launch_bounds__(256) void k_build_bricks3(uint32_t* __restrict__ wo
                                                        uint32_t BZ, uint32_t chunks_x, uint64_t nwords, unsigned long long* __restrict__ bricks3,
                                                        uint64_t ori_stride /*uint64 words per orientation*/, uint32_t* __restrict__ m1,
                                                        const uint32_t* __restrict__ tiled /*optional (X % 32 == 0): the voxelizer's tiled build mask is the
-                                                       source, and `words` -- the reference's bitmask -- is WRITTEN from it on the way (k_untile's job)*/)
+                                                       source, and `words` -- the reference's bitmask -- is WRITTEN from it on the way (k_untile's job)*/,
+                                                       uint32_t* __restrict__ line_cnt /*optional (with `tiled`, X % 512 == 0): the set bits of every 16-word
+                                                       line of the bitmask, nwords / 16 counts -- what the rank pass's prefix16 is the scan of*/)
 {
     __shared__ uint32_t rows[64][17];              // [z*8 + y][32-voxel chunk of the 512]; padded against bank conflicts of the column reads
     __shared__ unsigned long long sz[64][9];       // [brick][z slab]: bit y*8 + x (padded)
@@ -155,6 +157,15 @@ __global__ __launch_bounds__(256) void k_build_bricks3(uint32_t* __restrict__ wo
                     for (uint32_t k = 0; k < 4u && xs + k < xw; ++k) dst[k] = rows[r][q4 + k];
                 }
             }
+            if (line_cnt) {
+                // X % 512 == 0: the sixteen words a row has in this group ARE one 16-word line of the bitmask (its first word, xw * (y + Y z) +
+                // 16 cx, is a multiple of 16) -- the four threads of the row add up their words' bits and the first writes the count.  Every
+                // line of the mask belongs to exactly one (group, row); nothing beyond nwords is touched.
+                uint32_t c = empty ? 0u : (uint32_t)(__popc(rows[r][q4]) + __popc(rows[r][q4 + 1u]) + __popc(rows[r][q4 + 2u]) + __popc(rows[r][q4 + 3u]));
+                c += __shfl_xor(c, 1, 64);
+                c += __shfl_xor(c, 2, 64);
+                if (q4 == 0u && z < Z && y < Y) line_cnt[((uint64_t)xw * ((uint64_t)y + (uint64_t)Y * z) + cx * 16u) >> 4] = c;
+            }
         }
         if (empty) continue;  // (nothing of `rows` is read on this path: no barrier needed before the next group's loads overwrite it)
         // ---- z orientation (bit y*8 + x per z slab): two (brick, slab) pairs per thread, into LDS
@@ -223,7 +234,7 @@ __global__ __launch_bounds__(256) void k_build_bricks3(uint32_t* __restrict__ wo
 
 // Returns true when the level-1 mip was written by the brick kernel itself (and empty bricks were left unwritten).
 bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const uint32_t bdim[3], unsigned long long* bricks3, uint32_t* m1, hipStream_t s,
-                          const uint32_t* tiled)
+                          const uint32_t* tiled, uint32_t* line_cnt)
 {
     const uint64_t n = (uint64_t)bdim[0] * bdim[1] * bdim[2];
     if (!n) return false;
@@ -235,7 +246,7 @@ bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const ui
     if (nblk > 16384) nblk = 16384;
     const bool fused = (bdim[0] % 64u) == 0u && m1 != nullptr;
     VX_KL(k_build_bricks3, dim3((unsigned)nblk), dim3(256), 0, s, const_cast<uint32_t*>(words), dim[0], dim[1], dim[2], bdim[0], bdim[1], bdim[2], chunks_x, nwords, bricks3, n * 8ull,
-          fused ? m1 : nullptr, (dim[0] % 32u) == 0u ? tiled : nullptr);
+          fused ? m1 : nullptr, (dim[0] % 32u) == 0u ? tiled : nullptr, (tiled && (dim[0] % 512u) == 0u) ? line_cnt : nullptr);
     return fused;
 }
 
