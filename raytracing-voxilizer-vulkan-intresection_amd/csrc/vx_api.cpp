@@ -449,6 +449,7 @@ struct vx_grid : Home {
     DevBuf words{this}, twords{this} /*tiled build mask (launch_voxelize)*/, cwords{this}, c2words{this}, bricks{this}, idxtmp{this}, ttmp{this}, camera{this}, wprefix{this};
     DevBuf wsel{this} /*word of every 1024th occupied voxel (prefix scan)*/, wp16{this} /*every 16th entry of wprefix, dense (prefix scan)*/, recs{this};
     DevBuf lcnt{this} /*set bits per 16-word line of the bitmask (the brick kernel of a whole Vec build): wp16 is their scan*/;
+    DevBuf wring{this} /*k_walk's rank epilogue: per wave the chunks of rays it drew (walk_ring_cap words each); scratch of one ray batch*/;
     DevBuf ext{this} /*high bits of the candidate ranges*/, units{this}, ubase{this}, btri{this}, umask{this}, bhits{this} /*hits per block of 64 units*/;
     DevBuf hbase{this} /*their exclusive scan*/, scantmp{this}, small{this}, vec{this}, matids{this}, mattmp{this};
     // solid voxelization (vx_solid.hip): padded mask, exterior, H in the reference's layout (padded rows only) and the word prefix over H
@@ -2511,13 +2512,23 @@ static vx_status trace_common(vx_grid* g, vx::TraceIO io)
     VX_TRY(ensure_coarse(g));
     const uint32_t* prefix = nullptr;
     void* idx_tmp = nullptr;
+    vx::WalkRing ring;
     if (io.prim_out || io.hits || io.normal_out) {
         bool pending = false;
         VX_TRY(rank_launch(g, &pending));  // the ranks need wp16 or the prefix array on the stream, not the count on the host
         prefix = g->prefix_valid ? g->wprefix.as<uint32_t>() : nullptr;
         VX_HIP(g->idxtmp.ensure(vx::trace_idx_bytes(g->g, io.nrays)));
         idx_tmp = g->idxtmp.p;
-        if (!io.t_out) {  // the rank / normal / compaction pass reads t
+        // prim alone: the ray kernel's waves rank their own rays as they leave, from the chunk ring, where one launch and a ring of a sane
+        // size cover the batch (walk_ring_cap); that rank does not read t
+        uint32_t waves = 0;
+        const uint32_t cap = (io.prim_out && !io.hits && !io.normal_out && vx::trace_idx32(g->g)) ? vx::walk_ring_cap(io.nrays, &waves) : 0u;
+        if (cap) {
+            VX_HIP(g->wring.ensure((size_t)waves * cap * 4));
+            ring.words = g->wring.as<uint32_t>();
+            ring.cap = cap;
+            ring.waves = waves;
+        } else if (!io.t_out) {  // the rank / normal / compaction pass reads t
             VX_HIP(g->ttmp.ensure((size_t)io.nrays * 4 + 8));
             io.t_out = g->ttmp.as<float>();
         }
@@ -2528,9 +2539,11 @@ static vx_status trace_common(vx_grid* g, vx::TraceIO io)
     const bool list_beside = g->list_deferred;  // VX_VOXELIZE_LIST_ASYNC: the list's emission goes beside this ray batch
     if (list_beside) VX_HIP(g->list_side_begin());
     vx::WalkQueue wq;
-    vx::launch_trace(g->g, mips, prefix, io, g->small.as<Small>()->trace_counters, &g->trace_phase, idx_tmp, g->stream, p16, list_beside ? &wq : nullptr);
+    const bool queued = vx::launch_trace(g->g, mips, prefix, io, g->small.as<Small>()->trace_counters, &g->trace_phase, idx_tmp, g->stream, p16, list_beside ? &wq : nullptr,
+                                         ring.words ? &ring : nullptr);
     if (list_beside) VX_HIP(g->list_side_launch(wq.counter, wq.dry_at));
     VX_HIP(hipGetLastError());
+    if (!queued) return fail(VX_ERR_UNSUPPORTED, "internal: the ray kernel declined the rank epilogue its ring was sized for");
     return VX_OK;
 }
 

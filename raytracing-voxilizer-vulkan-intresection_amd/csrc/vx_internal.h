@@ -182,9 +182,31 @@ struct WalkQueue {
     unsigned long long dry_at = 0;
 };
 void launch_queue_gate(const WalkQueue& q, hipStream_t s);  // vx_trace.hip: holds `s` until the kernel's first wave has drawn from q (300 us bound)
-void launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, unsigned long long* counters /*2 device words, zero before the first trace; they alternate*/, int* phase /*host*/,
+// The chunk ring of the ray kernel's rank epilogue: a batch that wants t + prim and nothing else, on a grid with 32-bit voxel indices, is
+// ranked by the waves of k_walk themselves as they leave (no k_rank launch).  Every wave remembers the chunks of rays it drew from the work
+// queue in `cap` words of its own.  walk_ring_cap decides ONCE per batch (the API layer calls it and carries the answer in WalkRing): the
+// entries per wave for a batch of nrays and, in *waves, the waves of its launch; 0: the batch keeps k_rank (more than one launch, or no ring
+// of a sane size holds its chunks).  VOXHIP_TRACE_RING=<entries> overrides the choice (0: k_rank); whether waves * cap chunks cover the
+// batch still decides.
+uint32_t walk_ring_cap(uint64_t nrays, uint32_t* waves);
+struct WalkRing {
+    uint32_t* words = nullptr;   // waves * cap words of device memory; contents are scratch
+    uint32_t cap = 0;            // walk_ring_cap's answer for this batch ...
+    uint32_t waves = 0;          // ... and the waves it counted on
+};
+struct WalkRank {  // what launch_walk's epilogue ranks with and where to
+    const uint32_t* words = nullptr;        // the reference-layout bitmask
+    const uint32_t* word_prefix = nullptr;  // its word prefix, and / or ...
+    const uint32_t* prefix16 = nullptr;     // ... every 16th entry of it, dense (nwords % 16 == 0)
+    uint32_t* prim_out = nullptr;
+    WalkRing ring;
+};
+// Returns false when an output that was asked for could not be queued: a ring was given (so the caller kept no t for k_rank) and the ray
+// kernel declined the epilogue -- the caller's sizing and the launch disagree, an internal error.
+bool launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, unsigned long long* counters /*2 device words, zero before the first trace; they alternate*/, int* phase /*host*/,
                   void* idx_tmp /*trace_idx_bytes when ranks / normals / the hit list are wanted*/, hipStream_t s,
-                  const uint32_t* prefix16 = nullptr /*optional: launch_scan_u32's group16 of word_prefix*/, WalkQueue* queue = nullptr);
+                  const uint32_t* prefix16 = nullptr /*optional: launch_scan_u32's group16 of word_prefix*/, WalkQueue* queue = nullptr,
+                  const WalkRing* ring = nullptr /*walk_ring_cap's ring for this batch: t + prim batches are ranked inside k_walk*/);
 
 // Multi-hit query on the grid (vx_multihit.hip): per ray the first K (1..32) accepted hits in (t, prim) order into io.t_out / io.prim_out (K
 // entries per ray, ray-major, padded with -1 / all ones; both optional) and the number of all accepted hits into count (optional); after_t /

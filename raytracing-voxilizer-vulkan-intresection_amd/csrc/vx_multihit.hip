@@ -275,8 +275,7 @@ __global__ __launch_bounds__(kMhBlock) void k_multihit(const MultiParams P)
                                     const bool keep = n < K || !(t > kth);               // (an equal t may carry a smaller prim)
                                     if (!keep && t != cur_t) { ++total; continue; }      // counted; its prim is never read
                                     const uint64_t vi = (uint64_t)(uint32_t)x + (uint64_t)g.dim[0] * ((uint64_t)(uint32_t)y + (uint64_t)g.dim[1] * (uint32_t)z);
-                                    const uint64_t wi = vi >> 5;
-                                    const uint32_t prim = P.prefix[wi] + __popc(P.w0[wi] & ((1u << ((uint32_t)vi & 31u)) - 1u));  // as k_rank
+                                    const uint32_t prim = voxel_rank(vi, P.w0, P.prefix, nullptr);  // as k_rank
                                     if (t == cur_t && prim <= cur_p) continue;           // not strictly after the cursor
                                     ++total;
                                     if (!keep) continue;

@@ -109,23 +109,7 @@ __global__ __launch_bounds__(1024) void k_rank(const float* __restrict__ t, cons
         else i = reinterpret_cast<const unsigned long long*>(idx_any)[r];
         float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
         if (i != ~0ull) {
-            const uint64_t wi = i >> 5;
-            const uint32_t bit = (uint32_t)i & 31u;
-            if (prefix16) {
-                // The rank from the voxel's own 64-byte line of the mask and the dense array of every 16th prefix (1/16 of word_prefix: it stays
-                // in L2) -- one random line per ray instead of two (word_prefix[wi] is a line of its own): 19.7 -> ... us per 1M rays.
-                const uint64_t g0 = wi & ~15ull;
-                const uint32_t k = (uint32_t)wi & 15u;
-                const uint4* lp = reinterpret_cast<const uint4*>(words + g0);
-                const uint4 a = lp[0], b = lp[1], c = lp[2], d = lp[3];
-                const uint32_t w16[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-                uint32_t cnt = prefix16[wi >> 4];
-#pragma unroll
-                for (uint32_t j = 0; j < 16u; ++j) cnt += __popc(j < k ? w16[j] : (j == k ? (w16[j] & ((1u << bit) - 1u)) : 0u));
-                prim = cnt;
-            } else {
-                prim = word_prefix[wi] + __popc(words[wi] & ((1u << bit) - 1u));
-            }
+            prim = voxel_rank(i, words, word_prefix, prefix16);
             if (normal_out) {
                 const uint64_t XY = (uint64_t)g.dim[0] * g.dim[1];
                 const uint32_t z = (uint32_t)(i / XY);
@@ -144,7 +128,8 @@ __global__ __launch_bounds__(1024) void k_rank(const float* __restrict__ t, cons
     if (hits) compact_hit(active && prim != 0xFFFFFFFFu, r, prim, tt, hits, nhits);  // launched with 1024 threads: one counter touch per 16 waves
 }
 
-void launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, unsigned long long* counters, int* phase, void* idx_out, bool idx32, hipStream_t s, WalkQueue* queue);
+bool launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, unsigned long long* counters, int* phase, void* idx_out, bool idx32, hipStream_t s, WalkQueue* queue,
+                 const WalkRank* rank);
 
 // A gate in front of work that is to run BESIDE a ray batch on another stream (the Vec list's emission, VX_VOXELIZE_LIST_ASYNC): one wave
 // that leaves once the ray kernel's work counter has reached `at_least` -- 1: the first wave has come back for more rays, the kernel's
@@ -168,22 +153,30 @@ void launch_queue_gate(const WalkQueue& q, hipStream_t s)
     VX_KL(k_queue_gate, dim3(1), dim3(64), 0, s, q.counter, /*at_least=*/1ull, /*timeout_ticks=*/300ull * 100ull);
 }
 
-void launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, unsigned long long* counters /*2*/,
-                  int* phase, void* idx_tmp, hipStream_t s, const uint32_t* prefix16, WalkQueue* queue)
+bool launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, unsigned long long* counters /*2*/,
+                  int* phase, void* idx_tmp, hipStream_t s, const uint32_t* prefix16, WalkQueue* queue, const WalkRing* ring)
 {
     const uint64_t nrays = io.nrays;
-    if (!nrays) return;
+    if (!nrays) return true;
     // (the rank pass reads prefix16 where it is given and word_prefix otherwise: a build that left only prefix16 passes no word_prefix)
-    const bool want_rank = (io.prim_out || io.hits || io.normal_out) && (word_prefix || prefix16) && idx_tmp && io.t_out;
+    const bool can_rank = (io.prim_out || io.hits || io.normal_out) && (word_prefix || prefix16) && idx_tmp;
+    // prim and nothing else that k_rank makes (no hit list, no normals): the waves of k_walk rank the rays they retired as they leave,
+    // where the batch allows it (launch_walk); k_rank, which also reads t, stays for everything else
     const bool idx32 = trace_idx32(g);
-    launch_walk(g, mips, io, counters, phase, want_rank ? idx_tmp : nullptr, idx32, s, queue);
-    if (want_rank) {
+    const bool in_walk = can_rank && ring && ring->cap && io.prim_out && !io.hits && !io.normal_out && idx32;
+    const bool want_rank = can_rank && (io.t_out || in_walk);
+    WalkRank wr;
+    if (in_walk) { wr.words = mips.w0; wr.word_prefix = word_prefix; wr.prefix16 = prefix16; wr.prim_out = io.prim_out; wr.ring = *ring; }
+    const bool ranked = launch_walk(g, mips, io, counters, phase, want_rank ? idx_tmp : nullptr, idx32, s, queue, in_walk ? &wr : nullptr);
+    if (want_rank && !ranked && !io.t_out) return false;  // (the caller gave a ring and kept no t: see vx_internal.h)
+    if (want_rank && !ranked) {
         if (io.hits && io.nhits) (void)hipMemsetAsync(io.nhits, 0, sizeof(unsigned long long), s);
         const unsigned rthreads = io.hits ? 1024u : 256u;  // the hit list's compaction touches the global counter once per workgroup
         const dim3 rgrid((unsigned)((nrays + rthreads - 1) / rthreads)), rblock(rthreads);
         VX_KL(k_rank, rgrid, rblock, 0, s, io.t_out, (const void*)idx_tmp, idx32 ? 1 : 0, nrays, g, mips.w0, word_prefix, io.rays, io.cam_dev, io.prim_out, io.normal_out,
               io.hits, io.nhits, prefix16);
     }
+    return true;
 }
 
 }  // namespace vx

@@ -415,13 +415,19 @@ struct WalkCold {
     const Camera* cam;
     const float* tmax_per_ray;    // null: tmax
     float tmax;
-    uint32_t pad;
+    uint32_t ring_cap;            // rank epilogue: chunk-ring entries per wave (0: no epilogue, and rank_prim is null)
     uint64_t ray_base;            // index of this launch's first ray in the caller's batch (primary rays: pixel index)
     float* t_out;
     void* idx_out;                // IdxT per ray: voxel index of the hit, all ones = miss
     uint8_t* shadowed_out;
     unsigned long long* next_item;   // work counter
     unsigned long long* next_zero;   // the NEXT launch's work counter: cleared by this launch (two counters alternate: no memset between traces)
+    // rank epilogue (32-bit voxel indices only): every wave ranks the rays of the chunks it drew, from idx_out, as it leaves
+    uint32_t* ring;                  // [waves][ring_cap]: the dynamic chunks a wave drew -- first ray (a multiple of 64) | ceil(len / 64) - 1
+    uint32_t* rank_prim;             // prim per ray (all ones: miss)
+    const uint32_t* rank_words;      // the reference-layout bitmask ...
+    const uint32_t* rank_prefix;     // ... its word prefix (may be null with prefix16) ...
+    const uint32_t* rank_prefix16;   // ... and every 16th entry of that, dense (optional)
 };
 struct WalkParams {
     WalkHot hot;
@@ -439,7 +445,7 @@ __device__ __forceinline__ WalkColdPtr walk_cold()
 #define VX_W_TS
 #endif
 #ifdef VX_W_TS
-__device__ unsigned long long g_walk_ts[3 * 8192];  // per wave: s_memtime at entry, when its queue ran dry, at exit
+__device__ unsigned long long g_walk_ts[4 * 8192];  // per wave: s_memtime at entry, when its queue ran dry, at exit, and when it left the loop (the rank epilogue lies between that and the exit)
 #endif
 #ifdef VX_W_DEBUG
 // diagnostic build: lane utilisation per code site.  site i: g_walk_dbg[2i] = times a wave executed the site, [2i+1] = lanes active
@@ -831,6 +837,8 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
     bool drained = false;      // no ray left for this wave: the global counter and the wave's chunk are exhausted
     bool drained_global = false;
     uint32_t chunk_cur = 0, chunk_end = 0;
+    constexpr bool kRank = sizeof(IdxT) == 4;  // the rank epilogue reads 32-bit voxel indices back
+    uint32_t nring = 0;                        // dynamic chunks this wave has drawn and recorded in its ring
     const uint32_t nrays = P.nrays;
     // The first chunk of every wave is assigned statically: thousands of waves asking the one counter in the same microsecond
     // queue up behind each other at the memory-side atomic unit.
@@ -871,6 +879,16 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
                     chunk_cur = second + (need - take);
                     chunk_end = base + csz > nrays ? nrays : (uint32_t)(base + csz);
                     if (chunk_cur > chunk_end) chunk_cur = chunk_end;
+                    if (kRank) {
+                        // rank epilogue: remember the chunk (one fire-and-forget store).  A wave whose ring is full takes no further chunk -- for
+                        // it the queue is dry, the other waves take what is left (the host sized the rings so that all of them hold the batch).
+                        const WalkColdPtr C = walk_cold();
+                        const uint32_t cap = C->ring_cap;
+                        if (cap) {
+                            if (lane == 0) C->ring[(uint64_t)(kWavesPerBlock * blockIdx.x + (threadIdx.x >> 6)) * cap + nring] = second | ((chunk_end - second + 63u) / 64u - 1u);
+                            if (++nring >= cap) drained_global = true;
+                        }
+                    }
                 }
                 if (base + csz >= nrays) drained_global = true;
             }
@@ -1049,6 +1067,53 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
         }
         VX_W_T(3)
     }
+#ifdef VX_W_TS
+    const unsigned long long ts_loop_exit = __builtin_readcyclecounter();
+#endif
+    // ---- rank epilogue: prim for the rays this wave retired.  All pieces of a split ray stay in their wave, so the wave has written t and
+    // the voxel index of exactly the rays of the chunks it drew: its static first chunk (recomputed here, nothing was kept for it) and the
+    // chunks in its ring.  No lane state of the walk is live any more; the waves that left early rank while the late ones still walk.
+    if (kRank) {
+        const WalkColdPtr C = walk_cold();
+        uint32_t* prim_out = C->rank_prim;
+        if (prim_out) {
+            // The indices and ring words read below were stored by lanes of THIS wave, as a rule by other lanes than the ones that read them.
+            // Wavefront scope names exactly that.  Workgroup scope, one step wider, is used: it holds whatever lanes the compiler lets the
+            // stores and the loads end up on, and it costs the same -- no instruction on this target (workgroups are not split across CUs:
+            // all vector memory operations of a workgroup go through the CU's one write-through L1 in issue order, and a store updates or
+            // invalidates the line there, which is what the memory model's workgroup scope rests on); the fence is there to keep the
+            // compiler from moving the loads above the loop's stores.  The argument needs the reads below to BE vector loads (the scalar
+            // cache is not coherent with vector stores): they are -- per-lane addresses for the indices, and the ring, which this kernel
+            // writes, is never a candidate for scalar loads (checked in the generated code: global_load_dword for both).  It does not need
+            // the lines to be cold: with a small ring several waves' slots share a line that a neighbour's epilogue may already have read.
+            // Agent scope would write back and invalidate the L1 under the waves that are still walking.
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            const uint32_t* idx = (const uint32_t*)C->idx_out;
+            const uint32_t* words = C->rank_words;
+            const uint32_t* wprefix = C->rank_prefix;
+            const uint32_t* prefix16 = C->rank_prefix16;
+            const uint64_t rb = C->ray_base;
+            const uint32_t wave = kWavesPerBlock * blockIdx.x + (threadIdx.x >> 6);
+            const uint32_t* ring = C->ring + (uint64_t)wave * C->ring_cap;
+            uint32_t csz = nrays / (2u * kWavesPerBlock * gridDim.x);  // the static chunk: the arithmetic at the top of the kernel
+            csz = csz > kChunkMax ? kChunkMax : csz;
+            csz = csz < kChunkRays ? kChunkRays : (csz & ~63u);
+            const uint64_t s0 = (uint64_t)csz * wave;
+            uint32_t c0 = s0 > nrays ? nrays : (uint32_t)s0;
+            uint32_t c1 = s0 + csz > nrays ? nrays : (uint32_t)(s0 + csz);
+            for (uint32_t e = 0;; ++e) {
+                for (uint32_t q = c0 + (uint32_t)lane; q < c1; q += 64u) {  // 64 rays per pass, at most four passes per chunk
+                    const uint32_t i = idx[rb + q];
+                    prim_out[rb + q] = i == 0xFFFFFFFFu ? 0xFFFFFFFFu : voxel_rank(i, words, wprefix, prefix16);
+                }
+                if (e >= nring) break;
+                const uint32_t w = ring[e];
+                c0 = w & ~63u;
+                c1 = c0 + ((w & 63u) + 1u) * 64u;  // (nrays <= 2^31: no overflow)
+                c1 = c1 > nrays ? nrays : c1;
+            }
+        }
+    }
 #ifdef VX_W_DEBUG
     for (int i = 0; i < 8; ++i) {
         unsigned a = dbg_w[i], b = dbg_l[i];
@@ -1060,7 +1125,7 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
 #ifdef VX_W_TS
     {
         const uint32_t wid = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-        if (lane == 0 && wid < 8192u) { g_walk_ts[3 * wid] = ts_begin; g_walk_ts[3 * wid + 1] = ts_drained; g_walk_ts[3 * wid + 2] = __builtin_readcyclecounter(); }
+        if (lane == 0 && wid < 8192u) { g_walk_ts[4 * wid] = ts_begin; g_walk_ts[4 * wid + 1] = ts_drained; g_walk_ts[4 * wid + 2] = __builtin_readcyclecounter(); g_walk_ts[4 * wid + 3] = ts_loop_exit; }
     }
 #endif
 }
@@ -1084,17 +1149,60 @@ namespace vx {
 #endif
 #ifdef VX_W_TS
 }  // namespace vx
-extern "C" int vx_debug_walk_ts(unsigned long long* out /*[3 * 8192]*/)
+extern "C" int vx_debug_walk_ts(unsigned long long* out /*[4 * 8192]*/)
 {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(vx::g_walk_ts), 3 * 8192 * 8) == hipSuccess ? 0 : 1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(vx::g_walk_ts), 4 * 8192 * 8) == hipSuccess ? 0 : 1;
 }
 namespace vx {
 #endif
 
-void launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, unsigned long long* counters /*[2], both zero before the first launch*/,
-                 int* phase /*host: which of the two the next launch draws from*/, void* idx_out, bool idx32, hipStream_t s, WalkQueue* queue)
+// workgroups of the launch that traces n (<= 2^31) rays
+static uint64_t walk_blocks(uint64_t n)
 {
-    if (!io.nrays) return;
+    uint64_t max_blocks = 256ull * VX_W_MINWAVES * 4ull * 64ull / VX_W_BLOCK;  // one resident set of waves
+    // Batches of a few rays per lane: the launch ends with every wave draining the rays it started last, a span of about two mean
+    // ray latencies whatever the batch; with somewhat fewer waves a lane sees at least ~4 rays and the same work drains from fewer
+    // rays in flight (measured on the bench scene, 0.5M / 0.75M / 1M rays: -3 / -8 / -8 %; below ~0.4M rays, where a lane has at
+    // most one or two rays anyway, the full width is faster, and from ~1.1M rays on the rule gives the full width).
+    if (n >= 400000ull && n / 1040ull < max_blocks) max_blocks = n / 1040ull;
+    const uint64_t nblk = (n + VX_W_BLOCK - 1) / VX_W_BLOCK;
+    return nblk > max_blocks ? max_blocks : nblk;
+}
+// rays of the static first chunks of a launch of nblk workgroups over n rays (the kernel's own arithmetic; >= n: the queue is never touched)
+static uint64_t walk_static_rays(uint64_t n, uint64_t nblk)
+{
+    uint32_t csz = (uint32_t)n / (2u * (VX_W_BLOCK / 64u) * (uint32_t)nblk);
+    csz = csz > (uint32_t)VX_W_CHUNK_MAX ? (uint32_t)VX_W_CHUNK_MAX : csz;
+    csz = csz < (uint32_t)VX_W_CHUNK ? (uint32_t)VX_W_CHUNK : (csz & ~63u);
+    return (uint64_t)csz * (VX_W_BLOCK / 64u) * nblk;
+}
+
+// Every dynamic chunk but the batch's last has at least VX_W_CHUNK rays, so waves * cap ring entries hold the batch when
+// waves * cap * VX_W_CHUNK >= the rays behind the static chunks: the queue is empty before every ring is full, and a wave with a full ring
+// only leaves its share to the others.  The choice: four times the mean number of chunks a wave draws (counted in chunks of the minimum
+// size) plus 32 -- waves whose rays are short draw several times the mean -- within 64 MiB for all rings.
+uint32_t walk_ring_cap(uint64_t nrays, uint32_t* waves)
+{
+    *waves = 0;
+    if (!nrays || nrays > 0x80000000ull) return 0;  // one launch only
+    const uint64_t nblk = walk_blocks(nrays), nw = nblk * (VX_W_BLOCK / 64u);
+    const uint64_t sr = walk_static_rays(nrays, nblk), dyn = sr >= nrays ? 0ull : nrays - sr;
+    const uint64_t per_wave = (uint64_t)VX_W_CHUNK * nw;
+    uint64_t cap = 4ull * ((dyn + per_wave - 1) / per_wave) + 32ull;
+    const char* env_ring = getenv("VOXHIP_TRACE_RING");  // test hook: the entries per wave (0: keep k_rank)
+    if (env_ring) { const int v = atoi(env_ring); cap = v > 0 ? (uint64_t)v : 0ull; }
+    const uint64_t most = (64ull << 20) / 4ull / nw;
+    cap = cap > most ? most : cap;
+    if (!cap || cap * per_wave < dyn) return 0;
+    *waves = (uint32_t)nw;
+    return (uint32_t)cap;
+}
+
+// Returns true when the launch ranked the hits itself (rank given, and usable for this batch): prim is written, no k_rank is needed.
+bool launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, unsigned long long* counters /*[2], both zero before the first launch*/,
+                 int* phase /*host: which of the two the next launch draws from*/, void* idx_out, bool idx32, hipStream_t s, WalkQueue* queue, const WalkRank* rank)
+{
+    if (!io.nrays) return false;
     const uint64_t n1 = (uint64_t)mips.d1[0] * mips.d1[1] * mips.d1[2], n2 = (uint64_t)mips.d2[0] * mips.d2[1] * mips.d2[2];
     const uint32_t m1_words = (uint32_t)((n1 + 31) / 32), m2_words = (uint32_t)((n2 + 31) / 32);
     // VOXHIP_TRACE_LDS=0 forces the global-memory mips (the path every grid above ~550^3 takes) -- used by the parity tests
@@ -1122,6 +1230,19 @@ void launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, 
     P.cold.t_out = io.t_out;
     P.cold.idx_out = idx_out;
     P.cold.shadowed_out = io.shadowed_out;
+    // the rank epilogue: decided by the caller (walk_ring_cap, once per batch); here only what the kernel itself relies on is checked --
+    // 32-bit indices, one launch, and a ring laid out for exactly this launch's waves
+    bool ranked = false;
+    if (rank && idx32 && idx_out && rank->prim_out && rank->words && (rank->word_prefix || rank->prefix16) && rank->ring.words && rank->ring.cap &&
+        io.nrays <= 0x80000000ull && rank->ring.waves == walk_blocks(io.nrays) * (VX_W_BLOCK / 64u)) {
+        P.cold.ring = rank->ring.words;
+        P.cold.ring_cap = rank->ring.cap;
+        P.cold.rank_prim = rank->prim_out;
+        P.cold.rank_words = rank->words;
+        P.cold.rank_prefix = rank->word_prefix;
+        P.cold.rank_prefix16 = rank->prefix16;
+        ranked = true;
+    }
 
     const size_t shmem = lds ? (size_t)(m1_words + m2_words) * 4 : 0;
     // one launch per 2^31 rays: ray indices inside the kernel are 32-bit
@@ -1132,20 +1253,10 @@ void launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, 
         P.cold.next_item = counters + (*phase & 1);
         P.cold.next_zero = counters + ((*phase & 1) ^ 1);
         *phase ^= 1;
-        uint64_t max_blocks = 256ull * VX_W_MINWAVES * 4ull * 64ull / VX_W_BLOCK;  // one resident set of waves
-        // Batches of a few rays per lane: the launch ends with every wave draining the rays it started last, a span of about two mean
-        // ray latencies whatever the batch; with somewhat fewer waves a lane sees at least ~4 rays and the same work drains from fewer
-        // rays in flight (measured on the bench scene, 0.5M / 0.75M / 1M rays: -3 / -8 / -8 %; below ~0.4M rays, where a lane has at
-        // most one or two rays anyway, the full width is faster, and from ~1.1M rays on the rule gives the full width).
-        if (n >= 400000ull && n / 1040ull < max_blocks) max_blocks = n / 1040ull;
-        uint64_t nblk = (n + VX_W_BLOCK - 1) / VX_W_BLOCK;
-        if (nblk > max_blocks) nblk = max_blocks;
+        const uint64_t nblk = walk_blocks(n);
         const dim3 grid((unsigned)nblk), block(VX_W_BLOCK);
         if (queue) {  // the work counter of this launch and the value it reaches when the last chunk of rays has been handed out (the kernel's own arithmetic)
-            uint32_t csz = (uint32_t)n / (2u * (VX_W_BLOCK / 64u) * (uint32_t)nblk);
-            csz = csz > (uint32_t)VX_W_CHUNK_MAX ? (uint32_t)VX_W_CHUNK_MAX : csz;
-            csz = csz < (uint32_t)VX_W_CHUNK ? (uint32_t)VX_W_CHUNK : (csz & ~63u);
-            const uint64_t sr = (uint64_t)csz * (VX_W_BLOCK / 64u) * nblk;
+            const uint64_t sr = walk_static_rays(n, nblk);
             queue->counter = P.cold.next_item;
             queue->dry_at = sr >= n ? 0ull : n - sr;
         }
@@ -1157,6 +1268,7 @@ void launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, 
             if (idx32) VX_KL((k_walk<false, uint32_t>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long>), grid, block, shmem, s, P);
         }
     }
+    return ranked;
 }
 
 }  // namespace vx

@@ -24,9 +24,9 @@ for n in (1_000_000, 8_000_000):
         print("  %-20s wave-execs %10d (%.2f per ray)  lanes %11d (%.2f per ray)  utilisation %.3f" % (nm, w, w / n, l, l / n, l / (64.0 * w) if w else 0))
     c = a[16:20]; tot = float(sum(c)) or 1.0
     print("  wave cycles: refill %.1f%%  walk %.1f%%  brick %.1f%%  retire %.1f%%   (total %.3g)" % tuple([100 * x / tot for x in c] + [tot]))
-    ts = (C.c_ulonglong * (3 * 8192))()
+    ts = (C.c_ulonglong * (4 * 8192))()
     if hasattr(L, "vx_debug_walk_ts") and L.vx_debug_walk_ts(ts) == 0:
-        a = np.frombuffer(ts, dtype=np.uint64).reshape(8192, 3).astype(np.float64)
+        a = np.frombuffer(ts, dtype=np.uint64).reshape(8192, 4).astype(np.float64)
         a = a[a[:, 2] > 0]
         # (s_memtime bases differ between XCDs: only differences within one wave mean anything)
         d = np.where(a[:, 1] > 0, a[:, 1] - a[:, 0], a[:, 2] - a[:, 0]) / 2400.0
