@@ -380,7 +380,18 @@ void vx_octree_free(vx_octree* o);
  * For every ray the closest accepted hit over all occupied voxels' AABBs:  t = hitAabb() of that box,
  * accepted iff t > 0 and tmin <= t <= tmax;  prim = index of the box in vx_grid_aabbs() order of the Bool grid
  * (== gl_PrimitiveID); miss: t = -1, prim = 0xFFFFFFFF.  Rays: 6 float32 each (origin xyz, direction xyz).
- * The reference's ray interval is tmin 0.001, tmax 10000 (raytrace.rgen:50-51).                               */
+ * The reference's ray interval is tmin 0.001, tmax 10000 (raytrace.rgen:50-51).
+ *
+ * Non-finite rays.  A ray is non-finite when any of its six components is NaN (any sign, any payload), +Inf or -Inf, whether it was
+ * read from a ray buffer or generated from the camera matrices.  EVERY ray query of this header -- vx_trace*, vx_trace_multi*,
+ * vx_octree_trace*, vx_bvh_trace*, vx_bvh_trace_multi*, vx_tlas_trace*, vx_tlas_trace_multi* and the frames of vx_render_* -- reports a
+ * miss for it: t = -1, prim / instance = 0xFFFFFFFF, normal and bary zero, shadowed = 0, count = 0 with every list slot padded, no
+ * entry in the compacted hit list and no part in num_hits; in a frame, the pixel a miss gives (kind 0).  This is a rule of its own, not
+ * the brute force's answer: hitAabb's min / max drop a NaN, so a NaN on one axis (also 0 * inf, from o[a] = +-inf with d[a] = +-inf)
+ * removes that axis from the slab test and the brute force HITS the boxes the other two axes select.  Finite
+ * rays keep every promise of this header unchanged; an all-zero direction is a miss as before.
+ * NaN in the interval: a NaN tmin, tmax or tmax_per_ray[r] accepts nothing (every comparison with NaN fails in the acceptance rule),
+ * so those rays miss as well.  NaN in a multi-hit cursor (after_t) is not specified.                          */
 typedef struct vx_hit { uint32_t ray; uint32_t prim; float t; } vx_hit;
 vx_status vx_trace(const vx_grid* g, const float* host_rays, uint64_t num_rays, float tmin, float tmax,
                    float* host_t /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);

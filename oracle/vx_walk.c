@@ -170,6 +170,11 @@ static void trace_one(const walk_grid* g, const float* ray, float tmin, float tm
     r.tmin = tmin; r.tmax = tmax;
     *t_out = -1.0f;
     *idx_out = ~0ull;
+    /* a non-finite ray (NaN or +-Inf in any of the six components) is a miss (voxhip.h, "Non-finite rays"): it leaves here, before
+     * any integer is derived from its components.  x * 0 is NaN exactly for NaN and +-Inf. */
+    float nf = 0.0f;
+    for (int a = 0; a < 6; ++a) nf += ray[a] * 0.0f;
+    if (nf != nf) return;
     const float ax = fabsf(r.d[0]), ay = fabsf(r.d[1]), az = fabsf(r.d[2]);
     if (!(ax > 0.0f || ay > 0.0f || az > 0.0f) || !g->dim[0] || !g->dim[1] || !g->dim[2]) return;  /* degenerate ray (never hits: see vx_oracle.c) / empty grid */
     r.w = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);

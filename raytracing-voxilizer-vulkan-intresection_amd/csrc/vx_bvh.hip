@@ -342,7 +342,7 @@ __global__ __launch_bounds__(kBvhBlock) void k_bvh_trace(BvhParams P)
                 best = t; bp = id; bk = k; bu = u; bv = v; found = true;
             }
         };
-        bool alive = P.ntri != 0;
+        bool alive = P.ntri != 0 && !ray_nonfinite(ox, oy, oz, dx, dy, dz);  // a non-finite ray is a miss: neither the side list nor a box sees it
         for (uint32_t i = 0; i < P.nill && alive; ++i) test_tri(P.ill[i]);
         if (alive && !(found && P.io.any_hit)) {
             float t0;

@@ -262,7 +262,8 @@ __global__ __launch_bounds__(kMmBlock) void k_bvh_multihit(const BvhMultiParams 
         y.tlow = fmaxf(y.tmin, 0.0f);
         HitList<KC, false> L;
         list_begin(L, keys, lane, o, r);
-        if (P.ntri) blas_multi(P.nodes, P.tris, P.ill, P.nill, y, P.pad, mm_stack, 0u, 0u, L);
+        // (a non-finite ray is a miss: an empty list, before the side list or a box sees it)
+        if (P.ntri && !ray_nonfinite(y.ox, y.oy, y.oz, y.dx, y.dy, y.dz)) blas_multi(P.nodes, P.tris, P.ill, P.nill, y, P.pad, mm_stack, 0u, 0u, L);
         // ---- outputs: K entries per ray, ray-major
         for (uint32_t j = 0; j < K; ++j) {
             const bool have = j < L.n;
@@ -300,7 +301,8 @@ __global__ __launch_bounds__(kMmBlock) void k_tlas_multihit(const TlasMultiParam
         list_begin(L, keys, lane, o, r);
         const float rpad = P.ninst ? P.ray_pad * ord2f(P.small[6]) * fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz)) : 0.0f;
         float t0;
-        bool alive = P.ninst != 0 && tlas_box_enter(P.nodes[0], P.nodes[1], Rw, rpad, tlow, L.bound(), t0);
+        // (a non-finite ray is a miss: an empty list, before a box or an instance sees it)
+        bool alive = P.ninst != 0 && !ray_nonfinite(ox, oy, oz, dx, dy, dz) && tlas_box_enter(P.nodes[0], P.nodes[1], Rw, rpad, tlow, L.bound(), t0);
         uint32_t cur = 0, sp = 0;
         while (alive) {
             const float4 n0 = P.nodes[2ull * cur], n1 = P.nodes[2ull * cur + 1];

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(kMhBlock) void k_multihit(const MultiParams P)
         const float tol = Mx * 9.5367431640625e-07f;  // 16 * 2^-24 * max|coordinate| (vx_walk.hip)
         R.tol = tol;
         float tn = 0.0f, tf = tmax;
-        bool miss = !(ax > 0.0f || ay > 0.0f || az > 0.0f) || !g.nvox;
+        bool miss = !(ax > 0.0f || ay > 0.0f || az > 0.0f) || !g.nvox || ray_nonfinite(ox, oy, oz, dx, dy, dz);  // (miss: nothing below runs)
 #define VX_CLIP(o_, d_, inv_, lo_, hi_)                                                                  \
         {                                                                                                 \
             const float t1 = (((lo_)-tol) - (o_)) * (inv_), t2 = (((hi_) + tol) - (o_)) * (inv_);         \

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kOctBlock) void k_octree_trace(OctParams P)
         const float tmin = P.io.tmin;
         best = P.io.tmax_per_ray ? P.io.tmax_per_ray[r] : P.io.tmax;  // acceptance bound until the first hit (rint:69 + rgen:50-51)
 
-        bool alive = P.nitems != 0;
+        bool alive = P.nitems != 0 && !ray_nonfinite(ox, oy, oz, dx, dy, dz);  // a non-finite ray is a miss: no node is entered for it
         if (alive) {
             const uint32_t c0[3] = {0u, 0u, 0u};
             float t0, t1;

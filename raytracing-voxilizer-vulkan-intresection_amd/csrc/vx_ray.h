@@ -86,6 +86,16 @@ __device__ __forceinline__ void load_ray(bool primary, uint64_t r, const float* 
     }
 }
 
+// The non-finite rule of voxhip.h: a ray with NaN or +-Inf in any of its six components is a miss on every query.  Every ray kernel
+// asks this once per ray in its set-up, right after load_ray, and retires the ray before an integer, an index or an interval is derived
+// from its components.  x * 0 is NaN exactly for NaN (any sign, any payload) and +-Inf, and NaN survives the sum; no finite x can
+// overflow it.  Without fast-math the products may not be folded to 0 (checked in the generated code: six v_mul, one v_cmp_u).
+__device__ __forceinline__ bool ray_nonfinite(float ox, float oy, float oz, float dx, float dy, float dz)
+{
+    const float s = ((ox * 0.0f + oy * 0.0f) + oz * 0.0f) + ((dx * 0.0f + dy * 0.0f) + dz * 0.0f);
+    return s != s;
+}
+
 // The cube-face normal of raytrace2.rchit:60-73 for a hit at t on box bb.
 __device__ __forceinline__ void cube_normal(const float bb[6], float ox, float oy, float oz, float dx, float dy, float dz, float tt, float& n0, float& n1,
                                             float& n2)

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(kTlasBlock) void k_tlas_trace(TlasParams P)
         const float tmin = P.io.tmin, tlow = fmaxf(tmin, 0.0f);
         h.best = P.io.tmax_per_ray ? P.io.tmax_per_ray[r] : P.io.tmax;  // acceptance bound until the first hit
         const float rpad = kRayPad * ord2f(P.small[6]) * fabs_max3(ox, oy, oz);
-        bool alive = P.ninst != 0;
+        bool alive = P.ninst != 0 && !ray_nonfinite(ox, oy, oz, dx, dy, dz);  // a non-finite ray is a miss: no box, no instance sees it
         if (alive) {
             float t0;
             alive = tlas_enter(P.nodes[0], P.nodes[1], Rw, rpad, tlow, h.best, t0);

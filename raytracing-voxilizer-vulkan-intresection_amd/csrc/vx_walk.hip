@@ -347,7 +347,8 @@ __device__ __forceinline__ bool walk_setup(WalkLane<IdxT, WIDE>& R, const GridPa
     const float tol = Mx * 9.5367431640625e-07f;
     R.tol = tol;
     float tn = 0.0f, tf = tmax;
-    bool miss = !(ax > 0.0f || ay > 0.0f || az > 0.0f) || !g.nvox;  // a zero direction never reports a hit (inf/NaN slabs)
+    // a zero direction never reports a hit (inf/NaN slabs); a non-finite ray is a miss by rule and leaves below, before the first cast
+    bool miss = !(ax > 0.0f || ay > 0.0f || az > 0.0f) || !g.nvox || ray_nonfinite(ox, oy, oz, dx, dy, dz);
 #define VX_CLIP(o, d, inv, lo, hi)                                                                   \
     {                                                                                                 \
         const float t1 = (((lo)-tol) - (o)) * (inv), t2 = (((hi) + tol) - (o)) * (inv);               \
