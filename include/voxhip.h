@@ -384,7 +384,7 @@ void vx_octree_free(vx_octree* o);
  *
  * Non-finite rays.  A ray is non-finite when any of its six components is NaN (any sign, any payload), +Inf or -Inf, whether it was
  * read from a ray buffer or generated from the camera matrices.  EVERY ray query of this header -- vx_trace*, vx_trace_multi*,
- * vx_octree_trace*, vx_bvh_trace*, vx_bvh_trace_multi*, vx_tlas_trace*, vx_tlas_trace_multi* and the frames of vx_render_* -- reports a
+ * vx_octree_trace*, vx_octree_trace_multi*, vx_bvh_trace*, vx_bvh_trace_multi*, vx_tlas_trace*, vx_tlas_trace_multi* and the frames of vx_render_* -- reports a
  * miss for it: t = -1, prim / instance = 0xFFFFFFFF, normal and bary zero, shadowed = 0, count = 0 with every list slot padded, no
  * entry in the compacted hit list and no part in num_hits; in a frame, the pixel a miss gives (kind 0).  This is a rule of its own, not
  * the brute force's answer: hitAabb's min / max drop a NaN, so a NaN on one axis (also 0 * inf, from o[a] = +-inf with d[a] = +-inf)
@@ -473,6 +473,31 @@ vx_status vx_octree_trace_ex_device(const vx_octree* o, const vx_trace_args* arg
 vx_status vx_octree_trace_ex(const vx_octree* o, const vx_trace_args* args);         /* host pointers (staged), no `hits` */
 vx_status vx_octree_trace(const vx_octree* o, const float* host_rays, uint64_t num_rays, float tmin, float tmax,
                           float* host_t /*NULL ok*/, uint32_t* host_prim /*NULL ok*/, uint64_t* num_hits /*NULL ok*/);
+
+/* Multi-hit query on the octree: vx_trace_multi's query where the dense grid cannot exist (Grid voxelization refuses more than 2^37 cells
+ * with VX_ERR_CAPACITY).  The struct is vx_multihit_args, unchanged.
+ * List and runs.  The list is what vx_octree_aabbs returns: ascending Morton code, duplicates included.  A RUN is a maximal range of equal
+ * codes; equal codes have identical boxes.  A run stands for ONE voxel, and its prim is the first list index of the run -- the index
+ * vx_octree_trace_ex already reports.  Runs, not list entries, because a voxel touched by five triangles is one voxel to an X-ray:
+ * counting entries would fill the K slots with copies of one box, paging by (t, prim) would need every copy ordered, and the first-hit
+ * query already names a voxel by the first index of its run.
+ * A(r) is the set of runs whose t = hitAabb(box) passes the first-hit query's own acceptance rule: t > 0 and tmin <= t <= tmax, with
+ * tmax_per_ray[r] in place of tmax where given.  A(r) is ordered by (t, prim) ascending: t compared as float, ties to the smaller prim.
+ * With the cursor (after_t[r], after_prim[r]) only the elements STRICTLY after it in that order belong to A(r), for the lists and the
+ * counts alike; (-1, anything) means no cursor.  Outputs per ray, K = max_hits (1..VX_MULTIHIT_MAX):
+ *   t[r*K + j], prim[r*K + j]   the j-th element of A(r) for j < min(K, |A(r)|); the remaining slots are -1.0f and 0xFFFFFFFF;
+ *   count[r]                    |A(r)|, even above K.
+ * Every output is bit-equal to the brute force over the de-duplicated list; without a cursor slot 0 is exactly what vx_octree_trace_ex
+ * gives for t and prim.
+ * Consequences.  On a scene with every axis at or below 65535 cells the distinct boxes are the Bool grid's boxes, so count and the
+ * sequence of t values equal vx_trace_multi's on the same rays; the prim values differ (Morton order here, x-fastest there).  Above
+ * 65535 cells on an axis, the cells that alias to one code (the reference's 16-bit interleave, see above) form one run and count once.
+ * Checks, in this order, each writing nothing: NULL octree or args, K outside 1..VX_MULTIHIT_MAX, exactly one of the two cursor arrays,
+ * any forbidden field of `base` set (any_hit, normal, shadowed, hits, num_hits): VX_ERR_INVALID_ARG.  Zero rays: VX_OK.  An octree without
+ * items: every count 0, every slot padded.  Non-finite rays and NaN intervals: the rule above vx_trace.  Work runs on the octree's
+ * stream; a repeated device call at the same ray count requests no device memory (vx_device_allocations unchanged). */
+vx_status vx_octree_trace_multi_device(const vx_octree* o, const vx_multihit_args* a); /* device pointers, asynchronous on the octree's stream */
+vx_status vx_octree_trace_multi(const vx_octree* o, const vx_multihit_args* a);        /* host pointers, staged like vx_octree_trace_ex */
 
 /* ---- rays on the triangle mesh: the reference's triangle BLAS (hello_vulkan.cpp:596-635, objectToVkGeometryKHR over the model loadModel
  * reads at :197) under raytrace.rchit, as a BVH built on the device.  Rays, ray interval, camera rays and the compacted hit list are those

@@ -64,6 +64,22 @@ public:
     }
     vx_octree* handle() const noexcept { return m_o.get(); }
 
+    // Multi-hit ray query (vx_octree_trace_multi): for each ray (6 floats: origin, direction) the first maxHits (1..32) voxels it meets, ordered
+    // by (t, index in getAabbs() order), into t / prim (maxHits entries per ray, padded with -1 / 0xFFFFFFFF), and the number of all voxels it
+    // meets within [tmin, tmax] into count.  Duplicate items are one voxel: prim is the first index of the run of equal Morton codes.
+    void traceMulti(const std::vector<float>& rays, uint32_t maxHits, float tmin, float tmax, std::vector<float>& t, std::vector<uint32_t>& prim,
+                    std::vector<uint32_t>& count) const
+    {
+        const size_t n = rays.size() / 6;
+        t.assign(n * maxHits, -1.0f);
+        prim.assign(n * maxHits, 0xFFFFFFFFu);
+        count.assign(n, 0u);
+        vx_multihit_args a{};
+        a.base.rays = rays.data(); a.base.num_rays = n; a.base.tmin = tmin; a.base.tmax = tmax;
+        a.base.t = t.data(); a.base.prim = prim.data(); a.max_hits = maxHits; a.count = count.data();
+        vxdetail::check(vx_octree_trace_multi(m_o.get(), &a));
+    }
+
     Octree(const Octree&) = delete;
     Octree& operator=(const Octree&) = delete;
     Octree(Octree&&) noexcept = default;

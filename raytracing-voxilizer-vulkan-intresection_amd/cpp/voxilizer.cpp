@@ -48,6 +48,9 @@
 //                                       --bench, or --materials with --grid vec
 //   --xray FILE.pgm [--size WxH]        how many voxels each camera ray of --render meets (vx_trace_multi's count), as a binary 16-bit PGM
 //                                       (big-endian, min(count, 65535) per pixel); --camera-dump FILE as for --render
+//   --grid octree --octree-xray FILE.pgm [--size WxH]
+//                                       the same picture from the octree (vx_octree_trace_multi's count: duplicate items are one voxel), same
+//                                       file format, --camera-dump FILE as for --render; not with --gpus N > 1 or --bench
 //   --mesh M.obj --mesh-xray FILE.pgm [--size WxH]
 //                                       the same picture of the triangle model itself: how many triangles of M.obj each camera ray crosses
 //                                       (vx_bvh_trace_multi's count), same file format; --mesh then needs no --render
@@ -423,6 +426,20 @@ void write_xray(const vx_grid* grid, const std::string& file, uint32_t W, uint32
     write_counts_pgm(count, file, W, H, "voxel");
 }
 
+// --octree-xray: the same picture from the octree (vx_octree_trace_multi's count)
+void write_octree_xray(const vx_octree* octree, const std::string& file, uint32_t W, uint32_t H, const std::string& cameraDump)
+{
+    float vi[16], pi[16];
+    xray_camera(vi, pi, W, H, cameraDump);
+    std::vector<uint32_t> count((size_t)W * H);
+    vx_multihit_args a{};
+    a.base.view_inverse = vi; a.base.proj_inverse = pi; a.base.width = W; a.base.height = H; a.base.tmin = 0.001f; a.base.tmax = 10000.0f;  // rgen:50-51
+    a.max_hits = 1;
+    a.count = count.data();
+    vxdetail::check(vx_octree_trace_multi(octree, &a));
+    write_counts_pgm(count, file, W, H, "voxel");
+}
+
 // --mesh-xray: the same picture of the --mesh model itself, the triangles every primary ray crosses (vx_bvh_trace_multi's count)
 void write_mesh_xray(const vx_bvh* bvh, const std::string& file, uint32_t W, uint32_t H, const std::string& cameraDump)
 {
@@ -512,14 +529,14 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
                      argv[0]);
         return 2;
     }
     const std::string path = argv[1];
     float vs = 0.f;
     try { vs = std::stof(argv[2]); } catch (const std::exception&) { std::fprintf(stderr, "invalid voxel size '%s'\n", argv[2]); return 2; }
-    std::string grid = "bool", sdfFile, surfaceFile, componentsFile, xrayFile, meshXrayFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
+    std::string grid = "bool", sdfFile, surfaceFile, componentsFile, xrayFile, octreeXrayFile, meshXrayFile, dumpFile, renderFile, matDump, cameraDump, meshFile, instFile;
     uint32_t rw = 1280, rh = 720;  // main.cpp:72-73
     bool parallel = false, materials = false, logical = false, attributes = false, solid = false;
     int gpus = 1, connectivity = 6;
@@ -543,6 +560,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
         else if (!std::strcmp(argv[i], "--components") && i + 1 < argc) componentsFile = argv[++i];
         else if (!std::strcmp(argv[i], "--xray") && i + 1 < argc) xrayFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--octree-xray") && i + 1 < argc) octreeXrayFile = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh-xray") && i + 1 < argc) meshXrayFile = argv[++i];
         else if (!std::strcmp(argv[i], "--connectivity") && i + 1 < argc) connectivity = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) { frames = std::atol(argv[++i]); if (frames < 1) { std::fprintf(stderr, "--frames needs N >= 1\n"); return 2; } }
@@ -584,7 +602,11 @@ int main(int argc, char** argv)
         return 2;
     }
     if (!xrayFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
-        std::fprintf(stderr, "--xray counts the voxels of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        std::fprintf(stderr, "--xray counts the voxels of one grid on one device: not with --grid octree (use --octree-xray there), --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (!octreeXrayFile.empty() && (grid != "octree" || gpus > 1 || benchRuns > 0)) {
+        std::fprintf(stderr, "--octree-xray counts the voxels of the octree on one device: it needs --grid octree, and not --gpus N > 1 or --bench\n");
         return 2;
     }
     if (connectivity != 6 && connectivity != 26) { std::fprintf(stderr, "--connectivity must be 6 or 26\n"); return 2; }
@@ -663,6 +685,7 @@ int main(int argc, char** argv)
             const std::vector<Aabb> aabbs = tree.getAabbs();
             std::printf("[voxhip] octree: %zu AABBs\n", aabbs.size());
             dump(dumpFile, aabbs);
+            if (!octreeXrayFile.empty()) write_octree_xray(tree.handle(), octreeXrayFile, rw, rh, cameraDump);
             if (!renderFile.empty()) {  // the same picture of the octree's list, traced on the tree itself
                 RenderOpts ro;
                 ro.cameraDump = cameraDump;

@@ -2675,10 +2675,10 @@ vx_status vx_trace_ex(const vx_grid* gc, const vx_trace_args* args)
 }
 
 // ---- multi-hit query (vx_multihit.hip) -----------------------------------------------------------------------------
-// the argument checks of vx_trace_multi*, in the header's order; *io receives the ray batch (nrays == 0: nothing to do)
-static vx_status multihit_args_to_io(const vx_grid* g, const vx_multihit_args* a, vx::Camera* cam, vx::TraceIO* io)
+// the argument checks of vx_trace_multi* and vx_octree_trace_multi*, in the header's order; *io receives the ray batch (nrays == 0: nothing to do)
+static vx_status multihit_args_to_io(const void* handle, const vx_multihit_args* a, vx::Camera* cam, vx::TraceIO* io)
 {
-    if (!g || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (!handle || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
     if (a->max_hits < 1 || a->max_hits > VX_MULTIHIT_MAX) return fail(VX_ERR_INVALID_ARG, "max_hits must be 1..VX_MULTIHIT_MAX");
     if ((a->after_t != nullptr) != (a->after_prim != nullptr)) return fail(VX_ERR_INVALID_ARG, "the cursor needs both after_t and after_prim");
     const vx_trace_args& b = a->base;
@@ -2720,22 +2720,20 @@ vx_status vx_trace_multi_device(const vx_grid* gc, const vx_multihit_args* a)
     return multihit_common(g, io, a, a->count, a->after_t, a->after_prim);
 }
 
-vx_status vx_trace_multi(const vx_grid* gc, const vx_multihit_args* a)
+// host-buffer variant of a multi-hit query: every non-null array through pooled device memory of `home` (the handle: its device and
+// stream), as trace_ex_staged does for one entry per ray; run(io, count, after_t, after_prim) queues the query on the staged arrays
+extern "C++" {
+template <class Run>
+static vx_status multihit_staged(const Home& home, const vx_multihit_args* a, vx::TraceIO io, Run run)
 {
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(gc, a, &cam, &io));
     const uint64_t n = io.nrays;
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
     const size_t K = a->max_hits;
-    // every non-null array through pooled device memory on the grid's stream, as trace_ex_staged does for one entry per ray
-    DevBuf dr{g}, dtm{g}, dt{g}, dp{g}, dc{g}, dat{g}, dap{g};
+    hipStream_t stream = home.stream;
+    DevBuf dr{&home}, dtm{&home}, dt{&home}, dp{&home}, dc{&home}, dat{&home}, dap{&home};
     auto upload = [&](DevBuf& b, const void* host, size_t bytes) -> hipError_t {
         if (!host) return hipSuccess;
         const hipError_t e = b.ensure(bytes);
-        return e == hipSuccess ? hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, g->stream) : e;
+        return e == hipSuccess ? hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, stream) : e;
     };
     VX_HIP(upload(dr, a->base.rays, (size_t)n * 24));
     VX_HIP(upload(dtm, a->base.tmax_per_ray, (size_t)n * 4));
@@ -2748,16 +2746,30 @@ vx_status vx_trace_multi(const vx_grid* gc, const vx_multihit_args* a)
     if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
     io.t_out = dt.as<float>();
     io.prim_out = dp.as<uint32_t>();
-    const vx_status st = multihit_common(g, io, a, dc.as<uint32_t>(), dat.as<float>(), dap.as<uint32_t>());
+    const vx_status st = run(io, dc.as<uint32_t>(), dat.as<float>(), dap.as<uint32_t>());
     if (st != VX_OK) {
-        (void)hipStreamSynchronize(g->stream);  // the uploads read the caller's arrays
+        (void)hipStreamSynchronize(stream);  // the uploads read the caller's arrays
         return st;
     }
-    if (a->base.t) VX_HIP(hipMemcpyAsync(a->base.t, dt.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, g->stream));
-    if (a->base.prim) VX_HIP(hipMemcpyAsync(a->base.prim, dp.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, g->stream));
-    if (a->count) VX_HIP(hipMemcpyAsync(a->count, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream));
-    VX_HIP(hipStreamSynchronize(g->stream));
+    if (a->base.t) VX_HIP(hipMemcpyAsync(a->base.t, dt.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, stream));
+    if (a->base.prim) VX_HIP(hipMemcpyAsync(a->base.prim, dp.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, stream));
+    if (a->count) VX_HIP(hipMemcpyAsync(a->count, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    VX_HIP(hipStreamSynchronize(stream));
     return VX_OK;
+}
+}  // extern "C++"
+
+vx_status vx_trace_multi(const vx_grid* gc, const vx_multihit_args* a)
+{
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(multihit_args_to_io(gc, a, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return multihit_staged(*g, a, io, [&](const vx::TraceIO& sio, uint32_t* count, const float* after_t, const uint32_t* after_prim) {
+        return multihit_common(g, sio, a, count, after_t, after_prim);
+    });
 }
 
 // vx_trace / vx_octree_trace: t and prim of a host ray buffer through the handle's host-buffer extended query, hits counted on the host
@@ -2979,6 +2991,40 @@ vx_status vx_octree_trace(const vx_octree* oc, const float* host_rays, uint64_t 
 {
     if (!oc || (nrays && !host_rays)) return fail(VX_ERR_INVALID_ARG, "null argument");
     return trace_simple(host_rays, nrays, tmin, tmax, host_t, host_prim, num_hits, [&](const vx_trace_args* a) { return vx_octree_trace_ex(oc, a); });
+}
+
+// ---- multi-hit query on the octree (vx_octmulti.hip): vx_trace_multi's contract over the runs of equal codes of the list
+static vx_status octree_multihit_common(vx_octree* o, vx::TraceIO io, uint32_t K, uint32_t* count, const float* after_t, const uint32_t* after_prim)
+{
+    VX_TRY(upload_camera(o->camera, o->stream, io));
+    const uint64_t nitems = o->nnodes == 0 ? 0 : o->nitems;  // the list vx_octree_aabbs returns
+    vx::launch_octree_multihit(o->dnodes, o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, K, count, after_t, after_prim, o->stream);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+vx_status vx_octree_trace_multi_device(const vx_octree* oc, const vx_multihit_args* a)
+{
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(multihit_args_to_io(oc, a, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    vx_octree* o = const_cast<vx_octree*>(oc);
+    DeviceGuard dg(o->device);
+    return octree_multihit_common(o, io, a->max_hits, a->count, a->after_t, a->after_prim);
+}
+
+vx_status vx_octree_trace_multi(const vx_octree* oc, const vx_multihit_args* a)
+{
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(multihit_args_to_io(oc, a, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    vx_octree* o = const_cast<vx_octree*>(oc);
+    DeviceGuard dg(o->device);
+    return multihit_staged(*o, a, io, [&](const vx::TraceIO& sio, uint32_t* count, const float* after_t, const uint32_t* after_prim) {
+        return octree_multihit_common(o, sio, a->max_hits, count, after_t, after_prim);
+    });
 }
 
 void vx_octree_free(vx_octree* o)

@@ -219,6 +219,10 @@ void launch_multihit(const GridParams& g, const TraceMips& mips, const uint32_t*
 // prim = index in vx_octree_aabbs order); nodes may be null / nitems 0: every ray misses.
 void launch_octree_trace(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,
                          hipStream_t s);
+// Multi-hit query on the octree (vx_octmulti.hip): launch_multihit's outputs and cursor over the runs of equal codes of the item list (a run
+// is one voxel, prim = its first list index).  nodes / items / nitems as for launch_octree_trace.
+void launch_octree_multihit(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,
+                            uint32_t K, uint32_t* count, const float* after_t, const uint32_t* after_prim, hipStream_t s);
 
 // Triangle BVH (vx_bvh.hip).  Build, all on `s`: launch_bvh_prep (box6 = ordered-uint bounds of all triangles, initialised to ~0 x3 / 0 x3;
 // *err |= 1 when an index leaves [0, nv); keys = Morton code << 32 | triangle), launch_sort_u64 over 62 bits, launch_bvh_tree (radix tree,

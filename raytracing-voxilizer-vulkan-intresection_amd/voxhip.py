@@ -70,6 +70,60 @@ def _trace_ex(fn, h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want, bvh=
     return out
 
 
+def _trace_multi(fn, h, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want):
+    """vx_trace_multi / vx_octree_trace_multi on host arrays -> dict of the requested outputs: t (n, K) float32 and prim (n, K) uint32, padded
+    with -1 / 0xFFFFFFFF, count (n,) uint32"""
+    a = MultiHitArgs()
+    keep = []
+    if rays is not None:
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        keep.append(r)
+        a.base.rays, a.base.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
+    else:
+        vi, pi, w, h_ = camera
+        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
+        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
+        keep += [cvi, cpi]
+        a.base.view_inverse, a.base.proj_inverse, a.base.width, a.base.height, n = cvi, cpi, w, h_, w * h_
+    a.base.tmin, a.base.tmax, a.max_hits = np.float32(tmin), np.float32(tmax), int(max_hits)
+    if tmax_per_ray is not None:
+        tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
+        keep.append(tm)
+        a.base.tmax_per_ray = tm.ctypes.data
+    if after is not None:
+        at = np.ascontiguousarray(after[0], dtype=np.float32)
+        ap = np.ascontiguousarray(after[1], dtype=np.uint32)
+        if at.shape != (n,) or ap.shape != (n,):
+            raise ValueError("after = (after_t, after_prim), one entry per ray each")
+        keep += [at, ap]
+        a.after_t, a.after_prim = at.ctypes.data, ap.ctypes.data
+    k = max(int(max_hits), 0)
+    out = {}
+    if "t" in want:
+        out["t"] = np.zeros((n, k), np.float32); a.base.t = out["t"].ctypes.data
+    if "prim" in want:
+        out["prim"] = np.zeros((n, k), np.uint32); a.base.prim = out["prim"].ctypes.data
+    if "count" in want:
+        out["count"] = np.zeros(n, np.uint32); a.count = out["count"].ctypes.data
+    _check(fn(h, C.byref(a)))
+    return out
+
+
+def _trace_multi_device(fn, h, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax, tmax_per_ray_ptr, after_t_ptr, after_prim_ptr, camera):
+    """vx_trace_multi_device / vx_octree_trace_multi_device on raw device pointers"""
+    a = MultiHitArgs()
+    if camera is not None:
+        vi, pi, w, h_ = camera
+        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
+        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
+        a.base.view_inverse, a.base.proj_inverse, a.base.width, a.base.height = cvi, cpi, w, h_
+    else:
+        a.base.rays, a.base.num_rays = rays_ptr, nrays
+    a.base.tmin, a.base.tmax, a.base.tmax_per_ray, a.max_hits = np.float32(tmin), np.float32(tmax), tmax_per_ray_ptr, int(max_hits)
+    a.base.t, a.base.prim, a.count, a.after_t, a.after_prim = t_ptr, prim_ptr, count_ptr, after_t_ptr, after_prim_ptr
+    _check(fn(h, C.byref(a)))
+
+
 class GridDesc(C.Structure):
     _fields_ = [("dim", C.c_uint64 * 3), ("voxel_size", C.c_float), ("origin", C.c_float * 3), ("bbox_min", C.c_float * 3),
                 ("bbox_max", C.c_float * 3), ("bbox_center", C.c_float * 3), ("num_words", C.c_uint64), ("set_calls", C.c_uint64),
@@ -170,7 +224,7 @@ SYMBOLS = [
     "vx_octree_root_bounds", "vx_octree_aabbs", "vx_octree_aabbs_device", "vx_octree_free",
     "vx_trace", "vx_trace_device", "vx_trace_primary_device", "vx_trace_ex", "vx_trace_ex_device",
     "vx_trace_multi", "vx_trace_multi_device",
-    "vx_octree_trace", "vx_octree_trace_ex", "vx_octree_trace_ex_device",
+    "vx_octree_trace", "vx_octree_trace_ex", "vx_octree_trace_ex_device", "vx_octree_trace_multi", "vx_octree_trace_multi_device",
     "vx_bvh_build", "vx_bvh_build_into", "vx_bvh_num_triangles", "vx_bvh_num_nodes", "vx_bvh_bytes", "vx_bvh_height", "vx_bvh_num_ill_conditioned", "vx_bvh_root_bounds",
     "vx_bvh_nodes", "vx_bvh_leaf_triangles", "vx_bvh_nodes_device", "vx_bvh_trace_ex_device", "vx_bvh_trace_ex", "vx_bvh_trace",
     "vx_bvh_trace_multi", "vx_bvh_trace_multi_device", "vx_bvh_free",
@@ -333,6 +387,8 @@ def lib():
     L.vx_octree_trace.argtypes = [vp, vp, C.c_uint64, C.c_float, C.c_float, vp, vp, u64p]
     L.vx_octree_trace_ex.argtypes = [vp, C.POINTER(TraceArgs)]
     L.vx_octree_trace_ex_device.argtypes = [vp, C.POINTER(TraceArgs)]
+    L.vx_octree_trace_multi.argtypes = [vp, C.POINTER(MultiHitArgs)]
+    L.vx_octree_trace_multi_device.argtypes = [vp, C.POINTER(MultiHitArgs)]
     L.vx_bvh_build.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
     L.vx_bvh_build_into.argtypes = [vp, vp]
     for n in ("vx_bvh_num_triangles", "vx_bvh_num_nodes", "vx_bvh_bytes"):
@@ -895,56 +951,14 @@ class Grid:
         """vx_trace_multi on host arrays: per ray the first max_hits accepted hits in (t, prim) order and the number of all of them -> dict
         of the requested outputs: t (n, K) float32 and prim (n, K) uint32, padded with -1 / 0xFFFFFFFF, count (n,) uint32.  after =
         (after_t, after_prim): per-ray cursor, only hits strictly behind it are listed and counted."""
-        a = MultiHitArgs()
-        keep = []
-        if rays is not None:
-            r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
-            keep.append(r)
-            a.base.rays, a.base.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
-        else:
-            vi, pi, w, h_ = camera
-            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-            keep += [cvi, cpi]
-            a.base.view_inverse, a.base.proj_inverse, a.base.width, a.base.height, n = cvi, cpi, w, h_, w * h_
-        a.base.tmin, a.base.tmax, a.max_hits = np.float32(tmin), np.float32(tmax), int(max_hits)
-        if tmax_per_ray is not None:
-            tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
-            keep.append(tm)
-            a.base.tmax_per_ray = tm.ctypes.data
-        if after is not None:
-            at = np.ascontiguousarray(after[0], dtype=np.float32)
-            ap = np.ascontiguousarray(after[1], dtype=np.uint32)
-            if at.shape != (n,) or ap.shape != (n,):
-                raise ValueError("after = (after_t, after_prim), one entry per ray each")
-            keep += [at, ap]
-            a.after_t, a.after_prim = at.ctypes.data, ap.ctypes.data
-        k = max(int(max_hits), 0)
-        out = {}
-        if "t" in want:
-            out["t"] = np.zeros((n, k), np.float32); a.base.t = out["t"].ctypes.data
-        if "prim" in want:
-            out["prim"] = np.zeros((n, k), np.uint32); a.base.prim = out["prim"].ctypes.data
-        if "count" in want:
-            out["count"] = np.zeros(n, np.uint32); a.count = out["count"].ctypes.data
-        _check(lib().vx_trace_multi(self.h, C.byref(a)))
-        return out
+        return _trace_multi(lib().vx_trace_multi, self.h, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want)
 
     def trace_multi_device(self, rays_ptr, nrays, max_hits, t_ptr=None, prim_ptr=None, count_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None,
                            after_t_ptr=None, after_prim_ptr=None, camera=None):
         """vx_trace_multi_device on raw device pointers, asynchronous on the grid's stream; t / prim hold max_hits entries per ray.
         camera = (view_inv, proj_inv, width, height) in place of rays_ptr / nrays."""
-        a = MultiHitArgs()
-        if camera is not None:
-            vi, pi, w, h_ = camera
-            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-            a.base.view_inverse, a.base.proj_inverse, a.base.width, a.base.height = cvi, cpi, w, h_
-        else:
-            a.base.rays, a.base.num_rays = rays_ptr, nrays
-        a.base.tmin, a.base.tmax, a.base.tmax_per_ray, a.max_hits = np.float32(tmin), np.float32(tmax), tmax_per_ray_ptr, int(max_hits)
-        a.base.t, a.base.prim, a.count, a.after_t, a.after_prim = t_ptr, prim_ptr, count_ptr, after_t_ptr, after_prim_ptr
-        _check(lib().vx_trace_multi_device(self.h, C.byref(a)))
+        _trace_multi_device(lib().vx_trace_multi_device, self.h, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax, tmax_per_ray_ptr,
+                            after_t_ptr, after_prim_ptr, camera)
 
     def trace_primary_device(self, view_inv, proj_inv, width, height, t_ptr, prim_ptr=None, tmin=0.001, tmax=10000.0):
         vi = (C.c_float * 16)(*[float(x) for x in np.asarray(view_inv).reshape(16)])
@@ -1125,6 +1139,18 @@ class Octree:
         a.tmax_per_ray, a.t, a.prim, a.normal, a.shadowed = tmax_per_ray_ptr, t_ptr, prim_ptr, normal_ptr, shadowed_ptr
         a.hits, a.num_hits = hits_ptr, nhits_ptr
         _check(lib().vx_octree_trace_ex_device(self.h, C.byref(a)))
+
+    def trace_multi(self, rays=None, camera=None, max_hits=8, tmin=0.001, tmax=10000.0, tmax_per_ray=None, after=None, want=("t", "prim", "count")):
+        """vx_octree_trace_multi on host arrays: per ray the first max_hits accepted voxels in (t, prim) order and the number of all of them
+        -> dict as Grid.trace_multi gives it.  A voxel is a run of equal codes of the aabbs() list, prim the first list index of its run."""
+        return _trace_multi(lib().vx_octree_trace_multi, self.h, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want)
+
+    def trace_multi_device(self, rays_ptr, nrays, max_hits, t_ptr=None, prim_ptr=None, count_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None,
+                           after_t_ptr=None, after_prim_ptr=None, camera=None):
+        """vx_octree_trace_multi_device on raw device pointers, asynchronous on the octree's stream; t / prim hold max_hits entries per ray.
+        camera = (view_inv, proj_inv, width, height) in place of rays_ptr / nrays."""
+        _trace_multi_device(lib().vx_octree_trace_multi_device, self.h, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax,
+                            tmax_per_ray_ptr, after_t_ptr, after_prim_ptr, camera)
 
     def free(self):
         if self.h:
