@@ -451,7 +451,7 @@ struct vx_grid : Home {
     DevBuf lcnt{this} /*set bits per 16-word line of the bitmask (the brick kernel of a whole Vec build): wp16 is their scan*/;
     DevBuf wring{this} /*k_walk's rank epilogue: per wave the chunks of rays it drew (walk_ring_cap words each); scratch of one ray batch*/;
     DevBuf ext{this} /*high bits of the candidate ranges*/, units{this}, ubase{this}, btri{this}, umask{this}, bhits{this} /*hits per block of 64 units*/;
-    DevBuf hbase{this} /*their exclusive scan*/, scantmp{this}, small{this}, vec{this}, matids{this}, mattmp{this};
+    DevBuf hbase{this} /*their exclusive scan*/, scantmp{this}, hscantmp{this} /*status block of a block-hit scan queued with the list (list_scan)*/, small{this}, vec{this}, matids{this}, mattmp{this};
     // solid voxelization (vx_solid.hip): padded mask, exterior, H in the reference's layout (padded rows only) and the word prefix over H
     DevBuf solid_m{this}, solid_e{this}, solid_h{this}, solid_pre{this}, solid_agg{this} /*the column scans' per-chunk words*/;
     // distance fields (vx_distance.hip): the envelopes' stacks, and the field itself for the host variants
@@ -503,7 +503,9 @@ struct vx_grid : Home {
     hipEvent_t ev_ready = nullptr, ev_list = nullptr;
     bool list_deferred = false;  // the emission has not been queued yet (its arguments: ld)
     bool list_pending = false;   // it has been queued on `side`; the main stream has not waited for ev_list yet
-    struct { uint32_t ntri = 0; bool ext = false; vx_aabb* tgt = nullptr; uint64_t cap = 0; bool from_mask = false; } ld;  // from_mask: vx_grid_aabbs_device_async (K4)
+    // from_mask: vx_grid_aabbs_device_async (K4).  scan_blocks: hbase has not been written by the build -- the host took the hit count from the
+    // voxelizer's counters (k_build_bricks3) -- and the scan of the build's scan_blocks block-hit counts goes in front of the emission
+    struct { uint32_t ntri = 0; bool ext = false; vx_aabb* tgt = nullptr; uint64_t cap = 0; bool from_mask = false; uint64_t scan_blocks = 0; } ld;
     hipError_t side_init()
     {
         if (side) return hipSuccess;
@@ -516,8 +518,17 @@ struct vx_grid : Home {
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_list, evf);
         return e;
     }
+    // the hit bases the emission reads, where the build left their scan to the list: queued once, on the stream the emission follows on
+    // (a status block of its own, hscantmp, sized by the build: the main stream's scans use scantmp at the same time)
+    void list_scan(hipStream_t st)
+    {
+        if (ld.from_mask || !ld.scan_blocks) return;
+        (void)vx::launch_scan_u32(bhits.as<uint32_t>(), hbase.as<uint32_t>(), ld.scan_blocks, false, hscantmp.p, nullptr, st, true, 0, nullptr, advance_scan_gen(hscantmp, st));
+        ld.scan_blocks = 0;
+    }
     void list_emit(hipStream_t st)
     {
+        list_scan(st);
         if (ld.from_mask) {  // Bool / AABBstruct: the ascending list from the bitmask and its word prefix (both complete on the main stream)
             vx::launch_emit_bool_aabbs(words.as<uint32_t>(), wprefix.as<uint32_t>(), g, ld.tgt, ld.cap, st, sel_valid ? wsel.as<uint32_t>() : nullptr);
             return;
@@ -539,6 +550,9 @@ struct vx_grid : Home {
     {
         hipError_t e = hipStreamWaitEvent(side, ev_ready, 0);
         if (e != hipSuccess) return e;
+        // (the hit scan, a handful of 1024-thread workgroups, in front of the gate: it runs as the ray kernel starts, not in its drain, where a
+        // workgroup of that size finds no room until most of a CU's ray workgroups have left)
+        list_scan(side);
         // The emission is held until the first wave of the ray kernel has come back to the queue for more rays -- the kernel's persistent
         // workgroups are all placed by then, the emission cannot take their slots first (without the hold the step varies 0.497-0.535 ms
         // from run to run, with it 0.489-0.494).  The hold is a one-wave gate kernel with a time bound (vx_trace.hip: a stream-level wait
@@ -563,6 +577,7 @@ struct vx_grid : Home {
             // nobody asked for rays in between: the emission runs where it always did (a caller's buffer is always filled; the grid's own
             // Vec list may be dropped when it is about to be replaced)
             if (!drop_unqueued || ld.from_mask) list_emit(stream);
+            ld.scan_blocks = 0;  // (a dropped list drops its scan)
         }
         if (list_pending) {
             list_pending = false;
@@ -778,13 +793,15 @@ vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0, b
 // in its hands, also left the set bits of every 16-word line (g->lcnt).  Their exclusive scan IS word_prefix[16 i] -- the table the rank pass
 // of a ray batch reads beside the voxel's own line of the mask -- and its total the occupied count, posted to the same mailbox word: a scan
 // over nwords / 16 values instead of a pass that reads the mask again and writes nwords prefixes nobody on this path reads.
+// The level-2 mip, which like this scan reads only what the brick kernel wrote, shares the scan's launch (ensure_coarse calls this in place of
+// its own last kernel).
 vx_status p16_launch(vx_grid* g, unsigned long long tag, bool* tagged)
 {
     const uint64_t nl = g->g.nwords / 16;
     VX_HIP(g->wp16.ensure((size_t)(nl + 4) * 4));
     VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nl), g->stream));
-    const bool tg = vx::launch_scan_u32(g->lcnt.as<uint32_t>(), g->wp16.as<uint32_t>(), nl, false, g->scantmp.p, &g->mail->occupied, g->stream, true, tag, nullptr,
-                                        advance_scan_gen(g->scantmp, g->stream));
+    const bool tg = vx::launch_mip2_scan(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->lcnt.as<uint32_t>(), g->wp16.as<uint32_t>(), nl,
+                                         g->scantmp.p, &g->mail->occupied, g->stream, tag, advance_scan_gen(g->scantmp, g->stream));
     *tagged = tg;
     g->p16_valid = true;
     g->prefix_valid = g->sel_valid = false;  // (wprefix and wsel still describe an older mask)
@@ -828,8 +845,10 @@ vx_status ensure_occupied(vx_grid* g)
 }
 
 // from_tiled: the reference's bitmask has not been written yet -- the brick kernel reads the tiled build mask (g->twords) and writes it on the way
-// line_counts (with from_tiled): it also leaves the set bits per 16-word line in g->lcnt (p16_launch)
-vx_status ensure_coarse(vx_grid* g, bool from_tiled = false, bool line_counts = false)
+// line_counts (with from_tiled): it also leaves the set bits per 16-word line in g->lcnt, and their scan (p16_launch: wp16, the occupied count under
+// `tag`) is queued in one launch with the level-2 mip
+// post_hits (with from_tiled): the brick kernel posts the voxelizer's hit count to mail->hits under `tag`
+vx_status ensure_coarse(vx_grid* g, bool from_tiled = false, bool line_counts = false, unsigned long long tag = 0, bool* tagged = nullptr, bool post_hits = false)
 {
     if (g->coarse_valid && !from_tiled) return VX_OK;
     DeviceGuard dg(g->device);
@@ -846,9 +865,11 @@ vx_status ensure_coarse(vx_grid* g, bool from_tiled = false, bool line_counts = 
     const bool fuse_mip1 = !(getenv("VOXHIP_FUSE_MIP1") && atoi(getenv("VOXHIP_FUSE_MIP1")) == 0);  // 0: the separate kernel, every brick stored (tests)
     const bool fused = vx::launch_build_bricks3(g->words.as<uint32_t>(), g->g.dim, g->cdim, g->bricks.as<unsigned long long>(),
                                                 fuse_mip1 ? g->cwords.as<uint32_t>() : nullptr, g->stream, from_tiled ? g->twords.as<uint32_t>() : nullptr,
-                                                from_tiled && line_counts ? g->lcnt.as<uint32_t>() : nullptr);
+                                                from_tiled && line_counts ? g->lcnt.as<uint32_t>() : nullptr,
+                                                from_tiled && post_hits ? g->small.as<Small>()->set_calls : nullptr, from_tiled && post_hits ? &g->mail->hits : nullptr, tag);
     if (!fused) vx::launch_brick_mip1(g->bricks.as<unsigned long long>() + 2ull * nc * 8ull, nc, g->cwords.as<uint32_t>(), g->stream);
-    vx::launch_build_mip2(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->stream);
+    if (from_tiled && line_counts) VX_TRY(p16_launch(g, tag, tagged));
+    else vx::launch_build_mip2(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->stream);
     g->coarse_valid = true;
     return VX_OK;
 }
@@ -1444,7 +1465,14 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
     if (tiled && !untile_in_bricks) vx::launch_untile(g->twords.as<uint32_t>(), g->words.as<uint32_t>(), g->g.dim, s, wb, we);
     g->counts_valid = false;
     bool hits_tagged = false, occ_tagged = false, occ_queued = false;
-    if (g->kind == VX_GRID_VEC) {
+    // A list_async rebuild whose brick kernel follows at once: nothing queued in the build reads the hit bases -- the block-hit scan stood here
+    // for its total, the list's length -- so the brick kernel posts that total from the voxelizer's own counters and the scan goes in front
+    // of the emission (list_scan).  Everything else keeps the scan here.
+    const bool defer_scan = early && untile_in_bricks;
+    if (defer_scan) {
+        VX_HIP(ensure_scan_tmp(g->hscantmp, vx::scan_tmp_bytes(nUB), s));
+        hits_tagged = true;
+    } else if (g->kind == VX_GRID_VEC) {
         VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nUB), s));
         hits_tagged = vx::launch_scan_u32(bhits, g->hbase.as<uint32_t>(), nUB, false, g->scantmp.p, &g->mail->hits, s, true, mtag, nullptr, advance_scan_gen(g->scantmp, s));
     }
@@ -1466,10 +1494,9 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         // their list from the word prefix right away, materials index it: today's scan)
         const bool lines = untile_in_bricks && g->kind == VX_GRID_VEC && !want_mat && (ex.dim[0] % 512) == 0;
         if (lines) VX_HIP(g->lcnt.ensure((size_t)(g->g.nwords / 16 + 4) * 4));
-        VX_TRY(ensure_coarse(g, untile_in_bricks, lines));
+        VX_TRY(ensure_coarse(g, untile_in_bricks, lines, mtag, &occ_tagged, defer_scan));
         if (lines) {
             occ_queued = true;
-            VX_TRY(p16_launch(g, mtag, &occ_tagged));
         } else {
             bool pending = false;
             occ_queued = !g->prefix_valid;
@@ -1486,7 +1513,8 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         if (cap_rec && !list_async)
             vx::launch_emit_units(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, umask,
                                   g->hbase.as<uint32_t>(), tgt, nullptr, s, to_bound ? g->bound_cap : cap_rec, xw);
-        // The host needs the hit count (and takes the occupied count along).  Both are written by scans that run BEFORE the
+        // The host needs the hit count (and takes the occupied count along).  Both are written by scans -- the hit count of a build that
+        // left its block-hit scan to the list (defer_scan) by the brick kernel, from the voxelizer's counters -- that run BEFORE the
         // emission: the host polls the tagged mailbox words and goes on queueing work (the caller's next call: a trace) while
         // the emission still runs; a stream synchronize would wake it ~15 us after the last kernel.  An untagged total
         // (three-pass scan) or 5 ms without an answer: the synchronize.
@@ -1499,6 +1527,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
         if (hits_tagged && (!occ_along || (occ_queued && occ_tagged)))
             got = mail_wait(&g->mail->hits, occ_along ? &g->mail->occupied : nullptr, mtag, 5.0);
         if (!got) VX_HIP(hipStreamSynchronize(s));
+        uint64_t units_known = U;
         if (early) {
             // the unit total, in the mailbox since k_unit_blocks: checked as setup_finish checks it.  More units than the early launch's
             // buffers hold: the voxelizer did nothing -- the buffers grow and the build runs again the way of a first build
@@ -1513,6 +1542,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
                 VX_HIP(g->btri.ensure((size_t)(tot / 64 + 2) * 4));
                 return voxelize_build(mesh, vs, o, g, /*allow_early=*/false);
             }
+            units_known = tot;
         }
         const unsigned long long hits = g->mail->hits & kMailValue;
         if (hits >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 voxel hits");
@@ -1534,6 +1564,7 @@ static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts&
             g->ld.tgt = g->vec_ptr();
             g->ld.cap = g->vec_in_bound ? g->bound_cap : ~0ull;
             g->list_deferred = hits != 0;
+            g->ld.scan_blocks = defer_scan && hits ? (units_known + 63) / 64 : 0;  // (the true unit total: the build's own blocks, not the buffers')
         } else if (total + 1 > cap_rec) {
             vx::launch_emit_units(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, umask,
                                   g->hbase.as<uint32_t>(), g->vec.as<vx_aabb>(), nullptr, s, ~0ull, xw);

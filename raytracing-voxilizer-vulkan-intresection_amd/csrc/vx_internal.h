@@ -47,6 +47,7 @@ struct ProfScope {
 // K1: bbox of all vertices with the reference's first-occurrence tie rule; out6 = min xyz, max xyz (device).
 // state7: self-cleaning reduction state (initialise ONCE with bbox_state_init); out6 may point to pinned host memory;
 // zero64 (optional): the per-build setVoxel-call counters (kCallCounters of them, one per 64-byte line), cleared by the kernel.
+constexpr unsigned long long kScanTotalSat = (1ull << 40) - 1ull;  // where a posted total saturates (vx_kernels.hip, THE TOTAL)
 constexpr uint32_t kCallCounters = 64;  // k_voxelize's waves add to counter (wave index % 64): entry [8 * i] of the array
 // dgrid (optional, device memory): origin = bbox min and dims = ceil((max - min) / vs) as the host will derive them, for kernels
 // queued behind K1 before the host has read the bbox.
@@ -145,9 +146,15 @@ bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const ui
                           const uint32_t* tiled = nullptr /*the voxelizer's tiled build mask (dim[0] % 32 == 0): the source instead of `words`, and `words`
                                                             is WRITTEN from it -- launch_untile's job done on the way*/,
                           uint32_t* line_cnt = nullptr /*with `tiled`, dim[0] % 512 == 0 (so every 16-word line of the bitmask lies in one row): the set
-                                                         bits per line, nwords / 16 counts; their exclusive scan is word_prefix[16 i]*/);
+                                                         bits per line, nwords / 16 counts; their exclusive scan is word_prefix[16 i]*/,
+                          const unsigned long long* hit_counters = nullptr /*optional: k_voxelize's kCallCounters spread counters, complete on `s`*/,
+                          unsigned long long* hits_out = nullptr /*with hit_counters: receives hits_tag | their sum (THE TOTAL's contract) as the kernel starts*/,
+                          unsigned long long hits_tag = 0);
 void launch_brick_mip1(const unsigned long long* bricks_z /*orientation 2*/, uint64_t nbricks, uint32_t* m1, hipStream_t s);
 void launch_build_mip2(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, hipStream_t s);
+// the level-2 mip and the exclusive scan of n uint32 (launch_scan_u32 on a generation-managed, zero-between-scans tmp) in one launch
+bool launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, const uint32_t* in, uint32_t* out, uint64_t n, void* tmp,
+                      unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen);
 struct TraceMips {
     const unsigned long long* bricks3;
     const uint32_t* w0;                // the reference-layout bitmask (primitive rank only)

@@ -8,6 +8,7 @@
 //   K4  k_emit_bool       bitmask -> ascending AABB list                                  (voxelgridBool.cpp:18-52)
 //   K6  k_trace           two-level conservative 3D-DDA + the rint slab formula           (shaders/raytrace.rint:46-71)
 //   scan kernels          device-wide exclusive scan (work-unit bases, popcount prefixes)
+//   k_mip2_scan           the traversal structure's level-2 mip and the line-count scan of a Vec build in one launch
 //
 // Everything here is integer / float32 VALU and HBM/L2 traffic: no MFMA (nothing is a contraction).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (bit-exact float semantics, see vx_math.h).
@@ -194,7 +195,7 @@ void launch_bbox(const float* verts, uint64_t nverts, unsigned long long* state7
 // The per-element outputs out[i] are the exclusive prefix mod 2^32 for every tile whose own exclusive prefix is below
 // 2^40 - 1 (a scan whose total saturates is refused by every caller; past that point only the total is specified).
 // ------------------------------------------------------------------------------------------------------------
-constexpr unsigned long long kScanTotalSat = (1ull << 40) - 1ull;
+// (kScanTotalSat = 2^40 - 1: vx_internal.h -- the brick kernel posts the voxelizer's hit count under the same contract)
 template <bool POPC>
 __device__ __forceinline__ unsigned scan_ld(const uint32_t* __restrict__ in, uint64_t i, uint64_t n)
 {
@@ -324,13 +325,14 @@ constexpr unsigned long long kScanGenValMask = (1ull << 40) - 1ull;
 constexpr int kOneBlock = VX_SCAN_BLOCK, kOneItems = VX_SCAN_ITEMS, kOneTile = kOneBlock * kOneItems;
 
 // MODE 0: the uint32 values themselves, 1: their popcounts, 2: `in` is an array of BYTES (n of them), sixteen per 16-byte load
+// (the kernel's body, for the workgroup that takes tile `wg` in generation mode: k_scan_onepass, and k_mip2_scan behind its mip workgroups)
 template <int MODE>
-__global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n,
-                                                           unsigned long long* status /*[0]: ticket, [1]: finished tiles, [2 + tile]: state*/, uint32_t ntiles,
-                                                           unsigned long long* total, unsigned long long total_tag /*OR-ed into *total: bits 48..63*/,
-                                                           uint32_t* __restrict__ sel /*optional: sel[c] = index of the element whose range [pre, pre + v) holds c * 1024*/,
-                                                           uint32_t gen /*0: tickets + self-cleaning state; else generation mode*/,
-                                                           uint32_t* __restrict__ group16 /*optional: group16[i] = out[16 i], a dense copy of every 16th output*/)
+__device__ __forceinline__ void scan_onepass_tile(unsigned wg, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n,
+                                                  unsigned long long* status /*[0]: ticket, [1]: finished tiles, [2 + tile]: state*/, uint32_t ntiles,
+                                                  unsigned long long* total, unsigned long long total_tag /*OR-ed into *total: bits 48..63*/,
+                                                  uint32_t* __restrict__ sel /*optional: sel[c] = index of the element whose range [pre, pre + v) holds c * 1024*/,
+                                                  uint32_t gen /*0: tickets + self-cleaning state; else generation mode*/,
+                                                  uint32_t* __restrict__ group16 /*optional: group16[i] = out[16 i], a dense copy of every 16th output*/)
 {
     // MODE 0: 16384 uint32 sum to up to 2^46, so the tile total (what the look-back publishes) is carried in 64 bits; the
     // per-element prefixes only need it mod 2^32 and stay 32-bit.  MODE 1 / 2: at most 32 / 255 per element, i.e. below 2^19 /
@@ -340,7 +342,7 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
     __shared__ tsum_t wsum[kOneBlock / 64];
     __shared__ unsigned tile_s;
     __shared__ unsigned long long prefix_s;
-    unsigned tile = blockIdx.x;
+    unsigned tile = wg;
     if (!gen) {
         if (threadIdx.x == 0) tile_s = (unsigned)atomicAdd(status, 1ull);
         __syncthreads();
@@ -491,6 +493,14 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
     }
 }
 
+template <int MODE>
+__global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n, unsigned long long* status,
+                                                           uint32_t ntiles, unsigned long long* total, unsigned long long total_tag, uint32_t* __restrict__ sel,
+                                                           uint32_t gen, uint32_t* __restrict__ group16)
+{
+    scan_onepass_tile<MODE>(blockIdx.x, in, out, n, status, ntiles, total, total_tag, sel, gen, group16);
+}
+
 size_t scan_tmp_bytes(uint64_t n) { return (size_t)(((n + 1) + kScanTile - 1) / kScanTile + 4) * sizeof(unsigned long long); }
 
 // *total64: see THE TOTAL above (the exact range, the saturation at 2^40 - 1 and the tag bits).
@@ -523,6 +533,90 @@ bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcoun
     }
     if (tmp_is_zero || gen) (void)hipMemsetAsync(status, 0, scan_tmp_bytes(n), s);  // keep the caller's "zero between scans" contract (no stale words either)
     return false;  // (*total64 carries no tag)
+}
+
+// Level-2 mip of the traversal structure (vx_walk.hip): one bit per 8x8x8 bricks.  One workgroup per OUTPUT WORD (32 blocks: 16 waves x 2),
+// one lane per (y, z) row of a block's bricks: eight level-1 bits per lane, a ballot per block, one plain store per word -- no atomics, no memset.
+// (the body, for the workgroup that writes word `wg`: k_build_mip2, and the first workgroups of k_mip2_scan)
+__device__ __forceinline__ void mip2_word(uint32_t wg, const uint32_t* __restrict__ m1, uint32_t d1x, uint32_t d1y, uint32_t d1z, uint32_t d2x, uint32_t d2y,
+                                          uint32_t d2z, uint32_t* __restrict__ m2)
+{
+    __shared__ uint32_t bits_s;
+    if (threadIdx.x == 0) bits_s = 0u;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint64_t n2 = (uint64_t)d2x * d2y * d2z;
+    uint32_t mine = 0u;
+    for (uint32_t k = 0; k < 2u; ++k) {
+        const uint32_t bit = wv * 2u + k;
+        const uint64_t c = (uint64_t)wg * 32u + bit;
+        bool any = false;
+        if (c < n2) {
+            const uint32_t kz = (uint32_t)(c / ((uint64_t)d2x * d2y));
+            const uint32_t rem = (uint32_t)(c - (uint64_t)kz * d2x * d2y);
+            const uint32_t ky = rem / d2x, kx = rem - ky * d2x;
+            const uint32_t by = ky * 8u + (lane & 7u), bz = kz * 8u + (lane >> 3), bx0 = kx * 8u;
+            if (by < d1y && bz < d1z) {
+                const uint32_t nb = d1x - bx0 < 8u ? d1x - bx0 : 8u;
+                const uint64_t i0 = (uint64_t)bx0 + (uint64_t)d1x * ((uint64_t)by + (uint64_t)d1y * bz);
+                const uint32_t sh = (uint32_t)i0 & 31u;
+                uint32_t val = m1[i0 >> 5] >> sh;
+                if (sh + nb > 32u) val |= m1[(i0 >> 5) + 1] << (32u - sh);
+                any = (val & ((1u << nb) - 1u)) != 0u;
+            }
+        }
+        if (__ballot(any)) mine |= 1u << bit;
+    }
+    if (lane == 0u && mine) atomicOr(&bits_s, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) m2[wg] = bits_s;
+}
+
+__global__ __launch_bounds__(1024) void k_build_mip2(const uint32_t* __restrict__ m1, uint32_t d1x, uint32_t d1y, uint32_t d1z, uint32_t d2x, uint32_t d2y,
+                                                     uint32_t d2z, uint32_t* __restrict__ m2)
+{
+    mip2_word(blockIdx.x, m1, d1x, d1y, d1z, d2x, d2y, d2z, m2);
+}
+
+void launch_build_mip2(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, hipStream_t s)
+{
+    const uint64_t n2 = (uint64_t)d2[0] * d2[1] * d2[2];
+    if (!n2) return;
+    VX_KL(k_build_mip2, dim3((unsigned)((n2 + 31) / 32)), dim3(1024), 0, s, m1, d1[0], d1[1], d1[2], d2[0], d2[1], d2[2], m2);
+}
+
+// The level-2 mip and the scan of the brick kernel's line counts in ONE launch: both read only what k_build_bricks3 wrote (the level-1 mip,
+// the counts), both run workgroups of 1024 threads, and each alone is a launch-latency kernel of a handful of workgroups.  Workgroups
+// [0, n_mip) write the mip's words and leave; workgroup n_mip + i is the scan's tile i.  A scan tile only ever waits for tiles of lower
+// number, i.e. for workgroups dispatched before it, and the mip's workgroups in front of them wait for nobody.
+static_assert(kOneBlock == 1024, "k_mip2_scan: the mip's workgroups and the scan's tiles have the same shape");
+__global__ __launch_bounds__(kOneBlock) void k_mip2_scan(const uint32_t* __restrict__ m1, uint32_t d1x, uint32_t d1y, uint32_t d1z, uint32_t d2x, uint32_t d2y,
+                                                        uint32_t d2z, uint32_t* __restrict__ m2, uint32_t n_mip, const uint32_t* __restrict__ in,
+                                                        uint32_t* __restrict__ out, uint64_t n, unsigned long long* status, uint32_t ntiles,
+                                                        unsigned long long* total, unsigned long long total_tag, uint32_t gen)
+{
+    if (blockIdx.x < n_mip) mip2_word(blockIdx.x, m1, d1x, d1y, d1z, d2x, d2y, d2z, m2);
+    else scan_onepass_tile<0>(blockIdx.x - n_mip, in, out, n, status, ntiles, total, total_tag, nullptr, gen, nullptr);
+}
+
+// launch_build_mip2 + launch_scan_u32(in, out, n, values, generation-managed tmp) as one launch where the single-pass scan applies; returns
+// what the scan returns (whether *total64 carries the tag)
+bool launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, const uint32_t* in, uint32_t* out, uint64_t n, void* tmp,
+                      unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen)
+{
+    const uint64_t n_mip = ((uint64_t)d2[0] * d2[1] * d2[2] + 31) / 32;
+    const uint64_t ntiles = ((n + 1) + kOneTile - 1) / kOneTile;
+    const bool aligned = ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
+    if (!n_mip || !aligned || !gen || n_mip + ntiles > 0x7FFFFFFFull) {
+        launch_build_mip2(m1, d1, d2, m2, s);
+        return launch_scan_u32(in, out, n, false, tmp, total64, s, true, total_tag, nullptr, gen);
+    }
+    // generation mode as in launch_scan_u32, with the mip's workgroups counted among the resident ones
+    const uint32_t g = n_mip + ntiles <= kScanGenTiles ? gen : 0u;
+    if (!g) (void)hipMemsetAsync(tmp, 0, (size_t)(ntiles + 2) * sizeof(unsigned long long), s);
+    VX_KL(k_mip2_scan, dim3((unsigned)(n_mip + ntiles)), dim3(kOneBlock), 0, s, m1, d1[0], d1[1], d1[2], d2[0], d2[1], d2[2], m2, (uint32_t)n_mip, in, out, n,
+          (unsigned long long*)tmp, (uint32_t)ntiles, total64, total_tag, g);
+    return true;
 }
 
 // the bits past the grid's nvox cells in the last bitmask word (an externally written mask may set them): cleared, so that nothing

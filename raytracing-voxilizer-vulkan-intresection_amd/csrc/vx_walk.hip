@@ -81,11 +81,26 @@ __global__ __launch_bounds__(256) void k_build_bricks3(uint32_t* __restrict__ wo
                                                        const uint32_t* __restrict__ tiled /*optional (X % 32 == 0): the voxelizer's tiled build mask is the
                                                        source, and `words` -- the reference's bitmask -- is WRITTEN from it on the way (k_untile's job)*/,
                                                        uint32_t* __restrict__ line_cnt /*optional (with `tiled`, X % 512 == 0): the set bits of every 16-word
-                                                       line of the bitmask, nwords / 16 counts -- what the rank pass's prefix16 is the scan of*/)
+                                                       line of the bitmask, nwords / 16 counts -- what the rank pass's prefix16 is the scan of*/,
+                                                       const unsigned long long* __restrict__ hit_counters /*optional: the voxelizer's spread hit counters*/,
+                                                       unsigned long long* hits_out, unsigned long long hits_tag)
 {
     __shared__ uint32_t rows[64][17];              // [z*8 + y][32-voxel chunk of the 512]; padded against bank conflicts of the column reads
     __shared__ unsigned long long sz[64][9];       // [brick][z slab]: bit y*8 + x (padded)
     const uint64_t ngroups = (uint64_t)chunks_x * BY * BZ;
+    // (optional) the voxelizer's hit count -- the length of the Vec list -- for the host: the kCallCounters counters k_voxelize's waves added
+    // their hits to are complete when this kernel starts; one wave adds them up and posts the tagged total the way the scans post theirs.
+    // The block-hit scan, whose total this is, then only has to run in front of the list's emission, wherever that is queued.
+    if (hit_counters && blockIdx.x == 0u && threadIdx.x < 64u) {
+        static_assert(kCallCounters == 64, "one counter per lane");
+        unsigned long long c = hit_counters[threadIdx.x * 8u];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const unsigned lo = __shfl_xor((unsigned)c, m, 64), hi = __shfl_xor((unsigned)(c >> 32), m, 64);
+            c += ((unsigned long long)hi << 32) | lo;
+        }
+        if (threadIdx.x == 0u) *hits_out = hits_tag | (c < kScanTotalSat ? c : kScanTotalSat);
+    }
     if (tiled && blockIdx.x == 0u && threadIdx.x < 2u) words[nwords + threadIdx.x] = 0u;  // the two spare words behind the mask (init_grid_storage)
     for (uint64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const uint32_t cx = (uint32_t)(grp % chunks_x);
@@ -234,7 +249,7 @@ __global__ __launch_bounds__(256) void k_build_bricks3(uint32_t* __restrict__ wo
 
 // Returns true when the level-1 mip was written by the brick kernel itself (and empty bricks were left unwritten).
 bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const uint32_t bdim[3], unsigned long long* bricks3, uint32_t* m1, hipStream_t s,
-                          const uint32_t* tiled, uint32_t* line_cnt)
+                          const uint32_t* tiled, uint32_t* line_cnt, const unsigned long long* hit_counters, unsigned long long* hits_out, unsigned long long hits_tag)
 {
     const uint64_t n = (uint64_t)bdim[0] * bdim[1] * bdim[2];
     if (!n) return false;
@@ -246,7 +261,8 @@ bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const ui
     if (nblk > 16384) nblk = 16384;
     const bool fused = (bdim[0] % 64u) == 0u && m1 != nullptr;
     VX_KL(k_build_bricks3, dim3((unsigned)nblk), dim3(256), 0, s, const_cast<uint32_t*>(words), dim[0], dim[1], dim[2], bdim[0], bdim[1], bdim[2], chunks_x, nwords, bricks3, n * 8ull,
-          fused ? m1 : nullptr, (dim[0] % 32u) == 0u ? tiled : nullptr, (tiled && (dim[0] % 512u) == 0u) ? line_cnt : nullptr);
+          fused ? m1 : nullptr, (dim[0] % 32u) == 0u ? tiled : nullptr, (tiled && (dim[0] % 512u) == 0u) ? line_cnt : nullptr, hits_out ? hit_counters : nullptr, hits_out,
+          hits_tag);
     return fused;
 }
 
