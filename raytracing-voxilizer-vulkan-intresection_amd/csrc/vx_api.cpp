@@ -2706,13 +2706,33 @@ vx_status vx_trace_ex(const vx_grid* gc, const vx_trace_args* args)
 }
 
 // ---- multi-hit query (vx_multihit.hip) -----------------------------------------------------------------------------
-// the argument checks of vx_trace_multi* and vx_octree_trace_multi*, in the header's order; *io receives the ray batch (nrays == 0: nothing to do)
-static vx_status multihit_args_to_io(const void* handle, const vx_multihit_args* a, vx::Camera* cam, vx::TraceIO* io)
+// The four structures share one argument form inside the library: vx_tlas_multihit_args, of which vx_multihit_args (grid, octree) and
+// vx_bvh_multihit_args are leading parts.
+static vx_tlas_multihit_args from_grid_args(const vx_multihit_args* a)
+{
+    vx_tlas_multihit_args x{};
+    if (a) x.m = *a;
+    return x;
+}
+
+static vx_tlas_multihit_args from_bvh_args(const vx_bvh_multihit_args* a)
+{
+    vx_tlas_multihit_args x{};
+    if (a) { x.m = a->m; x.bary = a->bary; }
+    return x;
+}
+
+// The checks of the eight vx_*_trace_multi* entry points, in the header's order (tlas: the cursor has an instance part); *io receives the ray
+// batch (nrays == 0: nothing to do)
+static vx_status multihit_args_to_io(const void* handle, const vx_tlas_multihit_args* a, bool tlas, vx::Camera* cam, vx::TraceIO* io)
 {
     if (!handle || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
-    if (a->max_hits < 1 || a->max_hits > VX_MULTIHIT_MAX) return fail(VX_ERR_INVALID_ARG, "max_hits must be 1..VX_MULTIHIT_MAX");
-    if ((a->after_t != nullptr) != (a->after_prim != nullptr)) return fail(VX_ERR_INVALID_ARG, "the cursor needs both after_t and after_prim");
-    const vx_trace_args& b = a->base;
+    const vx_multihit_args& m = a->m;
+    if (m.max_hits < 1 || m.max_hits > VX_MULTIHIT_MAX) return fail(VX_ERR_INVALID_ARG, "max_hits must be 1..VX_MULTIHIT_MAX");
+    const bool cursor = m.after_t != nullptr;
+    if (cursor != (m.after_prim != nullptr) || (tlas && cursor != (a->after_instance != nullptr)))
+        return fail(VX_ERR_INVALID_ARG, tlas ? "the cursor needs after_t, after_instance and after_prim" : "the cursor needs both after_t and after_prim");
+    const vx_trace_args& b = m.base;
     if (b.any_hit || b.normal || b.shadowed || b.hits || b.num_hits)
         return fail(VX_ERR_INVALID_ARG, "any_hit, normal, shadowed, hits and num_hits are not part of the multi-hit query");
     const bool camera = b.view_inverse && b.proj_inverse && b.width && b.height;
@@ -2720,8 +2740,71 @@ static vx_status multihit_args_to_io(const void* handle, const vx_multihit_args*
     return args_to_io(&b, cam, io);
 }
 
-// the query on device arrays: io's pointers, count and the cursor are device memory
-static vx_status multihit_common(vx_grid* g, vx::TraceIO io, const vx_multihit_args* a, uint32_t* count, const float* after_t, const uint32_t* after_prim)
+static vx::MultiIO multi_io(const vx_tlas_multihit_args& a)
+{
+    vx::MultiIO m;
+    m.K = a.m.max_hits;
+    m.count = a.m.count;
+    m.bary = a.bary;
+    m.instance = a.instance;
+    m.after_t = a.m.after_t;
+    m.after_instance = a.after_instance;
+    m.after_prim = a.m.after_prim;
+    return m;
+}
+
+// the host variants: every non-null array of `a` through pooled device memory of `home` (the handle: its device and stream), then
+// `run(io, d)` on the staged batch io and the staged copy d of the arguments
+extern "C++" {
+template <class Run>
+static vx_status multihit_staged(const Home& home, const vx_tlas_multihit_args& a, vx::TraceIO io, Run run)
+{
+    const size_t n = (size_t)io.nrays, K = a.m.max_hits;
+    hipStream_t stream = home.stream;
+    DevBuf dr{&home}, dtm{&home}, dat{&home}, dai{&home}, dap{&home}, dt{&home}, dp{&home}, db{&home}, di{&home}, dc{&home};
+    auto upload = [&](DevBuf& b, const void* host, size_t bytes) -> hipError_t {
+        if (!host) return hipSuccess;
+        const hipError_t e = b.ensure(bytes);
+        return e == hipSuccess ? hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, stream) : e;
+    };
+    VX_HIP(upload(dr, a.m.base.rays, n * 24));
+    VX_HIP(upload(dtm, a.m.base.tmax_per_ray, n * 4));
+    VX_HIP(upload(dat, a.m.after_t, n * 4));
+    VX_HIP(upload(dai, a.after_instance, n * 4));
+    VX_HIP(upload(dap, a.m.after_prim, n * 4));
+    if (a.m.base.t) VX_HIP(dt.ensure(n * K * 4));
+    if (a.m.base.prim) VX_HIP(dp.ensure(n * K * 4));
+    if (a.bary) VX_HIP(db.ensure(n * K * 8));
+    if (a.instance) VX_HIP(di.ensure(n * K * 4));
+    if (a.m.count) VX_HIP(dc.ensure(n * 4));
+    if (io.rays) io.rays = dr.as<float>();
+    if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
+    io.t_out = dt.as<float>();
+    io.prim_out = dp.as<uint32_t>();
+    vx_tlas_multihit_args d = a;
+    d.m.count = dc.as<uint32_t>();
+    d.m.after_t = dat.as<float>();
+    d.after_instance = dai.as<uint32_t>();
+    d.m.after_prim = dap.as<uint32_t>();
+    d.bary = db.as<float>();
+    d.instance = di.as<uint32_t>();
+    const vx_status st = run(io, d);
+    if (st != VX_OK) {
+        (void)hipStreamSynchronize(stream);  // the uploads read the caller's arrays
+        return st;
+    }
+    if (a.m.base.t) VX_HIP(hipMemcpyAsync(a.m.base.t, dt.p, n * K * 4, hipMemcpyDeviceToHost, stream));
+    if (a.m.base.prim) VX_HIP(hipMemcpyAsync(a.m.base.prim, dp.p, n * K * 4, hipMemcpyDeviceToHost, stream));
+    if (a.bary) VX_HIP(hipMemcpyAsync(a.bary, db.p, n * K * 8, hipMemcpyDeviceToHost, stream));
+    if (a.instance) VX_HIP(hipMemcpyAsync(a.instance, di.p, n * K * 4, hipMemcpyDeviceToHost, stream));
+    if (a.m.count) VX_HIP(hipMemcpyAsync(a.m.count, dc.p, n * 4, hipMemcpyDeviceToHost, stream));
+    VX_HIP(hipStreamSynchronize(stream));
+    return VX_OK;
+}
+}  // extern "C++"
+
+// the query on device arrays: io's pointers and those of `a` are device memory
+static vx_status multihit_common(vx_grid* g, vx::TraceIO io, const vx_tlas_multihit_args& a)
 {
     vx::TraceMips mips{};
     const uint32_t* prefix = nullptr;
@@ -2735,72 +2818,33 @@ static vx_status multihit_common(vx_grid* g, vx::TraceIO io, const vx_multihit_a
     }
     VX_TRY(upload_camera(g->camera, g->stream, io));
     // (read-only: a deferred list emission is neither queued nor waited for here)
-    vx::launch_multihit(g->g, mips, prefix, io, a->max_hits, count, after_t, after_prim, g->stream);
+    vx::launch_multihit(g->g, mips, prefix, io, multi_io(a), g->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
 }
 
-vx_status vx_trace_multi_device(const vx_grid* gc, const vx_multihit_args* a)
+vx_status vx_trace_multi_device(const vx_grid* gc, const vx_multihit_args* args)
 {
+    const vx_tlas_multihit_args a = from_grid_args(args);
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(gc, a, &cam, &io));
+    VX_TRY(multihit_args_to_io(gc, args ? &a : nullptr, false, &cam, &io));
     if (!io.nrays) return VX_OK;
     vx_grid* g = const_cast<vx_grid*>(gc);
     DeviceGuard dg(g->device);
-    return multihit_common(g, io, a, a->count, a->after_t, a->after_prim);
+    return multihit_common(g, io, a);
 }
 
-// host-buffer variant of a multi-hit query: every non-null array through pooled device memory of `home` (the handle: its device and
-// stream), as trace_ex_staged does for one entry per ray; run(io, count, after_t, after_prim) queues the query on the staged arrays
-extern "C++" {
-template <class Run>
-static vx_status multihit_staged(const Home& home, const vx_multihit_args* a, vx::TraceIO io, Run run)
+vx_status vx_trace_multi(const vx_grid* gc, const vx_multihit_args* args)
 {
-    const uint64_t n = io.nrays;
-    const size_t K = a->max_hits;
-    hipStream_t stream = home.stream;
-    DevBuf dr{&home}, dtm{&home}, dt{&home}, dp{&home}, dc{&home}, dat{&home}, dap{&home};
-    auto upload = [&](DevBuf& b, const void* host, size_t bytes) -> hipError_t {
-        if (!host) return hipSuccess;
-        const hipError_t e = b.ensure(bytes);
-        return e == hipSuccess ? hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, stream) : e;
-    };
-    VX_HIP(upload(dr, a->base.rays, (size_t)n * 24));
-    VX_HIP(upload(dtm, a->base.tmax_per_ray, (size_t)n * 4));
-    VX_HIP(upload(dat, a->after_t, (size_t)n * 4));
-    VX_HIP(upload(dap, a->after_prim, (size_t)n * 4));
-    if (a->base.t) VX_HIP(dt.ensure((size_t)n * K * 4));
-    if (a->base.prim) VX_HIP(dp.ensure((size_t)n * K * 4));
-    if (a->count) VX_HIP(dc.ensure((size_t)n * 4));
-    if (io.rays) io.rays = dr.as<float>();
-    if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
-    io.t_out = dt.as<float>();
-    io.prim_out = dp.as<uint32_t>();
-    const vx_status st = run(io, dc.as<uint32_t>(), dat.as<float>(), dap.as<uint32_t>());
-    if (st != VX_OK) {
-        (void)hipStreamSynchronize(stream);  // the uploads read the caller's arrays
-        return st;
-    }
-    if (a->base.t) VX_HIP(hipMemcpyAsync(a->base.t, dt.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, stream));
-    if (a->base.prim) VX_HIP(hipMemcpyAsync(a->base.prim, dp.p, (size_t)n * K * 4, hipMemcpyDeviceToHost, stream));
-    if (a->count) VX_HIP(hipMemcpyAsync(a->count, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-    VX_HIP(hipStreamSynchronize(stream));
-    return VX_OK;
-}
-}  // extern "C++"
-
-vx_status vx_trace_multi(const vx_grid* gc, const vx_multihit_args* a)
-{
+    const vx_tlas_multihit_args a = from_grid_args(args);
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(gc, a, &cam, &io));
+    VX_TRY(multihit_args_to_io(gc, args ? &a : nullptr, false, &cam, &io));
     if (!io.nrays) return VX_OK;
     vx_grid* g = const_cast<vx_grid*>(gc);
     DeviceGuard dg(g->device);
-    return multihit_staged(*g, a, io, [&](const vx::TraceIO& sio, uint32_t* count, const float* after_t, const uint32_t* after_prim) {
-        return multihit_common(g, sio, a, count, after_t, after_prim);
-    });
+    return multihit_staged(*g, a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return multihit_common(g, sio, d); });
 }
 
 // vx_trace / vx_octree_trace: t and prim of a host ray buffer through the handle's host-buffer extended query, hits counted on the host
@@ -3025,37 +3069,37 @@ vx_status vx_octree_trace(const vx_octree* oc, const float* host_rays, uint64_t 
 }
 
 // ---- multi-hit query on the octree (vx_octmulti.hip): vx_trace_multi's contract over the runs of equal codes of the list
-static vx_status octree_multihit_common(vx_octree* o, vx::TraceIO io, uint32_t K, uint32_t* count, const float* after_t, const uint32_t* after_prim)
+static vx_status octree_multihit_common(vx_octree* o, vx::TraceIO io, const vx_tlas_multihit_args& a)
 {
     VX_TRY(upload_camera(o->camera, o->stream, io));
     const uint64_t nitems = o->nnodes == 0 ? 0 : o->nitems;  // the list vx_octree_aabbs returns
-    vx::launch_octree_multihit(o->dnodes, o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, K, count, after_t, after_prim, o->stream);
+    vx::launch_octree_multihit(o->dnodes, o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, multi_io(a), o->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
 }
 
-vx_status vx_octree_trace_multi_device(const vx_octree* oc, const vx_multihit_args* a)
+vx_status vx_octree_trace_multi_device(const vx_octree* oc, const vx_multihit_args* args)
 {
+    const vx_tlas_multihit_args a = from_grid_args(args);
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(oc, a, &cam, &io));
+    VX_TRY(multihit_args_to_io(oc, args ? &a : nullptr, false, &cam, &io));
     if (!io.nrays) return VX_OK;
     vx_octree* o = const_cast<vx_octree*>(oc);
     DeviceGuard dg(o->device);
-    return octree_multihit_common(o, io, a->max_hits, a->count, a->after_t, a->after_prim);
+    return octree_multihit_common(o, io, a);
 }
 
-vx_status vx_octree_trace_multi(const vx_octree* oc, const vx_multihit_args* a)
+vx_status vx_octree_trace_multi(const vx_octree* oc, const vx_multihit_args* args)
 {
+    const vx_tlas_multihit_args a = from_grid_args(args);
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(oc, a, &cam, &io));
+    VX_TRY(multihit_args_to_io(oc, args ? &a : nullptr, false, &cam, &io));
     if (!io.nrays) return VX_OK;
     vx_octree* o = const_cast<vx_octree*>(oc);
     DeviceGuard dg(o->device);
-    return multihit_staged(*o, a, io, [&](const vx::TraceIO& sio, uint32_t* count, const float* after_t, const uint32_t* after_prim) {
-        return octree_multihit_common(o, sio, a->max_hits, count, after_t, after_prim);
-    });
+    return multihit_staged(*o, a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return octree_multihit_common(o, sio, d); });
 }
 
 void vx_octree_free(vx_octree* o)
@@ -3277,103 +3321,15 @@ vx_status vx_bvh_trace(const vx_bvh* bc, const float* host_rays, uint64_t nrays,
     });
 }
 
-// ---- multi-hit queries on the mesh (vx_meshmulti.hip) -------------------------------------------------------------------------------
-// Both structures share one argument form inside the library: vx_tlas_multihit_args, of which vx_bvh_multihit_args is the leading part.
-// The checks of vx_bvh_trace_multi* / vx_tlas_trace_multi*, in the header's order; *io receives the ray batch (nrays == 0: nothing to do)
-static vx_status mesh_multihit_args_to_io(const void* handle, const vx_tlas_multihit_args* a, bool tlas, vx::Camera* cam, vx::TraceIO* io)
-{
-    if (!handle || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
-    const vx_multihit_args& m = a->m;
-    if (m.max_hits < 1 || m.max_hits > VX_MULTIHIT_MAX) return fail(VX_ERR_INVALID_ARG, "max_hits must be 1..VX_MULTIHIT_MAX");
-    const bool cursor = m.after_t != nullptr;
-    if (cursor != (m.after_prim != nullptr) || (tlas && cursor != (a->after_instance != nullptr)))
-        return fail(VX_ERR_INVALID_ARG, tlas ? "the cursor needs after_t, after_instance and after_prim" : "the cursor needs both after_t and after_prim");
-    const vx_trace_args& b = m.base;
-    if (b.any_hit || b.normal || b.shadowed || b.hits || b.num_hits)
-        return fail(VX_ERR_INVALID_ARG, "any_hit, normal, shadowed, hits and num_hits are not part of the multi-hit query");
-    const bool camera = b.view_inverse && b.proj_inverse && b.width && b.height;
-    if (!b.rays && !camera && !b.num_rays) { io->nrays = 0; return VX_OK; }  // zero rays
-    return args_to_io(&b, cam, io);
-}
-
-static vx::MeshMultiIO mesh_multi_io(const vx_tlas_multihit_args& a)
-{
-    vx::MeshMultiIO m;
-    m.K = a.m.max_hits;
-    m.count = a.m.count;
-    m.bary = a.bary;
-    m.instance = a.instance;
-    m.after_t = a.m.after_t;
-    m.after_instance = a.after_instance;
-    m.after_prim = a.m.after_prim;
-    return m;
-}
-
-// the host variants: every non-null array of `a` through pooled device memory of `home` (the handle: its device and stream), then
-// `run(io, d)` on the staged batch io and the staged copy d of the arguments
-extern "C++" {
-template <class Run>
-static vx_status mesh_multihit_staged(const Home& home, const vx_tlas_multihit_args& a, vx::TraceIO io, Run run)
-{
-    const size_t n = (size_t)io.nrays, K = a.m.max_hits;
-    hipStream_t stream = home.stream;
-    DevBuf dr{&home}, dtm{&home}, dat{&home}, dai{&home}, dap{&home}, dt{&home}, dp{&home}, db{&home}, di{&home}, dc{&home};
-    auto upload = [&](DevBuf& b, const void* host, size_t bytes) -> hipError_t {
-        if (!host) return hipSuccess;
-        const hipError_t e = b.ensure(bytes);
-        return e == hipSuccess ? hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, stream) : e;
-    };
-    VX_HIP(upload(dr, a.m.base.rays, n * 24));
-    VX_HIP(upload(dtm, a.m.base.tmax_per_ray, n * 4));
-    VX_HIP(upload(dat, a.m.after_t, n * 4));
-    VX_HIP(upload(dai, a.after_instance, n * 4));
-    VX_HIP(upload(dap, a.m.after_prim, n * 4));
-    if (a.m.base.t) VX_HIP(dt.ensure(n * K * 4));
-    if (a.m.base.prim) VX_HIP(dp.ensure(n * K * 4));
-    if (a.bary) VX_HIP(db.ensure(n * K * 8));
-    if (a.instance) VX_HIP(di.ensure(n * K * 4));
-    if (a.m.count) VX_HIP(dc.ensure(n * 4));
-    if (io.rays) io.rays = dr.as<float>();
-    if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
-    io.t_out = dt.as<float>();
-    io.prim_out = dp.as<uint32_t>();
-    vx_tlas_multihit_args d = a;
-    d.m.count = dc.as<uint32_t>();
-    d.m.after_t = dat.as<float>();
-    d.after_instance = dai.as<uint32_t>();
-    d.m.after_prim = dap.as<uint32_t>();
-    d.bary = db.as<float>();
-    d.instance = di.as<uint32_t>();
-    const vx_status st = run(io, d);
-    if (st != VX_OK) {
-        (void)hipStreamSynchronize(stream);  // the uploads read the caller's arrays
-        return st;
-    }
-    if (a.m.base.t) VX_HIP(hipMemcpyAsync(a.m.base.t, dt.p, n * K * 4, hipMemcpyDeviceToHost, stream));
-    if (a.m.base.prim) VX_HIP(hipMemcpyAsync(a.m.base.prim, dp.p, n * K * 4, hipMemcpyDeviceToHost, stream));
-    if (a.bary) VX_HIP(hipMemcpyAsync(a.bary, db.p, n * K * 8, hipMemcpyDeviceToHost, stream));
-    if (a.instance) VX_HIP(hipMemcpyAsync(a.instance, di.p, n * K * 4, hipMemcpyDeviceToHost, stream));
-    if (a.m.count) VX_HIP(hipMemcpyAsync(a.m.count, dc.p, n * 4, hipMemcpyDeviceToHost, stream));
-    VX_HIP(hipStreamSynchronize(stream));
-    return VX_OK;
-}
-}  // extern "C++"
-
+// ---- multi-hit queries on the mesh (vx_meshmulti.hip): the argument form, checks and staging of vx_trace_multi above
 // the query on device arrays: io's pointers and those of `a` are device memory
 static vx_status bvh_multihit_common(vx_bvh* b, vx::TraceIO io, const vx_tlas_multihit_args& a)
 {
     VX_TRY(upload_camera(b->camera, b->stream, io));
     vx::launch_bvh_multihit(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height,
-                            b->extent, b->coord_max, io, mesh_multi_io(a), b->stream);
+                            b->extent, b->coord_max, io, multi_io(a), b->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
-}
-
-static vx_tlas_multihit_args from_bvh_args(const vx_bvh_multihit_args* a)
-{
-    vx_tlas_multihit_args x{};
-    if (a) { x.m = a->m; x.bary = a->bary; }
-    return x;
 }
 
 vx_status vx_bvh_trace_multi_device(const vx_bvh* bc, const vx_bvh_multihit_args* args)
@@ -3381,7 +3337,7 @@ vx_status vx_bvh_trace_multi_device(const vx_bvh* bc, const vx_bvh_multihit_args
     const vx_tlas_multihit_args a = from_bvh_args(args);
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(mesh_multihit_args_to_io(bc, args ? &a : nullptr, false, &cam, &io));
+    VX_TRY(multihit_args_to_io(bc, args ? &a : nullptr, false, &cam, &io));
     if (!io.nrays) return VX_OK;
     vx_bvh* b = const_cast<vx_bvh*>(bc);
     DeviceGuard dg(b->device);
@@ -3393,11 +3349,11 @@ vx_status vx_bvh_trace_multi(const vx_bvh* bc, const vx_bvh_multihit_args* args)
     const vx_tlas_multihit_args a = from_bvh_args(args);
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(mesh_multihit_args_to_io(bc, args ? &a : nullptr, false, &cam, &io));
+    VX_TRY(multihit_args_to_io(bc, args ? &a : nullptr, false, &cam, &io));
     if (!io.nrays) return VX_OK;
     vx_bvh* b = const_cast<vx_bvh*>(bc);
     DeviceGuard dg(b->device);
-    return mesh_multihit_staged(*b, a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return bvh_multihit_common(b, sio, d); });
+    return multihit_staged(*b, a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return bvh_multihit_common(b, sio, d); });
 }
 
 void vx_bvh_free(vx_bvh* b)
@@ -3704,7 +3660,7 @@ static vx_status tlas_multihit_common(vx_tlas* t, vx::TraceIO io, const vx_tlas_
 {
     VX_TRY(upload_camera(t->camera, t->stream, io));
     VX_TRY(tlas_wait_blas(t));
-    vx::launch_tlas_multihit(tlas_dev(t), io, mesh_multi_io(a), t->stream);
+    vx::launch_tlas_multihit(tlas_dev(t), io, multi_io(a), t->stream);
     VX_HIP(hipGetLastError());
     return tlas_fence_blas(t);
 }
@@ -3713,7 +3669,7 @@ vx_status vx_tlas_trace_multi_device(const vx_tlas* tc, const vx_tlas_multihit_a
 {
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(mesh_multihit_args_to_io(tc, a, true, &cam, &io));
+    VX_TRY(multihit_args_to_io(tc, a, true, &cam, &io));
     if (!io.nrays) return VX_OK;
     vx_tlas* t = const_cast<vx_tlas*>(tc);
     DeviceGuard dg(t->device);
@@ -3724,11 +3680,11 @@ vx_status vx_tlas_trace_multi(const vx_tlas* tc, const vx_tlas_multihit_args* a)
 {
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(mesh_multihit_args_to_io(tc, a, true, &cam, &io));
+    VX_TRY(multihit_args_to_io(tc, a, true, &cam, &io));
     if (!io.nrays) return VX_OK;
     vx_tlas* t = const_cast<vx_tlas*>(tc);
     DeviceGuard dg(t->device);
-    return mesh_multihit_staged(*t, *a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return tlas_multihit_common(t, sio, d); });
+    return multihit_staged(*t, *a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return tlas_multihit_common(t, sio, d); });
 }
 
 void vx_tlas_free(vx_tlas* t)

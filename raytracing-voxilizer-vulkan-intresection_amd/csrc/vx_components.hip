@@ -28,12 +28,6 @@
 
 namespace vx {
 
-#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
-    do {                                                                     \
-        ProfScope ps_(#kern, stream);                                        \
-        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
-    } while (0)
-
 namespace {
 
 constexpr uint32_t kBY = 16, kBZ = 16;    // brick rows: 16 along y by 16 along z, one lane each

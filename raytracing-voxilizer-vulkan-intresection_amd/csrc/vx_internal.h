@@ -42,6 +42,12 @@ struct ProfScope {
     hipStream_t s_;
     hipEvent_t a_;
 };
+// every kernel launch goes through here so that the optional event profiler sees it
+#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
+    do {                                                                     \
+        ProfScope ps_(#kern, stream);                                        \
+        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
+    } while (0)
 
 // ---- launchers (all asynchronous on `s`) ------------------------------------------------------------------
 // K1: bbox of all vertices with the reference's first-occurrence tie rule; out6 = min xyz, max xyz (device).
@@ -215,21 +221,31 @@ bool launch_trace(const GridParams& g, const TraceMips& mips, const uint32_t* wo
                   const uint32_t* prefix16 = nullptr /*optional: launch_scan_u32's group16 of word_prefix*/, WalkQueue* queue = nullptr,
                   const WalkRing* ring = nullptr /*walk_ring_cap's ring for this batch: t + prim batches are ranked inside k_walk*/);
 
-// Multi-hit query on the grid (vx_multihit.hip): per ray the first K (1..32) accepted hits in (t, prim) order into io.t_out / io.prim_out (K
-// entries per ray, ray-major, padded with -1 / all ones; both optional) and the number of all accepted hits into count (optional); after_t /
-// after_prim: the optional per-ray cursor.  io as for launch_octree_trace (cam_dev, not cam); the other outputs of io are not written.
-// mips.bricks3 or word_prefix null: every ray misses.
-void launch_multihit(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, uint32_t K, uint32_t* count,
-                     const float* after_t, const uint32_t* after_prim, hipStream_t s);
+// Multi-hit queries (vx_hitlist.h; the grid in vx_multihit.hip, the octree in vx_octmulti.hip, the mesh in vx_meshmulti.hip): per ray the
+// first K (1..32) accepted primitives in (t, prim) order -- (t, instance, prim) on a TLAS -- into io.t_out / io.prim_out / bary / instance (K
+// entries per ray, ray-major, padded with -1 / all ones / (0, 0); all optional) and the number of all accepted primitives into count
+// (optional); after_*: the optional per-ray cursor.  bary: the mesh only; instance, after_instance: the TLAS only.  io's other outputs are
+// not written.
+struct MultiIO {
+    uint32_t K = 0;
+    uint32_t* count = nullptr;
+    float* bary = nullptr;
+    uint32_t* instance = nullptr;
+    const float* after_t = nullptr;
+    const uint32_t* after_instance = nullptr;
+    const uint32_t* after_prim = nullptr;
+};
+// On the grid: io as for launch_octree_trace (cam_dev, not cam).  mips.bricks3 or word_prefix null: every ray misses.
+void launch_multihit(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, const MultiIO& m, hipStream_t s);
 
 // First hit per ray against the octree's AABB list by descending its node array (vx_octrace.hip).  io as for launch_trace (cam_dev, not cam;
 // prim = index in vx_octree_aabbs order); nodes may be null / nitems 0: every ray misses.
 void launch_octree_trace(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,
                          hipStream_t s);
-// Multi-hit query on the octree (vx_octmulti.hip): launch_multihit's outputs and cursor over the runs of equal codes of the item list (a run
-// is one voxel, prim = its first list index).  nodes / items / nitems as for launch_octree_trace.
+// Multi-hit query on the octree, over the runs of equal codes of the item list (a run is one voxel, prim = its first list index).  nodes /
+// items / nitems as for launch_octree_trace.
 void launch_octree_multihit(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,
-                            uint32_t K, uint32_t* count, const float* after_t, const uint32_t* after_prim, hipStream_t s);
+                            const MultiIO& m, hipStream_t s);
 
 // Triangle BVH (vx_bvh.hip).  Build, all on `s`: launch_bvh_prep (box6 = ordered-uint bounds of all triangles, initialised to ~0 x3 / 0 x3;
 // *err |= 1 when an index leaves [0, nv); keys = Morton code << 32 | triangle), launch_sort_u64 over 62 bits, launch_bvh_tree (radix tree,
@@ -288,22 +304,10 @@ struct TlasDev {
 void launch_tlas_trace(const TlasDev& T, const TraceIO& io, float* bary_out, uint32_t* inst_out, hipStream_t s);
 float tlas_ray_pad();  // vx_tlas.hip: the per-ray widening of every TLAS box test, per unit of cond_max |o|
 
-// Multi-hit queries on the mesh (vx_meshmulti.hip): per ray the first K (1..32) accepted triangles in (t, prim) order -- (t, instance, prim) on
-// a TLAS -- into io.t_out / io.prim_out / bary / instance (K entries per ray, ray-major, padded with -1 / all ones / (0, 0); all optional)
-// and the number of all accepted triangles into count (optional); after_*: the optional per-ray cursor (after_instance: TLAS only).  io as
-// for launch_bvh_trace; its other outputs are not written.  The remaining arguments are launch_bvh_trace's / launch_tlas_trace's.
-struct MeshMultiIO {
-    uint32_t K = 0;
-    uint32_t* count = nullptr;
-    float* bary = nullptr;
-    uint32_t* instance = nullptr;
-    const float* after_t = nullptr;
-    const uint32_t* after_instance = nullptr;
-    const uint32_t* after_prim = nullptr;
-};
+// Multi-hit queries on the mesh: io as for launch_bvh_trace, the remaining arguments launch_bvh_trace's / launch_tlas_trace's.
 void launch_bvh_multihit(const float* nodes, const float* tris, const uint32_t* ill, uint32_t nill, uint32_t ntri, uint32_t height, float extent,
-                         float coord_max, const TraceIO& io, const MeshMultiIO& m, hipStream_t s);
-void launch_tlas_multihit(const TlasDev& T, const TraceIO& io, const MeshMultiIO& m, hipStream_t s);
+                         float coord_max, const TraceIO& io, const MultiIO& m, hipStream_t s);
+void launch_tlas_multihit(const TlasDev& T, const TraceIO& io, const MultiIO& m, hipStream_t s);
 
 #if defined(__HIPCC__)
 // The unit geometric normal of triangle k (leaf-order position in its BLAS) of instance inst in WORLD space: vertices M*v in the pinned

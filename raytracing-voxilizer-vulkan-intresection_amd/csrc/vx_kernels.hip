@@ -28,13 +28,6 @@ static inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap)
     if (b > cap) b = cap;
     return (unsigned)b;
 }
-// every kernel launch goes through here so that the optional event profiler (vx_prof.cpp) sees it
-#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
-    do {                                                                     \
-        ProfScope ps_(#kern, stream);                                        \
-        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
-    } while (0)
-
 constexpr unsigned kMaxBlocks = 256 * 8;  // 256 CUs x 8 resident 256-thread blocks: grid-stride beyond that
 
 // ------------------------------------------------------------------------------------------------------------

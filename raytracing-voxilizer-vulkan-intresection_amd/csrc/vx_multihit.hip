@@ -1,9 +1,10 @@
 // vx_multihit.hip -- multi-hit ray query on the voxel grids (vx_trace_multi*): per ray the first K accepted hits in (t, prim) order and the
 // number of all accepted hits, against the same boxes and under the same acceptance rule as K6 (vx_walk.hip; raytrace.rint:46-71).
 //
-// Contract (include/voxhip.h): A(r) = the occupied cells c whose t_c = hit_aabb(cell_aabb(c)) satisfies t_c > 0 and tmin <= t_c <= tmax (or
-// tmax_per_ray[r]) and, with a cursor, (t_c, prim_c) > (after_t[r], after_prim[r]); sorted by (t, prim) with t compared as float.  Slots
-// j < min(K, |A|) hold the j-th element, the others -1.0f / 0xFFFFFFFF; count = |A|.  Every output is bit-equal to the brute force over all boxes.
+// Contract: vx_hitlist.h's, over the occupied cells c with t_c = hit_aabb(cell_aabb(c)) and prim_c = the cell's rank in the Bool list.
+// Every output is bit-equal to the brute force over all boxes.  The list below is this kernel's own text of vx_hitlist.h's HitList (the
+// same order, cursor, eviction and strict pruning), kept because the kernel sits at 147-155 VGPRs with its SGPRs spilled and ran 2-4 %
+// slower on the shared struct; what it adds is the lazy prim, below.
 //
 // Enumeration.  The candidate cells come from the major-axis slab walk of vx_walk.hip, on the structure k_build_bricks3 / k_build_mip2 make for
 // it (level-0 bricks in the orientation of the ray's major axis, level-1 and level-2 mips): the same position tolerance, the same [ta, tb] of
@@ -30,8 +31,7 @@
 //
 // One ray per lane, workgroups of one wave (no barrier anywhere); the buffer is K' * 8 B * 64 lanes for K' = 4, 8, 16, 32 >= K, chosen at
 // launch: 2, 4, 8, 16 KiB per workgroup, so K = 32 still leaves ten workgroups on a CU's 160 KiB of LDS.
-#include "vx_internal.h"
-#include "vx_ray.h"
+#include "vx_hitlist.h"
 
 #include <cstring>
 
@@ -39,15 +39,7 @@
 
 namespace vx {
 
-#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
-    do {                                                                     \
-        ProfScope ps_(#kern, stream);                                        \
-        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
-    } while (0)
-
 namespace {
-
-constexpr uint32_t kMhBlock = 64;  // lanes per workgroup: one wave
 
 struct MultiParams {
     GridParams g;
@@ -139,15 +131,15 @@ __device__ __forceinline__ bool mip_bit(const uint32_t* __restrict__ m, const ui
 }  // namespace
 
 template <int KC>
-__global__ __launch_bounds__(kMhBlock) void k_multihit(const MultiParams P)
+__global__ __launch_bounds__(kMultiBlock) void k_multihit(const MultiParams P)
 {
-    __shared__ uint32_t key_t[KC][kMhBlock];  // [slot][lane]: consecutive lanes on consecutive banks
-    __shared__ uint32_t key_p[KC][kMhBlock];
+    __shared__ uint32_t key_t[KC][kMultiBlock];  // [slot][lane]: consecutive lanes on consecutive banks
+    __shared__ uint32_t key_p[KC][kMultiBlock];
     const uint32_t lane = threadIdx.x;
     const GridParams& g = P.g;
     const uint32_t K = P.K;
     const bool counting = P.count != nullptr;
-    for (uint64_t r = (uint64_t)blockIdx.x * kMhBlock + lane; r < P.io.nrays; r += (uint64_t)gridDim.x * kMhBlock) {
+    for (uint64_t r = (uint64_t)blockIdx.x * kMultiBlock + lane; r < P.io.nrays; r += (uint64_t)gridDim.x * kMultiBlock) {
         float ox, oy, oz, dx, dy, dz;
         load_ray(P.io.rays == nullptr, r, P.io.rays, P.io.cam, ox, oy, oz, dx, dy, dz);
         const float tmax = P.io.tmax_per_ray ? P.io.tmax_per_ray[r] : P.io.tmax;
@@ -310,10 +302,9 @@ __global__ __launch_bounds__(kMhBlock) void k_multihit(const MultiParams P)
     }
 }
 
-void launch_multihit(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, uint32_t K, uint32_t* count,
-                     const float* after_t, const uint32_t* after_prim, hipStream_t s)
+void launch_multihit(const GridParams& g, const TraceMips& mips, const uint32_t* word_prefix, const TraceIO& io, const MultiIO& m, hipStream_t s)
 {
-    if (!io.nrays || !K) return;
+    if (!io.nrays || !m.K) return;
     MultiParams P;
     std::memset(&P, 0, sizeof(P));
     P.g = g;
@@ -326,18 +317,12 @@ void launch_multihit(const GridParams& g, const TraceMips& mips, const uint32_t*
     P.w2 = mips.w2;
     for (int a = 0; a < 3; ++a) { P.d1[a] = mips.d1[a]; P.d2[a] = mips.d2[a]; }
     P.inv_vs = 1.0f / g.vs;
-    P.K = K;
-    P.count = count;
-    P.after_t = after_t;
-    P.after_prim = after_prim;
+    P.K = m.K;
+    P.count = m.count;
+    P.after_t = m.after_t;
+    P.after_prim = m.after_prim;
     set_ray_args(P.io, io, s);
-    uint64_t nblk = (io.nrays + kMhBlock - 1) / kMhBlock;
-    if (nblk > (1ull << 22)) nblk = 1ull << 22;  // grid-stride beyond 2^28 rays
-    const dim3 grid((unsigned)nblk), block(kMhBlock);
-    if (K <= 4) VX_KL(k_multihit<4>, grid, block, 0, s, P);
-    else if (K <= 8) VX_KL(k_multihit<8>, grid, block, 0, s, P);
-    else if (K <= 16) VX_KL(k_multihit<16>, grid, block, 0, s, P);
-    else VX_KL(k_multihit<32>, grid, block, 0, s, P);
+    VX_MULTI_LAUNCH(k_multihit, io.nrays, m.K, 0, s, P);
 }
 
 }  // namespace vx

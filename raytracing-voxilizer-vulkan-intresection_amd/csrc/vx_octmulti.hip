@@ -1,11 +1,7 @@
-// vx_octmulti.hip -- multi-hit ray query on the octree (vx_octree_trace_multi*): per ray the first K accepted voxels in (t, prim) order and
-// the number of all accepted voxels, over the list vx_octree_aabbs returns (one box per Morton item, ascending code, duplicates included).
-//
-// Contract (include/voxhip.h).  A run is a maximal range of equal codes of the list; its boxes are identical, it stands for one voxel and its
-// prim is the first list index of the run -- the index k_octree_trace reports.  A(r) = the runs whose t = hit_aabb(box) satisfies t > 0 and
-// tmin <= t <= tmax (or tmax_per_ray[r]) and, with a cursor, (t, prim) > (after_t[r], after_prim[r]); sorted by (t, prim), t compared as
-// float.  Slots j < min(K, |A|) hold the j-th element, the others -1.0f / 0xFFFFFFFF; count = |A|.  Every output is bit-equal to the brute
-// force over the de-duplicated list.
+// vx_octmulti.hip -- multi-hit ray query on the octree (vx_octree_trace_multi*): vx_hitlist.h's contract over the list vx_octree_aabbs
+// returns (one box per Morton item, ascending code, duplicates included).  A run is a maximal range of equal codes of the list; its boxes
+// are identical, it stands for one voxel and its prim is the first list index of the run -- the index k_octree_trace reports.  The
+// primitives are the runs, t = hit_aabb(box).  Every output is bit-equal to the brute force over the de-duplicated list.
 //
 // Enumeration: the depth-first descent of k_octree_trace (vx_octrace.hip), with vx_octnode.h's node_corner / node_enter / item_aabb: the
 // corner of a node from its Morton prefix, four planes per axis per interior node, children front to back by octant ^ dirmask as bits of a
@@ -25,22 +21,20 @@
 // hit_aabb accepts.  A reported t is such a t0_v.  Hence a node holds no element of A(r), and is dropped, when
 //   * !(t1 > max(t0, 0)), or the degenerate-axis test fails: no voxel inside is hit at all;
 //   * t1 < tmin:          every t0_v < t1 < tmin;
-//   * t0 > the ray's tmax: every t0_v >= t0 > tmax;
 //   * t1 < after_t (cursor): every t0_v < after_t, in front of the cursor whatever the prim;
-//   * without `count`, once the buffer holds K entries: t0 STRICTLY greater than the K-th kept t -- every t0_v is then greater as well and
-//     cannot enter the list.  An equal t0 may still hold a smaller prim (front-to-back order is not list order for negative directions), so
-//     equality keeps the node.  A child kept in a level's mask before the buffer filled is tested again when it is popped, as the first-hit
-//     kernel tests popped children against `best` again.
-// With `count` the last rule is off: the ray visits every node its clipped interval enters.  A NaN tmin fails `t1 >= tmin` at the root, a
-// NaN tmax lets nodes through and fails `t <= tmax` at every voxel: nothing is accepted either way.  A non-finite ray enters no node.
+//   * t0 STRICTLY greater than the list's bound(): every t0_v >= t0 is then behind the ray's tmax, or -- without `count`, once the list
+//     holds K entries -- behind the K-th kept t and cannot enter the list.  An equal t0 may still hold a smaller prim (front-to-back order
+//     is not list order for negative directions), so equality keeps the node.  A child kept in a level's mask before the list filled is
+//     tested again when it is popped, as the first-hit kernel tests popped children against `best` again.  (The kept t are <= tmax, so
+//     bound() <= tmax always: the one comparison covers both.)
+// With `count` the ray visits every node its clipped interval enters.  A NaN tmin fails `t1 >= tmin` at the root, a NaN tmax lets nodes
+// through (the list stays empty, bound() is that NaN) and fails `t <= tmax` at every voxel: nothing is accepted either way.  A non-finite
+// ray enters no node.
 //
-// The K nearest hits of a lane live in LDS beside its descent stack, both [slot][lane] so that consecutive lanes fall on consecutive banks:
-// {node, child mask} per level (levels = max(bits, 1) entries) and (t bits, prim) per kept hit, sorted by insertion from the tail.  Accepted
-// t are positive floats, so the order of their bits as unsigned integers is their float order.  One ray per lane, workgroups of one wave, no
-// barrier anywhere; the buffer holds KC = 4, 8, 16 or 32 >= K entries, chosen at launch: 64 * 8 * (levels + KC) bytes per workgroup.
-#include "vx_internal.h"
+// The list lives in LDS beside the descent stack, [level][lane] as well: {node, child mask} per level (levels = max(bits, 1) entries);
+// 64 * 8 * (levels + KC) bytes per workgroup.
+#include "vx_hitlist.h"
 #include "vx_octnode.h"
-#include "vx_ray.h"
 
 #include <cstring>
 
@@ -48,59 +42,40 @@
 
 namespace vx {
 
-#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
-    do {                                                                     \
-        ProfScope ps_(#kern, stream);                                        \
-        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
-    } while (0)
-
 namespace {
 
-constexpr uint32_t kOmBlock = 64;  // lanes per workgroup: one wave
-
 struct OctMultiParams : OctGeom {
-    uint32_t K;
-    uint32_t* count;             // optional
-    const float* after_t;        // optional cursor (both or neither)
-    const uint32_t* after_prim;
-    RayArgs io;                  // rays / camera / nrays / tmin / tmax / tmax_per_ray; t_out and prim_out hold K entries per ray
+    MultiOut o;
 };
 
 }  // namespace
 
 template <int KC>
-__global__ __launch_bounds__(kOmBlock) void k_octree_multihit(const OctMultiParams P)
+__global__ __launch_bounds__(kMultiBlock) void k_octree_multihit(const OctMultiParams P)
 {
     extern __shared__ uint32_t om_stack[];                   // [level][lane] node, then [level][lane] mask
-    __shared__ uint32_t key_t[KC][kOmBlock];                 // [slot][lane]
-    __shared__ uint32_t key_p[KC][kOmBlock];
+    __shared__ uint32_t keys[HitList<KC, false, false>::kWords];
     uint32_t* stk_node = om_stack;
-    uint32_t* stk_mask = om_stack + P.levels * kOmBlock;
+    uint32_t* stk_mask = om_stack + P.levels * kMultiBlock;
     const uint32_t lane = threadIdx.x;
     const GridParams g = P.g;
     const uint32_t bits = P.bits;
-    const uint32_t K = P.K;
-    const bool counting = P.count != nullptr;
-    for (uint64_t r = (uint64_t)blockIdx.x * kOmBlock + lane; r < P.io.nrays; r += (uint64_t)gridDim.x * kOmBlock) {
+    const RayArgs& io = P.o.io;
+    for (uint64_t r = (uint64_t)blockIdx.x * kMultiBlock + lane; r < io.nrays; r += (uint64_t)gridDim.x * kMultiBlock) {
         float ox, oy, oz, dx, dy, dz;
-        load_ray(P.io.rays == nullptr, r, P.io.rays, P.io.cam, ox, oy, oz, dx, dy, dz);
+        load_ray(io.rays == nullptr, r, io.rays, io.cam, ox, oy, oz, dx, dy, dz);
         SlabRay R;
         make_slab_ray(ox, oy, oz, dx, dy, dz, R);
         const uint32_t dirmask = (signbit(dx) ? 1u : 0u) | (signbit(dy) ? 2u : 0u) | (signbit(dz) ? 4u : 0u);
-        const float tmax = P.io.tmax_per_ray ? P.io.tmax_per_ray[r] : P.io.tmax;
-        const float tmin = P.io.tmin;
-        const float cur_t = P.after_t ? P.after_t[r] : -1.0f;
-        const uint32_t cur_p = P.after_prim ? P.after_prim[r] : 0u;
-        uint32_t n = 0;          // hits kept, <= K
-        uint32_t total = 0;      // |A(r)|
-        float kth = INFINITY;    // the K-th kept t once the buffer is full
-        float cut = INFINITY;    // nodes with t0 > cut are dropped: kth without `count`, never with it
+        HitList<KC, false, false> L;
+        list_begin(L, keys, lane, P.o, r);
+        const float tmax = L.tmax, tmin = io.tmin, cur_t = L.cur_t;
 
         bool alive = P.nitems != 0 && !ray_nonfinite(ox, oy, oz, dx, dy, dz);  // a non-finite ray is a miss: no node is entered for it
         if (alive) {
             const uint32_t c0[3] = {0u, 0u, 0u};
             float t0, t1;
-            alive = node_enter(g, R, c0, 1u << bits, t0, t1) && !(t0 > tmax) && t1 >= tmin && !(t1 < cur_t);
+            alive = node_enter(g, R, c0, 1u << bits, t0, t1) && !(t0 > L.bound()) && t1 >= tmin && !(t1 < cur_t);
         }
         uint32_t cur = 0, depth = 0;
         uint64_t path = 0;
@@ -121,26 +96,7 @@ __global__ __launch_bounds__(kOmBlock) void k_octree_multihit(const OctMultiPara
                     item_aabb(g, m, bb);
                     const float t = hit_aabb(bb, R.o, R.inv);
                     if (!(t > 0.0f && t >= tmin && t <= tmax)) continue;       // rint:69, rgen:50-51
-                    if (t < cur_t || (t == cur_t && j <= cur_p)) continue;      // not strictly after the cursor
-                    ++total;
-                    if (n == K && t > kth) continue;                            // counted; behind the list (an equal t may carry a smaller prim)
-                    const uint32_t tbits = __float_as_uint(t);
-                    uint32_t jn = n < K ? n : K - 1u;  // where the list's new tail goes: the K-th entry falls out of a full list
-                    if (n == K && !(tbits < key_t[jn][lane] || (tbits == key_t[jn][lane] && j < key_p[jn][lane]))) continue;
-                    while (jn > 0u) {
-                        const uint32_t pt = key_t[jn - 1u][lane], pp = key_p[jn - 1u][lane];
-                        if (!(tbits < pt || (tbits == pt && j < pp))) break;
-                        key_t[jn][lane] = pt;
-                        key_p[jn][lane] = pp;
-                        --jn;
-                    }
-                    key_t[jn][lane] = tbits;
-                    key_p[jn][lane] = j;
-                    if (n < K) ++n;
-                    if (n == K) {
-                        kth = __uint_as_float(key_t[K - 1u][lane]);
-                        cut = counting ? INFINITY : kth;
-                    }
+                    L.offer(t, j);
                 }
             } else {
                 // interior: the children the ray enters, front to back, as bits of the level's mask; four planes per axis (vx_octrace.hip)
@@ -161,6 +117,7 @@ __global__ __launch_bounds__(kOmBlock) void k_octree_multihit(const OctMultiPara
                     lo_in[a] = !R.deg[a] || (p0 <= R.o[a] && R.o[a] <= p1);
                     hi_in[a] = !R.deg[a] || (p2 <= R.o[a] && R.o[a] <= p3);
                 }
+                const float bound = L.bound();
                 uint32_t mask = 0u;
 #pragma unroll
                 for (uint32_t oct = 0; oct < 8u; ++oct) {  // (octant order: ch[] stays in registers; the mask bit is the visiting position)
@@ -168,34 +125,34 @@ __global__ __launch_bounds__(kOmBlock) void k_octree_multihit(const OctMultiPara
                     const float t0 = fmaxf(ux ? hi_mn[0] : lo_mn[0], fmaxf(uy ? hi_mn[1] : lo_mn[1], uz ? hi_mn[2] : lo_mn[2]));
                     const float t1 = fminf(ux ? hi_mx[0] : lo_mx[0], fminf(uy ? hi_mx[1] : lo_mx[1], uz ? hi_mx[2] : lo_mx[2]));
                     const bool inside = (ux ? hi_in[0] : lo_in[0]) && (uy ? hi_in[1] : lo_in[1]) && (uz ? hi_in[2] : lo_in[2]);
-                    const bool in = ch[oct] != 0xFFFFFFFFu && inside && t1 > fmaxf(t0, 0.0f) && !(t0 > tmax) && t1 >= tmin && !(t1 < cur_t) && !(t0 > cut);
+                    const bool in = ch[oct] != 0xFFFFFFFFu && inside && t1 > fmaxf(t0, 0.0f) && !(t0 > bound) && t1 >= tmin && !(t1 < cur_t);
                     mask |= in ? 1u << (oct ^ dirmask) : 0u;
                 }
                 if (mask) {
-                    stk_node[depth * kOmBlock + lane] = cur;
-                    stk_mask[depth * kOmBlock + lane] = mask;
+                    stk_node[depth * kMultiBlock + lane] = cur;
+                    stk_mask[depth * kMultiBlock + lane] = mask;
                     top = (int)depth;
                 }
             }
             // next node: the nearest remaining child of the deepest live level
             bool next = false;
             while (top >= 0) {
-                uint32_t m = stk_mask[(uint32_t)top * kOmBlock + lane];
+                uint32_t m = stk_mask[(uint32_t)top * kMultiBlock + lane];
                 if (!m) { --top; continue; }
                 const uint32_t i = (uint32_t)__builtin_ctz(m);
                 m &= m - 1u;
-                stk_mask[(uint32_t)top * kOmBlock + lane] = m;
+                stk_mask[(uint32_t)top * kMultiBlock + lane] = m;
                 const uint32_t oct = i ^ dirmask;
                 const uint32_t cd = (uint32_t)top + 1u;
                 const uint64_t cpath = ((path >> (3u * (depth - (uint32_t)top))) << 3) | oct;
-                if (cut < INFINITY) {  // the list has filled since the child was kept
+                if (L.tightened()) {  // the list may have filled since the child was kept
                     uint32_t cc[3];
                     node_corner(cpath, cd, bits, cc);
                     float t0, t1;
                     (void)node_enter(g, R, cc, 1u << (bits - cd), t0, t1);
-                    if (t0 > cut) continue;
+                    if (t0 > L.bound()) continue;
                 }
-                cur = P.nodes[stk_node[(uint32_t)top * kOmBlock + lane]].children[oct];
+                cur = P.nodes[stk_node[(uint32_t)top * kMultiBlock + lane]].children[oct];
                 depth = cd;
                 path = cpath;
                 next = true;
@@ -203,37 +160,20 @@ __global__ __launch_bounds__(kOmBlock) void k_octree_multihit(const OctMultiPara
             }
             if (!next) break;
         }
-        // ---- outputs: K entries per ray, ray-major
-        float* t_out = P.io.t_out ? P.io.t_out + r * K : nullptr;
-        uint32_t* p_out = P.io.prim_out ? P.io.prim_out + r * K : nullptr;
-        for (uint32_t jn = 0; jn < K; ++jn) {
-            if (t_out) t_out[jn] = jn < n ? __uint_as_float(key_t[jn][lane]) : -1.0f;
-            if (p_out) p_out[jn] = jn < n ? key_p[jn][lane] : 0xFFFFFFFFu;
-        }
-        if (counting) P.count[r] = total;
+        L.write(P.o, r);
     }
 }
 
 void launch_octree_multihit(const vx_octree_node* nodes, const uint64_t* items, uint64_t nitems, uint32_t bits, const float root_min[3], float vs, const TraceIO& io,
-                            uint32_t K, uint32_t* count, const float* after_t, const uint32_t* after_prim, hipStream_t s)
+                            const MultiIO& m, hipStream_t s)
 {
-    if (!io.nrays || !K) return;
+    if (!io.nrays || !m.K) return;
     OctMultiParams P;
     std::memset(&P, 0, sizeof(P));
     set_oct_geom(P, nodes, items, nitems, bits, root_min, vs);
-    P.K = K;
-    P.count = count;
-    P.after_t = after_t;
-    P.after_prim = after_prim;
-    set_ray_args(P.io, io, s);
-    const size_t shmem = (size_t)P.levels * kOmBlock * 8u;  // the stack; the K buffer is static
-    uint64_t nblk = (io.nrays + kOmBlock - 1) / kOmBlock;
-    if (nblk > (1ull << 22)) nblk = 1ull << 22;  // grid-stride beyond 2^28 rays
-    const dim3 grid((unsigned)nblk), block(kOmBlock);
-    if (K <= 4) VX_KL(k_octree_multihit<4>, grid, block, shmem, s, P);
-    else if (K <= 8) VX_KL(k_octree_multihit<8>, grid, block, shmem, s, P);
-    else if (K <= 16) VX_KL(k_octree_multihit<16>, grid, block, shmem, s, P);
-    else VX_KL(k_octree_multihit<32>, grid, block, shmem, s, P);
+    set_multi_out(P.o, io, m, s);
+    const size_t shmem = (size_t)P.levels * kMultiBlock * 8u;  // the stack; the list is static
+    VX_MULTI_LAUNCH(k_octree_multihit, io.nrays, m.K, shmem, s, P);
 }
 
 }  // namespace vx

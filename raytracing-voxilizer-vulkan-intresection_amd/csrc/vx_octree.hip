@@ -32,12 +32,6 @@
 
 namespace vx {
 
-#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
-    do {                                                                     \
-        ProfScope ps_(#kern, stream);                                        \
-        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
-    } while (0)
-
 namespace {
 
 // number of leading octal digits (of `bits` per code) two codes share

@@ -36,12 +36,6 @@
 
 namespace vx {
 
-#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
-    do {                                                                     \
-        ProfScope ps_(#kern, stream);                                        \
-        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
-    } while (0)
-
 namespace {
 
 constexpr uint32_t kBuildBlock = 256;

@@ -13,12 +13,6 @@
 
 namespace vx {
 
-#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
-    do {                                                                     \
-        ProfScope ps_(#kern, stream);                                        \
-        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
-    } while (0)
-
 // Level-1 mip: one bit per brick, x-fastest, from the z-oriented brick words.
 __global__ __launch_bounds__(256) void k_brick_mip1(const unsigned long long* __restrict__ bricks, uint64_t nbricks, uint32_t* __restrict__ m1)
 {

@@ -51,12 +51,6 @@
 
 namespace vx {
 
-#define VX_KL(kern, grid, block, shmem, stream, ...)                         \
-    do {                                                                     \
-        ProfScope ps_(#kern, stream);                                        \
-        hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);   \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------------------------
 // Brick-major re-tiling of the occupancy bitmask through LDS, three orientations.  A workgroup takes 64 bricks in a row along
 // x for one (by, bz): 64 voxel rows (8 z x 8 y) of 512 voxels.  Reads: row-contiguous words, funnel-shifted to the chunk's own

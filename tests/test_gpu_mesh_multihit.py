@@ -19,7 +19,8 @@ pytestmark = pytest.mark.gpu
 
 F = np.float32
 INVALID_ARG = 1
-KS = (1, 4, 5, 8, 32)
+# every compiled list size KC = 4, 8, 16, 32 exactly full (K = KC) and at its smallest K (5, 9, 17)
+KS = (1, 4, 5, 8, 9, 16, 17, 32)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "raytracing-voxilizer-vulkan-intresection_amd")
 ALL = ("t", "prim", "bary", "count")
@@ -104,15 +105,15 @@ def test_bvh_windows(gpu, name):
     same(b.trace_multi(c.rays, max_hits=2, tmax_per_ray=tpr, want=("t", "prim")), mm.select(mm.all_hits(c.v, c.t, c.rays, tmax_per_ray=tpr), 2), "tmax_per_ray, no count")
 
 
-@pytest.mark.parametrize("k", [5, 32])
+@pytest.mark.parametrize("k", [5, 16, 32])
 def test_bvh_paging_with_the_cursor(gpu, k):
-    """`layers`: pages chained through `after` until every ray is exhausted (K = 32: three pages of its 80 hits; K = 5 ends pages inside
+    """`layers`: pages chained through `after` until every ray is exhausted (K = 32: three pages of its 80 hits, K = 16: five; K = 5 ends pages inside
     runs of equal t) reassemble the whole list and count down the total"""
     c = mc.bvh_case("layers")
     b = bvhs("layers")[0]
     total = mm.select(c.hits, 1)["count"]
     npages = -(-int(total.max()) // k)
-    assert npages == (3 if k == 32 else 16)
+    assert npages == {5: 16, 16: 5, 32: 3}[k]
     whole = mm.select(c.hits, k * npages)
     n = len(c.rays)
     cur = (np.full(n, F(-1), F), np.full(n, 12345, np.uint32))   # (-1, anything) = no cursor

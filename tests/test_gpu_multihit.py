@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 F = np.float32
 INVALID_ARG = 1
-KS = (1, 3, 32)
+# every compiled list size KC = 4, 8, 16, 32 exactly full (K = KC) and at its smallest K (5, 9, 17)
+KS = (1, 3, 4, 5, 8, 9, 16, 17, 32)
 ORG = (0.25, -1.0, 3.0)   # with vs = 0.5 every lattice plane and box corner is an exact float: rays can lie exactly on them
 VS = F(0.5)
 # the full brick's lattice is NOT exact: boxes of neighbouring cells overlap by a few float32 ulps at some planes, and a ray inside such an
@@ -253,24 +254,25 @@ def test_windows(gpu, name):
 
 @pytest.mark.parametrize("name", ["full_8", "long_130", "ragged"])
 def test_paging_with_the_cursor(gpu, name):
-    """K = 2 pages chained through `after` reassemble the K = 32 list and count down the total"""
+    """K = 2 (and K = 16) pages chained through `after` reassemble the K = 32 list and count down the total"""
     c = _case(name)
     t32, p32, cnt = mr.select(c.times, 32)
     n = len(c.rays)
-    at, ap = np.full(n, F(-1), F), np.full(n, 12345, np.uint32)   # (-1, anything) = no cursor
-    pages_t, pages_p = [], []
-    for page in range(16):
-        got = c.g.trace_multi(c.rays, max_hits=2, after=(at, ap))
-        same(got, mr.select(c.times, 2, after=(at, ap)), "page %d" % page)
-        assert np.array_equal(got["count"], np.maximum(cnt.astype(np.int64) - 2 * page, 0))
-        pages_t.append(got["t"])
-        pages_p.append(got["prim"])
-        last = np.where(got["t"][:, 1] > 0, 1, 0)
-        have = got["t"][:, 0] > 0
-        at = np.where(have, got["t"][np.arange(n), last], at).astype(F)
-        ap = np.where(have, got["prim"][np.arange(n), last], ap).astype(np.uint32)
-    assert np.array_equal(np.concatenate(pages_t, axis=1).view(np.uint32), t32.view(np.uint32))
-    assert np.array_equal(np.concatenate(pages_p, axis=1), p32)
+    for k in (2, 16):
+        at, ap = np.full(n, F(-1), F), np.full(n, 12345, np.uint32)   # (-1, anything) = no cursor
+        pages_t, pages_p = [], []
+        for page in range(32 // k):
+            got = c.g.trace_multi(c.rays, max_hits=k, after=(at, ap))
+            same(got, mr.select(c.times, k, after=(at, ap)), "K=%d page %d" % (k, page))
+            assert np.array_equal(got["count"], np.maximum(cnt.astype(np.int64) - k * page, 0))
+            pages_t.append(got["t"])
+            pages_p.append(got["prim"])
+            last = np.maximum((got["t"] > 0).sum(axis=1) - 1, 0)
+            have = got["t"][:, 0] > 0
+            at = np.where(have, got["t"][np.arange(n), last], at).astype(F)
+            ap = np.where(have, got["prim"][np.arange(n), last], ap).astype(np.uint32)
+        assert np.array_equal(np.concatenate(pages_t, axis=1).view(np.uint32), t32.view(np.uint32))
+        assert np.array_equal(np.concatenate(pages_p, axis=1), p32)
     # the early-out path under a cursor
     same(c.g.trace_multi(c.rays, max_hits=2, after=(at, ap), want=("t", "prim")), mr.select(c.times, 2, after=(at, ap)), "last page, no count")
 

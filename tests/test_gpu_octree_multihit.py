@@ -22,6 +22,8 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 INVALID_ARG, CAPACITY = 1, 8
 KS = (1, 3, 8, 32)
+# with KS: every compiled list size KC = 4, 8, 16, 32 exactly full (K = KC) and at its smallest K (5, 9, 17); at one leaf size
+MORE_KS = (4, 5, 9, 16, 17)
 LEAF_SIZES = (1, 16, 100)     # the direct node-array form (<= 64) and the level-by-level form (> 64)
 ALL_SCENES = om.SCENES + (om.TIE,)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,8 +62,7 @@ def _case(name, vs):
 
 
 # ---- the lists and the counts -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("max_items", LEAF_SIZES)
-@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("k,max_items", [(k, m) for m in LEAF_SIZES for k in KS] + [(k, 16) for k in MORE_KS])
 @pytest.mark.parametrize("name,vs", ALL_SCENES)
 def test_lists_and_counts(gpu, name, vs, k, max_items):
     c = _case(name, vs)
@@ -141,28 +142,29 @@ def _paged_reference(times, k):
 
 @pytest.mark.parametrize("name,vs", [om.TIE, ("cube", 0.0625)])
 def test_paging_with_the_cursor(gpu, name, vs):
-    """K = 3 pages chained through `after` reassemble the whole lists and count down the totals"""
+    """K = 3 (and K = 16) pages chained through `after` reassemble the whole lists and count down the totals"""
     c = _case(name, vs)
     ft, fp, cnt = _paged_reference(c.times, 32)
     n = len(c.rays)
-    at, ap = np.full(n, F(-1), F), np.full(n, 12345, np.uint32)   # (-1, anything) = no cursor
-    pages_t, pages_p = [], []
-    npages = -(-int(cnt.max()) // 3) + 1
-    for page in range(npages):
-        got = c.o.trace_multi(c.rays, max_hits=3, after=(at, ap))
-        same(got, mr.select(c.times, 3, after=(at, ap)), "page %d" % page)
-        assert np.array_equal(got["count"], np.maximum(cnt.astype(np.int64) - 3 * page, 0))
-        pages_t.append(got["t"])
-        pages_p.append(got["prim"])
-        last = np.maximum((got["t"] > 0).sum(axis=1) - 1, 0)
-        have = got["t"][:, 0] > 0
-        at = np.where(have, got["t"][np.arange(n), last], at).astype(F)
-        ap = np.where(have, got["prim"][np.arange(n), last], ap).astype(np.uint32)
-    gt, gp = np.concatenate(pages_t, axis=1), np.concatenate(pages_p, axis=1)
-    w = int(cnt.max())
-    assert gt.shape[1] >= w and ft.shape[1] >= w
-    assert np.array_equal(gt[:, :w].view(np.uint32), ft[:, :w].view(np.uint32)) and np.array_equal(gp[:, :w], fp[:, :w])
-    assert (gt[:, w:] == F(-1)).all() and (gp[:, w:] == 0xFFFFFFFF).all()
+    for k in (3, 16):
+        at, ap = np.full(n, F(-1), F), np.full(n, 12345, np.uint32)   # (-1, anything) = no cursor
+        pages_t, pages_p = [], []
+        npages = -(-int(cnt.max()) // k) + 1
+        for page in range(npages):
+            got = c.o.trace_multi(c.rays, max_hits=k, after=(at, ap))
+            same(got, mr.select(c.times, k, after=(at, ap)), "K=%d page %d" % (k, page))
+            assert np.array_equal(got["count"], np.maximum(cnt.astype(np.int64) - k * page, 0))
+            pages_t.append(got["t"])
+            pages_p.append(got["prim"])
+            last = np.maximum((got["t"] > 0).sum(axis=1) - 1, 0)
+            have = got["t"][:, 0] > 0
+            at = np.where(have, got["t"][np.arange(n), last], at).astype(F)
+            ap = np.where(have, got["prim"][np.arange(n), last], ap).astype(np.uint32)
+        gt, gp = np.concatenate(pages_t, axis=1), np.concatenate(pages_p, axis=1)
+        w = int(cnt.max())
+        assert gt.shape[1] >= w and ft.shape[1] >= w
+        assert np.array_equal(gt[:, :w].view(np.uint32), ft[:, :w].view(np.uint32)) and np.array_equal(gp[:, :w], fp[:, :w])
+        assert (gt[:, w:] == F(-1)).all() and (gp[:, w:] == 0xFFFFFFFF).all()
     # the early-out path under a cursor, in the middle of the lists
     mid_t, mid_p = np.where(cnt > 4, ft[:, 3], F(-1)).astype(F), np.where(cnt > 4, fp[:, 3], 0).astype(np.uint32)
     ref = mr.select(c.times, 3, after=(mid_t, mid_p))
