@@ -290,6 +290,70 @@ uint32_t advance_scan_gen(DevBuf& tmp, hipStream_t s)
     return tmp.scan_gen;
 }
 
+// A scan queued on a handle's scratch: the block sized and zero (ensure_scan_tmp), the scan its next generation.  *tagged (optional):
+// whether *total64 carries a.total_tag (launch_scan_u32).
+vx_status scan_on(DevBuf& tmp, hipStream_t s, const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, unsigned long long* total64,
+                  vx::ScanArgs a = vx::ScanArgs(), bool* tagged = nullptr)
+{
+    VX_HIP(ensure_scan_tmp(tmp, vx::scan_tmp_bytes(n), s));
+    a.tmp_is_zero = true;
+    a.gen = advance_scan_gen(tmp, s);
+    const bool tg = vx::launch_scan_u32(in, out, n, popcount_input, tmp.p, total64, s, a);
+    if (tagged) *tagged = tg;
+    return VX_OK;
+}
+
+// A total that has arrived in the mailbox: the tag bits masked off, refused with the caller's message at 2^32 - 1 and above.
+vx_status mail_value(const volatile unsigned long long* word, const char* limit_message, uint64_t* out)
+{
+    const unsigned long long tot = *word & kMailValue;
+    if (tot >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, limit_message);
+    *out = tot;
+    return VX_OK;
+}
+
+// A total the host waits for: a tagged one is polled for (5 ms at most), an untagged one -- or one that does not come -- waits for the stream.
+vx_status mail_total(const volatile unsigned long long* word, bool tagged, unsigned long long tag, hipStream_t s, const char* limit_message, uint64_t* out)
+{
+    if (!(tagged && mail_wait(word, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+    return mail_value(word, limit_message, out);
+}
+
+// what is left of the record kernel's and the unit scan's optional arguments (UnitPipe::setup_launch)
+struct SetupOpts {
+    const vx::DevGrid* dgrid = nullptr;   // origin and dims as K1 left them on the device: a launch queued before the host has read the bbox
+    unsigned long long tag = 0;           // of the unit total in the mailbox
+    void* clear = nullptr;                // a buffer the record kernel zeroes beside its own work ...
+    uint64_t clear_bytes = 0;             // ... and its size
+    uint64_t shard_wb = 0, shard_we = 0;  // with dgrid: the word shard whose z slab the kernel derives (0, 0: whole grid)
+    uint32_t shard_rank = 0, shard_world = 0;  // with dgrid and world > 1: the word shard vx_shard_words gives that rank
+    unsigned long long* units_total = nullptr;  // where the unit total goes instead of the mailbox (device memory)
+};
+
+// The unit pipeline of a build (grids and the octree): triangle records, high bits of the candidate ranges, units per triangle and their
+// scan, the block table, per unit its hit mask, hits per block of 64 units and their exclusive scan, and the scratch of the scans.
+struct UnitPipe {
+    DevBuf recs, ext, units, ubase, btri, umask, bhits, hbase, scantmp;
+    explicit UnitPipe(const Home* h) : recs(h), ext(h), units(h), ubase(h), btri(h), umask(h), bhits(h), hbase(h), scantmp(h) {}
+    // what the launchers read; wide: an axis above 65535 cells, the unit kernels also read the extension words
+    vx::Units view(uint32_t ntri, bool wide) const
+    {
+        vx::Units u;
+        u.recs = recs.as<vx::TriRec>();
+        u.unit_base = ubase.as<uint32_t>();
+        u.block_tri = btri.as<uint32_t>();
+        u.ntri = ntri;
+        u.ext = wide ? ext.as<uint32_t>() : nullptr;
+        return u;
+    }
+    // The front half of buildVoxelGrid that grids and the octree share: records, unit counts, unit bases.  In two parts so that
+    // the caller can queue work that does not depend on the unit count (clearing the bitmask) before the host waits for it.
+    vx_status setup_launch(const vx_mesh* m, const vx::GridParams& g, int sat, uint64_t tb, uint32_t ntri, uint32_t zlo, uint32_t zhi, Mail* mail, hipStream_t s,
+                           const SetupOpts& o = SetupOpts(), bool* tagged = nullptr);
+    // btri_entries: entries of the block table a launch queued before the host knew the total has already filled (0: none)
+    vx_status setup_finish(uint32_t ntri, Mail* mail, hipStream_t s, uint64_t* total_units, bool stream_is_drained = false, uint64_t btri_entries = 0);
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------
@@ -447,11 +511,11 @@ struct vx_grid : Home {
     uint32_t cdim[3] = {0, 0, 0}, c2dim[3] = {0, 0, 0};
     MailPtr mail;  // (ahead of the buffers: freed after them)
     DevBuf words{this}, twords{this} /*tiled build mask (launch_voxelize)*/, cwords{this}, c2words{this}, bricks{this}, idxtmp{this}, ttmp{this}, camera{this}, wprefix{this};
-    DevBuf wsel{this} /*word of every 1024th occupied voxel (prefix scan)*/, wp16{this} /*every 16th entry of wprefix, dense (prefix scan)*/, recs{this};
+    DevBuf wsel{this} /*word of every 1024th occupied voxel (prefix scan)*/, wp16{this} /*every 16th entry of wprefix, dense (prefix scan)*/;
     DevBuf lcnt{this} /*set bits per 16-word line of the bitmask (the brick kernel of a whole Vec build): wp16 is their scan*/;
     DevBuf wring{this} /*k_walk's rank epilogue: per wave the chunks of rays it drew (walk_ring_cap words each); scratch of one ray batch*/;
-    DevBuf ext{this} /*high bits of the candidate ranges*/, units{this}, ubase{this}, btri{this}, umask{this}, bhits{this} /*hits per block of 64 units*/;
-    DevBuf hbase{this} /*their exclusive scan*/, scantmp{this}, hscantmp{this} /*status block of a block-hit scan queued with the list (list_scan)*/, small{this}, vec{this}, matids{this}, mattmp{this};
+    UnitPipe up{this};  // (its scantmp serves every scan on the main stream, the queries' too)
+    DevBuf hscantmp{this} /*status block of a block-hit scan queued with the list (list_scan)*/, small{this}, vec{this}, matids{this}, mattmp{this};
     // solid voxelization (vx_solid.hip): padded mask, exterior, H in the reference's layout (padded rows only) and the word prefix over H
     DevBuf solid_m{this}, solid_e{this}, solid_h{this}, solid_pre{this}, solid_agg{this} /*the column scans' per-chunk words*/;
     // distance fields (vx_distance.hip): the envelopes' stacks, and the field itself for the host variants
@@ -523,7 +587,10 @@ struct vx_grid : Home {
     void list_scan(hipStream_t st)
     {
         if (ld.from_mask || !ld.scan_blocks) return;
-        (void)vx::launch_scan_u32(bhits.as<uint32_t>(), hbase.as<uint32_t>(), ld.scan_blocks, false, hscantmp.p, nullptr, st, true, 0, nullptr, advance_scan_gen(hscantmp, st));
+        vx::ScanArgs a;
+        a.tmp_is_zero = true;
+        a.gen = advance_scan_gen(hscantmp, st);
+        (void)vx::launch_scan_u32(up.bhits.as<uint32_t>(), up.hbase.as<uint32_t>(), ld.scan_blocks, false, hscantmp.p, nullptr, st, a);
         ld.scan_blocks = 0;
     }
     void list_emit(hipStream_t st)
@@ -533,8 +600,7 @@ struct vx_grid : Home {
             vx::launch_emit_bool_aabbs(words.as<uint32_t>(), wprefix.as<uint32_t>(), g, ld.tgt, ld.cap, st, sel_valid ? wsel.as<uint32_t>() : nullptr);
             return;
         }
-        vx::launch_emit_units(recs.as<vx::TriRec>(), ubase.as<uint32_t>(), btri.as<uint32_t>(), ld.ntri, g, umask.as<uint32_t>(), hbase.as<uint32_t>(), ld.tgt, nullptr, st,
-                              ld.cap, ld.ext ? ext.as<uint32_t>() : nullptr);
+        vx::launch_emit_units(up.view(ld.ntri, ld.ext), g, up.umask.as<uint32_t>(), up.hbase.as<uint32_t>(), ld.tgt, nullptr, st, ld.cap);
     }
     // first half, BEFORE the caller queues the work the emission is to run beside; second half after it
     hipError_t list_side_begin()
@@ -595,6 +661,24 @@ struct vx_grid : Home {
         side = nullptr;
         ev_ready = ev_list = nullptr;
         list_deferred = list_pending = false;
+    }
+    // ---- what a build (or a failed one) resets, one place per kind of state
+    void reset_materials()
+    {
+        has_materials = mat_pending = mat_gathered = false;
+        materials.clear();
+        mat_count = 0;
+        mat_interior = mat_surface = 0;
+    }
+    void reset_solid() { interior = 0; solid_rounds = 0; }
+    // what is derived from the mask: traversal structure, prefixes, counts, the list's length.  counts_known: an EMPTY grid's occupied count
+    // is known (0); a fresh grid's is whatever the build that follows leaves
+    void reset_derived(bool counts_known)
+    {
+        coarse_valid = prefix_valid = p16_valid = false;
+        occupied_known = counts_known;
+        counts_valid = true;
+        occupied = set_calls = host_set_calls = vec_count = 0;
     }
     // the stream this handle queues work on; the pool orders the reuse of released blocks by it
     void set_stream(hipStream_t st)
@@ -725,40 +809,44 @@ void fill_params(vx::GridParams& g, const float org[3], float vs, const uint64_t
 
 constexpr uint64_t kMaxVoxels = 1ull << 37;  // 16 GiB of bitmask
 
-// The shared front half of buildVoxelGrid for grids and the octree: records, unit counts, unit bases.  In two parts so that
-// the caller can queue work that does not depend on the unit count (clearing the bitmask) before the host waits for it.
-vx_status setup_launch(const vx_mesh* m, const vx::GridParams& g, int sat, uint64_t tb, uint32_t ntri, uint32_t zlo, uint32_t zhi, DevBuf& recs,
-                       DevBuf& units, DevBuf& ubase, DevBuf& scantmp, Mail* mail, hipStream_t s, DevBuf& ext, const vx::DevGrid* dgrid = nullptr,
-                       unsigned long long mail_tag = 0, bool* tagged = nullptr, void* clear = nullptr, uint64_t clear_bytes = 0,
-                       uint64_t shard_wb = 0, uint64_t shard_we = 0, uint32_t shard_rank = 0, uint32_t shard_world = 0,
-                       unsigned long long* units_total = nullptr /*where the unit total goes instead of the mailbox (device memory)*/)
+vx_status UnitPipe::setup_launch(const vx_mesh* m, const vx::GridParams& g, int sat, uint64_t tb, uint32_t ntri, uint32_t zlo, uint32_t zhi, Mail* mail, hipStream_t s,
+                                 const SetupOpts& o, bool* tagged)
 {
     VX_HIP(recs.ensure((size_t)ntri * sizeof(vx::TriRec) + 64));
     VX_HIP(ext.ensure(((size_t)ntri + 1) * 4));  // high bits of the candidate ranges (read only when an axis has more than 65535 cells)
     VX_HIP(units.ensure(((size_t)ntri + 1) * 4));
     VX_HIP(ubase.ensure(((size_t)ntri + 2) * 4));
-    VX_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(ntri), s));
-    vx::launch_tri_setup(m->dv, m->di, tb, ntri, g, sat, zlo, zhi, recs.as<vx::TriRec>(), units.as<uint32_t>(), s, dgrid, clear, clear_bytes, shard_wb, shard_we,
-                         ext.as<uint32_t>(), shard_rank, shard_world);
-    const bool tg = vx::launch_scan_u32(units.as<uint32_t>(), ubase.as<uint32_t>(), ntri, false, scantmp.p, units_total ? units_total : &mail->units, s, true, mail_tag,
-                                        nullptr, advance_scan_gen(scantmp, s));
-    if (tagged) *tagged = tg && mail_tag != 0;
+    VX_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(ntri), s));  // (ahead of the record kernel, as ever: not scan_on)
+    vx::launch_tri_setup(m->dv, m->di, tb, ntri, g, sat, zlo, zhi, recs.as<vx::TriRec>(), units.as<uint32_t>(), s, o.dgrid, o.clear, o.clear_bytes, o.shard_wb, o.shard_we,
+                         ext.as<uint32_t>(), o.shard_rank, o.shard_world);
+    vx::ScanArgs a;
+    a.tmp_is_zero = true;
+    a.total_tag = o.tag;
+    a.gen = advance_scan_gen(scantmp, s);
+    const bool tg = vx::launch_scan_u32(units.as<uint32_t>(), ubase.as<uint32_t>(), ntri, false, scantmp.p, o.units_total ? o.units_total : &mail->units, s, a);
+    if (tagged) *tagged = tg && o.tag != 0;
     return VX_OK;
 }
 
-// btri_entries: entries of the block table a launch queued before the host knew the total has already filled (0: none)
-vx_status setup_finish(uint32_t ntri, DevBuf& ubase, DevBuf& btri, Mail* mail, hipStream_t s, uint64_t* total_units, bool stream_is_drained = false,
-                       uint64_t btri_entries = 0)
+vx_status UnitPipe::setup_finish(uint32_t ntri, Mail* mail, hipStream_t s, uint64_t* total_units, bool stream_is_drained, uint64_t btri_entries)
 {
-    if (!stream_is_drained) VX_HIP(hipStreamSynchronize(s));
-    const unsigned long long tot = mail->units & kMailValue;
-    if (tot >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 candidate row segments: shard the mesh or the grid");
+    const char* limit = "more than 2^32 candidate row segments: shard the mesh or the grid";
+    uint64_t tot = 0;
+    if (stream_is_drained) VX_TRY(mail_value(&mail->units, limit, &tot));
+    else VX_TRY(mail_total(&mail->units, false, 0, s, limit, &tot));
     *total_units = tot;
     if (tot && btri_entries < tot / 64 + 2) {
         VX_HIP(btri.ensure((size_t)(tot / 64 + 2) * 4));
-        vx::launch_unit_blocks(ubase.as<uint32_t>(), ntri, (uint32_t)tot, btri.as<uint32_t>(), s);
+        vx::launch_unit_blocks(view(ntri, false), (uint32_t)tot, btri.as<uint32_t>(), s);
     }
     return VX_OK;
+}
+
+// the sequence tag of the next total the handle's kernels post to its mailbox (bits 48..63, never 0: an untagged word never matches)
+unsigned long long next_tag(vx_grid* g)
+{
+    g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
+    return (unsigned long long)g->mail_seq << 48;
 }
 
 // word_prefix + occupied count.  Split in two so that callers can queue dependent kernels before the host waits for the
@@ -769,16 +857,16 @@ vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0, b
     if (tagged) *tagged = false;
     if (g->prefix_valid) return VX_OK;
     const bool count_known = g->p16_valid && g->occupied_known;  // (the line counts' scan gave the count already: nobody has to wait for this one's)
-    if (!tag) {  // a scan outside a build: its own sequence tag
-        g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
-        tag = (unsigned long long)g->mail_seq << 48;
-    }
+    if (!tag) tag = next_tag(g);  // a scan outside a build: its own sequence tag
     VX_HIP(g->wprefix.ensure((size_t)(g->g.nwords + 2) * 4));
     VX_HIP(g->wsel.ensure((size_t)(g->g.nwords / 32 + 4) * 4));  // at most 32 nwords / 1024 chunks of 1024 records
-    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(g->g.nwords), g->stream));
     VX_HIP(g->wp16.ensure((size_t)(g->g.nwords / 16 + 4) * 4));
-    const bool tg = vx::launch_scan_u32(g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), g->g.nwords, true, g->scantmp.p, &g->mail->occupied, g->stream, true, tag,
-                                        g->wsel.as<uint32_t>(), advance_scan_gen(g->scantmp, g->stream), g->wp16.as<uint32_t>());
+    vx::ScanArgs a;
+    a.total_tag = tag;
+    a.sel1024 = g->wsel.as<uint32_t>();
+    a.group16 = g->wp16.as<uint32_t>();
+    bool tg = false;
+    VX_TRY(scan_on(g->up.scantmp, g->stream, g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), g->g.nwords, true, &g->mail->occupied, a, &tg));
     g->sel_valid = tg;  // (the three-pass scan writes neither wsel nor wp16)
     if (tagged) *tagged = tg;
     g->prefix_valid = true;
@@ -799,9 +887,9 @@ vx_status p16_launch(vx_grid* g, unsigned long long tag, bool* tagged)
 {
     const uint64_t nl = g->g.nwords / 16;
     VX_HIP(g->wp16.ensure((size_t)(nl + 4) * 4));
-    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nl), g->stream));
+    VX_HIP(ensure_scan_tmp(g->up.scantmp, vx::scan_tmp_bytes(nl), g->stream));
     const bool tg = vx::launch_mip2_scan(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->lcnt.as<uint32_t>(), g->wp16.as<uint32_t>(), nl,
-                                         g->scantmp.p, &g->mail->occupied, g->stream, tag, advance_scan_gen(g->scantmp, g->stream));
+                                         g->up.scantmp.p, &g->mail->occupied, g->stream, tag, advance_scan_gen(g->up.scantmp, g->stream));
     *tagged = tg;
     g->p16_valid = true;
     g->prefix_valid = g->sel_valid = false;  // (wprefix and wsel still describe an older mask)
@@ -820,10 +908,7 @@ vx_status rank_launch(vx_grid* g, bool* pending)
 vx_status prefix_finish(vx_grid* g, bool pending)
 {
     if (!pending || g->occupied_known) return VX_OK;
-    if (!(g->occ_tag && mail_wait(&g->mail->occupied, nullptr, g->occ_tag, 5.0))) VX_HIP(hipStreamSynchronize(g->stream));
-    const unsigned long long tot = g->mail->occupied & kMailValue;
-    if (tot >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 occupied voxels");
-    g->occupied = tot;
+    VX_TRY(mail_total(&g->mail->occupied, g->occ_tag != 0, g->occ_tag, g->stream, "more than 2^32 occupied voxels", &g->occupied));
     g->occupied_known = true;
     return VX_OK;
 }
@@ -844,13 +929,18 @@ vx_status ensure_occupied(vx_grid* g)
     return prefix_finish(g, !g->occupied_known);
 }
 
-// from_tiled: the reference's bitmask has not been written yet -- the brick kernel reads the tiled build mask (g->twords) and writes it on the way
-// line_counts (with from_tiled): it also leaves the set bits per 16-word line in g->lcnt, and their scan (p16_launch: wp16, the occupied count under
-// `tag`) is queued in one launch with the level-2 mip
-// post_hits (with from_tiled): the brick kernel posts the voxelizer's hit count to mail->hits under `tag`
-vx_status ensure_coarse(vx_grid* g, bool from_tiled = false, bool line_counts = false, unsigned long long tag = 0, bool* tagged = nullptr, bool post_hits = false)
+// What a build asks of the traversal structure beyond the lazy form (ensure_coarse):
+struct CoarseBuild {
+    bool from_tiled = false;     // the reference's bitmask has not been written yet -- the brick kernel reads the tiled build mask (g->twords) and writes it on the way
+    bool line_counts = false;    // (with from_tiled) it also leaves the set bits per 16-word line in g->lcnt, and their scan (p16_launch: wp16, the occupied
+                                 // count under `tag`) is queued in one launch with the level-2 mip
+    unsigned long long tag = 0;  // of the totals it posts
+    bool post_hits = false;      // (with from_tiled) the brick kernel posts the voxelizer's hit count to mail->hits under `tag`
+};
+// *tagged (with line_counts): whether the occupied count carries the tag
+vx_status build_coarse(vx_grid* g, const CoarseBuild& c, bool* tagged)
 {
-    if (g->coarse_valid && !from_tiled) return VX_OK;
+    if (g->coarse_valid && !c.from_tiled) return VX_OK;
     DeviceGuard dg(g->device);
     for (int a = 0; a < 3; ++a) {
         g->cdim[a] = (g->g.dim[a] + vx::kCoarse - 1) / vx::kCoarse;
@@ -863,16 +953,27 @@ vx_status ensure_coarse(vx_grid* g, bool from_tiled = false, bool line_counts = 
     VX_HIP(g->bricks.ensure((size_t)(nc * 8 * 3 + 8) * 8));  // three orientations (x, y, z slabs)
     // bitmask -> brick-major slabs in three orientations -> level-1 mip (from the z orientation) -> level-2 mip
     const bool fuse_mip1 = !(getenv("VOXHIP_FUSE_MIP1") && atoi(getenv("VOXHIP_FUSE_MIP1")) == 0);  // 0: the separate kernel, every brick stored (tests)
+    vx::BricksArgs ba;
+    if (c.from_tiled) {
+        ba.tiled = g->twords.as<uint32_t>();
+        if (c.line_counts) ba.line_cnt = g->lcnt.as<uint32_t>();
+        if (c.post_hits) {
+            ba.hit_counters = g->small.as<Small>()->set_calls;
+            ba.hits_out = &g->mail->hits;
+        }
+    }
+    ba.hits_tag = c.tag;
     const bool fused = vx::launch_build_bricks3(g->words.as<uint32_t>(), g->g.dim, g->cdim, g->bricks.as<unsigned long long>(),
-                                                fuse_mip1 ? g->cwords.as<uint32_t>() : nullptr, g->stream, from_tiled ? g->twords.as<uint32_t>() : nullptr,
-                                                from_tiled && line_counts ? g->lcnt.as<uint32_t>() : nullptr,
-                                                from_tiled && post_hits ? g->small.as<Small>()->set_calls : nullptr, from_tiled && post_hits ? &g->mail->hits : nullptr, tag);
+                                                fuse_mip1 ? g->cwords.as<uint32_t>() : nullptr, g->stream, ba);
     if (!fused) vx::launch_brick_mip1(g->bricks.as<unsigned long long>() + 2ull * nc * 8ull, nc, g->cwords.as<uint32_t>(), g->stream);
-    if (from_tiled && line_counts) VX_TRY(p16_launch(g, tag, tagged));
+    if (c.from_tiled && c.line_counts) VX_TRY(p16_launch(g, c.tag, tagged));
     else vx::launch_build_mip2(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->stream);
     g->coarse_valid = true;
     return VX_OK;
 }
+
+// the traversal structure of the grid's mask as it stands, built in front of the first query that needs it
+vx_status ensure_coarse(vx_grid* g) { return build_coarse(g, CoarseBuild(), nullptr); }
 
 vx_status sync_counts(vx_grid* g)
 {
@@ -898,9 +999,7 @@ vx_status init_grid_storage(vx_grid* g, bool clear = true)
         VX_HIP(hipMemsetAsync(g->words.p, 0, (size_t)(g->g.nwords + 2) * 4, g->stream));
         VX_HIP(hipMemsetAsync(g->small.as<Small>()->set_calls, 0, sizeof(Small::set_calls), g->stream));
     }
-    g->coarse_valid = g->prefix_valid = g->p16_valid = g->occupied_known = false;
-    g->counts_valid = true;
-    g->occupied = g->set_calls = g->host_set_calls = g->vec_count = 0;
+    g->reset_derived(/*counts_known=*/false);  // (a fresh grid: the build or the caller's writes decide what it holds)
     return VX_OK;
 }
 
@@ -933,8 +1032,7 @@ vx_status finish_materials(vx_grid* g, const long long* first_use, size_t nvalue
     VX_HIP(g->matids.ensure((size_t)g->mat_nids * 2 + 16));
     if (g->mat_nids) {
         if (vec)
-            vx::launch_mat_ids_calls(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->umask.as<uint32_t>(), g->hbase.as<uint32_t>(),
-                                     g->mat_dtv, value_index, g->matids.as<int16_t>(), s);
+            vx::launch_mat_ids_calls(g->up.view(ntri, false), g->up.umask.as<uint32_t>(), g->up.hbase.as<uint32_t>(), g->mat_dtv, value_index, g->matids.as<int16_t>(), s);
         else
             vx::launch_mat_ids(last_tri, g->mat_nids, g->mat_dtv, value_index, g->matids.as<int16_t>(), s);
     }
@@ -966,7 +1064,7 @@ vx_status solid_fill(vx_grid* g, uint64_t* n_interior, const uint32_t** h_words)
     }
     VX_HIP(g->solid_pre.ensure((size_t)(g->g.nwords + 2) * 4));
     VX_HIP(g->solid_agg.ensure((size_t)vx::solid_agg_words(dim) * 4 + 16));
-    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(g->g.nwords), s));
+    VX_HIP(ensure_scan_tmp(g->up.scantmp, vx::scan_tmp_bytes(g->g.nwords), s));
     uint32_t* flags = g->small.as<Small>()->solid_flags;
     uint32_t* words = g->words.as<uint32_t>();
     const uint32_t* m = plan.padded ? g->solid_m.as<uint32_t>() : words;
@@ -981,26 +1079,23 @@ vx_status solid_fill(vx_grid* g, uint64_t* n_interior, const uint32_t** h_words)
             vx::launch_solid_round(m, ext, g->solid_agg.as<uint32_t>(), dim, flags + prev, flags + first + r, s);
             prev = first + r;
         }
-        g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
-        const unsigned long long tag = (unsigned long long)g->mail_seq << 48;
+        const unsigned long long tag = next_tag(g);
         vx::launch_solid_report(flags + first, batch, &g->mail->solid_rounds, tag, s);
-        if (!mail_wait(&g->mail->solid_rounds, nullptr, tag, 5.0)) VX_HIP(hipStreamSynchronize(s));
-        const uint32_t changed = (uint32_t)(g->mail->solid_rounds & kMailValue);
-        rounds += changed;
+        uint64_t changed = 0;  // (at most `batch`)
+        VX_TRY(mail_total(&g->mail->solid_rounds, true, tag, s, "solid fill: round count out of range", &changed));
+        rounds += (uint32_t)changed;
         if (changed < batch) break;  // a quiet round: every round after it exited at once
         if (batch < 32) batch *= 2;
     }
     g->solid_rounds = rounds + 1;
     uint32_t* h = plan.padded ? g->solid_h.as<uint32_t>() : ext;
     vx::launch_solid_finish(words, g->solid_m.as<uint32_t>(), ext, h, dim, g->g.nwords, s);
-    g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
-    const unsigned long long tag = (unsigned long long)g->mail_seq << 48;
-    const bool tagged = vx::launch_scan_u32(h, g->solid_pre.as<uint32_t>(), g->g.nwords, true, g->scantmp.p, &g->mail->interior, s, true, tag, nullptr,
-                                            advance_scan_gen(g->scantmp, s));
-    if (!(tagged && mail_wait(&g->mail->interior, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
-    const unsigned long long n = g->mail->interior & kMailValue;
-    if (n >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 interior voxels");
-    *n_interior = n;
+    vx::ScanArgs a;  // (the scratch was sized ahead of the seed, above: not scan_on)
+    a.tmp_is_zero = true;
+    a.total_tag = next_tag(g);
+    a.gen = advance_scan_gen(g->up.scantmp, s);
+    const bool tagged = vx::launch_scan_u32(h, g->solid_pre.as<uint32_t>(), g->g.nwords, true, g->up.scantmp.p, &g->mail->interior, s, a);
+    VX_TRY(mail_total(&g->mail->interior, tagged, a.total_tag, s, "more than 2^32 interior voxels", n_interior));
     *h_words = h;
     return VX_OK;
 }
@@ -1218,21 +1313,505 @@ static void grid_set_empty(vx_grid* g, float vs)
     fill_params(g->g, zero3, vs, zdim);
     for (int a = 0; a < 3; ++a) g->bbmin[a] = g->bbmax[a] = g->bbc[a] = 0.f;
     g->triangles = 0;
-    g->coarse_valid = g->prefix_valid = g->p16_valid = false;
-    g->occupied_known = g->counts_valid = true;
-    g->occupied = g->set_calls = g->host_set_calls = 0;
-    g->vec_count = 0;
+    g->reset_derived(/*counts_known=*/true);  // (an empty grid's counts are known: 0)
     g->vec_in_bound = false;
-    g->list_deferred = false;  // (a list of the previous build that was never emitted: its records are gone with it)
-    g->has_materials = g->mat_pending = g->mat_gathered = false;
-    g->materials.clear();
-    g->mat_count = 0;
-    g->interior = 0;
-    g->solid_rounds = 0;
-    g->mat_interior = 0;
+    g->list_deferred = false;  // (here only: a list of the previous build that was never emitted -- its records are gone with it)
+    g->reset_materials();
+    g->reset_solid();
 }
 
-static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g, bool allow_early = true);
+// ---- the build: one record, named phases ("The build, phase by phase") ----------------------------------------------
+// Everything one pass of a build decides and queues, handed from phase to phase.  A phase is an ordinary function of (grid, mesh, Build&);
+// build_pass calls them in order.  The ORDER of what they queue -- kernels, memsets, waits -- is what the voxelize stage's time is made of.
+struct Build {
+    enum Next { kGoOn, kDone /*nothing (more) to voxelize: the build is complete*/, kAgain /*run the pass again without the early launch*/ };
+    Next next = kGoOn;
+    const vx_voxelize_opts* o = nullptr;
+    float vs = 0.f;
+    bool allow_early = true;
+    hipStream_t s = nullptr;
+    // plan_args: the decoded options
+    bool want_mat = false, solid = false, list_async = false, by_rank = false, sharded_words = false;
+    uint64_t tb = 0, te = 0;  // the triangle range ...
+    uint32_t ntri = 0;        // ... and its length
+    unsigned long long mtag = 0;  // sequence tag of this pass's totals in the mailbox
+    // the early launch: the voxelizer queued before the host knows the unit total, sized by the previous build's buffers
+    bool early = false;
+    uint64_t unit_cap = 0;      // the units those buffers hold
+    uint64_t btri_entries = 0;  // entries of the block table filled by the launch queued ahead of the unit total
+    bool setup_queued = false;  // records and unit scan went out in front of the extent
+    // cleared ahead of the host wait
+    size_t cleared = 0;          // bytes of the build's mask ...
+    bool cleared_tiled = false;  // ... of the tiled build mask, that is
+    bool mask_is_clear = false;  // nothing is left to clear in g->words
+    size_t mask_bytes = 0;
+    Extent ex;
+    uint64_t nvox = 0;
+    // plan_grid
+    uint64_t wb = 0, we = 0;  // the words this build owns
+    bool whole_words = false, whole_build = false, tiled = false, untile_in_bricks = false, defer_scan = false, lines = false;
+    bool wide = false;  // an axis above 65535 cells: the unit kernels also read the extension words of the candidate ranges
+    // queued and tagged
+    uint64_t U = 0, nUB = 0;  // units, blocks of 64 units
+    uint32_t* umask = nullptr;
+    uint32_t* bhits = nullptr;
+    bool hits_tagged = false, occ_tagged = false, occ_queued = false;
+    uint64_t n_interior = 0;
+    const uint32_t* h_words = nullptr;
+};
+
+// 1. plan from the arguments: pure host work
+static void build_plan_args(vx_grid* g, const vx_mesh* mesh, Build& b)
+{
+    const vx_voxelize_opts& o = *b.o;
+    b.want_mat = (o.flags & VX_VOXELIZE_MATERIALS) != 0;
+    b.solid = (o.flags & VX_VOXELIZE_SOLID) != 0;
+    // (the material ids need the hit bases on the main stream; a solid build appends the interior's records behind the triangles')
+    b.list_async = (o.flags & VX_VOXELIZE_LIST_ASYNC) != 0 && g->kind == VX_GRID_VEC && !b.want_mat && !b.solid;
+    g->reset_solid();
+    g->reset_materials();
+    b.by_rank = o.shard_world > 1 && !(o.word_begin || o.word_end);
+    b.tb = 0;
+    b.te = mesh->nt;
+    if (o.tri_begin || o.tri_end) {
+        b.tb = o.tri_begin;
+        b.te = o.tri_end;
+    }
+    b.ntri = (uint32_t)(b.te - b.tb);
+    b.sharded_words = o.word_begin || o.word_end || b.by_rank;
+    b.mtag = next_tag(g);
+    // A VX_VOXELIZE_LIST_ASYNC rebuild (nothing queued inside the build but the voxelizer reads a buffer sized by the unit total U): the host
+    // waits for the BBOX only -- k_bbox posts a tag of its own -- and queues the voxelizer and everything behind it while the record kernel
+    // and the unit scan still run, instead of leaving the GPU idle for a mailbox round trip plus a launch (8-12 us) behind the scan.  The
+    // voxelizer finds U in device memory (the scan's total goes there, and on to the mailbox with k_unit_blocks) and does nothing when U
+    // exceeds what the handle's buffers from the previous build hold; the host reads U in the wait for the hit count and only then, or with
+    // 2^32 units or more, goes the way of a first build: U first, buffers, the same kernels again.
+    const UnitPipe& up = g->up;
+    b.early = b.allow_early && b.ntri > 0 && !b.sharded_words && b.list_async && up.umask.cap >= 64 && up.bhits.cap >= 64 && up.hbase.cap >= 64 && up.btri.cap >= 64;
+}
+
+// 2a. front, the queue: bbox, triangle records and unit scan, the block table ahead of the total, the early clear
+// Unsharded build: K1 leaves origin + dims in device memory, so the triangle records and the unit scan are queued right
+// behind it and the host waits ONCE for the bbox and the unit count (every host round trip costs ~20 us of idle GPU: the
+// wake-up plus the launch latency of an empty queue).  The bitmask of the previous build is cleared in the same window.
+// (a word shard's z slab is derived from the device-side dims by the record kernel itself)
+static vx_status build_front_queue(vx_grid* g, vx_mesh* mesh, Build& b, bool* units_tagged)
+{
+    const vx_voxelize_opts& o = *b.o;
+    Small* ds = g->small.as<Small>();
+    UnitPipe& up = g->up;
+    vx::GridParams gp{};
+    const float zero3[3] = {0.f, 0.f, 0.f};
+    const uint64_t zdim[3] = {0, 0, 0};
+    fill_params(gp, zero3, b.vs, zdim);
+    vx::launch_bbox(mesh->dv, mesh->nv, ds->bbox_state, g->mail->bbox, ds->set_calls, b.s, b.vs, &ds->dgrid, b.early ? &g->mail->bbox_tag : nullptr, b.mtag);
+    // the previous build's bitmask is cleared in the same window -- by the record kernel's own threads when there are enough of
+    // them (at most 256 bytes each), by a memset behind the block table otherwise
+    // (a handle whose previous build went through the tiled build mask is expected to do so again: that is the buffer to clear)
+    DevBuf& cb = (g->last_tiled && g->twords.p) ? g->twords : g->words;
+    b.cleared_tiled = &cb == &g->twords;
+    const bool clear_in_setup = cb.p && (cb.cap % 16) == 0 && cb.cap / 256 <= (size_t)b.ntri;
+    SetupOpts so;
+    so.dgrid = &ds->dgrid;
+    so.tag = b.mtag;
+    if (clear_in_setup) {
+        so.clear = cb.p;
+        so.clear_bytes = cb.cap;
+    }
+    if (b.sharded_words) {
+        so.shard_wb = o.word_begin;
+        so.shard_we = o.word_end;
+    }
+    if (b.by_rank) {
+        so.shard_rank = (uint32_t)o.shard_rank;
+        so.shard_world = (uint32_t)o.shard_world;
+    }
+    if (b.early) so.units_total = &ds->units64;
+    VX_TRY(up.setup_launch(mesh, gp, o.sat_variant, b.tb, b.ntri, 0, 0, g->mail.get(), b.s, so, units_tagged));
+    if (clear_in_setup) b.cleared = cb.cap;
+    // the block table of the units: queued now, for as many blocks as the handle's table from the previous build holds, so that
+    // it runs while the host waits for the unit total (redone by setup_finish should the table turn out too small)
+    if (up.btri.p && up.btri.cap >= 64) {
+        b.btri_entries = up.btri.cap / 4;
+        if (b.btri_entries > 0x3FFFFFFull) b.btri_entries = 0x3FFFFFFull;
+        vx::UnitBlockArgs ua;
+        ua.cap_blocks = (uint32_t)b.btri_entries;
+        if (b.early) {
+            // the units the buffers of the previous build hold; the hit scan runs over the blocks of that many units, so the entries
+            // behind this build's last block are zeroed on the way
+            b.unit_cap = std::min(std::min((uint64_t)up.umask.cap / 4 - 1, ((uint64_t)up.bhits.cap / 4 - 4) * 64),
+                                  std::min(((uint64_t)up.hbase.cap / 4 - 4) * 64, (b.btri_entries - 2) * 64));
+            ua.fwd_src = &ds->units64;
+            ua.fwd_dst = &g->mail->units;
+            ua.zero_hits = up.bhits.as<uint32_t>();
+        }
+        ua.zero_n = (uint32_t)((b.unit_cap + 63) / 64);
+        vx::launch_unit_blocks(up.view(b.ntri, false), (uint32_t)((b.btri_entries - 2) * 64), up.btri.as<uint32_t>(), b.s, ua);
+    }
+    if (cb.p && !clear_in_setup) {
+        VX_HIP(hipMemsetAsync(cb.p, 0, cb.cap, b.s));
+        b.cleared = cb.cap;
+    }
+    return VX_OK;
+}
+
+// 2. front: what goes out ahead of the extent, the build's single host wait, the extent, the grid's storage
+static vx_status build_front(vx_grid* g, vx_mesh* mesh, Build& b)
+{
+    if (b.ntri > 0) {
+        bool units_tagged = false;
+        VX_TRY(build_front_queue(g, mesh, b, &units_tagged));
+        if (b.early && units_tagged) {
+            if (!mail_wait(&g->mail->bbox_tag, nullptr, b.mtag, 5.0)) VX_HIP(hipStreamSynchronize(b.s));
+            std::atomic_thread_fence(std::memory_order_acquire);
+        } else {
+            // the bbox (written by k_bbox, two kernels earlier) and the unit total: polled from the mailbox, see the hit count below
+            // (an untagged total on its way through device memory: the drained stream has forwarded it)
+            if (!(units_tagged && !b.early && mail_wait(&g->mail->units, nullptr, b.mtag, 5.0))) VX_HIP(hipStreamSynchronize(b.s));
+            b.early = false;
+        }
+        VX_TRY(extent_from_bbox(g->mail->bbox, mesh->nv, b.vs, &b.ex));
+        b.setup_queued = true;
+    } else {
+        b.early = false;
+        VX_TRY(compute_extent(mesh, b.vs, g->small.as<Small>(), g->mail.get(), b.s, &b.ex));  // also clears the per-build call counter
+    }
+    b.nvox = b.ex.dim[0] * b.ex.dim[1] * b.ex.dim[2];
+    if (b.nvox > kMaxVoxels) return fail(VX_ERR_CAPACITY, "grid exceeds 2^37 voxels");
+    fill_params(g->g, b.ex.mn, b.vs, b.ex.dim);
+    for (int a = 0; a < 3; ++a) { g->bbmin[a] = b.ex.mn[a]; g->bbmax[a] = b.ex.mx[a]; g->bbc[a] = b.ex.ctr[a]; }
+    VX_TRY(init_grid_storage(g, /*clear=*/false));
+    b.mask_bytes = (size_t)(g->g.nwords + 2) * 4;
+    if (g->words.fresh) { if (!b.cleared_tiled) b.cleared = 0; g->words.fresh = false; }  // a new block: the early clear hit the old one
+    b.mask_is_clear = !b.cleared_tiled && b.cleared >= b.mask_bytes;
+    return VX_OK;
+}
+
+// 3. plan from the grid: pure host work -- the words this build owns and the form its mask takes
+static vx_status build_plan_grid(vx_grid* g, const vx_mesh* mesh, Build& b)
+{
+    const vx_voxelize_opts& o = *b.o;
+    b.wb = 0;
+    b.we = g->g.nwords;
+    if (b.by_rank) {
+        vx_shard_words(g->g.nwords, o.shard_rank, o.shard_world, &b.wb, &b.we, nullptr);
+    } else if (b.sharded_words) {
+        if (o.word_end > g->g.nwords) return fail(VX_ERR_INVALID_ARG, "word shard out of range");
+        b.wb = o.word_begin;
+        b.we = o.word_end;
+    }
+    b.whole_build = b.wb == 0 && b.we == g->g.nwords && b.tb == 0 && b.te == mesh->nt;
+    g->triangles = b.te - b.tb;
+    // Unsharded words, rows of whole words: the voxelizer ORs into the tiled build mask (one atomic request per 4 x 4 rows instead of one per
+    // row, launch_voxelize) and launch_untile writes every word of the reference's bitmask from it.  Ragged rows take the direct form.
+    b.whole_words = b.wb == 0 && b.we == g->g.nwords;
+    // (a word shard goes the same way: the voxelizer keeps to the rows whose words it owns, launch_untile writes those and zeroes the rest --
+    // a second pass over the WHOLE mask per rank, so only where the mask is small against the mesh: the size rule of the clear that rides in
+    // the record kernel's threads.  atrium262k, two logical ranks on one GPU: 512^3 voxelize stage 121 -> 95 us; 1024^3 392 -> 426, hence the rule)
+    // ... and only for shards of a fifth of the mask or more: shard 0 of 2 / 4 / 8 at 512^3 (tools/shard_time.py, kernels of a rebuild)
+    // 119.7 -> 97.9 / 90.6 -> 73.3 / 55.1 -> 64.0 us -- at an eighth the un-tiling pass costs what the voxelizer no longer has to gain
+    const bool shard_small = (size_t)vx::tiled_mask_words(g->g.dim) * 4 / 256 <= (size_t)b.ntri && (b.we - b.wb) * 5 >= g->g.nwords;
+    b.tiled = (b.whole_words || shard_small) && (b.ex.dim[0] % 32) == 0;
+    // (the tiled mask -> the reference's bitmask: by the brick kernel on its way when the traversal structure is built right away)
+    // (VX_VOXELIZE_SOLID: the fill reads and extends the reference's bitmask, the traversal structure is built from the final one)
+    b.untile_in_bricks = b.tiled && b.whole_words && !b.solid;
+    // A list_async rebuild whose brick kernel follows at once: nothing queued in the build reads the hit bases -- the block-hit scan stood
+    // there for its total, the list's length -- so the brick kernel posts that total from the voxelizer's own counters and the scan goes in
+    // front of the emission (list_scan).  Everything else keeps the scan in the build.
+    b.defer_scan = b.early && b.untile_in_bricks;
+    // (a Vec build's consumers -- the ray batch's rank pass -- read wp16 only: from the brick kernel's line counts where a line lies in
+    // one row, i.e. X % 512 == 0, which makes nwords a multiple of 16 as the rank pass's 16-word path needs it.  The Bool flavours emit
+    // their list from the word prefix right away, materials index it: the word-prefix scan)
+    b.lines = b.untile_in_bricks && g->kind == VX_GRID_VEC && !b.want_mat && (b.ex.dim[0] % 512) == 0;
+    b.wide = b.ex.dim[0] > 65535 || b.ex.dim[1] > 65535 || b.ex.dim[2] > 65535;
+    return VX_OK;
+}
+
+// a build without a setVoxel call: no material is ever used
+static vx_status build_no_calls(vx_grid* g, const vx_mesh* mesh, Build& b)
+{
+    b.next = Build::kDone;
+    if (!b.want_mat) return VX_OK;
+    g->mat_pending = true;
+    g->mat_values = mesh->values;
+    g->mat_first_use.assign(mesh->values.size(), -1);
+    g->mat_dtv = nullptr; g->mat_ntri = 0; g->mat_nids = 0;
+    VX_HIP(g->mattmp.ensure(mesh->values.size() * 2 + 256));
+    if (b.whole_build) return finish_materials(g, g->mat_first_use.data(), g->mat_first_use.size());
+    return VX_OK;
+}
+
+// 4. masks and unit total: what is left to clear, and U the early way, from the setup queued in the front, or behind a word shard's own setup
+static vx_status build_masks_units(vx_grid* g, vx_mesh* mesh, Build& b)
+{
+    const vx_voxelize_opts& o = *b.o;
+    hipStream_t s = b.s;
+    if (b.ntri == 0 || b.nvox == 0 || b.wb == b.we) {
+        if (!b.mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, b.mask_bytes, s));
+        return build_no_calls(g, mesh, b);
+    }
+    g->last_tiled = b.tiled;
+    if (b.tiled) {
+        const size_t tbytes = (size_t)vx::tiled_mask_words(g->g.dim) * 4;
+        VX_HIP(g->twords.ensure(tbytes));
+        const bool tw_clear = b.cleared_tiled && b.cleared >= tbytes && !g->twords.fresh;
+        g->twords.fresh = false;
+        if (!tw_clear) VX_HIP(hipMemsetAsync(g->twords.p, 0, tbytes, s));
+        b.mask_is_clear = true;  // every word of the mask and the two spare words behind it are written by launch_untile (or the brick kernel) --
+                                 // or, when there is no unit to run, by the memset below
+    }
+    if (b.early) {
+        if (!b.mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, b.mask_bytes, s));
+        b.U = b.unit_cap;  // (what the buffers below are sized for: they are the previous build's)
+    } else if (b.setup_queued) {
+        if (!b.mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, b.mask_bytes, s));
+        VX_TRY(g->up.setup_finish(b.ntri, g->mail.get(), s, &b.U, /*stream_is_drained=*/true, b.btri_entries));
+    } else {
+        // z slab that contains the voxels of words [wb, we)
+        const uint64_t XY = b.ex.dim[0] * b.ex.dim[1];
+        const uint32_t zlo = (uint32_t)((b.wb * 32) / XY);
+        uint64_t zh = (b.we * 32 + XY - 1) / XY;
+        if (zh > b.ex.dim[2]) zh = b.ex.dim[2];
+        // records + unit scan are queued, THEN the bitmask is cleared (it does not depend on the unit count), then the host waits
+        VX_TRY(g->up.setup_launch(mesh, g->g, o.sat_variant, b.tb, b.ntri, zlo, (uint32_t)zh, g->mail.get(), s));
+        VX_HIP(hipMemsetAsync(g->words.p, 0, b.mask_bytes, s));
+        VX_TRY(g->up.setup_finish(b.ntri, g->mail.get(), s, &b.U));
+    }
+    if (b.U == 0) {  // (e.g. a word shard whose z slab holds no triangle): nothing will write the mask
+        if (b.tiled) VX_HIP(hipMemsetAsync(g->words.p, 0, b.mask_bytes, s));
+        return build_no_calls(g, mesh, b);
+    }
+    return VX_OK;
+}
+
+// 5. the voxelizer, the un-tiling pass where the brick kernel does not do it, the block-hit scan or its deferral, the solid fill
+static vx_status build_voxelize(vx_grid* g, vx_mesh*, Build& b)
+{
+    hipStream_t s = b.s;
+    UnitPipe& up = g->up;
+    Small* ds = g->small.as<Small>();
+    if (g->kind == VX_GRID_VEC || b.want_mat) {
+        VX_HIP(up.umask.ensure((size_t)(b.U + 1) * 4));
+        b.umask = up.umask.as<uint32_t>();
+    }
+    // VoxelGridVec::setVoxel appends one Aabb per call (voxelgridVecEncoding.cpp:19-39): ordered emission, at the exclusive scan of the
+    // hit counts -- two-level: the voxelizer leaves the hits of every block of 64 units, the device scan runs over those
+    b.nUB = (b.U + 63) / 64;
+    if (g->kind == VX_GRID_VEC) {
+        VX_HIP(up.bhits.ensure((size_t)(b.nUB + 4) * 4));
+        VX_HIP(up.hbase.ensure((size_t)(b.nUB + 4) * 4));
+        b.bhits = up.bhits.as<uint32_t>();
+    }
+    vx::VoxelizeArgs va;
+    va.block_hits = b.bhits;
+    va.tiled = b.tiled;
+    va.units_total = b.early ? &ds->units64 : nullptr;
+    va.unit_cap = (uint32_t)b.unit_cap;
+    vx::launch_voxelize(up.view(b.ntri, b.wide), g->g, b.o->sat_variant, b.tiled ? g->twords.as<uint32_t>() : g->words.as<uint32_t>(), b.wb, b.we, b.umask, ds->set_calls, s, va);
+    if (b.tiled && !b.untile_in_bricks) vx::launch_untile(g->twords.as<uint32_t>(), g->words.as<uint32_t>(), g->g.dim, s, b.wb, b.we);
+    g->counts_valid = false;
+    if (b.defer_scan) {
+        VX_HIP(ensure_scan_tmp(g->hscantmp, vx::scan_tmp_bytes(b.nUB), s));  // (the scan itself: list_scan)
+        b.hits_tagged = true;
+    } else if (g->kind == VX_GRID_VEC) {
+        vx::ScanArgs a;
+        a.total_tag = b.mtag;
+        VX_TRY(scan_on(up.scantmp, s, b.bhits, up.hbase.as<uint32_t>(), b.nUB, false, &g->mail->hits, a, &b.hits_tagged));
+    }
+    // VX_VOXELIZE_SOLID: the second loop -- setVoxel on every interior cell in ascending order -- once the surface mask is complete
+    if (b.solid) {
+        VX_TRY(solid_fill(g, &b.n_interior, &b.h_words));
+        g->interior = b.n_interior;
+        g->host_set_calls += b.n_interior;
+    }
+    return VX_OK;
+}
+
+// 6. A complete (unsharded) bitmask: queue what every consumer of the grid needs next -- the traversal structure (bricks,
+// bounds, mips = the reference's acceleration-structure build, hello_vulkan.cpp:700-703) and the word prefix (getAabbs /
+// primitive ids), or the line counts' scan in its place -- behind the voxelizer instead of lazily in front of the first query.  For the
+// Vec flavour this work runs while the host waits for the hit count.  A word shard's stay lazy (ensure_coarse / ensure_prefix in the
+// query paths).
+static vx_status build_structure(vx_grid* g, vx_mesh*, Build& b)
+{
+    if (!b.whole_words) return VX_OK;
+    if (b.lines) VX_HIP(g->lcnt.ensure((size_t)(g->g.nwords / 16 + 4) * 4));
+    CoarseBuild c;
+    c.from_tiled = b.untile_in_bricks;
+    c.line_counts = b.lines;
+    c.tag = b.mtag;
+    c.post_hits = b.defer_scan;
+    VX_TRY(build_coarse(g, c, &b.occ_tagged));
+    if (b.lines) {
+        b.occ_queued = true;
+    } else {
+        bool pending = false;
+        b.occ_queued = !g->prefix_valid;
+        VX_TRY(prefix_launch(g, &pending, b.mtag, &b.occ_tagged));
+    }
+    return VX_OK;
+}
+
+// 7a. The host needs the hit count (and takes the occupied count along).  Both are written by scans -- the hit count of a build that
+// left its block-hit scan to the list (defer_scan) by the brick kernel, from the voxelizer's counters -- that run BEFORE the
+// emission: the host polls the tagged mailbox words and goes on queueing work (the caller's next call: a trace) while
+// the emission still runs; a stream synchronize would wake it ~15 us after the last kernel.  An untagged total
+// (three-pass scan) or 5 ms without an answer: the synchronize.
+// VX_VOXELIZE_LIST_ASYNC: only the hit count -- its scan runs in front of the traversal structure and the word prefix, so the host
+// is back in the caller ~40 us of GPU work before the build ends and the caller's ray batch is queued in time; the occupied count
+// (the LAST kernel's total) is fetched when somebody asks for it (prefix_finish).
+// *units_known: the true unit total.  An early launch whose buffers it outgrew: they grow, and next = kAgain.
+static vx_status build_list_wait(vx_grid* g, Build& b, uint64_t* hits, uint64_t* units_known)
+{
+    hipStream_t s = b.s;
+    const bool occ_in_flight = (g->prefix_valid || g->p16_valid) && !g->occupied_known;
+    const bool occ_along = occ_in_flight && !(b.list_async && b.occ_queued && b.occ_tagged);
+    bool got = false;
+    if (b.hits_tagged && (!occ_along || (b.occ_queued && b.occ_tagged)))
+        got = mail_wait(&g->mail->hits, occ_along ? &g->mail->occupied : nullptr, b.mtag, 5.0);
+    if (!got) VX_HIP(hipStreamSynchronize(s));
+    *units_known = b.U;
+    if (b.early) {
+        // the unit total, in the mailbox since k_unit_blocks: checked as setup_finish checks it.  More units than the early launch's
+        // buffers hold: the voxelizer did nothing -- the buffers grow and the build runs again the way of a first build
+        if ((g->mail->units & ~kMailValue) != b.mtag) VX_HIP(hipStreamSynchronize(s));
+        uint64_t tot = 0;
+        VX_TRY(mail_value(&g->mail->units, "more than 2^32 candidate row segments: shard the mesh or the grid", &tot));
+        if (tot > b.unit_cap) {
+            VX_HIP(hipStreamSynchronize(s));  // (the kernels of this pass read the blocks that are about to be replaced)
+            VX_HIP(g->up.umask.ensure((size_t)(tot + 1) * 4));
+            VX_HIP(g->up.bhits.ensure((size_t)(tot / 64 + 5) * 4));
+            VX_HIP(g->up.hbase.ensure((size_t)(tot / 64 + 5) * 4));
+            VX_HIP(g->up.btri.ensure((size_t)(tot / 64 + 2) * 4));
+            b.next = Build::kAgain;
+            return VX_OK;
+        }
+        *units_known = tot;
+    }
+    VX_TRY(mail_value(&g->mail->hits, "more than 2^32 voxel hits", hits));
+    if ((g->prefix_valid || g->p16_valid) && (occ_along || !got)) {  // the same wait covered the occupied count
+        VX_TRY(mail_value(&g->mail->occupied, "more than 2^32 occupied voxels", &g->occupied));
+        g->occupied_known = true;
+    }
+    return VX_OK;
+}
+
+// 7. the Vec list: emitted into the handle's existing buffer before the host knows the hit count (writes beyond the buffer's
+// capacity are dropped by the kernel); only a list that outgrew it is emitted again after the wait -- or, VX_VOXELIZE_LIST_ASYNC, recorded
+// for whoever queues it (g->ld)
+static vx_status build_list(vx_grid* g, vx_mesh*, Build& b)
+{
+    hipStream_t s = b.s;
+    UnitPipe& up = g->up;
+    const vx::Units units = up.view(b.ntri, b.wide);
+    const bool to_bound = g->bound != nullptr && g->bound_cap > 0;
+    vx_aabb* tgt = to_bound ? g->bound : g->vec.as<vx_aabb>();
+    const uint64_t cap_rec = to_bound ? g->bound_cap + 1 : (g->vec.p ? g->vec.cap / sizeof(vx_aabb) : 0);
+    g->vec_in_bound = false;
+    if (cap_rec && !b.list_async) vx::launch_emit_units(units, g->g, b.umask, up.hbase.as<uint32_t>(), tgt, nullptr, s, to_bound ? g->bound_cap : cap_rec);
+    uint64_t hits = 0, units_known = 0;
+    VX_TRY(build_list_wait(g, b, &hits, &units_known));
+    if (b.next == Build::kAgain) return VX_OK;
+    const uint64_t total = hits + b.n_interior;  // (a solid build: the interior's records follow the triangles')
+    if (total >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 voxel records");
+    if (total + 1 <= cap_rec) g->vec_in_bound = to_bound;
+    if (total + 1 > cap_rec) VX_HIP(g->vec.ensure((size_t)(total + 1) * sizeof(vx_aabb)));
+    if (b.list_async) {
+        // VX_VOXELIZE_LIST_ASYNC: the count is known, the records are written later -- beside the next ray batch (trace_common), or
+        // on this stream by whatever asks for them first (list_resolve)
+        g->ld.from_mask = false;
+        g->ld.ntri = b.ntri;
+        g->ld.ext = b.wide;
+        g->ld.tgt = g->vec_ptr();
+        g->ld.cap = g->vec_in_bound ? g->bound_cap : ~0ull;
+        g->list_deferred = hits != 0;
+        g->ld.scan_blocks = b.defer_scan && hits ? (units_known + 63) / 64 : 0;  // (the true unit total: the build's own blocks, not the buffers')
+    } else if (total + 1 > cap_rec) {
+        vx::launch_emit_units(units, g->g, b.umask, up.hbase.as<uint32_t>(), g->vec.as<vx_aabb>(), nullptr, s);
+    }
+    if (b.n_interior)  // cell_aabb of every interior cell in ascending order, at offset `hits`
+        vx::launch_emit_bool_aabbs(b.h_words, g->solid_pre.as<uint32_t>(), g->g, g->vec_ptr() + hits, b.n_interior, s);
+    g->vec_count = total;
+    g->mat_surface = hits;
+    return VX_OK;
+}
+
+// 8. per-voxel material ids (see k_mat_last): needs the word prefix (queued above for an unsharded build) and, for the Vec
+// flavour, the hit bases.  First half here: the last triangle per voxel of this shard and, per material value, the first
+// triangle of this shard that uses it; second half (finish_materials) once the first uses of ALL shards are known -- at once
+// for a whole build.
+static vx_status build_materials(vx_grid* g, vx_mesh* mesh, Build& b)
+{
+    hipStream_t s = b.s;
+    const uint32_t ntri = b.ntri;
+    bool pending = false;
+    VX_TRY(prefix_launch(g, &pending));
+    VX_TRY(prefix_finish(g, pending));
+    const uint64_t nids = g->kind == VX_GRID_VEC ? g->vec_count : g->occupied;
+    const size_t tmp_bytes = (g->kind == VX_GRID_VEC ? 0 : (size_t)nids * 4) + (size_t)ntri + 64 + mesh->values.size() * 2 + 64;
+    VX_HIP(g->mattmp.ensure(tmp_bytes));
+    uint8_t* base = g->mattmp.as<uint8_t>();
+    uint32_t* last_tri = g->kind == VX_GRID_VEC ? nullptr : reinterpret_cast<uint32_t*>(base);
+    uint8_t* tri_hit = base + (g->kind == VX_GRID_VEC ? 0 : (size_t)nids * 4);
+    VX_HIP(hipMemsetAsync(base, 0, (size_t)(tri_hit - base) + ntri, s));
+    vx::launch_mat_last(g->up.view(ntri, b.wide), g->g, b.umask, g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), last_tri, tri_hit, s);
+    std::vector<uint8_t> hit(ntri);
+    VX_HIP(hipMemcpyAsync(hit.data(), tri_hit, ntri, hipMemcpyDeviceToHost, s));
+    VX_HIP(hipStreamSynchronize(s));
+    g->mat_values = mesh->values;
+    g->mat_first_use.assign(mesh->values.size(), -1);
+    const int32_t* tv = mesh->tri_value.data() + b.tb;
+    for (uint32_t t = 0; t < ntri; ++t)
+        if (hit[t] && g->mat_first_use[(size_t)tv[t]] < 0) g->mat_first_use[(size_t)tv[t]] = (long long)(b.tb + t);
+    // the interior's calls come after every triangle's and carry MaterialObj{} (value 0): addMatrialIfNeeded appends it if no triangle used it
+    g->mat_interior = b.n_interior;
+    if (b.n_interior && g->mat_first_use[0] < 0) g->mat_first_use[0] = (long long)(b.tb + ntri);
+    g->mat_dtv = mesh->btv.as<int32_t>() + b.tb;
+    g->mat_ntri = ntri;
+    g->mat_nids = nids;
+    g->mat_pending = true;
+    if (b.whole_build) VX_TRY(finish_materials(g, g->mat_first_use.data(), g->mat_first_use.size()));
+    return VX_OK;
+}
+
+// one pass over the phases
+static vx_status build_pass(vx_grid* g, vx_mesh* mesh, Build& b)
+{
+    g->set_stream((hipStream_t)b.o->stream);
+    b.s = g->stream;
+    // a list emission of the previous build that is still to come reads the unit masks, hit bases and records this build overwrites (one
+    // that was never queued is dropped: its list is about to be replaced)
+    VX_HIP(g->list_resolve(/*drop_unqueued=*/true));
+    VX_HIP(ensure_small(g->small));
+    if (!g->mail) VX_HIP(mail_alloc(g->mail));
+    build_plan_args(g, mesh, b);
+    VX_TRY(build_front(g, mesh, b));
+    VX_TRY(build_plan_grid(g, mesh, b));
+    VX_TRY(build_masks_units(g, mesh, b));
+    if (b.next == Build::kDone) return VX_OK;
+    VX_TRY(build_voxelize(g, mesh, b));
+    VX_TRY(build_structure(g, mesh, b));
+    if (g->kind == VX_GRID_VEC) {
+        VX_TRY(build_list(g, mesh, b));
+        if (b.next == Build::kAgain) return VX_OK;
+    }
+    if (b.want_mat) VX_TRY(build_materials(g, mesh, b));
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+// At most two passes: a list-async rebuild that outgrew the buffers its early launch was sized by runs again with the total known.
+static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g)
+{
+    for (int pass = 0;; ++pass) {
+        Build b;
+        b.o = &o;
+        b.vs = vs;
+        b.allow_early = pass == 0;
+        VX_TRY(build_pass(g, mesh, b));
+        if (b.next != Build::kAgain) return VX_OK;
+    }
+}
 
 vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_opts* opts, vx_grid* g)
 {
@@ -1258,358 +1837,6 @@ vx_status vx_voxelize_into(const vx_mesh* mesh_c, float vs, const vx_voxelize_op
     const vx_status st = voxelize_build(mesh, vs, o, g);
     if (st != VX_OK) grid_set_empty(g, vs);
     return st;
-}
-
-static vx_status voxelize_build(vx_mesh* mesh, float vs, const vx_voxelize_opts& o, vx_grid* g, bool allow_early)
-{
-    g->set_stream((hipStream_t)o.stream);
-    hipStream_t s = g->stream;
-    // a list emission of the previous build that is still to come reads the unit masks, hit bases and records this build overwrites (one
-    // that was never queued is dropped: its list is about to be replaced)
-    VX_HIP(g->list_resolve(/*drop_unqueued=*/true));
-    const bool want_mat = (o.flags & VX_VOXELIZE_MATERIALS) != 0;
-    const bool solid = (o.flags & VX_VOXELIZE_SOLID) != 0;
-    // (the material ids need the hit bases on the main stream; a solid build appends the interior's records behind the triangles')
-    const bool list_async = (o.flags & VX_VOXELIZE_LIST_ASYNC) != 0 && g->kind == VX_GRID_VEC && !want_mat && !solid;
-    g->interior = 0;
-    g->solid_rounds = 0;
-    g->mat_interior = g->mat_surface = 0;
-    g->has_materials = false;
-    g->mat_pending = false;
-    g->mat_gathered = false;
-    g->materials.clear();
-    g->mat_count = 0;
-    const bool by_rank = o.shard_world > 1 && !(o.word_begin || o.word_end);
-
-    VX_HIP(ensure_small(g->small));
-    if (!g->mail) VX_HIP(mail_alloc(g->mail));
-    Small* ds = g->small.as<Small>();
-    uint64_t tb = 0, te = mesh->nt;
-    if (o.tri_begin || o.tri_end) {
-        tb = o.tri_begin;
-        te = o.tri_end;
-    }
-    const uint32_t ntri = (uint32_t)(te - tb);
-    const bool sharded_words = o.word_begin || o.word_end || by_rank;
-
-    // Unsharded build: K1 leaves origin + dims in device memory, so the triangle records and the unit scan are queued right
-    // behind it and the host waits ONCE for the bbox and the unit count (every host round trip costs ~20 us of idle GPU: the
-    // wake-up plus the launch latency of an empty queue).  The bitmask of the previous build is cleared in the same window.
-    // sequence tag of this build's totals in the mailbox (never 0: an untagged word never matches)
-    g->mail_seq = (g->mail_seq % 0xFFFFu) + 1u;
-    const unsigned long long mtag = (unsigned long long)g->mail_seq << 48;
-    // A VX_VOXELIZE_LIST_ASYNC rebuild (nothing queued inside the build but the voxelizer reads a buffer sized by the unit total U): the host
-    // waits for the BBOX only -- k_bbox posts a tag of its own -- and queues the voxelizer and everything behind it while the record kernel
-    // and the unit scan still run, instead of leaving the GPU idle for a mailbox round trip plus a launch (8-12 us) behind the scan.  The
-    // voxelizer finds U in device memory (the scan's total goes there, and on to the mailbox with k_unit_blocks) and does nothing when U
-    // exceeds what the handle's buffers from the previous build hold; the host reads U in the wait for the hit count and only then, or with
-    // 2^32 units or more, goes the way of a first build: U first, buffers, the same kernels again.
-    bool early = allow_early && ntri > 0 && !sharded_words && list_async && g->umask.cap >= 64 && g->bhits.cap >= 64 && g->hbase.cap >= 64 && g->btri.cap >= 64;
-    uint64_t unit_cap = 0;
-    Extent ex;
-    uint64_t btri_entries = 0;  // entries of the block table filled by the launch queued ahead of the unit total
-    bool setup_queued = false;
-    size_t cleared = 0;         // bytes of the build's mask cleared ahead of the host wait ...
-    bool cleared_tiled = false;  // ... of the tiled build mask, that is
-    if (ntri > 0) {  // (a word shard's z slab is derived from the device-side dims by the record kernel itself)
-        vx::GridParams gp{};
-        const float zero3[3] = {0.f, 0.f, 0.f};
-        const uint64_t zdim[3] = {0, 0, 0};
-        fill_params(gp, zero3, vs, zdim);
-        vx::launch_bbox(mesh->dv, mesh->nv, ds->bbox_state, g->mail->bbox, ds->set_calls, s, vs, &ds->dgrid, early ? &g->mail->bbox_tag : nullptr, mtag);
-        bool units_tagged = false;
-        // the previous build's bitmask is cleared in the same window -- by the record kernel's own threads when there are enough of
-        // them (at most 256 bytes each), by a memset behind the block table otherwise
-        // (a handle whose previous build went through the tiled build mask is expected to do so again: that is the buffer to clear)
-        DevBuf& cb = (g->last_tiled && g->twords.p) ? g->twords : g->words;
-        cleared_tiled = &cb == &g->twords;
-        const bool clear_in_setup = cb.p && (cb.cap % 16) == 0 && cb.cap / 256 <= (size_t)ntri;
-        VX_TRY(setup_launch(mesh, gp, o.sat_variant, tb, ntri, 0, 0, g->recs, g->units, g->ubase, g->scantmp, g->mail.get(), s, g->ext, &ds->dgrid, mtag, &units_tagged,
-                            clear_in_setup ? cb.p : nullptr, clear_in_setup ? cb.cap : 0, sharded_words ? o.word_begin : 0,
-                            sharded_words ? o.word_end : 0, by_rank ? (uint32_t)o.shard_rank : 0u, by_rank ? (uint32_t)o.shard_world : 0u,
-                            early ? &ds->units64 : nullptr));
-        if (clear_in_setup) cleared = cb.cap;
-        // the block table of the units: queued now, for as many blocks as the handle's table from the previous build holds, so that
-        // it runs while the host waits for the unit total (redone by setup_finish should the table turn out too small)
-        if (g->btri.p && g->btri.cap >= 64) {
-            btri_entries = g->btri.cap / 4;
-            if (btri_entries > 0x3FFFFFFull) btri_entries = 0x3FFFFFFull;
-            if (early) {
-                // the units the buffers of the previous build hold; the hit scan runs over the blocks of that many units, so the entries
-                // behind this build's last block are zeroed on the way
-                unit_cap = std::min(std::min((uint64_t)g->umask.cap / 4 - 1, ((uint64_t)g->bhits.cap / 4 - 4) * 64),
-                                    std::min(((uint64_t)g->hbase.cap / 4 - 4) * 64, (btri_entries - 2) * 64));
-            }
-            vx::launch_unit_blocks(g->ubase.as<uint32_t>(), ntri, (uint32_t)((btri_entries - 2) * 64), g->btri.as<uint32_t>(), s, (uint32_t)btri_entries,
-                                   early ? &ds->units64 : nullptr, early ? &g->mail->units : nullptr, early ? g->bhits.as<uint32_t>() : nullptr,
-                                   (uint32_t)((unit_cap + 63) / 64));
-        }
-        if (cb.p && !clear_in_setup) {
-            VX_HIP(hipMemsetAsync(cb.p, 0, cb.cap, s));
-            cleared = cb.cap;
-        }
-        if (early && units_tagged) {
-            if (!mail_wait(&g->mail->bbox_tag, nullptr, mtag, 5.0)) VX_HIP(hipStreamSynchronize(s));
-            std::atomic_thread_fence(std::memory_order_acquire);
-        } else {
-            // the bbox (written by k_bbox, two kernels earlier) and the unit total: polled from the mailbox, see the hit count below
-            // (an untagged total on its way through device memory: the drained stream has forwarded it)
-            if (!(units_tagged && !early && mail_wait(&g->mail->units, nullptr, mtag, 5.0))) VX_HIP(hipStreamSynchronize(s));
-            early = false;
-        }
-        VX_TRY(extent_from_bbox(g->mail->bbox, mesh->nv, vs, &ex));
-        setup_queued = true;
-    } else {
-        early = false;
-        VX_TRY(compute_extent(mesh, vs, ds, g->mail.get(), s, &ex));  // also clears the per-build call counter
-    }
-    const uint64_t nvox = ex.dim[0] * ex.dim[1] * ex.dim[2];
-    if (nvox > kMaxVoxels) return fail(VX_ERR_CAPACITY, "grid exceeds 2^37 voxels");
-    fill_params(g->g, ex.mn, vs, ex.dim);
-    for (int a = 0; a < 3; ++a) { g->bbmin[a] = ex.mn[a]; g->bbmax[a] = ex.mx[a]; g->bbc[a] = ex.ctr[a]; }
-    VX_TRY(init_grid_storage(g, /*clear=*/false));
-    const size_t mask_bytes = (size_t)(g->g.nwords + 2) * 4;
-    if (g->words.fresh) { if (!cleared_tiled) cleared = 0; g->words.fresh = false; }  // a new block: the early clear hit the old one
-    bool mask_is_clear = !cleared_tiled && cleared >= mask_bytes;
-
-    uint64_t wb = 0, we = g->g.nwords;
-    if (by_rank) {
-        vx_shard_words(g->g.nwords, o.shard_rank, o.shard_world, &wb, &we, nullptr);
-    } else if (sharded_words) {
-        if (o.word_end > g->g.nwords) return fail(VX_ERR_INVALID_ARG, "word shard out of range");
-        wb = o.word_begin;
-        we = o.word_end;
-    }
-    const bool whole_build = wb == 0 && we == g->g.nwords && tb == 0 && te == mesh->nt;
-    auto no_calls_materials = [&]() -> vx_status {  // a build without a setVoxel call: no material is ever used
-        if (!want_mat) return VX_OK;
-        g->mat_pending = true;
-        g->mat_values = mesh->values;
-        g->mat_first_use.assign(mesh->values.size(), -1);
-        g->mat_dtv = nullptr; g->mat_ntri = 0; g->mat_nids = 0;
-        VX_HIP(g->mattmp.ensure(mesh->values.size() * 2 + 256));
-        if (whole_build) return finish_materials(g, g->mat_first_use.data(), g->mat_first_use.size());
-        return VX_OK;
-    };
-    g->triangles = te - tb;
-    if (ntri == 0 || nvox == 0 || wb == we) {
-        if (!mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
-        return no_calls_materials();
-    }
-
-    // Unsharded words, rows of whole words: the voxelizer ORs into the tiled build mask (one atomic request per 4 x 4 rows instead of one per
-    // row, launch_voxelize) and launch_untile writes every word of the reference's bitmask from it.  Ragged rows take the direct form.
-    const bool whole_words = wb == 0 && we == g->g.nwords;
-    // (a word shard goes the same way: the voxelizer keeps to the rows whose words it owns, launch_untile writes those and zeroes the rest --
-    // a second pass over the WHOLE mask per rank, so only where the mask is small against the mesh: the size rule of the clear that rides in
-    // the record kernel's threads.  atrium262k, two logical ranks on one GPU: 512^3 voxelize stage 121 -> 95 us; 1024^3 392 -> 426, hence the rule)
-    // ... and only for shards of a fifth of the mask or more: shard 0 of 2 / 4 / 8 at 512^3 (tools/shard_time.py, kernels of a rebuild)
-    // 119.7 -> 97.9 / 90.6 -> 73.3 / 55.1 -> 64.0 us -- at an eighth the un-tiling pass costs what the voxelizer no longer has to gain
-    const bool shard_small = (size_t)vx::tiled_mask_words(g->g.dim) * 4 / 256 <= (size_t)ntri && (we - wb) * 5 >= g->g.nwords;
-    const bool tiled = (whole_words || shard_small) && (ex.dim[0] % 32) == 0;
-    g->last_tiled = tiled;
-    if (tiled) {
-        const size_t tbytes = (size_t)vx::tiled_mask_words(g->g.dim) * 4;
-        VX_HIP(g->twords.ensure(tbytes));
-        const bool tw_clear = cleared_tiled && cleared >= tbytes && !g->twords.fresh;
-        g->twords.fresh = false;
-        if (!tw_clear) VX_HIP(hipMemsetAsync(g->twords.p, 0, tbytes, s));
-        mask_is_clear = true;  // every word of the mask and the two spare words behind it are written by launch_untile (or the brick kernel) --
-                               // or, when there is no unit to run, by the memset below
-    }
-    uint64_t U = 0;
-    if (early) {
-        if (!mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
-        U = unit_cap;  // (what the buffers below are sized for: they are the previous build's)
-    } else if (setup_queued) {
-        if (!mask_is_clear) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
-        VX_TRY(setup_finish(ntri, g->ubase, g->btri, g->mail.get(), s, &U, /*stream_is_drained=*/true, btri_entries));
-    } else {
-        // z slab that contains the voxels of words [wb, we)
-        const uint64_t XY = ex.dim[0] * ex.dim[1];
-        uint32_t zlo = (uint32_t)((wb * 32) / XY);
-        uint64_t zh = (we * 32 + XY - 1) / XY;
-        if (zh > ex.dim[2]) zh = ex.dim[2];
-        const uint32_t zhi = (uint32_t)zh;
-        // records + unit scan are queued, THEN the bitmask is cleared (it does not depend on the unit count), then the host waits
-        VX_TRY(setup_launch(mesh, g->g, o.sat_variant, tb, ntri, zlo, zhi, g->recs, g->units, g->ubase, g->scantmp, g->mail.get(), s, g->ext));
-        VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
-        VX_TRY(setup_finish(ntri, g->ubase, g->btri, g->mail.get(), s, &U));
-    }
-    if (U == 0) {  // (e.g. a word shard whose z slab holds no triangle): nothing will write the mask
-        if (tiled) VX_HIP(hipMemsetAsync(g->words.p, 0, mask_bytes, s));
-        return no_calls_materials();
-    }
-    uint32_t* umask = nullptr;
-    if (g->kind == VX_GRID_VEC || want_mat) {
-        VX_HIP(g->umask.ensure((size_t)(U + 1) * 4));
-        umask = g->umask.as<uint32_t>();
-    }
-    // an axis above 65535 cells: the unit kernels also read the extension words of the candidate ranges
-    const uint32_t* xw = (ex.dim[0] > 65535 || ex.dim[1] > 65535 || ex.dim[2] > 65535) ? g->ext.as<uint32_t>() : nullptr;
-    // VoxelGridVec::setVoxel appends one Aabb per call (voxelgridVecEncoding.cpp:19-39): ordered emission, at the exclusive scan of the
-    // hit counts -- two-level: the voxelizer leaves the hits of every block of 64 units, the device scan runs over those
-    const uint64_t nUB = (U + 63) / 64;
-    uint32_t* bhits = nullptr;
-    if (g->kind == VX_GRID_VEC) {
-        VX_HIP(g->bhits.ensure((size_t)(nUB + 4) * 4));
-        VX_HIP(g->hbase.ensure((size_t)(nUB + 4) * 4));
-        bhits = g->bhits.as<uint32_t>();
-    }
-    vx::launch_voxelize(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, o.sat_variant,
-                        tiled ? g->twords.as<uint32_t>() : g->words.as<uint32_t>(), wb, we, umask, ds->set_calls, s, xw, bhits, tiled,
-                        early ? &ds->units64 : nullptr, (uint32_t)unit_cap);
-    // (the tiled mask -> the reference's bitmask: by the brick kernel on its way when the traversal structure is built right away, below)
-    // (VX_VOXELIZE_SOLID: the fill reads and extends the reference's bitmask, the traversal structure is built from the final one)
-    const bool untile_in_bricks = tiled && whole_words && !solid;
-    if (tiled && !untile_in_bricks) vx::launch_untile(g->twords.as<uint32_t>(), g->words.as<uint32_t>(), g->g.dim, s, wb, we);
-    g->counts_valid = false;
-    bool hits_tagged = false, occ_tagged = false, occ_queued = false;
-    // A list_async rebuild whose brick kernel follows at once: nothing queued in the build reads the hit bases -- the block-hit scan stood here
-    // for its total, the list's length -- so the brick kernel posts that total from the voxelizer's own counters and the scan goes in front
-    // of the emission (list_scan).  Everything else keeps the scan here.
-    const bool defer_scan = early && untile_in_bricks;
-    if (defer_scan) {
-        VX_HIP(ensure_scan_tmp(g->hscantmp, vx::scan_tmp_bytes(nUB), s));
-        hits_tagged = true;
-    } else if (g->kind == VX_GRID_VEC) {
-        VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nUB), s));
-        hits_tagged = vx::launch_scan_u32(bhits, g->hbase.as<uint32_t>(), nUB, false, g->scantmp.p, &g->mail->hits, s, true, mtag, nullptr, advance_scan_gen(g->scantmp, s));
-    }
-    // VX_VOXELIZE_SOLID: the second loop -- setVoxel on every interior cell in ascending order -- once the surface mask is complete
-    uint64_t n_interior = 0;
-    const uint32_t* h_words = nullptr;
-    if (solid) {
-        VX_TRY(solid_fill(g, &n_interior, &h_words));
-        g->interior = n_interior;
-        g->host_set_calls += n_interior;
-    }
-    // A complete (unsharded) bitmask: queue what every consumer of the grid needs next -- the traversal structure (bricks,
-    // bounds, mips = the reference's acceleration-structure build, hello_vulkan.cpp:700-703) and the word prefix (getAabbs /
-    // primitive ids) -- behind the voxelizer instead of lazily in front of the first query.  For the Vec flavour this work
-    // runs while the host waits for the hit count.  A word shard's stay lazy (ensure_coarse / ensure_prefix in the query paths).
-    if (whole_words) {
-        // (a Vec build's consumers -- the ray batch's rank pass -- read wp16 only: from the brick kernel's line counts where a line lies in
-        // one row, i.e. X % 512 == 0, which makes nwords a multiple of 16 as the rank pass's 16-word path needs it.  The Bool flavours emit
-        // their list from the word prefix right away, materials index it: today's scan)
-        const bool lines = untile_in_bricks && g->kind == VX_GRID_VEC && !want_mat && (ex.dim[0] % 512) == 0;
-        if (lines) VX_HIP(g->lcnt.ensure((size_t)(g->g.nwords / 16 + 4) * 4));
-        VX_TRY(ensure_coarse(g, untile_in_bricks, lines, mtag, &occ_tagged, defer_scan));
-        if (lines) {
-            occ_queued = true;
-        } else {
-            bool pending = false;
-            occ_queued = !g->prefix_valid;
-            VX_TRY(prefix_launch(g, &pending, mtag, &occ_tagged));
-        }
-    }
-    if (g->kind == VX_GRID_VEC) {
-        // The list is emitted into the handle's existing buffer before the host knows the hit count (writes beyond the
-        // buffer's capacity are dropped by the kernel); only a list that outgrew it is emitted again after the wait.
-        const bool to_bound = g->bound != nullptr && g->bound_cap > 0;
-        vx_aabb* tgt = to_bound ? g->bound : g->vec.as<vx_aabb>();
-        const uint64_t cap_rec = to_bound ? g->bound_cap + 1 : (g->vec.p ? g->vec.cap / sizeof(vx_aabb) : 0);
-        g->vec_in_bound = false;
-        if (cap_rec && !list_async)
-            vx::launch_emit_units(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, umask,
-                                  g->hbase.as<uint32_t>(), tgt, nullptr, s, to_bound ? g->bound_cap : cap_rec, xw);
-        // The host needs the hit count (and takes the occupied count along).  Both are written by scans -- the hit count of a build that
-        // left its block-hit scan to the list (defer_scan) by the brick kernel, from the voxelizer's counters -- that run BEFORE the
-        // emission: the host polls the tagged mailbox words and goes on queueing work (the caller's next call: a trace) while
-        // the emission still runs; a stream synchronize would wake it ~15 us after the last kernel.  An untagged total
-        // (three-pass scan) or 5 ms without an answer: the synchronize.
-        // VX_VOXELIZE_LIST_ASYNC: only the hit count -- its scan runs in front of the traversal structure and the word prefix, so the host
-        // is back in the caller ~40 us of GPU work before the build ends and the caller's ray batch is queued in time; the occupied count
-        // (the LAST kernel's total) is fetched when somebody asks for it (prefix_finish).
-        const bool occ_in_flight = (g->prefix_valid || g->p16_valid) && !g->occupied_known;
-        const bool occ_along = occ_in_flight && !(list_async && occ_queued && occ_tagged);
-        bool got = false;
-        if (hits_tagged && (!occ_along || (occ_queued && occ_tagged)))
-            got = mail_wait(&g->mail->hits, occ_along ? &g->mail->occupied : nullptr, mtag, 5.0);
-        if (!got) VX_HIP(hipStreamSynchronize(s));
-        uint64_t units_known = U;
-        if (early) {
-            // the unit total, in the mailbox since k_unit_blocks: checked as setup_finish checks it.  More units than the early launch's
-            // buffers hold: the voxelizer did nothing -- the buffers grow and the build runs again the way of a first build
-            if ((g->mail->units & ~kMailValue) != mtag) VX_HIP(hipStreamSynchronize(s));
-            const unsigned long long tot = g->mail->units & kMailValue;
-            if (tot >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 candidate row segments: shard the mesh or the grid");
-            if (tot > unit_cap) {
-                VX_HIP(hipStreamSynchronize(s));  // (the kernels of this pass read the blocks that are about to be replaced)
-                VX_HIP(g->umask.ensure((size_t)(tot + 1) * 4));
-                VX_HIP(g->bhits.ensure((size_t)(tot / 64 + 5) * 4));
-                VX_HIP(g->hbase.ensure((size_t)(tot / 64 + 5) * 4));
-                VX_HIP(g->btri.ensure((size_t)(tot / 64 + 2) * 4));
-                return voxelize_build(mesh, vs, o, g, /*allow_early=*/false);
-            }
-            units_known = tot;
-        }
-        const unsigned long long hits = g->mail->hits & kMailValue;
-        if (hits >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 voxel hits");
-        if ((g->prefix_valid || g->p16_valid) && (occ_along || !got)) {  // the same wait covered the occupied count
-            if ((g->mail->occupied & kMailValue) >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 occupied voxels");
-            g->occupied = g->mail->occupied & kMailValue;
-            g->occupied_known = true;
-        }
-        const uint64_t total = hits + n_interior;  // (a solid build: the interior's records follow the triangles')
-        if (total >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 voxel records");
-        if (total + 1 <= cap_rec) g->vec_in_bound = to_bound;
-        if (total + 1 > cap_rec) VX_HIP(g->vec.ensure((size_t)(total + 1) * sizeof(vx_aabb)));
-        if (list_async) {
-            // VX_VOXELIZE_LIST_ASYNC: the count is known, the records are written later -- beside the next ray batch (trace_common), or
-            // on this stream by whatever asks for them first (list_resolve)
-            g->ld.from_mask = false;
-            g->ld.ntri = ntri;
-            g->ld.ext = xw != nullptr;
-            g->ld.tgt = g->vec_ptr();
-            g->ld.cap = g->vec_in_bound ? g->bound_cap : ~0ull;
-            g->list_deferred = hits != 0;
-            g->ld.scan_blocks = defer_scan && hits ? (units_known + 63) / 64 : 0;  // (the true unit total: the build's own blocks, not the buffers')
-        } else if (total + 1 > cap_rec) {
-            vx::launch_emit_units(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, umask,
-                                  g->hbase.as<uint32_t>(), g->vec.as<vx_aabb>(), nullptr, s, ~0ull, xw);
-        }
-        if (n_interior)  // cell_aabb of every interior cell in ascending order, at offset `hits`
-            vx::launch_emit_bool_aabbs(h_words, g->solid_pre.as<uint32_t>(), g->g, g->vec_ptr() + hits, n_interior, s);
-        g->vec_count = total;
-        g->mat_surface = hits;
-    }
-    if (want_mat) {
-        // ---- per-voxel material ids (see k_mat_last): needs the word prefix (queued above for an unsharded build) and, for the Vec
-        // flavour, the hit bases.  First half here: the last triangle per voxel of this shard and, per material value, the first
-        // triangle of this shard that uses it; second half (finish_materials) once the first uses of ALL shards are known -- at once
-        // for a whole build.
-        bool pending = false;
-        VX_TRY(prefix_launch(g, &pending));
-        VX_TRY(prefix_finish(g, pending));
-        const uint64_t nids = g->kind == VX_GRID_VEC ? g->vec_count : g->occupied;
-        const size_t tmp_bytes = (g->kind == VX_GRID_VEC ? 0 : (size_t)nids * 4) + (size_t)ntri + 64 + mesh->values.size() * 2 + 64;
-        VX_HIP(g->mattmp.ensure(tmp_bytes));
-        uint8_t* base = g->mattmp.as<uint8_t>();
-        uint32_t* last_tri = g->kind == VX_GRID_VEC ? nullptr : reinterpret_cast<uint32_t*>(base);
-        uint8_t* tri_hit = base + (g->kind == VX_GRID_VEC ? 0 : (size_t)nids * 4);
-        VX_HIP(hipMemsetAsync(base, 0, (size_t)(tri_hit - base) + ntri, s));
-        vx::launch_mat_last(g->recs.as<vx::TriRec>(), g->ubase.as<uint32_t>(), g->btri.as<uint32_t>(), ntri, g->g, umask, g->words.as<uint32_t>(),
-                            g->wprefix.as<uint32_t>(), last_tri, tri_hit, s, xw);
-        std::vector<uint8_t> hit(ntri);
-        VX_HIP(hipMemcpyAsync(hit.data(), tri_hit, ntri, hipMemcpyDeviceToHost, s));
-        VX_HIP(hipStreamSynchronize(s));
-        g->mat_values = mesh->values;
-        g->mat_first_use.assign(mesh->values.size(), -1);
-        const int32_t* tv = mesh->tri_value.data() + tb;
-        for (uint32_t t = 0; t < ntri; ++t)
-            if (hit[t] && g->mat_first_use[(size_t)tv[t]] < 0) g->mat_first_use[(size_t)tv[t]] = (long long)(tb + t);
-        // the interior's calls come after every triangle's and carry MaterialObj{} (value 0): addMatrialIfNeeded appends it if no triangle used it
-        g->mat_interior = n_interior;
-        if (n_interior && g->mat_first_use[0] < 0) g->mat_first_use[0] = (long long)(tb + ntri);
-        g->mat_dtv = mesh->btv.as<int32_t>() + tb;
-        g->mat_ntri = ntri;
-        g->mat_nids = nids;
-        g->mat_pending = true;
-        if (whole_build) VX_TRY(finish_materials(g, g->mat_first_use.data(), g->mat_first_use.size()));
-    }
-    VX_HIP(hipGetLastError());
-    return VX_OK;
 }
 
 vx_status vx_voxelize(const vx_mesh* mesh, float vs, vx_grid_kind kind, const vx_voxelize_opts* opts, vx_grid** out)
@@ -2167,21 +2394,28 @@ static vx_status surface_count(vx_grid* g, bool want_mat, uint64_t* nv, uint64_t
     VX_HIP(g->surf_tpre.ensure((size_t)(g->g.nwords + 4) * 4));
     VX_HIP(g->surf_cm.ensure((size_t)(p.nlw + 4) * 4));
     VX_HIP(g->surf_vpre.ensure((size_t)(p.nlw + 4) * 4));
-    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(nmax), g->stream));
+    VX_HIP(ensure_scan_tmp(g->up.scantmp, vx::scan_tmp_bytes(nmax), g->stream));
     bool pending = false;
     if (want_mat) VX_TRY(prefix_launch(g, &pending));
     vx::launch_surface_count(g->words.as<uint32_t>(), g->g, p, g->surf_cnt.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->stream);
-    vx::launch_scan_u32(g->surf_cnt.as<uint32_t>(), g->surf_tpre.as<uint32_t>(), g->g.nwords, false, g->scantmp.p, &g->mail->surf_tris, g->stream, true, 0,
-                        nullptr, advance_scan_gen(g->scantmp, g->stream));
-    vx::launch_scan_u32(g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(), p.nlw, true, g->scantmp.p, &g->mail->surf_verts, g->stream, true, 0,
-                        nullptr, advance_scan_gen(g->scantmp, g->stream));
+    // (one scratch block for both scans, sized ahead of the count kernel: not scan_on)
+    vx::ScanArgs a;
+    a.tmp_is_zero = true;
+    a.gen = advance_scan_gen(g->up.scantmp, g->stream);
+    vx::launch_scan_u32(g->surf_cnt.as<uint32_t>(), g->surf_tpre.as<uint32_t>(), g->g.nwords, false, g->up.scantmp.p, &g->mail->surf_tris, g->stream, a);
+    a.gen = advance_scan_gen(g->up.scantmp, g->stream);
+    vx::launch_scan_u32(g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(), p.nlw, true, g->up.scantmp.p, &g->mail->surf_verts, g->stream, a);
     VX_HIP(hipGetLastError());
-    VX_HIP(hipStreamSynchronize(g->stream));
+    // (one wait for both totals; beyond 2^32 - 1 they are refused as surface_check refuses them)
+    const char* limit = "surface mesh above 2^31 - 1 vertices or triangles (int32 indices)";
+    uint64_t tris = 0, verts = 0;
+    VX_TRY(mail_total(&g->mail->surf_tris, false, 0, g->stream, limit, &tris));
+    VX_TRY(mail_value(&g->mail->surf_verts, limit, &verts));
     VX_TRY(prefix_finish(g, pending));
     if (want_mat && g->occupied > (g->mat_gathered ? g->mat_gather_count : g->mat_count))
         return fail(VX_ERR_INVALID_ARG, "surface materials: the grid's material ids do not cover its occupied cells");
-    *nt = g->mail->surf_tris & kMailValue;
-    *nv = g->mail->surf_verts & kMailValue;
+    *nt = tris;
+    *nv = verts;
     return VX_OK;
 }
 
@@ -2280,10 +2514,12 @@ static vx_status components_queue(vx_grid* g, uint32_t connectivity, uint32_t* l
 {
     VX_HIP(g->cc_roots.ensure((size_t)(g->g.nwords + 4) * 4));
     VX_HIP(g->cc_rpre.ensure((size_t)(g->g.nwords + 4) * 4));
-    VX_HIP(ensure_scan_tmp(g->scantmp, vx::scan_tmp_bytes(g->g.nwords), g->stream));
+    VX_HIP(ensure_scan_tmp(g->up.scantmp, vx::scan_tmp_bytes(g->g.nwords), g->stream));
     vx::launch_components(g->words.as<uint32_t>(), g->g, connectivity == VX_CONNECT_26, labels, g->cc_roots.as<uint32_t>(), g->stream);
-    vx::launch_scan_u32(g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), g->g.nwords, true, g->scantmp.p, &g->mail->cc_count, g->stream, true, 0,
-                        nullptr, advance_scan_gen(g->scantmp, g->stream));
+    vx::ScanArgs a;  // (the scratch is sized ahead of the union-find kernel: not scan_on)
+    a.tmp_is_zero = true;
+    a.gen = advance_scan_gen(g->up.scantmp, g->stream);
+    vx::launch_scan_u32(g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), g->g.nwords, true, g->up.scantmp.p, &g->mail->cc_count, g->stream, a);
     vx::launch_components_label(g->words.as<uint32_t>(), g->g, labels, g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), dev_count, g->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
@@ -2295,9 +2531,7 @@ static vx_status components_host(vx_grid* g, uint32_t connectivity, uint32_t* ho
     VX_HIP(g->cc_lab.ensure((size_t)g->g.nvox * 4));
     VX_TRY(components_queue(g, connectivity, g->cc_lab.as<uint32_t>(), nullptr));
     if (host_labels) VX_HIP(hipMemcpyAsync(host_labels, g->cc_lab.p, (size_t)g->g.nvox * 4, hipMemcpyDeviceToHost, g->stream));
-    VX_HIP(hipStreamSynchronize(g->stream));
-    *k = g->mail->cc_count & kMailValue;
-    return VX_OK;
+    return mail_total(&g->mail->cc_count, false, 0, g->stream, "components need X*Y*Z <= 2^32 - 1 (32-bit labels and union-find indices)", k);
 }
 
 vx_status vx_grid_components_device(const vx_grid* gc, uint32_t connectivity, uint32_t* dev_labels, uint64_t capacity, uint32_t* dev_count)
@@ -2893,8 +3127,8 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
     o->vs = vs;
     o->max_items = max_items;
     MailPtr mail;
-    DevBuf small{&here}, recs{&here}, ext{&here}, units{&here}, ubase{&here}, btri{&here}, scantmp{&here}, umask{&here}, bhits{&here}, hbase{&here}, unsorted{&here},
-        sorttmp{&here}, ncount{&here}, nbase{&here};
+    DevBuf small{&here}, unsorted{&here}, sorttmp{&here}, ncount{&here}, nbase{&here};
+    UnitPipe up{&here};
     VX_HIP(ensure_small(small));
     Small* ds = small.as<Small>();
     VX_HIP(mail_alloc(mail));
@@ -2913,29 +3147,30 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
     vx::GridParams g;
     fill_params(g, ex.mn, vs, ex.dim);
     uint64_t U = 0;
-    VX_TRY(setup_launch(mesh, g, /*sat a7: octTree.hpp:762*/ 0, 0, ntri, 0, (uint32_t)ex.dim[2], recs, units, ubase, scantmp, mail.get(), s, ext));
-    const uint32_t* xw = (ex.dim[0] > 65535 || ex.dim[1] > 65535 || ex.dim[2] > 65535) ? ext.as<uint32_t>() : nullptr;
-    VX_TRY(setup_finish(ntri, ubase, btri, mail.get(), s, &U));
-    unsigned long long hits = 0;
+    const bool wide = ex.dim[0] > 65535 || ex.dim[1] > 65535 || ex.dim[2] > 65535;  // the unit kernels also read the extension words
+    VX_TRY(up.setup_launch(mesh, g, /*sat a7: octTree.hpp:762*/ 0, 0, ntri, 0, (uint32_t)ex.dim[2], mail.get(), s));
+    VX_TRY(up.setup_finish(ntri, mail.get(), s, &U));
+    uint64_t hits = 0;
     if (U) {
-        VX_HIP(umask.ensure((size_t)(U + 1) * 4));
+        VX_HIP(up.umask.ensure((size_t)(U + 1) * 4));
         const uint64_t nUB = (U + 63) / 64;  // hits per block of 64 units from the voxelizer, scanned: the items' positions (as for the Vec grid)
-        VX_HIP(bhits.ensure((size_t)(nUB + 4) * 4));
-        VX_HIP(hbase.ensure((size_t)(nUB + 4) * 4));
-        VX_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(nUB), s));
-        vx::launch_voxelize(recs.as<vx::TriRec>(), ubase.as<uint32_t>(), btri.as<uint32_t>(), ntri, g, 0, nullptr, 0, 0, umask.as<uint32_t>(), ds->set_calls, s, xw,
-                            bhits.as<uint32_t>());
-        vx::launch_scan_u32(bhits.as<uint32_t>(), hbase.as<uint32_t>(), nUB, false, scantmp.p, &mail->hits, s, true, 0, nullptr, advance_scan_gen(scantmp, s));
-        VX_HIP(hipStreamSynchronize(s));
-        hits = mail->hits & kMailValue;
-        if (hits >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 octree items");
+        VX_HIP(up.bhits.ensure((size_t)(nUB + 4) * 4));
+        VX_HIP(up.hbase.ensure((size_t)(nUB + 4) * 4));
+        VX_HIP(ensure_scan_tmp(up.scantmp, vx::scan_tmp_bytes(nUB), s));  // (ahead of the voxelizer: not scan_on)
+        vx::VoxelizeArgs va;
+        va.block_hits = up.bhits.as<uint32_t>();
+        vx::launch_voxelize(up.view(ntri, wide), g, 0, nullptr, 0, 0, up.umask.as<uint32_t>(), ds->set_calls, s, va);
+        vx::ScanArgs sa;
+        sa.tmp_is_zero = true;
+        sa.gen = advance_scan_gen(up.scantmp, s);
+        vx::launch_scan_u32(up.bhits.as<uint32_t>(), up.hbase.as<uint32_t>(), nUB, false, up.scantmp.p, &mail->hits, s, sa);
+        VX_TRY(mail_total(&mail->hits, false, 0, s, "more than 2^32 octree items", &hits));
     }
     o->nitems = hits;
     if (hits) {
         VX_HIP(unsorted.ensure((size_t)hits * 8));
         VX_HIP(o->items.ensure((size_t)hits * 8));
-        vx::launch_emit_units(recs.as<vx::TriRec>(), ubase.as<uint32_t>(), btri.as<uint32_t>(), ntri, g, umask.as<uint32_t>(), hbase.as<uint32_t>(),
-                              nullptr, unsorted.as<uint64_t>(), s, ~0ull, xw);
+        vx::launch_emit_units(up.view(ntri, wide), g, up.umask.as<uint32_t>(), up.hbase.as<uint32_t>(), nullptr, unsorted.as<uint64_t>(), s);
         const size_t tb = vx::sort_tmp_bytes(hits);
         VX_HIP(sorttmp.ensure(tb));
         // octTree.hpp:363; the sort ping-pongs between the two buffers: whichever holds the result becomes the octree's item list
@@ -2948,12 +3183,12 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
         const uint32_t ni = (uint32_t)hits;
         VX_HIP(ncount.ensure((size_t)ni + 16));
         VX_HIP(nbase.ensure(((size_t)ni + 2) * 4));
-        VX_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(ni), s));
+        VX_HIP(ensure_scan_tmp(up.scantmp, vx::scan_tmp_bytes(ni), s));
         vx::launch_oct_depths(o->items.as<uint64_t>(), ni, o->bits, (uint32_t)max_items, ncount.as<uint8_t>(), s);
-        vx::launch_scan_u8(ncount.as<uint8_t>(), nbase.as<uint32_t>(), ni, scantmp.p, &mail->occupied, s, 0, advance_scan_gen(scantmp, s));
-        VX_HIP(hipStreamSynchronize(s));
-        const unsigned long long nn = mail->occupied & kMailValue;
-        if (nn == 0 || nn >= 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "more than 2^32 octree nodes");
+        vx::launch_scan_u8(ncount.as<uint8_t>(), nbase.as<uint32_t>(), ni, up.scantmp.p, &mail->occupied, s, 0, advance_scan_gen(up.scantmp, s));
+        uint64_t nn = 0;
+        VX_TRY(mail_total(&mail->occupied, false, 0, s, "more than 2^32 octree nodes", &nn));
+        if (nn == 0) return fail(VX_ERR_CAPACITY, "more than 2^32 octree nodes");
         VX_HIP(o->nodebuf.ensure((size_t)nn * sizeof(vx_octree_node)));
         o->dnodes = o->nodebuf.as<vx_octree_node>();
         VX_HIP(hipMemsetAsync(o->dnodes, 0xFF, (size_t)nn * sizeof(vx_octree_node), s));  // children = 0xFFFFFFFF (none)
@@ -4308,8 +4543,14 @@ vx_status vx_scan_u32(const vx_scan_args* a)
             vx::launch_scan_u8((const uint8_t*)din.p + a->in_offset, out, n, tmp.p, dtot.as<unsigned long long>(), s, a->total_tag, gen);
             one = true;
         } else {
-            one = vx::launch_scan_u32(din.as<uint32_t>() + a->in_offset, out, n, a->mode == VX_SCAN_POPCOUNT, tmp.p, dtot.as<unsigned long long>(), s, tz,
-                                      a->total_tag, sel, gen, g16, lp);
+            vx::ScanArgs sa;
+            sa.tmp_is_zero = tz;
+            sa.total_tag = a->total_tag;
+            sa.sel1024 = sel;
+            sa.gen = gen;
+            sa.group16 = g16;
+            sa.path = lp;
+            one = vx::launch_scan_u32(din.as<uint32_t>() + a->in_offset, out, n, a->mode == VX_SCAN_POPCOUNT, tmp.p, dtot.as<unsigned long long>(), s, sa);
         }
         const bool gen_mode = one && gen && (n + 1 + 16383) / 16384 <= 512;  // (kScanGenTiles tiles of 16384)
         VX_HIP(hipStreamSynchronize(s));

@@ -82,16 +82,20 @@ size_t scan_tmp_bytes(uint64_t n);
 // path: kScanPathAuto = single-pass; the other two choose in the call (test aid).
 // Unaligned in / out take the three-pass path whatever `path` says.
 constexpr int kScanPathAuto = 0, kScanPathOne = 1, kScanPathThree = 2;
-// tmp_is_zero: the caller guarantees tmp (scan_tmp_bytes(n)) is all zero; the scan leaves it all zero again.
-// total_tag (bits 48..63 only): OR-ed into *total64 by the single-pass kernel, so that a host polling a pinned mailbox word can tell
-// this scan's total from an older one; returns whether the tag was applied (false: the three-pass path, *total64 is the bare total).
-bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp,
-                     unsigned long long* total64, hipStream_t s, bool tmp_is_zero = false, unsigned long long total_tag = 0,
-                     uint32_t* sel1024 = nullptr /*optional (single-pass kernel only, values <= 1024): sel1024[c] = the element whose range holds c * 1024*/,
-                     uint32_t gen = 0 /*generation mode (vx_kernels.hip): the number of this scan on `tmp`, 1, 2, 3 ... < 2^22; 0 = tickets + self-cleaning state*/,
-                     uint32_t* group16 = nullptr /*optional (single-pass kernel only): group16[i] = out[16 i], n / 16 + 1 entries -- a dense array small
-                                                   enough to stay in L2 for readers that gather (k_rank)*/,
-                     int path = kScanPathAuto);
+// launch_scan_u32's optional arguments
+struct ScanArgs {
+    bool tmp_is_zero = false;          // the caller guarantees tmp (scan_tmp_bytes(n)) is all zero; the scan leaves it all zero again
+    // (bits 48..63 only) OR-ed into *total64 by the single-pass kernel, so that a host polling a pinned mailbox word can tell this scan's
+    // total from an older one; the launcher returns whether the tag was applied (false: the three-pass path, *total64 is the bare total)
+    unsigned long long total_tag = 0;
+    uint32_t* sel1024 = nullptr;       // optional (single-pass kernel only, values <= 1024): sel1024[c] = the element whose range holds c * 1024
+    uint32_t gen = 0;                  // generation mode (vx_kernels.hip): the number of this scan on `tmp`, 1, 2, 3 ... < 2^22; 0 = tickets + self-cleaning state
+    uint32_t* group16 = nullptr;       // optional (single-pass kernel only): group16[i] = out[16 i], n / 16 + 1 entries -- a dense array small
+                                       // enough to stay in L2 for readers that gather (k_rank)
+    int path = kScanPathAuto;
+};
+bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp, unsigned long long* total64, hipStream_t s,
+                     const ScanArgs& a = ScanArgs());
 
 // clears the bits past nvox in the last word of a bitmask of nvox cells (nothing to do when nvox is a multiple of 32)
 void launch_mask_tail(uint32_t* words, uint64_t nvox, hipStream_t s);
@@ -99,41 +103,55 @@ void launch_mask_tail(uint32_t* words, uint64_t nvox, hipStream_t s);
 void launch_scan_u8(const uint8_t* in, uint32_t* out, uint64_t n, void* tmp /*scan_tmp_bytes(n), all zero*/, unsigned long long* total64, hipStream_t s,
                     unsigned long long total_tag = 0, uint32_t gen = 0);
 
+// The unit pipeline as its readers see it: k_tri_setup's records, the exclusive scan of the unit counts (ntri + 1 entries), per 256-unit
+// block the triangle of its first unit (launch_unit_blocks; enables LDS staging) and the extension words of the candidate ranges (null
+// unless an axis has more than 65535 cells).  The first argument of every launcher that walks the units.
+struct Units {
+    const TriRec* recs = nullptr;
+    const uint32_t* unit_base = nullptr;
+    const uint32_t* block_tri = nullptr;
+    uint32_t ntri = 0;
+    const uint32_t* ext = nullptr;
+};
+// launch_unit_blocks' optional arguments
+struct UnitBlockArgs {
+    uint32_t cap_blocks = 0xFFFFFFFFu;              // the kernel never writes at or beyond this entry of block_tri
+    const unsigned long long* fwd_src = nullptr;    // optional: *fwd_dst = *fwd_src, the unit scan's total on its way from device memory to
+    unsigned long long* fwd_dst = nullptr;          // the host's mailbox
+    uint32_t* zero_hits = nullptr;                  // optional: entries [nUB, zero_n) of the voxelizer's block_hits are zeroed (zero_n at most
+    uint32_t zero_n = 0;                            // the blocks this launch covers)
+};
+// block_tri (u.block_tri is not read): the table to write
+void launch_unit_blocks(const Units& u, uint32_t total_units, uint32_t* block_tri, hipStream_t s, const UnitBlockArgs& a = UnitBlockArgs());
 // K2: triangle/voxel overlap over all work units; ORs hits into `words` (only words in [wb,we)), optionally
 // stores each unit's 32-bit hit mask (unit_mask) for the ordered emitters; adds the hit count to *set_calls.
-// block_tri (optional): per 256-unit block the triangle of its first unit (launch_unit_blocks), enables LDS staging.
-void launch_unit_blocks(const uint32_t* unit_base, uint32_t ntri, uint32_t total_units, uint32_t* block_tri, hipStream_t s, uint32_t cap_blocks = 0xFFFFFFFFu,
-                        const unsigned long long* fwd_src = nullptr, unsigned long long* fwd_dst = nullptr /*optional: *fwd_dst = *fwd_src, the unit
-                        scan's total on its way from device memory to the host's mailbox*/,
-                        uint32_t* zero_hits = nullptr, uint32_t zero_n = 0 /*optional: entries [nUB, zero_n) of the voxelizer's block_hits are zeroed (zero_n
-                        at most the blocks this launch covers)*/);
-void launch_voxelize(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const GridParams& g,
-                     int sat_variant, uint32_t* words, uint64_t wb, uint64_t we, uint32_t* unit_mask, unsigned long long* set_calls,
-                     hipStream_t s, const uint32_t* ext = nullptr /*k_tri_setup's extension words; null unless an axis has more than 65535 cells*/,
-                     uint32_t* block_hits = nullptr /*with unit_mask: hits per block of 64 units, (U + 63) / 64 entries -- what launch_emit_units'
-                                                      block_base is the exclusive scan of*/,
-                     bool tiled = false /*`words` is the tiled build mask (tiled_mask_words(dim) words, dim[0] % 32 == 0, whole grid): launch_untile
-                                          then writes the reference's bitmask*/,
-                     const unsigned long long* units_total = nullptr /*a launch queued before the host knows the unit total: the scan's 64-bit total in
-                                          device memory; the kernel does nothing when it exceeds unit_cap*/,
-                     uint32_t unit_cap = 0 /*the units unit_mask / block_hits / block_tri were sized for*/);
+struct VoxelizeArgs {
+    uint32_t* block_hits = nullptr;                    // with unit_mask: hits per block of 64 units, (U + 63) / 64 entries -- what
+                                                       // launch_emit_units' block_base is the exclusive scan of
+    bool tiled = false;                                // `words` is the tiled build mask (tiled_mask_words(dim) words, dim[0] % 32 == 0, whole
+                                                       // grid): launch_untile then writes the reference's bitmask
+    const unsigned long long* units_total = nullptr;   // a launch queued before the host knows the unit total: the scan's 64-bit total in
+                                                       // device memory; the kernel does nothing when it exceeds unit_cap
+    uint32_t unit_cap = 0;                             // the units unit_mask / block_hits / block_tri were sized for
+};
+void launch_voxelize(const Units& u, const GridParams& g, int sat_variant, uint32_t* words, uint64_t wb, uint64_t we, uint32_t* unit_mask,
+                     unsigned long long* set_calls, hipStream_t s, const VoxelizeArgs& a = VoxelizeArgs());
 uint64_t tiled_mask_words(const uint32_t dim[3]);
 void launch_untile(const uint32_t* tiled, uint32_t* words, const uint32_t dim[3], hipStream_t s, uint64_t wb = 0, uint64_t we = ~0ull /*the words the build owns: the others are written as zero*/);
 
 // K3: VoxelGridVec / Octree emitters: one output per set bit of unit_mask, in unit order (== reference order).  block_base[b] = position of
 // the first hit of units [64 b, 64 b + 64): the exclusive scan of launch_voxelize's block_hits.
-void launch_emit_units(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const GridParams& g,
-                       const uint32_t* unit_mask, const uint32_t* block_base, vx_aabb* aabbs, uint64_t* morton, hipStream_t s, uint64_t cap = ~0ull,
-                       const uint32_t* ext = nullptr);
+void launch_emit_units(const Units& u, const GridParams& g, const uint32_t* unit_mask, const uint32_t* block_base, vx_aabb* aabbs, uint64_t* morton,
+                       hipStream_t s, uint64_t cap = ~0ull);
 
 // Per-voxel material ids (the reference's commented-out addMatrialIfNeeded plumbing): pass 1 = last triangle per occupied voxel
 // (last_tri[rank], zeroed by the caller; may be null for the Vec flavour) + tri_hit[t] = 1 for triangles that set a voxel (zeroed by
 // the caller); pass 2 = triangle -> material value -> index of first use.
-void launch_mat_last(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const GridParams& g, const uint32_t* unit_mask,
-                     const uint32_t* words, const uint32_t* word_prefix, uint32_t* last_tri, uint8_t* tri_hit, hipStream_t s, const uint32_t* ext = nullptr);
+void launch_mat_last(const Units& u, const GridParams& g, const uint32_t* unit_mask, const uint32_t* words, const uint32_t* word_prefix, uint32_t* last_tri,
+                     uint8_t* tri_hit, hipStream_t s);
 void launch_mat_ids(const uint32_t* last_tri, uint64_t n, const int32_t* tri_value, const int16_t* value_index, int16_t* out, hipStream_t s);
-void launch_mat_ids_calls(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const uint32_t* unit_mask,
-                          const uint32_t* block_base, const int32_t* tri_value, const int16_t* value_index, int16_t* out, hipStream_t s);
+void launch_mat_ids_calls(const Units& u, const uint32_t* unit_mask, const uint32_t* block_base, const int32_t* tri_value, const int16_t* value_index,
+                          int16_t* out, hipStream_t s);
 
 // K4: bitmask -> ordered AABB list (word_prefix = exclusive scan of popcounts, nwords+1 entries)
 void launch_emit_bool_aabbs(const uint32_t* words, const uint32_t* word_prefix, const GridParams& g, vx_aabb* out,
@@ -148,14 +166,17 @@ void launch_emit_morton_aabbs(const uint64_t* items, uint64_t n, const float roo
 //            bit z*8+y per x slab, orientation 1 bit x*8+z per y slab
 //   w1       one bit per brick (dims d1), x-fastest;   w2: one bit per 8^3 bricks (dims d2)
 // (m1 given and bdim[0] % 64 == 0: the brick kernel writes the level-1 mip itself, leaves empty bricks unwritten and returns true)
+struct BricksArgs {
+    const uint32_t* tiled = nullptr;                   // the voxelizer's tiled build mask (dim[0] % 32 == 0): the source instead of `words`, and
+                                                       // `words` is WRITTEN from it -- launch_untile's job done on the way
+    uint32_t* line_cnt = nullptr;                      // with `tiled`, dim[0] % 512 == 0 (so every 16-word line of the bitmask lies in one row): the
+                                                       // set bits per line, nwords / 16 counts; their exclusive scan is word_prefix[16 i]
+    const unsigned long long* hit_counters = nullptr;  // optional: k_voxelize's kCallCounters spread counters, complete on `s`
+    unsigned long long* hits_out = nullptr;            // with hit_counters: receives hits_tag | their sum (THE TOTAL's contract) as the kernel starts
+    unsigned long long hits_tag = 0;
+};
 bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const uint32_t bdim[3], unsigned long long* bricks3, uint32_t* m1, hipStream_t s,
-                          const uint32_t* tiled = nullptr /*the voxelizer's tiled build mask (dim[0] % 32 == 0): the source instead of `words`, and `words`
-                                                            is WRITTEN from it -- launch_untile's job done on the way*/,
-                          uint32_t* line_cnt = nullptr /*with `tiled`, dim[0] % 512 == 0 (so every 16-word line of the bitmask lies in one row): the set
-                                                         bits per line, nwords / 16 counts; their exclusive scan is word_prefix[16 i]*/,
-                          const unsigned long long* hit_counters = nullptr /*optional: k_voxelize's kCallCounters spread counters, complete on `s`*/,
-                          unsigned long long* hits_out = nullptr /*with hit_counters: receives hits_tag | their sum (THE TOTAL's contract) as the kernel starts*/,
-                          unsigned long long hits_tag = 0);
+                          const BricksArgs& a = BricksArgs());
 void launch_brick_mip1(const unsigned long long* bricks_z /*orientation 2*/, uint64_t nbricks, uint32_t* m1, hipStream_t s);
 void launch_build_mip2(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, hipStream_t s);
 // the level-2 mip and the exclusive scan of n uint32 (launch_scan_u32 on a generation-managed, zero-between-scans tmp) in one launch

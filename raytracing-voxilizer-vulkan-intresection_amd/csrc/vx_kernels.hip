@@ -497,12 +497,13 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
 size_t scan_tmp_bytes(uint64_t n) { return (size_t)(((n + 1) + kScanTile - 1) / kScanTile + 4) * sizeof(unsigned long long); }
 
 // *total64: see THE TOTAL above (the exact range, the saturation at 2^40 - 1 and the tag bits).
-bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp, unsigned long long* total64,
-                     hipStream_t s, bool tmp_is_zero, unsigned long long total_tag, uint32_t* sel1024, uint32_t gen, uint32_t* group16, int path)
+bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp, unsigned long long* total64, hipStream_t s, const ScanArgs& a)
 {
+    const bool tmp_is_zero = a.tmp_is_zero;
+    const uint32_t gen = a.gen;
     const uint32_t nblocks = (uint32_t)(((n + 1) + kScanTile - 1) / kScanTile);
     unsigned long long* status = (unsigned long long*)tmp;
-    const bool three_pass = path == kScanPathThree;
+    const bool three_pass = a.path == kScanPathThree;
     const bool aligned = ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;  // the single-pass kernel moves 16-byte vectors
     if (!three_pass && aligned) {
         const uint32_t ntiles = (uint32_t)(((n + 1) + kOneTile - 1) / kOneTile);
@@ -510,8 +511,8 @@ bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcoun
         // first (they hold older scans' words) and runs with tickets, which leaves them zero again.
         const uint32_t g = (gen && ntiles <= kScanGenTiles) ? gen : 0u;
         if (!g && (!tmp_is_zero || gen)) (void)hipMemsetAsync(status, 0, (size_t)(ntiles + 2) * sizeof(unsigned long long), s);
-        if (popcount_input) VX_KL(k_scan_onepass<1>, dim3(ntiles), dim3(kOneBlock), 0, s, in, out, n, status, ntiles, total64, total_tag, sel1024, g, group16);
-        else VX_KL(k_scan_onepass<0>, dim3(ntiles), dim3(kOneBlock), 0, s, in, out, n, status, ntiles, total64, total_tag, sel1024, g, group16);
+        if (popcount_input) VX_KL(k_scan_onepass<1>, dim3(ntiles), dim3(kOneBlock), 0, s, in, out, n, status, ntiles, total64, a.total_tag, a.sel1024, g, a.group16);
+        else VX_KL(k_scan_onepass<0>, dim3(ntiles), dim3(kOneBlock), 0, s, in, out, n, status, ntiles, total64, a.total_tag, a.sel1024, g, a.group16);
         return true;
     }
     unsigned long long* sums = status;
@@ -602,7 +603,11 @@ bool launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d
     const bool aligned = ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
     if (!n_mip || !aligned || !gen || n_mip + ntiles > 0x7FFFFFFFull) {
         launch_build_mip2(m1, d1, d2, m2, s);
-        return launch_scan_u32(in, out, n, false, tmp, total64, s, true, total_tag, nullptr, gen);
+        ScanArgs a;
+        a.tmp_is_zero = true;
+        a.total_tag = total_tag;
+        a.gen = gen;
+        return launch_scan_u32(in, out, n, false, tmp, total64, s, a);
     }
     // generation mode as in launch_scan_u32, with the mip's workgroups counted among the resident ones
     const uint32_t g = n_mip + ntiles <= kScanGenTiles ? gen : 0u;
@@ -860,12 +865,11 @@ __global__ __launch_bounds__(256) void k_unit_blocks(const uint32_t* __restrict_
 
 // total_units: the host's figure -- or, for a launch queued before the host knows it, the most the table can describe (the kernel
 // reads the real total from unit_base[ntri] and never writes at or beyond cap_blocks)
-void launch_unit_blocks(const uint32_t* unit_base, uint32_t ntri, uint32_t total_units, uint32_t* block_tri, hipStream_t s, uint32_t cap_blocks,
-                        const unsigned long long* fwd_src, unsigned long long* fwd_dst, uint32_t* zero_hits, uint32_t zero_n)
+void launch_unit_blocks(const Units& u, uint32_t total_units, uint32_t* block_tri, hipStream_t s, const UnitBlockArgs& a)
 {
     const uint32_t nUB = (uint32_t)(((uint64_t)total_units + 63u) >> kUnitBlockLog2);
-    if (!ntri || !nUB) return;
-    VX_KL(k_unit_blocks, dim3((nUB + 255) / 256), dim3(256), 0, s, unit_base, ntri, block_tri, cap_blocks, fwd_src, fwd_dst, zero_hits, zero_n);
+    if (!u.ntri || !nUB) return;
+    VX_KL(k_unit_blocks, dim3((nUB + 255) / 256), dim3(256), 0, s, u.unit_base, u.ntri, block_tri, a.cap_blocks, a.fwd_src, a.fwd_dst, a.zero_hits, a.zero_n);
 }
 
 #ifdef VX_VOX_DEBUG
@@ -1189,19 +1193,18 @@ extern "C" int vx_debug_vox(unsigned long long* out8, int reset)
 namespace vx {
 #endif
 
-void launch_voxelize(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const GridParams& g, int sat_variant,
-                     uint32_t* words, uint64_t wb, uint64_t we, uint32_t* unit_mask, unsigned long long* set_calls, hipStream_t s, const uint32_t* ext,
-                     uint32_t* block_hits, bool tiled, const unsigned long long* units_total, uint32_t unit_cap)
+void launch_voxelize(const Units& u, const GridParams& g, int sat_variant, uint32_t* words, uint64_t wb, uint64_t we, uint32_t* unit_mask,
+                     unsigned long long* set_calls, hipStream_t s, const VoxelizeArgs& a)
 {
-    if (!ntri) return;
+    if (!u.ntri) return;
     const dim3 grid(kUnitBlocks), block(256);
-    const uint32_t ty = tiled ? (g.dim[1] + 3u) / 4u : 0u, xw = g.dim[0] / 32u;
+    const uint32_t ty = a.tiled ? (g.dim[1] + 3u) / 4u : 0u, xw = g.dim[0] / 32u;
     if (sat_variant == 0) {
-        if (unit_mask) VX_KL((k_voxelize<true, true>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, block_hits, ty, xw, units_total, unit_cap);
-        else VX_KL((k_voxelize<true, false>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, (uint32_t*)nullptr, ty, xw, units_total, unit_cap);
+        if (unit_mask) VX_KL((k_voxelize<true, true>), grid, block, 0, s, u.recs, u.unit_base, u.block_tri, u.ntri, g, words, wb, we, unit_mask, set_calls, u.ext, a.block_hits, ty, xw, a.units_total, a.unit_cap);
+        else VX_KL((k_voxelize<true, false>), grid, block, 0, s, u.recs, u.unit_base, u.block_tri, u.ntri, g, words, wb, we, unit_mask, set_calls, u.ext, (uint32_t*)nullptr, ty, xw, a.units_total, a.unit_cap);
     } else {
-        if (unit_mask) VX_KL((k_voxelize<false, true>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, block_hits, ty, xw, units_total, unit_cap);
-        else VX_KL((k_voxelize<false, false>), grid, block, 0, s, recs, unit_base, block_tri, ntri, g, words, wb, we, unit_mask, set_calls, ext, (uint32_t*)nullptr, ty, xw, units_total, unit_cap);
+        if (unit_mask) VX_KL((k_voxelize<false, true>), grid, block, 0, s, u.recs, u.unit_base, u.block_tri, u.ntri, g, words, wb, we, unit_mask, set_calls, u.ext, a.block_hits, ty, xw, a.units_total, a.unit_cap);
+        else VX_KL((k_voxelize<false, false>), grid, block, 0, s, u.recs, u.unit_base, u.block_tri, u.ntri, g, words, wb, we, unit_mask, set_calls, u.ext, (uint32_t*)nullptr, ty, xw, a.units_total, a.unit_cap);
     }
 }
 
@@ -1361,13 +1364,13 @@ __global__ __launch_bounds__(256) void k_emit_units(const TriRec* __restrict__ r
     });
 }
 
-void launch_emit_units(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const GridParams& g,
-                       const uint32_t* unit_mask, const uint32_t* block_base, vx_aabb* aabbs, uint64_t* morton, hipStream_t s, uint64_t cap, const uint32_t* ext)
+void launch_emit_units(const Units& u, const GridParams& g, const uint32_t* unit_mask, const uint32_t* block_base, vx_aabb* aabbs, uint64_t* morton, hipStream_t s,
+                       uint64_t cap)
 {
-    if (!ntri) return;
+    if (!u.ntri) return;
     // (bound by its stores, not by issue: 4096 workgroups -- several ragged rounds of the six a CU holds -- beat one even set: 45 us
     // with 1536, 41 with 2048, 39 with 4096)
-    VX_KL(k_emit_units, dim3(VX_EMIT_BLOCKS), dim3(256), 0, s, recs, unit_base, block_tri, ntri, g, unit_mask, block_base, aabbs, morton, cap, ext);
+    VX_KL(k_emit_units, dim3(VX_EMIT_BLOCKS), dim3(256), 0, s, u.recs, u.unit_base, u.block_tri, u.ntri, g, unit_mask, block_base, aabbs, morton, cap, u.ext);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1563,22 +1566,22 @@ __global__ __launch_bounds__(256) void k_mat_ids_calls(const TriRec* __restrict_
     });
 }
 
-void launch_mat_last(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const GridParams& g, const uint32_t* unit_mask,
-                     const uint32_t* words, const uint32_t* word_prefix, uint32_t* last_tri, uint8_t* tri_hit, hipStream_t s, const uint32_t* ext)
+void launch_mat_last(const Units& u, const GridParams& g, const uint32_t* unit_mask, const uint32_t* words, const uint32_t* word_prefix, uint32_t* last_tri,
+                     uint8_t* tri_hit, hipStream_t s)
 {
-    if (!ntri) return;
-    VX_KL(k_mat_last, dim3(kMaxBlocks), dim3(256), 0, s, recs, unit_base, block_tri, ntri, g, unit_mask, words, word_prefix, last_tri, tri_hit, ext);
+    if (!u.ntri) return;
+    VX_KL(k_mat_last, dim3(kMaxBlocks), dim3(256), 0, s, u.recs, u.unit_base, u.block_tri, u.ntri, g, unit_mask, words, word_prefix, last_tri, tri_hit, u.ext);
 }
 void launch_mat_ids(const uint32_t* last_tri, uint64_t n, const int32_t* tri_value, const int16_t* value_index, int16_t* out, hipStream_t s)
 {
     if (!n) return;
     VX_KL(k_mat_ids, dim3(grid_for(n, 256, kMaxBlocks)), dim3(256), 0, s, last_tri, n, tri_value, value_index, out);
 }
-void launch_mat_ids_calls(const TriRec* recs, const uint32_t* unit_base, const uint32_t* block_tri, uint32_t ntri, const uint32_t* unit_mask,
-                          const uint32_t* block_base, const int32_t* tri_value, const int16_t* value_index, int16_t* out, hipStream_t s)
+void launch_mat_ids_calls(const Units& u, const uint32_t* unit_mask, const uint32_t* block_base, const int32_t* tri_value, const int16_t* value_index, int16_t* out,
+                          hipStream_t s)
 {
-    if (!ntri) return;
-    VX_KL(k_mat_ids_calls, dim3(kMaxBlocks), dim3(256), 0, s, recs, unit_base, block_tri, ntri, unit_mask, block_base, tri_value, value_index, out);
+    if (!u.ntri) return;
+    VX_KL(k_mat_ids_calls, dim3(kMaxBlocks), dim3(256), 0, s, u.recs, u.unit_base, u.block_tri, u.ntri, unit_mask, block_base, tri_value, value_index, out);
 }
 
 __global__ void k_set_bit(uint32_t* words, uint64_t idx) { atomicOr(&words[idx >> 5], 1u << (idx & 31)); }

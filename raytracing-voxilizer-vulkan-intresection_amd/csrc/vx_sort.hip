@@ -202,13 +202,15 @@ int launch_sort_u64(uint64_t* keys_a, uint64_t* keys_b, uint64_t n, int bits, vo
     uint64_t* src = keys_a;
     uint64_t* dst = keys_b;
     int done = 0;
+    ScanArgs zero_tmp;
+    zero_tmp.tmp_is_zero = true;
     for (int p = 0; p < passes; ++p) {
         // spread the bits evenly: 33 bits = 9 + 8 + 8 + 8
         const int left = bits - done, nb = (left + (passes - p) - 1) / (passes - p);
         const uint32_t nd = 1u << nb;
         const uint64_t cells = (uint64_t)nd * ntiles;
         VX_KL(k_sort_hist, dim3(ntiles), dim3(kSortThreads), 0, s, (const uint64_t*)src, n, (uint32_t)done, nd, ntiles, H);
-        (void)launch_scan_u32(H, Hs, cells, false, scan_tmp, nullptr, s, /*tmp_is_zero=*/true);
+        (void)launch_scan_u32(H, Hs, cells, false, scan_tmp, nullptr, s, zero_tmp);
         switch (nb) {
 #define VX_SORT_CASE(B) case B: VX_KL((k_sort_scatter<B>), dim3(ntiles), dim3(kSortThreads), 0, s, (const uint64_t*)src, dst, n, (uint32_t)done, ntiles, (const uint32_t*)Hs); break;
             VX_SORT_CASE(1) VX_SORT_CASE(2) VX_SORT_CASE(3) VX_SORT_CASE(4) VX_SORT_CASE(5) VX_SORT_CASE(6) VX_SORT_CASE(7) VX_SORT_CASE(8) VX_SORT_CASE(9)

@@ -242,8 +242,7 @@ __global__ __launch_bounds__(256) void k_build_bricks3(uint32_t* __restrict__ wo
 }
 
 // Returns true when the level-1 mip was written by the brick kernel itself (and empty bricks were left unwritten).
-bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const uint32_t bdim[3], unsigned long long* bricks3, uint32_t* m1, hipStream_t s,
-                          const uint32_t* tiled, uint32_t* line_cnt, const unsigned long long* hit_counters, unsigned long long* hits_out, unsigned long long hits_tag)
+bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const uint32_t bdim[3], unsigned long long* bricks3, uint32_t* m1, hipStream_t s, const BricksArgs& a)
 {
     const uint64_t n = (uint64_t)bdim[0] * bdim[1] * bdim[2];
     if (!n) return false;
@@ -255,8 +254,8 @@ bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const ui
     if (nblk > 16384) nblk = 16384;
     const bool fused = (bdim[0] % 64u) == 0u && m1 != nullptr;
     VX_KL(k_build_bricks3, dim3((unsigned)nblk), dim3(256), 0, s, const_cast<uint32_t*>(words), dim[0], dim[1], dim[2], bdim[0], bdim[1], bdim[2], chunks_x, nwords, bricks3, n * 8ull,
-          fused ? m1 : nullptr, (dim[0] % 32u) == 0u ? tiled : nullptr, (tiled && (dim[0] % 512u) == 0u) ? line_cnt : nullptr, hits_out ? hit_counters : nullptr, hits_out,
-          hits_tag);
+          fused ? m1 : nullptr, (dim[0] % 32u) == 0u ? a.tiled : nullptr, (a.tiled && (dim[0] % 512u) == 0u) ? a.line_cnt : nullptr,
+          a.hits_out ? a.hit_counters : nullptr, a.hits_out, a.hits_tag);
     return fused;
 }
 
