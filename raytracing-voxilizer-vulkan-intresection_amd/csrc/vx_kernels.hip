@@ -876,6 +876,8 @@ void launch_unit_blocks(const Units& u, uint32_t total_units, uint32_t* block_tr
 // diagnostic build: wave cycles per phase of for_each_unit: [4] wait for outstanding memory operations at the top of a pass,
 // [0] issue of the next pass's staging, [1] unit search + record read, [2] the functor (SAT / emission), [3] rest
 __device__ unsigned long long g_vox_dbg[8];
+// k_voxelize's sweep: [0] voxel tests executed, [1] 64-lane sweep turns (the longest lane of every wave pass), [2] wave passes
+__device__ unsigned long long g_vox_sweep[3];
 #define VX_V_T(i) { const unsigned long long now_ = __builtin_readcyclecounter(); vdbg[i] += now_ - vlast; vlast = now_; }
 #define VX_V_SENT ++sent;
 #else
@@ -1033,6 +1035,15 @@ __device__ __forceinline__ void for_each_unit(const TriRec* __restrict__ recs, c
 #ifndef VX_VOX_MINWG
 #define VX_VOX_MINWG 1
 #endif
+// Rows of at least this many voxels sweep only the x interval their plane test allows (sat_row_interval); a pass without such a row
+// does not evaluate the rule at all.  Bench scene, steady-state rebuilds, us, Bool / Vec flavour, three runs each: without the rule
+// 61.5 61.4 61.8 / 66.5 66.3 66.8; 4: 57.4 54.5 54.5 / 59.0 58.5 59.2; 6: 55.1 54.5 54.9 / 61.2 59.9 59.3; 8: 54.7 55.2 54.9 / 58.8 59.5 60.7;
+// 12: 55.3 54.4 54.6 / 58.8 59.4 59.4; 16: 57.4 57.0 57.2 / 62.3 62.7 62.4 (the tilted walls' rows of 18-19 voxels are cut at multiples
+// of 32, and 16 leaves the shorter pieces on the full sweep).  4 to 12 do not differ by more than the runs do; 8 stays.
+#ifndef VX_INTERVAL_MIN_ROW
+#define VX_INTERVAL_MIN_ROW 8
+#endif
+constexpr uint32_t kIntervalMinRow = VX_INTERVAL_MIN_ROW;
 template <bool EPS, bool STORE_MASK>
 __global__ __launch_bounds__(256, VX_VOX_MINWG) void k_voxelize(const TriRec* __restrict__ recs, const uint32_t* __restrict__ unit_base,
                                                   const uint32_t* __restrict__ block_tri, uint32_t ntri, GridParams g, uint32_t* __restrict__ words,
@@ -1055,6 +1066,9 @@ __global__ __launch_bounds__(256, VX_VOX_MINWG) void k_voxelize(const TriRec* __
         uint32_t mask = 0;
         Unit w;
         w.xseg = w.y = w.z = 0u;
+#ifdef VX_VOX_DEBUG
+        uint32_t swept = 0;  // voxels this lane's sweep tests
+#endif
         if (valid) {
         w = decode_unit(r, t, rel, ext ? ext[t] : 0u);
         const float cy = cell_centre(g.org[1], g.vs, w.y), cz = cell_centre(g.org[2], g.vs, w.z);
@@ -1069,6 +1083,14 @@ __global__ __launch_bounds__(256, VX_VOX_MINWG) void k_voxelize(const TriRec* __
             // registers for no gain)
             // The x range is K2a's, trimmed with the box-axis test along x: the sweep leaves that test out (sat_row_test, BOXX).  (x + 0.5f
             // is carried as a float: exact below 2^23, one conversion less per voxel.)
+            // A long row of a tilted triangle meets the triangle's plane in one or two voxels: such rows sweep only the x interval that
+            // the plane test allows (sat_row_interval).  One wave-wide test keeps the passes of short rows on the path without it.
+            if (__any(w.x1 - w.x0 >= kIntervalMinRow)) {
+                if (w.x1 - w.x0 >= kIntervalMinRow) sat_row_interval(row, r.v, g.org[0], g.vs, g.half, w.x0, w.x1);
+            }
+#ifdef VX_VOX_DEBUG
+            swept = w.x1 - w.x0;
+#endif
             float xh = (float)w.x0 + 0.5f;
             uint32_t bit = 1u << (w.x0 & 31u);
             // EPS variant: when no lane's row can have an axis shorter than the threshold, the sweep without those checks.
@@ -1113,9 +1135,16 @@ __global__ __launch_bounds__(256, VX_VOX_MINWG) void k_voxelize(const TriRec* __
                 rem &= ~__ballot(key == k);
                 ++distinct;
             }
+            // voxel tests of the pass, and its sweep turns: the wave sweeps as long as its lane with the most voxels
+            const uint32_t tests = wave_sum_u32(swept);
+            uint32_t turns = swept;
+            for (int o = 32; o; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int)turns, o, 64); turns = other > turns ? other : turns; }
             if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) {
                 atomicAdd(&g_vox_dbg[6], (unsigned long long)__popcll(act));
                 atomicAdd(&g_vox_dbg[7], (unsigned long long)distinct);
+                atomicAdd(&g_vox_sweep[0], (unsigned long long)tests);
+                atomicAdd(&g_vox_sweep[1], (unsigned long long)turns);
+                atomicAdd(&g_vox_sweep[2], 1ull);
             }
         }
 #endif
@@ -1188,6 +1217,12 @@ extern "C" int vx_debug_vox(unsigned long long* out8, int reset)
 {
     if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(vx::g_vox_dbg), 8 * 8) != hipSuccess) return 1;
     if (reset) { unsigned long long z[8] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(vx::g_vox_dbg), z, 8 * 8) != hipSuccess) return 1; }
+    return 0;
+}
+extern "C" int vx_debug_vox_sweep(unsigned long long* out3, int reset)
+{
+    if (out3 && hipMemcpyFromSymbol(out3, HIP_SYMBOL(vx::g_vox_sweep), 3 * 8) != hipSuccess) return 1;
+    if (reset) { unsigned long long z[3] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(vx::g_vox_sweep), z, 3 * 8) != hipSuccess) return 1; }
     return 0;
 }
 namespace vx {

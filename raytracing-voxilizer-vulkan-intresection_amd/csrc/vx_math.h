@@ -165,6 +165,53 @@ VX_HD bool sat_row_all_live(const SatRow& r)
     return (fabsf(r.e0y) >= t) & (fabsf(r.e0z) >= t) & (fabsf(r.e1y) >= t) & (fabsf(r.e1z) >= t) & (fabsf(r.e2y) >= t) & (fabsf(r.e2z) >= t) & (fabsf(r.nx) >= t);
 }
 
+// The x interval that a row's plane test allows (DESIGN.md, K2 notes, "Row interval": derivation and constants).  Narrows [x0, x1) to
+// [x0', x1') such that every x of [x0, x1) for which sat_row_test<EPS, false, ...>(r, v, cell_centre(org, vs, x), h) is true lies in
+// [x0', x1'), for both variants; returns false and leaves the range as it is whenever it cannot prove that.
+// Over a row only cx changes: with E0 = v3 - v0, E1 = v6 - v3, NY = e0z E1 - e1z E0, NZ = E0 e1y - E1 e0y (reals) the real-valued plane
+// test reads |nx (v0 - cx) + Kp| <= RR with Kp = NY p0y + NZ p0z, RR = h (|nx| + |NY| + |NZ|).  The sweep's float s and rr differ from
+// that by at most D (the roundings of p, e, the two cross-product components, the three products, the two sums, twice over, and every
+// underflow); this function's own Kp and RR by no more, so with W = RR + 4 D a voxel that passes has cx - v0 in [Kp - W, Kp + W] / nx.
+// E bounds, in voxels, what the division, the sum with v0, cell_centre's two roundings and the conversion to an index add; with
+// E <= 1/2 the indices are ceil(tl - 1/2) and floor(th + 1/2), and the range is widened by one more voxel on each side.
+// |nx| >= 1e-8 makes the EPS variant's plane test live whatever x is (fl(|nx| + |ny| + |nz|) >= |nx|), so the test assumed is executed.
+VX_HD bool sat_row_interval(const SatRow& r, const float v[9], float org, float vs, float h, uint32_t& x0, uint32_t& x1)
+{
+    const float u = 5.9604645e-8f;  // 2^-24
+    const float anx = fabsf(r.nx);
+    if (!(anx >= 1e-8f) || !(vs > 0.0f) || !(x1 > x0)) return false;
+    const float c_lo = cell_centre(org, vs, x0), c_hi = cell_centre(org, vs, x1 - 1u);
+    const float M = fmaxf(max3(fabsf(v[0] - c_lo), fabsf(v[3] - c_lo), fabsf(v[6] - c_lo)), max3(fabsf(v[0] - c_hi), fabsf(v[3] - c_hi), fabsf(v[6] - c_hi)));
+    const float Ly = fmaxf(fabsf(r.e0y), fabsf(r.e1y)), Lz = fmaxf(fabsf(r.e0z), fabsf(r.e1z));
+    const float ay = fabsf(r.p0y) + h, az = fabsf(r.p0z) + h;
+    const float B = 8.0f * anx * (M + h) + 64.0f * M * (Lz * ay + Ly * az);
+    const float D = u * B + 1e-37f * (2.0f + ay + az);
+    const float E0 = v[3] - v[0], E1 = v[6] - v[3];
+    const float NY = r.e0z * E1 - r.e1z * E0;
+    const float NZ = E0 * r.e1y - E1 * r.e0y;
+    const float Kp = NY * r.p0y + NZ * r.p0z;
+    const float W = ((h * anx + h * fabsf(NY)) + h * fabsf(NZ)) + 4.0f * D;
+    if (!(4.0f * D <= 0.25f * (anx * vs))) return false;  // (false for a NaN as well)
+    const float rn = 1.0f / r.nx, rvs = 1.0f / vs;   // (two divisions instead of five: one more rounding each, inside E's factors)
+    const float qa = (Kp - W) * rn, qb = (Kp + W) * rn;
+    const float qlo = fminf(qa, qb), qhi = fmaxf(qa, qb);
+    const float tl = ((v[0] + qlo) - org) * rvs - 0.5f, th = ((v[0] + qhi) - org) * rvs - 0.5f;
+    const float fx0 = (float)x0, fx1 = (float)x1;   // exact: an axis has at most 2^21 cells
+    const float A = 2.0f * (fabsf(qlo) + fabsf(qhi)) + fabsf(v[0]) + fabsf(org) + fx1 * vs + fmaxf(fabsf(c_lo), fabsf(c_hi));
+    const float E = (2.0f * u) * (A * rvs) + (8.0f * u) * ((fabsf(tl) + fabsf(th)) + 2.0f);
+    if (!(E <= 0.5f) || !(B < 3.0e38f)) return false;  // (a NaN or an infinity anywhere above ends here: E or B is then not finite)
+    // clamped as floats, so that every conversion below is in range on the host and on the device alike
+    const float tlc = fminf(fmaxf(tl - 0.5f, fx0), fx1 + 1.0f);
+    const float thc = fminf(fmaxf(th + 0.5f, fx0 - 2.0f), fx1);
+    const uint32_t i = (uint32_t)ceilf(tlc);           // x >= tl - E: x >= ceil(tl - 1/2)
+    const int j = (int)floorf(thc) + 2;                // x <= th + E: x < floor(th + 1/2) + 1; j >= x0 >= 0
+    const uint32_t n0 = i > x0 ? i - 1u : x0;
+    const uint32_t n1 = (uint32_t)j < x1 ? (uint32_t)j : x1;
+    x0 = n0;
+    x1 = n1 > n0 ? n1 : n0;
+    return true;
+}
+
 // Whole test for one voxel (used by host-side checks and single-voxel paths)
 template <bool EPS>
 VX_HD bool tri_box_overlap(const float v[9], float cx, float cy, float cz, float h)
