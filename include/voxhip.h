@@ -288,6 +288,53 @@ vx_status vx_grid_distance_sq_device(const vx_grid* g, uint32_t flags, uint32_t*
 vx_status vx_grid_distance_sq(const vx_grid* g, uint32_t flags, uint32_t* host_out, uint64_t capacity);
 vx_status vx_grid_sdf_device(const vx_grid* g, float* dev_out, uint64_t capacity);
 vx_status vx_grid_sdf(const vx_grid* g, float* host_out, uint64_t capacity);
+/* Binary morphology of the bitmask with the digital Euclidean ball (scipy.ndimage.binary_dilation / _erosion / _opening / _closing).
+ * M = the occupied cells of the bitmask as it stands when the call is queued (after the last build, setVoxel, fill_interior, or an external
+ * write followed by vx_grid_refresh).  radius_sq = r2 is a squared radius in cells, R = floor(sqrt(r2)), and the structuring element is
+ *   B(r2) = {b in Z^3 : bx^2 + by^2 + bz^2 <= r2}:  B(0) the single cell, B(1) the 6-, B(2) the 18-, B(3) the 26-neighbourhood.
+ * ONE rule for the border: every operation is the operation on the infinite lattice Z^3, in which every cell outside the grid is empty,
+ * and its result is restricted to the grid.  There are no border flags.  c ranges over the cells of the grid:
+ *   VX_MORPH_DILATE   {c : some b in B has c + b in M}  =  {c : D_out(c) <= r2}
+ *   VX_MORPH_ERODE    {c : every b in B has c + b in M}  =  {c : D_in(c) > r2, and R <= x <= X-1-R, the same for y and z}: a cell nearer
+ *                     than R to the border always loses, since B holds (+-R, 0, 0), (0, +-R, 0), (0, 0, +-R)
+ *                     (= binary_erosion(M, B, border_value=0))
+ *   VX_MORPH_OPEN     the dilation of the erosion; a subset of M
+ *   VX_MORPH_CLOSE    {c : every b in B has c + b in D}, D = the dilation of M on Z^3 WITHOUT restriction (cells outside the grid included):
+ *                     pad M with R empty cells on every side, dilate, erode, crop.  Extensive (M is a subset) and idempotent;
+ *                     binary_closing on the unpadded array is neither at the border.
+ * A plain CLOSE does not seal a hole in a thin wall -- the cap of a ball inside the hole pokes through the wall, so the hole's cells
+ * survive the erosion.  vx_grid_seal is for that:
+ *   seal(M, r2) = M | crop(erode(fill(dilate(pad(M, R + 1))))): pad with R + 1 empty cells on every side (the dilated body is then
+ *                     surrounded by an empty shell), dilate, fill the interior exactly as VX_VOXELIZE_SOLID defines it
+ *                     (binary_fill_holes) on the padded grid, erode, crop, OR with M.  r2 = 0 is M | H, the plain solid grid.
+ * Integer bit operations only: every result is bit-exact.  R <= vx_morph_bit_radius() runs on mask words, 32 cells at a time; larger radii
+ * threshold the distance fields above (and inherit their cost and their limit).
+ * The mask variants return the result as a bitmask in the grid's own word layout (num_words words, padding bits past X*Y*Z zero) and follow
+ * the distance fields' rules: they only read the bitmask; nothing a reader of g can see changes; a pending VX_VOXELIZE_LIST_ASYNC emission
+ * is neither forced nor dropped; scratch stays on the handle, so a repeated call at the same dimensions and radius allocates nothing;
+ * _device queues on the grid's stream and returns without a host wait.  Checks, in this order, every failure writing nothing:
+ *   1. a NULL grid or buffer, an op above 3, radius_sq = 0xFFFFFFFF, or a dev_words range that overlaps the grid's own mask:
+ *      VX_ERR_INVALID_ARG;
+ *   2. a grid of 0 cells: VX_OK, nothing written;
+ *   3. a working domain (the grid; for CLOSE the grid padded by R, for seal by R + 1) of more than 2^21 cells on an axis or more than
+ *      2^37 cells, or, on the distance-field path, beyond the distance fields' limit on (X-1)^2 + (Y-1)^2 + (Z-1)^2: VX_ERR_CAPACITY
+ *      before anything is queued;
+ *   4. capacity_words < num_words: VX_ERR_CAPACITY.
+ * The grid variants return a NEW handle with the kind, dimensions, voxel size, origin, device and stream of src, src's bbox fields and
+ * triangles = 0; everything else is as if vx_grid_create were followed by vx_grid_set_voxel on every result cell in ascending voxel index:
+ * set_calls = occupied = the popcount, Bool / AABBstruct lists ascend by voxel index, a Vec list holds one cell_aabb record per cell in
+ * ascending index (vx_grid_bytes 24 x that), no materials.  Rays, frames, surface, components, distance fields, fill_interior and morph work
+ * on it like on any grid.  vx_grid_interior(out) is 0 after vx_grid_morph and the number of cells the seal added to M after vx_grid_seal.
+ * src is unchanged (bitmask, list, counts), also when it was built with VX_VOXELIZE_LIST_ASYNC. */
+#define VX_MORPH_DILATE 0u
+#define VX_MORPH_ERODE  1u
+#define VX_MORPH_OPEN   2u
+#define VX_MORPH_CLOSE  3u
+vx_status vx_grid_morph_device(const vx_grid* g, uint32_t op, uint32_t radius_sq, uint32_t* dev_words, uint64_t capacity_words);
+vx_status vx_grid_morph_mask(const vx_grid* g, uint32_t op, uint32_t radius_sq, uint32_t* host_words, uint64_t capacity_words);
+vx_status vx_grid_morph(const vx_grid* src, uint32_t op, uint32_t radius_sq, vx_grid** out);
+vx_status vx_grid_seal(const vx_grid* src, uint32_t radius_sq, vx_grid** out);
+uint32_t vx_morph_bit_radius(void); /* the largest R the bit-level path takes; above it the distance-field path runs */
 /* The boundary mesh of the bitmask M (as it stands when the call is queued, as for the distance fields).  Cell c = (x, y, z) in M has a face
  * in direction d = 0..5 (-X, +X, -Y, +Y, -Z, +Z) when c + e_d is outside the grid or not in M.  Lattice points (i, j, k), 0 <= i <= X,
  * 0 <= j <= Y, 0 <= k <= Z, index i + (X+1)*(j + (Y+1)*k), lie per axis at org + ((float)i + 0.5f)*vs - half (f32, no contraction: the minimum

@@ -258,3 +258,32 @@ protected:
         vxdetail::check(vx_grid_set_voxel(m_grid.get(), x, y, z));
     }
 };
+
+// Morphology of the occupancy with the Euclidean ball of squared radius r2 in cells (vx_grid_morph / vx_grid_seal; r2 = 1, 2, 3: the 6-, 18-,
+// 26-neighbourhood).  Every method returns a NEW grid of the same class -- dimensions, voxel size and origin kept, no materials; cells outside
+// the grid count as empty.  dilated / eroded grow and shrink; opened drops specks; closed fills gaps narrower than the ball; sealed adds the
+// interior that appears once holes up to the ball's size are closed (dilate, fill, erode) -- the solid grid of a mesh that is not watertight.
+// The three grid classes derive from this layer.
+template <class Derived, typename T>
+class VoxelGridMorph : public VoxelGrid<T>
+{
+protected:
+    using VoxelGrid<T>::VoxelGrid;
+
+    Derived morphed(int op, uint32_t r2) const
+    {
+        vx_grid* g = nullptr;
+        vxdetail::check(op < 0 ? vx_grid_seal(this->m_grid.get(), r2, &g) : vx_grid_morph(this->m_grid.get(), (uint32_t)op, r2, &g));
+        vxdetail::GridHandle h = vxdetail::adopt(g);
+        vx_grid_desc d;
+        vxdetail::check(vx_grid_describe(g, &d));
+        return Derived(std::move(h), d);
+    }
+
+public:
+    Derived dilated(uint32_t r2) const { return morphed((int)VX_MORPH_DILATE, r2); }
+    Derived eroded(uint32_t r2) const { return morphed((int)VX_MORPH_ERODE, r2); }
+    Derived opened(uint32_t r2) const { return morphed((int)VX_MORPH_OPEN, r2); }
+    Derived closed(uint32_t r2) const { return morphed((int)VX_MORPH_CLOSE, r2); }
+    Derived sealed(uint32_t r2) const { return morphed(-1, r2); }
+};

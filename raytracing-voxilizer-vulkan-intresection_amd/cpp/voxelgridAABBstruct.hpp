@@ -15,14 +15,14 @@ struct AabbInternal
 };
 }  // namespace
 
-class VoxelGridAABBstruct final : public VoxelGrid<AabbInternal>
+class VoxelGridAABBstruct final : public VoxelGridMorph<VoxelGridAABBstruct, AabbInternal>
 {
 public:
     using VoxelType = AabbInternal;
 
     VoxelGridAABBstruct(size_t x, size_t y, size_t z, float voxelSize, vec3 org = {0.f, 0.f, 0.f})
-        : VoxelGrid(VX_GRID_AABBSTRUCT, x, y, z, voxelSize, org) {}
-    VoxelGridAABBstruct(vxdetail::GridHandle h, const vx_grid_desc& d) : VoxelGrid(std::move(h), d) {}
+        : VoxelGridMorph(VX_GRID_AABBSTRUCT, x, y, z, voxelSize, org) {}
+    VoxelGridAABBstruct(vxdetail::GridHandle h, const vx_grid_desc& d) : VoxelGridMorph(std::move(h), d) {}
 
     std::vector<Aabb> getAabbs() const noexcept override
     {

@@ -3,13 +3,13 @@
 #pragma once
 #include "voxelgrid.hpp"
 
-class VoxelGridBool final : public VoxelGrid<unsigned int>
+class VoxelGridBool final : public VoxelGridMorph<VoxelGridBool, unsigned int>
 {
 public:
     using VoxelType = unsigned int;
 
-    VoxelGridBool(size_t x, size_t y, size_t z, float voxelSize, vec3 org) : VoxelGrid(VX_GRID_BOOL, x, y, z, voxelSize, org) {}
-    VoxelGridBool(vxdetail::GridHandle h, const vx_grid_desc& d) : VoxelGrid(std::move(h), d) {}
+    VoxelGridBool(size_t x, size_t y, size_t z, float voxelSize, vec3 org) : VoxelGridMorph(VX_GRID_BOOL, x, y, z, voxelSize, org) {}
+    VoxelGridBool(vxdetail::GridHandle h, const vx_grid_desc& d) : VoxelGridMorph(std::move(h), d) {}
 
     // ascending word, ascending bit (voxelgridBool.cpp:18-52)
     std::vector<Aabb> getAabbs() const noexcept override

@@ -3,13 +3,13 @@
 #pragma once
 #include "voxelgrid.hpp"
 
-class VoxelGridVec final : public VoxelGrid<Aabb>
+class VoxelGridVec final : public VoxelGridMorph<VoxelGridVec, Aabb>
 {
 public:
     using VoxelType = Aabb;
 
-    VoxelGridVec(size_t x, size_t y, size_t z, float voxelSize, vec3 org) : VoxelGrid(VX_GRID_VEC, x, y, z, voxelSize, org) {}
-    VoxelGridVec(vxdetail::GridHandle h, const vx_grid_desc& d) : VoxelGrid(std::move(h), d) {}
+    VoxelGridVec(size_t x, size_t y, size_t z, float voxelSize, vec3 org) : VoxelGridMorph(VX_GRID_VEC, x, y, z, voxelSize, org) {}
+    VoxelGridVec(vxdetail::GridHandle h, const vx_grid_desc& d) : VoxelGridMorph(std::move(h), d) {}
 
     std::vector<Aabb> getAabbs() const noexcept override
     {

@@ -37,6 +37,11 @@
 //   --solid                             solid voxelization (VX_VOXELIZE_SOLID): the enclosed empty cells are filled after the triangle loop;
 //                                       one more line gives their count.  bool / aabbstruct / vec with their options; not with --grid octree,
 //                                       --gpus N > 1 or --bench
+//   --morph OP:RADIUS                   the built grid is replaced by its morphology (vx_grid_morph) before every output that reads it (--dump,
+//                                       --sdf, --surface, --components, --xray, --render): OP dilate|erode|open|close, RADIUS in cells (may be
+//                                       fractional: radius_sq = floor(RADIUS^2)); one more line, morph: OP r2=.. occupied A -> B
+//   --seal RADIUS                       the same with vx_grid_seal: the grid plus the interior behind holes up to the ball's size; bool /
+//                                       aabbstruct / vec; neither with --grid octree, --bench or --materials (the result has none)
 //   --sdf FILE                          the grid's signed distance field (vx_grid_sdf: voxel size x Euclidean distance to the nearest occupied
 //                                       cell, negative inside by the distance to the nearest empty one) as raw little-endian f32, x fastest,
 //                                       X*Y*Z values; one line gives the dims and the finite min / max.  bool / aabbstruct / vec, with or
@@ -454,6 +459,45 @@ void write_mesh_xray(const vx_bvh* bvh, const std::string& file, uint32_t W, uin
     write_counts_pgm(count, file, W, H, "triangle");
 }
 
+// --morph OP:RADIUS / --seal RADIUS: op 0..3 = VX_MORPH_*, 4 = seal, -1 = none
+struct MorphOpt {
+    int op = -1;
+    uint32_t r2 = 0;
+};
+MorphOpt g_morph;
+
+bool parse_radius(const char* s, uint32_t* r2)
+{
+    char* end = nullptr;
+    const double r = std::strtod(s, &end);
+    if (end == s || *end || !(r >= 0.0) || !(r * r < 4294967295.0)) return false;
+    *r2 = (uint32_t)std::floor(r * r);
+    return true;
+}
+
+bool parse_morph(const char* s, MorphOpt* m)
+{
+    static const char* names[4] = {"dilate", "erode", "open", "close"};
+    const char* colon = std::strchr(s, ':');
+    if (!colon) return false;
+    for (int k = 0; k < 4; ++k)
+        if (std::string(s, colon) == names[k]) { m->op = k; return parse_radius(colon + 1, &m->r2); }
+    return false;
+}
+
+template <class T>
+T apply_morph(const T& g)
+{
+    static const char* names[5] = {"dilate", "erode", "open", "close", "seal"};
+    vx_grid_desc a, b;
+    vxdetail::check(vx_grid_describe(g.handle(), &a));
+    T out = g_morph.op == 4 ? g.sealed(g_morph.r2)
+            : g_morph.op == 0 ? g.dilated(g_morph.r2) : g_morph.op == 1 ? g.eroded(g_morph.r2) : g_morph.op == 2 ? g.opened(g_morph.r2) : g.closed(g_morph.r2);
+    vxdetail::check(vx_grid_describe(out.handle(), &b));
+    std::printf("[voxhip] morph: %s r2=%u occupied %llu -> %llu\n", names[g_morph.op], g_morph.r2, (unsigned long long)a.occupied, (unsigned long long)b.occupied);
+    return out;
+}
+
 template <class T, bool P>
 int run_grid(const std::string& path, float vs, const std::string& dumpFile, const char* label, const std::string& renderFile = "",
              uint32_t rw = 1280, uint32_t rh = 720, bool materials = false, const std::string& matDump = "", const std::string& cameraDump = "",
@@ -466,13 +510,14 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
     voxelBuilder.withDevices(devices);
     if (devices.size() > 1) std::printf("[voxhip] build sharded over %zu ranks (first device %d)\n", devices.size(), devices[0]);
     const auto t0 = Clock::now();
-    T vox = voxelBuilder.buildVoxelGrid(vs);
+    T built = voxelBuilder.buildVoxelGrid(vs);
     const auto t1 = Clock::now();
     if (solid) {
         uint64_t interior = 0;
-        vxdetail::check(vx_grid_interior(vox.handle(), &interior));
+        vxdetail::check(vx_grid_interior(built.handle(), &interior));
         std::printf("[voxhip] solid: %llu interior voxels filled\n", (unsigned long long)interior);
     }
+    T vox = g_morph.op < 0 ? built : apply_morph(built);  // (every output below reads the morphed grid)
     const std::vector<Aabb> aabbs = vox.getAabbs();
     const auto t2 = Clock::now();
     const auto msBuild = std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();
@@ -529,7 +574,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
                      argv[0]);
         return 2;
     }
@@ -556,6 +601,8 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--instances") && i + 1 < argc) instFile = argv[++i];
         else if (!std::strcmp(argv[i], "--attributes")) attributes = true;
         else if (!std::strcmp(argv[i], "--solid")) solid = true;
+        else if (!std::strcmp(argv[i], "--morph") && i + 1 < argc) { if (!parse_morph(argv[++i], &g_morph)) { std::fprintf(stderr, "bad --morph '%s': OP:RADIUS with OP dilate|erode|open|close and RADIUS >= 0 in cells\n", argv[i]); return 2; } }
+        else if (!std::strcmp(argv[i], "--seal") && i + 1 < argc) { g_morph.op = 4; if (!parse_radius(argv[++i], &g_morph.r2)) { std::fprintf(stderr, "bad --seal '%s': a radius >= 0 in cells\n", argv[i]); return 2; } }
         else if (!std::strcmp(argv[i], "--sdf") && i + 1 < argc) sdfFile = argv[++i];
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
         else if (!std::strcmp(argv[i], "--components") && i + 1 < argc) componentsFile = argv[++i];
@@ -587,6 +634,10 @@ int main(int argc, char** argv)
     }
     if (solid && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
         std::fprintf(stderr, "--solid fills the interior of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (g_morph.op >= 0 && (grid == "octree" || benchRuns > 0 || materials)) {
+        std::fprintf(stderr, "--morph / --seal replace a bool, aabbstruct or vec grid by its morphology, which carries no materials: not with --grid octree, --bench or --materials\n");
         return 2;
     }
     if (!sdfFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {

@@ -520,6 +520,9 @@ struct vx_grid : Home {
     DevBuf solid_m{this}, solid_e{this}, solid_h{this}, solid_pre{this}, solid_agg{this} /*the column scans' per-chunk words*/;
     // distance fields (vx_distance.hip): the envelopes' stacks, and the field itself for the host variants
     DevBuf dist_stk{this}, dist_out{this};
+    // morphology (vx_morph.hip): two row-aligned masks (a stage's output, the next one's input), a padded or intermediate mask in the
+    // reference's layout, the distance-field path's field and the host variant's result
+    DevBuf morph_a{this}, morph_b{this}, morph_p{this}, morph_d{this}, morph_out{this};
     // surface mesh (vx_surface.hip): triangles per mask word and their scan, the used lattice points and their scan, the host variant's arrays
     DevBuf surf_cnt{this}, surf_tpre{this}, surf_cm{this}, surf_vpre{this}, surf_out{this};
     // connected components (vx_components.hip): the root bitmask and its scan, the host variants' labels, the statistics
@@ -2368,6 +2371,283 @@ vx_status vx_grid_sdf(const vx_grid* gc, float* host_out, uint64_t capacity)
     DeviceGuard dg(g->device);
     return distance_host(g, 2, host_out, n);
 }
+
+// Morphology (vx_morph.hip).  Every operation is a chain of stages on the grid's stream; the scratch of all of them lives on the handle
+// whose mask is read.  Bit path (R <= vx_morph_bit_radius()): k_morph_ball stages, row-aligned in between, packed at the end.  Distance-field
+// path: launch_distance on a mask in the reference's layout (padded physically where the operation pads), thresholded into a mask again.
+constexpr uint32_t kMorphSeal = 4u;  // (internal: vx_grid_seal's plan)
+
+struct MorphPlan {
+    uint32_t R = 0, pad = 0;
+    bool bit = true;
+    uint32_t wdim[3] = {0, 0, 0};  // the working domain: the grid, padded for CLOSE (R) and seal (R + 1)
+};
+
+static uint32_t morph_isqrt(uint32_t v)
+{
+    uint32_t r = (uint32_t)std::sqrt((double)v);
+    while ((uint64_t)r * r > v) --r;
+    while ((uint64_t)(r + 1) * (r + 1) <= v) ++r;
+    return r;
+}
+
+static vx_status morph_plan(const vx_grid* g, uint32_t op, uint32_t r2, MorphPlan* p)
+{
+    p->R = morph_isqrt(r2);
+    p->bit = p->R <= vx::kMorphBitRadius;
+    p->pad = op == VX_MORPH_CLOSE ? p->R : (op == kMorphSeal ? p->R + 1u : 0u);
+    uint64_t cells = 1, dsq = 0;
+    for (int a = 0; a < 3; ++a) {
+        const uint64_t d = (uint64_t)g->g.dim[a] + 2ull * p->pad;
+        if (d > vx::kMaxDim) return fail(VX_ERR_CAPACITY, "morphology: the working domain exceeds 2^21 cells on an axis");
+        p->wdim[a] = (uint32_t)d;
+        cells *= d;
+        dsq += (d - 1) * (d - 1);
+    }
+    if (cells > kMaxVoxels) return fail(VX_ERR_CAPACITY, "morphology: the working domain exceeds 2^37 cells");
+    if (!p->bit && dsq > 0xFFFFFFFEull) return fail(VX_ERR_CAPACITY, "morphology: the distance-field path needs (X-1)^2 + (Y-1)^2 + (Z-1)^2 <= 0xFFFFFFFE");
+    return VX_OK;
+}
+
+static vx::MorphDom morph_dom(const uint32_t d[3], bool aligned)
+{
+    vx::MorphDom m;
+    for (int a = 0; a < 3; ++a) m.dim[a] = d[a];
+    m.stride = aligned ? 32ull * ((d[0] + 31u) / 32u) : d[0];
+    return m;
+}
+
+static uint64_t morph_words(const uint32_t d[3]) { return ((uint64_t)d[0] * d[1] * d[2] + 31u) / 32u; }
+
+// one ball stage whose result is wanted in the reference's layout (odim cells, in dst): straight into dst where the two layouts coincide and
+// nothing is OR-ed in, through `stage` and the pack kernel otherwise
+static vx_status morph_ball_ref(vx_grid* sc, DevBuf& stage, const uint32_t* src, const vx::MorphDom& in, const uint32_t odim[3], int32_t shift, uint32_t r2,
+                                uint32_t flags, const uint32_t* orw, uint32_t* dst)
+{
+    if (odim[0] % 32u == 0u && !orw) {
+        vx::launch_morph_ball(src, in, dst, odim, shift, r2, flags, sc->stream);
+        return VX_OK;
+    }
+    VX_HIP(stage.ensure((size_t)vx::morph_aligned_words(odim) * 4 + 16));
+    vx::launch_morph_ball(src, in, stage.as<uint32_t>(), odim, shift, r2, flags, sc->stream);
+    vx::launch_morph_pack(stage.as<uint32_t>(), odim, orw, dst, sc->stream);
+    return VX_OK;
+}
+
+// the squared distance field (mode 0: to the occupied cells, 1: to the empty ones) of a mask in the reference's layout -- two spare words
+// behind it, as the grid's own has -- into sc->morph_d
+static vx_status morph_field(vx_grid* sc, const uint32_t* mask, const uint32_t d[3], int mode)
+{
+    VX_HIP(sc->morph_d.ensure((size_t)d[0] * d[1] * d[2] * 4 + 16));
+    VX_HIP(sc->dist_stk.ensure((size_t)vx::distance_stack_entries(d, false) * 8));
+    vx::launch_distance(mask, d, mode, 1.0f, sc->morph_d.as<uint32_t>(), sc->dist_stk.as<uint2>(), sc->stream);
+    return VX_OK;
+}
+
+// op 0..3 of the mask src (the reference's layout, dim cells, two spare words behind it) into dst (the same layout); scratch and stream: sc
+static vx_status morph_run(vx_grid* sc, const uint32_t* src, const uint32_t dim[3], uint32_t op, uint32_t r2, const MorphPlan& p, uint32_t* dst)
+{
+    hipStream_t s = sc->stream;
+    const vx::MorphDom gd = morph_dom(dim, false);
+    const uint32_t both = vx::kMorphInvIn | vx::kMorphInvOut;
+    const int32_t R = (int32_t)p.R;
+    if (p.bit) {
+        switch (op) {
+        case VX_MORPH_DILATE: return morph_ball_ref(sc, sc->morph_b, src, gd, dim, 0, r2, 0u, nullptr, dst);
+        case VX_MORPH_ERODE: return morph_ball_ref(sc, sc->morph_b, src, gd, dim, 0, r2, both, nullptr, dst);
+        case VX_MORPH_OPEN:
+            VX_HIP(sc->morph_a.ensure((size_t)vx::morph_aligned_words(dim) * 4 + 16));
+            vx::launch_morph_ball(src, gd, sc->morph_a.as<uint32_t>(), dim, 0, r2, both, s);
+            return morph_ball_ref(sc, sc->morph_b, sc->morph_a.as<uint32_t>(), morph_dom(dim, true), dim, 0, r2, 0u, nullptr, dst);
+        default:  // CLOSE: dilate into the padded domain, erode back out of it
+            VX_HIP(sc->morph_a.ensure((size_t)vx::morph_aligned_words(p.wdim) * 4 + 16));
+            vx::launch_morph_ball(src, gd, sc->morph_a.as<uint32_t>(), p.wdim, -R, r2, 0u, s);
+            return morph_ball_ref(sc, sc->morph_b, sc->morph_a.as<uint32_t>(), morph_dom(p.wdim, true), dim, R, r2, both, nullptr, dst);
+        }
+    }
+    switch (op) {
+    case VX_MORPH_DILATE:
+        VX_TRY(morph_field(sc, src, dim, 0));
+        vx::launch_morph_thresh(sc->morph_d.as<uint32_t>(), dim, r2, false, dst, s);
+        return VX_OK;
+    case VX_MORPH_ERODE:
+        VX_TRY(morph_field(sc, src, dim, 1));
+        vx::launch_morph_thresh(sc->morph_d.as<uint32_t>(), dim, r2, true, dst, s);
+        return VX_OK;
+    case VX_MORPH_OPEN: {
+        VX_HIP(sc->morph_p.ensure((size_t)(morph_words(dim) + 2) * 4));
+        uint32_t* e = sc->morph_p.as<uint32_t>();
+        VX_TRY(morph_field(sc, src, dim, 1));
+        vx::launch_morph_thresh(sc->morph_d.as<uint32_t>(), dim, r2, true, e, s);
+        VX_TRY(morph_field(sc, e, dim, 0));
+        vx::launch_morph_thresh(sc->morph_d.as<uint32_t>(), dim, r2, false, dst, s);
+        return VX_OK;
+    }
+    default: {  // CLOSE on a physically padded copy; every stage is complete on the stream before the next overwrites what it read
+        VX_HIP(sc->morph_p.ensure((size_t)(morph_words(p.wdim) + 2) * 4));
+        uint32_t* pm = sc->morph_p.as<uint32_t>();
+        VX_TRY(morph_ball_ref(sc, sc->morph_a, src, gd, p.wdim, -R, 0u, 0u, nullptr, pm));
+        VX_TRY(morph_field(sc, pm, p.wdim, 0));
+        vx::launch_morph_thresh(sc->morph_d.as<uint32_t>(), p.wdim, r2, false, pm, s);
+        VX_TRY(morph_field(sc, pm, p.wdim, 1));
+        vx::launch_morph_thresh(sc->morph_d.as<uint32_t>(), p.wdim, r2, true, pm, s);
+        return morph_ball_ref(sc, sc->morph_a, pm, morph_dom(p.wdim, false), dim, R, 0u, 0u, nullptr, dst);
+    }
+    }
+}
+
+// a new grid like src (kind, cells, voxel size, origin, device, stream) with an all-zero mask
+static vx_status morph_new_grid(const vx_grid* src, int kind, const uint32_t dim[3], vx_grid** out)
+{
+    VX_TRY(need_device(src->device));
+    vx_grid* g = new vx_grid();
+    g->kind = kind;
+    g->device = src->device;
+    g->set_stream(src->stream);
+    const uint64_t d[3] = {dim[0], dim[1], dim[2]};
+    fill_params(g->g, src->g.org, src->g.vs, d);
+    DeviceGuard dg(g->device);
+    const vx_status s = init_grid_storage(g);
+    if (s != VX_OK) { delete g; return s; }
+    *out = g;
+    return VX_OK;
+}
+
+// seal(M, r2) = M | crop(erode(fill(dilate(pad(M, R + 1))))) into dst; the fill runs on an internal grid handle of the padded domain
+static vx_status morph_seal_run(vx_grid* g, uint32_t r2, const MorphPlan& p, uint32_t* dst)
+{
+    vx_grid* t = nullptr;
+    VX_TRY(morph_new_grid(g, VX_GRID_BOOL, p.wdim, &t));
+    hipStream_t s = g->stream;
+    const uint32_t* dim = g->g.dim;
+    const vx::MorphDom gd = morph_dom(dim, false), pd = morph_dom(p.wdim, false);
+    const uint32_t both = vx::kMorphInvIn | vx::kMorphInvOut;
+    const int32_t P = (int32_t)p.pad;
+    uint32_t* tw = t->words.as<uint32_t>();
+    vx_status st = VX_OK;
+    auto run = [&]() -> vx_status {
+        if (p.bit) {
+            VX_TRY(morph_ball_ref(g, g->morph_a, g->words.as<uint32_t>(), gd, p.wdim, -P, r2, 0u, nullptr, tw));
+        } else {
+            VX_TRY(morph_ball_ref(g, g->morph_a, g->words.as<uint32_t>(), gd, p.wdim, -P, 0u, 0u, nullptr, tw));
+            VX_TRY(morph_field(g, tw, p.wdim, 0));
+            vx::launch_morph_thresh(g->morph_d.as<uint32_t>(), p.wdim, r2, false, tw, s);
+        }
+        uint64_t n = 0;
+        const uint32_t* h = nullptr;
+        VX_TRY(solid_fill(t, &n, &h));
+        if (p.bit) return morph_ball_ref(g, g->morph_a, tw, pd, dim, P, r2, both, g->words.as<uint32_t>(), dst);
+        VX_TRY(morph_field(g, tw, p.wdim, 1));
+        vx::launch_morph_thresh(g->morph_d.as<uint32_t>(), p.wdim, r2, true, tw, s);
+        return morph_ball_ref(g, g->morph_a, tw, pd, dim, P, 0u, 0u, g->words.as<uint32_t>(), dst);
+    };
+    st = run();
+    const std::string e = g_err;
+    vx_grid_free(t);  // (waits for the stream: everything that read the padded mask is done)
+    return st == VX_OK ? VX_OK : fail(st, e);
+}
+
+static vx_status morph_args(const vx_grid* g, uint32_t op, uint32_t r2, const void* buf)
+{
+    if (!g || !buf) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (op > VX_MORPH_CLOSE) return fail(VX_ERR_INVALID_ARG, "unknown morphology operation");
+    if (r2 == 0xFFFFFFFFu) return fail(VX_ERR_INVALID_ARG, "radius_sq 0xFFFFFFFF is the distance fields' sentinel");
+    return VX_OK;
+}
+
+vx_status vx_grid_morph_device(const vx_grid* gc, uint32_t op, uint32_t radius_sq, uint32_t* dev_words, uint64_t capacity_words)
+{
+    VX_TRY(morph_args(gc, op, radius_sq, dev_words));
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    const uintptr_t a = (uintptr_t)dev_words, b = (uintptr_t)g->words.p, n = (uintptr_t)g->g.nwords * 4u;
+    if (n && a < b + n && b < a + n) return fail(VX_ERR_INVALID_ARG, "the output overlaps the grid's own bitmask");
+    if (!g->g.nvox) return VX_OK;
+    MorphPlan p;
+    VX_TRY(morph_plan(g, op, radius_sq, &p));
+    if (capacity_words < g->g.nwords) return fail(VX_ERR_CAPACITY, "morphology: mask buffer too small");
+    DeviceGuard dg(g->device);
+    VX_TRY(morph_run(g, g->words.as<uint32_t>(), g->g.dim, op, radius_sq, p, dev_words));
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+vx_status vx_grid_morph_mask(const vx_grid* gc, uint32_t op, uint32_t radius_sq, uint32_t* host_words, uint64_t capacity_words)
+{
+    VX_TRY(morph_args(gc, op, radius_sq, host_words));
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    if (!g->g.nvox) return VX_OK;
+    MorphPlan p;
+    VX_TRY(morph_plan(g, op, radius_sq, &p));
+    if (capacity_words < g->g.nwords) return fail(VX_ERR_CAPACITY, "morphology: mask buffer too small");
+    DeviceGuard dg(g->device);
+    VX_HIP(g->morph_out.ensure((size_t)(g->g.nwords + 2) * 4));
+    VX_TRY(morph_run(g, g->words.as<uint32_t>(), g->g.dim, op, radius_sq, p, g->morph_out.as<uint32_t>()));
+    VX_HIP(hipGetLastError());
+    VX_HIP(hipMemcpyAsync(host_words, g->morph_out.p, (size_t)g->g.nwords * 4, hipMemcpyDeviceToHost, g->stream));
+    VX_HIP(hipStreamSynchronize(g->stream));
+    return VX_OK;
+}
+
+// the result grid's counts, list and derived data from its mask: as if vx_grid_set_voxel had run on every cell in ascending index
+static vx_status morph_finish_grid(vx_grid* out, const vx_grid* src)
+{
+    for (int a = 0; a < 3; ++a) { out->bbmin[a] = src->bbmin[a]; out->bbmax[a] = src->bbmax[a]; out->bbc[a] = src->bbc[a]; }
+    out->triangles = 0;
+    out->coarse_valid = out->prefix_valid = out->p16_valid = out->occupied_known = false;
+    if (!out->g.nvox) { out->occupied_known = true; return VX_OK; }
+    VX_TRY(ensure_prefix(out));
+    out->host_set_calls = out->set_calls = out->occupied;
+    out->counts_valid = true;
+    if (out->kind == VX_GRID_VEC && out->occupied) {
+        VX_HIP(out->vec.ensure((size_t)(out->occupied + 1) * sizeof(vx_aabb)));
+        vx::launch_emit_bool_aabbs(out->words.as<uint32_t>(), out->wprefix.as<uint32_t>(), out->g, out->vec.as<vx_aabb>(), out->occupied, out->stream,
+                                   out->sel_valid ? out->wsel.as<uint32_t>() : nullptr);
+        out->vec_count = out->occupied;
+    }
+    VX_TRY(ensure_coarse(out));
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+static vx_status morph_grid(const vx_grid* src_c, uint32_t op, uint32_t r2, vx_grid** out)
+{
+    vx_grid* src = const_cast<vx_grid*>(src_c);
+    MorphPlan p;
+    if (src->g.nvox) VX_TRY(morph_plan(src, op, r2, &p));
+    vx_grid* g = nullptr;
+    VX_TRY(morph_new_grid(src, src->kind, src->g.dim, &g));
+    DeviceGuard dg(src->device);
+    vx_status st = VX_OK;
+    uint64_t before = 0;
+    if (src->g.nvox) {
+        if (op == kMorphSeal) {
+            st = ensure_occupied(src);
+            before = src->occupied;
+            if (st == VX_OK) st = morph_seal_run(src, r2, p, g->words.as<uint32_t>());
+        } else {
+            st = morph_run(src, src->words.as<uint32_t>(), src->g.dim, op, r2, p, g->words.as<uint32_t>());
+        }
+    }
+    if (st == VX_OK) st = morph_finish_grid(g, src);
+    if (st != VX_OK) { const std::string e = g_err; vx_grid_free(g); return fail(st, e); }
+    if (op == kMorphSeal) g->interior = g->occupied - before;
+    *out = g;
+    return VX_OK;
+}
+
+vx_status vx_grid_morph(const vx_grid* src, uint32_t op, uint32_t radius_sq, vx_grid** out)
+{
+    VX_TRY(morph_args(src, op, radius_sq, out));
+    return morph_grid(src, op, radius_sq, out);
+}
+
+vx_status vx_grid_seal(const vx_grid* src, uint32_t radius_sq, vx_grid** out)
+{
+    VX_TRY(morph_args(src, VX_MORPH_DILATE, radius_sq, out));
+    return morph_grid(src, kMorphSeal, radius_sq, out);
+}
+
+uint32_t vx_morph_bit_radius(void) { return vx::kMorphBitRadius; }
 
 // Surface mesh: the argument checks in the header's order, the counting pass and both scans on the grid's stream, one host wait for the
 // totals, then the emission (vx_surface.hip).  The passes only read the bitmask (and, with materials, the word prefix and the ids); a

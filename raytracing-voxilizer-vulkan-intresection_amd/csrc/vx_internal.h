@@ -467,6 +467,30 @@ void launch_solid_ids(int16_t* ids, uint64_t n, int16_t v, bool only_unset, hipS
 uint64_t distance_stack_entries(const uint32_t dim[3], bool is_signed);
 void launch_distance(const uint32_t* words, const uint32_t dim[3], int mode, float vs, uint32_t* buf, uint2* stk, hipStream_t s);
 
+// Morphology with the digital Euclidean ball (vx_morph.hip).  A domain: its cells and the bits from one (y, z) row to the next -- X for the
+// reference's bitmask, 32 * ceil(X / 32) for a ROW-ALIGNED mask (morph_aligned_words(dim) words, padding bits zero).
+struct MorphDom {
+    uint32_t dim[3];
+    uint64_t stride;
+};
+constexpr uint32_t kMorphInvIn = 1u;   // the source is complemented over the whole lattice (cells outside its domain become targets)
+constexpr uint32_t kMorphInvOut = 2u;  // the result is complemented (inside the output domain)
+// vx_morph_bit_radius(): the largest R the bit-level kernel takes; at most 32, so that a shift reaches only the neighbouring word.  Measured
+// (tools/morph_time.py); -DVX_MORPH_BIT_RADIUS=n builds the library for that measurement.
+#ifndef VX_MORPH_BIT_RADIUS
+#define VX_MORPH_BIT_RADIUS 16
+#endif
+constexpr uint32_t kMorphBitRadius = VX_MORPH_BIT_RADIUS;
+static_assert(kMorphBitRadius <= 32u, "the bit-level kernel stages one word of halo");
+uint64_t morph_aligned_words(const uint32_t dim[3]);
+// dst (row-aligned, odim) = the dilation by B(r2), R = isqrt(r2) <= 32, of src; output cell c reads the input around c + (shift, shift, shift).
+// r2 = 0: a bit copy with an offset (pad / crop).  Both flags: the erosion.
+void launch_morph_ball(const uint32_t* src, const MorphDom& in, uint32_t* dst, const uint32_t odim[3], int32_t shift, uint32_t r2, uint32_t flags, hipStream_t s);
+// dst (the reference's layout, ceil(X*Y*Z / 32) words, tail bits zero) = aligned | orw (orw optional, the reference's layout)
+void launch_morph_pack(const uint32_t* aligned, const uint32_t dim[3], const uint32_t* orw, uint32_t* dst, hipStream_t s);
+// dst (the reference's layout) = field <= r2, or with erode: field > r2 and at least R cells from every border
+void launch_morph_thresh(const uint32_t* field, const uint32_t dim[3], uint32_t r2, bool erode, uint32_t* dst, hipStream_t s);
+
 // Surface mesh (vx_surface.hip): npts = (X+1)(Y+1)(Z+1) lattice points, nlw = ceil(npts / 32) corner words.
 struct SurfacePlan {
     uint64_t npts = 0, nlw = 0;

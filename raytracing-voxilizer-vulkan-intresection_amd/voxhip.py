@@ -17,6 +17,7 @@ VOXELIZE_MATERIALS = 1
 VOXELIZE_LIST_ASYNC = 2
 VOXELIZE_SOLID = 4
 DISTANCE_INSIDE = 1
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3   # VX_MORPH_*
 CONNECT_6, CONNECT_26 = 6, 26
 STATUS_NAMES = {0: "VX_OK", 1: "VX_ERR_INVALID_ARG", 2: "VX_ERR_PATH", 3: "VX_ERR_PARSE", 4: "VX_ERR_OUT_OF_BOUNDS",
                 5: "VX_ERR_MORTON_BITS", 6: "VX_ERR_NO_DEVICE", 7: "VX_ERR_HIP", 8: "VX_ERR_CAPACITY", 9: "VX_ERR_UNSUPPORTED"}
@@ -216,6 +217,7 @@ SYMBOLS = [
     "vx_grid_create", "vx_grid_describe", "vx_grid_set_voxel", "vx_grid_test_voxel", "vx_grid_coords", "vx_grid_bytes",
     "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_fill_interior", "vx_grid_interior", "vx_grid_fill_rounds",
     "vx_grid_distance_sq_device", "vx_grid_distance_sq", "vx_grid_sdf_device", "vx_grid_sdf",
+    "vx_grid_morph_device", "vx_grid_morph_mask", "vx_grid_morph", "vx_grid_seal", "vx_morph_bit_radius",
     "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh",
     "vx_grid_components_device", "vx_grid_components", "vx_grid_component_stats", "vx_grid_aabbs",
     "vx_grid_aabbs_device", "vx_grid_bind_aabbs_device", "vx_grid_list_wait", "vx_grid_aabbs_device_async", "vx_grid_materials", "vx_grid_material_ids", "vx_grid_material_ids_device", "vx_grid_material_first_use",
@@ -346,6 +348,12 @@ def lib():
     L.vx_grid_distance_sq.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_sdf_device.argtypes = [vp, vp, C.c_uint64]
     L.vx_grid_sdf.argtypes = [vp, vp, C.c_uint64]
+    L.vx_grid_morph_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64]
+    L.vx_grid_morph_mask.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64]
+    L.vx_grid_morph.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.vx_grid_seal.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.vx_morph_bit_radius.argtypes = []
+    L.vx_morph_bit_radius.restype = C.c_uint32
     L.vx_grid_surface_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, u64p, u64p]
     L.vx_grid_surface.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, u64p, u64p]
     L.vx_grid_surface_mesh.argtypes = [vp, C.c_int, C.POINTER(vp)]
@@ -487,6 +495,26 @@ def profile_read():
         out[key] = (a + ms.value, b + n.value)
         slot += 1
     return out
+
+
+def morph_bit_radius():
+    """vx_morph_bit_radius: the largest R = floor(sqrt(radius_sq)) the bit-level morphology kernel takes."""
+    return int(lib().vx_morph_bit_radius())
+
+
+def morph_radius_sq(radius=None, radius_sq=None):
+    """radius (cells, may be fractional) -> radius_sq = floor(radius * radius) in float64; or radius_sq itself.  Exactly one of the two."""
+    if (radius is None) == (radius_sq is None):
+        raise ValueError("give exactly one of radius and radius_sq")
+    if radius_sq is None:
+        r = float(radius)
+        if not (r >= 0.0) or r * r >= 4294967295.0:
+            raise ValueError("radius out of range")
+        return int(np.floor(r * r))
+    r2 = int(radius_sq)
+    if r2 < 0 or r2 > 0xFFFFFFFF:
+        raise ValueError("radius_sq out of range")
+    return r2
 
 
 def device_allocations():
@@ -805,6 +833,58 @@ class Grid:
         import torch
         out, n = self._device_out(out, (torch.float32,), "float32")
         _check(lib().vx_grid_sdf_device(self.h, out.data_ptr(), n))
+        self._record(out)
+        return out
+
+    def _morph_grid(self, op, radius, radius_sq):
+        h = C.c_void_p()
+        r2 = morph_radius_sq(radius, radius_sq)
+        if op is None:
+            _check(lib().vx_grid_seal(self.h, r2, C.byref(h)))
+        else:
+            _check(lib().vx_grid_morph(self.h, op, r2, C.byref(h)))
+        g = Grid(h)
+        g._stream = getattr(self, "_stream", None)
+        return g
+
+    def dilate(self, radius=None, radius_sq=None):
+        """vx_grid_morph(VX_MORPH_DILATE): a new Grid, this one grown by the Euclidean ball of `radius` cells (fractional radii allowed:
+        radius_sq = floor(radius^2); radius=1.5 is the 18-neighbourhood).  Exactly one of radius / radius_sq."""
+        return self._morph_grid(MORPH_DILATE, radius, radius_sq)
+
+    def erode(self, radius=None, radius_sq=None):
+        """vx_grid_morph(VX_MORPH_ERODE): a new Grid of the cells whose whole ball lies in this one (cells outside the grid are empty)."""
+        return self._morph_grid(MORPH_ERODE, radius, radius_sq)
+
+    def open(self, radius=None, radius_sq=None):
+        """vx_grid_morph(VX_MORPH_OPEN): erosion, then dilation -- drops specks; a subset of this grid."""
+        return self._morph_grid(MORPH_OPEN, radius, radius_sq)
+
+    def close(self, radius=None, radius_sq=None):
+        """vx_grid_morph(VX_MORPH_CLOSE): dilation on the unbounded lattice, then erosion -- fills gaps narrower than the ball; a superset."""
+        return self._morph_grid(MORPH_CLOSE, radius, radius_sq)
+
+    def seal(self, radius=None, radius_sq=None):
+        """vx_grid_seal: this grid plus the interior that appears once holes up to the ball's size are closed (dilate, fill, erode); the
+        result's interior() is the number of cells added."""
+        return self._morph_grid(None, radius, radius_sq)
+
+    def morph_mask(self, op, radius_sq):
+        """vx_grid_morph_mask: the result of MORPH_* `op` as numpy uint32 words in this grid's own layout."""
+        n = self.describe()["num_words"]
+        w = np.zeros(max(n, 1), dtype=np.uint32)
+        _check(lib().vx_grid_morph_mask(self.h, op, radius_sq, w.ctypes.data, n))
+        return w[:n]
+
+    def morph_mask_device(self, op, radius_sq, out=None):
+        """vx_grid_morph_device, asynchronous on the grid's stream -> `out`, a device torch.uint32 (or int32) tensor of num_words words."""
+        import torch
+        n = self.describe()["num_words"]
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint32, device="cuda")
+        if out.dtype not in (torch.uint32, torch.int32) or out.numel() < n or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous device uint32 / int32 tensor of at least num_words elements")
+        _check(lib().vx_grid_morph_device(self.h, op, radius_sq, out.data_ptr(), out.numel()))
         self._record(out)
         return out
 
