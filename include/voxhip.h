@@ -180,6 +180,28 @@ vx_status vx_mesh_set_texture(vx_mesh* m, int32_t slot, uint32_t width, uint32_t
 vx_status vx_mesh_load_textures(vx_mesh* m);
 void vx_mesh_free(vx_mesh* m);
 
+/* ---- geometry at its extremes: what every builder does with vertices that are not ordinary numbers ----------
+ * 1. Non-finite vertices.  A coordinate is non-finite when it is NaN (either sign, any payload), +Inf or -Inf.
+ *    - vx_voxelize, vx_voxelize_into, vx_voxelize_multi, vx_multi_voxelize and vx_octree_build take the bounding box over ALL vertices
+ *      of the mesh, referenced by a triangle or not, as the reference does.  A mesh with any non-finite coordinate is refused with
+ *      VX_ERR_INVALID_ARG and a message that contains "non-finite".  The error is found on the device, from the bounding box, so it is
+ *      of vx_voxelize_into's second class: the grid handle is left EMPTY and the next successful build equals a fresh one.
+ *    - vx_bvh_build and vx_bvh_build_into refuse a mesh in which a vertex that some triangle REFERENCES has a non-finite coordinate:
+ *      VX_ERR_INVALID_ARG, "non-finite"; host meshes and borrowed device meshes alike, found beside the index check.  A failed
+ *      vx_bvh_build_into leaves the empty BVH.  Unreferenced vertices play no part in a BVH.
+ * 2. Finite vertices of any magnitude are ordinary input and every contract holds as written: an outlying vertex at 2^100, vertices at
+ *    +-FLT_MAX/2 whose extent overflows to +Inf.  The voxelizer refuses the latter with VX_ERR_CAPACITY and the octree with
+ *    VX_ERR_MORTON_BITS (the extent divided by the voxel size is above 2^21); BVH and TLAS queries stay bit-equal to the brute force over
+ *    all triangles, those that reach to the outlier included.  An instance whose world box overflows float32 is bounded by the whole
+ *    space in the TLAS and is entered by every ray.
+ * 3. Scale.  For the mesh times 2^k with the voxel size times 2^k the voxelizer is bit-identical to the reference on that same scaled
+ *    input for every k at which no intermediate of the triangle/box test overflows -- downwards through gradual underflow, where the
+ *    reference's own result changes with k (subnormal products, the 1e-8 thresholds of sat_variant 1).  Beyond that, once a product of
+ *    the test is Inf and a NaN follows (from about 2^42 times a unit-sized mesh on), the result is unspecified.
+ * 4. OBJ numerals (vx_mesh_load_obj: v, vt, vn and the reals of the MTL).  A numeral whose magnitude overflows double reads as +-Inf,
+ *    one that underflows as +-0; a double beyond float's range converts to +-Inf (no undefined cast); `nan`, `inf` and their signed
+ *    forms read as written; nothing consults the C locale.  Such a file LOADS; the builders then apply rule 1. */
+
 /* ---- voxelize: replaces VoxelBuilder<T,inParaell>::buildVoxelGrid (VoxelBuilder.hpp:338-542) ---------------
  * Limits (the reference has none besides memory): at most 2^21 cells per axis, 2^21 itself included -- the bound the reference's
  * own Octree has (octTree.hpp:583-585); the per-triangle candidate ranges are 16 + 16 bits in the triangle record plus 5 + 6 high
@@ -195,7 +217,7 @@ vx_status vx_voxelize(const vx_mesh* mesh, float voxel_size, vx_grid_kind kind, 
  *    device, sat_variant, shard_rank / shard_world, a triangle range past the mesh, word_begin > word_end) or in the mesh itself
  *    (with VX_VOXELIZE_MATERIALS, more than 32767 distinct materials; a failed upload of the mesh): nothing has been queued on the
  *    grid and it still holds its previous build, unchanged through every reader;
- *  - every other error (an axis above 2^21 cells, more than 2^37 cells, word_end past the new grid's word count, a counter
+ *  - every other error (a non-finite vertex coordinate, an axis above 2^21 cells, more than 2^37 cells, word_end past the new grid's word count, a counter
  *    overflow, a HIP error during the build): the grid is EMPTY -- 0 x 0 x 0 cells, no words, 0 occupied voxels and setVoxel calls, an empty list
  *    (a VX_VOXELIZE_LIST_ASYNC list of the previous build that was never written is dropped; a bound buffer holds 0 records), no
  *    materials, and every ray misses.
@@ -560,7 +582,8 @@ vx_status vx_octree_trace_multi(const vx_octree* o, const vx_multihit_args* a); 
  *   bary     (u, v) of prim: raytrace.rchit's hitAttributeEXT vec2 attribs (:31,66); (0, 0) on a miss;
  *   normal   the unit geometric normal cross(e1, e2) / sqrt(dot(., .)) of prim, not flipped (rounding not pinned); zeros on a miss;
  *   shadowed (any_hit) 1 iff some triangle is accepted, t then some accepted t; tmax_per_ray honoured.
- * t, prim and bary are bit-equal to the brute force over all triangles: the BVH only accelerates.
+ * t, prim and bary are bit-equal to the brute force over all triangles: the BVH only accelerates.  (Every vertex a triangle references
+ * is finite: the build refuses anything else.)
  * The BVH is a binary LBVH: vx_bvh_nodes returns its node array, vx_bvh_node records with the root at index 0:
  *   interior  a, b = the indices of its two children;
  *   leaf      b = 0x80000000 | count, a = the position of its first triangle in LEAF ORDER (the leaves' triangles, leaf after leaf);
@@ -572,7 +595,8 @@ typedef struct vx_bvh vx_bvh;
 typedef struct vx_bvh_node { float min[3]; uint32_t a; float max[3]; uint32_t b; } vx_bvh_node;
 #define VX_BVH_LEAF 0x80000000u
 #define VX_BVH_DEFAULT_LEAF 4u
-/* max_leaf_triangles: 0 = VX_BVH_DEFAULT_LEAF.  A borrowed device mesh whose indices leave [0, num_vertices) fails with VX_ERR_INVALID_ARG. */
+/* max_leaf_triangles: 0 = VX_BVH_DEFAULT_LEAF.  A borrowed device mesh whose indices leave [0, num_vertices) fails with VX_ERR_INVALID_ARG,
+ * and so does any mesh with a non-finite coordinate in a referenced vertex ("geometry at its extremes", rule 1). */
 vx_status vx_bvh_build(const vx_mesh* mesh, uint32_t max_leaf_triangles, void* stream, vx_bvh** out);
 /* steady state: rebuild from the (refreshed) mesh into the same handle -- no allocation when the triangle count repeats */
 vx_status vx_bvh_build_into(const vx_mesh* mesh, vx_bvh* bvh);
@@ -649,7 +673,8 @@ void vx_bvh_free(vx_bvh* b);
  * by that argument: a BLAS's side list of ill-conditioned triangles (vx_bvh_num_ill_conditioned) is tested only when the ray
  * reaches the instance's TLAS leaf, so a rounding-noise hit on such a sliver far outside the instance's widened world box may be pruned.
  * vx_tlas_nodes returns the node array (vx_bvh_node records, root at 0, 2n-1 of them for n >= 1 instances): interior a, b = the children;
- * leaf b = VX_BVH_LEAF | 1, a = the instance; min / max the widened world boxes (empty boxes, min > max, for inactive instances).
+ * leaf b = VX_BVH_LEAF | 1, a = the instance; min / max the widened world boxes (empty boxes, min > max, for inactive instances; -Inf / +Inf for an instance whose world box
+ * overflows float32).
  * Ownership: the TLAS BORROWS its BLAS handles; they must outlive it.  After a BLAS is rebuilt (vx_bvh_build_into) the caller calls
  * vx_tlas_update* (as in Vulkan): an update re-reads every BLAS's root box, node and triangle arrays, height and side list, and rebuilds the
  * TLAS over the given instances.  vx_tlas_update has copied the host array when it returns (the caller may reuse it at once) and does not

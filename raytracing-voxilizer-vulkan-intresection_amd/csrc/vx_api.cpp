@@ -4,6 +4,7 @@
 
 #include <cctype>
 #include <cmath>
+#include <limits>
 #include <cstdio>
 #include <algorithm>
 #include <atomic>
@@ -772,6 +773,9 @@ struct Extent {
 // morton_error: the caller is the Octree, whose limit of 2^21 cells per axis carries the reference's own message (octTree.hpp:583-585)
 vx_status extent_from_bbox(const float* bb, size_t nv, float vs, Extent* e, bool morton_error = false)
 {
+    // a NaN or infinite coordinate of any vertex is the minimum or the maximum of its axis (k_bbox orders +NaN above +Inf and -NaN below -Inf)
+    for (int a = 0; a < 6 && nv; ++a)
+        if (!std::isfinite(bb[a])) return fail(VX_ERR_INVALID_ARG, "mesh has a non-finite vertex coordinate (NaN or Inf)");
     for (int a = 0; a < 3; ++a) {
         e->mn[a] = bb[a];
         e->mx[a] = bb[3 + a];
@@ -3699,7 +3703,8 @@ vx_status bvh_build_impl(vx_mesh* mesh, vx_bvh* b)
     VX_HIP(hipMemcpyAsync(&err, &ds->err, 4, hipMemcpyDeviceToHost, s));
     VX_HIP(hipMemcpyAsync(&nill, &ds->nill, 4, hipMemcpyDeviceToHost, s));
     VX_HIP(hipStreamSynchronize(s));
-    if (err) return fail(VX_ERR_INVALID_ARG, "triangle index out of range");
+    if (err & 1u) return fail(VX_ERR_INVALID_ARG, "triangle index out of range");
+    if (err & 2u) return fail(VX_ERR_INVALID_ARG, "a triangle has a non-finite vertex coordinate (NaN or Inf)");
     std::memcpy(&b->height, &root[3], 4);
     for (int a = 0; a < 3; ++a) {
         b->root_min[a] = root[a];
@@ -3707,8 +3712,9 @@ vx_status bvh_build_impl(vx_mesh* mesh, vx_bvh* b)
         b->coord_max = std::max(b->coord_max, std::max(std::fabs(root[a]), std::fabs(root[4 + a])));
         b->extent = std::max(b->extent, root[4 + a] - root[a]);
     }
-    if (!std::isfinite(b->coord_max)) b->coord_max = 0.f;
-    if (!std::isfinite(b->extent)) b->extent = 0.f;
+    // every referenced vertex is finite (k_bvh_prep), so coord_max is; max - min of vertices beyond +-FLT_MAX/2 overflows: the widening
+    // then takes the largest finite extent (2^-10 of it stays finite), not 0, which would leave 2^-18 of coord_max alone
+    if (!std::isfinite(b->extent)) b->extent = std::numeric_limits<float>::max();
     b->ntri = n;
     b->nnodes = nn;
     b->nill = nill;

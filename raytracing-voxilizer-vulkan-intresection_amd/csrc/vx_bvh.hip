@@ -65,7 +65,8 @@ __device__ __forceinline__ bool load_tri(const float* __restrict__ v, const int3
 
 }  // namespace
 
-// Box of the bounds of all triangles (ordered uint encoding: 0..2 min, 3..5 max, initialised by the host to ~0 / 0) and the index check.
+// Box of the bounds of all triangles (ordered uint encoding: 0..2 min, 3..5 max, initialised by the host to ~0 / 0), the index check
+// (err bit 0) and the check for non-finite coordinates of referenced vertices (err bit 1).
 __global__ __launch_bounds__(kBuildBlock) void k_bvh_prep(const float* __restrict__ v, const int32_t* __restrict__ idx, uint64_t nv, uint32_t ntri,
                                                           uint32_t* __restrict__ box6, uint32_t* __restrict__ err)
 {
@@ -76,6 +77,10 @@ __global__ __launch_bounds__(kBuildBlock) void k_bvh_prep(const float* __restric
     if (t < ntri) {
         float p[9];
         if (!load_tri(v, idx, nv, t, p)) atomicOr(err, 1u);
+        bool fin = true;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) fin &= isfinite(p[k]);
+        if (!fin) atomicOr(err, 2u);  // a referenced vertex with a NaN or infinite coordinate: the build refuses the mesh
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             atomicMin(&sb[a], f2ord(fminf(fminf(p[a], p[3 + a]), p[6 + a])));

@@ -16,10 +16,12 @@
 // triangulation is not pinned by anything in the reference; fixtures use `f i j k` triangles and %.9g floats only.
 #include <cerrno>
 #include <charconv>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -31,16 +33,55 @@ namespace vx {
 
 static inline const char* skip_ws(const char* p, const char* eol) { while (p < eol && (*p == ' ' || *p == '\t')) ++p; return p; }
 
-// one decimal number in [q, eol); never reads past the line, never consults the C locale
+// one decimal number in [q, eol); never reads past the line, never consults the C locale.  A numeral beyond double's range reads as
+// +-Inf, one below it as +-0 (include/voxhip.h, "OBJ numerals"): from_chars leaves `out` untouched on result_out_of_range, so the
+// value comes from the numeral's own text -- the decimal exponent of its first non-zero digit, which is far from 0 on either side.
 static bool parse_real(const char*& q, const char* eol, double& out)
 {
     const char* s = q;
     if (s < eol && *s == '+') ++s;  // from_chars rejects an explicit plus sign
-    const std::from_chars_result r = std::from_chars(s, eol, out);
+    double d = 0.0;
+    const std::from_chars_result r = std::from_chars(s, eol, d);
     if (r.ec != std::errc() && r.ec != std::errc::result_out_of_range) return false;
     if (r.ptr == s) return false;
+    if (r.ec == std::errc::result_out_of_range) {
+        const char* p = s;
+        const bool neg = *p == '-';
+        if (neg) ++p;
+        long long lead = 0;  // decimal exponent of the first non-zero digit, before the explicit exponent
+        bool point = false, found = false;
+        for (; p < r.ptr && *p != 'e' && *p != 'E'; ++p) {
+            if (*p == '.') { point = true; continue; }
+            if (!found) {
+                if (*p != '0') { found = true; lead = point ? lead - 1 : 0; }
+                else if (point) --lead;
+            } else if (!point) ++lead;
+        }
+        long long ex = 0;
+        if (p < r.ptr) {  // e[+-]digits, saturated: the sign of the sum is all that is read
+            ++p;
+            const bool eneg = p < r.ptr && *p == '-';
+            if (p < r.ptr && (*p == '-' || *p == '+')) ++p;
+            for (; p < r.ptr; ++p) ex = ex < 1000000000LL ? ex * 10 + (*p - '0') : ex;
+            if (eneg) ex = -ex;
+        }
+        d = lead + ex > 0 ? HUGE_VAL : 0.0;
+        if (neg) d = -d;
+    }
+    out = d;
     q = r.ptr;
     return true;
+}
+
+// double -> float, rounded to nearest as the conversion does it inside float's range; beyond it, where the conversion is undefined,
+// +-Inf at or above FLT_MAX + half an ulp (2^128 - 2^103) and +-FLT_MAX below
+static float to_float(double d)
+{
+    constexpr double fmax = (double)std::numeric_limits<float>::max();
+    constexpr double lim = 340282356779733661637539395458142568448.0;
+    if (d > fmax) return d >= lim ? std::numeric_limits<float>::infinity() : std::numeric_limits<float>::max();
+    if (d < -fmax) return d <= -lim ? -std::numeric_limits<float>::infinity() : -std::numeric_limits<float>::max();
+    return (float)d;  // NaN converts to NaN
 }
 
 static std::string token(const char*& q, const char* eol)
@@ -101,13 +142,13 @@ static void load_mtl(const std::string& path, std::vector<vx_material>& mats, st
                 q = skip_ws(q, eol);
                 double d;
                 if (!parse_real(q, eol, d)) break;
-                dst[k] = (float)d;
+                dst[k] = to_float(d);
             }
         };
         auto real1 = [&](float& dst) {
             q = skip_ws(q, eol);
             double d;
-            if (parse_real(q, eol, d)) dst = (float)d;
+            if (parse_real(q, eol, d)) dst = to_float(d);
         };
         if (key == "newmtl") {
             const std::string name = token(q, eol);
@@ -126,7 +167,7 @@ static void load_mtl(const std::string& path, std::vector<vx_material>& mats, st
             else if (key == "Ni") real1(m.ior);
             else if (key == "d") real1(m.dissolve);
             else if (key == "Tr") { float tr = 0.0f; real1(tr); m.dissolve = 1.0f - tr; }
-            else if (key == "illum") { float v = 0.0f; real1(v); m.illum = (int32_t)v; }
+            else if (key == "illum") { float v = 0.0f; real1(v); m.illum = (v > -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : 0; }
             else if (key == "map_Kd") {
                 std::string last;
                 for (std::string t = token(q, eol); !t.empty(); t = token(q, eol)) last = t;
@@ -194,7 +235,7 @@ int load_obj(const char* path, std::vector<float>& verts, std::vector<int32_t>& 
                 q = skip_ws(q, eol);
                 double d;
                 if (!parse_real(q, eol, d)) break;
-                xyz[k] = (float)d;
+                xyz[k] = to_float(d);
             }
             verts.push_back(xyz[0]); verts.push_back(xyz[1]); verts.push_back(xyz[2]);
         } else if (q + 2 < eol && q[0] == 'v' && (q[1] == 't' || q[1] == 'n') && (q[2] == ' ' || q[2] == '\t')) {
@@ -205,7 +246,7 @@ int load_obj(const char* path, std::vector<float>& verts, std::vector<int32_t>& 
                 q = skip_ws(q, eol);
                 double d;
                 if (!parse_real(q, eol, d)) break;
-                c[k] = (float)d;
+                c[k] = to_float(d);
             }
             std::vector<float>& dst = nc == 2 ? vts : vns;
             dst.insert(dst.end(), c, c + nc);

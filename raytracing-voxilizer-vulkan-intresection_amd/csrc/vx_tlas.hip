@@ -52,7 +52,8 @@ __device__ __forceinline__ float xf_row(const float* m, float x, float y, float 
 
 }  // namespace
 
-// Per instance: inverse, active flag, widened world box (ibox: lo, hi as float4 pairs; inactive: the empty box +inf / -inf), the union of
+// Per instance: inverse, active flag, widened world box (ibox: lo, hi as float4 pairs; inactive: the empty box +inf / -inf; a box that
+// overflows float32: the whole space -inf / +inf, left out of the union), the union of
 // the active boxes (small[0..5], ordered uint, initialised to ~0 / 0) and the largest condition number (small[6], ordered uint, init 0).
 __global__ __launch_bounds__(kBuildBlock) void k_tlas_prep(const vx_instance* __restrict__ in, uint32_t n, const TlasBlas* __restrict__ tab, uint32_t nb,
                                                            float* __restrict__ xf, float* __restrict__ w2o, uint32_t* __restrict__ iblas,
@@ -96,6 +97,7 @@ __global__ __launch_bounds__(kBuildBlock) void k_tlas_prep(const vx_instance* __
     const float lo[3] = {B.rmin[0] - B.pad, B.rmin[1] - B.pad, B.rmin[2] - B.pad}, hi[3] = {B.rmax[0] + B.pad, B.rmax[1] + B.pad, B.rmax[2] + B.pad};
     float bmin[3] = {INFINITY, INFINITY, INFINITY}, bmax[3] = {-INFINITY, -INFINITY, -INFINITY};
     float omax = 0.0f;
+    bool whole = false;  // a corner that overflows (or 0 * Inf = NaN, which fminf / fmaxf would drop): the box is the whole space
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const float x = (c & 1) ? hi[0] : lo[0], y = (c & 2) ? hi[1] : lo[1], z = (c & 4) ? hi[2] : lo[2];
@@ -103,6 +105,7 @@ __global__ __launch_bounds__(kBuildBlock) void k_tlas_prep(const vx_instance* __
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const float v = xf_row(m + 4 * r, x, y, z);
+            whole |= !isfinite(v);
             bmin[r] = fminf(bmin[r], v);
             bmax[r] = fmaxf(bmax[r], v);
         }
@@ -119,7 +122,19 @@ __global__ __launch_bounds__(kBuildBlock) void k_tlas_prep(const vx_instance* __
     const float ext = fmaxf(fmaxf(bmax[0] - bmin[0], bmax[1] - bmin[1]), bmax[2] - bmin[2]);
     const float pad = (kCond * cond * (tn + cmax) + kCorner * (nm * omax + tn)) + kExt * ext;
 #pragma unroll
-    for (int r = 0; r < 3; ++r) { bmin[r] = bmin[r] - pad; bmax[r] = bmax[r] + pad; }
+    for (int r = 0; r < 3; ++r) {
+        bmin[r] = bmin[r] - pad;
+        bmax[r] = bmax[r] + pad;
+        whole |= !isfinite(bmin[r]) || !isfinite(bmax[r]);
+    }
+    atomicMax(&small[6], f2ord(cond));
+    if (whole) {
+        // a world box that is not finite bounds nothing: the instance is entered by every ray (its BLAS root box, in object space, still
+        // prunes), and it stays out of the union, so that the Morton codes of the other instances keep their resolution (its own is 0)
+        ibox[2ull * i] = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+        ibox[2ull * i + 1] = make_float4(INFINITY, INFINITY, INFINITY, 0.0f);
+        return;
+    }
     ibox[2ull * i] = make_float4(bmin[0], bmin[1], bmin[2], 0.0f);
     ibox[2ull * i + 1] = make_float4(bmax[0], bmax[1], bmax[2], 0.0f);
 #pragma unroll
@@ -127,7 +142,6 @@ __global__ __launch_bounds__(kBuildBlock) void k_tlas_prep(const vx_instance* __
         atomicMin(&small[a], f2ord(bmin[a]));
         atomicMax(&small[3 + a], f2ord(bmax[a]));
     }
-    atomicMax(&small[6], f2ord(cond));
 }
 
 __global__ __launch_bounds__(kBuildBlock) void k_tlas_keys(const float4* __restrict__ ibox, uint32_t n, const uint32_t* __restrict__ small,
@@ -143,7 +157,7 @@ __global__ __launch_bounds__(kBuildBlock) void k_tlas_keys(const float4* __restr
         const float lo = ord2f(small[a]), hi = ord2f(small[3 + a]);
         const float ext = hi - lo;
         const float f = ext > 0.0f ? (c[a] - lo) / ext * 1024.0f : 0.0f;
-        q[a] = f >= 1023.0f ? 1023u : (f > 0.0f ? (uint32_t)f : 0u);  // (NaN: inactive instances, an empty union -> 0)
+        q[a] = f >= 1023.0f ? 1023u : (f > 0.0f ? (uint32_t)f : 0u);  // (NaN: inactive or whole-space instances, an empty union -> 0)
     }
     const uint64_t code = (uint64_t)(spread10(q[0]) | (spread10(q[1]) << 1) | (spread10(q[2]) << 2));
     keys[i] = (code << 32) | i;
