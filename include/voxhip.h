@@ -378,6 +378,40 @@ vx_status vx_grid_surface(const vx_grid* g, float* host_xyz, uint64_t vertex_cap
 /* a mesh that owns its arrays, equal in everything observable to vx_mesh_from_arrays(the vx_grid_surface arrays) followed, with
  * with_materials, by vx_mesh_set_materials(vx_grid_materials records, the triangle ids); usable by vx_bvh_*, vx_render_*, vx_voxelize */
 vx_status vx_grid_surface_mesh(const vx_grid* g, int with_materials, vx_mesh** out);
+/* Surface nets: the mesh of vx_grid_surface with relaxed vertex positions and, optionally, vertex normals.  M, the lattice points, their
+ * index and order, the faces, tri and mat are those of vx_grid_surface, word for word; a cell outside the grid is empty.  All float32, no
+ * contraction; / and sqrtf correctly rounded.
+ * Initial offset.  Vertex v is lattice point p = (i, j, k).  Its block is the eight cells (i-1+a, j-1+b, k-1+e), a, b, e in {0, 1}.  Each of
+ * the block's twelve edges joins two cells that differ in one axis A; an edge crosses when exactly one of its two cells is in M.  n = the
+ * number of crossing edges (3..12 for every vertex).  T_x = the sum, over crossing edges NOT along x, of (2a - 1), a the edge's x bit; T_y,
+ * T_z likewise.  The offset in cells from p, per axis: u0 = (float)T / (float)(2*n), in [-1/3, 1/3].
+ * Neighbours.  Directions in the order -X, +X, -Y, +Y, -Z, +Z.  q = p +- e_A is a neighbour when q is a lattice point of the grid and the
+ * four cells around lattice edge pq are neither all in M nor all out; q is then always a vertex.  m = the number of neighbours (>= 3).
+ * One step with weight w (Jacobi: every vertex reads the previous field).  s = (+0, +0, +0); for each neighbour q in direction d, in
+ * direction order, s = s + r with r = u_q, except on d's axis, where r = (+-1.0f) + u_q.  mean = s / (float)m.  t = u + w*(mean - u),
+ * evaluated as written.  u' = fminf(fmaxf(t, -0.5f), 0.5f) per axis (the vertex stays in its dual cube).
+ * Parameters.  One iteration is a step with lambda, then a step with mu if mu != 0.  iterations <= 1024, lambda finite in [0, 1], mu finite
+ * in [-1, 0]; anything else is VX_ERR_INVALID_ARG.  iterations = 0 gives u0.
+ * World position, per axis: org + (((float)i + 0.5f) + u)*vs - half.  With u = +0 this is vx_grid_surface's position, bit for bit.
+ * Normals (optional, 3 f32 per vertex), from the final world positions P.  Over the block's twelve internal faces in this order: axis
+ * A = x, y, z, then the other two bits (b, e) = 00, 10, 01, 11 with the first of the other two axes fastest.  A face counts when its two
+ * cells differ; it is then the face (c, d) of its occupied cell, corners c0..c3 from vx_grid_surface's table.  a = P(c2) - P(c0),
+ * b = P(c3) - P(c1); N += (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), every product and difference rounded, N from +0.
+ * l = sqrtf((N.x*N.x + N.y*N.y) + N.z*N.z); the normal is N/l per component when l > 0 and finite, else (0, 0, 0).
+ * The size query, the capacity rule, the 2^31 - 1 limit, the NULL checks, the 0-cell grid, materials and "no side effects" are those of
+ * vx_grid_surface; dev_mat and dev_normals may be NULL.  Order of checks: NULL arguments and a bad vx_smooth first, then everything else as
+ * vx_grid_surface does.  Every failure writes nothing.  The _device variant waits on the host for V and T only; everything else, all
+ * iterations included, is queued back to back on the grid's stream.  Scratch stays on the handle. */
+typedef struct vx_smooth { uint32_t iterations; float lambda; float mu; } vx_smooth;
+vx_status vx_grid_surface_smooth_device(const vx_grid* g, const vx_smooth* params, float* dev_xyz, uint64_t vertex_capacity, int32_t* dev_tri,
+                                        uint64_t triangle_capacity, int32_t* dev_mat, float* dev_normals, uint64_t* num_vertices,
+                                        uint64_t* num_triangles);
+vx_status vx_grid_surface_smooth(const vx_grid* g, const vx_smooth* params, float* host_xyz, uint64_t vertex_capacity, int32_t* host_tri,
+                                 uint64_t triangle_capacity, int32_t* host_mat, float* host_normals, uint64_t* num_vertices,
+                                 uint64_t* num_triangles);
+/* as vx_grid_surface_mesh; with_normals: vx_mesh_set_attributes with the three vertex normals of each triangle's corners, so that
+ * VX_RENDER_ATTRIBUTES frames shade the mesh smoothly */
+vx_status vx_grid_surface_smooth_mesh(const vx_grid* g, const vx_smooth* params, int with_materials, int with_normals, vx_mesh** out);
 /* Connected components of the bitmask M (as it stands when the call is queued, as for the distance fields).  Two cells of M are adjacent
  * under VX_CONNECT_6 when they share a face, under VX_CONNECT_26 when they share a face, an edge or a corner; only cells of the grid count
  * (nothing wraps, no padding).  A component is a maximal set of cells of M that adjacency joins.  Labels: one uint32 per cell at

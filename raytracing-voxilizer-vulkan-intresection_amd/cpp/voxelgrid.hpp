@@ -210,6 +210,23 @@ public:
         if (nv || nt) vxdetail::check(vx_grid_surface(m_grid.get(), xyz.data(), nv, tris.data(), nt, mats ? mats->data() : nullptr, &nv, &nt));
     }
 
+    // The surface-nets mesh of the occupancy (vx_grid_surface_smooth): surface()'s vertices and triangles, the positions relaxed inside
+    // their dual cubes by params.iterations x (a step with lambda, a step with mu).  normals (optional): 3 floats per vertex.
+    void smoothSurface(const vx_smooth& params, std::vector<float>& xyz, std::vector<int32_t>& tris, std::vector<int32_t>* mats = nullptr,
+                       std::vector<float>* normals = nullptr) const
+    {
+        uint64_t nv = 0, nt = 0;
+        int32_t probe = 0;
+        vxdetail::check(vx_grid_surface_smooth(m_grid.get(), &params, nullptr, 0, nullptr, 0, mats ? &probe : nullptr, nullptr, &nv, &nt));
+        xyz.assign(nv * 3, 0.0f);
+        tris.assign(nt * 3, 0);
+        if (mats) mats->assign(nt, 0);
+        if (normals) normals->assign(nv * 3, 0.0f);
+        if (nv || nt)
+            vxdetail::check(vx_grid_surface_smooth(m_grid.get(), &params, xyz.data(), nv, tris.data(), nt, mats ? mats->data() : nullptr,
+                                                   normals ? normals->data() : nullptr, &nv, &nt));
+    }
+
     // Connected components of the occupancy (vx_grid_components): connectivity 6 (shared faces) or 26 (faces, edges, corners).  labels
     // gets one value per cell at x + X*(y + Y*z): 0 for empty cells, 1..K in ascending order of each component's smallest cell.  Returns K.
     uint32_t components(int connectivity, std::vector<uint32_t>& labels) const

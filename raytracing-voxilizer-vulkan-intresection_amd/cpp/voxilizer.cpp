@@ -51,6 +51,11 @@
 //                                       --materials also FILE.mtl (one `newmtl m<id>` per grid material) and a `usemtl m<id>` before each run
 //                                       of equal ids.  bool / aabbstruct / vec, with or without --solid; not with --grid octree, --gpus N > 1,
 //                                       --bench, or --materials with --grid vec
+//   --surface FILE.obj --smooth N[:LAMBDA:MU]
+//                                       the surface-nets mesh instead (vx_grid_surface_smooth: the same vertices and triangles, positions
+//                                       relaxed by N iterations of a step with LAMBDA, then one with MU; default 0.5:-0.53), with one `vn` line
+//                                       per vertex after the `v` lines and faces written `f a//a b//b c//c`; the usemtl runs as above.
+//                                       Refused without --surface
 //   --xray FILE.pgm [--size WxH]        how many voxels each camera ray of --render meets (vx_trace_multi's count), as a binary 16-bit PGM
 //                                       (big-endian, min(count, 65535) per pixel); --camera-dump FILE as for --render
 //   --grid octree --octree-xray FILE.pgm [--size WxH]
@@ -342,13 +347,34 @@ int render(Trace trace, const std::string& file, uint32_t W, uint32_t H, const R
     return 0;
 }
 
+// --smooth N[:LAMBDA:MU]: the surface-nets parameters of --surface
+struct SmoothOpt {
+    bool on = false;
+    vx_smooth p{0u, 0.5f, -0.53f};
+};
+SmoothOpt g_smooth;
+
+bool parse_smooth(const char* s, SmoothOpt* o)
+{
+    unsigned n = 0;
+    float lam = 0.5f, mu = -0.53f;
+    char tail = 0;
+    if (s[0] == '-' || (std::sscanf(s, "%u:%f:%f%c", &n, &lam, &mu, &tail) != 3 && std::sscanf(s, "%u%c", &n, &tail) != 1)) return false;
+    if (n > 1024u || !(lam >= 0.0f && lam <= 1.0f) || !(mu >= -1.0f && mu <= 0.0f)) return false;
+    o->on = true;
+    o->p = vx_smooth{n, lam, mu};
+    return true;
+}
+
 // --surface: the grid's boundary mesh as an OBJ (and, with materials, its MTL beside it)
 template <class T>
 void write_surface(const T& vox, const std::string& file, bool materials)
 {
     std::vector<float> xyz;
     std::vector<int32_t> tris, mats;
-    vox.surface(xyz, tris, materials ? &mats : nullptr);
+    std::vector<float> normals;
+    if (g_smooth.on) vox.smoothSurface(g_smooth.p, xyz, tris, materials ? &mats : nullptr, &normals);
+    else vox.surface(xyz, tris, materials ? &mats : nullptr);
     std::FILE* f = std::fopen(file.c_str(), "w");
     if (!f) throw std::runtime_error("cannot write " + file);
     if (materials) {
@@ -376,9 +402,12 @@ void write_surface(const T& vox, const std::string& file, bool materials)
         std::fprintf(f, "mtllib %s\n", s2 == std::string::npos ? mtl.c_str() : mtl.c_str() + s2 + 1);
     }
     for (size_t i = 0; i < xyz.size(); i += 3) std::fprintf(f, "v %.9g %.9g %.9g\n", (double)xyz[i], (double)xyz[i + 1], (double)xyz[i + 2]);
+    for (size_t i = 0; i < normals.size(); i += 3) std::fprintf(f, "vn %.9g %.9g %.9g\n", (double)normals[i], (double)normals[i + 1], (double)normals[i + 2]);
     for (size_t t = 0; t < tris.size() / 3; ++t) {
         if (materials && (t == 0 || mats[t] != mats[t - 1])) std::fprintf(f, "usemtl m%d\n", (int)mats[t]);
-        std::fprintf(f, "f %d %d %d\n", tris[3 * t] + 1, tris[3 * t + 1] + 1, tris[3 * t + 2] + 1);
+        const int a = tris[3 * t] + 1, b = tris[3 * t + 1] + 1, c = tris[3 * t + 2] + 1;
+        if (g_smooth.on) std::fprintf(f, "f %d//%d %d//%d %d//%d\n", a, a, b, b, c, c);
+        else std::fprintf(f, "f %d %d %d\n", a, b, c);
     }
     const bool ok = std::ferror(f) == 0;
     if (std::fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + file);
@@ -574,7 +603,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--surface FILE.obj] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--surface FILE.obj [--smooth N[:LAMBDA:MU]]] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
                      argv[0]);
         return 2;
     }
@@ -605,6 +634,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--seal") && i + 1 < argc) { g_morph.op = 4; if (!parse_radius(argv[++i], &g_morph.r2)) { std::fprintf(stderr, "bad --seal '%s': a radius >= 0 in cells\n", argv[i]); return 2; } }
         else if (!std::strcmp(argv[i], "--sdf") && i + 1 < argc) sdfFile = argv[++i];
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--smooth") && i + 1 < argc) { if (!parse_smooth(argv[++i], &g_smooth)) { std::fprintf(stderr, "bad --smooth '%s': N[:LAMBDA:MU] with N <= 1024, LAMBDA in [0, 1] and MU in [-1, 0]\n", argv[i]); return 2; } }
         else if (!std::strcmp(argv[i], "--components") && i + 1 < argc) componentsFile = argv[++i];
         else if (!std::strcmp(argv[i], "--xray") && i + 1 < argc) xrayFile = argv[++i];
         else if (!std::strcmp(argv[i], "--octree-xray") && i + 1 < argc) octreeXrayFile = argv[++i];
@@ -646,6 +676,10 @@ int main(int argc, char** argv)
     }
     if (!surfaceFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0 || (materials && grid == "vec"))) {
         std::fprintf(stderr, "--surface writes the boundary mesh of one grid on one device: not with --grid octree, --gpus N > 1, --bench, or --materials with --grid vec\n");
+        return 2;
+    }
+    if (g_smooth.on && surfaceFile.empty()) {
+        std::fprintf(stderr, "--smooth relaxes the mesh that --surface writes: it needs --surface FILE.obj\n");
         return 2;
     }
     if (!componentsFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {

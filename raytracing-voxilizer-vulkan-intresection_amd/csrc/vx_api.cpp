@@ -526,6 +526,7 @@ struct vx_grid : Home {
     DevBuf morph_a{this}, morph_b{this}, morph_p{this}, morph_d{this}, morph_out{this};
     // surface mesh (vx_surface.hip): triangles per mask word and their scan, the used lattice points and their scan, the host variant's arrays
     DevBuf surf_cnt{this}, surf_tpre{this}, surf_cm{this}, surf_vpre{this}, surf_out{this};
+    DevBuf nets_buf{this};  // surface nets: lattice index, neighbour table, two offset fields, configuration per vertex
     // connected components (vx_components.hip): the root bitmask and its scan, the host variants' labels, the statistics
     DevBuf cc_roots{this}, cc_rpre{this}, cc_lab{this}, cc_stat{this};
     uint64_t interior = 0;        // |H| of the last build or fill on the handle (vx_grid_interior)
@@ -2777,6 +2778,109 @@ vx_status vx_grid_surface_mesh(const vx_grid* gc, int with_materials, vx_mesh** 
         const vx_status st = vx_mesh_set_materials(m, gc->materials.data(), gc->materials.size(), mat.data());
         if (st != VX_OK) { vx_mesh_free(m); return st; }
     }
+    *out = m;
+    return VX_OK;
+}
+
+// Surface nets: vx_grid_surface's count, scans, wait and triangles; the positions from the relaxation instead of k_surf_verts, and
+// optionally the vertex normals (vx_surface.hip).  Everything after the wait for V and T is queued back to back.
+static vx_status smooth_params(const vx_smooth* sp)
+{
+    if (!sp) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (sp->iterations > 1024u) return fail(VX_ERR_INVALID_ARG, "vx_smooth: iterations above 1024");
+    if (!(sp->lambda >= 0.0f && sp->lambda <= 1.0f)) return fail(VX_ERR_INVALID_ARG, "vx_smooth: lambda must be finite in [0, 1]");
+    if (!(sp->mu >= -1.0f && sp->mu <= 0.0f)) return fail(VX_ERR_INVALID_ARG, "vx_smooth: mu must be finite in [-1, 0]");
+    return VX_OK;
+}
+
+static vx_status smooth_run(vx_grid* g, const vx_smooth* sp, bool host, float* xyz, uint64_t vcap, int32_t* tri, uint64_t tcap, int32_t* mat,
+                            float* normals, uint64_t* num_vertices, uint64_t* num_triangles)
+{
+    VX_TRY(smooth_params(sp));
+    if ((vcap || tcap) && (!xyz || !tri)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    DeviceGuard dg(g->device);
+    uint64_t nv = 0, nt = 0;
+    const int16_t* ids = nullptr;
+    VX_TRY(surface_count(g, mat != nullptr, &nv, &nt, &ids));
+    if (num_vertices) *num_vertices = nv;
+    if (num_triangles) *num_triangles = nt;
+    VX_TRY(surface_check(nv, nt, vcap, tcap));
+    if ((!vcap && !tcap) || (!nv && !nt)) return VX_OK;
+    const vx::SurfacePlan p = vx::surface_plan(g->g);
+    float* dx = xyz;
+    int32_t* dt = tri;
+    int32_t* dm = mat;
+    float* dn = normals;
+    if (host) {  // one staging block: positions, normals, triangles, ids
+        VX_HIP(g->surf_out.ensure((size_t)nv * 12 + (normals ? (size_t)nv * 12 : 0) + (size_t)nt * 12 + (mat ? (size_t)nt * 4 : 0) + 16));
+        dx = g->surf_out.as<float>();
+        dn = normals ? dx + 3 * nv : nullptr;
+        dt = reinterpret_cast<int32_t*>(dx + (normals ? 6 : 3) * nv);
+        dm = mat ? dt + 3 * nt : nullptr;
+    }
+    vx::NetsBufs nb;
+    VX_HIP(g->nets_buf.ensure(vx::nets_bytes(nv, nullptr)));
+    nb.base = g->nets_buf.p;
+    vx::nets_bytes(nv, &nb);
+    vx::launch_surface_nets(g->words.as<uint32_t>(), g->g, p, g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(), nv, nb, sp->iterations,
+                            sp->lambda, sp->mu, dx, dn, g->stream);
+    vx::launch_surface_tris(g->words.as<uint32_t>(), g->g, g->surf_tpre.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(),
+                            mat ? g->wprefix.as<uint32_t>() : nullptr, ids, dt, dm, g->stream);
+    VX_HIP(hipGetLastError());
+    if (host) {
+        VX_HIP(hipMemcpyAsync(xyz, dx, (size_t)nv * 12, hipMemcpyDeviceToHost, g->stream));
+        VX_HIP(hipMemcpyAsync(tri, dt, (size_t)nt * 12, hipMemcpyDeviceToHost, g->stream));
+        if (mat) VX_HIP(hipMemcpyAsync(mat, dm, (size_t)nt * 4, hipMemcpyDeviceToHost, g->stream));
+        if (normals) VX_HIP(hipMemcpyAsync(normals, dn, (size_t)nv * 12, hipMemcpyDeviceToHost, g->stream));
+        VX_HIP(hipStreamSynchronize(g->stream));
+    }
+    return VX_OK;
+}
+
+vx_status vx_grid_surface_smooth_device(const vx_grid* gc, const vx_smooth* params, float* dev_xyz, uint64_t vertex_capacity, int32_t* dev_tri,
+                                        uint64_t triangle_capacity, int32_t* dev_mat, float* dev_normals, uint64_t* num_vertices,
+                                        uint64_t* num_triangles)
+{
+    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return smooth_run(const_cast<vx_grid*>(gc), params, false, dev_xyz, vertex_capacity, dev_tri, triangle_capacity, dev_mat, dev_normals,
+                      num_vertices, num_triangles);
+}
+
+vx_status vx_grid_surface_smooth(const vx_grid* gc, const vx_smooth* params, float* host_xyz, uint64_t vertex_capacity, int32_t* host_tri,
+                                 uint64_t triangle_capacity, int32_t* host_mat, float* host_normals, uint64_t* num_vertices,
+                                 uint64_t* num_triangles)
+{
+    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return smooth_run(const_cast<vx_grid*>(gc), params, true, host_xyz, vertex_capacity, host_tri, triangle_capacity, host_mat, host_normals,
+                      num_vertices, num_triangles);
+}
+
+vx_status vx_grid_surface_smooth_mesh(const vx_grid* gc, const vx_smooth* params, int with_materials, int with_normals, vx_mesh** out)
+{
+    if (!gc || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    VX_TRY(smooth_params(params));
+    if (with_materials) {
+        const int16_t* ids = nullptr;
+        VX_TRY(surface_materials(gc, &ids));
+    }
+    uint64_t nv = 0, nt = 0;
+    VX_TRY(vx_grid_surface(gc, nullptr, 0, nullptr, 0, nullptr, &nv, &nt));
+    std::vector<float> xyz((size_t)nv * 3 + 1), nrm(with_normals ? (size_t)nv * 3 + 1 : 0);
+    std::vector<int32_t> tri((size_t)nt * 3 + 1), mat(with_materials ? (size_t)nt + 1 : 0);
+    if (nv || nt)
+        VX_TRY(vx_grid_surface_smooth(gc, params, xyz.data(), nv, tri.data(), nt, with_materials ? mat.data() : nullptr,
+                                      with_normals ? nrm.data() : nullptr, &nv, &nt));
+    vx_mesh* m = nullptr;
+    VX_TRY(vx_mesh_from_arrays(xyz.data(), (size_t)nv, tri.data(), (size_t)nt, &m));
+    vx_status st = VX_OK;
+    if (with_materials) st = vx_mesh_set_materials(m, gc->materials.data(), gc->materials.size(), mat.data());
+    if (st == VX_OK && with_normals) {  // per triangle, its three corners' vertex normals
+        std::vector<float> cn((size_t)nt * 9 + 1);
+        for (size_t c = 0; c < (size_t)nt * 3; ++c)
+            for (int a = 0; a < 3; ++a) cn[c * 3 + a] = nrm[(size_t)tri[c] * 3 + a];
+        st = vx_mesh_set_attributes(m, cn.data(), nullptr);
+    }
+    if (st != VX_OK) { vx_mesh_free(m); return st; }
     *out = m;
     return VX_OK;
 }

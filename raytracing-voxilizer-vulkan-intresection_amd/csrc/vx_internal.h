@@ -503,6 +503,24 @@ void launch_surface_count(const uint32_t* words, const GridParams& g, const Surf
 void launch_surface_emit(const uint32_t* words, const GridParams& g, const SurfacePlan& p, const uint32_t* tpre, const uint32_t* cmask,
                          const uint32_t* vpre, const uint32_t* wprefix, const int16_t* cell_mat, float* xyz, int32_t* tri, int32_t* mat,
                          hipStream_t s);
+// the triangles and ids alone (k_surf_emit)
+void launch_surface_tris(const uint32_t* words, const GridParams& g, const uint32_t* tpre, const uint32_t* cmask, const uint32_t* vpre,
+                         const uint32_t* wprefix, const int16_t* cell_mat, int32_t* tri, int32_t* mat, hipStream_t s);
+// Surface nets (vx_grid_surface_smooth*): per-vertex scratch carved from one block.  lat: lattice index; nb: the six neighbours' vertex
+// indices, nb[d * V + v], -1 = none; u[2]: the offsets in cells, ping-pong; cfg: the 2x2x2 block configuration.
+struct NetsBufs {
+    void* base = nullptr;
+    uint64_t* lat = nullptr;
+    int32_t* nb = nullptr;
+    float* u[2] = {nullptr, nullptr};
+    uint8_t* cfg = nullptr;
+};
+// bytes of the block for V vertices; with b->base set, also the pointers into it
+size_t nets_bytes(uint64_t V, NetsBufs* b);
+// after the count and both scans (cmask, vpre, V known to the host): configuration and u0, `iterations` x (a step with lambda, a step with
+// mu when mu != 0), the positions into xyz and, when normals is non-null, the vertex normals; all queued back to back on s
+void launch_surface_nets(const uint32_t* words, const GridParams& g, const SurfacePlan& p, const uint32_t* cmask, const uint32_t* vpre,
+                         uint64_t V, const NetsBufs& b, uint32_t iterations, float lambda, float mu, float* xyz, float* normals, hipStream_t s);
 
 // Connected components (vx_components.hip), X*Y*Z <= 2^32 - 1.  launch_components: labels (X*Y*Z) receives parent = the smallest cell of
 // the component for the occupied cells (empty slots untouched), roots (nwords) the root bitmask.  launch_components_label: rpre = the

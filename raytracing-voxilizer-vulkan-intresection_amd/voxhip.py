@@ -136,6 +136,11 @@ class VoxelizeOpts(C.Structure):
                 ("tri_begin", C.c_uint64), ("tri_end", C.c_uint64), ("stream", C.c_void_p), ("shard_rank", C.c_int32), ("shard_world", C.c_int32)]
 
 
+class Smooth(C.Structure):
+    """vx_smooth: iterations x (a step with lambda, then a step with mu when mu != 0)"""
+    _fields_ = [("iterations", C.c_uint32), ("lam", C.c_float), ("mu", C.c_float)]
+
+
 class ScanArgs(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("nscans", C.c_uint32), ("sizes", C.c_void_p), ("paths", C.c_void_p), ("inp", C.c_void_p), ("out", C.c_void_p),
                 ("totals", C.c_void_p), ("taken", C.c_void_p), ("clean", C.c_void_p), ("sel", C.c_void_p), ("group16", C.c_void_p),
@@ -219,6 +224,7 @@ SYMBOLS = [
     "vx_grid_distance_sq_device", "vx_grid_distance_sq", "vx_grid_sdf_device", "vx_grid_sdf",
     "vx_grid_morph_device", "vx_grid_morph_mask", "vx_grid_morph", "vx_grid_seal", "vx_morph_bit_radius",
     "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh",
+    "vx_grid_surface_smooth_device", "vx_grid_surface_smooth", "vx_grid_surface_smooth_mesh",
     "vx_grid_components_device", "vx_grid_components", "vx_grid_component_stats", "vx_grid_aabbs",
     "vx_grid_aabbs_device", "vx_grid_bind_aabbs_device", "vx_grid_list_wait", "vx_grid_aabbs_device_async", "vx_grid_materials", "vx_grid_material_ids", "vx_grid_material_ids_device", "vx_grid_material_first_use",
     "vx_grid_finish_materials", "vx_multi_create", "vx_multi_voxelize", "vx_multi_grid", "vx_multi_release_grid", "vx_multi_free", "vx_sort_u64", "vx_scan_u32", "vx_grid_free",
@@ -357,6 +363,9 @@ def lib():
     L.vx_grid_surface_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, u64p, u64p]
     L.vx_grid_surface.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, u64p, u64p]
     L.vx_grid_surface_mesh.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.vx_grid_surface_smooth_device.argtypes = [vp, C.POINTER(Smooth), vp, C.c_uint64, vp, C.c_uint64, vp, vp, u64p, u64p]
+    L.vx_grid_surface_smooth.argtypes = [vp, C.POINTER(Smooth), vp, C.c_uint64, vp, C.c_uint64, vp, vp, u64p, u64p]
+    L.vx_grid_surface_smooth_mesh.argtypes = [vp, C.POINTER(Smooth), C.c_int, C.c_int, C.POINTER(vp)]
     L.vx_grid_components_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp]
     L.vx_grid_components.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.vx_grid_component_stats.argtypes = [vp, C.c_uint32, vp, C.c_uint64, u64p]
@@ -926,6 +935,56 @@ class Grid:
         """vx_grid_surface_mesh: the boundary mesh as a Mesh (with materials: the grid's records and one id per triangle)."""
         h = C.c_void_p()
         _check(lib().vx_grid_surface_mesh(self.h, 1 if materials else 0, C.byref(h)))
+        return Mesh(h)
+
+    def _smooth_counts(self, iterations, lam, mu, materials):
+        """(vx_smooth, V, T): vx_grid_surface_smooth's size query, which also checks the parameters and, with materials, the ids"""
+        sp = Smooth(iterations, lam, mu)
+        nv, nt = C.c_uint64(), C.c_uint64()
+        probe = np.zeros(1, np.int32)
+        _check(lib().vx_grid_surface_smooth(self.h, C.byref(sp), None, 0, None, 0, probe.ctypes.data if materials else None, None, C.byref(nv),
+                                            C.byref(nt)))
+        return sp, nv.value, nt.value
+
+    def surface_smooth(self, iterations=8, lam=0.5, mu=-0.53, materials=False, normals=False):
+        """vx_grid_surface_smooth: the surface-nets mesh -> (verts (V, 3) float32, tris (T, 3) int32[, mats (T,) int32][, normals (V, 3)
+        float32]): vx_grid_surface's vertices and triangles, the positions relaxed by `iterations` x (a step with lam, a step with mu)."""
+        sp, nv, nt = self._smooth_counts(iterations, lam, mu, materials)
+        v = np.zeros((nv, 3), np.float32)
+        t = np.zeros((nt, 3), np.int32)
+        m = np.zeros(nt, np.int32) if materials else None
+        n = np.zeros((nv, 3), np.float32) if normals else None
+        if nv or nt:
+            a, b = C.c_uint64(), C.c_uint64()
+            _check(lib().vx_grid_surface_smooth(self.h, C.byref(sp), v.ctypes.data, nv, t.ctypes.data, nt, m.ctypes.data if materials else None,
+                                                n.ctypes.data if normals else None, C.byref(a), C.byref(b)))
+        return (v, t) + ((m,) if materials else ()) + ((n,) if normals else ())
+
+    def surface_smooth_device(self, iterations=8, lam=0.5, mu=-0.53, materials=False, normals=False):
+        """vx_grid_surface_smooth_device: the same arrays as device torch tensors, written asynchronously on the grid's stream (the host
+        waits for the two counts only)."""
+        import torch
+        sp, nv, nt = self._smooth_counts(iterations, lam, mu, materials)
+        v = torch.empty((nv, 3), dtype=torch.float32, device="cuda")
+        t = torch.empty((nt, 3), dtype=torch.int32, device="cuda")
+        m = torch.empty(nt, dtype=torch.int32, device="cuda") if materials else None
+        n = torch.empty((nv, 3), dtype=torch.float32, device="cuda") if normals else None
+        if nv or nt:
+            a, b = C.c_uint64(), C.c_uint64()
+            _check(lib().vx_grid_surface_smooth_device(self.h, C.byref(sp), v.data_ptr(), nv, t.data_ptr(), nt, m.data_ptr() if materials else None,
+                                                       n.data_ptr() if normals else None, C.byref(a), C.byref(b)))
+        out = (v, t) + ((m,) if materials else ()) + ((n,) if normals else ())
+        if nv or nt:
+            for x in out:
+                self._record(x)
+        return out
+
+    def surface_smooth_mesh(self, iterations=8, lam=0.5, mu=-0.53, materials=False, normals=False):
+        """vx_grid_surface_smooth_mesh: the surface-nets mesh as a Mesh (with normals: corner normals from the vertex normals, so an
+        attributes renderer shades it smoothly)."""
+        sp = Smooth(iterations, lam, mu)
+        h = C.c_void_p()
+        _check(lib().vx_grid_surface_smooth_mesh(self.h, C.byref(sp), 1 if materials else 0, 1 if normals else 0, C.byref(h)))
         return Mesh(h)
 
     def components(self, connectivity=CONNECT_6):
