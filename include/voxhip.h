@@ -780,6 +780,25 @@ void vx_tlas_free(vx_tlas* t);   /* waits for the TLAS's stream */
  * Light: position / intensity / type as the reference's push constants (hello_vulkan.h:84-90); NULL = its default, a point light at
  * {10, 55, 8} of intensity 1000.  Type 1 (directional, rchit:86-91): L = position * (1 / |position|), light distance 100000 (the shadow
  * ray's tMax), intensity not divided by the squared distance.
+ * Shading at its extremes.  Every max / min of the shading is IEEE maxNum / minNum (fmaxf / fminf: the operand that is not NaN), and every
+ * input below is a value the frame is defined for -- the stated float32 formula, evaluated as written:
+ *   colour     a channel that is NaN before the gamma encodes as 0, +Inf as 255, -Inf and every negative as 0 (clamp = fminf(fmaxf(c, 0), 1));
+ *   shininess  kSh = fmaxf(shininess, 4): a NaN shininess is 4;
+ *   dot(N, L)  NaN is "not lit": shadowed = 0, the shadow ray gets the empty interval (tMax 0 below tMin), the diffuse factor
+ *              fmaxf(dot, 0) is 0, and the attenuation is that of a hit facing away from the light -- 1 for a triangle, 0.3 for a voxel;
+ *   light      position and intensity are any float32 values, non-finite ones included; kind never depends on the light.  With
+ *              len = sqrtf(dot(l, l)) and L = l * (1 / len): a len of +Inf (dot overflows) gives 1 / len = 0 and L = 0, a non-finite l gives a
+ *              NaN in L, and both are "not lit"; so are len = 0 with l = 0 (0 * Inf) and any L that has a NaN where N is not 0.  A lit pixel
+ *              therefore has a finite shadow ray, with one exception: l != 0 so short that dot(l, l) underflows to 0 (|l| below about
+ *              1e-23) has L = +-Inf in every component (NaN where l is 0), and a pixel whose N and l are non-zero in all three may be lit;
+ *              its shadow ray is non-finite and, by the rule for non-finite rays above, hits nothing;
+ *   material   ambient, diffuse, specular and shininess are any float32 values (negative, above 1, non-finite); illum is any int32
+ *              (>= 1 adds the ambient term, >= 2 the specular one: 0 and negatives add neither, 3 and above both).  vx_mesh_set_materials
+ *              refuses a triangle id below -1 or at or above the table size (-1: no material, MaterialObj{}); a texture slot may be any int32
+ *              (negative or at or above vx_mesh_num_textures: no texture).
+ * Everything before the two powf calls (the specular term, the gamma) is float32 with its association pinned, so a byte differs from
+ * floor(255 * c^(1/2.2) + 0.5), evaluated with both powers in float64 from their float32 arguments, only where 255 * c^(1/2.2) lies within
+ * 2^-12 of a rounding tie, and then by 1 (tests/shading_extremes.py).
  * Streams: a frame runs on the scene's stream.  It first makes that stream wait for the work queued so far on the voxel source's and the
  * BVH's streams, and at its end makes those streams wait for the frame -- a later vx_voxelize_into / vx_bvh_build_into on them cannot
  * overwrite what the frame still reads.  The grid's traversal structure is built lazily on the grid's own stream, as for vx_trace_ex.

@@ -127,7 +127,7 @@ def shade(d, kind, vnormal, tnormal, L, dist, sv, sm, light=render_ref.DEFAULT_L
     mat = {k: np.where(tri[:, None] if vmat[k].ndim == 2 else tri, mmat[k], vmat[k]) for k in vmat}
     li = np.full(n, F(intensity), F) if ltype == 1 else F(intensity) / (dist * dist)
     dnl0 = render_ref._dot(N, L)
-    dnl = np.maximum(dnl0, F(0))
+    dnl = np.fmax(dnl0, F(0))
     diff = mat["diffuse"] * dnl[:, None]
     diff = np.where((mat["illum"] >= 1)[:, None], diff + mat["ambient"], diff)
     if tex is not None:
@@ -138,18 +138,18 @@ def shade(d, kind, vnormal, tnormal, L, dist, sv, sm, light=render_ref.DEFAULT_L
     spec = np.zeros_like(diff)
     s = lit & ~sh & (mat["illum"] >= 2) & (kind > 0)
     if s.any():
-        kSh = np.maximum(mat["shininess"][s], F(4))
+        kSh = np.fmax(mat["shininess"][s], F(4))
         kE = (F(2) + kSh) / (F(2) * F(3.14159265))
         e = d[s] * F(-1)
         V = e / np.sqrt(render_ref._dot(e, e))[:, None]
         I = L[s] * F(-1)
         Rr = I - N[s] * (F(2) * render_ref._dot(N[s], I))[:, None]
-        sp = kE * np.power(np.maximum(render_ref._dot(V, Rr), F(0)), kSh)
+        sp = kE * np.power(np.fmax(render_ref._dot(V, Rr), F(0)), kSh)
         spec[s] = mat["specular"][s] * sp[:, None]
     c = (li * att)[:, None] * (diff + spec)
     c[kind == 0] = render_ref.MISS
-    g = np.power(np.minimum(np.maximum(c, F(0)), F(1)), F(1.0) / F(2.2))
-    rgb = np.floor(g * F(255) + F(0.5)).astype(np.uint8)
+    g = np.power(np.fmin(np.fmax(c, F(0)), F(1)), F(1.0) / F(2.2))       # fmaxf / fminf: a NaN channel is 0, so g is in [0, 1]
+    rgb = np.floor(np.nan_to_num(g, nan=0.0) * F(255) + F(0.5)).astype(np.uint8)
     rgba = np.concatenate([rgb, np.full((n, 1), 255, np.uint8)], 1)
     return rgba, (sh & (kind > 0)).astype(np.uint8)
 

@@ -87,7 +87,7 @@ def shade(d, kind, vnormal, mnormal, L, dist, sv, sm, light=DEFAULT_LIGHT, vmat=
     mat = {k: np.where(tri[:, None] if vmat[k].ndim == 2 else tri, mmat[k], vmat[k]) for k in vmat}
     li = np.full(n, F(intensity), F) if ltype == 1 else F(intensity) / (dist * dist)   # rchit:83 / :85
     dnl0 = _dot(N, L)
-    dnl = np.maximum(dnl0, F(0))                                        # computeDiffuse, wavefront.glsl:25
+    dnl = np.fmax(dnl0, F(0))                                           # computeDiffuse, wavefront.glsl:25
     diff = mat["diffuse"] * dnl[:, None]
     diff = np.where((mat["illum"] >= 1)[:, None], diff + mat["ambient"], diff)
     lit = dnl0 > 0
@@ -96,17 +96,17 @@ def shade(d, kind, vnormal, mnormal, L, dist, sv, sm, light=DEFAULT_LIGHT, vmat=
     spec = np.zeros_like(diff)
     s = lit & ~sh & (mat["illum"] >= 2) & (kind > 0)
     if s.any():                                                          # computeSpecular, wavefront.glsl:32-48
-        kSh = np.maximum(mat["shininess"][s], F(4))
+        kSh = np.fmax(mat["shininess"][s], F(4))
         kE = (F(2) + kSh) / (F(2) * F(3.14159265))
         e = d[s] * F(-1)
         V = e / np.sqrt(_dot(e, e))[:, None]
         I = L[s] * F(-1)
         Rr = I - N[s] * (F(2) * _dot(N[s], I))[:, None]
-        sp = kE * np.power(np.maximum(_dot(V, Rr), F(0)), kSh)
+        sp = kE * np.power(np.fmax(_dot(V, Rr), F(0)), kSh)
         spec[s] = mat["specular"][s] * sp[:, None]
     c = (li * att)[:, None] * (diff + spec)
     c[kind == 0] = MISS
-    g = np.power(np.minimum(np.maximum(c, F(0)), F(1)), F(1.0) / F(2.2))    # post.frag:36
-    rgb = np.floor(g * F(255) + F(0.5)).astype(np.uint8)
+    g = np.power(np.fmin(np.fmax(c, F(0)), F(1)), F(1.0) / F(2.2))    # post.frag:36; fmaxf / fminf: a NaN channel is 0, so g is in [0, 1]
+    rgb = np.floor(np.nan_to_num(g, nan=0.0) * F(255) + F(0.5)).astype(np.uint8)
     rgba = np.concatenate([rgb, np.full((n, 1), 255, np.uint8)], 1)
     return rgba, (sh & (kind > 0)).astype(np.uint8)
