@@ -310,6 +310,32 @@ vx_status vx_grid_distance_sq_device(const vx_grid* g, uint32_t flags, uint32_t*
 vx_status vx_grid_distance_sq(const vx_grid* g, uint32_t flags, uint32_t* host_out, uint64_t capacity);
 vx_status vx_grid_sdf_device(const vx_grid* g, float* dev_out, uint64_t capacity);
 vx_status vx_grid_sdf(const vx_grid* g, float* host_out, uint64_t capacity);
+/* The feature transform: WHICH cell the distance fields' minimum belongs to.  i(c) = x + X*(y + Y*z) is the index of cell c; T is the target
+ * set of vx_grid_distance_sq with the same flags (flags 0: the occupied cells M of the bitmask as it stands when the call is queued;
+ * VX_DISTANCE_INSIDE: the empty cells of the grid).
+ *   N(c) = min { i(o) : o in T, |c - o|^2 = min over p in T of |c - p|^2 }
+ * -- the nearest target cell, and among several at the same exact squared distance the one of the smallest index (the smallest z, then the
+ * smallest y, then the smallest x).  N(c) = i(c) on T; N(c) = 0xFFFFFFFF everywhere when T is empty.  One uint32 per cell at i(c).  The
+ * squared distance is not returned: it is |c - N(c)|^2 and equals vx_grid_distance_sq(flags) on every cell.
+ *   vx_grid_nearest_gather*   out[i(c)] = values[N(c)], `fill` where N(c) is the sentinel: values holds one uint32 per cell (nvalues of them).
+ * Checks, in this order, every one before anything is queued, every failure writing nothing:
+ *   1. a NULL grid or buffer: VX_ERR_INVALID_ARG
+ *   2. unknown flag bits: VX_ERR_INVALID_ARG
+ *   3. gather: nvalues < X*Y*Z, or values == out: VX_ERR_INVALID_ARG
+ *   4. a grid of 0 cells (e.g. after a failed build): VX_OK, nothing written
+ *   5. capacity (in values) < X*Y*Z: VX_ERR_CAPACITY
+ *   6. the distance fields' limit, (X-1)^2 + (Y-1)^2 + (Z-1)^2 > 0xFFFFFFFE: VX_ERR_CAPACITY
+ *   7. more than 0xFFFFFFFF cells (the last index would collide with the sentinel): VX_ERR_CAPACITY
+ * (the distance fields run 1, 2, 4, 6, 5: the status of every call is the same either way.)  Everything else follows the distance fields'
+ * rules: the calls only read the bitmask, nothing a reader of the grid can see changes, a pending VX_VOXELIZE_LIST_ASYNC emission stays
+ * pending; the _device variants queue on the grid's stream and return without a host wait (values and out are device pointers), the host
+ * variants return once host_out is written; scratch stays on the handle, so a repeated call at the same dimensions allocates nothing. */
+vx_status vx_grid_nearest_device(const vx_grid* g, uint32_t flags, uint32_t* dev_out, uint64_t capacity);
+vx_status vx_grid_nearest(const vx_grid* g, uint32_t flags, uint32_t* host_out, uint64_t capacity);
+vx_status vx_grid_nearest_gather_device(const vx_grid* g, uint32_t flags, const uint32_t* dev_values, uint64_t nvalues, uint32_t fill,
+                                        uint32_t* dev_out, uint64_t capacity);
+vx_status vx_grid_nearest_gather(const vx_grid* g, uint32_t flags, const uint32_t* host_values, uint64_t nvalues, uint32_t fill,
+                                 uint32_t* host_out, uint64_t capacity);
 /* Binary morphology of the bitmask with the digital Euclidean ball (scipy.ndimage.binary_dilation / _erosion / _opening / _closing).
  * M = the occupied cells of the bitmask as it stands when the call is queued (after the last build, setVoxel, fill_interior, or an external
  * write followed by vx_grid_refresh).  radius_sq = r2 is a squared radius in cells, R = floor(sqrt(r2)), and the structuring element is

@@ -246,6 +246,25 @@ public:
         return ret;
     }
 
+    // The feature transform (vx_grid_nearest): per cell the index x + X*(y + Y*z) of its nearest occupied cell (inside: nearest empty cell),
+    // the smallest index among equally near ones; 0xFFFFFFFF when there is none.
+    std::vector<uint32_t> nearestCells(bool inside = false) const
+    {
+        std::vector<uint32_t> ret(m_x * m_y * m_z);
+        vxdetail::check(vx_grid_nearest(m_grid.get(), inside ? VX_DISTANCE_INSIDE : 0u, ret.data(), ret.size()));
+        return ret;
+    }
+    // nearestLabels: the Voronoi partition of the grid by part -- every cell gets the components(connectivity) label of its nearest occupied
+    // cell (all 0 when nothing is occupied).  Returns K.
+    uint32_t nearestLabels(int connectivity, std::vector<uint32_t>& labels) const
+    {
+        std::vector<uint32_t> own;
+        const uint32_t k = components(connectivity, own);
+        labels.assign(own.size(), 0u);
+        if (!own.empty()) vxdetail::check(vx_grid_nearest_gather(m_grid.get(), 0u, own.data(), own.size(), 0u, labels.data(), labels.size()));
+        return k;
+    }
+
     // Multi-hit ray query (vx_trace_multi): for each ray (6 floats: origin, direction) the first maxHits (1..32) voxels it meets, ordered by
     // (t, index in getAabbs() order of the Bool grid), into t / prim (maxHits entries per ray, padded with -1 / 0xFFFFFFFF), and the number of
     // all voxels it meets within [tmin, tmax] into count.

@@ -46,6 +46,11 @@
 //                                       cell, negative inside by the distance to the nearest empty one) as raw little-endian f32, x fastest,
 //                                       X*Y*Z values; one line gives the dims and the finite min / max.  bool / aabbstruct / vec, with or
 //                                       without --solid; not with --grid octree, --gpus N > 1 or --bench
+//   --nearest FILE [--nearest-inside]   the grid's feature transform (vx_grid_nearest: per cell the index x + X*(y + Y*z) of its nearest occupied
+//                                       cell, the smallest index among equally near ones; --nearest-inside: of its nearest empty cell;
+//                                       0xFFFFFFFF when there is none) as raw little-endian u32, x fastest, X*Y*Z values; one line gives the
+//                                       dims and the largest squared distance to a nearest cell.  bool / aabbstruct / vec, with or without
+//                                       --solid and --morph; not with --grid octree, --gpus N > 1 or --bench
 //   --surface FILE.obj                  the boundary mesh of the grid (vx_grid_surface: two triangles per exposed cell face over shared lattice
 //                                       points) as an OBJ: `v` lines in vertex order, then `f` lines (1-based) in triangle order.  With
 //                                       --materials also FILE.mtl (one `newmtl m<id>` per grid material) and a `usemtl m<id>` before each run
@@ -488,6 +493,32 @@ void write_mesh_xray(const vx_bvh* bvh, const std::string& file, uint32_t W, uin
     write_counts_pgm(count, file, W, H, "triangle");
 }
 
+// --nearest FILE [--nearest-inside]
+struct NearestOpt {
+    std::string file;
+    bool inside = false;
+};
+NearestOpt g_nearest;
+
+// the feature transform of the grid as raw little-endian u32, and one line: the dims and the largest |c - N(c)|^2 over cells that have an N
+template <class T>
+void write_nearest(const T& vox)
+{
+    const std::vector<uint32_t> nn = vox.nearestCells(g_nearest.inside);
+    const uint64_t X = vox.dimX(), Y = vox.dimY();
+    uint64_t far = 0;
+    for (uint64_t i = 0; i < nn.size(); ++i) {
+        if (nn[i] == 0xFFFFFFFFu) continue;
+        const uint64_t o = nn[i];
+        const int64_t dx = (int64_t)(i % X) - (int64_t)(o % X), dy = (int64_t)(i / X % Y) - (int64_t)(o / X % Y), dz = (int64_t)(i / (X * Y)) - (int64_t)(o / (X * Y));
+        far = std::max<uint64_t>(far, (uint64_t)(dx * dx + dy * dy + dz * dz));
+    }
+    std::ofstream f(g_nearest.file, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(nn.data()), (std::streamsize)(nn.size() * sizeof(uint32_t)));
+    if (!f) throw std::runtime_error("cannot write " + g_nearest.file);
+    std::printf("[voxhip] nearest: %zu x %zu x %zu cells, max squared distance %llu\n", vox.dimX(), vox.dimY(), vox.dimZ(), (unsigned long long)far);
+}
+
 // --morph OP:RADIUS / --seal RADIUS: op 0..3 = VX_MORPH_*, 4 = seal, -1 = none
 struct MorphOpt {
     int op = -1;
@@ -569,6 +600,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
         if (!f) throw std::runtime_error("cannot write " + sdfFile);
         std::printf("[voxhip] sdf: %zu x %zu x %zu cells, min %g max %g\n", vox.dimX(), vox.dimY(), vox.dimZ(), (double)lo, (double)hi);
     }
+    if (!g_nearest.file.empty()) write_nearest(vox);
     if (!surfaceFile.empty()) write_surface(vox, surfaceFile, materials);
     if (!componentsFile.empty()) {
         const std::vector<vx_component> cs = vox.componentStats(connectivity);
@@ -603,7 +635,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--surface FILE.obj [--smooth N[:LAMBDA:MU]]] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--nearest FILE [--nearest-inside]] [--surface FILE.obj [--smooth N[:LAMBDA:MU]]] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
                      argv[0]);
         return 2;
     }
@@ -633,6 +665,8 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--morph") && i + 1 < argc) { if (!parse_morph(argv[++i], &g_morph)) { std::fprintf(stderr, "bad --morph '%s': OP:RADIUS with OP dilate|erode|open|close and RADIUS >= 0 in cells\n", argv[i]); return 2; } }
         else if (!std::strcmp(argv[i], "--seal") && i + 1 < argc) { g_morph.op = 4; if (!parse_radius(argv[++i], &g_morph.r2)) { std::fprintf(stderr, "bad --seal '%s': a radius >= 0 in cells\n", argv[i]); return 2; } }
         else if (!std::strcmp(argv[i], "--sdf") && i + 1 < argc) sdfFile = argv[++i];
+        else if (!std::strcmp(argv[i], "--nearest") && i + 1 < argc) g_nearest.file = argv[++i];
+        else if (!std::strcmp(argv[i], "--nearest-inside")) g_nearest.inside = true;
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
         else if (!std::strcmp(argv[i], "--smooth") && i + 1 < argc) { if (!parse_smooth(argv[++i], &g_smooth)) { std::fprintf(stderr, "bad --smooth '%s': N[:LAMBDA:MU] with N <= 1024, LAMBDA in [0, 1] and MU in [-1, 0]\n", argv[i]); return 2; } }
         else if (!std::strcmp(argv[i], "--components") && i + 1 < argc) componentsFile = argv[++i];
@@ -672,6 +706,14 @@ int main(int argc, char** argv)
     }
     if (!sdfFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
         std::fprintf(stderr, "--sdf writes the distance field of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (!g_nearest.file.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
+        std::fprintf(stderr, "--nearest writes the nearest-cell field of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (g_nearest.inside && g_nearest.file.empty()) {
+        std::fprintf(stderr, "--nearest-inside chooses the field that --nearest writes: it needs --nearest FILE\n");
         return 2;
     }
     if (!surfaceFile.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0 || (materials && grid == "vec"))) {

@@ -521,6 +521,7 @@ struct vx_grid : Home {
     DevBuf solid_m{this}, solid_e{this}, solid_h{this}, solid_pre{this}, solid_agg{this} /*the column scans' per-chunk words*/;
     // distance fields (vx_distance.hip): the envelopes' stacks, and the field itself for the host variants
     DevBuf dist_stk{this}, dist_out{this};
+    DevBuf near_val{this};  // the feature transform's host gather: the values on the device (its stacks and result share dist_stk / dist_out)
     // morphology (vx_morph.hip): two row-aligned masks (a stage's output, the next one's input), a padded or intermediate mask in the
     // reference's layout, the distance-field path's field and the host variant's result
     DevBuf morph_a{this}, morph_b{this}, morph_p{this}, morph_d{this}, morph_out{this};
@@ -2375,6 +2376,92 @@ vx_status vx_grid_sdf(const vx_grid* gc, float* host_out, uint64_t capacity)
     vx_grid* g = const_cast<vx_grid*>(gc);
     DeviceGuard dg(g->device);
     return distance_host(g, 2, host_out, n);
+}
+
+// The feature transform (vx_grid_nearest*): the checks in the order the header lists them, then the three passes of launch_nearest.  The
+// stacks and the host variants' result share the distance fields' buffers (one stream: the calls are ordered).
+static vx_status nearest_check(const vx_grid* g, uint32_t flags, const uint32_t* values, uint64_t nvalues, bool gather, const uint32_t* out,
+                               uint64_t cap, uint64_t* n)
+{
+    *n = 0;
+    if (flags & ~(uint32_t)VX_DISTANCE_INSIDE) return fail(VX_ERR_INVALID_ARG, "unknown nearest flags");
+    if (gather && nvalues < g->g.nvox) return fail(VX_ERR_INVALID_ARG, "nearest gather: fewer values than cells");
+    if (gather && values == out) return fail(VX_ERR_INVALID_ARG, "nearest gather: values and out must differ");
+    if (!g->g.nvox) return VX_OK;  // (a grid of 0 cells: nothing to write)
+    if (cap < g->g.nvox) return fail(VX_ERR_CAPACITY, "nearest buffer too small");
+    const uint64_t d0 = g->g.dim[0] - 1ull, d1 = g->g.dim[1] - 1ull, d2 = g->g.dim[2] - 1ull;
+    if (d0 * d0 + d1 * d1 + d2 * d2 > 0xFFFFFFFEull) return fail(VX_ERR_CAPACITY, "nearest needs (X-1)^2 + (Y-1)^2 + (Z-1)^2 <= 0xFFFFFFFE");
+    if (g->g.nvox > 0xFFFFFFFFull) return fail(VX_ERR_CAPACITY, "nearest needs at most 0xFFFFFFFF cells");
+    *n = g->g.nvox;
+    return VX_OK;
+}
+
+static vx_status nearest_queue(vx_grid* g, uint32_t flags, const uint32_t* dev_values, uint32_t fill, uint32_t* dev_out)
+{
+    VX_HIP(g->dist_stk.ensure((size_t)vx::distance_stack_entries(g->g.dim, false) * 8));
+    vx::launch_nearest(g->words.as<uint32_t>(), g->g.dim, (flags & VX_DISTANCE_INSIDE) != 0, dev_values, fill, dev_out, g->dist_stk.as<uint2>(),
+                       g->stream);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+static vx_status nearest_host(vx_grid* g, uint32_t flags, const uint32_t* host_values, uint32_t fill, uint32_t* host_out, uint64_t n)
+{
+    VX_HIP(g->dist_out.ensure((size_t)n * 4));
+    if (host_values) {
+        VX_HIP(g->near_val.ensure((size_t)n * 4));
+        VX_HIP(hipMemcpyAsync(g->near_val.p, host_values, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    }
+    VX_TRY(nearest_queue(g, flags, host_values ? g->near_val.as<uint32_t>() : nullptr, fill, g->dist_out.as<uint32_t>()));
+    VX_HIP(hipMemcpyAsync(host_out, g->dist_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream));
+    VX_HIP(hipStreamSynchronize(g->stream));
+    return VX_OK;
+}
+
+vx_status vx_grid_nearest_device(const vx_grid* gc, uint32_t flags, uint32_t* dev_out, uint64_t capacity)
+{
+    if (!gc || !dev_out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    uint64_t n = 0;
+    VX_TRY(nearest_check(gc, flags, nullptr, 0, false, dev_out, capacity, &n));
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return nearest_queue(g, flags, nullptr, 0u, dev_out);
+}
+
+vx_status vx_grid_nearest(const vx_grid* gc, uint32_t flags, uint32_t* host_out, uint64_t capacity)
+{
+    if (!gc || !host_out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    uint64_t n = 0;
+    VX_TRY(nearest_check(gc, flags, nullptr, 0, false, host_out, capacity, &n));
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return nearest_host(g, flags, nullptr, 0u, host_out, n);
+}
+
+vx_status vx_grid_nearest_gather_device(const vx_grid* gc, uint32_t flags, const uint32_t* dev_values, uint64_t nvalues, uint32_t fill,
+                                        uint32_t* dev_out, uint64_t capacity)
+{
+    if (!gc || !dev_values || !dev_out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    uint64_t n = 0;
+    VX_TRY(nearest_check(gc, flags, dev_values, nvalues, true, dev_out, capacity, &n));
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return nearest_queue(g, flags, dev_values, fill, dev_out);
+}
+
+vx_status vx_grid_nearest_gather(const vx_grid* gc, uint32_t flags, const uint32_t* host_values, uint64_t nvalues, uint32_t fill,
+                                 uint32_t* host_out, uint64_t capacity)
+{
+    if (!gc || !host_values || !host_out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    uint64_t n = 0;
+    VX_TRY(nearest_check(gc, flags, host_values, nvalues, true, host_out, capacity, &n));
+    if (!n) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    return nearest_host(g, flags, host_values, fill, host_out, n);
 }
 
 // Morphology (vx_morph.hip).  Every operation is a chain of stages on the grid's stream; the scratch of all of them lives on the handle

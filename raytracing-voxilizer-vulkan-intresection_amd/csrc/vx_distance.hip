@@ -15,6 +15,9 @@
 // Modes: OUT (targets = occupied cells; 0 on M), IN (targets = empty cells; 0 off M) and SIGNED: each cell carries the transform it needs
 // (D_in on M, D_out off M) in the one 32-bit intermediate -- the other transform is 0 there, known from the mask -- and the column passes run
 // both envelopes over the one buffer, g_out(u) = m(u) ? 0 : v(u), g_in(u) = m(u) ? v(u) : 0.  The z pass of SIGNED converts to f32 in place.
+//
+// The feature transform (vx_grid_nearest*: the INDEX of the nearest target, smallest index on ties) runs the same passes with kernels of its
+// own, k_near_x and k_near_col, below the distance kernels.
 #include "vx_internal.h"
 
 #pragma clang fp contract(off)
@@ -226,7 +229,169 @@ __global__ __launch_bounds__(256) void k_dist_col(const uint32_t* __restrict__ w
     }
 }
 
+// ---- the feature transform (vx_grid_nearest*): the same three passes, carrying WHICH target wins instead of how far it is ------------------
+// The one 32-bit intermediate per cell is the packed feature x' | y' << 16 of the cell's nearest target so far (kNone: none); every g the
+// envelope needs is recomputed from it and the column's own position: (x - x')^2 after the x pass, (x - x')^2 + (y - y')^2 after the y pass.
+// The stack entry stays 8 bytes, (s | t << 16, feature of s).  Ties: the x pass keeps the left target, the envelope keeps the smaller s
+// (a parabola is popped only by a strictly better newcomer, and a newcomer starts where it is strictly better) -- together the smallest
+// cell index among the nearest targets.  x' | y' << 16 == kNone would need X = Y = 65536, which the distance fields' limit excludes.
+
+// position along the row of the nearest target of cell x (bit i of word w), the left one on a tie; kNone: the row has none
+__device__ __forceinline__ uint32_t row_near(uint32_t t, uint32_t i, uint32_t x, uint32_t prev, uint32_t next)
+{
+    const uint32_t lo = t & ((2u << i) - 1u);
+    const uint32_t hi = t >> i;
+    const uint32_t pl = lo ? x - i + (31u - (uint32_t)__builtin_clz(lo)) : prev;
+    const uint32_t pr = hi ? x + (uint32_t)__builtin_ctz(hi) : next;
+    const uint32_t dl = pl != kNone ? x - pl : kInf;
+    const uint32_t dr = pr != kNone ? pr - x : kInf;
+    return dl <= dr ? pl : pr;
+}
+
+template <bool OCC, bool VEC4>
+__global__ __launch_bounds__(256) void k_near_x(const uint32_t* __restrict__ words, uint32_t* __restrict__ out, uint32_t X, uint64_t rows)
+{
+    const uint32_t W = (X + 31u) / 32u;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < rows; r += (uint64_t)gridDim.x * 256u) {
+        const uint64_t rowbit = r * X;
+        uint32_t* o = out + rowbit;
+        uint32_t prev = kNone;
+        Ahead a{0u, kNone};
+        ahead_from<OCC>(a, words, rowbit, X, W, 1u);
+        for (uint32_t w = 0; w < W; ++w) {
+            if (a.lw == w) ahead_from<OCC>(a, words, rowbit, X, W, w + 1u);
+            uint32_t valid;
+            const uint32_t m = row_word(words, rowbit, X, w, valid);
+            const uint32_t t = (OCC ? m : ~m) & valid;
+            const uint32_t nb = (uint32_t)__builtin_popcount(valid);
+            uint32_t v[32];
+#pragma unroll
+            for (uint32_t i = 0; i < 32u; ++i) v[i] = row_near(t, i, 32u * w + i, prev, a.pos);
+            if (VEC4) {
+#pragma unroll
+                for (uint32_t i = 0; i < 32u; i += 4u)
+                    if (i < nb) *reinterpret_cast<uint4*>(o + 32u * w + i) = make_uint4(v[i], v[i + 1], v[i + 2], v[i + 3]);
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 32u; ++i)
+                    if (i < nb) o[32u * w + i] = v[i];
+            }
+            if (t) prev = 32u * w + 31u - (uint32_t)__builtin_clz(t);
+        }
+    }
+}
+
+// g of a packed feature seen from the column at (x, y): the squared distance within the axes already passed (y pass: x only, f >> 16 == 0)
+template <bool ZPASS>
+__device__ __forceinline__ uint32_t near_g(uint32_t f, uint32_t x, uint32_t y)
+{
+    const uint32_t dx = x - (f & 0xFFFFu);  // (the square of a wrapped difference is the square of the difference: below 2^32)
+    uint32_t g = dx * dx;
+    if (ZPASS) {
+        const uint32_t dy = y - (f >> 16);
+        g += dy * dy;
+    }
+    return g;
+}
+
+// Env with the feature of s in the entry's second word; g(s) is kept for the top only, recomputed on every load
+struct NearEnv {
+    uint2* stk;
+    uint64_t ld;
+    int q;
+    uint32_t s, t, f, g;
+};
+
+template <bool ZPASS>
+__device__ __forceinline__ void near_load(NearEnv& e, uint32_t x, uint32_t y)
+{
+    const uint2 v = e.stk[(uint64_t)e.q * e.ld];
+    e.s = v.x & 0xFFFFu;
+    e.t = v.x >> 16;
+    e.f = v.y;
+    e.g = near_g<ZPASS>(v.y, x, y);
+}
+__device__ __forceinline__ void near_push(NearEnv& e, uint32_t s, uint32_t t, uint32_t f, uint32_t g)
+{
+    ++e.q;
+    e.s = s;
+    e.t = t;
+    e.f = f;
+    e.g = g;
+    e.stk[(uint64_t)e.q * e.ld] = make_uint2(s | (t << 16), f);
+}
+
+// env_add with the feature fu of cell u (kNone: skipped)
+template <bool ZPASS>
+__device__ __forceinline__ void near_add(NearEnv& e, uint32_t u, uint32_t fu, uint32_t n, uint32_t x, uint32_t y)
+{
+    if (fu == kNone) return;
+    const uint32_t gu = near_g<ZPASS>(fu, x, y);
+    while (e.q >= 0 && para(e.t, e.s, e.g) > para(e.t, u, gu)) {
+        if (--e.q >= 0) near_load<ZPASS>(e, x, y);
+    }
+    if (e.q < 0) { near_push(e, u, 0u, fu, gu); return; }
+    const int64_t num = (int64_t)u * u - (int64_t)e.s * e.s + (int64_t)gu - (int64_t)e.g;
+    const int64_t den = 2 * ((int64_t)u - (int64_t)e.s);
+    const int64_t w = (num >= 0 ? num / den : -((-num + den - 1) / den)) + 1;
+    if (w < (int64_t)n) near_push(e, u, (uint32_t)w, fu, gu);
+}
+
+// Columns as for k_dist_col.  y pass (ZPASS false): buf holds x' (or kNone) and leaves as x' | y' << 16.  z pass: buf leaves as the cell
+// index x' + X (y' + Y z') of the nearest target; GATHER: as values[that index] instead, `fill` for kNone (values is not buf: every thread
+// reads and writes its own column of buf only, after phase 1 has read all of it).
+template <bool ZPASS, bool GATHER>
+__global__ __launch_bounds__(256) void k_near_col(uint32_t* __restrict__ buf, uint2* __restrict__ stk, uint32_t X, uint32_t Y, uint64_t ncols,
+                                                  uint64_t outer, uint64_t stride, uint32_t n, const uint32_t* __restrict__ values, uint32_t fill)
+{
+    for (uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x; c < ncols; c += (uint64_t)gridDim.x * 256u) {
+        const uint32_t x = (uint32_t)(c % X), y = (uint32_t)(c / X);  // (y pass: y is the column's z, and unused)
+        const uint64_t base = x + (c / X) * outer;
+        NearEnv e;
+        e.stk = stk + c;
+        e.ld = ncols;
+        e.q = -1;
+        e.s = e.t = e.f = e.g = 0u;
+        uint32_t v = buf[base];
+        for (uint32_t u = 0; u < n; ++u) {
+            const uint64_t i = base + (uint64_t)u * stride;
+            const uint32_t vn = u + 1u < n ? buf[i + stride] : 0u;  // the next step's load, issued ahead
+            near_add<ZPASS>(e, u, v, n, x, y);
+            v = vn;
+        }
+        for (uint32_t u = n; u-- > 0;) {
+            const uint64_t i = base + (uint64_t)u * stride;
+            uint32_t r = kNone;
+            if (e.q >= 0) {
+                r = ZPASS ? (e.f & 0xFFFFu) + X * ((e.f >> 16) + Y * e.s) : e.f | (e.s << 16);
+                if (u == e.t && --e.q >= 0) near_load<ZPASS>(e, x, y);
+            }
+            if (GATHER) r = r == kNone ? fill : values[r];
+            buf[i] = r;
+        }
+    }
+}
+
 }  // namespace
+
+void launch_nearest(const uint32_t* words, const uint32_t dim[3], bool inside, const uint32_t* values, uint32_t fill, uint32_t* buf, uint2* stk,
+                    hipStream_t s)
+{
+    const uint32_t X = dim[0], Y = dim[1], Z = dim[2];
+    const uint64_t rows = (uint64_t)Y * Z, xy = (uint64_t)X * Y, xz = (uint64_t)X * Z;
+    const unsigned gx = dist_grid(rows), gy = dist_grid(xz), gz = dist_grid(xy);
+    const bool v4 = X % 4u == 0u && ((uintptr_t)buf & 15u) == 0u;
+    if (inside) {
+        if (v4) VX_KL((k_near_x<false, true>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
+        else VX_KL((k_near_x<false, false>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
+    } else {
+        if (v4) VX_KL((k_near_x<true, true>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
+        else VX_KL((k_near_x<true, false>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
+    }
+    VX_KL((k_near_col<false, false>), dim3(gy), dim3(256), 0, s, buf, stk, X, Y, xz, xy, (uint64_t)X, Y, values, fill);
+    if (values) VX_KL((k_near_col<true, true>), dim3(gz), dim3(256), 0, s, buf, stk, X, Y, xy, (uint64_t)X, xy, Z, values, fill);
+    else VX_KL((k_near_col<true, false>), dim3(gz), dim3(256), 0, s, buf, stk, X, Y, xy, (uint64_t)X, xy, Z, values, fill);
+}
 
 uint64_t distance_stack_entries(const uint32_t dim[3], bool is_signed)
 {

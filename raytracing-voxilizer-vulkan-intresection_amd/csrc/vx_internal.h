@@ -466,6 +466,11 @@ void launch_solid_ids(int16_t* ids, uint64_t n, int16_t v, bool only_unset, hipS
 // entries of scratch (the envelopes' stacks, [k][column]).
 uint64_t distance_stack_entries(const uint32_t dim[3], bool is_signed);
 void launch_distance(const uint32_t* words, const uint32_t dim[3], int mode, float vs, uint32_t* buf, uint2* stk, hipStream_t s);
+// The feature transform (vx_distance.hip): the same passes carrying the nearest target itself; buf (N values, in place) ends as the cell
+// index of the nearest occupied (inside: empty) cell, 0xFFFFFFFF when there is none -- or, with values (N entries, not buf), as values[that
+// index], `fill` when there is none.  N <= 0xFFFFFFFF and the distance fields' limit hold.  stk: distance_stack_entries(dim, false) entries.
+void launch_nearest(const uint32_t* words, const uint32_t dim[3], bool inside, const uint32_t* values, uint32_t fill, uint32_t* buf, uint2* stk,
+                    hipStream_t s);
 
 // Morphology with the digital Euclidean ball (vx_morph.hip).  A domain: its cells and the bits from one (y, z) row to the next -- X for the
 // reference's bitmask, 32 * ceil(X / 32) for a ROW-ALIGNED mask (morph_aligned_words(dim) words, padding bits zero).

@@ -222,6 +222,7 @@ SYMBOLS = [
     "vx_grid_create", "vx_grid_describe", "vx_grid_set_voxel", "vx_grid_test_voxel", "vx_grid_coords", "vx_grid_bytes",
     "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_fill_interior", "vx_grid_interior", "vx_grid_fill_rounds",
     "vx_grid_distance_sq_device", "vx_grid_distance_sq", "vx_grid_sdf_device", "vx_grid_sdf",
+    "vx_grid_nearest_device", "vx_grid_nearest", "vx_grid_nearest_gather_device", "vx_grid_nearest_gather",
     "vx_grid_morph_device", "vx_grid_morph_mask", "vx_grid_morph", "vx_grid_seal", "vx_morph_bit_radius",
     "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh",
     "vx_grid_surface_smooth_device", "vx_grid_surface_smooth", "vx_grid_surface_smooth_mesh",
@@ -354,6 +355,10 @@ def lib():
     L.vx_grid_distance_sq.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_sdf_device.argtypes = [vp, vp, C.c_uint64]
     L.vx_grid_sdf.argtypes = [vp, vp, C.c_uint64]
+    L.vx_grid_nearest_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
+    L.vx_grid_nearest.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
+    L.vx_grid_nearest_gather_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64]
+    L.vx_grid_nearest_gather.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_morph_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_morph_mask.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_morph.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
@@ -844,6 +849,63 @@ class Grid:
         _check(lib().vx_grid_sdf_device(self.h, out.data_ptr(), n))
         self._record(out)
         return out
+
+    def nearest(self, inside=False):
+        """vx_grid_nearest: the cell index x + X*(y + Y*z) of every cell's nearest occupied cell (inside=True: nearest empty cell), the
+        smallest index among equally near ones -> numpy uint32 [Z, Y, X]; 0xFFFFFFFF where no such cell exists."""
+        shape, n = self._cells()
+        out = np.zeros(shape, dtype=np.uint32)
+        _check(lib().vx_grid_nearest(self.h, DISTANCE_INSIDE if inside else 0, out.ctypes.data, n))
+        return out
+
+    def nearest_device(self, out=None, inside=False):
+        """vx_grid_nearest_device, asynchronous on the grid's stream -> `out`, a device torch.uint32 tensor [Z, Y, X] (an int32 tensor
+        receives the same bits)."""
+        import torch
+        out, n = self._device_out(out, (torch.uint32, torch.int32), "uint32 / int32")
+        _check(lib().vx_grid_nearest_device(self.h, DISTANCE_INSIDE if inside else 0, out.data_ptr(), n))
+        self._record(out)
+        return out
+
+    def nearest_gather(self, values, fill=0, inside=False):
+        """vx_grid_nearest_gather: values[nearest()] per cell, `fill` where there is no nearest cell -> numpy uint32 [Z, Y, X].  `values`:
+        one uint32 per cell, [Z, Y, X] or flat."""
+        shape, n = self._cells()
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        if values.size != n:
+            raise ValueError("values must hold X*Y*Z elements")
+        out = np.zeros(shape, dtype=np.uint32)
+        _check(lib().vx_grid_nearest_gather(self.h, DISTANCE_INSIDE if inside else 0, values.ctypes.data, n, int(fill) & 0xFFFFFFFF,
+                                            out.ctypes.data, n))
+        return out
+
+    def nearest_gather_device(self, values, out=None, fill=0, inside=False):
+        """vx_grid_nearest_gather_device, asynchronous on the grid's stream: `values`, a contiguous device uint32 / int32 tensor of X*Y*Z
+        elements written on (or ordered before) that stream -> `out`, a different tensor of the same kind."""
+        import torch
+        out, n = self._device_out(out, (torch.uint32, torch.int32), "uint32 / int32")
+        if values.dtype not in (torch.uint32, torch.int32) or values.numel() != n or not values.is_contiguous() or not values.is_cuda:
+            raise ValueError("values must be a contiguous device uint32 / int32 tensor of X*Y*Z elements")
+        _check(lib().vx_grid_nearest_gather_device(self.h, DISTANCE_INSIDE if inside else 0, values.data_ptr(), n, int(fill) & 0xFFFFFFFF,
+                                                   out.data_ptr(), n))
+        self._record(values)
+        self._record(out)
+        return out
+
+    def nearest_labels(self, connectivity=CONNECT_6):
+        """The Voronoi partition of the grid by part: every cell gets the component label (components(connectivity)) of its nearest
+        occupied cell -> (numpy uint32 [Z, Y, X], K); all 0 when nothing is occupied.  components_device, then nearest_gather_device, on
+        the grid's stream, with one host wait."""
+        import torch
+        shape, n = self._cells()
+        if not n:
+            return np.zeros(shape, dtype=np.uint32), 0
+        lab, k = self.components_device(connectivity=connectivity)
+        out = self.nearest_gather_device(lab, fill=0)
+        st = getattr(self, "_stream", None)
+        with torch.cuda.stream(st if hasattr(st, "cuda_stream") else torch.cuda.ExternalStream(st) if st else torch.cuda.default_stream()):
+            host = torch.cat([out.view(torch.int32).reshape(-1), k.reshape(-1)]).cpu().numpy()  # (on the grid's stream: the one host wait)
+        return host[:-1].view(np.uint32).reshape(tuple(out.shape)).copy(), int(host[-1])
 
     def _morph_grid(self, op, radius, radius_sq):
         h = C.c_void_p()
