@@ -956,6 +956,20 @@ typedef struct vx_scan_args {
 } vx_scan_args;
 vx_status vx_scan_u32(const vx_scan_args* a);
 
+/* ---- test aid: poisoned pool blocks.  Every kernel works on blocks of the library's stream-ordered pool, and a block handed out holds
+ * whatever its previous owner left in it: another handle, another feature, an earlier and larger call.  While the mode is on
+ * (on != 0), every block the pool hands out -- recycled or new from hipMalloc -- is first filled with the 32-bit `pattern` over its whole
+ * rounded size.  The fill is queued on the stream the request names and waited for before the block is returned, so the mode serialises
+ * the host with that stream at every allocation: it is for tests, not for timing.  Process-wide and atomic (the worker threads of
+ * vx_multi allocate too); off when the library is loaded, where it costs one relaxed atomic load per request.  Nothing else changes:
+ * vx_device_allocations, vx_device_live_blocks, the same-stream / event rule of reuse and vx_release_cached_memory behave as without it.
+ * A library that computes the same outputs under 0xFFFFFFFF, 0xA5A5A5A5 and 0x00000001 as on clean blocks reads no word it has not
+ * written ("Who defines every block").
+ * vx_pool_poisoned_blocks: blocks filled since the library was loaded; over any interval with the mode on it rises by exactly what
+ * vx_device_allocations rises by. */
+vx_status vx_pool_poison(int on, uint32_t pattern);
+uint64_t vx_pool_poisoned_blocks(void);
+
 /* ---- measurement aid: per-kernel durations from HIP events recorded on the launch stream (off by default).
  * slot = 0,1,... until VX_ERR_INVALID_ARG; name is the kernel symbol as launched. */
 vx_status vx_profile_enable(int on);

@@ -78,22 +78,45 @@ size_t round_size(size_t b)
 
 std::atomic<uint64_t> g_pool_requests{0};  // vx_device_allocations
 
+// Poison mode (vx_pool_poison, a test aid): bit 32 = on, bits 0..31 = the pattern.  One word, so a worker thread of vx_multi never sees
+// the switch without its pattern.
+std::atomic<uint64_t> g_pool_poison{0};
+std::atomic<uint64_t> g_pool_poisoned{0};  // vx_pool_poisoned_blocks
+
+// A block about to be handed out, filled over its whole rounded size.  The fill is queued on the requesting stream and waited for: an owner
+// that initialises its block with a synchronous copy (ensure_small) must not find a fill still queued on a non-blocking stream behind it.
+hipError_t pool_poison_fill(void* p, size_t sz, uint32_t pattern, hipStream_t stream)
+{
+    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)pattern, sz / 4, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) g_pool_poisoned.fetch_add(1, std::memory_order_relaxed);
+    return e;
+}
+
 hipError_t pool_alloc(int dev, size_t bytes, void** out, hipStream_t stream)
 {
     g_pool_requests.fetch_add(1, std::memory_order_relaxed);
+    const uint64_t poison = g_pool_poison.load(std::memory_order_relaxed);
     const size_t sz = round_size(bytes);
     Pool& P = g_pool[dev];
+    void* hit = nullptr;
+    size_t hit_size = 0;
     {
         std::lock_guard<std::mutex> lk(P.mu);
         for (auto it = P.free_blocks.lower_bound(sz); it != P.free_blocks.end() && it->first <= sz * 2; ++it) {
             FreeBlock& fb = it->second;
             if (fb.ev && fb.stream != stream && hipEventQuery(fb.ev) != hipSuccess) continue;  // still in flight on another stream
             if (fb.ev) P.spare_events.push_back(fb.ev);
-            *out = fb.p;
-            P.live[*out] = it->first;
+            hit = fb.p;
+            hit_size = it->first;
+            P.live[hit] = hit_size;
             P.free_blocks.erase(it);
-            return hipSuccess;
+            break;
         }
+    }
+    if (hit) {
+        *out = hit;
+        return poison ? pool_poison_fill(hit, hit_size, (uint32_t)poison, stream) : hipSuccess;  // (outside the pool's lock: the fill waits)
     }
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, sz);
@@ -103,10 +126,12 @@ hipError_t pool_alloc(int dev, size_t bytes, void** out, hipStream_t stream)
         e = hipMalloc(&p, sz);
         if (e != hipSuccess) return e;
     }
-    std::lock_guard<std::mutex> lk(P.mu);
-    P.live[p] = sz;
+    {
+        std::lock_guard<std::mutex> lk(P.mu);
+        P.live[p] = sz;
+    }
     *out = p;
-    return hipSuccess;
+    return poison ? pool_poison_fill(p, sz, (uint32_t)poison, stream) : hipSuccess;
 }
 
 // `in_flight`: work that touches the block may still be queued on `stream` (false: the caller has synchronized)
@@ -5068,6 +5093,15 @@ uint64_t vx_device_live_blocks(void)
     }
     return n;
 }
+
+// ---- test aid: poisoned pool blocks ---------------------------------------------------------------------------
+vx_status vx_pool_poison(int on, uint32_t pattern)
+{
+    g_pool_poison.store(on ? ((1ull << 32) | (uint64_t)pattern) : 0ull, std::memory_order_relaxed);
+    return VX_OK;
+}
+
+uint64_t vx_pool_poisoned_blocks(void) { return g_pool_poisoned.load(std::memory_order_relaxed); }
 
 // ---- per-kernel timing (bench / profiling aid) ----------------------------------------------------------------
 vx_status vx_profile_enable(int on)

@@ -242,6 +242,7 @@ SYMBOLS = [
     "vx_tlas_trace_multi", "vx_tlas_trace_multi_device", "vx_tlas_free",
     "vx_render_create", "vx_render_create_tlas", "vx_render_refresh", "vx_render_set_shading", "vx_render_frame_device", "vx_render_frame", "vx_render_free",
     "vx_profile_enable", "vx_profile_select", "vx_profile_reset", "vx_profile_read", "vx_device_allocations", "vx_device_live_blocks",
+    "vx_pool_poison", "vx_pool_poisoned_blocks",
     "vx_shard_words", "vx_shard_range",
 ]
 
@@ -424,6 +425,9 @@ def lib():
     L.vx_device_allocations.restype = C.c_uint64
     L.vx_device_live_blocks.argtypes = []
     L.vx_device_live_blocks.restype = C.c_uint64
+    L.vx_pool_poison.argtypes = [C.c_int, C.c_uint32]
+    L.vx_pool_poisoned_blocks.argtypes = []
+    L.vx_pool_poisoned_blocks.restype = C.c_uint64
     L.vx_bvh_root_bounds.argtypes = [vp, fp, fp]
     L.vx_bvh_nodes.argtypes = [vp, vp, C.c_uint64, u64p]
     L.vx_bvh_leaf_triangles.argtypes = [vp, vp, C.c_uint64]
@@ -539,6 +543,19 @@ def device_allocations():
 def device_live_blocks():
     """vx_device_live_blocks: pool blocks held right now by handles and calls in progress, over all devices."""
     return int(lib().vx_device_live_blocks())
+
+
+def pool_poison(pattern):
+    """vx_pool_poison (a test aid): fill every block the pool hands out with the 32-bit `pattern` first; None switches the mode off."""
+    if pattern is None:
+        _check(lib().vx_pool_poison(0, 0))
+    else:
+        _check(lib().vx_pool_poison(1, int(pattern) & 0xFFFFFFFF))
+
+
+def pool_poisoned_blocks():
+    """vx_pool_poisoned_blocks: blocks the poison mode has filled since the library was loaded."""
+    return int(lib().vx_pool_poisoned_blocks())
 
 
 def shard_words(num_words, rank, world):
