@@ -2348,60 +2348,61 @@ static vx_status distance_queue(vx_grid* g, int mode, void* dev_out)
     return VX_OK;
 }
 
-static vx_status distance_host(vx_grid* g, int mode, void* host_out, uint64_t n)
+// The ten field entry points (distance_sq / sdf / nearest / nearest_gather / morph, each with its _device variant) in one order: null checks;
+// check(&bytes), the feature's own checks in the header's order -> the bytes the call writes (0: a grid of 0 cells, nothing to do); the
+// guard; queue(g, in, out) on the caller's device pointers, or (host) on the grid's staging blocks: `in` through near_val, the result in
+// g->*stage (`spare` bytes behind it), copied back and waited for.
+extern "C++" {
+template <class Check, class Queue>
+static vx_status field_entry(const vx_grid* gc, const void* in, bool needs_in, void* out, bool host, DevBuf vx_grid::*stage, size_t spare, Check check,
+                             Queue queue)
 {
-    VX_HIP(g->dist_out.ensure((size_t)n * 4));
-    VX_TRY(distance_queue(g, mode, g->dist_out.p));
-    VX_HIP(hipMemcpyAsync(host_out, g->dist_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream));
+    if (!gc || !out || (needs_in && !in)) return fail(VX_ERR_INVALID_ARG, "null argument");
+    size_t bytes = 0;
+    VX_TRY(check(&bytes));
+    if (!bytes) return VX_OK;
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    DeviceGuard dg(g->device);
+    if (!host) return queue(g, in, out);
+    DevBuf& res = g->*stage;
+    VX_HIP(res.ensure(bytes + spare));
+    if (in) {
+        VX_HIP(g->near_val.ensure(bytes));
+        VX_HIP(hipMemcpyAsync(g->near_val.p, in, bytes, hipMemcpyHostToDevice, g->stream));
+    }
+    VX_TRY(queue(g, in ? g->near_val.p : nullptr, res.p));
+    VX_HIP(hipMemcpyAsync(out, res.p, bytes, hipMemcpyDeviceToHost, g->stream));
     VX_HIP(hipStreamSynchronize(g->stream));
     return VX_OK;
 }
+}  // extern "C++"
 
-vx_status vx_grid_distance_sq_device(const vx_grid* gc, uint32_t flags, uint32_t* dev_out, uint64_t capacity)
+// mode: 0 distance_sq, 1 distance_sq inside, 2 sdf
+static vx_status distance_entry(const vx_grid* gc, uint32_t flags, int mode, void* out, uint64_t capacity, bool host)
 {
-    if (!gc || !dev_out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    if (flags & ~(uint32_t)VX_DISTANCE_INSIDE) return fail(VX_ERR_INVALID_ARG, "unknown distance flags");
-    uint64_t n = 0;
-    VX_TRY(distance_check(gc, capacity, &n));
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return distance_queue(g, (flags & VX_DISTANCE_INSIDE) ? 1 : 0, dev_out);
+    return field_entry(gc, nullptr, false, out, host, &vx_grid::dist_out, 0,
+        [&](size_t* bytes) {
+            if (flags & ~(uint32_t)VX_DISTANCE_INSIDE) return fail(VX_ERR_INVALID_ARG, "unknown distance flags");
+            uint64_t n = 0;
+            const vx_status st = distance_check(gc, capacity, &n);
+            *bytes = (size_t)n * 4;
+            return st;
+        },
+        [&](vx_grid* g, const void*, void* dev_out) { return distance_queue(g, mode, dev_out); });
 }
 
-vx_status vx_grid_distance_sq(const vx_grid* gc, uint32_t flags, uint32_t* host_out, uint64_t capacity)
+vx_status vx_grid_distance_sq_device(const vx_grid* g, uint32_t flags, uint32_t* dev_out, uint64_t capacity)
 {
-    if (!gc || !host_out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    if (flags & ~(uint32_t)VX_DISTANCE_INSIDE) return fail(VX_ERR_INVALID_ARG, "unknown distance flags");
-    uint64_t n = 0;
-    VX_TRY(distance_check(gc, capacity, &n));
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return distance_host(g, (flags & VX_DISTANCE_INSIDE) ? 1 : 0, host_out, n);
+    return distance_entry(g, flags, (flags & VX_DISTANCE_INSIDE) ? 1 : 0, dev_out, capacity, false);
 }
 
-vx_status vx_grid_sdf_device(const vx_grid* gc, float* dev_out, uint64_t capacity)
+vx_status vx_grid_distance_sq(const vx_grid* g, uint32_t flags, uint32_t* host_out, uint64_t capacity)
 {
-    if (!gc || !dev_out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    uint64_t n = 0;
-    VX_TRY(distance_check(gc, capacity, &n));
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return distance_queue(g, 2, dev_out);
+    return distance_entry(g, flags, (flags & VX_DISTANCE_INSIDE) ? 1 : 0, host_out, capacity, true);
 }
 
-vx_status vx_grid_sdf(const vx_grid* gc, float* host_out, uint64_t capacity)
-{
-    if (!gc || !host_out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    uint64_t n = 0;
-    VX_TRY(distance_check(gc, capacity, &n));
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return distance_host(g, 2, host_out, n);
-}
+vx_status vx_grid_sdf_device(const vx_grid* g, float* dev_out, uint64_t capacity) { return distance_entry(g, 0u, 2, dev_out, capacity, false); }
+vx_status vx_grid_sdf(const vx_grid* g, float* host_out, uint64_t capacity) { return distance_entry(g, 0u, 2, host_out, capacity, true); }
 
 // The feature transform (vx_grid_nearest*): the checks in the order the header lists them, then the three passes of launch_nearest.  The
 // stacks and the host variants' result share the distance fields' buffers (one stream: the calls are ordered).
@@ -2430,63 +2431,42 @@ static vx_status nearest_queue(vx_grid* g, uint32_t flags, const uint32_t* dev_v
     return VX_OK;
 }
 
-static vx_status nearest_host(vx_grid* g, uint32_t flags, const uint32_t* host_values, uint32_t fill, uint32_t* host_out, uint64_t n)
+// gather: `values` (one per cell) are what the result holds; otherwise the nearest cell's index
+static vx_status nearest_entry(const vx_grid* gc, uint32_t flags, bool gather, const uint32_t* values, uint64_t nvalues, uint32_t fill, uint32_t* out,
+                               uint64_t capacity, bool host)
 {
-    VX_HIP(g->dist_out.ensure((size_t)n * 4));
-    if (host_values) {
-        VX_HIP(g->near_val.ensure((size_t)n * 4));
-        VX_HIP(hipMemcpyAsync(g->near_val.p, host_values, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    }
-    VX_TRY(nearest_queue(g, flags, host_values ? g->near_val.as<uint32_t>() : nullptr, fill, g->dist_out.as<uint32_t>()));
-    VX_HIP(hipMemcpyAsync(host_out, g->dist_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, g->stream));
-    VX_HIP(hipStreamSynchronize(g->stream));
-    return VX_OK;
+    return field_entry(gc, values, gather, out, host, &vx_grid::dist_out, 0,
+        [&](size_t* bytes) {
+            uint64_t n = 0;
+            const vx_status st = nearest_check(gc, flags, values, nvalues, gather, out, capacity, &n);
+            *bytes = (size_t)n * 4;
+            return st;
+        },
+        [&](vx_grid* g, const void* dev_values, void* dev_out) {
+            return nearest_queue(g, flags, static_cast<const uint32_t*>(dev_values), fill, static_cast<uint32_t*>(dev_out));
+        });
 }
 
-vx_status vx_grid_nearest_device(const vx_grid* gc, uint32_t flags, uint32_t* dev_out, uint64_t capacity)
+vx_status vx_grid_nearest_device(const vx_grid* g, uint32_t flags, uint32_t* dev_out, uint64_t capacity)
 {
-    if (!gc || !dev_out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    uint64_t n = 0;
-    VX_TRY(nearest_check(gc, flags, nullptr, 0, false, dev_out, capacity, &n));
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return nearest_queue(g, flags, nullptr, 0u, dev_out);
+    return nearest_entry(g, flags, false, nullptr, 0, 0u, dev_out, capacity, false);
 }
 
-vx_status vx_grid_nearest(const vx_grid* gc, uint32_t flags, uint32_t* host_out, uint64_t capacity)
+vx_status vx_grid_nearest(const vx_grid* g, uint32_t flags, uint32_t* host_out, uint64_t capacity)
 {
-    if (!gc || !host_out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    uint64_t n = 0;
-    VX_TRY(nearest_check(gc, flags, nullptr, 0, false, host_out, capacity, &n));
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return nearest_host(g, flags, nullptr, 0u, host_out, n);
+    return nearest_entry(g, flags, false, nullptr, 0, 0u, host_out, capacity, true);
 }
 
-vx_status vx_grid_nearest_gather_device(const vx_grid* gc, uint32_t flags, const uint32_t* dev_values, uint64_t nvalues, uint32_t fill,
+vx_status vx_grid_nearest_gather_device(const vx_grid* g, uint32_t flags, const uint32_t* dev_values, uint64_t nvalues, uint32_t fill,
                                         uint32_t* dev_out, uint64_t capacity)
 {
-    if (!gc || !dev_values || !dev_out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    uint64_t n = 0;
-    VX_TRY(nearest_check(gc, flags, dev_values, nvalues, true, dev_out, capacity, &n));
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return nearest_queue(g, flags, dev_values, fill, dev_out);
+    return nearest_entry(g, flags, true, dev_values, nvalues, fill, dev_out, capacity, false);
 }
 
-vx_status vx_grid_nearest_gather(const vx_grid* gc, uint32_t flags, const uint32_t* host_values, uint64_t nvalues, uint32_t fill,
+vx_status vx_grid_nearest_gather(const vx_grid* g, uint32_t flags, const uint32_t* host_values, uint64_t nvalues, uint32_t fill,
                                  uint32_t* host_out, uint64_t capacity)
 {
-    if (!gc || !host_values || !host_out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    uint64_t n = 0;
-    VX_TRY(nearest_check(gc, flags, host_values, nvalues, true, host_out, capacity, &n));
-    if (!n) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return nearest_host(g, flags, host_values, fill, host_out, n);
+    return nearest_entry(g, flags, true, host_values, nvalues, fill, host_out, capacity, true);
 }
 
 // Morphology (vx_morph.hip).  Every operation is a chain of stages on the grid's stream; the scratch of all of them lives on the handle
@@ -2672,37 +2652,36 @@ static vx_status morph_args(const vx_grid* g, uint32_t op, uint32_t r2, const vo
     return VX_OK;
 }
 
-vx_status vx_grid_morph_device(const vx_grid* gc, uint32_t op, uint32_t radius_sq, uint32_t* dev_words, uint64_t capacity_words)
+// vx_grid_morph_device / vx_grid_morph_mask; only the device variant's output can overlap the grid's own mask
+static vx_status morph_entry(const vx_grid* gc, uint32_t op, uint32_t r2, uint32_t* words, uint64_t capacity_words, bool host)
 {
-    VX_TRY(morph_args(gc, op, radius_sq, dev_words));
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    const uintptr_t a = (uintptr_t)dev_words, b = (uintptr_t)g->words.p, n = (uintptr_t)g->g.nwords * 4u;
-    if (n && a < b + n && b < a + n) return fail(VX_ERR_INVALID_ARG, "the output overlaps the grid's own bitmask");
-    if (!g->g.nvox) return VX_OK;
     MorphPlan p;
-    VX_TRY(morph_plan(g, op, radius_sq, &p));
-    if (capacity_words < g->g.nwords) return fail(VX_ERR_CAPACITY, "morphology: mask buffer too small");
-    DeviceGuard dg(g->device);
-    VX_TRY(morph_run(g, g->words.as<uint32_t>(), g->g.dim, op, radius_sq, p, dev_words));
-    VX_HIP(hipGetLastError());
-    return VX_OK;
+    return field_entry(gc, nullptr, false, words, host, &vx_grid::morph_out, 8,
+        [&](size_t* bytes) {
+            VX_TRY(morph_args(gc, op, r2, words));
+            const uintptr_t a = (uintptr_t)words, b = (uintptr_t)gc->words.p, n = (uintptr_t)gc->g.nwords * 4u;
+            if (!host && n && a < b + n && b < a + n) return fail(VX_ERR_INVALID_ARG, "the output overlaps the grid's own bitmask");
+            if (!gc->g.nvox) return VX_OK;
+            VX_TRY(morph_plan(gc, op, r2, &p));
+            if (capacity_words < gc->g.nwords) return fail(VX_ERR_CAPACITY, "morphology: mask buffer too small");
+            *bytes = (size_t)gc->g.nwords * 4;
+            return VX_OK;
+        },
+        [&](vx_grid* g, const void*, void* dev_words) {
+            VX_TRY(morph_run(g, g->words.as<uint32_t>(), g->g.dim, op, r2, p, static_cast<uint32_t*>(dev_words)));
+            VX_HIP(hipGetLastError());
+            return VX_OK;
+        });
 }
 
-vx_status vx_grid_morph_mask(const vx_grid* gc, uint32_t op, uint32_t radius_sq, uint32_t* host_words, uint64_t capacity_words)
+vx_status vx_grid_morph_device(const vx_grid* g, uint32_t op, uint32_t radius_sq, uint32_t* dev_words, uint64_t capacity_words)
 {
-    VX_TRY(morph_args(gc, op, radius_sq, host_words));
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    if (!g->g.nvox) return VX_OK;
-    MorphPlan p;
-    VX_TRY(morph_plan(g, op, radius_sq, &p));
-    if (capacity_words < g->g.nwords) return fail(VX_ERR_CAPACITY, "morphology: mask buffer too small");
-    DeviceGuard dg(g->device);
-    VX_HIP(g->morph_out.ensure((size_t)(g->g.nwords + 2) * 4));
-    VX_TRY(morph_run(g, g->words.as<uint32_t>(), g->g.dim, op, radius_sq, p, g->morph_out.as<uint32_t>()));
-    VX_HIP(hipGetLastError());
-    VX_HIP(hipMemcpyAsync(host_words, g->morph_out.p, (size_t)g->g.nwords * 4, hipMemcpyDeviceToHost, g->stream));
-    VX_HIP(hipStreamSynchronize(g->stream));
-    return VX_OK;
+    return morph_entry(g, op, radius_sq, dev_words, capacity_words, false);
+}
+
+vx_status vx_grid_morph_mask(const vx_grid* g, uint32_t op, uint32_t radius_sq, uint32_t* host_words, uint64_t capacity_words)
+{
+    return morph_entry(g, op, radius_sq, host_words, capacity_words, true);
 }
 
 // the result grid's counts, list and derived data from its mask: as if vx_grid_set_voxel had run on every cell in ascending index
@@ -3272,7 +3251,9 @@ static vx_status upload_camera(DevBuf& buf, hipStream_t stream, vx::TraceIO& io)
     return VX_OK;
 }
 
-static vx_status trace_common(vx_grid* g, vx::TraceIO io)
+// The first-hit query on device arrays.  The four structures' *_trace_common share one signature, (handle, io, bary, instance), so that
+// trace_entry can call any of them; the grid and the octree have neither output.
+static vx_status trace_common(vx_grid* g, vx::TraceIO io, float* = nullptr, uint32_t* = nullptr)
 {
     VX_TRY(ensure_coarse(g));
     const uint32_t* prefix = nullptr;
@@ -3341,9 +3322,26 @@ vx_status vx_trace_primary_device(const vx_grid* gc, const float vi[16], const f
     return trace_common(g, io);
 }
 
-static vx_status args_to_io(const vx_trace_args* a, vx::Camera* cam, vx::TraceIO* io)
+// The four structures share one argument form inside the library: vx_tlas_trace_args, of which vx_trace_args (grid, octree) and
+// vx_bvh_trace_args are leading parts.
+static vx_tlas_trace_args from_trace_args(const vx_trace_args* a)
 {
-    if (!a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    vx_tlas_trace_args x{};
+    if (a) x.base = *a;
+    return x;
+}
+
+static vx_tlas_trace_args from_bvh_trace_args(const vx_bvh_trace_args* a)
+{
+    vx_tlas_trace_args x{};
+    if (a) { x.base = a->base; x.bary = a->bary; }
+    return x;
+}
+
+// The argument checks of the ray queries, in the header's order; *io receives the batch, and points at *cam for camera rays
+static vx_status args_to_io(const vx_tlas_trace_args& x, vx::Camera* cam, vx::TraceIO* io)
+{
+    const vx_trace_args* a = &x.base;
     if (!a->rays && !(a->view_inverse && a->proj_inverse && a->width && a->height)) return fail(VX_ERR_INVALID_ARG, "no rays and no camera");
     if (a->hits && !a->num_hits) return fail(VX_ERR_INVALID_ARG, "hits needs num_hits");
     io->rays = a->rays;
@@ -3359,85 +3357,97 @@ static vx_status args_to_io(const vx_trace_args* a, vx::Camera* cam, vx::TraceIO
     io->tmin = a->tmin; io->tmax = a->tmax; io->tmax_per_ray = a->tmax_per_ray; io->any_hit = a->any_hit != 0;
     io->t_out = a->t; io->prim_out = a->prim; io->normal_out = a->normal; io->shadowed_out = a->shadowed;
     io->hits = a->hits; io->nhits = (unsigned long long*)a->num_hits;
-    if (io->any_hit && (io->prim_out || io->normal_out || io->hits)) return fail(VX_ERR_INVALID_ARG, "any_hit reports only `shadowed` (and an arbitrary accepted t)");
+    if (io->any_hit && (io->prim_out || io->normal_out || io->hits || x.bary || x.instance))
+        return fail(VX_ERR_INVALID_ARG, "any_hit reports only `shadowed` (and an arbitrary accepted t)");
     return VX_OK;
 }
 
-vx_status vx_trace_ex_device(const vx_grid* gc, const vx_trace_args* args)
-{
-    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(args_to_io(args, &cam, &io));
-    return trace_common(g, io);
-}
+// The host variants' arrays, through pooled device memory of `home` (the handle: its device and stream), one block each.  in() queues an
+// upload, out() notes a download, finish() queues the downloads and waits once.  A null host array is no array: null comes back.  The
+// first failure is kept (status()) and turns every later call into a no-op.  From the first queued upload on the stream reads the
+// caller's arrays, so a Staging that goes out of scope before finish() has waited -- a failed run, a failed ensure or copy -- waits first.
+extern "C++" {
+class Staging {
+    struct Block {
+        DevBuf buf;
+        void* host;  // where finish() copies `bytes` back to; null: an input
+        size_t bytes;
+    };
+    const Home& home;
+    std::vector<Block> blocks;
+    vx_status st = VX_OK;
+    bool queued = false;
 
-// an output of one handle type beside vx_trace_args' (bary, instance): the host array (null: not wanted), its bytes per ray, and where
-// `run` finds the staged device array
-struct StagedOut {
-    void* host;
-    size_t stride;
-    void** dev;
+    void* add(const void* src, void* dst, size_t bytes, size_t spare)
+    {
+        if (st != VX_OK || !(src || dst)) return nullptr;
+        blocks.push_back(Block{DevBuf{&home}, dst, bytes});
+        DevBuf& b = blocks.back().buf;
+        hipError_t e = b.ensure(bytes + spare);
+        if (e == hipSuccess && src) {
+            e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, home.stream);
+            queued = queued || e == hipSuccess;
+        }
+        if (e != hipSuccess) st = fail(VX_ERR_HIP, std::string("staging a host array: ") + hipGetErrorString(e));
+        return st == VX_OK ? b.p : nullptr;
+    }
+
+public:
+    explicit Staging(const Home& h) : home(h) { blocks.reserve(10); }
+    Staging(const Staging&) = delete;
+    Staging& operator=(const Staging&) = delete;
+    ~Staging() { if (queued) (void)hipStreamSynchronize(home.stream); }
+    template <class T> T* in(const T* host, size_t bytes) { return static_cast<T*>(add(host, nullptr, bytes, 0)); }
+    // `spare`: bytes of the block behind the array, which the kernel may touch and nobody reads
+    template <class T> T* out(T* host, size_t bytes, size_t spare = 0) { return static_cast<T*>(add(nullptr, host, bytes, spare)); }
+    vx_status status() const { return st; }
+    vx_status finish()
+    {
+        VX_TRY(st);
+        for (const Block& b : blocks)
+            if (b.host) VX_HIP(hipMemcpyAsync(b.host, b.buf.p, b.bytes, hipMemcpyDeviceToHost, home.stream));
+        VX_HIP(hipStreamSynchronize(home.stream));
+        queued = false;
+        return VX_OK;
+    }
 };
 
-// host-buffer variant: stages every non-null array (and at most two `extra` outputs) through pooled device memory of `home` (the handle:
-// its device and stream), then runs `run(io)` on the staged io
-extern "C++" {
-template <class Run>
-static vx_status trace_ex_staged(const Home& home, const vx_trace_args* args, Run run, std::initializer_list<StagedOut> extra = {})
+// The eight vx_*_trace_ex* entry points: the null checks, the argument checks, (host) the refusal of `hits` and the zero-ray return, the
+// guard, then common(handle, io, bary, instance) on the caller's device arrays or on staged copies of the host arrays.  `given`: the
+// caller's args pointer, `a` its conversion.
+template <class H, class Common>
+static vx_status trace_entry(const H* hc, const void* given, const vx_tlas_trace_args& a, bool host, Common common)
 {
+    if (!hc || !given) return fail(VX_ERR_INVALID_ARG, "null argument");
     vx::Camera cam{};
     vx::TraceIO io;
-    VX_TRY(args_to_io(args, &cam, &io));
-    if (args->hits) return fail(VX_ERR_UNSUPPORTED, "the compacted hit list is a device-side output: use the _device variant");
-    const uint64_t n = io.nrays;
+    VX_TRY(args_to_io(a, &cam, &io));
+    H* h = const_cast<H*>(hc);
+    if (!host) {
+        DeviceGuard dg(h->device);
+        return common(h, io, a.bary, a.instance);
+    }
+    if (io.hits) return fail(VX_ERR_UNSUPPORTED, "the compacted hit list is a device-side output: use the _device variant");
+    const size_t n = (size_t)io.nrays;
     if (!n) return VX_OK;
-    if (extra.size() > 2) return fail(VX_ERR_INVALID_ARG, "trace_ex_staged: more than two extra outputs");
-    hipStream_t stream = home.stream;
-    DevBuf dr{&home}, dtm{&home}, dt{&home}, dp{&home}, dn{&home}, ds{&home}, dx[2] = {DevBuf{&home}, DevBuf{&home}};
-    if (io.rays) {
-        VX_HIP(dr.ensure((size_t)n * 24));
-        VX_HIP(hipMemcpyAsync(dr.p, args->rays, (size_t)n * 24, hipMemcpyHostToDevice, stream));
-        io.rays = dr.as<float>();
-    }
-    if (io.tmax_per_ray) {
-        VX_HIP(dtm.ensure((size_t)n * 4));
-        VX_HIP(hipMemcpyAsync(dtm.p, args->tmax_per_ray, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-        io.tmax_per_ray = dtm.as<float>();
-    }
-    if (args->t) { VX_HIP(dt.ensure((size_t)n * 4)); io.t_out = dt.as<float>(); }
-    if (args->prim) { VX_HIP(dp.ensure((size_t)n * 4)); io.prim_out = dp.as<uint32_t>(); }
-    if (args->normal) { VX_HIP(dn.ensure((size_t)n * 12)); io.normal_out = dn.as<float>(); }
-    if (args->shadowed) { VX_HIP(ds.ensure((size_t)n)); io.shadowed_out = ds.as<uint8_t>(); }
-    DevBuf* xb = dx;
-    for (const StagedOut& x : extra) {
-        if (x.host) { VX_HIP(xb->ensure((size_t)n * x.stride + 16)); *x.dev = xb->p; }
-        ++xb;
-    }
-    VX_TRY(run(io));
-    if (args->t) VX_HIP(hipMemcpyAsync(args->t, dt.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-    if (args->prim) VX_HIP(hipMemcpyAsync(args->prim, dp.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-    if (args->normal) VX_HIP(hipMemcpyAsync(args->normal, dn.p, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
-    if (args->shadowed) VX_HIP(hipMemcpyAsync(args->shadowed, ds.p, (size_t)n, hipMemcpyDeviceToHost, stream));
-    xb = dx;
-    for (const StagedOut& x : extra) {
-        if (x.host) VX_HIP(hipMemcpyAsync(x.host, xb->p, (size_t)n * x.stride, hipMemcpyDeviceToHost, stream));
-        ++xb;
-    }
-    VX_HIP(hipStreamSynchronize(stream));
-    return VX_OK;
+    DeviceGuard dg(h->device);
+    Staging s(*h);
+    io.rays = s.in(io.rays, n * 24);
+    io.tmax_per_ray = s.in(io.tmax_per_ray, n * 4);
+    io.t_out = s.out(io.t_out, n * 4);
+    io.prim_out = s.out(io.prim_out, n * 4);
+    io.normal_out = s.out(io.normal_out, n * 12);
+    io.shadowed_out = s.out(io.shadowed_out, n);
+    float* bary = s.out(a.bary, n * 8, 16);
+    uint32_t* inst = s.out(a.instance, n * 4, 16);
+    VX_TRY(s.status());
+    VX_TRY(common(h, io, bary, inst));
+    return s.finish();
 }
 }  // extern "C++"
 
-vx_status vx_trace_ex(const vx_grid* gc, const vx_trace_args* args)
-{
-    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return trace_ex_staged(*g, args, [&](const vx::TraceIO& io) { return trace_common(g, io); });
-}
+vx_status vx_trace_ex_device(const vx_grid* g, const vx_trace_args* args) { return trace_entry(g, args, from_trace_args(args), false, trace_common); }
+vx_status vx_trace_ex(const vx_grid* g, const vx_trace_args* args) { return trace_entry(g, args, from_trace_args(args), true, trace_common); }
 
 // ---- multi-hit query (vx_multihit.hip) -----------------------------------------------------------------------------
 // The four structures share one argument form inside the library: vx_tlas_multihit_args, of which vx_multihit_args (grid, octree) and
@@ -3471,7 +3481,7 @@ static vx_status multihit_args_to_io(const void* handle, const vx_tlas_multihit_
         return fail(VX_ERR_INVALID_ARG, "any_hit, normal, shadowed, hits and num_hits are not part of the multi-hit query");
     const bool camera = b.view_inverse && b.proj_inverse && b.width && b.height;
     if (!b.rays && !camera && !b.num_rays) { io->nrays = 0; return VX_OK; }  // zero rays
-    return args_to_io(&b, cam, io);
+    return args_to_io(from_trace_args(&b), cam, io);
 }
 
 static vx::MultiIO multi_io(const vx_tlas_multihit_args& a)
@@ -3487,53 +3497,35 @@ static vx::MultiIO multi_io(const vx_tlas_multihit_args& a)
     return m;
 }
 
-// the host variants: every non-null array of `a` through pooled device memory of `home` (the handle: its device and stream), then
-// `run(io, d)` on the staged batch io and the staged copy d of the arguments
+// The eight vx_*_trace_multi* entry points: the checks, the zero-ray return, the guard, then common(handle, io, args) on the caller's device
+// arrays or on staged copies of the host arrays.  `given`: the caller's args pointer, `a` its conversion; tlas: see multihit_args_to_io.
 extern "C++" {
-template <class Run>
-static vx_status multihit_staged(const Home& home, const vx_tlas_multihit_args& a, vx::TraceIO io, Run run)
+template <class H, class Common>
+static vx_status multihit_entry(const H* hc, const void* given, const vx_tlas_multihit_args& a, bool tlas, bool host, Common common)
 {
+    vx::Camera cam{};
+    vx::TraceIO io;
+    VX_TRY(multihit_args_to_io(hc, given ? &a : nullptr, tlas, &cam, &io));
+    if (!io.nrays) return VX_OK;
+    H* h = const_cast<H*>(hc);
+    DeviceGuard dg(h->device);
+    if (!host) return common(h, io, a);
     const size_t n = (size_t)io.nrays, K = a.m.max_hits;
-    hipStream_t stream = home.stream;
-    DevBuf dr{&home}, dtm{&home}, dat{&home}, dai{&home}, dap{&home}, dt{&home}, dp{&home}, db{&home}, di{&home}, dc{&home};
-    auto upload = [&](DevBuf& b, const void* host, size_t bytes) -> hipError_t {
-        if (!host) return hipSuccess;
-        const hipError_t e = b.ensure(bytes);
-        return e == hipSuccess ? hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, stream) : e;
-    };
-    VX_HIP(upload(dr, a.m.base.rays, n * 24));
-    VX_HIP(upload(dtm, a.m.base.tmax_per_ray, n * 4));
-    VX_HIP(upload(dat, a.m.after_t, n * 4));
-    VX_HIP(upload(dai, a.after_instance, n * 4));
-    VX_HIP(upload(dap, a.m.after_prim, n * 4));
-    if (a.m.base.t) VX_HIP(dt.ensure(n * K * 4));
-    if (a.m.base.prim) VX_HIP(dp.ensure(n * K * 4));
-    if (a.bary) VX_HIP(db.ensure(n * K * 8));
-    if (a.instance) VX_HIP(di.ensure(n * K * 4));
-    if (a.m.count) VX_HIP(dc.ensure(n * 4));
-    if (io.rays) io.rays = dr.as<float>();
-    if (io.tmax_per_ray) io.tmax_per_ray = dtm.as<float>();
-    io.t_out = dt.as<float>();
-    io.prim_out = dp.as<uint32_t>();
+    Staging s(*h);
     vx_tlas_multihit_args d = a;
-    d.m.count = dc.as<uint32_t>();
-    d.m.after_t = dat.as<float>();
-    d.after_instance = dai.as<uint32_t>();
-    d.m.after_prim = dap.as<uint32_t>();
-    d.bary = db.as<float>();
-    d.instance = di.as<uint32_t>();
-    const vx_status st = run(io, d);
-    if (st != VX_OK) {
-        (void)hipStreamSynchronize(stream);  // the uploads read the caller's arrays
-        return st;
-    }
-    if (a.m.base.t) VX_HIP(hipMemcpyAsync(a.m.base.t, dt.p, n * K * 4, hipMemcpyDeviceToHost, stream));
-    if (a.m.base.prim) VX_HIP(hipMemcpyAsync(a.m.base.prim, dp.p, n * K * 4, hipMemcpyDeviceToHost, stream));
-    if (a.bary) VX_HIP(hipMemcpyAsync(a.bary, db.p, n * K * 8, hipMemcpyDeviceToHost, stream));
-    if (a.instance) VX_HIP(hipMemcpyAsync(a.instance, di.p, n * K * 4, hipMemcpyDeviceToHost, stream));
-    if (a.m.count) VX_HIP(hipMemcpyAsync(a.m.count, dc.p, n * 4, hipMemcpyDeviceToHost, stream));
-    VX_HIP(hipStreamSynchronize(stream));
-    return VX_OK;
+    io.rays = s.in(io.rays, n * 24);
+    io.tmax_per_ray = s.in(io.tmax_per_ray, n * 4);
+    d.m.after_t = s.in(a.m.after_t, n * 4);
+    d.after_instance = s.in(a.after_instance, n * 4);
+    d.m.after_prim = s.in(a.m.after_prim, n * 4);
+    io.t_out = s.out(io.t_out, n * K * 4);
+    io.prim_out = s.out(io.prim_out, n * K * 4);
+    d.bary = s.out(a.bary, n * K * 8);
+    d.instance = s.out(a.instance, n * K * 4);
+    d.m.count = s.out(a.m.count, n * 4);
+    VX_TRY(s.status());
+    VX_TRY(common(h, io, d));
+    return s.finish();
 }
 }  // extern "C++"
 
@@ -3557,28 +3549,14 @@ static vx_status multihit_common(vx_grid* g, vx::TraceIO io, const vx_tlas_multi
     return VX_OK;
 }
 
-vx_status vx_trace_multi_device(const vx_grid* gc, const vx_multihit_args* args)
+vx_status vx_trace_multi_device(const vx_grid* g, const vx_multihit_args* args)
 {
-    const vx_tlas_multihit_args a = from_grid_args(args);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(gc, args ? &a : nullptr, false, &cam, &io));
-    if (!io.nrays) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return multihit_common(g, io, a);
+    return multihit_entry(g, args, from_grid_args(args), false, false, multihit_common);
 }
 
-vx_status vx_trace_multi(const vx_grid* gc, const vx_multihit_args* args)
+vx_status vx_trace_multi(const vx_grid* g, const vx_multihit_args* args)
 {
-    const vx_tlas_multihit_args a = from_grid_args(args);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(gc, args ? &a : nullptr, false, &cam, &io));
-    if (!io.nrays) return VX_OK;
-    vx_grid* g = const_cast<vx_grid*>(gc);
-    DeviceGuard dg(g->device);
-    return multihit_staged(*g, a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return multihit_common(g, sio, d); });
+    return multihit_entry(g, args, from_grid_args(args), false, true, multihit_common);
 }
 
 // vx_trace / vx_octree_trace: t and prim of a host ray buffer through the handle's host-buffer extended query, hits counted on the host
@@ -3767,7 +3745,7 @@ vx_status vx_octree_aabbs(const vx_octree* o, vx_aabb* host_out, uint64_t cap, u
 }
 
 // ---- rays on the octree: the grid trace's contract over the vx_octree_aabbs list (vx_octrace.hip) ----------------------------------
-static vx_status octree_trace_common(vx_octree* o, vx::TraceIO io)
+static vx_status octree_trace_common(vx_octree* o, vx::TraceIO io, float*, uint32_t*)
 {
     if (!io.nrays) return VX_OK;
     VX_TRY(upload_camera(o->camera, o->stream, io));
@@ -3777,23 +3755,14 @@ static vx_status octree_trace_common(vx_octree* o, vx::TraceIO io)
     return VX_OK;
 }
 
-vx_status vx_octree_trace_ex_device(const vx_octree* oc, const vx_trace_args* args)
+vx_status vx_octree_trace_ex_device(const vx_octree* o, const vx_trace_args* args)
 {
-    if (!oc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_octree* o = const_cast<vx_octree*>(oc);
-    DeviceGuard dg(o->device);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(args_to_io(args, &cam, &io));
-    return octree_trace_common(o, io);
+    return trace_entry(o, args, from_trace_args(args), false, octree_trace_common);
 }
 
-vx_status vx_octree_trace_ex(const vx_octree* oc, const vx_trace_args* args)
+vx_status vx_octree_trace_ex(const vx_octree* o, const vx_trace_args* args)
 {
-    if (!oc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_octree* o = const_cast<vx_octree*>(oc);
-    DeviceGuard dg(o->device);
-    return trace_ex_staged(*o, args, [&](const vx::TraceIO& io) { return octree_trace_common(o, io); });
+    return trace_entry(o, args, from_trace_args(args), true, octree_trace_common);
 }
 
 vx_status vx_octree_trace(const vx_octree* oc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim,
@@ -3813,28 +3782,14 @@ static vx_status octree_multihit_common(vx_octree* o, vx::TraceIO io, const vx_t
     return VX_OK;
 }
 
-vx_status vx_octree_trace_multi_device(const vx_octree* oc, const vx_multihit_args* args)
+vx_status vx_octree_trace_multi_device(const vx_octree* o, const vx_multihit_args* args)
 {
-    const vx_tlas_multihit_args a = from_grid_args(args);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(oc, args ? &a : nullptr, false, &cam, &io));
-    if (!io.nrays) return VX_OK;
-    vx_octree* o = const_cast<vx_octree*>(oc);
-    DeviceGuard dg(o->device);
-    return octree_multihit_common(o, io, a);
+    return multihit_entry(o, args, from_grid_args(args), false, false, octree_multihit_common);
 }
 
-vx_status vx_octree_trace_multi(const vx_octree* oc, const vx_multihit_args* args)
+vx_status vx_octree_trace_multi(const vx_octree* o, const vx_multihit_args* args)
 {
-    const vx_tlas_multihit_args a = from_grid_args(args);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(oc, args ? &a : nullptr, false, &cam, &io));
-    if (!io.nrays) return VX_OK;
-    vx_octree* o = const_cast<vx_octree*>(oc);
-    DeviceGuard dg(o->device);
-    return multihit_staged(*o, a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return octree_multihit_common(o, sio, d); });
+    return multihit_entry(o, args, from_grid_args(args), false, true, octree_multihit_common);
 }
 
 void vx_octree_free(vx_octree* o)
@@ -4005,7 +3960,7 @@ vx_status vx_bvh_leaf_triangles(const vx_bvh* b, uint32_t* host, uint64_t cap)
     return VX_OK;
 }
 
-static vx_status bvh_trace_common(vx_bvh* b, vx::TraceIO io, float* bary)
+static vx_status bvh_trace_common(vx_bvh* b, vx::TraceIO io, float* bary, uint32_t*)
 {
     if (!io.nrays) return VX_OK;
     VX_TRY(upload_camera(b->camera, b->stream, io));
@@ -4015,36 +3970,14 @@ static vx_status bvh_trace_common(vx_bvh* b, vx::TraceIO io, float* bary)
     return VX_OK;
 }
 
-static vx_status bvh_args_to_io(const vx_bvh_trace_args* a, vx::Camera* cam, vx::TraceIO* io)
+vx_status vx_bvh_trace_ex_device(const vx_bvh* b, const vx_bvh_trace_args* args)
 {
-    if (!a) return fail(VX_ERR_INVALID_ARG, "null argument");
-    VX_TRY(args_to_io(&a->base, cam, io));
-    if (io->any_hit && a->bary) return fail(VX_ERR_INVALID_ARG, "any_hit reports only `shadowed` (and an arbitrary accepted t)");
-    return VX_OK;
+    return trace_entry(b, args, from_bvh_trace_args(args), false, bvh_trace_common);
 }
 
-vx_status vx_bvh_trace_ex_device(const vx_bvh* bc, const vx_bvh_trace_args* args)
+vx_status vx_bvh_trace_ex(const vx_bvh* b, const vx_bvh_trace_args* args)
 {
-    if (!bc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_bvh* b = const_cast<vx_bvh*>(bc);
-    DeviceGuard dg(b->device);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(bvh_args_to_io(args, &cam, &io));
-    return bvh_trace_common(b, io, args->bary);
-}
-
-vx_status vx_bvh_trace_ex(const vx_bvh* bc, const vx_bvh_trace_args* args)
-{
-    if (!bc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_bvh* b = const_cast<vx_bvh*>(bc);
-    DeviceGuard dg(b->device);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(bvh_args_to_io(args, &cam, &io));
-    void* bary = nullptr;  // the staged array (null when args->bary is)
-    return trace_ex_staged(*b, &args->base, [&](const vx::TraceIO& sio) { return bvh_trace_common(b, sio, (float*)bary); },
-                           {{args->bary, 8, &bary}});
+    return trace_entry(b, args, from_bvh_trace_args(args), true, bvh_trace_common);
 }
 
 vx_status vx_bvh_trace(const vx_bvh* bc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_prim,
@@ -4069,28 +4002,14 @@ static vx_status bvh_multihit_common(vx_bvh* b, vx::TraceIO io, const vx_tlas_mu
     return VX_OK;
 }
 
-vx_status vx_bvh_trace_multi_device(const vx_bvh* bc, const vx_bvh_multihit_args* args)
+vx_status vx_bvh_trace_multi_device(const vx_bvh* b, const vx_bvh_multihit_args* args)
 {
-    const vx_tlas_multihit_args a = from_bvh_args(args);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(bc, args ? &a : nullptr, false, &cam, &io));
-    if (!io.nrays) return VX_OK;
-    vx_bvh* b = const_cast<vx_bvh*>(bc);
-    DeviceGuard dg(b->device);
-    return bvh_multihit_common(b, io, a);
+    return multihit_entry(b, args, from_bvh_args(args), false, false, bvh_multihit_common);
 }
 
-vx_status vx_bvh_trace_multi(const vx_bvh* bc, const vx_bvh_multihit_args* args)
+vx_status vx_bvh_trace_multi(const vx_bvh* b, const vx_bvh_multihit_args* args)
 {
-    const vx_tlas_multihit_args a = from_bvh_args(args);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(bc, args ? &a : nullptr, false, &cam, &io));
-    if (!io.nrays) return VX_OK;
-    vx_bvh* b = const_cast<vx_bvh*>(bc);
-    DeviceGuard dg(b->device);
-    return multihit_staged(*b, a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return bvh_multihit_common(b, sio, d); });
+    return multihit_entry(b, args, from_bvh_args(args), false, true, bvh_multihit_common);
 }
 
 void vx_bvh_free(vx_bvh* b)
@@ -4264,13 +4183,6 @@ vx_status tlas_trace_common(vx_tlas* t, vx::TraceIO io, float* bary, uint32_t* i
     return tlas_fence_blas(t);
 }
 
-vx_status tlas_args_to_io(const vx_tlas_trace_args* a, vx::Camera* cam, vx::TraceIO* io)
-{
-    if (!a) return fail(VX_ERR_INVALID_ARG, "null argument");
-    VX_TRY(args_to_io(&a->base, cam, io));
-    if (io->any_hit && (a->bary || a->instance)) return fail(VX_ERR_INVALID_ARG, "any_hit reports only `shadowed` (and an arbitrary accepted t)");
-    return VX_OK;
-}
 }  // namespace
 
 vx_status vx_tlas_build(const vx_bvh* const* blas, uint32_t num_blas, const vx_instance* host_instances, uint64_t num_instances, void* stream,
@@ -4356,28 +4268,14 @@ vx_status vx_tlas_nodes(const vx_tlas* t, void* host, uint64_t cap, uint64_t* by
     return VX_OK;
 }
 
-vx_status vx_tlas_trace_ex_device(const vx_tlas* tc, const vx_tlas_trace_args* args)
+vx_status vx_tlas_trace_ex_device(const vx_tlas* t, const vx_tlas_trace_args* args)
 {
-    if (!tc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_tlas* t = const_cast<vx_tlas*>(tc);
-    DeviceGuard dg(t->device);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(tlas_args_to_io(args, &cam, &io));
-    return tlas_trace_common(t, io, args->bary, args->instance);
+    return trace_entry(t, args, args ? *args : vx_tlas_trace_args{}, false, tlas_trace_common);
 }
 
-vx_status vx_tlas_trace_ex(const vx_tlas* tc, const vx_tlas_trace_args* args)
+vx_status vx_tlas_trace_ex(const vx_tlas* t, const vx_tlas_trace_args* args)
 {
-    if (!tc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    vx_tlas* t = const_cast<vx_tlas*>(tc);
-    DeviceGuard dg(t->device);
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(tlas_args_to_io(args, &cam, &io));
-    void *bary = nullptr, *inst = nullptr;  // the staged arrays (null when the argument is)
-    return trace_ex_staged(*t, &args->base, [&](const vx::TraceIO& sio) { return tlas_trace_common(t, sio, (float*)bary, (uint32_t*)inst); },
-                           {{args->bary, 8, &bary}, {args->instance, 4, &inst}});
+    return trace_entry(t, args, args ? *args : vx_tlas_trace_args{}, true, tlas_trace_common);
 }
 
 vx_status vx_tlas_trace(const vx_tlas* tc, const float* host_rays, uint64_t nrays, float tmin, float tmax, float* host_t, uint32_t* host_instance,
@@ -4402,26 +4300,14 @@ static vx_status tlas_multihit_common(vx_tlas* t, vx::TraceIO io, const vx_tlas_
     return tlas_fence_blas(t);
 }
 
-vx_status vx_tlas_trace_multi_device(const vx_tlas* tc, const vx_tlas_multihit_args* a)
+vx_status vx_tlas_trace_multi_device(const vx_tlas* t, const vx_tlas_multihit_args* a)
 {
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(tc, a, true, &cam, &io));
-    if (!io.nrays) return VX_OK;
-    vx_tlas* t = const_cast<vx_tlas*>(tc);
-    DeviceGuard dg(t->device);
-    return tlas_multihit_common(t, io, *a);
+    return multihit_entry(t, a, a ? *a : vx_tlas_multihit_args{}, true, false, tlas_multihit_common);
 }
 
-vx_status vx_tlas_trace_multi(const vx_tlas* tc, const vx_tlas_multihit_args* a)
+vx_status vx_tlas_trace_multi(const vx_tlas* t, const vx_tlas_multihit_args* a)
 {
-    vx::Camera cam{};
-    vx::TraceIO io;
-    VX_TRY(multihit_args_to_io(tc, a, true, &cam, &io));
-    if (!io.nrays) return VX_OK;
-    vx_tlas* t = const_cast<vx_tlas*>(tc);
-    DeviceGuard dg(t->device);
-    return multihit_staged(*t, *a, io, [&](const vx::TraceIO& sio, const vx_tlas_multihit_args& d) { return tlas_multihit_common(t, sio, d); });
+    return multihit_entry(t, a, a ? *a : vx_tlas_multihit_args{}, true, true, tlas_multihit_common);
 }
 
 void vx_tlas_free(vx_tlas* t)

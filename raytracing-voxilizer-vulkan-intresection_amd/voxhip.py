@@ -33,95 +33,127 @@ MATERIAL = np.dtype([("ambient", np.float32, 3), ("diffuse", np.float32, 3), ("s
                      ("illum", np.int32), ("texture_id", np.int32)])
 
 
-def _trace_ex(fn, h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want, bvh=False):
-    """vx_trace_ex / vx_octree_trace_ex / vx_bvh_trace_ex (bvh=True: fn takes vx_bvh_trace_args) on host arrays -> dict of the requested
-    outputs (t, prim, normal, shadowed; bary for the BVH)."""
-    ba = BvhTraceArgs() if bvh else None
-    a = ba.base if bvh else TraceArgs()
-    keep = []
-    if rays is not None:
+def _levels(a):
+    """An argument structure and the structures it leads with, outermost first: TlasMultiHitArgs -> [a, a.m, a.m.base], BvhTraceArgs ->
+    [a, a.base], TraceArgs -> [a].  The last one is always the TraceArgs."""
+    lv = [a]
+    for f in ("m", "base"):
+        if hasattr(lv[-1], f):
+            lv.append(getattr(lv[-1], f))
+    return lv
+
+
+def _ray_batch(base, rays, camera, tmin, tmax, tmax_per_ray, keep):
+    """Fills the ray batch of a TraceArgs (the .base of any of the six argument structures) and returns the number of rays.  rays: host
+    rays, anything that becomes contiguous float32 (n, 6), or a raw (pointer, n); None: camera = (view_inv, proj_inv, width, height).
+    tmax_per_ray: a host array or None.  What the structure then points at goes into `keep`, which the caller holds over the call."""
+    if rays is None:
+        vi, pi, w, h = camera
+        cvi, cpi = [(C.c_float * 16)(*[float(x) for x in np.asarray(m).reshape(16)]) for m in (vi, pi)]
+        keep += [cvi, cpi]
+        base.view_inverse, base.proj_inverse, base.width, base.height, n = cvi, cpi, w, h, w * h
+    elif isinstance(rays, tuple) and len(rays) == 2 and not hasattr(rays[0], "__len__"):
+        base.rays, base.num_rays = rays
+        n = rays[1]
+    else:
         r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
         keep.append(r)
-        a.rays, a.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
-    else:
-        vi, pi, w, h_ = camera
-        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-        keep += [cvi, cpi]
-        a.view_inverse, a.proj_inverse, a.width, a.height, n = cvi, cpi, w, h_, w * h_
-    a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
+        base.rays, base.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
+    base.tmin, base.tmax = np.float32(tmin), np.float32(tmax)
     if tmax_per_ray is not None:
         tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
         keep.append(tm)
-        a.tmax_per_ray = tm.ctypes.data
+        base.tmax_per_ray = tm.ctypes.data
+    return n
+
+
+# the outputs of the first-hit queries: name -> (shape behind the ray index, dtype)
+_FIRST_HIT = {"t": ((), np.float32), "prim": ((), np.uint32), "normal": ((3,), np.float32), "shadowed": ((), np.uint8),
+              "bary": ((2,), np.float32), "instance": ((), np.uint32)}
+_NOT_HERE = {"bary": "bary is an output of the triangle BVH only", "instance": "instance is an output of the TLAS only"}
+
+
+def _multi_hit(k):
+    """the outputs of the multi-hit queries at max_hits = k, as _FIRST_HIT"""
+    return {"t": ((k,), np.float32), "prim": ((k,), np.uint32), "bary": ((k, 2), np.float32), "instance": ((k,), np.uint32),
+            "count": ((), np.uint32)}
+
+
+def _outputs(a, want, n, table):
+    """Allocates the arrays of `table` that `want` names, (n,) + shape each and zeroed, and points the field of that name at each: the
+    field of `a` or of a structure it leads with (_levels).  A name the structure has no field for is a ValueError.  -> dict name -> array"""
     out = {}
-    if "t" in want:
-        out["t"] = np.zeros(n, np.float32); a.t = out["t"].ctypes.data
-    if "prim" in want:
-        out["prim"] = np.zeros(n, np.uint32); a.prim = out["prim"].ctypes.data
-    if "normal" in want:
-        out["normal"] = np.zeros((n, 3), np.float32); a.normal = out["normal"].ctypes.data
-    if "shadowed" in want:
-        out["shadowed"] = np.zeros(n, np.uint8); a.shadowed = out["shadowed"].ctypes.data
-    if "bary" in want:
-        if not bvh:
-            raise ValueError("bary is an output of the triangle BVH only")
-        out["bary"] = np.zeros((n, 2), np.float32); ba.bary = out["bary"].ctypes.data
-    _check(fn(h, C.byref(ba if bvh else a)))
+    for name, (shape, dtype) in table.items():
+        if name not in want:
+            continue
+        owner = [s for s in _levels(a) if hasattr(s, name)]
+        if not owner:
+            raise ValueError(_NOT_HERE[name])
+        out[name] = np.zeros((n,) + shape, dtype)
+        setattr(owner[0], name, out[name].ctypes.data)
     return out
 
 
-def _trace_multi(fn, h, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want):
-    """vx_trace_multi / vx_octree_trace_multi on host arrays -> dict of the requested outputs: t (n, K) float32 and prim (n, K) uint32, padded
-    with -1 / 0xFFFFFFFF, count (n,) uint32"""
-    a = MultiHitArgs()
-    keep = []
-    if rays is not None:
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
-        keep.append(r)
-        a.base.rays, a.base.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
-    else:
-        vi, pi, w, h_ = camera
-        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-        keep += [cvi, cpi]
-        a.base.view_inverse, a.base.proj_inverse, a.base.width, a.base.height, n = cvi, cpi, w, h_, w * h_
-    a.base.tmin, a.base.tmax, a.max_hits = np.float32(tmin), np.float32(tmax), int(max_hits)
-    if tmax_per_ray is not None:
-        tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
-        keep.append(tm)
-        a.base.tmax_per_ray = tm.ctypes.data
-    if after is not None:
-        at = np.ascontiguousarray(after[0], dtype=np.float32)
-        ap = np.ascontiguousarray(after[1], dtype=np.uint32)
-        if at.shape != (n,) or ap.shape != (n,):
-            raise ValueError("after = (after_t, after_prim), one entry per ray each")
-        keep += [at, ap]
-        a.after_t, a.after_prim = at.ctypes.data, ap.ctypes.data
-    k = max(int(max_hits), 0)
-    out = {}
-    if "t" in want:
-        out["t"] = np.zeros((n, k), np.float32); a.base.t = out["t"].ctypes.data
-    if "prim" in want:
-        out["prim"] = np.zeros((n, k), np.uint32); a.base.prim = out["prim"].ctypes.data
-    if "count" in want:
-        out["count"] = np.zeros(n, np.uint32); a.count = out["count"].ctypes.data
+def _set_pointers(a, ptrs):
+    """the device variants' arrays: field name -> raw device pointer, each into the structure of _levels(a) that has the field"""
+    for name, p in ptrs.items():
+        setattr([s for s in _levels(a) if hasattr(s, name)][0], name, p)
+
+
+def _trace_ex(fn, h, a, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want):
+    """vx_*_trace_ex (a = the handle's TraceArgs / BvhTraceArgs / TlasTraceArgs) on host arrays -> dict of the requested outputs (t, prim,
+    normal, shadowed; bary for the BVH and the TLAS; instance for the TLAS)."""
+    base, keep = _levels(a)[-1], []
+    n = _ray_batch(base, rays, camera, tmin, tmax, tmax_per_ray, keep)
+    base.any_hit = 1 if any_hit else 0
+    out = _outputs(a, want, n, _FIRST_HIT)
     _check(fn(h, C.byref(a)))
     return out
 
 
-def _trace_multi_device(fn, h, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax, tmax_per_ray_ptr, after_t_ptr, after_prim_ptr, camera):
-    """vx_trace_multi_device / vx_octree_trace_multi_device on raw device pointers"""
-    a = MultiHitArgs()
-    if camera is not None:
-        vi, pi, w, h_ = camera
-        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-        a.base.view_inverse, a.base.proj_inverse, a.base.width, a.base.height = cvi, cpi, w, h_
-    else:
-        a.base.rays, a.base.num_rays = rays_ptr, nrays
-    a.base.tmin, a.base.tmax, a.base.tmax_per_ray, a.max_hits = np.float32(tmin), np.float32(tmax), tmax_per_ray_ptr, int(max_hits)
-    a.base.t, a.base.prim, a.count, a.after_t, a.after_prim = t_ptr, prim_ptr, count_ptr, after_t_ptr, after_prim_ptr
+def _trace_ex_device(fn, h, a, rays_ptr, nrays, camera, tmin, tmax, any_hit, **ptrs):
+    """vx_*_trace_ex_device on raw device pointers (ptrs: field name -> pointer), asynchronous on the handle's stream; camera =
+    (view_inv, proj_inv, width, height) in place of rays_ptr / nrays."""
+    base, keep = _levels(a)[-1], []
+    _ray_batch(base, (rays_ptr, nrays) if camera is None else None, camera, tmin, tmax, None, keep)
+    base.any_hit = 1 if any_hit else 0
+    _set_pointers(a, ptrs)
+    _check(fn(h, C.byref(a)))
+
+
+def _trace_multi(fn, h, a, cursor, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want):
+    """vx_*_trace_multi (a = the handle's MultiHitArgs / BvhMultiHitArgs / TlasMultiHitArgs, cursor = the arrays of its cursor: 2, or 3 for
+    the TLAS) on host arrays -> dict of the requested outputs: t (n, K) float32, prim and instance (n, K) uint32, bary (n, K, 2) float32,
+    padded with -1 / 0xFFFFFFFF / (0, 0); count (n,) uint32."""
+    m, keep = _levels(a)[-2], []
+    n = _ray_batch(m.base, rays, camera, tmin, tmax, tmax_per_ray, keep)
+    m.max_hits = int(max_hits)
+    if after is not None:
+        # (the grid and the octree have one text for both mistakes, the mesh structures one each)
+        texts = ("after = (after_t, after_prim), one entry per ray each",) * 2 if m is a else (
+            "after = (after_t, after_instance, after_prim)" if cursor == 3 else "after = (after_t, after_prim)",
+            "the cursor has one entry per ray in each of its arrays")
+        if len(after) != cursor:
+            raise ValueError(texts[0])
+        cur = [np.ascontiguousarray(after[0], dtype=np.float32)] + [np.ascontiguousarray(x, dtype=np.uint32) for x in after[1:]]
+        if any(c.shape != (n,) for c in cur):
+            raise ValueError(texts[1])
+        keep += cur
+        m.after_t, m.after_prim = cur[0].ctypes.data, cur[-1].ctypes.data
+        if cursor == 3:
+            a.after_instance = cur[1].ctypes.data
+    out = _outputs(a, want, n, _multi_hit(max(int(max_hits), 0)))
+    _check(fn(h, C.byref(a)))
+    return out
+
+
+def _trace_multi_device(fn, h, a, rays_ptr, nrays, camera, max_hits, tmin, tmax, **ptrs):
+    """vx_*_trace_multi_device on raw device pointers (ptrs: field name -> pointer), asynchronous on the handle's stream; camera =
+    (view_inv, proj_inv, width, height) in place of rays_ptr / nrays."""
+    m, keep = _levels(a)[-2], []
+    _ray_batch(m.base, (rays_ptr, nrays) if camera is None else None, camera, tmin, tmax, None, keep)
+    m.max_hits = int(max_hits)
+    _set_pointers(a, ptrs)
     _check(fn(h, C.byref(a)))
 
 
@@ -1160,7 +1192,7 @@ class Grid:
 
     def trace_ex(self, rays=None, camera=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, any_hit=False, want=("t", "prim")):
         """Host-buffer extended query -> dict of the requested outputs (t, prim, normal, shadowed)."""
-        return _trace_ex(lib().vx_trace_ex, self.h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want)
+        return _trace_ex(lib().vx_trace_ex, self.h, TraceArgs(), rays, camera, tmin, tmax, tmax_per_ray, any_hit, want)
 
     def trace_device(self, rays_ptr, nrays, t_ptr, prim_ptr=None, hits_ptr=None, nhits_ptr=None, tmin=0.001, tmax=10000.0):
         _check(lib().vx_trace_device(self.h, rays_ptr, nrays, np.float32(tmin), np.float32(tmax), t_ptr, prim_ptr, hits_ptr, nhits_ptr))
@@ -1169,19 +1201,19 @@ class Grid:
         """vx_trace_multi on host arrays: per ray the first max_hits accepted hits in (t, prim) order and the number of all of them -> dict
         of the requested outputs: t (n, K) float32 and prim (n, K) uint32, padded with -1 / 0xFFFFFFFF, count (n,) uint32.  after =
         (after_t, after_prim): per-ray cursor, only hits strictly behind it are listed and counted."""
-        return _trace_multi(lib().vx_trace_multi, self.h, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want)
+        return _trace_multi(lib().vx_trace_multi, self.h, MultiHitArgs(), 2, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want)
 
     def trace_multi_device(self, rays_ptr, nrays, max_hits, t_ptr=None, prim_ptr=None, count_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None,
                            after_t_ptr=None, after_prim_ptr=None, camera=None):
         """vx_trace_multi_device on raw device pointers, asynchronous on the grid's stream; t / prim hold max_hits entries per ray.
         camera = (view_inv, proj_inv, width, height) in place of rays_ptr / nrays."""
-        _trace_multi_device(lib().vx_trace_multi_device, self.h, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax, tmax_per_ray_ptr,
-                            after_t_ptr, after_prim_ptr, camera)
+        _trace_multi_device(lib().vx_trace_multi_device, self.h, MultiHitArgs(), rays_ptr, nrays, camera, max_hits, tmin, tmax, t=t_ptr, prim=prim_ptr,
+                            count=count_ptr, tmax_per_ray=tmax_per_ray_ptr, after_t=after_t_ptr, after_prim=after_prim_ptr)
 
     def trace_primary_device(self, view_inv, proj_inv, width, height, t_ptr, prim_ptr=None, tmin=0.001, tmax=10000.0):
-        vi = (C.c_float * 16)(*[float(x) for x in np.asarray(view_inv).reshape(16)])
-        pi = (C.c_float * 16)(*[float(x) for x in np.asarray(proj_inv).reshape(16)])
-        _check(lib().vx_trace_primary_device(self.h, vi, pi, width, height, np.float32(tmin), np.float32(tmax), t_ptr, prim_ptr))
+        a = TraceArgs()
+        _ray_batch(a, None, (view_inv, proj_inv, width, height), tmin, tmax, None, [])
+        _check(lib().vx_trace_primary_device(self.h, a.view_inverse, a.proj_inverse, a.width, a.height, a.tmin, a.tmax, t_ptr, prim_ptr))
 
     def free(self):
         if self.h and self.owned:
@@ -1338,37 +1370,25 @@ class Octree:
 
     def trace_ex(self, rays=None, camera=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, any_hit=False, want=("t", "prim")):
         """vx_octree_trace_ex: host-buffer extended query -> dict of the requested outputs (t, prim, normal, shadowed)."""
-        return _trace_ex(lib().vx_octree_trace_ex, self.h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want)
+        return _trace_ex(lib().vx_octree_trace_ex, self.h, TraceArgs(), rays, camera, tmin, tmax, tmax_per_ray, any_hit, want)
 
     def trace_device(self, rays_ptr, nrays, t_ptr=None, prim_ptr=None, hits_ptr=None, nhits_ptr=None, tmin=0.001, tmax=10000.0,
                      normal_ptr=None, shadowed_ptr=None, tmax_per_ray_ptr=None, any_hit=False, camera=None):
         """vx_octree_trace_ex_device on device pointers (e.g. torch tensors' data_ptr()); camera = (view_inv, proj_inv, W, H) instead of rays."""
-        a = TraceArgs()
-        keep = []
-        if camera is not None:
-            vi, pi, w, h = camera
-            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-            keep += [cvi, cpi]
-            a.view_inverse, a.proj_inverse, a.width, a.height = cvi, cpi, w, h
-        else:
-            a.rays, a.num_rays = rays_ptr, nrays
-        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
-        a.tmax_per_ray, a.t, a.prim, a.normal, a.shadowed = tmax_per_ray_ptr, t_ptr, prim_ptr, normal_ptr, shadowed_ptr
-        a.hits, a.num_hits = hits_ptr, nhits_ptr
-        _check(lib().vx_octree_trace_ex_device(self.h, C.byref(a)))
+        _trace_ex_device(lib().vx_octree_trace_ex_device, self.h, TraceArgs(), rays_ptr, nrays, camera, tmin, tmax, any_hit, t=t_ptr, prim=prim_ptr,
+                         normal=normal_ptr, shadowed=shadowed_ptr, tmax_per_ray=tmax_per_ray_ptr, hits=hits_ptr, num_hits=nhits_ptr)
 
     def trace_multi(self, rays=None, camera=None, max_hits=8, tmin=0.001, tmax=10000.0, tmax_per_ray=None, after=None, want=("t", "prim", "count")):
         """vx_octree_trace_multi on host arrays: per ray the first max_hits accepted voxels in (t, prim) order and the number of all of them
         -> dict as Grid.trace_multi gives it.  A voxel is a run of equal codes of the aabbs() list, prim the first list index of its run."""
-        return _trace_multi(lib().vx_octree_trace_multi, self.h, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want)
+        return _trace_multi(lib().vx_octree_trace_multi, self.h, MultiHitArgs(), 2, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want)
 
     def trace_multi_device(self, rays_ptr, nrays, max_hits, t_ptr=None, prim_ptr=None, count_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None,
                            after_t_ptr=None, after_prim_ptr=None, camera=None):
         """vx_octree_trace_multi_device on raw device pointers, asynchronous on the octree's stream; t / prim hold max_hits entries per ray.
         camera = (view_inv, proj_inv, width, height) in place of rays_ptr / nrays."""
-        _trace_multi_device(lib().vx_octree_trace_multi_device, self.h, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax,
-                            tmax_per_ray_ptr, after_t_ptr, after_prim_ptr, camera)
+        _trace_multi_device(lib().vx_octree_trace_multi_device, self.h, MultiHitArgs(), rays_ptr, nrays, camera, max_hits, tmin, tmax, t=t_ptr,
+                            prim=prim_ptr, count=count_ptr, tmax_per_ray=tmax_per_ray_ptr, after_t=after_t_ptr, after_prim=after_prim_ptr)
 
     def free(self):
         if self.h:
@@ -1380,70 +1400,6 @@ class Octree:
             self.free()
         except Exception:
             pass
-
-
-def _mesh_trace_multi(fn, h, a, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want, tlas):
-    """vx_bvh_trace_multi / vx_tlas_trace_multi (a = the matching args structure) on host arrays -> dict of the requested outputs: t (n, K)
-    float32, prim and instance (n, K) uint32, bary (n, K, 2) float32, padded with -1 / 0xFFFFFFFF / (0, 0); count (n,) uint32."""
-    m = a.m
-    keep = []
-    if rays is not None:
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
-        keep.append(r)
-        m.base.rays, m.base.num_rays, n = r.ctypes.data, r.shape[0], r.shape[0]
-    else:
-        vi, pi, w, h_ = camera
-        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-        keep += [cvi, cpi]
-        m.base.view_inverse, m.base.proj_inverse, m.base.width, m.base.height, n = cvi, cpi, w, h_, w * h_
-    m.base.tmin, m.base.tmax, m.max_hits = np.float32(tmin), np.float32(tmax), int(max_hits)
-    if tmax_per_ray is not None:
-        tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
-        keep.append(tm)
-        m.base.tmax_per_ray = tm.ctypes.data
-    if after is not None:
-        if len(after) != (3 if tlas else 2):
-            raise ValueError("after = (after_t, after_instance, after_prim)" if tlas else "after = (after_t, after_prim)")
-        cur = [np.ascontiguousarray(after[0], dtype=np.float32)] + [np.ascontiguousarray(x, dtype=np.uint32) for x in after[1:]]
-        if any(c.shape != (n,) for c in cur):
-            raise ValueError("the cursor has one entry per ray in each of its arrays")
-        keep += cur
-        m.after_t, m.after_prim = cur[0].ctypes.data, cur[-1].ctypes.data
-        if tlas:
-            a.after_instance = cur[1].ctypes.data
-    k = max(int(max_hits), 0)
-    out = {}
-    if "t" in want:
-        out["t"] = np.zeros((n, k), np.float32); m.base.t = out["t"].ctypes.data
-    if "prim" in want:
-        out["prim"] = np.zeros((n, k), np.uint32); m.base.prim = out["prim"].ctypes.data
-    if "bary" in want:
-        out["bary"] = np.zeros((n, k, 2), np.float32); a.bary = out["bary"].ctypes.data
-    if "instance" in want:
-        if not tlas:
-            raise ValueError("instance is an output of the TLAS only")
-        out["instance"] = np.zeros((n, k), np.uint32); a.instance = out["instance"].ctypes.data
-    if "count" in want:
-        out["count"] = np.zeros(n, np.uint32); m.count = out["count"].ctypes.data
-    _check(fn(h, C.byref(a)))
-    return out
-
-
-def _mesh_trace_multi_device(fn, h, a, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax, tmax_per_ray_ptr, after_t_ptr,
-                             after_prim_ptr, camera):
-    """the device variants: raw device pointers (the caller has set a's own fields), asynchronous on the handle's stream"""
-    m = a.m
-    if camera is not None:
-        vi, pi, w, h_ = camera
-        cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-        cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-        m.base.view_inverse, m.base.proj_inverse, m.base.width, m.base.height = cvi, cpi, w, h_
-    else:
-        m.base.rays, m.base.num_rays = rays_ptr, nrays
-    m.base.tmin, m.base.tmax, m.base.tmax_per_ray, m.max_hits = np.float32(tmin), np.float32(tmax), tmax_per_ray_ptr, int(max_hits)
-    m.base.t, m.base.prim, m.count, m.after_t, m.after_prim = t_ptr, prim_ptr, count_ptr, after_t_ptr, after_prim_ptr
-    _check(fn(h, C.byref(a)))
 
 
 class Bvh:
@@ -1514,42 +1470,26 @@ class Bvh:
 
     def trace_ex(self, rays=None, camera=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, any_hit=False, want=("t", "prim")):
         """vx_bvh_trace_ex: host-buffer extended query -> dict of the requested outputs (t, prim, normal, shadowed, bary)."""
-        return _trace_ex(lib().vx_bvh_trace_ex, self.h, rays, camera, tmin, tmax, tmax_per_ray, any_hit, want, bvh=True)
+        return _trace_ex(lib().vx_bvh_trace_ex, self.h, BvhTraceArgs(), rays, camera, tmin, tmax, tmax_per_ray, any_hit, want)
 
     def trace_device(self, rays_ptr, nrays, t_ptr=None, prim_ptr=None, hits_ptr=None, nhits_ptr=None, tmin=0.001, tmax=10000.0,
                      normal_ptr=None, shadowed_ptr=None, tmax_per_ray_ptr=None, any_hit=False, camera=None, bary_ptr=None):
         """vx_bvh_trace_ex_device on device pointers; camera = (view_inv, proj_inv, W, H) instead of rays."""
-        ba = BvhTraceArgs()
-        a = ba.base
-        keep = []
-        if camera is not None:
-            vi, pi, w, h = camera
-            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-            keep += [cvi, cpi]
-            a.view_inverse, a.proj_inverse, a.width, a.height = cvi, cpi, w, h
-        else:
-            a.rays, a.num_rays = rays_ptr, nrays
-        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
-        a.tmax_per_ray, a.t, a.prim, a.normal, a.shadowed = tmax_per_ray_ptr, t_ptr, prim_ptr, normal_ptr, shadowed_ptr
-        a.hits, a.num_hits = hits_ptr, nhits_ptr
-        ba.bary = bary_ptr
-        _check(lib().vx_bvh_trace_ex_device(self.h, C.byref(ba)))
+        _trace_ex_device(lib().vx_bvh_trace_ex_device, self.h, BvhTraceArgs(), rays_ptr, nrays, camera, tmin, tmax, any_hit, t=t_ptr, prim=prim_ptr,
+                         normal=normal_ptr, shadowed=shadowed_ptr, tmax_per_ray=tmax_per_ray_ptr, hits=hits_ptr, num_hits=nhits_ptr, bary=bary_ptr)
 
     def trace_multi(self, rays=None, camera=None, max_hits=8, tmin=0.001, tmax=10000.0, tmax_per_ray=None, after=None, want=("t", "prim", "count")):
         """vx_bvh_trace_multi on host arrays: per ray the first max_hits accepted triangles in (t, prim) order and the number of all of them
         -> dict of the requested outputs (t, prim, bary, count).  after = (after_t, after_prim): per-ray cursor, only hits strictly behind it
         are listed and counted."""
-        return _mesh_trace_multi(lib().vx_bvh_trace_multi, self.h, BvhMultiHitArgs(), rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want, False)
+        return _trace_multi(lib().vx_bvh_trace_multi, self.h, BvhMultiHitArgs(), 2, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want)
 
     def trace_multi_device(self, rays_ptr, nrays, max_hits, t_ptr=None, prim_ptr=None, count_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None,
                            after_t_ptr=None, after_prim_ptr=None, camera=None, bary_ptr=None):
         """vx_bvh_trace_multi_device on raw device pointers, asynchronous on the BVH's stream; t / prim / bary hold max_hits entries per ray.
         camera = (view_inv, proj_inv, width, height) in place of rays_ptr / nrays."""
-        a = BvhMultiHitArgs()
-        a.bary = bary_ptr
-        _mesh_trace_multi_device(lib().vx_bvh_trace_multi_device, self.h, a, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax,
-                                 tmax_per_ray_ptr, after_t_ptr, after_prim_ptr, camera)
+        _trace_multi_device(lib().vx_bvh_trace_multi_device, self.h, BvhMultiHitArgs(), rays_ptr, nrays, camera, max_hits, tmin, tmax, t=t_ptr,
+                            prim=prim_ptr, count=count_ptr, tmax_per_ray=tmax_per_ray_ptr, after_t=after_t_ptr, after_prim=after_prim_ptr, bary=bary_ptr)
 
     def free(self):
         if self.h:
@@ -1647,65 +1587,27 @@ class Tlas:
     def trace_ex(self, rays=None, camera=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, any_hit=False,
                  want=("t", "instance", "prim", "bary", "normal")):
         """vx_tlas_trace_ex: host-buffer query -> dict of the requested outputs (t, instance, prim, bary, normal, shadowed)."""
-        ta = TlasTraceArgs()
-        a = ta.base
-        keep = []
-        if camera is not None:
-            vi, pi, w, h = camera
-            cvi = (C.c_float * 16)(*[float(x) for x in np.asarray(vi).reshape(16)])
-            cpi = (C.c_float * 16)(*[float(x) for x in np.asarray(pi).reshape(16)])
-            keep += [cvi, cpi]
-            a.view_inverse, a.proj_inverse, a.width, a.height = cvi, cpi, w, h
-            n = w * h
-        else:
-            r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
-            keep.append(r)
-            a.rays, a.num_rays = r.ctypes.data, r.shape[0]
-            n = r.shape[0]
-        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
-        if tmax_per_ray is not None:
-            tm = np.ascontiguousarray(tmax_per_ray, dtype=np.float32)
-            keep.append(tm)
-            a.tmax_per_ray = tm.ctypes.data
-        out = {}
-        shapes = {"t": ((n,), np.float32), "instance": ((n,), np.uint32), "prim": ((n,), np.uint32), "bary": ((n, 2), np.float32),
-                  "normal": ((n, 3), np.float32), "shadowed": ((n,), np.uint8)}
-        for k in want:
-            out[k] = np.zeros(*shapes[k])
-        if "t" in out: a.t = out["t"].ctypes.data
-        if "prim" in out: a.prim = out["prim"].ctypes.data
-        if "normal" in out: a.normal = out["normal"].ctypes.data
-        if "shadowed" in out: a.shadowed = out["shadowed"].ctypes.data
-        if "bary" in out: ta.bary = out["bary"].ctypes.data
-        if "instance" in out: ta.instance = out["instance"].ctypes.data
-        _check(lib().vx_tlas_trace_ex(self.h, C.byref(ta)))
-        return out
+        return _trace_ex(lib().vx_tlas_trace_ex, self.h, TlasTraceArgs(), rays if camera is None else None, camera, tmin, tmax, tmax_per_ray, any_hit, want)
 
     def trace_device(self, rays_ptr, nrays, t_ptr=None, prim_ptr=None, instance_ptr=None, bary_ptr=None, normal_ptr=None, shadowed_ptr=None,
                      hits_ptr=None, nhits_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None, any_hit=False):
         """vx_tlas_trace_ex_device on device pointers."""
-        ta = TlasTraceArgs()
-        a = ta.base
-        a.rays, a.num_rays = rays_ptr, nrays
-        a.tmin, a.tmax, a.any_hit = np.float32(tmin), np.float32(tmax), 1 if any_hit else 0
-        a.tmax_per_ray, a.t, a.prim, a.normal, a.shadowed = tmax_per_ray_ptr, t_ptr, prim_ptr, normal_ptr, shadowed_ptr
-        a.hits, a.num_hits = hits_ptr, nhits_ptr
-        ta.bary, ta.instance = bary_ptr, instance_ptr
-        _check(lib().vx_tlas_trace_ex_device(self.h, C.byref(ta)))
+        _trace_ex_device(lib().vx_tlas_trace_ex_device, self.h, TlasTraceArgs(), rays_ptr, nrays, None, tmin, tmax, any_hit, t=t_ptr, prim=prim_ptr,
+                         normal=normal_ptr, shadowed=shadowed_ptr, tmax_per_ray=tmax_per_ray_ptr, hits=hits_ptr, num_hits=nhits_ptr, bary=bary_ptr,
+                         instance=instance_ptr)
 
     def trace_multi(self, rays=None, camera=None, max_hits=8, tmin=0.001, tmax=10000.0, tmax_per_ray=None, after=None, want=("t", "instance", "prim", "count")):
         """vx_tlas_trace_multi on host arrays: per ray the first max_hits accepted (instance, triangle) pairs in (t, instance, prim) order and
         the number of all of them -> dict of the requested outputs (t, instance, prim, bary, count).  after = (after_t, after_instance,
         after_prim): per-ray cursor."""
-        return _mesh_trace_multi(lib().vx_tlas_trace_multi, self.h, TlasMultiHitArgs(), rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want, True)
+        return _trace_multi(lib().vx_tlas_trace_multi, self.h, TlasMultiHitArgs(), 3, rays, camera, max_hits, tmin, tmax, tmax_per_ray, after, want)
 
     def trace_multi_device(self, rays_ptr, nrays, max_hits, t_ptr=None, prim_ptr=None, count_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None,
                            after_t_ptr=None, after_prim_ptr=None, camera=None, bary_ptr=None, instance_ptr=None, after_instance_ptr=None):
         """vx_tlas_trace_multi_device on raw device pointers, asynchronous on the TLAS's stream."""
-        a = TlasMultiHitArgs()
-        a.bary, a.instance, a.after_instance = bary_ptr, instance_ptr, after_instance_ptr
-        _mesh_trace_multi_device(lib().vx_tlas_trace_multi_device, self.h, a, rays_ptr, nrays, max_hits, t_ptr, prim_ptr, count_ptr, tmin, tmax,
-                                 tmax_per_ray_ptr, after_t_ptr, after_prim_ptr, camera)
+        _trace_multi_device(lib().vx_tlas_trace_multi_device, self.h, TlasMultiHitArgs(), rays_ptr, nrays, camera, max_hits, tmin, tmax, t=t_ptr,
+                            prim=prim_ptr, count=count_ptr, tmax_per_ray=tmax_per_ray_ptr, after_t=after_t_ptr, after_prim=after_prim_ptr, bary=bary_ptr,
+                            instance=instance_ptr, after_instance=after_instance_ptr)
 
     def free(self):
         if self.h:

@@ -671,6 +671,46 @@ def test_primary_rays_with_normals(gpu):
     assert same.mean() > 0.999 and np.array_equal(out["normal"][same], ref["normal"][same])
 
 
+def test_trace_ex_device_equals_host(gpu):
+    """vx_trace_ex_device (no method of voxhip.Grid calls it) on the unit cube: rays and camera rays, closest hit with normals and the shadow
+    query with a per-ray tMax, each array identical to vx_trace_ex's."""
+    import ctypes as C
+    import torch
+    v, t = vx_scenes.cube(half=0.5)
+    g = gpu.Grid.voxelize(gpu.Mesh.from_arrays(v, t), np.float32(0.25))
+    rays = vx_scenes.random_rays(64, (-0.5,) * 3, (0.5,) * 3, seed=31)
+    vi, pi = vx_scenes.camera_matrices(eye=(1.0, 0.75, -1.25), ctr=(0.0, 0.0, 0.0), aspect=1.0)
+    cvi, cpi = (C.c_float * 16)(*[float(x) for x in vi]), (C.c_float * 16)(*[float(x) for x in pi])
+    dr = torch.from_numpy(rays).cuda()
+    for n, batch in ((64, dict(rays=rays)), (16, dict(camera=(vi, pi, 4, 4)))):
+        host = g.trace_ex(want=("t", "prim", "normal"), **batch)
+        assert (host["t"] > 0).any()
+        tm = np.where(host["t"] > 0, host["t"] * np.float32(0.75), np.float32(50.0)).astype(np.float32)   # every hit lies behind its tMax
+        tm[::2] = np.float32(50.0)
+        shadow = g.trace_ex(any_hit=True, tmax_per_ray=tm, want=("shadowed",), **batch)["shadowed"]
+        assert shadow.any() and not shadow.all()
+        dt = torch.full((n,), 7.0, dtype=torch.float32, device="cuda")
+        dp = torch.full((n,), 7, dtype=torch.int32, device="cuda")
+        dn = torch.full((n, 3), 7.0, dtype=torch.float32, device="cuda")
+        ds = torch.full((n,), 7, dtype=torch.uint8, device="cuda")
+        dtm = torch.from_numpy(tm).cuda()
+        a = gpu.TraceArgs()
+        if "rays" in batch:
+            a.rays, a.num_rays = dr.data_ptr(), n
+        else:
+            a.view_inverse, a.proj_inverse, a.width, a.height = cvi, cpi, 4, 4
+        a.tmin, a.tmax = np.float32(0.001), np.float32(10000.0)
+        a.t, a.prim, a.normal = dt.data_ptr(), dp.data_ptr(), dn.data_ptr()
+        torch.cuda.synchronize()
+        assert gpu.lib().vx_trace_ex_device(g.h, C.byref(a)) == 0
+        a.t = a.prim = a.normal = None
+        a.any_hit, a.tmax_per_ray, a.shadowed = 1, dtm.data_ptr(), ds.data_ptr()
+        assert gpu.lib().vx_trace_ex_device(g.h, C.byref(a)) == 0
+        torch.cuda.synchronize()
+        assert np.array_equal(dt.cpu().numpy(), host["t"]) and np.array_equal(dp.cpu().numpy().view(np.uint32), host["prim"])
+        assert np.array_equal(dn.cpu().numpy(), host["normal"]) and np.array_equal(ds.cpu().numpy(), shadow)
+
+
 def test_c4_atrium_1024_eight_shards(gpu):
     """BASELINE configs[3] on one device: the atrium at exactly 1024^3, voxelized as 8 word-aligned shards (what the 8 ranks
     of a node do) -- shards are word-disjoint, their union equals the unsharded mask, and that mask equals the oracle's."""
