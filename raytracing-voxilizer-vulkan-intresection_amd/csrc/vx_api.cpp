@@ -2803,78 +2803,8 @@ static vx_status surface_check(uint64_t nv, uint64_t nt, uint64_t vcap, uint64_t
     return VX_OK;
 }
 
-static vx_status surface_run(vx_grid* g, bool host, float* xyz, uint64_t vcap, int32_t* tri, uint64_t tcap, int32_t* mat, uint64_t* num_vertices,
-                             uint64_t* num_triangles)
-{
-    if ((vcap || tcap) && (!xyz || !tri)) return fail(VX_ERR_INVALID_ARG, "null argument");
-    DeviceGuard dg(g->device);
-    uint64_t nv = 0, nt = 0;
-    const int16_t* ids = nullptr;
-    VX_TRY(surface_count(g, mat != nullptr, &nv, &nt, &ids));
-    if (num_vertices) *num_vertices = nv;
-    if (num_triangles) *num_triangles = nt;
-    VX_TRY(surface_check(nv, nt, vcap, tcap));
-    if ((!vcap && !tcap) || (!nv && !nt)) return VX_OK;
-    const vx::SurfacePlan p = vx::surface_plan(g->g);
-    float* dx = xyz;
-    int32_t* dt = tri;
-    int32_t* dm = mat;
-    if (host) {  // one staging block: positions, triangles, ids
-        VX_HIP(g->surf_out.ensure((size_t)nv * 12 + (size_t)nt * 12 + (mat ? (size_t)nt * 4 : 0) + 16));
-        dx = g->surf_out.as<float>();
-        dt = reinterpret_cast<int32_t*>(dx + 3 * nv);
-        dm = mat ? dt + 3 * nt : nullptr;
-    }
-    vx::launch_surface_emit(g->words.as<uint32_t>(), g->g, p, g->surf_tpre.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(),
-                            mat ? g->wprefix.as<uint32_t>() : nullptr, ids, dx, dt, dm, g->stream);
-    VX_HIP(hipGetLastError());
-    if (host) {
-        VX_HIP(hipMemcpyAsync(xyz, dx, (size_t)nv * 12, hipMemcpyDeviceToHost, g->stream));
-        VX_HIP(hipMemcpyAsync(tri, dt, (size_t)nt * 12, hipMemcpyDeviceToHost, g->stream));
-        if (mat) VX_HIP(hipMemcpyAsync(mat, dm, (size_t)nt * 4, hipMemcpyDeviceToHost, g->stream));
-        VX_HIP(hipStreamSynchronize(g->stream));
-    }
-    return VX_OK;
-}
-
-vx_status vx_grid_surface_device(const vx_grid* gc, float* dev_xyz, uint64_t vertex_capacity, int32_t* dev_tri, uint64_t triangle_capacity,
-                                 int32_t* dev_mat, uint64_t* num_vertices, uint64_t* num_triangles)
-{
-    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    return surface_run(const_cast<vx_grid*>(gc), false, dev_xyz, vertex_capacity, dev_tri, triangle_capacity, dev_mat, num_vertices, num_triangles);
-}
-
-vx_status vx_grid_surface(const vx_grid* gc, float* host_xyz, uint64_t vertex_capacity, int32_t* host_tri, uint64_t triangle_capacity,
-                          int32_t* host_mat, uint64_t* num_vertices, uint64_t* num_triangles)
-{
-    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    return surface_run(const_cast<vx_grid*>(gc), true, host_xyz, vertex_capacity, host_tri, triangle_capacity, host_mat, num_vertices, num_triangles);
-}
-
-vx_status vx_grid_surface_mesh(const vx_grid* gc, int with_materials, vx_mesh** out)
-{
-    if (!gc || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    if (with_materials) {
-        const int16_t* ids = nullptr;
-        VX_TRY(surface_materials(gc, &ids));
-    }
-    uint64_t nv = 0, nt = 0;
-    VX_TRY(vx_grid_surface(gc, nullptr, 0, nullptr, 0, nullptr, &nv, &nt));
-    std::vector<float> xyz((size_t)nv * 3 + 1);
-    std::vector<int32_t> tri((size_t)nt * 3 + 1), mat(with_materials ? (size_t)nt + 1 : 0);
-    if (nv || nt) VX_TRY(vx_grid_surface(gc, xyz.data(), nv, tri.data(), nt, with_materials ? mat.data() : nullptr, &nv, &nt));
-    vx_mesh* m = nullptr;
-    VX_TRY(vx_mesh_from_arrays(xyz.data(), (size_t)nv, tri.data(), (size_t)nt, &m));
-    if (with_materials) {
-        const vx_status st = vx_mesh_set_materials(m, gc->materials.data(), gc->materials.size(), mat.data());
-        if (st != VX_OK) { vx_mesh_free(m); return st; }
-    }
-    *out = m;
-    return VX_OK;
-}
-
-// Surface nets: vx_grid_surface's count, scans, wait and triangles; the positions from the relaxation instead of k_surf_verts, and
-// optionally the vertex normals (vx_surface.hip).  Everything after the wait for V and T is queued back to back.
+// Surface nets (sp != null): vx_grid_surface's count, scans, wait and triangles; the positions from the relaxation instead of k_surf_verts,
+// and optionally the vertex normals (vx_surface.hip).  Everything after the wait for V and T is queued back to back.
 static vx_status smooth_params(const vx_smooth* sp)
 {
     if (!sp) return fail(VX_ERR_INVALID_ARG, "null argument");
@@ -2884,10 +2814,10 @@ static vx_status smooth_params(const vx_smooth* sp)
     return VX_OK;
 }
 
-static vx_status smooth_run(vx_grid* g, const vx_smooth* sp, bool host, float* xyz, uint64_t vcap, int32_t* tri, uint64_t tcap, int32_t* mat,
-                            float* normals, uint64_t* num_vertices, uint64_t* num_triangles)
+// sp null: the faces' mesh (normals null).  sp non-null: the surface nets, sp already through smooth_params.
+static vx_status surface_run(vx_grid* g, const vx_smooth* sp, bool host, float* xyz, uint64_t vcap, int32_t* tri, uint64_t tcap, int32_t* mat,
+                             float* normals, uint64_t* num_vertices, uint64_t* num_triangles)
 {
-    VX_TRY(smooth_params(sp));
     if ((vcap || tcap) && (!xyz || !tri)) return fail(VX_ERR_INVALID_ARG, "null argument");
     DeviceGuard dg(g->device);
     uint64_t nv = 0, nt = 0;
@@ -2909,14 +2839,20 @@ static vx_status smooth_run(vx_grid* g, const vx_smooth* sp, bool host, float* x
         dt = reinterpret_cast<int32_t*>(dx + (normals ? 6 : 3) * nv);
         dm = mat ? dt + 3 * nt : nullptr;
     }
-    vx::NetsBufs nb;
-    VX_HIP(g->nets_buf.ensure(vx::nets_bytes(nv, nullptr)));
-    nb.base = g->nets_buf.p;
-    vx::nets_bytes(nv, &nb);
-    vx::launch_surface_nets(g->words.as<uint32_t>(), g->g, p, g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(), nv, nb, sp->iterations,
-                            sp->lambda, sp->mu, dx, dn, g->stream);
-    vx::launch_surface_tris(g->words.as<uint32_t>(), g->g, g->surf_tpre.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(),
-                            mat ? g->wprefix.as<uint32_t>() : nullptr, ids, dt, dm, g->stream);
+    const uint32_t* wprefix = mat ? g->wprefix.as<uint32_t>() : nullptr;
+    if (sp) {
+        vx::NetsBufs nb;
+        VX_HIP(g->nets_buf.ensure(vx::nets_bytes(nv, nullptr)));
+        nb.base = g->nets_buf.p;
+        vx::nets_bytes(nv, &nb);
+        vx::launch_surface_nets(g->words.as<uint32_t>(), g->g, p, g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(), nv, nb, sp->iterations,
+                                sp->lambda, sp->mu, dx, dn, g->stream);
+        vx::launch_surface_tris(g->words.as<uint32_t>(), g->g, g->surf_tpre.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(),
+                                wprefix, ids, dt, dm, g->stream);
+    } else {
+        vx::launch_surface_emit(g->words.as<uint32_t>(), g->g, p, g->surf_tpre.as<uint32_t>(), g->surf_cm.as<uint32_t>(),
+                                g->surf_vpre.as<uint32_t>(), wprefix, ids, dx, dt, dm, g->stream);
+    }
     VX_HIP(hipGetLastError());
     if (host) {
         VX_HIP(hipMemcpyAsync(xyz, dx, (size_t)nv * 12, hipMemcpyDeviceToHost, g->stream));
@@ -2928,13 +2864,30 @@ static vx_status smooth_run(vx_grid* g, const vx_smooth* sp, bool host, float* x
     return VX_OK;
 }
 
+vx_status vx_grid_surface_device(const vx_grid* gc, float* dev_xyz, uint64_t vertex_capacity, int32_t* dev_tri, uint64_t triangle_capacity,
+                                 int32_t* dev_mat, uint64_t* num_vertices, uint64_t* num_triangles)
+{
+    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return surface_run(const_cast<vx_grid*>(gc), nullptr, false, dev_xyz, vertex_capacity, dev_tri, triangle_capacity, dev_mat, nullptr,
+                       num_vertices, num_triangles);
+}
+
+vx_status vx_grid_surface(const vx_grid* gc, float* host_xyz, uint64_t vertex_capacity, int32_t* host_tri, uint64_t triangle_capacity,
+                          int32_t* host_mat, uint64_t* num_vertices, uint64_t* num_triangles)
+{
+    if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return surface_run(const_cast<vx_grid*>(gc), nullptr, true, host_xyz, vertex_capacity, host_tri, triangle_capacity, host_mat, nullptr,
+                       num_vertices, num_triangles);
+}
+
 vx_status vx_grid_surface_smooth_device(const vx_grid* gc, const vx_smooth* params, float* dev_xyz, uint64_t vertex_capacity, int32_t* dev_tri,
                                         uint64_t triangle_capacity, int32_t* dev_mat, float* dev_normals, uint64_t* num_vertices,
                                         uint64_t* num_triangles)
 {
     if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    return smooth_run(const_cast<vx_grid*>(gc), params, false, dev_xyz, vertex_capacity, dev_tri, triangle_capacity, dev_mat, dev_normals,
-                      num_vertices, num_triangles);
+    VX_TRY(smooth_params(params));
+    return surface_run(const_cast<vx_grid*>(gc), params, false, dev_xyz, vertex_capacity, dev_tri, triangle_capacity, dev_mat, dev_normals,
+                       num_vertices, num_triangles);
 }
 
 vx_status vx_grid_surface_smooth(const vx_grid* gc, const vx_smooth* params, float* host_xyz, uint64_t vertex_capacity, int32_t* host_tri,
@@ -2942,14 +2895,14 @@ vx_status vx_grid_surface_smooth(const vx_grid* gc, const vx_smooth* params, flo
                                  uint64_t* num_triangles)
 {
     if (!gc) return fail(VX_ERR_INVALID_ARG, "null argument");
-    return smooth_run(const_cast<vx_grid*>(gc), params, true, host_xyz, vertex_capacity, host_tri, triangle_capacity, host_mat, host_normals,
-                      num_vertices, num_triangles);
+    VX_TRY(smooth_params(params));
+    return surface_run(const_cast<vx_grid*>(gc), params, true, host_xyz, vertex_capacity, host_tri, triangle_capacity, host_mat, host_normals,
+                       num_vertices, num_triangles);
 }
 
-vx_status vx_grid_surface_smooth_mesh(const vx_grid* gc, const vx_smooth* params, int with_materials, int with_normals, vx_mesh** out)
+// The mesh of either surface as a vx_mesh (sp as for surface_run, already checked): the size query is vx_grid_surface's for both.
+static vx_status surface_mesh(const vx_grid* gc, const vx_smooth* sp, int with_materials, int with_normals, vx_mesh** out)
 {
-    if (!gc || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
-    VX_TRY(smooth_params(params));
     if (with_materials) {
         const int16_t* ids = nullptr;
         VX_TRY(surface_materials(gc, &ids));
@@ -2959,8 +2912,8 @@ vx_status vx_grid_surface_smooth_mesh(const vx_grid* gc, const vx_smooth* params
     std::vector<float> xyz((size_t)nv * 3 + 1), nrm(with_normals ? (size_t)nv * 3 + 1 : 0);
     std::vector<int32_t> tri((size_t)nt * 3 + 1), mat(with_materials ? (size_t)nt + 1 : 0);
     if (nv || nt)
-        VX_TRY(vx_grid_surface_smooth(gc, params, xyz.data(), nv, tri.data(), nt, with_materials ? mat.data() : nullptr,
-                                      with_normals ? nrm.data() : nullptr, &nv, &nt));
+        VX_TRY(surface_run(const_cast<vx_grid*>(gc), sp, true, xyz.data(), nv, tri.data(), nt, with_materials ? mat.data() : nullptr,
+                           with_normals ? nrm.data() : nullptr, &nv, &nt));
     vx_mesh* m = nullptr;
     VX_TRY(vx_mesh_from_arrays(xyz.data(), (size_t)nv, tri.data(), (size_t)nt, &m));
     vx_status st = VX_OK;
@@ -2974,6 +2927,19 @@ vx_status vx_grid_surface_smooth_mesh(const vx_grid* gc, const vx_smooth* params
     if (st != VX_OK) { vx_mesh_free(m); return st; }
     *out = m;
     return VX_OK;
+}
+
+vx_status vx_grid_surface_mesh(const vx_grid* gc, int with_materials, vx_mesh** out)
+{
+    if (!gc || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    return surface_mesh(gc, nullptr, with_materials, 0, out);
+}
+
+vx_status vx_grid_surface_smooth_mesh(const vx_grid* gc, const vx_smooth* params, int with_materials, int with_normals, vx_mesh** out)
+{
+    if (!gc || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    VX_TRY(smooth_params(params));
+    return surface_mesh(gc, params, with_materials, with_normals, out);
 }
 
 // Connected components: the argument checks in the header's order, then the labelling passes and one scan on the grid's stream

@@ -25,6 +25,7 @@
 // are not coherent with each other); no workgroup ever waits for another (a CAS fails only because another lane's link made progress).
 // A read that is out of date still names an ancestor (an older parent), so finds stay correct and every decision is taken by the CAS.
 #include "vx_internal.h"
+#include "vx_mask.h"
 
 namespace vx {
 
@@ -35,31 +36,18 @@ constexpr uint32_t kRows = kBY * kBZ;     // 256 lanes
 constexpr uint32_t kCells = 32u * kRows;  // 8192 cells, 32 KiB of LDS parents
 constexpr unsigned kCellBlocks = 256 * 32;
 
-inline unsigned cell_grid(uint64_t n)
-{
-    uint64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > kCellBlocks) b = kCellBlocks;
-    return (unsigned)b;
-}
-
 struct CcDims {
     uint32_t X, Y, Z, nbx, nby;
     uint64_t n, nwords;
 };
 
-// cells x0 .. x0 + 31 of the row whose first cell is bit `rowbit`, masked to x < X (the mask has two spare words past nwords; bits past a
+// cells x0 .. x0 + 31 (x0 % 32 == 0: bricks are word-aligned in x) of the row whose first cell is bit `rowbit`, masked to x < X (bits past a
 // row, or past the last cell, are never trusted)
 __device__ __forceinline__ uint32_t row_bits(const uint32_t* __restrict__ words, uint64_t rowbit, uint32_t X, uint32_t x0)
 {
-    const uint64_t s = rowbit + x0;
-    const uint64_t two = (uint64_t)words[s >> 5] | ((uint64_t)words[(s >> 5) + 1] << 32);
-    const uint32_t nb = X - x0 < 32u ? X - x0 : 32u;
-    const uint32_t valid = nb == 32u ? ~0u : ((1u << nb) - 1u);
-    return (uint32_t)(two >> (s & 31u)) & valid;
+    uint32_t valid;
+    return row_word(words, rowbit, X, x0 >> 5, valid) & valid;
 }
-
-__device__ __forceinline__ uint32_t cell_bit(const uint32_t* __restrict__ words, uint64_t i) { return (words[i >> 5] >> (i & 31u)) & 1u; }
 
 // ---- union-find, in LDS (SCOPE = workgroup) or in global memory (SCOPE = agent) ---------------------------------------------------
 constexpr int kLds = __HIP_MEMORY_SCOPE_WORKGROUP;
@@ -167,11 +155,11 @@ __global__ __launch_bounds__(256) void k_cc_merge(const uint32_t* __restrict__ w
         const uint64_t c0 = (uint64_t)d.X * yz + x0;  // the row's cell x0
         const uint32_t m = row_bits(words, c0 - x0, d.X, x0);
         if (!m) continue;
-        const uint32_t self_l = x0 ? cell_bit(words, c0 - 1u) : 0u;                // this row's cell x0 - 1
-        const uint32_t self_r = x0 + 32u < d.X ? cell_bit(words, c0 + 32u) : 0u;  // and x0 + 32
+        const uint32_t self_l = x0 ? mask_bit(words, c0 - 1u) : 0u;                // this row's cell x0 - 1
+        const uint32_t self_r = x0 + 32u < d.X ? mask_bit(words, c0 + 32u) : 0u;  // and x0 + 32
         // (-1, 0, 0) across the x border; implied when the row below in y, inside the brick, has both cells (then the join of that row,
         // and the dx = 0 joins of both bricks, connect these two)
-        if ((m & 1u) && self_l && !(y % kBY && cell_bit(words, c0 - d.X) && cell_bit(words, c0 - d.X - 1u)))
+        if ((m & 1u) && self_l && !(y % kBY && mask_bit(words, c0 - d.X) && mask_bit(words, c0 - d.X - 1u)))
             uf_unite<kAgent>(par, (uint32_t)c0, (uint32_t)(c0 - 1u));
         constexpr int nrows = CONN == 6 ? 2 : 4;
         for (int q = 0; q < nrows; ++q) {
@@ -190,8 +178,8 @@ __global__ __launch_bounds__(256) void k_cc_merge(const uint32_t* __restrict__ w
                 }
                 continue;
             }
-            const uint32_t left = x0 ? cell_bit(words, n0 - 1u) : 0u;                // the partner row's cell x0 - 1
-            const uint32_t right = x0 + 32u < d.X ? cell_bit(words, n0 + 32u) : 0u;  // and x0 + 32
+            const uint32_t left = x0 ? mask_bit(words, n0 - 1u) : 0u;                // the partner row's cell x0 - 1
+            const uint32_t right = x0 + 32u < d.X ? mask_bit(words, n0 + 32u) : 0u;  // and x0 + 32
             const uint32_t r = row_bits(words, n0 - x0, d.X, x0);
             if (!cross) {  // a row of the same brick: only the x offsets past the brick's 32 cells, unless implied as in k_cc_local
                 if ((m & 1u) && left && !(r & 1u) && !self_l) uf_unite<kAgent>(par, (uint32_t)c0, (uint32_t)(n0 - 1u));
@@ -277,7 +265,7 @@ __global__ __launch_bounds__(256) void k_cc_label(const uint32_t* __restrict__ w
         return;
     }
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-        par[i] = cell_bit(words, i) ? rank_label(roots, rpre, par[i]) : 0u;
+        par[i] = mask_bit(words, i) ? rank_label(roots, rpre, par[i]) : 0u;
 }
 
 // rec: 8 words per component (vx_component: cells as two words, min[3], max[3])
@@ -352,27 +340,27 @@ void launch_components(const uint32_t* words, const GridParams& g, bool conn26, 
     const uint64_t nrow = (uint64_t)d.nbx * d.Y * d.Z;
     if (conn26) {
         VX_KL(k_cc_local<26>, dim3((unsigned)nbricks), dim3(256), 0, s, words, d, labels);
-        VX_KL(k_cc_merge<26>, dim3(cell_grid(nrow)), dim3(256), 0, s, words, d, labels);
+        VX_KL(k_cc_merge<26>, dim3(blocks_for(nrow, kCellBlocks)), dim3(256), 0, s, words, d, labels);
     } else {
         VX_KL(k_cc_local<6>, dim3((unsigned)nbricks), dim3(256), 0, s, words, d, labels);
-        VX_KL(k_cc_merge<6>, dim3(cell_grid(nrow)), dim3(256), 0, s, words, d, labels);
+        VX_KL(k_cc_merge<6>, dim3(blocks_for(nrow, kCellBlocks)), dim3(256), 0, s, words, d, labels);
     }
-    VX_KL(k_cc_flatten, dim3(cell_grid(d.nwords)), dim3(256), 0, s, words, d.n, d.nwords, labels, roots);  // (one lane per word)
+    VX_KL(k_cc_flatten, dim3(blocks_for(d.nwords, kCellBlocks)), dim3(256), 0, s, words, d.n, d.nwords, labels, roots);  // (one lane per word)
 }
 
 void launch_components_label(const uint32_t* words, const GridParams& g, uint32_t* labels, const uint32_t* roots, const uint32_t* rpre,
                              uint32_t* dev_count, hipStream_t s)
 {
     if (g.nvox % 4u == 0u && (reinterpret_cast<uintptr_t>(labels) & 15u) == 0u)
-        VX_KL(k_cc_label<true>, dim3(cell_grid(g.nvox / 4u)), dim3(256), 0, s, words, g.nvox, g.nwords, labels, roots, rpre, dev_count);
+        VX_KL(k_cc_label<true>, dim3(blocks_for(g.nvox / 4u, kCellBlocks)), dim3(256), 0, s, words, g.nvox, g.nwords, labels, roots, rpre, dev_count);
     else
-        VX_KL(k_cc_label<false>, dim3(cell_grid(g.nvox)), dim3(256), 0, s, words, g.nvox, g.nwords, labels, roots, rpre, dev_count);
+        VX_KL(k_cc_label<false>, dim3(blocks_for(g.nvox, kCellBlocks)), dim3(256), 0, s, words, g.nvox, g.nwords, labels, roots, rpre, dev_count);
 }
 
 void launch_component_stats(const uint32_t* labels, const GridParams& g, uint64_t k, uint32_t* rec, hipStream_t s)
 {
-    VX_KL(k_cc_stats_init, dim3(cell_grid(k * 8u)), dim3(256), 0, s, rec, k);
-    VX_KL(k_cc_stats, dim3(cell_grid(g.nvox)), dim3(256), 0, s, labels, cc_dims(g), rec);
+    VX_KL(k_cc_stats_init, dim3(blocks_for(k * 8u, kCellBlocks)), dim3(256), 0, s, rec, k);
+    VX_KL(k_cc_stats, dim3(blocks_for(g.nvox, kCellBlocks)), dim3(256), 0, s, labels, cc_dims(g), rec);
 }
 
 }  // namespace vx

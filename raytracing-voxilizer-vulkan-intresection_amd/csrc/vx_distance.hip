@@ -16,9 +16,11 @@
 // (D_in on M, D_out off M) in the one 32-bit intermediate -- the other transform is 0 there, known from the mask -- and the column passes run
 // both envelopes over the one buffer, g_out(u) = m(u) ? 0 : v(u), g_in(u) = m(u) ? v(u) : 0.  The z pass of SIGNED converts to f32 in place.
 //
-// The feature transform (vx_grid_nearest*: the INDEX of the nearest target, smallest index on ties) runs the same passes with kernels of its
-// own, k_near_x and k_near_col, below the distance kernels.
+// The feature transform (vx_grid_nearest*: the INDEX of the nearest target, smallest index on ties) runs the same passes and carries WHICH
+// target wins instead of how far it is: k_near_x and k_near_col are the same row sweep and the same envelope with another expression per cell
+// and another second word in the stack entry (NearCell, FeatureWord).
 #include "vx_internal.h"
+#include "vx_mask.h"
 
 #pragma clang fp contract(off)
 
@@ -27,30 +29,12 @@ namespace vx {
 namespace {
 
 constexpr uint32_t kInf = 0xFFFFFFFFu;  // no target in reach (the contract's sentinel)
-constexpr uint32_t kNone = 0xFFFFFFFFu; // no target position
+constexpr uint32_t kNone = 0xFFFFFFFFu; // no target position, no feature
 constexpr unsigned kDistBlocks = 256 * 8;
-
-inline unsigned dist_grid(uint64_t n)
-{
-    uint64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > kDistBlocks) b = kDistBlocks;
-    return (unsigned)b;
-}
 
 enum : int { kOut = 0, kIn = 1, kSigned = 2 };
 
-// word w of the row whose first cell is bit `rowbit` of the mask: cells x = 32 w .. 32 w + 31, `valid` marks those with x < X (the mask has
-// two spare words past nwords, so the second word of the window always exists)
-__device__ __forceinline__ uint32_t row_word(const uint32_t* __restrict__ words, uint64_t rowbit, uint32_t X, uint32_t w, uint32_t& valid)
-{
-    const uint64_t s = rowbit + 32ull * w;
-    const uint64_t two = (uint64_t)words[s >> 5] | ((uint64_t)words[(s >> 5) + 1] << 32);
-    const uint32_t nb = X - 32u * w < 32u ? X - 32u * w : 32u;
-    valid = nb == 32u ? ~0u : ((1u << nb) - 1u);
-    return (uint32_t)(two >> (s & 31u));
-}
-
+// ---- x pass: the row sweep ---------------------------------------------------------------------------------------------------------------
 // The nearest target of a row at or after word w + 1: `lw` the word it lies in (W: none), `pos` its cell.  Moves forward only.
 struct Ahead {
     uint32_t lw, pos;
@@ -78,8 +62,45 @@ __device__ __forceinline__ uint32_t row_dist(uint32_t t, uint32_t i, uint32_t x,
     return d == kInf ? kInf : d * d;  // d <= 65535: d^2 < 2^32 - 1
 }
 
-template <int MODE, bool VEC4>
-__global__ __launch_bounds__(256) void k_dist_x(const uint32_t* __restrict__ words, uint32_t* __restrict__ out, uint32_t X, uint64_t rows)
+// position along the row of the nearest target of cell x (bit i of word w), the left one on a tie; kNone: the row has none
+__device__ __forceinline__ uint32_t row_near(uint32_t t, uint32_t i, uint32_t x, uint32_t prev, uint32_t next)
+{
+    const uint32_t lo = t & ((2u << i) - 1u);
+    const uint32_t hi = t >> i;
+    const uint32_t pl = lo ? x - i + (31u - (uint32_t)__builtin_clz(lo)) : prev;
+    const uint32_t pr = hi ? x + (uint32_t)__builtin_ctz(hi) : next;
+    const uint32_t dl = pl != kNone ? x - pl : kInf;
+    const uint32_t dr = pr != kNone ? pr - x : kInf;
+    return dl <= dr ? pl : pr;
+}
+
+// What the sweep writes per cell: which target kinds it follows (kOcc, kEmp), and the value of cell x = bit i of the word m from the word's
+// occupied and empty targets to / te, the last target of either kind before the word (po, pe) and the first after it (no, ne).
+template <int MODE>
+struct DistCell {  // dx^2, or the sentinel when the row has no target; SIGNED: to the empty cells on M, to the occupied ones off M
+    static constexpr bool kOcc = MODE != kIn, kEmp = MODE != kOut;
+    static __device__ __forceinline__ uint32_t at(uint32_t m, uint32_t i, uint32_t x, uint32_t to, uint32_t te, uint32_t po, uint32_t pe,
+                                                  uint32_t no, uint32_t ne)
+    {
+        if (MODE == kOut) return row_dist(to, i, x, po, no);
+        if (MODE == kIn) return row_dist(te, i, x, pe, ne);
+        return (m >> i) & 1u ? row_dist(te, i, x, pe, ne) : row_dist(to, i, x, po, no);
+    }
+};
+template <bool OCC>
+struct NearCell {  // x' of the nearest target
+    static constexpr bool kOcc = OCC, kEmp = !OCC;
+    static __device__ __forceinline__ uint32_t at(uint32_t, uint32_t i, uint32_t x, uint32_t to, uint32_t te, uint32_t po, uint32_t pe,
+                                                  uint32_t no, uint32_t ne)
+    {
+        return OCC ? row_near(to, i, x, po, no) : row_near(te, i, x, pe, ne);
+    }
+};
+
+// One row (y, z) per thread.  VEC4: X % 4 == 0 and `out` is 16-byte aligned, so rows start on 16-byte boundaries.
+// (The state stays in plain locals: packed into one struct per target kind, k_near_x came out 3-6 % slower)
+template <class CELL, bool VEC4>
+__device__ __forceinline__ void row_sweep(const uint32_t* __restrict__ words, uint32_t* __restrict__ out, uint32_t X, uint64_t rows)
 {
     const uint32_t W = (X + 31u) / 32u;
     for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < rows; r += (uint64_t)gridDim.x * 256u) {
@@ -87,24 +108,19 @@ __global__ __launch_bounds__(256) void k_dist_x(const uint32_t* __restrict__ wor
         uint32_t* o = out + rowbit;
         uint32_t prev_occ = kNone, prev_emp = kNone;  // last target of the words before
         Ahead ao{0u, kNone}, ae{0u, kNone};           // first target of the words after
-        if (MODE != kIn) ahead_from<true>(ao, words, rowbit, X, W, 1u);
-        if (MODE != kOut) ahead_from<false>(ae, words, rowbit, X, W, 1u);
+        if (CELL::kOcc) ahead_from<true>(ao, words, rowbit, X, W, 1u);
+        if (CELL::kEmp) ahead_from<false>(ae, words, rowbit, X, W, 1u);
         for (uint32_t w = 0; w < W; ++w) {
-            if (MODE != kIn && ao.lw == w) ahead_from<true>(ao, words, rowbit, X, W, w + 1u);
-            if (MODE != kOut && ae.lw == w) ahead_from<false>(ae, words, rowbit, X, W, w + 1u);
+            if (CELL::kOcc && ao.lw == w) ahead_from<true>(ao, words, rowbit, X, W, w + 1u);
+            if (CELL::kEmp && ae.lw == w) ahead_from<false>(ae, words, rowbit, X, W, w + 1u);
             uint32_t valid;
             const uint32_t m = row_word(words, rowbit, X, w, valid);
             const uint32_t to = m & valid, te = ~m & valid;  // padding bits are neither occupied nor empty
             const uint32_t nb = (uint32_t)__builtin_popcount(valid);
             uint32_t v[32];
 #pragma unroll
-            for (uint32_t i = 0; i < 32u; ++i) {
-                const uint32_t x = 32u * w + i;
-                if (MODE == kOut) v[i] = row_dist(to, i, x, prev_occ, ao.pos);
-                else if (MODE == kIn) v[i] = row_dist(te, i, x, prev_emp, ae.pos);
-                else v[i] = (m >> i) & 1u ? row_dist(te, i, x, prev_emp, ae.pos) : row_dist(to, i, x, prev_occ, ao.pos);
-            }
-            if (VEC4) {  // X % 4 == 0: the row and nb are multiples of four cells
+            for (uint32_t i = 0; i < 32u; ++i) v[i] = CELL::at(m, i, 32u * w + i, to, te, prev_occ, prev_emp, ao.pos, ae.pos);
+            if (VEC4) {  // the row and nb are multiples of four cells
 #pragma unroll
                 for (uint32_t i = 0; i < 32u; i += 4u)
                     if (i < nb) *reinterpret_cast<uint4*>(o + 32u * w + i) = make_uint4(v[i], v[i + 1], v[i + 2], v[i + 3]);
@@ -113,42 +129,93 @@ __global__ __launch_bounds__(256) void k_dist_x(const uint32_t* __restrict__ wor
                 for (uint32_t i = 0; i < 32u; ++i)
                     if (i < nb) o[32u * w + i] = v[i];
             }
-            if (to) prev_occ = 32u * w + 31u - (uint32_t)__builtin_clz(to);
-            if (te) prev_emp = 32u * w + 31u - (uint32_t)__builtin_clz(te);
+            if (CELL::kOcc && to) prev_occ = 32u * w + 31u - (uint32_t)__builtin_clz(to);
+            if (CELL::kEmp && te) prev_emp = 32u * w + 31u - (uint32_t)__builtin_clz(te);
         }
     }
 }
 
+template <int MODE, bool VEC4>
+__global__ __launch_bounds__(256) void k_dist_x(const uint32_t* __restrict__ words, uint32_t* __restrict__ out, uint32_t X, uint64_t rows)
+{
+    row_sweep<DistCell<MODE>, VEC4>(words, out, X, rows);
+}
+
+template <bool OCC, bool VEC4>
+__global__ __launch_bounds__(256) void k_near_x(const uint32_t* __restrict__ words, uint32_t* __restrict__ out, uint32_t X, uint64_t rows)
+{
+    row_sweep<NearCell<OCC>, VEC4>(words, out, X, rows);
+}
+
+// ---- y and z passes: the envelope --------------------------------------------------------------------------------------------------------
+// What the second word of a stack entry is: how g(s) comes out of it, and what the pass writes to a cell u where s wins with the value d.
+// The distance fields keep g itself and write d.  The feature transform keeps the packed feature x' | y' << 16 of the cell's nearest target
+// so far, the one 32-bit intermediate it has per cell, and recomputes g from it and the column's own position on every load: (x - x')^2
+// after the x pass, (x - x')^2 + (y - y')^2 after the y pass (y pass: f >> 16 == 0).  It writes the feature extended by s.
+// x' | y' << 16 == kNone would need X = Y = 65536, which the distance fields' limit excludes.
+struct DistWord {
+    __device__ __forceinline__ uint32_t g(uint32_t word) const { return word; }
+    __device__ __forceinline__ uint32_t result(uint32_t, uint32_t, uint32_t d) const { return d; }
+};
+template <bool ZPASS>
+struct FeatureWord {
+    uint32_t x, y, X, Y;  // the column's position, the grid's size
+    __device__ __forceinline__ uint32_t g(uint32_t f) const
+    {
+        const uint32_t dx = x - (f & 0xFFFFu);  // (the square of a wrapped difference is the square of the difference: below 2^32)
+        uint32_t g = dx * dx;
+        if (ZPASS) {
+            const uint32_t dy = y - (f >> 16);
+            g += dy * dy;
+        }
+        return g;
+    }
+    // y pass: x' | y' << 16 with y' = s.  z pass: the cell index x' + X (y' + Y z') with z' = s.
+    // (the value d is not used: env_take computes it for every policy, and the compiler drops it here)
+    __device__ __forceinline__ uint32_t result(uint32_t s, uint32_t f, uint32_t) const
+    {
+        return ZPASS ? (f & 0xFFFFu) + X * ((f >> 16) + Y * s) : f | (s << 16);
+    }
+};
+
 // One lower envelope of a column (Meijster): entries k = 0..q, parabola s_k with value g_k, winning from t_k on; the top in registers,
-// every entry also at stk[k * ld] (s | t << 16, g) -- s, t < 65536.
+// every entry also at stk[k * ld] (s | t << 16, word) -- s, t < 65536.  g(s) is kept for the top only, through G.
+template <class G>
 struct Env {
     uint2* stk;
     uint64_t ld;
     int q;
-    uint32_t s, t, g;
+    uint32_t s, t, word, g;
+    G of;
 };
 
-__device__ __forceinline__ void env_init(Env& e, uint2* stk, uint64_t ld)
+template <class G>
+__device__ __forceinline__ void env_init(Env<G>& e, uint2* stk, uint64_t ld, G of = G())
 {
     e.stk = stk;
     e.ld = ld;
     e.q = -1;
-    e.s = e.t = e.g = 0u;
+    e.s = e.t = e.word = e.g = 0u;
+    e.of = of;
 }
-__device__ __forceinline__ void env_load(Env& e)
+template <class G>
+__device__ __forceinline__ void env_load(Env<G>& e)
 {
     const uint2 v = e.stk[(uint64_t)e.q * e.ld];
     e.s = v.x & 0xFFFFu;
     e.t = v.x >> 16;
-    e.g = v.y;
+    e.word = v.y;
+    e.g = e.of.g(v.y);
 }
-__device__ __forceinline__ void env_push(Env& e, uint32_t s, uint32_t t, uint32_t g)
+template <class G>
+__device__ __forceinline__ void env_push(Env<G>& e, uint32_t s, uint32_t t, uint32_t word, uint32_t g)
 {
     ++e.q;
     e.s = s;
     e.t = t;
+    e.word = word;
     e.g = g;
-    e.stk[(uint64_t)e.q * e.ld] = make_uint2(s | (t << 16), g);
+    e.stk[(uint64_t)e.q * e.ld] = make_uint2(s | (t << 16), word);
 }
 __device__ __forceinline__ uint64_t para(uint32_t x, uint32_t s, uint32_t g)
 {
@@ -156,42 +223,47 @@ __device__ __forceinline__ uint64_t para(uint32_t x, uint32_t s, uint32_t g)
     return (uint64_t)(d * d) + g;
 }
 
-// phase 1, one cell u of a column of n: the parabolas u now beats at their start are dropped, then u starts where it first beats the top
-__device__ __forceinline__ void env_add(Env& e, uint32_t u, uint32_t gu, uint32_t n)
+// phase 1, one cell u of a column of n with its word (kInf / kNone: skipped, never pushed): the parabolas u now beats at their start are
+// dropped -- only by a strictly better newcomer -- then u starts where it first beats the top.  Ties so keep the smaller s.
+template <class G>
+__device__ __forceinline__ void env_add(Env<G>& e, uint32_t u, uint32_t word, uint32_t n)
 {
-    if (gu == kInf) return;  // sentinels are skipped, never pushed
+    if (word == kInf) return;
+    const uint32_t gu = e.of.g(word);
     while (e.q >= 0 && para(e.t, e.s, e.g) > para(e.t, u, gu)) {
         if (--e.q >= 0) env_load(e);
     }
-    if (e.q < 0) { env_push(e, u, 0u, gu); return; }
+    if (e.q < 0) { env_push(e, u, 0u, word, gu); return; }
     // Sep(s, u) = floor((u^2 - s^2 + g_u - g_s) / (2 (u - s))); not popped: the crossing lies at or past t >= 0, the numerator is >= 0
     const int64_t num = (int64_t)u * u - (int64_t)e.s * e.s + (int64_t)gu - (int64_t)e.g;
     const int64_t den = 2 * ((int64_t)u - (int64_t)e.s);
     const int64_t w = (num >= 0 ? num / den : -((-num + den - 1) / den)) + 1;
-    if (w < (int64_t)n) env_push(e, u, (uint32_t)w, gu);
+    if (w < (int64_t)n) env_push(e, u, (uint32_t)w, word, gu);
 }
 
-// phase 2, cells u = n-1 down to 0: the envelope's value at u, then the entry that starts at u is dropped
-__device__ __forceinline__ uint32_t env_take(Env& e, uint32_t u)
+// phase 2, cells u = n-1 down to 0: the result at u of the parabola that wins there (kInf / kNone: the envelope is empty), its value being
+// the exact minimum, within the grid's 32-bit limit; then the entry that starts at u is dropped
+template <class G>
+__device__ __forceinline__ uint32_t env_take(Env<G>& e, uint32_t u)
 {
     if (e.q < 0) return kInf;
-    const uint32_t v = (uint32_t)para(u, e.s, e.g);  // the exact minimum: within the grid's 32-bit limit
+    const uint32_t v = e.of.result(e.s, e.word, (uint32_t)para(u, e.s, e.g));
     if (u == e.t && --e.q >= 0) env_load(e);
     return v;
 }
 
-__device__ __forceinline__ uint32_t mask_bit(const uint32_t* __restrict__ words, uint64_t i) { return (words[i >> 5] >> (i & 31u)) & 1u; }
-
 // Columns c < ncols of n cells: cell j of column c at base(c) + j * stride with base(c) = c % X + (c / X) * outer.
 // y pass: ncols = X Z, outer = X Y, stride = X.  z pass: ncols = X Y, outer = X, stride = X Y.
-// stk: n * ncols entries per envelope (SIGNED: the in-envelope's follow the out-envelope's).
+// stk: n * ncols entries per envelope.  Phase 1 reads the whole column before phase 2 writes it: the passes run in place.
+
+// SIGNED: two envelopes over the one buffer (stk: the in-envelope's entries follow the out-envelope's); TO_F32: the z pass converts in place.
 template <int MODE, bool TO_F32>
 __global__ __launch_bounds__(256) void k_dist_col(const uint32_t* __restrict__ words, uint32_t* __restrict__ buf, uint2* __restrict__ stk,
                                                   uint32_t X, uint64_t ncols, uint64_t outer, uint64_t stride, uint32_t n, float vs)
 {
     for (uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x; c < ncols; c += (uint64_t)gridDim.x * 256u) {
         const uint64_t base = c % X + (c / X) * outer;
-        Env eo, ei;
+        Env<DistWord> eo, ei;
         env_init(eo, stk + c, ncols);
         env_init(ei, stk + (uint64_t)n * ncols + c, ncols);
         uint32_t v = buf[base];
@@ -229,147 +301,65 @@ __global__ __launch_bounds__(256) void k_dist_col(const uint32_t* __restrict__ w
     }
 }
 
-// ---- the feature transform (vx_grid_nearest*): the same three passes, carrying WHICH target wins instead of how far it is ------------------
-// The one 32-bit intermediate per cell is the packed feature x' | y' << 16 of the cell's nearest target so far (kNone: none); every g the
-// envelope needs is recomputed from it and the column's own position: (x - x')^2 after the x pass, (x - x')^2 + (y - y')^2 after the y pass.
-// The stack entry stays 8 bytes, (s | t << 16, feature of s).  Ties: the x pass keeps the left target, the envelope keeps the smaller s
-// (a parabola is popped only by a strictly better newcomer, and a newcomer starts where it is strictly better) -- together the smallest
-// cell index among the nearest targets.  x' | y' << 16 == kNone would need X = Y = 65536, which the distance fields' limit excludes.
-
-// position along the row of the nearest target of cell x (bit i of word w), the left one on a tie; kNone: the row has none
-__device__ __forceinline__ uint32_t row_near(uint32_t t, uint32_t i, uint32_t x, uint32_t prev, uint32_t next)
-{
-    const uint32_t lo = t & ((2u << i) - 1u);
-    const uint32_t hi = t >> i;
-    const uint32_t pl = lo ? x - i + (31u - (uint32_t)__builtin_clz(lo)) : prev;
-    const uint32_t pr = hi ? x + (uint32_t)__builtin_ctz(hi) : next;
-    const uint32_t dl = pl != kNone ? x - pl : kInf;
-    const uint32_t dr = pr != kNone ? pr - x : kInf;
-    return dl <= dr ? pl : pr;
-}
-
-template <bool OCC, bool VEC4>
-__global__ __launch_bounds__(256) void k_near_x(const uint32_t* __restrict__ words, uint32_t* __restrict__ out, uint32_t X, uint64_t rows)
-{
-    const uint32_t W = (X + 31u) / 32u;
-    for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < rows; r += (uint64_t)gridDim.x * 256u) {
-        const uint64_t rowbit = r * X;
-        uint32_t* o = out + rowbit;
-        uint32_t prev = kNone;
-        Ahead a{0u, kNone};
-        ahead_from<OCC>(a, words, rowbit, X, W, 1u);
-        for (uint32_t w = 0; w < W; ++w) {
-            if (a.lw == w) ahead_from<OCC>(a, words, rowbit, X, W, w + 1u);
-            uint32_t valid;
-            const uint32_t m = row_word(words, rowbit, X, w, valid);
-            const uint32_t t = (OCC ? m : ~m) & valid;
-            const uint32_t nb = (uint32_t)__builtin_popcount(valid);
-            uint32_t v[32];
-#pragma unroll
-            for (uint32_t i = 0; i < 32u; ++i) v[i] = row_near(t, i, 32u * w + i, prev, a.pos);
-            if (VEC4) {
-#pragma unroll
-                for (uint32_t i = 0; i < 32u; i += 4u)
-                    if (i < nb) *reinterpret_cast<uint4*>(o + 32u * w + i) = make_uint4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-            } else {
-#pragma unroll
-                for (uint32_t i = 0; i < 32u; ++i)
-                    if (i < nb) o[32u * w + i] = v[i];
-            }
-            if (t) prev = 32u * w + 31u - (uint32_t)__builtin_clz(t);
-        }
-    }
-}
-
-// g of a packed feature seen from the column at (x, y): the squared distance within the axes already passed (y pass: x only, f >> 16 == 0)
-template <bool ZPASS>
-__device__ __forceinline__ uint32_t near_g(uint32_t f, uint32_t x, uint32_t y)
-{
-    const uint32_t dx = x - (f & 0xFFFFu);  // (the square of a wrapped difference is the square of the difference: below 2^32)
-    uint32_t g = dx * dx;
-    if (ZPASS) {
-        const uint32_t dy = y - (f >> 16);
-        g += dy * dy;
-    }
-    return g;
-}
-
-// Env with the feature of s in the entry's second word; g(s) is kept for the top only, recomputed on every load
-struct NearEnv {
-    uint2* stk;
-    uint64_t ld;
-    int q;
-    uint32_t s, t, f, g;
-};
-
-template <bool ZPASS>
-__device__ __forceinline__ void near_load(NearEnv& e, uint32_t x, uint32_t y)
-{
-    const uint2 v = e.stk[(uint64_t)e.q * e.ld];
-    e.s = v.x & 0xFFFFu;
-    e.t = v.x >> 16;
-    e.f = v.y;
-    e.g = near_g<ZPASS>(v.y, x, y);
-}
-__device__ __forceinline__ void near_push(NearEnv& e, uint32_t s, uint32_t t, uint32_t f, uint32_t g)
-{
-    ++e.q;
-    e.s = s;
-    e.t = t;
-    e.f = f;
-    e.g = g;
-    e.stk[(uint64_t)e.q * e.ld] = make_uint2(s | (t << 16), f);
-}
-
-// env_add with the feature fu of cell u (kNone: skipped)
-template <bool ZPASS>
-__device__ __forceinline__ void near_add(NearEnv& e, uint32_t u, uint32_t fu, uint32_t n, uint32_t x, uint32_t y)
-{
-    if (fu == kNone) return;
-    const uint32_t gu = near_g<ZPASS>(fu, x, y);
-    while (e.q >= 0 && para(e.t, e.s, e.g) > para(e.t, u, gu)) {
-        if (--e.q >= 0) near_load<ZPASS>(e, x, y);
-    }
-    if (e.q < 0) { near_push(e, u, 0u, fu, gu); return; }
-    const int64_t num = (int64_t)u * u - (int64_t)e.s * e.s + (int64_t)gu - (int64_t)e.g;
-    const int64_t den = 2 * ((int64_t)u - (int64_t)e.s);
-    const int64_t w = (num >= 0 ? num / den : -((-num + den - 1) / den)) + 1;
-    if (w < (int64_t)n) near_push(e, u, (uint32_t)w, fu, gu);
-}
-
-// Columns as for k_dist_col.  y pass (ZPASS false): buf holds x' (or kNone) and leaves as x' | y' << 16.  z pass: buf leaves as the cell
-// index x' + X (y' + Y z') of the nearest target; GATHER: as values[that index] instead, `fill` for kNone (values is not buf: every thread
-// reads and writes its own column of buf only, after phase 1 has read all of it).
+// y pass (ZPASS false): buf holds x' (or kNone) and leaves as x' | y' << 16.  z pass: buf leaves as the cell index x' + X (y' + Y z') of
+// the nearest target; GATHER: as values[that index] instead, `fill` for kNone (values is not buf: every thread reads and writes its own
+// column of buf only, after phase 1 has read all of it).  With the x pass keeping the left target and the envelope the smaller s, the
+// index is the smallest among the nearest targets.
 template <bool ZPASS, bool GATHER>
 __global__ __launch_bounds__(256) void k_near_col(uint32_t* __restrict__ buf, uint2* __restrict__ stk, uint32_t X, uint32_t Y, uint64_t ncols,
                                                   uint64_t outer, uint64_t stride, uint32_t n, const uint32_t* __restrict__ values, uint32_t fill)
 {
     for (uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x; c < ncols; c += (uint64_t)gridDim.x * 256u) {
-        const uint32_t x = (uint32_t)(c % X), y = (uint32_t)(c / X);  // (y pass: y is the column's z, and unused)
-        const uint64_t base = x + (c / X) * outer;
-        NearEnv e;
-        e.stk = stk + c;
-        e.ld = ncols;
-        e.q = -1;
-        e.s = e.t = e.f = e.g = 0u;
+        const uint64_t base = c % X + (c / X) * outer;
+        Env<FeatureWord<ZPASS>> e;  // (y pass: y is the column's z, and unused)
+        env_init(e, stk + c, ncols, FeatureWord<ZPASS>{(uint32_t)(c % X), (uint32_t)(c / X), X, Y});
         uint32_t v = buf[base];
         for (uint32_t u = 0; u < n; ++u) {
             const uint64_t i = base + (uint64_t)u * stride;
             const uint32_t vn = u + 1u < n ? buf[i + stride] : 0u;  // the next step's load, issued ahead
-            near_add<ZPASS>(e, u, v, n, x, y);
+            env_add(e, u, v, n);
             v = vn;
         }
         for (uint32_t u = n; u-- > 0;) {
-            const uint64_t i = base + (uint64_t)u * stride;
-            uint32_t r = kNone;
-            if (e.q >= 0) {
-                r = ZPASS ? (e.f & 0xFFFFu) + X * ((e.f >> 16) + Y * e.s) : e.f | (e.s << 16);
-                if (u == e.t && --e.q >= 0) near_load<ZPASS>(e, x, y);
-            }
+            uint32_t r = env_take(e, u);
             if (GATHER) r = r == kNone ? fill : values[r];
-            buf[i] = r;
+            buf[base + (uint64_t)u * stride] = r;
         }
     }
+}
+
+// ---- the three launches of a transform ---------------------------------------------------------------------------------------------------
+struct Passes {
+    uint32_t X, Y, Z;
+    uint64_t rows, xy, xz;  // rows of the x pass, columns of the z pass, columns of the y pass
+    unsigned gx, gy, gz;
+    bool v4;  // the x pass may store 16 bytes at a time: rows start on 16-byte boundaries
+    Passes(const uint32_t dim[3], const uint32_t* buf)
+        : X(dim[0]), Y(dim[1]), Z(dim[2]), rows((uint64_t)Y * Z), xy((uint64_t)X * Y), xz((uint64_t)X * Z), gx(blocks_for(rows, kDistBlocks)),
+          gy(blocks_for(xz, kDistBlocks)), gz(blocks_for(xy, kDistBlocks)), v4(X % 4u == 0u && ((uintptr_t)buf & 15u) == 0u)
+    {
+    }
+};
+
+template <int MODE>
+void distance_passes(const uint32_t* words, const uint32_t dim[3], float vs, uint32_t* buf, uint2* stk, hipStream_t s)
+{
+    const Passes p(dim, buf);
+    if (p.v4) VX_KL((k_dist_x<MODE, true>), dim3(p.gx), dim3(256), 0, s, words, buf, p.X, p.rows);
+    else VX_KL((k_dist_x<MODE, false>), dim3(p.gx), dim3(256), 0, s, words, buf, p.X, p.rows);
+    VX_KL((k_dist_col<MODE, false>), dim3(p.gy), dim3(256), 0, s, words, buf, stk, p.X, p.xz, p.xy, (uint64_t)p.X, p.Y, vs);
+    VX_KL((k_dist_col<MODE, MODE == kSigned>), dim3(p.gz), dim3(256), 0, s, words, buf, stk, p.X, p.xy, (uint64_t)p.X, p.xy, p.Z, vs);
+}
+
+template <bool OCC>
+void nearest_passes(const uint32_t* words, const uint32_t dim[3], const uint32_t* values, uint32_t fill, uint32_t* buf, uint2* stk, hipStream_t s)
+{
+    const Passes p(dim, buf);
+    if (p.v4) VX_KL((k_near_x<OCC, true>), dim3(p.gx), dim3(256), 0, s, words, buf, p.X, p.rows);
+    else VX_KL((k_near_x<OCC, false>), dim3(p.gx), dim3(256), 0, s, words, buf, p.X, p.rows);
+    VX_KL((k_near_col<false, false>), dim3(p.gy), dim3(256), 0, s, buf, stk, p.X, p.Y, p.xz, p.xy, (uint64_t)p.X, p.Y, values, fill);
+    if (values) VX_KL((k_near_col<true, true>), dim3(p.gz), dim3(256), 0, s, buf, stk, p.X, p.Y, p.xy, (uint64_t)p.X, p.xy, p.Z, values, fill);
+    else VX_KL((k_near_col<true, false>), dim3(p.gz), dim3(256), 0, s, buf, stk, p.X, p.Y, p.xy, (uint64_t)p.X, p.xy, p.Z, values, fill);
 }
 
 }  // namespace
@@ -377,20 +367,8 @@ __global__ __launch_bounds__(256) void k_near_col(uint32_t* __restrict__ buf, ui
 void launch_nearest(const uint32_t* words, const uint32_t dim[3], bool inside, const uint32_t* values, uint32_t fill, uint32_t* buf, uint2* stk,
                     hipStream_t s)
 {
-    const uint32_t X = dim[0], Y = dim[1], Z = dim[2];
-    const uint64_t rows = (uint64_t)Y * Z, xy = (uint64_t)X * Y, xz = (uint64_t)X * Z;
-    const unsigned gx = dist_grid(rows), gy = dist_grid(xz), gz = dist_grid(xy);
-    const bool v4 = X % 4u == 0u && ((uintptr_t)buf & 15u) == 0u;
-    if (inside) {
-        if (v4) VX_KL((k_near_x<false, true>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-        else VX_KL((k_near_x<false, false>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-    } else {
-        if (v4) VX_KL((k_near_x<true, true>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-        else VX_KL((k_near_x<true, false>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-    }
-    VX_KL((k_near_col<false, false>), dim3(gy), dim3(256), 0, s, buf, stk, X, Y, xz, xy, (uint64_t)X, Y, values, fill);
-    if (values) VX_KL((k_near_col<true, true>), dim3(gz), dim3(256), 0, s, buf, stk, X, Y, xy, (uint64_t)X, xy, Z, values, fill);
-    else VX_KL((k_near_col<true, false>), dim3(gz), dim3(256), 0, s, buf, stk, X, Y, xy, (uint64_t)X, xy, Z, values, fill);
+    if (inside) nearest_passes<false>(words, dim, values, fill, buf, stk, s);
+    else nearest_passes<true>(words, dim, values, fill, buf, stk, s);
 }
 
 uint64_t distance_stack_entries(const uint32_t dim[3], bool is_signed)
@@ -401,29 +379,10 @@ uint64_t distance_stack_entries(const uint32_t dim[3], bool is_signed)
 
 void launch_distance(const uint32_t* words, const uint32_t dim[3], int mode, float vs, uint32_t* buf, uint2* stk, hipStream_t s)
 {
-    const uint32_t X = dim[0], Y = dim[1], Z = dim[2];
-    const uint64_t rows = (uint64_t)Y * Z, xy = (uint64_t)X * Y, xz = (uint64_t)X * Z;
-    const unsigned gx = dist_grid(rows), gy = dist_grid(xz), gz = dist_grid(xy);
-    const bool v4 = X % 4u == 0u && ((uintptr_t)buf & 15u) == 0u;  // (rows start on 16-byte boundaries)
     switch (mode) {
-    case kOut:
-        if (v4) VX_KL((k_dist_x<kOut, true>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-        else VX_KL((k_dist_x<kOut, false>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-        VX_KL((k_dist_col<kOut, false>), dim3(gy), dim3(256), 0, s, words, buf, stk, X, xz, xy, (uint64_t)X, Y, vs);
-        VX_KL((k_dist_col<kOut, false>), dim3(gz), dim3(256), 0, s, words, buf, stk, X, xy, (uint64_t)X, xy, Z, vs);
-        break;
-    case kIn:
-        if (v4) VX_KL((k_dist_x<kIn, true>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-        else VX_KL((k_dist_x<kIn, false>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-        VX_KL((k_dist_col<kIn, false>), dim3(gy), dim3(256), 0, s, words, buf, stk, X, xz, xy, (uint64_t)X, Y, vs);
-        VX_KL((k_dist_col<kIn, false>), dim3(gz), dim3(256), 0, s, words, buf, stk, X, xy, (uint64_t)X, xy, Z, vs);
-        break;
-    default:
-        if (v4) VX_KL((k_dist_x<kSigned, true>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-        else VX_KL((k_dist_x<kSigned, false>), dim3(gx), dim3(256), 0, s, words, buf, X, rows);
-        VX_KL((k_dist_col<kSigned, false>), dim3(gy), dim3(256), 0, s, words, buf, stk, X, xz, xy, (uint64_t)X, Y, vs);
-        VX_KL((k_dist_col<kSigned, true>), dim3(gz), dim3(256), 0, s, words, buf, stk, X, xy, (uint64_t)X, xy, Z, vs);
-        break;
+    case kOut: distance_passes<kOut>(words, dim, vs, buf, stk, s); break;
+    case kIn: distance_passes<kIn>(words, dim, vs, buf, stk, s); break;
+    default: distance_passes<kSigned>(words, dim, vs, buf, stk, s); break;
     }
 }
 

@@ -19,6 +19,7 @@
 //   k_morph_thresh  the distance-field path: cell i is linear in the field, so a wave64 ballot of D[i] <= r2 (erosion: D[i] > r2 and the
 //                   box rule) yields two mask words; the tail bits of the last word stay clear
 #include "vx_internal.h"
+#include "vx_mask.h"
 
 #pragma clang fp contract(off)
 
@@ -157,14 +158,6 @@ __global__ __launch_bounds__(256) void k_morph_thresh(const uint32_t* __restrict
     }
 }
 
-inline unsigned morph_grid(uint64_t n)
-{
-    uint64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > kMorphBlocks) b = kMorphBlocks;
-    return (unsigned)b;
-}
-
 }  // namespace
 
 void launch_morph_ball(const uint32_t* src, const MorphDom& in, uint32_t* dst, const uint32_t odim[3], int32_t shift, uint32_t r2, uint32_t flags, hipStream_t s)
@@ -198,7 +191,7 @@ void launch_morph_pack(const uint32_t* aligned, const uint32_t dim[3], const uin
 {
     const uint64_t nvox = (uint64_t)dim[0] * dim[1] * dim[2], nwords = (nvox + 31u) / 32u;
     if (!nwords) return;
-    VX_KL(k_morph_pack, dim3(morph_grid(nwords)), dim3(256), 0, s, aligned, 32ull * ((dim[0] + 31u) / 32u), dim[0], nvox, nwords, orw, dst);
+    VX_KL(k_morph_pack, dim3(blocks_for(nwords, kMorphBlocks)), dim3(256), 0, s, aligned, 32ull * ((dim[0] + 31u) / 32u), dim[0], nvox, nwords, orw, dst);
 }
 
 void launch_morph_thresh(const uint32_t* field, const uint32_t dim[3], uint32_t r2, bool erode, uint32_t* dst, hipStream_t s)
@@ -207,8 +200,8 @@ void launch_morph_thresh(const uint32_t* field, const uint32_t dim[3], uint32_t 
     if (!nvox) return;
     uint32_t R = 0;
     while ((uint64_t)(R + 1) * (R + 1) <= r2) ++R;
-    if (erode) VX_KL((k_morph_thresh<true>), dim3(morph_grid(nvox)), dim3(256), 0, s, field, dim[0], dim[1], dim[2], nvox, r2, R, dst);
-    else VX_KL((k_morph_thresh<false>), dim3(morph_grid(nvox)), dim3(256), 0, s, field, dim[0], dim[1], dim[2], nvox, r2, R, dst);
+    if (erode) VX_KL((k_morph_thresh<true>), dim3(blocks_for(nvox, kMorphBlocks)), dim3(256), 0, s, field, dim[0], dim[1], dim[2], nvox, r2, R, dst);
+    else VX_KL((k_morph_thresh<false>), dim3(blocks_for(nvox, kMorphBlocks)), dim3(256), 0, s, field, dim[0], dim[1], dim[2], nvox, r2, R, dst);
 }
 
 }  // namespace vx

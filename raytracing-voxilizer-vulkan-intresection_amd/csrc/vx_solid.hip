@@ -16,6 +16,7 @@
 // reads one word per batch through the handle's mailbox (k_solid_report); there is no grid-wide barrier and no cap on the rounds.
 // Nothing is exchanged between workgroups inside a launch: every thread owns the words it writes, kernel boundaries order the rest.
 #include "vx_internal.h"
+#include "vx_mask.h"
 
 #pragma clang fp contract(off)
 
@@ -24,14 +25,6 @@ namespace vx {
 namespace {
 
 constexpr unsigned kSolidBlocks = 256 * 8;
-
-inline unsigned solid_grid(uint64_t n)
-{
-    uint64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > kSolidBlocks) b = kSolidBlocks;
-    return (unsigned)b;
-}
 
 // V consecutive words: one 16-byte access for V == 4
 template <int V> struct Words { uint32_t w[V]; };
@@ -89,11 +82,8 @@ __global__ __launch_bounds__(256) void k_solid_seed(const uint32_t* __restrict__
         const uint32_t y = (uint32_t)(r - (uint64_t)z * Y);
         uint32_t m;
         if (mp) {
-            const uint64_t s = r * X + 32ull * w;  // first cell of this padded word in the reference's bit order
-            const uint32_t nb = X - 32u * w < 32u ? X - 32u * w : 32u;
-            const uint64_t two = (uint64_t)words[s >> 5] | ((uint64_t)words[(s >> 5) + 1] << 32);  // (the mask has two spare words)
-            const uint32_t valid = nb == 32u ? ~0u : ((1u << nb) - 1u);
-            m = ((uint32_t)(two >> (s & 31u)) & valid) | ~valid;
+            uint32_t valid;  // this padded word's cells in the reference's bit order
+            m = (row_word(words, r * X, X, w, valid) & valid) | ~valid;
             mp[q] = m;
         } else {
             m = words[q];
@@ -383,7 +373,7 @@ SolidPlan solid_plan(const uint32_t dim[3])
 void launch_solid_seed(const uint32_t* words, uint32_t* mp, uint32_t* ext, const uint32_t dim[3], uint32_t* flag, hipStream_t s)
 {
     const SolidPlan p = solid_plan(dim);
-    VX_KL(k_solid_seed, dim3(solid_grid(p.pwords)), dim3(256), 0, s, words, p.padded ? mp : nullptr, ext, dim[0], dim[1], dim[2], p.W, flag);
+    VX_KL(k_solid_seed, dim3(blocks_for(p.pwords, kSolidBlocks)), dim3(256), 0, s, words, p.padded ? mp : nullptr, ext, dim[0], dim[1], dim[2], p.W, flag);
 }
 
 template <int V>
@@ -392,10 +382,10 @@ static void solid_col(const uint32_t* m, uint32_t* ext, uint32_t* agg, uint64_t 
 {
     const uint32_t nch = (nsteps + kChunk<V> - 1) / kChunk<V>;
     const uint64_t units = nouter * nch * groups;
-    VX_KL(k_solid_col_agg<V>, dim3(solid_grid(units)), dim3(256), 0, s, m, ext, agg, nouter, outer_stride, groups, step, nsteps, nch, prev_flag);
+    VX_KL(k_solid_col_agg<V>, dim3(blocks_for(units, kSolidBlocks)), dim3(256), 0, s, m, ext, agg, nouter, outer_stride, groups, step, nsteps, nch, prev_flag);
     const uint64_t ncols = nouter * groups;
-    VX_KL(k_solid_col_carry<V>, dim3(solid_grid(ncols * 64)), dim3(256), 0, s, agg, ncols, groups, nch, prev_flag);
-    VX_KL(k_solid_col<V>, dim3(solid_grid(units)), dim3(256), 0, s, m, ext, agg, nouter, outer_stride, groups, step, nsteps, nch, prev_flag, flag);
+    VX_KL(k_solid_col_carry<V>, dim3(blocks_for(ncols * 64, kSolidBlocks)), dim3(256), 0, s, agg, ncols, groups, nch, prev_flag);
+    VX_KL(k_solid_col<V>, dim3(blocks_for(units, kSolidBlocks)), dim3(256), 0, s, m, ext, agg, nouter, outer_stride, groups, step, nsteps, nch, prev_flag, flag);
 }
 
 uint64_t solid_agg_words(const uint32_t dim[3])
@@ -411,11 +401,11 @@ void launch_solid_round(const uint32_t* m, uint32_t* ext, uint32_t* agg, const u
     const uint64_t rows = (uint64_t)dim[1] * dim[2];
     const uint64_t yw = (uint64_t)dim[1] * p.W;
     if (p.W % 4u == 0u) {
-        VX_KL(k_solid_x<4>, dim3(solid_grid(rows)), dim3(256), 0, s, m, ext, rows, p.W, prev_flag, flag);
+        VX_KL(k_solid_x<4>, dim3(blocks_for(rows, kSolidBlocks)), dim3(256), 0, s, m, ext, rows, p.W, prev_flag, flag);
         solid_col<4>(m, ext, agg, dim[2], yw, p.W / 4u, p.W, dim[1], prev_flag, flag, s);
         solid_col<4>(m, ext, agg, dim[1], p.W, p.W / 4u, yw, dim[2], prev_flag, flag, s);
     } else {
-        VX_KL(k_solid_x<1>, dim3(solid_grid(rows)), dim3(256), 0, s, m, ext, rows, p.W, prev_flag, flag);
+        VX_KL(k_solid_x<1>, dim3(blocks_for(rows, kSolidBlocks)), dim3(256), 0, s, m, ext, rows, p.W, prev_flag, flag);
         solid_col<1>(m, ext, agg, dim[2], yw, p.W, p.W, dim[1], prev_flag, flag, s);
         solid_col<1>(m, ext, agg, dim[1], p.W, p.W, yw, dim[2], prev_flag, flag, s);
     }
@@ -430,17 +420,17 @@ void launch_solid_finish(uint32_t* words, const uint32_t* mp, uint32_t* ext, uin
 {
     const SolidPlan p = solid_plan(dim);
     if (!p.padded) {
-        VX_KL(k_solid_finish_aligned, dim3(solid_grid((nwords + 3) / 4)), dim3(256), 0, s, words, ext, nwords);
+        VX_KL(k_solid_finish_aligned, dim3(blocks_for((nwords + 3) / 4, kSolidBlocks)), dim3(256), 0, s, words, ext, nwords);
     } else {
         const uint64_t nvox = (uint64_t)dim[0] * dim[1] * dim[2];
-        VX_KL(k_solid_finish_padded, dim3(solid_grid(nwords)), dim3(256), 0, s, words, mp, ext, h, nwords, nvox, dim[0], p.W);
+        VX_KL(k_solid_finish_padded, dim3(blocks_for(nwords, kSolidBlocks)), dim3(256), 0, s, words, mp, ext, h, nwords, nvox, dim[0], p.W);
     }
 }
 
 void launch_solid_ids(int16_t* ids, uint64_t n, int16_t v, bool only_unset, hipStream_t s)
 {
     if (!n) return;
-    VX_KL(k_solid_ids, dim3(solid_grid(n)), dim3(256), 0, s, ids, n, v, only_unset ? 1 : 0);
+    VX_KL(k_solid_ids, dim3(blocks_for(n, kSolidBlocks)), dim3(256), 0, s, ids, n, v, only_unset ? 1 : 0);
 }
 
 }  // namespace vx

@@ -21,6 +21,7 @@
 //   k_nets_finish  one lane per vertex: org + (((float)i + 0.5f) + u) * vs - half;
 //   k_nets_normals one lane per vertex: the block's mixed internal faces from the final positions.
 #include "vx_internal.h"
+#include "vx_mask.h"
 
 #pragma clang fp contract(off)
 
@@ -29,14 +30,6 @@ namespace vx {
 namespace {
 
 constexpr unsigned kSurfBlocks = 256 * 8;
-
-inline unsigned surf_grid(uint64_t n)
-{
-    uint64_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > kSurfBlocks) b = kSurfBlocks;
-    return (unsigned)b;
-}
 
 // 64 bits of the mask from bit `bit` on (any sign): words outside [0, nwords) read as empty
 __device__ __forceinline__ uint64_t window(const uint32_t* __restrict__ words, uint64_t nwords, int64_t bit)
@@ -459,21 +452,21 @@ SurfacePlan surface_plan(const GridParams& g)
 void launch_surface_count(const uint32_t* words, const GridParams& g, const SurfacePlan& p, uint32_t* tcount, uint32_t* cmask, hipStream_t s)
 {
     const uint64_t n = g.nwords > p.nlw ? g.nwords : p.nlw;
-    VX_KL(k_surf_count, dim3(surf_grid(n)), dim3(256), 0, s, words, g, tcount, cmask, p.nlw, p.npts);
+    VX_KL(k_surf_count, dim3(blocks_for(n, kSurfBlocks)), dim3(256), 0, s, words, g, tcount, cmask, p.nlw, p.npts);
 }
 
 void launch_surface_emit(const uint32_t* words, const GridParams& g, const SurfacePlan& p, const uint32_t* tpre, const uint32_t* cmask,
                          const uint32_t* vpre, const uint32_t* wprefix, const int16_t* cell_mat, float* xyz, int32_t* tri, int32_t* mat,
                          hipStream_t s)
 {
-    VX_KL(k_surf_verts, dim3(surf_grid(p.nlw)), dim3(256), 0, s, cmask, vpre, g, p.nlw, xyz);
+    VX_KL(k_surf_verts, dim3(blocks_for(p.nlw, kSurfBlocks)), dim3(256), 0, s, cmask, vpre, g, p.nlw, xyz);
     launch_surface_tris(words, g, tpre, cmask, vpre, wprefix, cell_mat, tri, mat, s);
 }
 
 void launch_surface_tris(const uint32_t* words, const GridParams& g, const uint32_t* tpre, const uint32_t* cmask, const uint32_t* vpre,
                          const uint32_t* wprefix, const int16_t* cell_mat, int32_t* tri, int32_t* mat, hipStream_t s)
 {
-    VX_KL(k_surf_emit, dim3(surf_grid(g.nwords)), dim3(256), 0, s, words, g, tpre, cmask, vpre, wprefix, cell_mat, tri, mat);
+    VX_KL(k_surf_emit, dim3(blocks_for(g.nwords, kSurfBlocks)), dim3(256), 0, s, words, g, tpre, cmask, vpre, wprefix, cell_mat, tri, mat);
 }
 
 size_t nets_bytes(uint64_t V, NetsBufs* b)
@@ -500,8 +493,8 @@ size_t nets_bytes(uint64_t V, NetsBufs* b)
 void launch_surface_nets(const uint32_t* words, const GridParams& g, const SurfacePlan& p, const uint32_t* cmask, const uint32_t* vpre,
                          uint64_t V, const NetsBufs& b, uint32_t iterations, float lambda, float mu, float* xyz, float* normals, hipStream_t s)
 {
-    VX_KL(k_nets_init, dim3(surf_grid(p.nlw)), dim3(256), 0, s, words, g, cmask, vpre, p.nlw, p.npts, b.cfg, b.lat);
-    const dim3 grid(surf_grid(V));
+    VX_KL(k_nets_init, dim3(blocks_for(p.nlw, kSurfBlocks)), dim3(256), 0, s, words, g, cmask, vpre, p.nlw, p.npts, b.cfg, b.lat);
+    const dim3 grid(blocks_for(V, kSurfBlocks));
     VX_KL(k_nets_table, grid, dim3(256), 0, s, b.cfg, b.lat, cmask, vpre, g, V, b.nb, b.u[0]);
     int cur = 0;  // (the buffer that holds the current offsets: the steps ping-pong, so an odd count ends in u[1])
     for (uint32_t it = 0; it < iterations; ++it) {

@@ -1015,32 +1015,41 @@ class Grid:
         _check(lib().vx_grid_surface(self.h, None, 0, None, 0, probe.ctypes.data if materials else None, C.byref(nv), C.byref(nt)))
         return nv.value, nt.value
 
+    def _surface_arrays(self, counts, device, materials, normals, sp=None):
+        """(verts, tris[, mats][, normals]) for counts = (V, T): numpy arrays from the host entry point, or device torch tensors from the
+        _device one, recorded on the grid's stream.  sp: the vx_smooth of the surface nets; None: the faces' mesh."""
+        nv, nt = counts
+        if device:
+            import torch
+
+            def new(shape, dtype):
+                return torch.empty(shape, dtype=getattr(torch, dtype), device="cuda")
+        else:
+            def new(shape, dtype):
+                return np.zeros(shape, getattr(np, dtype))
+        v, t = new((nv, 3), "float32"), new((nt, 3), "int32")
+        out = (v, t) + ((new(nt, "int32"),) if materials else ()) + ((new((nv, 3), "float32"),) if normals else ())
+        if nv or nt:
+            ptr = [x.data_ptr() if device else x.ctypes.data for x in out]
+            args = [ptr[0], nv, ptr[1], nt, ptr[2] if materials else None]
+            if sp is not None:
+                args = [C.byref(sp)] + args + [ptr[-1] if normals else None]
+            a, b = C.c_uint64(), C.c_uint64()
+            entry = "vx_grid_surface" + ("_smooth" if sp is not None else "") + ("_device" if device else "")
+            _check(getattr(lib(), entry)(self.h, *args, C.byref(a), C.byref(b)))
+            if device:
+                for x in out:
+                    self._record(x)
+        return out
+
     def surface(self, materials=False):
         """vx_grid_surface: the boundary mesh of the occupancy -> (verts (V, 3) float32, tris (T, 3) int32[, mats (T,) int32])."""
-        nv, nt = self.surface_counts(materials)
-        v = np.zeros((nv, 3), np.float32)
-        t = np.zeros((nt, 3), np.int32)
-        m = np.zeros(nt, np.int32) if materials else None
-        if nv or nt:
-            a, b = C.c_uint64(), C.c_uint64()
-            _check(lib().vx_grid_surface(self.h, v.ctypes.data, nv, t.ctypes.data, nt, m.ctypes.data if materials else None, C.byref(a), C.byref(b)))
-        return (v, t, m) if materials else (v, t)
+        return self._surface_arrays(self.surface_counts(materials), False, materials, False)
 
     def surface_device(self, materials=False):
         """vx_grid_surface_device: the same arrays as device torch tensors, written asynchronously on the grid's stream (the host waits
         for the two counts only)."""
-        import torch
-        nv, nt = self.surface_counts(materials)
-        v = torch.empty((nv, 3), dtype=torch.float32, device="cuda")
-        t = torch.empty((nt, 3), dtype=torch.int32, device="cuda")
-        m = torch.empty(nt, dtype=torch.int32, device="cuda") if materials else None
-        if nv or nt:
-            a, b = C.c_uint64(), C.c_uint64()
-            _check(lib().vx_grid_surface_device(self.h, v.data_ptr(), nv, t.data_ptr(), nt, m.data_ptr() if materials else None, C.byref(a),
-                                                C.byref(b)))
-            for x in (v, t) + ((m,) if materials else ()):
-                self._record(x)
-        return (v, t, m) if materials else (v, t)
+        return self._surface_arrays(self.surface_counts(materials), True, materials, False)
 
     def surface_mesh(self, materials=False):
         """vx_grid_surface_mesh: the boundary mesh as a Mesh (with materials: the grid's records and one id per triangle)."""
@@ -1061,34 +1070,13 @@ class Grid:
         """vx_grid_surface_smooth: the surface-nets mesh -> (verts (V, 3) float32, tris (T, 3) int32[, mats (T,) int32][, normals (V, 3)
         float32]): vx_grid_surface's vertices and triangles, the positions relaxed by `iterations` x (a step with lam, a step with mu)."""
         sp, nv, nt = self._smooth_counts(iterations, lam, mu, materials)
-        v = np.zeros((nv, 3), np.float32)
-        t = np.zeros((nt, 3), np.int32)
-        m = np.zeros(nt, np.int32) if materials else None
-        n = np.zeros((nv, 3), np.float32) if normals else None
-        if nv or nt:
-            a, b = C.c_uint64(), C.c_uint64()
-            _check(lib().vx_grid_surface_smooth(self.h, C.byref(sp), v.ctypes.data, nv, t.ctypes.data, nt, m.ctypes.data if materials else None,
-                                                n.ctypes.data if normals else None, C.byref(a), C.byref(b)))
-        return (v, t) + ((m,) if materials else ()) + ((n,) if normals else ())
+        return self._surface_arrays((nv, nt), False, materials, normals, sp)
 
     def surface_smooth_device(self, iterations=8, lam=0.5, mu=-0.53, materials=False, normals=False):
         """vx_grid_surface_smooth_device: the same arrays as device torch tensors, written asynchronously on the grid's stream (the host
         waits for the two counts only)."""
-        import torch
         sp, nv, nt = self._smooth_counts(iterations, lam, mu, materials)
-        v = torch.empty((nv, 3), dtype=torch.float32, device="cuda")
-        t = torch.empty((nt, 3), dtype=torch.int32, device="cuda")
-        m = torch.empty(nt, dtype=torch.int32, device="cuda") if materials else None
-        n = torch.empty((nv, 3), dtype=torch.float32, device="cuda") if normals else None
-        if nv or nt:
-            a, b = C.c_uint64(), C.c_uint64()
-            _check(lib().vx_grid_surface_smooth_device(self.h, C.byref(sp), v.data_ptr(), nv, t.data_ptr(), nt, m.data_ptr() if materials else None,
-                                                       n.data_ptr() if normals else None, C.byref(a), C.byref(b)))
-        out = (v, t) + ((m,) if materials else ()) + ((n,) if normals else ())
-        if nv or nt:
-            for x in out:
-                self._record(x)
-        return out
+        return self._surface_arrays((nv, nt), True, materials, normals, sp)
 
     def surface_smooth_mesh(self, iterations=8, lam=0.5, mu=-0.53, materials=False, normals=False):
         """vx_grid_surface_smooth_mesh: the surface-nets mesh as a Mesh (with normals: corner normals from the vertex normals, so an

@@ -123,6 +123,47 @@ def test_long_columns(gpu, dims):
     check_fields(g)
 
 
+@pytest.mark.parametrize("dims", [(2, 1024, 520), (1024, 2, 520), (1024, 520, 2)])
+def test_grid_stride_loops(gpu, dims):
+    """more rows, more y columns and more z columns than the 2048 x 256 threads of a launch: the signed kernels' loops go round too"""
+    X, Y, Z = dims
+    assert max(Y * Z, X * Z, X * Y) > 2048 * 256
+    cells = np.random.default_rng(X + 2 * Y).random((Z, Y, X)) < 0.01
+    g = masked_grid(gpu, cells)
+    check_fields(g, device=False)
+
+
+def misaligned_out(n, dtype, canary):
+    """a contiguous device tensor of n elements that starts 4 bytes past a 16-byte boundary, between two canaries -> (whole, slice)"""
+    import torch
+    big = torch.full((n + 2,), canary, dtype=dtype, device="cuda")
+    out = big[1:1 + n]
+    assert big.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 4 and out.is_contiguous()
+    return big, out
+
+
+def test_misaligned_device_output(gpu):
+    """X % 4 == 0, but the output is only 4-byte aligned: the x pass takes its scalar stores because of the pointer.  Every field equals
+    its host variant (whose staging buffer is aligned) bit for bit, and nothing is written outside the n elements."""
+    import torch
+    cells = np.random.default_rng(64).random((3, 5, 64)) < 0.3
+    g = masked_grid(gpu, cells)
+    n = cells.size
+    for inside in (False, True):
+        big, out = misaligned_out(n, torch.int32, 0x5A5A5A5A)
+        g.distance_sq_device(out=out.view(3, 5, 64), inside=inside)
+        torch.cuda.synchronize()
+        got = big.cpu().numpy()
+        assert got[0] == 0x5A5A5A5A and got[n + 1] == 0x5A5A5A5A
+        assert np.array_equal(got[1:1 + n].view(np.uint32), g.distance_sq(inside=inside).reshape(-1)), inside
+    big, out = misaligned_out(n, torch.float32, 7.5)
+    g.sdf_device(out=out)
+    torch.cuda.synchronize()
+    got = big.cpu().numpy()
+    assert got[0] == 7.5 and got[n + 1] == 7.5
+    assert got[1:1 + n].tobytes() == g.sdf().tobytes()
+
+
 def test_over_the_limit_is_refused(gpu):
     import torch
     g = gpu.Grid.create(gpu.GRID_BOOL, 65537, 1, 1, F(0.01))
