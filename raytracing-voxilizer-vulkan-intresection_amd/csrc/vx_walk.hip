@@ -467,7 +467,10 @@ __device__ unsigned long long g_walk_hist[2 * 16];  // rays by slab steps (bucke
 #define VX_W_SITE_DECL , unsigned* dbg_w, unsigned* dbg_l
 #define VX_W_SITE_ARGS , dbg_w, dbg_l
 #define VX_W_T(i) { const unsigned long long now_ = __builtin_readcyclecounter(); dbg_c[i] += now_ - dbg_last; dbg_last = now_; }
+// g_walk_dbg[20..22]: exact-test phases after which the lane retired at once / went to a sibling brick / had a hit and the check declined
+#define VX_W_EARLY(i) atomicAdd(&g_walk_dbg[i], 1ull);
 #else
+#define VX_W_EARLY(i)
 #define VX_W_SITE(i)
 #define VX_W_SITE_DECL
 #define VX_W_SITE_ARGS
@@ -486,6 +489,16 @@ __device__ unsigned long long g_walk_hist[2 * 16];  // rays by slab steps (bucke
 #ifndef VX_W_STEPS
 #define VX_W_STEPS 2
 #endif
+// Steps per round by the size of the batch.  A launch of a few rays per lane is mostly ramp and drain -- every wave finishing the rays it
+// started last, a span counted in rounds -- and a round's fixed part (ballots, the exact-test, brick and retire phases) is paid per round:
+// more steps per round shorten it.  A large batch is bound by instruction issue, where the lanes that sit out the rest of a round (parked
+// candidates, a brick to fetch, a finished ray) cost more the longer the round is.  Measured: DESIGN.md section 8, "Round 9".
+#ifndef VX_W_STEPS_FEW
+#define VX_W_STEPS_FEW 4
+#endif
+#ifndef VX_W_FEW_BELOW
+#define VX_W_FEW_BELOW 1064960ull   // = 1040 rays x one resident set of workgroups: the batches walk_blocks launches with fewer waves, and smaller ones
+#endif
 #ifndef VX_W_ITERS
 #define VX_W_ITERS 1
 #endif
@@ -503,6 +516,12 @@ __device__ unsigned long long g_walk_hist[2 * 16];  // rays by slab steps (bucke
 #endif
 #ifndef VX_W_MINWAVES
 #define VX_W_MINWAVES 4
+#endif
+#ifndef VX_W_NARROW_FROM
+#define VX_W_NARROW_FROM 400000ull   // walk_blocks: batches from this many rays on get one workgroup per ...
+#endif
+#ifndef VX_W_NARROW_RAYS
+#define VX_W_NARROW_RAYS 1040ull     // ... this many rays, where that is fewer than a resident set
 #endif
 
 // After a slab has been dealt with: on to the next one -- and up to the block level at the end of a block slab's eight brick
@@ -745,8 +764,9 @@ __device__ __forceinline__ bool walk_step(WalkLane<IdxT, WIDE>& R, const WalkHot
 }
 
 // The exact tests of the candidates a lane parked in its LDS slot: hitAabb on every candidate cell of one 1-cell slab of a brick.
+// Returns the slab's cell index along w.
 template <typename IdxT, bool WIDE>
-__device__ __forceinline__ void walk_exact(WalkLane<IdxT, WIDE>& R, const WalkHot& P, const uint4* __restrict__ xslot, const uint32_t* __restrict__ xslot_hi VX_W_SITE_DECL)
+__device__ __forceinline__ int walk_exact(WalkLane<IdxT, WIDE>& R, const WalkHot& P, const uint4* __restrict__ xslot, const uint32_t* __restrict__ xslot_hi VX_W_SITE_DECL)
 {
     const GridParams& g = P.g;
     const uint4 xs = *xslot;
@@ -778,6 +798,7 @@ __device__ __forceinline__ void walk_exact(WalkLane<IdxT, WIDE>& R, const WalkHo
             R.best_idx = vi;
         }
     }
+    return k;
 }
 
 // position of the n-th (0-based) set bit of a 64-bit mask (n < popcount)
@@ -799,11 +820,11 @@ __device__ __forceinline__ float shfl_fw(float v, int src) { return __shfl(v, sr
 // Persistent waves with dynamic work fetch.  Exit condition every wave reaches: the work counter passes the ray count (no
 // refill possible) and every lane's ray has finished; a ray finishes in a bounded number of slabs (its index along the major
 // axis is monotone at both levels).
-template <bool LDS_MIPS, typename IdxT, bool WIDE = false>
+template <bool LDS_MIPS, typename IdxT, bool WIDE = false, int STEPS = VX_W_STEPS>
 __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkParams PP)
 {
     const WalkHot& P = PP.hot;
-    constexpr int kStepsPerRound = VX_W_STEPS;   // slab steps between two brick phases
+    constexpr int kStepsPerRound = STEPS;        // slab steps between two brick phases (walk_steps: by the size of the batch)
     constexpr int kItersPerRound = VX_W_ITERS;   // (walk, brick) iterations between two refill checks
     constexpr int kRefillBelow = VX_W_REFILL;    // refill when fewer than this many lanes are busy
     constexpr uint32_t kChunkRays = VX_W_CHUNK;      // rays a wave reserves per touch of the global counter: at least ...
@@ -1020,8 +1041,20 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
         // ---- exact tests of the candidates the steps parked
         if (__ballot(xpend)) {
             if (xpend) {
-                walk_exact(R, P, &xslots[threadIdx.x], &xslots_hi[WIDE ? threadIdx.x : 0] VX_W_SITE_ARGS);
+                const int kx = walk_exact(R, P, &xslots[threadIdx.x], &xslots_hi[WIDE ? threadIdx.x : 0] VX_W_SITE_ARGS);
                 xpend = false;
+                // The ray's fate, from the new best hit: the ta of the NEXT 1-cell slab in travel order, in walk_step's own expression (the
+                // same integers and float operations: the float a later step would compare against).  ta is monotone in travel order at
+                // every level, so with best < ta no box of any later slab can win -- not of this brick, not of a later brick slab, not of a
+                // later block slab (the rule walk_step stops by).  Only the sibling bricks of the same brick slab lie beside and not behind;
+                // the brick being walked is still the lowest set bit of R.pend.  Without the check the next round's step finds the same,
+                // one slab step, one brick phase and one round later.
+                const float ta_next = R.iw > 0.0f ? R.iw * (((R.orgw + (float)(kx + 1) * g.vs) - R.tol) - R.ow) : R.iw * (((R.orgw + (float)kx * g.vs) + R.tol) - R.ow);
+                if (R.best < ta_next) {
+                    const uint32_t low = R.pend & 0xFFFFu;
+                    if (!(low & (low - 1u)) && !(R.pend >> 31)) { VX_W_EARLY(20) finished = true; }  // no sibling, no further window: retires in this round
+                    else { VX_W_EARLY(21) fstate = 1u | 2u | 4u; }                                    // pop, dead: this round's brick phase goes to the sibling
+                } else if (R.best_idx != (IdxT)~(IdxT)0) { VX_W_EARLY(22) }
                 if (P.any_hit && R.best_idx != (IdxT)~(IdxT)0) finished = true;  // shadow query (gl_RayFlagsTerminateOnFirstHitEXT, raytrace2.rchit:108)
             }
         }
@@ -1174,7 +1207,7 @@ static uint64_t walk_blocks(uint64_t n)
     // ray latencies whatever the batch; with somewhat fewer waves a lane sees at least ~4 rays and the same work drains from fewer
     // rays in flight (measured on the bench scene, 0.5M / 0.75M / 1M rays: -3 / -8 / -8 %; below ~0.4M rays, where a lane has at
     // most one or two rays anyway, the full width is faster, and from ~1.1M rays on the rule gives the full width).
-    if (n >= 400000ull && n / 1040ull < max_blocks) max_blocks = n / 1040ull;
+    if (n >= VX_W_NARROW_FROM && n / VX_W_NARROW_RAYS < max_blocks) max_blocks = n / VX_W_NARROW_RAYS;
     const uint64_t nblk = (n + VX_W_BLOCK - 1) / VX_W_BLOCK;
     return nblk > max_blocks ? max_blocks : nblk;
 }
@@ -1270,13 +1303,16 @@ bool launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, 
             queue->counter = P.cold.next_item;
             queue->dry_at = sr >= n ? 0ull : n - sr;
         }
-        if (lds) {
-            if (idx32) VX_KL((k_walk<true, uint32_t>), grid, block, shmem, s, P); else VX_KL((k_walk<true, unsigned long long>), grid, block, shmem, s, P);
-        } else if (wide) {
-            if (idx32) VX_KL((k_walk<false, uint32_t, true>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long, true>), grid, block, shmem, s, P);
-        } else {
-            if (idx32) VX_KL((k_walk<false, uint32_t>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long>), grid, block, shmem, s, P);
+#define VX_WALK_LAUNCH(STEPS)                                                                                                                                   \
+        if (lds) {                                                                                                                                                  \
+            if (idx32) VX_KL((k_walk<true, uint32_t, false, STEPS>), grid, block, shmem, s, P); else VX_KL((k_walk<true, unsigned long long, false, STEPS>), grid, block, shmem, s, P);   \
+        } else if (wide) {                                                                                                                                          \
+            if (idx32) VX_KL((k_walk<false, uint32_t, true, STEPS>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long, true, STEPS>), grid, block, shmem, s, P);   \
+        } else {                                                                                                                                                    \
+            if (idx32) VX_KL((k_walk<false, uint32_t, false, STEPS>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long, false, STEPS>), grid, block, shmem, s, P); \
         }
+        if (n < VX_W_FEW_BELOW) { VX_WALK_LAUNCH(VX_W_STEPS_FEW) } else { VX_WALK_LAUNCH(VX_W_STEPS) }
+#undef VX_WALK_LAUNCH
     }
     return ranked;
 }

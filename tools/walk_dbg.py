@@ -24,6 +24,9 @@ for n in (1_000_000, 8_000_000):
         print("  %-20s wave-execs %10d (%.2f per ray)  lanes %11d (%.2f per ray)  utilisation %.3f" % (nm, w, w / n, l, l / n, l / (64.0 * w) if w else 0))
     c = a[16:20]; tot = float(sum(c)) or 1.0
     print("  wave cycles: refill %.1f%%  walk %.1f%%  brick %.1f%%  retire %.1f%%   (total %.3g)" % tuple([100 * x / tot for x in c] + [tot]))
+    e = a[20:23]; tot_e = float(sum(e)) or 1.0
+    print("  after a lane's exact tests: retired at once %d (%.1f%%)  on to a sibling brick %d (%.1f%%)  hit known, check declined %d (%.1f%%)" %
+          (e[0], 100 * e[0] / tot_e, e[1], 100 * e[1] / tot_e, e[2], 100 * e[2] / tot_e))
     ts = (C.c_ulonglong * (4 * 8192))()
     if hasattr(L, "vx_debug_walk_ts") and L.vx_debug_walk_ts(ts) == 0:
         a = np.frombuffer(ts, dtype=np.uint64).reshape(8192, 4).astype(np.float64)
