@@ -179,16 +179,15 @@ struct DevBuf {
     size_t cap = 0;
     const Home* const home;
     bool fresh = false;  // set when ensure() handed out a new block (contents undefined); the owner clears it
-    uint32_t scan_gen = 0;  // scan scratch only: the number of the last scan that used this block (generation mode of the single-pass scan)
     explicit DevBuf(const Home* h) : home(h) {}
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), home(o.home), fresh(o.fresh), scan_gen(o.scan_gen) { o.p = nullptr; o.cap = 0; }
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), home(o.home), fresh(o.fresh) { o.p = nullptr; o.cap = 0; }
     DevBuf& operator=(DevBuf&& o) noexcept
     {
         if (this != &o) {
             release();
-            p = o.p; cap = o.cap; fresh = o.fresh; scan_gen = o.scan_gen;
+            p = o.p; cap = o.cap; fresh = o.fresh;
             o.p = nullptr; o.cap = 0;
         }
         return *this;
@@ -296,38 +295,64 @@ hipError_t ensure_small(DevBuf& small)
     return e;
 }
 
-// scan scratch with the "all zero between scans" contract of launch_scan_u32(..., tmp_is_zero = true)
-hipError_t ensure_scan_tmp(DevBuf& tmp, size_t bytes, hipStream_t s)
-{
-    hipError_t e = tmp.ensure(bytes);
-    if (e != hipSuccess || !tmp.fresh) return e;
-    e = hipMemsetAsync(tmp.p, 0, tmp.cap, s);
-    if (e == hipSuccess) { tmp.fresh = false; tmp.scan_gen = 0; }
-    return e;
-}
+struct ScanOpts {  // what the callers of a handle scan vary (the rest of vx::ScanArgs is ScanScratch's business)
+    unsigned long long total_tag = 0;
+    uint32_t *sel1024 = nullptr, *group16 = nullptr;
+};
 
-// the number of the next scan on this scratch block (generation mode: state words of older scans read as "not there yet")
-uint32_t advance_scan_gen(DevBuf& tmp, hipStream_t s)
-{
-    if (++tmp.scan_gen >= (1u << 22)) {
-        (void)hipMemsetAsync(tmp.p, 0, tmp.cap, s);
-        tmp.scan_gen = 1u;
+// The scratch of the scans queued on a handle: the single-pass scan's status block and the number of the last scan on it.  The block is
+// cleared once when it comes from the pool, and every scan on it is the next generation (state words of older scans read as "not there
+// yet"; the numbers wrap at 2^22, where the block is cleared again).  in / out are whole blocks, hence 16-byte aligned: a scan queued
+// here always runs single-pass, so its total carries the caller's tag and sel1024 / group16 are written.
+struct ScanScratch {
+    DevBuf block;
+    uint32_t gen = 0;  // the number of the last scan on the block
+    vx::ScanTaken took = vx::ScanTaken::ticket;  // the path of the last scan (test aid)
+    explicit ScanScratch(const Home* h) : block(h) {}
+    // the block sized for a scan of n elements: for callers that must size it ahead of an earlier kernel of theirs (the scans do it themselves)
+    hipError_t reserve(uint64_t n, hipStream_t s)
+    {
+        hipError_t e = block.ensure(vx::scan_tmp_bytes(n));
+        if (e != hipSuccess || !block.fresh) return e;
+        e = hipMemsetAsync(block.p, 0, block.cap, s);
+        if (e == hipSuccess) { block.fresh = false; gen = 0; }
+        return e;
     }
-    return tmp.scan_gen;
-}
-
-// A scan queued on a handle's scratch: the block sized and zero (ensure_scan_tmp), the scan its next generation.  *tagged (optional):
-// whether *total64 carries a.total_tag (launch_scan_u32).
-vx_status scan_on(DevBuf& tmp, hipStream_t s, const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, unsigned long long* total64,
-                  vx::ScanArgs a = vx::ScanArgs(), bool* tagged = nullptr)
-{
-    VX_HIP(ensure_scan_tmp(tmp, vx::scan_tmp_bytes(n), s));
-    a.tmp_is_zero = true;
-    a.gen = advance_scan_gen(tmp, s);
-    const bool tg = vx::launch_scan_u32(in, out, n, popcount_input, tmp.p, total64, s, a);
-    if (tagged) *tagged = tg;
-    return VX_OK;
-}
+    uint32_t next_gen(hipStream_t s)
+    {
+        if (gen + 1u >= (1u << 22)) { (void)hipMemsetAsync(block.p, 0, block.cap, s); gen = 0; }
+        return ++gen;
+    }
+    void start_at(uint32_t g) { gen = g; }  // (test aid: the next scan is generation g + 1)
+    vx_status u32(const DevBuf& in, const DevBuf& out, uint64_t n, bool popcount_input, unsigned long long* total64, hipStream_t s, const ScanOpts& o = ScanOpts())
+    {
+        VX_HIP(reserve(n, s));
+        vx::ScanArgs a;
+        a.tmp_is_zero = true;
+        a.total_tag = o.total_tag;
+        a.sel1024 = o.sel1024;
+        a.group16 = o.group16;
+        a.gen = next_gen(s);
+        return done(vx::launch_scan_u32(in.as<uint32_t>(), out.as<uint32_t>(), n, popcount_input, block.p, total64, s, a));
+    }
+    vx_status u8(const DevBuf& in, const DevBuf& out, uint64_t n, unsigned long long* total64, hipStream_t s, unsigned long long total_tag = 0)
+    {
+        VX_HIP(reserve(n, s));
+        return done(vx::launch_scan_u8(in.as<uint8_t>(), out.as<uint32_t>(), n, block.p, total64, s, total_tag, next_gen(s)));
+    }
+    // the scan of n uint32 values and the level-2 mip in one launch (launch_mip2_scan)
+    vx_status mip2(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, const DevBuf& in, const DevBuf& out, uint64_t n,
+                   unsigned long long* total64, hipStream_t s, unsigned long long total_tag)
+    {
+        VX_HIP(reserve(n, s));
+        return done(vx::launch_mip2_scan(m1, d1, d2, m2, in.as<uint32_t>(), out.as<uint32_t>(), n, block.p, total64, s, total_tag, next_gen(s)));
+    }
+    vx_status done(vx::ScanTaken t)
+    {
+        took = t;
+        return t != vx::ScanTaken::three_pass ? VX_OK : fail(VX_ERR_UNSUPPORTED, "internal: a scan on a handle's scratch took the three-pass path");
+    }
+};
 
 // A total that has arrived in the mailbox: the tag bits masked off, refused with the caller's message at 2^32 - 1 and above.
 vx_status mail_value(const volatile unsigned long long* word, const char* limit_message, uint64_t* out)
@@ -338,10 +363,10 @@ vx_status mail_value(const volatile unsigned long long* word, const char* limit_
     return VX_OK;
 }
 
-// A total the host waits for: a tagged one is polled for (5 ms at most), an untagged one -- or one that does not come -- waits for the stream.
-vx_status mail_total(const volatile unsigned long long* word, bool tagged, unsigned long long tag, hipStream_t s, const char* limit_message, uint64_t* out)
+// A total the host waits for: under its tag it is polled for (5 ms at most); tag 0 -- or a total that does not come -- waits for the stream.
+vx_status mail_total(const volatile unsigned long long* word, unsigned long long tag, hipStream_t s, const char* limit_message, uint64_t* out)
 {
-    if (!(tagged && mail_wait(word, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
+    if (!(tag && mail_wait(word, nullptr, tag, 5.0))) VX_HIP(hipStreamSynchronize(s));
     return mail_value(word, limit_message, out);
 }
 
@@ -359,7 +384,8 @@ struct SetupOpts {
 // The unit pipeline of a build (grids and the octree): triangle records, high bits of the candidate ranges, units per triangle and their
 // scan, the block table, per unit its hit mask, hits per block of 64 units and their exclusive scan, and the scratch of the scans.
 struct UnitPipe {
-    DevBuf recs, ext, units, ubase, btri, umask, bhits, hbase, scantmp;
+    DevBuf recs, ext, units, ubase, btri, umask, bhits, hbase;
+    ScanScratch scantmp;
     explicit UnitPipe(const Home* h) : recs(h), ext(h), units(h), ubase(h), btri(h), umask(h), bhits(h), hbase(h), scantmp(h) {}
     // what the launchers read; wide: an axis above 65535 cells, the unit kernels also read the extension words
     vx::Units view(uint32_t ntri, bool wide) const
@@ -375,7 +401,7 @@ struct UnitPipe {
     // The front half of buildVoxelGrid that grids and the octree share: records, unit counts, unit bases.  In two parts so that
     // the caller can queue work that does not depend on the unit count (clearing the bitmask) before the host waits for it.
     vx_status setup_launch(const vx_mesh* m, const vx::GridParams& g, int sat, uint64_t tb, uint32_t ntri, uint32_t zlo, uint32_t zhi, Mail* mail, hipStream_t s,
-                           const SetupOpts& o = SetupOpts(), bool* tagged = nullptr);
+                           const SetupOpts& o = SetupOpts());
     // btri_entries: entries of the block table a launch queued before the host knew the total has already filled (0: none)
     vx_status setup_finish(uint32_t ntri, Mail* mail, hipStream_t s, uint64_t* total_units, bool stream_is_drained = false, uint64_t btri_entries = 0);
 };
@@ -541,7 +567,8 @@ struct vx_grid : Home {
     DevBuf lcnt{this} /*set bits per 16-word line of the bitmask (the brick kernel of a whole Vec build): wp16 is their scan*/;
     DevBuf wring{this} /*k_walk's rank epilogue: per wave the chunks of rays it drew (walk_ring_cap words each); scratch of one ray batch*/;
     UnitPipe up{this};  // (its scantmp serves every scan on the main stream, the queries' too)
-    DevBuf hscantmp{this} /*status block of a block-hit scan queued with the list (list_scan)*/, small{this}, vec{this}, matids{this}, mattmp{this};
+    ScanScratch hscantmp{this};  // of a block-hit scan queued with the list (list_scan)
+    DevBuf small{this}, vec{this}, matids{this}, mattmp{this};
     // solid voxelization (vx_solid.hip): padded mask, exterior, H in the reference's layout (padded rows only) and the word prefix over H
     DevBuf solid_m{this}, solid_e{this}, solid_h{this}, solid_pre{this}, solid_agg{this} /*the column scans' per-chunk words*/;
     // distance fields (vx_distance.hip): the envelopes' stacks, and the field itself for the host variants
@@ -581,7 +608,7 @@ struct vx_grid : Home {
     uint64_t vec_count = 0;
     uint32_t mail_seq = 0;  // sequence tag of the totals the current build writes to the mailbox
     bool sel_valid = false;  // wsel belongs to the current word prefix
-    unsigned long long occ_tag = 0;  // tag of the word-prefix scan whose total (the occupied count) is in flight; 0: untagged
+    unsigned long long occ_tag = 0;  // tag of the scan whose total (the occupied count) is in flight; 0: none
     int trace_phase = 0;  // which of Small::trace_counters[0..1] the next ray launch draws its work from (the launch clears the other)
     // VX_GRID_VEC: the caller's own list buffer (vx_grid_bind_aabbs_device); builds emit straight into it when it is large enough
     vx_aabb* bound = nullptr;
@@ -618,10 +645,7 @@ struct vx_grid : Home {
     void list_scan(hipStream_t st)
     {
         if (ld.from_mask || !ld.scan_blocks) return;
-        vx::ScanArgs a;
-        a.tmp_is_zero = true;
-        a.gen = advance_scan_gen(hscantmp, st);
-        (void)vx::launch_scan_u32(up.bhits.as<uint32_t>(), up.hbase.as<uint32_t>(), ld.scan_blocks, false, hscantmp.p, nullptr, st, a);
+        (void)hscantmp.u32(up.bhits, up.hbase, ld.scan_blocks, false, nullptr, st);
         ld.scan_blocks = 0;
     }
     void list_emit(hipStream_t st)
@@ -844,22 +868,17 @@ void fill_params(vx::GridParams& g, const float org[3], float vs, const uint64_t
 constexpr uint64_t kMaxVoxels = 1ull << 37;  // 16 GiB of bitmask
 
 vx_status UnitPipe::setup_launch(const vx_mesh* m, const vx::GridParams& g, int sat, uint64_t tb, uint32_t ntri, uint32_t zlo, uint32_t zhi, Mail* mail, hipStream_t s,
-                                 const SetupOpts& o, bool* tagged)
+                                 const SetupOpts& o)
 {
     VX_HIP(recs.ensure((size_t)ntri * sizeof(vx::TriRec) + 64));
     VX_HIP(ext.ensure(((size_t)ntri + 1) * 4));  // high bits of the candidate ranges (read only when an axis has more than 65535 cells)
     VX_HIP(units.ensure(((size_t)ntri + 1) * 4));
     VX_HIP(ubase.ensure(((size_t)ntri + 2) * 4));
-    VX_HIP(ensure_scan_tmp(scantmp, vx::scan_tmp_bytes(ntri), s));  // (ahead of the record kernel, as ever: not scan_on)
+    VX_HIP(scantmp.reserve(ntri, s));  // (ahead of the record kernel, as ever)
     vx::launch_tri_setup(m->dv, m->di, tb, ntri, g, sat, zlo, zhi, recs.as<vx::TriRec>(), units.as<uint32_t>(), s, o.dgrid, o.clear, o.clear_bytes, o.shard_wb, o.shard_we,
                          ext.as<uint32_t>(), o.shard_rank, o.shard_world);
-    vx::ScanArgs a;
-    a.tmp_is_zero = true;
-    a.total_tag = o.tag;
-    a.gen = advance_scan_gen(scantmp, s);
-    const bool tg = vx::launch_scan_u32(units.as<uint32_t>(), ubase.as<uint32_t>(), ntri, false, scantmp.p, o.units_total ? o.units_total : &mail->units, s, a);
-    if (tagged) *tagged = tg && o.tag != 0;
-    return VX_OK;
+    // (o.tag == 0: the total carries no tag, its reader waits for the stream -- setup_finish)
+    return scantmp.u32(units, ubase, ntri, false, o.units_total ? o.units_total : &mail->units, s, {o.tag});
 }
 
 vx_status UnitPipe::setup_finish(uint32_t ntri, Mail* mail, hipStream_t s, uint64_t* total_units, bool stream_is_drained, uint64_t btri_entries)
@@ -867,7 +886,7 @@ vx_status UnitPipe::setup_finish(uint32_t ntri, Mail* mail, hipStream_t s, uint6
     const char* limit = "more than 2^32 candidate row segments: shard the mesh or the grid";
     uint64_t tot = 0;
     if (stream_is_drained) VX_TRY(mail_value(&mail->units, limit, &tot));
-    else VX_TRY(mail_total(&mail->units, false, 0, s, limit, &tot));
+    else VX_TRY(mail_total(&mail->units, 0, s, limit, &tot));
     *total_units = tot;
     if (tot && btri_entries < tot / 64 + 2) {
         VX_HIP(btri.ensure((size_t)(tot / 64 + 2) * 4));
@@ -885,27 +904,19 @@ unsigned long long next_tag(vx_grid* g)
 
 // word_prefix + occupied count.  Split in two so that callers can queue dependent kernels before the host waits for the
 // count (a host sync in front of a kernel leaves the GPU idle and the clocks down for its start).
-vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0, bool* tagged = nullptr)
+vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0)
 {
     *pending = !g->occupied_known;
-    if (tagged) *tagged = false;
     if (g->prefix_valid) return VX_OK;
     const bool count_known = g->p16_valid && g->occupied_known;  // (the line counts' scan gave the count already: nobody has to wait for this one's)
     if (!tag) tag = next_tag(g);  // a scan outside a build: its own sequence tag
     VX_HIP(g->wprefix.ensure((size_t)(g->g.nwords + 2) * 4));
     VX_HIP(g->wsel.ensure((size_t)(g->g.nwords / 32 + 4) * 4));  // at most 32 nwords / 1024 chunks of 1024 records
     VX_HIP(g->wp16.ensure((size_t)(g->g.nwords / 16 + 4) * 4));
-    vx::ScanArgs a;
-    a.total_tag = tag;
-    a.sel1024 = g->wsel.as<uint32_t>();
-    a.group16 = g->wp16.as<uint32_t>();
-    bool tg = false;
-    VX_TRY(scan_on(g->up.scantmp, g->stream, g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), g->g.nwords, true, &g->mail->occupied, a, &tg));
-    g->sel_valid = tg;  // (the three-pass scan writes neither wsel nor wp16)
-    if (tagged) *tagged = tg;
-    g->prefix_valid = true;
+    VX_TRY(g->up.scantmp.u32(g->words, g->wprefix, g->g.nwords, true, &g->mail->occupied, g->stream, {tag, g->wsel.as<uint32_t>(), g->wp16.as<uint32_t>()}));
+    g->prefix_valid = g->sel_valid = true;
     if (count_known) return VX_OK;
-    g->occ_tag = tg ? tag : 0;  // what the host may poll the mailbox for instead of draining the stream (prefix_finish)
+    g->occ_tag = tag;  // what the host polls the mailbox for instead of draining the stream (prefix_finish)
     g->occupied_known = false;
     *pending = true;
     return VX_OK;
@@ -917,17 +928,14 @@ vx_status prefix_launch(vx_grid* g, bool* pending, unsigned long long tag = 0, b
 // over nwords / 16 values instead of a pass that reads the mask again and writes nwords prefixes nobody on this path reads.
 // The level-2 mip, which like this scan reads only what the brick kernel wrote, shares the scan's launch (ensure_coarse calls this in place of
 // its own last kernel).
-vx_status p16_launch(vx_grid* g, unsigned long long tag, bool* tagged)
+vx_status p16_launch(vx_grid* g, unsigned long long tag)
 {
     const uint64_t nl = g->g.nwords / 16;
     VX_HIP(g->wp16.ensure((size_t)(nl + 4) * 4));
-    VX_HIP(ensure_scan_tmp(g->up.scantmp, vx::scan_tmp_bytes(nl), g->stream));
-    const bool tg = vx::launch_mip2_scan(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->lcnt.as<uint32_t>(), g->wp16.as<uint32_t>(), nl,
-                                         g->up.scantmp.p, &g->mail->occupied, g->stream, tag, advance_scan_gen(g->up.scantmp, g->stream));
-    *tagged = tg;
+    VX_TRY(g->up.scantmp.mip2(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->lcnt, g->wp16, nl, &g->mail->occupied, g->stream, tag));
     g->p16_valid = true;
     g->prefix_valid = g->sel_valid = false;  // (wprefix and wsel still describe an older mask)
-    g->occ_tag = tg ? tag : 0;
+    g->occ_tag = tag;
     g->occupied_known = false;
     return VX_OK;
 }
@@ -942,7 +950,7 @@ vx_status rank_launch(vx_grid* g, bool* pending)
 vx_status prefix_finish(vx_grid* g, bool pending)
 {
     if (!pending || g->occupied_known) return VX_OK;
-    VX_TRY(mail_total(&g->mail->occupied, g->occ_tag != 0, g->occ_tag, g->stream, "more than 2^32 occupied voxels", &g->occupied));
+    VX_TRY(mail_total(&g->mail->occupied, g->occ_tag, g->stream, "more than 2^32 occupied voxels", &g->occupied));
     g->occupied_known = true;
     return VX_OK;
 }
@@ -971,8 +979,7 @@ struct CoarseBuild {
     unsigned long long tag = 0;  // of the totals it posts
     bool post_hits = false;      // (with from_tiled) the brick kernel posts the voxelizer's hit count to mail->hits under `tag`
 };
-// *tagged (with line_counts): whether the occupied count carries the tag
-vx_status build_coarse(vx_grid* g, const CoarseBuild& c, bool* tagged)
+vx_status build_coarse(vx_grid* g, const CoarseBuild& c)
 {
     if (g->coarse_valid && !c.from_tiled) return VX_OK;
     DeviceGuard dg(g->device);
@@ -1000,14 +1007,14 @@ vx_status build_coarse(vx_grid* g, const CoarseBuild& c, bool* tagged)
     const bool fused = vx::launch_build_bricks3(g->words.as<uint32_t>(), g->g.dim, g->cdim, g->bricks.as<unsigned long long>(),
                                                 fuse_mip1 ? g->cwords.as<uint32_t>() : nullptr, g->stream, ba);
     if (!fused) vx::launch_brick_mip1(g->bricks.as<unsigned long long>() + 2ull * nc * 8ull, nc, g->cwords.as<uint32_t>(), g->stream);
-    if (c.from_tiled && c.line_counts) VX_TRY(p16_launch(g, c.tag, tagged));
+    if (c.from_tiled && c.line_counts) VX_TRY(p16_launch(g, c.tag));
     else vx::launch_build_mip2(g->cwords.as<uint32_t>(), g->cdim, g->c2dim, g->c2words.as<uint32_t>(), g->stream);
     g->coarse_valid = true;
     return VX_OK;
 }
 
 // the traversal structure of the grid's mask as it stands, built in front of the first query that needs it
-vx_status ensure_coarse(vx_grid* g) { return build_coarse(g, CoarseBuild(), nullptr); }
+vx_status ensure_coarse(vx_grid* g) { return build_coarse(g, CoarseBuild()); }
 
 vx_status sync_counts(vx_grid* g)
 {
@@ -1098,7 +1105,7 @@ vx_status solid_fill(vx_grid* g, uint64_t* n_interior, const uint32_t** h_words)
     }
     VX_HIP(g->solid_pre.ensure((size_t)(g->g.nwords + 2) * 4));
     VX_HIP(g->solid_agg.ensure((size_t)vx::solid_agg_words(dim) * 4 + 16));
-    VX_HIP(ensure_scan_tmp(g->up.scantmp, vx::scan_tmp_bytes(g->g.nwords), s));
+    VX_HIP(g->up.scantmp.reserve(g->g.nwords, s));  // (ahead of the seed)
     uint32_t* flags = g->small.as<Small>()->solid_flags;
     uint32_t* words = g->words.as<uint32_t>();
     const uint32_t* m = plan.padded ? g->solid_m.as<uint32_t>() : words;
@@ -1116,21 +1123,18 @@ vx_status solid_fill(vx_grid* g, uint64_t* n_interior, const uint32_t** h_words)
         const unsigned long long tag = next_tag(g);
         vx::launch_solid_report(flags + first, batch, &g->mail->solid_rounds, tag, s);
         uint64_t changed = 0;  // (at most `batch`)
-        VX_TRY(mail_total(&g->mail->solid_rounds, true, tag, s, "solid fill: round count out of range", &changed));
+        VX_TRY(mail_total(&g->mail->solid_rounds, tag, s, "solid fill: round count out of range", &changed));
         rounds += (uint32_t)changed;
         if (changed < batch) break;  // a quiet round: every round after it exited at once
         if (batch < 32) batch *= 2;
     }
     g->solid_rounds = rounds + 1;
-    uint32_t* h = plan.padded ? g->solid_h.as<uint32_t>() : ext;
-    vx::launch_solid_finish(words, g->solid_m.as<uint32_t>(), ext, h, dim, g->g.nwords, s);
-    vx::ScanArgs a;  // (the scratch was sized ahead of the seed, above: not scan_on)
-    a.tmp_is_zero = true;
-    a.total_tag = next_tag(g);
-    a.gen = advance_scan_gen(g->up.scantmp, s);
-    const bool tagged = vx::launch_scan_u32(h, g->solid_pre.as<uint32_t>(), g->g.nwords, true, g->up.scantmp.p, &g->mail->interior, s, a);
-    VX_TRY(mail_total(&g->mail->interior, tagged, a.total_tag, s, "more than 2^32 interior voxels", n_interior));
-    *h_words = h;
+    const DevBuf& h = plan.padded ? g->solid_h : g->solid_e;
+    vx::launch_solid_finish(words, g->solid_m.as<uint32_t>(), ext, h.as<uint32_t>(), dim, g->g.nwords, s);
+    const unsigned long long tag = next_tag(g);
+    VX_TRY(g->up.scantmp.u32(h, g->solid_pre, g->g.nwords, true, &g->mail->interior, s, {tag}));
+    VX_TRY(mail_total(&g->mail->interior, tag, s, "more than 2^32 interior voxels", n_interior));
+    *h_words = h.as<uint32_t>();
     return VX_OK;
 }
 
@@ -1385,11 +1389,11 @@ struct Build {
     uint64_t wb = 0, we = 0;  // the words this build owns
     bool whole_words = false, whole_build = false, tiled = false, untile_in_bricks = false, defer_scan = false, lines = false;
     bool wide = false;  // an axis above 65535 cells: the unit kernels also read the extension words of the candidate ranges
-    // queued and tagged
+    // queued
     uint64_t U = 0, nUB = 0;  // units, blocks of 64 units
     uint32_t* umask = nullptr;
     uint32_t* bhits = nullptr;
-    bool hits_tagged = false, occ_tagged = false, occ_queued = false;
+    bool occ_queued = false;  // this build queued the scan that posts the occupied count under mtag
     uint64_t n_interior = 0;
     const uint32_t* h_words = nullptr;
 };
@@ -1429,7 +1433,7 @@ static void build_plan_args(vx_grid* g, const vx_mesh* mesh, Build& b)
 // behind it and the host waits ONCE for the bbox and the unit count (every host round trip costs ~20 us of idle GPU: the
 // wake-up plus the launch latency of an empty queue).  The bitmask of the previous build is cleared in the same window.
 // (a word shard's z slab is derived from the device-side dims by the record kernel itself)
-static vx_status build_front_queue(vx_grid* g, vx_mesh* mesh, Build& b, bool* units_tagged)
+static vx_status build_front_queue(vx_grid* g, vx_mesh* mesh, Build& b)
 {
     const vx_voxelize_opts& o = *b.o;
     Small* ds = g->small.as<Small>();
@@ -1461,7 +1465,7 @@ static vx_status build_front_queue(vx_grid* g, vx_mesh* mesh, Build& b, bool* un
         so.shard_world = (uint32_t)o.shard_world;
     }
     if (b.early) so.units_total = &ds->units64;
-    VX_TRY(up.setup_launch(mesh, gp, o.sat_variant, b.tb, b.ntri, 0, 0, g->mail.get(), b.s, so, units_tagged));
+    VX_TRY(up.setup_launch(mesh, gp, o.sat_variant, b.tb, b.ntri, 0, 0, g->mail.get(), b.s, so));
     if (clear_in_setup) b.cleared = cb.cap;
     // the block table of the units: queued now, for as many blocks as the handle's table from the previous build holds, so that
     // it runs while the host waits for the unit total (redone by setup_finish should the table turn out too small)
@@ -1493,16 +1497,13 @@ static vx_status build_front_queue(vx_grid* g, vx_mesh* mesh, Build& b, bool* un
 static vx_status build_front(vx_grid* g, vx_mesh* mesh, Build& b)
 {
     if (b.ntri > 0) {
-        bool units_tagged = false;
-        VX_TRY(build_front_queue(g, mesh, b, &units_tagged));
-        if (b.early && units_tagged) {
+        VX_TRY(build_front_queue(g, mesh, b));
+        if (b.early) {
             if (!mail_wait(&g->mail->bbox_tag, nullptr, b.mtag, 5.0)) VX_HIP(hipStreamSynchronize(b.s));
             std::atomic_thread_fence(std::memory_order_acquire);
         } else {
             // the bbox (written by k_bbox, two kernels earlier) and the unit total: polled from the mailbox, see the hit count below
-            // (an untagged total on its way through device memory: the drained stream has forwarded it)
-            if (!(units_tagged && !b.early && mail_wait(&g->mail->units, nullptr, b.mtag, 5.0))) VX_HIP(hipStreamSynchronize(b.s));
-            b.early = false;
+            if (!mail_wait(&g->mail->units, nullptr, b.mtag, 5.0)) VX_HIP(hipStreamSynchronize(b.s));
         }
         VX_TRY(extent_from_bbox(g->mail->bbox, mesh->nv, b.vs, &b.ex));
         b.setup_queued = true;
@@ -1645,12 +1646,9 @@ static vx_status build_voxelize(vx_grid* g, vx_mesh*, Build& b)
     if (b.tiled && !b.untile_in_bricks) vx::launch_untile(g->twords.as<uint32_t>(), g->words.as<uint32_t>(), g->g.dim, s, b.wb, b.we);
     g->counts_valid = false;
     if (b.defer_scan) {
-        VX_HIP(ensure_scan_tmp(g->hscantmp, vx::scan_tmp_bytes(b.nUB), s));  // (the scan itself: list_scan)
-        b.hits_tagged = true;
+        VX_HIP(g->hscantmp.reserve(b.nUB, s));  // (the scan itself: list_scan)
     } else if (g->kind == VX_GRID_VEC) {
-        vx::ScanArgs a;
-        a.total_tag = b.mtag;
-        VX_TRY(scan_on(up.scantmp, s, b.bhits, up.hbase.as<uint32_t>(), b.nUB, false, &g->mail->hits, a, &b.hits_tagged));
+        VX_TRY(up.scantmp.u32(up.bhits, up.hbase, b.nUB, false, &g->mail->hits, s, {b.mtag}));
     }
     // VX_VOXELIZE_SOLID: the second loop -- setVoxel on every interior cell in ascending order -- once the surface mask is complete
     if (b.solid) {
@@ -1675,22 +1673,21 @@ static vx_status build_structure(vx_grid* g, vx_mesh*, Build& b)
     c.line_counts = b.lines;
     c.tag = b.mtag;
     c.post_hits = b.defer_scan;
-    VX_TRY(build_coarse(g, c, &b.occ_tagged));
+    VX_TRY(build_coarse(g, c));
     if (b.lines) {
         b.occ_queued = true;
     } else {
         bool pending = false;
         b.occ_queued = !g->prefix_valid;
-        VX_TRY(prefix_launch(g, &pending, b.mtag, &b.occ_tagged));
+        VX_TRY(prefix_launch(g, &pending, b.mtag));
     }
     return VX_OK;
 }
 
 // 7a. The host needs the hit count (and takes the occupied count along).  Both are written by scans -- the hit count of a build that
 // left its block-hit scan to the list (defer_scan) by the brick kernel, from the voxelizer's counters -- that run BEFORE the
-// emission: the host polls the tagged mailbox words and goes on queueing work (the caller's next call: a trace) while
-// the emission still runs; a stream synchronize would wake it ~15 us after the last kernel.  An untagged total
-// (three-pass scan) or 5 ms without an answer: the synchronize.
+// emission: the host polls the mailbox words for the build's tag and goes on queueing work (the caller's next call: a trace) while
+// the emission still runs; a stream synchronize would wake it ~15 us after the last kernel.  5 ms without an answer: the synchronize.
 // VX_VOXELIZE_LIST_ASYNC: only the hit count -- its scan runs in front of the traversal structure and the word prefix, so the host
 // is back in the caller ~40 us of GPU work before the build ends and the caller's ray batch is queued in time; the occupied count
 // (the LAST kernel's total) is fetched when somebody asks for it (prefix_finish).
@@ -1699,10 +1696,9 @@ static vx_status build_list_wait(vx_grid* g, Build& b, uint64_t* hits, uint64_t*
 {
     hipStream_t s = b.s;
     const bool occ_in_flight = (g->prefix_valid || g->p16_valid) && !g->occupied_known;
-    const bool occ_along = occ_in_flight && !(b.list_async && b.occ_queued && b.occ_tagged);
-    bool got = false;
-    if (b.hits_tagged && (!occ_along || (b.occ_queued && b.occ_tagged)))
-        got = mail_wait(&g->mail->hits, occ_along ? &g->mail->occupied : nullptr, b.mtag, 5.0);
+    const bool occ_along = occ_in_flight && !(b.list_async && b.occ_queued);
+    bool got = false;  // (an occupied count in flight that this build did not queue carries another tag: the stream is drained for it)
+    if (!occ_along || b.occ_queued) got = mail_wait(&g->mail->hits, occ_along ? &g->mail->occupied : nullptr, b.mtag, 5.0);
     if (!got) VX_HIP(hipStreamSynchronize(s));
     *units_known = b.U;
     if (b.early) {
@@ -2770,22 +2766,17 @@ static vx_status surface_count(vx_grid* g, bool want_mat, uint64_t* nv, uint64_t
     VX_HIP(g->surf_tpre.ensure((size_t)(g->g.nwords + 4) * 4));
     VX_HIP(g->surf_cm.ensure((size_t)(p.nlw + 4) * 4));
     VX_HIP(g->surf_vpre.ensure((size_t)(p.nlw + 4) * 4));
-    VX_HIP(ensure_scan_tmp(g->up.scantmp, vx::scan_tmp_bytes(nmax), g->stream));
+    VX_HIP(g->up.scantmp.reserve(nmax, g->stream));  // (one scratch block for both scans, sized ahead of the count kernel)
     bool pending = false;
     if (want_mat) VX_TRY(prefix_launch(g, &pending));
     vx::launch_surface_count(g->words.as<uint32_t>(), g->g, p, g->surf_cnt.as<uint32_t>(), g->surf_cm.as<uint32_t>(), g->stream);
-    // (one scratch block for both scans, sized ahead of the count kernel: not scan_on)
-    vx::ScanArgs a;
-    a.tmp_is_zero = true;
-    a.gen = advance_scan_gen(g->up.scantmp, g->stream);
-    vx::launch_scan_u32(g->surf_cnt.as<uint32_t>(), g->surf_tpre.as<uint32_t>(), g->g.nwords, false, g->up.scantmp.p, &g->mail->surf_tris, g->stream, a);
-    a.gen = advance_scan_gen(g->up.scantmp, g->stream);
-    vx::launch_scan_u32(g->surf_cm.as<uint32_t>(), g->surf_vpre.as<uint32_t>(), p.nlw, true, g->up.scantmp.p, &g->mail->surf_verts, g->stream, a);
+    VX_TRY(g->up.scantmp.u32(g->surf_cnt, g->surf_tpre, g->g.nwords, false, &g->mail->surf_tris, g->stream));
+    VX_TRY(g->up.scantmp.u32(g->surf_cm, g->surf_vpre, p.nlw, true, &g->mail->surf_verts, g->stream));
     VX_HIP(hipGetLastError());
     // (one wait for both totals; beyond 2^32 - 1 they are refused as surface_check refuses them)
     const char* limit = "surface mesh above 2^31 - 1 vertices or triangles (int32 indices)";
     uint64_t tris = 0, verts = 0;
-    VX_TRY(mail_total(&g->mail->surf_tris, false, 0, g->stream, limit, &tris));
+    VX_TRY(mail_total(&g->mail->surf_tris, 0, g->stream, limit, &tris));
     VX_TRY(mail_value(&g->mail->surf_verts, limit, &verts));
     VX_TRY(prefix_finish(g, pending));
     if (want_mat && g->occupied > (g->mat_gathered ? g->mat_gather_count : g->mat_count))
@@ -2959,12 +2950,9 @@ static vx_status components_queue(vx_grid* g, uint32_t connectivity, uint32_t* l
 {
     VX_HIP(g->cc_roots.ensure((size_t)(g->g.nwords + 4) * 4));
     VX_HIP(g->cc_rpre.ensure((size_t)(g->g.nwords + 4) * 4));
-    VX_HIP(ensure_scan_tmp(g->up.scantmp, vx::scan_tmp_bytes(g->g.nwords), g->stream));
+    VX_HIP(g->up.scantmp.reserve(g->g.nwords, g->stream));  // (ahead of the union-find kernel)
     vx::launch_components(g->words.as<uint32_t>(), g->g, connectivity == VX_CONNECT_26, labels, g->cc_roots.as<uint32_t>(), g->stream);
-    vx::ScanArgs a;  // (the scratch is sized ahead of the union-find kernel: not scan_on)
-    a.tmp_is_zero = true;
-    a.gen = advance_scan_gen(g->up.scantmp, g->stream);
-    vx::launch_scan_u32(g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), g->g.nwords, true, g->up.scantmp.p, &g->mail->cc_count, g->stream, a);
+    VX_TRY(g->up.scantmp.u32(g->cc_roots, g->cc_rpre, g->g.nwords, true, &g->mail->cc_count, g->stream));
     vx::launch_components_label(g->words.as<uint32_t>(), g->g, labels, g->cc_roots.as<uint32_t>(), g->cc_rpre.as<uint32_t>(), dev_count, g->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
@@ -2976,7 +2964,7 @@ static vx_status components_host(vx_grid* g, uint32_t connectivity, uint32_t* ho
     VX_HIP(g->cc_lab.ensure((size_t)g->g.nvox * 4));
     VX_TRY(components_queue(g, connectivity, g->cc_lab.as<uint32_t>(), nullptr));
     if (host_labels) VX_HIP(hipMemcpyAsync(host_labels, g->cc_lab.p, (size_t)g->g.nvox * 4, hipMemcpyDeviceToHost, g->stream));
-    return mail_total(&g->mail->cc_count, false, 0, g->stream, "components need X*Y*Z <= 2^32 - 1 (32-bit labels and union-find indices)", k);
+    return mail_total(&g->mail->cc_count, 0, g->stream, "components need X*Y*Z <= 2^32 - 1 (32-bit labels and union-find indices)", k);
 }
 
 vx_status vx_grid_components_device(const vx_grid* gc, uint32_t connectivity, uint32_t* dev_labels, uint64_t capacity, uint32_t* dev_count)
@@ -3192,7 +3180,7 @@ void vx_grid_free(vx_grid* g)
 
 // ---- rays -----------------------------------------------------------------------------------------------------
 // the grid's traversal structure as launch_trace takes it; *p16: the 16th-prefix table of the word prefix for the rank pass, null where it
-// cannot be used (a three-pass scan wrote none; the mask is allocated with two spare words, so a rank may read its voxel's whole
+// cannot be used (no scan on the stream has written it; the mask is allocated with two spare words, so a rank may read its voxel's whole
 // 16-word group only when that lies inside: nwords % 16 == 0)
 static vx::TraceMips grid_mips(const vx_grid* g, const uint32_t** p16)
 {
@@ -3600,15 +3588,12 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
         const uint64_t nUB = (U + 63) / 64;  // hits per block of 64 units from the voxelizer, scanned: the items' positions (as for the Vec grid)
         VX_HIP(up.bhits.ensure((size_t)(nUB + 4) * 4));
         VX_HIP(up.hbase.ensure((size_t)(nUB + 4) * 4));
-        VX_HIP(ensure_scan_tmp(up.scantmp, vx::scan_tmp_bytes(nUB), s));  // (ahead of the voxelizer: not scan_on)
+        VX_HIP(up.scantmp.reserve(nUB, s));  // (ahead of the voxelizer)
         vx::VoxelizeArgs va;
         va.block_hits = up.bhits.as<uint32_t>();
         vx::launch_voxelize(up.view(ntri, wide), g, 0, nullptr, 0, 0, up.umask.as<uint32_t>(), ds->set_calls, s, va);
-        vx::ScanArgs sa;
-        sa.tmp_is_zero = true;
-        sa.gen = advance_scan_gen(up.scantmp, s);
-        vx::launch_scan_u32(up.bhits.as<uint32_t>(), up.hbase.as<uint32_t>(), nUB, false, up.scantmp.p, &mail->hits, s, sa);
-        VX_TRY(mail_total(&mail->hits, false, 0, s, "more than 2^32 octree items", &hits));
+        VX_TRY(up.scantmp.u32(up.bhits, up.hbase, nUB, false, &mail->hits, s));
+        VX_TRY(mail_total(&mail->hits, 0, s, "more than 2^32 octree items", &hits));
     }
     o->nitems = hits;
     if (hits) {
@@ -3627,11 +3612,11 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
         const uint32_t ni = (uint32_t)hits;
         VX_HIP(ncount.ensure((size_t)ni + 16));
         VX_HIP(nbase.ensure(((size_t)ni + 2) * 4));
-        VX_HIP(ensure_scan_tmp(up.scantmp, vx::scan_tmp_bytes(ni), s));
+        VX_HIP(up.scantmp.reserve(ni, s));  // (ahead of the depth kernel)
         vx::launch_oct_depths(o->items.as<uint64_t>(), ni, o->bits, (uint32_t)max_items, ncount.as<uint8_t>(), s);
-        vx::launch_scan_u8(ncount.as<uint8_t>(), nbase.as<uint32_t>(), ni, up.scantmp.p, &mail->occupied, s, 0, advance_scan_gen(up.scantmp, s));
+        VX_TRY(up.scantmp.u8(ncount, nbase, ni, &mail->occupied, s));
         uint64_t nn = 0;
-        VX_TRY(mail_total(&mail->occupied, false, 0, s, "more than 2^32 octree nodes", &nn));
+        VX_TRY(mail_total(&mail->occupied, 0, s, "more than 2^32 octree nodes", &nn));
         if (nn == 0) return fail(VX_ERR_CAPACITY, "more than 2^32 octree nodes");
         VX_HIP(o->nodebuf.ensure((size_t)nn * sizeof(vx_octree_node)));
         o->dnodes = o->nodebuf.as<vx_octree_node>();
@@ -4860,7 +4845,8 @@ vx_status vx_scan_u32(const vx_scan_args* a)
     DeviceGuard dg(g_device);
     hipStream_t s = nullptr;
     const Home here(g_device, s, /*drained=*/true);  // (every scan below is waited for before the next step)
-    DevBuf din{&here}, dout{&here}, dsel{&here}, dg16{&here}, tmp{&here}, dtot{&here};
+    DevBuf din{&here}, dout{&here}, dsel{&here}, dg16{&here}, dtot{&here};
+    ScanScratch tmp{&here};
     const uint64_t out_words = a->out_offset + nmax + 1 + VX_SCAN_CANARY;
     const uint64_t sel_cap = a->sel ? a->sel_cap : 0, g16_cap = a->group16 ? a->group16_cap : 0;
     std::vector<uint32_t> canary(std::max<uint64_t>(std::max(out_words, sel_cap), g16_cap), VX_SCAN_CANARY_VALUE);
@@ -4869,9 +4855,9 @@ vx_status vx_scan_u32(const vx_scan_args* a)
     VX_HIP(dsel.ensure((size_t)sel_cap * 4 + 4));
     VX_HIP(dg16.ensure((size_t)g16_cap * 4 + 4));
     VX_HIP(dtot.ensure(8));
-    VX_HIP(ensure_scan_tmp(tmp, vx::scan_tmp_bytes(nmax), s));
-    std::vector<unsigned long long> state(tmp.cap / sizeof(unsigned long long));
-    tmp.scan_gen = a->gen_start;
+    VX_HIP(tmp.reserve(nmax, s));
+    std::vector<unsigned long long> state(tmp.block.cap / sizeof(unsigned long long));
+    tmp.start_at(a->gen_start);
     bool zero = true;  // the scratch block is known to be all zero (what ticket-mode and three-pass scans require and leave behind)
     uint64_t ioff = 0, ooff = 0;
     for (uint32_t k = 0; k < a->nscans; ++k) {
@@ -4884,35 +4870,39 @@ vx_status vx_scan_u32(const vx_scan_args* a)
         if (g16) VX_HIP(hipMemcpy(g16, canary.data(), (size_t)g16_cap * 4, hipMemcpyHostToDevice));
         if (n) VX_HIP(hipMemcpy((char*)din.p + a->in_offset * esz, (const char*)a->in + ioff * esz, (size_t)n * esz, hipMemcpyHostToDevice));
         VX_HIP(hipMemset(dtot.p, 0, 8));
-        // the path: GEN = the next generation of the block (ticket mode above kScanGenTiles tiles, as for every library caller);
+        // the path: GEN / AUTO = what the library's own callers do, the next generation of the block (ticket mode above kScanGenTiles tiles):
+        // through ScanScratch where in and out start their blocks, as theirs do;
         // TICKET / THREE = no generation, on a block that is all zero (cleared first when an older generation-mode scan left words);
-        // AUTO = what the library's own callers do (the next generation, kScanPathAuto)
+        // those and offset starts go to the launchers directly
         const uint32_t p = a->paths[k];
-        const uint32_t gen = (p == VX_SCAN_PATH_GEN || p == VX_SCAN_PATH_AUTO) ? advance_scan_gen(tmp, s) : 0u;
-        const int lp = p == VX_SCAN_PATH_THREE ? vx::kScanPathThree : p == VX_SCAN_PATH_AUTO ? vx::kScanPathAuto : vx::kScanPathOne;
-        if (!gen && !zero) (void)hipMemsetAsync(tmp.p, 0, tmp.cap, s);
-        const bool tz = true;
-        bool one;
-        if (a->mode == VX_SCAN_BYTES) {
-            vx::launch_scan_u8((const uint8_t*)din.p + a->in_offset, out, n, tmp.p, dtot.as<unsigned long long>(), s, a->total_tag, gen);
-            one = true;
+        const bool numbered = p == VX_SCAN_PATH_GEN || p == VX_SCAN_PATH_AUTO;
+        vx::ScanTaken took;
+        if (numbered && !a->in_offset && !a->out_offset) {
+            if (a->mode == VX_SCAN_BYTES) VX_TRY(tmp.u8(din, dout, n, dtot.as<unsigned long long>(), s, a->total_tag));
+            else VX_TRY(tmp.u32(din, dout, n, a->mode == VX_SCAN_POPCOUNT, dtot.as<unsigned long long>(), s, {a->total_tag, sel, g16}));
+            took = tmp.took;
         } else {
-            vx::ScanArgs sa;
-            sa.tmp_is_zero = tz;
-            sa.total_tag = a->total_tag;
-            sa.sel1024 = sel;
-            sa.gen = gen;
-            sa.group16 = g16;
-            sa.path = lp;
-            one = vx::launch_scan_u32(din.as<uint32_t>() + a->in_offset, out, n, a->mode == VX_SCAN_POPCOUNT, tmp.p, dtot.as<unsigned long long>(), s, sa);
+            const uint32_t gen = numbered ? tmp.next_gen(s) : 0u;
+            if (!gen && !zero) (void)hipMemsetAsync(tmp.block.p, 0, tmp.block.cap, s);
+            if (a->mode == VX_SCAN_BYTES) {
+                took = vx::launch_scan_u8((const uint8_t*)din.p + a->in_offset, out, n, tmp.block.p, dtot.as<unsigned long long>(), s, a->total_tag, gen);
+            } else {
+                vx::ScanArgs sa;
+                sa.tmp_is_zero = true;
+                sa.total_tag = a->total_tag;
+                sa.sel1024 = sel;
+                sa.gen = gen;
+                sa.group16 = g16;
+                sa.path = p == VX_SCAN_PATH_THREE ? vx::kScanPathThree : p == VX_SCAN_PATH_AUTO ? vx::kScanPathAuto : vx::kScanPathOne;
+                took = vx::launch_scan_u32(din.as<uint32_t>() + a->in_offset, out, n, a->mode == VX_SCAN_POPCOUNT, tmp.block.p, dtot.as<unsigned long long>(), s, sa);
+            }
         }
-        const bool gen_mode = one && gen && (n + 1 + 16383) / 16384 <= 512;  // (kScanGenTiles tiles of 16384)
         VX_HIP(hipStreamSynchronize(s));
         VX_HIP(hipMemcpy(a->out + ooff, out, (size_t)(n + 1 + VX_SCAN_CANARY) * 4, hipMemcpyDeviceToHost));
         VX_HIP(hipMemcpy(&a->totals[k], dtot.p, 8, hipMemcpyDeviceToHost));
         if (sel) VX_HIP(hipMemcpy(a->sel + (size_t)k * sel_cap, sel, (size_t)sel_cap * 4, hipMemcpyDeviceToHost));
         if (g16) VX_HIP(hipMemcpy(a->group16 + (size_t)k * g16_cap, g16, (size_t)g16_cap * 4, hipMemcpyDeviceToHost));
-        VX_HIP(hipMemcpy(state.data(), tmp.p, state.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        VX_HIP(hipMemcpy(state.data(), tmp.block.p, state.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         // clean: a scan without a generation number leaves the block all zero; one with a generation number leaves the ticket and the
         // finished-tiles words zero and state words of its own or an older generation only, never of a later one (which a later scan
         // would take for its own)
@@ -4922,11 +4912,11 @@ vx_status vx_scan_u32(const vx_scan_args* a)
             if (!w) continue;
             all_zero = false;
             const unsigned long long wg = (w >> 40) & ((1ull << 22) - 1ull);
-            if (i < 2 || (w >> 62) == 0 || wg == 0 || wg > tmp.scan_gen) ok = false;
+            if (i < 2 || (w >> 62) == 0 || wg == 0 || wg > tmp.gen) ok = false;
         }
-        if (!gen && !all_zero) ok = false;
+        if (!numbered && !all_zero) ok = false;
         if (a->clean) a->clean[k] = ok ? 1u : 0u;
-        if (a->taken) a->taken[k] = !one ? VX_SCAN_PATH_THREE : gen_mode ? VX_SCAN_PATH_GEN : VX_SCAN_PATH_TICKET;
+        if (a->taken) a->taken[k] = took == vx::ScanTaken::three_pass ? VX_SCAN_PATH_THREE : took == vx::ScanTaken::generation ? VX_SCAN_PATH_GEN : VX_SCAN_PATH_TICKET;
         zero = all_zero;
         ioff += n;
         ooff += n + 1 + VX_SCAN_CANARY;

@@ -86,7 +86,7 @@ constexpr int kScanPathAuto = 0, kScanPathOne = 1, kScanPathThree = 2;
 struct ScanArgs {
     bool tmp_is_zero = false;          // the caller guarantees tmp (scan_tmp_bytes(n)) is all zero; the scan leaves it all zero again
     // (bits 48..63 only) OR-ed into *total64 by the single-pass kernel, so that a host polling a pinned mailbox word can tell this scan's
-    // total from an older one; the launcher returns whether the tag was applied (false: the three-pass path, *total64 is the bare total)
+    // total from an older one (the three-pass path applies no tag: *total64 is the bare total)
     unsigned long long total_tag = 0;
     uint32_t* sel1024 = nullptr;       // optional (single-pass kernel only, values <= 1024): sel1024[c] = the element whose range holds c * 1024
     uint32_t gen = 0;                  // generation mode (vx_kernels.hip): the number of this scan on `tmp`, 1, 2, 3 ... < 2^22; 0 = tickets + self-cleaning state
@@ -94,14 +94,16 @@ struct ScanArgs {
                                        // enough to stay in L2 for readers that gather (k_rank)
     int path = kScanPathAuto;
 };
-bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp, unsigned long long* total64, hipStream_t s,
-                     const ScanArgs& a = ScanArgs());
+// what a launcher answers: the path the scan took (three_pass: no tag in *total64, no sel1024 / group16 output)
+enum class ScanTaken { three_pass, ticket, generation };
+ScanTaken launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp, unsigned long long* total64, hipStream_t s,
+                          const ScanArgs& a = ScanArgs());
 
 // clears the bits past nvox in the last word of a bitmask of nvox cells (nothing to do when nvox is a multiple of 32)
 void launch_mask_tail(uint32_t* words, uint64_t nvox, hipStream_t s);
 
-void launch_scan_u8(const uint8_t* in, uint32_t* out, uint64_t n, void* tmp /*scan_tmp_bytes(n), all zero*/, unsigned long long* total64, hipStream_t s,
-                    unsigned long long total_tag = 0, uint32_t gen = 0);
+ScanTaken launch_scan_u8(const uint8_t* in, uint32_t* out, uint64_t n, void* tmp /*scan_tmp_bytes(n), all zero*/, unsigned long long* total64, hipStream_t s,
+                         unsigned long long total_tag = 0, uint32_t gen = 0);
 
 // The unit pipeline as its readers see it: k_tri_setup's records, the exclusive scan of the unit counts (ntri + 1 entries), per 256-unit
 // block the triangle of its first unit (launch_unit_blocks; enables LDS staging) and the extension words of the candidate ranges (null
@@ -180,8 +182,8 @@ bool launch_build_bricks3(const uint32_t* words, const uint32_t dim[3], const ui
 void launch_brick_mip1(const unsigned long long* bricks_z /*orientation 2*/, uint64_t nbricks, uint32_t* m1, hipStream_t s);
 void launch_build_mip2(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, hipStream_t s);
 // the level-2 mip and the exclusive scan of n uint32 (launch_scan_u32 on a generation-managed, zero-between-scans tmp) in one launch
-bool launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, const uint32_t* in, uint32_t* out, uint64_t n, void* tmp,
-                      unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen);
+ScanTaken launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, const uint32_t* in, uint32_t* out, uint64_t n, void* tmp,
+                           unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen);
 struct TraceMips {
     const unsigned long long* bricks3;
     const uint32_t* w0;                // the reference-layout bitmask (primitive rank only)

@@ -496,24 +496,34 @@ __global__ __launch_bounds__(kOneBlock) void k_scan_onepass(const uint32_t* __re
 
 size_t scan_tmp_bytes(uint64_t n) { return (size_t)(((n + 1) + kScanTile - 1) / kScanTile + 4) * sizeof(unsigned long long); }
 
-// *total64: see THE TOTAL above (the exact range, the saturation at 2^40 - 1 and the tag bits).
-bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp, unsigned long long* total64, hipStream_t s, const ScanArgs& a)
+// The single-pass scan's mode, decided in one place for the three launchers: generation mode for a numbered scan whose workgroups are all
+// resident -- its tiles and the `extra` ones in front of them (k_mip2_scan's mip) -- else tickets, behind a clear of the status words unless
+// they are known to be zero (the caller vouches for tmp and does not number its scans, whose words would remain).
+struct ScanMode {
+    uint32_t ntiles, gen;  // (gen: what the kernel gets, 0 = tickets)
+    ScanTaken taken() const { return gen ? ScanTaken::generation : ScanTaken::ticket; }
+};
+static ScanMode scan_begin(void* tmp, uint64_t n, uint32_t gen, bool tmp_is_zero, uint64_t extra, hipStream_t s)
 {
-    const bool tmp_is_zero = a.tmp_is_zero;
-    const uint32_t gen = a.gen;
+    ScanMode m;
+    m.ntiles = (uint32_t)(((n + 1) + kOneTile - 1) / kOneTile);
+    m.gen = (gen && extra + m.ntiles <= kScanGenTiles) ? gen : 0u;
+    if (!m.gen && (!tmp_is_zero || gen)) (void)hipMemsetAsync(tmp, 0, (size_t)(m.ntiles + 2) * sizeof(unsigned long long), s);
+    return m;
+}
+
+// *total64: see THE TOTAL above (the exact range, the saturation at 2^40 - 1 and the tag bits).
+ScanTaken launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcount_input, void* tmp, unsigned long long* total64, hipStream_t s, const ScanArgs& a)
+{
     const uint32_t nblocks = (uint32_t)(((n + 1) + kScanTile - 1) / kScanTile);
     unsigned long long* status = (unsigned long long*)tmp;
     const bool three_pass = a.path == kScanPathThree;
     const bool aligned = ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;  // the single-pass kernel moves 16-byte vectors
     if (!three_pass && aligned) {
-        const uint32_t ntiles = (uint32_t)(((n + 1) + kOneTile - 1) / kOneTile);
-        // generation mode: small scans only (every tile resident).  A larger scan on a generation-managed buffer clears its state words
-        // first (they hold older scans' words) and runs with tickets, which leaves them zero again.
-        const uint32_t g = (gen && ntiles <= kScanGenTiles) ? gen : 0u;
-        if (!g && (!tmp_is_zero || gen)) (void)hipMemsetAsync(status, 0, (size_t)(ntiles + 2) * sizeof(unsigned long long), s);
-        if (popcount_input) VX_KL(k_scan_onepass<1>, dim3(ntiles), dim3(kOneBlock), 0, s, in, out, n, status, ntiles, total64, a.total_tag, a.sel1024, g, a.group16);
-        else VX_KL(k_scan_onepass<0>, dim3(ntiles), dim3(kOneBlock), 0, s, in, out, n, status, ntiles, total64, a.total_tag, a.sel1024, g, a.group16);
-        return true;
+        const ScanMode m = scan_begin(tmp, n, a.gen, a.tmp_is_zero, 0, s);
+        if (popcount_input) VX_KL(k_scan_onepass<1>, dim3(m.ntiles), dim3(kOneBlock), 0, s, in, out, n, status, m.ntiles, total64, a.total_tag, a.sel1024, m.gen, a.group16);
+        else VX_KL(k_scan_onepass<0>, dim3(m.ntiles), dim3(kOneBlock), 0, s, in, out, n, status, m.ntiles, total64, a.total_tag, a.sel1024, m.gen, a.group16);
+        return m.taken();
     }
     unsigned long long* sums = status;
     if (popcount_input) {
@@ -525,8 +535,8 @@ bool launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool popcoun
         VX_KL(k_scan_spine, dim3(1), dim3(1024), 0, s, sums, nblocks, total64);
         VX_KL(k_scan_apply<false>, dim3(nblocks), dim3(kScanBlock), 0, s, in, out, n, sums);
     }
-    if (tmp_is_zero || gen) (void)hipMemsetAsync(status, 0, scan_tmp_bytes(n), s);  // keep the caller's "zero between scans" contract (no stale words either)
-    return false;  // (*total64 carries no tag)
+    if (a.tmp_is_zero || a.gen) (void)hipMemsetAsync(status, 0, scan_tmp_bytes(n), s);  // keep the caller's "zero between scans" contract (no stale words either)
+    return ScanTaken::three_pass;  // (*total64 carries no tag)
 }
 
 // Level-2 mip of the traversal structure (vx_walk.hip): one bit per 8x8x8 bricks.  One workgroup per OUTPUT WORD (32 blocks: 16 waves x 2),
@@ -594,9 +604,9 @@ __global__ __launch_bounds__(kOneBlock) void k_mip2_scan(const uint32_t* __restr
 }
 
 // launch_build_mip2 + launch_scan_u32(in, out, n, values, generation-managed tmp) as one launch where the single-pass scan applies; returns
-// what the scan returns (whether *total64 carries the tag)
-bool launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, const uint32_t* in, uint32_t* out, uint64_t n, void* tmp,
-                      unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen)
+// what the scan returns (the path it took)
+ScanTaken launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, const uint32_t* in, uint32_t* out, uint64_t n, void* tmp,
+                           unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen)
 {
     const uint64_t n_mip = ((uint64_t)d2[0] * d2[1] * d2[2] + 31) / 32;
     const uint64_t ntiles = ((n + 1) + kOneTile - 1) / kOneTile;
@@ -609,12 +619,10 @@ bool launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d
         a.gen = gen;
         return launch_scan_u32(in, out, n, false, tmp, total64, s, a);
     }
-    // generation mode as in launch_scan_u32, with the mip's workgroups counted among the resident ones
-    const uint32_t g = n_mip + ntiles <= kScanGenTiles ? gen : 0u;
-    if (!g) (void)hipMemsetAsync(tmp, 0, (size_t)(ntiles + 2) * sizeof(unsigned long long), s);
+    const ScanMode m = scan_begin(tmp, n, gen, true, n_mip, s);
     VX_KL(k_mip2_scan, dim3((unsigned)(n_mip + ntiles)), dim3(kOneBlock), 0, s, m1, d1[0], d1[1], d1[2], d2[0], d2[1], d2[2], m2, (uint32_t)n_mip, in, out, n,
-          (unsigned long long*)tmp, (uint32_t)ntiles, total64, total_tag, g);
-    return true;
+          (unsigned long long*)tmp, (uint32_t)ntiles, total64, total_tag, m.gen);
+    return m.taken();
 }
 
 // the bits past the grid's nvox cells in the last bitmask word (an externally written mask may set them): cleared, so that nothing
@@ -632,13 +640,12 @@ void launch_mask_tail(uint32_t* words, uint64_t nvox, hipStream_t s)
 }
 
 // exclusive scan of n BYTES into out[0..n] (uint32); single-pass kernel only (in and out 16-byte aligned, tmp all zero before and after)
-void launch_scan_u8(const uint8_t* in, uint32_t* out, uint64_t n, void* tmp, unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen)
+ScanTaken launch_scan_u8(const uint8_t* in, uint32_t* out, uint64_t n, void* tmp, unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen)
 {
-    const uint32_t ntiles = (uint32_t)(((n + 1) + kOneTile - 1) / kOneTile);
-    const uint32_t g = (gen && ntiles <= kScanGenTiles) ? gen : 0u;
-    if (!g && gen) (void)hipMemsetAsync(tmp, 0, (size_t)(ntiles + 2) * sizeof(unsigned long long), s);
-    VX_KL(k_scan_onepass<2>, dim3(ntiles), dim3(kOneBlock), 0, s, reinterpret_cast<const uint32_t*>(in), out, n, (unsigned long long*)tmp, ntiles, total64, total_tag,
-          (uint32_t*)nullptr, g, (uint32_t*)nullptr);
+    const ScanMode m = scan_begin(tmp, n, gen, true, 0, s);
+    VX_KL(k_scan_onepass<2>, dim3(m.ntiles), dim3(kOneBlock), 0, s, reinterpret_cast<const uint32_t*>(in), out, n, (unsigned long long*)tmp, m.ntiles, total64, total_tag,
+          (uint32_t*)nullptr, m.gen, (uint32_t*)nullptr);
+    return m.taken();
 }
 
 // ------------------------------------------------------------------------------------------------------------

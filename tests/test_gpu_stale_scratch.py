@@ -62,6 +62,36 @@ def test_grid_analysis_large_small_large(gpu, kind):
         sc.check_components(g, filled, device=False)
 
 
+# ---- one handle's scan scratch across the generation / ticket boundary -------------------------------------------------------------------------
+POP8 = np.array([bin(b).count("1") for b in range(256)], np.uint8)
+
+
+def test_scan_scratch_across_the_ticket_boundary(gpu):
+    """The single-pass scan numbers its scans on a scratch block up to 512 tiles of 16384 elements (8 388 608) and hands out tickets, on
+    cleared status words, above: a Bool grid of 1024 x 1024 x 257 cells (8 421 376 mask words) lies just above it, one of 128 x 128 x 33 far below.
+    One handle: large, small, large, small -- every word-prefix scan after the first finds the other mode's status words.  The reference
+    is numpy's popcount of the mask, which no scan has touched."""
+    v, t = vx_scenes.cube(half=0.5, center=(0.5, 0.5, 0.5))
+    mesh = gpu.Mesh.from_arrays(v * F([1024, 1024, 257]), t)
+    assert len(t) == 12
+    g, tris = None, []
+    for step, (vs, dim) in enumerate(((1.0, (1024, 1024, 257)), (8.0, (128, 128, 33))) * 2):
+        if g is None:
+            g = gpu.Grid.voxelize(mesh, vs, gpu.GRID_BOOL)
+        else:
+            g.revoxelize(mesh, vs)
+        d = g.describe()
+        assert d["dim"] == dim, step
+        if dim[0] == 1024:
+            assert d["num_words"] == 8421376 > 512 * 16384
+        occupied = int(POP8[g.bitmask().view(np.uint8)].sum(dtype=np.int64))
+        assert occupied > 0 and d["occupied"] == occupied, "step %d: %d occupied, the mask holds %d" % (step, d["occupied"], occupied)
+        assert len(g.aabbs()) == occupied, step
+        if dim[0] == 1024:                                         # two scans of different length on the one block
+            tris.append(g.surface_counts()[1])
+    assert tris[0] > 0 and tris[0] == tris[1]
+
+
 # ---- one mode after another at fixed dimensions ----------------------------------------------------------------------------------------------
 def test_distance_modes_then_nearest(gpu):
     cells = sc.mask("large_half")
