@@ -904,6 +904,84 @@ vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a);  
 vx_status vx_render_frame(vx_render_scene* s, const vx_render_args* a);         /* host buffers: returns when they are written */
 void vx_render_free(vx_render_scene* s);                                        /* waits for the scene's stream */
 
+/* ---- distance-field queries: a snapshot of the signed field that stays on the device, sampled at the caller's own points -------------
+ * vx_field_create runs vx_grid_sdf_device's passes on the grid's stream into a buffer the field owns, copies dim, origin and voxel_size,
+ * takes `state` from the grid's occupied count and returns once the field is complete (one host wait).  After that the field does not
+ * depend on the grid, which may be rebuilt or freed.  `stream` is the stream of the field's queries (NULL: the default stream).  Nothing
+ * a reader of the grid can see changes; a pending VX_VOXELIZE_LIST_ASYNC emission stays pending.  Checks, in this order, every failure
+ * writing nothing and leaving *out NULL: NULL grid or out -> VX_ERR_INVALID_ARG; a grid of 0 cells -> VX_ERR_INVALID_ARG; the distance
+ * fields' size limit -> VX_ERR_CAPACITY.  vx_field_update re-snapshots a grid of the SAME dimensions (else VX_ERR_INVALID_ARG) into the
+ * same buffer and allocates nothing; origin, voxel_size and state are taken anew.  vx_field_values_device: X*Y*Z f32 at
+ * x + X*(y + Y*z), exactly vx_grid_sdf's values.  vx_field_free waits for the field's stream and returns its blocks to the pool.
+ *
+ * THE SAMPLED FIELD (float32, in the order written, nothing fused; / and sqrtf correctly rounded; csrc/vx_field.h is this text as code).
+ * Per axis a of point p:   u_raw = (p[a] - org[a]) / vs - 0.5f
+ *                          out_a = (u_raw < 0) || (u_raw > (float)(dim[a]-1)) || dim[a] == 1
+ *                          u = fminf(fmaxf(u_raw, 0.0f), (float)(dim[a]-1))
+ *                          i0 = min((uint32_t)u, dim[a] >= 2 ? dim[a]-2 : 0);  i1 = min(i0+1, dim[a]-1);  f_a = u - (float)i0
+ * With lerp(a,b,f) = a + f*(b - a) and cXYZ = S[i_X, i_Y, i_Z]:
+ *   value = lerp(lerp(lerp(c000,c100,fx), lerp(c010,c110,fx), fy), lerp(lerp(c001,c101,fx), lerp(c011,c111,fx), fy), fz)
+ *   gx = lerp(lerp(c100-c000, c110-c010, fy), lerp(c101-c001, c111-c011, fy), fz) / vs      (0 where out_x)
+ *   gy = lerp(lerp(c010-c000, c110-c100, fx), lerp(c011-c001, c111-c101, fx), fz) / vs      (0 where out_y)
+ *   gz = lerp(lerp(c001-c000, c101-c100, fx), lerp(c011-c010, c111-c110, fx), fy) / vs      (0 where out_z)
+ *   occupied = every (p[a]-org[a])/vs lies in [0, dim[a])  &&  S at cell ((uint32_t)that per axis) < 0
+ * The trilinear interpolant of the cell-centre values, clamped to the box of cell centres (constant across the half-cell rim and outside
+ * the grid), and its exact gradient; the zero level lies on the shared face of an occupied and an empty cell.  State EMPTY: value +inf,
+ * gradient 0, occupied 0.  State FULL: value -inf, gradient 0, occupied = the in-box test.  A point with a NaN or +-Inf component: value
+ * 0x7FC00000, gradient 0, occupied 0.
+ * vx_field_sample*: NULL f, a or points (num_points > 0), or all three outputs NULL -> VX_ERR_INVALID_ARG; zero points -> VX_OK.  The host
+ * variant stages through blocks that stay on the handle: a repeated call of the same size allocates nothing.
+ *
+ * THE SPHERE CAST: a sphere of `radius` (world units) moved along origin + t * direction.  Per ray, float32, in this order:
+ *  1. a miss (t = -1, clearance = +inf, steps = 0, status MISS) when the ray has a NaN or +-Inf component, its radius is NaN, infinite or
+ *     negative, or dn = sqrtf((dx*dx + dy*dy) + dz*dz) is not > 0 or is infinite;
+ *  2. [tmin, tmax] (tmax_per_ray[r] in place of tmax where given) is clipped to the grid's own box [org, org + (float)dim*vs], not grown:
+ *     per axis inv = 1.0f/d[a]; isinf(inv): a miss unless lo <= o[a] <= hi; else ta = (lo-o[a])*inv, tb = (hi-o[a])*inv,
+ *     t0 = fmaxf(t0, fminf(ta,tb)), t1 = fminf(t1, fmaxf(ta,tb)); !(t0 <= t1) is a miss;
+ *  3. t = t0; clearance = +inf; for k in 0 .. max_steps-1:
+ *         p[a] = o[a] + t*d[a];  f = value(p);  steps = k+1;  clearance = fminf(clearance, f);  g = f - radius
+ *         if (g <= hit_eps*vs) { t_out = t; status = HIT; stop }
+ *         t = t + (g*step_scale)/dn
+ *         if (t > t1) { t_out = -1; status = MISS; stop }
+ *     after the loop: t_out = -1, status = STEP_LIMIT.
+ * Every partial derivative of the interpolant is at most 2 in magnitude, so |grad| <= 2 sqrt 3: with step_scale <= 1/(2 sqrt 3) ~ 0.2887
+ * the march never steps over a point of the clipped segment where the field is <= radius.
+ * Checks before anything is queued: NULL handle, args or rays (num_rays > 0); all outputs NULL; step_scale outside {0} U (0, 1]; hit_eps
+ * negative or non-finite; max_steps > 65535; a global radius that is NaN, infinite or negative while radius_per_ray is NULL ->
+ * VX_ERR_INVALID_ARG.  Zero rays -> VX_OK.  The _device variants take device pointers and are asynchronous on the field's stream. */
+typedef struct vx_field vx_field;
+typedef struct vx_field_desc { uint64_t dim[3]; float voxel_size; float origin[3]; uint32_t state; uint64_t bytes; } vx_field_desc;
+#define VX_FIELD_FINITE 0   /* some cells occupied, some empty: every value finite   */
+#define VX_FIELD_EMPTY  1   /* no occupied cell: every value +inf                    */
+#define VX_FIELD_FULL   2   /* every cell occupied: every value -inf                 */
+vx_status vx_field_create(const vx_grid* g, void* stream, vx_field** out);
+vx_status vx_field_update(vx_field* f, const vx_grid* g);
+vx_status vx_field_describe(const vx_field* f, vx_field_desc* out);
+const float* vx_field_values_device(const vx_field* f);
+void vx_field_free(vx_field* f);
+
+typedef struct vx_field_sample_args {
+    const float* points; uint64_t num_points;   /* 3 f32 each */
+    float* value; float* gradient /*3 each*/; uint8_t* occupied;   /* outputs: NULL ok, not all */
+} vx_field_sample_args;
+vx_status vx_field_sample_device(const vx_field* f, const vx_field_sample_args* a);
+vx_status vx_field_sample(const vx_field* f, const vx_field_sample_args* a);
+
+#define VX_FIELD_MISS 0
+#define VX_FIELD_HIT 1
+#define VX_FIELD_STEP_LIMIT 2
+typedef struct vx_field_trace_args {
+    const float* rays; uint64_t num_rays;            /* 6 f32: origin, direction, as vx_trace */
+    float tmin, tmax; const float* tmax_per_ray;     /* NULL ok */
+    float radius; const float* radius_per_ray;       /* NULL ok; world units */
+    float step_scale;                                /* 0 = default 0.25; else in (0, 1] */
+    float hit_eps;                                   /* in cells; 0 = default 1/64; else > 0, finite */
+    uint32_t max_steps;                              /* 0 = default 256; at most 65535 */
+    float* t; float* clearance; uint32_t* steps; uint8_t* status;   /* each NULL ok, not all */
+} vx_field_trace_args;
+vx_status vx_field_sphere_trace_device(const vx_field* f, const vx_field_trace_args* a);
+vx_status vx_field_sphere_trace(const vx_field* f, const vx_field_trace_args* a);
+
 /* ---- test aid: the device radix sort the Octree uses for its Morton items (octTree.hpp:363 -> vx_sort.hip), applied to a host array.
  * Keys must have no bit set at or above `bits` (1..64); sorted in place. */
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits);

@@ -45,6 +45,48 @@ using GridHandle = std::shared_ptr<vx_grid>;
 inline GridHandle adopt(vx_grid* g) { return GridHandle(g, GridDeleter{}); }
 }  // namespace vxdetail
 
+// A snapshot of a grid's signed distance field that stays on the device (vx_field), queried at the caller's own points.  It does not
+// depend on the grid it was taken from.
+class DistanceField
+{
+    std::shared_ptr<vx_field> m_field;
+
+public:
+    explicit DistanceField(const vx_grid* grid)
+    {
+        vx_field* f = nullptr;
+        vxdetail::check(vx_field_create(grid, nullptr, &f));
+        m_field = std::shared_ptr<vx_field>(f, [](vx_field* p) noexcept { vx_field_free(p); });
+    }
+    vx_field* handle() const noexcept { return m_field.get(); }
+
+    // Trilinear sample at points (x y z each): one value per point, and its gradient (3 per point) where asked for.
+    void sample(const std::vector<float>& points, std::vector<float>& values, std::vector<float>* gradients = nullptr) const
+    {
+        const size_t n = points.size() / 3;
+        values.assign(n, 0.0f);
+        if (gradients) gradients->assign(3 * n, 0.0f);
+        vx_field_sample_args a{};
+        a.points = points.data(); a.num_points = n;
+        a.value = values.data(); a.gradient = gradients ? gradients->data() : nullptr;
+        vxdetail::check(vx_field_sample(m_field.get(), &a));
+    }
+
+    // Sphere cast: a sphere of `radius` (world units) along rays (origin, direction: 6 floats each) -> t (-1: no hit) and
+    // VX_FIELD_MISS / VX_FIELD_HIT / VX_FIELD_STEP_LIMIT per ray, with the default step scale, hit tolerance and step limit.
+    void sphereTrace(const std::vector<float>& rays, float radius, float tmin, float tmax, std::vector<float>& t, std::vector<uint8_t>& status) const
+    {
+        const size_t n = rays.size() / 6;
+        t.assign(n, -1.0f);
+        status.assign(n, (uint8_t)VX_FIELD_MISS);
+        vx_field_trace_args a{};
+        a.rays = rays.data(); a.num_rays = n;
+        a.tmin = tmin; a.tmax = tmax; a.radius = radius;
+        a.t = t.data(); a.status = status.data();
+        vxdetail::check(vx_field_sphere_trace(m_field.get(), &a));
+    }
+};
+
 template <typename T>
 class VoxelGrid
 {
@@ -195,6 +237,9 @@ public:
         vxdetail::check(vx_grid_sdf(m_grid.get(), ret.data(), ret.size()));
         return ret;
     }
+
+    // The signed field kept on the device for queries at arbitrary points: trilinear samples and sphere casts (DistanceField above).
+    DistanceField distanceField() const { return DistanceField(m_grid.get()); }
 
     // The boundary mesh of the occupancy (vx_grid_surface): one quad (two triangles) per exposed cell face over de-duplicated lattice
     // points.  xyz: 3 floats per vertex; tris: 3 vertex indices per triangle; mats (optional; a grid built with materials, not VoxelGridVec):

@@ -46,6 +46,14 @@
 //                                       cell, negative inside by the distance to the nearest empty one) as raw little-endian f32, x fastest,
 //                                       X*Y*Z values; one line gives the dims and the finite min / max.  bool / aabbstruct / vec, with or
 //                                       without --solid; not with --grid octree, --gpus N > 1 or --bench
+//   --probe POINTS.txt [--probe-out FILE]
+//                                       the grid's distance field sampled at the file's points ("x y z" per line; vx_field_sample): per point a
+//                                       line "x y z value gx gy gz occupied" (%.9g) to FILE or the standard output, and one summary line.
+//                                       bool / aabbstruct / vec; not with --grid octree, --gpus N > 1 or --bench
+//   --sphere-depth FILE.pgm --radius R [--size WxH]
+//                                       a sphere of radius R (world units) cast along every camera ray of --xray's picture
+//                                       (vx_field_sphere_trace) as a binary 16-bit PGM: 0 = no hit, else 1 + t in sixteenths of the voxel size,
+//                                       at most 65535; same grids and refusals as --probe
 //   --nearest FILE [--nearest-inside]   the grid's feature transform (vx_grid_nearest: per cell the index x + X*(y + Y*z) of its nearest occupied
 //                                       cell, the smallest index among equally near ones; --nearest-inside: of its nearest empty cell;
 //                                       0xFFFFFFFF when there is none) as raw little-endian u32, x fastest, X*Y*Z values; one line gives the
@@ -500,6 +508,90 @@ struct NearestOpt {
 };
 NearestOpt g_nearest;
 
+// --probe POINTS.txt [--probe-out FILE], --sphere-depth FILE.pgm --radius R: queries on the grid's distance field (DistanceField)
+struct FieldOpt {
+    std::string probe, probeOut, depth;
+    float radius = 0.0f;
+    bool radiusGiven = false;
+};
+FieldOpt g_field;
+
+// --probe: "x y z" lines in, "x y z value gx gy gz occupied" lines out (%.9g: every float32 survives the round trip)
+void write_probe(const DistanceField& field)
+{
+    std::ifstream in(g_field.probe);
+    if (!in) throw std::runtime_error("cannot read " + g_field.probe);
+    std::vector<float> pts;
+    for (std::string a, b, c; in >> a >> b >> c;) {
+        pts.push_back(std::strtof(a.c_str(), nullptr));  // (strtof reads nan and inf)
+        pts.push_back(std::strtof(b.c_str(), nullptr));
+        pts.push_back(std::strtof(c.c_str(), nullptr));
+    }
+    const size_t n = pts.size() / 3;
+    std::vector<float> value(n), grad(3 * n);
+    std::vector<uint8_t> occ(n);
+    vx_field_sample_args a{};
+    a.points = pts.data(); a.num_points = n; a.value = value.data(); a.gradient = grad.data(); a.occupied = occ.data();
+    if (n) vxdetail::check(vx_field_sample(field.handle(), &a));
+    std::FILE* f = g_field.probeOut.empty() ? stdout : std::fopen(g_field.probeOut.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + g_field.probeOut);
+    size_t inside = 0;
+    for (size_t i = 0; i < n; ++i) {
+        std::fprintf(f, "%.9g %.9g %.9g %.9g %.9g %.9g %.9g %d\n", (double)pts[3 * i], (double)pts[3 * i + 1], (double)pts[3 * i + 2], (double)value[i],
+                     (double)grad[3 * i], (double)grad[3 * i + 1], (double)grad[3 * i + 2], (int)occ[i]);
+        inside += occ[i];
+    }
+    const bool ok = std::ferror(f) == 0;
+    if (f != stdout && (std::fclose(f) != 0 || !ok)) throw std::runtime_error("cannot write " + g_field.probeOut);
+    std::printf("[voxhip] probe: %zu points, %zu in occupied cells\n", n, inside);
+}
+
+void xray_camera(float vi[16], float pi[16], uint32_t W, uint32_t H, const std::string& cameraDump);
+
+// --sphere-depth: the sphere cast's t of every primary ray of the reference camera (the ray of pixel (px, py) as the ray kernels generate
+// it) as a 16-bit PGM in --xray's form: 0 = no hit, else 1 + t in sixteenths of the voxel size, at most 65535
+void write_sphere_depth(const DistanceField& field, float vs, uint32_t W, uint32_t H, const std::string& cameraDump)
+{
+    float vi[16], pi[16];
+    xray_camera(vi, pi, W, H, cameraDump);
+    const size_t n = (size_t)W * H;
+    std::vector<float> rays(6 * n), t;
+    std::vector<uint8_t> status;
+    for (size_t r = 0; r < n; ++r) {
+        const uint32_t px = (uint32_t)(r % W), py = (uint32_t)(r / W);
+        const float u = ((float)px + 0.5f) / (float)W, v = ((float)py + 0.5f) / (float)H;
+        const float ndx = u * 2.0f - 1.0f, ndy = v * 2.0f - 1.0f;
+        float tg[3];
+        for (int k = 0; k < 3; ++k) tg[k] = (pi[0 + k] * ndx + pi[4 + k] * ndy) + (pi[8 + k] * 1.0f + pi[12 + k] * 1.0f);
+        const float il = 1.0f / std::sqrt((tg[0] * tg[0] + tg[1] * tg[1]) + tg[2] * tg[2]);
+        const float n0 = tg[0] * il, n1 = tg[1] * il, n2 = tg[2] * il;
+        float* ray = &rays[6 * r];
+        ray[0] = vi[12]; ray[1] = vi[13]; ray[2] = vi[14];
+        for (int k = 0; k < 3; ++k) ray[3 + k] = (vi[0 + k] * n0 + vi[4 + k] * n1) + vi[8 + k] * n2;
+    }
+    field.sphereTrace(rays, g_field.radius, 0.001f, 10000.0f, t, status);
+    std::vector<unsigned char> px(2 * n);
+    size_t hits = 0, limited = 0;
+    float far = 0.0f;
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t c = 0;
+        if (status[i] == VX_FIELD_HIT) {
+            const float q = t[i] / vs * 16.0f;
+            c = q < 65534.0f ? (uint32_t)q + 1u : 65535u;
+            ++hits;
+            far = std::max(far, t[i]);
+        }
+        limited += status[i] == VX_FIELD_STEP_LIMIT;
+        px[2 * i] = (unsigned char)(c >> 8);
+        px[2 * i + 1] = (unsigned char)(c & 255u);
+    }
+    std::ofstream f(g_field.depth, std::ios::binary);
+    f << "P5\n" << W << ' ' << H << "\n65535\n";
+    f.write(reinterpret_cast<const char*>(px.data()), (std::streamsize)px.size());
+    if (!f) throw std::runtime_error("cannot write " + g_field.depth);
+    std::printf("[voxhip] sphere depth %ux%u: radius %g, %zu hits, farthest t %g, %zu rays at the step limit\n", W, H, (double)g_field.radius, hits, (double)far, limited);
+}
+
 // the feature transform of the grid as raw little-endian u32, and one line: the dims and the largest |c - N(c)|^2 over cells that have an N
 template <class T>
 void write_nearest(const T& vox)
@@ -601,6 +693,11 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
         std::printf("[voxhip] sdf: %zu x %zu x %zu cells, min %g max %g\n", vox.dimX(), vox.dimY(), vox.dimZ(), (double)lo, (double)hi);
     }
     if (!g_nearest.file.empty()) write_nearest(vox);
+    if (!g_field.probe.empty() || !g_field.depth.empty()) {
+        const DistanceField field = vox.distanceField();
+        if (!g_field.probe.empty()) write_probe(field);
+        if (!g_field.depth.empty()) write_sphere_depth(field, vox.voxelSize(), rw, rh, cameraDump);
+    }
     if (!surfaceFile.empty()) write_surface(vox, surfaceFile, materials);
     if (!componentsFile.empty()) {
         const std::vector<vx_component> cs = vox.componentStats(connectivity);
@@ -635,7 +732,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--nearest FILE [--nearest-inside]] [--surface FILE.obj [--smooth N[:LAMBDA:MU]]] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--nearest FILE [--nearest-inside]] [--probe POINTS.txt [--probe-out FILE]] [--sphere-depth FILE.pgm --radius R [--size WxH]] [--surface FILE.obj [--smooth N[:LAMBDA:MU]]] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
                      argv[0]);
         return 2;
     }
@@ -667,6 +764,10 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--sdf") && i + 1 < argc) sdfFile = argv[++i];
         else if (!std::strcmp(argv[i], "--nearest") && i + 1 < argc) g_nearest.file = argv[++i];
         else if (!std::strcmp(argv[i], "--nearest-inside")) g_nearest.inside = true;
+        else if (!std::strcmp(argv[i], "--probe") && i + 1 < argc) g_field.probe = argv[++i];
+        else if (!std::strcmp(argv[i], "--probe-out") && i + 1 < argc) g_field.probeOut = argv[++i];
+        else if (!std::strcmp(argv[i], "--sphere-depth") && i + 1 < argc) g_field.depth = argv[++i];
+        else if (!std::strcmp(argv[i], "--radius") && i + 1 < argc) { g_field.radius = std::strtof(argv[++i], nullptr); g_field.radiusGiven = true; }
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
         else if (!std::strcmp(argv[i], "--smooth") && i + 1 < argc) { if (!parse_smooth(argv[++i], &g_smooth)) { std::fprintf(stderr, "bad --smooth '%s': N[:LAMBDA:MU] with N <= 1024, LAMBDA in [0, 1] and MU in [-1, 0]\n", argv[i]); return 2; } }
         else if (!std::strcmp(argv[i], "--components") && i + 1 < argc) componentsFile = argv[++i];
@@ -710,6 +811,16 @@ int main(int argc, char** argv)
     }
     if (!g_nearest.file.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
         std::fprintf(stderr, "--nearest writes the nearest-cell field of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if ((!g_field.probe.empty() || !g_field.depth.empty()) && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
+        std::fprintf(stderr, "--probe / --sphere-depth query the distance field of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (!g_field.probeOut.empty() && g_field.probe.empty()) { std::fprintf(stderr, "--probe-out names the file --probe writes: it needs --probe POINTS.txt\n"); return 2; }
+    if (g_field.radiusGiven && g_field.depth.empty()) { std::fprintf(stderr, "--radius is the sphere of --sphere-depth: it needs --sphere-depth FILE.pgm\n"); return 2; }
+    if (!g_field.depth.empty() && (!g_field.radiusGiven || !(g_field.radius >= 0.0f) || std::isinf(g_field.radius))) {
+        std::fprintf(stderr, "--sphere-depth needs --radius R, finite and not negative (world units)\n");
         return 2;
     }
     if (g_nearest.inside && g_nearest.file.empty()) {

@@ -1,6 +1,7 @@
 // vx_api.cpp -- the C ABI declared in include/voxhip.h: handles, device-memory pool, launch sequencing.
 // All compute happens in the kernels of vx_kernels.hip; there is no CPU compute path in this library.
 #include "vx_internal.h"
+#include "vx_field.h"
 
 #include <cctype>
 #include <cmath>
@@ -3177,6 +3178,208 @@ void vx_grid_free(vx_grid* g)
     { DeviceGuard dg(g->device); (void)g->list_resolve(/*drop_unqueued=*/true); g->side_release(); (void)hipStreamSynchronize(g->stream); }
     delete g;
 }
+
+// ---- distance-field queries (vx_field.hip) ----------------------------------------------------------------------
+// A snapshot of the signed field in a block of its own, and the blocks the host variants stage through: they stay on the handle, so a
+// repeated call of the same size asks the pool for nothing.
+struct vx_field : Home {
+    vx::FieldGeom G{};
+    uint64_t nvox = 0;
+    DevBuf values{this};
+    DevBuf st_in{this}, st_tmax{this}, st_radius{this};            // points or rays, tmax_per_ray, radius_per_ray
+    DevBuf st_a{this}, st_b{this}, st_c{this}, st_d{this};         // value / t, gradient / clearance, steps, occupied / status
+};
+
+// The snapshot: the signed field's passes on the GRID's stream into the field's block (which no query reads meanwhile: the field's stream
+// is drained first), the state from the occupied count, one wait.  The grid's readers see no change (distance_queue).
+static vx_status field_snapshot(vx_field* f, vx_grid* g)
+{
+    DeviceGuard dg(g->device);
+    VX_HIP(hipStreamSynchronize(f->stream));
+    VX_TRY(ensure_occupied(g));
+    VX_TRY(distance_queue(g, 2, f->values.p));
+    VX_HIP(hipStreamSynchronize(g->stream));
+    for (int a = 0; a < 3; ++a) { f->G.org[a] = g->g.org[a]; f->G.dim[a] = g->g.dim[a]; }
+    f->G.vs = g->g.vs;
+    f->G.state = g->occupied == 0 ? VX_FIELD_EMPTY : (g->occupied == g->g.nvox ? VX_FIELD_FULL : VX_FIELD_FINITE);
+    return VX_OK;
+}
+
+vx_status vx_field_create(const vx_grid* gc, void* stream, vx_field** out)
+{
+    if (out) *out = nullptr;
+    if (!gc || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (!gc->g.nvox) return fail(VX_ERR_INVALID_ARG, "a field needs a grid of at least one cell");
+    uint64_t n = 0;
+    VX_TRY(distance_check(gc, ~0ull, &n));
+    vx_grid* g = const_cast<vx_grid*>(gc);
+    std::unique_ptr<vx_field> f(new vx_field());
+    f->device = g->device;
+    f->stream = (hipStream_t)stream;
+    f->nvox = n;
+    vx_status st = VX_OK;
+    {
+        DeviceGuard dg(g->device);
+        const hipError_t e = f->values.ensure((size_t)n * 4);
+        st = e == hipSuccess ? field_snapshot(f.get(), g) : fail(VX_ERR_HIP, std::string("the field's block: ") + hipGetErrorString(e));
+    }
+    if (st != VX_OK) {
+        const std::string e = g_err;
+        vx_field_free(f.release());
+        return fail(st, e);
+    }
+    *out = f.release();
+    return VX_OK;
+}
+
+vx_status vx_field_update(vx_field* f, const vx_grid* gc)
+{
+    if (!f || !gc) return fail(VX_ERR_INVALID_ARG, "null argument");
+    for (int a = 0; a < 3; ++a)
+        if (gc->g.dim[a] != f->G.dim[a]) return fail(VX_ERR_INVALID_ARG, "vx_field_update needs a grid of the field's dimensions");
+    if (gc->device != f->device) return fail(VX_ERR_INVALID_ARG, "vx_field_update needs a grid on the field's device");
+    return field_snapshot(f, const_cast<vx_grid*>(gc));
+}
+
+vx_status vx_field_describe(const vx_field* f, vx_field_desc* d)
+{
+    if (!f || !d) return fail(VX_ERR_INVALID_ARG, "null argument");
+    std::memset(d, 0, sizeof(*d));
+    for (int a = 0; a < 3; ++a) { d->dim[a] = f->G.dim[a]; d->origin[a] = f->G.org[a]; }
+    d->voxel_size = f->G.vs;
+    d->state = f->G.state;
+    d->bytes = f->nvox * 4;
+    return VX_OK;
+}
+
+const float* vx_field_values_device(const vx_field* f) { return f ? f->values.as<float>() : nullptr; }
+
+void vx_field_free(vx_field* f)
+{
+    if (!f) return;
+    { DeviceGuard dg(f->device); (void)hipStreamSynchronize(f->stream); }
+    f->drained = true;
+    delete f;
+}
+
+// a host array of the field's host variants through one of the handle's blocks: null stays null; *queued: the stream reads host memory
+static vx_status field_stage_in(vx_field* f, DevBuf& b, const void* host, size_t bytes, const void** dev)
+{
+    *dev = nullptr;
+    if (!host) return VX_OK;
+    VX_HIP(b.ensure(bytes));
+    VX_HIP(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, f->stream));
+    *dev = b.p;
+    return VX_OK;
+}
+
+static vx_status field_stage_out(DevBuf& b, const void* host, size_t bytes, void** dev)
+{
+    *dev = nullptr;
+    if (!host) return VX_OK;
+    VX_HIP(b.ensure(bytes));
+    *dev = b.p;
+    return VX_OK;
+}
+
+static vx_status field_copy_back(vx_field* f, void* host, const void* dev, size_t bytes)
+{
+    if (host) VX_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, f->stream));
+    return VX_OK;
+}
+
+static vx_status field_sample_entry(const vx_field* fc, const vx_field_sample_args* a, bool host)
+{
+    if (!fc || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (a->num_points && !a->points) return fail(VX_ERR_INVALID_ARG, "null points");
+    if (!a->value && !a->gradient && !a->occupied) return fail(VX_ERR_INVALID_ARG, "the sample needs at least one output");
+    const size_t n = (size_t)a->num_points;
+    if (!n) return VX_OK;
+    vx_field* f = const_cast<vx_field*>(fc);
+    DeviceGuard dg(f->device);
+    if (!host) {
+        vx::launch_field_sample(f->values.as<float>(), f->G, a->points, n, a->value, a->gradient, a->occupied, f->stream);
+        VX_HIP(hipGetLastError());
+        return VX_OK;
+    }
+    // (every block before the first copy: a failed ensure leaves nothing queued that reads the caller's arrays)
+    void *dv = nullptr, *dg3 = nullptr, *doc = nullptr;
+    VX_TRY(field_stage_out(f->st_a, a->value, n * 4, &dv));
+    VX_TRY(field_stage_out(f->st_b, a->gradient, n * 12, &dg3));
+    VX_TRY(field_stage_out(f->st_d, a->occupied, n, &doc));
+    const void* dp = nullptr;
+    vx_status st = field_stage_in(f, f->st_in, a->points, n * 12, &dp);
+    if (st == VX_OK) {
+        vx::launch_field_sample(f->values.as<float>(), f->G, static_cast<const float*>(dp), n, static_cast<float*>(dv), static_cast<float*>(dg3),
+                                static_cast<uint8_t*>(doc), f->stream);
+        if (hipGetLastError() != hipSuccess) st = fail(VX_ERR_HIP, "k_field_sample: launch failed");
+    }
+    if (st == VX_OK) st = field_copy_back(f, a->value, dv, n * 4);
+    if (st == VX_OK) st = field_copy_back(f, a->gradient, dg3, n * 12);
+    if (st == VX_OK) st = field_copy_back(f, a->occupied, doc, n);
+    const hipError_t e = hipStreamSynchronize(f->stream);  // (also after a failure: the stream may still read the caller's points)
+    if (st == VX_OK && e != hipSuccess) st = fail(VX_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return st;
+}
+
+vx_status vx_field_sample_device(const vx_field* f, const vx_field_sample_args* a) { return field_sample_entry(f, a, false); }
+vx_status vx_field_sample(const vx_field* f, const vx_field_sample_args* a) { return field_sample_entry(f, a, true); }
+
+static vx_status field_trace_entry(const vx_field* fc, const vx_field_trace_args* a, bool host)
+{
+    if (!fc || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (a->num_rays && !a->rays) return fail(VX_ERR_INVALID_ARG, "null rays");
+    if (!a->t && !a->clearance && !a->steps && !a->status) return fail(VX_ERR_INVALID_ARG, "the sphere cast needs at least one output");
+    if (!(a->step_scale == 0.0f || (a->step_scale > 0.0f && a->step_scale <= 1.0f))) return fail(VX_ERR_INVALID_ARG, "step_scale must be 0 or in (0, 1]");
+    if (!(a->hit_eps >= 0.0f) || std::isinf(a->hit_eps)) return fail(VX_ERR_INVALID_ARG, "hit_eps must be finite and not negative");
+    if (a->max_steps > 65535u) return fail(VX_ERR_INVALID_ARG, "max_steps must be at most 65535");
+    if (!a->radius_per_ray && (!(a->radius >= 0.0f) || std::isinf(a->radius))) return fail(VX_ERR_INVALID_ARG, "radius must be finite and not negative");
+    const size_t n = (size_t)a->num_rays;
+    if (!n) return VX_OK;
+    vx_field* f = const_cast<vx_field*>(fc);
+    DeviceGuard dg(f->device);
+    vx::FieldTraceIO io{};
+    io.rays = a->rays; io.nrays = n;
+    io.tmin = a->tmin; io.tmax = a->tmax; io.tmax_per_ray = a->tmax_per_ray;
+    io.radius = a->radius; io.radius_per_ray = a->radius_per_ray;
+    io.step_scale = a->step_scale == 0.0f ? 0.25f : a->step_scale;
+    io.hit_eps = a->hit_eps == 0.0f ? 0.015625f : a->hit_eps;
+    io.max_steps = a->max_steps ? a->max_steps : 256u;
+    io.t = a->t; io.clearance = a->clearance; io.steps = a->steps; io.status = a->status;
+    if (!host) {
+        vx::launch_field_trace(f->values.as<float>(), f->G, io, f->stream);
+        VX_HIP(hipGetLastError());
+        return VX_OK;
+    }
+    void *dt = nullptr, *dc = nullptr, *ds = nullptr, *dst = nullptr;
+    VX_TRY(field_stage_out(f->st_a, a->t, n * 4, &dt));
+    VX_TRY(field_stage_out(f->st_b, a->clearance, n * 4, &dc));
+    VX_TRY(field_stage_out(f->st_c, a->steps, n * 4, &ds));
+    VX_TRY(field_stage_out(f->st_d, a->status, n, &dst));
+    VX_HIP(f->st_in.ensure(n * 24));
+    if (a->tmax_per_ray) VX_HIP(f->st_tmax.ensure(n * 4));
+    if (a->radius_per_ray) VX_HIP(f->st_radius.ensure(n * 4));
+    const void *dr = nullptr, *dtm = nullptr, *drad = nullptr;
+    vx_status st = field_stage_in(f, f->st_in, a->rays, n * 24, &dr);
+    if (st == VX_OK) st = field_stage_in(f, f->st_tmax, a->tmax_per_ray, n * 4, &dtm);
+    if (st == VX_OK) st = field_stage_in(f, f->st_radius, a->radius_per_ray, n * 4, &drad);
+    if (st == VX_OK) {
+        io.rays = static_cast<const float*>(dr); io.tmax_per_ray = static_cast<const float*>(dtm); io.radius_per_ray = static_cast<const float*>(drad);
+        io.t = static_cast<float*>(dt); io.clearance = static_cast<float*>(dc); io.steps = static_cast<uint32_t*>(ds); io.status = static_cast<uint8_t*>(dst);
+        vx::launch_field_trace(f->values.as<float>(), f->G, io, f->stream);
+        if (hipGetLastError() != hipSuccess) st = fail(VX_ERR_HIP, "k_field_trace: launch failed");
+    }
+    if (st == VX_OK) st = field_copy_back(f, a->t, dt, n * 4);
+    if (st == VX_OK) st = field_copy_back(f, a->clearance, dc, n * 4);
+    if (st == VX_OK) st = field_copy_back(f, a->steps, ds, n * 4);
+    if (st == VX_OK) st = field_copy_back(f, a->status, dst, n);
+    const hipError_t e = hipStreamSynchronize(f->stream);
+    if (st == VX_OK && e != hipSuccess) st = fail(VX_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return st;
+}
+
+vx_status vx_field_sphere_trace_device(const vx_field* f, const vx_field_trace_args* a) { return field_trace_entry(f, a, false); }
+vx_status vx_field_sphere_trace(const vx_field* f, const vx_field_trace_args* a) { return field_trace_entry(f, a, true); }
 
 // ---- rays -----------------------------------------------------------------------------------------------------
 // the grid's traversal structure as launch_trace takes it; *p16: the 16th-prefix table of the word prefix for the rank pass, null where it

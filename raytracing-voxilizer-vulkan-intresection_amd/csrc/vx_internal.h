@@ -474,6 +474,27 @@ void launch_distance(const uint32_t* words, const uint32_t dim[3], int mode, flo
 void launch_nearest(const uint32_t* words, const uint32_t dim[3], bool inside, const uint32_t* values, uint32_t fill, uint32_t* buf, uint2* stk,
                     hipStream_t s);
 
+// Queries on a snapshot S of the signed field (vx_field.hip; the arithmetic is vx_field.h's): the trilinear sample of n points (each output
+// optional) and the sphere cast of a ray batch (device pointers; step_scale, hit_eps and max_steps with their defaults filled in).
+struct FieldGeom;
+struct FieldTraceIO {
+    const float* rays;
+    uint64_t nrays;
+    float tmin, tmax;
+    const float* tmax_per_ray;
+    float radius;
+    const float* radius_per_ray;
+    float step_scale, hit_eps;
+    uint32_t max_steps;
+    float* t;
+    float* clearance;
+    uint32_t* steps;
+    uint8_t* status;
+};
+void launch_field_sample(const float* S, const FieldGeom& G, const float* points, uint64_t n, float* value, float* gradient, uint8_t* occupied,
+                         hipStream_t s);
+void launch_field_trace(const float* S, const FieldGeom& G, const FieldTraceIO& io, hipStream_t s);
+
 // Morphology with the digital Euclidean ball (vx_morph.hip).  A domain: its cells and the bits from one (y, z) row to the next -- X for the
 // reference's bitmask, 32 * ceil(X / 32) for a ROW-ALIGNED mask (morph_aligned_words(dim) words, padding bits zero).
 struct MorphDom {

@@ -180,6 +180,20 @@ class ScanArgs(C.Structure):
                 ("total_tag", C.c_uint64), ("gen_start", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class FieldDesc(C.Structure):
+    _fields_ = [("dim", C.c_uint64 * 3), ("voxel_size", C.c_float), ("origin", C.c_float * 3), ("state", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class FieldSampleArgs(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("num_points", C.c_uint64), ("value", C.c_void_p), ("gradient", C.c_void_p), ("occupied", C.c_void_p)]
+
+
+class FieldTraceArgs(C.Structure):
+    _fields_ = [("rays", C.c_void_p), ("num_rays", C.c_uint64), ("tmin", C.c_float), ("tmax", C.c_float), ("tmax_per_ray", C.c_void_p),
+                ("radius", C.c_float), ("radius_per_ray", C.c_void_p), ("step_scale", C.c_float), ("hit_eps", C.c_float),
+                ("max_steps", C.c_uint32), ("t", C.c_void_p), ("clearance", C.c_void_p), ("steps", C.c_void_p), ("status", C.c_void_p)]
+
+
 class TraceArgs(C.Structure):
     _fields_ = [("rays", C.c_void_p), ("view_inverse", C.POINTER(C.c_float)), ("proj_inverse", C.POINTER(C.c_float)), ("width", C.c_uint32),
                 ("height", C.c_uint32), ("num_rays", C.c_uint64), ("tmin", C.c_float), ("tmax", C.c_float), ("tmax_per_ray", C.c_void_p),
@@ -255,6 +269,8 @@ SYMBOLS = [
     "vx_grid_bitmask", "vx_grid_bitmask_device", "vx_grid_bitmask_device_mut", "vx_grid_refresh", "vx_grid_fill_interior", "vx_grid_interior", "vx_grid_fill_rounds",
     "vx_grid_distance_sq_device", "vx_grid_distance_sq", "vx_grid_sdf_device", "vx_grid_sdf",
     "vx_grid_nearest_device", "vx_grid_nearest", "vx_grid_nearest_gather_device", "vx_grid_nearest_gather",
+    "vx_field_create", "vx_field_update", "vx_field_describe", "vx_field_values_device", "vx_field_free",
+    "vx_field_sample_device", "vx_field_sample", "vx_field_sphere_trace_device", "vx_field_sphere_trace",
     "vx_grid_morph_device", "vx_grid_morph_mask", "vx_grid_morph", "vx_grid_seal", "vx_morph_bit_radius",
     "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh",
     "vx_grid_surface_smooth_device", "vx_grid_surface_smooth", "vx_grid_surface_smooth_mesh",
@@ -388,6 +404,17 @@ def lib():
     L.vx_grid_distance_sq.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_sdf_device.argtypes = [vp, vp, C.c_uint64]
     L.vx_grid_sdf.argtypes = [vp, vp, C.c_uint64]
+    L.vx_field_create.argtypes = [vp, vp, C.POINTER(vp)]
+    L.vx_field_update.argtypes = [vp, vp]
+    L.vx_field_describe.argtypes = [vp, C.POINTER(FieldDesc)]
+    L.vx_field_values_device.argtypes = [vp]
+    L.vx_field_values_device.restype = vp
+    L.vx_field_free.argtypes = [vp]
+    L.vx_field_free.restype = None
+    L.vx_field_sample_device.argtypes = [vp, C.POINTER(FieldSampleArgs)]
+    L.vx_field_sample.argtypes = [vp, C.POINTER(FieldSampleArgs)]
+    L.vx_field_sphere_trace_device.argtypes = [vp, C.POINTER(FieldTraceArgs)]
+    L.vx_field_sphere_trace.argtypes = [vp, C.POINTER(FieldTraceArgs)]
     L.vx_grid_nearest_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_nearest.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_nearest_gather_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64]
@@ -899,6 +926,13 @@ class Grid:
         self._record(out)
         return out
 
+    def field(self, stream=None):
+        """vx_field_create: a snapshot of the signed field that stays on the device, for queries at the caller's own points -> Field.
+        `stream`: the stream of the field's queries.  The field does not depend on the grid afterwards."""
+        h = C.c_void_p()
+        _check(lib().vx_field_create(self.h, _stream_handle(stream), C.byref(h)))
+        return Field(h)
+
     def nearest(self, inside=False):
         """vx_grid_nearest: the cell index x + X*(y + Y*z) of every cell's nearest occupied cell (inside=True: nearest empty cell), the
         smallest index among equally near ones -> numpy uint32 [Z, Y, X]; 0xFFFFFFFF where no such cell exists."""
@@ -1206,6 +1240,96 @@ class Grid:
     def free(self):
         if self.h and self.owned:
             lib().vx_grid_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+FIELD_FINITE, FIELD_EMPTY, FIELD_FULL = 0, 1, 2
+FIELD_MISS, FIELD_HIT, FIELD_STEP_LIMIT = 0, 1, 2
+# the outputs of the field queries, as _FIRST_HIT
+_FIELD_SAMPLE = {"value": ((), np.float32), "gradient": ((3,), np.float32), "occupied": ((), np.uint8)}
+_FIELD_TRACE = {"t": ((), np.float32), "clearance": ((), np.float32), "steps": ((), np.uint32), "status": ((), np.uint8)}
+
+
+class Field:
+    """vx_field handle: a device-resident snapshot of a grid's signed distance field, sampled trilinearly at arbitrary points and sphere
+    traced along rays (include/voxhip.h, "distance-field queries")."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def update(self, grid):
+        """vx_field_update: re-snapshots a grid of the same dimensions into the same buffer."""
+        _check(lib().vx_field_update(self.h, grid.h))
+
+    def describe(self):
+        d = FieldDesc()
+        _check(lib().vx_field_describe(self.h, C.byref(d)))
+        return dict(dim=tuple(int(x) for x in d.dim), voxel_size=float(d.voxel_size), origin=np.array(d.origin, np.float32), state=int(d.state),
+                    bytes=int(d.bytes))
+
+    def values_device_ptr(self):
+        """the snapshot on the device: X*Y*Z float32 at x + X*(y + Y*z), exactly sdf()'s values"""
+        return lib().vx_field_values_device(self.h)
+
+    def sample(self, points, want=("value", "gradient", "occupied")):
+        """vx_field_sample on host points (n, 3) -> dict of the requested outputs: value (n,) float32, gradient (n, 3) float32, occupied
+        (n,) uint8."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        a = FieldSampleArgs()
+        a.points, a.num_points = p.ctypes.data, p.shape[0]
+        out = _outputs(a, want, p.shape[0], _FIELD_SAMPLE)
+        _check(lib().vx_field_sample(self.h, C.byref(a)))
+        return out
+
+    def sample_device(self, points_ptr, n, value_ptr=None, gradient_ptr=None, occupied_ptr=None):
+        """vx_field_sample_device on raw device pointers, asynchronous on the field's stream."""
+        a = FieldSampleArgs()
+        a.points, a.num_points = points_ptr, n
+        _set_pointers(a, dict(value=value_ptr, gradient=gradient_ptr, occupied=occupied_ptr))
+        _check(lib().vx_field_sample_device(self.h, C.byref(a)))
+
+    @staticmethod
+    def _trace_args(rays_ptr, n, radius, tmin, tmax, step_scale, hit_eps, max_steps):
+        a = FieldTraceArgs()
+        a.rays, a.num_rays = rays_ptr, n
+        a.tmin, a.tmax, a.radius = np.float32(tmin), np.float32(tmax), np.float32(radius)
+        a.step_scale, a.hit_eps, a.max_steps = np.float32(step_scale), np.float32(hit_eps), int(max_steps)
+        return a
+
+    def sphere_trace(self, rays, radius=0.0, radius_per_ray=None, tmin=0.001, tmax=10000.0, tmax_per_ray=None, step_scale=0.25, hit_eps=1.0 / 64,
+                     max_steps=256, want=("t", "clearance", "steps", "status")):
+        """vx_field_sphere_trace on host rays (n, 6): a sphere of `radius` (world units) moved along each ray until the field at its centre
+        is within hit_eps cells of the radius -> dict of the requested outputs: t (n,) float32 (-1: no hit), clearance (n,) float32 (the
+        smallest field value met), steps (n,) uint32, status (n,) uint8 (FIELD_MISS / FIELD_HIT / FIELD_STEP_LIMIT)."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        a = self._trace_args(r.ctypes.data, r.shape[0], radius, tmin, tmax, step_scale, hit_eps, max_steps)
+        keep = [np.ascontiguousarray(x, dtype=np.float32) if x is not None else None for x in (tmax_per_ray, radius_per_ray)]
+        for name, x in zip(("tmax_per_ray", "radius_per_ray"), keep):
+            if x is not None:
+                if x.shape != (r.shape[0],):
+                    raise ValueError("%s has one entry per ray" % name)
+                setattr(a, name, x.ctypes.data)
+        out = _outputs(a, want, r.shape[0], _FIELD_TRACE)
+        _check(lib().vx_field_sphere_trace(self.h, C.byref(a)))
+        return out
+
+    def sphere_trace_device(self, rays_ptr, nrays, radius=0.0, radius_per_ray_ptr=None, tmin=0.001, tmax=10000.0, tmax_per_ray_ptr=None, step_scale=0.25,
+                            hit_eps=1.0 / 64, max_steps=256, t_ptr=None, clearance_ptr=None, steps_ptr=None, status_ptr=None):
+        """vx_field_sphere_trace_device on raw device pointers, asynchronous on the field's stream."""
+        a = self._trace_args(rays_ptr, nrays, radius, tmin, tmax, step_scale, hit_eps, max_steps)
+        _set_pointers(a, dict(radius_per_ray=radius_per_ray_ptr, tmax_per_ray=tmax_per_ray_ptr, t=t_ptr, clearance=clearance_ptr, steps=steps_ptr,
+                              status=status_ptr))
+        _check(lib().vx_field_sphere_trace_device(self.h, C.byref(a)))
+
+    def free(self):
+        if self.h:
+            lib().vx_field_free(self.h)
         self.h = None
 
     def __del__(self):
