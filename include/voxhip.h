@@ -982,6 +982,41 @@ typedef struct vx_field_trace_args {
 vx_status vx_field_sphere_trace_device(const vx_field* f, const vx_field_trace_args* a);
 vx_status vx_field_sphere_trace(const vx_field* f, const vx_field_trace_args* a);
 
+/* ---- pose queries: a body of points or spheres under many candidate poses, against the sampled field ---------------------------------
+ * A body is num_points points p in its own frame (3 f32 each) with optional radii (world units; NULL: 0).  A pose is a body-to-world
+ * transform m: row-major 3 x 4, 12 f32, the layout of vx_tlas_instance.transform.  THE CONTRACT (float32, in the order written, nothing
+ * fused; csrc/vx_poses.h is this text as code).  For pose n and point i:
+ *     q[a] = ((m[4a]*p[0] + m[4a+1]*p[1]) + m[4a+2]*p[2]) + m[4a+3]      a = 0, 1, 2
+ *     v    = value(q)              the sampled field above: 0x7FC00000 for a non-finite q, +-inf on an EMPTY / FULL field
+ *     g    = (v - radius[i]) + 0.0f          (the + 0.0f turns -0 into +0: equal values have equal bits)
+ * A point whose g is NaN is skipped (a non-finite point, transform entry or radius, an overflowing product, inf - inf); nothing else is:
+ * g = +-inf takes part.  Per pose, each output optional but not all NULL:
+ *     clearance f32      the smallest g over the points not skipped; +inf when there is none
+ *     point     u32      the lowest i among the points whose g equals clearance; 0xFFFFFFFF when there is none
+ *     count     u32      the number of points not skipped with g <= margin
+ *     position  3 f32    q of `point`, by the formula above; 0 0 0 when there is none
+ *     gradient  3 f32    vx_field_sample's gradient at position: the contact normal, pointing out of the solid; 0 0 0 when there is none
+ * Every output is the same bits whatever the launch shape: the reduction is an integer minimum over orderable(g) << 32 | i and an integer
+ * sum.  Checks, before anything is queued, a failure writing nothing: NULL f or a, num_poses > 0 with NULL transforms, num_points > 0
+ * with NULL points, all outputs NULL, a NaN margin (+-inf is allowed) -> VX_ERR_INVALID_ARG; num_points > 0xFFFFFFFE -> VX_ERR_CAPACITY.
+ * Zero poses -> VX_OK, nothing written.  Zero points: every pose gets the answer of "none".
+ * vx_field_poses_device takes device pointers, is asynchronous on the field's stream and does not wait on the host; vx_field_poses takes
+ * host arrays and returns when they are written.  Its staging blocks and the reduction's scratch (12 bytes per pose) stay on the handle:
+ * a repeated call of the same sizes allocates nothing; vx_field_free returns them.
+ * VX_FIELD_POSE_CHUNK / _TILE: how a body of more than 64 points is cut (points per workgroup, poses a workgroup walks).  They do not show
+ * in any result; tests place their sizes around them. */
+#define VX_FIELD_POSE_CHUNK 256
+#define VX_FIELD_POSE_TILE 32
+typedef struct vx_field_pose_args {
+    const float* points; uint64_t num_points;        /* the body: 3 f32 each */
+    const float* radii;                              /* NULL ok: every radius 0 */
+    const float* transforms; uint64_t num_poses;     /* 12 f32 each */
+    float margin;                                    /* world units; not NaN */
+    float* clearance; uint32_t* point; uint32_t* count; float* position /*3 each*/; float* gradient /*3 each*/;   /* each NULL ok, not all */
+} vx_field_pose_args;
+vx_status vx_field_poses_device(const vx_field* f, const vx_field_pose_args* a);
+vx_status vx_field_poses(const vx_field* f, const vx_field_pose_args* a);
+
 /* ---- test aid: the device radix sort the Octree uses for its Morton items (octTree.hpp:363 -> vx_sort.hip), applied to a host array.
  * Keys must have no bit set at or above `bits` (1..64); sorted in place. */
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits);

@@ -26,8 +26,8 @@ FLAGS = EXTRA + ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-m
 # k_walk at 1M and at 8M rays, any value from 8 to 48; no effect on the other kernels (measured on vx_kernels.hip)
 SOURCE_FLAGS = {"vx_walk.hip": ["-mllvm", "-two-entry-phi-node-folding-threshold=16"]}
 
-SOURCES = ["vx_kernels.hip", "vx_trace.hip", "vx_walk.hip", "vx_multihit.hip", "vx_octrace.hip", "vx_octmulti.hip", "vx_bvh.hip", "vx_tlas.hip", "vx_meshmulti.hip", "vx_octree.hip", "vx_sort.hip", "vx_render.hip", "vx_solid.hip", "vx_distance.hip", "vx_morph.hip", "vx_surface.hip", "vx_components.hip", "vx_field.hip", "vx_api.cpp", "vx_obj.cpp", "vx_prof.cpp"]
-HEADERS = ["vx_math.h", "vx_internal.h", "vx_ray.h", "vx_octnode.h", "vx_blas.h", "vx_hitlist.h", "vx_mask.h", "vx_field.h", os.path.join(ROOT, "include", "voxhip.h")]
+SOURCES = ["vx_kernels.hip", "vx_trace.hip", "vx_walk.hip", "vx_multihit.hip", "vx_octrace.hip", "vx_octmulti.hip", "vx_bvh.hip", "vx_tlas.hip", "vx_meshmulti.hip", "vx_octree.hip", "vx_sort.hip", "vx_render.hip", "vx_solid.hip", "vx_distance.hip", "vx_morph.hip", "vx_surface.hip", "vx_components.hip", "vx_field.hip", "vx_poses.hip", "vx_api.cpp", "vx_obj.cpp", "vx_prof.cpp"]
+HEADERS = ["vx_math.h", "vx_internal.h", "vx_ray.h", "vx_octnode.h", "vx_blas.h", "vx_hitlist.h", "vx_mask.h", "vx_field.h", "vx_poses.h", os.path.join(ROOT, "include", "voxhip.h")]
 
 
 def _newer(target, deps):

@@ -85,6 +85,30 @@ public:
         a.t = t.data(); a.status = status.data();
         vxdetail::check(vx_field_sphere_trace(m_field.get(), &a));
     }
+
+    // Pose query: a body of points (x y z each) with radii (world units; empty: all 0) under transforms (body to world, row-major 3 x 4,
+    // 12 floats each) -> per pose the smallest value - radius over the body, the point that has it (0xFFFFFFFF: none) and the number of
+    // points with value - radius <= margin; where asked for, the contact position and the gradient there (3 per pose each).
+    void poses(const std::vector<float>& points, const std::vector<float>& radii, const std::vector<float>& transforms, float margin,
+               std::vector<float>& clearance, std::vector<uint32_t>& point, std::vector<uint32_t>& count, std::vector<float>* position = nullptr,
+               std::vector<float>* gradient = nullptr) const
+    {
+        const size_t np = points.size() / 3, n = transforms.size() / 12;
+        if (!radii.empty() && radii.size() != np) throw std::invalid_argument("poses: one radius per point, or none");
+        clearance.assign(n, 0.0f);
+        point.assign(n, 0u);
+        count.assign(n, 0u);
+        if (position) position->assign(3 * n, 0.0f);
+        if (gradient) gradient->assign(3 * n, 0.0f);
+        vx_field_pose_args a{};
+        a.points = np ? points.data() : nullptr; a.num_points = np;
+        a.radii = radii.empty() ? nullptr : radii.data();
+        a.transforms = n ? transforms.data() : nullptr; a.num_poses = n;
+        a.margin = margin;
+        a.clearance = clearance.data(); a.point = point.data(); a.count = count.data();
+        a.position = position ? position->data() : nullptr; a.gradient = gradient ? gradient->data() : nullptr;
+        if (n) vxdetail::check(vx_field_poses(m_field.get(), &a));
+    }
 };
 
 template <typename T>

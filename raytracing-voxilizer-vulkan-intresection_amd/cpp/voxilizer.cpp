@@ -54,6 +54,13 @@
 //                                       a sphere of radius R (world units) cast along every camera ray of --xray's picture
 //                                       (vx_field_sphere_trace) as a binary 16-bit PGM: 0 = no hit, else 1 + t in sixteenths of the voxel size,
 //                                       at most 65535; same grids and refusals as --probe
+//   --poses POSES.txt --body POINTS.txt [--pose-margin M] [--pose-out FILE]
+//                                       a body of points or spheres ("x y z [radius]" per line, body frame, world units) under the file's poses
+//                                       (12 floats per line: body to world, row-major 3 x 4) against the grid's distance field
+//                                       (vx_field_poses): per pose a line "clearance point count px py pz gx gy gz" (%.9g) to FILE or the
+//                                       standard output -- the smallest value - radius over the body, the point that has it, the number of
+//                                       points within M (default 0), the contact position and the normal there -- and one summary line with
+//                                       the number of colliding poses (count > 0); same grids and refusals as --probe
 //   --nearest FILE [--nearest-inside]   the grid's feature transform (vx_grid_nearest: per cell the index x + X*(y + Y*z) of its nearest occupied
 //                                       cell, the smallest index among equally near ones; --nearest-inside: of its nearest empty cell;
 //                                       0xFFFFFFFF when there is none) as raw little-endian u32, x fastest, X*Y*Z values; one line gives the
@@ -513,6 +520,9 @@ struct FieldOpt {
     std::string probe, probeOut, depth;
     float radius = 0.0f;
     bool radiusGiven = false;
+    std::string poses, body, poseOut;  // --poses POSES.txt --body POINTS.txt [--pose-margin M] [--pose-out FILE]
+    float poseMargin = 0.0f;
+    bool poseMarginGiven = false;
 };
 FieldOpt g_field;
 
@@ -544,6 +554,51 @@ void write_probe(const DistanceField& field)
     const bool ok = std::ferror(f) == 0;
     if (f != stdout && (std::fclose(f) != 0 || !ok)) throw std::runtime_error("cannot write " + g_field.probeOut);
     std::printf("[voxhip] probe: %zu points, %zu in occupied cells\n", n, inside);
+}
+
+// the numbers of every non-empty line of a text file (strtof reads nan and inf)
+std::vector<std::vector<float>> read_number_lines(const std::string& path)
+{
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("cannot read " + path);
+    std::vector<std::vector<float>> rows;
+    for (std::string line; std::getline(in, line);) {
+        std::istringstream ls(line);
+        std::vector<float> row;
+        for (std::string tok; ls >> tok;) row.push_back(std::strtof(tok.c_str(), nullptr));
+        if (!row.empty()) rows.push_back(row);
+    }
+    return rows;
+}
+
+// --poses: "clearance point count px py pz gx gy gz" per pose (%.9g: every float32 survives the round trip; point 4294967295: none)
+void write_poses(const DistanceField& field)
+{
+    std::vector<float> pts, radii, xf;
+    for (const std::vector<float>& r : read_number_lines(g_field.body)) {
+        if (r.size() != 3 && r.size() != 4) throw std::runtime_error(g_field.body + ": a line is \"x y z\" or \"x y z radius\"");
+        pts.insert(pts.end(), r.begin(), r.begin() + 3);
+        radii.push_back(r.size() == 4 ? r[3] : 0.0f);
+    }
+    for (const std::vector<float>& r : read_number_lines(g_field.poses)) {
+        if (r.size() != 12) throw std::runtime_error(g_field.poses + ": a line is 12 numbers, a row-major 3 x 4 transform");
+        xf.insert(xf.end(), r.begin(), r.end());
+    }
+    const size_t n = xf.size() / 12;
+    std::vector<float> clearance, position, gradient;
+    std::vector<uint32_t> point, count;
+    field.poses(pts, radii, xf, g_field.poseMargin, clearance, point, count, &position, &gradient);
+    std::FILE* f = g_field.poseOut.empty() ? stdout : std::fopen(g_field.poseOut.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + g_field.poseOut);
+    size_t colliding = 0;
+    for (size_t i = 0; i < n; ++i) {
+        std::fprintf(f, "%.9g %u %u %.9g %.9g %.9g %.9g %.9g %.9g\n", (double)clearance[i], point[i], count[i], (double)position[3 * i],
+                     (double)position[3 * i + 1], (double)position[3 * i + 2], (double)gradient[3 * i], (double)gradient[3 * i + 1], (double)gradient[3 * i + 2]);
+        colliding += count[i] > 0;
+    }
+    const bool ok = std::ferror(f) == 0;
+    if (f != stdout && (std::fclose(f) != 0 || !ok)) throw std::runtime_error("cannot write " + g_field.poseOut);
+    std::printf("[voxhip] poses: %zu poses of %zu points, margin %.9g: %zu colliding\n", n, pts.size() / 3, (double)g_field.poseMargin, colliding);
 }
 
 void xray_camera(float vi[16], float pi[16], uint32_t W, uint32_t H, const std::string& cameraDump);
@@ -693,9 +748,10 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
         std::printf("[voxhip] sdf: %zu x %zu x %zu cells, min %g max %g\n", vox.dimX(), vox.dimY(), vox.dimZ(), (double)lo, (double)hi);
     }
     if (!g_nearest.file.empty()) write_nearest(vox);
-    if (!g_field.probe.empty() || !g_field.depth.empty()) {
+    if (!g_field.probe.empty() || !g_field.depth.empty() || !g_field.poses.empty()) {
         const DistanceField field = vox.distanceField();
         if (!g_field.probe.empty()) write_probe(field);
+        if (!g_field.poses.empty()) write_poses(field);
         if (!g_field.depth.empty()) write_sphere_depth(field, vox.voxelSize(), rw, rh, cameraDump);
     }
     if (!surfaceFile.empty()) write_surface(vox, surfaceFile, materials);
@@ -732,7 +788,7 @@ int run_grid(const std::string& path, float vs, const std::string& dumpFile, con
 int main(int argc, char** argv)
 {
     if (argc < 3) {  // the reference reads argv[1], argv[2] unchecked (main.cpp:80,163)
-        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--nearest FILE [--nearest-inside]] [--probe POINTS.txt [--probe-out FILE]] [--sphere-depth FILE.pgm --radius R [--size WxH]] [--surface FILE.obj [--smooth N[:LAMBDA:MU]]] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
+        std::fprintf(stderr, "usage: %s <Path to obj file> <Voxlesize> [--grid bool|aabbstruct|vec|octree] [--parallel] [--dump FILE] [--bench RUNS] [--render FILE.ppm [--size WxH] [--camera-dump FILE] [--mesh FILE.obj [--instances FILE]] [--frames N [--attributes]]] [--materials [--dump-materials FILE]] (octree: --render, no --materials) [--gpus N [--logical]] [--solid] [--morph dilate|erode|open|close:RADIUS] [--seal RADIUS] [--sdf FILE] [--nearest FILE [--nearest-inside]] [--probe POINTS.txt [--probe-out FILE]] [--sphere-depth FILE.pgm --radius R [--size WxH]] [--poses POSES.txt --body POINTS.txt [--pose-margin M] [--pose-out FILE]] [--surface FILE.obj [--smooth N[:LAMBDA:MU]]] [--components FILE.csv [--connectivity 6|26]] [--xray FILE.pgm [--size WxH]] [--grid octree --octree-xray FILE.pgm [--size WxH]] [--mesh FILE.obj --mesh-xray FILE.pgm [--size WxH]]\n",
                      argv[0]);
         return 2;
     }
@@ -767,6 +823,10 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--probe") && i + 1 < argc) g_field.probe = argv[++i];
         else if (!std::strcmp(argv[i], "--probe-out") && i + 1 < argc) g_field.probeOut = argv[++i];
         else if (!std::strcmp(argv[i], "--sphere-depth") && i + 1 < argc) g_field.depth = argv[++i];
+        else if (!std::strcmp(argv[i], "--poses") && i + 1 < argc) g_field.poses = argv[++i];
+        else if (!std::strcmp(argv[i], "--body") && i + 1 < argc) g_field.body = argv[++i];
+        else if (!std::strcmp(argv[i], "--pose-out") && i + 1 < argc) g_field.poseOut = argv[++i];
+        else if (!std::strcmp(argv[i], "--pose-margin") && i + 1 < argc) { g_field.poseMargin = std::strtof(argv[++i], nullptr); g_field.poseMarginGiven = true; }
         else if (!std::strcmp(argv[i], "--radius") && i + 1 < argc) { g_field.radius = std::strtof(argv[++i], nullptr); g_field.radiusGiven = true; }
         else if (!std::strcmp(argv[i], "--surface") && i + 1 < argc) surfaceFile = argv[++i];
         else if (!std::strcmp(argv[i], "--smooth") && i + 1 < argc) { if (!parse_smooth(argv[++i], &g_smooth)) { std::fprintf(stderr, "bad --smooth '%s': N[:LAMBDA:MU] with N <= 1024, LAMBDA in [0, 1] and MU in [-1, 0]\n", argv[i]); return 2; } }
@@ -817,6 +877,19 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--probe / --sphere-depth query the distance field of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
         return 2;
     }
+    if (!g_field.poses.empty() && (grid == "octree" || gpus > 1 || benchRuns > 0)) {
+        std::fprintf(stderr, "--poses queries the distance field of one grid on one device: not with --grid octree, --gpus N > 1 or --bench\n");
+        return 2;
+    }
+    if (g_field.poses.empty() != g_field.body.empty()) {
+        std::fprintf(stderr, "--poses POSES.txt and --body POINTS.txt go together: the poses of a body\n");
+        return 2;
+    }
+    if ((!g_field.poseOut.empty() || g_field.poseMarginGiven) && g_field.poses.empty()) {
+        std::fprintf(stderr, "--pose-out and --pose-margin belong to --poses POSES.txt --body POINTS.txt\n");
+        return 2;
+    }
+    if (g_field.poseMargin != g_field.poseMargin) { std::fprintf(stderr, "--pose-margin must be a number (inf and -inf are allowed)\n"); return 2; }
     if (!g_field.probeOut.empty() && g_field.probe.empty()) { std::fprintf(stderr, "--probe-out names the file --probe writes: it needs --probe POINTS.txt\n"); return 2; }
     if (g_field.radiusGiven && g_field.depth.empty()) { std::fprintf(stderr, "--radius is the sphere of --sphere-depth: it needs --sphere-depth FILE.pgm\n"); return 2; }
     if (!g_field.depth.empty() && (!g_field.radiusGiven || !(g_field.radius >= 0.0f) || std::isinf(g_field.radius))) {

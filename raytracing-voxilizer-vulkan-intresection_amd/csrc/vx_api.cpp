@@ -3188,6 +3188,8 @@ struct vx_field : Home {
     DevBuf values{this};
     DevBuf st_in{this}, st_tmax{this}, st_radius{this};            // points or rays, tmax_per_ray, radius_per_ray
     DevBuf st_a{this}, st_b{this}, st_c{this}, st_d{this};         // value / t, gradient / clearance, steps, occupied / status
+    DevBuf st_xf{this}, st_e{this};                                // pose queries: transforms, position (the rest goes through the blocks above)
+    DevBuf pose_keys{this}, pose_counts{this};                     // pose queries: the reduction's scratch, 8 + 4 bytes per pose
 };
 
 // The snapshot: the signed field's passes on the GRID's stream into the field's block (which no query reads meanwhile: the field's stream
@@ -3380,6 +3382,62 @@ static vx_status field_trace_entry(const vx_field* fc, const vx_field_trace_args
 
 vx_status vx_field_sphere_trace_device(const vx_field* f, const vx_field_trace_args* a) { return field_trace_entry(f, a, false); }
 vx_status vx_field_sphere_trace(const vx_field* f, const vx_field_trace_args* a) { return field_trace_entry(f, a, true); }
+
+// Pose queries (vx_poses.hip).  Every check and every block before anything is queued.
+static vx_status field_poses_entry(const vx_field* fc, const vx_field_pose_args* a, bool host)
+{
+    if (!fc || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
+    if (a->num_poses && !a->transforms) return fail(VX_ERR_INVALID_ARG, "null transforms");
+    if (a->num_points && !a->points) return fail(VX_ERR_INVALID_ARG, "null points");
+    if (!a->clearance && !a->point && !a->count && !a->position && !a->gradient) return fail(VX_ERR_INVALID_ARG, "the pose query needs at least one output");
+    if (a->margin != a->margin) return fail(VX_ERR_INVALID_ARG, "margin must not be NaN");
+    if (a->num_points > 0xFFFFFFFEull) return fail(VX_ERR_CAPACITY, "a body has at most 0xFFFFFFFE points");
+    const size_t n = (size_t)a->num_poses, np = (size_t)a->num_points;
+    if (!n) return VX_OK;
+    vx_field* f = const_cast<vx_field*>(fc);
+    DeviceGuard dg(f->device);
+    VX_HIP(f->pose_keys.ensure(n * 8));
+    VX_HIP(f->pose_counts.ensure(n * 4));
+    vx::FieldPoseIO io{};
+    io.points = a->points; io.npoints = (uint32_t)np; io.radii = np ? a->radii : nullptr;
+    io.transforms = a->transforms; io.nposes = n; io.margin = a->margin;
+    io.keys = f->pose_keys.as<unsigned long long>(); io.counts = f->pose_counts.as<uint32_t>();
+    io.clearance = a->clearance; io.point = a->point; io.count = a->count; io.position = a->position; io.gradient = a->gradient;
+    if (!host) {
+        VX_HIP(vx::launch_field_poses(f->values.as<float>(), f->G, io, f->stream));
+        return VX_OK;
+    }
+    void *dc = nullptr, *dg3 = nullptr, *dp = nullptr, *dn = nullptr, *dq = nullptr;
+    VX_TRY(field_stage_out(f->st_a, a->clearance, n * 4, &dc));
+    VX_TRY(field_stage_out(f->st_b, a->gradient, n * 12, &dg3));
+    VX_TRY(field_stage_out(f->st_c, a->point, n * 4, &dp));
+    VX_TRY(field_stage_out(f->st_d, a->count, n * 4, &dn));
+    VX_TRY(field_stage_out(f->st_e, a->position, n * 12, &dq));
+    if (np) VX_HIP(f->st_in.ensure(np * 12));
+    if (io.radii) VX_HIP(f->st_radius.ensure(np * 4));
+    VX_HIP(f->st_xf.ensure(n * 48));
+    const void *dpts = nullptr, *drad = nullptr, *dxf = nullptr;
+    vx_status st = np ? field_stage_in(f, f->st_in, a->points, np * 12, &dpts) : VX_OK;
+    if (st == VX_OK) st = field_stage_in(f, f->st_radius, io.radii, np * 4, &drad);
+    if (st == VX_OK) st = field_stage_in(f, f->st_xf, a->transforms, n * 48, &dxf);
+    if (st == VX_OK) {
+        io.points = static_cast<const float*>(dpts); io.radii = static_cast<const float*>(drad); io.transforms = static_cast<const float*>(dxf);
+        io.clearance = static_cast<float*>(dc); io.gradient = static_cast<float*>(dg3); io.point = static_cast<uint32_t*>(dp);
+        io.count = static_cast<uint32_t*>(dn); io.position = static_cast<float*>(dq);
+        if (vx::launch_field_poses(f->values.as<float>(), f->G, io, f->stream) != hipSuccess) st = fail(VX_ERR_HIP, "k_field_poses: launch failed");
+    }
+    if (st == VX_OK) st = field_copy_back(f, a->clearance, dc, n * 4);
+    if (st == VX_OK) st = field_copy_back(f, a->gradient, dg3, n * 12);
+    if (st == VX_OK) st = field_copy_back(f, a->point, dp, n * 4);
+    if (st == VX_OK) st = field_copy_back(f, a->count, dn, n * 4);
+    if (st == VX_OK) st = field_copy_back(f, a->position, dq, n * 12);
+    const hipError_t e = hipStreamSynchronize(f->stream);  // (also after a failure: the stream may still read the caller's arrays)
+    if (st == VX_OK && e != hipSuccess) st = fail(VX_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    return st;
+}
+
+vx_status vx_field_poses_device(const vx_field* f, const vx_field_pose_args* a) { return field_poses_entry(f, a, false); }
+vx_status vx_field_poses(const vx_field* f, const vx_field_pose_args* a) { return field_poses_entry(f, a, true); }
 
 // ---- rays -----------------------------------------------------------------------------------------------------
 // the grid's traversal structure as launch_trace takes it; *p16: the 16th-prefix table of the word prefix for the rank pass, null where it

@@ -495,6 +495,28 @@ void launch_field_sample(const float* S, const FieldGeom& G, const float* points
                          hipStream_t s);
 void launch_field_trace(const float* S, const FieldGeom& G, const FieldTraceIO& io, hipStream_t s);
 
+// Pose queries on the snapshot (vx_poses.hip; the arithmetic is vx_poses.h's).  Device pointers; keys / counts: nposes entries of scratch
+// each, which the launch initialises itself where it merges into them; each output optional.  A body of more than 64 points is cut into
+// chunks of kPoseChunk points that walk tiles of kPoseTile poses; a smaller one takes a group of lanes per pose, kPoseNarrowRounds poses
+// per group and workgroup.  The shape does not show in the results.
+constexpr uint32_t kPoseChunk = VX_FIELD_POSE_CHUNK, kPoseTile = VX_FIELD_POSE_TILE, kPoseNarrowRounds = 8;
+struct FieldPoseIO {
+    const float* points;
+    uint32_t npoints;
+    const float* radii;
+    const float* transforms;
+    uint64_t nposes;
+    float margin;
+    unsigned long long* keys;
+    uint32_t* counts;
+    float* clearance;
+    uint32_t* point;
+    uint32_t* count;
+    float* position;
+    float* gradient;
+};
+hipError_t launch_field_poses(const float* S, const FieldGeom& G, const FieldPoseIO& io, hipStream_t s);
+
 // Morphology with the digital Euclidean ball (vx_morph.hip).  A domain: its cells and the bits from one (y, z) row to the next -- X for the
 // reference's bitmask, 32 * ceil(X / 32) for a ROW-ALIGNED mask (morph_aligned_words(dim) words, padding bits zero).
 struct MorphDom {

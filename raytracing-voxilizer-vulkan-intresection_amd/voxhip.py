@@ -194,6 +194,12 @@ class FieldTraceArgs(C.Structure):
                 ("max_steps", C.c_uint32), ("t", C.c_void_p), ("clearance", C.c_void_p), ("steps", C.c_void_p), ("status", C.c_void_p)]
 
 
+class FieldPoseArgs(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("num_points", C.c_uint64), ("radii", C.c_void_p), ("transforms", C.c_void_p), ("num_poses", C.c_uint64),
+                ("margin", C.c_float), ("clearance", C.c_void_p), ("point", C.c_void_p), ("count", C.c_void_p), ("position", C.c_void_p),
+                ("gradient", C.c_void_p)]
+
+
 class TraceArgs(C.Structure):
     _fields_ = [("rays", C.c_void_p), ("view_inverse", C.POINTER(C.c_float)), ("proj_inverse", C.POINTER(C.c_float)), ("width", C.c_uint32),
                 ("height", C.c_uint32), ("num_rays", C.c_uint64), ("tmin", C.c_float), ("tmax", C.c_float), ("tmax_per_ray", C.c_void_p),
@@ -271,6 +277,7 @@ SYMBOLS = [
     "vx_grid_nearest_device", "vx_grid_nearest", "vx_grid_nearest_gather_device", "vx_grid_nearest_gather",
     "vx_field_create", "vx_field_update", "vx_field_describe", "vx_field_values_device", "vx_field_free",
     "vx_field_sample_device", "vx_field_sample", "vx_field_sphere_trace_device", "vx_field_sphere_trace",
+    "vx_field_poses_device", "vx_field_poses",
     "vx_grid_morph_device", "vx_grid_morph_mask", "vx_grid_morph", "vx_grid_seal", "vx_morph_bit_radius",
     "vx_grid_surface_device", "vx_grid_surface", "vx_grid_surface_mesh",
     "vx_grid_surface_smooth_device", "vx_grid_surface_smooth", "vx_grid_surface_smooth_mesh",
@@ -415,6 +422,8 @@ def lib():
     L.vx_field_sample.argtypes = [vp, C.POINTER(FieldSampleArgs)]
     L.vx_field_sphere_trace_device.argtypes = [vp, C.POINTER(FieldTraceArgs)]
     L.vx_field_sphere_trace.argtypes = [vp, C.POINTER(FieldTraceArgs)]
+    L.vx_field_poses_device.argtypes = [vp, C.POINTER(FieldPoseArgs)]
+    L.vx_field_poses.argtypes = [vp, C.POINTER(FieldPoseArgs)]
     L.vx_grid_nearest_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_nearest.argtypes = [vp, C.c_uint32, vp, C.c_uint64]
     L.vx_grid_nearest_gather_device.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64]
@@ -1254,6 +1263,10 @@ FIELD_MISS, FIELD_HIT, FIELD_STEP_LIMIT = 0, 1, 2
 # the outputs of the field queries, as _FIRST_HIT
 _FIELD_SAMPLE = {"value": ((), np.float32), "gradient": ((3,), np.float32), "occupied": ((), np.uint8)}
 _FIELD_TRACE = {"t": ((), np.float32), "clearance": ((), np.float32), "steps": ((), np.uint32), "status": ((), np.uint8)}
+_FIELD_POSES = {"clearance": ((), np.float32), "point": ((), np.uint32), "count": ((), np.uint32), "position": ((3,), np.float32),
+                "gradient": ((3,), np.float32)}
+POSE_CHUNK, POSE_TILE = 256, 32   # VX_FIELD_POSE_CHUNK / _TILE: how the pose kernel cuts a body of more than 64 points (no result shows it)
+POSE_NO_POINT = 0xFFFFFFFF
 
 
 class Field:
@@ -1326,6 +1339,39 @@ class Field:
         _set_pointers(a, dict(radius_per_ray=radius_per_ray_ptr, tmax_per_ray=tmax_per_ray_ptr, t=t_ptr, clearance=clearance_ptr, steps=steps_ptr,
                               status=status_ptr))
         _check(lib().vx_field_sphere_trace_device(self.h, C.byref(a)))
+
+    def poses(self, points, transforms, radii=None, margin=0.0, want=("clearance", "point", "count")):
+        """vx_field_poses: a body of host points (P, 3) with optional radii (P,) under host transforms (N, 3, 4) (body to world, row-major)
+        -> dict of the requested outputs, one entry per pose: clearance (N,) float32 (the smallest value - radius over the body; +inf: no
+        point took part), point (N,) uint32 (which point; POSE_NO_POINT), count (N,) uint32 (points within `margin`), position (N, 3)
+        and gradient (N, 3) float32 (the contact point and the normal out of the solid)."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        m = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 12)
+        a = FieldPoseArgs()
+        a.points, a.num_points = p.ctypes.data if p.shape[0] else None, p.shape[0]
+        a.transforms, a.num_poses = m.ctypes.data if m.shape[0] else None, m.shape[0]
+        a.margin = np.float32(margin)
+        r = None
+        if radii is not None:
+            r = np.ascontiguousarray(radii, dtype=np.float32)
+            if r.shape != (p.shape[0],):
+                raise ValueError("radii has one entry per point")
+            a.radii = r.ctypes.data if p.shape[0] else None
+        out = _outputs(a, want, m.shape[0], _FIELD_POSES)
+        _check(lib().vx_field_poses(self.h, C.byref(a)))
+        return out
+
+    def poses_device(self, points_ptr, num_points, transforms_ptr, num_poses, radii_ptr=None, margin=0.0, **output_ptrs):
+        """vx_field_poses_device on raw device pointers, asynchronous on the field's stream; output_ptrs: clearance, point, count,
+        position, gradient -> device pointer."""
+        unknown = set(output_ptrs) - set(_FIELD_POSES)
+        if unknown:
+            raise ValueError("no such pose output: %s" % ", ".join(sorted(unknown)))
+        a = FieldPoseArgs()
+        a.points, a.num_points, a.transforms, a.num_poses = points_ptr, num_points, transforms_ptr, num_poses
+        a.margin = np.float32(margin)
+        _set_pointers(a, dict(radii=radii_ptr, **output_ptrs))
+        _check(lib().vx_field_poses_device(self.h, C.byref(a)))
 
     def free(self):
         if self.h:
