@@ -224,6 +224,59 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
+// The host variants' arrays, through device memory of `home` (the handle: its device and stream), one block each: a pooled one that goes
+// back when the call ends, or `kept`, a block the handle keeps so that a repeated call of the same size asks the pool for nothing.  in()
+// queues an upload, out() notes a download, finish() queues the downloads and waits once.  A null host array is no array: null comes back
+// and its kept block is not touched.  The first failure is kept (status()) and turns every later call into a no-op.  From the first
+// queued upload on the stream reads the caller's arrays, so a Staging that goes out of scope before finish() has waited -- a failed run,
+// a failed ensure or copy -- waits first.
+class Staging {
+    struct Block {
+        DevBuf pooled;  // empty where the array goes through a kept block
+        void* dev;
+        void* host;     // where finish() copies `bytes` back to; null: an input
+        size_t bytes;
+    };
+    const Home& home;
+    std::vector<Block> blocks;
+    vx_status st = VX_OK;
+    bool queued = false;
+
+    void* add(const void* src, void* dst, size_t bytes, size_t spare, DevBuf* kept)
+    {
+        if (st != VX_OK || !(src || dst)) return nullptr;
+        blocks.reserve(10);  // (here, not in the constructor: a Staging that a _device call never uses costs nothing)
+        blocks.push_back(Block{DevBuf{&home}, nullptr, dst, bytes});
+        DevBuf& b = kept ? *kept : blocks.back().pooled;
+        hipError_t e = b.ensure(bytes + spare);
+        if (e == hipSuccess && src) {
+            e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, home.stream);
+            queued = queued || e == hipSuccess;
+        }
+        if (e != hipSuccess) st = fail(VX_ERR_HIP, std::string("staging a host array: ") + hipGetErrorString(e));
+        return blocks.back().dev = st == VX_OK ? b.p : nullptr;  // (the address of the memory, never of the Block: `blocks` may grow)
+    }
+
+public:
+    explicit Staging(const Home& h) : home(h) {}
+    Staging(const Staging&) = delete;
+    Staging& operator=(const Staging&) = delete;
+    ~Staging() { if (queued) (void)hipStreamSynchronize(home.stream); }
+    template <class T> T* in(const T* host, size_t bytes, DevBuf* kept = nullptr) { return static_cast<T*>(add(host, nullptr, bytes, 0, kept)); }
+    // `spare`: bytes of the block behind the array, which the kernel may touch and nobody reads
+    template <class T> T* out(T* host, size_t bytes, size_t spare = 0, DevBuf* kept = nullptr) { return static_cast<T*>(add(nullptr, host, bytes, spare, kept)); }
+    vx_status status() const { return st; }
+    vx_status finish()
+    {
+        VX_TRY(st);
+        for (const Block& b : blocks)
+            if (b.host) VX_HIP(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, home.stream));
+        VX_HIP(hipStreamSynchronize(home.stream));
+        queued = false;
+        return VX_OK;
+    }
+};
+
 vx_status need_device(int dev)
 {
     int n = 0;
@@ -2347,8 +2400,8 @@ static vx_status distance_queue(vx_grid* g, int mode, void* dev_out)
 
 // The ten field entry points (distance_sq / sdf / nearest / nearest_gather / morph, each with its _device variant) in one order: null checks;
 // check(&bytes), the feature's own checks in the header's order -> the bytes the call writes (0: a grid of 0 cells, nothing to do); the
-// guard; queue(g, in, out) on the caller's device pointers, or (host) on the grid's staging blocks: `in` through near_val, the result in
-// g->*stage (`spare` bytes behind it), copied back and waited for.
+// guard; queue(g, in, out) on the caller's device pointers, or (host) on a Staging over blocks the grid keeps: `in` through near_val, the
+// result through g->*stage (`spare` bytes behind it).
 extern "C++" {
 template <class Check, class Queue>
 static vx_status field_entry(const vx_grid* gc, const void* in, bool needs_in, void* out, bool host, DevBuf vx_grid::*stage, size_t spare, Check check,
@@ -2361,16 +2414,12 @@ static vx_status field_entry(const vx_grid* gc, const void* in, bool needs_in, v
     vx_grid* g = const_cast<vx_grid*>(gc);
     DeviceGuard dg(g->device);
     if (!host) return queue(g, in, out);
-    DevBuf& res = g->*stage;
-    VX_HIP(res.ensure(bytes + spare));
-    if (in) {
-        VX_HIP(g->near_val.ensure(bytes));
-        VX_HIP(hipMemcpyAsync(g->near_val.p, in, bytes, hipMemcpyHostToDevice, g->stream));
-    }
-    VX_TRY(queue(g, in ? g->near_val.p : nullptr, res.p));
-    VX_HIP(hipMemcpyAsync(out, res.p, bytes, hipMemcpyDeviceToHost, g->stream));
-    VX_HIP(hipStreamSynchronize(g->stream));
-    return VX_OK;
+    Staging s(*g);
+    out = s.out(out, bytes, spare, &(g->*stage));
+    in = s.in(in, bytes, &g->near_val);
+    VX_TRY(s.status());
+    VX_TRY(queue(g, in, out));
+    return s.finish();
 }
 }  // extern "C++"
 
@@ -3091,12 +3140,11 @@ vx_status vx_grid_aabbs(const vx_grid* gc, vx_aabb* host_out, uint64_t cap, uint
         VX_HIP(hipStreamSynchronize(g->stream));
         return VX_OK;
     }
-    DevBuf tmp{g};
-    VX_HIP(tmp.ensure((size_t)m * sizeof(vx_aabb)));
-    vx::launch_emit_bool_aabbs(g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), g->g, tmp.as<vx_aabb>(), m, g->stream, g->sel_valid ? g->wsel.as<uint32_t>() : nullptr);
-    VX_HIP(hipMemcpyAsync(host_out, tmp.p, (size_t)m * sizeof(vx_aabb), hipMemcpyDeviceToHost, g->stream));
-    VX_HIP(hipStreamSynchronize(g->stream));
-    return VX_OK;
+    Staging s(*g);
+    vx_aabb* list = s.out(host_out, (size_t)m * sizeof(vx_aabb));
+    VX_TRY(s.status());
+    vx::launch_emit_bool_aabbs(g->words.as<uint32_t>(), g->wprefix.as<uint32_t>(), g->g, list, m, g->stream, g->sel_valid ? g->wsel.as<uint32_t>() : nullptr);
+    return s.finish();
 }
 
 vx_status vx_grid_list_wait(vx_grid* g)
@@ -3264,32 +3312,8 @@ void vx_field_free(vx_field* f)
     delete f;
 }
 
-// a host array of the field's host variants through one of the handle's blocks: null stays null; *queued: the stream reads host memory
-static vx_status field_stage_in(vx_field* f, DevBuf& b, const void* host, size_t bytes, const void** dev)
-{
-    *dev = nullptr;
-    if (!host) return VX_OK;
-    VX_HIP(b.ensure(bytes));
-    VX_HIP(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, f->stream));
-    *dev = b.p;
-    return VX_OK;
-}
-
-static vx_status field_stage_out(DevBuf& b, const void* host, size_t bytes, void** dev)
-{
-    *dev = nullptr;
-    if (!host) return VX_OK;
-    VX_HIP(b.ensure(bytes));
-    *dev = b.p;
-    return VX_OK;
-}
-
-static vx_status field_copy_back(vx_field* f, void* host, const void* dev, size_t bytes)
-{
-    if (host) VX_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, f->stream));
-    return VX_OK;
-}
-
+// The three queries in trace_entry's order: the checks, the zero-count return, the guard, then one launch on the caller's device arrays or
+// (host) on a Staging over the handle's st_* blocks.
 static vx_status field_sample_entry(const vx_field* fc, const vx_field_sample_args* a, bool host)
 {
     if (!fc || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
@@ -3299,29 +3323,18 @@ static vx_status field_sample_entry(const vx_field* fc, const vx_field_sample_ar
     if (!n) return VX_OK;
     vx_field* f = const_cast<vx_field*>(fc);
     DeviceGuard dg(f->device);
-    if (!host) {
-        vx::launch_field_sample(f->values.as<float>(), f->G, a->points, n, a->value, a->gradient, a->occupied, f->stream);
-        VX_HIP(hipGetLastError());
-        return VX_OK;
+    vx_field_sample_args io = *a;
+    Staging s(*f);
+    if (host) {
+        io.value = s.out(a->value, n * 4, 0, &f->st_a);
+        io.gradient = s.out(a->gradient, n * 12, 0, &f->st_b);
+        io.occupied = s.out(a->occupied, n, 0, &f->st_d);
+        io.points = s.in(a->points, n * 12, &f->st_in);
+        VX_TRY(s.status());
     }
-    // (every block before the first copy: a failed ensure leaves nothing queued that reads the caller's arrays)
-    void *dv = nullptr, *dg3 = nullptr, *doc = nullptr;
-    VX_TRY(field_stage_out(f->st_a, a->value, n * 4, &dv));
-    VX_TRY(field_stage_out(f->st_b, a->gradient, n * 12, &dg3));
-    VX_TRY(field_stage_out(f->st_d, a->occupied, n, &doc));
-    const void* dp = nullptr;
-    vx_status st = field_stage_in(f, f->st_in, a->points, n * 12, &dp);
-    if (st == VX_OK) {
-        vx::launch_field_sample(f->values.as<float>(), f->G, static_cast<const float*>(dp), n, static_cast<float*>(dv), static_cast<float*>(dg3),
-                                static_cast<uint8_t*>(doc), f->stream);
-        if (hipGetLastError() != hipSuccess) st = fail(VX_ERR_HIP, "k_field_sample: launch failed");
-    }
-    if (st == VX_OK) st = field_copy_back(f, a->value, dv, n * 4);
-    if (st == VX_OK) st = field_copy_back(f, a->gradient, dg3, n * 12);
-    if (st == VX_OK) st = field_copy_back(f, a->occupied, doc, n);
-    const hipError_t e = hipStreamSynchronize(f->stream);  // (also after a failure: the stream may still read the caller's points)
-    if (st == VX_OK && e != hipSuccess) st = fail(VX_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    return st;
+    vx::launch_field_sample(f->values.as<float>(), f->G, io.points, n, io.value, io.gradient, io.occupied, f->stream);
+    VX_HIP(hipGetLastError());
+    return host ? s.finish() : VX_OK;
 }
 
 vx_status vx_field_sample_device(const vx_field* f, const vx_field_sample_args* a) { return field_sample_entry(f, a, false); }
@@ -3348,42 +3361,26 @@ static vx_status field_trace_entry(const vx_field* fc, const vx_field_trace_args
     io.hit_eps = a->hit_eps == 0.0f ? 0.015625f : a->hit_eps;
     io.max_steps = a->max_steps ? a->max_steps : 256u;
     io.t = a->t; io.clearance = a->clearance; io.steps = a->steps; io.status = a->status;
-    if (!host) {
-        vx::launch_field_trace(f->values.as<float>(), f->G, io, f->stream);
-        VX_HIP(hipGetLastError());
-        return VX_OK;
+    Staging s(*f);
+    if (host) {
+        io.t = s.out(io.t, n * 4, 0, &f->st_a);
+        io.clearance = s.out(io.clearance, n * 4, 0, &f->st_b);
+        io.steps = s.out(io.steps, n * 4, 0, &f->st_c);
+        io.status = s.out(io.status, n, 0, &f->st_d);
+        io.rays = s.in(io.rays, n * 24, &f->st_in);
+        io.tmax_per_ray = s.in(io.tmax_per_ray, n * 4, &f->st_tmax);
+        io.radius_per_ray = s.in(io.radius_per_ray, n * 4, &f->st_radius);
+        VX_TRY(s.status());
     }
-    void *dt = nullptr, *dc = nullptr, *ds = nullptr, *dst = nullptr;
-    VX_TRY(field_stage_out(f->st_a, a->t, n * 4, &dt));
-    VX_TRY(field_stage_out(f->st_b, a->clearance, n * 4, &dc));
-    VX_TRY(field_stage_out(f->st_c, a->steps, n * 4, &ds));
-    VX_TRY(field_stage_out(f->st_d, a->status, n, &dst));
-    VX_HIP(f->st_in.ensure(n * 24));
-    if (a->tmax_per_ray) VX_HIP(f->st_tmax.ensure(n * 4));
-    if (a->radius_per_ray) VX_HIP(f->st_radius.ensure(n * 4));
-    const void *dr = nullptr, *dtm = nullptr, *drad = nullptr;
-    vx_status st = field_stage_in(f, f->st_in, a->rays, n * 24, &dr);
-    if (st == VX_OK) st = field_stage_in(f, f->st_tmax, a->tmax_per_ray, n * 4, &dtm);
-    if (st == VX_OK) st = field_stage_in(f, f->st_radius, a->radius_per_ray, n * 4, &drad);
-    if (st == VX_OK) {
-        io.rays = static_cast<const float*>(dr); io.tmax_per_ray = static_cast<const float*>(dtm); io.radius_per_ray = static_cast<const float*>(drad);
-        io.t = static_cast<float*>(dt); io.clearance = static_cast<float*>(dc); io.steps = static_cast<uint32_t*>(ds); io.status = static_cast<uint8_t*>(dst);
-        vx::launch_field_trace(f->values.as<float>(), f->G, io, f->stream);
-        if (hipGetLastError() != hipSuccess) st = fail(VX_ERR_HIP, "k_field_trace: launch failed");
-    }
-    if (st == VX_OK) st = field_copy_back(f, a->t, dt, n * 4);
-    if (st == VX_OK) st = field_copy_back(f, a->clearance, dc, n * 4);
-    if (st == VX_OK) st = field_copy_back(f, a->steps, ds, n * 4);
-    if (st == VX_OK) st = field_copy_back(f, a->status, dst, n);
-    const hipError_t e = hipStreamSynchronize(f->stream);
-    if (st == VX_OK && e != hipSuccess) st = fail(VX_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    return st;
+    vx::launch_field_trace(f->values.as<float>(), f->G, io, f->stream);
+    VX_HIP(hipGetLastError());
+    return host ? s.finish() : VX_OK;
 }
 
 vx_status vx_field_sphere_trace_device(const vx_field* f, const vx_field_trace_args* a) { return field_trace_entry(f, a, false); }
 vx_status vx_field_sphere_trace(const vx_field* f, const vx_field_trace_args* a) { return field_trace_entry(f, a, true); }
 
-// Pose queries (vx_poses.hip).  Every check and every block before anything is queued.
+// Pose queries (vx_poses.hip).  Every check before a block is asked for; the reduction's scratch before the arrays.
 static vx_status field_poses_entry(const vx_field* fc, const vx_field_pose_args* a, bool host)
 {
     if (!fc || !a) return fail(VX_ERR_INVALID_ARG, "null argument");
@@ -3403,37 +3400,20 @@ static vx_status field_poses_entry(const vx_field* fc, const vx_field_pose_args*
     io.transforms = a->transforms; io.nposes = n; io.margin = a->margin;
     io.keys = f->pose_keys.as<unsigned long long>(); io.counts = f->pose_counts.as<uint32_t>();
     io.clearance = a->clearance; io.point = a->point; io.count = a->count; io.position = a->position; io.gradient = a->gradient;
-    if (!host) {
-        VX_HIP(vx::launch_field_poses(f->values.as<float>(), f->G, io, f->stream));
-        return VX_OK;
+    Staging s(*f);
+    if (host) {
+        io.clearance = s.out(io.clearance, n * 4, 0, &f->st_a);
+        io.gradient = s.out(io.gradient, n * 12, 0, &f->st_b);
+        io.point = s.out(io.point, n * 4, 0, &f->st_c);
+        io.count = s.out(io.count, n * 4, 0, &f->st_d);
+        io.position = s.out(io.position, n * 12, 0, &f->st_e);
+        io.points = s.in(np ? io.points : nullptr, np * 12, &f->st_in);  // (a body of no points: no array)
+        io.radii = s.in(io.radii, np * 4, &f->st_radius);
+        io.transforms = s.in(io.transforms, n * 48, &f->st_xf);
+        VX_TRY(s.status());
     }
-    void *dc = nullptr, *dg3 = nullptr, *dp = nullptr, *dn = nullptr, *dq = nullptr;
-    VX_TRY(field_stage_out(f->st_a, a->clearance, n * 4, &dc));
-    VX_TRY(field_stage_out(f->st_b, a->gradient, n * 12, &dg3));
-    VX_TRY(field_stage_out(f->st_c, a->point, n * 4, &dp));
-    VX_TRY(field_stage_out(f->st_d, a->count, n * 4, &dn));
-    VX_TRY(field_stage_out(f->st_e, a->position, n * 12, &dq));
-    if (np) VX_HIP(f->st_in.ensure(np * 12));
-    if (io.radii) VX_HIP(f->st_radius.ensure(np * 4));
-    VX_HIP(f->st_xf.ensure(n * 48));
-    const void *dpts = nullptr, *drad = nullptr, *dxf = nullptr;
-    vx_status st = np ? field_stage_in(f, f->st_in, a->points, np * 12, &dpts) : VX_OK;
-    if (st == VX_OK) st = field_stage_in(f, f->st_radius, io.radii, np * 4, &drad);
-    if (st == VX_OK) st = field_stage_in(f, f->st_xf, a->transforms, n * 48, &dxf);
-    if (st == VX_OK) {
-        io.points = static_cast<const float*>(dpts); io.radii = static_cast<const float*>(drad); io.transforms = static_cast<const float*>(dxf);
-        io.clearance = static_cast<float*>(dc); io.gradient = static_cast<float*>(dg3); io.point = static_cast<uint32_t*>(dp);
-        io.count = static_cast<uint32_t*>(dn); io.position = static_cast<float*>(dq);
-        if (vx::launch_field_poses(f->values.as<float>(), f->G, io, f->stream) != hipSuccess) st = fail(VX_ERR_HIP, "k_field_poses: launch failed");
-    }
-    if (st == VX_OK) st = field_copy_back(f, a->clearance, dc, n * 4);
-    if (st == VX_OK) st = field_copy_back(f, a->gradient, dg3, n * 12);
-    if (st == VX_OK) st = field_copy_back(f, a->point, dp, n * 4);
-    if (st == VX_OK) st = field_copy_back(f, a->count, dn, n * 4);
-    if (st == VX_OK) st = field_copy_back(f, a->position, dq, n * 12);
-    const hipError_t e = hipStreamSynchronize(f->stream);  // (also after a failure: the stream may still read the caller's arrays)
-    if (st == VX_OK && e != hipSuccess) st = fail(VX_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-    return st;
+    VX_HIP(vx::launch_field_poses(f->values.as<float>(), f->G, io, f->stream));
+    return host ? s.finish() : VX_OK;
 }
 
 vx_status vx_field_poses_device(const vx_field* f, const vx_field_pose_args* a) { return field_poses_entry(f, a, false); }
@@ -3577,59 +3557,10 @@ static vx_status args_to_io(const vx_tlas_trace_args& x, vx::Camera* cam, vx::Tr
     return VX_OK;
 }
 
-// The host variants' arrays, through pooled device memory of `home` (the handle: its device and stream), one block each.  in() queues an
-// upload, out() notes a download, finish() queues the downloads and waits once.  A null host array is no array: null comes back.  The
-// first failure is kept (status()) and turns every later call into a no-op.  From the first queued upload on the stream reads the
-// caller's arrays, so a Staging that goes out of scope before finish() has waited -- a failed run, a failed ensure or copy -- waits first.
-extern "C++" {
-class Staging {
-    struct Block {
-        DevBuf buf;
-        void* host;  // where finish() copies `bytes` back to; null: an input
-        size_t bytes;
-    };
-    const Home& home;
-    std::vector<Block> blocks;
-    vx_status st = VX_OK;
-    bool queued = false;
-
-    void* add(const void* src, void* dst, size_t bytes, size_t spare)
-    {
-        if (st != VX_OK || !(src || dst)) return nullptr;
-        blocks.push_back(Block{DevBuf{&home}, dst, bytes});
-        DevBuf& b = blocks.back().buf;
-        hipError_t e = b.ensure(bytes + spare);
-        if (e == hipSuccess && src) {
-            e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, home.stream);
-            queued = queued || e == hipSuccess;
-        }
-        if (e != hipSuccess) st = fail(VX_ERR_HIP, std::string("staging a host array: ") + hipGetErrorString(e));
-        return st == VX_OK ? b.p : nullptr;
-    }
-
-public:
-    explicit Staging(const Home& h) : home(h) { blocks.reserve(10); }
-    Staging(const Staging&) = delete;
-    Staging& operator=(const Staging&) = delete;
-    ~Staging() { if (queued) (void)hipStreamSynchronize(home.stream); }
-    template <class T> T* in(const T* host, size_t bytes) { return static_cast<T*>(add(host, nullptr, bytes, 0)); }
-    // `spare`: bytes of the block behind the array, which the kernel may touch and nobody reads
-    template <class T> T* out(T* host, size_t bytes, size_t spare = 0) { return static_cast<T*>(add(nullptr, host, bytes, spare)); }
-    vx_status status() const { return st; }
-    vx_status finish()
-    {
-        VX_TRY(st);
-        for (const Block& b : blocks)
-            if (b.host) VX_HIP(hipMemcpyAsync(b.host, b.buf.p, b.bytes, hipMemcpyDeviceToHost, home.stream));
-        VX_HIP(hipStreamSynchronize(home.stream));
-        queued = false;
-        return VX_OK;
-    }
-};
-
 // The eight vx_*_trace_ex* entry points: the null checks, the argument checks, (host) the refusal of `hits` and the zero-ray return, the
 // guard, then common(handle, io, bary, instance) on the caller's device arrays or on staged copies of the host arrays.  `given`: the
 // caller's args pointer, `a` its conversion.
+extern "C++" {
 template <class H, class Common>
 static vx_status trace_entry(const H* hc, const void* given, const vx_tlas_trace_args& a, bool host, Common common)
 {
@@ -3948,12 +3879,11 @@ vx_status vx_octree_aabbs(const vx_octree* o, vx_aabb* host_out, uint64_t cap, u
     const uint64_t m = cap < n ? cap : n;
     if (!m || !host_out) return VX_OK;
     DeviceGuard dg(o->device);
-    DevBuf tmp{o};
-    VX_HIP(tmp.ensure((size_t)m * sizeof(vx_aabb)));
-    vx::launch_emit_morton_aabbs(o->items.as<uint64_t>(), m, o->root_min, o->vs, tmp.as<vx_aabb>(), o->stream);
-    VX_HIP(hipMemcpyAsync(host_out, tmp.p, (size_t)m * sizeof(vx_aabb), hipMemcpyDeviceToHost, o->stream));
-    VX_HIP(hipStreamSynchronize(o->stream));
-    return VX_OK;
+    Staging s(*o);
+    vx_aabb* list = s.out(host_out, (size_t)m * sizeof(vx_aabb));
+    VX_TRY(s.status());
+    vx::launch_emit_morton_aabbs(o->items.as<uint64_t>(), m, o->root_min, o->vs, list, o->stream);
+    return s.finish();
 }
 
 // ---- rays on the octree: the grid trace's contract over the vx_octree_aabbs list (vx_octrace.hip) ----------------------------------
