@@ -1039,7 +1039,7 @@ vx_status build_coarse(vx_grid* g, const CoarseBuild& c)
     DeviceGuard dg(g->device);
     for (int a = 0; a < 3; ++a) {
         g->cdim[a] = (g->g.dim[a] + vx::kCoarse - 1) / vx::kCoarse;
-        g->c2dim[a] = (g->cdim[a] + vx::kCoarse - 1) / vx::kCoarse;
+        g->c2dim[a] = (g->cdim[a] + vx::kBlockBricks - 1) / vx::kBlockBricks;
     }
     const uint64_t nc = (uint64_t)g->cdim[0] * g->cdim[1] * g->cdim[2];
     const uint64_t nc2 = (uint64_t)g->c2dim[0] * g->c2dim[1] * g->c2dim[2];

@@ -21,8 +21,14 @@ static_assert(sizeof(TriRec) == 48, "TriRec must be 48 bytes");
 // candidate ranges are kept as 16 + 16 bits per axis in TriRec plus 5 + 6 high bits in a per-triangle extension word (vx_math.h,
 // range_ext).  The limit is inclusive: a triangle may span all 2^21 cells of an axis.
 constexpr uint32_t kMaxDim = 1u << 21;
-constexpr uint32_t kCoarse = 8;        // cells per brick edge, bricks per block edge (ray traversal structure)
+constexpr uint32_t kCoarse = 8;        // cells per brick edge (ray traversal structure)
 constexpr uint32_t kCoarseShift = 3;
+// the traversal structure's block level (level-2 mip, k_walk's and k_multihit's block slabs): 4^3 bricks = 32^3 cells per block
+constexpr uint32_t kBlockBricks = 4;   // bricks per block edge
+constexpr uint32_t kBlockBricksShift = 2;
+constexpr uint32_t kBlockCells = kBlockBricks * kCoarse;   // cells per block edge
+constexpr uint32_t kBlockCellsShift = kBlockBricksShift + kCoarseShift;
+static_assert(kBlockBricks == 1u << kBlockBricksShift && kCoarse == 1u << kCoarseShift && kBlockCells == 32u, "block and brick edges are powers of two");
 constexpr int kScanBlock = 256;
 constexpr int kScanItems = 8;          // elements per thread in the scan kernels
 constexpr int kScanTile = kScanBlock * kScanItems;
@@ -166,7 +172,7 @@ void launch_emit_morton_aabbs(const uint64_t* items, uint64_t n, const float roo
 //   bricks3  the bitmask re-tiled brick-major (8^3 cells) in three orientations, one per possible major axis of a ray:
 //            bricks3[ori][brick][slab along ori], ori 0 x / 1 y / 2 z; orientation 2 holds bit y*8+x per z slab, orientation 0
 //            bit z*8+y per x slab, orientation 1 bit x*8+z per y slab
-//   w1       one bit per brick (dims d1), x-fastest;   w2: one bit per 8^3 bricks (dims d2)
+//   w1       one bit per brick (dims d1), x-fastest;   w2: one bit per block of kBlockBricks^3 bricks (dims d2)
 // (m1 given and bdim[0] % 64 == 0: the brick kernel writes the level-1 mip itself, leaves empty bricks unwritten and returns true)
 struct BricksArgs {
     const uint32_t* tiled = nullptr;                   // the voxelizer's tiled build mask (dim[0] % 32 == 0): the source instead of `words`, and

@@ -539,29 +539,30 @@ ScanTaken launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, bool po
     return ScanTaken::three_pass;  // (*total64 carries no tag)
 }
 
-// Level-2 mip of the traversal structure (vx_walk.hip): one bit per 8x8x8 bricks.  One workgroup per OUTPUT WORD (32 blocks: 16 waves x 2),
-// one lane per (y, z) row of a block's bricks: eight level-1 bits per lane, a ballot per block, one plain store per word -- no atomics, no memset.
-// (the body, for the workgroup that writes word `wg`: k_build_mip2, and the first workgroups of k_mip2_scan)
+// Level-2 mip of the traversal structure (vx_walk.hip): one bit per block of 4x4x4 bricks.  One workgroup per kMip2GroupWords OUTPUT WORDS
+// (256 blocks: 16 waves x 16), one lane per (y, z) row of a block's bricks: four level-1 bits per lane, sixteen lanes per block, so a ballot
+// covers four blocks and four ballots give a wave its half word; the halves meet in LDS, one plain store per word -- no atomics, no memset.
+// (the body, for the workgroup that writes words [wg * kMip2GroupWords, + kMip2GroupWords): k_build_mip2, and the first workgroups of k_mip2_scan)
+constexpr uint32_t kMip2GroupWords = 8;
+static_assert(kBlockBricks == 4 && kMip2GroupWords * 32u == 1024u / 64u * 16u, "mip2_word: 16 lanes per block, 16 blocks per wave, 16 waves");
 __device__ __forceinline__ void mip2_word(uint32_t wg, const uint32_t* __restrict__ m1, uint32_t d1x, uint32_t d1y, uint32_t d1z, uint32_t d2x, uint32_t d2y,
                                           uint32_t d2z, uint32_t* __restrict__ m2)
 {
-    __shared__ uint32_t bits_s;
-    if (threadIdx.x == 0) bits_s = 0u;
-    __syncthreads();
+    __shared__ uint32_t half_s[16];  // [wave]: its sixteen blocks' bits
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint64_t n2 = (uint64_t)d2x * d2y * d2z;
+    const uint64_t c0 = ((uint64_t)wg * kMip2GroupWords + (wv >> 1)) * 32u + (wv & 1u) * 16u;  // the wave's first block
     uint32_t mine = 0u;
-    for (uint32_t k = 0; k < 2u; ++k) {
-        const uint32_t bit = wv * 2u + k;
-        const uint64_t c = (uint64_t)wg * 32u + bit;
+    for (uint32_t it = 0; it < 4u; ++it) {
+        const uint64_t c = c0 + it * 4u + (lane >> 4);
         bool any = false;
         if (c < n2) {
             const uint32_t kz = (uint32_t)(c / ((uint64_t)d2x * d2y));
             const uint32_t rem = (uint32_t)(c - (uint64_t)kz * d2x * d2y);
             const uint32_t ky = rem / d2x, kx = rem - ky * d2x;
-            const uint32_t by = ky * 8u + (lane & 7u), bz = kz * 8u + (lane >> 3), bx0 = kx * 8u;
+            const uint32_t by = ky * kBlockBricks + (lane & 3u), bz = kz * kBlockBricks + ((lane >> 2) & 3u), bx0 = kx * kBlockBricks;
             if (by < d1y && bz < d1z) {
-                const uint32_t nb = d1x - bx0 < 8u ? d1x - bx0 : 8u;
+                const uint32_t nb = d1x - bx0 < kBlockBricks ? d1x - bx0 : kBlockBricks;
                 const uint64_t i0 = (uint64_t)bx0 + (uint64_t)d1x * ((uint64_t)by + (uint64_t)d1y * bz);
                 const uint32_t sh = (uint32_t)i0 & 31u;
                 uint32_t val = m1[i0 >> 5] >> sh;
@@ -569,11 +570,15 @@ __device__ __forceinline__ void mip2_word(uint32_t wg, const uint32_t* __restric
                 any = (val & ((1u << nb) - 1u)) != 0u;
             }
         }
-        if (__ballot(any)) mine |= 1u << bit;
+        const unsigned long long bal = __ballot(any);
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q)
+            if ((bal >> (16u * q)) & 0xFFFFull) mine |= 1u << (it * 4u + q);
     }
-    if (lane == 0u && mine) atomicOr(&bits_s, mine);
+    if (lane == 0u) half_s[wv] = mine;
     __syncthreads();
-    if (threadIdx.x == 0) m2[wg] = bits_s;
+    const uint64_t w = (uint64_t)wg * kMip2GroupWords + threadIdx.x;
+    if (threadIdx.x < kMip2GroupWords && w < (n2 + 31) / 32) m2[w] = half_s[2u * threadIdx.x] | (half_s[2u * threadIdx.x + 1u] << 16);
 }
 
 __global__ __launch_bounds__(1024) void k_build_mip2(const uint32_t* __restrict__ m1, uint32_t d1x, uint32_t d1y, uint32_t d1z, uint32_t d2x, uint32_t d2y,
@@ -586,7 +591,7 @@ void launch_build_mip2(const uint32_t* m1, const uint32_t d1[3], const uint32_t 
 {
     const uint64_t n2 = (uint64_t)d2[0] * d2[1] * d2[2];
     if (!n2) return;
-    VX_KL(k_build_mip2, dim3((unsigned)((n2 + 31) / 32)), dim3(1024), 0, s, m1, d1[0], d1[1], d1[2], d2[0], d2[1], d2[2], m2);
+    VX_KL(k_build_mip2, dim3((unsigned)(((n2 + 31) / 32 + kMip2GroupWords - 1) / kMip2GroupWords)), dim3(1024), 0, s, m1, d1[0], d1[1], d1[2], d2[0], d2[1], d2[2], m2);
 }
 
 // The level-2 mip and the scan of the brick kernel's line counts in ONE launch: both read only what k_build_bricks3 wrote (the level-1 mip,
@@ -608,7 +613,7 @@ __global__ __launch_bounds__(kOneBlock) void k_mip2_scan(const uint32_t* __restr
 ScanTaken launch_mip2_scan(const uint32_t* m1, const uint32_t d1[3], const uint32_t d2[3], uint32_t* m2, const uint32_t* in, uint32_t* out, uint64_t n, void* tmp,
                            unsigned long long* total64, hipStream_t s, unsigned long long total_tag, uint32_t gen)
 {
-    const uint64_t n_mip = ((uint64_t)d2[0] * d2[1] * d2[2] + 31) / 32;
+    const uint64_t n_mip = (((uint64_t)d2[0] * d2[1] * d2[2] + 31) / 32 + kMip2GroupWords - 1) / kMip2GroupWords;  // the mip's workgroups
     const uint64_t ntiles = ((n + 1) + kOneTile - 1) / kOneTile;
     const bool aligned = ((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0;
     if (!n_mip || !aligned || !gen || n_mip + ntiles > 0x7FFFFFFFull) {

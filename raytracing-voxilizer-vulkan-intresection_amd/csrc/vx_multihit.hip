@@ -9,7 +9,7 @@
 // Enumeration.  The candidate cells come from the major-axis slab walk of vx_walk.hip, on the structure k_build_bricks3 / k_build_mip2 make for
 // it (level-0 bricks in the orientation of the ray's major axis, level-1 and level-2 mips): the same position tolerance, the same [ta, tb] of
 // a slab, ta = inv_w * ((P_near -/+ tol) - o_w), tb = inv_w * ((P_far +/- tol) - o_w), the same u/v rectangle
-// [min(p(ta), p(tb)) - 2 tol, max(p(ta), p(tb)) + 2 tol] at 64-cell, 8-cell and 1-cell granularity.  The superset argument at the head of
+// [min(p(ta), p(tb)) - 2 tol, max(p(ta), p(tb)) + 2 tol] at 32-cell, 8-cell and 1-cell granularity.  The superset argument at the head of
 // vx_walk.hip carries over word for word: every cell whose float box the ray can enter lies in the rectangle of its 1-cell slab, and every
 // box of a slab has a computed entry time >= the slab's ta.  k_walk keeps that argument in a state machine built for its persistent waves;
 // here the same expressions stand in three nested loops (block slabs, the brick slabs of an occupied block rectangle, the occupied bricks of
@@ -48,7 +48,7 @@ struct MultiParams {
     const uint32_t* w0;                 // the reference-layout bitmask and its word prefix (prim)
     const uint32_t* prefix;
     const uint32_t* w1;                 // level-1 mip: one bit per brick
-    const uint32_t* w2;                 // level-2 mip: one bit per 8^3 bricks
+    const uint32_t* w2;                 // level-2 mip: one bit per 4^3 bricks
     uint32_t d1[3], d2[3];
     float inv_vs;
     uint32_t K;
@@ -198,23 +198,24 @@ __global__ __launch_bounds__(kMultiBlock) void k_multihit(const MultiParams P)
             const float pw = sel3f(p, ox + tn * dx, oy + tn * dy, oz + tn * dz);
             int cw = (int)floorf((pw - R.orgw) * P.inv_vs) + (R.pos ? -1 : 1);  // one cell of slack against the rounding of this estimate
             cw = cw < 0 ? 0 : (cw > R.dimw - 1 ? R.dimw - 1 : cw);
-            const int nk2 = (R.dimw + 63) >> 6, nk1 = (R.dimw + 7) >> 3;
+            constexpr int kBlkShift = (int)kBlockCellsShift, kBlkBricksShift = (int)kBlockBricksShift, kBlkBricks = (int)kBlockBricks;
+            const int nk2 = (R.dimw + (int)kBlockCells - 1) >> kBlkShift, nk1 = (R.dimw + 7) >> 3;
             bool done = false;
-            // ---- block slabs (64 cells), from the one that holds the entry point
-            for (int k2 = cw >> 6; k2 >= 0 && k2 < nk2 && !done; k2 += s) {
+            // ---- block slabs (32 cells), from the one that holds the entry point
+            for (int k2 = cw >> kBlkShift; k2 >= 0 && k2 < nk2 && !done; k2 += s) {
                 float ta, tb;
-                const int e2 = (k2 + 1) << 6;
-                slab_interval(R, g.vs, k2 << 6, e2 > R.dimw ? R.dimw : e2, ta, tb);
+                const int e2 = (k2 + 1) << kBlkShift;
+                slab_interval(R, g.vs, k2 << kBlkShift, e2 > R.dimw ? R.dimw : e2, ta, tb);
                 if (ta > R.tf || (!counting && n == K && ta > kth)) break;  // beyond the interval / no box from here on can enter the list
                 MhRect q2;
                 if (!slab_rect(R, P.inv_vs, ta, tb, q2)) continue;
                 bool occ2 = false;
-                for (int cv = q2.v0 >> 6; cv <= (q2.v1 >> 6); ++cv)
-                    for (int cu = q2.u0 >> 6; cu <= (q2.u1 >> 6); ++cu) occ2 |= mip_bit(P.w2, P.d2, p, cu, cv, k2);
+                for (int cv = q2.v0 >> kBlkShift; cv <= (q2.v1 >> kBlkShift); ++cv)
+                    for (int cu = q2.u0 >> kBlkShift; cu <= (q2.u1 >> kBlkShift); ++cu) occ2 |= mip_bit(P.w2, P.d2, p, cu, cv, k2);
                 if (!occ2) continue;
                 // ---- its brick slabs (8 cells), in travel order
-                for (int j = 0; j < 8 && !done; ++j) {
-                    const int k1 = (k2 << 3) + (R.pos ? j : 7 - j);
+                for (int j = 0; j < kBlkBricks && !done; ++j) {
+                    const int k1 = (k2 << kBlkBricksShift) + (R.pos ? j : kBlkBricks - 1 - j);
                     if (k1 >= nk1) continue;
                     const int e1 = (k1 + 1) << 3;
                     slab_interval(R, g.vs, k1 << 3, e1 > R.dimw ? R.dimw : e1, ta, tb);

@@ -7,7 +7,7 @@
 // the lanes of a wave, and provably a superset of the cells whose float boxes the ray can enter:
 //
 //   Let w be the axis of the largest |direction| component, u and v the other two.  The grid is cut into slabs perpendicular to
-//   w at three granularities: 64 cells (block slabs, level 2), 8 cells (brick slabs, level 1), 1 cell (level 0).  For a slab with lattice
+//   w at three granularities: 32 cells (block slabs, level 2), 8 cells (brick slabs, level 1), 1 cell (level 0).  For a slab with lattice
 //   planes P_near, P_far (in travel order) the ray is within the position tolerance `tol` of the slab for
 //        t in [ta, tb],  ta = inv_w * ((P_near -/+ tol) - o_w),  tb = inv_w * ((P_far +/- tol) - o_w)
 //   -- the same expression form as hitAabb's `invDir * (plane - origin)` (rint:49-50), so by monotonicity of float subtraction
@@ -20,8 +20,9 @@
 //
 // A step of the walk = one slab, the same code at every level: the slab's [ta, tb], the termination test, the rectangle.  A
 // block slab (level 2) or brick slab (level 1) looks its rectangle up in the occupancy mip of its level; an occupied block
-// rectangle descends to its eight brick slabs; the occupied bricks of a brick slab's rectangle are walked one after the other at
-// level 0.  Entering a brick costs ONE 64-byte line -- its eight slab words -- and drops the slabs whose word misses the
+// rectangle descends to its four brick slabs; the occupied bricks of a brick slab's rectangle are walked one after the other at
+// level 0 -- in large batches in the order the ray visits them, and not at all once a hit is known that the ray reaches before it can
+// enter the brick.  Entering a brick costs ONE 64-byte line -- its eight slab words -- and drops the slabs whose word misses the
 // rectangle the ray sweeps across the whole brick; each remaining slab ANDs its own (tighter) rectangle with its word, and the
 // surviving cells go through the exact rint formula on the float box the reference would have built for them, which is the only
 // arbiter of hit and t -- the reported t is the very float the brute-force minimum yields.
@@ -31,7 +32,7 @@
 //   level 0  "bricks": the bitmask re-tiled brick-major in THREE orientations, one per possible major axis: for orientation w one
 //            uint64 per (8x8x8 brick, slab along w), bit = (v&7)*8 + (u&7) with (u, v) = the axes after w cyclically.  Whatever
 //            the ray's major axis, a brick is one contiguous 64-byte line of eight slab words.
-//   level 1  one bit per brick, x-fastest; level 2 one bit per 8^3 bricks; both staged in LDS by every workgroup when they fit.
+//   level 1  one bit per brick, x-fastest; level 2 one bit per 4^3 bricks; both staged in LDS by every workgroup when they fit.
 //
 // Wave efficiency.  Persistent waves; a lane whose ray has finished takes the next ray of its wave's chunk of a global queue
 // (first chunk static, later ones by one atomicAdd of a guided size).  Every busy lane executes the same slab step whatever its
@@ -267,6 +268,9 @@ namespace {
 // Two cell (or brick) coordinates in one register: 16 + 16 bits -- every grid whose axes have at most 65535 cells -- or, WIDE, 32 + 32
 // bits (grids with an axis of up to 2^21 cells; the reference's dims are size_t, VoxelBuilder.hpp:347-349).  The wide form costs four
 // registers and is compiled only into the variants that walk such grids.
+// the block level as the walk's signed arithmetic reads it (vx_internal.h): block slabs of kBlkCells cells = kBlkBricks brick slabs
+constexpr int kBlkShift = (int)kBlockCellsShift, kBlkCells = (int)kBlockCells, kBlkBricksShift = (int)kBlockBricksShift, kBlkBricks = (int)kBlockBricks;
+
 template <bool WIDE> struct Pk { typedef uint32_t T; };
 template <> struct Pk<true> { typedef unsigned long long T; };
 template <bool WIDE> __device__ __forceinline__ typename Pk<WIDE>::T pk_make(int lo, int hi)
@@ -293,11 +297,12 @@ struct WalkLane {
     int lvl, k;              // current slab: level (2 block slabs, 1 brick slabs; 0: inside a brick of brick slab k) and its index along w
     int cw0;                 // cell index along w where this ray (or piece) starts, one cell of slack: slabs wholly in front of it are never looked at
     // occupied bricks of the current brick slab's rectangle, waiting for the brick phase
-    uint32_t pend;           // bits 0..15: brick jb + j = (cu0 + (jb + j) % nu, cv0 + (jb + j) / nu) is occupied; bits 16..30: nu (WIDE: in nu_w); bit 31: more windows
+    uint32_t pend;           // bits 0..15: brick jb + j = (cu0 + (jb + j) % nu, cv0 + (jb + j) / nu) is occupied; bits 16..29: nu (WIDE: in nu_w); bit 31: more windows
+                             // bit 30 (kPendTravel): the rule's 2 x 2 form, bits 0..3 in VISITING order -- bit j = brick (cu0 + ((j & 1) ^ (du < 0)), cv0 + ((j >> 1) ^ (dv < 0)))
     int jb;                  // first rectangle cell of the current 16-cell window (0 unless the rectangle has more than 16 cells)
     typename Pk<WIDE>::T pc;      // cu0 | cv0 << 16 (WIDE: << 32)
     typename Pk<WIDE>::T pu, pv;  // the slab's cell rectangle: u0 | u1 << 16, v0 | v1 << 16
-    int nu_w;                // WIDE only: the rectangle's width in bricks (does not fit 15 bits)
+    int nu_w;                // WIDE only: the rectangle's width in bricks (does not fit the 14 bits pend has for it)
     // level 0: the brick being walked -- its eight slab words (one 64-byte line) and the slabs still to look at
     unsigned long long w0, w1, w2, w3, w4, w5, w6, w7;
     uint32_t sm;             // bit s: slab s of the brick may hold a cell the ray touches (word & brick-level rectangle != 0)
@@ -394,7 +399,7 @@ __device__ __forceinline__ bool walk_setup(WalkLane<IdxT, WIDE>& R, const GridPa
     const float pw = sel3f(p, ox + tn * dx, oy + tn * dy, oz + tn * dz);
     int cw = (int)floorf((pw - R.orgw) * inv_vs) + (pos ? -1 : 1);
     cw = cw < 0 ? 0 : (cw > R.dimw - 1 ? R.dimw - 1 : cw);
-    R.k = cw >> 6;
+    R.k = cw >> kBlkShift;
     R.cw0 = cw;
     return true;
 }
@@ -411,7 +416,7 @@ struct WalkHot {
     const unsigned long long* bricks3;  // [3 orientations][bricks][8 slabs]
     uint64_t ori_stride;                // uint64 words per orientation
     const uint32_t* w1;                 // level-1 mip: one bit per brick
-    const uint32_t* w2;                 // level-2 mip: one bit per 8^3 bricks
+    const uint32_t* w2;                 // level-2 mip: one bit per 4^3 bricks
     uint32_t d1[3], d2[3];
     float inv_vs;
     float tmin;
@@ -493,6 +498,7 @@ __device__ unsigned long long g_walk_hist[2 * 16];  // rays by slab steps (bucke
 // started last, a span counted in rounds -- and a round's fixed part (ballots, the exact-test, brick and retire phases) is paid per round:
 // more steps per round shorten it.  A large batch is bound by instruction issue, where the lanes that sit out the rest of a round (parked
 // candidates, a brick to fetch, a finished ray) cost more the longer the round is.  Measured: DESIGN.md section 8, "Round 9".
+// The same boundary decides k_walk's TRAVEL parameter (sibling bricks in travel order, pruned by their entry plane): section 8, "Round 10".
 #ifndef VX_W_STEPS_FEW
 #define VX_W_STEPS_FEW 4
 #endif
@@ -524,7 +530,7 @@ __device__ unsigned long long g_walk_hist[2 * 16];  // rays by slab steps (bucke
 #define VX_W_NARROW_RAYS 1040ull     // ... this many rays, where that is fewer than a resident set
 #endif
 
-// After a slab has been dealt with: on to the next one -- and up to the block level at the end of a block slab's eight brick
+// After a slab has been dealt with: on to the next one -- and up to the block level at the end of a block slab's four brick
 // slabs.  Returns false when the walk leaves the grid.
 template <typename IdxT, bool WIDE>
 __device__ __forceinline__ bool walk_advance(WalkLane<IdxT, WIDE>& R)
@@ -532,26 +538,58 @@ __device__ __forceinline__ bool walk_advance(WalkLane<IdxT, WIDE>& R)
     const int s = R.iw > 0.0f ? 1 : -1;
     const int k = R.k;
     int nl = 1, kn = k + s;
-    if (R.lvl == 2 || (kn >> 3) != (k >> 3)) { nl = 2; kn = (R.lvl == 2 ? k : (k >> 3)) + s; }
-    const int ncw = (R.dimw + (nl == 2 ? 63 : 7)) >> (nl == 2 ? 6 : 3);
+    if (R.lvl == 2 || (kn >> kBlkBricksShift) != (k >> kBlkBricksShift)) { nl = 2; kn = (R.lvl == 2 ? k : (k >> kBlkBricksShift)) + s; }
+    const int ncw = (R.dimw + (nl == 2 ? kBlkCells - 1 : 7)) >> (nl == 2 ? kBlkShift : 3);
     if (kn < 0 || kn >= ncw) return false;  // left the grid
     R.lvl = nl;
     R.k = kn;
     return true;
 }
 
+constexpr uint32_t kPendTravel = 1u << 30;  // WalkLane::pend: the 2 x 2 form in visiting order
+
+// The rectangle cell (ju, jv) of the lowest pending bit of R.pend (one is set).  The 2 x 2 form holds its bits in the order the ray
+// visits the bricks -- columns mirrored when it travels down u, rows when it travels down v: a brick the ray enters later never stands
+// in front of one it enters earlier -- and the mirror is undone here, from the signs of R.du and R.dv.  (A zero or negative-zero
+// component counts as "up": with no travel along an axis either order of that axis is a visiting order.)  Windows keep index order.
+template <bool TRAVEL, typename IdxT, bool WIDE>
+__device__ __forceinline__ void walk_pend_cell(const WalkLane<IdxT, WIDE>& R, int& ju, int& jv)
+{
+    const int jj = __ffs(R.pend & 0xFFFFu) - 1;
+    if (TRAVEL && (R.pend & kPendTravel)) {
+        const int m = jj ^ ((R.du < 0.0f ? 1 : 0) | (R.dv < 0.0f ? 2 : 0));
+        ju = m & 1;
+        jv = (m >> 1) & 1;
+    } else {
+        const int nu = WIDE ? R.nu_w : (int)((R.pend >> 16) & 0x3FFFu);
+        jv = 0;
+        ju = R.jb + jj;  // j = jv * nu + ju, by subtraction (nu >= 1)
+        while (ju >= nu) { ju -= nu; ++jv; }
+    }
+}
+
+// The earliest time at which the ray can be inside brick (cu, cv) of a brick slab, from the u and v lattice planes it enters the brick
+// through: te = max(te_u, te_v) -- walk_step's ta with u (v) in the place of w.  Travelling up u the entry plane is the brick's low plane
+// less the tolerance, travelling down u its far plane (clamped to the grid, as a slab's i1 is) plus the tolerance; an axis without travel
+// sets no bound (-inf).  Every box of the brick has a COMPUTED hitAabb t0 >= te (K6 notes, "sibling prune"): with best < te none can win.
+template <typename IdxT, bool WIDE>
+__device__ __forceinline__ float walk_brick_entry(const WalkLane<IdxT, WIDE>& R, float vs, int cu, int cv)
+{
+    const int fu = (cu + 1) << 3, fv = (cv + 1) << 3;
+    const float pu = R.du > 0.0f ? (R.orgu + (float)(cu << 3) * vs) - R.tol : (R.orgu + (float)(fu > R.dimu ? R.dimu : fu) * vs) + R.tol;
+    const float pv = R.dv > 0.0f ? (R.orgv + (float)(cv << 3) * vs) - R.tol : (R.orgv + (float)(fv > R.dimv ? R.dimv : fv) * vs) + R.tol;
+    const float te_u = R.du != 0.0f ? R.iu * (pu - R.ou) : -INFINITY;
+    const float te_v = R.dv != 0.0f ? R.iv * (pv - R.ov) : -INFINITY;
+    return fmaxf(te_u, te_v);  // (a NaN -- an infinite reciprocal times a zero distance -- drops out of the maximum or leaves a NaN: no prune)
+}
+
 // Level 0, entering a brick: the brick's eight slab words are ONE 64-byte line (four 16-byte loads in flight together -- the
 // walk is bound by dependent memory round trips, not by issue); slabs whose word misses the rectangle the ray sweeps across the
 // whole brick slab are dropped here without any arithmetic.
 template <typename IdxT, bool WIDE>
-__device__ __forceinline__ void walk_fetch_brick(WalkLane<IdxT, WIDE>& R, const WalkHot& P VX_W_SITE_DECL)
+__device__ __forceinline__ void walk_fetch_brick(WalkLane<IdxT, WIDE>& R, const WalkHot& P, int cu, int cv VX_W_SITE_DECL)
 {
     VX_W_SITE(3)
-    const int nu = WIDE ? R.nu_w : (int)((R.pend >> 16) & 0x7FFFu);
-    const int j = R.jb + __ffs(R.pend & 0xFFFFu) - 1;
-    int jv = 0, ju = j;  // j = jv * nu + ju, by subtraction (nu >= 1)
-    while (ju >= nu) { ju -= nu; ++jv; }
-    const int cu = pk_lo<WIDE>(R.pc) + ju, cv = pk_hi<WIDE>(R.pc) + jv;
     int bx, by, bz;
     unperm(R.perm, cu, cv, R.k, bx, by, bz);
     const uint32_t bi = (uint32_t)bx + P.d1[0] * ((uint32_t)by + P.d1[1] * (uint32_t)bz);
@@ -576,20 +614,31 @@ __device__ __forceinline__ void walk_fetch_brick(WalkLane<IdxT, WIDE>& R, const 
 
 // Level 0, a brick is done (or a brick slab's rectangle has just been found occupied): on to the next occupied brick of the
 // rectangle; after the last one back to level 1 and on to the next slab.  Returns false when the ray is finished.
-template <typename IdxT, bool WIDE>
+template <bool TRAVEL, typename IdxT, bool WIDE>
 __device__ __forceinline__ bool walk_bricks(WalkLane<IdxT, WIDE>& R, const WalkHot& P, bool pop, bool dead VX_W_SITE_DECL)
 {
+    const bool hit = R.best_idx != (IdxT)~(IdxT)0;
     for (;;) {
         if (pop) {  // R.pc goes back to the rectangle's first brick for the decode of the next one
-            const uint32_t low = R.pend & 0xFFFFu;
-            const int nu = WIDE ? R.nu_w : (int)((R.pend >> 16) & 0x7FFFu);
-            int jv = 0, ju = R.jb + __ffs(low) - 1;  // the finished brick was rectangle cell j = jb + ffs(low) - 1
-            while (ju >= nu) { ju -= nu; ++jv; }
+            int ju, jv;  // the finished brick was the lowest pending bit
+            walk_pend_cell<TRAVEL>(R, ju, jv);
             R.pc = pk_make<WIDE>(pk_lo<WIDE>(R.pc) - ju, pk_hi<WIDE>(R.pc) - jv);
+            const uint32_t low = R.pend & 0xFFFFu;
             R.pend = (R.pend & 0xFFFF0000u) | (low & (low - 1u));
+            pop = false;
         }
         if (!(R.pend & 0xFFFFu)) break;
-        walk_fetch_brick(R, P VX_W_SITE_ARGS);
+        int ju, jv;
+        walk_pend_cell<TRAVEL>(R, ju, jv);
+        const int cu = pk_lo<WIDE>(R.pc) + ju, cv = pk_hi<WIDE>(R.pc) + jv;
+        // sibling prune: a hit is known and the ray cannot be inside this brick before it -- dropped without its fetch, and a run of such
+        // bricks without a round (strict: an equal t with a lower voxel index is still looked for)
+        if (TRAVEL && hit && R.best < walk_brick_entry(R, P.g.vs, cu, cv)) {
+            const uint32_t low = R.pend & 0xFFFFu;
+            R.pend = (R.pend & 0xFFFF0000u) | (low & (low - 1u));
+            continue;
+        }
+        walk_fetch_brick(R, P, cu, cv VX_W_SITE_ARGS);
         if (R.sm != 0u) return true;
         pop = true;  // nothing of this brick inside the rectangle: on to the next without spending a step
     }
@@ -605,7 +654,7 @@ __device__ __forceinline__ bool walk_bricks(WalkLane<IdxT, WIDE>& R, const WalkH
 // One step of the walk = one slab: a block slab (level 2), a brick slab (level 1), or one 1-cell slab of the brick being walked
 // (level 0).  All three share the slab's [ta, tb], the termination test and the rectangle of cells; they differ in what the
 // rectangle is looked up in.  Returns false when the ray is finished.
-template <bool LDS_MIPS, typename IdxT, bool WIDE>
+template <bool LDS_MIPS, bool TRAVEL, typename IdxT, bool WIDE>
 __device__ __forceinline__ bool walk_step(WalkLane<IdxT, WIDE>& R, const WalkHot& P, const uint32_t* __restrict__ mips_lds, bool& xpend, uint4* __restrict__ xslot,
                                           uint32_t* __restrict__ xslot_hi /*WIDE: the upper half of the parked brick coordinates*/, uint32_t& fstate VX_W_SITE_DECL)
 {
@@ -620,7 +669,7 @@ __device__ __forceinline__ bool walk_step(WalkLane<IdxT, WIDE>& R, const WalkHot
         sl = pos ? (__ffs(R.sm) - 1) : (31 - __clz(R.sm));  // next candidate slab of the brick in travel order
         R.sm &= ~(1u << sl);
     }
-    const int sh = lvl == 2 ? 6 : (lvl == 1 ? 3 : 0);
+    const int sh = lvl == 2 ? kBlkShift : (lvl == 1 ? 3 : 0);
     const int k = lvl == 0 ? (R.k << 3) + sl : R.k;
     const int i0 = k << sh;
     int i1 = (k + 1) << sh;
@@ -701,7 +750,14 @@ __device__ __forceinline__ bool walk_step(WalkLane<IdxT, WIDE>& R, const WalkHot
                     w00 = mp[i00 >> 5]; w10 = mp[i10 >> 5]; w01 = mp[i01 >> 5]; w11 = mp[i11 >> 5];
                 }
                 const uint32_t b00 = (w00 >> (i00 & 31u)) & 1u, b10 = (w10 >> (i10 & 31u)) & 1u, b01 = (w01 >> (i01 & 31u)) & 1u, b11 = (w11 >> (i11 & 31u)) & 1u;
-                if (n > 0) occ = b00 | (hu ? b10 << 1 : 0u) | (hv ? b01 << nu : 0u) | ((hu && hv) ? b11 << 3 : 0u);
+                if (top || !TRAVEL) {
+                    if (n > 0) occ = b00 | (hu ? b10 << 1 : 0u) | (hv ? b01 << nu : 0u) | ((hu && hv) ? b11 << 3 : 0u);
+                } else if (n > 0) {
+                    // bricks: in visiting order (walk_pend_cell) -- cell (ju, jv) at bit ((jv << 1) | ju) ^ mir
+                    const uint32_t mir = (R.du < 0.0f ? 1u : 0u) | (R.dv < 0.0f ? 2u : 0u);
+                    occ = (b00 << mir) | (hu ? b10 << (mir ^ 1u) : 0u) | (hv ? b01 << (mir ^ 2u) : 0u) | ((hu && hv) ? b11 << (mir ^ 3u) : 0u);
+                    if (occ) occ |= kPendTravel;
+                }
             } else {
                 int ju = jb, jv = 0;
                 while (ju >= nu && nu > 0) { ju -= nu; ++jv; }
@@ -719,12 +775,13 @@ __device__ __forceinline__ bool walk_step(WalkLane<IdxT, WIDE>& R, const WalkHot
             }
             const bool more = jend < n;
             if (occ) {
-                if (top) {  // down into the eight brick slabs of this block slab
+                if (top) {  // down into the four brick slabs of this block slab
                     const int ncw = (R.dimw + 7) >> 3;
                     // the first brick slab of this block slab -- not in front of the ray's start cell
                     const int ks = R.cw0 >> 3;
-                    int kf = pos ? ((k << 3) > ks ? (k << 3) : ks) : ((k << 3) + 7 < ks ? (k << 3) + 7 : ks);
-                    kf = kf < (k << 3) ? (k << 3) : (kf > (k << 3) + 7 ? (k << 3) + 7 : kf);
+                    const int kb0 = k << kBlkBricksShift, kb1 = kb0 + kBlkBricks - 1;  // the block slab's first and last brick slab
+                    int kf = pos ? (kb0 > ks ? kb0 : ks) : (kb1 < ks ? kb1 : ks);
+                    kf = kf < kb0 ? kb0 : (kf > kb1 ? kb1 : kf);
                     kf = kf > ncw - 1 ? ncw - 1 : kf;
                     R.lvl = 1;
                     R.k = kf;
@@ -732,7 +789,7 @@ __device__ __forceinline__ bool walk_step(WalkLane<IdxT, WIDE>& R, const WalkHot
                     return true;
                 }
                 // the occupied bricks of this brick slab's rectangle: walked one after the other at level 0
-                R.pend = occ | (WIDE ? 0u : ((uint32_t)nu << 16)) | (more ? 0x80000000u : 0u);
+                R.pend = occ | ((WIDE || (occ & kPendTravel)) ? 0u : ((uint32_t)nu << 16)) | (more ? 0x80000000u : 0u);
                 if (WIDE) R.nu_w = nu;
                 R.pc = pk_make<WIDE>(cu0, cv0);
                 R.pu = pk_make<WIDE>(u0, u1);
@@ -820,7 +877,7 @@ __device__ __forceinline__ float shfl_fw(float v, int src) { return __shfl(v, sr
 // Persistent waves with dynamic work fetch.  Exit condition every wave reaches: the work counter passes the ray count (no
 // refill possible) and every lane's ray has finished; a ray finishes in a bounded number of slabs (its index along the major
 // axis is monotone at both levels).
-template <bool LDS_MIPS, typename IdxT, bool WIDE = false, int STEPS = VX_W_STEPS>
+template <bool LDS_MIPS, typename IdxT, bool WIDE = false, int STEPS = VX_W_STEPS, bool TRAVEL = true>
 __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkParams PP)
 {
     const WalkHot& P = PP.hot;
@@ -969,7 +1026,7 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
             const int nb = __popcll(bm);
             if (nb <= kDonateBelow && VOXHIP_DONATE_ON) {
                 const bool pos = R.iw > 0.0f;
-                const int sh = R.lvl == 2 ? 6 : 3;
+                const int sh = R.lvl == 2 ? kBlkShift : 3;
                 int ip = pos ? (R.k << sh) : ((R.k + 1) << sh);
                 ip = ip > R.dimw ? R.dimw : ip;
                 const float t_cur = fmaxf(R.iw * (((R.orgw + (float)ip * g.vs) + (pos ? -R.tol : R.tol)) - R.ow), R.tn);  // the current slab's ta
@@ -1019,7 +1076,7 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
                         const float pw = s_ow + s_mid * (1.0f / s_iw);
                         int cw = (int)floorf((pw - s_orgw) * P.inv_vs) + (s_iw > 0.0f ? -1 : 1);
                         cw = cw < 0 ? 0 : (cw > s_dimw - 1 ? s_dimw - 1 : cw);
-                        R.k = cw >> 6;
+                        R.k = cw >> kBlkShift;
                         R.cw0 = cw;
                         r = s_r;
                         slot = s_slot;
@@ -1036,7 +1093,7 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
 #ifdef VX_W_DEBUG
             if (go) ++dbg_steps;
 #endif
-            if (go && !walk_step<LDS_MIPS>(R, P, mips_lds, xpend, &xslots[threadIdx.x], &xslots_hi[WIDE ? threadIdx.x : 0], fstate VX_W_SITE_ARGS)) finished = true;
+            if (go && !walk_step<LDS_MIPS, TRAVEL>(R, P, mips_lds, xpend, &xslots[threadIdx.x], &xslots_hi[WIDE ? threadIdx.x : 0], fstate VX_W_SITE_ARGS)) finished = true;
         }
         // ---- exact tests of the candidates the steps parked
         if (__ballot(xpend)) {
@@ -1061,7 +1118,7 @@ __global__ __launch_bounds__(VX_W_BLOCK, VX_W_MINWAVES) void k_walk(const WalkPa
         // ---- brick phase: the lanes whose step ended at a brick boundary fetch their next brick
         if (__ballot(fstate != 0u)) {
             if (fstate) {
-                if (!finished && !walk_bricks(R, P, (fstate & 2u) != 0u, (fstate & 4u) != 0u VX_W_SITE_ARGS)) finished = true;
+                if (!finished && !walk_bricks<TRAVEL>(R, P, (fstate & 2u) != 0u, (fstate & 4u) != 0u VX_W_SITE_ARGS)) finished = true;
                 fstate = 0u;
             }
         }
@@ -1251,7 +1308,10 @@ bool launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, 
     // VOXHIP_TRACE_LDS=0 forces the global-memory mips (the path every grid above ~550^3 takes) -- used by the parity tests
     const char* env_lds = getenv("VOXHIP_TRACE_LDS");
     const bool wide = g.dim[0] > 65535u || g.dim[1] > 65535u || g.dim[2] > 65535u;  // cell coordinates beyond 16 bits: the WIDE variants (global-memory mips only)
-    const bool lds = !wide && (size_t)(m1_words + m2_words) * 4 <= 32768 + 1024 && !(env_lds && atoi(env_lds) == 0);
+    // LDS mips only while four workgroups fit a CU: 160 KiB / 4 less k_walk's static LDS (don_key, don_cnt, xslots, one word of xslots_hi).
+    // A byte more and the kernel runs at three workgroups per CU, which costs more than the LDS look-ups save (512^3: 33 280 B of 33 788).
+    const size_t lds_room = 40960 - (size_t)VX_W_BLOCK * (sizeof(unsigned long long) + sizeof(unsigned) + sizeof(uint4)) - sizeof(uint32_t);
+    const bool lds = !wide && (size_t)(m1_words + m2_words) * 4 <= lds_room && !(env_lds && atoi(env_lds) == 0);
     WalkParams P;
     std::memset(&P, 0, sizeof(P));
     P.hot.g = g;
@@ -1303,15 +1363,17 @@ bool launch_walk(const GridParams& g, const TraceMips& mips, const TraceIO& io, 
             queue->counter = P.cold.next_item;
             queue->dry_at = sr >= n ? 0ull : n - sr;
         }
-#define VX_WALK_LAUNCH(STEPS)                                                                                                                                   \
+#define VX_WALK_LAUNCH(STEPS, TRAVEL)                                                                                                                           \
         if (lds) {                                                                                                                                                  \
-            if (idx32) VX_KL((k_walk<true, uint32_t, false, STEPS>), grid, block, shmem, s, P); else VX_KL((k_walk<true, unsigned long long, false, STEPS>), grid, block, shmem, s, P);   \
+            if (idx32) VX_KL((k_walk<true, uint32_t, false, STEPS, TRAVEL>), grid, block, shmem, s, P); else VX_KL((k_walk<true, unsigned long long, false, STEPS, TRAVEL>), grid, block, shmem, s, P);   \
         } else if (wide) {                                                                                                                                          \
-            if (idx32) VX_KL((k_walk<false, uint32_t, true, STEPS>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long, true, STEPS>), grid, block, shmem, s, P);   \
+            if (idx32) VX_KL((k_walk<false, uint32_t, true, STEPS, TRAVEL>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long, true, STEPS, TRAVEL>), grid, block, shmem, s, P);   \
         } else {                                                                                                                                                    \
-            if (idx32) VX_KL((k_walk<false, uint32_t, false, STEPS>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long, false, STEPS>), grid, block, shmem, s, P); \
+            if (idx32) VX_KL((k_walk<false, uint32_t, false, STEPS, TRAVEL>), grid, block, shmem, s, P); else VX_KL((k_walk<false, unsigned long long, false, STEPS, TRAVEL>), grid, block, shmem, s, P); \
         }
-        if (n < VX_W_FEW_BELOW) { VX_WALK_LAUNCH(VX_W_STEPS_FEW) } else { VX_WALK_LAUNCH(VX_W_STEPS) }
+        // by the size of the batch: steps per round, and whether the sibling bricks are visited in travel order and pruned (TRAVEL) -- work
+        // that an issue-bound launch no longer does (-11 % at 8M rays) and a drain-bound one pays for in every round (+6 % at 1M)
+        if (n < VX_W_FEW_BELOW) { VX_WALK_LAUNCH(VX_W_STEPS_FEW, false) } else { VX_WALK_LAUNCH(VX_W_STEPS, true) }
 #undef VX_WALK_LAUNCH
     }
     return ranked;
