@@ -163,12 +163,13 @@ void pool_free(int dev, void* p, hipStream_t stream, bool in_flight)
 
 // Where a buffer lives: the device of its blocks and the stream its owner queues their work on (the pool orders reuse by it).  Every handle
 // IS a Home (g->device, g->stream), a function's temporaries share a local one.  `drained`: the owner has synchronised the stream and queues
-// nothing more -- its blocks go back without an event each (the free functions).  Not copyable: buffers point at it.
+// nothing more -- its blocks go back without an event each (handle_free).  Not copyable: buffers point at it.
 struct Home {
     int device;
     hipStream_t stream;
     bool drained;
     explicit Home(int d = 0, hipStream_t s = nullptr, bool is_drained = false) : device(d), stream(s), drained(is_drained) {}
+    void before_free() {}  // handle_free's hook: what a handle type must settle before its stream is waited for (vx_grid)
     Home(const Home&) = delete;
     Home& operator=(const Home&) = delete;
 };
@@ -202,6 +203,17 @@ struct DevBuf {
         if (e == hipSuccess) { cap = round_size(bytes); fresh = true; }
         return e;
     }
+    // ensure() for an array that keeps its first `keep` bytes: a larger block (at least twice the old one) from the same Home, a copy on its
+    // stream, and the old block goes back in flight -- the pool hands it to nobody else before the copy has run.  No host wait.
+    hipError_t grow(size_t keep, size_t bytes)
+    {
+        if (bytes <= cap && p) return hipSuccess;
+        DevBuf larger{home};
+        hipError_t e = larger.ensure(std::max(bytes, 2 * cap));
+        if (e == hipSuccess && keep) e = hipMemcpyAsync(larger.p, p, keep, hipMemcpyDeviceToDevice, home->stream);
+        if (e == hipSuccess) *this = std::move(larger);
+        return e;
+    }
     // `in_flight`: see pool_free; a drained Home's blocks never are
     void release(bool in_flight = true)
     {
@@ -223,6 +235,29 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+// The one way a handle goes (every vx_*_free of a stream-owning Home): its device current, the type's hook, one wait for its stream -- an
+// asynchronous call may still be in flight -- and then its blocks go back without an event each.
+template <class H> void handle_free(H* h)
+{
+    if (!h) return;
+    DeviceGuard dg(h->device);
+    h->before_free();
+    (void)hipStreamSynchronize(h->stream);
+    h->drained = true;
+    delete h;
+}
+// The one way a create function holds a handle it has not handed out yet: a failure on the way frees it like any other handle, and the
+// failure's message stays the last error.
+template <class H> struct FreshFree {
+    void operator()(H* h) const
+    {
+        const std::string e = g_err;
+        handle_free(h);
+        g_err = e;
+    }
+};
+template <class H> using Fresh = std::unique_ptr<H, FreshFree<H>>;
 
 // The host variants' arrays, through device memory of `home` (the handle: its device and stream), one block each: a pooled one that goes
 // back when the call ends, or `kept`, a block the handle keeps so that a repeated call of the same size asks the pool for nothing.  in()
@@ -335,6 +370,57 @@ hipError_t mail_alloc(MailPtr& out)
     out.reset(reinterpret_cast<Mail*>(p));
     return hipSuccess;
 }
+
+// What a handle owns besides pool blocks and its mailbox, each destroyed by its destructor: an event (created on first use, with its flags),
+// a pinned host block, the grid's low-priority side stream.  Not copyable.
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
+    operator hipEvent_t() const { return ev; }
+};
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t ensure(size_t bytes)  // (contents are not kept)
+    {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+};
+struct SideStream {
+    hipStream_t s = nullptr;
+    SideStream() = default;
+    SideStream(const SideStream&) = delete;
+    SideStream& operator=(const SideStream&) = delete;
+    ~SideStream()  // (waits: what it still runs reads its owner's blocks)
+    {
+        if (!s) return;
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    hipError_t create()
+    {
+        if (s) return hipSuccess;
+        int lo = 0, hi = 0;
+        hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);  // (lo: numerically greatest = lowest priority)
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, lo);
+        return e;
+    }
+    operator hipStream_t() const { return s; }
+};
 
 // (re)allocated Small: the bbox reduction state needs its initial values once; everything else starts at zero
 hipError_t ensure_small(DevBuf& small)
@@ -675,8 +761,9 @@ struct vx_grid : Home {
     // into that: the next ray batch queues it on a low-priority SIDE stream of the handle, behind an event recorded on the main stream in front
     // of the ray kernel, so that its workgroups fill the slots the ray kernel's leave.  Whatever reads the list or overwrites what the emission
     // reads (host / device copies of the list, re-binding, setVoxel, the next build, free) goes through list_resolve() first.
-    hipStream_t side = nullptr;
-    hipEvent_t ev_ready = nullptr, ev_list = nullptr;
+    // (behind every DevBuf, the stream last: it is destroyed first, drained, before the events it waits on and the blocks its work touches)
+    Event ev_ready, ev_list;
+    SideStream side;
     bool list_deferred = false;  // the emission has not been queued yet (its arguments: ld)
     bool list_pending = false;   // it has been queued on `side`; the main stream has not waited for ev_list yet
     // from_mask: vx_grid_aabbs_device_async (K4).  scan_blocks: hbase has not been written by the build -- the host took the hit count from the
@@ -684,14 +771,11 @@ struct vx_grid : Home {
     struct { uint32_t ntri = 0; bool ext = false; vx_aabb* tgt = nullptr; uint64_t cap = 0; bool from_mask = false; uint64_t scan_blocks = 0; } ld;
     hipError_t side_init()
     {
-        if (side) return hipSuccess;
-        int lo = 0, hi = 0;
-        hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);  // (lo: numerically greatest = lowest priority)
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, lo);
         // (both events order streams of ONE device: no system-scope fence -- its cache write-back would stand in front of the ray kernel)
         const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_ready, evf);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_list, evf);
+        hipError_t e = side.create();
+        if (e == hipSuccess) e = ev_ready.create(evf);
+        if (e == hipSuccess) e = ev_list.create(evf);
         return e;
     }
     // the hit bases the emission reads, where the build left their scan to the list: queued once, on the stream the emission follows on
@@ -760,17 +844,7 @@ struct vx_grid : Home {
         }
         return hipSuccess;
     }
-    void side_release()
-    {
-        if (!side) return;
-        (void)hipStreamSynchronize(side);
-        (void)hipStreamDestroy(side);
-        if (ev_ready) (void)hipEventDestroy(ev_ready);
-        if (ev_list) (void)hipEventDestroy(ev_list);
-        side = nullptr;
-        ev_ready = ev_list = nullptr;
-        list_deferred = list_pending = false;
-    }
+    void before_free() { (void)list_resolve(/*drop_unqueued=*/true); }  // (the main stream then waits for the side stream's emission)
     // ---- what a build (or a failed one) resets, one place per kind of state
     void reset_materials()
     {
@@ -808,14 +882,9 @@ struct vx_octree : Home {
     uint64_t max_items = 16;
     uint64_t nitems = 0;
     DevBuf items{this};  // sorted Morton codes
-    vx_octree_node* dnodes = nullptr;  // pre-order node array (device): in `nodebuf` (pooled) or hipMalloc'ed (level-by-level build)
-    DevBuf nodebuf{this};
+    DevBuf nodebuf{this};  // pre-order node array, from either form of the node build
     uint64_t nnodes = 0;
     DevBuf camera{this};  // vx_octree_trace*: the camera block of primary-ray batches
-    ~vx_octree()  // (destroyed with its device current: vx_octree_build, vx_octree_free)
-    {
-        if (!nodebuf.p && dnodes) (void)hipFree(dnodes);
-    }
 };
 
 namespace {
@@ -1927,15 +1996,11 @@ vx_status vx_voxelize(const vx_mesh* mesh, float vs, vx_grid_kind kind, const vx
 {
     if (!mesh || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
     if (kind != VX_GRID_BOOL && kind != VX_GRID_AABBSTRUCT && kind != VX_GRID_VEC) return fail(VX_ERR_INVALID_ARG, "unknown grid kind");
-    vx_grid* g = new vx_grid();
+    Fresh<vx_grid> g(new vx_grid());
     g->kind = kind;
     g->device = mesh->device;
-    const vx_status s = vx_voxelize_into(mesh, vs, opts, g);
-    if (s != VX_OK) {
-        delete g;
-        return s;
-    }
-    *out = g;
+    VX_TRY(vx_voxelize_into(mesh, vs, opts, g.get()));
+    *out = g.release();
     return VX_OK;
 }
 
@@ -2191,7 +2256,7 @@ vx_status vx_grid_create(vx_grid_kind kind, uint64_t x, uint64_t y, uint64_t z, 
     if (kind != VX_GRID_BOOL && kind != VX_GRID_AABBSTRUCT && kind != VX_GRID_VEC) return fail(VX_ERR_INVALID_ARG, "unknown grid kind");
     if (x > vx::kMaxDim || y > vx::kMaxDim || z > vx::kMaxDim || x * y * z > kMaxVoxels) return fail(VX_ERR_CAPACITY, "grid too large");
     VX_TRY(need_device(g_device));
-    vx_grid* g = new vx_grid();
+    Fresh<vx_grid> g(new vx_grid());
     g->kind = kind;
     g->device = g_device;
     g->set_stream((hipStream_t)stream);
@@ -2199,9 +2264,8 @@ vx_status vx_grid_create(vx_grid_kind kind, uint64_t x, uint64_t y, uint64_t z, 
     const uint64_t dim[3] = {x, y, z};
     fill_params(g->g, origin ? origin : zero, vs, dim);
     DeviceGuard dg(g->device);
-    const vx_status s = init_grid_storage(g);
-    if (s != VX_OK) { delete g; return s; }
-    *out = g;
+    VX_TRY(init_grid_storage(g.get()));
+    *out = g.release();
     return VX_OK;
 }
 
@@ -2643,16 +2707,15 @@ static vx_status morph_run(vx_grid* sc, const uint32_t* src, const uint32_t dim[
 static vx_status morph_new_grid(const vx_grid* src, int kind, const uint32_t dim[3], vx_grid** out)
 {
     VX_TRY(need_device(src->device));
-    vx_grid* g = new vx_grid();
+    Fresh<vx_grid> g(new vx_grid());
     g->kind = kind;
     g->device = src->device;
     g->set_stream(src->stream);
     const uint64_t d[3] = {dim[0], dim[1], dim[2]};
     fill_params(g->g, src->g.org, src->g.vs, d);
     DeviceGuard dg(g->device);
-    const vx_status s = init_grid_storage(g);
-    if (s != VX_OK) { delete g; return s; }
-    *out = g;
+    VX_TRY(init_grid_storage(g.get()));
+    *out = g.release();
     return VX_OK;
 }
 
@@ -3220,12 +3283,7 @@ const int16_t* vx_grid_material_ids_device(const vx_grid* g)
     return g->mat_count ? g->matids.as<int16_t>() : nullptr;
 }
 
-void vx_grid_free(vx_grid* g)
-{
-    if (!g) return;
-    { DeviceGuard dg(g->device); (void)g->list_resolve(/*drop_unqueued=*/true); g->side_release(); (void)hipStreamSynchronize(g->stream); }
-    delete g;
-}
+void vx_grid_free(vx_grid* g) { handle_free(g); }
 
 // ---- distance-field queries (vx_field.hip) ----------------------------------------------------------------------
 // A snapshot of the signed field in a block of its own, and the blocks the host variants stage through: they stay on the handle, so a
@@ -3263,21 +3321,14 @@ vx_status vx_field_create(const vx_grid* gc, void* stream, vx_field** out)
     uint64_t n = 0;
     VX_TRY(distance_check(gc, ~0ull, &n));
     vx_grid* g = const_cast<vx_grid*>(gc);
-    std::unique_ptr<vx_field> f(new vx_field());
+    Fresh<vx_field> f(new vx_field());
     f->device = g->device;
     f->stream = (hipStream_t)stream;
     f->nvox = n;
-    vx_status st = VX_OK;
-    {
-        DeviceGuard dg(g->device);
-        const hipError_t e = f->values.ensure((size_t)n * 4);
-        st = e == hipSuccess ? field_snapshot(f.get(), g) : fail(VX_ERR_HIP, std::string("the field's block: ") + hipGetErrorString(e));
-    }
-    if (st != VX_OK) {
-        const std::string e = g_err;
-        vx_field_free(f.release());
-        return fail(st, e);
-    }
+    DeviceGuard dg(g->device);
+    const hipError_t e = f->values.ensure((size_t)n * 4);
+    if (e != hipSuccess) return fail(VX_ERR_HIP, std::string("the field's block: ") + hipGetErrorString(e));
+    VX_TRY(field_snapshot(f.get(), g));
     *out = f.release();
     return VX_OK;
 }
@@ -3304,13 +3355,7 @@ vx_status vx_field_describe(const vx_field* f, vx_field_desc* d)
 
 const float* vx_field_values_device(const vx_field* f) { return f ? f->values.as<float>() : nullptr; }
 
-void vx_field_free(vx_field* f)
-{
-    if (!f) return;
-    { DeviceGuard dg(f->device); (void)hipStreamSynchronize(f->stream); }
-    f->drained = true;
-    delete f;
-}
+void vx_field_free(vx_field* f) { handle_free(f); }
 
 // The three queries in trace_entry's order: the checks, the zero-count return, the guard, then one launch on the caller's device arrays or
 // (host) on a Staging over the handle's st_* blocks.
@@ -3735,6 +3780,64 @@ vx_status vx_trace(const vx_grid* gc, const float* host_rays, uint64_t nrays, fl
 }
 
 // ---- octree ---------------------------------------------------------------------------------------------------
+// The node array level by level (vx_octree.hip, LEVEL-BY-LEVEL FORM) from o's sorted items into o->nodebuf: breadth-first expansion with one
+// host wait per level (the size of the next one), then the pre-order renumbering.  Scratch on the build's Home; the four arrays indexed by
+// breadth-first id grow as the levels arrive and keep their contents.
+static vx_status octree_nodes_by_level(vx_octree* o, const Home& here, ScanScratch& scan, Mail* mail)
+{
+    hipStream_t s = here.stream;
+    const uint64_t* items = o->items.as<uint64_t>();
+    const uint32_t max_items = o->max_items > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o->max_items;
+    DevBuf start{&here}, count{&here}, children{&here}, depth_of{&here}, nchild{&here}, cbase{&here};
+    const size_t first = 1024;  // nodes of the first blocks
+    VX_HIP(start.ensure(first * 4));
+    VX_HIP(count.ensure(first * 4));
+    VX_HIP(children.ensure(first * 32));
+    VX_HIP(depth_of.ensure(first));
+    const uint32_t root[2] = {0u, (uint32_t)o->nitems};
+    VX_HIP(hipMemcpyAsync(start.p, &root[0], 4, hipMemcpyHostToDevice, s));
+    VX_HIP(hipMemcpyAsync(count.p, &root[1], 4, hipMemcpyHostToDevice, s));
+    uint32_t total = 1, level_off = 0, level_n = 1;
+    for (uint32_t depth = 0;; ++depth) {
+        VX_HIP(nchild.ensure(((size_t)level_n + 1) * 4));
+        VX_HIP(cbase.ensure(((size_t)level_n + 2) * 4));
+        vx::launch_oct_count(items, start.as<uint32_t>() + level_off, count.as<uint32_t>() + level_off, level_n, depth, o->bits, max_items, nchild.as<uint32_t>(), s);
+        VX_TRY(scan.u32(nchild, cbase, level_n, false, &mail->occupied, s));
+        uint64_t next_n = 0;
+        VX_TRY(mail_total(&mail->occupied, 0, s, "more than 2^32 octree nodes", &next_n));
+        const size_t need = (size_t)total + next_n;
+        if (need >= 0xFFFFFFFFull) return fail(VX_ERR_HIP, "2^32 - 1 octree nodes or more");
+        VX_HIP(start.grow((size_t)total * 4, need * 4));
+        VX_HIP(count.grow((size_t)total * 4, need * 4));
+        VX_HIP(children.grow((size_t)total * 32, need * 32));
+        VX_HIP(depth_of.grow(total, need));
+        vx::launch_oct_emit(items, start.as<uint32_t>(), count.as<uint32_t>(), children.as<uint32_t>(), depth_of.as<uint8_t>(), level_off, level_n, depth, o->bits,
+                            max_items, cbase.as<uint32_t>(), /*next_off=*/total, s);
+        if (next_n == 0) break;
+        level_off = total;
+        level_n = (uint32_t)next_n;
+        total += level_n;
+    }
+    // pre-order numbering: rank of (start << 8 | depth)
+    DevBuf keys{&here}, keys2{&here}, ids{&here}, order{&here}, newidx{&here}, sorttmp{&here};
+    const size_t tb = vx::oct_sort_tmp_bytes(total);
+    VX_HIP(keys.ensure((size_t)total * 8));
+    VX_HIP(keys2.ensure((size_t)total * 8));
+    VX_HIP(ids.ensure((size_t)total * 4));
+    VX_HIP(order.ensure((size_t)total * 4));
+    VX_HIP(newidx.ensure((size_t)total * 4));
+    VX_HIP(sorttmp.ensure(tb));
+    VX_HIP(o->nodebuf.ensure((size_t)total * sizeof(vx_octree_node)));
+    vx::launch_oct_keys(start.as<uint32_t>(), depth_of.as<uint8_t>(), total, keys.as<uint64_t>(), ids.as<uint32_t>(), s);
+    VX_HIP(vx::launch_oct_sort(keys.as<uint64_t>(), keys2.as<uint64_t>(), ids.as<uint32_t>(), order.as<uint32_t>(), total, sorttmp.p, tb, s));
+    vx::launch_oct_inverse(order.as<uint32_t>(), total, newidx.as<uint32_t>(), s);
+    vx::launch_oct_finalize(order.as<uint32_t>(), newidx.as<uint32_t>(), start.as<uint32_t>(), count.as<uint32_t>(), children.as<uint32_t>(), total,
+                            o->nodebuf.as<vx_octree_node>(), s);
+    VX_HIP(hipStreamSynchronize(s));
+    o->nnodes = total;
+    return VX_OK;
+}
+
 vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, void* stream, vx_octree** out)
 {
     if (!mesh_c || !out) return fail(VX_ERR_INVALID_ARG, "null argument");
@@ -3744,8 +3847,8 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
     DeviceGuard dg(mesh->device);
     VX_TRY(mesh_to_device(mesh));
     hipStream_t s = (hipStream_t)stream;
-    const Home here(mesh->device, s);  // of the build's scratch: it outlives the octree, which a failed build deletes on its way out
-    std::unique_ptr<vx_octree> o(new vx_octree());
+    const Home here(mesh->device, s);  // of the build's scratch: it outlives the octree, which a failed build frees on its way out
+    Fresh<vx_octree> o(new vx_octree());
     o->device = mesh->device;
     o->stream = s;
     o->vs = vs;
@@ -3811,14 +3914,12 @@ vx_status vx_octree_build(const vx_mesh* mesh_c, float vs, uint64_t max_items, v
         VX_TRY(mail_total(&mail->occupied, 0, s, "more than 2^32 octree nodes", &nn));
         if (nn == 0) return fail(VX_ERR_CAPACITY, "more than 2^32 octree nodes");
         VX_HIP(o->nodebuf.ensure((size_t)nn * sizeof(vx_octree_node)));
-        o->dnodes = o->nodebuf.as<vx_octree_node>();
-        VX_HIP(hipMemsetAsync(o->dnodes, 0xFF, (size_t)nn * sizeof(vx_octree_node), s));  // children = 0xFFFFFFFF (none)
-        vx::launch_oct_nodes(o->items.as<uint64_t>(), ni, o->bits, nbase.as<uint32_t>(), o->dnodes, s);
+        VX_HIP(hipMemsetAsync(o->nodebuf.p, 0xFF, (size_t)nn * sizeof(vx_octree_node), s));  // children = 0xFFFFFFFF (none)
+        vx::launch_oct_nodes(o->items.as<uint64_t>(), ni, o->bits, nbase.as<uint32_t>(), o->nodebuf.as<vx_octree_node>(), s);
         VX_HIP(hipStreamSynchronize(s));
         o->nnodes = nn;
     } else {
-        // level by level: breadth-first expansion + pre-order renumbering (any max_items; also the empty item list's lone root)
-        VX_HIP(vx::build_octree_nodes(o->items.as<uint64_t>(), (uint32_t)hits, o->bits, max_items, &o->dnodes, &o->nnodes, s));
+        VX_TRY(octree_nodes_by_level(o.get(), here, up.scantmp, mail.get()));  // (any max_items; also the empty item list's lone root)
     }
     *out = o.release();
     return VX_OK;
@@ -3845,7 +3946,7 @@ vx_status vx_octree_nodes(const vx_octree* o, vx_octree_node* host, uint64_t cap
     if (cap < o->nnodes) return fail(VX_ERR_CAPACITY, "node buffer too small");
     if (!o->nnodes) return VX_OK;
     DeviceGuard dg(o->device);
-    VX_HIP(hipMemcpyAsync(host, o->dnodes, (size_t)o->nnodes * sizeof(vx_octree_node), hipMemcpyDeviceToHost, o->stream));
+    VX_HIP(hipMemcpyAsync(host, o->nodebuf.as<vx_octree_node>(), (size_t)o->nnodes * sizeof(vx_octree_node), hipMemcpyDeviceToHost, o->stream));
     VX_HIP(hipStreamSynchronize(o->stream));
     return VX_OK;
 }
@@ -3892,7 +3993,7 @@ static vx_status octree_trace_common(vx_octree* o, vx::TraceIO io, float*, uint3
     if (!io.nrays) return VX_OK;
     VX_TRY(upload_camera(o->camera, o->stream, io));
     const uint64_t nitems = o->nnodes == 0 ? 0 : o->nitems;  // the list vx_octree_aabbs returns
-    vx::launch_octree_trace(o->dnodes, o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, o->stream);
+    vx::launch_octree_trace(o->nodebuf.as<vx_octree_node>(), o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, o->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
 }
@@ -3919,7 +4020,7 @@ static vx_status octree_multihit_common(vx_octree* o, vx::TraceIO io, const vx_t
 {
     VX_TRY(upload_camera(o->camera, o->stream, io));
     const uint64_t nitems = o->nnodes == 0 ? 0 : o->nitems;  // the list vx_octree_aabbs returns
-    vx::launch_octree_multihit(o->dnodes, o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, multi_io(a), o->stream);
+    vx::launch_octree_multihit(o->nodebuf.as<vx_octree_node>(), o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, multi_io(a), o->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
 }
@@ -3934,16 +4035,7 @@ vx_status vx_octree_trace_multi(const vx_octree* o, const vx_multihit_args* args
     return multihit_entry(o, args, from_grid_args(args), false, true, octree_multihit_common);
 }
 
-void vx_octree_free(vx_octree* o)
-{
-    if (!o) return;
-    {   // vx_octree_aabbs_device is asynchronous: nothing of this octree may still be in flight when its memory goes back
-        DeviceGuard dg(o->device);
-        (void)hipStreamSynchronize(o->stream);
-        o->drained = true;
-        delete o;
-    }
-}
+void vx_octree_free(vx_octree* o) { handle_free(o); }
 
 // ---- triangle BVH: the reference's triangle BLAS (hello_vulkan.cpp:596-635) under raytrace.rchit (vx_bvh.hip) -------------------------
 struct vx_bvh : Home {
@@ -4041,17 +4133,12 @@ vx_status vx_bvh_build(const vx_mesh* mesh_c, uint32_t max_leaf, void* stream, v
     if (max_leaf >= 0x80000000u) return fail(VX_ERR_INVALID_ARG, "max_leaf_triangles must be below 2^31");
     vx_mesh* mesh = const_cast<vx_mesh*>(mesh_c);
     VX_TRY(need_device(mesh->device));
-    vx_bvh* b = new vx_bvh();
+    Fresh<vx_bvh> b(new vx_bvh());
     b->device = mesh->device;
     b->stream = (hipStream_t)stream;
     b->max_leaf = max_leaf ? max_leaf : VX_BVH_DEFAULT_LEAF;
-    const vx_status st = bvh_build_impl(mesh, b);
-    if (st != VX_OK) {
-        const std::string e = g_err;
-        vx_bvh_free(b);
-        return fail(st, e);
-    }
-    *out = b;
+    VX_TRY(bvh_build_impl(mesh, b.get()));
+    *out = b.release();
     return VX_OK;
 }
 
@@ -4154,16 +4241,7 @@ vx_status vx_bvh_trace_multi(const vx_bvh* b, const vx_bvh_multihit_args* args)
     return multihit_entry(b, args, from_bvh_args(args), false, true, bvh_multihit_common);
 }
 
-void vx_bvh_free(vx_bvh* b)
-{
-    if (!b) return;
-    {
-        DeviceGuard dg(b->device);
-        (void)hipStreamSynchronize(b->stream);
-        b->drained = true;
-        delete b;
-    }
-}
+void vx_bvh_free(vx_bvh* b) { handle_free(b); }
 
 // ---- instanced scenes: the reference's TLAS (createTopLevelAS, hello_vulkan.cpp:760-790) over vx_bvh BLAS (vx_tlas.hip) --------------
 struct vx_tlas : Home {
@@ -4175,11 +4253,11 @@ struct vx_tlas : Home {
         nodes{this}, hgt{this}, small{this}, dtab{this}, camera{this};
     // host staging of vx_tlas_update: two pinned buffers used in turn, so that an update waits (on the host) only for the copy out of
     // the buffer it reuses, the one of the update before the previous one
-    vx_instance* pinned[2] = {nullptr, nullptr};
-    uint64_t pinned_cap[2] = {0, 0};
+    PinnedBuf pinned[2];
     bool staged[2] = {false, false};      // ev_staged[k] marks the end of the last copy out of pinned[k]
     int stage = 0;                        // the buffer the next host update fills
-    hipEvent_t ev_src = nullptr, ev_end = nullptr, ev_staged[2] = {nullptr, nullptr};
+    // (behind the DevBufs: the events and pinned blocks are destroyed ahead of the device blocks that the copies they order fill)
+    Event ev_src, ev_end, ev_staged[2];   // created by vx_tlas_build
 };
 
 namespace {
@@ -4298,16 +4376,10 @@ vx_status tlas_update_host(vx_tlas* t, const vx_instance* in, uint64_t n)
     if (n) {
         const int k = t->stage;
         if (t->staged[k]) { VX_HIP(hipEventSynchronize(t->ev_staged[k])); t->staged[k] = false; }  // the copy out of this buffer is done
-        if (n > t->pinned_cap[k]) {
-            if (t->pinned[k]) VX_HIP(hipHostFree(t->pinned[k]));
-            t->pinned[k] = nullptr;
-            t->pinned_cap[k] = 0;
-            VX_HIP(hipHostMalloc((void**)&t->pinned[k], (size_t)n * sizeof(vx_instance), hipHostMallocDefault));
-            t->pinned_cap[k] = n;
-        }
-        std::memcpy(t->pinned[k], in, (size_t)n * sizeof(vx_instance));
+        VX_HIP(t->pinned[k].ensure((size_t)n * sizeof(vx_instance)));
+        std::memcpy(t->pinned[k].p, in, (size_t)n * sizeof(vx_instance));
         VX_HIP(t->dinst.ensure((size_t)n * sizeof(vx_instance)));
-        VX_HIP(hipMemcpyAsync(t->dinst.p, t->pinned[k], (size_t)n * sizeof(vx_instance), hipMemcpyHostToDevice, t->stream));
+        VX_HIP(hipMemcpyAsync(t->dinst.p, t->pinned[k].p, (size_t)n * sizeof(vx_instance), hipMemcpyHostToDevice, t->stream));
         VX_HIP(hipEventRecord(t->ev_staged[k], t->stream));
         t->staged[k] = true;
         t->stage = 1 - k;
@@ -4340,22 +4412,19 @@ vx_status vx_tlas_build(const vx_bvh* const* blas, uint32_t num_blas, const vx_i
     VX_TRY(need_device(dev));
     for (uint32_t k = 0; k < num_blas; ++k)
         if (blas[k]->device != dev) return fail(VX_ERR_INVALID_ARG, "the BLAS handles live on different devices");
-    vx_tlas* t = new vx_tlas();
+    Fresh<vx_tlas> t(new vx_tlas());
     t->device = dev;
     t->stream = (hipStream_t)stream;
     for (uint32_t k = 0; k < num_blas; ++k) t->blas.push_back(const_cast<vx_bvh*>(blas[k]));
     DeviceGuard dg(t->device);
-    hipError_t e = hipEventCreateWithFlags(&t->ev_src, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ev_end, hipEventDisableTiming);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&t->ev_staged[k], hipEventDisableTiming);
-    vx_status st = e == hipSuccess ? tlas_update_host(t, host_instances, num_instances) : fail(VX_ERR_HIP, std::string("vx_tlas_build: ") + hipGetErrorString(e));
-    if (st == VX_OK) { const hipError_t se = hipStreamSynchronize(t->stream); if (se != hipSuccess) st = fail(VX_ERR_HIP, hipGetErrorString(se)); }
-    if (st != VX_OK) {
-        const std::string err = g_err;
-        vx_tlas_free(t);
-        return fail(st, err);
-    }
-    *out = t;
+    hipError_t e = hipSuccess;
+    for (Event* ev : {&t->ev_src, &t->ev_end, &t->ev_staged[0], &t->ev_staged[1]})
+        if (e == hipSuccess) e = ev->create();
+    if (e != hipSuccess) return fail(VX_ERR_HIP, std::string("vx_tlas_build: ") + hipGetErrorString(e));
+    VX_TRY(tlas_update_host(t.get(), host_instances, num_instances));
+    e = hipStreamSynchronize(t->stream);
+    if (e != hipSuccess) return fail(VX_ERR_HIP, hipGetErrorString(e));
+    *out = t.release();
     return VX_OK;
 }
 
@@ -4452,20 +4521,7 @@ vx_status vx_tlas_trace_multi(const vx_tlas* t, const vx_tlas_multihit_args* a)
     return multihit_entry(t, a, a ? *a : vx_tlas_multihit_args{}, true, true, tlas_multihit_common);
 }
 
-void vx_tlas_free(vx_tlas* t)
-{
-    if (!t) return;
-    {
-        DeviceGuard dg(t->device);
-        (void)hipStreamSynchronize(t->stream);
-        t->drained = true;
-        for (vx_instance* p : t->pinned)
-            if (p) (void)hipHostFree(p);
-        for (hipEvent_t ev : {t->ev_src, t->ev_end, t->ev_staged[0], t->ev_staged[1]})
-            if (ev) (void)hipEventDestroy(ev);
-        delete t;
-    }
-}
+void vx_tlas_free(vx_tlas* t) { handle_free(t); }
 
 // ---- frames: the reference's per-frame raytrace dispatch as one asynchronous sequence on the scene's stream (vx_render.hip) ------------
 // camera block -> primary traversals (voxels, mesh) -> k_render_shadow_rays -> shadow traversals (voxels, mesh) -> k_render_shade.  The
@@ -4487,8 +4543,9 @@ struct vx_render_scene : Home {
     int phase = 0;              // which of the two walk counters the next k_walk launch draws from (launch_trace)
     uint64_t nvmat = 0, nmmat = 0;
     bool has_mids = false;
-    hipEvent_t ev_src[2] = {nullptr, nullptr};  // recorded on the voxel source's and the BVH's stream at the start of a frame
-    hipEvent_t ev_end = nullptr;                          // recorded on the scene's stream at its end
+    // (behind the DevBufs: destroyed ahead of the blocks of the frames they order)
+    Event ev_src[2];  // recorded on the voxel source's and the BVH's stream at the start of a frame
+    Event ev_end;     // recorded on the scene's stream at its end
 };
 
 namespace {
@@ -4750,7 +4807,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     vx_octree* o = s->octree;
     auto voxels = [&](const vx::TraceIO& q) {
         if (g) vx::launch_trace(g->g, mips, g->wprefix.as<uint32_t>(), q, s->counters.as<unsigned long long>(), &s->phase, s->idxtmp.p, st, p16, nullptr);
-        else vx::launch_octree_trace(o->dnodes, o->items.as<uint64_t>(), o->nnodes == 0 ? 0 : o->nitems, o->bits, o->root_min, o->vs, q, st);
+        else vx::launch_octree_trace(o->nodebuf.as<vx_octree_node>(), o->items.as<uint64_t>(), o->nnodes == 0 ? 0 : o->nitems, o->bits, o->root_min, o->vs, q, st);
     };
     vx_bvh* b = s->bvh;
     vx_tlas* tl = s->tlas;
@@ -4861,7 +4918,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
 }  // namespace
 
 namespace {
-vx_status render_create_common(vx_render_scene* s, vx_render_scene** out);
+vx_status render_create_common(Fresh<vx_render_scene> s, vx_render_scene** out);
 }
 
 vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out)
@@ -4870,13 +4927,13 @@ vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out)
     *out = nullptr;
     VX_TRY(render_desc_check(desc));
     VX_TRY(need_device(g_device));
-    vx_render_scene* s = new vx_render_scene();
+    Fresh<vx_render_scene> s(new vx_render_scene());
     s->grid = const_cast<vx_grid*>(desc->grid);
     s->octree = const_cast<vx_octree*>(desc->octree);
     s->bvh = const_cast<vx_bvh*>(desc->bvh);
     s->mesh = const_cast<vx_mesh*>(desc->mesh);
     s->stream = (hipStream_t)desc->stream;
-    return render_create_common(s, out);
+    return render_create_common(std::move(s), out);
 }
 
 vx_status vx_render_create_tlas(const vx_render_tlas_desc* desc, vx_render_scene** out)
@@ -4886,34 +4943,27 @@ vx_status vx_render_create_tlas(const vx_render_tlas_desc* desc, vx_render_scene
     if (!desc || !desc->tlas || (!desc->meshes && desc->tlas->blas.size())) return fail(VX_ERR_INVALID_ARG, "null argument");
     if (desc->grid && desc->octree) return fail(VX_ERR_INVALID_ARG, "at most one voxel source: grid or octree");
     VX_TRY(need_device(desc->tlas->device));
-    vx_render_scene* s = new vx_render_scene();
+    Fresh<vx_render_scene> s(new vx_render_scene());
     s->grid = const_cast<vx_grid*>(desc->grid);
     s->octree = const_cast<vx_octree*>(desc->octree);
     s->tlas = const_cast<vx_tlas*>(desc->tlas);
     for (size_t k = 0; k < s->tlas->blas.size(); ++k) s->meshes.push_back(const_cast<vx_mesh*>(desc->meshes[k]));
     s->stream = (hipStream_t)desc->stream;
-    return render_create_common(s, out);
+    return render_create_common(std::move(s), out);
 }
 
 namespace {
-struct RenderFree {
-    void operator()(vx_render_scene* s) const { vx_render_free(s); }
-};
-
-vx_status render_create_common(vx_render_scene* fresh, vx_render_scene** out)
+vx_status render_create_common(Fresh<vx_render_scene> s, vx_render_scene** out)
 {
-    const vx_status cs = render_sources_check(fresh);
-    if (cs != VX_OK) { delete fresh; return cs; }
-    fresh->device = fresh->grid ? fresh->grid->device : (fresh->octree ? fresh->octree->device : fresh->tlas->device);
-    std::unique_ptr<vx_render_scene, RenderFree> s(fresh);  // a failure below frees what the scene holds by then
+    s->device = s->grid ? s->grid->device : (s->octree ? s->octree->device : s->tlas->device);
+    VX_TRY(render_sources_check(s.get()));
     DeviceGuard dg(s->device);
     if (s->mesh) VX_TRY(mesh_to_device(s->mesh));
     for (vx_mesh* m : s->meshes) VX_TRY(mesh_to_device(m));
     VX_HIP(s->camera.ensure(sizeof(vx::Camera)));
     VX_HIP(s->counters.ensure(4 * sizeof(unsigned long long)));
     VX_HIP(hipMemsetAsync(s->counters.p, 0, 4 * sizeof(unsigned long long), s->stream));  // the walk's counters start at zero
-    for (int k = 0; k < 2; ++k) VX_HIP(hipEventCreateWithFlags(&s->ev_src[k], hipEventDisableTiming));
-    VX_HIP(hipEventCreateWithFlags(&s->ev_end, hipEventDisableTiming));
+    for (Event* ev : {&s->ev_src[0], &s->ev_src[1], &s->ev_end}) VX_HIP(ev->create());
     VX_TRY(render_upload_materials(s.get()));
     VX_TRY(render_upload_attributes(s.get()));
     *out = s.release();
@@ -4972,19 +5022,7 @@ vx_status vx_render_frame(vx_render_scene* s, const vx_render_args* a)
     return VX_OK;
 }
 
-void vx_render_free(vx_render_scene* s)
-{
-    if (!s) return;
-    {
-        DeviceGuard dg(s->device);
-        (void)hipStreamSynchronize(s->stream);
-        s->drained = true;
-        for (hipEvent_t& ev : s->ev_src)
-            if (ev) (void)hipEventDestroy(ev);
-        if (s->ev_end) (void)hipEventDestroy(s->ev_end);
-        delete s;
-    }
-}
+void vx_render_free(vx_render_scene* s) { handle_free(s); }
 
 // ---- test aid: the octree's item sort on a host array ----------------------------------------------------------
 vx_status vx_sort_u64(uint64_t* host_keys, uint64_t n, int bits)

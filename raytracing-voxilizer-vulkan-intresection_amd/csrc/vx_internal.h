@@ -599,9 +599,19 @@ constexpr uint64_t kOctDirectMaxItems = 64;
 void launch_oct_depths(const uint64_t* items, uint32_t nitems, uint32_t bits, uint32_t max_items, uint8_t* ncount, hipStream_t s);
 void launch_oct_nodes(const uint64_t* items, uint32_t nitems, uint32_t bits, const uint32_t* base, vx_octree_node* nodes, hipStream_t s);
 
-// Octree node array (pre-order, octTree.hpp:319-358) built on the device from the sorted items, level by level (any max_items);
-// *nodes_out is hipMalloc'ed.
-hipError_t build_octree_nodes(const uint64_t* items, uint32_t nitems, uint32_t max_depth, uint64_t max_items, vx_octree_node** nodes_out,
-                              uint64_t* nnodes_out, hipStream_t s);
+// Octree node array (pre-order, octTree.hpp:319-358), level by level (any max_items): per level launch_oct_count (children per node), an
+// exclusive scan, launch_oct_emit (the next level's start / count, 8 child links per node in breadth-first ids, the depth); then
+// launch_oct_keys, the sort of (key, id) pairs on 40 key bits (tmp: oct_sort_tmp_bytes), launch_oct_inverse and launch_oct_finalize,
+// which writes the nodes in pre-order.  Sequenced by vx_api.cpp (octree_nodes_by_level).
+void launch_oct_count(const uint64_t* items, const uint32_t* start, const uint32_t* count, uint32_t nnodes, uint32_t depth, uint32_t max_depth, uint32_t max_items,
+                      uint32_t* nchild, hipStream_t s);
+void launch_oct_emit(const uint64_t* items, uint32_t* start, uint32_t* count, uint32_t* children, uint8_t* depth_of, uint32_t level_off, uint32_t nnodes,
+                     uint32_t depth, uint32_t max_depth, uint32_t max_items, const uint32_t* child_base, uint32_t next_off, hipStream_t s);
+void launch_oct_keys(const uint32_t* start, const uint8_t* depth_of, uint32_t n, uint64_t* keys, uint32_t* ids, hipStream_t s);
+size_t oct_sort_tmp_bytes(uint32_t n);
+hipError_t launch_oct_sort(const uint64_t* keys, uint64_t* keys_out, const uint32_t* ids, uint32_t* order, uint32_t n, void* tmp, size_t tmp_bytes, hipStream_t s);
+void launch_oct_inverse(const uint32_t* order, uint32_t n, uint32_t* newidx, hipStream_t s);
+void launch_oct_finalize(const uint32_t* order, const uint32_t* newidx, const uint32_t* start, const uint32_t* count, const uint32_t* children, uint32_t n,
+                         vx_octree_node* out, hipStream_t s);
 
 }  // namespace vx

@@ -11,7 +11,7 @@
 //
 // A run is never split by a leaf boundary.  A node's item range [start, start + count) is the set of ALL items that carry its Morton
 // prefix (vx_octree.hip: k_oct_depths / k_oct_nodes start a node at the first item of a prefix and end it where the next prefix starts;
-// build_octree_nodes' k_count_children / k_emit_children split a range by the next three bits of the code), equal codes share every prefix,
+// the level-by-level form's k_oct_count / k_oct_emit split a range by the next three bits of the code), equal codes share every prefix,
 // and a leaf at the full depth (depth == bits) holds exactly one code, of which only the first item is tested.  A cell belongs to one node
 // per level, so it is reached along one path only: counts need no de-duplication beyond the run rule.
 //

@@ -19,7 +19,8 @@
 // Traffic: items twice, one byte and one uint32 per item, 40 B per node -- against a sort of (start, depth) keys and two
 // passes of seven binary searches per node and level in the level-by-level form below (kept for maxItems > 64).
 //
-// LEVEL-BY-LEVEL FORM: the tree is expanded breadth-first,
+// LEVEL-BY-LEVEL FORM (this file holds its kernels and their launchers; the level loop, its pool blocks and its one host wait per
+// level are vx_api.cpp's octree_nodes_by_level, beside every other build): the tree is expanded breadth-first,
 // one level per pass (every node of a level splits its item range with seven binary searches), and the pre-order numbering
 // is recovered afterwards: in pre-order a node precedes exactly the nodes with a larger (start, depth) pair -- a node's
 // subtree is a contiguous item range, children are visited in ascending start, and nested nodes with equal start are
@@ -276,29 +277,6 @@ __global__ __launch_bounds__(256) void k_oct_finalize(const uint32_t* __restrict
     out[r] = nd;
 }
 
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-hipError_t grow(Buf& b, size_t keep_bytes, size_t need_bytes, hipStream_t s)
-{
-    if (need_bytes <= b.cap) return hipSuccess;
-    size_t ncap = b.cap ? b.cap : 4096;
-    while (ncap < need_bytes) ncap *= 2;
-    void* np = nullptr;
-    hipError_t e = hipMalloc(&np, ncap);
-    if (e != hipSuccess) return e;
-    if (b.p && keep_bytes) {
-        e = hipMemcpyAsync(np, b.p, keep_bytes, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    if (b.p) (void)hipFree(b.p);
-    b.p = np;
-    b.cap = ncap;
-    return e;
-}
-
 }  // namespace
 
 void launch_oct_depths(const uint64_t* items, uint32_t nitems, uint32_t bits, uint32_t max_items, uint8_t* ncount, hipStream_t s)
@@ -313,78 +291,47 @@ void launch_oct_nodes(const uint64_t* items, uint32_t nitems, uint32_t bits, con
     VX_KL(k_oct_nodes, dim3((nitems + 4u * kNodeStretch - 1u) / (4u * kNodeStretch)), dim3(256), 0, s, items, nitems, (int)bits, base, nodes);
 }
 
-// Builds the node array on the device.  items: sorted Morton codes (device).  On success *nodes_out is a hipMalloc'ed array
-// of *nnodes_out nodes (the caller frees it with hipFree).
-hipError_t build_octree_nodes(const uint64_t* items, uint32_t nitems, uint32_t max_depth, uint64_t max_items_, vx_octree_node** nodes_out,
-                              uint64_t* nnodes_out, hipStream_t s)
+// ---- level-by-level form: one plain launcher per kernel; the level loop, the buffers and the waits are vx_api.cpp's (octree_nodes_by_level)
+void launch_oct_count(const uint64_t* items, const uint32_t* start, const uint32_t* count, uint32_t nnodes, uint32_t depth, uint32_t max_depth, uint32_t max_items,
+                      uint32_t* nchild, hipStream_t s)
 {
-    const uint32_t max_items = max_items_ > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)max_items_;
-    Buf start, count, children, depth_of, nchild, cbase, tmp;
-    hipError_t e = hipSuccess;
-    auto cleanup = [&]() { for (Buf* b : {&start, &count, &children, &depth_of, &nchild, &cbase, &tmp}) if (b->p) (void)hipFree(b->p); };
-#define OC(expr) do { e = (expr); if (e != hipSuccess) { cleanup(); return e; } } while (0)
-    uint32_t total = 1, level_off = 0, level_n = 1;
-    OC(grow(start, 0, 4096, s));
-    OC(grow(count, 0, 4096, s));
-    OC(grow(children, 0, 4096 * 8, s));
-    OC(grow(depth_of, 0, 4096, s));
-    const uint32_t root[2] = {0u, nitems};
-    OC(hipMemcpyAsync(start.p, &root[0], 4, hipMemcpyHostToDevice, s));
-    OC(hipMemcpyAsync(count.p, &root[1], 4, hipMemcpyHostToDevice, s));
-    for (uint32_t depth = 0;; ++depth) {
-        // pass A + scan -> size of the next level
-        OC(grow(nchild, 0, ((size_t)level_n + 1) * 4, s));
-        OC(grow(cbase, 0, ((size_t)level_n + 2) * 4, s));
-        OC(grow(tmp, 0, scan_tmp_bytes(level_n) + 16, s));
-        VX_KL(k_oct_count, dim3((level_n + 255) / 256), dim3(256), 0, s, items, (const uint32_t*)start.p + level_off, (const uint32_t*)count.p + level_off, level_n,
-              depth, max_depth, max_items, (uint32_t*)nchild.p);
-        unsigned long long* tot_dev = (unsigned long long*)((char*)tmp.p + scan_tmp_bytes(level_n));
-        launch_scan_u32((const uint32_t*)nchild.p, (uint32_t*)cbase.p, level_n, false, tmp.p, tot_dev, s);
-        unsigned long long next_n = 0;
-        OC(hipMemcpyAsync(&next_n, tot_dev, 8, hipMemcpyDeviceToHost, s));
-        OC(hipStreamSynchronize(s));
-        if ((unsigned long long)total + next_n >= 0xFFFFFFFFull) { cleanup(); return hipErrorOutOfMemory; }
-        const uint32_t next_off = total;
-        const size_t need = (size_t)total + next_n;
-        OC(grow(start, (size_t)total * 4, need * 4, s));
-        OC(grow(count, (size_t)total * 4, need * 4, s));
-        OC(grow(children, (size_t)total * 32, need * 32, s));
-        OC(grow(depth_of, (size_t)total, need, s));
-        VX_KL(k_oct_emit, dim3((level_n + 255) / 256), dim3(256), 0, s, items, (uint32_t*)start.p, (uint32_t*)count.p, (uint32_t*)children.p, (uint8_t*)depth_of.p,
-              level_off, level_n, depth, max_depth, max_items, (const uint32_t*)cbase.p, next_off);
-        if (next_n == 0) break;
-        level_off = next_off;
-        level_n = (uint32_t)next_n;
-        total += level_n;
-    }
-    // pre-order numbering: rank of (start << 8 | depth)
-    Buf keys, keys2, ids, order, newidx, sorttmp;
-    auto cleanup2 = [&]() { for (Buf* b : {&keys, &keys2, &ids, &order, &newidx, &sorttmp}) if (b->p) (void)hipFree(b->p); };
-#define OC2(expr) do { e = (expr); if (e != hipSuccess) { cleanup2(); cleanup(); return e; } } while (0)
-    OC2(grow(keys, 0, (size_t)total * 8, s));
-    OC2(grow(keys2, 0, (size_t)total * 8, s));
-    OC2(grow(ids, 0, (size_t)total * 4, s));
-    OC2(grow(order, 0, (size_t)total * 4, s));
-    OC2(grow(newidx, 0, (size_t)total * 4, s));
-    VX_KL(k_oct_keys, dim3((total + 255) / 256), dim3(256), 0, s, (const uint32_t*)start.p, (const uint8_t*)depth_of.p, total, (uint64_t*)keys.p, (uint32_t*)ids.p);
+    VX_KL(k_oct_count, dim3((nnodes + 255) / 256), dim3(256), 0, s, items, start, count, nnodes, depth, max_depth, max_items, nchild);
+}
+
+void launch_oct_emit(const uint64_t* items, uint32_t* start, uint32_t* count, uint32_t* children, uint8_t* depth_of, uint32_t level_off, uint32_t nnodes,
+                     uint32_t depth, uint32_t max_depth, uint32_t max_items, const uint32_t* child_base, uint32_t next_off, hipStream_t s)
+{
+    VX_KL(k_oct_emit, dim3((nnodes + 255) / 256), dim3(256), 0, s, items, start, count, children, depth_of, level_off, nnodes, depth, max_depth, max_items,
+          child_base, next_off);
+}
+
+void launch_oct_keys(const uint32_t* start, const uint8_t* depth_of, uint32_t n, uint64_t* keys, uint32_t* ids, hipStream_t s)
+{
+    VX_KL(k_oct_keys, dim3((n + 255) / 256), dim3(256), 0, s, start, depth_of, n, keys, ids);
+}
+
+// the pre-order numbering: (start << 8 | depth, breadth-first id) pairs sorted by their 40 key bits; tmp: oct_sort_tmp_bytes(n) bytes
+size_t oct_sort_tmp_bytes(uint32_t n)
+{
     size_t tb = 0;
-    OC2(rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)ids.p, (uint32_t*)order.p, (size_t)total, 0u, 40u, s));
-    OC2(grow(sorttmp, 0, tb ? tb : 16, s));
-    OC2(rocprim::radix_sort_pairs(sorttmp.p, tb, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint32_t*)ids.p, (uint32_t*)order.p, (size_t)total, 0u, 40u, s));
-    VX_KL(k_oct_inverse, dim3((total + 255) / 256), dim3(256), 0, s, (const uint32_t*)order.p, total, (uint32_t*)newidx.p);
-    vx_octree_node* out = nullptr;
-    OC2(hipMalloc((void**)&out, (size_t)total * sizeof(vx_octree_node)));
-    VX_KL(k_oct_finalize, dim3((total + 255) / 256), dim3(256), 0, s, (const uint32_t*)order.p, (const uint32_t*)newidx.p, (const uint32_t*)start.p,
-          (const uint32_t*)count.p, (const uint32_t*)children.p, total, out);
-    e = hipStreamSynchronize(s);
-    cleanup2();
-    cleanup();
-    if (e != hipSuccess) { (void)hipFree(out); return e; }
-    *nodes_out = out;
-    *nnodes_out = total;
-    return hipSuccess;
-#undef OC
-#undef OC2
+    (void)rocprim::radix_sort_pairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, 40u);
+    return tb ? tb : 16;
+}
+
+hipError_t launch_oct_sort(const uint64_t* keys, uint64_t* keys_out, const uint32_t* ids, uint32_t* order, uint32_t n, void* tmp, size_t tmp_bytes, hipStream_t s)
+{
+    return rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, ids, order, (size_t)n, 0u, 40u, s);
+}
+
+void launch_oct_inverse(const uint32_t* order, uint32_t n, uint32_t* newidx, hipStream_t s)
+{
+    VX_KL(k_oct_inverse, dim3((n + 255) / 256), dim3(256), 0, s, order, n, newidx);
+}
+
+void launch_oct_finalize(const uint32_t* order, const uint32_t* newidx, const uint32_t* start, const uint32_t* count, const uint32_t* children, uint32_t n,
+                         vx_octree_node* out, hipStream_t s)
+{
+    VX_KL(k_oct_finalize, dim3((n + 255) / 256), dim3(256), 0, s, order, newidx, start, count, children, n, out);
 }
 
 }  // namespace vx

@@ -638,8 +638,28 @@ def shard_range(count, rank, world):
     return b.value, e.value
 
 
-class Mesh:
+class _Handle:
+    """What the handle classes share: `h`, the name of the C free function, an idempotent free() and a __del__ that swallows exceptions.
+    owned = False (BorrowedGrid): free() only forgets the handle."""
+    h = None
+    owned = True
+    _free = None
+
+    def free(self):
+        if self.h and self.owned:
+            getattr(lib(), self._free)(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Mesh(_Handle):
     """vx_mesh handle (what VoxelBuilder keeps after readObjFile)."""
+    _free = "vx_mesh_free"
 
     def __init__(self, handle, keep=None):
         self.h = handle
@@ -757,22 +777,10 @@ class Mesh:
         """vx_mesh_load_textures: decode every slot's file (PPM P6 / TGA; 1x1 magenta where that fails)"""
         _check(lib().vx_mesh_load_textures(self.h))
 
-    def free(self):
-        if self.h:
-            lib().vx_mesh_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Grid:
+class Grid(_Handle):
     """vx_grid handle (a VoxelGridBool / VoxelGridAABBstruct / VoxelGridVec)."""
-    owned = True
-
+    _free = "vx_grid_free"
 
     def __init__(self, handle):
         self.h = handle
@@ -1246,17 +1254,6 @@ class Grid:
         _ray_batch(a, None, (view_inv, proj_inv, width, height), tmin, tmax, None, [])
         _check(lib().vx_trace_primary_device(self.h, a.view_inverse, a.proj_inverse, a.width, a.height, a.tmin, a.tmax, t_ptr, prim_ptr))
 
-    def free(self):
-        if self.h and self.owned:
-            lib().vx_grid_free(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 FIELD_FINITE, FIELD_EMPTY, FIELD_FULL = 0, 1, 2
 FIELD_MISS, FIELD_HIT, FIELD_STEP_LIMIT = 0, 1, 2
@@ -1269,9 +1266,10 @@ POSE_CHUNK, POSE_TILE = 256, 32   # VX_FIELD_POSE_CHUNK / _TILE: how the pose ke
 POSE_NO_POINT = 0xFFFFFFFF
 
 
-class Field:
+class Field(_Handle):
     """vx_field handle: a device-resident snapshot of a grid's signed distance field, sampled trilinearly at arbitrary points and sphere
     traced along rays (include/voxhip.h, "distance-field queries")."""
+    _free = "vx_field_free"
 
     def __init__(self, handle):
         self.h = handle
@@ -1373,17 +1371,6 @@ class Field:
         _set_pointers(a, dict(radii=radii_ptr, **output_ptrs))
         _check(lib().vx_field_poses_device(self.h, C.byref(a)))
 
-    def free(self):
-        if self.h:
-            lib().vx_field_free(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 def sort_u64(keys, bits):
     """vx_sort_u64: the octree's device radix sort on a host array (returns a sorted copy)."""
@@ -1442,9 +1429,10 @@ class BorrowedGrid(Grid):
     owned = False
 
 
-class Multi:
+class Multi(_Handle):
     """vx_multi handle: a mesh resident on several devices (logical ranks allowed), one grid and one worker thread per rank;
     voxelize() rebuilds the grid in steady state (word shards by rank + peer copies)."""
+    _free = "vx_multi_free"
 
     def __init__(self, mesh, devices, kind=GRID_BOOL):
         dv = (C.c_int * len(devices))(*devices)
@@ -1460,20 +1448,10 @@ class Multi:
         _check(lib().vx_multi_voxelize(self.h, np.float32(voxel_size), C.byref(o), 1 if all_gather else 0))
         return [BorrowedGrid(C.c_void_p(lib().vx_multi_grid(self.h, k))) for k in range(self.n if all_gather else 1)]
 
-    def free(self):
-        if self.h:
-            lib().vx_multi_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Octree:
+class Octree(_Handle):
     """vx_octree handle (the reference's Octree)."""
+    _free = "vx_octree_free"
 
     def __init__(self, mesh, voxel_size, max_items=16, stream=None):
         h = C.c_void_p()
@@ -1548,20 +1526,10 @@ class Octree:
         _trace_multi_device(lib().vx_octree_trace_multi_device, self.h, MultiHitArgs(), rays_ptr, nrays, camera, max_hits, tmin, tmax, t=t_ptr,
                             prim=prim_ptr, count=count_ptr, tmax_per_ray=tmax_per_ray_ptr, after_t=after_t_ptr, after_prim=after_prim_ptr)
 
-    def free(self):
-        if self.h:
-            lib().vx_octree_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Bvh:
+class Bvh(_Handle):
     """vx_bvh handle: the mesh's triangle BVH (the reference's triangle BLAS)."""
+    _free = "vx_bvh_free"
 
     def __init__(self, mesh, max_leaf=0, stream=None):
         h = C.c_void_p()
@@ -1649,17 +1617,6 @@ class Bvh:
         _trace_multi_device(lib().vx_bvh_trace_multi_device, self.h, BvhMultiHitArgs(), rays_ptr, nrays, camera, max_hits, tmin, tmax, t=t_ptr,
                             prim=prim_ptr, count=count_ptr, tmax_per_ray=tmax_per_ray_ptr, after_t=after_t_ptr, after_prim=after_prim_ptr, bary=bary_ptr)
 
-    def free(self):
-        if self.h:
-            lib().vx_bvh_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 def instances(transforms, blas=None, mask=None):
     """(transforms[n, 12], blas[n], mask[n]) -> an INSTANCE array (blas defaults to 0, mask to 0xFF)."""
@@ -1679,8 +1636,9 @@ def _as_instances(inst):
     return np.ascontiguousarray(np.asarray(inst), dtype=INSTANCE)
 
 
-class Tlas:
+class Tlas(_Handle):
     """vx_tlas handle: a top-level structure over transformed instances of Bvh handles (borrowed: keep them alive)."""
+    _free = "vx_tlas_free"
 
     def __init__(self, blas_list, instances, stream=None):
         self.blas = list(blas_list)
@@ -1767,17 +1725,6 @@ class Tlas:
                             prim=prim_ptr, count=count_ptr, tmax_per_ray=tmax_per_ray_ptr, after_t=after_t_ptr, after_prim=after_prim_ptr, bary=bary_ptr,
                             instance=instance_ptr, after_instance=after_instance_ptr)
 
-    def free(self):
-        if self.h:
-            lib().vx_tlas_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 def _stream_handle(stream):
     """a torch.cuda.Stream, a raw hipStream_t (int) or None (the default stream) -> the pointer the C ABI takes"""
@@ -1786,10 +1733,11 @@ def _stream_handle(stream):
     return getattr(stream, "cuda_stream", stream)
 
 
-class Renderer:
+class Renderer(_Handle):
     """vx_render_scene: whole frames on the device -- primary rays on the voxels (a Grid of kind GRID_BOOL, or an Octree) and the optional
     triangle model (bvh + the mesh it was built from), shadow rays, shading, gamma.  The scene borrows voxels, bvh and mesh: keep them
     alive while it is in use (this object holds references to them)."""
+    _free = "vx_render_free"
 
     def __init__(self, voxels, bvh=None, mesh=None, stream=None, attributes=False):
         d = RenderDesc()
@@ -1896,13 +1844,5 @@ class Renderer:
         _check(lib().vx_render_refresh(self.h))
 
     def free(self):
-        if self.h:
-            lib().vx_render_free(self.h)
-            self.h = None
+        super().free()
         self._keep = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass

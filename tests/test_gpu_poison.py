@@ -193,6 +193,23 @@ def check_octree(o, ref, what=""):
     assert np.array_equal(mn, ref["root_min"]) and np.array_equal(mx, ref["root_max"]), what + ": root bounds"
 
 
+GROWN_VS, GROWN_ITEMS = F(1.0 / 64), 65   # 37 037 items, 2 970 nodes (846 at the next smaller candidate, soup(4000))
+
+
+def grown_soup():
+    return vx_scenes.soup(5000, seed=4, edge=1.5 / 64)
+
+
+@functools.lru_cache(maxsize=None)
+def grown_ref():
+    """the oracle's sorted items of grown_soup() and Octree::buildTree on them (test_gpu_parity.test_octree_node_array_large's reference)"""
+    v, t = grown_soup()
+    h = oracle.hits(v, t, GROWN_VS, threads=2, sat=0)
+    items = np.sort(oracle.morton3d_np(h[:, 0], h[:, 1], h[:, 2]))
+    bits = int(np.ceil(np.log2(max(oracle.grid_info(v, GROWN_VS)["dim"]))))
+    return items, oracle.octree_nodes_from_sorted_items(items, bits, GROWN_ITEMS)
+
+
 @patterns
 def test_octree_build(gpu, pattern):
     with poisoned(gpu, pattern):
@@ -201,6 +218,12 @@ def test_octree_build(gpu, pattern):
             mesh = gpu.Mesh.from_arrays(r.v, r.t)
             for max_items in (16, 1, 100):   # the direct node-array form (<= 64) and the level-by-level form
                 check_octree(gpu.Octree(mesh, sc.SOUP_VS, max_items), octree_ref(dims, max_items), "%s max_items %d" % (dims, max_items))
+        # the level-by-level form past its first blocks of 1024 nodes: the arrays indexed by breadth-first id grow and keep their contents
+        o = gpu.Octree(gpu.Mesh.from_arrays(*grown_soup()), GROWN_VS, GROWN_ITEMS)
+        items, nodes = grown_ref()
+        assert len(nodes) > 2048
+        assert np.array_equal(o.items(), items)
+        assert o.num_nodes == len(nodes) and o.nodes().tobytes() == nodes.tobytes()
 
 
 # ---- 4. first hits on the grid -------------------------------------------------------------------------------------------------------------

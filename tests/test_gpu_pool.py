@@ -125,6 +125,24 @@ def test_octree_balanced(gpu):
     balanced(gpu, cycle)
 
 
+def test_octree_node_array_is_a_pool_block(gpu):
+    """the node array is one more live block whichever form builds it -- the direct one (16), the level-by-level one (65, and 1 << 20: the
+    lone root) -- and free() returns every block"""
+    v, t = vx_scenes.rotated_cube()
+    m = gpu.Mesh.from_arrays(v, t)
+    gpu.Octree(m, VS).free()                          # (uploads the mesh)
+    rises = []
+    for max_items in (16, 65, 1 << 20):
+        before = settled(gpu)
+        o = gpu.Octree(m, VS, max_items=max_items)
+        assert o.num_nodes > 0
+        rises.append(live(gpu) - before)
+        o.free()
+        assert live(gpu) == before
+    assert rises[0] == rises[1] == rises[2] and rises[0] > 0, rises
+    m.free()
+
+
 def test_bvh_tlas_renderer_balanced(gpu):
     v, t = vx_scenes.rotated_cube()
     rays = cube_rays()
