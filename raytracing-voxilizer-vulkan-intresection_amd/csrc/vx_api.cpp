@@ -3988,12 +3988,18 @@ vx_status vx_octree_aabbs(const vx_octree* o, vx_aabb* host_out, uint64_t cap, u
 }
 
 // ---- rays on the octree: the grid trace's contract over the vx_octree_aabbs list (vx_octrace.hip) ----------------------------------
+// the traversal of the octree's current build, queued on st: the octree's own stream, or a frame's (render_enqueue)
+static void octree_launch(const vx_octree* o, const vx::TraceIO& io, hipStream_t st)
+{
+    const uint64_t nitems = o->nnodes == 0 ? 0 : o->nitems;  // the list vx_octree_aabbs returns
+    vx::launch_octree_trace(o->nodebuf.as<vx_octree_node>(), o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, st);
+}
+
 static vx_status octree_trace_common(vx_octree* o, vx::TraceIO io, float*, uint32_t*)
 {
     if (!io.nrays) return VX_OK;
     VX_TRY(upload_camera(o->camera, o->stream, io));
-    const uint64_t nitems = o->nnodes == 0 ? 0 : o->nitems;  // the list vx_octree_aabbs returns
-    vx::launch_octree_trace(o->nodebuf.as<vx_octree_node>(), o->items.as<uint64_t>(), nitems, o->bits, o->root_min, o->vs, io, o->stream);
+    octree_launch(o, io, o->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
 }
@@ -4189,12 +4195,18 @@ vx_status vx_bvh_leaf_triangles(const vx_bvh* b, uint32_t* host, uint64_t cap)
     return VX_OK;
 }
 
+// the traversal of the BVH's current build, queued on st: the BVH's own stream, or a frame's (render_enqueue)
+static void bvh_launch(const vx_bvh* b, const vx::TraceIO& io, float* bary, hipStream_t st)
+{
+    vx::launch_bvh_trace(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height, b->extent, b->coord_max, io, bary,
+                         st);
+}
+
 static vx_status bvh_trace_common(vx_bvh* b, vx::TraceIO io, float* bary, uint32_t*)
 {
     if (!io.nrays) return VX_OK;
     VX_TRY(upload_camera(b->camera, b->stream, io));
-    vx::launch_bvh_trace(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height, b->extent, b->coord_max, io, bary,
-                         b->stream);
+    bvh_launch(b, io, bary, b->stream);
     VX_HIP(hipGetLastError());
     return VX_OK;
 }
@@ -4524,16 +4536,16 @@ vx_status vx_tlas_trace_multi(const vx_tlas* t, const vx_tlas_multihit_args* a)
 void vx_tlas_free(vx_tlas* t) { handle_free(t); }
 
 // ---- frames: the reference's per-frame raytrace dispatch as one asynchronous sequence on the scene's stream (vx_render.hip) ------------
-// camera block -> primary traversals (voxels, mesh) -> k_render_shadow_rays -> shadow traversals (voxels, mesh) -> k_render_shade.  The
-// scene owns every buffer the sequence touches, the walk's work counters included, so a frame never shares scratch with a trace the user
-// runs on a source's own stream.
+// camera block -> primary traversals (voxels, mesh) -> launch_render_shadow_rays -> shadow traversals (voxels, mesh) -> launch_render_shade,
+// each of the two one of four kernels (k_render_shadow_rays / k_render_shade, _tlas, _attr, _attr_tlas).  The scene owns every buffer the
+// sequence touches, the walk's work counters included, so a frame never shares scratch with a trace the user runs on a source's own stream.
 struct vx_render_scene : Home {
     vx_grid* grid = nullptr;
     vx_octree* octree = nullptr;
     vx_bvh* bvh = nullptr;
-    vx_mesh* mesh = nullptr;
-    vx_tlas* tlas = nullptr;              // instanced scenes (vx_render_create_tlas): the TLAS and one mesh per BLAS
-    std::vector<vx_mesh*> meshes;
+    vx_tlas* tlas = nullptr;              // instanced scenes (vx_render_create_tlas)
+    std::vector<vx_mesh*> meshes;         // the BVH's mesh, or one per BLAS of the TLAS; none without triangles
+    std::vector<vx::InstMesh> imeshes;    // a record per mesh (render_upload_materials); instanced scenes read the table from `imesh`
     DevBuf camera{this}, counters{this}, idxtmp{this}, vt{this}, vprim{this}, vnrm{this}, mt{this}, mprim{this}, mnrm{this}, mbary{this}, srays{this}, sdist{this},
         stmax{this}, sv{this}, sm{this}, vmat{this}, mmat{this}, mids{this}, rgba{this}, kind{this}, shad{this}, minst{this}, imesh{this};
     // attribute shading: per-mesh records, corner normals / uvs, material slots, texture records and texels of every mesh (concatenated), the
@@ -4541,8 +4553,7 @@ struct vx_render_scene : Home {
     DevBuf amesh{this}, anrm{this}, auv{this}, aslot{this}, atex{this}, texels{this}, srgb{this}, nbuf{this};
     uint32_t shading = 0;       // vx_render_set_shading flags
     int phase = 0;              // which of the two walk counters the next k_walk launch draws from (launch_trace)
-    uint64_t nvmat = 0, nmmat = 0;
-    bool has_mids = false;
+    uint64_t nvmat = 0;
     // (behind the DevBufs: destroyed ahead of the blocks of the frames they order)
     Event ev_src[2];  // recorded on the voxel source's and the BVH's stream at the start of a frame
     Event ev_end;     // recorded on the scene's stream at its end
@@ -4582,17 +4593,21 @@ vx_status render_args_check(const vx_render_args* a, vx_render_light* light)
 vx_status render_sources_check(const vx_render_scene* s)
 {
     if (s->grid && s->grid->kind != VX_GRID_BOOL) return fail(VX_ERR_INVALID_ARG, "the grid must be a VX_GRID_BOOL grid");
-    if (s->bvh && s->bvh->ntri != s->mesh->nt) return fail(VX_ERR_INVALID_ARG, "the mesh's triangle count differs from the BVH's");
     const int dev = s->grid ? s->grid->device : (s->octree ? s->octree->device : s->tlas->device);
-    if ((s->bvh && s->bvh->device != dev) || (s->mesh && s->mesh->device != dev)) return fail(VX_ERR_INVALID_ARG, "the scene's handles live on different devices");
+    const char* const devices = "the scene's handles live on different devices";
+    if (s->bvh) {  // (its one mesh: render_desc_check)
+        if (s->bvh->ntri != s->meshes[0]->nt) return fail(VX_ERR_INVALID_ARG, "the mesh's triangle count differs from the BVH's");
+        if (s->bvh->device != dev) return fail(VX_ERR_INVALID_ARG, devices);
+    }
     if (s->tlas) {
-        if (s->tlas->device != dev) return fail(VX_ERR_INVALID_ARG, "the scene's handles live on different devices");
+        if (s->tlas->device != dev) return fail(VX_ERR_INVALID_ARG, devices);
         if (s->meshes.size() != s->tlas->blas.size()) return fail(VX_ERR_INVALID_ARG, "one mesh per BLAS of the TLAS");
-        for (size_t k = 0; k < s->meshes.size(); ++k) {
-            if (!s->meshes[k]) return fail(VX_ERR_INVALID_ARG, "null mesh");
-            if (s->meshes[k]->nt != s->tlas->blas[k]->ntri) return fail(VX_ERR_INVALID_ARG, "mesh " + std::to_string(k) + ": its triangle count differs from its BLAS's");
-            if (s->meshes[k]->device != dev) return fail(VX_ERR_INVALID_ARG, "the scene's handles live on different devices");
-        }
+    }
+    for (size_t k = 0; k < s->meshes.size(); ++k) {
+        const vx_mesh* m = s->meshes[k];
+        if (!m) return fail(VX_ERR_INVALID_ARG, "null mesh");
+        if (s->tlas && m->nt != s->tlas->blas[k]->ntri) return fail(VX_ERR_INVALID_ARG, "mesh " + std::to_string(k) + ": its triangle count differs from its BLAS's");
+        if (m->device != dev) return fail(VX_ERR_INVALID_ARG, devices);
     }
     return VX_OK;
 }
@@ -4605,30 +4620,27 @@ hipStream_t source_stream(const vx_render_scene* s, int k)
     return s->bvh ? s->bvh->stream : s->tlas->stream;
 }
 
+// one table of a scene: `bytes` from host memory into b, on st; nothing to upload leaves b alone
+hipError_t render_upload(DevBuf& b, const void* src, size_t bytes, hipStream_t st)
+{
+    if (!bytes) return hipSuccess;
+    hipError_t e = b.ensure(bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
+    return e;
+}
+
+// the grid's material table (getMatrials), and every mesh's OBJ records and per-triangle ids, concatenated, with a record per mesh (ids
+// only where there is one per triangle: a hit of a mesh without them shades with MaterialObj{}); staged once, not per frame
 vx_status render_upload_materials(vx_render_scene* s)
 {
-    // the grid's material table (getMatrials) and the mesh's OBJ records with its per-triangle ids; staged once, not per frame
-    s->nvmat = s->nmmat = 0;
-    s->has_mids = false;
-    std::vector<vx_material> vm = (s->grid && s->grid->has_materials) ? s->grid->materials : std::vector<vx_material>();
-    if (!vm.empty()) {
-        VX_HIP(s->vmat.ensure(vm.size() * sizeof(vx_material)));
-        VX_HIP(hipMemcpyAsync(s->vmat.p, vm.data(), vm.size() * sizeof(vx_material), hipMemcpyHostToDevice, s->stream));
+    s->nvmat = 0;
+    if (s->grid && s->grid->has_materials) {
+        const std::vector<vx_material>& vm = s->grid->materials;
+        VX_HIP(render_upload(s->vmat, vm.data(), vm.size() * sizeof(vx_material), s->stream));
         s->nvmat = vm.size();
     }
-    if (s->mesh && !s->mesh->materials.empty()) {
-        VX_HIP(s->mmat.ensure(s->mesh->materials.size() * sizeof(vx_material)));
-        VX_HIP(hipMemcpyAsync(s->mmat.p, s->mesh->materials.data(), s->mesh->materials.size() * sizeof(vx_material), hipMemcpyHostToDevice, s->stream));
-        s->nmmat = s->mesh->materials.size();
-    }
-    if (s->mesh && !s->mesh->tri_mat.empty() && s->mesh->tri_mat.size() == s->mesh->nt) {
-        VX_HIP(s->mids.ensure(s->mesh->nt * 4));
-        VX_HIP(hipMemcpyAsync(s->mids.p, s->mesh->tri_mat.data(), s->mesh->nt * 4, hipMemcpyHostToDevice, s->stream));
-        s->has_mids = true;
-    }
-    std::vector<vx_material> tm;  // instanced scenes: every mesh's materials and material ids, concatenated, and a table of the meshes
+    std::vector<vx_material> tm;
     std::vector<int32_t> ti;
-    std::vector<vx::InstMesh> im(s->meshes.size());
     std::vector<std::pair<int64_t, int64_t>> off(s->meshes.size(), {-1, 0});
     for (size_t k = 0; k < s->meshes.size(); ++k) {
         const vx_mesh* m = s->meshes[k];
@@ -4639,26 +4651,20 @@ vx_status render_upload_materials(vx_render_scene* s)
             ti.insert(ti.end(), m->tri_mat.begin(), m->tri_mat.end());
         }
     }
-    if (!tm.empty()) {
-        VX_HIP(s->mmat.ensure(tm.size() * sizeof(vx_material)));
-        VX_HIP(hipMemcpyAsync(s->mmat.p, tm.data(), tm.size() * sizeof(vx_material), hipMemcpyHostToDevice, s->stream));
-    }
-    if (!ti.empty()) {
-        VX_HIP(s->mids.ensure(ti.size() * 4));
-        VX_HIP(hipMemcpyAsync(s->mids.p, ti.data(), ti.size() * 4, hipMemcpyHostToDevice, s->stream));
-    }
+    VX_HIP(render_upload(s->mmat, tm.data(), tm.size() * sizeof(vx_material), s->stream));
+    VX_HIP(render_upload(s->mids, ti.data(), ti.size() * 4, s->stream));
+    s->imeshes.resize(s->meshes.size());
     for (size_t k = 0; k < s->meshes.size(); ++k) {
         const vx_mesh* m = s->meshes[k];
-        im[k].verts = m->dv;
-        im[k].idx = m->di;
-        im[k].mids = off[k].first >= 0 ? s->mids.as<int32_t>() + off[k].first : nullptr;
-        im[k].mat = m->materials.empty() ? nullptr : s->mmat.as<vx_material>() + off[k].second;
-        im[k].nmat = m->materials.size();
+        vx::InstMesh& im = s->imeshes[k];
+        im.verts = m->dv;
+        im.idx = m->di;
+        im.mids = off[k].first >= 0 ? s->mids.as<int32_t>() + off[k].first : nullptr;
+        im.mat = m->materials.empty() ? nullptr : s->mmat.as<vx_material>() + off[k].second;
+        im.nmat = m->materials.size();
     }
-    if (!im.empty()) {
-        VX_HIP(s->imesh.ensure(im.size() * sizeof(vx::InstMesh)));
-        VX_HIP(hipMemcpyAsync(s->imesh.p, im.data(), im.size() * sizeof(vx::InstMesh), hipMemcpyHostToDevice, s->stream));
-    }
+    // the table on the device is what the _tlas kernels read; a BVH scene's one record travels in RenderParams (render_enqueue)
+    if (s->tlas) VX_HIP(render_upload(s->imesh, s->imeshes.data(), s->imeshes.size() * sizeof(vx::InstMesh), s->stream));
     VX_HIP(hipStreamSynchronize(s->stream));  // the host vectors may change after this call
     return VX_OK;
 }
@@ -4677,9 +4683,7 @@ void srgb_table(float out[256])
 // at creation and by vx_render_refresh, never per frame.
 vx_status render_upload_attributes(vx_render_scene* s)
 {
-    std::vector<const vx_mesh*> ms;
-    if (s->mesh) ms.push_back(s->mesh);
-    for (const vx_mesh* m : s->meshes) ms.push_back(m);
+    const std::vector<vx_mesh*>& ms = s->meshes;
     std::vector<float> nrm, uv;
     std::vector<int32_t> slot;
     std::vector<vx::TexRec> tex;
@@ -4711,20 +4715,14 @@ vx_status render_upload_attributes(vx_render_scene* s)
             tex.push_back(r);
         }
     }
-    auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-        if (!bytes) return hipSuccess;
-        hipError_t e = b.ensure(bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s->stream);
-        return e;
-    };
     float lut[256];
     srgb_table(lut);
-    VX_HIP(up(s->srgb, lut, sizeof(lut)));
-    VX_HIP(up(s->anrm, nrm.data(), nrm.size() * 4));
-    VX_HIP(up(s->auv, uv.data(), uv.size() * 4));
-    VX_HIP(up(s->aslot, slot.data(), slot.size() * 4));
-    VX_HIP(up(s->atex, tex.data(), tex.size() * sizeof(vx::TexRec)));
-    VX_HIP(up(s->texels, texels.data(), texels.size() * 4));
+    VX_HIP(render_upload(s->srgb, lut, sizeof(lut), s->stream));
+    VX_HIP(render_upload(s->anrm, nrm.data(), nrm.size() * 4, s->stream));
+    VX_HIP(render_upload(s->auv, uv.data(), uv.size() * 4, s->stream));
+    VX_HIP(render_upload(s->aslot, slot.data(), slot.size() * 4, s->stream));
+    VX_HIP(render_upload(s->atex, tex.data(), tex.size() * sizeof(vx::TexRec), s->stream));
+    VX_HIP(render_upload(s->texels, texels.data(), texels.size() * 4, s->stream));
     std::vector<vx::AttrMesh> am(ms.size());
     for (size_t k = 0; k < ms.size(); ++k) {
         const vx_mesh* m = ms[k];
@@ -4736,7 +4734,7 @@ vx_status render_upload_attributes(vx_render_scene* s)
         am[k].tex = am[k].ntex ? s->atex.as<vx::TexRec>() + off[k].tex : nullptr;
         am[k].pad = 0;
     }
-    VX_HIP(up(s->amesh, am.data(), am.size() * sizeof(vx::AttrMesh)));
+    VX_HIP(render_upload(s->amesh, am.data(), am.size() * sizeof(vx::AttrMesh), s->stream));
     VX_HIP(hipStreamSynchronize(s->stream));  // the host vectors go out of scope
     return VX_OK;
 }
@@ -4807,14 +4805,13 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     vx_octree* o = s->octree;
     auto voxels = [&](const vx::TraceIO& q) {
         if (g) vx::launch_trace(g->g, mips, g->wprefix.as<uint32_t>(), q, s->counters.as<unsigned long long>(), &s->phase, s->idxtmp.p, st, p16, nullptr);
-        else vx::launch_octree_trace(o->nodebuf.as<vx_octree_node>(), o->items.as<uint64_t>(), o->nnodes == 0 ? 0 : o->nitems, o->bits, o->root_min, o->vs, q, st);
+        else octree_launch(o, q, st);
     };
     vx_bvh* b = s->bvh;
     vx_tlas* tl = s->tlas;
     auto triangles = [&](const vx::TraceIO& q, float* bary, uint32_t* inst) {
         if (tl) vx::launch_tlas_trace(tlas_dev(tl), q, bary, inst, st);
-        else vx::launch_bvh_trace(b->ntri ? b->nodes.as<float>() : nullptr, b->tris.as<float>(), b->ill.as<uint32_t>(), b->nill, (uint32_t)b->ntri, b->height,
-                                  b->extent, b->coord_max, q, bary, st);
+        else bvh_launch(b, q, bary, st);
     };
     const bool vox = has_source(s, 0);
     if (vox) voxels(io);
@@ -4831,28 +4828,26 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
     P.vt = vox ? s->vt.as<float>() : nullptr;
     P.vprim = vox ? s->vprim.as<uint32_t>() : nullptr;
     P.vnrm = vox ? s->vnrm.as<float>() : nullptr;
-    if (tl) {
+    if (b || tl) {
         P.mt = s->mt.as<float>();
         P.mprim = s->mprim.as<uint32_t>();
         P.mnrm = s->mnrm.as<float>();
         P.mbary = s->mbary.as<float>();
         P.sm = s->sm.as<uint8_t>();
+    }
+    if (tl) {
         P.minst = s->minst.as<uint32_t>();
         P.ixf = tl->xf.as<float>();
         P.iblas = tl->iblas.as<uint32_t>();
         P.imesh = s->imesh.as<vx::InstMesh>();
     }
-    if (b) {
-        P.mt = s->mt.as<float>();
-        P.mprim = s->mprim.as<uint32_t>();
-        P.mnrm = s->mnrm.as<float>();
-        P.mbary = s->mbary.as<float>();
-        P.verts = s->mesh->dv;
-        P.idx = s->mesh->di;
-        P.sm = s->sm.as<uint8_t>();
-        if (s->has_mids) P.mids = s->mids.as<int32_t>();
-        P.mmat = s->mmat.as<vx_material>();
-        P.nmmat = s->nmmat;
+    if (b) {  // its one mesh's record, by value
+        const vx::InstMesh& im = s->imeshes[0];
+        P.verts = im.verts;
+        P.idx = im.idx;
+        P.mids = im.mids;
+        P.mmat = im.mat;
+        P.nmmat = im.nmat;
     }
     for (int k = 0; k < 3; ++k) P.light[k] = light.position[k];
     P.intensity = light.intensity;
@@ -4880,9 +4875,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
         A.w2o = tl ? tl->w2o.as<float>() : nullptr;
         A.nbuf = s->nbuf.as<float>();
     }
-    if (attr) vx::launch_render_shadow_rays_attr(P, A, tl != nullptr, st);
-    else if (tl) vx::launch_render_shadow_rays_tlas(P, st);
-    else vx::launch_render_shadow_rays(P, st);
+    vx::launch_render_shadow_rays(P, attr ? &A : nullptr, tl != nullptr, st);
     // shadow rays: any-hit against the voxels and the mesh (rchit:108-122), tMax = the light distance -- or 0, the empty interval
     // (0 < tmin) that the traversals leave at once, for pixels whose shading cannot read the flag: misses, hits facing away from the
     // light (5-12 % of the frame)
@@ -4899,9 +4892,7 @@ vx_status render_enqueue(vx_render_scene* s, const vx_render_args* a, const vx_r
         sio.shadowed_out = s->sm.as<uint8_t>();
         triangles(sio, nullptr, nullptr);
     }
-    if (attr) vx::launch_render_shade_attr(P, A, tl != nullptr, st);
-    else if (tl) vx::launch_render_shade_tlas(P, st);
-    else vx::launch_render_shade(P, st);
+    vx::launch_render_shade(P, attr ? &A : nullptr, tl != nullptr, st);
     VX_HIP(hipGetLastError());
     // end: later work on the sources' streams (a rebuild) waits for the frame's reads
     VX_HIP(hipEventRecord(s->ev_end, st));
@@ -4931,7 +4922,7 @@ vx_status vx_render_create(const vx_render_desc* desc, vx_render_scene** out)
     s->grid = const_cast<vx_grid*>(desc->grid);
     s->octree = const_cast<vx_octree*>(desc->octree);
     s->bvh = const_cast<vx_bvh*>(desc->bvh);
-    s->mesh = const_cast<vx_mesh*>(desc->mesh);
+    if (desc->mesh) s->meshes.push_back(const_cast<vx_mesh*>(desc->mesh));
     s->stream = (hipStream_t)desc->stream;
     return render_create_common(std::move(s), out);
 }
@@ -4958,7 +4949,6 @@ vx_status render_create_common(Fresh<vx_render_scene> s, vx_render_scene** out)
     s->device = s->grid ? s->grid->device : (s->octree ? s->octree->device : s->tlas->device);
     VX_TRY(render_sources_check(s.get()));
     DeviceGuard dg(s->device);
-    if (s->mesh) VX_TRY(mesh_to_device(s->mesh));
     for (vx_mesh* m : s->meshes) VX_TRY(mesh_to_device(m));
     VX_HIP(s->camera.ensure(sizeof(vx::Camera)));
     VX_HIP(s->counters.ensure(4 * sizeof(unsigned long long)));
@@ -4989,7 +4979,9 @@ vx_status vx_render_set_shading(vx_render_scene* s, uint32_t flags)
     return VX_OK;
 }
 
-vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a)
+// The two frame entry points: the argument and light checks, the device count, the null scene, the sources' state, the guard, then one
+// frame into the caller's device arrays or (host) into the blocks the scene keeps, through a Staging.
+static vx_status render_frame_entry(vx_render_scene* s, const vx_render_args* a, bool host)
 {
     vx_render_light light;
     VX_TRY(render_args_check(a, &light));
@@ -4998,29 +4990,19 @@ vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a)
     if (!s) return fail(VX_ERR_INVALID_ARG, "null argument");
     VX_TRY(render_sources_check(s));
     DeviceGuard dg(s->device);
-    return render_enqueue(s, a, light, a->rgba, a->kind, a->shadowed);
+    if (!host) return render_enqueue(s, a, light, a->rgba, a->kind, a->shadowed);
+    const size_t n = (size_t)a->width * a->height;
+    Staging st(*s);
+    uint32_t* rgba = st.out(a->rgba, n * 4, 0, &s->rgba);
+    uint8_t* kind = st.out(a->kind, n, 0, &s->kind);
+    uint8_t* shadowed = st.out(a->shadowed, n, 0, &s->shad);
+    VX_TRY(st.status());
+    VX_TRY(render_enqueue(s, a, light, rgba, kind, shadowed));
+    return st.finish();
 }
 
-vx_status vx_render_frame(vx_render_scene* s, const vx_render_args* a)
-{
-    vx_render_light light;
-    VX_TRY(render_args_check(a, &light));
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return fail(VX_ERR_NO_DEVICE, "no HIP device available: libvoxhip has no CPU path");
-    if (!s) return fail(VX_ERR_INVALID_ARG, "null argument");
-    VX_TRY(render_sources_check(s));
-    DeviceGuard dg(s->device);
-    const uint64_t n = (uint64_t)a->width * a->height;
-    VX_HIP(s->rgba.ensure(n * 4));
-    if (a->kind) VX_HIP(s->kind.ensure(n));
-    if (a->shadowed) VX_HIP(s->shad.ensure(n));
-    VX_TRY(render_enqueue(s, a, light, s->rgba.as<uint32_t>(), a->kind ? s->kind.as<uint8_t>() : nullptr, a->shadowed ? s->shad.as<uint8_t>() : nullptr));
-    VX_HIP(hipMemcpyAsync(a->rgba, s->rgba.p, n * 4, hipMemcpyDeviceToHost, s->stream));
-    if (a->kind) VX_HIP(hipMemcpyAsync(a->kind, s->kind.p, n, hipMemcpyDeviceToHost, s->stream));
-    if (a->shadowed) VX_HIP(hipMemcpyAsync(a->shadowed, s->shad.p, n, hipMemcpyDeviceToHost, s->stream));
-    VX_HIP(hipStreamSynchronize(s->stream));
-    return VX_OK;
-}
+vx_status vx_render_frame_device(vx_render_scene* s, const vx_render_args* a) { return render_frame_entry(s, a, false); }
+vx_status vx_render_frame(vx_render_scene* s, const vx_render_args* a) { return render_frame_entry(s, a, true); }
 
 void vx_render_free(vx_render_scene* s) { handle_free(s); }
 

@@ -401,7 +401,7 @@ struct RenderParams {
     const int32_t* mids = nullptr;  // per-triangle material ids (-1 none); null: MaterialObj{}
     const vx_material* mmat = nullptr;
     uint64_t nmmat = 0;
-    // instanced scenes (the _tlas launches): the hit's instance per pixel, the instances' object-to-world rows (12 f32 each), their BLAS,
+    // instanced scenes (inst: the _tlas kernels): the hit's instance per pixel, the instances' object-to-world rows (12 f32 each), their BLAS,
     // and the mesh of each BLAS; vt may be null (no voxel source: every voxel query misses)
     const uint32_t* minst = nullptr;
     const float* ixf = nullptr;
@@ -412,12 +412,6 @@ struct RenderParams {
     uint8_t* shadowed_out = nullptr;
 };
 void launch_render_camera(const Camera& cam, Camera* dev, hipStream_t s);  // one thread: the camera block, from a kernel argument
-void launch_render_shadow_rays(const RenderParams& P, hipStream_t s);
-void launch_render_shade(const RenderParams& P, hipStream_t s);
-// the same stages for an instanced scene (P.minst / ixf / iblas / imesh set): the triangle hit point M * ((p0*b0 + p1*b1) + p2*b2) and the
-// instance's mesh materials
-void launch_render_shadow_rays_tlas(const RenderParams& P, hipStream_t s);
-void launch_render_shade_tlas(const RenderParams& P, hipStream_t s);
 // Attribute shading (vx_render_set_shading(VX_RENDER_ATTRIBUTES)): what a triangle hit reads besides RenderParams, per mesh (one record for a
 // BVH scene, one per BLAS of an instanced scene): corner normals (9 f32 per triangle, null: the face normal), corner uvs (6 f32 per triangle,
 // null: (0, 0)), the texture slot of every material (nslot of them) and the mesh's textures (ntex records into the scene's texel pool).
@@ -441,9 +435,10 @@ struct AttrParams {
     const float* w2o = nullptr;      // instanced scenes: the TLAS's world-to-object rows (12 f32 per instance)
     float* nbuf = nullptr;           // 3 f32 per pixel: the normal of a triangle hit, written by the shadow-ray stage, read by the shading
 };
-// the same stages with attribute shading; the default launches above keep their kernels (and ISA) unchanged
-void launch_render_shadow_rays_attr(const RenderParams& P, const AttrParams& A, bool inst, hipStream_t s);
-void launch_render_shade_attr(const RenderParams& P, const AttrParams& A, bool inst, hipStream_t s);
+// The two per-pixel stages, each one of four kernels.  A: attribute shading's tables, null for the default shading; inst: an instanced scene,
+// whose triangle hit point is M * ((p0*b0 + p1*b1) + p2*b2) and whose materials are the instance's mesh's.
+void launch_render_shadow_rays(const RenderParams& P, const AttrParams* A, bool inst, hipStream_t s);
+void launch_render_shade(const RenderParams& P, const AttrParams* A, bool inst, hipStream_t s);
 
 // single-voxel helpers
 void launch_set_bit(uint32_t* words, uint64_t idx, hipStream_t s);

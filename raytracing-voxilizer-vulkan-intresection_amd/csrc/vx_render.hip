@@ -58,6 +58,29 @@ __device__ __forceinline__ void shade_normal(bool tri, const RenderParams& P, ui
     if (tri && dot3(n0, n1, n2, d0, d1, d2) > 0.0f) { n0 = n0 * -1.0f; n1 = n1 * -1.0f; n2 = n2 * -1.0f; }
 }
 
+// A pixel's triangle hit, resolved once per site: the mesh it belongs to (0, or the instance's BLAS), that mesh's vertices and index triples,
+// the instance, and the barycentrics in the pinned form b0 = 1 - b1 - b2.  What a site does not read costs nothing.
+struct TriHit {
+    uint32_t mesh, inst;
+    const float* verts;
+    const int32_t* idx;
+    float b0, b1, b2;
+};
+template <bool kInst>
+__device__ __forceinline__ TriHit tri_hit(const RenderParams& P, uint64_t r)
+{
+    TriHit h{0, 0, P.verts, P.idx, 0.0f, P.mbary[2 * r], P.mbary[2 * r + 1]};
+    if (kInst) {
+        h.inst = P.minst[r];
+        h.mesh = P.iblas[h.inst];
+        const InstMesh& im = P.imesh[h.mesh];
+        h.verts = im.verts;
+        h.idx = im.idx;
+    }
+    h.b0 = 1.0f - h.b1 - h.b2;
+    return h;
+}
+
 // Attribute shading (include/voxhip.h): the unit normal N of a triangle hit -- the corner normals interpolated ((n0*b0 + n1*b1) +
 // n2*b2, or the face normal cross(p1 - p0, p2 - p0) without them), moved to world space by W^T n for an instance ((w0j*n0 + w1j*n1) + w2j*n2),
 // then n / sqrtf(dot(n, n)), NOT turned toward the ray (raytrace.rchit:73-74).  A zero-length or non-finite N: the default normal.
@@ -66,19 +89,9 @@ __device__ __forceinline__ void attr_normal(const RenderParams& P, const AttrPar
                                             float& n2)
 {
     const uint32_t k = P.mprim[r];
-    const float* verts = P.verts;
-    const int32_t* idx = P.idx;
-    const AttrMesh* am = A.mesh;
-    uint32_t inst = 0;
-    if (kInst) {
-        inst = P.minst[r];
-        const uint32_t b = P.iblas[inst];
-        const InstMesh& im = P.imesh[b];
-        verts = im.verts;
-        idx = im.idx;
-        am = A.mesh + b;
-    }
-    const float b1 = P.mbary[2 * r], b2 = P.mbary[2 * r + 1], b0 = 1.0f - b1 - b2;
+    const TriHit h = tri_hit<kInst>(P, r);
+    const AttrMesh* am = A.mesh + h.mesh;
+    const float b0 = h.b0, b1 = h.b1, b2 = h.b2;
     float x, y, z;
     if (am->nrm) {
         const float* c = am->nrm + 9ull * k;
@@ -86,10 +99,10 @@ __device__ __forceinline__ void attr_normal(const RenderParams& P, const AttrPar
         y = (c[1] * b0 + c[4] * b1) + c[7] * b2;
         z = (c[2] * b0 + c[5] * b1) + c[8] * b2;
     } else {
-        const int32_t* ti = idx + 3 * (uint64_t)k;
-        const float* p0 = verts + 3 * (uint64_t)ti[0];
-        const float* p1 = verts + 3 * (uint64_t)ti[1];
-        const float* p2 = verts + 3 * (uint64_t)ti[2];
+        const int32_t* ti = h.idx + 3 * (uint64_t)k;
+        const float* p0 = h.verts + 3 * (uint64_t)ti[0];
+        const float* p1 = h.verts + 3 * (uint64_t)ti[1];
+        const float* p2 = h.verts + 3 * (uint64_t)ti[2];
         const float e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e1z = p1[2] - p0[2];
         const float e2x = p2[0] - p0[0], e2y = p2[1] - p0[1], e2z = p2[2] - p0[2];
         x = e1y * e2z - e1z * e2y;
@@ -97,7 +110,7 @@ __device__ __forceinline__ void attr_normal(const RenderParams& P, const AttrPar
         z = e1x * e2y - e1y * e2x;
     }
     if (kInst) {
-        const float* w = A.w2o + 12ull * inst;
+        const float* w = A.w2o + 12ull * h.inst;
         const float ox = x, oy = y, oz = z;
         x = (w[0] * ox + w[4] * oy) + w[8] * oz;
         y = (w[1] * ox + w[5] * oy) + w[9] * oz;
@@ -129,25 +142,17 @@ __device__ __forceinline__ void render_shadow_rays(const RenderParams& P, const 
         l0 = P.light[0]; l1 = P.light[1]; l2 = P.light[2];
     } else if (tri) {          // rchit:67-68,78-83: from the position the barycentrics interpolate
         const uint32_t k = P.mprim[r];
-        const float* verts = P.verts;
-        const int32_t* idx = P.idx;
-        const float* m = nullptr;
-        if (kInst) {                // the instance's mesh, and its object-to-world rows (rchit:70, gl_ObjectToWorldEXT)
-            const uint32_t inst = P.minst[r];
-            const InstMesh& im = P.imesh[P.iblas[inst]];
-            verts = im.verts;
-            idx = im.idx;
-            m = P.ixf + 12ull * inst;
-        }
-        const int32_t* ti = idx + 3 * (uint64_t)k;
-        const float b1 = P.mbary[2 * r], b2 = P.mbary[2 * r + 1], b0 = 1.0f - b1 - b2;
-        const float* p0 = verts + 3 * (uint64_t)ti[0];
-        const float* p1 = verts + 3 * (uint64_t)ti[1];
-        const float* p2 = verts + 3 * (uint64_t)ti[2];
+        const TriHit h = tri_hit<kInst>(P, r);  // an instance's mesh; its object-to-world rows below (rchit:70, gl_ObjectToWorldEXT)
+        const int32_t* ti = h.idx + 3 * (uint64_t)k;
+        const float b0 = h.b0, b1 = h.b1, b2 = h.b2;
+        const float* p0 = h.verts + 3 * (uint64_t)ti[0];
+        const float* p1 = h.verts + 3 * (uint64_t)ti[1];
+        const float* p2 = h.verts + 3 * (uint64_t)ti[2];
         float h0 = p0[0] * b0 + p1[0] * b1 + p2[0] * b2;
         float h1 = p0[1] * b0 + p1[1] * b1 + p2[1] * b2;
         float h2 = p0[2] * b0 + p1[2] * b1 + p2[2] * b2;
         if (kInst) {  // M * p in the pinned association ((m0*x + m1*y) + m2*z) + m3
+            const float* m = P.ixf + 12ull * h.inst;
             const float x = h0, y = h1, z = h2;
             h0 = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
             h1 = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
@@ -233,12 +238,15 @@ __device__ __forceinline__ void tex_axis(float u, uint32_t w, uint32_t& i0, uint
 template <bool kInst>
 __device__ __forceinline__ void attr_texture(const RenderParams& P, const AttrParams& A, const float* lut, uint64_t r, int64_t mi, float diff[3])
 {
+    // (the mesh lookup as it was before tri_hit, and tri_hit only behind the early returns: A.mesh + h.mesh from one call up here changes
+    // k_render_shade_attr's instructions)
     const AttrMesh* am = kInst ? A.mesh + P.iblas[P.minst[r]] : A.mesh;
     if (mi < 0 || (uint64_t)mi >= am->nslot) return;
     const int32_t slot = am->slot[mi];
     if (slot < 0 || (uint32_t)slot >= am->ntex) return;
     const uint32_t k = P.mprim[r];
-    const float b1 = P.mbary[2 * r], b2 = P.mbary[2 * r + 1], b0 = 1.0f - b1 - b2;
+    const TriHit h = tri_hit<kInst>(P, r);
+    const float b0 = h.b0, b1 = h.b1, b2 = h.b2;
     float u = 0.0f, v = 0.0f;
     if (am->uv) {
         const float* c = am->uv + 6ull * k;
@@ -288,7 +296,7 @@ __device__ __forceinline__ void render_shade(const RenderParams& P, const AttrPa
         uint64_t nmat = 0;
         const vx_material* tab = nullptr;
         if (tri && kInst) {  // rchit:52,92-93: objDesc[gl_InstanceCustomIndexEXT] -> the instance's mesh's material of the triangle
-            const InstMesh& im = P.imesh[P.iblas[P.minst[r]]];
+            const InstMesh& im = P.imesh[tri_hit<kInst>(P, r).mesh];
             if (im.mids) mi = im.mids[P.mprim[r]];
             tab = im.mat; nmat = im.nmat;
         } else if (tri) {  // rchit:92-93: the triangle's OBJ material
@@ -358,44 +366,29 @@ void launch_render_camera(const Camera& cam, Camera* dev, hipStream_t s)
     VX_KL(k_render_camera, dim3(1), dim3(64), 0, s, cam, dev);
 }
 
-void launch_render_shadow_rays(const RenderParams& P, hipStream_t s)
+namespace {
+dim3 render_grid(uint64_t n) { return dim3((unsigned)((n + kRenderBlock - 1) / kRenderBlock)); }
+}  // namespace
+
+// A: attribute shading's tables, or null for the default shading; inst: an instanced scene (P.minst / ixf / iblas / imesh set)
+void launch_render_shadow_rays(const RenderParams& P, const AttrParams* A, bool inst, hipStream_t s)
 {
     if (!P.n) return;
-    VX_KL(k_render_shadow_rays, dim3((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, P);
+    const dim3 g = render_grid(P.n), b(kRenderBlock);
+    if (A && inst) VX_KL(k_render_shadow_rays_attr_tlas, g, b, 0, s, P, *A);
+    else if (A) VX_KL(k_render_shadow_rays_attr, g, b, 0, s, P, *A);
+    else if (inst) VX_KL(k_render_shadow_rays_tlas, g, b, 0, s, P);
+    else VX_KL(k_render_shadow_rays, g, b, 0, s, P);
 }
 
-void launch_render_shade(const RenderParams& P, hipStream_t s)
+void launch_render_shade(const RenderParams& P, const AttrParams* A, bool inst, hipStream_t s)
 {
     if (!P.n) return;
-    VX_KL(k_render_shade, dim3((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, P);
-}
-
-void launch_render_shadow_rays_tlas(const RenderParams& P, hipStream_t s)
-{
-    if (!P.n) return;
-    VX_KL(k_render_shadow_rays_tlas, dim3((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, P);
-}
-
-void launch_render_shade_tlas(const RenderParams& P, hipStream_t s)
-{
-    if (!P.n) return;
-    VX_KL(k_render_shade_tlas, dim3((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, P);
-}
-
-void launch_render_shadow_rays_attr(const RenderParams& P, const AttrParams& A, bool inst, hipStream_t s)
-{
-    if (!P.n) return;
-    const dim3 g((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock));
-    if (inst) VX_KL(k_render_shadow_rays_attr_tlas, g, dim3(kRenderBlock), 0, s, P, A);
-    else VX_KL(k_render_shadow_rays_attr, g, dim3(kRenderBlock), 0, s, P, A);
-}
-
-void launch_render_shade_attr(const RenderParams& P, const AttrParams& A, bool inst, hipStream_t s)
-{
-    if (!P.n) return;
-    const dim3 g((unsigned)((P.n + kRenderBlock - 1) / kRenderBlock));
-    if (inst) VX_KL(k_render_shade_attr_tlas, g, dim3(kRenderBlock), 0, s, P, A);
-    else VX_KL(k_render_shade_attr, g, dim3(kRenderBlock), 0, s, P, A);
+    const dim3 g = render_grid(P.n), b(kRenderBlock);
+    if (A && inst) VX_KL(k_render_shade_attr_tlas, g, b, 0, s, P, *A);
+    else if (A) VX_KL(k_render_shade_attr, g, b, 0, s, P, *A);
+    else if (inst) VX_KL(k_render_shade_tlas, g, b, 0, s, P);
+    else VX_KL(k_render_shade, g, b, 0, s, P);
 }
 
 }  // namespace vx

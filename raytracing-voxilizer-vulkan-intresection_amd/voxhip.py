@@ -1747,11 +1747,15 @@ class Renderer(_Handle):
             d.grid = voxels.h
         d.bvh = bvh.h if bvh is not None else None
         d.mesh = mesh.h if mesh is not None else None
-        d.stream = _stream_handle(stream)
+        self._create(lib().vx_render_create, d, (voxels, bvh, mesh), stream, attributes)
+
+    def _create(self, create, desc, keep, stream, attributes):
+        """what both constructors end with: the scene of `desc` on `stream`, the objects it borrows kept alive, the shading flag applied"""
+        desc.stream = _stream_handle(stream)
         self._torch_stream = stream if hasattr(stream, "cuda_stream") else None
-        self._keep = (voxels, bvh, mesh)
+        self._keep = keep
         h = C.c_void_p()
-        _check(lib().vx_render_create(C.byref(d), C.byref(h)))
+        _check(create(C.byref(desc), C.byref(h)))
         self.h = h
         if attributes:
             self.set_shading(RENDER_ATTRIBUTES)
@@ -1770,15 +1774,7 @@ class Renderer(_Handle):
         meshes = list(meshes)
         arr = (C.c_void_p * max(len(meshes), 1))(*[m.h if m is not None else None for m in meshes])
         d.meshes = C.cast(arr, C.c_void_p) if meshes else None
-        d.stream = _stream_handle(stream)
-        self._torch_stream = stream if hasattr(stream, "cuda_stream") else None
-        self._keep = (voxels, tlas, meshes)
-        self.h = None
-        h = C.c_void_p()
-        _check(lib().vx_render_create_tlas(C.byref(d), C.byref(h)))
-        self.h = h
-        if attributes:
-            self.set_shading(RENDER_ATTRIBUTES)
+        self._create(lib().vx_render_create_tlas, d, (voxels, tlas, meshes), stream, attributes)
         return self
 
     def set_shading(self, flags):

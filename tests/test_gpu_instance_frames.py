@@ -10,6 +10,7 @@ import render_ref
 import vx_scenes
 from test_gpu_instances import random_transforms
 from test_gpu_render import assert_lsb, write_two_material_cube
+from test_gpu_render import reference as bvh_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -101,6 +102,43 @@ def test_identity_instance_frame_equals_bvh_frame(gpu, vx, source):
         for k in ("rgba", "kind", "shadowed"):
             assert np.array_equal(a[k], b[k]), (source, c, k)
         assert (a["kind"] == 2).sum() + (a["kind"] == 1).sum() > 1000
+
+
+def test_material_table_with_and_without_ids(gpu, vx):
+    """Both scene forms gather a mesh's materials the same way: with a table but no per-triangle ids every triangle hit shades with
+    MaterialObj{}, with ids by its triangle's record.  A two-triangle quad over a slab of voxels, 16 x 12: the BVH scene's frame is the
+    identity-instance scene's bit for bit, and both are render_ref's picture (kind and shadowed exact, rgba within powf's 1 LSB)."""
+    sv, st = vx_scenes.cube()
+    vox = vx.Grid.voxelize(vx.Mesh.from_arrays(sv * F([0.4, 0.1, 0.4]), st), F(0.125))
+    assert max(vox.describe()["dim"]) <= 8
+    qv = F([[-0.2, 0.45, -0.2], [0.2, 0.45, -0.2], [0.2, 0.45, 0.2], [-0.2, 0.45, 0.2]])
+    qt = np.int32([[0, 1, 2], [0, 2, 3]])
+    mesh = vx.Mesh.from_arrays(qv, qt)
+    bvh = mesh.bvh()
+    tl = vx.Tlas([bvh], vx.instances([instance_ref.transform()]))
+    mats = np.zeros(2, vx.MATERIAL)
+    mats["ambient"] = F([[0.2, 0.05, 0.05], [0.02, 0.1, 0.1]])
+    mats["diffuse"] = F([[0.8, 0.2, 0.1], [0.1, 0.6, 0.6]])
+    mats["specular"] = F([[0.5, 0.5, 0.5], [0.0, 0.0, 0.0]])
+    mats["shininess"] = F([32, 1])
+    mats["illum"] = [2, 1]
+    W, H = 16, 12
+    cam = camera(W, H, eye=(0.35, 0.9, -0.55), ctr=(0.0, 0.2, 0.0))
+    hit = bvh.trace_ex(camera=cam, want=("t", "prim"))
+    assert set(hit["prim"][hit["t"] > 0].tolist()) == {0, 1}           # the camera sees both triangles
+    seen = {}
+    for ids in (None, np.int32([1, 0])):
+        what = "table only" if ids is None else "table and ids"
+        mesh.set_materials(mats, ids)
+        ref = bvh_reference(vox, W, H, cam[0], cam[1], bvh, (qv, qt, mats, ids))
+        tri = ref["kind"] == 2
+        assert tri.sum() >= 12 and (ref["kind"] == 1).sum() >= 30, what
+        a = check(vx.Renderer(vox, bvh, mesh), ref, cam, what + ", BVH scene")
+        b = check(vx.Renderer.from_tlas(vox, tl, [mesh]), ref, cam, what + ", identity instance")
+        for k in ("rgba", "kind", "shadowed"):
+            assert np.array_equal(a[k], b[k]), (what, k)
+        seen[what] = a["rgba"].reshape(-1, 4)[tri]
+    assert (np.abs(seen["table only"].astype(int) - seen["table and ids"].astype(int)).max(1) > 1).all()   # no pixel passes as the other case's
 
 
 def instanced_scene(vx, tmp_path, n=16, seed=7):
